@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- benchmarks of the partition_stripe / pack_stripe hot path on MI355X.
 
-  python bench.py [--config C] --gpus N --steps K --warmup W
+  python bench.py [--config C] --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W warmup steps, times EXACTLY K steps and prints the headline line (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step`, `config`).  `--dump-outputs DIR` then writes what the last timed step returned to its
+caller (the split / chunk vector, `DIR/spl.npy`, float64) -- the inputs are seeded, so two builds can be compared output for
+output.  Everything else (roofline, per-kernel breakdown, full-size checks, CPU baselines, other configs, the row-tiled extra
+of N > 1) runs only under `--full`.
 
 N > 1: either under `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...` (RANK / WORLD_SIZE in the
 environment) or plain `python bench.py --gpus N`, which starts the N ranks itself from a parent that never touches a GPU
@@ -30,7 +36,7 @@ what the reference's `@benchmarkable partition_stripe($A,$K,$f)` times, test/run
               `--gpus 8 --mode tiled` is its 8-GPU row-tiled form, `--gpus 1` the same partition on one GPU: ptr is 4 B x K x n = 51 GB).
   5shape      the same with K = 64 (round-2 comparisons).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) including
+Prints ONE JSON line on rank 0; with --full it also carries
   roofline     : the dominant kernel, HIP-event timed inside the timed region, against the 8 TB/s HBM peak
   cpu_baseline : the literal CPU restatement (oracle/, kind "port", 1 core) on a bounded sample
 and, for the default config, `extras.other_configs`: short runs of `constrained`, `bottleneck` and `2`, the time with the
@@ -372,6 +378,32 @@ def dp_cpu_baseline(B, cfg, sizes):
             "sample_seconds": [s[1] for s in samples], "a_per_size": [s[2] for s in samples], "host_cores": os.cpu_count()}
 
 
+def keep_outputs(B, dist, world):
+    """what the last timed step returned to its caller, for --dump-outputs: the split vector (N > 1, independent partitions:
+    every rank's, exchanged with one RCCL all_gather)"""
+    B.outputs = {"spl": B.spl.copy()}
+    if dist is not None:
+        spl_t = torch.from_numpy(B.spl.copy()).to(B.dev)
+        gathered = [torch.empty_like(spl_t) for _ in range(world)]      # the K+1-entry split vectors of all ranks
+        dist.all_gather(gathered, spl_t)
+        if world > 1 and not B.tiled:
+            B.outputs["spl_all_ranks"] = torch.stack(gathered).cpu().numpy()
+
+
+def dp_headline(B, cfg, world, dt, args):
+    n, N, K = B.n, B.N, B.K
+    return {
+        "metric": "partitions/sec, %s, K=%d" % (B.method_name(), K),
+        "value": (1 if B.tiled else world) * args.steps / dt, "unit": "partitions/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "strong" if B.tiled else "weak", "vs_baseline": None,
+        "dtype": "int64", "data": "synthetic",
+        "config": {"workload": "config %s: %s on suitesparse_shaped CSR (seeded SplitMix64 generator, tests/synth.py), n=%d rows, nnz=%d, K=%d; %s"
+                               % (cfg, B.method_name(), n, N, K, "one partition, DP rows tiled over the GPUs" if B.tiled else "one independent partition per GPU"),
+                   "n": n, "nnz": N, "K": K, "includes_oracle_build": True,
+                   "device_block_pool": True},      # (every step rebuilds the oracle structures; the raw device blocks they live in are recycled: csrc/core.hip dev_alloc)
+    }
+
+
 def run_dp(args, cfg, dev, rank, world, dist):
     tiled = args.mode == "tiled" and dist is not None
     B = DpBench(args, cfg, dev, rank, world, tiled)
@@ -379,6 +411,13 @@ def run_dp(args, cfg, dev, rank, world, dist):
     for kv in args.opt:
         name, val = kv.split("=")
         assert hip.set_option(name, int(val)) == 0, kv
+    if not args.full:
+        for _ in range(args.warmup):
+            B.step()
+        dt = time_region(B, args.steps, dist, dev)
+        B.last_step_s = dt / args.steps
+        keep_outputs(B, dist, world)
+        return (dp_headline(B, cfg, world, dt, args) if rank == 0 else None), B
     copy_gbs = measure_copy_gbs(dev)
     # The per-kernel breakdown (HIP events around every launch group: ~40 records per DP round) is taken on an UNTIMED step; the
     # timed region keeps events around the dominant kernel only (2 per round), as the roofline line needs them live.
@@ -398,15 +437,11 @@ def run_dp(args, cfg, dev, rank, world, dist):
     hip.prof_enable(False)
     hip.set_option("prof_only", -1)
     prof = hip.prof_get()
-    spl_t = torch.from_numpy(B.spl.copy()).to(dev)
-    if dist is not None:
-        gathered = [torch.empty_like(spl_t) for _ in range(world)]      # the K+1-entry split vectors of all ranks: one RCCL all_gather
-        dist.all_gather(gathered, spl_t)
+    keep_outputs(B, dist, world)
     info = B.check()
     if rank != 0:
         return None, B
     ms_per_step = dt / args.steps * 1e3
-    value = (1 if tiled else world) * args.steps / dt
     ex = prof[dom]
     bytes_per_launch = ex["units"] / max(ex["launches"], 1)       # accumulated by the library per launch
     avg_ms = ex["ms"] / max(ex["launches"], 1)
@@ -422,15 +457,8 @@ def run_dp(args, cfg, dev, rank, world, dist):
             traffic = {"bytes": pm.get("traffic_bytes_per_launch_corrected"), "bytes_raw": pm.get("traffic_bytes_per_launch_raw"),
                        "stored": True, "source": "profiles/%s_pmc_%s.json" % (rnd, kname), "measured_at": pm.get("measured_at", "round 2 (commit 5d697b7)")}
             break
-    out = {
-        "metric": "partitions/sec, %s, K=%d" % (B.method_name(), K),
-        "value": value, "unit": "partitions/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong" if tiled else "weak", "vs_baseline": None,
-        "dtype": "int64", "data": "synthetic",
-        "config": {"workload": "config %s: %s on suitesparse_shaped CSR (seeded SplitMix64 generator, tests/synth.py), n=%d rows, nnz=%d, K=%d; %s"
-                               % (cfg, B.method_name(), n, N, K, "one partition, DP rows tiled over the GPUs" if tiled else "one independent partition per GPU"),
-                   "n": n, "nnz": N, "K": K, "includes_oracle_build": True,
-                   "device_block_pool": True},      # (every step rebuilds the oracle structures; the raw device blocks they live in are recycled: csrc/core.hip dev_alloc)
+    out = dp_headline(B, cfg, world, dt, args)
+    out.update({
         "roofline": {"bound": "hbm", "kernel": "%s (%s)" % (dom, kname), "achieved": achieved, "peak": HBM_PEAK_GBS,
                      "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
                      "measured_copy_gbs": copy_gbs,      # this box's device-to-device copy rate (read + write bytes), SURVEY 8(d)
@@ -441,7 +469,7 @@ def run_dp(args, cfg, dev, rank, world, dist):
         "kernels_ms_per_step": {k: round(v["ms"], 3) for k, v in prof_all.items() if v["launches"]},      # from the untimed profiling step
         "check": info,
         "extras": {},
-    }
+    })
     if cfg == "3":
         out["extras"]["closed_form_note"] = ("for every cost this path admits, ptr[j',k] = j' and spl = [1, n+1, ..., n+1] (DESIGN.md section 4): "
                                              "`value` times all K layers; the layer kernels are checked with injected previous rows (tests/test_gpu_blocks.py)")
@@ -467,7 +495,7 @@ def run_dp(args, cfg, dev, rank, world, dist):
 
 
 # ------------------------------------------------------------------------------------------------ config 2
-def run_cfg2(args, dev, brief=False):
+def run_cfg2(args, dev, brief=False, outputs=None):
     cp = cpamd.load()
     from chainpartitioners_jl_amd import _lib
     hip = _lib.HipBackend(device=dev.index)
@@ -477,16 +505,37 @@ def run_cfg2(args, dev, brief=False):
     N = int(rowval.numel())
     h = hip.csr_from_device(n, n, N, colptr.data_ptr(), rowval.data_ptr())
     spl = np.zeros(K + 1, dtype=np.int64)
-    res = {}
-    for name, mdl in (("work", cp.AffineWorkModel(0, 10, 1)), ("connectivity", cp.AffineConnectivityModel(0, 10, 1, 100))):
-        mm = mdl.marshal()
+    outputs = {} if outputs is None else outputs
 
+    def bisect_cost(mm):
         def run():
             hip.reset_cache(h)
             rc = hip.partition_bisect_cost(h, K, mm, 0.01, 0, spl)
             assert rc == 0, hip.last_error()
+        return run
+
+    def headline(ms, steps, warmup):
+        return {"metric": "partitions/sec, BisectCostBottleneckSplitter(AffineConnectivityModel{Int64}(0,10,1,100), 0.01), K=%d" % K,
+                "value": 1e3 / ms, "unit": "partitions/s", "n_gpus": 1, "steps": steps, "warmup": warmup,
+                "ms_per_step": ms, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
+                "data": "synthetic",
+                "config": {"workload": "config 2: BisectCostBottleneckSplitter on suitesparse_shaped CSR, n=%d, nnz=%d, K=%d, eps=0.01 (includes link-array + counter build)" % (n, N, K)}}
+    if not args.full:
+        run = bisect_cost(cp.AffineConnectivityModel(0, 10, 1, 100).marshal())
+        for _ in range(args.warmup):
+            run()
+        t = timed(run, args.steps)
+        outputs["spl"] = spl.copy()
+        hip.csr_destroy(h)
+        return headline(t * 1e3, args.steps, args.warmup)
+    res = {}
+    for name, mdl in (("work", cp.AffineWorkModel(0, 10, 1)), ("connectivity", cp.AffineConnectivityModel(0, 10, 1, 100))):
+        mm = mdl.marshal()
+        run = bisect_cost(mm)
         run()
         t = timed(run, max(args.steps, 3))
+        if name == "connectivity":
+            outputs["spl"] = spl.copy()
         rc, obj = hip.objective(h, K, spl, mm, None, 1)
         rc, lo, hi = hip.bound_stripe(h, K, mm)
         assert lo <= obj <= hi                                               # the bounds sandwich of test_Costs.jl
@@ -527,14 +576,11 @@ def run_cfg2(args, dev, brief=False):
     if brief:
         return info
     # CPU baseline: the oracle's BisectCost directly at full size
-    out = {"metric": "partitions/sec, BisectCostBottleneckSplitter(AffineConnectivityModel{Int64}(0,10,1,100), 0.01), K=%d" % K,
-           "value": 1e3 / res["connectivity"]["ms_per_step"], "unit": "partitions/s", "n_gpus": 1, "steps": max(args.steps, 3), "warmup": 1,
-           "ms_per_step": res["connectivity"]["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64",
-           "data": "synthetic",
-           "config": {"workload": "config 2: BisectCostBottleneckSplitter on suitesparse_shaped CSR, n=%d, nnz=%d, K=%d, eps=0.01 (includes link-array + counter build)" % (n, N, K)},
+    out = headline(res["connectivity"]["ms_per_step"], max(args.steps, 3), 1)
+    out.update({
            "roofline": {"bound": "hbm", "kernel": "k_bisect (one wave: latency-bound probe chain; roofline N/A, SURVEY 8d)", "achieved": 8.0 * (n + 1 + N) / (res["connectivity"]["ms_per_step"] * 1e-3) / 1e9,
                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": 8.0 * (n + 1 + N) / (res["connectivity"]["ms_per_step"] * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": None},
-           "check": info}
+           "check": info})
     if not args.no_cpu_baseline:
         orc = oracle_backend()
         A = cp.SparseMatrixCSC(n, n, colptr.cpu().numpy(), rowval.cpu().numpy())
@@ -558,7 +604,7 @@ def run_cfg2(args, dev, brief=False):
 
 
 # ------------------------------------------------------------------------------------------------ config 4
-def run_cfg4(args, dev):
+def run_cfg4(args, dev, outputs=None):
     cp = cpamd.load()
     from chainpartitioners_jl_amd import _lib
     hip = _lib.HipBackend(device=dev.index)
@@ -572,20 +618,41 @@ def run_cfg4(args, dev):
     from chainpartitioners_jl_amd import api
     proxy = types.SimpleNamespace(n=n, m=n)             # (the closure w -> 1 + w is tabulated for the widths a method evaluates)
     mms = {"convex": api._marshal(proxy, f, None, stack_method=True), "dynamic": api._marshal(proxy, f, None)}
-    out_spl = {}
-    times = {}
-    for name in ("convex", "dynamic"):
-        spl = np.zeros(n + 2, dtype=np.int64); Kout = np.zeros(1, dtype=np.int64)
+    outputs = {} if outputs is None else outputs
+
+    def pack(name, spl, Kout):
         _, mm, wm, wi, wf, _, _keep = mms[name]
 
         def run():
             hip.reset_cache(h)
             rc = (hip.pack_convex if name == "convex" else hip.pack_dynamic)(h, mm, None, wm, wi, wf, spl, Kout)
             assert rc == 0, hip.last_error()
+        return run
+
+    def headline(s, steps, warmup):
+        return {"metric": "partitions/sec, pack_stripe(ConvexTotalChunker(ConstrainedCost(ColumnBlockComponentCostModel{Int}(3, w->1+w), VertexCount(), 8)))",
+                "value": 1.0 / s, "unit": "partitions/s", "n_gpus": 1, "steps": steps, "warmup": warmup, "ms_per_step": s * 1e3,
+                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int64", "data": "synthetic",
+                "config": {"workload": "config 4: ConvexTotalChunker + ColumnBlock cost, w_max=8, banded n=%d (half bandwidth 16, fill 0.5), nnz=%d; includes link arrays + window table" % (n, N)}}
+    if not args.full:
+        spl = np.zeros(n + 2, dtype=np.int64); Kout = np.zeros(1, dtype=np.int64)
+        run = pack("convex", spl, Kout)
+        for _ in range(args.warmup):
+            run()
+        t = timed(run, args.steps)
+        outputs["spl"] = spl[:int(Kout[0]) + 1].copy()
+        hip.csr_destroy(h)
+        return headline(t, args.steps, args.warmup)
+    out_spl = {}
+    times = {}
+    for name in ("convex", "dynamic"):
+        spl = np.zeros(n + 2, dtype=np.int64); Kout = np.zeros(1, dtype=np.int64)
+        run = pack(name, spl, Kout)
         run()
         times[name] = timed(run, max(1, args.steps if name == "dynamic" else 1))
         out_spl[name] = spl[:int(Kout[0]) + 1].copy()
         assert int(np.diff(out_spl[name]).max()) <= 8
+    outputs["spl"] = out_spl["convex"]
     value = {}
     mm_obj = api._marshal(proxy, colb, None)[1]
     for name in ("convex", "dynamic"):
@@ -594,15 +661,13 @@ def run_cfg4(args, dev):
         assert rc == 0, hip.last_error()
         value[name] = int(v)
     assert value["dynamic"] <= value["convex"]          # the DP is optimal; the convex chunker is a heuristic on this non-Monge cost
-    out = {"metric": "partitions/sec, pack_stripe(ConvexTotalChunker(ConstrainedCost(ColumnBlockComponentCostModel{Int}(3, w->1+w), VertexCount(), 8)))",
-           "value": 1.0 / times["convex"], "unit": "partitions/s", "n_gpus": 1, "steps": 1, "warmup": 1, "ms_per_step": times["convex"] * 1e3,
-           "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int64", "data": "synthetic",
-           "config": {"workload": "config 4: ConvexTotalChunker + ColumnBlock cost, w_max=8, banded n=%d (half bandwidth 16, fill 0.5), nnz=%d; includes link arrays + window table" % (n, N)},
+    out = headline(times["convex"], 1, 1)
+    out.update({
            "roofline": {"bound": "hbm", "kernel": "k_pack_convex_win (one wave, sequential by the algorithm: latency-bound)",
                         "achieved": (8.0 * (n + 1 + N) + 24.0 * (n + 1)) / times["convex"] / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                         "frac": (8.0 * (n + 1 + N) + 24.0 * (n + 1)) / times["convex"] / 1e9 / HBM_PEAK_GBS, "traffic": None},
            "check": {"K_convex": len(out_spl["convex"]) - 1, "K_dynamic": len(out_spl["dynamic"]) - 1, "total_value": value,
-                     "dynamic_total_chunker_ms": times["dynamic"] * 1e3}}
+                     "dynamic_total_chunker_ms": times["dynamic"] * 1e3}})
     # ---- a batch: requests (cost constants x width limits) on the same pattern in ONE launch (cp_pack_convex_batch), one wave each
     nb = args.batch
     bmeth = []
@@ -673,6 +738,20 @@ def dry_run(args, rank, world, dist):
             "config": {"workload": "dry run"}, "ranks_seen": [int(t[0]) for t in seen], "pids": [int(t[1]) for t in seen]}
 
 
+def dump_outputs(d, arrays, budget=64_000_000):
+    """--dump-outputs: every array as DIR/<name>.npy in float64 (split / chunk indices are exact in it), at most `budget` bytes
+    in all.  An array beyond its share is written as a fixed, seeded sample of its entries, their positions in <name>_index.npy."""
+    os.makedirs(d, exist_ok=True)
+    share = budget // max(len(arrays), 1)
+    for name, a in sorted(arrays.items()):
+        a = np.asarray(a, dtype=np.float64)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(SEED).choice(a.size, share // 16, replace=False))
+            np.save(os.path.join(d, name + "_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="3", choices=["3", "constrained", "bottleneck", "constrained-bottleneck", "2", "4", "5", "5shape"])
@@ -683,8 +762,13 @@ def main():
     ap.add_argument("--n", type=int, default=0)
     ap.add_argument("--nnz", type=int, default=0)
     ap.add_argument("--parts", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="config 3: skip the short runs of the other configs; N > 1: skip extras.tiled")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: roofline, per-kernel breakdown, full-size checks, CPU baselines, the other "
+                         "configs of the default line, extras.tiled of N > 1 (a plain run only warms up, times --steps steps and prints)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (split / chunk vector) as DIR/<name>.npy, float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: config 3: skip the short runs of the other configs; N > 1: skip extras.tiled")
     ap.add_argument("--opt", action="append", default=[], help="library tunable name=value (cp_set_option), e.g. short_t=4")
     ap.add_argument("--mode", choices=["independent", "tiled"], default="independent",
                     help="N>1: 'independent' = one partition per GPU (weak scaling, `value`) followed by ONE row-tiled partition in "
@@ -694,6 +778,8 @@ def main():
     ap.add_argument("--dry-run", action="store_true", help="rehearse launcher + collectives without GPU work (tests)")
     ap.add_argument("--emit-spl", action="store_true", help="put rank 0's split vector into check.spl (parity tests at small n)")
     args = ap.parse_args()
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be at least 1")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -736,14 +822,19 @@ def main():
         torch.cuda.set_device(0)
     dev = torch.device("cuda", local_rank if world > 1 else 0)
 
+    outputs = {}
     if args.config == "2":
-        out = run_cfg2(args, dev) if rank == 0 else None
+        out = run_cfg2(args, dev, outputs=outputs) if rank == 0 else None
     elif args.config == "4":
-        out = run_cfg4(args, dev) if rank == 0 else None
+        out = run_cfg4(args, dev, outputs=outputs) if rank == 0 else None
     else:
         out, B = run_dp(args, args.config, dev, rank, world, dist)
+        outputs = B.outputs
         if out is not None and args.emit_spl:
-            out["check"]["spl"] = [int(x) for x in B.spl]
+            out.setdefault("check", {})["spl"] = [int(x) for x in outputs["spl"]]
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, outputs)
+    if args.config not in ("2", "4") and args.full:
         if world > 1 and args.mode == "independent" and not args.no_extras:
             expect_s = float(B.last_step_s)
             B.hip.csr_destroy(B.h); del B

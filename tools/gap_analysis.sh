@@ -1,15 +1,15 @@
 #!/bin/bash
 # Idle time between dependent kernels of one bench step (run on the GPU box):
-#   bash tools/gap_analysis.sh <tag> [bench.py arguments]   -> gpurun_out/gaps_<tag>/{summary.txt, bench.json}
+#   bash tools/gap_analysis.sh <tag> [bench.py arguments]   -> ${BENCH_OUT:-bench_out}/gaps_<tag>/{summary.txt, bench.json}
 # rocprofv3 --kernel-trace (no counters); the LAST step's dispatches are taken (after the largest pause = the host-side check
 # between steps is excluded by looking at the final `frac` of the trace), busy = sum of durations, idle = gaps between one
 # kernel's end and the next one's start, attributed to the kernel that follows.
 set -e
 tag=$1; shift
-cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-out=gpurun_out/gaps_$tag
+export TMPDIR=/tmp && cd "$(dirname "$0")/.."
+out=${BENCH_OUT:-bench_out}/gaps_$tag
 rm -rf "$out" && mkdir -p "$out"
-rocprofv3 --kernel-trace --output-format csv -d "$out/raw" -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-extras "$@" > "$out/bench.json" 2> "$out/bench.err"
+rocprofv3 --kernel-trace --output-format csv -d "$out/raw" -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-extras "$@" > "$out/bench.json" 2> "$out/bench.err"
 python3 - "$out" <<'PY'
 import csv, glob, sys, collections, re
 out = sys.argv[1]

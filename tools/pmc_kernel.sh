@@ -1,13 +1,13 @@
 #!/bin/bash
 # Hardware counters of the dispatches of one kernel (run on the GPU box), one rocprofv3 --pmc pass (kernel trace only):
 #   bash tools/pmc_kernel.sh <tag> <kernel-name-substring> "<COUNTER ...>" [bench.py arguments]
-# -> gpurun_out/pmc_<tag>/table.txt : one line per dispatch of the LAST layer (in dispatch order), the counters side by side
+# -> ${BENCH_OUT:-bench_out}/pmc_<tag>/table.txt : one line per dispatch of the LAST layer (in dispatch order), the counters side by side
 set -e
 tag=$1; pat=$2; ctrs=$3; shift 3
-cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-out=gpurun_out/pmc_$tag
+export TMPDIR=/tmp && cd "$(dirname "$0")/.."
+out=${BENCH_OUT:-bench_out}/pmc_$tag
 rm -rf "$out" && mkdir -p "$out"
-rocprofv3 --kernel-trace --pmc $ctrs --output-format csv -d "$out/raw" -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-extras --parts 4 "$@" > "$out/bench.log" 2>&1
+rocprofv3 --kernel-trace --pmc $ctrs --output-format csv -d "$out/raw" -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-extras --parts 4 "$@" > "$out/bench.log" 2>&1
 python3 - "$out" "$pat" <<'PY'
 import csv, glob, sys, collections
 out, pat = sys.argv[1], sys.argv[2]

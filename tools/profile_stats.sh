@@ -1,13 +1,13 @@
 #!/bin/bash
 # rocprofv3 kernel-trace statistics of one bench configuration (run on the GPU box):
-#   bash tools/profile_stats.sh <tag> [bench.py arguments]     -> gpurun_out/prof_<tag>/{kernel_stats.csv, domain_stats.csv, bench.json}
+#   bash tools/profile_stats.sh <tag> [bench.py arguments]     -> ${BENCH_OUT:-bench_out}/prof_<tag>/{kernel_stats.csv, domain_stats.csv, bench.json}
 # (the program after `--` is python3 itself: no env / bash -c hop between rocprofv3 and the process that opens the GPU)
 set -e
 tag=$1; shift
-cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-out=gpurun_out/prof_$tag
+export TMPDIR=/tmp && cd "$(dirname "$0")/.."
+out=${BENCH_OUT:-bench_out}/prof_$tag
 rm -rf "$out" && mkdir -p "$out"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$out/raw" -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-extras "$@" > "$out/bench.json" 2> "$out/bench.err"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$out/raw" -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-extras "$@" > "$out/bench.json" 2> "$out/bench.err"
 python3 - "$out" <<'PY'
 import csv, glob, sys
 out = sys.argv[1]
