@@ -106,10 +106,11 @@ static bool model_known(const cp_model_t *m)
 // is the O(n log^2 n) total-cost scheme exact for this model?  Needs W[p]+f(p,r) inverse-Monge:
 // modular terms (alpha, vertices, pins) are free; the net count is submodular, so beta_net >= 0;
 // hyperedge cost = d*b_cut + l*(b_self - b_cut) needs b_cut >= 0 and b_self <= b_cut.
-// Float64 models qualify only when every parameter is integer-valued (then all sums are exact).
+// Both element types qualify only while every reachable total is exact (model_exact_on): a Float64 model needs integer-valued
+// parameters and totals below 2^53, an Int64 model totals below 2^60 -- a wrapped Int64 total is not inverse-Monge.
 static bool fast_total_ok(const cp_model_t *m, int64_t n, int64_t N, int64_t K)
 {
-    if (!model_exact_on(m, n, N, K)) return false;      // (Float64: integer-valued parameters AND every reachable total below 2^53)
+    if (!model_exact_on(m, n, N, K)) return false;
     auto P = [&](int i) { return m->dtype == CP_I64 ? (double)m->p_i64[i] : m->p_f64[i]; };
     if (m->kind == CP_MODEL_WORK) return true;
     if (m->kind == CP_MODEL_CONNECTIVITY) return P(CP_P_NET) >= 0;
@@ -125,14 +126,16 @@ static bool fast_total_ok(const cp_model_t *m, int64_t n, int64_t N, int64_t K)
 // with non-integral betas the rounded value can rise by an ulp while the part shrinks and the valley breaks (35 of 360 layers
 // differed from the literal sweep for (0,0,0,.1,.1), (0,0,0,.7,.1), (.3,.1,0,.3,.3)).  Those go to the general sweep; with
 // integer-valued parameters and totals below 2^53 every product and sum is exact and the real-number argument holds.
+// Int64 costs of every kind need the bound of model_exact_on: a cost that wraps past 2^63 stops growing with its part.
 static bool fast_bottleneck_ok(const cp_model_t *m, int64_t n, int64_t N, int64_t K)
 {
     auto P = [&](int i) { return m->dtype == CP_I64 ? (double)m->p_i64[i] : m->p_f64[i]; };
+    if (m->dtype == CP_I64 && !model_exact_on(m, n, N, K)) return false;
     if (!(P(CP_P_VERTEX) >= 0 && P(CP_P_PIN) >= 0)) return false;
     if (m->kind == CP_MODEL_WORK) return true;
     if (m->kind == CP_MODEL_CONNECTIVITY) return P(CP_P_NET) >= 0;
     if (m->kind == CP_MODEL_HYPEREDGE_CUT)
-        return P(CP_P_CUT_NET) >= 0 && P(CP_P_SELF_NET) >= P(CP_P_CUT_NET) && (m->dtype == CP_I64 || model_exact_on(m, n, N, K));
+        return P(CP_P_CUT_NET) >= 0 && P(CP_P_SELF_NET) >= P(CP_P_CUT_NET) && model_exact_on(m, n, N, K);
     return false;
 }
 

@@ -12,8 +12,10 @@
 //   2. k_cs_scan  : one wave folds the B block products into the state in front of every block (B is a few thousand);
 //   3. k_cs_apply : cst[t] = min_c R[t][c] + S_b[c], one lane per row;
 //   4. k_cs_argmin: spl[t] = the reference's arg min over the <= w candidates of the finished cost row, one lane per row.
-// (min,+) over Int64 is exact, so cst -- and with it every tie -- equals the sequential sweep's; Float64 models use
-// this path only when all parameters are integer-valued (sums exact below 2^53), otherwise the one-wave literal kernel.
+// (min,+) over exact integers reassociates freely, so cst -- and with it every tie -- equals the sequential sweep's while no
+// sum rounds or wraps: the caller takes this path only for models whose every reachable total is exact (model_exact_on:
+// Float64 integer-valued and below 2^53, Int64 below 2^60, clear of the 2^61 saturation of cs_add), otherwise the one-wave
+// literal kernel.
 #include "csr.hpp"
 #include "model.hpp"
 #include "dp.hpp"

@@ -28,7 +28,7 @@
 //
 // Ties: every comparison is strict < in walking order (diagonal, inner p descending, outer planes ascending, p descending
 // inside a plane), i.e. the largest p wins, as in the reference (DynamicSplitter.jl:40 `<=` while scanning upwards).
-// Arithmetic: the eligible models (fast_total_ok) are exact -- Int64 (wrap-around ring) or Float64 with integer values
+// Arithmetic: the eligible models (fast_total_ok) are exact -- Int64 totals below 2^60 (no wrap) or Float64 with integer values
 // below 2^53 -- so the affine costs may be split into a row part and a candidate part.
 //
 // WIDTH-WINDOWED layers (struct Geo, DESIGN.md section 4b; candidates max(0, r - w) <= p <= r with 2^6 <= 2^s <= w): the outer planes

@@ -110,7 +110,8 @@ __device__ __forceinline__ TC comb(int32_t g, TC a, TC b)
 }
 
 // Int64 model, or a Float64 model whose scalar parameters are all integer-valued (then every cost is an exactly
-// represented integer and sums are associative below 2^53)
+// represented integer).  Neither makes sums exact by itself: Float64 rounds above 2^53 and Int64 wraps (cadd / cmulc, as
+// Julia does) -- model_exact_on adds the bound.
 inline bool model_all_integral(const cp_model_t *m)
 {
     if (m->dtype == CP_I64) return true;
@@ -120,13 +121,39 @@ inline bool model_all_integral(const cp_model_t *m)
     return true;
 }
 
-// ... and bounded so: the exact-arithmetic paths (O(n log^2 n) DP, (min,+) chunk scan) reassociate sums and argue about ties, which
-// is only the reference's sequential Float64 arithmetic while every cost and every running total stays below 2^53.  Largest
-// reachable total of a K-part partition of an n-column, N-nonzero pattern: K*|alpha| + n*|b_vertex| + N*|b_pin| + N*max|b_net-like|.
+// ... and bounded so: the exact-arithmetic paths (O(n log^2 n) DP, windowed DP, valley search, (min,+) chunk scan) reassociate
+// sums, rely on inverse-Monge / monotone costs and argue about ties, which is the reference's sequential arithmetic only while
+// every cost and every running total is the true integer.  Largest reachable |total| of a K-part partition of an n-column,
+// N-nonzero pattern: K*|alpha| + n*|b_vertex| + N*|b_pin| + N*max|b_net-like| (column blocks: K*max|alpha_col| + N*max|beta_col|).
+// Float64: below 2^53.  Int64: a wrapped total is none of the three (a wrapped cost is neither inverse-Monge nor monotone), so
+// the bound is computed exactly in 128 bits and kept below 2^60 -- which also keeps every real total under the 2^61 that marks
+// "outside the window" (BigCost, CsInf) and sentinel + cost from wrapping.  Other Int64 kinds: no bound, not exact.
 inline bool model_exact_on(const cp_model_t *m, int64_t n, int64_t N, int64_t K)
 {
     if (!model_all_integral(m)) return false;
-    if (m->dtype == CP_I64) return true;
+    if (m->dtype == CP_I64) {
+        typedef unsigned __int128 u128;
+        auto mag = [](int64_t v) { return v < 0 ? (u128)0 - (u128)(__int128)v : (u128)v; };
+        auto comp_max = [&](const cp_component_t &c) {
+            u128 r = mag(c.c_i64);
+            if (!c.is_const) { r = 0; if (c.table) for (int64_t i = 0; i < c.len; i++) r = std::max(r, mag(((const int64_t *)c.table)[i])); }
+            return r;
+        };
+        u128 amax, bv = 0, bp = 0, bnet;
+        if (m->kind == CP_MODEL_COLBLOCK) {
+            amax = comp_max(m->alpha_col);
+            bnet = comp_max(m->beta_col[0]);
+        } else if (m->kind == CP_MODEL_WORK || m->kind == CP_MODEL_CONNECTIVITY || m->kind == CP_MODEL_HYPEREDGE_CUT) {
+            amax = mag(m->p_i64[CP_P_ALPHA]);
+            if (m->alpha_k) for (int64_t i = 0; i < m->n_alpha_k; i++) amax = std::max(amax, mag(((const int64_t *)m->alpha_k)[i]));
+            bv = mag(m->p_i64[CP_P_VERTEX]); bp = mag(m->p_i64[CP_P_PIN]);
+            bnet = std::max(mag(m->p_i64[3]), mag(m->p_i64[4]));
+        } else {
+            return false;
+        }
+        const u128 bound = amax * (u128)(K > 0 ? K : 1) + bv * (u128)(n > 0 ? n : 0) + (bp + bnet) * (u128)(N > 0 ? N : 0);
+        return bound < ((u128)1 << 60);
+    }
     double amax = std::fabs(m->p_f64[CP_P_ALPHA]);
     if (m->alpha_k) for (int64_t i = 0; i < m->n_alpha_k; i++) amax = std::max(amax, std::fabs(((const double *)m->alpha_k)[i]));
     double bnet = std::max(std::fabs(m->p_f64[3]), std::fabs(m->p_f64[4]));

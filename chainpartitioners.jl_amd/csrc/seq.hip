@@ -958,10 +958,10 @@ int32_t run_pack_dynamic(cp_csr_s *A, const cp_model_t *mdl, const cp_rowpart_t 
     CP_HIP(hipMemsetAsync(spl.p, 0, spl.bytes(), s));
     {
         ProfScope ps(PROF_CHUNK, s, 0.0);
-        // width-windowed costs whose sums are exact: parallel (min,+) scan (chunk_scan.hip); tables of block-component
-        // models hold tabulated component values, which the host marshals as exact integers too
+        // width-windowed costs whose sums are exact: parallel (min,+) scan (chunk_scan.hip).  Int64 sums wrap, so Int64 models
+        // are bounded as Float64 ones are (model_exact_on; column-block models by their tabulated components)
         bool scanned = false;
-        bool exact = std::is_same<TC, int64_t>::value || (model_exact_on(mdl, n, A->N, n + 1) && mdl->kind != CP_MODEL_COLBLOCK);
+        bool exact = model_exact_on(mdl, n, A->N, n + 1) && (std::is_same<TC, int64_t>::value || mdl->kind != CP_MODEL_COLBLOCK);
         if (W.kind == CP_MODEL_VERTEX_COUNT && C->O.Ftab && C->O.Wc == wi && exact && !g_opt_force_brute)
             scanned = pack_dynamic_scan<TC>(s, n, wi, C->O.Ftab, cst.p, spl.p);
         if (!scanned)

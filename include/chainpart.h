@@ -111,7 +111,8 @@ int32_t cp_objective(cp_csr_t csr, int64_t K, const int64_t *spl, const cp_model
 /* ---- partitioners ---- */
 /* partition_stripe(A, K, Dynamic{Total,Bottleneck}{Splitter,Chunker}(f | ConstrainedCost(f,w,w_max)), [Pi])
  * DynamicSplitter.jl:15-50 (order SPLITTER), :52-87 (order CHUNKER), :206-314 (constrained);
- * Reference{Total,Bottleneck}Splitter (ReferenceSplitter.jl:1-13) are the same entry. */
+ * Reference{Total,Bottleneck}Splitter (ReferenceSplitter.jl:1-13) are the same entry.  A model whose totals can round (Float64
+ * above 2^53) or wrap (Int64 at 2^60 and beyond) has no fast path: above the brute_max_n option it is CP_EUNSUPPORTED, never a guess. */
 int32_t cp_partition_dynamic(cp_csr_t csr, int64_t K, int32_t combine, int32_t order,
                              const cp_model_t *model, const cp_rowpart_t *Pi,
                              const cp_model_t *weight, int64_t wmax_i64, double wmax_f64,
