@@ -741,6 +741,7 @@ int32_t cp_set_option(const char *name, int64_t value)
     if (!strcmp(name, "fixed_point")) { g_opt_fixed_point = value; return CP_OK; }
     if (!strcmp(name, "nospec")) { g_opt_nospec = value; return CP_OK; }
     if (!strcmp(name, "own_min")) { g_opt_own_min = value < 64 ? 64 : value; return CP_OK; }
+    if (!strcmp(name, "own_blk")) { g_opt_own_blk = value ? 1 : 0; return CP_OK; }      // (1, default: own tiles at 256-column blocks, run in block order; 0: tiles counted from each task head, in task order)
     if (!strcmp(name, "bn_chunk")) { g_opt_bn_chunk = value < 1 ? 1 : value; return CP_OK; }
     if (!strcmp(name, "bn_wave")) { g_opt_bn_wave = value; return CP_OK; }
     if (!strcmp(name, "bn_slack")) { g_opt_bn_slack = value < 0 ? 0 : value; return CP_OK; }

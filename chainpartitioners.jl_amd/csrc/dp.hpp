@@ -66,6 +66,7 @@ extern int64_t g_opt_setup_bs;                  // lanes per block of k_setup_sh
 extern int64_t g_opt_rpass_cap;                 // lane-private entries per row in k_rpass_small, per cent of the mean (200)
 extern int64_t g_opt_rpass_ch;                 // columns per wave in k_rpass_wave (power of two >= 16)
 extern int64_t g_opt_own_min;                  // tasks with at least this many steps get tiles of their own (>= 64)
+extern int64_t g_opt_own_blk;                  // 1: their tiles sit at 256-column blocks and run in block order; 0: tiles counted from each task head (k_own_map)
 extern int64_t g_opt_short_t, g_opt_short_e;   // k_setup_short: tasks with <= short_t candidates and <= short_e link entries finish in setup
 extern int64_t g_opt_force_brute;      // cp_set_option("force_brute", 1)
 extern int64_t g_opt_brute_max_n;

@@ -471,6 +471,27 @@ __device__ __forceinline__ void wave_segmin(Best<TC, HYP> &x, int &f, int lane)
     }
 }
 
+// ------------------------------------------------------------------ tile geometry of the tasks with tiles of their own (see k_own_map)
+__host__ __device__ __forceinline__ int32_t own_ntiles(int blk, int64_t B, int64_t L)
+{
+    return blk ? (int32_t)(B / LT - (B - L + 1) / LT + 1) : (int32_t)((L + LT - 1) / LT);
+}
+// tile kt of a task with head B and L steps: steps 0 .. tl of the tile are the columns pf .. pf - tl (the tile is the task's head
+// tile iff kt == 0: its step 0 is the candidate B itself, no column stepped over)
+__device__ __forceinline__ void own_tile_geo(int blk, int32_t B, int32_t L, int32_t kt, int32_t &pf, int32_t &tl)
+{
+    if (blk) {
+        const int32_t a = B - L + 1;
+        pf = kt == 0 ? B : (B / LT - kt) * LT + (LT - 1);
+        const int32_t c0 = pf - pf % LT;
+        tl = pf - (a > c0 ? a : c0);
+    } else {
+        pf = B - kt * LT;
+        const int32_t rest = L - kt * LT;                // steps of the task from this tile on
+        tl = (rest < LT ? rest : LT) - 1;
+    }
+}
+
 // ------------------------------------------------------------------ task setup, second form: short tasks finish here
 // One lane per task.  A task with at most `short_t` candidates and at most `short_e` link entries to step over is finished
 // by its lane on the spot (at low tau more than half of all tasks have ONE candidate: B == a, nothing to compare); the
@@ -489,7 +510,7 @@ __global__ void __launch_bounds__(1024) k_setup_short(RoundDesc R, int32_t *__re
                                                       unsigned long long *__restrict__ own_steps, int32_t OWN_MIN, int32_t o_cap,
                                                       int32_t *__restrict__ err, const uint8_t *__restrict__ fin, const int32_t *__restrict__ last_s0,
                                                       int32_t *__restrict__ dbg_ntriv, const int32_t *__restrict__ anch, const int32_t *__restrict__ anch2,
-                                                      int32_t *__restrict__ pz)
+                                                      int32_t *__restrict__ pz, int OWN_BLK)
 {
     // pz (cp_set_option("poison", 1)): the planes were filled with an out-of-range column before the layer; a task whose bounds
     // come out of range has read a cell nobody wrote -- counted, and clamped so that the task stays well-formed
@@ -658,7 +679,7 @@ __global__ void __launch_bounds__(1024) k_setup_short(RoundDesc R, int32_t *__re
         o_tdesc[idx] = make_int4((int32_t)B, (int32_t)S0, (int32_t)r, pos32[r]);
         o_tb[idx] = (uint8_t)b;
         o_rlen[idx] = (int32_t)Lmine;
-        o_ntl[idx] = (int32_t)((Lmine + LT - 1) / LT);
+        o_ntl[idx] = own_ntiles(OWN_BLK, B, Lmine);
         if (HYP) o_tS0l[idx] = (int32_t)S0l;
     }
 }
@@ -875,13 +896,21 @@ __device__ __forceinline__ void interior_stream(const int32_t *__restrict__ arr,
 }
 
 // ------------------------------------------------------------------ long tasks with tiles of their own
-// A task with >= LT steps is cut into tiles counted from ITS OWN head (the last one partial): every tile lies in one task,
-// so all of them -- head and tail included -- take the uniform path: one contiguous run of the link array, suffix counts,
-// tile-local evaluation.  k_own_map: tile -> (task, tile index inside the task); k_lpass_own: one wave per tile;
-// k_fix_own: one wave per task merges its tiles (adding the counts made before each tile).
+// A task with >= OWN_MIN steps gets tiles of its own: every tile lies in one task, so all of them -- head and tail included --
+// take the uniform path: one contiguous run of the link array, suffix counts, tile-local evaluation.  k_own_map: tile ->
+// (task, tile index inside the task); k_lpass_own: one wave per tile; k_fix_own: one wave per task merges its tiles (adding the
+// counts made before each tile).  Tile ids are task-major, the head tile first.  Two geometries (own_ntiles / own_tile_geo):
+//   blk = 1 (default, cp_set_option("own_blk")): one tile per 256-column block floor(p / LT) the task's candidates [a, B] touch
+//           (the head and the tail tile partial: at most one tile more than cdiv(L, LT)).  k_own_map counts the tiles of every
+//           block, a scan and k_blk_order sort the tile ids by block, and k_lpass_own runs them in that order: the four waves
+//           of a workgroup mostly stream the same block's entries for different tasks (the bit planes of the round) at the
+//           same time, and all but the first find them in the caches.
+//   blk = 0: tiles counted from the task's own head, LT steps each (the last one partial), in task order.
+// bcnt (blk = 1): tiles per column block, and each tile's rank inside its block (brank)
 __global__ void __launch_bounds__(256) k_own_map(const RoundCounts *__restrict__ rc, const int64_t *__restrict__ toffs, const int4 *__restrict__ tdesc,
                                                  const int32_t *__restrict__ rlen, int4 *__restrict__ rec, int32_t *__restrict__ tile_task,
-                                                 const uint8_t *__restrict__ tb, int32_t *__restrict__ gap_hi, int tau, int64_t n)
+                                                 const uint8_t *__restrict__ tb, int32_t *__restrict__ gap_hi, int tau, int64_t n, int blk,
+                                                 int32_t *__restrict__ bcnt, int32_t *__restrict__ brank)
 {
     const int64_t ntask = rc->nown, ntile = rc->NT;
     for (int64_t tile = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; tile < ntile; tile += (int64_t)gridDim.x * blockDim.x) {
@@ -892,12 +921,13 @@ __global__ void __launch_bounds__(256) k_own_map(const RoundCounts *__restrict__
     }
     int32_t kt = (int32_t)(tile - toffs[lo]);
     int4 td = tdesc[lo];
-    int32_t rest = rlen[lo] - kt * LT;                // steps of the task from this tile on
-    int32_t tl = (rest < LT ? rest : LT) - 1;
+    int32_t pf, tl;
+    own_tile_geo(blk, td.x, rlen[lo], kt, pf, tl);
     // {column of step 0, row, pos[row], tl | tile of a gap task | head}
     const bool isgap = gap_hi != nullptr;
-    rec[tile] = make_int4(td.x - kt * LT, td.z, td.w, (tl << 2) | (isgap ? 2 : 0) | (kt == 0 ? 1 : 0));
+    rec[tile] = make_int4(pf, td.z, td.w, (tl << 2) | (isgap ? 2 : 0) | (kt == 0 ? 1 : 0));
     tile_task[tile] = (int32_t)lo;
+    if (bcnt) brank[tile] = atomicAdd(&bcnt[pf / LT], 1);
     if (isgap) {                                       // gap pass: rows (r - 2^tau, hi) of the rectangle are finished together
         int64_t r = td.z, b = tb[lo];
         int64_t hi = r + ((int64_t)1 << tau), re = (((r >> b) + 1) << b);
@@ -908,8 +938,19 @@ __global__ void __launch_bounds__(256) k_own_map(const RoundCounts *__restrict__
     }
 }
 
+// the counting sort's scatter: the tiles of column block c are border[bstart[c] .. bstart[c + 1])
+__global__ void __launch_bounds__(256) k_blk_order(const RoundCounts *__restrict__ rc, const int4 *__restrict__ rec, const int32_t *__restrict__ brank,
+                                                   const int64_t *__restrict__ bstart, int32_t *__restrict__ border)
+{
+    const int64_t ntile = rc->NT;
+    for (int64_t tile = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; tile < ntile; tile += (int64_t)gridDim.x * blockDim.x)
+        border[bstart[rec[tile].x / LT] + brank[tile]] = (int32_t)tile;
+}
+
+// border (blk = 1): the tile ids in column-block order; wave k takes tile border[k]
 template <typename TC, bool HYP, bool GAP>
-__global__ void __launch_bounds__(256) k_lpass_own(int isA, const RoundCounts *__restrict__ rc, const int32_t *__restrict__ a_pos, const int32_t *__restrict__ a_next,
+__global__ void __launch_bounds__(256) k_lpass_own(int isA, const RoundCounts *__restrict__ rc, const int32_t *__restrict__ border,
+                                                   const int32_t *__restrict__ a_pos, const int32_t *__restrict__ a_next,
                                                    const int32_t *__restrict__ a_fpos, const int32_t *__restrict__ a_flast,
                                                    int32_t *__restrict__ a_tileS, int32_t *__restrict__ a_tileS2, const int4 *__restrict__ a_rec,
                                                    const TC *__restrict__ W, DevModel<TC> M, TC alpha, Best<TC, HYP> *__restrict__ part,
@@ -922,12 +963,15 @@ __global__ void __launch_bounds__(256) k_lpass_own(int isA, const RoundCounts *_
     // with the task's own row (the rows differ by terms that do not depend on the candidate), and `spec` says whether the tile
     // holds an entry that only some of the rows count.
     // (Tried: tiles visited in column order, one contiguous share of the order per XCD, so that the ~10 passes of the bit planes
-    //  over a column meet in L2: 10 % off this kernel, less than the sort of the tile list costs.)
+    //  over a column meet in L2: 10 % off this kernel, less than the sort of the tile list costs.  The block order of own_blk is a
+    //  counting sort by 256-column block (k_own_map, one scan, k_blk_order): 4 % off, and the sort is paid.  Staging each block's
+    //  entries once per round in LDS for all its tiles (one workgroup per block) was 23 % slower: DESIGN.md section 6b.)
     // (No grid-stride loop here: it costs 14 VGPRs = two waves per SIMD.  The host launches one wave per tile of the buffer's
     //  CAPACITY, which k_round_finish has checked the true count against.)
     int lane = threadIdx.x & 63;
     int64_t tile = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (tile >= rc->NT) return;
+    if (border) tile = border[tile];
     int4 rec = a_rec[tile];
     int head = rec.w & 1;
     int32_t tl = rec.w >> 2;
@@ -1088,6 +1132,7 @@ struct GapCtx {
     const int64_t *tilePS, *tilePS2;
     const int32_t *pos, *next, *fpos, *flast;
     const TC *W;
+    int blk;                    // the tile geometry (own_tile_geo)
 };
 
 // wave-uniform lane index: one v_readlane instead of a ds_bpermute
@@ -1171,8 +1216,8 @@ __device__ __forceinline__ bool gap_walk(const GapCtx<TC, HYP> &C, const DevMode
         if (!SLOW) return false;
         if (SLOW) {
         const int head = k == k0 ? 1 : 0;
-        const int32_t pf = B - (int32_t)(k - k0) * LT;
-        int32_t tlk = L - (int32_t)(k - k0) * LT; tlk = (tlk < LT ? tlk : LT) - 1;
+        int32_t pf, tlk;
+        own_tile_geo(C.blk, B, L, (int32_t)(k - k0), pf, tlk);
         // C.pos[pf + 1 - j] and C.W[pf - j] of the tile's columns are fetched lane-strided; the entries come through 64-entry
         // windows (one coalesced load each) and are handed to all lanes one at a time
 #define CP_SEL5(a_, i_) ((i_) < 64 ? a_[0] : (i_) < 128 ? a_[1] : (i_) < 192 ? a_[2] : (i_) < 256 ? a_[3] : a_[4])
@@ -2368,6 +2413,10 @@ struct LayerWork {
     int fin_stamp = 255;                                // ... iff the cell holds the current layer's stamp (run_layer; 255: cleared before the next layer)
     DBuf<int64_t> o_toffs, o_tilePS, o_tilePS2;
     DBuf<Best<TC, true>> o_part;
+    // own_blk: the tiles sorted by 256-column block (k_own_map -> scan -> k_blk_order)
+    DBuf<int32_t> b_cnt, b_n, o_brank, o_border;        // tiles per block, the block count (device); per tile: rank in its block, tile ids in block order
+    DBuf<int64_t> b_start;
+    int64_t b_nblk = 0;
     int64_t max_tasks = 0;
     bool planes_full = false;                           // the last layer stored every per-block winner (cp_dp_block_tables)
     DBuf<int32_t> pz;                                   // poison mode: cells read that nobody wrote
@@ -2390,7 +2439,7 @@ struct LayerWork {
         if (o_rec.n >= NT && o_rec.n > 0) return;
         size_t c = NT > 0 ? NT : 1;
         o_rec.release();
-        o_task.alloc(c); o_tileS.alloc(c); o_tilePS.alloc(c + 1); o_part.alloc(c); o_hi.alloc(c); o_spec.alloc(c);
+        o_task.alloc(c); o_tileS.alloc(c); o_tilePS.alloc(c + 1); o_part.alloc(c); o_hi.alloc(c); o_spec.alloc(c); o_brank.alloc(c); o_border.alloc(c);
         o_sub.alloc(c * (SMAX + 1)); o_spv.alloc(c * (SMAX + 1));
         if (hyp) { o_tileS2.alloc(c); o_tilePS2.alloc(c + 1); }
         o_rec.alloc(c);
@@ -2626,10 +2675,10 @@ static void win_build(cp_csr_s *A, LayerWork<TC> &Wk)
 // the gap round's finishing kernels: fast variants first, then the SLOW ones over what they listed
 template <typename TC, bool HYP>
 static void launch_gap(hipStream_t s, cp_csr_s *A, LayerWork<TC> &Wk, int tau, int nchunk, int gnr, RoundCounts *rc, int64_t n, const TC *W,
-                       const DevModel<TC> &M, TC alpha, unsigned gg, unsigned gs_grid, unsigned gm, unsigned gslow_grid)
+                       const DevModel<TC> &M, TC alpha, unsigned gg, unsigned gs_grid, unsigned gm, unsigned gslow_grid, int blk)
 {
     GapCtx<TC, HYP> C{reinterpret_cast<const Best<TC, HYP> *>(Wk.o_part.p), reinterpret_cast<const Best<TC, HYP> *>(Wk.o_sub.p), Wk.o_spv.p, Wk.o_spec.p,
-                      Wk.o_tilePS.p, HYP ? Wk.o_tilePS2.p : nullptr, A->pos32.p, A->next.p, HYP ? A->fpos32.p : nullptr, HYP ? A->flast.p : nullptr, W};
+                      Wk.o_tilePS.p, HYP ? Wk.o_tilePS2.p : nullptr, A->pos32.p, A->next.p, HYP ? A->fpos32.p : nullptr, HYP ? A->flast.p : nullptr, W, blk};
     auto *gs = reinterpret_cast<GapSegRec<TC, HYP> *>(Wk.g_seg.p);
     const int32_t *lp = HYP ? A->lpos32.p : nullptr, *lf = HYP ? A->lfirst.p : nullptr;
     int32_t *nl = HYP ? Wk.nlopt.p : nullptr;
@@ -2719,6 +2768,17 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
     const int NR = nbits + 1;
     CP_HIP(hipMemsetAsync(Wk.rc.p, 0, sizeof(RoundCounts) * (size_t)NR, s));
     const bool gaps = own_tiles && g_opt_gap_tau >= 0;
+    // cp_set_option("own_blk", 0 | 1): the tile geometry of the own-tiled tasks (see k_own_map).  Fixed for the whole layer: the
+    // tile counts of setup depend on it.
+    const int oblk = g_opt_own_blk ? 1 : 0;
+    if (oblk) {
+        const int64_t nblk = n / LT + 1;                 // the blocks of the columns 0 .. n
+        if (Wk.b_nblk != nblk || !Wk.b_cnt.p) {
+            Wk.b_cnt.ensure((size_t)nblk); Wk.b_start.ensure((size_t)nblk + 1); Wk.b_n.ensure(1);
+            CP_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(Wk.b_n.p), (int)nblk, 1, s));
+            Wk.b_nblk = nblk;
+        }
+    }
     // cp_set_option("poison", 1) (tests): every layer starts from planes full of an out-of-range column; the kernels that turn
     // plane cells into addresses count and clamp what they read of it.  The invariant behind the speculative layers -- "whatever a
     // layer that is NOT redone has read was written by that layer" -- then reads: hits > 0 implies the layer is flagged for a redo.
@@ -2886,7 +2946,7 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
                 hyp ? A->flast.p : (const int32_t *)nullptr, W, M, alpha, Wk.tdesc.p, Wk.tb.p, Wk.len.p, Wk.tS0l.p, &rc->nlong,               \
                 (int32_t)g_opt_short_t, (int32_t)g_opt_short_e, own_tiles ? Wk.o_tdesc.p : (int4 *)nullptr, Wk.o_tb.p, Wk.o_rlen.p, Wk.o_ntl.p,            \
                 Wk.o_tS0l.p, &rc->nown, &rc->own_steps, (int32_t)(forced ? 2 : gap ? g_opt_gap_min : g_opt_own_min),                                         \
-                (int32_t)std::min<size_t>(Wk.o_ntl.n, (size_t)INT32_MAX), &rc->err, Wk.fin.p, Wk.last_s0.p, (g_opt_dbg & 4096) ? &rc->_pad : (int32_t *)nullptr, Wk.w_anch.p, Wk.w_anch2.p, pzp
+                (int32_t)std::min<size_t>(Wk.o_ntl.n, (size_t)INT32_MAX), &rc->err, Wk.fin.p, Wk.last_s0.p, (g_opt_dbg & 4096) ? &rc->_pad : (int32_t *)nullptr, Wk.w_anch.p, Wk.w_anch2.p, pzp, oblk
             const int sbs = (int)g_opt_setup_bs;          // lanes per block: one list atomic per block, but the block's waves meet at two barriers
             dim3 sgrid((unsigned)cdiv(R.ntask, sbs));
             if (!R.isA) {                                // one grid row per bit plane above tau
@@ -2946,11 +3006,17 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
                 CP_HIP(hipMemsetAsync(Wk.o_rec.p, pat, Wk.o_rec.bytes(), s));
                 if (hyp) CP_HIP(hipMemsetAsync(Wk.o_tileS2.p, pat, Wk.o_tileS2.bytes(), s));
             }
-            hipLaunchKernelGGL(k_own_map, dim3((unsigned)std::min<int64_t>(cdiv(gNT, 256), 8192)), dim3(256), 0, s, rc, Wk.o_toffs.p, Wk.o_tdesc.p, Wk.o_rlen.p, Wk.o_rec.p, Wk.o_task.p,
-                               Wk.o_tb.p, gap ? Wk.o_hi.p : (int32_t *)nullptr, R.tau, n);
+            if (oblk) CP_HIP(hipMemsetAsync(Wk.b_cnt.p, 0, sizeof(int32_t) * (size_t)Wk.b_nblk, s));
+            const unsigned mgrid = (unsigned)std::min<int64_t>(cdiv(gNT, 256), 8192);
+            hipLaunchKernelGGL(k_own_map, dim3(mgrid), dim3(256), 0, s, rc, Wk.o_toffs.p, Wk.o_tdesc.p, Wk.o_rlen.p, Wk.o_rec.p, Wk.o_task.p,
+                               Wk.o_tb.p, gap ? Wk.o_hi.p : (int32_t *)nullptr, R.tau, n, oblk, oblk ? Wk.b_cnt.p : (int32_t *)nullptr, Wk.o_brank.p);
             {
                 ProfScope ps(gap ? PROF_GAPSTREAM : PROF_OWN, s, (double)P.own_steps * step_bytes);      // same bytes per step as dp_lpass
-#define LO_ARGS R.isA, rc, A->pos32.p, A->next.p, hyp ? A->fpos32.p : (const int32_t *)nullptr, hyp ? A->flast.p : (const int32_t *)nullptr,            \
+                if (oblk) {                       // the tile ids by column block (counted in k_own_map): ~10^5 tiles, a counting sort
+                    exclusive_scan_i32_lb(Wk.b_cnt.p, Wk.b_start.p, Wk.b_n.p, Wk.b_nblk, nullptr, Wk.scanws, s);
+                    hipLaunchKernelGGL(k_blk_order, dim3(mgrid), dim3(256), 0, s, rc, Wk.o_rec.p, Wk.o_brank.p, Wk.b_start.p, Wk.o_border.p);
+                }
+#define LO_ARGS R.isA, rc, oblk ? Wk.o_border.p : (const int32_t *)nullptr, A->pos32.p, A->next.p, hyp ? A->fpos32.p : (const int32_t *)nullptr, hyp ? A->flast.p : (const int32_t *)nullptr,            \
                 Wk.o_tileS.p, Wk.o_tileS2.p, Wk.o_rec.p, W, M, alpha
 #define LO_TAIL R.tau, Wk.o_hi.p, Wk.o_spec.p, (int)((g_opt_dbg & 512) != 0)
                 Best<TC, false> *sb0 = reinterpret_cast<Best<TC, false> *>(Wk.o_sub.p);
@@ -2985,8 +3051,8 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
                 unsigned gs_grid = (unsigned)std::min<int64_t>(cdiv((int64_t)(2 * ncap) * nchunk, 4), 8192);
                 unsigned gm = (unsigned)std::min<int64_t>(cdiv((int64_t)ncap * nchunk, 4), 4096);
                 const unsigned gslow_grid = 2048;                               // (grid-stride over the device-side counts n_gslow / n_sslow: usually none)
-                if (hyp) launch_gap<TC, true>(s, A, Wk, R.tau, nchunk, gnr, rc, n, W, M, alpha, gg, gs_grid, gm, gslow_grid);
-                else launch_gap<TC, false>(s, A, Wk, R.tau, nchunk, gnr, rc, n, W, M, alpha, gg, gs_grid, gm, gslow_grid);
+                if (hyp) launch_gap<TC, true>(s, A, Wk, R.tau, nchunk, gnr, rc, n, W, M, alpha, gg, gs_grid, gm, gslow_grid, oblk);
+                else launch_gap<TC, false>(s, A, Wk, R.tau, nchunk, gnr, rc, n, W, M, alpha, gg, gs_grid, gm, gslow_grid, oblk);
             } else {
                 ProfScope ps(PROF_FIX, s, 24.0 * (double)P.NT);
                 // one lane per task: single tiles are final already, short tasks are merged on the spot, the rest is listed
