@@ -19,7 +19,7 @@ LIB_PATH = os.environ.get("CP_LIB_PATH") or os.path.join(_HERE, "libchainpart.so
 SYMBOLS = [
     "cp_last_error", "cp_version", "cp_device_count", "cp_csr_create", "cp_csr_create_device", "cp_csr_destroy",
     "cp_csr_reset_cache", "cp_count_build", "cp_count_query", "cp_count_destroy", "cp_link_array", "cp_partwise", "cp_domsum_build", "cp_rook_build", "cp_wsum_query", "cp_wsum_destroy",
-    "cp_oracle_eval", "cp_oracle_step", "cp_bound_stripe", "cp_objective", "cp_partition_dynamic", "cp_pack_dynamic",
+    "cp_oracle_eval", "cp_oracle_step", "cp_bound_stripe", "cp_objective", "cp_partition_dynamic", "cp_pack_dynamic", "cp_pack_dynamic_tables",
     "cp_partition_bisect_cost", "cp_partition_bisect_cost_batch", "cp_pack_convex", "cp_pack_convex_batch", "cp_partition_convex", "cp_partition_equi", "cp_pack_equi",
     "cp_dynamic_tables", "cp_dynamic_tables_constrained", "cp_dynamic_tables_constrained_combine", "cp_set_stream", "cp_reset_stream", "cp_get_stat", "cp_set_option", "cp_prof_enable", "cp_prof_reset", "cp_prof_get",
     "cp_dp_begin", "cp_dp_layer", "cp_dp_ptr_at", "cp_dp_destroy", "cp_dp_ptr_row", "cp_dp_block_tables", "cp_dp_set_window", "cp_dp_set_rows",
@@ -156,6 +156,17 @@ class HipBackend:
     def pack_dynamic(self, A, mm, rp, wm, wi, wf, spl, Kout):
         return self.lib.cp_pack_dynamic(self._h(A), mm.ptr, C.byref(rp) if rp is not None else None,
                                         wm.ptr if wm is not None else None, _i64(wi), C.c_double(wf), _p(spl), _p(Kout))
+
+    def pack_dynamic_tables(self, A, mm, rp, wm, wi, wf):
+        """(rc, cst[n+1], spl[n+1]) of DynamicTotalChunker: the tables DynamicChunker.jl:20-56 builds before unravel_chunks!
+        (index j' - 1; spl[0] = 0)"""
+        spl = np.zeros(A.n + 1, dtype=np.int64)
+        cst = np.zeros(A.n + 1, dtype=np.int64 if mm.struct.dtype == M.CP_I64 else np.float64)
+        rc = self.lib.cp_pack_dynamic_tables(self._h(A), mm.ptr, C.byref(rp) if rp is not None else None,
+                                             wm.ptr if wm is not None else None, _i64(wi), C.c_double(wf), _p(spl),
+                                             _p(cst) if mm.struct.dtype == M.CP_I64 else None,
+                                             _p(cst) if mm.struct.dtype == M.CP_F64 else None)
+        return rc, cst, spl
 
     def partition_bisect_cost(self, A, K, mm, eps, flip, spl, rp=None):
         return self.lib.cp_partition_bisect_cost_pi(self._h(A), _i64(K), mm.ptr, C.byref(rp) if rp is not None else None,

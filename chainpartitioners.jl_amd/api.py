@@ -245,6 +245,21 @@ def pack_stripe(A: SparseMatrixCSC, method, Pi=None, *, backend=None) -> SplitPa
     raise NotImplementedError(f"pack_stripe: method {type(method).__name__} is outside the hot path")
 
 
+def pack_stripe_tables(A: SparseMatrixCSC, method, Pi=None, *, backend=None):
+    """(cst, spl) of pack_stripe(A, DynamicTotalChunker(f)): the per-column tables DynamicChunker.jl:20-56 builds before
+    unravel_chunks!, indexed by j' - 1 -- cst[j' - 1] is the least total cost of columns 1 : j' - 1, spl[j' - 1] the smallest
+    minimising start of its last chunk (spl[0] = 0)."""
+    if not isinstance(method, M.DynamicTotalChunker):
+        raise NotImplementedError(f"pack_stripe_tables: method {type(method).__name__} is not a DynamicTotalChunker")
+    b = get_backend(backend)
+    if not hasattr(b, "pack_dynamic_tables"):
+        raise NotImplementedError(f"pack_stripe_tables: backend {b.name} has no tables")
+    mdl, mm, wm, wi, wf, rp, keep = _marshal(A, method.f, Pi)
+    rc, cst, spl = b.pack_dynamic_tables(A, mm, rp, wm, wi, wf)
+    _check(rc, "pack_stripe_tables(DynamicTotalChunker)", b)
+    return cst, spl
+
+
 # ---------------------------------------------------------------- oracles / scoring
 class Oracle:
     """Callable cost oracle ocl(j, j', k...) (vectorised over arrays of queries)."""

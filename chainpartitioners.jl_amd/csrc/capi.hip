@@ -2,6 +2,7 @@
 #include "csr.hpp"
 #include "model.hpp"
 #include "dp.hpp"
+#include "weight.hpp"
 #include <cmath>
 #include <memory>
 
@@ -103,20 +104,6 @@ static bool model_known(const cp_model_t *m)
 }
 
 
-// is the O(n log^2 n) total-cost scheme exact for this model?  Needs W[p]+f(p,r) inverse-Monge:
-// modular terms (alpha, vertices, pins) are free; the net count is submodular, so beta_net >= 0;
-// hyperedge cost = d*b_cut + l*(b_self - b_cut) needs b_cut >= 0 and b_self <= b_cut.
-// Both element types qualify only while every reachable total is exact (model_exact_on): a Float64 model needs integer-valued
-// parameters and totals below 2^53, an Int64 model totals below 2^60 -- a wrapped Int64 total is not inverse-Monge.
-static bool fast_total_ok(const cp_model_t *m, int64_t n, int64_t N, int64_t K)
-{
-    if (!model_exact_on(m, n, N, K)) return false;
-    auto P = [&](int i) { return m->dtype == CP_I64 ? (double)m->p_i64[i] : m->p_f64[i]; };
-    if (m->kind == CP_MODEL_WORK) return true;
-    if (m->kind == CP_MODEL_CONNECTIVITY) return P(CP_P_NET) >= 0;
-    if (m->kind == CP_MODEL_HYPEREDGE_CUT) return P(CP_P_CUT_NET) >= 0 && P(CP_P_SELF_NET) <= P(CP_P_CUT_NET);
-    return false;
-}
 
 // is the valley search of dp_bottleneck.hip exact for this model?  Needs a cost that grows with its part: every beta >= 0
 // (hyperedge cut: cost = d*b_cut + l*(b_self - b_cut) with d, l growing, so b_cut >= 0 and b_self >= b_cut).  alpha, alpha[k]
@@ -285,22 +272,6 @@ static void width_windows(int64_t n, int64_t K, int64_t w, std::vector<int64_t> 
 // the layer's candidate limits directly (no masked row: the crossing is searched inside [max(lo[k-1], j' - w), min(j', hi[k-1])],
 // where the previous layer's costs are finite and still grow with the prefix -- dropping the last column of a feasible prefix
 // keeps every width <= w).
-// Any monotone weight w(j, j') = alpha + b_v (j' - j) + b_p (pos[j'] - pos[j]) with b_v, b_p >= 0 (AffineWorkModel: pins per part,
-// work per part): the part [j, j') fits iff j >= j0(j'), the first column whose part up to j' fits -- non-decreasing in j'.  The
-// reference finds it by advancing j0 while w(j0, j', k) > w_max (DynamicSplitter.jl:235-237); with a monotone weight that is this
-// array, found by bisection in the weight's own arithmetic (WorkCosts.jl:17).  j0[r] (0-based row r = j' - 1, 0-based column),
-// r + 1 when not even the empty part fits.
-template <typename TW>
-__global__ void __launch_bounds__(256) k_weight_j0(int64_t n, const int64_t *__restrict__ pos, TW alpha, TW bv, TW bp, TW wmax, int32_t *__restrict__ j0)
-{
-    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r > n) return;
-    const int64_t pr = pos[r];
-    auto fits = [&](int64_t p) { return cadd(cadd(alpha, cmulc(r - p, bv)), cmulc(pr - pos[p], bp)) <= wmax; };
-    int64_t lo = 0, hi = r + 1;                            // first p in [0, r] that fits; r + 1: none
-    while (lo < hi) { const int64_t mid = (lo + hi) >> 1; if (fits(mid)) hi = mid; else lo = mid + 1; }
-    j0[r] = (int32_t)lo;
-}
 
 // column_constraints (DynamicSplitter.jl:144-172) from that array: j'_lo walks back from n + 1 (:150-158, the first step taken
 // unconditionally), j'_hi forward from 1 (:161-169).  1-based j', as the reference's vectors.
@@ -424,33 +395,7 @@ static bool windowed_ok(cp_csr_s *A, int64_t K, int32_t combine, const cp_model_
            fast_total_ok(model, A->n, A->N, K);
 }
 
-// A weight that is a function of the WIDTH only -- VertexCount(), or AffineWorkModel(alpha, c, 0) with c > 0 (the reference's own
-// tests constrain with AffineWorkModel(0, 1, 0), test/test_Partitioners.jl:178-183,256-261) -- bounds the parts by a number of
-// columns: the largest nv with w(nv) = alpha + nv c <= w_max, evaluated in the weight's own arithmetic and order (WorkCosts.jl:17;
-// the pin term is nv * 0 = 0).  -> that width (0: only empty parts fit, -1: not even those), or -2: not a width weight.
-static int64_t width_of_weight(const cp_model_t *w, int64_t n, int64_t wmax_i64, double wmax_f64)
-{
-    if (!w) return -2;
-    if (w->kind == CP_MODEL_VERTEX_COUNT) return wmax_i64;
-    if (w->kind != CP_MODEL_WORK || w->alpha_k) return -2;
-    auto fits_i = [&](int64_t nv) { return cadd(cadd(w->p_i64[CP_P_ALPHA], cmulc(nv, w->p_i64[CP_P_VERTEX])), cmulc((int64_t)0, w->p_i64[CP_P_PIN])) <= wmax_i64; };
-    auto fits_f = [&](int64_t nv) { return cadd(cadd(w->p_f64[CP_P_ALPHA], cmulc(nv, w->p_f64[CP_P_VERTEX])), cmulc((int64_t)0, w->p_f64[CP_P_PIN])) <= wmax_f64; };
-    const bool is_i = w->dtype == CP_I64;
-    if (is_i ? !(w->p_i64[CP_P_PIN] == 0 && w->p_i64[CP_P_VERTEX] > 0) : !(w->p_f64[CP_P_PIN] == 0.0 && w->p_f64[CP_P_VERTEX] > 0.0)) return -2;
-    auto fits = [&](int64_t nv) { return is_i ? fits_i(nv) : fits_f(nv); };
-    if (!fits(0)) return -1;
-    int64_t lo = 0, hi = n + 1;                       // fits(lo); the weight grows with nv: the largest nv <= n + 1 that fits
-    if (fits(hi)) return hi;
-    while (hi - lo > 1) { const int64_t mid = lo + ((hi - lo) >> 1); if (fits(mid)) lo = mid; else hi = mid; }
-    return lo;
-}
 
-// AffineWorkModel(alpha, b_v, b_p) with b_v, b_p >= 0: grows with its part (k_weight_j0)
-static bool monotone_work_weight(const cp_model_t *w)
-{
-    if (!w || w->kind != CP_MODEL_WORK || w->alpha_k) return false;
-    return w->dtype == CP_I64 ? (w->p_i64[CP_P_VERTEX] >= 0 && w->p_i64[CP_P_PIN] >= 0) : (w->p_f64[CP_P_VERTEX] >= 0 && w->p_f64[CP_P_PIN] >= 0);
-}
 
 // ------------------------------------------------------------------ row-tiled DP (one rank = one tile of rows per layer)
 // cp_dp_*: the same layers as run_dynamic, but a rank computes only rows [row_lo, row_hi) of every layer and the caller
@@ -745,6 +690,8 @@ int32_t cp_set_option(const char *name, int64_t value)
     if (!strcmp(name, "bn_chunk")) { g_opt_bn_chunk = value < 1 ? 1 : value; return CP_OK; }
     if (!strcmp(name, "bn_wave")) { g_opt_bn_wave = value; return CP_OK; }
     if (!strcmp(name, "bn_slack")) { g_opt_bn_slack = value < 0 ? 0 : value; return CP_OK; }
+    if (!strcmp(name, "lws")) { g_opt_lws = value ? 1 : 0; return CP_OK; }      // (1, default: DynamicTotalChunker past the scan by chunk_lws.hip; 0: the one-wave kernel)
+    if (!strcmp(name, "lws_leaf")) { int64_t v = 256; while (v < value && v < 2048) v <<= 1; g_opt_lws_leaf = v; return CP_OK; }
     if (!strcmp(name, "bn_run")) { g_opt_bn_run = value < 2 ? 2 : value; return CP_OK; }
     set_error("unknown option");
     return CP_EINVAL;

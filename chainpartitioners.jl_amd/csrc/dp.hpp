@@ -51,6 +51,15 @@ int32_t run_plaid_dynamic(cp_csr_s *A, int64_t K, int32_t combine, int32_t order
 template <typename TC>
 bool pack_dynamic_scan(hipStream_t s, int64_t n, int64_t wmax, const TC *Ftab, TC *cst1, int64_t *spl1);
 
+// chunk_lws.hip: DynamicTotalChunker for any width or monotone work budget as an on-line divide and conquer; lws_ok: the gate
+// (cp_set_option("lws", 0) restores the one-wave kernel); run_pack_lws fills the 1-based tables of k_pack_dynamic (spl1 zeroed)
+extern int64_t g_opt_lws, g_opt_lws_leaf;      // on / rows per leaf wave (256, 512, 1024 or 2048)
+struct WaveletDev;
+bool lws_ok(const cp_csr_s *A, const cp_model_t *mdl, const cp_model_t *w, int64_t wi, double wf);
+template <typename TC>
+int32_t run_pack_lws(cp_csr_s *A, const DevModel<TC> &M, const WaveletDev &wnet, const WaveletDev &wself, const cp_model_t *w, int64_t wi,
+                     double wf, TC *cst1, int64_t *spl1);
+
 extern int64_t g_opt_gap_nr;                      // 64-row chunks per wave of the gap finish (1 or 2)
 extern int64_t g_opt_gap_tau, g_opt_gap_min;   // gap passes in the rounds tau <= gap_tau (-1: none) for tasks of >= gap_min candidates
 extern int64_t g_opt_poison, g_poison_hits;    // poison mode (tests): see run_layer

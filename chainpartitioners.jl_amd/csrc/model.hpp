@@ -161,6 +161,21 @@ inline bool model_exact_on(const cp_model_t *m, int64_t n, int64_t N, int64_t K)
     return bound < 9007199254740992.0;       // 2^53
 }
 
+// is the O(n log^2 n) total-cost scheme exact for this model?  Needs W[p]+f(p,r) inverse-Monge:
+// modular terms (alpha, vertices, pins) are free; the net count is submodular, so beta_net >= 0;
+// hyperedge cost = d*b_cut + l*(b_self - b_cut) needs b_cut >= 0 and b_self <= b_cut.
+// Both element types qualify only while every reachable total is exact (model_exact_on): a Float64 model needs integer-valued
+// parameters and totals below 2^53, an Int64 model totals below 2^60 -- a wrapped Int64 total is not inverse-Monge.
+inline bool fast_total_ok(const cp_model_t *m, int64_t n, int64_t N, int64_t K)
+{
+    if (!model_exact_on(m, n, N, K)) return false;
+    auto P = [&](int i) { return m->dtype == CP_I64 ? (double)m->p_i64[i] : m->p_f64[i]; };
+    if (m->kind == CP_MODEL_WORK) return true;
+    if (m->kind == CP_MODEL_CONNECTIVITY) return P(CP_P_NET) >= 0;
+    if (m->kind == CP_MODEL_HYPEREDGE_CUT) return P(CP_P_CUT_NET) >= 0 && P(CP_P_SELF_NET) <= P(CP_P_CUT_NET);
+    return false;
+}
+
 // host: build a DevModel from the C-ABI struct, uploading alpha_k / tables
 template <typename TC>
 struct HostModel {

@@ -943,20 +943,25 @@ static int64_t unravel_chunks_host(std::vector<int64_t> &spl, int64_t n)
 
 template <typename TC>
 int32_t run_pack_dynamic(cp_csr_s *A, const cp_model_t *mdl, const cp_rowpart_t *Pi, const cp_model_t *w, int64_t wi, double wf,
-                         int64_t *spl_out, int64_t *K_out)
+                         int64_t *spl_out, int64_t *K_out, int64_t *spl_tab = nullptr, TC *cst_tab = nullptr)
 {
     hipStream_t s = A->stream;
     int64_t n = A->n;
     std::unique_ptr<SeqCtx<TC>> C(new SeqCtx<TC>());
     seq_oracle<TC>(A, mdl, Pi, *C);
-    seq_window_table<TC>(A, mdl, w, wi, *C);
+    // any width past the scan's 16 columns, a monotone work budget or no constraint: the on-line divide and conquer (chunk_lws.hip)
+    const bool lws = lws_ok(A, mdl, w, wi, wf);
+    if (!lws) seq_window_table<TC>(A, mdl, w, wi, *C);
     SeqWeight W = make_weight(A, w, wi, wf);
     DBuf<TC> cst((size_t)n + 2);
     DBuf<int64_t> spl((size_t)n + 2);
     DBuf<int32_t> st(1);
     CP_HIP(hipMemsetAsync(st.p, 0, sizeof(int32_t), s));
     CP_HIP(hipMemsetAsync(spl.p, 0, spl.bytes(), s));
-    {
+    if (lws) {
+        const int32_t rc = run_pack_lws<TC>(A, C->HM.d, C->O.net, C->O.self, w, wi, wf, cst.p, spl.p);
+        if (rc != CP_OK) return rc;
+    } else {
         ProfScope ps(PROF_CHUNK, s, 0.0);
         // width-windowed costs whose sums are exact: parallel (min,+) scan (chunk_scan.hip).  Int64 sums wrap, so Int64 models
         // are bounded as Float64 ones are (model_exact_on; column-block models by their tabulated components)
@@ -972,12 +977,14 @@ int32_t run_pack_dynamic(cp_csr_s *A, const cp_model_t *mdl, const cp_rowpart_t 
     std::vector<int64_t> h((size_t)n + 1);
     CP_HIP(hipMemcpyAsync(&rc, st.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     CP_HIP(hipMemcpyAsync(h.data(), spl.p, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyDeviceToHost, s));
+    if (cst_tab) CP_HIP(hipMemcpyAsync(cst_tab, cst.p, sizeof(TC) * (size_t)(n + 1), hipMemcpyDeviceToHost, s));
     CP_HIP(hipStreamSynchronize(s));
     prof_collect();
     if (rc != CP_OK) { set_error("pack_stripe: a single column exceeds w_max (@assert j0 < j')"); return rc; }
+    if (spl_tab) for (int64_t t = 0; t <= n; t++) spl_tab[t] = h[(size_t)t];
     int64_t K = unravel_chunks_host(h, n);
-    for (int64_t k = 0; k <= K; k++) spl_out[k] = h[(size_t)k];
-    *K_out = K;
+    if (spl_out) for (int64_t k = 0; k <= K; k++) spl_out[k] = h[(size_t)k];
+    if (K_out) *K_out = K;
     return CP_OK;
 }
 
@@ -1280,6 +1287,18 @@ int32_t cp_pack_dynamic(cp_csr_t A, const cp_model_t *model, const cp_rowpart_t 
         CP_HIP(hipSetDevice(A->device));
         if (model->dtype == CP_I64) return run_pack_dynamic<int64_t>(A, model, Pi, weight, wmax_i64, wmax_f64, spl_out, K_out);
         return run_pack_dynamic<double>(A, model, Pi, weight, wmax_i64, wmax_f64, spl_out, K_out);
+    } CP_CATCH_ALL
+}
+
+int32_t cp_pack_dynamic_tables(cp_csr_t A, const cp_model_t *model, const cp_rowpart_t *Pi, const cp_model_t *weight, int64_t wmax_i64,
+                               double wmax_f64, int64_t *spl_tab, int64_t *cst_i64, double *cst_f64)
+{
+    try {
+        CP_REQUIRE(A && spl_tab && seq_model_ok(model) && weight_ok(weight), CP_EINVAL, "bad argument");
+        CP_REQUIRE(model->dtype == CP_I64 ? cst_i64 != nullptr : cst_f64 != nullptr, CP_EINVAL, "cst table of the model's element type needed");
+        CP_HIP(hipSetDevice(A->device));
+        if (model->dtype == CP_I64) return run_pack_dynamic<int64_t>(A, model, Pi, weight, wmax_i64, wmax_f64, nullptr, nullptr, spl_tab, cst_i64);
+        return run_pack_dynamic<double>(A, model, Pi, weight, wmax_i64, wmax_f64, nullptr, nullptr, spl_tab, cst_f64);
     } CP_CATCH_ALL
 }
 

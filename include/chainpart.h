@@ -121,6 +121,11 @@ int32_t cp_partition_dynamic(cp_csr_t csr, int64_t K, int32_t combine, int32_t o
 int32_t cp_pack_dynamic(cp_csr_t csr, const cp_model_t *model, const cp_rowpart_t *Pi,
                         const cp_model_t *weight, int64_t wmax_i64, double wmax_f64,
                         int64_t *spl_out /* n+1 */, int64_t *K_out);
+/* the tables DynamicChunker.jl:20-56 builds before unravel_chunks!: cst[j'] and spl[j'] (the smallest minimising j) at index j' - 1,
+ * spl_tab[0] = 0, from whichever path cp_pack_dynamic takes.  cst_i64 / cst_f64 (n+1): the one of the model's element type. */
+int32_t cp_pack_dynamic_tables(cp_csr_t csr, const cp_model_t *model, const cp_rowpart_t *Pi,
+                               const cp_model_t *weight, int64_t wmax_i64, double wmax_f64,
+                               int64_t *spl_tab /* n+1 */, int64_t *cst_i64 /* n+1 */, double *cst_f64 /* n+1 */);
 /* partition_stripe(A, K, [Flip]BisectCostBottleneckSplitter(f, eps))  BisectCostBottleneckSplitter.jl:6-127 */
 int32_t cp_partition_bisect_cost(cp_csr_t csr, int64_t K, const cp_model_t *model, double eps,
                                  int32_t flip, int64_t *spl_out /* K+1 */);
@@ -249,7 +254,9 @@ int32_t cp_get_stat(const char *name, int64_t *out);
  * layer are one leaf pass, csrc/dp_leaf.inc; 0: divide-and-conquer rounds down to tau = 0), "block_tables" (1: the leaf pass also
  * stores every per-block winner, needed by cp_dp_block_tables), "poison" (1: test mode of cp_get_stat above), "fixed_point" (1: layers
  * after one that reproduced its input row are copied), "bn_wave" (bottleneck DP walk: 0 lane per chunk of "bn_chunk" rows, 1 wave
- * per run of "bn_run" rows in lockstep, 2 = default: searched crossings for Int64 costs), "bn_slack" (columns of the start bracket), "prof_only" slot (events on one profile slot only), "dbg"
+ * per run of "bn_run" rows in lockstep, 2 = default: searched crossings for Int64 costs), "bn_slack" (columns of the start bracket), "lws" (1,
+ * default: cp_pack_dynamic past the scan -- any width, a monotone work budget, no constraint -- runs the on-line divide and conquer of
+ * csrc/chunk_lws.hip; 0: the one-wave kernel), "lws_leaf" (its rows per leaf wave: 256, 512, 1024 or 2048), "prof_only" slot (events on one profile slot only), "dbg"
  * (diagnostic bit mask).  Unknown names return CP_EINVAL. */
 int32_t cp_set_option(const char *name, int64_t value);
 /* built-in per-kernel HIP-event timing of the named hot kernels on the launch stream */
