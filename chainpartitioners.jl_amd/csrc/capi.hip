@@ -1,4 +1,5 @@
-// capi.hip -- extern "C" entry points of libchainpart.so (include/chainpart.h) and the DP drivers.
+// capi.hip -- extern "C" entry points of libchainpart.so (include/chainpart.h): argument checks and dispatch.  The K-layer DP
+// drivers behind cp_partition_dynamic, cp_dynamic_tables* and cp_dp_* are in dp_driver.hip.
 #include "csr.hpp"
 #include "model.hpp"
 #include "dp.hpp"
@@ -8,36 +9,9 @@
 
 using namespace cpk;
 
-namespace cpk { struct DpBase; }
-struct cp_dp_s { int32_t dtype; cpk::DpBase *impl; cp_csr_s *A; };
-
 namespace cpk {
 
-// ------------------------------------------------------------------ small kernels used by the drivers
-// per-column count of entries whose previous occurrence lies before `thr` (thr = 0: first occurrences)
-__global__ void k_col_count_prev_lt(const int64_t *__restrict__ pos, const int32_t *__restrict__ prev, int32_t thr,
-                                    int32_t *__restrict__ out, int64_t n)
-{
-    int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= n) return;
-    int32_t k = 0;
-    for (int64_t q = pos[c]; q < pos[c + 1]; q++) k += (prev[q] < thr);
-    out[c] = k;
-}
-
-// layer 1: cst[r] = f(1, j', 1) with nets(0, r) = #first occurrences in columns [0, r)   (DynamicSplitter.jl:26-31)
-template <typename TC>
-__global__ void k_layer1(int64_t n, const int64_t *__restrict__ pos, const int64_t *__restrict__ firsts_before,
-                         const int64_t *__restrict__ lpos, DevModel<TC> M, TC alpha, TC *__restrict__ cst, int32_t *__restrict__ ptr)
-{
-    int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r > n) return;
-    int64_t nn = firsts_before ? firsts_before[r] : 0;
-    int64_t nl = (M.kind == CP_MODEL_HYPEREDGE_CUT) ? lpos[r] : 0;     // rows whose last column < r
-    cst[r] = dm_apply(M, alpha, r, pos[r], nn, nl);
-    ptr[r] = 0;
-}
-
+// ------------------------------------------------------------------ small kernels of the oracle batches
 // counts for (p, r) ranges: nets = #{q in cols [p,r) : prev[q] < p}, selfnets = #{rows with first in [p,r) and last < r}.
 // gridDim.y blocks share one query (grid-stride over its entries) and combine with one atomic per block.
 __global__ void __launch_bounds__(256) k_range_counts(int64_t nq, const int64_t *__restrict__ P, const int64_t *__restrict__ Rr,
@@ -101,392 +75,6 @@ static bool model_known(const cp_model_t *m)
     if (!m || m->kind < CP_MODEL_FEASIBLE || m->kind > CP_MODEL_SECONDARY) return false;
     if (m->kind == CP_MODEL_POWER_WORK) return m->dtype == CP_F64;
     return m->dtype == CP_I64 || m->dtype == CP_F64;
-}
-
-
-
-// is the valley search of dp_bottleneck.hip exact for this model?  Needs a cost that grows with its part: every beta >= 0
-// (hyperedge cut: cost = d*b_cut + l*(b_self - b_cut) with d, l growing, so b_cut >= 0 and b_self >= b_cut).  alpha, alpha[k]
-// are free.  Element type: Work / Connectivity costs are sums of terms that are EACH monotone in the part (counts times a
-// non-negative beta) and IEEE addition is monotone, so non-integral Float64 parameters keep the valley.  The hyperedge cost is
-// evaluated as fl(l*b_self) + fl((d-l)*b_cut) (HyperedgeCutCosts.jl:21) and its (d - l) term is NOT monotone in the part:
-// with non-integral betas the rounded value can rise by an ulp while the part shrinks and the valley breaks (35 of 360 layers
-// differed from the literal sweep for (0,0,0,.1,.1), (0,0,0,.7,.1), (.3,.1,0,.3,.3)).  Those go to the general sweep; with
-// integer-valued parameters and totals below 2^53 every product and sum is exact and the real-number argument holds.
-// Int64 costs of every kind need the bound of model_exact_on: a cost that wraps past 2^63 stops growing with its part.
-static bool fast_bottleneck_ok(const cp_model_t *m, int64_t n, int64_t N, int64_t K)
-{
-    auto P = [&](int i) { return m->dtype == CP_I64 ? (double)m->p_i64[i] : m->p_f64[i]; };
-    if (m->dtype == CP_I64 && !model_exact_on(m, n, N, K)) return false;
-    if (!(P(CP_P_VERTEX) >= 0 && P(CP_P_PIN) >= 0)) return false;
-    if (m->kind == CP_MODEL_WORK) return true;
-    if (m->kind == CP_MODEL_CONNECTIVITY) return P(CP_P_NET) >= 0;
-    if (m->kind == CP_MODEL_HYPEREDGE_CUT)
-        return P(CP_P_CUT_NET) >= 0 && P(CP_P_SELF_NET) >= P(CP_P_CUT_NET) && model_exact_on(m, n, N, K);
-    return false;
-}
-
-template <typename TC> static TC host_alpha(const cp_model_t *m, int64_t k)
-{
-    if (m->alpha_k && k >= 1 && k <= m->n_alpha_k) return ((const TC *)m->alpha_k)[k - 1];
-    return model_param<TC>(m, CP_P_ALPHA);
-}
-
-// diff[0] |= "the two cost rows differ somewhere" (bitwise comparison: the tables are compared, not the values' meaning)
-template <typename TC>
-__global__ void __launch_bounds__(256) k_rows_differ(const TC *__restrict__ a, const TC *__restrict__ b, int64_t n1, int32_t *__restrict__ diff)
-{
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    bool d = false;
-    if (i < n1) {
-        static_assert(sizeof(TC) == 8, "cost rows are 8-byte elements");
-        d = reinterpret_cast<const unsigned long long *>(a)[i] != reinterpret_cast<const unsigned long long *>(b)[i];
-    }
-    if (__ballot(d) && (threadIdx.x & 63) == 0) atomicOr(diff, 1);
-}
-
-// ------------------------------------------------------------------ the K-part DP driver (unconstrained)
-template <typename TC>
-static int32_t run_dynamic(cp_csr_s *A, int64_t K, int32_t combine, int32_t order, const cp_model_t *mdl,
-                           int64_t *spl_out, int64_t *ptr_tab, TC *cst_tab)
-{
-    hipStream_t s = A->stream;
-    int64_t n = A->n;
-    bool need_self = mdl->kind == CP_MODEL_HYPEREDGE_CUT;
-    bool fast = combine == CP_COMBINE_SUM && fast_total_ok(mdl, A->n, A->N, K) && !g_opt_force_brute;
-    const bool fast_bn = combine == CP_COMBINE_MAX && fast_bottleneck_ok(mdl, A->n, A->N, K) && !g_opt_force_brute;
-    if (!fast && !fast_bn)
-        CP_REQUIRE(n <= g_opt_brute_max_n, CP_EUNSUPPORTED,
-                   "model/objective outside the O(n log^2 n) class and n too large for the O(n^2) device sweep");
-    ensure_links(A);
-    if (need_self) ensure_self(A);
-    HostModel<TC> HM;
-    build_dev_model<TC>(mdl, HM, s);
-    size_t n1 = (size_t)n + 1;
-    DBuf<TC> cstA(n1), cstB(n1);
-    DBuf<int32_t> ptr((size_t)K * n1);
-    DBuf<int32_t> cnt0((size_t)(n > 0 ? n : 1));
-    DBuf<int64_t> firsts(n1), scratch;
-    // layer 1
-    bool has_nets = mdl->kind == CP_MODEL_CONNECTIVITY || mdl->kind == CP_MODEL_HYPEREDGE_CUT || mdl->kind == CP_MODEL_COLBLOCK;
-    if (has_nets) {
-        if (n > 0) hipLaunchKernelGGL(k_col_count_prev_lt, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, A->pos.p, A->prev.p, 0, cnt0.p, n);
-        exclusive_scan_i32(cnt0.p, firsts.p, n, scratch, s);
-    }
-    // splitter order passes the part index (per-part alpha[k]); the chunker loop order calls f(j,j') (DynamicSplitter.jl:64)
-    auto alpha_of = [&](int64_t k) { return order == CP_ORDER_SPLITTER ? host_alpha<TC>(mdl, k) : model_param<TC>(mdl, CP_P_ALPHA); };
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_layer1<TC>), dim3((unsigned)cdiv(n + 1, 256)), dim3(256), 0, s, n, A->pos.p,
-                       has_nets ? firsts.p : nullptr, need_self ? A->lpos.p : nullptr, HM.d, alpha_of(1), cstA.p, ptr.p);
-    CP_HIP(hipGetLastError());
-    auto dump_layer = [&](int64_t k, const TC *cst_dev, bool last_only) {
-        if (!ptr_tab) return;
-        std::vector<TC> hc(n1);
-        std::vector<int32_t> hp(n1);
-        CP_HIP(hipMemcpyAsync(hc.data(), cst_dev, sizeof(TC) * n1, hipMemcpyDeviceToHost, s));
-        CP_HIP(hipMemcpyAsync(hp.data(), ptr.p + (size_t)(k - 1) * n1, sizeof(int32_t) * n1, hipMemcpyDeviceToHost, s));
-        CP_HIP(hipStreamSynchronize(s));
-        for (size_t r = 0; r < n1; r++) {
-            bool keep = !last_only || r == (size_t)n;
-            ptr_tab[(size_t)(k - 1) * n1 + r] = keep ? (int64_t)hp[r] + 1 : 0;               // zeros(Ti, n+1, K)
-            cst_tab[(size_t)(k - 1) * n1 + r] = keep ? hc[r] : CostTraits<TC>::typemax();     // fill(typemax, ...)
-        }
-    };
-    dump_layer(1, cstA.p, false);
-    void *work = fast ? dp_total_work_get<TC>(A) : nullptr;       // (kept in the handle between calls)
-    TC *prevc = cstA.p, *curc = cstB.p;
-    // cp_set_option("fixed_point", 1) -- OFF by default: a layer is a function of the previous layer's cost row alone (the model
-    // does not depend on k unless per-part alphas are given), so once a full layer reproduces its input row bit for bit every
-    // later layer repeats it: its argmin row is copied instead of recomputed.  Exact, but it turns K layers into two for
-    // costs where empty parts are free (alpha = 0): a property of the input, kept out of the default so that timings mean
-    // "K layers computed".
-    const bool fp_ok = g_opt_fixed_point && !(order == CP_ORDER_SPLITTER && mdl->alpha_k && mdl->n_alpha_k > 0);
-    DBuf<int32_t> diff(1);
-    for (int64_t k = 2; k <= K; k++) {
-        int32_t *pk = ptr.p + (size_t)(k - 1) * n1;
-        bool last = (k == K);
-        if (fast) dp_total_layer<TC>(A, HM.d, alpha_of(k), prevc, curc, pk, work, last ? n : 0, n);   // layer K: row n+1 only (:34)
-        else if (fast_bn) dp_bottleneck_layer<TC>(A, HM.d, alpha_of(k), prevc, curc, pk, last ? n : 0, n);
-        else dp_brute_layer<TC>(A, HM.d, alpha_of(k), combine, prevc, curc, pk, last ? n : 0, n);   // layer K: row n+1 only (:34)
-        dump_layer(k, curc, last);
-        if (fp_ok && !last) {
-            int32_t hd = 1;
-            CP_HIP(hipMemsetAsync(diff.p, 0, sizeof(int32_t), s));
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rows_differ<TC>), dim3((unsigned)cdiv((int64_t)n1, 256)), dim3(256), 0, s, prevc, curc, (int64_t)n1, diff.p);
-            CP_HIP(hipMemcpyAsync(&hd, diff.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-            CP_HIP(hipStreamSynchronize(s));
-            if (!hd) {                               // fixed point: layers k+1 .. K repeat layer k
-                for (int64_t k2 = k + 1; k2 <= K; k2++) {
-                    CP_HIP(hipMemcpyAsync(ptr.p + (size_t)(k2 - 1) * n1, pk, sizeof(int32_t) * n1, hipMemcpyDeviceToDevice, s));
-                    dump_layer(k2, curc, k2 == K);
-                }
-                break;
-            }
-        }
-        std::swap(prevc, curc);
-    }
-    // unravel_splits (DynamicSplitter.jl:89-99): K dependent single-element reads of ptr
-    std::vector<int64_t> spl((size_t)K + 1);
-    spl[K] = n;
-    for (int64_t k = K; k >= 1; k--) {
-        int32_t v = 0;
-        CP_HIP(hipMemcpyAsync(&v, ptr.p + (size_t)(k - 1) * n1 + (size_t)spl[k], sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        CP_HIP(hipStreamSynchronize(s));
-        spl[k - 1] = v;
-    }
-    for (int64_t k = 0; k <= K; k++) spl_out[k] = spl[k] + 1;
-    CP_HIP(hipStreamSynchronize(s));
-    prof_collect();
-    return CP_OK;
-}
-
-// ------------------------------------------------------------------ the K-part DP under a width constraint
-// partition_stripe(A, K, DynamicTotal{Splitter,Chunker}(ConstrainedCost(f, VertexCount(), w_max)))   DynamicSplitter.jl:206-314.
-// Layer k lives on the rows j' in [j'_lo[k], j'_hi[k]] (column_constraints :144-172; for the width weight: closed forms), its
-// candidates are j in [max(j'_lo[k-1], j' - w_max), min(j', j'_hi[k-1])] (:233-246), ties -> largest j.  The previous layer's
-// window enters through its cost row -- a value no real total reaches outside the window -- and the width through the windowed
-// geometry of dp_total_layer; the rows are restricted to the layer's window (the row-tile mechanism of the multi-GPU path).
-// The chunker loop order (:260-314) fills the same cells with the same recurrence (part_constraints :174-204 describes the
-// same windows column by column) and calls the cost without the part index.
-template <typename TC> struct BigCost;
-template <> struct BigCost<int64_t> { static __host__ __device__ int64_t v() { return (int64_t)1 << 61; } };
-template <> struct BigCost<double> { static __host__ __device__ double v() { return 1152921504606846976.0; } };      // 2^60
-
-// W[p] = cst[p] inside [lo, hi] (0-based rows), a huge value outside
-template <typename TC>
-__global__ void __launch_bounds__(256) k_mask_row(int64_t n1, int64_t lo, int64_t hi, const TC *__restrict__ cst, TC *__restrict__ W)
-{
-    int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p < n1) W[p] = (p >= lo && p <= hi) ? cst[p] : BigCost<TC>::v();
-}
-
-static void width_windows(int64_t n, int64_t K, int64_t w, std::vector<int64_t> &lo, std::vector<int64_t> &hi)
-{
-    lo.assign((size_t)K + 1, 0); hi.assign((size_t)K + 1, 0);           // 1-based k, 1-based j'
-    int64_t jp = n + 1;
-    for (int64_t k = K; k >= 1; k--) { lo[(size_t)k] = jp; jp = std::max<int64_t>(1, jp > w ? jp - w : 1); }
-    int64_t j = 1;
-    for (int64_t k = 1; k <= K; k++) { hi[(size_t)k] = (w >= n + 1 - j) ? n + 1 : j + w; j = hi[(size_t)k]; }
-}
-
-// combine = CP_COMBINE_MAX (DynamicBottleneck*(ConstrainedCost(...))): the same windows; the valley search of dp_bottleneck.hip takes
-// the layer's candidate limits directly (no masked row: the crossing is searched inside [max(lo[k-1], j' - w), min(j', hi[k-1])],
-// where the previous layer's costs are finite and still grow with the prefix -- dropping the last column of a feasible prefix
-// keeps every width <= w).
-
-// column_constraints (DynamicSplitter.jl:144-172) from that array: j'_lo walks back from n + 1 (:150-158, the first step taken
-// unconditionally), j'_hi forward from 1 (:161-169).  1-based j', as the reference's vectors.
-static void weight_windows(int64_t n, int64_t K, const std::vector<int32_t> &j0, std::vector<int64_t> &lo, std::vector<int64_t> &hi)
-{
-    lo.assign((size_t)K + 1, 0); hi.assign((size_t)K + 1, 0);
-    int64_t jp = n + 1;
-    for (int64_t k = K; k >= 1; k--) { lo[(size_t)k] = jp; jp = std::min<int64_t>(jp, (int64_t)j0[(size_t)jp - 1] + 1); }
-    int64_t j = 1;
-    for (int64_t k = 1; k <= K; k++) {
-        // the largest j' >= j with j0(j') <= j: j0 is non-decreasing in j'
-        const int64_t fit = (int64_t)(std::upper_bound(j0.begin(), j0.end(), (int32_t)(j - 1)) - j0.begin());     // #rows with j0 <= j - 1 (0-based) = the largest such j' (1-based)
-        hi[(size_t)k] = std::max<int64_t>(j, fit);
-        j = hi[(size_t)k];
-    }
-}
-
-template <typename TC>
-static int32_t run_dynamic_windowed(cp_csr_s *A, int64_t K, int32_t order, const cp_model_t *mdl, int64_t wmax,
-                                    int64_t *spl_out, int64_t *ptr_tab, TC *cst_tab, int64_t *win_lo, int64_t *win_hi,
-                                    int32_t combine = CP_COMBINE_SUM, const cp_model_t *weight = nullptr, int64_t wmax_i64 = 0, double wmax_f64 = 0)
-{
-    hipStream_t s = A->stream;
-    const int64_t n = A->n;
-    const size_t n1 = (size_t)n + 1;
-    std::vector<int64_t> lo, hi;
-    DBuf<int32_t> j0;
-    if (weight) {                                                        // a general monotone weight (bottleneck only): its j0 array
-        CP_REQUIRE(combine == CP_COMBINE_MAX && weight->kind == CP_MODEL_WORK && !weight->alpha_k, CP_EINTERNAL, "general weights: bottleneck DP only");
-        j0.alloc(n1);
-        const unsigned gw = (unsigned)cdiv((int64_t)n1, 256);
-        if (weight->dtype == CP_I64)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_weight_j0<int64_t>), dim3(gw), dim3(256), 0, s, n, A->pos.p, weight->p_i64[CP_P_ALPHA],
-                               weight->p_i64[CP_P_VERTEX], weight->p_i64[CP_P_PIN], wmax_i64, j0.p);
-        else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_weight_j0<double>), dim3(gw), dim3(256), 0, s, n, A->pos.p, weight->p_f64[CP_P_ALPHA],
-                               weight->p_f64[CP_P_VERTEX], weight->p_f64[CP_P_PIN], wmax_f64, j0.p);
-        CP_HIP(hipGetLastError());
-        std::vector<int32_t> hj(n1);
-        CP_HIP(hipMemcpyAsync(hj.data(), j0.p, sizeof(int32_t) * n1, hipMemcpyDeviceToHost, s));
-        CP_HIP(hipStreamSynchronize(s));
-        weight_windows(n, K, hj, lo, hi);
-    } else {
-        width_windows(n, K, wmax, lo, hi);
-    }
-    if (win_lo) for (int64_t k = 1; k <= K; k++) { win_lo[k - 1] = lo[(size_t)k]; win_hi[k - 1] = hi[(size_t)k]; }
-    if (ptr_tab) for (size_t i = 0; i < (size_t)K * n1; i++) { ptr_tab[i] = 0; cst_tab[i] = CostTraits<TC>::typemax(); }
-    if (hi[(size_t)K] < n + 1) {                                         // infeasible (:217-222): a degenerate partition, no exception
-        for (int64_t k = 0; k < K; k++) spl_out[k] = 1;
-        spl_out[K] = n + 1;
-        return CP_INFEASIBLE;
-    }
-    const int64_t w = weight ? 0 : std::min<int64_t>(wmax, std::max<int64_t>(n, 1));     // (wider than the matrix: every window is [0, r])
-    const bool need_self = mdl->kind == CP_MODEL_HYPEREDGE_CUT;
-    ensure_links(A);
-    if (need_self) ensure_self(A);
-    HostModel<TC> HM;
-    build_dev_model<TC>(mdl, HM, s);
-    DBuf<TC> cst(n1), Wm(n1);
-    DBuf<int32_t> ptr((size_t)K * n1);
-    DBuf<int32_t> cnt0((size_t)(n > 0 ? n : 1));
-    DBuf<int64_t> firsts(n1), scratch;
-    const bool has_nets = mdl->kind == CP_MODEL_CONNECTIVITY || mdl->kind == CP_MODEL_HYPEREDGE_CUT;
-    if (has_nets) {
-        if (n > 0) hipLaunchKernelGGL(k_col_count_prev_lt, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, A->pos.p, A->prev.p, 0, cnt0.p, n);
-        exclusive_scan_i32(cnt0.p, firsts.p, n, scratch, s);
-    }
-    auto alpha_of = [&](int64_t k) { return order == CP_ORDER_SPLITTER ? host_alpha<TC>(mdl, k) : model_param<TC>(mdl, CP_P_ALPHA); };
-    const unsigned g1 = (unsigned)cdiv((int64_t)n1, 256);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_layer1<TC>), dim3(g1), dim3(256), 0, s, n, A->pos.p, has_nets ? firsts.p : nullptr,
-                       need_self ? A->lpos.p : nullptr, HM.d, alpha_of(1), cst.p, ptr.p);
-    CP_HIP(hipGetLastError());
-    auto dump_layer = [&](int64_t k) {
-        if (!ptr_tab) return;
-        std::vector<TC> hc(n1);
-        std::vector<int32_t> hp(n1);
-        CP_HIP(hipMemcpyAsync(hc.data(), cst.p, sizeof(TC) * n1, hipMemcpyDeviceToHost, s));
-        CP_HIP(hipMemcpyAsync(hp.data(), ptr.p + (size_t)(k - 1) * n1, sizeof(int32_t) * n1, hipMemcpyDeviceToHost, s));
-        CP_HIP(hipStreamSynchronize(s));
-        for (int64_t r = lo[(size_t)k] - 1; r <= hi[(size_t)k] - 1; r++) {
-            ptr_tab[(size_t)(k - 1) * n1 + (size_t)r] = (int64_t)hp[(size_t)r] + 1;
-            cst_tab[(size_t)(k - 1) * n1 + (size_t)r] = hc[(size_t)r];
-        }
-    };
-    dump_layer(1);
-    void *work = combine == CP_COMBINE_SUM ? dp_total_work_get<TC>(A) : nullptr;
-    for (int64_t k = 2; k <= K; k++) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_mask_row<TC>), dim3(g1), dim3(256), 0, s, (int64_t)n1, lo[(size_t)k - 1] - 1, hi[(size_t)k - 1] - 1, cst.p, Wm.p);
-        if (combine == CP_COMBINE_SUM)
-            dp_total_layer<TC>(A, HM.d, alpha_of(k), Wm.p, cst.p, ptr.p + (size_t)(k - 1) * n1, work, lo[(size_t)k] - 1, hi[(size_t)k] - 1, w);
-        else
-            dp_bottleneck_layer<TC>(A, HM.d, alpha_of(k), Wm.p, cst.p, ptr.p + (size_t)(k - 1) * n1, lo[(size_t)k] - 1, hi[(size_t)k] - 1,
-                                    w, lo[(size_t)k - 1] - 1, hi[(size_t)k - 1] - 1, weight ? j0.p : nullptr);
-        dump_layer(k);
-    }
-    // unravel_splits (DynamicSplitter.jl:89-99); every visited cell lies in its layer's window
-    std::vector<int64_t> spl((size_t)K + 1);
-    spl[(size_t)K] = n;
-    for (int64_t k = K; k >= 1; k--) {
-        int32_t v = 0;
-        CP_HIP(hipMemcpyAsync(&v, ptr.p + (size_t)(k - 1) * n1 + (size_t)spl[(size_t)k], sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        CP_HIP(hipStreamSynchronize(s));
-        spl[(size_t)k - 1] = v;
-    }
-    for (int64_t k = 0; k <= K; k++) spl_out[k] = spl[(size_t)k] + 1;
-    CP_HIP(hipStreamSynchronize(s));
-    prof_collect();
-    return CP_OK;
-}
-
-// the scalable path takes: total cost, a model of the inverse-Monge class, the width weight, w_max >= 1
-static bool windowed_ok(cp_csr_s *A, int64_t K, int32_t combine, const cp_model_t *model, const cp_model_t *weight, int64_t wmax)
-{
-    // bottleneck: the searched-crossings walk carries the candidate limits (Int64 costs; dp_bottleneck.hip)
-    if (combine == CP_COMBINE_MAX)
-        return weight && weight->kind == CP_MODEL_VERTEX_COUNT && wmax >= 1 && !g_opt_force_brute && model->dtype == CP_I64 &&
-               g_opt_bn_wave >= 2 && (model->kind == CP_MODEL_WORK || model->kind == CP_MODEL_CONNECTIVITY || model->kind == CP_MODEL_HYPEREDGE_CUT) &&
-               fast_bottleneck_ok(model, A->n, A->N, K);
-    return combine == CP_COMBINE_SUM && weight && weight->kind == CP_MODEL_VERTEX_COUNT && wmax >= 1 && !g_opt_force_brute &&
-           (model->kind == CP_MODEL_WORK || model->kind == CP_MODEL_CONNECTIVITY || model->kind == CP_MODEL_HYPEREDGE_CUT) &&
-           fast_total_ok(model, A->n, A->N, K);
-}
-
-
-
-// ------------------------------------------------------------------ row-tiled DP (one rank = one tile of rows per layer)
-// cp_dp_*: the same layers as run_dynamic, but a rank computes only rows [row_lo, row_hi) of every layer and the caller
-// completes the layer's cost vector with a collective (RCCL all_gather over xGMI) before the next layer.
-struct DpBase { virtual ~DpBase() {} };
-template <typename TC>
-struct DpRun : DpBase {
-    cp_csr_s *A = nullptr;
-    int64_t K = 0, rlo = 0, rhi = 0;          // 0-based inclusive row window
-    int64_t wwin = 0;                          // > 0: layers k >= 2 take their candidates from the width window max(0, r - wwin) <= p <= r (cp_dp_set_window)
-    std::vector<int64_t> lay_lo, lay_hi;       // the row tile every layer was computed with (cp_dp_set_rows moves it between layers)
-    int32_t combine = 0, order = 0;
-    cp_model_t mdl{};
-    std::vector<TC> alpha_k_host;
-    HostModel<TC> HM;
-    bool fast = false, fast_bn = false, need_self = false;
-    void *work = nullptr;
-    DBuf<int32_t> ptr;                         // K x (n+1); only the tile rows of layers >= 2 are meaningful
-    ~DpRun() {}                                  // (the layer scratch belongs to the handle)
-    TC alpha_of(int64_t k) const
-    {
-        if (order == CP_ORDER_SPLITTER && !alpha_k_host.empty() && k >= 1 && k <= (int64_t)alpha_k_host.size()) return alpha_k_host[(size_t)k - 1];
-        return model_param<TC>(&mdl, CP_P_ALPHA);
-    }
-};
-
-template <typename TC>
-static int32_t dp_begin(cp_csr_s *A, int64_t K, int32_t combine, int32_t order, const cp_model_t *model, int64_t row_lo, int64_t row_hi,
-                        DpBase **out)
-{
-    std::unique_ptr<DpRun<TC>> D(new DpRun<TC>());
-    int64_t n = A->n;
-    D->A = A; D->K = K; D->combine = combine; D->order = order; D->mdl = *model;
-    D->rlo = row_lo - 1; D->rhi = row_hi - 2;
-    D->lay_lo.assign((size_t)K + 1, 0); D->lay_hi.assign((size_t)K + 1, -1);      // (a layer this rank never computes owns no row)
-    if (model->alpha_k && model->n_alpha_k > 0) {
-        D->alpha_k_host.assign((const TC *)model->alpha_k, (const TC *)model->alpha_k + model->n_alpha_k);
-        D->mdl.alpha_k = D->alpha_k_host.data();
-    }
-    D->need_self = model->kind == CP_MODEL_HYPEREDGE_CUT;
-    D->fast = combine == CP_COMBINE_SUM && fast_total_ok(model, A->n, A->N, K) && !g_opt_force_brute;
-    D->fast_bn = combine == CP_COMBINE_MAX && fast_bottleneck_ok(model, A->n, A->N, K) && !g_opt_force_brute;
-    if (!D->fast && !D->fast_bn)
-        CP_REQUIRE(n <= g_opt_brute_max_n, CP_EUNSUPPORTED,
-                   "model/objective outside the O(n log^2 n) class and n too large for the O(n^2) device sweep");
-    ensure_links(A);
-    if (D->need_self) ensure_self(A);
-    build_dev_model<TC>(&D->mdl, D->HM, A->stream);
-    D->ptr.alloc((size_t)K * (size_t)(n + 1));
-    CP_HIP(hipMemsetAsync(D->ptr.p, 0, D->ptr.bytes(), A->stream));
-    if (D->fast) D->work = dp_total_work_get<TC>(A);
-    CP_HIP(hipStreamSynchronize(A->stream));
-    *out = D.release();
-    return CP_OK;
-}
-
-template <typename TC>
-static int32_t dp_layer(DpRun<TC> *D, int64_t k, const TC *prev, TC *cur)
-{
-    cp_csr_s *A = D->A;
-    hipStream_t s = A->stream;
-    int64_t n = A->n;
-    size_t n1 = (size_t)n + 1;
-    int32_t *pk = D->ptr.p + (size_t)(k - 1) * n1;
-    if (k == 1) {                                  // every rank computes the whole first layer: a column scan, no exchange needed
-        const cp_model_t *mdl = &D->mdl;
-        bool has_nets = mdl->kind == CP_MODEL_CONNECTIVITY || mdl->kind == CP_MODEL_HYPEREDGE_CUT || mdl->kind == CP_MODEL_COLBLOCK;
-        DBuf<int32_t> cnt0((size_t)(n > 0 ? n : 1));
-        DBuf<int64_t> firsts(n1), scratch;
-        if (has_nets) {
-            if (n > 0) hipLaunchKernelGGL(k_col_count_prev_lt, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, A->pos.p, A->prev.p, 0, cnt0.p, n);
-            exclusive_scan_i32(cnt0.p, firsts.p, n, scratch, s);
-        }
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_layer1<TC>), dim3((unsigned)cdiv(n + 1, 256)), dim3(256), 0, s, n, A->pos.p,
-                           has_nets ? firsts.p : nullptr, D->need_self ? A->lpos.p : nullptr, D->HM.d, D->alpha_of(1), cur, pk);
-        CP_HIP(hipGetLastError());
-        CP_HIP(hipStreamSynchronize(s));
-        return CP_OK;
-    }
-    CP_REQUIRE(prev && cur && k >= 2 && k <= D->K, CP_EINVAL, "bad layer");
-    int64_t rlo = D->rlo < 0 ? 0 : D->rlo, rhi = D->rhi > n ? n : D->rhi;
-    D->lay_lo[(size_t)k] = rlo; D->lay_hi[(size_t)k] = rhi;
-    if (rhi >= rlo) {
-        CP_REQUIRE(D->wwin == 0 || D->fast, CP_EUNSUPPORTED, "the width window needs the O(n log^2 n) path");
-        if (D->fast) dp_total_layer<TC>(A, D->HM.d, D->alpha_of(k), prev, cur, pk, D->work, rlo, rhi, D->wwin);
-        else if (D->fast_bn) dp_bottleneck_layer<TC>(A, D->HM.d, D->alpha_of(k), prev, cur, pk, rlo, rhi);
-        else dp_brute_layer<TC>(A, D->HM.d, D->alpha_of(k), D->combine, prev, cur, pk, rlo, rhi);
-    }
-    CP_HIP(hipStreamSynchronize(s));
-    prof_collect();
-    return CP_OK;
 }
 
 // ------------------------------------------------------------------ ocl(j, j', k) batches
@@ -741,30 +329,26 @@ int32_t cp_partition_dynamic(cp_csr_t A, int64_t K, int32_t combine, int32_t ord
         bool constrained = weight && weight->kind != CP_MODEL_FEASIBLE;
         if (model->kind == CP_MODEL_PRIMARY || model->kind == CP_MODEL_SECONDARY) {
             CP_REQUIRE(!constrained, CP_EUNSUPPORTED, "ConstrainedCost over a plaid connectivity model has no device path");
-            if (model->dtype == CP_I64) return run_plaid_dynamic<int64_t>(A, K, combine, order, model, Pi, spl_out);
-            return run_plaid_dynamic<double>(A, K, combine, order, model, Pi, spl_out);
+            return with_cost_type(model->dtype, [&](auto tag) { return run_plaid_dynamic<decltype(tag)>(A, K, combine, order, model, Pi, spl_out); });
         }
         if (constrained) {
             CP_REQUIRE(weight->kind == CP_MODEL_VERTEX_COUNT || (weight->kind == CP_MODEL_WORK && !weight->alpha_k), CP_EINVAL,
                        "weight must be VertexCount or an AffineWorkModel");
             // width weights (VertexCount, AffineWorkModel(alpha, c, 0)): the equivalent number of columns
             const int64_t wv = width_of_weight(weight, A->n, wmax_i64, wmax_f64);
-            cp_model_t vc{}; vc.kind = CP_MODEL_VERTEX_COUNT; vc.dtype = CP_I64;
-            if (wv >= 1 && windowed_ok(A, K, combine, model, &vc, wv)) {      // O(K n log^2 n): the windowed geometry of dp_total.hip
-                if (model->dtype == CP_I64) return run_dynamic_windowed<int64_t>(A, K, order, model, wv, spl_out, nullptr, nullptr, nullptr, nullptr, combine);
-                return run_dynamic_windowed<double>(A, K, order, model, wv, spl_out, nullptr, nullptr, nullptr, nullptr, combine);
-            }
-            // bottleneck under any monotone work weight (pins, vertices + pins): the valley search with the weight's j0 array
-            if (combine == CP_COMBINE_MAX && wv == -2 && monotone_work_weight(weight) && model->dtype == CP_I64 && windowed_ok(A, K, combine, model, &vc, 1))
-                return run_dynamic_windowed<int64_t>(A, K, order, model, 0, spl_out, nullptr, nullptr, nullptr, nullptr, combine, weight, wmax_i64, wmax_f64);
-            if (model->dtype == CP_I64) return run_dyn_constrained<int64_t>(A, K, combine, order, model, Pi, weight, wmax_i64, wmax_f64, spl_out);
-            return run_dyn_constrained<double>(A, K, combine, order, model, Pi, weight, wmax_i64, wmax_f64, spl_out);
+            if (windowed_ok(A, K, combine, model, wv))                          // O(K n log^2 n): the windowed geometry of dp_total.hip
+                return run_dynamic_windowed(A, K, combine, order, model, wv, nullptr, 0, 0, spl_out, nullptr, nullptr, nullptr, nullptr, nullptr);
+            // bottleneck under any monotone work weight (pins, vertices + pins): the valley search with the weight's j0 array (Int64 costs only)
+            if (combine == CP_COMBINE_MAX && wv == -2 && monotone_work_weight(weight) && model->dtype == CP_I64 && windowed_ok(A, K, combine, model, 1))
+                return run_dynamic_windowed(A, K, combine, order, model, 0, weight, wmax_i64, wmax_f64, spl_out, nullptr, nullptr, nullptr, nullptr, nullptr);
+            return with_cost_type(model->dtype, [&](auto tag) {
+                return run_dyn_constrained<decltype(tag)>(A, K, combine, order, model, Pi, weight, wmax_i64, wmax_f64, spl_out);
+            });
         }
         CP_REQUIRE(model->kind == CP_MODEL_WORK || model->kind == CP_MODEL_CONNECTIVITY || model->kind == CP_MODEL_HYPEREDGE_CUT ||
                        model->kind == CP_MODEL_COLBLOCK || model->kind == CP_MODEL_POWER_WORK,
                    CP_EUNSUPPORTED, "model kind has no device DP path yet");
-        if (model->dtype == CP_I64) return run_dynamic<int64_t>(A, K, combine, order, model, spl_out, nullptr, nullptr);
-        return run_dynamic<double>(A, K, combine, order, model, spl_out, nullptr, nullptr);
+        return run_dynamic(A, K, combine, order, model, spl_out, nullptr, nullptr, nullptr);
     });
 }
 
@@ -780,8 +364,7 @@ int32_t cp_dynamic_tables(cp_csr_t A, int64_t K, int32_t combine, const cp_model
                    CP_EUNSUPPORTED, "model kind has no device DP path");
         CP_HIP(hipSetDevice(A->device));
         std::vector<int64_t> spl((size_t)K + 1);
-        if (model->dtype == CP_I64) return run_dynamic<int64_t>(A, K, combine, CP_ORDER_SPLITTER, model, spl.data(), ptr_out, cst_i64);
-        return run_dynamic<double>(A, K, combine, CP_ORDER_SPLITTER, model, spl.data(), ptr_out, cst_f64);
+        return run_dynamic(A, K, combine, CP_ORDER_SPLITTER, model, spl.data(), ptr_out, cst_i64, cst_f64);
     });
 }
 
@@ -794,15 +377,13 @@ int32_t cp_dynamic_tables_constrained_combine(cp_csr_t A, int64_t K, int32_t com
         CP_REQUIRE(combine == CP_COMBINE_SUM || combine == CP_COMBINE_MAX, CP_EINVAL, "bad combine");
         CP_REQUIRE(!weight || weight->kind == CP_MODEL_VERTEX_COUNT || (weight->kind == CP_MODEL_WORK && !weight->alpha_k), CP_EINVAL,
                    "weight must be VertexCount or an AffineWorkModel");
-        cp_model_t vc{}; vc.kind = CP_MODEL_VERTEX_COUNT; vc.dtype = CP_I64;
         const int64_t wv = weight ? width_of_weight(weight, A->n, wmax_i64, wmax_f64) : wmax_i64;      // (null: the width weight)
         const bool general = wv == -2 && combine == CP_COMBINE_MAX && monotone_work_weight(weight) && model->dtype == CP_I64;
-        CP_REQUIRE(windowed_ok(A, K, combine, model, &vc, general ? 1 : wv), CP_EUNSUPPORTED, "outside the windowed scalable path");
+        CP_REQUIRE(windowed_ok(A, K, combine, model, general ? 1 : wv), CP_EUNSUPPORTED, "outside the windowed scalable path");
         CP_HIP(hipSetDevice(A->device));
         std::vector<int64_t> spl((size_t)K + 1);
-        if (general) return run_dynamic_windowed<int64_t>(A, K, CP_ORDER_SPLITTER, model, 0, spl.data(), ptr_out, cst_i64, win_lo, win_hi, combine, weight, wmax_i64, wmax_f64);
-        if (model->dtype == CP_I64) return run_dynamic_windowed<int64_t>(A, K, CP_ORDER_SPLITTER, model, wv, spl.data(), ptr_out, cst_i64, win_lo, win_hi, combine);
-        return run_dynamic_windowed<double>(A, K, CP_ORDER_SPLITTER, model, wv, spl.data(), ptr_out, cst_f64, win_lo, win_hi, combine);
+        return run_dynamic_windowed(A, K, combine, CP_ORDER_SPLITTER, model, general ? 0 : wv, general ? weight : nullptr, wmax_i64, wmax_f64,
+                                    spl.data(), ptr_out, cst_i64, cst_f64, win_lo, win_hi);
     });
 }
 
@@ -819,16 +400,14 @@ int32_t cp_oracle_eval(cp_csr_t A, const cp_model_t *model, const cp_rowpart_t *
     return guarded([&]() -> int32_t {
         CP_REQUIRE(A && model_known(model) && (nq == 0 || (j && jp)), CP_EINVAL, "bad argument");
         CP_HIP(hipSetDevice(A->device));
-        if (model->kind == CP_MODEL_PRIMARY || model->kind == CP_MODEL_SECONDARY) {
-            if (model->dtype == CP_I64) return run_plaid_eval<int64_t>(A, model, Pi, nq, j, jp, k, out_i64);
-            return run_plaid_eval<double>(A, model, Pi, nq, j, jp, k, out_f64);
-        }
-        if (model->kind == CP_MODEL_BLOCK) {          // stateful step oracle: evaluated in query order by one wave (seq.hip)
-            if (model->dtype == CP_I64) return run_seq_eval<int64_t>(A, model, Pi, nq, j, jp, k, out_i64);
-            return run_seq_eval<double>(A, model, Pi, nq, j, jp, k, out_f64);
-        }
-        if (model->dtype == CP_I64) return run_oracle_eval<int64_t>(A, model, nq, j, jp, k, out_i64);
-        return run_oracle_eval<double>(A, model, nq, j, jp, k, out_f64);
+        return with_cost_type(model->dtype, [&](auto tag) {
+            using TC = decltype(tag);
+            TC *out = pick<TC>(out_i64, out_f64);
+            if (model->kind == CP_MODEL_PRIMARY || model->kind == CP_MODEL_SECONDARY) return run_plaid_eval<TC>(A, model, Pi, nq, j, jp, k, out);
+            // stateful step oracle: evaluated in query order by one wave (seq.hip)
+            if (model->kind == CP_MODEL_BLOCK) return run_seq_eval<TC>(A, model, Pi, nq, j, jp, k, out);
+            return run_oracle_eval<TC>(A, model, nq, j, jp, k, out);
+        });
     });
 }
 
@@ -1032,7 +611,7 @@ int32_t cp_link_array(cp_csr_t A, int64_t *out)
     });
 }
 
-// ---- row-tiled DP across ranks (multi-GPU): see include/chainpart.h
+// ---- row-tiled DP across ranks (multi-GPU): see include/chainpart.h; the handle and its layers: dp.hpp, dp_driver.hip
 int32_t cp_dp_begin(cp_csr_t A, int64_t K, int32_t combine, int32_t order, const cp_model_t *model, int64_t row_lo, int64_t row_hi,
                     cp_dp_t *out)
 {
@@ -1042,14 +621,7 @@ int32_t cp_dp_begin(cp_csr_t A, int64_t K, int32_t combine, int32_t order, const
         CP_REQUIRE(model->kind == CP_MODEL_WORK || model->kind == CP_MODEL_CONNECTIVITY || model->kind == CP_MODEL_HYPEREDGE_CUT ||
                        model->kind == CP_MODEL_COLBLOCK, CP_EUNSUPPORTED, "model kind has no device DP path");
         CP_HIP(hipSetDevice(A->device));
-        DpBase *impl = nullptr;
-        int32_t rc = model->dtype == CP_I64 ? dp_begin<int64_t>(A, K, combine, order, model, row_lo, row_hi, &impl)
-                                            : dp_begin<double>(A, K, combine, order, model, row_lo, row_hi, &impl);
-        if (rc != CP_OK) return rc;
-        cp_dp_s *h = new cp_dp_s();
-        h->dtype = model->dtype; h->impl = impl; h->A = A;
-        *out = h;
-        return CP_OK;
+        return dp_begin(A, K, combine, order, model, row_lo, row_hi, out);
     });
 }
 
@@ -1058,8 +630,7 @@ int32_t cp_dp_layer(cp_dp_t dp, int64_t k, const void *cst_prev_device, void *cs
     return guarded([&]() -> int32_t {
         CP_REQUIRE(dp && cst_cur_device && k >= 1, CP_EINVAL, "bad argument");
         CP_HIP(hipSetDevice(dp->A->device));
-        if (dp->dtype == CP_I64) return dp_layer<int64_t>(static_cast<DpRun<int64_t> *>(dp->impl), k, (const int64_t *)cst_prev_device, (int64_t *)cst_cur_device);
-        return dp_layer<double>(static_cast<DpRun<double> *>(dp->impl), k, (const double *)cst_prev_device, (double *)cst_cur_device);
+        return dp->step_layer(k, cst_prev_device, cst_cur_device);
     });
 }
 
@@ -1068,17 +639,13 @@ int32_t cp_dp_ptr_at(cp_dp_t dp, int64_t k, int64_t jp, int64_t *out)
     return guarded([&]() -> int32_t {
         CP_REQUIRE(dp && out && k >= 1 && jp >= 1 && jp <= dp->A->n + 1, CP_EINVAL, "bad argument");
         CP_HIP(hipSetDevice(dp->A->device));
-        int64_t rlo, rhi; DBuf<int32_t> *ptr; int64_t K;
-        if (dp->dtype == CP_I64) { auto *D = static_cast<DpRun<int64_t> *>(dp->impl); ptr = &D->ptr; K = D->K; CP_REQUIRE(k <= K, CP_EINVAL, "bad layer");
-                                   rlo = (size_t)k < D->lay_lo.size() ? D->lay_lo[(size_t)k] : D->rlo; rhi = (size_t)k < D->lay_hi.size() ? D->lay_hi[(size_t)k] : D->rhi; }
-        else { auto *D = static_cast<DpRun<double> *>(dp->impl); ptr = &D->ptr; K = D->K; CP_REQUIRE(k <= K, CP_EINVAL, "bad layer");
-               rlo = (size_t)k < D->lay_lo.size() ? D->lay_lo[(size_t)k] : D->rlo; rhi = (size_t)k < D->lay_hi.size() ? D->lay_hi[(size_t)k] : D->rhi; }
+        CP_REQUIRE(k <= dp->K, CP_EINVAL, "bad layer");
         *out = 0;
         if (k == 1) { *out = 1; return CP_OK; }                 // ptr[:, 1] == 1 on every rank
         int64_t r = jp - 1;
-        if (r < rlo || r > rhi) return CP_OK;                   // another rank owns this row
+        if (r < dp->lay_lo[(size_t)k] || r > dp->lay_hi[(size_t)k]) return CP_OK;      // another rank owns this row
         int32_t v = 0;
-        CP_HIP(hipMemcpyAsync(&v, ptr->p + (size_t)(k - 1) * (size_t)(dp->A->n + 1) + (size_t)r, sizeof(int32_t), hipMemcpyDeviceToHost, dp->A->stream));
+        CP_HIP(hipMemcpyAsync(&v, dp->ptr.p + (size_t)(k - 1) * (size_t)(dp->A->n + 1) + (size_t)r, sizeof(int32_t), hipMemcpyDeviceToHost, dp->A->stream));
         CP_HIP(hipStreamSynchronize(dp->A->stream));
         *out = (int64_t)v + 1;
         return CP_OK;
@@ -1088,16 +655,14 @@ int32_t cp_dp_ptr_at(cp_dp_t dp, int64_t k, int64_t jp, int64_t *out)
 int32_t cp_dp_set_rows(cp_dp_t dp, int64_t row_lo, int64_t row_hi)
 {
     if (!dp || row_lo < 1 || row_hi < row_lo || row_hi > dp->A->n + 2) return CP_EINVAL;
-    if (dp->dtype == CP_I64) { auto *D = static_cast<DpRun<int64_t> *>(dp->impl); D->rlo = row_lo - 1; D->rhi = row_hi - 2; }
-    else { auto *D = static_cast<DpRun<double> *>(dp->impl); D->rlo = row_lo - 1; D->rhi = row_hi - 2; }
+    dp->rlo = row_lo - 1; dp->rhi = row_hi - 2;
     return CP_OK;
 }
 
 int32_t cp_dp_set_window(cp_dp_t dp, int64_t wmax)
 {
     if (!dp || wmax < 0) return CP_EINVAL;
-    if (dp->dtype == CP_I64) static_cast<DpRun<int64_t> *>(dp->impl)->wwin = wmax;
-    else static_cast<DpRun<double> *>(dp->impl)->wwin = wmax;
+    dp->wwin = wmax;
     return CP_OK;
 }
 
@@ -1106,15 +671,11 @@ int32_t cp_dp_ptr_row(cp_dp_t dp, int64_t k, int64_t *out)
     return guarded([&]() -> int32_t {
         CP_REQUIRE(dp && out && k >= 1, CP_EINVAL, "bad argument");
         CP_HIP(hipSetDevice(dp->A->device));
-        int64_t rlo, rhi; DBuf<int32_t> *ptr; int64_t K;
-        if (dp->dtype == CP_I64) { auto *D = static_cast<DpRun<int64_t> *>(dp->impl); ptr = &D->ptr; K = D->K; CP_REQUIRE(k <= K, CP_EINVAL, "bad layer");
-                                   rlo = (size_t)k < D->lay_lo.size() ? D->lay_lo[(size_t)k] : D->rlo; rhi = (size_t)k < D->lay_hi.size() ? D->lay_hi[(size_t)k] : D->rhi; }
-        else { auto *D = static_cast<DpRun<double> *>(dp->impl); ptr = &D->ptr; K = D->K; CP_REQUIRE(k <= K, CP_EINVAL, "bad layer");
-               rlo = (size_t)k < D->lay_lo.size() ? D->lay_lo[(size_t)k] : D->rlo; rhi = (size_t)k < D->lay_hi.size() ? D->lay_hi[(size_t)k] : D->rhi; }
-        const int64_t n = dp->A->n;
+        CP_REQUIRE(k <= dp->K, CP_EINVAL, "bad layer");
+        const int64_t n = dp->A->n, rlo = dp->lay_lo[(size_t)k], rhi = dp->lay_hi[(size_t)k];
         if (k == 1) { for (int64_t r = 0; r <= n; r++) out[r] = 1; return CP_OK; }
         std::vector<int32_t> h((size_t)n + 1);
-        CP_HIP(hipMemcpyAsync(h.data(), ptr->p + (size_t)(k - 1) * (size_t)(n + 1), sizeof(int32_t) * (size_t)(n + 1), hipMemcpyDeviceToHost, dp->A->stream));
+        CP_HIP(hipMemcpyAsync(h.data(), dp->ptr.p + (size_t)(k - 1) * (size_t)(n + 1), sizeof(int32_t) * (size_t)(n + 1), hipMemcpyDeviceToHost, dp->A->stream));
         CP_HIP(hipStreamSynchronize(dp->A->stream));
         for (int64_t r = 0; r <= n; r++) out[r] = (r < rlo || r > rhi) ? 0 : (int64_t)h[(size_t)r] + 1;
         return CP_OK;
@@ -1126,18 +687,7 @@ int32_t cp_dp_block_tables(cp_dp_t dp, int32_t *nplanes_out, int64_t *opt_out, i
     return guarded([&]() -> int32_t {
         CP_REQUIRE(dp && opt_out && nets_out, CP_EINVAL, "bad argument");
         CP_HIP(hipSetDevice(dp->A->device));
-        int nb = 0;
-        if (dp->dtype == CP_I64) {
-            auto *D = static_cast<DpRun<int64_t> *>(dp->impl);
-            CP_REQUIRE(D->fast && D->work, CP_EUNSUPPORTED, "block tables exist on the O(n log^2 n) path only");
-            nb = dp_total_block_tables<int64_t>(dp->A, D->work, opt_out, nets_out, selfnets_out);
-        } else {
-            auto *D = static_cast<DpRun<double> *>(dp->impl);
-            CP_REQUIRE(D->fast && D->work, CP_EUNSUPPORTED, "block tables exist on the O(n log^2 n) path only");
-            nb = dp_total_block_tables<double>(dp->A, D->work, opt_out, nets_out, selfnets_out);
-        }
-        if (nplanes_out) *nplanes_out = nb;
-        return CP_OK;
+        return dp->block_tables(nplanes_out, opt_out, nets_out, selfnets_out);
     });
 }
 
@@ -1145,7 +695,6 @@ int32_t cp_dp_destroy(cp_dp_t dp)
 {
     if (!dp) return CP_OK;
     (void)hipSetDevice(dp->A->device);
-    delete dp->impl;
     delete dp;
     return CP_OK;
 }

@@ -3,7 +3,44 @@
 #include "csr.hpp"
 #include "model.hpp"
 
+// The handle of the row-tiled step protocol (cp_dp_t) and the base of the K-layer driver DpRun<TC> (dp_driver.hip): what does not
+// depend on the cost type.
+struct cp_dp_s {
+    cp_csr_s *A = nullptr;
+    int64_t K = 0;
+    int32_t combine = 0, order = 0;
+    bool fast = false, fast_bn = false, need_self = false;      // O(n log^2 n) total / valley-search bottleneck / neither: the O(n^2) sweep
+    void *work = nullptr;                      // scratch of the total-cost layers (dp_total_work_get)
+    cpk::DBuf<int32_t> ptr;                    // K x (n+1) argmins; a step handle fills only its tile rows of layers >= 2
+    // step protocol only
+    int64_t rlo = 0, rhi = 0;                  // 0-based inclusive row tile (cp_dp_set_rows moves it between layers)
+    int64_t wwin = 0;                          // > 0: layers k >= 2 take their candidates from the width window max(0, r - wwin) <= p <= r (cp_dp_set_window)
+    std::vector<int64_t> lay_lo, lay_hi;       // the row tile every layer was computed with
+    virtual ~cp_dp_s() = default;
+    virtual int32_t step_layer(int64_t k, const void *cst_prev_device, void *cst_cur_device) = 0;      // cp_dp_layer
+    virtual int32_t block_tables(int32_t *nplanes_out, int64_t *opt_out, int64_t *nets_out, int64_t *selfnets_out) = 0;
+};
+
 namespace cpk {
+
+using DpBase = ::cp_dp_s;
+
+// candidate limits of a weight-constrained layer (0-based); default-constructed: unconstrained
+struct DpWindow {
+    int64_t w = 0;                             // row r takes its candidates from p >= r - w (0: no width)
+    int64_t lo = 0, hi = -1;                   // and from the previous layer's row window [lo, hi] (bottleneck; hi < 0: none)
+    const int32_t *j0 = nullptr;               // device array (n + 1): p >= j0[r] instead of the width (bottleneck)
+};
+
+// dp_driver.hip: the K-layer drivers.  cst_i64 / cst_f64: the one matching model->dtype is used.
+int32_t run_dynamic(cp_csr_s *A, int64_t K, int32_t combine, int32_t order, const cp_model_t *mdl, int64_t *spl_out,
+                    int64_t *ptr_tab, int64_t *cst_i64, double *cst_f64);
+bool windowed_ok(cp_csr_s *A, int64_t K, int32_t combine, const cp_model_t *model, int64_t wmax);      // the gate of:
+int32_t run_dynamic_windowed(cp_csr_s *A, int64_t K, int32_t combine, int32_t order, const cp_model_t *mdl, int64_t width,
+                             const cp_model_t *weight, int64_t wmax_i64, double wmax_f64, int64_t *spl_out, int64_t *ptr_tab,
+                             int64_t *cst_i64, double *cst_f64, int64_t *win_lo, int64_t *win_hi);
+int32_t dp_begin(cp_csr_s *A, int64_t K, int32_t combine, int32_t order, const cp_model_t *model, int64_t row_lo, int64_t row_hi,
+                 cp_dp_s **out);
 
 // one layer of the total-cost DP by the O(n log^2 n) scheme (dp_total.hip)
 template <typename TC>
@@ -78,7 +115,7 @@ extern int64_t g_opt_own_min;                  // tasks with at least this many 
 extern int64_t g_opt_own_blk;                  // 1: their tiles sit at 256-column blocks and run in block order; 0: tiles counted from each task head (k_own_map)
 extern int64_t g_opt_short_t, g_opt_short_e;   // k_setup_short: tasks with <= short_t candidates and <= short_e link entries finish in setup
 extern int64_t g_opt_force_brute;      // cp_set_option("force_brute", 1)
-extern int64_t g_opt_brute_max_n;
-extern int64_t g_opt_dbg;            // timing experiments only (cp_set_option("dbg", mask)); results are wrong when non-zero      // largest n the O(n^2) path accepts
+extern int64_t g_opt_brute_max_n;      // largest n the O(n^2) path accepts
+extern int64_t g_opt_dbg;            // cp_set_option("dbg", mask): timing experiments; every bit leaves the tables unchanged (the tests demand it)
 
 }  // namespace cpk

@@ -19,7 +19,7 @@
 // Floating point: every term of the Work / Connectivity models is monotone in its count and IEEE addition is monotone, so the
 // valley holds for their non-integral Float64 parameters as well; max() is exact.  NOT so for the hyperedge-cut cost, whose
 // (d - l) * b_cut term shrinks while the part grows: its rounded sum can rise by an ulp against the real-number order, and
-// fast_bottleneck_ok (capi.hip) admits it only with integer-valued parameters (exact arithmetic) -- the rest runs dp_brute.hip.
+// fast_bottleneck_ok (dp_driver.hip) admits it only with integer-valued parameters (exact arithmetic) -- the rest runs dp_brute.hip.
 #include "csr.hpp"
 #include "model.hpp"
 #include "dp.hpp"

@@ -187,6 +187,12 @@ struct HostModel {
 template <typename TC> inline TC model_param(const cp_model_t *m, int i);
 template <> inline int64_t model_param<int64_t>(const cp_model_t *m, int i) { return m->p_i64[i]; }
 template <> inline double model_param<double>(const cp_model_t *m, int i) { return m->p_f64[i]; }
+// The one place the C ABI's dtype becomes a C++ cost type:  with_cost_type(m->dtype, [&](auto tag) { using TC = decltype(tag); ... })
+template <typename F> inline auto with_cost_type(int32_t dtype, F &&f) { return dtype == CP_I64 ? f(int64_t()) : f(double()); }
+// of a paired (Int64, Float64) argument, the one that belongs to TC
+template <typename TC> inline TC *pick(int64_t *i64, double *f64);
+template <> inline int64_t *pick<int64_t>(int64_t *i64, double *) { return i64; }
+template <> inline double *pick<double>(int64_t *, double *f64) { return f64; }
 template <typename TC> inline TC comp_const(const cp_component_t &c);
 template <> inline int64_t comp_const<int64_t>(const cp_component_t &c) { return c.c_i64; }
 template <> inline double comp_const<double>(const cp_component_t &c) { return c.c_f64; }

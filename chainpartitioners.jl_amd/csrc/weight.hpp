@@ -1,5 +1,5 @@
 // weight.hpp -- the weights of ConstrainedCost(f, w, w_max) that bound a part from the left: j0(j'), the first column whose part up
-// to j' fits, is non-decreasing in j' (capi.hip: windowed splitters; chunk_lws.hip: the scalable DynamicTotalChunker).
+// to j' fits, is non-decreasing in j' (dp_driver.hip: windowed splitters; chunk_lws.hip: the scalable DynamicTotalChunker).
 #pragma once
 #include "model.hpp"
 

@@ -225,7 +225,7 @@ def test_int64_wrap_splitters_and_windowed_tables(hip, orc, mi):
 
 @pytest.mark.parametrize("mi", [0, 1, 2, 3, 5])
 def test_int64_wrap_pin_weighted_bottleneck(hip, orc, mi):
-    """ConstrainedCost(f, AffineWorkModel(0, 0, 1), w_max): the valley search with the weight's j0 array (capi.hip) or the literal kernel"""
+    """ConstrainedCost(f, AffineWorkModel(0, 0, 1), w_max): the valley search with the weight's j0 array (dp_driver.hip) or the literal kernel"""
     mdl = i64_wrap()[mi]
     wgt = cp.AffineWorkModel(0, 0, 1)
     for A in MATS:

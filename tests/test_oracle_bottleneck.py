@@ -58,7 +58,7 @@ def _literal_max_layer(W, F):
 
 
 def test_non_integral_hyperedge_costs_are_outside_the_valley_class(orc):
-    """Why fast_bottleneck_ok (csrc/capi.hip) sends Float64 hyperedge-cut models with non-integral betas to the general sweep
+    """Why fast_bottleneck_ok (csrc/dp_driver.hip) sends Float64 hyperedge-cut models with non-integral betas to the general sweep
     (ADVICE round 2): the cost fl(l*b_self) + fl((d-l)*b_cut) is not monotone in the part after rounding, so the valley search
     is NOT the literal DP for them -- while a literal sweep over the same rounded cost table is.  Work / Connectivity models with
     non-integral parameters stay inside the class (every term is monotone)."""

@@ -68,7 +68,7 @@ while time.time() - t0 < budget:
     # windows from "barely feasible" to "wider than the matrix"
     if A.n >= 1 and A.n <= 2500:
         for w in (max(1, -(-A.n // K) + int(rng.integers(0, 4))), max(1, int(rng.integers(1, A.n + 3)))):
-            # the width weight under its own name, or as a work model alpha + c * width (windowed path too: csrc/capi.hip width_of_weight)
+            # the width weight under its own name, or as a work model alpha + c * width (windowed path too: csrc/weight.hpp width_of_weight)
             wk = int(rng.integers(0, 4))
             c = int(rng.integers(1, 4)); a0 = int(rng.integers(0, 3))
             # wk 3: a pin-weighted budget (the bottleneck DP takes it on the valley search through the weight's j0 array)
