@@ -21,7 +21,7 @@ SYMBOLS = [
     "cp_csr_reset_cache", "cp_count_build", "cp_count_query", "cp_count_destroy", "cp_link_array", "cp_partwise", "cp_domsum_build", "cp_rook_build", "cp_wsum_query", "cp_wsum_destroy",
     "cp_oracle_eval", "cp_oracle_step", "cp_bound_stripe", "cp_objective", "cp_partition_dynamic", "cp_pack_dynamic", "cp_pack_dynamic_tables",
     "cp_partition_bisect_cost", "cp_partition_bisect_cost_batch", "cp_pack_convex", "cp_pack_convex_batch", "cp_partition_convex", "cp_partition_equi", "cp_pack_equi",
-    "cp_dynamic_tables", "cp_dynamic_tables_constrained", "cp_dynamic_tables_constrained_combine", "cp_set_stream", "cp_reset_stream", "cp_get_stat", "cp_set_option", "cp_prof_enable", "cp_prof_reset", "cp_prof_get",
+    "cp_dynamic_tables", "cp_dynamic_tables_constrained", "cp_dynamic_tables_constrained_combine", "cp_set_stream", "cp_reset_stream", "cp_get_stat", "cp_test_round_scans", "cp_set_option", "cp_prof_enable", "cp_prof_reset", "cp_prof_get",
     "cp_dp_begin", "cp_dp_layer", "cp_dp_ptr_at", "cp_dp_destroy", "cp_dp_ptr_row", "cp_dp_block_tables", "cp_dp_set_window", "cp_dp_set_rows",
     "cp_partition_bisect_index", "cp_partition_lazy_bisect_cost", "cp_pack_concave", "cp_partition_concave",
     "cp_adjoint", "cp_csr_download", "cp_bound_stripe_pi", "cp_partition_bisect_cost_pi", "cp_partition_bisect_index_pi",
@@ -140,6 +140,19 @@ class HipBackend:
         if rc != 0:
             raise KeyError(name)
         return out.value
+
+    def test_round_scans(self, a, na_max, b, nb_max, two=True, cap_t=2**62, cap_nt=2**62, err_in=0, reps=1):
+        """the two task scans + verdict of a DP round in one launch (test entry): (offs, toffs, {T, NT, nlong, nown, ntile, err})"""
+        a = np.ascontiguousarray(a, dtype=np.int32)
+        b = np.ascontiguousarray(b, dtype=np.int32)
+        offs = np.zeros(len(a) + 1, dtype=np.int64)
+        toffs = np.zeros(len(b) + 1, dtype=np.int64)
+        res = np.zeros(6, dtype=np.int64)
+        rc = self.lib.cp_test_round_scans(_p(a), _i64(len(a)), _i64(na_max), _p(b), _i64(len(b)), _i64(nb_max), C.c_int32(1 if two else 0),
+                                          _i64(cap_t), _i64(cap_nt), C.c_int32(err_in), C.c_int32(reps), _p(offs), _p(toffs), _p(res))
+        if rc != 0:
+            raise RuntimeError(f"cp_test_round_scans -> {rc}: {self.last_error()}")
+        return offs, toffs, dict(zip(("T", "NT", "nlong", "nown", "ntile", "err"), (int(v) for v in res)))
 
     def set_option(self, name, value):
         return self.lib.cp_set_option(name.encode(), _i64(value))

@@ -232,7 +232,20 @@ int32_t cp_get_stat(const char *name, int64_t *out)
     if (!name || !out) return CP_EINVAL;
     if (!strcmp(name, "spec_redo")) { *out = g_spec_redo; return CP_OK; }
     if (!strcmp(name, "poison_hits")) { *out = g_poison_hits; return CP_OK; }
+    // tasks the block merge walked in more than one trip; bits 0 / 1 / 2: a task of 1 / FIX_SERIAL / FIX_SERIAL + 1 tiles was merged
+    if (!strcmp(name, "fix_trips")) { *out = g_fix_trips; return CP_OK; }
+    if (!strcmp(name, "fix_edges")) { *out = g_fix_edges; return CP_OK; }
     return CP_EINVAL;
+}
+
+int32_t cp_test_round_scans(const int32_t *a, int64_t na, int64_t na_max, const int32_t *b, int64_t nb, int64_t nb_max, int32_t two, int64_t cap_t,
+                            int64_t cap_nt, int32_t err_in, int32_t reps, int64_t *offs_out, int64_t *toffs_out, int64_t *res)
+{
+    if (!offs_out || !toffs_out || !res || (na > 0 && !a) || (nb > 0 && !b)) return CP_EINVAL;
+    return guarded([&]() -> int32_t {
+        dp_round_scans_test(a, na, na_max, b, nb, nb_max, two, cap_t, cap_nt, err_in, reps, offs_out, toffs_out, res);
+        return CP_OK;
+    });
 }
 
 int32_t cp_reset_stream(cp_csr_t A)
@@ -255,6 +268,7 @@ int32_t cp_set_option(const char *name, int64_t value)
     if (!strcmp(name, "force_brute")) { g_opt_force_brute = value; return CP_OK; }
     if (!strcmp(name, "brute_max_n")) { g_opt_brute_max_n = value; return CP_OK; }
     if (!strcmp(name, "dbg")) { g_opt_dbg = value; return CP_OK; }
+    if (!strcmp(name, "stat_reset")) { g_poison_hits = 0; g_spec_redo = 0; g_fix_trips = 0; g_fix_edges = 0; return CP_OK; }      // the counters of cp_get_stat
     if (!strcmp(name, "short_t")) { g_opt_short_t = value; return CP_OK; }
     if (!strcmp(name, "short_e")) { g_opt_short_e = value; return CP_OK; }
     if (!strcmp(name, "rpass_ch")) { int64_t v = 16; while (v < value && v < 4096) v <<= 1; g_opt_rpass_ch = v; return CP_OK; }
@@ -265,7 +279,7 @@ int32_t cp_set_option(const char *name, int64_t value)
     if (!strcmp(name, "pool")) { g_opt_pool = value ? 1 : 0; if (!value) dev_pool_trim(); return CP_OK; }      // (1: keep freed device blocks >= 1 MB for reuse; 0: return them)
     if (!strcmp(name, "ra_cache")) { g_opt_ra_cache = value; return CP_OK; }
     if (!strcmp(name, "leaf")) { g_opt_leaf = value; return CP_OK; }
-    if (!strcmp(name, "poison")) { g_opt_poison = value; if (value) { g_poison_hits = 0; g_spec_redo = 0; } return CP_OK; }
+    if (!strcmp(name, "poison")) { g_opt_poison = value; if (value) { g_poison_hits = 0; g_spec_redo = 0; g_fix_trips = 0; g_fix_edges = 0; } return CP_OK; }
     if (!strcmp(name, "block_tables")) { g_opt_block_tables = value; return CP_OK; }
     if (!strcmp(name, "rpass_small_tau")) { g_opt_rpass_small_tau = value; return CP_OK; }
     if (!strcmp(name, "force_max")) { g_opt_force_max = value < 0 ? 0 : value; return CP_OK; }

@@ -114,12 +114,73 @@ void exclusive_scan_i32_devn(const int32_t *in, int64_t *out, const int32_t *n_d
                              DBuf<int64_t> &scratch, hipStream_t s);
 // Single-launch form (decoupled look-back) for the scans inside the DP rounds: dozens of small scans per layer, where three
 // launches each are most of the cost.  Sums must stay below 2^40 (they are step / tile counts).  One ScanWS per stream of work.
+constexpr int SCAN_T = 256;
+constexpr int SCAN_I = 8;
+constexpr int SCAN_TILE = SCAN_T * SCAN_I;
 struct ScanWS {
     DBuf<unsigned long long> st;      // per block: [epoch:22][status:2][value:40]
-    DBuf<uint32_t> ticket;            // blocks take their index here (a block only waits for blocks that already run)
+    DBuf<uint32_t> ticket;            // [0]: blocks take their index here (a block only waits for blocks that already run);
+                                      // [1]: totals written by launches that hold two scans (+2 per launch)
     uint32_t epoch = 0, tbase = 0;
+    uint32_t pairs = 0;               // what ticket[1] holds when the next launch begins
 };
 void exclusive_scan_i32_lb(const int32_t *in, int64_t *out, const int32_t *n_dev, int64_t n_max, int64_t *total_out, ScanWS &ws, hipStream_t s);
+uint32_t scan_ws_begin(ScanWS &ws, int64_t nb, hipStream_t s);       // for kernels that hold scan_lb_block themselves: see core.hip
+
+__device__ __forceinline__ unsigned long long lb_pack(uint32_t epoch, uint32_t status, int64_t v)
+{
+    return ((unsigned long long)epoch << 42) | ((unsigned long long)status << 40) | ((unsigned long long)v & 0xFFFFFFFFFFull);
+}
+// One block (SCAN_T threads) of a chained scan: block `bid` of the scan whose status words are st[0 ..]; blocks get their `bid` in
+// the order they start (a ticket), so the blocks a block waits for already run.  The block holding index n writes out[n] and
+// *total_out (an agent-scope atomic store: a kernel that holds two scans reads it from another block) and returns true in
+// its thread 0.  sh: SCAN_T words of shared memory, s_prefix: one.
+__device__ __forceinline__ bool scan_lb_block(const int32_t *__restrict__ in, int64_t *__restrict__ out, int64_t n, int64_t *__restrict__ total_out,
+                                              unsigned long long *__restrict__ st, int64_t bid, uint32_t epoch, int64_t *sh, int64_t *s_prefix)
+{
+    const int64_t blast = n / SCAN_TILE;                 // the block holding index n writes the total
+    if (bid > blast) return false;
+    int64_t base = bid * SCAN_TILE + (int64_t)threadIdx.x * SCAN_I;
+    int32_t v[SCAN_I];
+    int64_t s = 0;
+    bool wrote = false;
+#pragma unroll
+    for (int k = 0; k < SCAN_I; k++) { v[k] = (base + k < n) ? in[base + k] : 0; s += v[k]; }
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 1; o < SCAN_T; o <<= 1) {
+        int64_t t = threadIdx.x >= (unsigned)o ? sh[threadIdx.x - o] : 0;
+        __syncthreads();
+        sh[threadIdx.x] += t;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const int64_t tot = sh[SCAN_T - 1];
+        int64_t prefix = 0;
+        if (bid > 0) {
+            __hip_atomic_store(&st[bid], lb_pack(epoch, 1, tot), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            for (int64_t j = bid - 1;; ) {
+                unsigned long long w = __hip_atomic_load(&st[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if ((uint32_t)(w >> 42) != epoch || ((w >> 40) & 3ull) == 0ull) { __builtin_amdgcn_s_sleep(1); continue; }      // not there yet
+                prefix += (int64_t)(w & 0xFFFFFFFFFFull);
+                if (((w >> 40) & 3ull) == 2ull) break;              // an inclusive prefix: done
+                j--;
+            }
+        }
+        __hip_atomic_store(&st[bid], lb_pack(epoch, 2, prefix + tot), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        *s_prefix = prefix;
+        if (bid == blast) {
+            out[n] = prefix + tot;
+            if (total_out) __hip_atomic_store(total_out, prefix + tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            wrote = true;
+        }
+    }
+    __syncthreads();
+    int64_t run = *s_prefix + sh[threadIdx.x] - s;
+#pragma unroll
+    for (int k = 0; k < SCAN_I; k++) if (base + k < n) { out[base + k] = run; run += v[k]; }
+    return wrote;
+}
 void exclusive_scan_i32_i32(const int32_t *in, int32_t *out, int64_t n, DBuf<int64_t> &scratch, hipStream_t s);
 
 // wave64 helpers

@@ -100,6 +100,9 @@ int32_t run_pack_lws(cp_csr_s *A, const DevModel<TC> &M, const WaveletDev &wnet,
 extern int64_t g_opt_gap_nr;                      // 64-row chunks per wave of the gap finish (1 or 2)
 extern int64_t g_opt_gap_tau, g_opt_gap_min;   // gap passes in the rounds tau <= gap_tau (-1: none) for tasks of >= gap_min candidates
 extern int64_t g_opt_poison, g_poison_hits;    // poison mode (tests): see run_layer
+void dp_round_scans_test(const int32_t *a, int64_t na, int64_t na_max, const int32_t *b, int64_t nb, int64_t nb_max, int two, int64_t capT, int64_t capNT,
+                         int err_in, int reps, int64_t *offs_out, int64_t *toffs_out, int64_t *res);      // dp_total.hip: cp_test_round_scans
+extern int64_t g_fix_trips, g_fix_edges;       // what the own-tile merges met since the last reset (tests): see RoundCounts::n_trips / n_edge
 extern int64_t g_opt_leaf;                     // 1: the rounds tau < 6 of an unconstrained layer are one leaf pass (dp_leaf.inc)
 extern int64_t g_opt_block_tables;             // 1: the leaf pass also stores the per-block winners (cp_dp_block_tables)
 extern int64_t g_opt_ra_cache;                 // 1: round A from counts computed once per partition

@@ -113,6 +113,7 @@ struct RoundCounts {
     int32_t n_wide, _pad;             // own-tiled tasks of more than FIX_SERIAL tiles (k_fix_own_lane -> k_fix_own)
     int32_t n_glong, n_gslots;        // gap tasks of more than GAPSEG tiles and their segment slots (k_gap_finish -> k_gap_seg)
     int32_t n_gslow, n_sslow;         // work items of k_gap_finish / k_gap_seg that met a tile with more than SMAX specials (redone by the SLOW variants)
+    int32_t n_trips, n_edge;          // what the merge met (cp_get_stat, tests): tasks of more than one trip of k_fix_own; bit 0 / 1 / 2: a task of 1 / FIX_SERIAL / FIX_SERIAL + 1 tiles
 };
 
 __device__ __forceinline__ void decode_task(const RoundDesc &R, int64_t t, int64_t &r, int &b)
@@ -898,8 +899,8 @@ __device__ __forceinline__ void interior_stream(const int32_t *__restrict__ arr,
 // ------------------------------------------------------------------ long tasks with tiles of their own
 // A task with >= OWN_MIN steps gets tiles of its own: every tile lies in one task, so all of them -- head and tail included --
 // take the uniform path: one contiguous run of the link array, suffix counts, tile-local evaluation.  k_own_map: tile ->
-// (task, tile index inside the task); k_lpass_own: one wave per tile; k_fix_own: one wave per task merges its tiles (adding the
-// counts made before each tile).  Tile ids are task-major, the head tile first.  Two geometries (own_ntiles / own_tile_geo):
+// (task, tile index inside the task); k_lpass_own: one wave per tile; k_fix_own_lane / k_fix_own: one lane or one block per task merges its tiles
+// (adding the counts made before each tile).  Tile ids are task-major, the head tile first.  Two geometries (own_ntiles / own_tile_geo):
 //   blk = 1 (default, cp_set_option("own_blk")): one tile per 256-column block floor(p / LT) the task's candidates [a, B] touch
 //           (the head and the tail tile partial: at most one tile more than cdiv(L, LT)).  k_own_map counts the tiles of every
 //           block, a scan and k_blk_order sort the tile ids by block, and k_lpass_own runs them in that order: the four waves
@@ -938,13 +939,18 @@ __global__ void __launch_bounds__(256) k_own_map(const RoundCounts *__restrict__
     }
 }
 
-// the counting sort's scatter: the tiles of column block c are border[bstart[c] .. bstart[c + 1])
+// the counting sort's scatter: the tiles of column block c are border[bstart[c] .. bstart[c + 1]).  The counts have been scanned
+// by now, and the tile of rank 0 of every block that has tiles puts its block's count back to zero: bcnt is all zero between
+// rounds without a clearing pass (k_own_map and this kernel walk the same rc->NT tiles).
 __global__ void __launch_bounds__(256) k_blk_order(const RoundCounts *__restrict__ rc, const int4 *__restrict__ rec, const int32_t *__restrict__ brank,
-                                                   const int64_t *__restrict__ bstart, int32_t *__restrict__ border)
+                                                   const int64_t *__restrict__ bstart, int32_t *__restrict__ border, int32_t *__restrict__ bcnt)
 {
     const int64_t ntile = rc->NT;
-    for (int64_t tile = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; tile < ntile; tile += (int64_t)gridDim.x * blockDim.x)
-        border[bstart[rec[tile].x / LT] + brank[tile]] = (int32_t)tile;
+    for (int64_t tile = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; tile < ntile; tile += (int64_t)gridDim.x * blockDim.x) {
+        const int32_t c = rec[tile].x / LT, rk = brank[tile];
+        border[bstart[c] + rk] = (int32_t)tile;
+        if (rk == 0) bcnt[c] = 0;
+    }
 }
 
 // border (blk = 1): the tile ids in column-block order; wave k takes tile border[k]
@@ -967,7 +973,7 @@ __global__ void __launch_bounds__(256) k_lpass_own(int isA, const RoundCounts *_
     //  counting sort by 256-column block (k_own_map, one scan, k_blk_order): 4 % off, and the sort is paid.  Staging each block's
     //  entries once per round in LDS for all its tiles (one workgroup per block) was 23 % slower: DESIGN.md section 6b.)
     // (No grid-stride loop here: it costs 14 VGPRs = two waves per SIMD.  The host launches one wave per tile of the buffer's
-    //  CAPACITY, which k_round_finish has checked the true count against.)
+    //  CAPACITY, which the round's verdict (k_round_scans) has checked the true count against.)
     int lane = threadIdx.x & 63;
     int64_t tile = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (tile >= rc->NT) return;
@@ -1452,9 +1458,13 @@ __global__ void __launch_bounds__(256) k_gap_merge(int tau, int nchunk, const Ro
 }
 
 // Merging the tiles of a task: one LANE per task looks at the tile count -- up to FIX_SERIAL: merged by the lane; more: appended
-// to the list k_fix_own walks (one wave or one block per task).  (Tried: k_lpass_own writing the winner of a single-tile task
-// itself -- the dependent loads at the end of every wave cost it more than the merge saves.)
+// to the list k_fix_own walks (one block per task).  The counts made before a tile are the task's anchor plus the counts of
+// the task's earlier tiles (tileS, written by k_lpass_own): a running sum here, a block-wide scan per trip in k_fix_own -- sums
+// inside ONE task, so no device-wide prefix over the round's tiles is made for them.  (The gap rounds do make one: k_gap_finish
+// and its helpers look tiles up at random.)  (Tried: k_lpass_own writing the winner of a single-tile task itself -- the dependent
+// loads at the end of every wave cost it more than the merge saves.)
 constexpr int FIX_SERIAL = 16;
+constexpr int FIX_U = 8;             // consecutive tiles per lane and trip of k_fix_own (a trip: 256 * FIX_U tiles)
 
 template <typename TC, bool HYP>
 __device__ __forceinline__ void fix_merge(Best<TC, HYP> &acc, Best<TC, HYP> c, int64_t base, int64_t base2, const DevModel<TC> &M)
@@ -1471,7 +1481,7 @@ __device__ __forceinline__ void fix_merge(Best<TC, HYP> &acc, Best<TC, HYP> c, i
 template <typename TC, bool HYP>
 __global__ void __launch_bounds__(256) k_fix_own_lane(RoundCounts *__restrict__ rc, const int64_t *__restrict__ toffs, const Best<TC, HYP> *__restrict__ part,
                                                       const int4 *__restrict__ tdesc, const uint8_t *__restrict__ tb, const int32_t *__restrict__ tS0l,
-                                                      const int64_t *__restrict__ tilePS, const int64_t *__restrict__ tilePS2, DevModel<TC> M,
+                                                      const int32_t *__restrict__ tileS, const int32_t *__restrict__ tileS2, DevModel<TC> M,
                                                       int32_t *__restrict__ opt, int32_t *__restrict__ nnopt, int32_t *__restrict__ nlopt, int64_t n1,
                                                       int32_t *__restrict__ wide_list)
 {
@@ -1490,61 +1500,96 @@ __global__ void __launch_bounds__(256) k_fix_own_lane(RoundCounts *__restrict__ 
             base = __shfl(base, 0);
             if (wide) wide_list[base + __popcll(mw & ((1ull << lane) - 1ull))] = (int32_t)t;
         }
+        const unsigned long long e1 = __ballot(nt == 1), e2 = __ballot(nt == FIX_SERIAL), e3 = __ballot(nt == FIX_SERIAL + 1);
+        if (lane == 0) {
+            const int32_t em = (e1 ? 1 : 0) | (e2 ? 2 : 0) | (e3 ? 4 : 0);
+            if (em & ~rc->n_edge) atomicOr(&rc->n_edge, em);
+        }
         if (nt < 1 || wide) continue;
         int4 td = tdesc[t];
-        int64_t S0 = td.y, S0l = HYP ? (int64_t)tS0l[t] : 0;
+        int64_t run = td.y, run2 = HYP ? (int64_t)tS0l[t] : 0;     // the counts made before tile k
         Best<TC, HYP> acc; best_clear(acc);
-        for (int64_t k = k0; k < k1; k++)                          // increasing k = decreasing p: larger p wins ties
-            fix_merge<TC, HYP>(acc, part[k], S0 + (tilePS[k] - tilePS[k0]), HYP ? S0l + (tilePS2[k] - tilePS2[k0]) : 0, M);
+        for (int64_t k = k0; k < k1; k++) {                        // (the winner does not depend on the order: larger p wins ties)
+            fix_merge<TC, HYP>(acc, part[k], run, run2, M);
+            run += tileS[k];
+            if (HYP) run2 += tileS2[k];
+        }
         int64_t rw = (int64_t)tb[t] * n1 + PR((int64_t)td.z);
         opt[rw] = acc.p; nnopt[rw] = acc.nn;
         if (HYP) nlopt[rw] = best_nl(acc);
     }
 }
 
-template <typename TC, bool HYP, int WPT>
-__global__ void __launch_bounds__(256) k_fix_own(const RoundCounts *__restrict__ rc, const int64_t *__restrict__ toffs, const Best<TC, HYP> *__restrict__ part,
+// one block per listed task (rounds with a few tasks of thousands of tiles each: the longest task sets the pace)
+template <typename TC, bool HYP>
+__global__ void __launch_bounds__(256) k_fix_own(RoundCounts *__restrict__ rc, const int64_t *__restrict__ toffs, const Best<TC, HYP> *__restrict__ part,
                                                  const int4 *__restrict__ tdesc, const uint8_t *__restrict__ tb, const int32_t *__restrict__ tS0l,
-                                                 const int64_t *__restrict__ tilePS, const int64_t *__restrict__ tilePS2, DevModel<TC> M,
+                                                 const int32_t *__restrict__ tileS, const int32_t *__restrict__ tileS2, DevModel<TC> M,
                                                  int32_t *__restrict__ opt, int32_t *__restrict__ nnopt, int32_t *__restrict__ nlopt, int64_t n1,
                                                  const int32_t *__restrict__ wide_list)
 {
-    // WPT = 1: one wave per task (four tasks per block); WPT = 4: the whole block works on one task (rounds with a few
-    // tasks of thousands of tiles each)
     __shared__ Best<TC, HYP> s_part[4];
+    __shared__ int64_t s_w[4], s_w2[4];
+    __shared__ int64_t s_pre[256 * FIX_U], s_pre2[HYP ? 256 * FIX_U : 1];      // per tile of the trip: the counts since its wave's first tile
     int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int64_t nlist = rc->n_wide;
-    // (the loop is block-uniform when WPT == 4: the barrier below is reached by the whole block)
-    for (int64_t i = WPT == 1 ? (int64_t)blockIdx.x * 4 + wv : (int64_t)blockIdx.x; i < nlist; i += WPT == 1 ? (int64_t)gridDim.x * 4 : (int64_t)gridDim.x) {
+    for (int64_t i = blockIdx.x; i < nlist; i += gridDim.x) {        // block-uniform: the barriers below are reached by the whole block
     int64_t t = wide_list[i];
     int64_t k0 = toffs[t], k1 = toffs[t + 1];
     int4 td = tdesc[t];
-    int64_t S0 = td.y, S0l = HYP ? (int64_t)tS0l[t] : 0;
     Best<TC, HYP> acc; best_clear(acc);
-    // (In every round the last row of the top rectangle owns a task over its whole block -- tens of thousands of tiles: eight tiles
-    //  per lane and step are in flight; one at a time, that task alone took 30 us of every round.)
-    const int64_t ps0 = tilePS[k0], ps20 = HYP ? tilePS2[k0] : 0;
-    for (int64_t kb = k0 + (WPT == 1 ? lane : (int64_t)threadIdx.x); kb < k1; kb += 8 * 64 * WPT) {
-        Best<TC, HYP> cc[8]; int64_t ps[8], ps2[8];
+    // (In every round the last row of the top rectangle owns a task over its whole block -- tens of thousands of tiles: FIX_U tiles
+    //  per lane and trip are in flight; one at a time, that task alone took 30 us of every round.)
+    int64_t carry = td.y, carry2 = HYP ? (int64_t)tS0l[t] : 0;      // the counts made before the trip's first tile
+    if (threadIdx.x == 0 && k1 - k0 > 256 * FIX_U) atomicAdd(&rc->n_trips, 1);
+    for (int64_t kt = k0; kt < k1; kt += 256 * FIX_U) {
+        // the 16-byte partials: lane x takes the tiles x, x + 256, ... of the trip (neighbouring lanes, neighbouring records)
+        Best<TC, HYP> cc[FIX_U];
 #pragma unroll
-        for (int u = 0; u < 8; u++) {
-            const int64_t k = kb + (int64_t)u * 64 * WPT;
-            best_clear(cc[u]); ps[u] = 0; ps2[u] = 0;
-            if (k < k1) { cc[u] = part[k]; ps[u] = tilePS[k]; if (HYP) ps2[u] = tilePS2[k]; }
+        for (int u = 0; u < FIX_U; u++) {
+            const int64_t k = kt + u * 256 + (int64_t)threadIdx.x;
+            best_clear(cc[u]);
+            if (k < k1) cc[u] = part[k];
         }
+        // the 4-byte counts: lane x takes FIX_U consecutive tiles, scans them with its wave and leaves every tile's exclusive
+        // prefix inside the wave's 64 * FIX_U tiles in LDS
+        int32_t ts[FIX_U], ts2[FIX_U];
+        int64_t sum = 0, sum2 = 0;
 #pragma unroll
-        for (int u = 0; u < 8; u++) {
-            Best<TC, HYP> c = cc[u];
-            if (c.p >= 0) {
-                int64_t base = S0 + (ps[u] - ps0);
-                int64_t base2 = HYP ? S0l + (ps2[u] - ps20) : 0;
-                c.v = cadd(c.v, dm_apply(M, (TC)0, (int64_t)0, (int64_t)0, base, base2));
-                c.nn = (int32_t)(c.nn + base);
-                if (HYP) best_set_nl(c, (int32_t)(best_nl(c) + base2));
+        for (int u = 0; u < FIX_U; u++) {
+            const int64_t k = kt + (int64_t)threadIdx.x * FIX_U + u;
+            ts[u] = 0; ts2[u] = 0;
+            if (k < k1) { ts[u] = tileS[k]; if (HYP) ts2[u] = tileS2[k]; }
+            sum += ts[u]; sum2 += ts2[u];
+        }
+        int64_t inc = sum, inc2 = sum2;
+        for (int o = 1; o < 64; o <<= 1) {
+            int64_t v = shfl_up64(inc, o);
+            if (lane >= o) inc += v;
+            if (HYP) { int64_t v2 = shfl_up64(inc2, o); if (lane >= o) inc2 += v2; }
+        }
+        __syncthreads();                                 // (the previous trip's prefixes have been read)
+        {
+            int64_t run = inc - sum, run2 = inc2 - sum2;
+#pragma unroll
+            for (int u = 0; u < FIX_U; u++) {
+                s_pre[threadIdx.x * FIX_U + u] = run; run += ts[u];
+                if (HYP) { s_pre2[threadIdx.x * FIX_U + u] = run2; run2 += ts2[u]; }
             }
-            bool take = (acc.p < 0) ? (c.p >= 0) : (c.p >= 0 && (c.v < acc.v || (c.v == acc.v && c.p > acc.p)));
-            if (take) acc = c;
         }
+        if (lane == 63) { s_w[wv] = inc; if (HYP) s_w2[wv] = inc2; }
+        __syncthreads();
+        int64_t wb[5], wb2[5];                           // counts before wave w's tiles; [4]: the trip's total
+        wb[0] = carry; wb2[0] = carry2;
+#pragma unroll
+        for (int w = 0; w < 4; w++) { wb[w + 1] = wb[w] + s_w[w]; wb2[w + 1] = HYP ? wb2[w] + s_w2[w] : 0; }
+#pragma unroll
+        for (int u = 0; u < FIX_U; u++) {                // tile u * 256 + x of the trip was scanned by wave (u * 256 + x) / (64 * FIX_U)
+            static_assert((64 * FIX_U) % 256 == 0, "a wave's tiles are whole rows of 256");
+            const int e = u * 256 + (int)threadIdx.x, w = (u * 256) / (64 * FIX_U);
+            fix_merge<TC, HYP>(acc, cc[u], wb[w] + s_pre[e], HYP ? wb2[w] + s_pre2[e] : 0, M);
+        }
+        carry = wb[4]; carry2 = wb2[4];
     }
     for (int o = 32; o > 0; o >>= 1) {
         int src = (lane + o) & 63;
@@ -1553,18 +1598,15 @@ __global__ void __launch_bounds__(256) k_fix_own(const RoundCounts *__restrict__
         bool take = (acc.p < 0) ? (c.p >= 0) : (c.p >= 0 && (c.v < acc.v || (c.v == acc.v && c.p > acc.p)));
         if (lane + o < 64 && take) acc = c;
     }
-    if (WPT > 1) {
-        __syncthreads();                                 // (the previous task's partials have been read)
-        if (lane == 0) s_part[wv] = acc;
-        __syncthreads();
-        if (threadIdx.x == 0)
-            for (int w = 1; w < 4; w++) {
-                Best<TC, HYP> c = s_part[w];
-                bool take = (acc.p < 0) ? (c.p >= 0) : (c.p >= 0 && (c.v < acc.v || (c.v == acc.v && c.p > acc.p)));
-                if (take) acc = c;
-            }
-    }
-    if (threadIdx.x == (WPT == 1 ? (unsigned)(wv * 64) : 0u)) {
+    __syncthreads();                                     // (the previous task's partials have been read)
+    if (lane == 0) s_part[wv] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; w++) {
+            Best<TC, HYP> c = s_part[w];
+            bool take = (acc.p < 0) ? (c.p >= 0) : (c.p >= 0 && (c.v < acc.v || (c.v == acc.v && c.p > acc.p)));
+            if (take) acc = c;
+        }
         int b = tb[t];
         int64_t rw = (int64_t)b * n1 + PR((int64_t)td.z);
         opt[rw] = acc.p; nnopt[rw] = acc.nn;
@@ -2367,12 +2409,95 @@ __global__ void __launch_bounds__(256) k_ra_merge(RATab T, int64_t nrow, const B
 }
 
 // ------------------------------------------------------------------ end of a round's counting phase
-// One thread: derives the tile count and checks the scan totals against the capacities of the buffers the host sized from
-// its prediction (the previous layer); on overflow the round's work is dropped and the flag makes the host redo the layer.
-__global__ void k_round_finish(RoundCounts *__restrict__ rc, int64_t capT, int64_t capNT)
+// The verdict on a round's scan totals, by one thread: derives the tile count and checks the totals against the capacities of
+// the buffers the host sized from its prediction (the previous layer); on overflow -- or a flag set earlier in the round -- the
+// round's work is dropped (T, NT, nlong, nown read as 0 by every later kernel of the round) and the flag makes the host redo the layer.
+__device__ __forceinline__ void round_verdict(RoundCounts *__restrict__ rc, int64_t capT, int64_t capNT)
 {
-    if (rc->T > capT || rc->NT > capNT || rc->err) { rc->err = 1; rc->T = 0; rc->NT = 0; rc->nlong = 0; rc->nown = 0; }
-    rc->ntile = (int32_t)((rc->T + LT - 1) / LT);
+    int64_t T = __hip_atomic_load(&rc->T, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int64_t NT = __hip_atomic_load(&rc->NT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (T > capT || NT > capNT || rc->err) { rc->err = 1; rc->T = 0; rc->NT = 0; rc->nlong = 0; rc->nown = 0; T = 0; }
+    rc->ntile = (int32_t)((T + LT - 1) / LT);
+}
+// (task lists beyond LB_MAX entries are scanned by the three-launch form: the verdict as a launch of its own)
+__global__ void k_round_finish(RoundCounts *__restrict__ rc, int64_t capT, int64_t capNT) { round_verdict(rc, capT, capNT); }
+
+// One launch for len -> offs (total T), o_ntl -> o_toffs (total NT) and the verdict.  The first nbA tickets are the blocks of the
+// first scan, the rest those of the second (status words st[nbA ..]): a block still waits only for blocks of its own scan with
+// lower tickets.  Each scan's total is written by one thread, which then counts itself in ticket[1]; the one that finds the
+// other already counted (the counter stood at `done0` when the launch began: the host counts two per launch) gives the
+// verdict.  (By then every block that has work has read its element count: the verdict may zero nlong / nown under the blocks
+// that start later -- they are beyond the last block of either count and return.)  The counts are clamped to the sizes the
+// grid was made for (nmaxA / nmaxB; a count beyond them has set err in k_setup_short): each range always holds the block
+// that writes its total, so the verdict is given in every launch, as it was by a kernel of its own.
+__global__ void __launch_bounds__(SCAN_T) k_round_scans(RoundCounts *__restrict__ rc, const int32_t *__restrict__ len, int64_t *__restrict__ offs,
+                                                        const int32_t *__restrict__ ntl, int64_t *__restrict__ toffs, uint32_t nbA, int two,
+                                                        int64_t nmaxA, int64_t nmaxB, int64_t capT, int64_t capNT, unsigned long long *__restrict__ st,
+                                                        uint32_t *__restrict__ ticket, uint32_t tbase, uint32_t epoch, uint32_t done0)
+{
+    __shared__ int64_t sh[SCAN_T];
+    __shared__ uint32_t s_bid;
+    __shared__ int64_t s_prefix;
+    if (threadIdx.x == 0) s_bid = atomicAdd(ticket, 1u) - tbase;
+    __syncthreads();
+    const uint32_t bid = s_bid;
+    const bool second = bid >= nbA;
+    int64_t n = second ? (int64_t)rc->nown : (int64_t)rc->nlong;
+    const int64_t nmax = second ? nmaxB : nmaxA;
+    n = n < 0 ? 0 : (n > nmax ? nmax : n);
+    const bool wrote = second ? scan_lb_block(ntl, toffs, n, &rc->NT, st + nbA, (int64_t)(bid - nbA), epoch, sh, &s_prefix)
+                              : scan_lb_block(len, offs, n, &rc->T, st, (int64_t)bid, epoch, sh, &s_prefix);
+    if (wrote && (!two || __hip_atomic_fetch_add(ticket + 1, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) - done0 == 1u))
+        round_verdict(rc, capT, capNT);
+}
+
+// host side of k_round_scans: lenA[0 .. rc->nlong) -> offs, lenB[0 .. rc->nown) -> toffs (two = false: the first only)
+static void launch_round_scans(RoundCounts *rc, const int32_t *lenA, int64_t *offs, int64_t nmaxA, const int32_t *lenB, int64_t *toffs, int64_t nmaxB,
+                               bool two, int64_t capT, int64_t capNT, ScanWS &ws, hipStream_t s)
+{
+    if (nmaxA < 0) nmaxA = 0;
+    if (nmaxB < 0) nmaxB = 0;
+    const int64_t nbA = nmaxA / SCAN_TILE + 1, nbB = two ? nmaxB / SCAN_TILE + 1 : 0;      // (each covers the block that holds index n == n_max)
+    const uint32_t tbase = scan_ws_begin(ws, nbA + nbB, s);
+    const uint32_t done0 = ws.pairs;
+    if (two) ws.pairs += 2u;
+    hipLaunchKernelGGL(k_round_scans, dim3((unsigned)(nbA + nbB)), dim3(SCAN_T), 0, s, rc, lenA, offs, lenB, toffs, (uint32_t)nbA, two ? 1 : 0,
+                       nmaxA, nmaxB, capT, capNT, ws.st.p, ws.ticket.p, tbase, ws.epoch, done0);
+    CP_HIP(hipGetLastError());
+}
+
+// Test entry (cp_test_round_scans): the launch above on host arrays with the counts na / nb on the device (grids for na_max / nb_max),
+// `reps` times on one ScanWS (tickets, epochs and the totals' counter go on from launch to launch).
+// res: {T, NT, nlong, nown, ntile, err} after the last launch; offs_out: na + 1 values, toffs_out: nb + 1 values (what the scans wrote).
+void dp_round_scans_test(const int32_t *a, int64_t na, int64_t na_max, const int32_t *b, int64_t nb, int64_t nb_max, int two, int64_t capT, int64_t capNT,
+                         int err_in, int reps, int64_t *offs_out, int64_t *toffs_out, int64_t *res)
+{
+    CP_REQUIRE(na >= 0 && nb >= 0 && na <= na_max && nb <= nb_max && na_max < INT32_MAX && nb_max < INT32_MAX && reps >= 1, CP_EINVAL, "round scans test: bad sizes");
+    hipStream_t s = nullptr;
+    DBuf<int32_t> da((size_t)na_max + 1), db((size_t)nb_max + 1);
+    DBuf<int64_t> doffs((size_t)na_max + 2), dtoffs((size_t)nb_max + 2);
+    DBuf<RoundCounts> drc(1);
+    ScanWS ws;
+    // (entries beyond the counts hold a value that would show in any sum that read them)
+    CP_HIP(hipMemsetAsync(da.p, 0x01, da.bytes(), s));
+    CP_HIP(hipMemsetAsync(db.p, 0x01, db.bytes(), s));
+    if (na > 0) CP_HIP(hipMemcpyAsync(da.p, a, sizeof(int32_t) * (size_t)na, hipMemcpyHostToDevice, s));
+    if (nb > 0) CP_HIP(hipMemcpyAsync(db.p, b, sizeof(int32_t) * (size_t)nb, hipMemcpyHostToDevice, s));
+    RoundCounts h;
+    for (int r = 0; r < reps; r++) {
+        memset(&h, 0, sizeof(h));
+        h.nlong = (int32_t)na; h.nown = (int32_t)nb; h.err = err_in;
+        CP_HIP(hipMemsetAsync(doffs.p, 0xFF, doffs.bytes(), s));
+        CP_HIP(hipMemsetAsync(dtoffs.p, 0xFF, dtoffs.bytes(), s));
+        CP_HIP(hipMemcpyAsync(drc.p, &h, sizeof(h), hipMemcpyHostToDevice, s));
+        CP_HIP(hipStreamSynchronize(s));               // (h is reused)
+        launch_round_scans(drc.p, da.p, doffs.p, na_max, db.p, dtoffs.p, nb_max, two != 0, capT, capNT, ws, s);
+    }
+    CP_HIP(hipMemcpyAsync(&h, drc.p, sizeof(h), hipMemcpyDeviceToHost, s));
+    CP_HIP(hipMemcpyAsync(offs_out, doffs.p, sizeof(int64_t) * (size_t)(na + 1), hipMemcpyDeviceToHost, s));
+    CP_HIP(hipMemcpyAsync(toffs_out, dtoffs.p, sizeof(int64_t) * (size_t)(nb + 1), hipMemcpyDeviceToHost, s));
+    CP_HIP(hipStreamSynchronize(s));
+    res[0] = h.T; res[1] = h.NT; res[2] = h.nlong; res[3] = h.nown; res[4] = h.ntile; res[5] = h.err;
 }
 
 #include "dp_leaf.inc"
@@ -2417,6 +2542,7 @@ struct LayerWork {
     DBuf<int32_t> b_cnt, b_n, o_brank, o_border;        // tiles per block, the block count (device); per tile: rank in its block, tile ids in block order
     DBuf<int64_t> b_start;
     int64_t b_nblk = 0;
+    bool b_dirty = true;                                // b_cnt may hold counts (run_layer clears it before its first round)
     int64_t max_tasks = 0;
     bool planes_full = false;                           // the last layer stored every per-block winner (cp_dp_block_tables)
     DBuf<int32_t> pz;                                   // poison mode: cells read that nobody wrote
@@ -2777,7 +2903,13 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
             Wk.b_cnt.ensure((size_t)nblk); Wk.b_start.ensure((size_t)nblk + 1); Wk.b_n.ensure(1);
             CP_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(Wk.b_n.p), (int)nblk, 1, s));
             Wk.b_nblk = nblk;
+            Wk.b_dirty = true;
         }
+        // b_cnt is zero between rounds (k_blk_order puts back what k_own_map counted): cleared when allocated.  The clear after a
+        // layer that did not come to its end in order is a safeguard only: k_own_map and k_blk_order are enqueued as a pair and
+        // walk the same tiles (a dropped round: none), so only an error thrown between the two could leave counts behind.
+        if (Wk.b_dirty) CP_HIP(hipMemsetAsync(Wk.b_cnt.p, 0, Wk.b_cnt.bytes(), s));
+        Wk.b_dirty = true;
     }
     // cp_set_option("poison", 1) (tests): every layer starts from planes full of an out-of-range column; the kernels that turn
     // plane cells into addresses count and clamp what they read of it.  The invariant behind the speculative layers -- "whatever a
@@ -2967,25 +3099,24 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
                 P.own_steps = (unsigned long long)sc((int64_t)P.own_steps);
             }
             if ((g_opt_dbg & 1024) && (rd & 1)) { P.nown = 0; P.NT = 0; P.nlong = 0; P.T = 0; }      // test: a prediction that skips stages with work
-            // buffers from the prediction (grown only here; k_round_finish checks the true totals against them)
+            // buffers from the prediction (grown only here; the round's verdict, k_round_scans, checks the true totals against them)
             Wk.ensure_own((size_t)grow(P.NT));
             Wk.ensure_flat((size_t)grow(P.T));
         }
         {
-            // both scans read their element count on the device
+            // both scans read their element count on the device; one launch holds them and the round's verdict
             ProfScope ps(PROF_SCAN, s, 12.0 * (double)R.ntask);
-            // (single-launch scans take their block index from one counter: fine for a few hundred blocks, not for 27 000)
-            if (R.ntask <= LB_MAX) exclusive_scan_i32_lb(Wk.len.p, Wk.offs.p, &rc->nlong, R.ntask, &rc->T, Wk.scanws, s);
-            else exclusive_scan_i32_devn(Wk.len.p, Wk.offs.p, &rc->nlong, R.ntask, &rc->T, Wk.scratch, s);
-            if (own_tiles)
-                {
-                    const int64_t nm = std::min<int64_t>(R.ntask, (int64_t)Wk.o_ntl.n);
-                    if (nm <= LB_MAX) exclusive_scan_i32_lb(Wk.o_ntl.p, Wk.o_toffs.p, &rc->nown, nm, &rc->NT, Wk.scanws, s);
-                    else exclusive_scan_i32_devn(Wk.o_ntl.p, Wk.o_toffs.p, &rc->nown, nm, &rc->NT, Wk.scratch, s);
-                }
             const bool tiny = spec && (g_opt_dbg & 2048);       // test: pretend the buffers sized from the prediction are too small
-            hipLaunchKernelGGL(k_round_finish, dim3(1), dim3(1), 0, s, rc, spec ? (tiny ? (int64_t)64 : (int64_t)Wk.loc.n) : INT64_MAX,
-                               spec ? (tiny ? (int64_t)1 : (int64_t)Wk.o_rec.n) : INT64_MAX);
+            const int64_t capT = spec ? (tiny ? (int64_t)64 : (int64_t)Wk.loc.n) : INT64_MAX, capNT = spec ? (tiny ? (int64_t)1 : (int64_t)Wk.o_rec.n) : INT64_MAX;
+            const int64_t nm = std::min<int64_t>(R.ntask, (int64_t)Wk.o_ntl.n);
+            if (R.ntask <= LB_MAX) {
+                launch_round_scans(rc, Wk.len.p, Wk.offs.p, R.ntask, Wk.o_ntl.p, Wk.o_toffs.p, nm, own_tiles, capT, capNT, Wk.scanws, s);
+            } else {
+                // (single-launch scans take their block index from one counter: fine for a few hundred blocks, not for 27 000)
+                exclusive_scan_i32_devn(Wk.len.p, Wk.offs.p, &rc->nlong, R.ntask, &rc->T, Wk.scratch, s);
+                if (own_tiles) exclusive_scan_i32_devn(Wk.o_ntl.p, Wk.o_toffs.p, &rc->nown, nm, &rc->NT, Wk.scratch, s);
+                hipLaunchKernelGGL(k_round_finish, dim3(1), dim3(1), 0, s, rc, capT, capNT);
+            }
         }
         if (!spec) {
             CP_HIP(hipMemcpyAsync(&P, rc, sizeof(P), hipMemcpyDeviceToHost, s));
@@ -3006,7 +3137,6 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
                 CP_HIP(hipMemsetAsync(Wk.o_rec.p, pat, Wk.o_rec.bytes(), s));
                 if (hyp) CP_HIP(hipMemsetAsync(Wk.o_tileS2.p, pat, Wk.o_tileS2.bytes(), s));
             }
-            if (oblk) CP_HIP(hipMemsetAsync(Wk.b_cnt.p, 0, sizeof(int32_t) * (size_t)Wk.b_nblk, s));
             const unsigned mgrid = (unsigned)std::min<int64_t>(cdiv(gNT, 256), 8192);
             hipLaunchKernelGGL(k_own_map, dim3(mgrid), dim3(256), 0, s, rc, Wk.o_toffs.p, Wk.o_tdesc.p, Wk.o_rlen.p, Wk.o_rec.p, Wk.o_task.p,
                                Wk.o_tb.p, gap ? Wk.o_hi.p : (int32_t *)nullptr, R.tau, n, oblk, oblk ? Wk.b_cnt.p : (int32_t *)nullptr, Wk.o_brank.p);
@@ -3014,7 +3144,7 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
                 ProfScope ps(gap ? PROF_GAPSTREAM : PROF_OWN, s, (double)P.own_steps * step_bytes);      // same bytes per step as dp_lpass
                 if (oblk) {                       // the tile ids by column block (counted in k_own_map): ~10^5 tiles, a counting sort
                     exclusive_scan_i32_lb(Wk.b_cnt.p, Wk.b_start.p, Wk.b_n.p, Wk.b_nblk, nullptr, Wk.scanws, s);
-                    hipLaunchKernelGGL(k_blk_order, dim3(mgrid), dim3(256), 0, s, rc, Wk.o_rec.p, Wk.o_brank.p, Wk.b_start.p, Wk.o_border.p);
+                    hipLaunchKernelGGL(k_blk_order, dim3(mgrid), dim3(256), 0, s, rc, Wk.o_rec.p, Wk.o_brank.p, Wk.b_start.p, Wk.o_border.p, Wk.b_cnt.p);
                 }
 #define LO_ARGS R.isA, rc, oblk ? Wk.o_border.p : (const int32_t *)nullptr, A->pos32.p, A->next.p, hyp ? A->fpos32.p : (const int32_t *)nullptr, hyp ? A->flast.p : (const int32_t *)nullptr,            \
                 Wk.o_tileS.p, Wk.o_tileS2.p, Wk.o_rec.p, W, M, alpha
@@ -3030,13 +3160,15 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
 #undef LO_ARGS
             }
             note(rd, 0, gap ? PROF_GAPSTREAM : PROF_OWN);
-            {
-                ProfScope ps(PROF_CARRY, s, 12.0 * (double)P.NT);
-                const int32_t *ntp = reinterpret_cast<const int32_t *>(&rc->NT);       // (NT < 2^31: the low word)
-                exclusive_scan_i32_lb(Wk.o_tileS.p, Wk.o_tilePS.p, ntp, (int64_t)Wk.o_tileS.n, nullptr, Wk.scanws, s);
-                if (hyp) exclusive_scan_i32_lb(Wk.o_tileS2.p, Wk.o_tilePS2.p, ntp, (int64_t)Wk.o_tileS.n, nullptr, Wk.scanws, s);
-            }
             if (gap) {
+                {
+                    // the gap kernels look a tile's prefix up at random: a device-wide scan of the tile counts.  (The other rounds need
+                    // sums inside one task only: k_fix_own_lane / k_fix_own make them from o_tileS.)
+                    ProfScope ps(PROF_CARRY, s, 12.0 * (double)P.NT);
+                    const int32_t *ntp = reinterpret_cast<const int32_t *>(&rc->NT);       // (NT < 2^31: the low word)
+                    exclusive_scan_i32_lb(Wk.o_tileS.p, Wk.o_tilePS.p, ntp, (int64_t)Wk.o_tileS.n, nullptr, Wk.scanws, s);
+                    if (hyp) exclusive_scan_i32_lb(Wk.o_tileS2.p, Wk.o_tilePS2.p, ntp, (int64_t)Wk.o_tileS.n, nullptr, Wk.scanws, s);
+                }
                 // every row of the gaps gets its winner: one wave per (task, 64 rows); tasks of more than GAPSEG tiles in two steps
                 ProfScope ps(PROF_GAP, s, 24.0 * (double)P.NT);
                 const int nchunk = (int)std::max<int64_t>(1, ((int64_t)2 << R.tau) / 64);
@@ -3055,26 +3187,22 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
                 else launch_gap<TC, false>(s, A, Wk, R.tau, nchunk, gnr, rc, n, W, M, alpha, gg, gs_grid, gm, gslow_grid, oblk);
             } else {
                 ProfScope ps(PROF_FIX, s, 24.0 * (double)P.NT);
-                // one lane per task: single tiles are final already, short tasks are merged on the spot, the rest is listed
-                const bool wide = true;                          // one block per listed task (the longest task sets the pace)
-                unsigned lgrid = (unsigned)std::min<int64_t>(cdiv(gown, 256), 4096), wgrid = (unsigned)std::min<int64_t>(wide ? gown : cdiv(gown, 4), 8192);
+                // one lane per task: single tiles are final already, short tasks are merged on the spot, the rest is listed and
+                // merged by one block per task
+                unsigned lgrid = (unsigned)std::min<int64_t>(cdiv(gown, 256), 4096), wgrid = (unsigned)std::min<int64_t>(gown, 8192);
 #define FO_ARGS rc, Wk.o_toffs.p
 #define FO_TAIL Wk.o_tdesc.p, Wk.o_tb.p
                 if (hyp) {
                     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fix_own_lane<TC, true>), dim3(lgrid), dim3(256), 0, s, FO_ARGS, Wk.o_part.p, FO_TAIL, Wk.o_tS0l.p,
-                                       Wk.o_tilePS.p, Wk.o_tilePS2.p, M, Wk.opt.p, Wk.nnopt.p, Wk.nlopt.p, n + 1, Wk.o_wide.p);
-                    if (wide) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fix_own<TC, true, 4>), dim3(wgrid), dim3(256), 0, s, FO_ARGS, Wk.o_part.p, FO_TAIL,
-                                                 Wk.o_tS0l.p, Wk.o_tilePS.p, Wk.o_tilePS2.p, M, Wk.opt.p, Wk.nnopt.p, Wk.nlopt.p, n + 1, Wk.o_wide.p);
-                    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fix_own<TC, true, 1>), dim3(wgrid), dim3(256), 0, s, FO_ARGS, Wk.o_part.p,
-                                            FO_TAIL, Wk.o_tS0l.p, Wk.o_tilePS.p, Wk.o_tilePS2.p, M, Wk.opt.p, Wk.nnopt.p, Wk.nlopt.p, n + 1, Wk.o_wide.p);
+                                       Wk.o_tileS.p, Wk.o_tileS2.p, M, Wk.opt.p, Wk.nnopt.p, Wk.nlopt.p, n + 1, Wk.o_wide.p);
+                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fix_own<TC, true>), dim3(wgrid), dim3(256), 0, s, FO_ARGS, Wk.o_part.p, FO_TAIL,
+                                       Wk.o_tS0l.p, Wk.o_tileS.p, Wk.o_tileS2.p, M, Wk.opt.p, Wk.nnopt.p, Wk.nlopt.p, n + 1, Wk.o_wide.p);
                 } else {
                     const Best<TC, false> *pp = reinterpret_cast<const Best<TC, false> *>(Wk.o_part.p);
                     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fix_own_lane<TC, false>), dim3(lgrid), dim3(256), 0, s, FO_ARGS, pp, FO_TAIL, (const int32_t *)nullptr,
-                                       Wk.o_tilePS.p, (const int64_t *)nullptr, M, Wk.opt.p, Wk.nnopt.p, (int32_t *)nullptr, n + 1, Wk.o_wide.p);
-                    if (wide) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fix_own<TC, false, 4>), dim3(wgrid), dim3(256), 0, s, FO_ARGS, pp, FO_TAIL,
-                                                 (const int32_t *)nullptr, Wk.o_tilePS.p, (const int64_t *)nullptr, M, Wk.opt.p, Wk.nnopt.p, (int32_t *)nullptr, n + 1, Wk.o_wide.p);
-                    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fix_own<TC, false, 1>), dim3(wgrid), dim3(256), 0, s, FO_ARGS, pp, FO_TAIL,
-                                            (const int32_t *)nullptr, Wk.o_tilePS.p, (const int64_t *)nullptr, M, Wk.opt.p, Wk.nnopt.p, (int32_t *)nullptr, n + 1, Wk.o_wide.p);
+                                       Wk.o_tileS.p, (const int32_t *)nullptr, M, Wk.opt.p, Wk.nnopt.p, (int32_t *)nullptr, n + 1, Wk.o_wide.p);
+                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fix_own<TC, false>), dim3(wgrid), dim3(256), 0, s, FO_ARGS, pp, FO_TAIL,
+                                       (const int32_t *)nullptr, Wk.o_tileS.p, (const int32_t *)nullptr, M, Wk.opt.p, Wk.nnopt.p, (int32_t *)nullptr, n + 1, Wk.o_wide.p);
                 }
 #undef FO_ARGS
 #undef FO_TAIL
@@ -3220,6 +3348,8 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
         g_poison_hits += pz_hits[0];
         CP_REQUIRE(!(ok && pz_hits[0] > 0), CP_EINTERNAL, "a DP layer that is not redone read plane cells nobody wrote (poison mode)");
     }
+    if (ok) Wk.b_dirty = false;
+    if (ok) for (int rd = 0; rd < NR; rd++) { g_fix_trips += got[(size_t)rd].n_trips; g_fix_edges |= got[(size_t)rd].n_edge; }
     if (ok) {
         for (auto &pt : patches) {
             const RoundCounts &g = got[(size_t)pt.rd];

@@ -240,8 +240,18 @@ int32_t cp_reset_stream(cp_csr_t csr);
 /* diagnostics counters of the library (tests): "spec_redo" -- DP layers enqueued from the previous layer's counts that had to be
  * run again with exact counts; "poison_hits" -- with cp_set_option("poison", 1): plane cells read that the layer had not written
  * (each such layer must be one of the redone ones; the library checks it and fails with CP_EINTERNAL otherwise).  Both are reset
- * when "poison" is switched on. */
+ * when "poison" is switched on.  "fix_trips" -- own-tiled DP tasks whose block merge took more than one trip; "fix_edges" -- bits
+ * 0 / 1 / 2: a task of 1 / 16 / 17 tiles was merged (both sides of the lane / block split); both count the layers that stand, not
+ * attempts that were redone.  All four are reset when "poison" is switched on and by cp_set_option("stat_reset", 1); reading
+ * changes nothing. */
 int32_t cp_get_stat(const char *name, int64_t *out);
+/* Test entry: the launch that ends the counting phase of a DP round, on host arrays.  Exclusive scans of a[0 .. na) and (two != 0)
+ * b[0 .. nb) in ONE launch whose grid is sized for na_max >= na / nb_max >= nb elements while the counts are read on the device;
+ * then the round's verdict: totals beyond cap_t / cap_nt, or err_in != 0, drop the round.  reps >= 1 launches in a row on one
+ * workspace.  offs_out: na + 1 values (the last: the total), toffs_out: nb + 1; res: {T, NT, nlong, nown, ntile = ceil(T / 256), err}
+ * as the round's later kernels read them -- after a dropped round {0, 0, 0, 0, 0, 1}. */
+int32_t cp_test_round_scans(const int32_t *a, int64_t na, int64_t na_max, const int32_t *b, int64_t nb, int64_t nb_max, int32_t two,
+                            int64_t cap_t, int64_t cap_nt, int32_t err_in, int32_t reps, int64_t *offs_out, int64_t *toffs_out, int64_t *res);
 /* Library-wide tunables and test switches; results never depend on them (tests/test_gpu_dynamic.py runs every one against the
  * oracle).  "force_brute" 1: the general O(K n^2) device DP even where the O(K n log^2 n) scheme applies; "brute_max_n": its size
  * limit.  Layer driver of the O(K n log^2 n) scheme: "short_t"/"short_e" (tasks finished during setup),
