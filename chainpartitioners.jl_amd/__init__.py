@@ -8,6 +8,7 @@ from .types import *          # noqa: F401,F403
 from .types import to_map, to_domain   # noqa: F401
 from .models import (PowerWorkModel, ConvexWorkModel, ConcaveWorkModel,   # noqa: F401
                      AffineWorkModel, AffinePrimaryConnectivityModel, AffineSecondaryConnectivityModel, AffineConnectivityModel, AffineHyperedgeCutModel,      # noqa: F401
+                     AffineSymmetricConnectivityModel, AffineMonotonizedSymmetricConnectivityModel, AffineSymmetricEdgeCutModel,
                      ColumnBlockComponentCostModel, BlockComponentCostModel, VertexCount, FeasibleCost,
                      ConstrainedCost, EquiSplitter, EquiChunker, DynamicTotalSplitter,
                      DynamicBottleneckSplitter, DynamicTotalChunker, DynamicBottleneckChunker,
@@ -19,5 +20,5 @@ from .models import (PowerWorkModel, ConvexWorkModel, ConcaveWorkModel,   # noqa
                      ConvexTotalChunker, ConvexTotalSplitter, ConcaveTotalChunker, ConcaveTotalSplitter)
 from . import _lib  # noqa: F401
 from .api import (adjointpattern, partition_plaid, partition_stripe, partition_stripe_batch, pack_stripe, pack_stripe_batch, pack_stripe_tables, oracle_stripe, bound_stripe, total_value,   # noqa: F401
-                  bottleneck_value, netcount, selfnetcount, dominancecount, set_default_backend,
+                  bottleneck_value, netcount, selfnetcount, dominancecount, dianetcount, selfpincount, set_default_backend,
                   get_backend, CPError, Step, Same, Next, Prev, Jump)

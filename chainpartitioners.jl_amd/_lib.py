@@ -23,7 +23,7 @@ SYMBOLS = [
     "cp_partition_bisect_cost", "cp_partition_bisect_cost_batch", "cp_pack_convex", "cp_pack_convex_batch", "cp_partition_convex", "cp_partition_equi", "cp_pack_equi",
     "cp_dynamic_tables", "cp_dynamic_tables_constrained", "cp_dynamic_tables_constrained_combine", "cp_set_stream", "cp_reset_stream", "cp_get_stat", "cp_test_round_scans", "cp_set_option", "cp_prof_enable", "cp_prof_reset", "cp_prof_get",
     "cp_dp_begin", "cp_dp_layer", "cp_dp_ptr_at", "cp_dp_destroy", "cp_dp_ptr_row", "cp_dp_block_tables", "cp_dp_set_window", "cp_dp_set_rows",
-    "cp_partition_bisect_index", "cp_partition_lazy_bisect_cost", "cp_pack_concave", "cp_partition_concave",
+    "cp_partition_bisect_index", "cp_partition_lazy_bisect_cost", "cp_partition_lazy_bisect_cost_probes", "cp_pack_concave", "cp_partition_concave",
     "cp_adjoint", "cp_csr_download", "cp_bound_stripe_pi", "cp_partition_bisect_cost_pi", "cp_partition_bisect_index_pi",
 ]
 
@@ -49,7 +49,7 @@ def _i64(x):
     return C.c_int64(int(x))
 
 
-_COUNT_KIND = {"dom": 0, "net": 1, "selfnet": 2}
+_COUNT_KIND = {"dom": 0, "net": 1, "selfnet": 2, "dianet": 3, "selfpin": 4}
 
 
 class HipBackend:
@@ -204,6 +204,13 @@ class HipBackend:
     def partition_lazy_bisect_cost(self, A, K, mm, eps, spl):
         return self.lib.cp_partition_lazy_bisect_cost(self._h(A), _i64(K), mm.ptr, C.c_double(eps), _p(spl))
 
+    def partition_lazy_bisect_cost_probes(self, A, K, mm, eps):
+        """(rc, spl, number of probes the bisection ran)"""
+        spl = np.zeros(K + 1, dtype=np.int64)
+        npr = C.c_int64()
+        rc = self.lib.cp_partition_lazy_bisect_cost_probes(self._h(A), _i64(K), mm.ptr, C.c_double(eps), _p(spl), C.byref(npr))
+        return rc, spl, npr.value
+
     def pack_convex(self, A, mm, rp, wm, wi, wf, spl, Kout):
         return self.lib.cp_pack_convex(self._h(A), mm.ptr, C.byref(rp) if rp is not None else None,
                                        wm.ptr if wm is not None else None, _i64(wi), C.c_double(wf), _p(spl), _p(Kout))
@@ -290,6 +297,8 @@ class HipBackend:
         h = C.c_void_p()
         rc = self.lib.cp_count_build(self._h(A), C.c_int32(_COUNT_KIND[kind]), C.c_int32(hint), C.byref(h))
         if rc != 0:
+            if rc == M.CP_EINVAL and kind in ("dianet", "selfpin"):      # the reference asserts m == n
+                raise AssertionError(f"cp_count_build({kind}): violated precondition ({self.last_error()})")
             raise NotImplementedError(f"cp_count_build({kind}) -> {rc}: {self.last_error()}")
         return h
 

@@ -89,6 +89,13 @@ def _w_table_for(A, f, weight, w_max, stack_method=False):
     return (-(A.n + 1), A.n + 1) if stack_method else (0, A.n + 1)
 
 
+def _need_hip(b, mdl):
+    """The symmetric cost family exists on the HIP backend only (the CPU test oracle does not know these kinds)."""
+    if getattr(mdl, "symmetric", False) and getattr(b, "name", "") != "hip":
+        raise NotImplementedError(f"{type(mdl).__name__} is implemented by the HIP backend only, not by backend "
+                                  f"'{getattr(b, 'name', type(b).__name__)}'")
+
+
 def _marshal(A, f, Pi, stack_method=False):
     mdl, weight, w_max = M.split_constraint(f)
     wlo, wt = _w_table_for(A, mdl, weight, w_max, stack_method)
@@ -124,6 +131,8 @@ def partition_stripe(A: SparseMatrixCSC, K, method, Pi=None, *, backend=None) ->
         k = np.arange(0, K + 1, dtype=np.int64)
         return SplitPartition(K, k * (n // K) + np.minimum(n % K, k) + 1)
     b = get_backend(backend)
+    if hasattr(method, "f"):
+        _need_hip(b, M.split_constraint(method.f)[0])
     if isinstance(method, (M.DynamicTotalSplitter, M.DynamicBottleneckSplitter,
                            M.DynamicTotalChunker, M.DynamicBottleneckChunker)):
         mdl, mm, wm, wi, wf, rp, keep = _marshal(A, method.f, Pi)
@@ -178,6 +187,9 @@ def partition_stripe_batch(A: SparseMatrixCSC, requests, *, backend=None):
     b = get_backend(backend)
     if not requests:
         return []
+    for _, m in requests:
+        if hasattr(m, "f"):
+            _need_hip(b, M.split_constraint(m.f)[0])
     if not all(isinstance(m, M.BisectCostBottleneckSplitter) for _, m in requests):
         raise NotImplementedError("partition_stripe_batch takes BisectCostBottleneckSplitter requests")
     if not hasattr(b, "partition_bisect_cost_batch"):
@@ -200,6 +212,9 @@ def pack_stripe_batch(A: SparseMatrixCSC, methods, *, backend=None):
     b = get_backend(backend)
     if not methods:
         return []
+    for m in methods:
+        if hasattr(m, "f"):
+            _need_hip(b, M.split_constraint(m.f)[0])
     ok = all(isinstance(m, M.ConvexTotalChunker) and isinstance(M.split_constraint(m.f)[1], M.VertexCount) for m in methods)
     if not ok:
         raise NotImplementedError("pack_stripe_batch takes ConvexTotalChunker(ConstrainedCost(f, VertexCount(), w)) requests")
@@ -221,6 +236,8 @@ def pack_stripe(A: SparseMatrixCSC, method, Pi=None, *, backend=None) -> SplitPa
         spl = np.concatenate([np.arange(1, n + 1, w, dtype=np.int64), [n + 1]])   # [1:w:n; n+1]
         return SplitPartition(len(spl) - 1, spl)
     b = get_backend(backend)
+    if hasattr(method, "f"):
+        _need_hip(b, M.split_constraint(method.f)[0])
     if isinstance(method, M.DynamicTotalChunker):
         mdl, mm, wm, wi, wf, rp, keep = _marshal(A, method.f, Pi)
         spl = np.zeros(A.n + 1, dtype=np.int64)
@@ -252,6 +269,7 @@ def pack_stripe_tables(A: SparseMatrixCSC, method, Pi=None, *, backend=None):
     if not isinstance(method, M.DynamicTotalChunker):
         raise NotImplementedError(f"pack_stripe_tables: method {type(method).__name__} is not a DynamicTotalChunker")
     b = get_backend(backend)
+    _need_hip(b, M.split_constraint(method.f)[0])
     if not hasattr(b, "pack_dynamic_tables"):
         raise NotImplementedError(f"pack_stripe_tables: backend {b.name} has no tables")
     mdl, mm, wm, wi, wf, rp, keep = _marshal(A, method.f, Pi)
@@ -265,6 +283,7 @@ class Oracle:
     """Callable cost oracle ocl(j, j', k...) (vectorised over arrays of queries)."""
 
     def __init__(self, hint, mdl, A, Pi, backend):
+        _need_hip(backend, mdl)
         self.hint, self.mdl, self.A, self.Pi, self.backend = hint, mdl, A, Pi, backend
 
     def __call__(self, j, jp, k=None):
@@ -339,6 +358,7 @@ def oracle_stripe(hint, mdl, A, Pi=None, *, backend=None) -> Oracle:
 def bound_stripe(A, K, mdl, Pi=None, *, backend=None):
     """bound_stripe(A, K, [Pi], mdl): Pi only matters to the secondary connectivity model (Costs.jl:17-19)."""
     b = get_backend(backend)
+    _need_hip(b, mdl)
     mm = mdl.marshal(w_table=A.n + 1)
     if Pi is not None and isinstance(mdl, M.AffineSecondaryConnectivityModel):
         rp, keep = _rowpart(Pi)
@@ -353,6 +373,7 @@ def _objective(g, A, Phi, mdl, Pi, backend):
     b = get_backend(backend)
     if not isinstance(Phi, SplitPartition):
         raise NotImplementedError("scoring of non-contiguous partitions is outside the hot path")
+    _need_hip(b, mdl)
     _, mm, _, _, _, rp, keep = _marshal(A, mdl, Pi)
     rc, v = b.objective(A, Phi.K, np.ascontiguousarray(Phi.spl, dtype=np.int64), mm, rp, g)
     _check(rc, "objective", b)
@@ -446,3 +467,20 @@ def selfnetcount(A, hint=None, *, backend=None):
 def dominancecount(A, hint=None, *, backend=None):
     """dominancecount(hint, A)  SparsePrefixMatrices.jl:438-446 : C[i, j] = #{nonzeros row < i, col < j}"""
     return CountMatrix("dom", A, hint or NoHint(), get_backend(backend))
+
+
+def _sym_count(kind, A, hint, backend):
+    b = get_backend(backend)
+    if getattr(b, "name", "") != "hip":
+        raise NotImplementedError(f"{kind}count is implemented by the HIP backend only")
+    return CountMatrix(kind, A, hint or NoHint(), b)
+
+
+def dianetcount(A, hint=None, *, backend=None):
+    """dianetcount(hint, A)  SparseColorArrays.jl:65-99 : D[j, j'] = #(rows of A[:, j:j'-1] united with j:j'-1); square A"""
+    return _sym_count("dianet", A, hint, backend)
+
+
+def selfpincount(A, hint=None, *, backend=None):
+    """selfpincount(hint, A)  SparseColorArrays.jl:268-318 : S[j, j'] = nnz(A[j:j'-1, j:j'-1]); square A"""
+    return _sym_count("selfpin", A, hint, backend)

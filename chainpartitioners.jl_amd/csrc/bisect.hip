@@ -13,6 +13,7 @@
 #include "csr.hpp"
 #include "model.hpp"
 #include "wavelet.hpp"
+#include "sym.hpp"
 
 namespace cpk {
 
@@ -50,6 +51,14 @@ struct OracleDev {
     const int64_t *spl, *tpos;            // secondary: the row split (1-based) and the row pointer of A (0-based)
 };
 
+// the symmetric cost family (sym.hpp): an oracle type of its own, so the kernels of the other models are instantiated unchanged
+template <typename TC>
+struct SymOracleDev {
+    DevModel<TC> M;
+    int64_t n;
+    SymDev S;
+};
+
 // PartwiseCount rank: pios[k] + searchsortedfirst(prm[pios[k] : pios[k+1]-1], j) - 1   (PartwiseCounts.jl:86-88)
 template <typename TC>
 __device__ __forceinline__ int64_t pw_rank(const OracleDev<TC> &O, int64_t j, int64_t k)
@@ -82,8 +91,14 @@ __device__ __forceinline__ TC oracle_eval_dev(const OracleDev<TC> &O, int64_t j,
     return dm_apply(O.M, dm_alpha(O.M, k), r - p, np, nn, (int64_t)0);
 }
 
-template <typename TC, typename CT>
-__device__ int64_t search6(const OracleDev<TC> &O, int64_t j, int64_t lo, int64_t hi, int64_t k, CT c, int flip, int lane)
+template <typename TC>
+__device__ __forceinline__ TC oracle_eval_dev(const SymOracleDev<TC> &O, int64_t j, int64_t jp, int64_t k)
+{
+    return sym_eval<TC>(O.S, O.M, dm_alpha(O.M, k), j - 1, jp - 1);
+}
+
+template <typename OD, typename CT>
+__device__ int64_t search6(const OD &O, int64_t j, int64_t lo, int64_t hi, int64_t k, CT c, int flip, int lane)
 {
     if (lo < j) lo = j;                                   // j'_lo = max(j, j'_lo)  (:17)
     while (lo <= hi) {
@@ -117,8 +132,8 @@ __device__ int64_t search6(const OracleDev<TC> &O, int64_t j, int64_t lo, int64_
     return flip ? lo : hi;
 }
 
-template <typename TC>
-__device__ __forceinline__ void bisect_cost_body(const OracleDev<TC> &O, int64_t K, double c_lo, double c_hi, double eps, int flip,
+template <typename OD>
+__device__ __forceinline__ void bisect_cost_body(const OD &O, int64_t K, double c_lo, double c_hi, double eps, int flip,
                                                  int64_t *__restrict__ spl_lo, int64_t *__restrict__ spl_hi, int64_t *__restrict__ spl,
                                                  int64_t *__restrict__ out, int64_t *__restrict__ nprobes)
 {
@@ -167,12 +182,12 @@ __device__ __forceinline__ void bisect_cost_body(const OracleDev<TC> &O, int64_t
     if (lane == 0) *nprobes = stuck ? -1 : probes;
 }
 
-template <typename TC>
-__global__ void __launch_bounds__(64) k_bisect(OracleDev<TC> O, int64_t K, double c_lo, double c_hi, double eps, int flip,
+template <typename OD>
+__global__ void __launch_bounds__(64) k_bisect(OD O, int64_t K, double c_lo, double c_hi, double eps, int flip,
                                                int64_t *__restrict__ spl_lo, int64_t *__restrict__ spl_hi, int64_t *__restrict__ spl,
                                                int64_t *__restrict__ out, int64_t *__restrict__ nprobes)
 {
-    bisect_cost_body<TC>(O, K, c_lo, c_hi, eps, flip, spl_lo, spl_hi, spl, out, nprobes);
+    bisect_cost_body<OD>(O, K, c_lo, c_hi, eps, flip, spl_lo, spl_hi, spl, out, nprobes);
 }
 
 // B independent requests (K, model, eps, flip) on ONE pattern, one wave each: the sequential probe chain of a single partition
@@ -187,7 +202,7 @@ __global__ void __launch_bounds__(64) k_bisect_batch(OracleDev<TC> O, const Bise
     const BisectReq<TC> R = req[blockIdx.x];
     O.M = R.M;
     int64_t *w = work + (int64_t)blockIdx.x * 3 * ld;
-    bisect_cost_body<TC>(O, R.K, R.c_lo, R.c_hi, R.eps, R.flip, w, w + ld, w + 2 * ld, out + (int64_t)blockIdx.x * ld, nprobes + blockIdx.x);
+    bisect_cost_body<OracleDev<TC>>(O, R.K, R.c_lo, R.c_hi, R.eps, R.flip, w, w + ld, w + 2 * ld, out + (int64_t)blockIdx.x * ld, nprobes + blockIdx.x);
 }
 
 // ------------------------------------------------------------------ BisectIndexBottleneckSplitter.jl:5-83, flip :85-166
@@ -209,8 +224,8 @@ template <> struct IdxBound<int64_t> {
     __device__ bool c_lt(int64_t c) const { return is_int ? c < i : lt_f64(c, f); }
 };
 
-template <typename TC>
-__global__ void __launch_bounds__(64) k_bisect_index(OracleDev<TC> O, int64_t K, double c_lo0, double c_hi0, int flip,
+template <typename TC, typename OD>
+__global__ void __launch_bounds__(64) k_bisect_index(OD O, int64_t K, double c_lo0, double c_hi0, int flip,
                                                      int64_t *__restrict__ spl_lo, int64_t *__restrict__ spl_hi, int64_t *__restrict__ spl,
                                                      int64_t *__restrict__ out, int64_t *__restrict__ nprobes)
 {
@@ -288,6 +303,10 @@ int32_t run_bisect(cp_csr_s *A, int64_t K, const cp_model_t *mdl, const cp_rowpa
     WaveletHost net, lcn;
     CsrGuard Ap;
     DBuf<int64_t> d_pios, d_prm, d_spl2;
+    SymHost SH;
+    SymOracleDev<TC> OS;
+    const bool sym = model_is_sym(mdl->kind);
+    if (sym) { sym_prepare(A, mdl, SH); memset(&OS, 0, sizeof(OS)); OS.M = HM.d; OS.n = A->n; OS.S = SH.d; }
     if (mdl->kind == CP_MODEL_CONNECTIVITY || mdl->kind == CP_MODEL_PRIMARY) { ensure_net_counter(A, net); O.has_net = 1; O.net = net.d; }
     if (mdl->kind == CP_MODEL_PRIMARY || mdl->kind == CP_MODEL_SECONDARY) {
         bool sec = mdl->kind == CP_MODEL_SECONDARY;
@@ -322,8 +341,10 @@ int32_t run_bisect(cp_csr_s *A, int64_t K, const cp_model_t *mdl, const cp_rowpa
     int64_t *d_lo = buf.p, *d_hi = buf.p + (K + 1), *d_spl = buf.p + 2 * (K + 1), *d_out = buf.p + 3 * (K + 1), *d_np = buf.p + 4 * (K + 1);
     {
         ProfScope ps(PROF_BISECT, s, 0.0);
-        if (by_index) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bisect_index<TC>), dim3(1), dim3(64), 0, s, O, K, c_lo, c_hi, flip, d_lo, d_hi, d_spl, d_out, d_np);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bisect<TC>), dim3(1), dim3(64), 0, s, O, K, c_lo, c_hi, eps, flip, d_lo, d_hi, d_spl, d_out, d_np);
+        if (sym && by_index) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bisect_index<TC, SymOracleDev<TC>>), dim3(1), dim3(64), 0, s, OS, K, c_lo, c_hi, flip, d_lo, d_hi, d_spl, d_out, d_np);
+        else if (sym) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bisect<SymOracleDev<TC>>), dim3(1), dim3(64), 0, s, OS, K, c_lo, c_hi, eps, flip, d_lo, d_hi, d_spl, d_out, d_np);
+        else if (by_index) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bisect_index<TC, OracleDev<TC>>), dim3(1), dim3(64), 0, s, O, K, c_lo, c_hi, flip, d_lo, d_hi, d_spl, d_out, d_np);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bisect<OracleDev<TC>>), dim3(1), dim3(64), 0, s, O, K, c_lo, c_hi, eps, flip, d_lo, d_hi, d_spl, d_out, d_np);
     }
     CP_HIP(hipGetLastError());
     int64_t np_host = 0;

@@ -4,6 +4,7 @@
 #include "model.hpp"
 #include "dp.hpp"
 #include "weight.hpp"
+#include "sym.hpp"
 #include <cmath>
 #include <memory>
 
@@ -72,7 +73,7 @@ static int32_t guarded(F &&f)
 
 static bool model_known(const cp_model_t *m)
 {
-    if (!m || m->kind < CP_MODEL_FEASIBLE || m->kind > CP_MODEL_SECONDARY) return false;
+    if (!m || m->kind < CP_MODEL_FEASIBLE || m->kind > CP_MODEL_SYM_EDGE_CUT) return false;
     if (m->kind == CP_MODEL_POWER_WORK) return m->dtype == CP_F64;
     return m->dtype == CP_I64 || m->dtype == CP_F64;
 }
@@ -235,6 +236,7 @@ int32_t cp_get_stat(const char *name, int64_t *out)
     // tasks the block merge walked in more than one trip; bits 0 / 1 / 2: a task of 1 / FIX_SERIAL / FIX_SERIAL + 1 tiles was merged
     if (!strcmp(name, "fix_trips")) { *out = g_fix_trips; return CP_OK; }
     if (!strcmp(name, "fix_edges")) { *out = g_fix_edges; return CP_OK; }
+    if (!strcmp(name, "bn_sym_layers")) { *out = g_bn_sym_layers; return CP_OK; }      // DP layers the valley search ran for the monotonized symmetric model
     return CP_EINVAL;
 }
 
@@ -268,7 +270,7 @@ int32_t cp_set_option(const char *name, int64_t value)
     if (!strcmp(name, "force_brute")) { g_opt_force_brute = value; return CP_OK; }
     if (!strcmp(name, "brute_max_n")) { g_opt_brute_max_n = value; return CP_OK; }
     if (!strcmp(name, "dbg")) { g_opt_dbg = value; return CP_OK; }
-    if (!strcmp(name, "stat_reset")) { g_poison_hits = 0; g_spec_redo = 0; g_fix_trips = 0; g_fix_edges = 0; return CP_OK; }      // the counters of cp_get_stat
+    if (!strcmp(name, "stat_reset")) { g_poison_hits = 0; g_spec_redo = 0; g_fix_trips = 0; g_fix_edges = 0; g_bn_sym_layers = 0; return CP_OK; }      // the counters of cp_get_stat
     if (!strcmp(name, "short_t")) { g_opt_short_t = value; return CP_OK; }
     if (!strcmp(name, "short_e")) { g_opt_short_e = value; return CP_OK; }
     if (!strcmp(name, "rpass_ch")) { int64_t v = 16; while (v < value && v < 4096) v <<= 1; g_opt_rpass_ch = v; return CP_OK; }
@@ -345,6 +347,8 @@ int32_t cp_partition_dynamic(cp_csr_t A, int64_t K, int32_t combine, int32_t ord
             CP_REQUIRE(!constrained, CP_EUNSUPPORTED, "ConstrainedCost over a plaid connectivity model has no device path");
             return with_cost_type(model->dtype, [&](auto tag) { return run_plaid_dynamic<decltype(tag)>(A, K, combine, order, model, Pi, spl_out); });
         }
+        // the symmetric family: the O(n^2) sweep over the wavelet counters (dp_driver.hip); no constrained form
+        CP_REQUIRE(!(constrained && model_is_sym(model->kind)), CP_EUNSUPPORTED, "ConstrainedCost over a symmetric cost model has no device path");
         if (constrained) {
             CP_REQUIRE(weight->kind == CP_MODEL_VERTEX_COUNT || (weight->kind == CP_MODEL_WORK && !weight->alpha_k), CP_EINVAL,
                        "weight must be VertexCount or an AffineWorkModel");
@@ -360,7 +364,7 @@ int32_t cp_partition_dynamic(cp_csr_t A, int64_t K, int32_t combine, int32_t ord
             });
         }
         CP_REQUIRE(model->kind == CP_MODEL_WORK || model->kind == CP_MODEL_CONNECTIVITY || model->kind == CP_MODEL_HYPEREDGE_CUT ||
-                       model->kind == CP_MODEL_COLBLOCK || model->kind == CP_MODEL_POWER_WORK,
+                       model->kind == CP_MODEL_COLBLOCK || model->kind == CP_MODEL_POWER_WORK || model_is_sym(model->kind),
                    CP_EUNSUPPORTED, "model kind has no device DP path yet");
         return run_dynamic(A, K, combine, order, model, spl_out, nullptr, nullptr, nullptr);
     });
@@ -374,7 +378,7 @@ int32_t cp_dynamic_tables(cp_csr_t A, int64_t K, int32_t combine, const cp_model
         CP_REQUIRE(A && ptr_out && model_known(model) && K >= 1, CP_EINVAL, "bad argument");
         CP_REQUIRE(combine == CP_COMBINE_SUM || combine == CP_COMBINE_MAX, CP_EINVAL, "bad combine");
         CP_REQUIRE(model->kind == CP_MODEL_WORK || model->kind == CP_MODEL_CONNECTIVITY || model->kind == CP_MODEL_HYPEREDGE_CUT ||
-                       model->kind == CP_MODEL_COLBLOCK || model->kind == CP_MODEL_POWER_WORK,
+                       model->kind == CP_MODEL_COLBLOCK || model->kind == CP_MODEL_POWER_WORK || model_is_sym(model->kind),
                    CP_EUNSUPPORTED, "model kind has no device DP path");
         CP_HIP(hipSetDevice(A->device));
         std::vector<int64_t> spl((size_t)K + 1);
@@ -420,6 +424,7 @@ int32_t cp_oracle_eval(cp_csr_t A, const cp_model_t *model, const cp_rowpart_t *
             if (model->kind == CP_MODEL_PRIMARY || model->kind == CP_MODEL_SECONDARY) return run_plaid_eval<TC>(A, model, Pi, nq, j, jp, k, out);
             // stateful step oracle: evaluated in query order by one wave (seq.hip)
             if (model->kind == CP_MODEL_BLOCK) return run_seq_eval<TC>(A, model, Pi, nq, j, jp, k, out);
+            if (model_is_sym(model->kind)) return run_sym_eval<TC>(A, model, nq, j, jp, k, out);
             return run_oracle_eval<TC>(A, model, nq, j, jp, k, out);
         });
     });
@@ -516,8 +521,15 @@ int32_t cp_bound_stripe(cp_csr_t A, int64_t K, const cp_model_t *model, int64_t 
             else c.p_f64[CP_P_NET] = std::min(model->p_f64[3], model->p_f64[4]);
             return cp_bound_stripe(A, K, &c, lo_i64, &dh, lo_f64, &dg);
         }
-        if (model->kind == CP_MODEL_CONNECTIVITY && model->alpha_k && model->n_alpha_k > 0) {
-            // per-part alpha = the reference tests' FunkyConnectivityModel; its bound_stripe (test_Partitioners.jl:36-41) is
+        if (model->kind == CP_MODEL_MONO_SYM_CONNECTIVITY) {                           // MonotonizedSymmetricConnectivityCosts.jl:50-66
+            bool neg = model->dtype == CP_I64 ? (model->p_i64[1] < 0 || model->p_i64[2] < 0 || model->p_i64[3] < 0)
+                                              : !(model->p_f64[1] >= 0 && model->p_f64[2] >= 0 && model->p_f64[3] >= 0);
+            CP_REQUIRE(A->m == A->n, CP_EINVAL, "bound_stripe asserts m == n");
+            CP_REQUIRE(!neg, CP_EINVAL, "bound_stripe asserts beta >= 0");
+        }
+        if ((model->kind == CP_MODEL_CONNECTIVITY || model->kind == CP_MODEL_MONO_SYM_CONNECTIVITY) && model->alpha_k && model->n_alpha_k > 0) {
+            // per-part alpha = the reference tests' FunkyConnectivityModel / FunkyMonotonizedSymmetricConnectivityModel; its
+            // bound_stripe (test_Partitioners.jl:36-41) is
             // (minimum, maximum) of (minimum(alpha), maximum(alpha), maximum_k ocl(1, n+1, k))
             CP_REQUIRE(model->n_alpha_k >= K, CP_EINVAL, "bound_stripe: fewer per-part alphas than parts");
             std::vector<int64_t> one((size_t)K, 1), np1((size_t)K, n + 1), ks((size_t)K);
@@ -557,6 +569,23 @@ int32_t cp_bound_stripe(cp_csr_t A, int64_t K, const cp_model_t *model, int64_t 
                 int32_t rc = cp_oracle_eval(A, model, nullptr, CP_HINT_STEP, 1, &one, &np1, nullptr, nullptr, &chi);
                 if (rc != CP_OK) return rc;
                 *hi_f64 = chi; *lo_f64 = model->p_f64[0] + std::floor((chi - model->p_f64[0]) / (double)K);
+            }
+            return CP_OK;
+        }
+        if (model->kind == CP_MODEL_MONO_SYM_CONNECTIVITY) {
+            // the model form: c_hi = alpha + b_vertex*n + b_over_pin*sum(max(deg - Delta_pins, 0)) + b_dia_net*m, left to right
+            SymHost H;
+            CP_HIP(hipSetDevice(A->device));
+            sym_prepare(A, model, H, false);
+            if (model->dtype == CP_I64) {
+                const int64_t *p = model->p_i64;
+                int64_t chi = cadd(cadd(cadd(p[0], cmulc(n, p[CP_P_VERTEX])), cmulc(H.over_total, p[CP_P_OVER_PIN])), cmulc(A->m, p[CP_P_DIA_NET]));
+                *hi_i64 = chi; *lo_i64 = p[0] + fld_i64(chi - p[0], K);
+                *lo_f64 = (double)*lo_i64; *hi_f64 = (double)*hi_i64;
+            } else {
+                const double *p = model->p_f64;
+                double chi = cadd(cadd(cadd(p[0], cmulc(n, p[CP_P_VERTEX])), cmulc(H.over_total, p[CP_P_OVER_PIN])), cmulc(A->m, p[CP_P_DIA_NET]));
+                *hi_f64 = chi; *lo_f64 = p[0] + std::floor((chi - p[0]) / (double)K);
             }
             return CP_OK;
         }

@@ -37,10 +37,15 @@ struct cp_csr_s {
     void *bn_work = nullptr;
     void (*bn_work_free_fn)(void *) = nullptr;
     void (*bn_work_reset_fn)(void *) = nullptr;
+    // the derived pattern D and the dianet / selfpin counters of the symmetric cost family: sym.hpp
+    void *sym_work = nullptr;
+    void (*sym_work_free_fn)(void *) = nullptr;
+    void (*sym_work_reset_fn)(void *) = nullptr;
     ~cp_csr_s()
     {
         for (int i = 0; i < 2; i++) if (dp_work[i] && dp_work_free_fn[i]) dp_work_free_fn[i](dp_work[i]);
         if (bn_work && bn_work_free_fn) bn_work_free_fn(bn_work);
+        if (sym_work && sym_work_free_fn) sym_work_free_fn(sym_work);
         if (own_stream && stream) (void)hipStreamDestroy(stream);      // (also on the error paths of the create entry points)
     }
 };
@@ -52,4 +57,5 @@ void ensure_self(cp_csr_s *A);
 void drop_cache(cp_csr_s *A);
 void csr_adjoint(cp_csr_s *A, cp_csr_s *T);                                 // T: fresh handle (device / stream set by the caller)
 void csr_download(cp_csr_s *A, int64_t *colptr, int64_t *rowval);
+__global__ void k_narrow(const int64_t *__restrict__ in, int32_t *__restrict__ out, int64_t n);      // core.hip: out[i] = (int32_t)in[i]
 }  // namespace cpk

@@ -58,13 +58,24 @@ template <typename TC>
 void dp_brute_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, int32_t combine, const TC *W, TC *cst_out,
                     int32_t *ptr_out, int64_t r_lo, int64_t r_hi);
 
+// a pattern other than A's own for the valley search: column pointer, link arrays and net counter of the derived pattern D of
+// sym.hpp, and the prefix array the pin count is read from (the monotonized symmetric model)
+struct WaveletDev;
+struct BnPattern {
+    const int64_t *pos; const int32_t *pos32, *pin32, *prev, *next;
+    int64_t N;
+    const WaveletDev *net;
+};
+extern int64_t g_bn_sym_layers;                // layers the valley search ran over such a pattern (cp_get_stat("bn_sym_layers"))
+
 // one layer of the bottleneck (g = max) DP for costs that grow with their part, by the valley search (dp_bottleneck.hip)
 template <typename TC>
 void dp_bottleneck_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W, TC *cst_out, int32_t *ptr_out,
                          int64_t r_lo, int64_t r_hi,
                          // candidate limits of a weight-constrained layer (0-based; defaults: none): row r takes max(p_lo0, j0(r)) <= p <= min(r, p_hi0),
                          // j0(r) = r - wwin, or j0[r] when the device array j0 (n + 1 entries) is given
-                         int64_t wwin = 0, int64_t p_lo0 = 0, int64_t p_hi0 = -1, const int32_t *j0 = nullptr);
+                         int64_t wwin = 0, int64_t p_lo0 = 0, int64_t p_hi0 = -1, const int32_t *j0 = nullptr,
+                         const BnPattern *pat = nullptr);      // null: A's own links, counter and pins
 extern int64_t g_opt_bn_wave, g_opt_bn_run, g_opt_bn_slack;    // wave-per-run walk (default) and its rows per wave
 extern int64_t g_opt_bn_chunk;                 // rows per two-pointer walk (one lane each)
 
@@ -91,7 +102,6 @@ bool pack_dynamic_scan(hipStream_t s, int64_t n, int64_t wmax, const TC *Ftab, T
 // chunk_lws.hip: DynamicTotalChunker for any width or monotone work budget as an on-line divide and conquer; lws_ok: the gate
 // (cp_set_option("lws", 0) restores the one-wave kernel); run_pack_lws fills the 1-based tables of k_pack_dynamic (spl1 zeroed)
 extern int64_t g_opt_lws, g_opt_lws_leaf;      // on / rows per leaf wave (256, 512, 1024 or 2048)
-struct WaveletDev;
 bool lws_ok(const cp_csr_s *A, const cp_model_t *mdl, const cp_model_t *w, int64_t wi, double wf);
 template <typename TC>
 int32_t run_pack_lws(cp_csr_s *A, const DevModel<TC> &M, const WaveletDev &wnet, const WaveletDev &wself, const cp_model_t *w, int64_t wi,

@@ -52,6 +52,7 @@ struct BnCtx {
     const int32_t *j0;
     const int64_t *pos, *lpos;
     const int32_t *pos32, *prev, *next, *fpos32, *flast, *lpos32, *lfirst;
+    const int32_t *pin32;                // the prefix the pin count of bn_cost comes from: pos32, or overpos for the symmetric model
     WaveletDev net, self;
     const TC *W;
 };
@@ -59,7 +60,7 @@ struct BnCtx {
 template <typename TC>
 __device__ __forceinline__ TC bn_cost(const BnCtx<TC> &C, int64_t p, int64_t r, int64_t nn, int64_t nl)
 {
-    return dm_apply(C.M, C.alpha, r - p, (int64_t)(C.pos32[r] - C.pos32[p]), nn, nl);
+    return dm_apply(C.M, C.alpha, r - p, (int64_t)(C.pin32[r] - C.pin32[p]), nn, nl);
 }
 
 // runend[p] = last index of the run of equal values of W through p (W is non-decreasing: runs are contiguous)
@@ -736,11 +737,12 @@ static BnWork *bn_work_get(cp_csr_s *A)
 int64_t g_opt_bn_chunk = 8;       // lane-per-chunk walk (bn_wave 0): rows per lane (config 3 matrix, K = 64: 8 rows 0.50 s, 32 rows 0.58 s, 128 rows 0.97 s, 256 rows 1.32 s per partition)
 int64_t g_opt_bn_wave = 2;        // 0: lane per chunk (k_bn_walk); 1: wave per run, lockstep (k_bn_walk64); 2: wave per run, searched crossings for Int64 costs (k_bn_walk_vec)
 int64_t g_opt_bn_slack = 64;      // hinted starts of the wave walks: columns left of the predicted crossing
+int64_t g_bn_sym_layers = 0;
 int64_t g_opt_bn_run = 253;       // ... rows per wave (1 + 63 m: m sub-runs of 64 rows sharing their end rows)
 
 template <typename TC>
 void dp_bottleneck_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W, TC *cst_out, int32_t *ptr_out,
-                         int64_t rlo, int64_t rhi, int64_t wwin, int64_t p_lo0, int64_t p_hi0, const int32_t *j0)
+                         int64_t rlo, int64_t rhi, int64_t wwin, int64_t p_lo0, int64_t p_hi0, const int32_t *j0, const BnPattern *pat)
 {
     hipStream_t s = A->stream;
     const int64_t n = A->n, n1 = n + 1;
@@ -749,7 +751,7 @@ void dp_bottleneck_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC 
     const bool hyp = M.kind == CP_MODEL_HYPEREDGE_CUT;
     ensure_links(A);
     if (hyp) ensure_self(A);
-    if (M.kind != CP_MODEL_WORK && !B->have_net) { ProfScope ps(PROF_WAVELET, s, 0.0); ensure_net_counter(A, B->net); B->have_net = true; }
+    if (!pat && M.kind != CP_MODEL_WORK && !B->have_net) { ProfScope ps(PROF_WAVELET, s, 0.0); ensure_net_counter(A, B->net); B->have_net = true; }
     if (hyp && !B->have_self) { ProfScope ps(PROF_WAVELET, s, 0.0); ensure_selfnet_counter(A, B->self); B->have_self = true; }
     BnCtx<TC> C;
     C.M = M; C.alpha = alpha; C.n = n; C.hyp = hyp ? 1 : 0;
@@ -762,10 +764,18 @@ void dp_bottleneck_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC 
     C.pos32 = A->pos32.p; C.prev = A->prev.p; C.next = A->next.p;
     C.fpos32 = hyp ? A->fpos32.p : nullptr; C.flast = hyp ? A->flast.p : nullptr;
     C.lpos32 = hyp ? A->lpos32.p : nullptr; C.lfirst = hyp ? A->lfirst.p : nullptr;
+    C.pin32 = C.pos32;
     C.net = B->net.d; C.self = B->self.d; C.W = W;
+    if (pat) {
+        // the wave-per-run walks take the pin count from the link positions themselves; only the lane-per-chunk walk reads it through
+        // bn_cost, so a pattern with a pin prefix of its own runs that walk
+        CP_REQUIRE(!limited && !hyp, CP_EINTERNAL, "a derived pattern has no constrained or hyperedge form");
+        C.pos = pat->pos; C.pos32 = pat->pos32; C.pin32 = pat->pin32; C.prev = pat->prev; C.next = pat->next; C.N = pat->N; C.net = *pat->net;
+        g_bn_sym_layers++;
+    }
     const int64_t nblk = cdiv(n1, 1024);
     B->runend.ensure((size_t)n1); B->blk.ensure((size_t)nblk + 1);
-    const bool wave = g_opt_bn_wave != 0;
+    const bool wave = g_opt_bn_wave != 0 && !pat;
     const int64_t CH = wave ? std::max<int64_t>(2, g_opt_bn_run) : std::max<int64_t>(1, g_opt_bn_chunk);
     // A weight-constrained layer's row window moves from layer to layer: its chunks are aligned to multiples of CH (the first one
     // starts inside its chunk, at rmin) and the hints are kept per ABSOLUTE chunk, so a row's crossing in the previous layer still
@@ -835,7 +845,7 @@ void dp_bottleneck_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC 
     CP_HIP(hipGetLastError());
 }
 
-template void dp_bottleneck_layer<int64_t>(cp_csr_s *, const DevModel<int64_t> &, int64_t, const int64_t *, int64_t *, int32_t *, int64_t, int64_t, int64_t, int64_t, int64_t, const int32_t *);
-template void dp_bottleneck_layer<double>(cp_csr_s *, const DevModel<double> &, double, const double *, double *, int32_t *, int64_t, int64_t, int64_t, int64_t, int64_t, const int32_t *);
+template void dp_bottleneck_layer<int64_t>(cp_csr_s *, const DevModel<int64_t> &, int64_t, const int64_t *, int64_t *, int32_t *, int64_t, int64_t, int64_t, int64_t, int64_t, const int32_t *, const BnPattern *);
+template void dp_bottleneck_layer<double>(cp_csr_s *, const DevModel<double> &, double, const double *, double *, int32_t *, int64_t, int64_t, int64_t, int64_t, int64_t, const int32_t *, const BnPattern *);
 
 }  // namespace cpk

@@ -4,6 +4,7 @@
 #include "model.hpp"
 #include "dp.hpp"
 #include "weight.hpp"
+#include "sym.hpp"
 #include <memory>
 
 namespace cpk {
@@ -74,6 +75,8 @@ static bool fast_bottleneck_ok(const cp_model_t *m, int64_t n, int64_t N, int64_
     if (!(P(CP_P_VERTEX) >= 0 && P(CP_P_PIN) >= 0)) return false;
     if (m->kind == CP_MODEL_WORK) return true;
     if (m->kind == CP_MODEL_CONNECTIVITY) return P(CP_P_NET) >= 0;
+    // the monotonized symmetric cost is the Connectivity cost on the pattern with its diagonal added (sym.hpp): the same conditions
+    if (m->kind == CP_MODEL_MONO_SYM_CONNECTIVITY) return P(CP_P_DIA_NET) >= 0;
     if (m->kind == CP_MODEL_HYPEREDGE_CUT)
         return P(CP_P_CUT_NET) >= 0 && P(CP_P_SELF_NET) >= P(CP_P_CUT_NET) && model_exact_on(m, n, N, K);
     return false;
@@ -89,6 +92,8 @@ struct DpRun : cp_dp_s {
     HostModel<TC> HM;
     DBuf<int32_t> cnt0;                        // layer-1 scratch: stays until the stream has run layer 1
     DBuf<int64_t> firsts, scan_tmp;
+    bool sym = false;                          // a symmetric cost model: every layer is the candidate sweep over the counters (sym.hip)
+    SymHost SH;
     int64_t *ptr_tab = nullptr;                // host tables (n+1) x K filled by dump_layer, or null: none asked for
     TC *cst_tab = nullptr;
 
@@ -103,6 +108,7 @@ struct DpRun : cp_dp_s {
             mdl.alpha_k = alpha_k_host.data();
         }
         need_self = mdl.kind == CP_MODEL_HYPEREDGE_CUT;
+        sym = model_is_sym(mdl.kind);
         fast = combine == CP_COMBINE_SUM && fast_total_ok(&mdl, A->n, A->N, K) && !g_opt_force_brute;
         fast_bn = combine == CP_COMBINE_MAX && fast_bottleneck_ok(&mdl, A->n, A->N, K) && !g_opt_force_brute;
         if (!fast && !fast_bn)
@@ -110,6 +116,7 @@ struct DpRun : cp_dp_s {
                        "model/objective outside the O(n log^2 n) class and n too large for the O(n^2) device sweep");
         ensure_links(A);
         if (need_self) ensure_self(A);
+        if (sym) sym_prepare(A, &mdl, SH);
         build_dev_model<TC>(&mdl, HM, A->stream);
         ptr.alloc((size_t)K * n1());
         if (fast) work = dp_total_work_get<TC>(A);       // (kept in the matrix handle between calls)
@@ -127,6 +134,7 @@ struct DpRun : cp_dp_s {
     {
         hipStream_t s = A->stream;
         const int64_t n = A->n;
+        if (sym) { sym_layer1<TC>(A, SH.d, HM.d, alpha_of(1), cur, ptr_row(1)); return; }
         const bool has_nets = mdl.kind == CP_MODEL_CONNECTIVITY || mdl.kind == CP_MODEL_HYPEREDGE_CUT || mdl.kind == CP_MODEL_COLBLOCK;
         if (has_nets) {
             cnt0.alloc((size_t)(n > 0 ? n : 1)); firsts.alloc(n1());
@@ -141,7 +149,16 @@ struct DpRun : cp_dp_s {
     // layer k >= 2, rows [rlo, rhi] (0-based), from the previous layer's cost row
     void layer(int64_t k, const TC *prev, TC *cur, int64_t rlo, int64_t rhi, const DpWindow &win = DpWindow())
     {
-        if (fast) dp_total_layer<TC>(A, HM.d, alpha_of(k), prev, cur, ptr_row(k), work, rlo, rhi, win.w);
+        if (sym && fast_bn) {
+            // kind 11 under max: the valley search over D's links and counter, pins from overpos; the formula is Connectivity's slot for slot
+            DevModel<TC> Mc = HM.d;
+            Mc.kind = CP_MODEL_CONNECTIVITY;
+            const SymWork *SW = sym_work_get(A);
+            const BnPattern pat{SW->dpos.p, SW->dpos32.p, SW->pin32.p, SW->dprev.p, SW->dnext.p, SW->Nd, &SW->dia.d};
+            dp_bottleneck_layer<TC>(A, Mc, alpha_of(k), prev, cur, ptr_row(k), rlo, rhi, win.w, win.lo, win.hi, win.j0, &pat);
+        }
+        else if (sym) sym_brute_layer<TC>(A, SH.d, HM.d, alpha_of(k), combine, prev, cur, ptr_row(k), rlo, rhi);
+        else if (fast) dp_total_layer<TC>(A, HM.d, alpha_of(k), prev, cur, ptr_row(k), work, rlo, rhi, win.w);
         else if (fast_bn) dp_bottleneck_layer<TC>(A, HM.d, alpha_of(k), prev, cur, ptr_row(k), rlo, rhi, win.w, win.lo, win.hi, win.j0);
         else dp_brute_layer<TC>(A, HM.d, alpha_of(k), combine, prev, cur, ptr_row(k), rlo, rhi);
     }

@@ -140,7 +140,14 @@ inline bool model_exact_on(const cp_model_t *m, int64_t n, int64_t N, int64_t K)
             return r;
         };
         u128 amax, bv = 0, bp = 0, bnet;
-        if (m->kind == CP_MODEL_COLBLOCK) {
+        int64_t Nnet = N;                      // how many entries the net-like count can reach
+        if (m->kind == CP_MODEL_MONO_SYM_CONNECTIVITY) {
+            // the Connectivity bound on the pattern with its diagonal added: the dianet count reaches N + n; p[4] is Delta_pins, no cost
+            amax = mag(m->p_i64[CP_P_ALPHA]);
+            if (m->alpha_k) for (int64_t i = 0; i < m->n_alpha_k; i++) amax = std::max(amax, mag(((const int64_t *)m->alpha_k)[i]));
+            bv = mag(m->p_i64[CP_P_VERTEX]); bp = mag(m->p_i64[CP_P_OVER_PIN]); bnet = mag(m->p_i64[CP_P_DIA_NET]);
+            Nnet = N + n;
+        } else if (m->kind == CP_MODEL_COLBLOCK) {
             amax = comp_max(m->alpha_col);
             bnet = comp_max(m->beta_col[0]);
         } else if (m->kind == CP_MODEL_WORK || m->kind == CP_MODEL_CONNECTIVITY || m->kind == CP_MODEL_HYPEREDGE_CUT) {
@@ -151,13 +158,14 @@ inline bool model_exact_on(const cp_model_t *m, int64_t n, int64_t N, int64_t K)
         } else {
             return false;
         }
-        const u128 bound = amax * (u128)(K > 0 ? K : 1) + bv * (u128)(n > 0 ? n : 0) + (bp + bnet) * (u128)(N > 0 ? N : 0);
+        const u128 bound = amax * (u128)(K > 0 ? K : 1) + bv * (u128)(n > 0 ? n : 0) + bp * (u128)(N > 0 ? N : 0) + bnet * (u128)(Nnet > 0 ? Nnet : 0);
         return bound < ((u128)1 << 60);
     }
     double amax = std::fabs(m->p_f64[CP_P_ALPHA]);
     if (m->alpha_k) for (int64_t i = 0; i < m->n_alpha_k; i++) amax = std::max(amax, std::fabs(((const double *)m->alpha_k)[i]));
-    double bnet = std::max(std::fabs(m->p_f64[3]), std::fabs(m->p_f64[4]));
-    double bound = amax * (double)(K > 0 ? K : 1) + std::fabs(m->p_f64[CP_P_VERTEX]) * (double)n + std::fabs(m->p_f64[CP_P_PIN]) * (double)N + bnet * (double)N;
+    const bool mono = m->kind == CP_MODEL_MONO_SYM_CONNECTIVITY;
+    double bnet = mono ? std::fabs(m->p_f64[CP_P_DIA_NET]) : std::max(std::fabs(m->p_f64[3]), std::fabs(m->p_f64[4]));
+    double bound = amax * (double)(K > 0 ? K : 1) + std::fabs(m->p_f64[CP_P_VERTEX]) * (double)n + std::fabs(m->p_f64[CP_P_PIN]) * (double)N + bnet * (double)(mono ? N + n : N);
     return bound < 9007199254740992.0;       // 2^53
 }
 

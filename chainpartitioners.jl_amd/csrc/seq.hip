@@ -1277,12 +1277,15 @@ static bool seq_model_ok(const cp_model_t *m)
            (m->dtype == CP_I64 || m->dtype == CP_F64);
 }
 
+static bool seq_model_sym(const cp_model_t *m) { return m && m->kind >= CP_MODEL_SYM_CONNECTIVITY && m->kind <= CP_MODEL_SYM_EDGE_CUT; }
+
 extern "C" {
 
 int32_t cp_pack_dynamic(cp_csr_t A, const cp_model_t *model, const cp_rowpart_t *Pi, const cp_model_t *weight, int64_t wmax_i64,
                         double wmax_f64, int64_t *spl_out, int64_t *K_out)
 {
     try {
+        CP_REQUIRE(!seq_model_sym(model), CP_EUNSUPPORTED, "the symmetric cost models have no device path in this method");
         CP_REQUIRE(A && spl_out && K_out && seq_model_ok(model) && weight_ok(weight), CP_EINVAL, "bad argument");
         CP_HIP(hipSetDevice(A->device));
         if (model->dtype == CP_I64) return run_pack_dynamic<int64_t>(A, model, Pi, weight, wmax_i64, wmax_f64, spl_out, K_out);
@@ -1294,6 +1297,7 @@ int32_t cp_pack_dynamic_tables(cp_csr_t A, const cp_model_t *model, const cp_row
                                double wmax_f64, int64_t *spl_tab, int64_t *cst_i64, double *cst_f64)
 {
     try {
+        CP_REQUIRE(!seq_model_sym(model), CP_EUNSUPPORTED, "the symmetric cost models have no device path in this method");
         CP_REQUIRE(A && spl_tab && seq_model_ok(model) && weight_ok(weight), CP_EINVAL, "bad argument");
         CP_REQUIRE(model->dtype == CP_I64 ? cst_i64 != nullptr : cst_f64 != nullptr, CP_EINVAL, "cst table of the model's element type needed");
         CP_HIP(hipSetDevice(A->device));
@@ -1306,6 +1310,7 @@ int32_t cp_pack_convex(cp_csr_t A, const cp_model_t *model, const cp_rowpart_t *
                        double wmax_f64, int64_t *spl_out, int64_t *K_out)
 {
     try {
+        CP_REQUIRE(!seq_model_sym(model), CP_EUNSUPPORTED, "the symmetric cost models have no device path in this method");
         CP_REQUIRE(A && spl_out && K_out && seq_model_ok(model) && weight_ok(weight), CP_EINVAL, "bad argument");
         CP_HIP(hipSetDevice(A->device));
         if (model->dtype == CP_I64) return run_pack_convex<int64_t>(A, model, Pi, weight, wmax_i64, wmax_f64, spl_out, K_out);
@@ -1319,6 +1324,7 @@ int32_t cp_pack_convex_batch(cp_csr_t A, int64_t B, const cp_model_t *models, co
         CP_REQUIRE(A && models && wmax && spl_out && K_out && B >= 1 && B <= 65535 && ld >= 2, CP_EINVAL, "bad argument");
         CP_REQUIRE(A->n >= 1 && (double)(A->n + 2) * (double)(2 * CW_MAXW + 3) < 2e9, CP_EUNSUPPORTED, "pattern too small / too large for the window table");
         for (int64_t b = 0; b < B; b++) {
+            CP_REQUIRE(!seq_model_sym(models + b), CP_EUNSUPPORTED, "the symmetric cost models have no device path in this method");
             CP_REQUIRE(seq_model_ok(models + b) && models[b].dtype == models[0].dtype, CP_EINVAL, "bad model in the batch (one element type per batch)");
             CP_REQUIRE((models[b].kind == CP_MODEL_COLBLOCK || models[b].kind == CP_MODEL_CONNECTIVITY || models[b].kind == CP_MODEL_WORK) && !models[b].alpha_k,
                        CP_EUNSUPPORTED, "a batch takes ColumnBlock / Connectivity / Work models without per-part alpha");
@@ -1334,6 +1340,7 @@ int32_t cp_partition_convex(cp_csr_t A, int64_t K, const cp_model_t *model, cons
                             int64_t wmax_i64, double wmax_f64, int64_t *spl_out)
 {
     try {
+        CP_REQUIRE(!seq_model_sym(model), CP_EUNSUPPORTED, "the symmetric cost models have no device path in this method");
         CP_REQUIRE(A && spl_out && K >= 1 && seq_model_ok(model) && weight_ok(weight), CP_EINVAL, "bad argument");
         CP_HIP(hipSetDevice(A->device));
         if (model->dtype == CP_I64) return run_partition_convex<int64_t>(A, K, model, Pi, weight, wmax_i64, wmax_f64, spl_out);
@@ -1345,6 +1352,7 @@ int32_t cp_pack_concave(cp_csr_t A, const cp_model_t *model, const cp_rowpart_t 
                         double wmax_f64, int64_t *spl_out, int64_t *K_out)
 {
     try {
+        CP_REQUIRE(!seq_model_sym(model), CP_EUNSUPPORTED, "the symmetric cost models have no device path in this method");
         CP_REQUIRE(A && spl_out && K_out && seq_model_ok(model) && weight_ok(weight), CP_EINVAL, "bad argument");
         CP_HIP(hipSetDevice(A->device));
         if (model->dtype == CP_I64) return run_pack_concave<int64_t>(A, model, Pi, weight, wmax_i64, wmax_f64, spl_out, K_out);
@@ -1356,6 +1364,7 @@ int32_t cp_partition_concave(cp_csr_t A, int64_t K, const cp_model_t *model, con
                              int64_t wmax_i64, double wmax_f64, int64_t *spl_out)
 {
     try {
+        CP_REQUIRE(!seq_model_sym(model), CP_EUNSUPPORTED, "the symmetric cost models have no device path in this method");
         CP_REQUIRE(A && spl_out && K >= 1 && seq_model_ok(model) && weight_ok(weight), CP_EINVAL, "bad argument");
         CP_HIP(hipSetDevice(A->device));
         if (model->dtype == CP_I64) return run_partition_concave<int64_t>(A, K, model, Pi, weight, wmax_i64, wmax_f64, spl_out);

@@ -9,6 +9,7 @@
 //   bucket_start + (zeros in the bucket) + (ones before it in the bucket) if its bit is 1.
 #include "csr.hpp"
 #include "wavelet.hpp"
+#include "sym.hpp"
 #include <memory>
 #include <vector>
 
@@ -398,14 +399,21 @@ int32_t cp_count_build(cp_csr_t A, int32_t kind, int32_t hint, cp_count_t *out)
 {
     (void)hint;         // every hint is served by the same exact structure
     try {
-        CP_REQUIRE(A && out && kind >= CP_COUNT_DOM && kind <= CP_COUNT_SELFNET, CP_EINVAL, "bad argument");
+        CP_REQUIRE(A && out && kind >= CP_COUNT_DOM && kind <= CP_COUNT_SELFPIN, CP_EINVAL, "bad argument");
+        CP_REQUIRE(kind < CP_COUNT_DIANET || A->m == A->n, CP_EINVAL, "dianetcount / selfpincount need a square pattern");
         CP_HIP(hipSetDevice(A->device));
         cp_count_s *h = new cp_count_s();
         h->A = A; h->kind = kind;
         try {
             if (kind == CP_COUNT_DOM) build_dom_counter(A, h->wt);
             else if (kind == CP_COUNT_NET) ensure_net_counter(A, h->wt);
-            else ensure_selfnet_counter(A, h->wt);
+            else if (kind == CP_COUNT_SELFNET) ensure_selfnet_counter(A, h->wt);
+            else if (kind == CP_COUNT_DIANET) {
+                build_dianet_counter(A, h->wt);
+                h->colstart.alloc((size_t)A->n + 1);
+                CP_HIP(hipMemcpyAsync(h->colstart.p, sym_work_get(A)->dpos.p, sizeof(int64_t) * ((size_t)A->n + 1), hipMemcpyDeviceToDevice, A->stream));
+                CP_HIP(hipStreamSynchronize(A->stream));
+            } else build_selfpin_counter(A, h->wt, h->colstart);
         } catch (...) { delete h; throw; }
         prof_collect();
         *out = h;
@@ -428,10 +436,13 @@ int32_t cp_count_query(cp_count_t h, int64_t nq, const int64_t *a, const int64_t
         DBuf<int64_t> da((size_t)nq), db((size_t)nq), dout((size_t)nq);
         CP_HIP(hipMemcpyAsync(da.p, a, sizeof(int64_t) * (size_t)nq, hipMemcpyHostToDevice, s));
         CP_HIP(hipMemcpyAsync(db.p, b, sizeof(int64_t) * (size_t)nq, hipMemcpyHostToDevice, s));
-        const int64_t *colstart = (h->kind == CP_COUNT_SELFNET) ? A->lpos.p : A->pos.p;
+        // dianet is the net count over D's columns, selfpin the plain dominance count over the max(i,j) buckets
+        const bool own = h->kind == CP_COUNT_DIANET || h->kind == CP_COUNT_SELFPIN;
+        const int64_t *colstart = own ? h->colstart.p : (h->kind == CP_COUNT_SELFNET) ? A->lpos.p : A->pos.p;
+        const int32_t qkind = h->kind == CP_COUNT_DIANET ? CP_COUNT_NET : h->kind == CP_COUNT_SELFPIN ? CP_COUNT_SELFNET : h->kind;
         {
             ProfScope ps(PROF_QUERY, s, 0.0);
-            hipLaunchKernelGGL(k_count_query, dim3((unsigned)cdiv(nq, 256)), dim3(256), 0, s, h->kind, h->wt.d, A->n, colstart, A->pos.p,
+            hipLaunchKernelGGL(k_count_query, dim3((unsigned)cdiv(nq, 256)), dim3(256), 0, s, qkind, h->wt.d, A->n, colstart, own ? colstart : A->pos.p,
                                nq, da.p, db.p, dout.p);
         }
         CP_HIP(hipGetLastError());

@@ -63,6 +63,7 @@ struct cp_count_s {
     cp_csr_s *A;
     int32_t kind;
     cpk::WaveletHost wt;
+    cpk::DBuf<int64_t> colstart;      // dianet / selfpin: the handle's own column pointer (D's columns / the max(i,j) buckets)
 };
 
 namespace cpk {

@@ -14,6 +14,9 @@ Mirrors (file:line under /root/reference/src):
   Reference*                     ReferenceSplitter.jl:1-21
   [Flip]BisectCostBottleneckSplitter            BisectCostBottleneckSplitter.jl:1-4, 65-68
   ConvexTotalChunker / ConvexTotalSplitter      ConvexTotalChunker.jl:1-7
+  AffineSymmetricConnectivityModel              SymmetricConnectivityCosts.jl:5-19
+  AffineMonotonizedSymmetricConnectivityModel   MonotonizedSymmetricConnectivityCosts.jl:5-33
+  AffineSymmetricEdgeCutModel                   SymmetricEdgeCutCosts.jl:5-18
 
 Julia's constructors `promote` all parameters to one element type (ConnectivityCosts.jl:14-16):
 all-int arguments give an Int64 model, any float gives Float64.  Closures (e.g.
@@ -28,6 +31,7 @@ CP_I64, CP_F64 = 0, 1
 (CP_MODEL_FEASIBLE, CP_MODEL_WORK, CP_MODEL_CONNECTIVITY, CP_MODEL_HYPEREDGE_CUT,
  CP_MODEL_COLBLOCK, CP_MODEL_BLOCK, CP_MODEL_VERTEX_COUNT, CP_MODEL_POWER_WORK, CP_MODEL_PRIMARY,
  CP_MODEL_SECONDARY) = range(10)
+CP_MODEL_SYM_CONNECTIVITY, CP_MODEL_MONO_SYM_CONNECTIVITY, CP_MODEL_SYM_EDGE_CUT = 10, 11, 12
 CP_COMBINE_SUM, CP_COMBINE_MAX = 0, 1
 CP_ORDER_SPLITTER, CP_ORDER_CHUNKER = 0, 1
 CP_MAX_R = 4
@@ -235,6 +239,91 @@ class AffineSecondaryConnectivityModel(AffinePrimaryConnectivityModel):
     kind = CP_MODEL_SECONDARY
 
 
+# ---------------------------------------------------------------- the symmetric family (square patterns, one partition for
+# rows and columns; HIP backend only)
+class AffineSymmetricConnectivityModel(_Model):
+    """SymmetricConnectivityCosts.jl:5-19: alpha + nv*beta_vertex + np*beta_pin + local*beta_local_net + remote*beta_remote_net with
+    remote = dianet(j, j') - nv (the nets of the part that reach outside its own rows) and local = net(j, j') - remote."""
+    kind = CP_MODEL_SYM_CONNECTIVITY
+    symmetric = True
+
+    def __init__(self, alpha=0, beta_vertex=0, beta_pin=0, beta_local_net=0, beta_remote_net=0):
+        self.alpha, self.beta_vertex, self.beta_pin = alpha, beta_vertex, beta_pin
+        self.beta_local_net, self.beta_remote_net = beta_local_net, beta_remote_net
+        self.alpha_k = None
+        self.dtype = _promote(alpha, beta_vertex, beta_pin, beta_local_net, beta_remote_net)
+
+    def _params(self):
+        return [self.alpha, self.beta_vertex, self.beta_pin, self.beta_local_net, self.beta_remote_net]
+
+    def __call__(self, n_vertices, n_pins, n_local, n_remote, k=None):
+        return (self.alpha + n_vertices * self.beta_vertex + n_pins * self.beta_pin + n_local * self.beta_local_net
+                + n_remote * self.beta_remote_net)
+
+
+def _cld(a, b):
+    """Julia cld: Int for Ints (exact), ceil(a / b) for floats"""
+    if _is_int(a) and _is_int(b):
+        return -((-int(a)) // int(b))
+    return float(np.ceil(a / b))
+
+
+class AffineMonotonizedSymmetricConnectivityModel(_Model):
+    """MonotonizedSymmetricConnectivityCosts.jl:5-33: alpha + nv*beta_vertex + overpins*beta_over_pin + dianet(j, j')*beta_dia_net,
+    overpins = sum of max(deg - delta_pins, 0) over the part's columns; every term grows with the part.  Positional, keyword
+    (:13-15) and converting (from an AffineSymmetricConnectivityModel, :17-29) constructors.  `alpha_k` gives the per-part alpha[k]
+    of the reference tests' FunkyMonotonizedSymmetricConnectivityModel (test_Partitioners.jl:12-22).  delta_pins must be
+    integer-valued (the reference keeps the over-pin prefix in an integer vector)."""
+    kind = CP_MODEL_MONO_SYM_CONNECTIVITY
+    symmetric = True
+
+    def __init__(self, alpha=0, beta_vertex=0, beta_over_pin=0, beta_dia_net=0, delta_pins=0, *, alpha_k=None):
+        if isinstance(alpha, AffineSymmetricConnectivityModel):
+            if (beta_vertex, beta_over_pin, beta_dia_net, delta_pins) != (0, 0, 0, 0):
+                raise TypeError("the converting constructor takes the symmetric model alone")
+            s = alpha
+            zero = 0 if s.dtype == CP_I64 else 0.0
+            alpha, beta_dia_net, beta_over_pin = s.alpha, s.beta_remote_net, s.beta_pin
+            if s.beta_vertex < s.beta_remote_net:
+                delta_pins, beta_vertex = _cld(s.beta_remote_net - s.beta_vertex, s.beta_pin), zero
+            else:
+                delta_pins, beta_vertex = 0, s.beta_vertex - s.beta_remote_net
+            if s.dtype == CP_F64:                    # the struct is {Tv}: every field converts to the model's element type
+                alpha, beta_vertex, beta_over_pin, beta_dia_net, delta_pins = (float(v) for v in (alpha, beta_vertex, beta_over_pin, beta_dia_net, delta_pins))
+        self.alpha, self.beta_vertex, self.beta_over_pin = alpha, beta_vertex, beta_over_pin
+        self.beta_dia_net, self.delta_pins = beta_dia_net, delta_pins
+        self.alpha_k = alpha_k
+        self.dtype = _promote(alpha, beta_vertex, beta_over_pin, beta_dia_net, delta_pins, *([alpha_k] if alpha_k is not None else []))
+
+    def _params(self):
+        return [self.alpha, self.beta_vertex, self.beta_over_pin, self.beta_dia_net, self.delta_pins]
+
+    def _alpha_k(self):
+        return self.alpha_k
+
+    def __call__(self, n_vertices, n_over_pins, n_dia_nets, k=None):
+        a = self.alpha if self.alpha_k is None or k is None else self.alpha_k[k - 1]
+        return a + n_vertices * self.beta_vertex + n_over_pins * self.beta_over_pin + n_dia_nets * self.beta_dia_net
+
+
+class AffineSymmetricEdgeCutModel(_Model):
+    """SymmetricEdgeCutCosts.jl:5-18: alpha + nv*beta_vertex + selfpin(j, j')*beta_self_pin + (np - selfpin)*beta_cut_pin,
+    selfpin = nonzeros of the part's diagonal block."""
+    kind = CP_MODEL_SYM_EDGE_CUT
+    symmetric = True
+
+    def __init__(self, alpha=0, beta_vertex=0, beta_self_pin=0, beta_cut_pin=0):
+        self.alpha, self.beta_vertex, self.beta_self_pin, self.beta_cut_pin = alpha, beta_vertex, beta_self_pin, beta_cut_pin
+        self.alpha_k = None
+        self.dtype = _promote(alpha, beta_vertex, beta_self_pin, beta_cut_pin)
+
+    def _params(self):
+        return [self.alpha, self.beta_vertex, self.beta_self_pin, self.beta_cut_pin]
+
+    def __call__(self, n_vertices, n_self_pins, n_cut_pins, k=None):
+        return self.alpha + n_vertices * self.beta_vertex + n_self_pins * self.beta_self_pin + n_cut_pins * self.beta_cut_pin
+
+
 def _tabulate(f, lo, hi, npdt):
     """f(w) for w = lo .. hi; vectorised when the callable allows it, checked against three scalar calls."""
     ws = np.arange(lo, hi + 1, dtype=np.int64)
@@ -413,7 +502,7 @@ class FlipBisectIndexBottleneckSplitter(BisectIndexBottleneckSplitter):
 
 
 class LazyBisectCostBottleneckSplitter:
-    """LazyBisectCostBottleneckSplitter.jl:1-4, connectivity specialisation :140-258"""
+    """LazyBisectCostBottleneckSplitter.jl:1-4, connectivity specialisation :140-258, monotonized symmetric one :260-388"""
 
     def __init__(self, f, eps):
         self.f, self.eps = f, float(eps)

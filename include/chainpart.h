@@ -59,6 +59,11 @@ int32_t cp_csr_reset_cache(cp_csr_t csr);
 #define CP_COUNT_DOM     0
 #define CP_COUNT_NET     1
 #define CP_COUNT_SELFNET 2
+/* dianetcount(hint, A)      SparseColorArrays.jl:65-99   kind CP_COUNT_DIANET  : nets of A[:, j:j'-1] with the diagonal added
+ * selfpincount(hint, A)     SparseColorArrays.jl:268-318 kind CP_COUNT_SELFPIN : nnz(A[j:j'-1, j:j'-1])
+ * both need a square pattern (CP_EINVAL otherwise); dianet refuses nnz + n >= 2^31 - 1 with CP_EUNSUPPORTED */
+#define CP_COUNT_DIANET  3
+#define CP_COUNT_SELFPIN 4
 int32_t cp_count_build(cp_csr_t csr, int32_t kind, int32_t hint, cp_count_t *out);
 int32_t cp_count_query(cp_count_t h, int64_t nq, const int64_t *a, const int64_t *b, int64_t *out);
 int32_t cp_count_destroy(cp_count_t h);
@@ -160,6 +165,10 @@ int32_t cp_partition_bisect_index(cp_csr_t csr, int64_t K, const cp_model_t *mod
  * Models that are not connectivity models return CP_EINVAL (the reference's generic method asserts, :486-501). */
 int32_t cp_partition_lazy_bisect_cost(cp_csr_t csr, int64_t K, const cp_model_t *model, double eps,
                                       int64_t *spl_out /* K+1 */);
+/* ... and with f an AffineMonotonizedSymmetricConnectivityModel (CP_MODEL_MONO_SYM_CONNECTIVITY, :260-388): the same probe over
+ * the pattern with its diagonal added.  This form also reports the number of probes the bisection ran (nprobes_out may be NULL). */
+int32_t cp_partition_lazy_bisect_cost_probes(cp_csr_t csr, int64_t K, const cp_model_t *model, double eps,
+                                             int64_t *spl_out /* K+1 */, int64_t *nprobes_out);
 /* pack_stripe(A, ConvexTotalChunker(..), [Pi]) / partition_stripe(A, K, ConvexTotalSplitter(..), [Pi])
  * ConvexTotalChunker.jl:9-265 */
 int32_t cp_pack_convex(cp_csr_t csr, const cp_model_t *model, const cp_rowpart_t *Pi,

@@ -14,6 +14,9 @@
  *   VertexCount (a weight)      SparseColorArrays.jl:1-6
  *   FeasibleCost (no weight)    Costs.jl:153-171
  *   per-part alpha[k] models ("Funky*")  test/test_Partitioners.jl:1-8
+ *   AffineSymmetricConnectivityModel            SymmetricConnectivityCosts.jl:5-19
+ *   AffineMonotonizedSymmetricConnectivityModel MonotonizedSymmetricConnectivityCosts.jl:5-33
+ *   AffineSymmetricEdgeCutModel                 SymmetricEdgeCutCosts.jl:5-18
  */
 #ifndef CHAINPART_TYPES_H
 #define CHAINPART_TYPES_H
@@ -55,6 +58,13 @@ extern "C" {
                                       tests define (test/test_Partitioners.jl:54-74); gamma == 2 is evaluated as x*x
                                       (Julia's literal_pow), any other exponent with pow() */
 
+/* the symmetric family: one partition for the rows and columns of a square pattern (m == n, else CP_EINVAL) */
+#define CP_MODEL_SYM_CONNECTIVITY      10  /* alpha + nv*b_vertex + np*b_pin + local*b_local_net + remote*b_remote_net with
+                                              remote = dianet(j,j') - nv, local = net(j,j') - remote */
+#define CP_MODEL_MONO_SYM_CONNECTIVITY 11  /* alpha + nv*b_vertex + overpins*b_over_pin + dianet(j,j')*b_dia_net; overpins sums
+                                              max(deg - Delta_pins, 0) over the columns; Delta_pins (p[4]) integer-valued */
+#define CP_MODEL_SYM_EDGE_CUT          12  /* alpha + nv*b_vertex + selfpin(j,j')*b_self_pin + (np - selfpin)*b_cut_pin */
+
 /* parameter slots of p_i64 / p_f64 */
 #define CP_P_ALPHA      0
 #define CP_P_VERTEX     1
@@ -65,6 +75,11 @@ extern "C" {
 #define CP_P_GAMMA      3   /* power work model: the exponent */
 #define CP_P_LOCAL_NET  3   /* primary / secondary connectivity */
 #define CP_P_REMOTE_NET 4
+#define CP_P_OVER_PIN   2   /* monotonized symmetric connectivity */
+#define CP_P_DIA_NET    3
+#define CP_P_DELTA_PINS 4
+#define CP_P_SELF_PIN   2   /* symmetric edge cut */
+#define CP_P_CUT_PIN    3
 
 #define CP_MAX_R 4
 
