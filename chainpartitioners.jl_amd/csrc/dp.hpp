@@ -130,5 +130,28 @@ extern int64_t g_opt_short_t, g_opt_short_e;   // k_setup_short: tasks with <= s
 extern int64_t g_opt_force_brute;      // cp_set_option("force_brute", 1)
 extern int64_t g_opt_brute_max_n;      // largest n the O(n^2) path accepts
 extern int64_t g_opt_dbg;            // cp_set_option("dbg", mask): timing experiments; every bit leaves the tables unchanged (the tests demand it)
+// The bits of that mask (callers pass the numbers; the same table is in DESIGN.md section 4e).  Bits 1, 2, 4, 16, 8192, 32768, 65536,
+// 131072 and 16777216 are free.  33554432 has one meaning in dp_total.hip and another in dp_bottleneck.hip: take a free bit, not a
+// third meaning.
+enum DbgBit : int64_t {
+    DBG_PRINT_ROUNDS = 8,                // total DP: every round's task counts to stderr
+    DBG_NO_INTERIOR = 32,                // k_tile_t0 marks no tile as interior to one task (k_lpass takes its general path everywhere)
+    DBG_NO_OWN_TILES = 64,               // every long task stays in the flattened space (no k_lpass_own, no gap passes)
+    DBG_POISON = 128,                    // fill the per-tile buffers of a stage before it runs: 0x7F bytes ...
+    DBG_POISON_ZERO = 256,               // ... or, with this bit too, zero bytes
+    DBG_GAP_ALL_SPECIAL = 512,           // k_lpass_own flags every gap tile: the SLOW gap kernels walk them entry by entry
+    DBG_MISPREDICT = 1024,               // speculative layers: every odd round is predicted empty (stages with work are skipped, the layer redone)
+    DBG_TINY_BUFFERS = 2048,             // speculative layers: the round verdicts take the buffers for too small (every round dropped, the layer redone)
+    DBG_COUNT_NONTRIVIAL = 4096,         // k_setup_short counts the tasks it does not finish itself (RoundCounts::_pad, printed by DBG_PRINT_ROUNDS)
+    DBG_COMBINE_BY_SLOT = 16384,         // k_combine / k_combine_win without the leaf pass: threads in plane-slot order
+    DBG_RA_ROWMAJOR = 262144,            // unconstrained round A from the cache by the row-major kernel k_ra_layer
+    DBG_NO_FORCE_OWN = 524288,           // no round trades its flattened stage for own tiles (LayerWork::force_own ignored)
+    DBG_WIN_NO_RA_CACHE = 1048576,       // windowed layers: round A without the cached tables (every head a generic task)
+    DBG_WIN_NO_MIR_CACHE = 2097152,      // windowed layers: standard heads from the cache, mirrored heads as generic tasks
+    DBG_BN_NO_HINT2 = 4194304,           // bottleneck: starts from the last layer's crossings only, not extrapolated from the last two
+    DBG_MIR_ROWMAJOR = 8388608,          // windowed layers: the mirrored heads from their cache by the row-major kernel k_ra_layer
+    DBG_RA_ALL_LEVELS = 33554432,        // total DP: round A from the cache computes the levels below LEAF_T too, as without the leaf pass
+    DBG_BN_NO_HINT_STARTS = 33554432,    // bottleneck (SAME BIT): the wave-per-run walk brackets its starts instead of taking them from the hint
+};
 
 }  // namespace cpk

@@ -809,8 +809,8 @@ void dp_bottleneck_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC 
     //  - the fine starts as a 4-ary search, three interleaved descents per step: 1.0 ms against 0.9 ms -- 1.25 M lanes are bound by
     //    the number of line requests, not by the length of the chain.
     const int32_t *h1 = hinted ? B->hint.p + tbase : (const int32_t *)nullptr;
-    const int32_t *h2 = hinted && B->hint_layers >= 2 && !(g_opt_dbg & 4194304) ? B->hint2.p + tbase : (const int32_t *)nullptr;
-    if (hinted && wave && !(g_opt_dbg & 33554432)) {
+    const int32_t *h2 = hinted && B->hint_layers >= 2 && !(g_opt_dbg & DBG_BN_NO_HINT2) ? B->hint2.p + tbase : (const int32_t *)nullptr;
+    if (hinted && wave && !(g_opt_dbg & DBG_BN_NO_HINT_STARTS)) {
         // the wave-per-run walks need one start per few hundred rows, and any column left of the crossing will do: the crossing of
         // the same row in the previous layer (continued by that layer's move) minus a slack, one confirming probe
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bn_starts<TC>), dim3((unsigned)cdiv(nchunk, 256)), dim3(256), 0, s, C, rlo, rhi, CH, nchunk, 1, 0, B->c0.p, B->nn0.p, B->nl0.p, h1, h2,

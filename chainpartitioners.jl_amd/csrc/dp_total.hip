@@ -2561,6 +2561,8 @@ struct LayerWork {
     int64_t force_rows = 0;               // rows of the layer the flags come from (a one-row last layer says nothing about a full one)
     // (o_rec / loc are the size witnesses of their groups: they are released first and allocated LAST, so a hipMalloc failure in
     //  the middle leaves the witness empty and the next call allocates the whole group again)
+    // what the pattern's cached tables and the last layer's counts say no longer holds (another pattern, another shape)
+    void forget() { ra_built = false; pred_ok = false; win_built = false; mir_built = false; force_own.clear(); force_rows = 0; }
     void ensure_own(size_t NT) {                        // per-tile arrays of the own-tiled tasks
         if (o_rec.n >= NT && o_rec.n > 0) return;
         size_t c = NT > 0 ? NT : 1;
@@ -2581,6 +2583,13 @@ struct LayerWork {
         loc.alloc(c);
     }
 };
+
+// A layer's variant (HYP: hyperedge costs, with the second count) is fixed when the layer starts: run_layer<TC, HYP> and what it
+// calls see the work buffers through these two.
+// the record buffers are sized for the larger record and read as the variant's own
+template <bool HYP, typename TC> static Best<TC, HYP> *recs(const DBuf<Best<TC, true>> &b) { return reinterpret_cast<Best<TC, HYP> *>(b.p); }
+// the arrays of the second (self-net) count: the kernels of the other variant get null
+template <bool HYP, typename T> static T *if_hyp(T *p) { return HYP ? p : nullptr; }
 
 // number of rows r <= x of the form (base << (b+1)) | (1 << b) | ((2v+1) << tau): the rows with ctz == tau whose bit b is set
 static int64_t count_rows(int b, int tau, int64_t x)
@@ -2709,43 +2718,73 @@ static void launch_rpass(hipStream_t s, const RoundDesc &R, int nbits, int64_t n
     }
 }
 
-// builds the cached round-A counts (once per partition: they depend on the pattern only)
-template <typename TC>
-static void ra_build(cp_csr_s *A, LayerWork<TC> &Wk)
+// Builds a cached round-A table: the counts of `levels` levels of rows_of(b) rows each (they depend on the pattern only -- once per
+// partition; the table of the mirrored heads of the windowed geometry, mir_w > 0, also on the window width: once per (pattern, w),
+// after win_build, whose anchors `anch` / `anch2` its counts carry).  Fills T, the counts c (c2: second count) and the sizes;
+// `part` gets room for the partials of the rows of more than LT candidates.
+template <typename TC, typename Rows>
+static void ra_build(cp_csr_s *A, LayerWork<TC> &Wk, RATab &T, int levels, Rows rows_of, int64_t mir_w, const int32_t *anch, const int32_t *anch2,
+                     DBuf<int32_t> &c, DBuf<int32_t> &c2, DBuf<Best<TC, true>> &part, int64_t &ntile, int64_t &nrow)
 {
     hipStream_t s = A->stream;
-    const int64_t n = A->n;
     const bool hyp = Wk.hyp;
-    RATab &T = Wk.ra_tab;
     memset(&T, 0, sizeof(T));
-    T.nbits = Wk.nbits; T.n = n;
-    for (int b = 0; b < 33; b++) { T.tlo[b] = 0; T.thi[b] = INT64_MAX; }
+    T.nbits = levels; T.n = A->n; T.mir_w = mir_w;
+    for (int b = 0; b < 33; b++) { T.tlo[b] = 0; T.thi[b] = INT64_MAX; T.aoff[b] = (mir_w && b < 32) ? Wk.win_aoff[b] : 0; }
     int64_t tb = 0, rb = 0;
     for (int b = 0; b < 33; b++) {
         T.tbase[b] = tb; T.rbase[b] = rb;
-        if (b >= Wk.nbits) continue;
-        int64_t nrows = ((n >> b) + 1) >> 1;
+        if (b >= levels) continue;
+        const int64_t nrows = rows_of(b);
         tb += cdiv(nrows << b, LT);
         if (b >= 9) rb += nrows;
     }
-    Wk.ra_ntile = tb; Wk.ra_nrow = rb;
+    ntile = tb; nrow = rb;
     const size_t total = (size_t)tb * LT;
-    Wk.ra_c.ensure(total + 8);
-    if (hyp) Wk.ra_c2.ensure(total + 8);
-    Wk.ra_part.ensure((size_t)std::max<int64_t>(1, tb - T.tbase[9]));
-    if (tb <= 0) { Wk.ra_built = true; return; }
+    c.ensure(total + 8);
+    if (hyp) c2.ensure(total + 8);
+    part.ensure((size_t)std::max<int64_t>(1, tb - T.tbase[9]));
+    if (tb <= 0) return;
     DBuf<int64_t> &G = Wk.ra_G, &scratch = Wk.scratch;        // (kept with the layer scratch: 8 B per element)
     G.ensure(total + 1);
     hipLaunchKernelGGL(k_ra_colcount, dim3((unsigned)tb), dim3(LT), 0, s, T, A->pos32.p, A->next.p, hyp ? A->fpos32.p : (const int32_t *)nullptr,
-                       hyp ? A->flast.p : (const int32_t *)nullptr, Wk.ra_c.p, hyp ? Wk.ra_c2.p : (int32_t *)nullptr);
-    exclusive_scan_i32(Wk.ra_c.p, G.p, (int64_t)total, scratch, s);
-    hipLaunchKernelGGL(k_ra_final, dim3((unsigned)tb), dim3(LT), 0, s, T, G.p, Wk.ra_c.p, (const int32_t *)nullptr);
+                       hyp ? A->flast.p : (const int32_t *)nullptr, c.p, hyp ? c2.p : (int32_t *)nullptr);
+    exclusive_scan_i32(c.p, G.p, (int64_t)total, scratch, s);
+    hipLaunchKernelGGL(k_ra_final, dim3((unsigned)tb), dim3(LT), 0, s, T, G.p, c.p, anch);
     if (hyp) {
-        exclusive_scan_i32(Wk.ra_c2.p, G.p, (int64_t)total, scratch, s);
-        hipLaunchKernelGGL(k_ra_final, dim3((unsigned)tb), dim3(LT), 0, s, T, G.p, Wk.ra_c2.p, (const int32_t *)nullptr);
+        exclusive_scan_i32(c2.p, G.p, (int64_t)total, scratch, s);
+        hipLaunchKernelGGL(k_ra_final, dim3((unsigned)tb), dim3(LT), 0, s, T, G.p, c2.p, anch2);
     }
     CP_HIP(hipGetLastError());
+}
+// the table of the unconstrained scheme's round A (the windowed layers' standard heads are its levels below s)
+template <typename TC>
+static void ra_build_std(cp_csr_s *A, LayerWork<TC> &Wk)
+{
+    const int64_t n = A->n;
+    ra_build<TC>(A, Wk, Wk.ra_tab, Wk.nbits, [n](int b) { return ((n >> b) + 1) >> 1; }, 0, nullptr, nullptr, Wk.ra_c, Wk.ra_c2, Wk.ra_part, Wk.ra_ntile, Wk.ra_nrow);
     Wk.ra_built = true;
+}
+// ... and of the mirrored heads of the current window: rows (u + 1) 2^(b+1) <= n
+template <typename TC>
+static void ra_build_mir(cp_csr_s *A, LayerWork<TC> &Wk)
+{
+    const int64_t n = A->n;
+    ra_build<TC>(A, Wk, Wk.mir_tab, Wk.G.s, [n](int b) { return n >> (b + 1); }, Wk.G.w, Wk.w_anch.p, Wk.w_anch2.p, Wk.mir_c, Wk.mir_c2, Wk.mir_part,
+                 Wk.mir_ntile, Wk.mir_nrow);
+    Wk.mir_built = true; Wk.mir_w = Wk.G.w;
+}
+
+// the nets (pass 0) / self nets (pass 1) a window of width x cuts, per column into w_hist and as prefix sums into w_E
+template <typename TC>
+static void win_hist_scan(cp_csr_s *A, LayerWork<TC> &Wk, int64_t x, int pass)
+{
+    hipStream_t s = A->stream;
+    const int64_t n = A->n;
+    if (pass == 1 || A->N == 0) CP_HIP(hipMemsetAsync(Wk.w_hist.p, 0, sizeof(int32_t) * (size_t)(n + 1), s));
+    if (pass == 0) { if (A->N > 0) hipLaunchKernelGGL(k_win_hist, dim3((unsigned)cdiv(n + 1, 256)), dim3(256), 0, s, n, x, A->pos32.p, A->prev.p, A->next.p, Wk.w_hist.p); }
+    else if (A->m > 0) hipLaunchKernelGGL(k_win_hist_rows, dim3((unsigned)cdiv(A->m, 256)), dim3(256), 0, s, A->m, n, x, A->rfirst.p, A->rlast.p, Wk.w_hist.p);
+    exclusive_scan_i32(Wk.w_hist.p, Wk.w_E.p, n + 1, Wk.scratch, s);
 }
 
 // anchors of the mirrored head tasks of the windowed layers (k_win_*): once per (pattern, w)
@@ -2767,10 +2806,7 @@ static void win_build(cp_csr_s *A, LayerWork<TC> &Wk)
         make_round(R, true, 0, sb + 1, n, 0, n, Wk.G, Wk.win_aoff);
         const unsigned wg = (unsigned)std::min<int64_t>(cdiv(acc, 4), 65536);
         for (int pass = 0; pass < (Wk.hyp ? 2 : 1); pass++) {
-            if (pass == 1 || A->N == 0) CP_HIP(hipMemsetAsync(Wk.w_hist.p, 0, sizeof(int32_t) * (size_t)(n + 1), s));
-            if (pass == 0) { if (A->N > 0) hipLaunchKernelGGL(k_win_hist, dim3((unsigned)cdiv(n + 1, 256)), dim3(256), 0, s, n, w, A->pos32.p, A->prev.p, A->next.p, Wk.w_hist.p); }
-            else if (A->m > 0) hipLaunchKernelGGL(k_win_hist_rows, dim3((unsigned)cdiv(A->m, 256)), dim3(256), 0, s, A->m, n, w, A->rfirst.p, A->rlast.p, Wk.w_hist.p);
-            exclusive_scan_i32(Wk.w_hist.p, Wk.w_E.p, n + 1, Wk.scratch, s);
+            win_hist_scan<TC>(A, Wk, w, pass);
             if (pass == 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_win_block_totals<true>), dim3(wg), dim3(256), 0, s, R, acc, A->pos32.p, A->next.p, Wk.w_tot.p);
             else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_win_block_totals<false>), dim3(wg), dim3(256), 0, s, R, acc, A->fpos32.p, A->flast.p, Wk.w_tot.p);
             hipLaunchKernelGGL(k_win_anchors, dim3((unsigned)cdiv(acc, 256)), dim3(256), 0, s, R, acc, pass == 0 ? A->pos.p : A->lpos.p, Wk.w_E.p, Wk.w_tot.p,
@@ -2786,10 +2822,7 @@ static void win_build(cp_csr_s *A, LayerWork<TC> &Wk)
         Wk.leaf_anch.alloc((size_t)ng);
         if (Wk.hyp) Wk.leaf_anch2.alloc((size_t)ng);
         for (int pass = 0; pass < (Wk.hyp ? 2 : 1); pass++) {
-            if (pass == 1 || A->N == 0) CP_HIP(hipMemsetAsync(Wk.w_hist.p, 0, sizeof(int32_t) * (size_t)(n + 1), s));
-            if (pass == 0) { if (A->N > 0) hipLaunchKernelGGL(k_win_hist, dim3((unsigned)cdiv(n + 1, 256)), dim3(256), 0, s, n, w - 62, A->pos32.p, A->prev.p, A->next.p, Wk.w_hist.p); }
-            else if (A->m > 0) hipLaunchKernelGGL(k_win_hist_rows, dim3((unsigned)cdiv(A->m, 256)), dim3(256), 0, s, A->m, n, w - 62, A->rfirst.p, A->rlast.p, Wk.w_hist.p);
-            exclusive_scan_i32(Wk.w_hist.p, Wk.w_E.p, n + 1, Wk.scratch, s);
+            win_hist_scan<TC>(A, Wk, w - 62, pass);
             hipLaunchKernelGGL(k_leaf_anchors, dim3((unsigned)cdiv(ng, 256)), dim3(256), 0, s, ng, n, pass == 0 ? A->pos.p : A->lpos.p, Wk.w_E.p,
                                pass == 0 ? Wk.leaf_anch.p : Wk.leaf_anch2.p);
         }
@@ -2803,11 +2836,11 @@ template <typename TC, bool HYP>
 static void launch_gap(hipStream_t s, cp_csr_s *A, LayerWork<TC> &Wk, int tau, int nchunk, int gnr, RoundCounts *rc, int64_t n, const TC *W,
                        const DevModel<TC> &M, TC alpha, unsigned gg, unsigned gs_grid, unsigned gm, unsigned gslow_grid, int blk)
 {
-    GapCtx<TC, HYP> C{reinterpret_cast<const Best<TC, HYP> *>(Wk.o_part.p), reinterpret_cast<const Best<TC, HYP> *>(Wk.o_sub.p), Wk.o_spv.p, Wk.o_spec.p,
-                      Wk.o_tilePS.p, HYP ? Wk.o_tilePS2.p : nullptr, A->pos32.p, A->next.p, HYP ? A->fpos32.p : nullptr, HYP ? A->flast.p : nullptr, W, blk};
-    auto *gs = reinterpret_cast<GapSegRec<TC, HYP> *>(Wk.g_seg.p);
-    const int32_t *lp = HYP ? A->lpos32.p : nullptr, *lf = HYP ? A->lfirst.p : nullptr;
-    int32_t *nl = HYP ? Wk.nlopt.p : nullptr;
+    GapCtx<TC, HYP> C{recs<HYP>(Wk.o_part), recs<HYP>(Wk.o_sub), Wk.o_spv.p, Wk.o_spec.p, Wk.o_tilePS.p, if_hyp<HYP>(Wk.o_tilePS2.p), A->pos32.p, A->next.p,
+                      if_hyp<HYP>(A->fpos32.p), if_hyp<HYP>(A->flast.p), W, blk};
+    auto *gs = reinterpret_cast<GapSegRec<TC, HYP> *>(Wk.g_seg.p);      // (sized for the larger record, like the Best buffers)
+    const int32_t *lp = if_hyp<HYP>(A->lpos32.p), *lf = if_hyp<HYP>(A->lfirst.p);
+    int32_t *nl = if_hyp<HYP>(Wk.nlopt.p);
 #define GF_ARGS tau, nchunk, rc, n, Wk.o_toffs.p, C, Wk.o_tdesc.p, Wk.o_tb.p, Wk.o_rlen.p, A->prev.p, lp, lf, M, alpha, Wk.opt.p, Wk.nnopt.p, nl, Wk.fin.p, \
                 Wk.g_list.p, Wk.g_slot.p, Wk.fin_stamp, Wk.g_slow.p
     if (gnr == 2) {
@@ -2828,45 +2861,33 @@ static void launch_gap(hipStream_t s, cp_csr_s *A, LayerWork<TC> &Wk, int tau, i
 
 constexpr int64_t LB_MAX = 1 << 20;      // largest scan (elements) done in a single launch
 
-// the same for the mirrored heads of the windowed geometry (once per pattern and window width; after win_build: the counts carry
-// the heads' anchors)
-template <typename TC>
-static void ra_build_mir(cp_csr_s *A, LayerWork<TC> &Wk)
+// Round A from a cached table T with the counts cnt / cnt2: the column-major kernel over the candidate tiles [tile0, tile1)
+// (`mirrored`: the table of the mirrored heads) or the row-major one over the table's `ntile` tiles, then the rows of more than LT
+// candidates (nrow_merge of them) merge their partials in `part`.
+template <typename TC, bool HYP>
+static void launch_round_a(hipStream_t s, cp_csr_s *A, LayerWork<TC> &Wk, const TC *W, const DevModel<TC> &M, TC alpha, const RATab &T, const DBuf<int32_t> &cnt,
+                           const DBuf<int32_t> &cnt2, const DBuf<Best<TC, true>> &part, int64_t ntile, int64_t nrow_merge, int64_t tile0, int64_t tile1,
+                           int bmin, bool mirrored, bool colmajor)
 {
-    hipStream_t s = A->stream;
-    const int64_t n = A->n;
-    const bool hyp = Wk.hyp;
-    const Geo G = Wk.G;
-    RATab &T = Wk.mir_tab;
-    memset(&T, 0, sizeof(T));
-    T.nbits = G.s; T.n = n; T.mir_w = G.w;
-    for (int b = 0; b < 33; b++) { T.tlo[b] = 0; T.thi[b] = INT64_MAX; T.aoff[b] = b < 32 ? Wk.win_aoff[b] : 0; }
-    int64_t tb = 0, rb = 0;
-    for (int b = 0; b < 33; b++) {
-        T.tbase[b] = tb; T.rbase[b] = rb;
-        if (b >= G.s) continue;
-        const int64_t nrows = n >> (b + 1);                  // rows (u + 1) 2^(b+1) <= n
-        tb += cdiv(nrows << b, LT);
-        if (b >= 9) rb += nrows;
-    }
-    Wk.mir_ntile = tb; Wk.mir_nrow = rb;
-    const size_t total = (size_t)tb * LT;
-    Wk.mir_c.ensure(total + 8);
-    if (hyp) Wk.mir_c2.ensure(total + 8);
-    Wk.mir_part.ensure((size_t)std::max<int64_t>(1, tb - T.tbase[9]));
-    Wk.mir_built = true; Wk.mir_w = G.w;
-    if (tb <= 0) return;
-    DBuf<int64_t> &Gs = Wk.ra_G, &scratch = Wk.scratch;
-    Gs.ensure(total + 1);
-    hipLaunchKernelGGL(k_ra_colcount, dim3((unsigned)tb), dim3(LT), 0, s, T, A->pos32.p, A->next.p, hyp ? A->fpos32.p : (const int32_t *)nullptr,
-                       hyp ? A->flast.p : (const int32_t *)nullptr, Wk.mir_c.p, hyp ? Wk.mir_c2.p : (int32_t *)nullptr);
-    exclusive_scan_i32(Wk.mir_c.p, Gs.p, (int64_t)total, scratch, s);
-    hipLaunchKernelGGL(k_ra_final, dim3((unsigned)tb), dim3(LT), 0, s, T, Gs.p, Wk.mir_c.p, (const int32_t *)Wk.w_anch.p);
-    if (hyp) {
-        exclusive_scan_i32(Wk.mir_c2.p, Gs.p, (int64_t)total, scratch, s);
-        hipLaunchKernelGGL(k_ra_final, dim3((unsigned)tb), dim3(LT), 0, s, T, Gs.p, Wk.mir_c2.p, (const int32_t *)Wk.w_anch2.p);
-    }
+    int32_t *nl = if_hyp<HYP>(Wk.nlopt.p);
+    if (colmajor)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(mirrored ? k_ra_cols<TC, HYP, true> : k_ra_cols<TC, HYP, false>), dim3((unsigned)std::max<int64_t>(1, cdiv(tile1 - tile0, 4))), dim3(256), 0, s,
+                           T, cnt.p, if_hyp<HYP>(cnt2.p), A->pos32.p, W, M, alpha, Wk.opt.p, Wk.nnopt.p, nl, recs<HYP>(part), tile0, tile1, bmin);
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ra_layer<TC, HYP>), dim3((unsigned)cdiv(ntile, 4)), dim3(256), 0, s, T, ntile, cnt.p, if_hyp<HYP>(cnt2.p), A->pos32.p, W, M,
+                           alpha, Wk.opt.p, Wk.nnopt.p, nl, recs<HYP>(part));
+    if (nrow_merge > 0)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ra_merge<TC, HYP>), dim3((unsigned)cdiv(nrow_merge, 4)), dim3(256), 0, s, T, nrow_merge, recs<HYP>(part), Wk.opt.p,
+                           Wk.nnopt.p, nl);
     CP_HIP(hipGetLastError());
+}
+
+// cp_set_option("dbg", DBG_POISON [+ DBG_POISON_ZERO]): fills buffers a stage must write before it reads (null: not of this variant)
+static void poison_fill(hipStream_t s, std::initializer_list<std::pair<void *, size_t>> bufs)
+{
+    if (!(g_opt_dbg & DBG_POISON)) return;
+    const int pat = (g_opt_dbg & DBG_POISON_ZERO) ? 0x00 : 0x7F;
+    for (const auto &b : bufs) if (b.first) CP_HIP(hipMemsetAsync(b.first, pat, b.second, s));
 }
 
 // Runs the rounds of one layer.  `spec`: the per-round counts of the PREVIOUS layer (Wk.pred) size the grids, the buffers and
@@ -2874,13 +2895,13 @@ static void ra_build_mir(cp_csr_s *A, LayerWork<TC> &Wk)
 // grid strides, so a wrong prediction costs time, never correctness -- except a stage skipped or a buffer too small, which
 // run_layer reports (false) after the layer and the caller redoes the layer with spec = false: one host sync per round brings
 // the exact counts back before the dependent launches (the only mode of the first layer).
-template <typename TC>
+template <typename TC, bool HYP>
 static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W, TC *cst_out, int32_t *ptr_out, LayerWork<TC> &Wk,
-                      int64_t rlo, int64_t rhi, bool spec, bool allow_force = true)
+                      int64_t rlo, int64_t rhi, bool spec, bool allow_force)
 {
     hipStream_t s = A->stream;
     const int64_t n = A->n;
-    const bool hyp = Wk.hyp;
+    constexpr bool hyp = HYP;                              // (== Wk.hyp: dp_total_layer picks the instance)
     const Geo G = Wk.G;
     const int nbits = G.win ? G.s + 1 : Wk.nbits;          // windowed layers: planes 0 .. s
     const double avg_deg = n > 0 ? (double)A->N / (double)n : 0.0;
@@ -2890,7 +2911,7 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
     // (16 B + 16 B per 256 steps).  (Round 1 priced a step at 4 deg + 24 B -- 8-byte column pointers and a per-step descriptor share
     // the kernels do not read -- which put the achieved rate above the box's copy rate.)
     const double step_bytes = 4.0 * (avg_deg + self_deg) + 12.0 + 32.0 / (double)LT;
-    const bool own_tiles = !(g_opt_dbg & 64);      // cp_set_option("dbg", 64): keep every long task in the flattened space
+    const bool own_tiles = !(g_opt_dbg & DBG_NO_OWN_TILES);      // (keep every long task in the flattened space)
     const int NR = nbits + 1;
     CP_HIP(hipMemsetAsync(Wk.rc.p, 0, sizeof(RoundCounts) * (size_t)NR, s));
     const bool gaps = own_tiles && g_opt_gap_tau >= 0;
@@ -2927,6 +2948,8 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
     // (s >= 6) and no per-block table is asked for
     const bool leaf = g_opt_leaf && (!G.win || (G.s >= LEAF_T && !g_opt_block_tables && Wk.leaf_anch.p));
     Wk.planes_full = !leaf || g_opt_block_tables;
+    // round A from the cached counts leaves the levels below LEAF_T to the leaf pass (DBG_RA_ALL_LEVELS: all levels, as without it)
+    const int ra_bmin = (leaf && !Wk.planes_full && !(g_opt_dbg & DBG_RA_ALL_LEVELS)) ? LEAF_T : 0;
     // `fin` flags hold the layer's stamp: no 240 MB clear per layer (every attempt of a layer -- a redo included -- takes a new stamp)
     if (++Wk.fin_stamp > 255 || Wk.fin_stamp <= 0) { CP_HIP(hipMemsetAsync(Wk.fin.p, 0, Wk.fin.bytes(), s)); Wk.fin_stamp = 1; }
     std::vector<RoundCounts> used((size_t)NR);          // what the host sized each round with
@@ -2946,65 +2969,29 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
         if (rd == 0 && g_opt_ra_cache && rlo <= 1 && rhi >= n && n >= 1 && !G.win) {
             // a full layer: round A of the rows' lowest blocks from the cached counts; what is left of round A below is the
             // last row in its upper planes
-            if (!Wk.ra_built) { ProfScope ps(PROF_LINKS, s, 0.0); ra_build<TC>(A, Wk); }
+            if (!Wk.ra_built) { ProfScope ps(PROF_LINKS, s, 0.0); ra_build_std<TC>(A, Wk); }
             ProfScope ps(PROF_RA, s, 16.0 * (double)Wk.ra_ntile * LT);
-            const bool colmajor = !(g_opt_dbg & 262144);       // (dbg 262144: the row-major kernel k_ra_layer)
-            const unsigned cgrid = (unsigned)cdiv(cdiv(n, LT), 4);
-            const int ra_bmin = (leaf && !Wk.planes_full && !(g_opt_dbg & 33554432)) ? LEAF_T : 0;      // (dbg 33554432: all levels, as without the leaf pass)
-            if (colmajor && hyp)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ra_cols<TC, true, false>), dim3(cgrid), dim3(256), 0, s, Wk.ra_tab, Wk.ra_c.p, Wk.ra_c2.p, A->pos32.p, W, M, alpha,
-                                   Wk.opt.p, Wk.nnopt.p, Wk.nlopt.p, Wk.ra_part.p, (int64_t)0, cdiv(n, LT), ra_bmin);
-            else if (colmajor)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ra_cols<TC, false, false>), dim3(cgrid), dim3(256), 0, s, Wk.ra_tab, Wk.ra_c.p, (const int32_t *)nullptr, A->pos32.p, W, M, alpha,
-                                   Wk.opt.p, Wk.nnopt.p, (int32_t *)nullptr, reinterpret_cast<Best<TC, false> *>(Wk.ra_part.p), (int64_t)0, cdiv(n, LT), ra_bmin);
-            if (hyp) {
-                if (!colmajor)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ra_layer<TC, true>), dim3((unsigned)cdiv(Wk.ra_ntile, 4)), dim3(256), 0, s, Wk.ra_tab, Wk.ra_ntile, Wk.ra_c.p, Wk.ra_c2.p,
-                                   A->pos32.p, W, M, alpha, Wk.opt.p, Wk.nnopt.p, Wk.nlopt.p, Wk.ra_part.p);
-                if (Wk.ra_nrow > 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ra_merge<TC, true>), dim3((unsigned)cdiv(Wk.ra_nrow, 4)), dim3(256), 0, s, Wk.ra_tab, Wk.ra_nrow,
-                                                       Wk.ra_part.p, Wk.opt.p, Wk.nnopt.p, Wk.nlopt.p);
-            } else {
-                auto *pa = reinterpret_cast<Best<TC, false> *>(Wk.ra_part.p);
-                if (!colmajor)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ra_layer<TC, false>), dim3((unsigned)cdiv(Wk.ra_ntile, 4)), dim3(256), 0, s, Wk.ra_tab, Wk.ra_ntile, Wk.ra_c.p,
-                                   (const int32_t *)nullptr, A->pos32.p, W, M, alpha, Wk.opt.p, Wk.nnopt.p, (int32_t *)nullptr, pa);
-                if (Wk.ra_nrow > 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ra_merge<TC, false>), dim3((unsigned)cdiv(Wk.ra_nrow, 4)), dim3(256), 0, s, Wk.ra_tab, Wk.ra_nrow,
-                                                       pa, Wk.opt.p, Wk.nnopt.p, (int32_t *)nullptr);
-            }
-            CP_HIP(hipGetLastError());
+            launch_round_a<TC, HYP>(s, A, Wk, W, M, alpha, Wk.ra_tab, Wk.ra_c, Wk.ra_c2, Wk.ra_part, Wk.ra_ntile, Wk.ra_nrow, 0, cdiv(n, LT), ra_bmin, false,
+                                    !(g_opt_dbg & DBG_RA_ROWMAJOR));
             R.a_nmain = 0; R.ntask = R.nextra + R.nlast;
         }
-        if (rd == 0 && g_opt_ra_cache && G.win && G.s >= 1 && n >= 1 && !(g_opt_dbg & 1048576)) {
+        if (rd == 0 && g_opt_ra_cache && G.win && G.s >= 1 && n >= 1 && !(g_opt_dbg & DBG_WIN_NO_RA_CACHE)) {
             // Windowed layer: the STANDARD heads of round A (rows with ctz == b < s, block [r - 2^b, r)) are the unconstrained scheme's
             // round-A rows of the levels below s -- same blocks, same layer-independent counts: k_ra_cols computes them for all rows
             // from the cache (60 B per candidate) and the generic round keeps the mirrored and common heads only.  The heads the layer
             // reads are those make_round lists -- within 2^(b+1) of the row tile in plane b <= s: their blocks start at rlo - 3 * 2^s or later.
-            if (!Wk.ra_built) { ProfScope ps(PROF_LINKS, s, 0.0); ra_build<TC>(A, Wk); }
+            if (!Wk.ra_built) { ProfScope ps(PROF_LINKS, s, 0.0); ra_build_std<TC>(A, Wk); }
             RATab T2 = Wk.ra_tab;
             T2.nbits = std::min<int32_t>(G.s, Wk.ra_tab.nbits);
             const int64_t nrow2 = T2.nbits > 9 ? Wk.ra_tab.rbase[T2.nbits] : 0;
             const int64_t c_lo = std::max<int64_t>(0, (rlo > 0 ? rlo : 0) - ((int64_t)4 << G.s)), c_hi = std::min<int64_t>(n, rhi);
             const int64_t tile0 = c_lo / LT, tile1 = cdiv(c_hi, LT);
             ProfScope ps(PROF_RA, s, 60.0 * (double)(tile1 - tile0) * LT);
-            const unsigned cgrid = (unsigned)std::max<int64_t>(1, cdiv(tile1 - tile0, 4));
             // (the standard heads below LEAF_T are rows inside a leaf group: the leaf pass computes them; the MIRRORED heads of those
             //  levels include the multiples of 64 -- every row has a task in every plane -- and stay)
-            const int ra_bmin2 = (leaf && !Wk.planes_full && !(g_opt_dbg & 33554432)) ? LEAF_T : 0;
-            if (hyp) {
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ra_cols<TC, true, false>), dim3(cgrid), dim3(256), 0, s, T2, Wk.ra_c.p, Wk.ra_c2.p, A->pos32.p, W, M, alpha,
-                                   Wk.opt.p, Wk.nnopt.p, Wk.nlopt.p, Wk.ra_part.p, tile0, tile1, ra_bmin2);
-                if (nrow2 > 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ra_merge<TC, true>), dim3((unsigned)cdiv(nrow2, 4)), dim3(256), 0, s, T2, nrow2,
-                                                  Wk.ra_part.p, Wk.opt.p, Wk.nnopt.p, Wk.nlopt.p);
-            } else {
-                auto *pa = reinterpret_cast<Best<TC, false> *>(Wk.ra_part.p);
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ra_cols<TC, false, false>), dim3(cgrid), dim3(256), 0, s, T2, Wk.ra_c.p, (const int32_t *)nullptr, A->pos32.p, W, M, alpha,
-                                   Wk.opt.p, Wk.nnopt.p, (int32_t *)nullptr, pa, tile0, tile1, ra_bmin2);
-                if (nrow2 > 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ra_merge<TC, false>), dim3((unsigned)cdiv(nrow2, 4)), dim3(256), 0, s, T2, nrow2,
-                                                  pa, Wk.opt.p, Wk.nnopt.p, (int32_t *)nullptr);
-            }
-            CP_HIP(hipGetLastError());
+            launch_round_a<TC, HYP>(s, A, Wk, W, M, alpha, T2, Wk.ra_c, Wk.ra_c2, Wk.ra_part, Wk.ra_ntile, nrow2, tile0, tile1, ra_bmin, false, true);
             R.skip_std = 1;
-            if (!(g_opt_dbg & 2097152)) {
+            if (!(g_opt_dbg & DBG_WIN_NO_MIR_CACHE)) {
                 // the MIRRORED heads the same way, from their own table (row-major kernel; per level the tiles of the rows near the window)
                 if (!Wk.mir_built || Wk.mir_w != G.w) { ProfScope ps2(PROF_LINKS, s, 0.0); ra_build_mir<TC>(A, Wk); }
                 if (Wk.mir_ntile > 0) {
@@ -3018,30 +3005,11 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
                         elems += (double)std::max<int64_t>(0, T3.thi[b] - T3.tlo[b]) * LT;
                     }
                     // column-major like the standard heads (z = p + w + 1: the blocks of the rows r_lo .. r_hi lie in [r_lo, r_hi + 2^s)); the
-                    // row-major kernel (dbg 8388608) reads 16 B per (candidate, level) instead of 4
-                    const bool mcols = !(g_opt_dbg & 8388608);
+                    // row-major kernel reads 16 B per (candidate, level) instead of 4
+                    const bool mcols = !(g_opt_dbg & DBG_MIR_ROWMAJOR);
                     const int64_t zt0 = r_lo / LT, zt1 = cdiv(std::min<int64_t>(n + G.w + 1, r_hi + ((int64_t)1 << G.s) + 1), LT);
                     ProfScope ps2(PROF_RA, s, mcols ? 80.0 * (double)(zt1 - zt0) * LT : 16.0 * elems);
-                    const unsigned mgrid = (unsigned)std::max<int64_t>(1, cdiv(zt1 - zt0, 4));
-                    if (hyp) {
-                        if (mcols) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ra_cols<TC, true, true>), dim3(mgrid), dim3(256), 0, s, T3, Wk.mir_c.p, Wk.mir_c2.p, A->pos32.p, W, M, alpha,
-                                                      Wk.opt.p, Wk.nnopt.p, Wk.nlopt.p, Wk.mir_part.p, zt0, zt1, 0);
-                        else
-                        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ra_layer<TC, true>), dim3((unsigned)cdiv(Wk.mir_ntile, 4)), dim3(256), 0, s, T3, Wk.mir_ntile, Wk.mir_c.p, Wk.mir_c2.p,
-                                           A->pos32.p, W, M, alpha, Wk.opt.p, Wk.nnopt.p, Wk.nlopt.p, Wk.mir_part.p);
-                        if (Wk.mir_nrow > 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ra_merge<TC, true>), dim3((unsigned)cdiv(Wk.mir_nrow, 4)), dim3(256), 0, s, T3, Wk.mir_nrow,
-                                                                Wk.mir_part.p, Wk.opt.p, Wk.nnopt.p, Wk.nlopt.p);
-                    } else {
-                        auto *pm = reinterpret_cast<Best<TC, false> *>(Wk.mir_part.p);
-                        if (mcols) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ra_cols<TC, false, true>), dim3(mgrid), dim3(256), 0, s, T3, Wk.mir_c.p, (const int32_t *)nullptr, A->pos32.p, W, M,
-                                                      alpha, Wk.opt.p, Wk.nnopt.p, (int32_t *)nullptr, pm, zt0, zt1, 0);
-                        else
-                        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ra_layer<TC, false>), dim3((unsigned)cdiv(Wk.mir_ntile, 4)), dim3(256), 0, s, T3, Wk.mir_ntile, Wk.mir_c.p,
-                                           (const int32_t *)nullptr, A->pos32.p, W, M, alpha, Wk.opt.p, Wk.nnopt.p, (int32_t *)nullptr, pm);
-                        if (Wk.mir_nrow > 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ra_merge<TC, false>), dim3((unsigned)cdiv(Wk.mir_nrow, 4)), dim3(256), 0, s, T3, Wk.mir_nrow,
-                                                                pm, Wk.opt.p, Wk.nnopt.p, (int32_t *)nullptr);
-                    }
-                    CP_HIP(hipGetLastError());
+                    launch_round_a<TC, HYP>(s, A, Wk, W, M, alpha, T3, Wk.mir_c, Wk.mir_c2, Wk.mir_part, Wk.mir_ntile, Wk.mir_nrow, zt0, zt1, 0, true, mcols);
                     R.skip_mir = 1;
                 }
             }
@@ -3054,31 +3022,25 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
         // launches, ~40 us) typically serves three or four medium tasks.  Where the last layer that ran it saw at most force_max (1024), every task
         // that is not finished in setup gets tiles of its own instead, and the stage disappears from the round.
         const bool forced = allow_force && own_tiles && !gap && !R.isA && (size_t)rd < Wk.force_own.size() && Wk.force_own[(size_t)rd] &&
-                            (rhi - rlo + 1) <= 2 * Wk.force_rows && !(g_opt_dbg & 524288);
+                            (rhi - rlo + 1) <= 2 * Wk.force_rows && !(g_opt_dbg & DBG_NO_FORCE_OWN);
         any_forced |= forced;
         if (!R.isA) {
             int64_t cols = (((n >> R.tau) + 1) >> 1) << R.tau;
             ProfScope ps(PROF_RPASS, s, 4.0 * (avg_deg + self_deg) * (double)cols + 8.0 * (double)R.ntask);
             if (((int64_t)1 << R.tau) > g_opt_rpass_ch)   // several chunks per row accumulate with atomics: clear first
                 hipLaunchKernelGGL(k_setup, dim3((unsigned)cdiv(R.ntask, 256)), dim3(256), 0, s, R, Wk.opt.p, Wk.nnopt.p, Wk.cr.p, 1,
-                                   Wk.tdesc.p, A->pos32.p, Wk.tb.p, Wk.len.p, (const int32_t *)nullptr, hyp ? Wk.crl.p : (int32_t *)nullptr,
-                                   (int32_t *)nullptr);
+                                   Wk.tdesc.p, A->pos32.p, Wk.tb.p, Wk.len.p, (const int32_t *)nullptr, if_hyp<HYP>(Wk.crl.p), (int32_t *)nullptr);
             launch_rpass(s, R, nbits, n, rlo, rhi, A->pos.p, A->prev.p, 0, Wk.opt.p, Wk.cr.p, avg_deg);                   // prev[q] < B
             if (hyp) launch_rpass(s, R, nbits, n, rlo, rhi, A->lpos.p, A->lfirst.p, 1, Wk.opt.p, Wk.crl.p, self_deg);      // rows ending in the column with first >= B
         }
         if (R.isA && R.nlast > 0) {
             CP_HIP(hipMemsetAsync(Wk.last_s0.p, 0, Wk.last_s0.bytes(), s));
-            hipLaunchKernelGGL(k_last_row_counts, dim3(1024), dim3(256), 0, s, R, A->pos32.p, A->prev.p, hyp ? A->lpos32.p : (const int32_t *)nullptr,
-                               hyp ? A->lfirst.p : (const int32_t *)nullptr, Wk.last_s0.p, Wk.fin.p);
+            hipLaunchKernelGGL(k_last_row_counts, dim3(1024), dim3(256), 0, s, R, A->pos32.p, A->prev.p, if_hyp<HYP>(A->lpos32.p), if_hyp<HYP>(A->lfirst.p),
+                               Wk.last_s0.p, Wk.fin.p);
         }
         {
             // per task: four gathers from the plane arrays + the record; short tasks also step over their columns here
             ProfScope ps(PROF_SETUP, s, 29.0 * (double)R.ntask);
-#define SS_ARGS R, Wk.opt.p, Wk.nnopt.p, Wk.nlopt.p, Wk.cr.p, Wk.crl.p, A->pos32.p, A->next.p, hyp ? A->fpos32.p : (const int32_t *)nullptr,   \
-                hyp ? A->flast.p : (const int32_t *)nullptr, W, M, alpha, Wk.tdesc.p, Wk.tb.p, Wk.len.p, Wk.tS0l.p, &rc->nlong,               \
-                (int32_t)g_opt_short_t, (int32_t)g_opt_short_e, own_tiles ? Wk.o_tdesc.p : (int4 *)nullptr, Wk.o_tb.p, Wk.o_rlen.p, Wk.o_ntl.p,            \
-                Wk.o_tS0l.p, &rc->nown, &rc->own_steps, (int32_t)(forced ? 2 : gap ? g_opt_gap_min : g_opt_own_min),                                         \
-                (int32_t)std::min<size_t>(Wk.o_ntl.n, (size_t)INT32_MAX), &rc->err, Wk.fin.p, Wk.last_s0.p, (g_opt_dbg & 4096) ? &rc->_pad : (int32_t *)nullptr, Wk.w_anch.p, Wk.w_anch2.p, pzp, oblk
             const int sbs = (int)g_opt_setup_bs;          // lanes per block: one list atomic per block, but the block's waves meet at two barriers
             dim3 sgrid((unsigned)cdiv(R.ntask, sbs));
             if (!R.isA) {                                // one grid row per bit plane above tau
@@ -3086,9 +3048,13 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
                 for (int bb = R.tau + 1; bb < nbits; bb++) mx = std::max<int64_t>(mx, R.tbase[bb + 1] - R.tbase[bb]);
                 sgrid = dim3((unsigned)cdiv(mx, sbs), (unsigned)std::max(1, nbits - R.tau - 1));
             }
-            if (hyp) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_setup_short<TC, true>), sgrid, dim3(sbs), 0, s, SS_ARGS);
-            else     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_setup_short<TC, false>), sgrid, dim3(sbs), 0, s, SS_ARGS);
-#undef SS_ARGS
+            // (nlopt, crl, tS0l, o_tS0l and w_anch2 are read by the hyperedge variant only; null or stale for the other)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_setup_short<TC, HYP>), sgrid, dim3(sbs), 0, s, R, Wk.opt.p, Wk.nnopt.p, Wk.nlopt.p, Wk.cr.p, Wk.crl.p, A->pos32.p,
+                               A->next.p, if_hyp<HYP>(A->fpos32.p), if_hyp<HYP>(A->flast.p), W, M, alpha, Wk.tdesc.p, Wk.tb.p, Wk.len.p, Wk.tS0l.p, &rc->nlong,
+                               (int32_t)g_opt_short_t, (int32_t)g_opt_short_e, own_tiles ? Wk.o_tdesc.p : (int4 *)nullptr, Wk.o_tb.p, Wk.o_rlen.p, Wk.o_ntl.p,
+                               Wk.o_tS0l.p, &rc->nown, &rc->own_steps, (int32_t)(forced ? 2 : gap ? g_opt_gap_min : g_opt_own_min),
+                               (int32_t)std::min<size_t>(Wk.o_ntl.n, (size_t)INT32_MAX), &rc->err, Wk.fin.p, Wk.last_s0.p,
+                               (g_opt_dbg & DBG_COUNT_NONTRIVIAL) ? &rc->_pad : (int32_t *)nullptr, Wk.w_anch.p, Wk.w_anch2.p, pzp, oblk);
         }
         RoundCounts P;                                   // the counts this round is sized with
         if (spec) {
@@ -3098,7 +3064,7 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
                 P.nlong = (int32_t)sc(P.nlong); P.nown = (int32_t)sc(P.nown); P.T = sc(P.T); P.NT = sc(P.NT);
                 P.own_steps = (unsigned long long)sc((int64_t)P.own_steps);
             }
-            if ((g_opt_dbg & 1024) && (rd & 1)) { P.nown = 0; P.NT = 0; P.nlong = 0; P.T = 0; }      // test: a prediction that skips stages with work
+            if ((g_opt_dbg & DBG_MISPREDICT) && (rd & 1)) { P.nown = 0; P.NT = 0; P.nlong = 0; P.T = 0; }      // test: a prediction that skips stages with work
             // buffers from the prediction (grown only here; the round's verdict, k_round_scans, checks the true totals against them)
             Wk.ensure_own((size_t)grow(P.NT));
             Wk.ensure_flat((size_t)grow(P.T));
@@ -3106,7 +3072,7 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
         {
             // both scans read their element count on the device; one launch holds them and the round's verdict
             ProfScope ps(PROF_SCAN, s, 12.0 * (double)R.ntask);
-            const bool tiny = spec && (g_opt_dbg & 2048);       // test: pretend the buffers sized from the prediction are too small
+            const bool tiny = spec && (g_opt_dbg & DBG_TINY_BUFFERS);       // test: pretend the buffers sized from the prediction are too small
             const int64_t capT = spec ? (tiny ? (int64_t)64 : (int64_t)Wk.loc.n) : INT64_MAX, capNT = spec ? (tiny ? (int64_t)1 : (int64_t)Wk.o_rec.n) : INT64_MAX;
             const int64_t nm = std::min<int64_t>(R.ntask, (int64_t)Wk.o_ntl.n);
             if (R.ntask <= LB_MAX) {
@@ -3125,18 +3091,13 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
             Wk.ensure_flat((size_t)P.T);
         }
         used[(size_t)rd] = P;
-        if (g_opt_dbg & 8) fprintf(stderr, "round isA=%d tau=%d ntask=%lld %s long=%d own=%d T=%lld NT=%lld nontrivial=%d\n", R.isA, R.tau, (long long)R.ntask,
+        if (g_opt_dbg & DBG_PRINT_ROUNDS) fprintf(stderr, "round isA=%d tau=%d ntask=%lld %s long=%d own=%d T=%lld NT=%lld nontrivial=%d\n", R.isA, R.tau, (long long)R.ntask,
                                    spec ? "predicted" : "exact", P.nlong, P.nown, (long long)P.T, (long long)P.NT, P._pad);
         if (P.nown > 0 && P.NT > 0) {
             // ---- long tasks with tiles of their own: map, stream + evaluate, merge
             const int64_t gNT = spec ? (int64_t)Wk.o_rec.n : P.NT, gown = spec ? grow(P.nown) : P.nown;      // (capacity >= the true NT, checked)
-            if (g_opt_dbg & 128) {                // poison what this block must write before it reads
-                int pat = (g_opt_dbg & 256) ? 0x00 : 0x7F;
-                CP_HIP(hipMemsetAsync(Wk.o_part.p, pat, Wk.o_part.bytes(), s));
-                CP_HIP(hipMemsetAsync(Wk.o_tileS.p, pat, Wk.o_tileS.bytes(), s));
-                CP_HIP(hipMemsetAsync(Wk.o_rec.p, pat, Wk.o_rec.bytes(), s));
-                if (hyp) CP_HIP(hipMemsetAsync(Wk.o_tileS2.p, pat, Wk.o_tileS2.bytes(), s));
-            }
+            poison_fill(s, {{Wk.o_part.p, Wk.o_part.bytes()}, {Wk.o_tileS.p, Wk.o_tileS.bytes()}, {Wk.o_rec.p, Wk.o_rec.bytes()},
+                            {if_hyp<HYP>(Wk.o_tileS2.p), Wk.o_tileS2.bytes()}});
             const unsigned mgrid = (unsigned)std::min<int64_t>(cdiv(gNT, 256), 8192);
             hipLaunchKernelGGL(k_own_map, dim3(mgrid), dim3(256), 0, s, rc, Wk.o_toffs.p, Wk.o_tdesc.p, Wk.o_rlen.p, Wk.o_rec.p, Wk.o_task.p,
                                Wk.o_tb.p, gap ? Wk.o_hi.p : (int32_t *)nullptr, R.tau, n, oblk, oblk ? Wk.b_cnt.p : (int32_t *)nullptr, Wk.o_brank.p);
@@ -3146,18 +3107,11 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
                     exclusive_scan_i32_lb(Wk.b_cnt.p, Wk.b_start.p, Wk.b_n.p, Wk.b_nblk, nullptr, Wk.scanws, s);
                     hipLaunchKernelGGL(k_blk_order, dim3(mgrid), dim3(256), 0, s, rc, Wk.o_rec.p, Wk.o_brank.p, Wk.b_start.p, Wk.o_border.p, Wk.b_cnt.p);
                 }
-#define LO_ARGS R.isA, rc, oblk ? Wk.o_border.p : (const int32_t *)nullptr, A->pos32.p, A->next.p, hyp ? A->fpos32.p : (const int32_t *)nullptr, hyp ? A->flast.p : (const int32_t *)nullptr,            \
-                Wk.o_tileS.p, Wk.o_tileS2.p, Wk.o_rec.p, W, M, alpha
-#define LO_TAIL R.tau, Wk.o_hi.p, Wk.o_spec.p, (int)((g_opt_dbg & 512) != 0)
-                Best<TC, false> *sb0 = reinterpret_cast<Best<TC, false> *>(Wk.o_sub.p);
-                unsigned og = (unsigned)cdiv(gNT, 4);
-                Best<TC, false> *pp0 = reinterpret_cast<Best<TC, false> *>(Wk.o_part.p);
-                if (hyp) { if (gap) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lpass_own<TC, true, true>), dim3(og), dim3(256), 0, s, LO_ARGS, Wk.o_part.p, LO_TAIL, Wk.o_sub.p, Wk.o_spv.p, A->col.p, A->ffirst.p);
-                           else     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lpass_own<TC, true, false>), dim3(og), dim3(256), 0, s, LO_ARGS, Wk.o_part.p, LO_TAIL, Wk.o_sub.p, Wk.o_spv.p, A->col.p, A->ffirst.p); }
-                else     { if (gap) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lpass_own<TC, false, true>), dim3(og), dim3(256), 0, s, LO_ARGS, pp0, LO_TAIL, sb0, Wk.o_spv.p, A->col.p, (const int32_t *)nullptr);
-                           else     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lpass_own<TC, false, false>), dim3(og), dim3(256), 0, s, LO_ARGS, pp0, LO_TAIL, sb0, Wk.o_spv.p, A->col.p, (const int32_t *)nullptr); }
-#undef LO_TAIL
-#undef LO_ARGS
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(gap ? k_lpass_own<TC, HYP, true> : k_lpass_own<TC, HYP, false>), dim3((unsigned)cdiv(gNT, 4)), dim3(256), 0, s,
+                                   R.isA, rc,
+                                   oblk ? Wk.o_border.p : (const int32_t *)nullptr, A->pos32.p, A->next.p, if_hyp<HYP>(A->fpos32.p), if_hyp<HYP>(A->flast.p),
+                                   Wk.o_tileS.p, Wk.o_tileS2.p, Wk.o_rec.p, W, M, alpha, recs<HYP>(Wk.o_part), R.tau, Wk.o_hi.p, Wk.o_spec.p,
+                                   (int)((g_opt_dbg & DBG_GAP_ALL_SPECIAL) != 0), recs<HYP>(Wk.o_sub), Wk.o_spv.p, A->col.p, if_hyp<HYP>(A->ffirst.p));
             }
             note(rd, 0, gap ? PROF_GAPSTREAM : PROF_OWN);
             if (gap) {
@@ -3183,58 +3137,34 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
                 unsigned gs_grid = (unsigned)std::min<int64_t>(cdiv((int64_t)(2 * ncap) * nchunk, 4), 8192);
                 unsigned gm = (unsigned)std::min<int64_t>(cdiv((int64_t)ncap * nchunk, 4), 4096);
                 const unsigned gslow_grid = 2048;                               // (grid-stride over the device-side counts n_gslow / n_sslow: usually none)
-                if (hyp) launch_gap<TC, true>(s, A, Wk, R.tau, nchunk, gnr, rc, n, W, M, alpha, gg, gs_grid, gm, gslow_grid, oblk);
-                else launch_gap<TC, false>(s, A, Wk, R.tau, nchunk, gnr, rc, n, W, M, alpha, gg, gs_grid, gm, gslow_grid, oblk);
+                launch_gap<TC, HYP>(s, A, Wk, R.tau, nchunk, gnr, rc, n, W, M, alpha, gg, gs_grid, gm, gslow_grid, oblk);
             } else {
                 ProfScope ps(PROF_FIX, s, 24.0 * (double)P.NT);
                 // one lane per task: single tiles are final already, short tasks are merged on the spot, the rest is listed and
                 // merged by one block per task
                 unsigned lgrid = (unsigned)std::min<int64_t>(cdiv(gown, 256), 4096), wgrid = (unsigned)std::min<int64_t>(gown, 8192);
-#define FO_ARGS rc, Wk.o_toffs.p
-#define FO_TAIL Wk.o_tdesc.p, Wk.o_tb.p
-                if (hyp) {
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fix_own_lane<TC, true>), dim3(lgrid), dim3(256), 0, s, FO_ARGS, Wk.o_part.p, FO_TAIL, Wk.o_tS0l.p,
-                                       Wk.o_tileS.p, Wk.o_tileS2.p, M, Wk.opt.p, Wk.nnopt.p, Wk.nlopt.p, n + 1, Wk.o_wide.p);
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fix_own<TC, true>), dim3(wgrid), dim3(256), 0, s, FO_ARGS, Wk.o_part.p, FO_TAIL,
-                                       Wk.o_tS0l.p, Wk.o_tileS.p, Wk.o_tileS2.p, M, Wk.opt.p, Wk.nnopt.p, Wk.nlopt.p, n + 1, Wk.o_wide.p);
-                } else {
-                    const Best<TC, false> *pp = reinterpret_cast<const Best<TC, false> *>(Wk.o_part.p);
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fix_own_lane<TC, false>), dim3(lgrid), dim3(256), 0, s, FO_ARGS, pp, FO_TAIL, (const int32_t *)nullptr,
-                                       Wk.o_tileS.p, (const int32_t *)nullptr, M, Wk.opt.p, Wk.nnopt.p, (int32_t *)nullptr, n + 1, Wk.o_wide.p);
-                    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fix_own<TC, false>), dim3(wgrid), dim3(256), 0, s, FO_ARGS, pp, FO_TAIL,
-                                       (const int32_t *)nullptr, Wk.o_tileS.p, (const int32_t *)nullptr, M, Wk.opt.p, Wk.nnopt.p, (int32_t *)nullptr, n + 1, Wk.o_wide.p);
-                }
-#undef FO_ARGS
-#undef FO_TAIL
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fix_own_lane<TC, HYP>), dim3(lgrid), dim3(256), 0, s, rc, Wk.o_toffs.p, recs<HYP>(Wk.o_part), Wk.o_tdesc.p, Wk.o_tb.p,
+                                   if_hyp<HYP>(Wk.o_tS0l.p), Wk.o_tileS.p, if_hyp<HYP>(Wk.o_tileS2.p), M, Wk.opt.p, Wk.nnopt.p, if_hyp<HYP>(Wk.nlopt.p), n + 1, Wk.o_wide.p);
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fix_own<TC, HYP>), dim3(wgrid), dim3(256), 0, s, rc, Wk.o_toffs.p, recs<HYP>(Wk.o_part), Wk.o_tdesc.p, Wk.o_tb.p,
+                                   if_hyp<HYP>(Wk.o_tS0l.p), Wk.o_tileS.p, if_hyp<HYP>(Wk.o_tileS2.p), M, Wk.opt.p, Wk.nnopt.p, if_hyp<HYP>(Wk.nlopt.p), n + 1, Wk.o_wide.p);
             }
             CP_HIP(hipGetLastError());
         }
         if (P.nlong <= 0 || P.T <= 0) continue;
         // ---- from here on the round consists of the flattened tasks only (their number: rc->nlong)
         const int64_t gtile = spec ? (int64_t)Wk.tileS.n : cdiv(P.T, LT);      // (capacity >= the true tile count, checked)
-        if (g_opt_dbg & 128) {                    // poison everything a round must write before it reads
-            int pat = (g_opt_dbg & 256) ? 0x00 : 0x7F;
-            CP_HIP(hipMemsetAsync(Wk.loc.p, pat, Wk.loc.bytes(), s));
-            if (hyp) CP_HIP(hipMemsetAsync(Wk.loc2.p, pat, Wk.loc2.bytes(), s));
-            CP_HIP(hipMemsetAsync(Wk.partL.p, pat, Wk.partL.bytes(), s));
-            CP_HIP(hipMemsetAsync(Wk.partR.p, pat, Wk.partR.bytes(), s));
-            CP_HIP(hipMemsetAsync(Wk.tileS.p, pat, Wk.tileS.bytes(), s));
-            if (hyp) CP_HIP(hipMemsetAsync(Wk.tileS2.p, pat, Wk.tileS2.bytes(), s));
-        }
+        poison_fill(s, {{Wk.loc.p, Wk.loc.bytes()}, {if_hyp<HYP>(Wk.loc2.p), Wk.loc2.bytes()}, {Wk.partL.p, Wk.partL.bytes()}, {Wk.partR.p, Wk.partR.bytes()},
+                        {Wk.tileS.p, Wk.tileS.bytes()}, {if_hyp<HYP>(Wk.tileS2.p), Wk.tileS2.bytes()}});
         hipLaunchKernelGGL(k_tile_t0, dim3((unsigned)cdiv(gtile, 256)), dim3(256), 0, s, rc, Wk.offs.p, Wk.tdesc.p, Wk.tile_t0.p,
-                           Wk.tile_rec.p, (int)((g_opt_dbg & 32) != 0), Wk.taskR.p);
+                           Wk.tile_rec.p, (int)((g_opt_dbg & DBG_NO_INTERIOR) != 0), Wk.taskR.p);
         {
             // algorithmic bytes of one launch: per flattened step the stepped column's link
             // entries (4 B x N/n, plus 4 B x nonempty-rows/n for hyperedge costs), its colptr entry (8 B), the
             // candidate's previous-layer cost (8 B) and the task-descriptor share (offsets/B/anchor/row, amortised 8 B)
             ProfScope ps(PROF_EXPAND, s, (double)P.T * step_bytes);
-#define LP_ARGS R, rc, Wk.offs.p, Wk.tdesc.p, Wk.tS0l.p, Wk.tb.p, A->pos32.p, A->next.p, hyp ? A->fpos32.p : (const int32_t *)nullptr,           \
-                hyp ? A->flast.p : (const int32_t *)nullptr, Wk.opt.p, Wk.nnopt.p, Wk.nlopt.p, Wk.loc.p, Wk.loc2.p, Wk.tileS.p, Wk.tileS2.p,     \
-                Wk.taskR.p, Wk.tile_t0.p, Wk.tile_rec.p, W, M, alpha
-            if (hyp) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lpass<TC, true>), dim3((unsigned)cdiv(gtile, 4)), dim3(256), 0, s, LP_ARGS, Wk.partR.p, Wk.partL.p);
-            else     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lpass<TC, false>), dim3((unsigned)cdiv(gtile, 4)), dim3(256), 0, s, LP_ARGS,
-                                        reinterpret_cast<Best<TC, false> *>(Wk.partR.p), reinterpret_cast<Best<TC, false> *>(Wk.partL.p));
-#undef LP_ARGS
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lpass<TC, HYP>), dim3((unsigned)cdiv(gtile, 4)), dim3(256), 0, s, R, rc, Wk.offs.p, Wk.tdesc.p, Wk.tS0l.p, Wk.tb.p,
+                               A->pos32.p, A->next.p, if_hyp<HYP>(A->fpos32.p), if_hyp<HYP>(A->flast.p), Wk.opt.p, Wk.nnopt.p, Wk.nlopt.p, Wk.loc.p, Wk.loc2.p,
+                               Wk.tileS.p, Wk.tileS2.p, Wk.taskR.p, Wk.tile_t0.p, Wk.tile_rec.p, W, M, alpha, recs<HYP>(Wk.partR), recs<HYP>(Wk.partL));
         }
         note(rd, 1, PROF_EXPAND);
         {
@@ -3245,29 +3175,17 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
         unsigned wgrid = (unsigned)std::min<int64_t>(cdiv(gtile, 4), 8192);     // the wave kernels walk work lists
         {
             ProfScope ps(PROF_EVAL, s, 0.0);
-#define SP_ARGS R, rc, Wk.offs.p, Wk.tdesc.p, Wk.tS0l.p, Wk.tb.p, A->pos32.p, Wk.loc.p, Wk.loc2.p, Wk.tile_t0.p, Wk.taskR.p, Wk.tileS.p, Wk.tileS2.p
-            if (hyp) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_span_short<TC, true>), dim3((unsigned)cdiv(gtile, 256)), dim3(256), 0, s, SP_ARGS,
-                               Wk.partR.p, W, M, alpha, Wk.opt.p, Wk.nnopt.p, Wk.nlopt.p, Wk.open_list.p, Wk.fix_list.p, Wk.tile_rec.p);
-            else     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_span_short<TC, false>), dim3((unsigned)cdiv(gtile, 256)), dim3(256), 0, s, SP_ARGS,
-                               reinterpret_cast<const Best<TC, false> *>(Wk.partR.p), W, M, alpha, Wk.opt.p, Wk.nnopt.p, (int32_t *)nullptr,
-                               Wk.open_list.p, Wk.fix_list.p, Wk.tile_rec.p);
-#undef SP_ARGS
-#define OP_ARGS R, rc, Wk.offs.p, Wk.tdesc.p, Wk.tS0l.p, A->pos32.p, Wk.loc.p, Wk.loc2.p, Wk.tile_t0.p, Wk.tilePS.p
-            if (hyp) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_open<TC, true>), dim3(wgrid), dim3(256), 0, s, OP_ARGS, Wk.tilePS2.p, W, M, alpha, Wk.partL.p,
-                               Wk.open_list.p);
-            else     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_open<TC, false>), dim3(wgrid), dim3(256), 0, s, OP_ARGS, (const int64_t *)nullptr, W, M, alpha,
-                               reinterpret_cast<Best<TC, false> *>(Wk.partL.p), Wk.open_list.p);
-#undef OP_ARGS
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_span_short<TC, HYP>), dim3((unsigned)cdiv(gtile, 256)), dim3(256), 0, s, R, rc, Wk.offs.p, Wk.tdesc.p, Wk.tS0l.p,
+                               Wk.tb.p, A->pos32.p, Wk.loc.p, Wk.loc2.p, Wk.tile_t0.p, Wk.taskR.p, Wk.tileS.p, Wk.tileS2.p, recs<HYP>(Wk.partR), W, M, alpha,
+                               Wk.opt.p, Wk.nnopt.p, if_hyp<HYP>(Wk.nlopt.p), Wk.open_list.p, Wk.fix_list.p, Wk.tile_rec.p);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_open<TC, HYP>), dim3(wgrid), dim3(256), 0, s, R, rc, Wk.offs.p, Wk.tdesc.p, Wk.tS0l.p, A->pos32.p, Wk.loc.p,
+                               Wk.loc2.p, Wk.tile_t0.p, Wk.tilePS.p, if_hyp<HYP>(Wk.tilePS2.p), W, M, alpha, recs<HYP>(Wk.partL), Wk.open_list.p);
         }
         {
             ProfScope ps(PROF_FIX, s, 8.0 * (double)cdiv(P.T, LT));
-            if (hyp) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fix<TC, true>), dim3(wgrid), dim3(256), 0, s, rc, Wk.offs.p, Wk.taskR.p,
-                               Wk.partL.p, Wk.partR.p, Wk.tdesc.p, Wk.tb.p, Wk.opt.p, Wk.nnopt.p, Wk.nlopt.p, n + 1, Wk.fix_list.p,
-                               Wk.tile_rec.p, Wk.tilePS.p, Wk.tilePS2.p, Wk.tS0l.p, M);
-            else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fix<TC, false>), dim3(wgrid), dim3(256), 0, s, rc, Wk.offs.p, Wk.taskR.p,
-                               reinterpret_cast<const Best<TC, false> *>(Wk.partL.p), reinterpret_cast<const Best<TC, false> *>(Wk.partR.p),
-                               Wk.tdesc.p, Wk.tb.p, Wk.opt.p, Wk.nnopt.p, (int32_t *)nullptr, n + 1, Wk.fix_list.p,
-                               Wk.tile_rec.p, Wk.tilePS.p, (const int64_t *)nullptr, (const int32_t *)nullptr, M);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fix<TC, HYP>), dim3(wgrid), dim3(256), 0, s, rc, Wk.offs.p, Wk.taskR.p, recs<HYP>(Wk.partL), recs<HYP>(Wk.partR),
+                               Wk.tdesc.p, Wk.tb.p, Wk.opt.p, Wk.nnopt.p, if_hyp<HYP>(Wk.nlopt.p), n + 1, Wk.fix_list.p, Wk.tile_rec.p, Wk.tilePS.p,
+                               if_hyp<HYP>(Wk.tilePS2.p), if_hyp<HYP>(Wk.tS0l.p), M);
         }
         CP_HIP(hipGetLastError());
     }
@@ -3286,48 +3204,37 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
             // allocation: a range of millions of candidates per group, seconds of work for a layer that is redone anyway).  Such a
             // group flags the layer (err) and skips the plane.
             const int32_t lcap = (gaps && g_opt_gap_tau >= LEAF_T) ? (int32_t)std::max<int64_t>(g_opt_gap_min, 2) : INT32_MAX;
-            LeafArgs<TC, false> L0{n, g0, g1 - g0 + 1, c0, c1, nbits, (int32_t)(g_opt_block_tables != 0), A->pos32.p, A->prev.p, A->next.p, A->col.p,
-                                   nullptr, nullptr, nullptr, nullptr, nullptr, Wk.opt.p, Wk.nnopt.p, nullptr, Wk.fin.p, Wk.fin_stamp, W, M, alpha, cst_out, ptr_out,
-                                   G, Wk.leaf_anch.p, nullptr, lcap, &Wk.rc.p->err, pzp};
-            if (hyp) {
-                LeafArgs<TC, true> L1{n, g0, g1 - g0 + 1, c0, c1, nbits, (int32_t)(g_opt_block_tables != 0), A->pos32.p, A->prev.p, A->next.p, A->col.p,
-                                      A->fpos32.p, A->flast.p, A->ffirst.p, A->lpos32.p, A->lfirst.p, Wk.opt.p, Wk.nnopt.p, Wk.nlopt.p, Wk.fin.p, Wk.fin_stamp, W, M, alpha,
-                                      cst_out, ptr_out, G, Wk.leaf_anch.p, Wk.leaf_anch2.p, lcap, &Wk.rc.p->err, pzp};
-                const unsigned lg = (unsigned)cdiv(L1.ngroups, LeafWPB<true>::v);
-                if (need <= 18) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_leaf<TC, true, 18>), dim3(lg), dim3(64 * LeafWPB<true>::v), 0, s, L1);
-                else             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_leaf<TC, true, 25>), dim3(lg), dim3(64 * LeafWPB<true>::v), 0, s, L1);
-            } else {
-                const unsigned lg = (unsigned)cdiv(L0.ngroups, LeafWPB<false>::v);
-                if (need <= 18) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_leaf<TC, false, 18>), dim3(lg), dim3(64 * LeafWPB<false>::v), 0, s, L0);
-                else             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_leaf<TC, false, 25>), dim3(lg), dim3(64 * LeafWPB<false>::v), 0, s, L0);
-            }
+            LeafArgs<TC, HYP> L{};
+            L.n = n; L.g0 = g0; L.ngroups = g1 - g0 + 1; L.c0 = c0; L.c1 = c1; L.nbits = nbits; L.planes = (int32_t)(g_opt_block_tables != 0);
+            L.pos = A->pos32.p; L.prev = A->prev.p; L.next = A->next.p; L.col = A->col.p;
+            L.fpos = if_hyp<HYP>(A->fpos32.p); L.flast = if_hyp<HYP>(A->flast.p); L.ffirst = if_hyp<HYP>(A->ffirst.p);
+            L.lpos = if_hyp<HYP>(A->lpos32.p); L.lfirst = if_hyp<HYP>(A->lfirst.p);
+            L.opt = Wk.opt.p; L.nnopt = Wk.nnopt.p; L.nlopt = if_hyp<HYP>(Wk.nlopt.p); L.fin = Wk.fin.p; L.fin_stamp = Wk.fin_stamp;
+            L.W = W; L.M = M; L.alpha = alpha; L.cst = cst_out; L.ptr = ptr_out; L.G = G;
+            L.anchM = Wk.leaf_anch.p; L.anchM2 = if_hyp<HYP>(Wk.leaf_anch2.p); L.lcap = lcap; L.err = &Wk.rc.p->err; L.pz = pzp;
+            constexpr int WPB = LeafWPB<HYP>::v;
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(need <= 18 ? k_leaf<TC, HYP, 18> : k_leaf<TC, HYP, 25>), dim3((unsigned)cdiv(L.ngroups, WPB)), dim3(64 * WPB), 0, s, L);
             CP_HIP(hipGetLastError());
         }
     }
-    if (leaf) {
-        ProfScope ps(PROF_COMBINE, s, 24.0 * (double)((n >> LEAF_T) + 1));
+    {
+        // the rows left: with the leaf pass the multiples of 64 (their planes from LEAF_T up), without it every row.  Threads in row
+        // order.  (lvl = 1, DBG_COMBINE_BY_SLOT: in plane-slot order, so that the dozen plane reads of a row are contiguous across a
+        // wave -- measured 867 us against 650 us at config 3: the 2 x 12 gathers W[p], pos[p] of a row are what counts, and they are
+        // neighbours only for neighbouring rows.)
+        ProfScope ps(PROF_COMBINE, s, 24.0 * (double)(leaf ? (n >> LEAF_T) + 1 : n + 1));
         const int64_t c0 = rlo > 0 ? rlo : 0, c1 = rhi < n ? rhi : n;
-        const int64_t f0 = (c0 + LEAF_G - 1) >> LEAF_T, f1 = c1 >> LEAF_T;       // the multiples of 64 in [c0, c1]
-        if (c1 >= c0 && f1 >= f0 && G.win)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_combine_win<TC>), dim3((unsigned)cdiv(f1 - f0 + 1, 256)), dim3(256), 0, s, 0, G, n, f0, f1, A->pos32.p,
-                           Wk.opt.p, Wk.nnopt.p, hyp ? Wk.nlopt.p : (const int32_t *)nullptr, W, M, alpha, cst_out, ptr_out, LEAF_T, pzp);
-        else if (c1 >= c0 && f1 >= f0)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_combine<TC>), dim3((unsigned)cdiv(f1 - f0 + 1, 256)), dim3(256), 0, s, 0, n, f0, f1, nbits, A->pos32.p,
-                           Wk.opt.p, Wk.nnopt.p, hyp ? Wk.nlopt.p : (const int32_t *)nullptr, W, M, alpha, cst_out, ptr_out, LEAF_T, pzp);
-    } else {
-        ProfScope ps(PROF_COMBINE, s, 24.0 * (double)(n + 1));
-        int64_t c0 = rlo > 0 ? rlo : 0, c1 = rhi < n ? rhi : n;
-        // threads in row order.  (lvl = 1, cp_set_option("dbg", 16384): in plane-slot order, so that the dozen plane reads of a row are
-        // contiguous across a wave -- measured 867 us against 650 us at config 3: the 2 x 12 gathers W[p], pos[p] of a row are what
-        // counts, and they are neighbours only for neighbouring rows.)
-        const int lvl = (g_opt_dbg & 16384) ? (2 * (c1 - c0 + 1) >= n + 1) : 0;
-        const int64_t nthr = lvl ? n + 1 : c1 - c0 + 1;
-        if (c1 >= c0 && G.win)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_combine_win<TC>), dim3((unsigned)cdiv(nthr, 256)), dim3(256), 0, s, lvl, G, n, c0, c1, A->pos32.p,
-                           Wk.opt.p, Wk.nnopt.p, hyp ? Wk.nlopt.p : (const int32_t *)nullptr, W, M, alpha, cst_out, ptr_out, 0, pzp);
-        else if (c1 >= c0)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_combine<TC>), dim3((unsigned)cdiv(nthr, 256)), dim3(256), 0, s, lvl, n, c0, c1, nbits, A->pos32.p,
-                           Wk.opt.p, Wk.nnopt.p, hyp ? Wk.nlopt.p : (const int32_t *)nullptr, W, M, alpha, cst_out, ptr_out, 0, pzp);
+        const int64_t r0 = leaf ? (c0 + LEAF_G - 1) >> LEAF_T : c0, r1 = leaf ? c1 >> LEAF_T : c1;       // leaf: the multiples of 64 in [c0, c1]
+        const int lvl = (!leaf && (g_opt_dbg & DBG_COMBINE_BY_SLOT)) ? (2 * (c1 - c0 + 1) >= n + 1) : 0;
+        const int sh = leaf ? LEAF_T : 0;
+        const int32_t *nl = if_hyp<HYP>(Wk.nlopt.p);
+        if (c1 >= c0 && r1 >= r0) {
+            const unsigned cgrid = (unsigned)cdiv(lvl ? n + 1 : r1 - r0 + 1, 256);
+            if (G.win) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_combine_win<TC>), dim3(cgrid), dim3(256), 0, s, lvl, G, n, r0, r1, A->pos32.p, Wk.opt.p, Wk.nnopt.p, nl, W, M,
+                                          alpha, cst_out, ptr_out, sh, pzp);
+            else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_combine<TC>), dim3(cgrid), dim3(256), 0, s, lvl, n, r0, r1, nbits, A->pos32.p, Wk.opt.p, Wk.nnopt.p, nl, W, M, alpha,
+                                    cst_out, ptr_out, sh, pzp);
+        }
     }
     CP_HIP(hipGetLastError());
     // ---- the true counts of every round: the next layer's prediction, this layer's verdict
@@ -3381,7 +3288,8 @@ void dp_total_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W, T
     CP_REQUIRE(nbits <= NBMAX, CP_EINVAL, "n exceeds the bit-plane budget");
     if (Wk.n != n || Wk.hyp != hyp) {
         // (the shape is recorded only after every allocation succeeded: a hipMalloc failure leaves n == -1 and the next call starts over)
-        Wk.n = -1; Wk.nbits = nbits; Wk.hyp = hyp; Wk.pred_ok = false; Wk.ra_built = false; Wk.win_built = false; Wk.mir_built = false; Wk.force_own.clear(); Wk.force_rows = 0;      // (the window anchors of a hyperedge model carry a second array)
+        Wk.n = -1; Wk.nbits = nbits; Wk.hyp = hyp;
+        Wk.forget();                                // (the window anchors of a hyperedge model carry a second array)
         Wk.o_rec.release(); Wk.loc.release();       // (the per-tile arrays are re-made for the new shape on first use)
         size_t plane = (size_t)nbits * (size_t)(n + 1);
         Wk.opt.alloc(plane); Wk.nnopt.alloc(plane); Wk.cr.alloc(plane);
@@ -3434,11 +3342,16 @@ void dp_total_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W, T
         else Wk.pred_scale = b / a;
     }
     if (Wk.pred_win != G.win || Wk.pred_w != G.w || (int)Wk.force_own.size() != (G.win ? G.s + 1 : Wk.nbits) + 1) { Wk.force_own.clear(); Wk.force_rows = 0; }      // (another geometry: other rounds)
-    if (run_layer<TC>(A, M, alpha, W, cst_out, ptr_out, Wk, rlo, rhi, spec)) return;
+    // the layer's variant is chosen here, once: everything below is instantiated for it
+    auto run = [&](bool sp, bool allow_force) {
+        return hyp ? run_layer<TC, true>(A, M, alpha, W, cst_out, ptr_out, Wk, rlo, rhi, sp, allow_force)
+                   : run_layer<TC, false>(A, M, alpha, W, cst_out, ptr_out, Wk, rlo, rhi, sp, allow_force);
+    };
+    if (run(spec, true)) return;
     // the prediction missed (a stage that had been empty, or a buffer too small): the same layer again with exact counts
     g_spec_redo++;
     Wk.force_own.clear(); Wk.force_rows = 0;
-    bool ok = run_layer<TC>(A, M, alpha, W, cst_out, ptr_out, Wk, rlo, rhi, false, false);
+    bool ok = run(false, false);
     CP_REQUIRE(ok, CP_EINTERNAL, "DP layer failed with exact counts");
 }
 
@@ -3475,17 +3388,16 @@ template int dp_total_block_tables<int64_t>(cp_csr_s *, void *, int64_t *, int64
 template int dp_total_block_tables<double>(cp_csr_s *, void *, int64_t *, int64_t *, int64_t *);
 
 template <typename TC> void *dp_total_work_new() { return new LayerWork<TC>(); }
-template <typename TC> static void work_free_fn(void *w) { delete reinterpret_cast<LayerWork<TC> *>(w); }
-template <typename TC> static void work_reset_fn(void *w) { auto *W = reinterpret_cast<LayerWork<TC> *>(w); W->ra_built = false; W->pred_ok = false; W->win_built = false; W->mir_built = false; W->force_own.clear(); W->force_rows = 0; }
+template <typename TC> void dp_total_work_free(void *w) { delete reinterpret_cast<LayerWork<TC> *>(w); }
+template <typename TC> static void work_reset_fn(void *w) { reinterpret_cast<LayerWork<TC> *>(w)->forget(); }
 template <typename TC> void *dp_total_work_get(cp_csr_s *A)
 {
     const int i = sizeof(TC) == sizeof(double) && ((TC)0.5 != (TC)0) ? 1 : 0;
-    if (!A->dp_work[i]) { A->dp_work[i] = new LayerWork<TC>(); A->dp_work_free_fn[i] = work_free_fn<TC>; A->dp_work_reset_fn[i] = work_reset_fn<TC>; }
+    if (!A->dp_work[i]) { A->dp_work[i] = new LayerWork<TC>(); A->dp_work_free_fn[i] = dp_total_work_free<TC>; A->dp_work_reset_fn[i] = work_reset_fn<TC>; }
     return A->dp_work[i];
 }
 template void *dp_total_work_get<int64_t>(cp_csr_s *);
 template void *dp_total_work_get<double>(cp_csr_s *);
-template <typename TC> void dp_total_work_free(void *w) { delete reinterpret_cast<LayerWork<TC> *>(w); }
 
 template void dp_total_layer<int64_t>(cp_csr_s *, const DevModel<int64_t> &, int64_t, const int64_t *, int64_t *, int32_t *, void *, int64_t, int64_t, int64_t);
 template void dp_total_layer<double>(cp_csr_s *, const DevModel<double> &, double, const double *, double *, int32_t *, void *, int64_t, int64_t, int64_t);

@@ -276,7 +276,8 @@ int32_t cp_test_round_scans(const int32_t *a, int64_t na, int64_t na_max, const 
  * per run of "bn_run" rows in lockstep, 2 = default: searched crossings for Int64 costs), "bn_slack" (columns of the start bracket), "lws" (1,
  * default: cp_pack_dynamic past the scan -- any width, a monotone work budget, no constraint -- runs the on-line divide and conquer of
  * csrc/chunk_lws.hip; 0: the one-wave kernel), "lws_leaf" (its rows per leaf wave: 256, 512, 1024 or 2048), "prof_only" slot (events on one profile slot only), "dbg"
- * (diagnostic bit mask).  Unknown names return CP_EINVAL. */
+ * (diagnostic bit mask: the bits are named in csrc/dp.hpp, enum DbgBit, and tabulated in DESIGN.md section 4e).  Unknown names
+ * return CP_EINVAL. */
 int32_t cp_set_option(const char *name, int64_t value);
 /* built-in per-kernel HIP-event timing of the named hot kernels on the launch stream */
 int32_t cp_prof_enable(int32_t on);
