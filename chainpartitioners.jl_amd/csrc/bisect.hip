@@ -405,7 +405,7 @@ using namespace cpk;
 extern "C" int32_t cp_partition_bisect_cost_batch(cp_csr_t A, int64_t B, const int64_t *K, const cp_model_t *models, const double *eps,
                                                   const int32_t *flip, int64_t ld, int64_t *spl_out)
 {
-    try {
+    return guarded([&]() -> int32_t {
         CP_REQUIRE(A && K && models && eps && spl_out && B >= 1 && B <= 65535, CP_EINVAL, "bad argument");
         for (int64_t b = 0; b < B; b++) {
             CP_REQUIRE(K[b] >= 1 && K[b] + 1 <= ld, CP_EINVAL, "every request needs 1 <= K and K + 1 <= ld");
@@ -413,23 +413,28 @@ extern "C" int32_t cp_partition_bisect_cost_batch(cp_csr_t A, int64_t B, const i
                        "a batch takes Work / Connectivity models of one element type");
         }
         CP_HIP(hipSetDevice(A->device));
-        if (models[0].dtype == CP_I64) return run_bisect_batch<int64_t>(A, B, K, models, eps, flip, ld, spl_out);
-        return run_bisect_batch<double>(A, B, K, models, eps, flip, ld, spl_out);
-    } CP_CATCH_ALL
+        return with_cost_type(models[0].dtype, [&](auto tag) { return run_bisect_batch<decltype(tag)>(A, B, K, models, eps, flip, ld, spl_out); });
+    });
+}
+
+// the cost and the index bisection between (c_lo, c_hi) = bound_stripe(A, K, args..., f) ./ 1  (BisectCostBottleneckSplitter.jl:39)
+static int32_t bisect_entry(cp_csr_t A, int64_t K, const cp_model_t *model, const cp_rowpart_t *Pi, double eps, int32_t flip, int64_t *spl_out,
+                            bool by_index)
+{
+    return guarded([&]() -> int32_t {
+        CP_REQUIRE(A && model && spl_out && K >= 1, CP_EINVAL, "bad argument");
+        CP_HIP(hipSetDevice(A->device));
+        int64_t li, hi; double lf, hf;
+        int32_t rc = cp_bound_stripe_pi(A, K, Pi, model, &li, &hi, &lf, &hf);
+        if (rc != CP_OK) return rc;
+        return with_cost_type(model->dtype, [&](auto tag) { return run_bisect<decltype(tag)>(A, K, model, Pi, lf, hf, eps, flip, spl_out, by_index); });
+    });
 }
 
 extern "C" int32_t cp_partition_bisect_cost_pi(cp_csr_t A, int64_t K, const cp_model_t *model, const cp_rowpart_t *Pi, double eps,
                                                int32_t flip, int64_t *spl_out)
 {
-    try {
-        CP_REQUIRE(A && model && spl_out && K >= 1, CP_EINVAL, "bad argument");
-        CP_HIP(hipSetDevice(A->device));
-        int64_t li, hi; double lf, hf;
-        int32_t rc = cp_bound_stripe_pi(A, K, Pi, model, &li, &hi, &lf, &hf);    // (c_lo, c_hi) = bound_stripe(A, K, args..., f) ./ 1  (:39)
-        if (rc != CP_OK) return rc;
-        if (model->dtype == CP_I64) return run_bisect<int64_t>(A, K, model, Pi, lf, hf, eps, flip, spl_out);
-        return run_bisect<double>(A, K, model, Pi, lf, hf, eps, flip, spl_out);
-    } CP_CATCH_ALL
+    return bisect_entry(A, K, model, Pi, eps, flip, spl_out, false);
 }
 
 extern "C" int32_t cp_partition_bisect_cost(cp_csr_t A, int64_t K, const cp_model_t *model, double eps, int32_t flip, int64_t *spl_out)
@@ -441,15 +446,7 @@ extern "C" int32_t cp_partition_bisect_cost(cp_csr_t A, int64_t K, const cp_mode
 extern "C" int32_t cp_partition_bisect_index_pi(cp_csr_t A, int64_t K, const cp_model_t *model, const cp_rowpart_t *Pi, int32_t flip,
                                                 int64_t *spl_out)
 {
-    try {
-        CP_REQUIRE(A && model && spl_out && K >= 1, CP_EINVAL, "bad argument");
-        CP_HIP(hipSetDevice(A->device));
-        int64_t li, hi; double lf, hf;
-        int32_t rc = cp_bound_stripe_pi(A, K, Pi, model, &li, &hi, &lf, &hf);    // (c_lo, c_hi) = bound_stripe(...) ./ 1  (:39)
-        if (rc != CP_OK) return rc;
-        if (model->dtype == CP_I64) return run_bisect<int64_t>(A, K, model, Pi, lf, hf, 0.0, flip, spl_out, true);
-        return run_bisect<double>(A, K, model, Pi, lf, hf, 0.0, flip, spl_out, true);
-    } CP_CATCH_ALL
+    return bisect_entry(A, K, model, Pi, 0.0, flip, spl_out, true);
 }
 
 extern "C" int32_t cp_partition_bisect_index(cp_csr_t A, int64_t K, const cp_model_t *model, int32_t flip, int64_t *spl_out)

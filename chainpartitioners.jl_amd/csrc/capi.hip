@@ -63,14 +63,6 @@ __global__ void k_apply_model(int64_t nq, const int64_t *__restrict__ P, const i
 }
 
 // ------------------------------------------------------------------ helpers
-template <typename F>
-static int32_t guarded(F &&f)
-{
-    try { return f(); }
-    catch (const HipFail &e) { return e.code; }
-    catch (const std::bad_alloc &) { set_error("host allocation failed"); return CP_EHIP; }
-}
-
 static bool model_known(const cp_model_t *m)
 {
     if (!m || m->kind < CP_MODEL_FEASIBLE || m->kind > CP_MODEL_SYM_EDGE_CUT) return false;
@@ -122,11 +114,66 @@ static int32_t run_oracle_eval(cp_csr_s *A, const cp_model_t *mdl, int64_t nq, c
     return CP_OK;
 }
 
-static int64_t fld_i64(int64_t a, int64_t b)
+// ------------------------------------------------------------------ what differs between the Int64 and the Float64 body of an entry
+static int64_t fld(int64_t a, int64_t b)                    // fld(a, b): Int64 floor division ...
 {
     int64_t q = a / b, r = a % b;
     if (r != 0 && ((r < 0) != (b < 0))) q -= 1;
     return q;
+}
+static double fld(double a, int64_t b) { return std::floor(a / (double)b); }      // ... and floor(a / b) of Float64 costs
+static int64_t max_identity(int64_t) { return INT64_MIN; }                        // objective_identity Costs.jl:23-24
+static double max_identity(double) { return -INFINITY; }
+// Int64 bounds are also reported as Float64 (the bisections search on doubles)
+static void also_f64(const int64_t *lo, const int64_t *hi, double *lo_f64, double *hi_f64) { *lo_f64 = (double)*lo; *hi_f64 = (double)*hi; }
+static void also_f64(const double *, const double *, double *, double *) {}
+
+// cp_oracle_eval with the result in TC's slot of its (Int64, Float64) pair
+template <typename TC>
+static int32_t oracle_eval_into(cp_csr_t A, const cp_model_t *model, const cp_rowpart_t *Pi, int64_t nq, const int64_t *j, const int64_t *jp,
+                                const int64_t *k, TC *out)
+{
+    const bool i64 = std::is_same<TC, int64_t>::value;
+    return cp_oracle_eval(A, model, Pi, CP_HINT_STEP, nq, j, jp, k, i64 ? (int64_t *)out : nullptr, i64 ? nullptr : (double *)out);
+}
+
+// ------------------------------------------------------------------ the counters of cp_get_stat
+// fix_trips: tasks the block merge walked in more than one trip; bits 0 / 1 / 2: a task of 1 / FIX_SERIAL / FIX_SERIAL + 1 tiles was
+// merged.  bn_sym_layers: DP layers the valley search ran for the monotonized symmetric model.  kept: cp_set_option("poison", 1)
+// starts a poison pass by zeroing the other counters and leaves this one.
+static const struct { const char *name; int64_t *var; bool kept; } g_stats[] = {
+    {"spec_redo", &g_spec_redo, false}, {"poison_hits", &g_poison_hits, false}, {"fix_trips", &g_fix_trips, false},
+    {"fix_edges", &g_fix_edges, false}, {"bn_sym_layers", &g_bn_sym_layers, true},
+};
+static void stats_reset(bool all) { for (const auto &c : g_stats) if (all || !c.kept) *c.var = 0; }
+
+// ------------------------------------------------------------------ the options of cp_set_option (DESIGN 4e lists them with their rules)
+enum OptRule { OPT_PLAIN, OPT_BOOL, OPT_CLAMP, OPT_POW2 };      // the value as given | value != 0 | clamped to [lo, hi] | lo doubled until >= value or == hi
+constexpr int64_t NOLIM_LO = INT64_MIN, NOLIM_HI = INT64_MAX;
+static const struct Opt { const char *name; int64_t *var; OptRule rule; int64_t lo, hi; } g_options[] = {
+    {"force_brute", &g_opt_force_brute, OPT_PLAIN, 0, 0}, {"brute_max_n", &g_opt_brute_max_n, OPT_PLAIN, 0, 0}, {"dbg", &g_opt_dbg, OPT_PLAIN, 0, 0},
+    {"short_t", &g_opt_short_t, OPT_PLAIN, 0, 0}, {"short_e", &g_opt_short_e, OPT_PLAIN, 0, 0}, {"ra_cache", &g_opt_ra_cache, OPT_PLAIN, 0, 0},
+    {"leaf", &g_opt_leaf, OPT_PLAIN, 0, 0}, {"block_tables", &g_opt_block_tables, OPT_PLAIN, 0, 0}, {"nospec", &g_opt_nospec, OPT_PLAIN, 0, 0},
+    {"rpass_small_tau", &g_opt_rpass_small_tau, OPT_PLAIN, 0, 0}, {"fixed_point", &g_opt_fixed_point, OPT_PLAIN, 0, 0},
+    {"bn_wave", &g_opt_bn_wave, OPT_PLAIN, 0, 0},
+    {"poison", &g_opt_poison, OPT_PLAIN, 0, 0},                 // (a nonzero value also zeroes the counters of a poison pass)
+    {"pool", &g_opt_pool, OPT_BOOL, 0, 0},                      // (1: keep freed device blocks >= 1 MB for reuse; 0: return them, now and from here on)
+    {"own_blk", &g_opt_own_blk, OPT_BOOL, 0, 0},                // (1, default: own tiles at 256-column blocks, run in block order; 0: tiles counted from each task head, in task order)
+    {"lws", &g_opt_lws, OPT_BOOL, 0, 0},                        // (1, default: DynamicTotalChunker past the scan by chunk_lws.hip; 0: the one-wave kernel)
+    {"gap_tau", &g_opt_gap_tau, OPT_CLAMP, NOLIM_LO, 20}, {"gap_min", &g_opt_gap_min, OPT_CLAMP, 8, NOLIM_HI}, {"gap_nr", &g_opt_gap_nr, OPT_CLAMP, 1, 2},
+    {"force_max", &g_opt_force_max, OPT_CLAMP, 0, NOLIM_HI}, {"rpass_cap", &g_opt_rpass_cap, OPT_CLAMP, 1, NOLIM_HI},
+    {"own_min", &g_opt_own_min, OPT_CLAMP, 64, NOLIM_HI}, {"bn_chunk", &g_opt_bn_chunk, OPT_CLAMP, 1, NOLIM_HI},
+    {"bn_slack", &g_opt_bn_slack, OPT_CLAMP, 0, NOLIM_HI}, {"bn_run", &g_opt_bn_run, OPT_CLAMP, 2, NOLIM_HI},
+    {"rpass_ch", &g_opt_rpass_ch, OPT_POW2, 16, 4096}, {"setup_bs", &g_opt_setup_bs, OPT_POW2, 64, 1024}, {"lws_leaf", &g_opt_lws_leaf, OPT_POW2, 256, 2048},
+};
+static int64_t opt_value(const Opt &o, int64_t value)
+{
+    switch (o.rule) {
+    case OPT_BOOL: return value ? 1 : 0;
+    case OPT_CLAMP: return value < o.lo ? o.lo : value > o.hi ? o.hi : value;
+    case OPT_POW2: { int64_t v = o.lo; while (v < value && v < o.hi) v <<= 1; return v; }
+    default: return value;
+    }
 }
 
 }  // namespace cpk
@@ -231,12 +278,7 @@ int32_t cp_set_stream(cp_csr_t A, void *hip_stream)
 int32_t cp_get_stat(const char *name, int64_t *out)
 {
     if (!name || !out) return CP_EINVAL;
-    if (!strcmp(name, "spec_redo")) { *out = g_spec_redo; return CP_OK; }
-    if (!strcmp(name, "poison_hits")) { *out = g_poison_hits; return CP_OK; }
-    // tasks the block merge walked in more than one trip; bits 0 / 1 / 2: a task of 1 / FIX_SERIAL / FIX_SERIAL + 1 tiles was merged
-    if (!strcmp(name, "fix_trips")) { *out = g_fix_trips; return CP_OK; }
-    if (!strcmp(name, "fix_edges")) { *out = g_fix_edges; return CP_OK; }
-    if (!strcmp(name, "bn_sym_layers")) { *out = g_bn_sym_layers; return CP_OK; }      // DP layers the valley search ran for the monotonized symmetric model
+    for (const auto &c : g_stats) if (!strcmp(name, c.name)) { *out = *c.var; return CP_OK; }
     return CP_EINVAL;
 }
 
@@ -267,36 +309,15 @@ int32_t cp_reset_stream(cp_csr_t A)
 int32_t cp_set_option(const char *name, int64_t value)
 {
     if (!name) return CP_EINVAL;
-    if (!strcmp(name, "force_brute")) { g_opt_force_brute = value; return CP_OK; }
-    if (!strcmp(name, "brute_max_n")) { g_opt_brute_max_n = value; return CP_OK; }
-    if (!strcmp(name, "dbg")) { g_opt_dbg = value; return CP_OK; }
-    if (!strcmp(name, "stat_reset")) { g_poison_hits = 0; g_spec_redo = 0; g_fix_trips = 0; g_fix_edges = 0; g_bn_sym_layers = 0; return CP_OK; }      // the counters of cp_get_stat
-    if (!strcmp(name, "short_t")) { g_opt_short_t = value; return CP_OK; }
-    if (!strcmp(name, "short_e")) { g_opt_short_e = value; return CP_OK; }
-    if (!strcmp(name, "rpass_ch")) { int64_t v = 16; while (v < value && v < 4096) v <<= 1; g_opt_rpass_ch = v; return CP_OK; }
-    if (!strcmp(name, "prof_only")) { g_prof_only = (int)value; return CP_OK; }
-    if (!strcmp(name, "gap_tau")) { g_opt_gap_tau = value > 20 ? 20 : value; return CP_OK; }
-    if (!strcmp(name, "gap_min")) { g_opt_gap_min = value < 8 ? 8 : value; return CP_OK; }
-    if (!strcmp(name, "gap_nr")) { g_opt_gap_nr = value >= 2 ? 2 : 1; return CP_OK; }
-    if (!strcmp(name, "pool")) { g_opt_pool = value ? 1 : 0; if (!value) dev_pool_trim(); return CP_OK; }      // (1: keep freed device blocks >= 1 MB for reuse; 0: return them)
-    if (!strcmp(name, "ra_cache")) { g_opt_ra_cache = value; return CP_OK; }
-    if (!strcmp(name, "leaf")) { g_opt_leaf = value; return CP_OK; }
-    if (!strcmp(name, "poison")) { g_opt_poison = value; if (value) { g_poison_hits = 0; g_spec_redo = 0; g_fix_trips = 0; g_fix_edges = 0; } return CP_OK; }
-    if (!strcmp(name, "block_tables")) { g_opt_block_tables = value; return CP_OK; }
-    if (!strcmp(name, "rpass_small_tau")) { g_opt_rpass_small_tau = value; return CP_OK; }
-    if (!strcmp(name, "force_max")) { g_opt_force_max = value < 0 ? 0 : value; return CP_OK; }
-    if (!strcmp(name, "setup_bs")) { int64_t v = 64; while (v < value && v < 1024) v <<= 1; g_opt_setup_bs = v; return CP_OK; }
-    if (!strcmp(name, "rpass_cap")) { g_opt_rpass_cap = value < 1 ? 1 : value; return CP_OK; }
-    if (!strcmp(name, "fixed_point")) { g_opt_fixed_point = value; return CP_OK; }
-    if (!strcmp(name, "nospec")) { g_opt_nospec = value; return CP_OK; }
-    if (!strcmp(name, "own_min")) { g_opt_own_min = value < 64 ? 64 : value; return CP_OK; }
-    if (!strcmp(name, "own_blk")) { g_opt_own_blk = value ? 1 : 0; return CP_OK; }      // (1, default: own tiles at 256-column blocks, run in block order; 0: tiles counted from each task head, in task order)
-    if (!strcmp(name, "bn_chunk")) { g_opt_bn_chunk = value < 1 ? 1 : value; return CP_OK; }
-    if (!strcmp(name, "bn_wave")) { g_opt_bn_wave = value; return CP_OK; }
-    if (!strcmp(name, "bn_slack")) { g_opt_bn_slack = value < 0 ? 0 : value; return CP_OK; }
-    if (!strcmp(name, "lws")) { g_opt_lws = value ? 1 : 0; return CP_OK; }      // (1, default: DynamicTotalChunker past the scan by chunk_lws.hip; 0: the one-wave kernel)
-    if (!strcmp(name, "lws_leaf")) { int64_t v = 256; while (v < value && v < 2048) v <<= 1; g_opt_lws_leaf = v; return CP_OK; }
-    if (!strcmp(name, "bn_run")) { g_opt_bn_run = value < 2 ? 2 : value; return CP_OK; }
+    if (!strcmp(name, "stat_reset")) { stats_reset(true); return CP_OK; }
+    if (!strcmp(name, "prof_only")) { g_prof_only = (int)value; return CP_OK; }      // (the one option that is not an int64_t)
+    for (const Opt &o : g_options) {
+        if (strcmp(name, o.name)) continue;
+        *o.var = opt_value(o, value);
+        if (o.var == &g_opt_pool && !value) dev_pool_trim();
+        if (o.var == &g_opt_poison && value) stats_reset(false);
+        return CP_OK;
+    }
     set_error("unknown option");
     return CP_EINVAL;
 }
@@ -466,22 +487,16 @@ int32_t cp_objective(cp_csr_t A, int64_t K, const int64_t *spl, const cp_model_t
         }
         std::vector<int64_t> j((size_t)K), jp((size_t)K), kk((size_t)K);
         for (int64_t k = 0; k < K; k++) { j[k] = spl[k]; jp[k] = spl[k + 1]; kk[k] = k + 1; }
-        if (model->dtype == CP_I64) {
-            std::vector<int64_t> v((size_t)K);
-            int32_t rc = cp_oracle_eval(A, model, Pi, CP_HINT_STEP, K, j.data(), jp.data(), kk.data(), v.data(), nullptr);
+        return with_cost_type(model->dtype, [&](auto tag) -> int32_t {
+            using TC = decltype(tag);
+            std::vector<TC> v((size_t)K);
+            int32_t rc = oracle_eval_into<TC>(A, model, Pi, K, j.data(), jp.data(), kk.data(), v.data());
             if (rc != CP_OK) return rc;
-            int64_t acc = combine == CP_COMBINE_SUM ? 0 : INT64_MIN;                  // objective_identity Costs.jl:23-24
+            TC acc = combine == CP_COMBINE_SUM ? (TC)0 : max_identity(tag);             // (Int64 sums wrap: cadd)
             for (int64_t k = 0; k < K; k++) acc = combine == CP_COMBINE_SUM ? cadd(acc, v[k]) : (acc > v[k] ? acc : v[k]);
-            *out_i64 = acc;
-        } else {
-            std::vector<double> v((size_t)K);
-            int32_t rc = cp_oracle_eval(A, model, Pi, CP_HINT_STEP, K, j.data(), jp.data(), kk.data(), nullptr, v.data());
-            if (rc != CP_OK) return rc;
-            double acc = combine == CP_COMBINE_SUM ? 0.0 : -INFINITY;
-            for (int64_t k = 0; k < K; k++) acc = combine == CP_COMBINE_SUM ? acc + v[k] : (acc > v[k] ? acc : v[k]);
-            *out_f64 = acc;
-        }
-        return CP_OK;
+            *pick<TC>(out_i64, out_f64) = acc;
+            return CP_OK;
+        });
     });
 }
 
@@ -489,108 +504,74 @@ int32_t cp_bound_stripe(cp_csr_t A, int64_t K, const cp_model_t *model, int64_t 
 {
     return guarded([&]() -> int32_t {
         CP_REQUIRE(A && model_known(model) && K >= 1, CP_EINVAL, "bad argument");
-        int64_t n = A->n, N = A->N;
-        if (model->kind == CP_MODEL_WORK) {                                            // WorkCosts.jl:39-51
-            if (model->dtype == CP_I64) {
-                int64_t a = model->p_i64[0], bv = model->p_i64[1], bp = model->p_i64[2];
-                *lo_i64 = a + fld_i64(bv * n + bp * N, K);
-                if (bv >= 0 && bp >= 0) *hi_i64 = a + bv * n + bp * N;
-                else if (bv <= 0 && bp <= 0) *hi_i64 = a;
+        return with_cost_type(model->dtype, [&](auto tag) -> int32_t {
+            using TC = decltype(tag);
+            const int64_t n = A->n, N = A->N;
+            auto P = [&](int i) { return model_param<TC>(model, i); };
+            TC *lo = pick<TC>(lo_i64, lo_f64), *hi = pick<TC>(hi_i64, hi_f64);
+            if (model->kind == CP_MODEL_WORK) {                                        // WorkCosts.jl:39-51
+                const TC a = P(0), bv = P(1), bp = P(2);
+                *lo = a + fld(bv * (TC)n + bp * (TC)N, K);
+                if (bv >= 0 && bp >= 0) *hi = a + bv * (TC)n + bp * (TC)N;
+                else if (bv <= 0 && bp <= 0) *hi = a;
                 else { set_error("bound_stripe: mixed-sign work model"); return CP_EINVAL; }
-                *lo_f64 = (double)*lo_i64; *hi_f64 = (double)*hi_i64;
-            } else {
-                double a = model->p_f64[0], bv = model->p_f64[1], bp = model->p_f64[2];
-                *lo_f64 = a + std::floor((bv * (double)n + bp * (double)N) / (double)K);
-                if (bv >= 0 && bp >= 0) *hi_f64 = a + (double)n * bv + (double)N * bp;
-                else if (bv <= 0 && bp <= 0) *hi_f64 = a;
-                else { set_error("bound_stripe: mixed-sign work model"); return CP_EINVAL; }
+                also_f64(lo, hi, lo_f64, hi_f64);
+                return CP_OK;
             }
-            return CP_OK;
-        }
-        if (model->kind == CP_MODEL_PRIMARY) {                                         // PrimaryConnectivityCosts.jl:43-51
-            bool neg = model->dtype == CP_I64 ? (model->p_i64[1] < 0 || model->p_i64[2] < 0 || model->p_i64[3] < 0 || model->p_i64[4] < 0)
-                                              : (model->p_f64[1] < 0 || model->p_f64[2] < 0 || model->p_f64[3] < 0 || model->p_f64[4] < 0);
-            CP_REQUIRE(!neg, CP_EINVAL, "bound_stripe asserts beta >= 0");
-            cp_model_t c = *model; c.kind = CP_MODEL_CONNECTIVITY; c.alpha_k = nullptr; c.n_alpha_k = 0;
-            int64_t di, dh; double df, dg;
-            if (model->dtype == CP_I64) { c.p_i64[CP_P_NET] = std::max(model->p_i64[3], model->p_i64[4]); c.p_i64[4] = 0; }
-            else { c.p_f64[CP_P_NET] = std::max(model->p_f64[3], model->p_f64[4]); c.p_f64[4] = 0; }
-            int32_t rc = cp_bound_stripe(A, K, &c, &di, hi_i64, &df, hi_f64);
-            if (rc != CP_OK) return rc;
-            if (model->dtype == CP_I64) c.p_i64[CP_P_NET] = std::min(model->p_i64[3], model->p_i64[4]);
-            else c.p_f64[CP_P_NET] = std::min(model->p_f64[3], model->p_f64[4]);
-            return cp_bound_stripe(A, K, &c, lo_i64, &dh, lo_f64, &dg);
-        }
-        if (model->kind == CP_MODEL_MONO_SYM_CONNECTIVITY) {                           // MonotonizedSymmetricConnectivityCosts.jl:50-66
-            bool neg = model->dtype == CP_I64 ? (model->p_i64[1] < 0 || model->p_i64[2] < 0 || model->p_i64[3] < 0)
-                                              : !(model->p_f64[1] >= 0 && model->p_f64[2] >= 0 && model->p_f64[3] >= 0);
-            CP_REQUIRE(A->m == A->n, CP_EINVAL, "bound_stripe asserts m == n");
-            CP_REQUIRE(!neg, CP_EINVAL, "bound_stripe asserts beta >= 0");
-        }
-        if ((model->kind == CP_MODEL_CONNECTIVITY || model->kind == CP_MODEL_MONO_SYM_CONNECTIVITY) && model->alpha_k && model->n_alpha_k > 0) {
-            // per-part alpha = the reference tests' FunkyConnectivityModel / FunkyMonotonizedSymmetricConnectivityModel; its
-            // bound_stripe (test_Partitioners.jl:36-41) is
-            // (minimum, maximum) of (minimum(alpha), maximum(alpha), maximum_k ocl(1, n+1, k))
-            CP_REQUIRE(model->n_alpha_k >= K, CP_EINVAL, "bound_stripe: fewer per-part alphas than parts");
-            std::vector<int64_t> one((size_t)K, 1), np1((size_t)K, n + 1), ks((size_t)K);
-            for (int64_t k = 0; k < K; k++) ks[(size_t)k] = k + 1;
-            if (model->dtype == CP_I64) {
-                std::vector<int64_t> v((size_t)K);
-                int32_t rc = cp_oracle_eval(A, model, nullptr, CP_HINT_STEP, K, one.data(), np1.data(), ks.data(), v.data(), nullptr);
+            if (model->kind == CP_MODEL_PRIMARY) {                                     // PrimaryConnectivityCosts.jl:43-51
+                CP_REQUIRE(!(P(1) < 0 || P(2) < 0 || P(3) < 0 || P(4) < 0), CP_EINVAL, "bound_stripe asserts beta >= 0");
+                cp_model_t c = *model; c.kind = CP_MODEL_CONNECTIVITY; c.alpha_k = nullptr; c.n_alpha_k = 0;
+                TC *cp = pick<TC>(c.p_i64, c.p_f64);
+                int64_t di, dh; double df, dg;
+                cp[CP_P_NET] = std::max(P(3), P(4)); cp[4] = 0;
+                int32_t rc = cp_bound_stripe(A, K, &c, &di, hi_i64, &df, hi_f64);
                 if (rc != CP_OK) return rc;
-                const int64_t *al = (const int64_t *)model->alpha_k;
-                int64_t amin = al[0], amax = al[0], fmax = v[0];
+                cp[CP_P_NET] = std::min(P(3), P(4));
+                return cp_bound_stripe(A, K, &c, lo_i64, &dh, lo_f64, &dg);
+            }
+            const bool mono = model->kind == CP_MODEL_MONO_SYM_CONNECTIVITY;
+            if (mono) {                                                                // MonotonizedSymmetricConnectivityCosts.jl:50-66
+                CP_REQUIRE(A->m == A->n, CP_EINVAL, "bound_stripe asserts m == n");
+                CP_REQUIRE(P(1) >= 0 && P(2) >= 0 && P(3) >= 0, CP_EINVAL, "bound_stripe asserts beta >= 0");      // (a NaN fails it too)
+            }
+            if ((model->kind == CP_MODEL_CONNECTIVITY || mono) && model->alpha_k && model->n_alpha_k > 0) {
+                // per-part alpha = the reference tests' FunkyConnectivityModel / FunkyMonotonizedSymmetricConnectivityModel; its
+                // bound_stripe (test_Partitioners.jl:36-41) is
+                // (minimum, maximum) of (minimum(alpha), maximum(alpha), maximum_k ocl(1, n+1, k))
+                CP_REQUIRE(model->n_alpha_k >= K, CP_EINVAL, "bound_stripe: fewer per-part alphas than parts");
+                std::vector<int64_t> one((size_t)K, 1), np1((size_t)K, n + 1), ks((size_t)K);
+                for (int64_t k = 0; k < K; k++) ks[(size_t)k] = k + 1;
+                std::vector<TC> v((size_t)K);
+                int32_t rc = oracle_eval_into<TC>(A, model, nullptr, K, one.data(), np1.data(), ks.data(), v.data());
+                if (rc != CP_OK) return rc;
+                const TC *al = (const TC *)model->alpha_k;
+                TC amin = al[0], amax = al[0], fmax = v[0];
                 for (int64_t k = 1; k < K; k++) { amin = std::min(amin, al[k]); amax = std::max(amax, al[k]); fmax = std::max(fmax, v[(size_t)k]); }
-                *lo_i64 = std::min(amin, std::min(amax, fmax)); *hi_i64 = std::max(amin, std::max(amax, fmax));
-                *lo_f64 = (double)*lo_i64; *hi_f64 = (double)*hi_i64;
-            } else {
-                std::vector<double> v((size_t)K);
-                int32_t rc = cp_oracle_eval(A, model, nullptr, CP_HINT_STEP, K, one.data(), np1.data(), ks.data(), nullptr, v.data());
-                if (rc != CP_OK) return rc;
-                const double *al = (const double *)model->alpha_k;
-                double amin = al[0], amax = al[0], fmax = v[0];
-                for (int64_t k = 1; k < K; k++) { amin = std::min(amin, al[k]); amax = std::max(amax, al[k]); fmax = std::max(fmax, v[(size_t)k]); }
-                *lo_f64 = std::min(amin, std::min(amax, fmax)); *hi_f64 = std::max(amin, std::max(amax, fmax));
+                *lo = std::min(amin, std::min(amax, fmax)); *hi = std::max(amin, std::max(amax, fmax));
+                also_f64(lo, hi, lo_f64, hi_f64);
+                return CP_OK;
             }
-            return CP_OK;
-        }
-        if (model->kind == CP_MODEL_CONNECTIVITY) {                                    // ConnectivityCosts.jl:25-35
-            int64_t one = 1, np1 = n + 1;
-            if (model->dtype == CP_I64) {
-                CP_REQUIRE(model->p_i64[1] >= 0 && model->p_i64[2] >= 0 && model->p_i64[3] >= 0, CP_EINVAL, "bound_stripe asserts beta >= 0");
-                int64_t chi = 0;
-                int32_t rc = cp_oracle_eval(A, model, nullptr, CP_HINT_STEP, 1, &one, &np1, nullptr, &chi, nullptr);
-                if (rc != CP_OK) return rc;
-                *hi_i64 = chi; *lo_i64 = model->p_i64[0] + fld_i64(chi - model->p_i64[0], K);
-                *lo_f64 = (double)*lo_i64; *hi_f64 = (double)*hi_i64;
-            } else {
-                CP_REQUIRE(model->p_f64[1] >= 0 && model->p_f64[2] >= 0 && model->p_f64[3] >= 0, CP_EINVAL, "bound_stripe asserts beta >= 0");
-                double chi = 0;
-                int32_t rc = cp_oracle_eval(A, model, nullptr, CP_HINT_STEP, 1, &one, &np1, nullptr, nullptr, &chi);
-                if (rc != CP_OK) return rc;
-                *hi_f64 = chi; *lo_f64 = model->p_f64[0] + std::floor((chi - model->p_f64[0]) / (double)K);
+            if (model->kind == CP_MODEL_CONNECTIVITY || mono) {
+                TC chi = 0;
+                if (mono) {
+                    // the model form: c_hi = alpha + b_vertex*n + b_over_pin*sum(max(deg - Delta_pins, 0)) + b_dia_net*m, left to right
+                    SymHost H;
+                    CP_HIP(hipSetDevice(A->device));
+                    sym_prepare(A, model, H, false);
+                    chi = cadd(cadd(cadd(P(0), cmulc(n, P(CP_P_VERTEX))), cmulc(H.over_total, P(CP_P_OVER_PIN))), cmulc(A->m, P(CP_P_DIA_NET)));
+                } else {                                                               // ConnectivityCosts.jl:25-35
+                    CP_REQUIRE(P(1) >= 0 && P(2) >= 0 && P(3) >= 0, CP_EINVAL, "bound_stripe asserts beta >= 0");
+                    int64_t one = 1, np1 = n + 1;
+                    int32_t rc = oracle_eval_into<TC>(A, model, nullptr, 1, &one, &np1, nullptr, &chi);
+                    if (rc != CP_OK) return rc;
+                }
+                *hi = chi; *lo = P(0) + fld(chi - P(0), K);
+                also_f64(lo, hi, lo_f64, hi_f64);
+                return CP_OK;
             }
-            return CP_OK;
-        }
-        if (model->kind == CP_MODEL_MONO_SYM_CONNECTIVITY) {
-            // the model form: c_hi = alpha + b_vertex*n + b_over_pin*sum(max(deg - Delta_pins, 0)) + b_dia_net*m, left to right
-            SymHost H;
-            CP_HIP(hipSetDevice(A->device));
-            sym_prepare(A, model, H, false);
-            if (model->dtype == CP_I64) {
-                const int64_t *p = model->p_i64;
-                int64_t chi = cadd(cadd(cadd(p[0], cmulc(n, p[CP_P_VERTEX])), cmulc(H.over_total, p[CP_P_OVER_PIN])), cmulc(A->m, p[CP_P_DIA_NET]));
-                *hi_i64 = chi; *lo_i64 = p[0] + fld_i64(chi - p[0], K);
-                *lo_f64 = (double)*lo_i64; *hi_f64 = (double)*hi_i64;
-            } else {
-                const double *p = model->p_f64;
-                double chi = cadd(cadd(cadd(p[0], cmulc(n, p[CP_P_VERTEX])), cmulc(H.over_total, p[CP_P_OVER_PIN])), cmulc(A->m, p[CP_P_DIA_NET]));
-                *hi_f64 = chi; *lo_f64 = p[0] + std::floor((chi - p[0]) / (double)K);
-            }
-            return CP_OK;
-        }
-        set_error("bound_stripe has no method for this model (the reference raises MethodError)");
-        return CP_EUNSUPPORTED;
+            set_error("bound_stripe has no method for this model (the reference raises MethodError)");
+            return CP_EUNSUPPORTED;
+        });
     });
 }
 
@@ -602,38 +583,30 @@ int32_t cp_bound_stripe_pi(cp_csr_t A, int64_t K, const cp_rowpart_t *Pi, const 
     if (!model || model->kind != CP_MODEL_SECONDARY) return cp_bound_stripe(A, K, model, lo_i64, hi_i64, lo_f64, hi_f64);
     return guarded([&]() -> int32_t {
         CP_REQUIRE(A && model_known(model) && K >= 1 && Pi && Pi->spl, CP_EINVAL, "bad argument");
-        bool neg = model->dtype == CP_I64 ? (model->p_i64[1] < 0 || model->p_i64[2] < 0 || model->p_i64[3] < 0 || model->p_i64[4] < 0)
-                                          : (model->p_f64[1] < 0 || model->p_f64[2] < 0 || model->p_f64[3] < 0 || model->p_f64[4] < 0);
-        CP_REQUIRE(!neg, CP_EINVAL, "bound_stripe asserts beta >= 0");
-        // the two bounds are the secondary cost with all nets local resp. all nets remote: evaluate the oracle on the empty and the
-        // full column range of every part with (b_local, b_remote) = (0, 0) resp. (b_remote, b_remote)
-        int64_t Kp = Pi->K;
-        std::vector<int64_t> one((size_t)Kp, 1), ks((size_t)Kp);
-        for (int64_t k = 0; k < Kp; k++) ks[(size_t)k] = k + 1;
-        cp_model_t lo_m = *model, hi_m = *model;
-        if (model->dtype == CP_I64) { lo_m.p_i64[3] = 0; lo_m.p_i64[4] = 0; hi_m.p_i64[3] = model->p_i64[4]; }
-        else { lo_m.p_f64[3] = 0; lo_m.p_f64[4] = 0; hi_m.p_f64[3] = model->p_f64[4]; }
-        lo_m.alpha_k = nullptr; lo_m.n_alpha_k = 0; hi_m.alpha_k = nullptr; hi_m.n_alpha_k = 0;
-        if (model->dtype == CP_I64) {
-            std::vector<int64_t> a((size_t)Kp), b((size_t)Kp);
-            int32_t rc = cp_oracle_eval(A, &lo_m, Pi, CP_HINT_STEP, Kp, one.data(), one.data(), ks.data(), a.data(), nullptr);
+        return with_cost_type(model->dtype, [&](auto tag) -> int32_t {
+            using TC = decltype(tag);
+            auto P = [&](int i) { return model_param<TC>(model, i); };
+            CP_REQUIRE(!(P(1) < 0 || P(2) < 0 || P(3) < 0 || P(4) < 0), CP_EINVAL, "bound_stripe asserts beta >= 0");
+            // the two bounds are the secondary cost with all nets local resp. all nets remote: evaluate the oracle on the empty and the
+            // full column range of every part with (b_local, b_remote) = (0, 0) resp. (b_remote, b_remote)
+            int64_t Kp = Pi->K;
+            std::vector<int64_t> one((size_t)Kp, 1), ks((size_t)Kp);
+            for (int64_t k = 0; k < Kp; k++) ks[(size_t)k] = k + 1;
+            cp_model_t lo_m = *model, hi_m = *model;
+            TC *pl = pick<TC>(lo_m.p_i64, lo_m.p_f64), *ph = pick<TC>(hi_m.p_i64, hi_m.p_f64);
+            pl[3] = 0; pl[4] = 0; ph[3] = P(4);
+            lo_m.alpha_k = nullptr; lo_m.n_alpha_k = 0; hi_m.alpha_k = nullptr; hi_m.n_alpha_k = 0;
+            std::vector<TC> a((size_t)Kp), b((size_t)Kp);
+            int32_t rc = oracle_eval_into<TC>(A, &lo_m, Pi, Kp, one.data(), one.data(), ks.data(), a.data());
             if (rc != CP_OK) return rc;
-            rc = cp_oracle_eval(A, &hi_m, Pi, CP_HINT_STEP, Kp, one.data(), one.data(), ks.data(), b.data(), nullptr);
+            rc = oracle_eval_into<TC>(A, &hi_m, Pi, Kp, one.data(), one.data(), ks.data(), b.data());
             if (rc != CP_OK) return rc;
-            int64_t clo = 0, chi = 0;                                  // "c_lo = 0; c_hi = 0" (:44-45)
-            for (int64_t k = 0; k < Kp; k++) { clo = std::max(clo, a[(size_t)k]); chi = std::max(chi, b[(size_t)k]); }
-            *lo_i64 = clo; *hi_i64 = chi; *lo_f64 = (double)clo; *hi_f64 = (double)chi;
-        } else {
-            std::vector<double> a((size_t)Kp), b((size_t)Kp);
-            int32_t rc = cp_oracle_eval(A, &lo_m, Pi, CP_HINT_STEP, Kp, one.data(), one.data(), ks.data(), nullptr, a.data());
-            if (rc != CP_OK) return rc;
-            rc = cp_oracle_eval(A, &hi_m, Pi, CP_HINT_STEP, Kp, one.data(), one.data(), ks.data(), nullptr, b.data());
-            if (rc != CP_OK) return rc;
-            double clo = 0, chi = 0;
-            for (int64_t k = 0; k < Kp; k++) { clo = std::max(clo, a[(size_t)k]); chi = std::max(chi, b[(size_t)k]); }
-            *lo_f64 = clo; *hi_f64 = chi;
-        }
-        return CP_OK;
+            TC *lo = pick<TC>(lo_i64, lo_f64), *hi = pick<TC>(hi_i64, hi_f64);
+            *lo = 0; *hi = 0;                                              // "c_lo = 0; c_hi = 0" (:44-45)
+            for (int64_t k = 0; k < Kp; k++) { *lo = std::max(*lo, a[(size_t)k]); *hi = std::max(*hi, b[(size_t)k]); }
+            also_f64(lo, hi, lo_f64, hi_f64);
+            return CP_OK;
+        });
     });
 }
 

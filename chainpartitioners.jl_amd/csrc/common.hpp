@@ -41,6 +41,9 @@ struct HipFail { int32_t code; };
     catch (const cpk::HipFail &e) { return e.code; }                                         \
     catch (const std::bad_alloc &) { cpk::set_error("host allocation failed"); return CP_EHIP; }
 
+// the same as a function: an entry point's body is  return guarded([&]() -> int32_t { ... });
+template <typename F> inline int32_t guarded(F &&f) { try { return f(); } CP_CATCH_ALL }
+
 // ------------------------------------------------------------------ device buffers (RAII)
 // Allocations of 1 MB and more go through a per-process pool keyed by (device, exact byte size): the builds and drivers allocate the
 // same multi-hundred-MB temporaries in every call, and handing them back to the HIP runtime each time makes it stall for ~1.3 s

@@ -119,7 +119,7 @@ using namespace cpk;
 // the same call, also returning the number of probes the bisection ran (tests, tools/bench_symmetric.py)
 extern "C" int32_t cp_partition_lazy_bisect_cost_probes(cp_csr_t A, int64_t K, const cp_model_t *model, double eps, int64_t *spl_out, int64_t *nprobes_out)
 {
-    try {
+    return guarded([&]() -> int32_t {
         CP_REQUIRE(A && model && spl_out && K >= 1, CP_EINVAL, "bad argument");
         // only AbstractConnectivityModel reaches the specialised method; other models hit the generic one whose g() asserts
         // false for them (LazyBisectCostBottleneckSplitter.jl:486-501)
@@ -130,9 +130,8 @@ extern "C" int32_t cp_partition_lazy_bisect_cost_probes(cp_csr_t A, int64_t K, c
         int32_t rc = cp_bound_stripe(A, K, model, &li, &hi, &lf, &hf);        // :231
         if (rc != CP_OK) return rc;
         CP_REQUIRE(A->N < ((int64_t)1 << 31) - LZ_CH, CP_EUNSUPPORTED, "LazyBisectCost needs nnz < 2^31");
-        if (model->dtype == CP_I64) return run_lazy<int64_t>(A, K, model, lf, hf, eps, spl_out, nprobes_out);
-        return run_lazy<double>(A, K, model, lf, hf, eps, spl_out, nprobes_out);
-    } CP_CATCH_ALL
+        return with_cost_type(model->dtype, [&](auto tag) { return run_lazy<decltype(tag)>(A, K, model, lf, hf, eps, spl_out, nprobes_out); });
+    });
 }
 
 extern "C" int32_t cp_partition_lazy_bisect_cost(cp_csr_t A, int64_t K, const cp_model_t *model, double eps, int64_t *spl_out)

@@ -941,25 +941,77 @@ static int64_t unravel_chunks_host(std::vector<int64_t> &spl, int64_t n)
     return K;
 }
 
+// the chunkers' ptr[0 .. n+1] (ptr[j'] = where the chunk ending before j' starts; ptr[0] unused) -> boundaries sp[0 .. K]
+static int64_t chunks_of_ptr(const std::vector<int64_t> &ptr, int64_t n, std::vector<int64_t> &sp)
+{
+    sp.resize((size_t)n + 1);
+    for (int64_t jp = 1; jp <= n + 1; jp++) sp[(size_t)jp - 1] = ptr[(size_t)jp];
+    return unravel_chunks_host(sp, n);
+}
+
+// One call of a one-wave method: the oracle, the status word, the launch and the readback.  A runner is its buffers and memsets,
+// begin(), launch() of its one kernel, and one of the finish_* tails with its error string.  (Unnamed namespace: the library
+// exports every named template instance.)
+namespace {
+template <typename TC>
+struct SeqRun {
+    hipStream_t s;
+    int64_t n;
+    std::unique_ptr<SeqCtx<TC>> C;
+    DBuf<int32_t> st;             // the kernel's status word ...
+    int32_t rc = 0;               // ... and its host copy, valid after finish()
+
+    SeqRun(cp_csr_s *A, const cp_model_t *mdl, const cp_rowpart_t *Pi) : s(A->stream), n(A->n), C(new SeqCtx<TC>()) { seq_oracle<TC>(A, mdl, Pi, *C); }
+    void begin() { st.alloc(1); CP_HIP(hipMemsetAsync(st.p, 0, sizeof(int32_t), s)); }
+    void launched() { CP_HIP(hipGetLastError()); CP_HIP(hipMemcpyAsync(&rc, st.p, sizeof(int32_t), hipMemcpyDeviceToHost, s)); }
+    template <typename... P, typename... Q>
+    void launch(void (*kern)(P...), Q &&...args)              // one wave, inside the profile slot
+    {
+        { ProfScope ps(PROF_CHUNK, s, 0.0); hipLaunchKernelGGL(kern, dim3(1), dim3(64), 0, s, args...); }
+        launched();
+    }
+    template <typename T> void fetch(T *dst, const T *src, size_t cnt) { CP_HIP(hipMemcpyAsync(dst, src, sizeof(T) * cnt, hipMemcpyDeviceToHost, s)); }
+    int32_t finish() { CP_HIP(hipStreamSynchronize(s)); prof_collect(); return rc; }
+
+    // chunkers: any failure status carries msg; else ptr unravelled into spl_out[0 .. K] and *K_out
+    int32_t finish_chunks(const int64_t *ptr, const char *msg, int64_t *spl_out, int64_t *K_out)
+    {
+        std::vector<int64_t> h((size_t)n + 2), sp;
+        fetch(h.data(), ptr, (size_t)n + 2);
+        if (finish() != CP_OK) { set_error(msg); return rc; }
+        int64_t K = chunks_of_ptr(h, n, sp);
+        for (int64_t k = 0; k <= K; k++) spl_out[k] = sp[(size_t)k];
+        *K_out = K;
+        return CP_OK;
+    }
+    // splitters: the kernel wrote spl[0 .. K] itself; status `code` carries msg
+    int32_t finish_splits(const int64_t *spl, int64_t K, int64_t *spl_out, int32_t code, const char *msg)
+    {
+        fetch(spl_out, spl, (size_t)K + 1);
+        if (finish() == code) set_error(msg);
+        return rc;
+    }
+};
+}  // namespace
+
 template <typename TC>
 int32_t run_pack_dynamic(cp_csr_s *A, const cp_model_t *mdl, const cp_rowpart_t *Pi, const cp_model_t *w, int64_t wi, double wf,
                          int64_t *spl_out, int64_t *K_out, int64_t *spl_tab = nullptr, TC *cst_tab = nullptr)
 {
-    hipStream_t s = A->stream;
-    int64_t n = A->n;
-    std::unique_ptr<SeqCtx<TC>> C(new SeqCtx<TC>());
-    seq_oracle<TC>(A, mdl, Pi, *C);
+    SeqRun<TC> R(A, mdl, Pi);
+    hipStream_t s = R.s;
+    int64_t n = R.n;
+    SeqCtx<TC> &C = *R.C;
     // any width past the scan's 16 columns, a monotone work budget or no constraint: the on-line divide and conquer (chunk_lws.hip)
     const bool lws = lws_ok(A, mdl, w, wi, wf);
-    if (!lws) seq_window_table<TC>(A, mdl, w, wi, *C);
+    if (!lws) seq_window_table<TC>(A, mdl, w, wi, C);
     SeqWeight W = make_weight(A, w, wi, wf);
     DBuf<TC> cst((size_t)n + 2);
     DBuf<int64_t> spl((size_t)n + 2);
-    DBuf<int32_t> st(1);
-    CP_HIP(hipMemsetAsync(st.p, 0, sizeof(int32_t), s));
+    R.begin();
     CP_HIP(hipMemsetAsync(spl.p, 0, spl.bytes(), s));
     if (lws) {
-        const int32_t rc = run_pack_lws<TC>(A, C->HM.d, C->O.net, C->O.self, w, wi, wf, cst.p, spl.p);
+        const int32_t rc = run_pack_lws<TC>(A, C.HM.d, C.O.net, C.O.self, w, wi, wf, cst.p, spl.p);
         if (rc != CP_OK) return rc;
     } else {
         ProfScope ps(PROF_CHUNK, s, 0.0);
@@ -967,20 +1019,16 @@ int32_t run_pack_dynamic(cp_csr_s *A, const cp_model_t *mdl, const cp_rowpart_t 
         // are bounded as Float64 ones are (model_exact_on; column-block models by their tabulated components)
         bool scanned = false;
         bool exact = model_exact_on(mdl, n, A->N, n + 1) && (std::is_same<TC, int64_t>::value || mdl->kind != CP_MODEL_COLBLOCK);
-        if (W.kind == CP_MODEL_VERTEX_COUNT && C->O.Ftab && C->O.Wc == wi && exact && !g_opt_force_brute)
-            scanned = pack_dynamic_scan<TC>(s, n, wi, C->O.Ftab, cst.p, spl.p);
+        if (W.kind == CP_MODEL_VERTEX_COUNT && C.O.Ftab && C.O.Wc == wi && exact && !g_opt_force_brute)
+            scanned = pack_dynamic_scan<TC>(s, n, wi, C.O.Ftab, cst.p, spl.p);
         if (!scanned)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack_dynamic<TC>), dim3(1), dim3(64), 0, s, C->O, W, cst.p, spl.p, st.p);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack_dynamic<TC>), dim3(1), dim3(64), 0, s, C.O, W, cst.p, spl.p, R.st.p);
     }
-    CP_HIP(hipGetLastError());
-    int32_t rc = 0;
+    R.launched();
     std::vector<int64_t> h((size_t)n + 1);
-    CP_HIP(hipMemcpyAsync(&rc, st.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    CP_HIP(hipMemcpyAsync(h.data(), spl.p, sizeof(int64_t) * (size_t)(n + 1), hipMemcpyDeviceToHost, s));
-    if (cst_tab) CP_HIP(hipMemcpyAsync(cst_tab, cst.p, sizeof(TC) * (size_t)(n + 1), hipMemcpyDeviceToHost, s));
-    CP_HIP(hipStreamSynchronize(s));
-    prof_collect();
-    if (rc != CP_OK) { set_error("pack_stripe: a single column exceeds w_max (@assert j0 < j')"); return rc; }
+    R.fetch(h.data(), spl.p, (size_t)n + 1);
+    if (cst_tab) R.fetch(cst_tab, cst.p, (size_t)n + 1);
+    if (R.finish() != CP_OK) { set_error("pack_stripe: a single column exceeds w_max (@assert j0 < j')"); return R.rc; }
     if (spl_tab) for (int64_t t = 0; t <= n; t++) spl_tab[t] = h[(size_t)t];
     int64_t K = unravel_chunks_host(h, n);
     if (spl_out) for (int64_t k = 0; k <= K; k++) spl_out[k] = h[(size_t)k];
@@ -992,27 +1040,26 @@ template <typename TC>
 int32_t run_pack_convex(cp_csr_s *A, const cp_model_t *mdl, const cp_rowpart_t *Pi, const cp_model_t *w, int64_t wi, double wf,
                         int64_t *spl_out, int64_t *K_out)
 {
-    hipStream_t s = A->stream;
-    int64_t n = A->n, cap = 2 * n + 4;
-    std::unique_ptr<SeqCtx<TC>> C(new SeqCtx<TC>());
-    seq_oracle<TC>(A, mdl, Pi, *C);
-    seq_window_table<TC>(A, mdl, w, wi, *C, 2);
+    SeqRun<TC> R(A, mdl, Pi);
+    hipStream_t s = R.s;
+    int64_t n = R.n, cap = 2 * n + 4;
+    SeqCtx<TC> &C = *R.C;
+    seq_window_table<TC>(A, mdl, w, wi, C, 2);
     SeqWeight W = make_weight(A, w, wi, wf);
     int constrained = W.kind != CP_MODEL_FEASIBLE;
     DBuf<Ext<TC>> cst((size_t)n + 2), sig_cst((size_t)cap);
     DBuf<int64_t> ptr((size_t)n + 2), ftr((size_t)(2 * cap)), sig_j((size_t)cap), sig_jp((size_t)cap), sig_ptr((size_t)cap);
-    DBuf<int32_t> st(1);
-    CP_HIP(hipMemsetAsync(st.p, 0, sizeof(int32_t), s));
+    R.begin();
     CP_HIP(hipMemsetAsync(sig_ptr.p, 0, sig_ptr.bytes(), s));
     {
         ProfScope ps(PROF_CHUNK, s, 0.0);
         // width window with its table resident: the LDS form of the same algorithm (k_pack_convex_win)
-        const bool win = W.kind == CP_MODEL_VERTEX_COUNT && C->O.Ftab && wi >= 1 && wi <= CW_MAXW && C->O.Wc == 2 * wi + 2 && !g_opt_force_brute &&
+        const bool win = W.kind == CP_MODEL_VERTEX_COUNT && C.O.Ftab && wi >= 1 && wi <= CW_MAXW && C.O.Wc == 2 * wi + 2 && !g_opt_force_brute &&
                          mdl->kind != CP_MODEL_BLOCK;
         DBuf<SeqOracle<TC>> odev(1);                      // (the general oracle, for the rare pair outside the resident table)
         if (win) {
-            CP_HIP(hipMemcpyAsync(odev.p, &C->O, sizeof(SeqOracle<TC>), hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack_convex_win<TC>), dim3(1), dim3(64), 0, s, C->O, (int32_t)wi, ptr.p, st.p, odev.p);
+            CP_HIP(hipMemcpyAsync(odev.p, &C.O, sizeof(SeqOracle<TC>), hipMemcpyHostToDevice, s));
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack_convex_win<TC>), dim3(1), dim3(64), 0, s, C.O, (int32_t)wi, ptr.p, R.st.p, odev.p);
             CP_HIP(hipStreamSynchronize(s));              // (odev leaves scope)
 #ifdef CW_STATS
             unsigned long long st8[8];
@@ -1020,23 +1067,11 @@ int32_t run_pack_convex(cp_csr_s *A, const cp_model_t *mdl, const cp_rowpart_t *
             fprintf(stderr, "cw stats: general(j>j')=%llu general(other)=%llu steps=%llu pops=%llu bsearch=%llu\n", st8[0], st8[1], st8[2], st8[3], st8[4]);
 #endif
         }
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack_convex<TC>), dim3(1), dim3(64), 0, s, C->O, W, constrained, cst.p, ptr.p, ftr.p,
-                           sig_j.p, sig_jp.p, sig_ptr.p, sig_cst.p, st.p);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack_convex<TC>), dim3(1), dim3(64), 0, s, C.O, W, constrained, cst.p, ptr.p, ftr.p,
+                           sig_j.p, sig_jp.p, sig_ptr.p, sig_cst.p, R.st.p);
     }
-    CP_HIP(hipGetLastError());
-    int32_t rc = 0;
-    std::vector<int64_t> h((size_t)n + 2);
-    CP_HIP(hipMemcpyAsync(&rc, st.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    CP_HIP(hipMemcpyAsync(h.data(), ptr.p, sizeof(int64_t) * (size_t)(n + 2), hipMemcpyDeviceToHost, s));
-    CP_HIP(hipStreamSynchronize(s));
-    prof_collect();
-    if (rc != CP_OK) { set_error("ConvexTotalChunker: a single column exceeds w_max"); return rc; }
-    std::vector<int64_t> sp((size_t)n + 1);
-    for (int64_t jp = 1; jp <= n + 1; jp++) sp[(size_t)jp - 1] = h[(size_t)jp];
-    int64_t K = unravel_chunks_host(sp, n);
-    for (int64_t k = 0; k <= K; k++) spl_out[k] = sp[(size_t)k];
-    *K_out = K;
-    return CP_OK;
+    R.launched();
+    return R.finish_chunks(ptr.p, "ConvexTotalChunker: a single column exceeds w_max", spl_out, K_out);
 }
 
 // pack_stripe(A, ConvexTotalChunker(ConstrainedCost(f_b, VertexCount(), w_b))) for B requests on one pattern: ONE launch, the net
@@ -1083,15 +1118,14 @@ int32_t run_pack_convex_batch(cp_csr_s *A, int64_t B, const cp_model_t *models, 
     }
     CP_HIP(hipGetLastError());
     std::vector<int32_t> hst((size_t)B);
-    std::vector<int64_t> h((size_t)n + 2), sp((size_t)n + 1);
+    std::vector<int64_t> h((size_t)n + 2), sp;
     CP_HIP(hipMemcpyAsync(hst.data(), st.p, sizeof(int32_t) * (size_t)B, hipMemcpyDeviceToHost, s));
     CP_HIP(hipStreamSynchronize(s));
     prof_collect();
     for (int64_t b = 0; b < B; b++) {
         if (hst[(size_t)b] != CP_OK) { set_error("ConvexTotalChunker: a single column exceeds w_max"); return hst[(size_t)b]; }
         CP_HIP(hipMemcpy(h.data(), ptr.p + (size_t)b * (size_t)(n + 2), sizeof(int64_t) * (size_t)(n + 2), hipMemcpyDeviceToHost));
-        for (int64_t jp = 1; jp <= n + 1; jp++) sp[(size_t)jp - 1] = h[(size_t)jp];
-        const int64_t K = unravel_chunks_host(sp, n);
+        const int64_t K = chunks_of_ptr(h, n, sp);
         CP_REQUIRE(K + 1 <= ld, CP_EINVAL, "ld is smaller than a request's number of chunks + 1 (n + 1 always suffices)");
         for (int64_t k = 0; k <= K; k++) spl_out[(size_t)b * (size_t)ld + (size_t)k] = sp[(size_t)k];
         K_out[b] = K;
@@ -1103,110 +1137,61 @@ template <typename TC>
 int32_t run_partition_convex(cp_csr_s *A, int64_t K, const cp_model_t *mdl, const cp_rowpart_t *Pi, const cp_model_t *w, int64_t wi,
                              double wf, int64_t *spl_out)
 {
-    hipStream_t s = A->stream;
     int64_t n = A->n, cap = 2 * n + 4;
     SeqWeight W = make_weight(A, w, wi, wf);
     int constrained = W.kind != CP_MODEL_FEASIBLE;
     if (!constrained && K == 1) { spl_out[0] = 1; spl_out[1] = n + 1; return CP_OK; }         // :32-34
     CP_REQUIRE((double)K * (double)(n + 2) < 4e8, CP_EUNSUPPORTED, "ConvexTotalSplitter tables exceed the device budget");
-    std::unique_ptr<SeqCtx<TC>> C(new SeqCtx<TC>());
-    seq_oracle<TC>(A, mdl, Pi, *C);
+    SeqRun<TC> R(A, mdl, Pi);
     DBuf<Ext<TC>> cst((size_t)K * (size_t)(n + 2)), sig_cst((size_t)cap);
     DBuf<int64_t> ptr((size_t)K * (size_t)(n + 2)), jlo((size_t)K), jhi((size_t)K), ftr((size_t)(2 * cap)), sig_j((size_t)cap),
         sig_jp((size_t)cap), sig_ptr((size_t)cap), spl((size_t)K + 1);
-    DBuf<int32_t> st(1);
-    CP_HIP(hipMemsetAsync(st.p, 0, sizeof(int32_t), s));
-    CP_HIP(hipMemsetAsync(sig_ptr.p, 0, sig_ptr.bytes(), s));
-    {
-        ProfScope ps(PROF_CHUNK, s, 0.0);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_partition_convex<TC>), dim3(1), dim3(64), 0, s, C->O, W, constrained, K, cst.p, ptr.p, jlo.p,
-                           jhi.p, ftr.p, sig_j.p, sig_jp.p, sig_ptr.p, sig_cst.p, spl.p, st.p);
-    }
-    CP_HIP(hipGetLastError());
-    int32_t rc = 0;
-    CP_HIP(hipMemcpyAsync(&rc, st.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    CP_HIP(hipMemcpyAsync(spl_out, spl.p, sizeof(int64_t) * (size_t)(K + 1), hipMemcpyDeviceToHost, s));
-    CP_HIP(hipStreamSynchronize(s));
-    prof_collect();
-    if (rc == CP_EINVAL) set_error("ConvexTotalSplitter: a single column exceeds w_max");
-    return rc;
+    R.begin();
+    CP_HIP(hipMemsetAsync(sig_ptr.p, 0, sig_ptr.bytes(), R.s));
+    R.launch(k_partition_convex<TC>, R.C->O, W, constrained, K, cst.p, ptr.p, jlo.p, jhi.p, ftr.p, sig_j.p, sig_jp.p, sig_ptr.p, sig_cst.p, spl.p, R.st.p);
+    return R.finish_splits(spl.p, K, spl_out, CP_EINVAL, "ConvexTotalSplitter: a single column exceeds w_max");
 }
 
 template <typename TC>
 int32_t run_pack_concave(cp_csr_s *A, const cp_model_t *mdl, const cp_rowpart_t *Pi, const cp_model_t *w, int64_t wi, double wf,
                          int64_t *spl_out, int64_t *K_out)
 {
-    hipStream_t s = A->stream;
-    int64_t n = A->n;
-    std::unique_ptr<SeqCtx<TC>> C(new SeqCtx<TC>());
-    seq_oracle<TC>(A, mdl, Pi, *C);
+    SeqRun<TC> R(A, mdl, Pi);
+    int64_t n = R.n;
     SeqWeight W = make_weight(A, w, wi, wf);
     int constrained = W.kind != CP_MODEL_FEASIBLE;
     DBuf<Ext<TC>> cst((size_t)n + 2);
     DBuf<int64_t> ptr((size_t)n + 2), dq((size_t)(2 * (n + 2)));
-    DBuf<int32_t> st(1);
-    CP_HIP(hipMemsetAsync(st.p, 0, sizeof(int32_t), s));
-    {
-        ProfScope ps(PROF_CHUNK, s, 0.0);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack_concave<TC>), dim3(1), dim3(64), 0, s, C->O, W, constrained, cst.p, ptr.p, dq.p, st.p);
-    }
-    CP_HIP(hipGetLastError());
-    int32_t rc = 0;
-    std::vector<int64_t> h((size_t)n + 2);
-    CP_HIP(hipMemcpyAsync(&rc, st.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    CP_HIP(hipMemcpyAsync(h.data(), ptr.p, sizeof(int64_t) * (size_t)(n + 2), hipMemcpyDeviceToHost, s));
-    CP_HIP(hipStreamSynchronize(s));
-    prof_collect();
-    if (rc != CP_OK) { set_error("ConcaveTotalChunker: the candidate deque ran empty (the reference throws)"); return rc; }
-    std::vector<int64_t> sp((size_t)n + 1);
-    for (int64_t jp = 1; jp <= n + 1; jp++) sp[(size_t)jp - 1] = h[(size_t)jp];
-    int64_t K = unravel_chunks_host(sp, n);
-    for (int64_t k = 0; k <= K; k++) spl_out[k] = sp[(size_t)k];
-    *K_out = K;
-    return CP_OK;
+    R.begin();
+    R.launch(k_pack_concave<TC>, R.C->O, W, constrained, cst.p, ptr.p, dq.p, R.st.p);
+    return R.finish_chunks(ptr.p, "ConcaveTotalChunker: the candidate deque ran empty (the reference throws)", spl_out, K_out);
 }
 
 template <typename TC>
 int32_t run_partition_concave(cp_csr_s *A, int64_t K, const cp_model_t *mdl, const cp_rowpart_t *Pi, const cp_model_t *w, int64_t wi,
                               double wf, int64_t *spl_out)
 {
-    hipStream_t s = A->stream;
     int64_t n = A->n;
     SeqWeight W = make_weight(A, w, wi, wf);
     int constrained = W.kind != CP_MODEL_FEASIBLE;
     if (!constrained && K == 1) { spl_out[0] = 1; spl_out[1] = n + 1; return CP_OK; }         // :32-34
     CP_REQUIRE((double)K * (double)(n + 2) < 4e8, CP_EUNSUPPORTED, "ConcaveTotalSplitter tables exceed the device budget");
-    std::unique_ptr<SeqCtx<TC>> C(new SeqCtx<TC>());
-    seq_oracle<TC>(A, mdl, Pi, *C);
+    SeqRun<TC> R(A, mdl, Pi);
     DBuf<Ext<TC>> cst((size_t)K * (size_t)(n + 2));
     DBuf<int64_t> ptr((size_t)K * (size_t)(n + 2)), jlo((size_t)K), jhi((size_t)K), dq((size_t)(2 * (n + 2))), spl((size_t)K + 1);
-    DBuf<int32_t> st(1);
-    CP_HIP(hipMemsetAsync(st.p, 0, sizeof(int32_t), s));
-    {
-        ProfScope ps(PROF_CHUNK, s, 0.0);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_partition_concave<TC>), dim3(1), dim3(64), 0, s, C->O, W, constrained, K, cst.p, ptr.p, jlo.p,
-                           jhi.p, dq.p, spl.p, st.p);
-    }
-    CP_HIP(hipGetLastError());
-    int32_t rc = 0;
-    CP_HIP(hipMemcpyAsync(&rc, st.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    CP_HIP(hipMemcpyAsync(spl_out, spl.p, sizeof(int64_t) * (size_t)(K + 1), hipMemcpyDeviceToHost, s));
-    CP_HIP(hipStreamSynchronize(s));
-    prof_collect();
-    if (rc == CP_EINVAL) set_error("ConcaveTotalSplitter: the candidate deque ran empty (the reference throws)");
-    return rc;
+    R.begin();
+    R.launch(k_partition_concave<TC>, R.C->O, W, constrained, K, cst.p, ptr.p, jlo.p, jhi.p, dq.p, spl.p, R.st.p);
+    return R.finish_splits(spl.p, K, spl_out, CP_EINVAL, "ConcaveTotalSplitter: the candidate deque ran empty (the reference throws)");
 }
 
 template <typename TC>
 int32_t run_dyn_constrained(cp_csr_s *A, int64_t K, int32_t g, int32_t order, const cp_model_t *mdl, const cp_rowpart_t *Pi,
                             const cp_model_t *w, int64_t wi, double wf, int64_t *spl_out)
 {
-    hipStream_t s = A->stream;
     int64_t n = A->n;
     // DynamicSplitter.jl:279 rebuilds f WITHOUT the row partition in the chunker loop order
     if (order == CP_ORDER_CHUNKER && mdl->kind == CP_MODEL_BLOCK) { set_error("no oracle_stripe(BlockComponentCostModel, A) without a row partition (DynamicSplitter.jl:279)"); return CP_EUNSUPPORTED; }
-    std::unique_ptr<SeqCtx<TC>> C(new SeqCtx<TC>());
-    seq_oracle<TC>(A, mdl, order == CP_ORDER_CHUNKER ? nullptr : Pi, *C);
+    SeqRun<TC> R(A, mdl, order == CP_ORDER_CHUNKER ? nullptr : Pi);
     SeqWeight W = make_weight(A, w, wi, wf);
     int64_t ncol = order == CP_ORDER_SPLITTER ? K : n + 1;
     int64_t cap = (int64_t)2e8;
@@ -1214,22 +1199,10 @@ int32_t run_dyn_constrained(cp_csr_s *A, int64_t K, int32_t g, int32_t order, co
     if (est < (double)cap) cap = (int64_t)est + 16;
     DBuf<int64_t> lo((size_t)ncol + 1), hi((size_t)ncol + 1), wpos((size_t)ncol + 2), pv((size_t)cap), spl((size_t)K + 1);
     DBuf<TC> cv((size_t)cap);
-    DBuf<int32_t> st(1);
-    CP_HIP(hipMemsetAsync(st.p, 0, sizeof(int32_t), s));
-    CP_HIP(hipMemsetAsync(pv.p, 0, pv.bytes(), s));
-    {
-        ProfScope ps(PROF_CHUNK, s, 0.0);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_dyn_constrained<TC>), dim3(1), dim3(64), 0, s, C->O, W, K, g, order, lo.p, hi.p, wpos.p, cv.p,
-                           pv.p, cap, spl.p, st.p);
-    }
-    CP_HIP(hipGetLastError());
-    int32_t rc = 0;
-    CP_HIP(hipMemcpyAsync(&rc, st.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    CP_HIP(hipMemcpyAsync(spl_out, spl.p, sizeof(int64_t) * (size_t)(K + 1), hipMemcpyDeviceToHost, s));
-    CP_HIP(hipStreamSynchronize(s));
-    prof_collect();
-    if (rc == CP_EUNSUPPORTED) set_error("constrained DP window tables exceed the device budget");
-    return rc;
+    R.begin();
+    CP_HIP(hipMemsetAsync(pv.p, 0, pv.bytes(), R.s));
+    R.launch(k_dyn_constrained<TC>, R.C->O, W, K, g, order, lo.p, hi.p, wpos.p, cv.p, pv.p, cap, spl.p, R.st.p);
+    return R.finish_splits(spl.p, K, spl_out, CP_EUNSUPPORTED, "constrained DP window tables exceed the device budget");
 }
 
 // ocl(j, j', k) for a batch, evaluated in order by the stateful oracle (BlockComponentCostStepOracle)
@@ -1279,48 +1252,57 @@ static bool seq_model_ok(const cp_model_t *m)
 
 static bool seq_model_sym(const cp_model_t *m) { return m && m->kind >= CP_MODEL_SYM_CONNECTIVITY && m->kind <= CP_MODEL_SYM_EDGE_CUT; }
 
+// What every single-request entry checks first, in this order (it decides which error a doubly wrong call gets); args_ok: the entry's
+// own pointers and K.
+static void seq_check(bool args_ok, const cp_model_t *model, const cp_model_t *weight)
+{
+    CP_REQUIRE(!seq_model_sym(model), CP_EUNSUPPORTED, "the symmetric cost models have no device path in this method");
+    CP_REQUIRE(args_ok && seq_model_ok(model) && weight_ok(weight), CP_EINVAL, "bad argument");
+}
+// ... and how it leaves for its runner: f(tag) with the model's cost type, on the handle's device
+template <typename F>
+static int32_t seq_run(cp_csr_t A, const cp_model_t *model, F &&f)
+{
+    CP_HIP(hipSetDevice(A->device));
+    return with_cost_type(model->dtype, f);
+}
+
 extern "C" {
 
 int32_t cp_pack_dynamic(cp_csr_t A, const cp_model_t *model, const cp_rowpart_t *Pi, const cp_model_t *weight, int64_t wmax_i64,
                         double wmax_f64, int64_t *spl_out, int64_t *K_out)
 {
-    try {
-        CP_REQUIRE(!seq_model_sym(model), CP_EUNSUPPORTED, "the symmetric cost models have no device path in this method");
-        CP_REQUIRE(A && spl_out && K_out && seq_model_ok(model) && weight_ok(weight), CP_EINVAL, "bad argument");
-        CP_HIP(hipSetDevice(A->device));
-        if (model->dtype == CP_I64) return run_pack_dynamic<int64_t>(A, model, Pi, weight, wmax_i64, wmax_f64, spl_out, K_out);
-        return run_pack_dynamic<double>(A, model, Pi, weight, wmax_i64, wmax_f64, spl_out, K_out);
-    } CP_CATCH_ALL
+    return guarded([&]() -> int32_t {
+        seq_check(A && spl_out && K_out, model, weight);
+        return seq_run(A, model, [&](auto tag) { return run_pack_dynamic<decltype(tag)>(A, model, Pi, weight, wmax_i64, wmax_f64, spl_out, K_out); });
+    });
 }
 
 int32_t cp_pack_dynamic_tables(cp_csr_t A, const cp_model_t *model, const cp_rowpart_t *Pi, const cp_model_t *weight, int64_t wmax_i64,
                                double wmax_f64, int64_t *spl_tab, int64_t *cst_i64, double *cst_f64)
 {
-    try {
-        CP_REQUIRE(!seq_model_sym(model), CP_EUNSUPPORTED, "the symmetric cost models have no device path in this method");
-        CP_REQUIRE(A && spl_tab && seq_model_ok(model) && weight_ok(weight), CP_EINVAL, "bad argument");
+    return guarded([&]() -> int32_t {
+        seq_check(A && spl_tab, model, weight);
         CP_REQUIRE(model->dtype == CP_I64 ? cst_i64 != nullptr : cst_f64 != nullptr, CP_EINVAL, "cst table of the model's element type needed");
-        CP_HIP(hipSetDevice(A->device));
-        if (model->dtype == CP_I64) return run_pack_dynamic<int64_t>(A, model, Pi, weight, wmax_i64, wmax_f64, nullptr, nullptr, spl_tab, cst_i64);
-        return run_pack_dynamic<double>(A, model, Pi, weight, wmax_i64, wmax_f64, nullptr, nullptr, spl_tab, cst_f64);
-    } CP_CATCH_ALL
+        return seq_run(A, model, [&](auto tag) {
+            using TC = decltype(tag);
+            return run_pack_dynamic<TC>(A, model, Pi, weight, wmax_i64, wmax_f64, nullptr, nullptr, spl_tab, pick<TC>(cst_i64, cst_f64));
+        });
+    });
 }
 
 int32_t cp_pack_convex(cp_csr_t A, const cp_model_t *model, const cp_rowpart_t *Pi, const cp_model_t *weight, int64_t wmax_i64,
                        double wmax_f64, int64_t *spl_out, int64_t *K_out)
 {
-    try {
-        CP_REQUIRE(!seq_model_sym(model), CP_EUNSUPPORTED, "the symmetric cost models have no device path in this method");
-        CP_REQUIRE(A && spl_out && K_out && seq_model_ok(model) && weight_ok(weight), CP_EINVAL, "bad argument");
-        CP_HIP(hipSetDevice(A->device));
-        if (model->dtype == CP_I64) return run_pack_convex<int64_t>(A, model, Pi, weight, wmax_i64, wmax_f64, spl_out, K_out);
-        return run_pack_convex<double>(A, model, Pi, weight, wmax_i64, wmax_f64, spl_out, K_out);
-    } CP_CATCH_ALL
+    return guarded([&]() -> int32_t {
+        seq_check(A && spl_out && K_out, model, weight);
+        return seq_run(A, model, [&](auto tag) { return run_pack_convex<decltype(tag)>(A, model, Pi, weight, wmax_i64, wmax_f64, spl_out, K_out); });
+    });
 }
 
 int32_t cp_pack_convex_batch(cp_csr_t A, int64_t B, const cp_model_t *models, const int64_t *wmax, int64_t ld, int64_t *spl_out, int64_t *K_out)
 {
-    try {
+    return guarded([&]() -> int32_t {
         CP_REQUIRE(A && models && wmax && spl_out && K_out && B >= 1 && B <= 65535 && ld >= 2, CP_EINVAL, "bad argument");
         CP_REQUIRE(A->n >= 1 && (double)(A->n + 2) * (double)(2 * CW_MAXW + 3) < 2e9, CP_EUNSUPPORTED, "pattern too small / too large for the window table");
         for (int64_t b = 0; b < B; b++) {
@@ -1330,46 +1312,35 @@ int32_t cp_pack_convex_batch(cp_csr_t A, int64_t B, const cp_model_t *models, co
                        CP_EUNSUPPORTED, "a batch takes ColumnBlock / Connectivity / Work models without per-part alpha");
             CP_REQUIRE(wmax[b] >= 1 && wmax[b] <= CW_MAXW, CP_EUNSUPPORTED, "a batch takes width limits 1 .. 15 (the LDS-resident window kernel)");
         }
-        CP_HIP(hipSetDevice(A->device));
-        if (models[0].dtype == CP_I64) return run_pack_convex_batch<int64_t>(A, B, models, wmax, ld, spl_out, K_out);
-        return run_pack_convex_batch<double>(A, B, models, wmax, ld, spl_out, K_out);
-    } CP_CATCH_ALL
+        return seq_run(A, models, [&](auto tag) { return run_pack_convex_batch<decltype(tag)>(A, B, models, wmax, ld, spl_out, K_out); });
+    });
 }
 
 int32_t cp_partition_convex(cp_csr_t A, int64_t K, const cp_model_t *model, const cp_rowpart_t *Pi, const cp_model_t *weight,
                             int64_t wmax_i64, double wmax_f64, int64_t *spl_out)
 {
-    try {
-        CP_REQUIRE(!seq_model_sym(model), CP_EUNSUPPORTED, "the symmetric cost models have no device path in this method");
-        CP_REQUIRE(A && spl_out && K >= 1 && seq_model_ok(model) && weight_ok(weight), CP_EINVAL, "bad argument");
-        CP_HIP(hipSetDevice(A->device));
-        if (model->dtype == CP_I64) return run_partition_convex<int64_t>(A, K, model, Pi, weight, wmax_i64, wmax_f64, spl_out);
-        return run_partition_convex<double>(A, K, model, Pi, weight, wmax_i64, wmax_f64, spl_out);
-    } CP_CATCH_ALL
+    return guarded([&]() -> int32_t {
+        seq_check(A && spl_out && K >= 1, model, weight);
+        return seq_run(A, model, [&](auto tag) { return run_partition_convex<decltype(tag)>(A, K, model, Pi, weight, wmax_i64, wmax_f64, spl_out); });
+    });
 }
 
 int32_t cp_pack_concave(cp_csr_t A, const cp_model_t *model, const cp_rowpart_t *Pi, const cp_model_t *weight, int64_t wmax_i64,
                         double wmax_f64, int64_t *spl_out, int64_t *K_out)
 {
-    try {
-        CP_REQUIRE(!seq_model_sym(model), CP_EUNSUPPORTED, "the symmetric cost models have no device path in this method");
-        CP_REQUIRE(A && spl_out && K_out && seq_model_ok(model) && weight_ok(weight), CP_EINVAL, "bad argument");
-        CP_HIP(hipSetDevice(A->device));
-        if (model->dtype == CP_I64) return run_pack_concave<int64_t>(A, model, Pi, weight, wmax_i64, wmax_f64, spl_out, K_out);
-        return run_pack_concave<double>(A, model, Pi, weight, wmax_i64, wmax_f64, spl_out, K_out);
-    } CP_CATCH_ALL
+    return guarded([&]() -> int32_t {
+        seq_check(A && spl_out && K_out, model, weight);
+        return seq_run(A, model, [&](auto tag) { return run_pack_concave<decltype(tag)>(A, model, Pi, weight, wmax_i64, wmax_f64, spl_out, K_out); });
+    });
 }
 
 int32_t cp_partition_concave(cp_csr_t A, int64_t K, const cp_model_t *model, const cp_rowpart_t *Pi, const cp_model_t *weight,
                              int64_t wmax_i64, double wmax_f64, int64_t *spl_out)
 {
-    try {
-        CP_REQUIRE(!seq_model_sym(model), CP_EUNSUPPORTED, "the symmetric cost models have no device path in this method");
-        CP_REQUIRE(A && spl_out && K >= 1 && seq_model_ok(model) && weight_ok(weight), CP_EINVAL, "bad argument");
-        CP_HIP(hipSetDevice(A->device));
-        if (model->dtype == CP_I64) return run_partition_concave<int64_t>(A, K, model, Pi, weight, wmax_i64, wmax_f64, spl_out);
-        return run_partition_concave<double>(A, K, model, Pi, weight, wmax_i64, wmax_f64, spl_out);
-    } CP_CATCH_ALL
+    return guarded([&]() -> int32_t {
+        seq_check(A && spl_out && K >= 1, model, weight);
+        return seq_run(A, model, [&](auto tag) { return run_partition_concave<decltype(tag)>(A, K, model, Pi, weight, wmax_i64, wmax_f64, spl_out); });
+    });
 }
 
 }  // extern "C"

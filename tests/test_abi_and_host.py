@@ -106,3 +106,29 @@ def test_plain_c_client_builds_against_the_header():
     import subprocess
     subprocess.check_call(["make", "-C", os.path.join(ROOT, "examples"), "clean", "c_abi_demo"], stdout=subprocess.DEVNULL)
     assert os.path.exists(os.path.join(ROOT, "examples", "c_abi_demo"))
+
+
+# every option of cp_set_option with its default (csrc: the g_opt_* definitions): setting it again leaves the process as it was
+OPTIONS = {"force_brute": 0, "brute_max_n": 200000, "dbg": 0, "short_t": 8, "short_e": 64, "rpass_ch": 256, "prof_only": -1, "gap_tau": 6,
+           "gap_min": 64, "gap_nr": 2, "pool": 1, "ra_cache": 1, "leaf": 1, "poison": 0, "block_tables": 0, "rpass_small_tau": 4,
+           "force_max": 1024, "setup_bs": 1024, "rpass_cap": 200, "fixed_point": 0, "nospec": 0, "own_min": 64, "own_blk": 1, "bn_chunk": 8,
+           "bn_wave": 2, "bn_slack": 64, "lws": 1, "lws_leaf": 512, "bn_run": 253}
+STATS = ["spec_redo", "poison_hits", "fix_trips", "fix_edges", "bn_sym_layers"]
+
+
+def test_options_and_stats_by_name():
+    from chainpartitioners_jl_amd import _lib
+    lib = C.CDLL(_lib.LIB_PATH)
+    lib.cp_last_error.restype = C.c_char_p
+    for name, default in OPTIONS.items():
+        assert lib.cp_set_option(name.encode(), C.c_int64(default)) == 0, name
+    assert lib.cp_set_option(b"no_such_option", C.c_int64(1)) == 1            # CP_EINVAL
+    assert lib.cp_last_error() == b"unknown option"
+    assert lib.cp_set_option(None, C.c_int64(1)) == 1
+    out = C.c_int64(-1)
+    assert lib.cp_set_option(b"stat_reset", C.c_int64(0)) == 0
+    for name in STATS:
+        out.value = -1
+        assert lib.cp_get_stat(name.encode(), C.byref(out)) == 0 and out.value == 0, name
+    assert lib.cp_get_stat(b"no_such_stat", C.byref(out)) == 1
+    assert lib.cp_get_stat(b"spec_redo", None) == 1
