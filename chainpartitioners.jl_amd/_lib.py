@@ -1,12 +1,15 @@
 """ctypes binding of the product C-ABI library libchainpart.so (HIP, gfx950).
 
 No fallback of any kind lives here: if the shared object is missing, or no HIP device is
-visible, construction raises.  The symbols bound are exactly those of include/chainpart.h.
+visible, construction raises.  The symbols bound are exactly those of include/chainpart.h:
+SIGNATURES declares each prototype once, load_library() applies it, and the argument classes
+below check at the boundary what C cannot (element type and contiguity of every host array).
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
+from functools import partial
 import weakref
 
 import numpy as np
@@ -16,18 +19,124 @@ from . import models as M
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CP_LIB_PATH") or os.path.join(_HERE, "libchainpart.so")   # CP_LIB_PATH: A/B builds only
 
-SYMBOLS = [
-    "cp_last_error", "cp_version", "cp_device_count", "cp_csr_create", "cp_csr_create_device", "cp_csr_destroy",
-    "cp_csr_reset_cache", "cp_count_build", "cp_count_query", "cp_count_destroy", "cp_link_array", "cp_partwise", "cp_domsum_build", "cp_rook_build", "cp_wsum_query", "cp_wsum_destroy",
-    "cp_oracle_eval", "cp_oracle_step", "cp_bound_stripe", "cp_objective", "cp_partition_dynamic", "cp_pack_dynamic", "cp_pack_dynamic_tables",
-    "cp_partition_bisect_cost", "cp_partition_bisect_cost_batch", "cp_pack_convex", "cp_pack_convex_batch", "cp_partition_convex", "cp_partition_equi", "cp_pack_equi",
-    "cp_dynamic_tables", "cp_dynamic_tables_constrained", "cp_dynamic_tables_constrained_combine", "cp_set_stream", "cp_reset_stream", "cp_get_stat", "cp_test_round_scans", "cp_set_option", "cp_prof_enable", "cp_prof_reset", "cp_prof_get",
-    "cp_dp_begin", "cp_dp_layer", "cp_dp_ptr_at", "cp_dp_destroy", "cp_dp_ptr_row", "cp_dp_block_tables", "cp_dp_set_window", "cp_dp_set_rows",
-    "cp_partition_bisect_index", "cp_partition_lazy_bisect_cost", "cp_partition_lazy_bisect_cost_probes", "cp_pack_concave", "cp_partition_concave",
-    "cp_adjoint", "cp_csr_download", "cp_bound_stripe_pi", "cp_partition_bisect_cost_pi", "cp_partition_bisect_index_pi",
-]
+
+class _Array:
+    """`T *name` over caller-owned host memory: None (NULL) or a C-contiguous numpy array of exactly this element type."""
+
+    def __init__(self, dtype, name):
+        self.dtype, self.name, self.what = np.dtype(dtype), name, np.dtype(dtype).name
+
+    def _accepts(self, a):
+        return a.dtype == self.dtype
+
+    def from_param(self, a):
+        if a is None:
+            return None
+        if not (isinstance(a, np.ndarray) and self._accepts(a) and a.flags.c_contiguous):
+            got = f"{'' if a.flags.c_contiguous else 'non-contiguous '}{a.dtype} array" if isinstance(a, np.ndarray) else type(a).__name__
+            raise TypeError(f"{self.name}: expected None or a C-contiguous {self.what} array, got {got}")
+        return C.c_void_p(a.ctypes.data)
+
+
+class _Words(_Array):
+    """`const void *name`: 8-byte elements whose type another argument gives (the weights of cp_domsum_build / cp_rook_build)."""
+
+    def __init__(self, name):
+        self.dtype, self.name, self.what = None, name, "8-byte-element"
+
+    def _accepts(self, a):
+        return a.dtype.itemsize == 8
+
+
+_I64, _I32, _F64 = (partial(_Array, t) for t in (np.int64, np.int32, np.float64))
+_i32, _i64, _f64, _vp, _str = C.c_int32, C.c_int64, C.c_double, C.c_void_p, C.c_char_p   # handles and device pointers: c_void_p
+_pi32, _pi64, _pf64, _pvp = C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double), C.POINTER(C.c_void_p)    # out scalars
+_MODEL, _ROWPART = C.POINTER(M.cp_model_t), C.POINTER(M.cp_rowpart_t)     # take the struct, byref(struct), a Marshalled or None
+_PACK = (_i32, [_vp, _MODEL, _ROWPART, _MODEL, _i64, _f64, _I64("spl_out"), _I64("K_out")])
+_SPLIT = (_i32, [_vp, _i64, _MODEL, _ROWPART, _MODEL, _i64, _f64, _I64("spl_out")])
+
+# every function of include/chainpart.h: name -> (restype, argtypes); tests/test_abi_and_host.py holds it against the header
+SIGNATURES = {
+    "cp_last_error": (_str, []),
+    "cp_version": (_i32, []),
+    "cp_device_count": (_i32, []),
+    "cp_csr_create": (_i32, [_i64, _i64, _i64, _I64("colptr"), _I64("rowval"), _i32, _pvp]),
+    "cp_csr_create_device": (_i32, [_i64, _i64, _i64, _vp, _vp, _i32, _pvp]),
+    "cp_csr_destroy": (_i32, [_vp]),
+    "cp_adjoint": (_i32, [_vp, _pvp]),
+    "cp_csr_download": (_i32, [_vp, _I64("dims_out"), _I64("colptr_out"), _I64("rowval_out")]),
+    "cp_csr_reset_cache": (_i32, [_vp]),
+    "cp_count_build": (_i32, [_vp, _i32, _i32, _pvp]),
+    "cp_count_query": (_i32, [_vp, _i64, _I64("a"), _I64("b"), _I64("out")]),
+    "cp_count_destroy": (_i32, [_vp]),
+    "cp_link_array": (_i32, [_vp, _I64("out")]),
+    "cp_domsum_build": (_i32, [_vp, _i32, _Words("val"), _pvp]),
+    "cp_rook_build": (_i32, [_i64, _I64("idx"), _i32, _Words("val"), _i32, _pvp]),
+    "cp_wsum_query": (_i32, [_vp, _i64, _I64("i"), _I64("j"), _I64("count_out"), _I64("sum_i64"), _F64("sum_f64")]),
+    "cp_wsum_destroy": (_i32, [_vp]),
+    "cp_partwise": (_i32, [_vp, _i64, _I64("asg"), _pi64, _I64("pios_out"), _I64("prm_out"), _I64("pos_out"), _I64("idx_out")]),
+    "cp_oracle_eval": (_i32, [_vp, _MODEL, _ROWPART, _i32, _i64, _I64("j"), _I64("jp"), _I64("k"), _I64("out_i64"), _F64("out_f64")]),
+    "cp_oracle_step": (_i32, [_vp, _MODEL, _ROWPART, _i64, _I32("move_j"), _I64("j"), _I32("move_jp"), _I64("jp"), _I64("k"),
+                              _I64("out_i64"), _F64("out_f64")]),
+    "cp_bound_stripe": (_i32, [_vp, _i64, _MODEL, _pi64, _pi64, _pf64, _pf64]),
+    "cp_bound_stripe_pi": (_i32, [_vp, _i64, _ROWPART, _MODEL, _pi64, _pi64, _pf64, _pf64]),
+    "cp_objective": (_i32, [_vp, _i64, _I64("spl"), _MODEL, _ROWPART, _i32, _pi64, _pf64]),
+    "cp_partition_dynamic": (_i32, [_vp, _i64, _i32, _i32, _MODEL, _ROWPART, _MODEL, _i64, _f64, _I64("spl_out")]),
+    "cp_pack_dynamic": _PACK,
+    "cp_pack_dynamic_tables": (_i32, [_vp, _MODEL, _ROWPART, _MODEL, _i64, _f64, _I64("spl_tab"), _I64("cst_i64"), _F64("cst_f64")]),
+    "cp_partition_bisect_cost": (_i32, [_vp, _i64, _MODEL, _f64, _i32, _I64("spl_out")]),
+    "cp_partition_bisect_cost_batch": (_i32, [_vp, _i64, _I64("K"), _MODEL, _F64("eps"), _I32("flip"), _i64, _I64("spl_out")]),
+    "cp_partition_bisect_cost_pi": (_i32, [_vp, _i64, _MODEL, _ROWPART, _f64, _i32, _I64("spl_out")]),
+    "cp_partition_bisect_index_pi": (_i32, [_vp, _i64, _MODEL, _ROWPART, _i32, _I64("spl_out")]),
+    "cp_pack_concave": _PACK,
+    "cp_partition_concave": _SPLIT,
+    "cp_partition_bisect_index": (_i32, [_vp, _i64, _MODEL, _i32, _I64("spl_out")]),
+    "cp_partition_lazy_bisect_cost": (_i32, [_vp, _i64, _MODEL, _f64, _I64("spl_out")]),
+    "cp_partition_lazy_bisect_cost_probes": (_i32, [_vp, _i64, _MODEL, _f64, _I64("spl_out"), _pi64]),
+    "cp_pack_convex": _PACK,
+    "cp_pack_convex_batch": (_i32, [_vp, _i64, _MODEL, _I64("wmax"), _i64, _I64("spl_out"), _I64("K_out")]),
+    "cp_partition_convex": _SPLIT,
+    "cp_partition_equi": (_i32, [_i64, _i64, _I64("spl_out")]),
+    "cp_pack_equi": (_i32, [_i64, _i64, _I64("spl_out"), _I64("K_out")]),
+    "cp_dynamic_tables": (_i32, [_vp, _i64, _i32, _MODEL, _ROWPART, _I64("ptr_out"), _I64("cst_i64"), _F64("cst_f64")]),
+    "cp_dynamic_tables_constrained": (_i32, [_vp, _i64, _MODEL, _i64, _I64("win_lo"), _I64("win_hi"), _I64("ptr_out"),
+                                             _I64("cst_i64"), _F64("cst_f64")]),
+    "cp_dynamic_tables_constrained_combine": (_i32, [_vp, _i64, _i32, _MODEL, _MODEL, _i64, _f64, _I64("win_lo"), _I64("win_hi"),
+                                                     _I64("ptr_out"), _I64("cst_i64"), _F64("cst_f64")]),
+    "cp_dp_begin": (_i32, [_vp, _i64, _i32, _i32, _MODEL, _i64, _i64, _pvp]),
+    "cp_dp_layer": (_i32, [_vp, _i64, _vp, _vp]),
+    "cp_dp_ptr_at": (_i32, [_vp, _i64, _i64, _pi64]),
+    "cp_dp_ptr_row": (_i32, [_vp, _i64, _I64("out")]),
+    "cp_dp_set_window": (_i32, [_vp, _i64]),
+    "cp_dp_set_rows": (_i32, [_vp, _i64, _i64]),
+    "cp_dp_block_tables": (_i32, [_vp, _pi32, _I64("opt_out"), _I64("nets_out"), _I64("selfnets_out")]),
+    "cp_dp_destroy": (_i32, [_vp]),
+    "cp_set_stream": (_i32, [_vp, _vp]),
+    "cp_reset_stream": (_i32, [_vp]),
+    "cp_get_stat": (_i32, [_str, _pi64]),
+    "cp_test_round_scans": (_i32, [_I32("a"), _i64, _i64, _I32("b"), _i64, _i64, _i32, _i64, _i64, _i32, _i32,
+                                   _I64("offs_out"), _I64("toffs_out"), _I64("res")]),
+    "cp_set_option": (_i32, [_str, _i64]),
+    "cp_prof_enable": (_i32, [_i32]),
+    "cp_prof_reset": (_i32, []),
+    "cp_prof_get": (_i32, [_i32, C.POINTER(C.c_char_p), _pi64, _pf64, _pf64]),
+}
+SYMBOLS = list(SIGNATURES)
 
 _lib = None
+
+
+def _typed(name, fn, restype, argtypes):
+    """fn with its prototype set.  ctypes reports an argument its argtype refused as ctypes.ArgumentError; callers get the
+    TypeError it stands for."""
+    fn.restype, fn.argtypes = restype, argtypes
+
+    def call(*args):
+        try:
+            return fn(*args)
+        except C.ArgumentError as e:
+            raise TypeError(f"{name}: {e}") from None
+    return call
 
 
 def load_library():
@@ -36,17 +145,20 @@ def load_library():
         if not os.path.exists(LIB_PATH):
             raise RuntimeError(f"{LIB_PATH} is missing: build it with __graft_entry__.build() "
                                "(make -C chainpartitioners.jl_amd/csrc); there is no CPU fallback")
-        _lib = C.CDLL(LIB_PATH)
-        _lib.cp_last_error.restype = C.c_char_p
+        lib = C.CDLL(LIB_PATH)
+        for name, (restype, argtypes) in SIGNATURES.items():
+            setattr(lib, name, _typed(name, getattr(lib, name), restype, argtypes))
+        _lib = lib
     return _lib
 
 
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
+def _cost_zeros(mm, shape):
+    return np.zeros(shape, dtype=np.int64 if mm.struct.dtype == M.CP_I64 else np.float64)
 
 
-def _i64(x):
-    return C.c_int64(int(x))
+def _by_type(a):
+    """the `int64_t *x_i64, double *x_f64` pair of an entry that writes values of the model's element type: a and NULL"""
+    return (None, a) if a.dtype == np.float64 else (a, None)
 
 
 _COUNT_KIND = {"dom": 0, "net": 1, "selfnet": 2, "dianet": 3, "selfpin": 4}
@@ -66,30 +178,37 @@ class HipBackend:
     def last_error(self):
         return (self.lib.cp_last_error() or b"").decode()
 
+    def _ok(self, rc, what, exc=RuntimeError):
+        if rc != 0:
+            raise exc(f"{what} -> {rc}: {self.last_error()}")
+
     # ---- CSR residency: one device handle per host matrix object, dropped with it
+    def _register(self, obj, h):
+        lib, handles, key = self.lib, self._handles, id(obj)
+
+        def _drop(_ref):
+            handles.pop(key, None)
+            lib.cp_csr_destroy(h)
+        handles[key] = (weakref.ref(obj, _drop), h)
+        return h
+
     def csr(self, A):
-        key = id(A)
-        ent = self._handles.get(key)
+        ent = self._handles.get(id(A))
         if ent is not None and ent[0]() is A:
             return ent[1]
         h = C.c_void_p()
-        rc = self.lib.cp_csr_create(_i64(A.m), _i64(A.n), _i64(A.nnz), _p(A.colptr), _p(A.rowval), C.c_int32(self.device), C.byref(h))
+        rc = self.lib.cp_csr_create(A.m, A.n, A.nnz, A.colptr, A.rowval, self.device, C.byref(h))
         if rc != 0:
             raise RuntimeError(f"cp_csr_create failed ({rc}): {self.last_error()}")
-        lib = self.lib
-        handles = self._handles
+        return self._register(A, h)
 
-        def _drop(_ref, key=key, h=h):
-            handles.pop(key, None)
-            lib.cp_csr_destroy(h)
-        self._handles[key] = (weakref.ref(A, _drop), h)
-        return h
+    def _h(self, A):
+        return A if isinstance(A, C.c_void_p) else self.csr(A)
 
     def csr_from_device(self, m, n, N, colptr_dev_ptr, rowval_dev_ptr):
         """Handle over colptr/rowval already resident in HBM (1-based int64 device arrays)."""
         h = C.c_void_p()
-        rc = self.lib.cp_csr_create_device(_i64(m), _i64(n), _i64(N), C.c_void_p(colptr_dev_ptr), C.c_void_p(rowval_dev_ptr),
-                                           C.c_int32(self.device), C.byref(h))
+        rc = self.lib.cp_csr_create_device(m, n, N, colptr_dev_ptr, rowval_dev_ptr, self.device, C.byref(h))
         if rc != 0:
             raise RuntimeError(f"cp_csr_create_device failed ({rc}): {self.last_error()}")
         return h
@@ -106,33 +225,25 @@ class HipBackend:
         if rc != 0:
             raise RuntimeError(f"cp_adjoint failed ({rc}): {self.last_error()}")
         dims = np.zeros(3, dtype=np.int64)
-        self.lib.cp_csr_download(t, _p(dims), None, None)
+        self.lib.cp_csr_download(t, dims, None, None)
         m, n, N = (int(x) for x in dims)
         colptr = np.zeros(n + 1, dtype=np.int64); rowval = np.zeros(max(N, 1), dtype=np.int64)
-        rc = self.lib.cp_csr_download(t, _p(dims), _p(colptr), _p(rowval))
+        rc = self.lib.cp_csr_download(t, dims, colptr, rowval)
         if rc != 0:
             self.lib.cp_csr_destroy(t)
             raise RuntimeError(f"cp_csr_download failed ({rc}): {self.last_error()}")
         T = SparseMatrixCSC(m, n, colptr, rowval[:N])
-        lib, handles, key = self.lib, self._handles, id(T)
-
-        def _drop(_ref, key=key, t=t):
-            handles.pop(key, None)
-            lib.cp_csr_destroy(t)
-        self._handles[key] = (weakref.ref(T, _drop), t)
+        self._register(T, t)
         return T
 
     def reset_cache(self, A_or_handle):
-        h = A_or_handle if isinstance(A_or_handle, C.c_void_p) else self.csr(A_or_handle)
-        return self.lib.cp_csr_reset_cache(h)
+        return self.lib.cp_csr_reset_cache(self._h(A_or_handle))
 
     def set_stream(self, A_or_handle, stream_ptr):
-        h = A_or_handle if isinstance(A_or_handle, C.c_void_p) else self.csr(A_or_handle)
-        return self.lib.cp_set_stream(h, C.c_void_p(stream_ptr))
+        return self.lib.cp_set_stream(self._h(A_or_handle), stream_ptr)
 
     def reset_stream(self, A_or_handle):
-        h = A_or_handle if isinstance(A_or_handle, C.c_void_p) else self.csr(A_or_handle)
-        return self.lib.cp_reset_stream(h)
+        return self.lib.cp_reset_stream(self._h(A_or_handle))
 
     def get_stat(self, name):
         out = C.c_int64()
@@ -148,42 +259,31 @@ class HipBackend:
         offs = np.zeros(len(a) + 1, dtype=np.int64)
         toffs = np.zeros(len(b) + 1, dtype=np.int64)
         res = np.zeros(6, dtype=np.int64)
-        rc = self.lib.cp_test_round_scans(_p(a), _i64(len(a)), _i64(na_max), _p(b), _i64(len(b)), _i64(nb_max), C.c_int32(1 if two else 0),
-                                          _i64(cap_t), _i64(cap_nt), C.c_int32(err_in), C.c_int32(reps), _p(offs), _p(toffs), _p(res))
-        if rc != 0:
-            raise RuntimeError(f"cp_test_round_scans -> {rc}: {self.last_error()}")
+        rc = self.lib.cp_test_round_scans(a, len(a), na_max, b, len(b), nb_max, 1 if two else 0, cap_t, cap_nt, err_in, reps,
+                                          offs, toffs, res)
+        self._ok(rc, "cp_test_round_scans")
         return offs, toffs, dict(zip(("T", "NT", "nlong", "nown", "ntile", "err"), (int(v) for v in res)))
 
     def set_option(self, name, value):
-        return self.lib.cp_set_option(name.encode(), _i64(value))
-
-    def _h(self, A):
-        return A if isinstance(A, C.c_void_p) else self.csr(A)
+        return self.lib.cp_set_option(name.encode(), value)
 
     # ---- partitioners
     def partition_dynamic(self, A, K, combine, order, mm, rp, wm, wi, wf, spl):
-        return self.lib.cp_partition_dynamic(self._h(A), _i64(K), C.c_int32(combine), C.c_int32(order), mm.ptr,
-                                             C.byref(rp) if rp is not None else None,
-                                             wm.ptr if wm is not None else None, _i64(wi), C.c_double(wf), _p(spl))
+        return self.lib.cp_partition_dynamic(self._h(A), K, combine, order, mm, rp, wm, wi, wf, spl)
 
     def pack_dynamic(self, A, mm, rp, wm, wi, wf, spl, Kout):
-        return self.lib.cp_pack_dynamic(self._h(A), mm.ptr, C.byref(rp) if rp is not None else None,
-                                        wm.ptr if wm is not None else None, _i64(wi), C.c_double(wf), _p(spl), _p(Kout))
+        return self.lib.cp_pack_dynamic(self._h(A), mm, rp, wm, wi, wf, spl, Kout)
 
     def pack_dynamic_tables(self, A, mm, rp, wm, wi, wf):
         """(rc, cst[n+1], spl[n+1]) of DynamicTotalChunker: the tables DynamicChunker.jl:20-56 builds before unravel_chunks!
         (index j' - 1; spl[0] = 0)"""
         spl = np.zeros(A.n + 1, dtype=np.int64)
-        cst = np.zeros(A.n + 1, dtype=np.int64 if mm.struct.dtype == M.CP_I64 else np.float64)
-        rc = self.lib.cp_pack_dynamic_tables(self._h(A), mm.ptr, C.byref(rp) if rp is not None else None,
-                                             wm.ptr if wm is not None else None, _i64(wi), C.c_double(wf), _p(spl),
-                                             _p(cst) if mm.struct.dtype == M.CP_I64 else None,
-                                             _p(cst) if mm.struct.dtype == M.CP_F64 else None)
+        cst = _cost_zeros(mm, A.n + 1)
+        rc = self.lib.cp_pack_dynamic_tables(self._h(A), mm, rp, wm, wi, wf, spl, *_by_type(cst))
         return rc, cst, spl
 
     def partition_bisect_cost(self, A, K, mm, eps, flip, spl, rp=None):
-        return self.lib.cp_partition_bisect_cost_pi(self._h(A), _i64(K), mm.ptr, C.byref(rp) if rp is not None else None,
-                                                    C.c_double(eps), C.c_int32(flip), _p(spl))
+        return self.lib.cp_partition_bisect_cost_pi(self._h(A), K, mm, rp, eps, flip, spl)
 
     def partition_bisect_cost_batch(self, A, Ks, mms, epss, flips):
         """B requests on one pattern in one launch -> (rc, [split vector of request b])"""
@@ -194,26 +294,24 @@ class HipBackend:
         fv = np.ascontiguousarray(flips, dtype=np.int32)
         ld = int(Kv.max()) + 1
         out = np.zeros((B, ld), dtype=np.int64)
-        rc = self.lib.cp_partition_bisect_cost_batch(self._h(A), _i64(B), _p(Kv), arr, _p(ev), _p(fv), _i64(ld), _p(out))
+        rc = self.lib.cp_partition_bisect_cost_batch(self._h(A), B, Kv, arr, ev, fv, ld, out)
         return rc, [out[b, :int(Kv[b]) + 1].copy() for b in range(B)]
 
     def partition_bisect_index(self, A, K, mm, flip, spl, rp=None):
-        return self.lib.cp_partition_bisect_index_pi(self._h(A), _i64(K), mm.ptr, C.byref(rp) if rp is not None else None,
-                                                     C.c_int32(flip), _p(spl))
+        return self.lib.cp_partition_bisect_index_pi(self._h(A), K, mm, rp, flip, spl)
 
     def partition_lazy_bisect_cost(self, A, K, mm, eps, spl):
-        return self.lib.cp_partition_lazy_bisect_cost(self._h(A), _i64(K), mm.ptr, C.c_double(eps), _p(spl))
+        return self.lib.cp_partition_lazy_bisect_cost(self._h(A), K, mm, eps, spl)
 
     def partition_lazy_bisect_cost_probes(self, A, K, mm, eps):
         """(rc, spl, number of probes the bisection ran)"""
         spl = np.zeros(K + 1, dtype=np.int64)
         npr = C.c_int64()
-        rc = self.lib.cp_partition_lazy_bisect_cost_probes(self._h(A), _i64(K), mm.ptr, C.c_double(eps), _p(spl), C.byref(npr))
+        rc = self.lib.cp_partition_lazy_bisect_cost_probes(self._h(A), K, mm, eps, spl, C.byref(npr))
         return rc, spl, npr.value
 
     def pack_convex(self, A, mm, rp, wm, wi, wf, spl, Kout):
-        return self.lib.cp_pack_convex(self._h(A), mm.ptr, C.byref(rp) if rp is not None else None,
-                                       wm.ptr if wm is not None else None, _i64(wi), C.c_double(wf), _p(spl), _p(Kout))
+        return self.lib.cp_pack_convex(self._h(A), mm, rp, wm, wi, wf, spl, Kout)
 
     def pack_convex_batch(self, A, mms, wmaxs, n):
         """B requests (model, w_max) on one pattern in one launch -> (rc, [chunk boundaries of request b])"""
@@ -223,87 +321,70 @@ class HipBackend:
         ld = int(n) + 1
         out = np.zeros((B, ld), dtype=np.int64)
         Kout = np.zeros(B, dtype=np.int64)
-        rc = self.lib.cp_pack_convex_batch(self._h(A), _i64(B), arr, _p(wv), _i64(ld), _p(out), _p(Kout))
+        rc = self.lib.cp_pack_convex_batch(self._h(A), B, arr, wv, ld, out, Kout)
         return rc, [out[b, :int(Kout[b]) + 1].copy() for b in range(B)]
 
     def partition_convex(self, A, K, mm, rp, wm, wi, wf, spl):
-        return self.lib.cp_partition_convex(self._h(A), _i64(K), mm.ptr, C.byref(rp) if rp is not None else None,
-                                            wm.ptr if wm is not None else None, _i64(wi), C.c_double(wf), _p(spl))
+        return self.lib.cp_partition_convex(self._h(A), K, mm, rp, wm, wi, wf, spl)
 
     def pack_concave(self, A, mm, rp, wm, wi, wf, spl, Kout):
-        return self.lib.cp_pack_concave(self._h(A), mm.ptr, C.byref(rp) if rp is not None else None,
-                                        wm.ptr if wm is not None else None, _i64(wi), C.c_double(wf), _p(spl), _p(Kout))
+        return self.lib.cp_pack_concave(self._h(A), mm, rp, wm, wi, wf, spl, Kout)
 
     def partition_concave(self, A, K, mm, rp, wm, wi, wf, spl):
-        return self.lib.cp_partition_concave(self._h(A), _i64(K), mm.ptr, C.byref(rp) if rp is not None else None,
-                                             wm.ptr if wm is not None else None, _i64(wi), C.c_double(wf), _p(spl))
+        return self.lib.cp_partition_concave(self._h(A), K, mm, rp, wm, wi, wf, spl)
 
     # ---- oracles / scoring
     def oracle_eval(self, A, mm, rp, hint, j, jp, k, out):
-        oi = out if out.dtype == np.int64 else None
-        of = out if out.dtype == np.float64 else None
-        return self.lib.cp_oracle_eval(self._h(A), mm.ptr, C.byref(rp) if rp is not None else None, C.c_int32(hint),
-                                       _i64(j.size), _p(j), _p(jp), _p(k), _p(oi), _p(of))
+        return self.lib.cp_oracle_eval(self._h(A), mm, rp, hint, j.size, j, jp, k, *_by_type(out))
 
     def oracle_step(self, A, mm, rp, mj, j, mjp, jp, k, out):
-        oi = out if out.dtype == np.int64 else None
-        of = out if out.dtype == np.float64 else None
-        return self.lib.cp_oracle_step(self._h(A), mm.ptr, C.byref(rp) if rp is not None else None, _i64(j.size),
-                                       _p(mj), _p(j), _p(mjp), _p(jp), _p(k), _p(oi), _p(of))
+        return self.lib.cp_oracle_step(self._h(A), mm, rp, j.size, mj, j, mjp, jp, k, *_by_type(out))
+
+    def _bounds(self, fn, mm, *args):
+        li, hi, lf, hf = C.c_int64(), C.c_int64(), C.c_double(), C.c_double()
+        rc = fn(*args, C.byref(li), C.byref(hi), C.byref(lf), C.byref(hf))
+        if mm.struct.dtype == M.CP_I64:
+            return rc, li.value, hi.value
+        return rc, lf.value, hf.value
 
     def bound_stripe(self, A, K, mm):
-        li, hi, lf, hf = C.c_int64(), C.c_int64(), C.c_double(), C.c_double()
-        rc = self.lib.cp_bound_stripe(self._h(A), _i64(K), mm.ptr, C.byref(li), C.byref(hi), C.byref(lf), C.byref(hf))
-        if mm.struct.dtype == M.CP_I64:
-            return rc, li.value, hi.value
-        return rc, lf.value, hf.value
+        return self._bounds(self.lib.cp_bound_stripe, mm, self._h(A), K, mm)
 
     def bound_stripe_pi(self, A, K, rp, mm):
-        li, hi, lf, hf = C.c_int64(), C.c_int64(), C.c_double(), C.c_double()
-        rc = self.lib.cp_bound_stripe_pi(self._h(A), _i64(K), C.byref(rp), mm.ptr, C.byref(li), C.byref(hi), C.byref(lf), C.byref(hf))
-        if mm.struct.dtype == M.CP_I64:
-            return rc, li.value, hi.value
-        return rc, lf.value, hf.value
+        return self._bounds(self.lib.cp_bound_stripe_pi, mm, self._h(A), K, rp, mm)
 
     def objective(self, A, K, spl, mm, rp, g):
         oi, of = C.c_int64(), C.c_double()
-        rc = self.lib.cp_objective(self._h(A), _i64(K), _p(spl), mm.ptr, C.byref(rp) if rp is not None else None,
-                                   C.c_int32(g), C.byref(oi), C.byref(of))
+        rc = self.lib.cp_objective(self._h(A), K, spl, mm, rp, g, C.byref(oi), C.byref(of))
         return rc, (oi.value if mm.struct.dtype == M.CP_I64 else of.value)
 
     def dynamic_tables(self, A, K, combine, mm, rp):
         ptr = np.zeros((K, A.n + 1), dtype=np.int64)
-        cst = np.zeros((K, A.n + 1), dtype=np.int64 if mm.struct.dtype == M.CP_I64 else np.float64)
-        rc = self.lib.cp_dynamic_tables(self._h(A), _i64(K), C.c_int32(combine), mm.ptr,
-                                        C.byref(rp) if rp is not None else None, _p(ptr),
-                                        _p(cst) if mm.struct.dtype == M.CP_I64 else None,
-                                        _p(cst) if mm.struct.dtype == M.CP_F64 else None)
+        cst = _cost_zeros(mm, (K, A.n + 1))
+        rc = self.lib.cp_dynamic_tables(self._h(A), K, combine, mm, rp, ptr, *_by_type(cst))
         return rc, ptr.T, cst.T
 
     def dynamic_tables_constrained(self, A, K, mm, wmax, combine=0, wm=None):
         """(rc, j'_lo[K], j'_hi[K], ptr[j', k], cst[j', k]) of Dynamic{Total,Bottleneck}Splitter(ConstrainedCost(f, w, wmax))
         (combine 0 = total, 1 = bottleneck; wm: the marshalled weight, None = VertexCount())"""
         ptr = np.zeros((K, A.n + 1), dtype=np.int64)
-        cst = np.zeros((K, A.n + 1), dtype=np.int64 if mm.struct.dtype == M.CP_I64 else np.float64)
+        cst = _cost_zeros(mm, (K, A.n + 1))
         lo = np.zeros(K, dtype=np.int64); hi = np.zeros(K, dtype=np.int64)
-        rc = self.lib.cp_dynamic_tables_constrained_combine(self._h(A), _i64(K), C.c_int32(combine), mm.ptr, wm.ptr if wm is not None else None,
-                                                            _i64(int(wmax)), C.c_double(float(wmax)), _p(lo), _p(hi), _p(ptr),
-                                                            _p(cst) if mm.struct.dtype == M.CP_I64 else None,
-                                                            _p(cst) if mm.struct.dtype == M.CP_F64 else None)
+        rc = self.lib.cp_dynamic_tables_constrained_combine(self._h(A), K, combine, mm, wm, int(wmax), float(wmax), lo, hi, ptr,
+                                                            *_by_type(cst))
         return rc, lo, hi, ptr.T, cst.T
 
     # ---- counting structures
     def count_build(self, kind, A, hint):
         h = C.c_void_p()
-        rc = self.lib.cp_count_build(self._h(A), C.c_int32(_COUNT_KIND[kind]), C.c_int32(hint), C.byref(h))
-        if rc != 0:
-            if rc == M.CP_EINVAL and kind in ("dianet", "selfpin"):      # the reference asserts m == n
-                raise AssertionError(f"cp_count_build({kind}): violated precondition ({self.last_error()})")
-            raise NotImplementedError(f"cp_count_build({kind}) -> {rc}: {self.last_error()}")
+        rc = self.lib.cp_count_build(self._h(A), _COUNT_KIND[kind], hint, C.byref(h))
+        if rc == M.CP_EINVAL and kind in ("dianet", "selfpin"):      # the reference asserts m == n
+            raise AssertionError(f"cp_count_build({kind}): violated precondition ({self.last_error()})")
+        self._ok(rc, f"cp_count_build({kind})", NotImplementedError)
         return h
 
     def count_query(self, kind, h, a, b, out):
-        return self.lib.cp_count_query(h, _i64(a.size), _p(a), _p(b), _p(out))
+        return self.lib.cp_count_query(h, a.size, a, b, out)
 
     def count_free(self, kind, h):
         self.lib.cp_count_destroy(h)
@@ -313,9 +394,7 @@ class HipBackend:
         val = np.ascontiguousarray(val)
         dt = M.CP_F64 if val.dtype == np.float64 else M.CP_I64
         h = C.c_void_p()
-        rc = self.lib.cp_domsum_build(self._h(A), C.c_int32(dt), _p(val), C.byref(h))
-        if rc != 0:
-            raise RuntimeError(f"cp_domsum_build -> {rc}: {self.last_error()}")
+        self._ok(self.lib.cp_domsum_build(self._h(A), dt, val, C.byref(h)), "cp_domsum_build")
         return h, dt
 
     def rook_build(self, N, idx, val=None):
@@ -325,26 +404,22 @@ class HipBackend:
             val = np.ascontiguousarray(val)
             dt = M.CP_F64 if val.dtype == np.float64 else M.CP_I64
         h = C.c_void_p()
-        rc = self.lib.cp_rook_build(_i64(N), _p(idx), C.c_int32(dt), _p(val), C.c_int32(self.device), C.byref(h))
-        if rc != 0:
-            raise RuntimeError(f"cp_rook_build -> {rc}: {self.last_error()}")
+        self._ok(self.lib.cp_rook_build(N, idx, dt, val, self.device, C.byref(h)), "cp_rook_build")
         return h, dt
 
     def wsum_query(self, h, dt, i, j, unsigned=False):
         i = np.ascontiguousarray(i, dtype=np.int64); j = np.ascontiguousarray(j, dtype=np.int64)
         cnt = np.zeros(i.shape, dtype=np.int64)
-        sm = np.zeros(i.shape, dtype=np.float64 if dt == M.CP_F64 else (np.uint64 if unsigned else np.int64))
-        rc = self.lib.cp_wsum_query(h, _i64(i.size), _p(i), _p(j), _p(cnt), _p(sm) if dt == M.CP_I64 else None, _p(sm) if dt == M.CP_F64 else None)
-        if rc != 0:
-            raise RuntimeError(f"cp_wsum_query -> {rc}: {self.last_error()}")
-        return cnt, sm
+        sm = np.zeros(i.shape, dtype=np.float64 if dt == M.CP_F64 else np.int64)
+        self._ok(self.lib.cp_wsum_query(h, i.size, i, j, cnt, *_by_type(sm)), "cp_wsum_query")
+        return cnt, (sm.view(np.uint64) if unsigned and dt == M.CP_I64 else sm)      # the same words, read as UInt
 
     def wsum_free(self, h):
         self.lib.cp_wsum_destroy(h)
 
     def link_array(self, A):
         out = np.zeros(max(A.nnz, 1), dtype=np.int64)
-        rc = self.lib.cp_link_array(self._h(A), _p(out))
+        rc = self.lib.cp_link_array(self._h(A), out)
         if rc != 0:
             raise RuntimeError(self.last_error())
         return out[:A.nnz]
@@ -356,37 +431,28 @@ class HipBackend:
         prm = np.zeros(max(A.nnz, 1), dtype=np.int64)
         pos = np.zeros(A.nnz + 1, dtype=np.int64)
         idx = np.zeros(max(A.nnz, 1), dtype=np.int64)
-        rc = self.lib.cp_partwise(self._h(A), _i64(K), _p(asg), C.byref(npr), _p(pios), _p(prm), _p(pos), _p(idx))
-        if rc != 0:
-            raise NotImplementedError(f"cp_partwise -> {rc}: {self.last_error()}")
+        rc = self.lib.cp_partwise(self._h(A), K, asg, C.byref(npr), pios, prm, pos, idx)
+        self._ok(rc, "cp_partwise", NotImplementedError)
         n = npr.value
         return n, pios, prm[:n].copy(), pos[:n + 1].copy(), idx[:A.nnz].copy()
 
     # ---- row-tiled DP (multi-GPU): see distributed.py
     def dp_begin(self, A, K, combine, order, mm, row_lo, row_hi):
         h = C.c_void_p()
-        rc = self.lib.cp_dp_begin(self._h(A), _i64(K), C.c_int32(combine), C.c_int32(order), mm.ptr, _i64(row_lo), _i64(row_hi), C.byref(h))
-        if rc != 0:
-            raise RuntimeError(f"cp_dp_begin -> {rc}: {self.last_error()}")
+        self._ok(self.lib.cp_dp_begin(self._h(A), K, combine, order, mm, row_lo, row_hi, C.byref(h)), "cp_dp_begin")
         return h
 
     def dp_layer(self, dp, k, prev_ptr, cur_ptr):
-        rc = self.lib.cp_dp_layer(dp, _i64(k), C.c_void_p(prev_ptr), C.c_void_p(cur_ptr))
-        if rc != 0:
-            raise RuntimeError(f"cp_dp_layer -> {rc}: {self.last_error()}")
+        self._ok(self.lib.cp_dp_layer(dp, k, prev_ptr, cur_ptr), "cp_dp_layer")
 
     def dp_ptr_at(self, dp, k, jp):
         out = C.c_int64()
-        rc = self.lib.cp_dp_ptr_at(dp, _i64(k), _i64(jp), C.byref(out))
-        if rc != 0:
-            raise RuntimeError(f"cp_dp_ptr_at -> {rc}: {self.last_error()}")
+        self._ok(self.lib.cp_dp_ptr_at(dp, k, jp, C.byref(out)), "cp_dp_ptr_at")
         return out.value
 
     def dp_ptr_row(self, dp, k, n):
         out = np.zeros(n + 1, dtype=np.int64)
-        rc = self.lib.cp_dp_ptr_row(dp, _i64(k), _p(out))
-        if rc != 0:
-            raise RuntimeError(f"cp_dp_ptr_row -> {rc}: {self.last_error()}")
+        self._ok(self.lib.cp_dp_ptr_row(dp, k, out), "cp_dp_ptr_row")
         return out
 
     def dp_block_tables(self, dp, n, hyper=False):
@@ -394,21 +460,19 @@ class HipBackend:
         nb = C.c_int32()
         opt = np.zeros((31, n + 1), dtype=np.int64); nn = np.zeros((31, n + 1), dtype=np.int64)
         nl = np.zeros((31, n + 1), dtype=np.int64) if hyper else None
-        rc = self.lib.cp_dp_block_tables(dp, C.byref(nb), _p(opt), _p(nn), _p(nl))
-        if rc != 0:
-            raise RuntimeError(f"cp_dp_block_tables -> {rc}: {self.last_error()}")
+        self._ok(self.lib.cp_dp_block_tables(dp, C.byref(nb), opt, nn, nl), "cp_dp_block_tables")
         # the library lays the planes out with stride n+1
         k = nb.value
         return k, opt.reshape(-1)[:k * (n + 1)].reshape(k, n + 1), nn.reshape(-1)[:k * (n + 1)].reshape(k, n + 1), \
             (nl.reshape(-1)[:k * (n + 1)].reshape(k, n + 1) if hyper else None)
 
     def dp_set_window(self, dp, wmax):
-        rc = self.lib.cp_dp_set_window(dp, _i64(wmax))
+        rc = self.lib.cp_dp_set_window(dp, wmax)
         if rc != 0:
             raise RuntimeError(f"cp_dp_set_window -> {rc}")
 
     def dp_set_rows(self, dp, lo, hi):
-        rc = self.lib.cp_dp_set_rows(dp, _i64(lo), _i64(hi))
+        rc = self.lib.cp_dp_set_rows(dp, lo, hi)
         if rc != 0:
             raise RuntimeError(f"cp_dp_set_rows({lo}, {hi}) -> {rc}")
 
@@ -420,9 +484,7 @@ class HipBackend:
         dev = torch.device("cuda", self.device)
         dp = self.dp_begin(A, 3, 0, 0, mm, lo or 1, hi or n + 2)
         try:
-            rc = self.lib.cp_dp_set_window(dp, _i64(wmax))
-            if rc != 0:
-                raise RuntimeError(f"cp_dp_set_window -> {rc}")
+            self.dp_set_window(dp, wmax)
             prev = torch.from_numpy(np.ascontiguousarray(W)).to(dev)
             cur = torch.zeros(n + 1, dtype=prev.dtype, device=dev)
             self.dp_layer(dp, 2, prev.data_ptr(), cur.data_ptr())
@@ -435,7 +497,7 @@ class HipBackend:
 
     # ---- measurement
     def prof_enable(self, on=True):
-        self.lib.cp_prof_enable(C.c_int32(1 if on else 0))
+        self.lib.cp_prof_enable(1 if on else 0)
 
     def prof_reset(self):
         self.lib.cp_prof_reset()
@@ -444,8 +506,8 @@ class HipBackend:
         out = {}
         name = C.c_char_p()
         n, ms, by = C.c_int64(), C.c_double(), C.c_double()
-        nslots = self.lib.cp_prof_get(C.c_int32(0), C.byref(name), C.byref(n), C.byref(ms), C.byref(by))
-        for s in range(nslots):
-            self.lib.cp_prof_get(C.c_int32(s), C.byref(name), C.byref(n), C.byref(ms), C.byref(by))
+        args = (C.byref(name), C.byref(n), C.byref(ms), C.byref(by))
+        for s in range(self.lib.cp_prof_get(0, *args)):
+            self.lib.cp_prof_get(s, *args)
             out[name.value.decode()] = {"launches": n.value, "ms": ms.value, "units": by.value}
         return out

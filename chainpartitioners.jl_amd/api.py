@@ -15,6 +15,8 @@ Reference entry points mirrored (under /root/reference/src):
 """
 from __future__ import annotations
 
+from collections import namedtuple
+
 import numpy as np
 
 from . import models as M
@@ -101,11 +103,9 @@ def _marshal(A, f, Pi, stack_method=False):
     wlo, wt = _w_table_for(A, mdl, weight, w_max, stack_method)
     if not isinstance(mdl, (M.BlockComponentCostModel, M.ColumnBlockComponentCostModel)):
         wlo = 0
-    if isinstance(mdl, M.BlockComponentCostModel):
-        ut = A.m + 1
-        mm = mdl.marshal(w_table=wt, w_lo=wlo) if mdl.u_table is not None else _marshal_block(mdl, wt, ut, wlo)
-    else:
-        mm = mdl.marshal(w_table=wt, w_lo=wlo)
+    # the block model's row tables run to m + 1 unless the model presets u_table (a preset w_table does not win)
+    ut = A.m + 1 if isinstance(mdl, M.BlockComponentCostModel) and mdl.u_table is None else None
+    mm = mdl.marshal(w_table=wt, w_lo=wlo, u_table=ut)
     wm = weight.marshal() if weight is not None else None
     wmax_i = int(w_max) if weight is not None and (weight.dtype == M.CP_I64) else 0
     wmax_f = float(w_max) if weight is not None else 0.0
@@ -113,16 +113,57 @@ def _marshal(A, f, Pi, stack_method=False):
     return mdl, mm, wm, wmax_i, wmax_f, rp, keep
 
 
-def _marshal_block(mdl, wt, ut, wlo=0):
-    old = (mdl.w_table, mdl.u_table)
-    mdl.w_table, mdl.u_table = wt, ut
-    try:
-        return mdl.marshal(w_lo=wlo)
-    finally:
-        mdl.w_table, mdl.u_table = old
+# ---------------------------------------------------------------- partition_stripe / pack_stripe
+# How a method reaches the backend: the backend method, the name _check reports, stack_method of _w_table_for, when Pi is
+# passed, the refusal of a ConstrainedCost (None: constraints are served) and the method's own scalars.  A row that serves
+# constraints calls b.<call>(A, [K,] *scalars, mm, rp, wm, wi, wf, *outs), one that refuses them b.<call>(A, K, mm, *scalars,
+# spl[, rp]).  Rows are found along the MRO, so the Reference* and Flip* classes follow their bases.
+_Row = namedtuple("_Row", "call what stack pi refuse scalars")
+_PI_ALWAYS, _PI_IF_NEEDED, _PI_NEVER = "always", "if the model needs_rowpart", "never"
+_DYNAMIC = _Row("partition_dynamic", "Dynamic*", False, _PI_ALWAYS, None, lambda m: (m.combine, m.order))
+_PARTITION = {
+    M.DynamicTotalSplitter: _DYNAMIC, M.DynamicBottleneckSplitter: _DYNAMIC,
+    M.DynamicTotalChunker: _DYNAMIC, M.DynamicBottleneckChunker: _DYNAMIC,
+    M.BisectCostBottleneckSplitter: _Row("partition_bisect_cost", "BisectCost", False, _PI_IF_NEEDED,
+                                         "BisectCost on a ConstrainedCost errors in the reference (Costs.jl:150)", lambda m: (m.eps, m.flip)),
+    M.BisectIndexBottleneckSplitter: _Row("partition_bisect_index", "BisectIndex", False, _PI_IF_NEEDED,
+                                          "BisectIndex on a ConstrainedCost errors in the reference (Costs.jl:150)", lambda m: (m.flip,)),
+    M.LazyBisectCostBottleneckSplitter: _Row("partition_lazy_bisect_cost", "LazyBisectCost", False, _PI_NEVER,
+                                             "LazyBisectCost on a ConstrainedCost has no method in the reference", lambda m: (m.eps,)),
+    M.ConvexTotalSplitter: _Row("partition_convex", "ConvexTotalSplitter", True, _PI_ALWAYS, None, lambda m: ()),
+    M.ConcaveTotalSplitter: _Row("partition_concave", "ConcaveTotalSplitter", True, _PI_ALWAYS, None, lambda m: ()),
+}
+_PACK = {
+    M.DynamicTotalChunker: _Row("pack_dynamic", "DynamicTotalChunker", False, _PI_ALWAYS, None, lambda m: ()),
+    M.ConvexTotalChunker: _Row("pack_convex", "ConvexTotalChunker", True, _PI_ALWAYS, None, lambda m: ()),
+    M.ConcaveTotalChunker: _Row("pack_concave", "ConcaveTotalChunker", True, _PI_ALWAYS, None, lambda m: ()),
+}
 
 
-# ---------------------------------------------------------------- partition_stripe
+def _dispatch(fn, table, head, method, Pi, backend, alloc):
+    """The body partition_stripe (head = (A, K)) and pack_stripe (head = (A,)) share: marshal, allocate the outputs, one backend
+    call, _check.  -> the outputs"""
+    b = get_backend(backend)
+    if hasattr(method, "f"):
+        _need_hip(b, M.split_constraint(method.f)[0])
+    row = next((table[c] for c in type(method).__mro__ if c in table), None)
+    if row is None:
+        raise NotImplementedError(f"{fn}: method {type(method).__name__} is outside the hot path")
+    if row.pi == _PI_NEVER or (row.pi == _PI_IF_NEEDED and not getattr(M.split_constraint(method.f)[0], "needs_rowpart", False)):
+        Pi = None
+    mdl, mm, wm, wi, wf, rp, keep = _marshal(head[0], method.f, Pi, row.stack)
+    if row.refuse is not None and wm is not None:
+        raise NotImplementedError(row.refuse)
+    outs = alloc()
+    if row.refuse is None:
+        args = (*row.scalars(method), mm, rp, wm, wi, wf, *outs)
+    else:
+        args = (mm, *row.scalars(method), *outs) + ((rp,) if row.pi == _PI_IF_NEEDED else ())
+    rc = getattr(b, row.call)(*head, *args)
+    _check(rc, f"{fn}({row.what})", b)
+    return outs
+
+
 def partition_stripe(A: SparseMatrixCSC, K, method, Pi=None, *, backend=None) -> SplitPartition:
     K = int(K)
     if isinstance(method, M.EquiSplitter):
@@ -130,53 +171,8 @@ def partition_stripe(A: SparseMatrixCSC, K, method, Pi=None, *, backend=None) ->
         n = A.n
         k = np.arange(0, K + 1, dtype=np.int64)
         return SplitPartition(K, k * (n // K) + np.minimum(n % K, k) + 1)
-    b = get_backend(backend)
-    if hasattr(method, "f"):
-        _need_hip(b, M.split_constraint(method.f)[0])
-    if isinstance(method, (M.DynamicTotalSplitter, M.DynamicBottleneckSplitter,
-                           M.DynamicTotalChunker, M.DynamicBottleneckChunker)):
-        mdl, mm, wm, wi, wf, rp, keep = _marshal(A, method.f, Pi)
-        spl = np.zeros(K + 1, dtype=np.int64)
-        rc = b.partition_dynamic(A, K, method.combine, method.order, mm, rp, wm, wi, wf, spl)
-        _check(rc, "partition_stripe(Dynamic*)", b)
-        return SplitPartition(K, spl)
-    if isinstance(method, M.BisectCostBottleneckSplitter):
-        mdl, mm, wm, wi, wf, rp, keep = _marshal(A, method.f, Pi if getattr(M.split_constraint(method.f)[0], "needs_rowpart", False) else None)
-        if wm is not None:
-            raise NotImplementedError("BisectCost on a ConstrainedCost errors in the reference (Costs.jl:150)")
-        spl = np.zeros(K + 1, dtype=np.int64)
-        rc = b.partition_bisect_cost(A, K, mm, method.eps, method.flip, spl, rp)
-        _check(rc, "partition_stripe(BisectCost)", b)
-        return SplitPartition(K, spl)
-    if isinstance(method, M.BisectIndexBottleneckSplitter):
-        mdl, mm, wm, wi, wf, rp, keep = _marshal(A, method.f, Pi if getattr(M.split_constraint(method.f)[0], "needs_rowpart", False) else None)
-        if wm is not None:
-            raise NotImplementedError("BisectIndex on a ConstrainedCost errors in the reference (Costs.jl:150)")
-        spl = np.zeros(K + 1, dtype=np.int64)
-        rc = b.partition_bisect_index(A, K, mm, method.flip, spl, rp)
-        _check(rc, "partition_stripe(BisectIndex)", b)
-        return SplitPartition(K, spl)
-    if isinstance(method, M.LazyBisectCostBottleneckSplitter):
-        mdl, mm, wm, wi, wf, rp, keep = _marshal(A, method.f, None)
-        if wm is not None:
-            raise NotImplementedError("LazyBisectCost on a ConstrainedCost has no method in the reference")
-        spl = np.zeros(K + 1, dtype=np.int64)
-        rc = b.partition_lazy_bisect_cost(A, K, mm, method.eps, spl)
-        _check(rc, "partition_stripe(LazyBisectCost)", b)
-        return SplitPartition(K, spl)
-    if isinstance(method, M.ConvexTotalSplitter):
-        mdl, mm, wm, wi, wf, rp, keep = _marshal(A, method.f, Pi, stack_method=True)
-        spl = np.zeros(K + 1, dtype=np.int64)
-        rc = b.partition_convex(A, K, mm, rp, wm, wi, wf, spl)
-        _check(rc, "partition_stripe(ConvexTotalSplitter)", b)
-        return SplitPartition(K, spl)
-    if isinstance(method, M.ConcaveTotalSplitter):
-        mdl, mm, wm, wi, wf, rp, keep = _marshal(A, method.f, Pi, stack_method=True)
-        spl = np.zeros(K + 1, dtype=np.int64)
-        rc = b.partition_concave(A, K, mm, rp, wm, wi, wf, spl)
-        _check(rc, "partition_stripe(ConcaveTotalSplitter)", b)
-        return SplitPartition(K, spl)
-    raise NotImplementedError(f"partition_stripe: method {type(method).__name__} is outside the hot path")
+    spl, = _dispatch("partition_stripe", _PARTITION, (A, K), method, Pi, backend, lambda: (np.zeros(K + 1, dtype=np.int64),))
+    return SplitPartition(K, spl)
 
 
 def partition_stripe_batch(A: SparseMatrixCSC, requests, *, backend=None):
@@ -235,31 +231,9 @@ def pack_stripe(A: SparseMatrixCSC, method, Pi=None, *, backend=None) -> SplitPa
         n, w = A.n, method.w
         spl = np.concatenate([np.arange(1, n + 1, w, dtype=np.int64), [n + 1]])   # [1:w:n; n+1]
         return SplitPartition(len(spl) - 1, spl)
-    b = get_backend(backend)
-    if hasattr(method, "f"):
-        _need_hip(b, M.split_constraint(method.f)[0])
-    if isinstance(method, M.DynamicTotalChunker):
-        mdl, mm, wm, wi, wf, rp, keep = _marshal(A, method.f, Pi)
-        spl = np.zeros(A.n + 1, dtype=np.int64)
-        Kout = np.zeros(1, dtype=np.int64)
-        rc = b.pack_dynamic(A, mm, rp, wm, wi, wf, spl, Kout)
-        _check(rc, "pack_stripe(DynamicTotalChunker)", b)
-        return SplitPartition(int(Kout[0]), spl[:int(Kout[0]) + 1].copy())
-    if isinstance(method, M.ConvexTotalChunker):
-        mdl, mm, wm, wi, wf, rp, keep = _marshal(A, method.f, Pi, stack_method=True)
-        spl = np.zeros(A.n + 1, dtype=np.int64)
-        Kout = np.zeros(1, dtype=np.int64)
-        rc = b.pack_convex(A, mm, rp, wm, wi, wf, spl, Kout)
-        _check(rc, "pack_stripe(ConvexTotalChunker)", b)
-        return SplitPartition(int(Kout[0]), spl[:int(Kout[0]) + 1].copy())
-    if isinstance(method, M.ConcaveTotalChunker):
-        mdl, mm, wm, wi, wf, rp, keep = _marshal(A, method.f, Pi, stack_method=True)
-        spl = np.zeros(A.n + 1, dtype=np.int64)
-        Kout = np.zeros(1, dtype=np.int64)
-        rc = b.pack_concave(A, mm, rp, wm, wi, wf, spl, Kout)
-        _check(rc, "pack_stripe(ConcaveTotalChunker)", b)
-        return SplitPartition(int(Kout[0]), spl[:int(Kout[0]) + 1].copy())
-    raise NotImplementedError(f"pack_stripe: method {type(method).__name__} is outside the hot path")
+    spl, Kout = _dispatch("pack_stripe", _PACK, (A,), method, Pi, backend,
+                          lambda: (np.zeros(A.n + 1, dtype=np.int64), np.zeros(1, dtype=np.int64)))
+    return SplitPartition(int(Kout[0]), spl[:int(Kout[0]) + 1].copy())
 
 
 def pack_stripe_tables(A: SparseMatrixCSC, method, Pi=None, *, backend=None):

@@ -80,24 +80,36 @@ class Marshalled:
     def ptr(self):
         return C.byref(self.struct)
 
+    _as_parameter_ = ptr     # what a `const cp_model_t *` parameter of the binding takes
+
 
 class _Model:
     kind = None
     dtype = CP_I64
+    fields = ()             # the attributes that fill cp_model_t.p_i64 / p_f64, in that order
+    alpha_k = None          # per-part alpha[k], where the constructor takes it
     w_table = None          # tabulation length for callables; set via with_table()
 
     def cost_dtype(self):
         return np.int64 if self.dtype == CP_I64 else np.float64
 
+    def _set(self, *values, alpha_k=None):
+        """the constructor of an affine model: stores `values` under `fields` and promotes them all to one element type"""
+        for name, v in zip(self.fields, values):
+            setattr(self, name, v)
+        self.alpha_k = alpha_k
+        self.dtype = _promote(*values, *([alpha_k] if alpha_k is not None else []))
+
     def _params(self):
-        return []
+        return [getattr(self, name) for name in self.fields]
 
     def _alpha_k(self):
-        return None
+        return self.alpha_k
 
-    def marshal(self, w_table=None, w_lo=0):
+    def marshal(self, w_table=None, w_lo=0, u_table=None):
+        """-> Marshalled.  w_lo .. w_table (u_table: the same for the row tables of the block model) is the range closures over
+        the part width are tabulated for; nothing is written to the model."""
         s = cp_model_t()
-        self._w_lo = w_lo
         keep = []
         s.kind = self.kind
         s.dtype = self.dtype
@@ -112,26 +124,19 @@ class _Model:
             keep.append(arr)
             s.alpha_k = arr.ctypes.data
             s.n_alpha_k = arr.size
-        self._marshal_extra(s, keep, w_table)
+        self._marshal_extra(s, keep, w_table, w_lo, u_table)
         return Marshalled(s, keep)
 
-    def _marshal_extra(self, s, keep, w_table):
+    def _marshal_extra(self, s, keep, w_table, w_lo, u_table):
         pass
 
 
 class AffineWorkModel(_Model):
     kind = CP_MODEL_WORK
+    fields = ("alpha", "beta_vertex", "beta_pin")
 
     def __init__(self, alpha=0, beta_vertex=0, beta_pin=0, *, alpha_k=None):
-        self.alpha, self.beta_vertex, self.beta_pin = alpha, beta_vertex, beta_pin
-        self.alpha_k = alpha_k
-        self.dtype = _promote(alpha, beta_vertex, beta_pin, *( [alpha_k] if alpha_k is not None else []))
-
-    def _params(self):
-        return [self.alpha, self.beta_vertex, self.beta_pin]
-
-    def _alpha_k(self):
-        return self.alpha_k
+        self._set(alpha, beta_vertex, beta_pin, alpha_k=alpha_k)
 
     def __call__(self, n_vertices, n_pins, k=None):
         a = self.alpha if self.alpha_k is None or k is None else self.alpha_k[k - 1]
@@ -142,17 +147,12 @@ class PowerWorkModel(_Model):
     """alpha + (n_vertices*beta_vertex + n_pins*beta_pin)^gamma, Float64: the ConvexWorkModel (gamma 0.8) and
     ConcaveWorkModel (gamma 2) of the reference's tests (test/test_Partitioners.jl:54-74)."""
     kind = CP_MODEL_POWER_WORK
+    fields = ("alpha", "beta_vertex", "beta_pin", "gamma")
 
     def __init__(self, alpha, beta_vertex, beta_pin, gamma):
         self.alpha, self.beta_vertex, self.beta_pin, self.gamma = float(alpha), float(beta_vertex), float(beta_pin), float(gamma)
         self.alpha_k = None
         self.dtype = CP_F64
-
-    def _params(self):
-        return [self.alpha, self.beta_vertex, self.beta_pin, self.gamma]
-
-    def _alpha_k(self):
-        return None
 
     def __call__(self, n_vertices, n_pins, k=None):
         x = n_vertices * self.beta_vertex + n_pins * self.beta_pin
@@ -171,17 +171,10 @@ class AffineConnectivityModel(_Model):
     """alpha + nv*beta_vertex + np*beta_pin + nets*beta_net.  `alpha_k` gives the per-part
     alpha[k] of the reference tests' FunkyConnectivityModel (test_Partitioners.jl:1-8)."""
     kind = CP_MODEL_CONNECTIVITY
+    fields = ("alpha", "beta_vertex", "beta_pin", "beta_net")
 
     def __init__(self, alpha=0, beta_vertex=0, beta_pin=0, beta_net=0, *, alpha_k=None):
-        self.alpha, self.beta_vertex, self.beta_pin, self.beta_net = alpha, beta_vertex, beta_pin, beta_net
-        self.alpha_k = alpha_k
-        self.dtype = _promote(alpha, beta_vertex, beta_pin, beta_net, *([alpha_k] if alpha_k is not None else []))
-
-    def _params(self):
-        return [self.alpha, self.beta_vertex, self.beta_pin, self.beta_net]
-
-    def _alpha_k(self):
-        return self.alpha_k
+        self._set(alpha, beta_vertex, beta_pin, beta_net, alpha_k=alpha_k)
 
     def __call__(self, n_vertices, n_pins, n_nets, k=None):
         a = self.alpha if self.alpha_k is None or k is None else self.alpha_k[k - 1]
@@ -190,19 +183,10 @@ class AffineConnectivityModel(_Model):
 
 class AffineHyperedgeCutModel(_Model):
     kind = CP_MODEL_HYPEREDGE_CUT
+    fields = ("alpha", "beta_vertex", "beta_pin", "beta_self_net", "beta_cut_net")
 
     def __init__(self, alpha=0, beta_vertex=0, beta_pin=0, beta_self_net=0, beta_cut_net=0, *, alpha_k=None):
-        self.alpha, self.beta_vertex, self.beta_pin = alpha, beta_vertex, beta_pin
-        self.beta_self_net, self.beta_cut_net = beta_self_net, beta_cut_net
-        self.alpha_k = alpha_k
-        self.dtype = _promote(alpha, beta_vertex, beta_pin, beta_self_net, beta_cut_net,
-                              *([alpha_k] if alpha_k is not None else []))
-
-    def _params(self):
-        return [self.alpha, self.beta_vertex, self.beta_pin, self.beta_self_net, self.beta_cut_net]
-
-    def _alpha_k(self):
-        return self.alpha_k
+        self._set(alpha, beta_vertex, beta_pin, beta_self_net, beta_cut_net, alpha_k=alpha_k)
 
     def __call__(self, n_vertices, n_pins, n_self, n_cut, k=None):
         a = self.alpha if self.alpha_k is None or k is None else self.alpha_k[k - 1]
@@ -215,18 +199,10 @@ class AffinePrimaryConnectivityModel(_Model):
     part number) and remote ones.  Needs Pi (any partition of the rows)."""
     kind = CP_MODEL_PRIMARY
     needs_rowpart = True
+    fields = ("alpha", "beta_vertex", "beta_pin", "beta_local_net", "beta_remote_net")
 
     def __init__(self, alpha=0, beta_vertex=0, beta_pin=0, beta_local_net=0, beta_remote_net=0, *, alpha_k=None):
-        self.alpha, self.beta_vertex, self.beta_pin = alpha, beta_vertex, beta_pin
-        self.beta_local_net, self.beta_remote_net = beta_local_net, beta_remote_net
-        self.alpha_k = alpha_k
-        self.dtype = _promote(alpha, beta_vertex, beta_pin, beta_local_net, beta_remote_net, *([alpha_k] if alpha_k is not None else []))
-
-    def _params(self):
-        return [self.alpha, self.beta_vertex, self.beta_pin, self.beta_local_net, self.beta_remote_net]
-
-    def _alpha_k(self):
-        return self.alpha_k
+        self._set(alpha, beta_vertex, beta_pin, beta_local_net, beta_remote_net, alpha_k=alpha_k)
 
     def __call__(self, n_vertices, n_pins, n_local, n_remote, k=None):
         a = self.alpha if self.alpha_k is None or k is None else self.alpha_k[k - 1]
@@ -246,15 +222,10 @@ class AffineSymmetricConnectivityModel(_Model):
     remote = dianet(j, j') - nv (the nets of the part that reach outside its own rows) and local = net(j, j') - remote."""
     kind = CP_MODEL_SYM_CONNECTIVITY
     symmetric = True
+    fields = ("alpha", "beta_vertex", "beta_pin", "beta_local_net", "beta_remote_net")
 
     def __init__(self, alpha=0, beta_vertex=0, beta_pin=0, beta_local_net=0, beta_remote_net=0):
-        self.alpha, self.beta_vertex, self.beta_pin = alpha, beta_vertex, beta_pin
-        self.beta_local_net, self.beta_remote_net = beta_local_net, beta_remote_net
-        self.alpha_k = None
-        self.dtype = _promote(alpha, beta_vertex, beta_pin, beta_local_net, beta_remote_net)
-
-    def _params(self):
-        return [self.alpha, self.beta_vertex, self.beta_pin, self.beta_local_net, self.beta_remote_net]
+        self._set(alpha, beta_vertex, beta_pin, beta_local_net, beta_remote_net)
 
     def __call__(self, n_vertices, n_pins, n_local, n_remote, k=None):
         return (self.alpha + n_vertices * self.beta_vertex + n_pins * self.beta_pin + n_local * self.beta_local_net
@@ -276,6 +247,7 @@ class AffineMonotonizedSymmetricConnectivityModel(_Model):
     integer-valued (the reference keeps the over-pin prefix in an integer vector)."""
     kind = CP_MODEL_MONO_SYM_CONNECTIVITY
     symmetric = True
+    fields = ("alpha", "beta_vertex", "beta_over_pin", "beta_dia_net", "delta_pins")
 
     def __init__(self, alpha=0, beta_vertex=0, beta_over_pin=0, beta_dia_net=0, delta_pins=0, *, alpha_k=None):
         if isinstance(alpha, AffineSymmetricConnectivityModel):
@@ -290,16 +262,7 @@ class AffineMonotonizedSymmetricConnectivityModel(_Model):
                 delta_pins, beta_vertex = 0, s.beta_vertex - s.beta_remote_net
             if s.dtype == CP_F64:                    # the struct is {Tv}: every field converts to the model's element type
                 alpha, beta_vertex, beta_over_pin, beta_dia_net, delta_pins = (float(v) for v in (alpha, beta_vertex, beta_over_pin, beta_dia_net, delta_pins))
-        self.alpha, self.beta_vertex, self.beta_over_pin = alpha, beta_vertex, beta_over_pin
-        self.beta_dia_net, self.delta_pins = beta_dia_net, delta_pins
-        self.alpha_k = alpha_k
-        self.dtype = _promote(alpha, beta_vertex, beta_over_pin, beta_dia_net, delta_pins, *([alpha_k] if alpha_k is not None else []))
-
-    def _params(self):
-        return [self.alpha, self.beta_vertex, self.beta_over_pin, self.beta_dia_net, self.delta_pins]
-
-    def _alpha_k(self):
-        return self.alpha_k
+        self._set(alpha, beta_vertex, beta_over_pin, beta_dia_net, delta_pins, alpha_k=alpha_k)
 
     def __call__(self, n_vertices, n_over_pins, n_dia_nets, k=None):
         a = self.alpha if self.alpha_k is None or k is None else self.alpha_k[k - 1]
@@ -311,14 +274,10 @@ class AffineSymmetricEdgeCutModel(_Model):
     selfpin = nonzeros of the part's diagonal block."""
     kind = CP_MODEL_SYM_EDGE_CUT
     symmetric = True
+    fields = ("alpha", "beta_vertex", "beta_self_pin", "beta_cut_pin")
 
     def __init__(self, alpha=0, beta_vertex=0, beta_self_pin=0, beta_cut_pin=0):
-        self.alpha, self.beta_vertex, self.beta_self_pin, self.beta_cut_pin = alpha, beta_vertex, beta_self_pin, beta_cut_pin
-        self.alpha_k = None
-        self.dtype = _promote(alpha, beta_vertex, beta_self_pin, beta_cut_pin)
-
-    def _params(self):
-        return [self.alpha, self.beta_vertex, self.beta_self_pin, self.beta_cut_pin]
+        self._set(alpha, beta_vertex, beta_self_pin, beta_cut_pin)
 
     def __call__(self, n_vertices, n_self_pins, n_cut_pins, k=None):
         return self.alpha + n_vertices * self.beta_vertex + n_self_pins * self.beta_self_pin + n_cut_pins * self.beta_cut_pin
@@ -373,11 +332,11 @@ class ColumnBlockComponentCostModel(_Model):
         self.dtype = CP_I64 if dtype in (int, np.int64, "int", CP_I64) else CP_F64
         self.w_table = w_table
 
-    def _marshal_extra(self, s, keep, w_table):
+    def _marshal_extra(self, s, keep, w_table, w_lo, u_table):
         wt = w_table if w_table is not None else self.w_table
         s.R = 1
-        s.alpha_col = _component(self.alpha_col, self.dtype, wt, keep, getattr(self, "_w_lo", 0))
-        s.beta_col[0] = _component(self.beta_col, self.dtype, wt, keep, getattr(self, "_w_lo", 0))
+        s.alpha_col = _component(self.alpha_col, self.dtype, wt, keep, w_lo)
+        s.beta_col[0] = _component(self.beta_col, self.dtype, wt, keep, w_lo)
 
     def __call__(self, n_vertices, n_pins, n_nets, k=None):
         bc = lambda f, w: f(w) if callable(f) else (f[w - 1] if isinstance(f, (list, tuple, np.ndarray)) else f)
@@ -395,16 +354,15 @@ class BlockComponentCostModel(_Model):
         self.dtype = CP_I64 if dtype in (int, np.int64, "int", CP_I64) else CP_F64
         self.w_table, self.u_table = w_table, u_table
 
-    def _marshal_extra(self, s, keep, w_table):
+    def _marshal_extra(self, s, keep, w_table, w_lo, u_table):
         wt = w_table if w_table is not None else self.w_table
-        ut = self.u_table if self.u_table is not None else wt
+        ut = u_table if u_table is not None else self.u_table if self.u_table is not None else wt
         s.R = len(self.beta_row)
         s.alpha_row = _component(self.alpha_row, self.dtype, ut, keep)
-        lo = getattr(self, "_w_lo", 0)
-        s.alpha_col = _component(self.alpha_col, self.dtype, wt, keep, lo)
+        s.alpha_col = _component(self.alpha_col, self.dtype, wt, keep, w_lo)
         for r in range(s.R):
             s.beta_row[r] = _component(self.beta_row[r], self.dtype, ut, keep)
-            s.beta_col[r] = _component(self.beta_col[r], self.dtype, wt, keep, lo)
+            s.beta_col[r] = _component(self.beta_col[r], self.dtype, wt, keep, w_lo)
 
 
 class VertexCount(_Model):
