@@ -116,6 +116,9 @@ SIGNATURES = {
     "cp_get_stat": (_i32, [_str, _pi64]),
     "cp_test_round_scans": (_i32, [_I32("a"), _i64, _i64, _I32("b"), _i64, _i64, _i32, _i64, _i64, _i32, _i32,
                                    _I64("offs_out"), _I64("toffs_out"), _I64("res")]),
+    "cp_test_fix_merge": (_i32, [_MODEL, _i64, _I64("toffs"), _I64("part_v"), _I32("part_p"), _I32("part_nn"), _I32("part_nl"), _I32("tile_s"),
+                                 _I32("tile_s2"), _I32("anchor"), _I32("anchor2"), _I32("row"), _I32("plane"), _i64, _i32, _I32("p_out"),
+                                 _I32("nn_out"), _I32("nl_out"), _I64("res")]),
     "cp_set_option": (_i32, [_str, _i64]),
     "cp_prof_enable": (_i32, [_i32]),
     "cp_prof_reset": (_i32, []),
@@ -263,6 +266,20 @@ class HipBackend:
                                           offs, toffs, res)
         self._ok(rc, "cp_test_round_scans")
         return offs, toffs, dict(zip(("T", "NT", "nlong", "nown", "ntile", "err"), (int(v) for v in res)))
+
+    def test_fix_merge(self, mm, toffs, part_v, part_p, part_nn, part_nl, tile_s, tile_s2, anchor, anchor2, row, plane, n, reps=1):
+        """the own-tile merge of a DP round in one launch (test entry): (p, nn, nl or None, {items, trips, edges, tickets_left}); part_v
+        holds the costs in the model's element type, part_nl / tile_s2 / anchor2 are None unless the model is HyperedgeCut"""
+        i32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.int32)
+        toffs = np.ascontiguousarray(toffs, dtype=np.int64)
+        ntask = len(toffs) - 1
+        part_v = np.ascontiguousarray(part_v, dtype=np.int64 if mm.struct.dtype == M.CP_I64 else np.float64).view(np.int64)
+        p, nn, res = np.zeros(ntask, np.int32), np.zeros(ntask, np.int32), np.zeros(4, np.int64)
+        nl = None if part_nl is None else np.zeros(ntask, np.int32)
+        rc = self.lib.cp_test_fix_merge(mm, ntask, toffs, part_v, i32(part_p), i32(part_nn), i32(part_nl), i32(tile_s), i32(tile_s2), i32(anchor),
+                                        i32(anchor2), i32(row), i32(plane), n, reps, p, nn, nl, res)
+        self._ok(rc, "cp_test_fix_merge")
+        return p, nn, nl, dict(zip(("items", "trips", "edges", "tickets_left"), (int(v) for v in res)))
 
     def set_option(self, name, value):
         return self.lib.cp_set_option(name.encode(), value)

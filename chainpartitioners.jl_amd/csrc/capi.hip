@@ -139,11 +139,12 @@ static int32_t oracle_eval_into(cp_csr_t A, const cp_model_t *model, const cp_ro
 
 // ------------------------------------------------------------------ the counters of cp_get_stat
 // fix_trips: tasks the block merge walked in more than one trip; bits 0 / 1 / 2: a task of 1 / FIX_SERIAL / FIX_SERIAL + 1 tiles was
-// merged.  bn_sym_layers: DP layers the valley search ran for the monotonized symmetric model.  kept: cp_set_option("poison", 1)
-// starts a poison pass by zeroing the other counters and leaves this one.
+// merged; fix_items: the (task, trip) items the merges were handed (every attempt of a layer: a dropped round lists none).
+// bn_sym_layers: DP layers the valley search ran for the monotonized symmetric model.  kept: cp_set_option("poison", 1) starts a
+// poison pass by zeroing the other counters and leaves this one.
 static const struct { const char *name; int64_t *var; bool kept; } g_stats[] = {
     {"spec_redo", &g_spec_redo, false}, {"poison_hits", &g_poison_hits, false}, {"fix_trips", &g_fix_trips, false},
-    {"fix_edges", &g_fix_edges, false}, {"bn_sym_layers", &g_bn_sym_layers, true},
+    {"fix_edges", &g_fix_edges, false}, {"fix_items", &g_fix_items, false}, {"bn_sym_layers", &g_bn_sym_layers, true},
 };
 static void stats_reset(bool all) { for (const auto &c : g_stats) if (all || !c.kept) *c.var = 0; }
 
@@ -288,6 +289,17 @@ int32_t cp_test_round_scans(const int32_t *a, int64_t na, int64_t na_max, const 
     if (!offs_out || !toffs_out || !res || (na > 0 && !a) || (nb > 0 && !b)) return CP_EINVAL;
     return guarded([&]() -> int32_t {
         dp_round_scans_test(a, na, na_max, b, nb, nb_max, two, cap_t, cap_nt, err_in, reps, offs_out, toffs_out, res);
+        return CP_OK;
+    });
+}
+
+int32_t cp_test_fix_merge(const cp_model_t *model, int64_t ntask, const int64_t *toffs, const int64_t *part_v, const int32_t *part_p, const int32_t *part_nn,
+                          const int32_t *part_nl, const int32_t *tile_s, const int32_t *tile_s2, const int32_t *anchor, const int32_t *anchor2,
+                          const int32_t *row, const int32_t *plane, int64_t n, int32_t reps, int32_t *p_out, int32_t *nn_out, int32_t *nl_out, int64_t *res)
+{
+    if (!model || !toffs || !part_v || !part_p || !part_nn || !tile_s || !anchor || !row || !plane || !p_out || !nn_out || !res) return CP_EINVAL;
+    return guarded([&]() -> int32_t {
+        dp_fix_merge_test(model, ntask, toffs, part_v, part_p, part_nn, part_nl, tile_s, tile_s2, anchor, anchor2, row, plane, n, reps, p_out, nn_out, nl_out, res);
         return CP_OK;
     });
 }

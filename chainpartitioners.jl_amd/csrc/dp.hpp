@@ -112,7 +112,11 @@ extern int64_t g_opt_gap_tau, g_opt_gap_min;   // gap passes in the rounds tau <
 extern int64_t g_opt_poison, g_poison_hits;    // poison mode (tests): see run_layer
 void dp_round_scans_test(const int32_t *a, int64_t na, int64_t na_max, const int32_t *b, int64_t nb, int64_t nb_max, int two, int64_t capT, int64_t capNT,
                          int err_in, int reps, int64_t *offs_out, int64_t *toffs_out, int64_t *res);      // dp_total.hip: cp_test_round_scans
+void dp_fix_merge_test(const cp_model_t *model, int64_t ntask, const int64_t *toffs, const int64_t *part_v, const int32_t *part_p, const int32_t *part_nn,
+                       const int32_t *part_nl, const int32_t *tile_s, const int32_t *tile_s2, const int32_t *anchor, const int32_t *anchor2, const int32_t *row,
+                       const int32_t *plane, int64_t n, int reps, int32_t *p_out, int32_t *nn_out, int32_t *nl_out, int64_t *res);      // dp_total.hip: cp_test_fix_merge
 extern int64_t g_fix_trips, g_fix_edges;       // what the own-tile merges met since the last reset (tests): see RoundCounts::n_trips / n_edge
+extern int64_t g_fix_items;                    // ... and the (task, trip) items they merged, attempts that were redone included (RoundCounts::n_items)
 extern int64_t g_opt_leaf;                     // 1: the rounds tau < 6 of an unconstrained layer are one leaf pass (dp_leaf.inc)
 extern int64_t g_opt_block_tables;             // 1: the leaf pass also stores the per-block winners (cp_dp_block_tables)
 extern int64_t g_opt_ra_cache;                 // 1: round A from counts computed once per partition

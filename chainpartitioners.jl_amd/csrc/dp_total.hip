@@ -110,10 +110,10 @@ struct RoundCounts {
     unsigned long long own_steps;     // steps of the latter
     int64_t T, NT;                    // flattened steps / own tiles (scan totals)
     int32_t ntile, err;               // cdiv(T, LT); 1: a buffer sized from the prediction is too small (the layer is redone)
-    int32_t n_wide, _pad;             // own-tiled tasks of more than FIX_SERIAL tiles (k_fix_own_lane -> k_fix_own)
+    int32_t n_items, _pad;            // (task, trip) items of the own-tiled tasks of more than FIX_SERIAL tiles (k_own_map -> k_fix_own)
     int32_t n_glong, n_gslots;        // gap tasks of more than GAPSEG tiles and their segment slots (k_gap_finish -> k_gap_seg)
     int32_t n_gslow, n_sslow;         // work items of k_gap_finish / k_gap_seg that met a tile with more than SMAX specials (redone by the SLOW variants)
-    int32_t n_trips, n_edge;          // what the merge met (cp_get_stat, tests): tasks of more than one trip of k_fix_own; bit 0 / 1 / 2: a task of 1 / FIX_SERIAL / FIX_SERIAL + 1 tiles
+    int32_t n_trips, n_edge;          // what the merge met (cp_get_stat, tests): tasks of more than one trip (folded by k_fix_own); bit 0 / 1 / 2: a task of 1 / FIX_SERIAL / FIX_SERIAL + 1 tiles
 };
 
 __device__ __forceinline__ void decode_task(const RoundDesc &R, int64_t t, int64_t &r, int &b)
@@ -899,7 +899,7 @@ __device__ __forceinline__ void interior_stream(const int32_t *__restrict__ arr,
 // ------------------------------------------------------------------ long tasks with tiles of their own
 // A task with >= OWN_MIN steps gets tiles of its own: every tile lies in one task, so all of them -- head and tail included --
 // take the uniform path: one contiguous run of the link array, suffix counts, tile-local evaluation.  k_own_map: tile ->
-// (task, tile index inside the task); k_lpass_own: one wave per tile; k_fix_own_lane / k_fix_own: one lane or one block per task merges its tiles
+// (task, tile index inside the task); k_lpass_own: one wave per tile; k_fix_own: one lane per short task, one block per trip of a longer one merges the tiles
 // (adding the counts made before each tile).  Tile ids are task-major, the head tile first.  Two geometries (own_ntiles / own_tile_geo):
 //   blk = 1 (default, cp_set_option("own_blk")): one tile per 256-column block floor(p / LT) the task's candidates [a, B] touch
 //           (the head and the tail tile partial: at most one tile more than cdiv(L, LT)).  k_own_map counts the tiles of every
@@ -908,10 +908,17 @@ __device__ __forceinline__ void interior_stream(const int32_t *__restrict__ arr,
 //           same time, and all but the first find them in the caches.
 //   blk = 0: tiles counted from the task's own head, LT steps each (the last one partial), in task order.
 // bcnt (blk = 1): tiles per column block, and each tile's rank inside its block (brank)
-__global__ void __launch_bounds__(256) k_own_map(const RoundCounts *__restrict__ rc, const int64_t *__restrict__ toffs, const int4 *__restrict__ tdesc,
+// items (outside the gap rounds): the work list of the merge, k_fix_own -- one item {task, first tile} per trip of FIX_TRIP tiles of
+// every task of more than FIX_SERIAL tiles, appended by the trip's first tile (a wave-aggregated atomic on rc->n_items; a dropped
+// round walks no tiles and lists nothing); item_of[that tile] = the item's index, by which the merge finds a task's trips in order.
+constexpr int FIX_SERIAL = 16;       // tasks of up to FIX_SERIAL tiles are merged by one lane
+constexpr int FIX_U = 8;             // consecutive tiles per lane and trip of k_fix_own
+constexpr int FIX_TRIP = 256 * FIX_U;
+__global__ void __launch_bounds__(256) k_own_map(RoundCounts *__restrict__ rc, const int64_t *__restrict__ toffs, const int4 *__restrict__ tdesc,
                                                  const int32_t *__restrict__ rlen, int4 *__restrict__ rec, int32_t *__restrict__ tile_task,
                                                  const uint8_t *__restrict__ tb, int32_t *__restrict__ gap_hi, int tau, int64_t n, int blk,
-                                                 int32_t *__restrict__ bcnt, int32_t *__restrict__ brank)
+                                                 int32_t *__restrict__ bcnt, int32_t *__restrict__ brank, int2 *__restrict__ items,
+                                                 int32_t *__restrict__ item_of)
 {
     const int64_t ntask = rc->nown, ntile = rc->NT;
     for (int64_t tile = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; tile < ntile; tile += (int64_t)gridDim.x * blockDim.x) {
@@ -921,6 +928,21 @@ __global__ void __launch_bounds__(256) k_own_map(const RoundCounts *__restrict__
         if (toffs[mid] <= tile) lo = mid; else hi = mid;
     }
     int32_t kt = (int32_t)(tile - toffs[lo]);
+    if (items) {
+        const bool first = kt % FIX_TRIP == 0 && toffs[lo + 1] - toffs[lo] > FIX_SERIAL;
+        const unsigned long long mf = __ballot(first);      // (the lanes still in the loop)
+        if (mf) {
+            const int lane = threadIdx.x & 63, lead = __ffsll((long long)mf) - 1;
+            int32_t base = 0;
+            if (lane == lead) base = atomicAdd(&rc->n_items, (int32_t)__popcll(mf));
+            base = __shfl(base, lead);
+            if (first) {
+                const int32_t it = base + __popcll(mf & ((1ull << lane) - 1ull));
+                items[it] = make_int2((int32_t)lo, kt);
+                item_of[tile] = it;
+            }
+        }
+    }
     int4 td = tdesc[lo];
     int32_t pf, tl;
     own_tile_geo(blk, td.x, rlen[lo], kt, pf, tl);
@@ -1457,15 +1479,24 @@ __global__ void __launch_bounds__(256) k_gap_merge(int tau, int nchunk, const Ro
     }
 }
 
-// Merging the tiles of a task: one LANE per task looks at the tile count -- up to FIX_SERIAL: merged by the lane; more: appended
-// to the list k_fix_own walks (one block per task).  The counts made before a tile are the task's anchor plus the counts of
-// the task's earlier tiles (tileS, written by k_lpass_own): a running sum here, a block-wide scan per trip in k_fix_own -- sums
-// inside ONE task, so no device-wide prefix over the round's tiles is made for them.  (The gap rounds do make one: k_gap_finish
-// and its helpers look tiles up at random.)  (Tried: k_lpass_own writing the winner of a single-tile task itself -- the dependent
-// loads at the end of every wave cost it more than the merge saves.)
-constexpr int FIX_SERIAL = 16;
-constexpr int FIX_U = 8;             // consecutive tiles per lane and trip of k_fix_own (a trip: 256 * FIX_U tiles)
-
+// Merging the tiles of a task, one launch (k_fix_own), the role of a block chosen by its index.  The counts made before a tile
+// are the task's anchor plus the counts of the task's earlier tiles (tileS, written by k_lpass_own) -- sums inside ONE task, so no
+// device-wide prefix over the round's tiles is made for them.  (The gap rounds do make one: k_gap_finish and its helpers look
+// tiles up at random.)
+//   lane blocks: one LANE per task; up to FIX_SERIAL tiles are merged by the lane with a running sum, longer tasks are left to
+//   item blocks: one BLOCK per item {task, first tile} of the list k_own_map made: a trip of FIX_TRIP tiles, merged with the
+//     trip-LOCAL exclusive prefix as base (the trip's first tile: 0).  The costs are affine in the counts, so what the task's
+//     earlier trips counted adds the same amount to every candidate of the trip: neither the order nor the ties inside the trip
+//     depend on it.  A task of one trip is finished by its block (anchor added to the winner).  Otherwise the block leaves a
+//     record {winner, the trip's counts} and draws a ticket of its task; whoever draws the last one folds the task: the records in
+//     trip order, a running base from the anchor on, each trip winner raised by its base through the same fix_merge arithmetic
+//     (sums of integers below 2^53 / wrapping Int64: adding the base in two steps is exact) and compared by the same rule --
+//     smaller value, then larger p, a total order: the winner does not depend on who finishes when.  The folder puts the ticket
+//     back to zero (no clearing pass between rounds: the b_cnt pattern of k_blk_order).  No block waits for another one.
+//     Records cross XCDs: written with agent-scope stores, released at agent scope before the ticket is drawn, read by the
+//     folder behind an agent-scope acquire with agent-scope loads (never from a stale L1 / L2 line).
+// (Tried: k_lpass_own writing the winner of a single-tile task itself -- the dependent loads at the end of every wave cost it
+//  more than the merge saves.)
 template <typename TC, bool HYP>
 __device__ __forceinline__ void fix_merge(Best<TC, HYP> &acc, Best<TC, HYP> c, int64_t base, int64_t base2, const DevModel<TC> &M)
 {
@@ -1478,71 +1509,80 @@ __device__ __forceinline__ void fix_merge(Best<TC, HYP> &acc, Best<TC, HYP> c, i
     if (take) acc = c;
 }
 
+// what a trip leaves for the fold, as 8-byte words: {v, p | nn << 32, the trip's count, nl, the trip's second count}
+constexpr int FIX_REC_W = 5;
+template <typename TC> __device__ __forceinline__ unsigned long long fix_bits(TC v);
+template <> __device__ __forceinline__ unsigned long long fix_bits<int64_t>(int64_t v) { return (unsigned long long)v; }
+template <> __device__ __forceinline__ unsigned long long fix_bits<double>(double v) { return (unsigned long long)__double_as_longlong(v); }
+template <typename TC> __device__ __forceinline__ TC fix_val(unsigned long long w);
+template <> __device__ __forceinline__ int64_t fix_val<int64_t>(unsigned long long w) { return (int64_t)w; }
+template <> __device__ __forceinline__ double fix_val<double>(unsigned long long w) { return __longlong_as_double((long long)w); }
+
 template <typename TC, bool HYP>
-__global__ void __launch_bounds__(256) k_fix_own_lane(RoundCounts *__restrict__ rc, const int64_t *__restrict__ toffs, const Best<TC, HYP> *__restrict__ part,
-                                                      const int4 *__restrict__ tdesc, const uint8_t *__restrict__ tb, const int32_t *__restrict__ tS0l,
-                                                      const int32_t *__restrict__ tileS, const int32_t *__restrict__ tileS2, DevModel<TC> M,
-                                                      int32_t *__restrict__ opt, int32_t *__restrict__ nnopt, int32_t *__restrict__ nlopt, int64_t n1,
-                                                      int32_t *__restrict__ wide_list)
+__device__ __forceinline__ void best_wave_min(Best<TC, HYP> &acc, int lane)      // lane 0 ends with the wave's winner
 {
-    const int64_t ntask = rc->nown;
-    int lane = threadIdx.x & 63;
-    for (int64_t t0 = (int64_t)blockIdx.x * blockDim.x; t0 < ntask; t0 += (int64_t)gridDim.x * blockDim.x) {      // wave-uniform
-        int64_t t = t0 + threadIdx.x;
-        int64_t k0 = 0, k1 = 0;
-        if (t < ntask) { k0 = toffs[t]; k1 = toffs[t + 1]; }
-        int64_t nt = k1 - k0;
-        bool wide = nt > FIX_SERIAL;
-        unsigned long long mw = __ballot(wide);
-        if (mw) {                                                   // wave-aggregated append
-            int32_t base = 0;
-            if (lane == 0) base = atomicAdd(&rc->n_wide, (int32_t)__popcll(mw));
-            base = __shfl(base, 0);
-            if (wide) wide_list[base + __popcll(mw & ((1ull << lane) - 1ull))] = (int32_t)t;
-        }
-        const unsigned long long e1 = __ballot(nt == 1), e2 = __ballot(nt == FIX_SERIAL), e3 = __ballot(nt == FIX_SERIAL + 1);
-        if (lane == 0) {
-            const int32_t em = (e1 ? 1 : 0) | (e2 ? 2 : 0) | (e3 ? 4 : 0);
-            if (em & ~rc->n_edge) atomicOr(&rc->n_edge, em);
-        }
-        if (nt < 1 || wide) continue;
-        int4 td = tdesc[t];
-        int64_t run = td.y, run2 = HYP ? (int64_t)tS0l[t] : 0;     // the counts made before tile k
-        Best<TC, HYP> acc; best_clear(acc);
-        for (int64_t k = k0; k < k1; k++) {                        // (the winner does not depend on the order: larger p wins ties)
-            fix_merge<TC, HYP>(acc, part[k], run, run2, M);
-            run += tileS[k];
-            if (HYP) run2 += tileS2[k];
-        }
-        int64_t rw = (int64_t)tb[t] * n1 + PR((int64_t)td.z);
-        opt[rw] = acc.p; nnopt[rw] = acc.nn;
-        if (HYP) nlopt[rw] = best_nl(acc);
+    for (int o = 32; o > 0; o >>= 1) {
+        int src = (lane + o) & 63;
+        Best<TC, HYP> c; best_clear(c); c.v = shfl64(acc.v, src); c.p = __shfl(acc.p, src); c.nn = __shfl(acc.nn, src);
+        if (HYP) best_set_nl(c, __shfl(best_nl(acc), src));
+        bool take = (acc.p < 0) ? (c.p >= 0) : (c.p >= 0 && (c.v < acc.v || (c.v == acc.v && c.p > acc.p)));
+        if (lane + o < 64 && take) acc = c;
     }
 }
 
-// one block per listed task (rounds with a few tasks of thousands of tiles each: the longest task sets the pace)
+// grid: `iblocks` item blocks (grid stride over rc->n_items), then the lane blocks (grid stride over rc->nown)
 template <typename TC, bool HYP>
 __global__ void __launch_bounds__(256) k_fix_own(RoundCounts *__restrict__ rc, const int64_t *__restrict__ toffs, const Best<TC, HYP> *__restrict__ part,
                                                  const int4 *__restrict__ tdesc, const uint8_t *__restrict__ tb, const int32_t *__restrict__ tS0l,
                                                  const int32_t *__restrict__ tileS, const int32_t *__restrict__ tileS2, DevModel<TC> M,
                                                  int32_t *__restrict__ opt, int32_t *__restrict__ nnopt, int32_t *__restrict__ nlopt, int64_t n1,
-                                                 const int32_t *__restrict__ wide_list)
+                                                 const int2 *__restrict__ items, const int32_t *__restrict__ item_of,
+                                                 unsigned long long *__restrict__ trec, uint32_t *__restrict__ tick, int iblocks)
 {
     __shared__ Best<TC, HYP> s_part[4];
     __shared__ int64_t s_w[4], s_w2[4];
-    __shared__ int64_t s_pre[256 * FIX_U], s_pre2[HYP ? 256 * FIX_U : 1];      // per tile of the trip: the counts since its wave's first tile
+    __shared__ int64_t s_pre[FIX_TRIP], s_pre2[HYP ? FIX_TRIP : 1];      // per tile of the trip: the counts since its wave's first tile
+    // (The lane blocks carry these 16 / 32 KB without using them: static LDS is per kernel.  A dozen lane blocks per round -- the
+    //  allocation limits nothing there.)
     int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int64_t nlist = rc->n_wide;
-    for (int64_t i = blockIdx.x; i < nlist; i += gridDim.x) {        // block-uniform: the barriers below are reached by the whole block
-    int64_t t = wide_list[i];
-    int64_t k0 = toffs[t], k1 = toffs[t + 1];
-    int4 td = tdesc[t];
-    Best<TC, HYP> acc; best_clear(acc);
-    // (In every round the last row of the top rectangle owns a task over its whole block -- tens of thousands of tiles: FIX_U tiles
-    //  per lane and trip are in flight; one at a time, that task alone took 30 us of every round.)
-    int64_t carry = td.y, carry2 = HYP ? (int64_t)tS0l[t] : 0;      // the counts made before the trip's first tile
-    if (threadIdx.x == 0 && k1 - k0 > 256 * FIX_U) atomicAdd(&rc->n_trips, 1);
-    for (int64_t kt = k0; kt < k1; kt += 256 * FIX_U) {
+    if ((int)blockIdx.x >= iblocks) {
+        // ---- lane blocks
+        const int64_t ntask = rc->nown;
+        const int64_t nlb = (int64_t)gridDim.x - iblocks;
+        for (int64_t t0 = ((int64_t)blockIdx.x - iblocks) * blockDim.x; t0 < ntask; t0 += nlb * blockDim.x) {      // wave-uniform
+            int64_t t = t0 + threadIdx.x;
+            int64_t k0 = 0, k1 = 0;
+            if (t < ntask) { k0 = toffs[t]; k1 = toffs[t + 1]; }
+            int64_t nt = k1 - k0;
+            const unsigned long long e1 = __ballot(nt == 1), e2 = __ballot(nt == FIX_SERIAL), e3 = __ballot(nt == FIX_SERIAL + 1);
+            if (lane == 0) {
+                const int32_t em = (e1 ? 1 : 0) | (e2 ? 2 : 0) | (e3 ? 4 : 0);
+                if (em & ~rc->n_edge) atomicOr(&rc->n_edge, em);
+            }
+            if (nt < 1 || nt > FIX_SERIAL) continue;
+            int4 td = tdesc[t];
+            int64_t run = td.y, run2 = HYP ? (int64_t)tS0l[t] : 0;     // the counts made before tile k
+            Best<TC, HYP> acc; best_clear(acc);
+            for (int64_t k = k0; k < k1; k++) {                        // (the winner does not depend on the order: larger p wins ties)
+                fix_merge<TC, HYP>(acc, part[k], run, run2, M);
+                run += tileS[k];
+                if (HYP) run2 += tileS2[k];
+            }
+            int64_t rw = (int64_t)tb[t] * n1 + PR((int64_t)td.z);
+            opt[rw] = acc.p; nnopt[rw] = acc.nn;
+            if (HYP) nlopt[rw] = best_nl(acc);
+        }
+        return;
+    }
+    // ---- item blocks
+    // (In every round the last row of the top rectangle owns a task over its whole block -- tens of thousands of tiles, a dozen
+    //  trips and more: as one block's serial walk that task alone set the length of the launch.)
+    const int64_t nlist = rc->n_items;
+    for (int64_t i = blockIdx.x; i < nlist; i += iblocks) {          // block-uniform: the barriers below are reached by the whole block
+        const int2 it = items[i];
+        const int64_t t = it.x;
+        const int64_t k0 = toffs[t], k1 = toffs[t + 1], kt = k0 + it.y;
+        Best<TC, HYP> acc; best_clear(acc);
         // the 16-byte partials: lane x takes the tiles x, x + 256, ... of the trip (neighbouring lanes, neighbouring records)
         Best<TC, HYP> cc[FIX_U];
 #pragma unroll
@@ -1568,7 +1608,7 @@ __global__ void __launch_bounds__(256) k_fix_own(RoundCounts *__restrict__ rc, c
             if (lane >= o) inc += v;
             if (HYP) { int64_t v2 = shfl_up64(inc2, o); if (lane >= o) inc2 += v2; }
         }
-        __syncthreads();                                 // (the previous trip's prefixes have been read)
+        __syncthreads();                                     // (the previous item's prefixes and partials have been read)
         {
             int64_t run = inc - sum, run2 = inc2 - sum2;
 #pragma unroll
@@ -1579,39 +1619,98 @@ __global__ void __launch_bounds__(256) k_fix_own(RoundCounts *__restrict__ rc, c
         }
         if (lane == 63) { s_w[wv] = inc; if (HYP) s_w2[wv] = inc2; }
         __syncthreads();
-        int64_t wb[5], wb2[5];                           // counts before wave w's tiles; [4]: the trip's total
-        wb[0] = carry; wb2[0] = carry2;
+        int64_t wb[5], wb2[5];                               // counts of the trip before wave w's tiles; [4]: the trip's total
+        wb[0] = 0; wb2[0] = 0;
 #pragma unroll
         for (int w = 0; w < 4; w++) { wb[w + 1] = wb[w] + s_w[w]; wb2[w + 1] = HYP ? wb2[w] + s_w2[w] : 0; }
 #pragma unroll
-        for (int u = 0; u < FIX_U; u++) {                // tile u * 256 + x of the trip was scanned by wave (u * 256 + x) / (64 * FIX_U)
+        for (int u = 0; u < FIX_U; u++) {                    // tile u * 256 + x of the trip was scanned by wave (u * 256 + x) / (64 * FIX_U)
             static_assert((64 * FIX_U) % 256 == 0, "a wave's tiles are whole rows of 256");
             const int e = u * 256 + (int)threadIdx.x, w = (u * 256) / (64 * FIX_U);
             fix_merge<TC, HYP>(acc, cc[u], wb[w] + s_pre[e], HYP ? wb2[w] + s_pre2[e] : 0, M);
         }
-        carry = wb[4]; carry2 = wb2[4];
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        int src = (lane + o) & 63;
-        Best<TC, HYP> c; best_clear(c); c.v = shfl64(acc.v, src); c.p = __shfl(acc.p, src); c.nn = __shfl(acc.nn, src);
-        if (HYP) best_set_nl(c, __shfl(best_nl(acc), src));
-        bool take = (acc.p < 0) ? (c.p >= 0) : (c.p >= 0 && (c.v < acc.v || (c.v == acc.v && c.p > acc.p)));
-        if (lane + o < 64 && take) acc = c;
-    }
-    __syncthreads();                                     // (the previous task's partials have been read)
-    if (lane == 0) s_part[wv] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int w = 1; w < 4; w++) {
-            Best<TC, HYP> c = s_part[w];
-            bool take = (acc.p < 0) ? (c.p >= 0) : (c.p >= 0 && (c.v < acc.v || (c.v == acc.v && c.p > acc.p)));
-            if (take) acc = c;
+        best_wave_min<TC, HYP>(acc, lane);
+        if (lane == 0) s_part[wv] = acc;
+        __syncthreads();
+        if (wv != 0) continue;                               // (wave-uniform; the other waves go on to the next item's loads)
+        const int64_t ntrip = (k1 - k0 + FIX_TRIP - 1) / FIX_TRIP;
+        const int4 td = tdesc[t];
+        const int64_t anchor = td.y, anchor2 = HYP ? (int64_t)tS0l[t] : 0;
+        Best<TC, HYP> out; best_clear(out);
+        bool write = false;
+        if (lane == 0) {
+            for (int w = 1; w < 4; w++) {
+                Best<TC, HYP> c = s_part[w];
+                bool take = (acc.p < 0) ? (c.p >= 0) : (c.p >= 0 && (c.v < acc.v || (c.v == acc.v && c.p > acc.p)));
+                if (take) acc = c;
+            }
         }
-        int b = tb[t];
-        int64_t rw = (int64_t)b * n1 + PR((int64_t)td.z);
-        opt[rw] = acc.p; nnopt[rw] = acc.nn;
-        if (HYP) nlopt[rw] = best_nl(acc);
-    }
+        if (ntrip == 1) {                                    // the whole task: the anchor on top, done
+            if (lane == 0) { fix_merge<TC, HYP>(out, acc, anchor, anchor2, M); write = true; }
+        } else {
+            uint32_t got = 0;
+            if (lane == 0) {
+                unsigned long long *r = trec + (size_t)i * FIX_REC_W;
+                __hip_atomic_store(r + 0, fix_bits<TC>(acc.v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(r + 1, (unsigned long long)(uint32_t)acc.p | ((unsigned long long)(uint32_t)acc.nn << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(r + 2, (unsigned long long)wb[4], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (HYP) {
+                    __hip_atomic_store(r + 3, (unsigned long long)(uint32_t)best_nl(acc), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_store(r + 4, (unsigned long long)wb2[4], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+                // The record is released at agent scope BEFORE the ticket is drawn.  The fence alone is the release the memory model asks
+                // for; the explicit wait behind it is there because a release fence's own wait for the stores has been seen to be
+                // dropped by the compiler when a waited load or a used atomic precedes it, and ACQ_REL on the ticket costs nothing more
+                // (one more write-back of an L2 that is clean by then) and makes the last arriver's acquire part of the atomic itself.
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                got = __hip_atomic_fetch_add(&tick[t], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            got = (uint32_t)__shfl((int)got, 0);
+            if ((int64_t)got != ntrip - 1) continue;         // (wave-uniform) somebody else draws the last ticket
+            // ---- the fold, by this wave: lane j takes the trips j, j + 64, ... in order
+            // Only lane 0 drew the ticket, all 64 lanes read records.  What that relies on: the acquire fence is one instruction of the
+            // WAVE (it drops the stale lines of this CU's L1 and of this XCD's L2 for every lane), it is executed after the ticket's
+            // value has come back, and every record word is read by an agent-scope load, which is served from neither of those caches.
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            int64_t base = anchor, base2 = anchor2;
+            for (int64_t j0 = 0; j0 < ntrip; j0 += 64) {
+                const int64_t j = j0 + lane;
+                Best<TC, HYP> c; best_clear(c);
+                int64_t s1 = 0, s2 = 0;
+                if (j < ntrip) {
+                    const unsigned long long *r = trec + (size_t)item_of[k0 + j * FIX_TRIP] * FIX_REC_W;
+                    const unsigned long long w0 = __hip_atomic_load(r + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    const unsigned long long w1 = __hip_atomic_load(r + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    s1 = (int64_t)__hip_atomic_load(r + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    c.v = fix_val<TC>(w0); c.p = (int32_t)(uint32_t)w1; c.nn = (int32_t)(uint32_t)(w1 >> 32);
+                    if (HYP) {
+                        best_set_nl(c, (int32_t)(uint32_t)__hip_atomic_load(r + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+                        s2 = (int64_t)__hip_atomic_load(r + 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    }
+                }
+                int64_t inc1 = s1, incb = s2;
+                for (int o = 1; o < 64; o <<= 1) {
+                    int64_t v = shfl_up64(inc1, o);
+                    if (lane >= o) inc1 += v;
+                    if (HYP) { int64_t v2 = shfl_up64(incb, o); if (lane >= o) incb += v2; }
+                }
+                fix_merge<TC, HYP>(out, c, base + inc1 - s1, base2 + incb - s2, M);
+                base += shfl64(inc1, 63);
+                if (HYP) base2 += shfl64(incb, 63);
+            }
+            best_wave_min<TC, HYP>(out, lane);
+            if (lane == 0) {
+                __hip_atomic_store(&tick[t], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (every ticket of the task is drawn: zero again for the next round)
+                atomicAdd(&rc->n_trips, 1);
+                write = true;
+            }
+        }
+        if (write) {
+            int64_t rw = (int64_t)tb[t] * n1 + PR((int64_t)td.z);
+            opt[rw] = out.p; nnopt[rw] = out.nn;
+            if (HYP) nlopt[rw] = best_nl(out);
+        }
     }
 }
 
@@ -2502,6 +2601,135 @@ void dp_round_scans_test(const int32_t *a, int64_t na, int64_t na_max, const int
 
 #include "dp_leaf.inc"
 
+// ------------------------------------------------------------------ host side of the own-tile merge (k_fix_own)
+// items a round of `nt` own tiles can list: one per FIX_TRIP tiles and at most one partial trip per task of more than FIX_SERIAL tiles
+static size_t fix_items_cap(size_t nt) { return nt / FIX_TRIP + nt / (FIX_SERIAL + 1) + 2; }
+// the grid, from what the host knows: the round's tiles (predicted or exact) and tasks.  Both roles walk their device-side
+// counts with grid strides, so a count beyond the estimate costs time only.
+struct FixGrid { int iblocks, lblocks; };
+static FixGrid fix_grid(int64_t nt, int64_t ntask)
+{
+    nt = std::max<int64_t>(nt, 0); ntask = std::max<int64_t>(ntask, 0);
+    const int64_t items = nt / FIX_TRIP + std::min<int64_t>(ntask, nt / (FIX_SERIAL + 1)) + 1;
+    FixGrid g;
+    g.iblocks = (int)std::min<int64_t>(items, 2048);
+    g.lblocks = (int)std::min<int64_t>(std::max<int64_t>(cdiv(ntask, (int64_t)256), 1), 4096);
+    return g;
+}
+template <typename TC, bool HYP>
+static void launch_fix_own(hipStream_t s, RoundCounts *rc, const int64_t *toffs, const Best<TC, HYP> *part, const int4 *tdesc, const uint8_t *tb,
+                           const int32_t *tS0l, const int32_t *tileS, const int32_t *tileS2, const DevModel<TC> &M, int32_t *opt, int32_t *nnopt,
+                           int32_t *nlopt, int64_t n, const int2 *items, const int32_t *item_of, unsigned long long *trec, uint32_t *tick,
+                           int64_t nt, int64_t ntask)
+{
+    const FixGrid g = fix_grid(nt, ntask);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fix_own<TC, HYP>), dim3((unsigned)(g.iblocks + g.lblocks)), dim3(256), 0, s, rc, toffs, part, tdesc, tb, tS0l, tileS,
+                       tileS2, M, opt, nnopt, nlopt, n + 1, items, item_of, trec, tick, g.iblocks);
+    CP_HIP(hipGetLastError());
+}
+
+// Test entry (cp_test_fix_merge): k_own_map (tiles counted from the task heads: it lists the items) and the merge launch on host
+// arrays, `reps` times on one workspace (the tickets must come back to zero).  Task t has the tiles toffs[t] .. toffs[t + 1),
+// partial records {part_v (the value's 8 bytes), part_p (< 0: an empty tile), part_nn, part_nl}, tile counts tile_s / tile_s2,
+// anchors anchor / anchor2 and writes its winner to the cell of (plane[t], row[t]) of planes over the rows 0 .. n.
+// res: {items listed, tasks folded from more than one trip, the edge bits, tickets left nonzero} of the last launch.
+template <typename TC, bool HYP>
+static void fix_merge_test_run(const cp_model_t *model, int64_t ntask, const int64_t *toffs, const int64_t *part_v, const int32_t *part_p, const int32_t *part_nn,
+                               const int32_t *part_nl, const int32_t *tile_s, const int32_t *tile_s2, const int32_t *anchor, const int32_t *anchor2,
+                               const int32_t *row, const int32_t *plane, int64_t n, int reps, int32_t *p_out, int32_t *nn_out, int32_t *nl_out, int64_t *res)
+{
+    hipStream_t s = nullptr;
+    const int64_t NT = toffs[ntask], n1 = n + 1;
+    int np = 1;
+    for (int64_t t = 0; t < ntask; t++) np = std::max(np, plane[t] + 1);
+    std::vector<Best<TC, HYP>> hpart((size_t)NT);
+    for (int64_t k = 0; k < NT; k++) {
+        Best<TC, HYP> b;
+        memset(&b, 0, sizeof(b));
+        memcpy(&b.v, part_v + k, sizeof(TC)); b.p = part_p[k]; b.nn = part_nn[k];
+        if constexpr (HYP) b.nl = part_nl[k];
+        hpart[(size_t)k] = b;
+    }
+    std::vector<int4> htd((size_t)ntask);
+    std::vector<uint8_t> htb((size_t)ntask);
+    std::vector<int32_t> hrlen((size_t)ntask);
+    for (int64_t t = 0; t < ntask; t++) {
+        htd[(size_t)t] = make_int4(0, anchor[t], row[t], 0); htb[(size_t)t] = (uint8_t)plane[t];
+        hrlen[(size_t)t] = (int32_t)std::min<int64_t>((toffs[t + 1] - toffs[t]) * LT, INT32_MAX);
+    }
+    HostModel<TC> HM;
+    build_dev_model<TC>(model, HM, s);
+    const size_t c = (size_t)NT, icap = fix_items_cap(c), pl = (size_t)np * (size_t)n1;
+    DBuf<int64_t> dtoffs((size_t)ntask + 1);
+    DBuf<Best<TC, HYP>> dpart(c);
+    DBuf<int4> dtd((size_t)ntask), drec(c);
+    DBuf<uint8_t> dtb((size_t)ntask);
+    DBuf<int32_t> drlen((size_t)ntask), dS0l((size_t)ntask), dS(c), dS2(c), dtask(c), ditem_of(c), dopt(pl), dnn(pl), dnl(pl);
+    DBuf<int2> ditems(icap);
+    DBuf<unsigned long long> dtrec(icap * FIX_REC_W);
+    DBuf<uint32_t> dtick((size_t)ntask);
+    DBuf<RoundCounts> drc(1);
+    auto up = [&](void *d, const void *h, size_t bytes) { CP_HIP(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s)); };
+    up(dtoffs.p, toffs, dtoffs.bytes()); up(dpart.p, hpart.data(), dpart.bytes()); up(dtd.p, htd.data(), dtd.bytes()); up(dtb.p, htb.data(), dtb.bytes());
+    up(drlen.p, hrlen.data(), drlen.bytes()); up(dS.p, tile_s, dS.bytes());
+    if (HYP) { up(dS0l.p, anchor2, dS0l.bytes()); up(dS2.p, tile_s2, dS2.bytes()); }
+    CP_HIP(hipMemsetAsync(dtick.p, 0, dtick.bytes(), s));
+    RoundCounts h;
+    for (int r = 0; r < reps; r++) {
+        memset(&h, 0, sizeof(h));
+        h.nown = (int32_t)ntask; h.NT = NT;
+        up(drc.p, &h, sizeof(h));
+        // (whatever a launch does not write shows: no column, and records / items of the launch before are gone)
+        CP_HIP(hipMemsetAsync(dopt.p, 0xFF, dopt.bytes(), s)); CP_HIP(hipMemsetAsync(dnn.p, 0xFF, dnn.bytes(), s)); CP_HIP(hipMemsetAsync(dnl.p, 0xFF, dnl.bytes(), s));
+        CP_HIP(hipMemsetAsync(ditems.p, 0x7F, ditems.bytes(), s)); CP_HIP(hipMemsetAsync(ditem_of.p, 0x7F, ditem_of.bytes(), s));
+        CP_HIP(hipMemsetAsync(dtrec.p, 0x7F, dtrec.bytes(), s));
+        hipLaunchKernelGGL(k_own_map, dim3((unsigned)std::min<int64_t>(cdiv(NT, (int64_t)256), 8192)), dim3(256), 0, s, drc.p, dtoffs.p, dtd.p, drlen.p, drec.p,
+                           dtask.p, dtb.p, (int32_t *)nullptr, 0, n, 0, (int32_t *)nullptr, (int32_t *)nullptr, ditems.p, ditem_of.p);
+        launch_fix_own<TC, HYP>(s, drc.p, dtoffs.p, dpart.p, dtd.p, dtb.p, HYP ? dS0l.p : nullptr, dS.p, HYP ? dS2.p : nullptr, HM.d, dopt.p, dnn.p, HYP ? dnl.p : nullptr, n,
+                                ditems.p, ditem_of.p, dtrec.p, dtick.p, NT, ntask);
+        CP_HIP(hipMemcpyAsync(&h, drc.p, sizeof(h), hipMemcpyDeviceToHost, s));
+        CP_HIP(hipStreamSynchronize(s));               // (h is reused)
+        g_fix_items += h.n_items;
+    }
+    std::vector<int32_t> hopt(pl), hnn(pl), hnl(HYP ? pl : 0);
+    std::vector<uint32_t> htick((size_t)ntask);
+    CP_HIP(hipMemcpyAsync(hopt.data(), dopt.p, dopt.bytes(), hipMemcpyDeviceToHost, s));
+    CP_HIP(hipMemcpyAsync(hnn.data(), dnn.p, dnn.bytes(), hipMemcpyDeviceToHost, s));
+    if (HYP) CP_HIP(hipMemcpyAsync(hnl.data(), dnl.p, dnl.bytes(), hipMemcpyDeviceToHost, s));
+    CP_HIP(hipMemcpyAsync(htick.data(), dtick.p, dtick.bytes(), hipMemcpyDeviceToHost, s));
+    CP_HIP(hipStreamSynchronize(s));
+    int64_t left = 0;
+    for (int64_t t = 0; t < ntask; t++) {
+        const int64_t r = row[t];
+        const int lv = __builtin_ctzll((unsigned long long)r);                  // prow on the host
+        const size_t cell = (size_t)plane[t] * (size_t)n1 + (size_t)((n - (n >> lv)) + (r >> (lv + 1)));
+        p_out[t] = hopt[cell]; nn_out[t] = hnn[cell];
+        if (HYP) nl_out[t] = hnl[cell];
+        left += htick[(size_t)t] != 0;
+    }
+    res[0] = h.n_items; res[1] = h.n_trips; res[2] = h.n_edge; res[3] = left;
+}
+
+void dp_fix_merge_test(const cp_model_t *model, int64_t ntask, const int64_t *toffs, const int64_t *part_v, const int32_t *part_p, const int32_t *part_nn,
+                       const int32_t *part_nl, const int32_t *tile_s, const int32_t *tile_s2, const int32_t *anchor, const int32_t *anchor2, const int32_t *row,
+                       const int32_t *plane, int64_t n, int reps, int32_t *p_out, int32_t *nn_out, int32_t *nl_out, int64_t *res)
+{
+    const bool hyp = model->kind == CP_MODEL_HYPEREDGE_CUT;
+    CP_REQUIRE(model->kind == CP_MODEL_WORK || model->kind == CP_MODEL_CONNECTIVITY || hyp, CP_EINVAL, "fix merge test: not a model of the O(n log^2 n) scheme");
+    CP_REQUIRE(!hyp || (part_nl && tile_s2 && anchor2 && nl_out), CP_EINVAL, "fix merge test: a hyperedge model needs the second counts");
+    CP_REQUIRE(ntask >= 1 && ntask < ((int64_t)1 << 24) && n >= 1 && n < ((int64_t)1 << 26) && reps >= 1 && reps <= 16, CP_EINVAL, "fix merge test: bad sizes");
+    CP_REQUIRE(toffs[0] == 0, CP_EINVAL, "fix merge test: toffs must start at 0");
+    for (int64_t t = 0; t < ntask; t++) {
+        CP_REQUIRE(toffs[t + 1] > toffs[t] && toffs[t + 1] < ((int64_t)1 << 26), CP_EINVAL, "fix merge test: every task needs a tile, 2^26 tiles at most");
+        CP_REQUIRE(row[t] >= 1 && row[t] <= n && plane[t] >= 0 && plane[t] < 4, CP_EINVAL, "fix merge test: rows are 1 .. n, planes 0 .. 3");
+    }
+    with_cost_type(model->dtype, [&](auto tag) {
+        using TC = decltype(tag);
+        if (hyp) fix_merge_test_run<TC, true>(model, ntask, toffs, part_v, part_p, part_nn, part_nl, tile_s, tile_s2, anchor, anchor2, row, plane, n, reps, p_out, nn_out, nl_out, res);
+        else fix_merge_test_run<TC, false>(model, ntask, toffs, part_v, part_p, part_nn, part_nl, tile_s, tile_s2, anchor, anchor2, row, plane, n, reps, p_out, nn_out, nl_out, res);
+    });
+}
+
 // ------------------------------------------------------------------ host driver for one layer
 template <typename TC>
 struct LayerWork {
@@ -2518,7 +2746,11 @@ struct LayerWork {
     // tasks with tiles of their own (k_lpass_own)
     DBuf<int4> o_tdesc, o_rec;
     DBuf<uint8_t> o_tb;
-    DBuf<int32_t> o_rlen, o_ntl, o_tS0l, o_task, o_tileS, o_tileS2, o_wide, o_hi;
+    DBuf<int32_t> o_rlen, o_ntl, o_tS0l, o_task, o_tileS, o_tileS2, o_hi;
+    // the merge of the own tiles (k_fix_own): its items {task, first tile} and each trip-start tile's item (k_own_map), one record per
+    // item, one ticket per task (zero between rounds: the folder of a task puts it back)
+    DBuf<int2> o_items; DBuf<int32_t> o_item_of; DBuf<unsigned long long> o_trec; DBuf<uint32_t> o_tick;
+    bool t_dirty = true;                                // o_tick may hold tickets (run_layer clears it before its first round)
     DBuf<Best<TC, true>> o_sub;                         // gap passes: segment winners of the tiles with specials, [tile][SMAX + 1]
     DBuf<int32_t> o_spv;                                // ... and the specials between them
     // round A from cached counts
@@ -2568,6 +2800,7 @@ struct LayerWork {
         size_t c = NT > 0 ? NT : 1;
         o_rec.release();
         o_task.alloc(c); o_tileS.alloc(c); o_tilePS.alloc(c + 1); o_part.alloc(c); o_hi.alloc(c); o_spec.alloc(c); o_brank.alloc(c); o_border.alloc(c);
+        o_item_of.alloc(c); o_items.alloc(fix_items_cap(c)); o_trec.alloc(fix_items_cap(c) * FIX_REC_W);
         o_sub.alloc(c * (SMAX + 1)); o_spv.alloc(c * (SMAX + 1));
         if (hyp) { o_tileS2.alloc(c); o_tilePS2.alloc(c + 1); }
         o_rec.alloc(c);
@@ -2932,6 +3165,10 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
         if (Wk.b_dirty) CP_HIP(hipMemsetAsync(Wk.b_cnt.p, 0, Wk.b_cnt.bytes(), s));
         Wk.b_dirty = true;
     }
+    // o_tick is zero between rounds the same way (the block that folds a task puts its ticket back): cleared when allocated and,
+    // as a safeguard only, after a layer that did not come to its end in order
+    if (Wk.t_dirty) CP_HIP(hipMemsetAsync(Wk.o_tick.p, 0, Wk.o_tick.bytes(), s));
+    Wk.t_dirty = true;
     // cp_set_option("poison", 1) (tests): every layer starts from planes full of an out-of-range column; the kernels that turn
     // plane cells into addresses count and clamp what they read of it.  The invariant behind the speculative layers -- "whatever a
     // layer that is NOT redone has read was written by that layer" -- then reads: hits > 0 implies the layer is flagged for a redo.
@@ -3097,10 +3334,12 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
             // ---- long tasks with tiles of their own: map, stream + evaluate, merge
             const int64_t gNT = spec ? (int64_t)Wk.o_rec.n : P.NT, gown = spec ? grow(P.nown) : P.nown;      // (capacity >= the true NT, checked)
             poison_fill(s, {{Wk.o_part.p, Wk.o_part.bytes()}, {Wk.o_tileS.p, Wk.o_tileS.bytes()}, {Wk.o_rec.p, Wk.o_rec.bytes()},
-                            {if_hyp<HYP>(Wk.o_tileS2.p), Wk.o_tileS2.bytes()}});
+                            {if_hyp<HYP>(Wk.o_tileS2.p), Wk.o_tileS2.bytes()}, {Wk.o_items.p, Wk.o_items.bytes()}, {Wk.o_item_of.p, Wk.o_item_of.bytes()},
+                            {Wk.o_trec.p, Wk.o_trec.bytes()}});
             const unsigned mgrid = (unsigned)std::min<int64_t>(cdiv(gNT, 256), 8192);
             hipLaunchKernelGGL(k_own_map, dim3(mgrid), dim3(256), 0, s, rc, Wk.o_toffs.p, Wk.o_tdesc.p, Wk.o_rlen.p, Wk.o_rec.p, Wk.o_task.p,
-                               Wk.o_tb.p, gap ? Wk.o_hi.p : (int32_t *)nullptr, R.tau, n, oblk, oblk ? Wk.b_cnt.p : (int32_t *)nullptr, Wk.o_brank.p);
+                               Wk.o_tb.p, gap ? Wk.o_hi.p : (int32_t *)nullptr, R.tau, n, oblk, oblk ? Wk.b_cnt.p : (int32_t *)nullptr, Wk.o_brank.p,
+                               gap ? (int2 *)nullptr : Wk.o_items.p, Wk.o_item_of.p);
             {
                 ProfScope ps(gap ? PROF_GAPSTREAM : PROF_OWN, s, (double)P.own_steps * step_bytes);      // same bytes per step as dp_lpass
                 if (oblk) {                       // the tile ids by column block (counted in k_own_map): ~10^5 tiles, a counting sort
@@ -3117,7 +3356,7 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
             if (gap) {
                 {
                     // the gap kernels look a tile's prefix up at random: a device-wide scan of the tile counts.  (The other rounds need
-                    // sums inside one task only: k_fix_own_lane / k_fix_own make them from o_tileS.)
+                    // sums inside one task only: k_fix_own makes them from o_tileS.)
                     ProfScope ps(PROF_CARRY, s, 12.0 * (double)P.NT);
                     const int32_t *ntp = reinterpret_cast<const int32_t *>(&rc->NT);       // (NT < 2^31: the low word)
                     exclusive_scan_i32_lb(Wk.o_tileS.p, Wk.o_tilePS.p, ntp, (int64_t)Wk.o_tileS.n, nullptr, Wk.scanws, s);
@@ -3140,13 +3379,10 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
                 launch_gap<TC, HYP>(s, A, Wk, R.tau, nchunk, gnr, rc, n, W, M, alpha, gg, gs_grid, gm, gslow_grid, oblk);
             } else {
                 ProfScope ps(PROF_FIX, s, 24.0 * (double)P.NT);
-                // one lane per task: single tiles are final already, short tasks are merged on the spot, the rest is listed and
-                // merged by one block per task
-                unsigned lgrid = (unsigned)std::min<int64_t>(cdiv(gown, 256), 4096), wgrid = (unsigned)std::min<int64_t>(gown, 8192);
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fix_own_lane<TC, HYP>), dim3(lgrid), dim3(256), 0, s, rc, Wk.o_toffs.p, recs<HYP>(Wk.o_part), Wk.o_tdesc.p, Wk.o_tb.p,
-                                   if_hyp<HYP>(Wk.o_tS0l.p), Wk.o_tileS.p, if_hyp<HYP>(Wk.o_tileS2.p), M, Wk.opt.p, Wk.nnopt.p, if_hyp<HYP>(Wk.nlopt.p), n + 1, Wk.o_wide.p);
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fix_own<TC, HYP>), dim3(wgrid), dim3(256), 0, s, rc, Wk.o_toffs.p, recs<HYP>(Wk.o_part), Wk.o_tdesc.p, Wk.o_tb.p,
-                                   if_hyp<HYP>(Wk.o_tS0l.p), Wk.o_tileS.p, if_hyp<HYP>(Wk.o_tileS2.p), M, Wk.opt.p, Wk.nnopt.p, if_hyp<HYP>(Wk.nlopt.p), n + 1, Wk.o_wide.p);
+                // one launch: a lane per task of up to FIX_SERIAL tiles, a block per listed trip of the longer ones
+                launch_fix_own<TC, HYP>(s, rc, Wk.o_toffs.p, recs<HYP>(Wk.o_part), Wk.o_tdesc.p, Wk.o_tb.p, if_hyp<HYP>(Wk.o_tS0l.p), Wk.o_tileS.p,
+                                        if_hyp<HYP>(Wk.o_tileS2.p), M, Wk.opt.p, Wk.nnopt.p, if_hyp<HYP>(Wk.nlopt.p), n, Wk.o_items.p, Wk.o_item_of.p, Wk.o_trec.p,
+                                        Wk.o_tick.p, spec ? grow(P.NT) : P.NT, gown);
             }
             CP_HIP(hipGetLastError());
         }
@@ -3256,7 +3492,9 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
         CP_REQUIRE(!(ok && pz_hits[0] > 0), CP_EINTERNAL, "a DP layer that is not redone read plane cells nobody wrote (poison mode)");
     }
     if (ok) Wk.b_dirty = false;
+    Wk.t_dirty = false;                                  // (every merge that was enqueued has run to its end, also in a layer that is redone)
     if (ok) for (int rd = 0; rd < NR; rd++) { g_fix_trips += got[(size_t)rd].n_trips; g_fix_edges |= got[(size_t)rd].n_edge; }
+    for (int rd = 0; rd < NR; rd++) g_fix_items += got[(size_t)rd].n_items;      // (attempts that are redone included: a dropped round lists none)
     if (ok) {
         for (auto &pt : patches) {
             const RoundCounts &g = got[(size_t)pt.rd];
@@ -3317,7 +3555,8 @@ void dp_total_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W, T
         int64_t mmin = std::max<int64_t>(2, std::min(g_opt_own_min, g_opt_gap_tau >= 0 ? g_opt_gap_min : g_opt_own_min));
         size_t mo = (size_t)(2 * n / mmin + 64) * (size_t)nbits + 1024;
         if (mo > mt) mo = mt;
-        Wk.o_tdesc.alloc(mo); Wk.o_tb.alloc(mo); Wk.o_rlen.alloc(mo); Wk.o_ntl.alloc(mo); Wk.o_toffs.alloc(mo + 1); Wk.o_wide.alloc(mo);
+        Wk.o_tdesc.alloc(mo); Wk.o_tb.alloc(mo); Wk.o_rlen.alloc(mo); Wk.o_ntl.alloc(mo); Wk.o_toffs.alloc(mo + 1); Wk.o_tick.alloc(mo);
+        Wk.t_dirty = true;
         if (hyp) Wk.o_tS0l.alloc(mo);
         Wk.rc.alloc((size_t)NBMAX + 2);
         Wk.fin.alloc(plane); Wk.last_s0.alloc(64); Wk.fin_stamp = 255;      // (fresh memory: the first layer clears it)

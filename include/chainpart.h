@@ -251,7 +251,9 @@ int32_t cp_reset_stream(cp_csr_t csr);
  * (each such layer must be one of the redone ones; the library checks it and fails with CP_EINTERNAL otherwise).  Both are reset
  * when "poison" is switched on.  "fix_trips" -- own-tiled DP tasks whose block merge took more than one trip; "fix_edges" -- bits
  * 0 / 1 / 2: a task of 1 / 16 / 17 tiles was merged (both sides of the lane / block split); both count the layers that stand, not
- * attempts that were redone.  All four are reset when "poison" is switched on and by cp_set_option("stat_reset", 1); reading
+ * attempts that were redone.  "fix_items" -- the (task, trip) work items those merges were handed: one per 2 048 tiles, or part of
+ * them, of every task of more than 16 tiles, in every attempt of a layer (a round dropped by its verdict lists none) and in
+ * cp_test_fix_merge.  All five are reset when "poison" is switched on and by cp_set_option("stat_reset", 1); reading
  * changes nothing. */
 int32_t cp_get_stat(const char *name, int64_t *out);
 /* Test entry: the launch that ends the counting phase of a DP round, on host arrays.  Exclusive scans of a[0 .. na) and (two != 0)
@@ -261,6 +263,19 @@ int32_t cp_get_stat(const char *name, int64_t *out);
  * as the round's later kernels read them -- after a dropped round {0, 0, 0, 0, 0, 1}. */
 int32_t cp_test_round_scans(const int32_t *a, int64_t na, int64_t na_max, const int32_t *b, int64_t nb, int64_t nb_max, int32_t two,
                             int64_t cap_t, int64_t cap_nt, int32_t err_in, int32_t reps, int64_t *offs_out, int64_t *toffs_out, int64_t *res);
+/* Test entry: the launch that merges the tile partials of a DP round's own-tiled tasks, on host arrays.  Task t of ntask owns the
+ * tiles toffs[t] .. toffs[t + 1) (toffs[0] == 0, at least one tile each); tile k has the partial winner {part_v[k]: the 8 bytes of
+ * its cost in the model's element type, part_p[k]: its column, < 0 for a tile without a candidate, part_nn[k], part_nl[k]: its
+ * counts inside the tile} and made tile_s[k] / tile_s2[k] counts; anchor[t] / anchor2[t] were made before the task's first tile.
+ * The counts before a tile are added to its winner through the model (Work, Connectivity or HyperedgeCut; the second-count arrays
+ * are read for HyperedgeCut only and may be NULL otherwise), the smallest cost wins, among equals the largest column.  The winner
+ * of task t goes through the plane cell of (plane[t] in 0 .. 3, row[t] in 1 .. n; distinct cells) into p_out / nn_out / nl_out[t].
+ * reps launches (1 .. 16) in a row on one workspace.  res: {items listed, tasks folded from more than one trip, the "fix_edges" bits,
+ * tasks whose ticket was left nonzero} of the last launch; every launch adds its items to "fix_items". */
+int32_t cp_test_fix_merge(const cp_model_t *model, int64_t ntask, const int64_t *toffs, const int64_t *part_v, const int32_t *part_p,
+                          const int32_t *part_nn, const int32_t *part_nl, const int32_t *tile_s, const int32_t *tile_s2, const int32_t *anchor,
+                          const int32_t *anchor2, const int32_t *row, const int32_t *plane, int64_t n, int32_t reps, int32_t *p_out,
+                          int32_t *nn_out, int32_t *nl_out, int64_t *res);
 /* Library-wide tunables and test switches; results never depend on them (tests/test_gpu_dynamic.py runs every one against the
  * oracle).  "force_brute" 1: the general O(K n^2) device DP even where the O(K n log^2 n) scheme applies; "brute_max_n": its size
  * limit.  Layer driver of the O(K n log^2 n) scheme: "short_t"/"short_e" (tasks finished during setup),

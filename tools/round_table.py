@@ -21,7 +21,7 @@ for r, n in zip(rows[lo:hi], names[lo:hi]):
     cur[n] = cur.get(n, 0) + d
 rounds.append(cur)
 keys = ['k_rpass_small', 'k_rpass_wave', 'k_setup_short', 'k_scan_reduce', 'k_scan_blocksums', 'k_scan_apply', 'k_own_map', 'k_lpass_own', 'k_lpass_gap',
-        'k_gap_finish', 'k_gap_seg', 'k_gap_merge', 'k_fix_own_lane', 'k_fix_own', 'k_tile_t0', 'k_lpass', 'k_span_short', 'k_open', 'k_fix']
+        'k_gap_finish', 'k_gap_seg', 'k_gap_merge', 'k_fix_own', 'k_tile_t0', 'k_lpass', 'k_span_short', 'k_open', 'k_fix']
 print('rd ' + ' '.join(f'{k[2:10]:>8}' for k in keys) + '    total')
 tot = collections.Counter()
 for i, c in enumerate(rounds):
