@@ -119,6 +119,7 @@ SIGNATURES = {
     "cp_test_fix_merge": (_i32, [_MODEL, _i64, _I64("toffs"), _I64("part_v"), _I32("part_p"), _I32("part_nn"), _I32("part_nl"), _I32("tile_s"),
                                  _I32("tile_s2"), _I32("anchor"), _I32("anchor2"), _I32("row"), _I32("plane"), _i64, _i32, _I32("p_out"),
                                  _I32("nn_out"), _I32("nl_out"), _I64("res")]),
+    "cp_test_own_split": (_i32, [_vp, _I32("vpos_out"), _I32("vsa_out"), _I32("vnext_out"), _I64("res")]),
     "cp_set_option": (_i32, [_str, _i64]),
     "cp_prof_enable": (_i32, [_i32]),
     "cp_prof_reset": (_i32, []),
@@ -280,6 +281,16 @@ class HipBackend:
                                         i32(anchor2), i32(row), i32(plane), n, reps, p, nn, nl, res)
         self._ok(rc, "cp_test_fix_merge")
         return p, nn, nl, dict(zip(("items", "trips", "edges", "tickets_left"), (int(v) for v in res)))
+
+    def test_own_split(self, A):
+        """the link entries split by bit plane (test entry): (nb, vpos[nb, n + 1], vsa[nb, n + 1], vnext[total])"""
+        nb = max(0, int(A.n).bit_length() - 8)
+        vpos = np.zeros((max(nb, 1), A.n + 1), np.int32); vsa = np.zeros_like(vpos)
+        vnext = np.zeros(max(A.nnz, 1), np.int32); res = np.zeros(2, np.int64)
+        rc = self.lib.cp_test_own_split(self._h(A), vpos.reshape(-1), vsa.reshape(-1), vnext, res)
+        self._ok(rc, "cp_test_own_split")
+        assert int(res[0]) == nb
+        return nb, vpos[:nb], vsa[:nb], vnext[:int(res[1])]
 
     def set_option(self, name, value):
         return self.lib.cp_set_option(name.encode(), value)

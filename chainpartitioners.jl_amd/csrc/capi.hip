@@ -140,11 +140,13 @@ static int32_t oracle_eval_into(cp_csr_t A, const cp_model_t *model, const cp_ro
 // ------------------------------------------------------------------ the counters of cp_get_stat
 // fix_trips: tasks the block merge walked in more than one trip; bits 0 / 1 / 2: a task of 1 / FIX_SERIAL / FIX_SERIAL + 1 tiles was
 // merged; fix_items: the (task, trip) items the merges were handed (every attempt of a layer: a dropped round lists none).
+// own_split_tiles: own tiles that streamed only their plane's variable link entries (layers that were not redone).
 // bn_sym_layers: DP layers the valley search ran for the monotonized symmetric model.  kept: cp_set_option("poison", 1) starts a
 // poison pass by zeroing the other counters and leaves this one.
 static const struct { const char *name; int64_t *var; bool kept; } g_stats[] = {
     {"spec_redo", &g_spec_redo, false}, {"poison_hits", &g_poison_hits, false}, {"fix_trips", &g_fix_trips, false},
     {"fix_edges", &g_fix_edges, false}, {"fix_items", &g_fix_items, false}, {"bn_sym_layers", &g_bn_sym_layers, true},
+    {"own_split_tiles", &g_own_split_tiles, false},
 };
 static void stats_reset(bool all) { for (const auto &c : g_stats) if (all || !c.kept) *c.var = 0; }
 
@@ -160,6 +162,7 @@ static const struct Opt { const char *name; int64_t *var; OptRule rule; int64_t 
     {"poison", &g_opt_poison, OPT_PLAIN, 0, 0},                 // (a nonzero value also zeroes the counters of a poison pass)
     {"pool", &g_opt_pool, OPT_BOOL, 0, 0},                      // (1: keep freed device blocks >= 1 MB for reuse; 0: return them, now and from here on)
     {"own_blk", &g_opt_own_blk, OPT_BOOL, 0, 0},                // (1, default: own tiles at 256-column blocks, run in block order; 0: tiles counted from each task head, in task order)
+    {"own_split", &g_opt_own_split, OPT_BOOL, 0, 0},            // (1, default: own tiles of the planes >= 8 stream only the plane's variable link entries; 0: the whole columns)
     {"lws", &g_opt_lws, OPT_BOOL, 0, 0},                        // (1, default: DynamicTotalChunker past the scan by chunk_lws.hip; 0: the one-wave kernel)
     {"gap_tau", &g_opt_gap_tau, OPT_CLAMP, NOLIM_LO, 20}, {"gap_min", &g_opt_gap_min, OPT_CLAMP, 8, NOLIM_HI}, {"gap_nr", &g_opt_gap_nr, OPT_CLAMP, 1, 2},
     {"force_max", &g_opt_force_max, OPT_CLAMP, 0, NOLIM_HI}, {"rpass_cap", &g_opt_rpass_cap, OPT_CLAMP, 1, NOLIM_HI},
@@ -300,6 +303,16 @@ int32_t cp_test_fix_merge(const cp_model_t *model, int64_t ntask, const int64_t 
     if (!model || !toffs || !part_v || !part_p || !part_nn || !tile_s || !anchor || !row || !plane || !p_out || !nn_out || !res) return CP_EINVAL;
     return guarded([&]() -> int32_t {
         dp_fix_merge_test(model, ntask, toffs, part_v, part_p, part_nn, part_nl, tile_s, tile_s2, anchor, anchor2, row, plane, n, reps, p_out, nn_out, nl_out, res);
+        return CP_OK;
+    });
+}
+
+int32_t cp_test_own_split(cp_csr_t A, int32_t *vpos_out, int32_t *vsa_out, int32_t *vnext_out, int64_t *res)
+{
+    if (!A || !vpos_out || !vsa_out || !vnext_out || !res) return CP_EINVAL;
+    return guarded([&]() -> int32_t {
+        CP_HIP(hipSetDevice(A->device));
+        dp_own_split_test(A, vpos_out, vsa_out, vnext_out, res);
         return CP_OK;
     });
 }

@@ -51,6 +51,8 @@ __device__ __forceinline__ TC dm_apply_affine(const DevModel<TC> &m, TC alpha, i
 
 constexpr int LT = 256;          // steps per tile (one wave owns one tile)
 constexpr int NBMAX = 31;        // bit planes (n < 2^30)
+constexpr int SPLIT_BMIN = 8;     // own_split (SplitLinks): first plane whose own tiles stream only the plane's variable link entries (tiles are 256 columns: from here on a tile lies inside one block)
+constexpr int SPLIT_NB = NBMAX - SPLIT_BMIN;      // ... and their number at most
 
 // Plane arrays (opt / nnopt / nlopt / cr / crl) hold row r of a bit plane at slot prow(r): rows are grouped by their level
 // ctz(r) -- the rows one round reads and writes are then CONTIGUOUS in every plane (in row-major order they sit 2^(tau+1)
@@ -113,6 +115,7 @@ struct RoundCounts {
     int32_t n_items, _pad;            // (task, trip) items of the own-tiled tasks of more than FIX_SERIAL tiles (k_own_map -> k_fix_own)
     int32_t n_glong, n_gslots;        // gap tasks of more than GAPSEG tiles and their segment slots (k_gap_finish -> k_gap_seg)
     int32_t n_gslow, n_sslow;         // work items of k_gap_finish / k_gap_seg that met a tile with more than SMAX specials (redone by the SLOW variants)
+    int32_t n_split, _pad2;           // own tiles that stream only their plane's variable link entries, where a launch mixes them with others (k_own_map, split == 2)
     int32_t n_trips, n_edge;          // what the merge met (cp_get_stat, tests): tasks of more than one trip (folded by k_fix_own); bit 0 / 1 / 2: a task of 1 / FIX_SERIAL / FIX_SERIAL + 1 tiles
 };
 
@@ -818,11 +821,19 @@ constexpr int SMAX = 31;
 template <bool GE, bool DET = false>
 __device__ __forceinline__ void interior_stream(const int32_t *__restrict__ arr, const int32_t *__restrict__ cpos, int32_t p_first, int32_t tl,
                                                 int32_t thr, int lane, int32_t acc[4], int32_t sk[4], int head = 0, int32_t sp_lo = 0, int32_t sp_hi = 0,
-                                                int32_t *s_es = nullptr, int32_t *s_v = nullptr, int32_t *s_cnt = nullptr, int kind = 0)
+                                                int32_t *s_es = nullptr, int32_t *s_v = nullptr, int32_t *s_cnt = nullptr, int kind = 0,
+                                                const int32_t *__restrict__ psum = nullptr)
 {
     const int32_t FILL = GE ? INT32_MIN : INT32_MAX;      // never flagged
+    // psum (wave-uniform; own_split): a step starts from psum[end of the run's columns] - psum[its column], what the columns hold apart
+    // from the streamed entries.  (Loaded here, next to the column pointers: the counters are live through the loop anyway.)
+    const int32_t ptop = psum ? psum[p_first + 1 - head] : 0;
 #pragma unroll
-    for (int k = 0; k < 4; k++) { int32_t e = lane + 64 * k; sk[k] = e <= tl ? cpos[p_first - e] : INT32_MAX; acc[k] = 0; }
+    for (int k = 0; k < 4; k++) {
+        int32_t e = lane + 64 * k;
+        sk[k] = e <= tl ? cpos[p_first - e] : INT32_MAX;
+        acc[k] = (psum && e <= tl) ? ptop - psum[p_first - e] : 0;
+    }
     // head != 0: step 0 is the candidate p_first itself (no column stepped over): the run ends in front of that column
     int32_t Q_hi = cpos[p_first + 1 - head], Q_lo = cpos[p_first - tl];       // wave-uniform
     int32_t x = Q_lo & ~3;
@@ -918,7 +929,7 @@ __global__ void __launch_bounds__(256) k_own_map(RoundCounts *__restrict__ rc, c
                                                  const int32_t *__restrict__ rlen, int4 *__restrict__ rec, int32_t *__restrict__ tile_task,
                                                  const uint8_t *__restrict__ tb, int32_t *__restrict__ gap_hi, int tau, int64_t n, int blk,
                                                  int32_t *__restrict__ bcnt, int32_t *__restrict__ brank, int2 *__restrict__ items,
-                                                 int32_t *__restrict__ item_of)
+                                                 int32_t *__restrict__ item_of, int split)
 {
     const int64_t ntask = rc->nown, ntile = rc->NT;
     for (int64_t tile = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; tile < ntile; tile += (int64_t)gridDim.x * blockDim.x) {
@@ -946,9 +957,14 @@ __global__ void __launch_bounds__(256) k_own_map(RoundCounts *__restrict__ rc, c
     int4 td = tdesc[lo];
     int32_t pf, tl;
     own_tile_geo(blk, td.x, rlen[lo], kt, pf, tl);
-    // {column of step 0, row, pos[row], tl | tile of a gap task | head}
+    // {column of step 0, row, pos[row], split plane (bits 10 ..; 0: the tile streams the whole columns) | tl (8 bits) | tile of a gap task | head}
     const bool isgap = gap_hi != nullptr;
-    rec[tile] = make_int4(pf, td.z, td.w, (tl << 2) | (isgap ? 2 : 0) | (kt == 0 ? 1 : 0));
+    const int sb = (split && tb[lo] >= SPLIT_BMIN) ? tb[lo] : 0;
+    rec[tile] = make_int4(pf, td.z, td.w, (sb << 10) | (tl << 2) | (isgap ? 2 : 0) | (kt == 0 ? 1 : 0));
+    if (split == 2) {                                  // (a launch that also holds tiles of the planes below: counted here, one atomic per wave)
+        const unsigned long long ms = __ballot(sb != 0);
+        if (ms && (int)(threadIdx.x & 63) == __ffsll((long long)ms) - 1) atomicAdd(&rc->n_split, (int32_t)__popcll(ms));
+    }
     tile_task[tile] = (int32_t)lo;
     if (bcnt) brank[tile] = atomicAdd(&bcnt[pf / LT], 1);
     if (isgap) {                                       // gap pass: rows (r - 2^tau, hi) of the rectangle are finished together
@@ -984,7 +1000,9 @@ __global__ void __launch_bounds__(256) k_lpass_own(int isA, const RoundCounts *_
                                                    const TC *__restrict__ W, DevModel<TC> M, TC alpha, Best<TC, HYP> *__restrict__ part,
                                                    int tau, const int32_t *__restrict__ gap_hi, uint8_t *__restrict__ spec, int force_spec,
                                                    Best<TC, HYP> *__restrict__ sub, int32_t *__restrict__ spv,
-                                                   const int32_t *__restrict__ a_col, const int32_t *__restrict__ a_ffirst)
+                                                   const int32_t *__restrict__ a_col, const int32_t *__restrict__ a_ffirst,
+                                                   const int32_t *__restrict__ a_vnext, const int32_t *__restrict__ a_vpos,
+                                                   const int32_t *__restrict__ a_vsa, int64_t vstride)
 {
     // GAP (rounds tau <= gap_tau, see k_gap_finish): the tile is evaluated for ALL rows r' of (r - 2^tau, hi) at once: the counts
     // taken here are those of the entries every such row counts (next >= hi - 1; last <= r - 2^tau), the candidates are valued
@@ -1001,14 +1019,15 @@ __global__ void __launch_bounds__(256) k_lpass_own(int isA, const RoundCounts *_
     if (tile >= rc->NT) return;
     if (border) tile = border[tile];
     int4 rec = a_rec[tile];
-    int head = rec.w & 1;
-    int32_t tl = rec.w >> 2;
+    const int32_t rw = __builtin_amdgcn_readfirstlane(rec.w);      // (the record is the wave's: head, tile length and plane as scalars -- two VGPRs fewer)
+    int head = rw & 1;
+    int32_t tl = (rw >> 2) & 255;
     int32_t acc[4], acc2[4] = {0, 0, 0, 0}, sk[4], sk2[4];
     __shared__ int32_t s_es_all[4][2][SMAX + 1], s_v_all[4][2][SMAX + 1];      // the wave's specials: as found / sorted by step
     __shared__ int32_t s_cnt_all[4];
     int32_t(*s_es)[SMAX + 1] = s_es_all[threadIdx.x >> 6], (*s_v)[SMAX + 1] = s_v_all[threadIdx.x >> 6];
     int ns = 0;
-    if (GAP && (rec.w & 2)) {
+    if (GAP && (rw & 2)) {
         int32_t *s_cnt = &s_cnt_all[threadIdx.x >> 6];
         if (lane == 0) *s_cnt = 0;
         __threadfence_block();
@@ -1025,6 +1044,18 @@ __global__ void __launch_bounds__(256) k_lpass_own(int isA, const RoundCounts *_
                 s_es[0][lane] = rec.x - (k1 ? a_ffirst[q] : a_col[q]);
             }
             __threadfence_block();
+        }
+    } else if (!HYP && !GAP) {
+        // own_split (k_own_map put the plane into the record): only the plane's variable entries are streamed; the entries every
+        // row of the rectangle counts are a difference of prefix sums per step (the stream starts its counters from it), and the pin
+        // count wants the column's own position
+        const int sb = rw >> 10;                                         // (scalar: the arrays stay scalar operands)
+        const int64_t so = sb ? (int64_t)(sb - SPLIT_BMIN) * vstride : 0;
+        interior_stream<true>(sb ? a_vnext : a_next, sb ? a_vpos + so : a_pos, rec.x, tl, rec.y, lane, acc, sk, head, 0, 0, nullptr, nullptr, nullptr, 0,
+                              sb ? a_vsa + so : (const int32_t *)nullptr);
+        if (sb) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) if (lane + 64 * k <= tl) sk[k] = a_pos[rec.x - lane - 64 * k];
         }
     } else {
         interior_stream<true>(a_next, a_pos, rec.x, tl, rec.y, lane, acc, sk, head);
@@ -2684,7 +2715,7 @@ static void fix_merge_test_run(const cp_model_t *model, int64_t ntask, const int
         CP_HIP(hipMemsetAsync(ditems.p, 0x7F, ditems.bytes(), s)); CP_HIP(hipMemsetAsync(ditem_of.p, 0x7F, ditem_of.bytes(), s));
         CP_HIP(hipMemsetAsync(dtrec.p, 0x7F, dtrec.bytes(), s));
         hipLaunchKernelGGL(k_own_map, dim3((unsigned)std::min<int64_t>(cdiv(NT, (int64_t)256), 8192)), dim3(256), 0, s, drc.p, dtoffs.p, dtd.p, drlen.p, drec.p,
-                           dtask.p, dtb.p, (int32_t *)nullptr, 0, n, 0, (int32_t *)nullptr, (int32_t *)nullptr, ditems.p, ditem_of.p);
+                           dtask.p, dtb.p, (int32_t *)nullptr, 0, n, 0, (int32_t *)nullptr, (int32_t *)nullptr, ditems.p, ditem_of.p, 0);
         launch_fix_own<TC, HYP>(s, drc.p, dtoffs.p, dpart.p, dtd.p, dtb.p, HYP ? dS0l.p : nullptr, dS.p, HYP ? dS2.p : nullptr, HM.d, dopt.p, dnn.p, HYP ? dnl.p : nullptr, n,
                                 ditems.p, ditem_of.p, dtrec.p, dtick.p, NT, ntask);
         CP_HIP(hipMemcpyAsync(&h, drc.p, sizeof(h), hipMemcpyDeviceToHost, s));
@@ -2730,6 +2761,116 @@ void dp_fix_merge_test(const cp_model_t *model, int64_t ntask, const int64_t *to
     });
 }
 
+// ------------------------------------------------------------------ the link entries split by plane (own_split)
+// A left step of a task (row r, plane b) over column p counts the entries of p with next >= r.  The task's columns lie in the
+// Fenwick block [r_b - 2^b, r_b), r in [r_b, r_b + 2^b).  With h = the highest bit in which p and x = next[q] differ (-1: none):
+//   h < b: x lies in p's own block, below r_b: no row of the rectangle counts the entry;
+//   h > b: x >= r_b + 2^b: every row counts it -- a constant of (column, plane);
+//   h == b: x lies in the sibling block: the only entries whose contribution depends on r ("variable in plane b").
+// Every entry is variable in exactly one plane.  For the planes b = SPLIT_BMIN .. nbits - 1 (nb of them, index b - SPLIT_BMIN):
+//   vnext: the variable entries' next values, plane-major, column-major inside a plane, entry order inside a column (+ 8 of slack);
+//   vpos[b][p], p = 0 .. n: where column p's plane-b entries start in vnext (vpos[b][n] = vpos[b + 1][0]; one word more: the total);
+//   vsa[b][p]: #{entries of the columns < p with h > b}.
+// They depend on the pattern only: built once per partition, by the first layer that uses them (split_build).
+struct SplitLinks {
+    bool built = false;
+    int nb = 0;
+    int64_t stride = 0;                        // n + 1
+    int64_t tot[SPLIT_NB + 1] = {0};           // variable entries per plane; [nb]: all of them
+    DBuf<int32_t> vnext, vpos, vsa;
+};
+
+__device__ __forceinline__ int split_plane(int32_t p, int32_t x) { return 31 - __clz((int)(p ^ x)); }       // (-1 for x == p)
+
+// one lane per column: cnt[b][p] = the column's entries with h == SPLIT_BMIN + b (column n: none)
+__global__ void __launch_bounds__(256) k_split_count(const int32_t *__restrict__ pos, const int32_t *__restrict__ next, int64_t n, int nb,
+                                                     int32_t *__restrict__ cnt)
+{
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p > n) return;
+    int32_t c[SPLIT_NB];
+#pragma unroll
+    for (int b = 0; b < SPLIT_NB; b++) c[b] = 0;
+    if (p < n)
+        for (int32_t q = pos[p], qe = pos[p + 1]; q < qe; q++) {
+            const int h = split_plane((int32_t)p, next[q]) - SPLIT_BMIN;
+#pragma unroll
+            for (int b = 0; b < SPLIT_NB; b++) c[b] += (h == b);
+        }
+#pragma unroll
+    for (int b = 0; b < SPLIT_NB; b++) if (b < nb) cnt[(int64_t)b * (n + 1) + p] = c[b];
+}
+
+// one lane per column: the column's variable entries to their planes, in entry order; vsa from the scanned offsets:
+// vsa[b][p] = sum over b' > b of (vpos[b'][p] - vpos[b'][0])
+__global__ void __launch_bounds__(256) k_split_scatter(const int32_t *__restrict__ pos, const int32_t *__restrict__ next, int64_t n, int nb,
+                                                       const int32_t *__restrict__ vpos, int32_t *__restrict__ vnext, int32_t *__restrict__ vsa)
+{
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p > n) return;
+    int32_t c[SPLIT_NB];
+#pragma unroll
+    for (int b = 0; b < SPLIT_NB; b++) c[b] = b < nb ? vpos[(int64_t)b * (n + 1) + p] : 0;
+    int32_t above = 0;
+#pragma unroll
+    for (int b = SPLIT_NB - 1; b >= 0; b--)
+        if (b < nb) { vsa[(int64_t)b * (n + 1) + p] = above; above += c[b] - vpos[(int64_t)b * (n + 1)]; }
+    if (p < n)
+        for (int32_t q = pos[p], qe = pos[p + 1]; q < qe; q++) {
+            const int32_t x = next[q];
+            const int h = split_plane((int32_t)p, x) - SPLIT_BMIN;
+            int32_t dst = -1;
+#pragma unroll
+            for (int b = 0; b < SPLIT_NB; b++) if (h == b) { dst = c[b]; c[b]++; }
+            if (dst >= 0) vnext[dst] = x;
+        }
+}
+
+static void split_build(cp_csr_s *A, SplitLinks &S, DBuf<int64_t> &scratch)
+{
+    hipStream_t s = A->stream;
+    const int64_t n = A->n, n1 = n + 1;
+    int nbits = 1;
+    while (((int64_t)1 << nbits) <= n) nbits++;
+    S.nb = std::max(0, nbits - SPLIT_BMIN); S.stride = n1;
+    for (auto &t : S.tot) t = 0;
+    if (S.nb > 0) {
+        CP_REQUIRE(S.nb <= SPLIT_NB, CP_EINVAL, "n exceeds the bit-plane budget");
+        const size_t cells = (size_t)S.nb * (size_t)n1;
+        S.vpos.ensure(cells + 1); S.vsa.ensure(cells + 1); S.vnext.ensure((size_t)A->N + 8);
+        const unsigned grid = (unsigned)cdiv(n1, 256);
+        // (the counts live in vsa until the scatter writes it)
+        hipLaunchKernelGGL(k_split_count, dim3(grid), dim3(256), 0, s, A->pos32.p, A->next.p, n, S.nb, S.vsa.p);
+        exclusive_scan_i32_i32(S.vsa.p, S.vpos.p, (int64_t)cells, scratch, s);
+        hipLaunchKernelGGL(k_split_scatter, dim3(grid), dim3(256), 0, s, A->pos32.p, A->next.p, n, S.nb, S.vpos.p, S.vnext.p, S.vsa.p);
+        CP_HIP(hipGetLastError());
+        int32_t st[SPLIT_NB + 1];                       // the planes' starts and the total: the entries a round's planes stream
+        for (int b = 0; b <= S.nb; b++)
+            CP_HIP(hipMemcpyAsync(&st[b], S.vpos.p + (size_t)b * (size_t)n1, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        CP_HIP(hipStreamSynchronize(s));
+        for (int b = 0; b < S.nb; b++) S.tot[b] = (int64_t)st[b + 1] - st[b];
+        S.tot[S.nb] = st[S.nb];
+    }
+    S.built = true;
+}
+
+// Test entry (cp_test_own_split): the three arrays of the pattern on the host.  vpos_out / vsa_out: nb (n + 1) words, vnext_out: room
+// for the N entries; res: {nb, entries in vnext}.
+void dp_own_split_test(cp_csr_s *A, int32_t *vpos_out, int32_t *vsa_out, int32_t *vnext_out, int64_t *res)
+{
+    ensure_links(A);
+    SplitLinks S;
+    DBuf<int64_t> scratch;
+    split_build(A, S, scratch);
+    res[0] = S.nb; res[1] = S.tot[S.nb];
+    if (S.nb <= 0) return;
+    const size_t cells = (size_t)S.nb * (size_t)S.stride;
+    CP_HIP(hipMemcpyAsync(vpos_out, S.vpos.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, A->stream));
+    CP_HIP(hipMemcpyAsync(vsa_out, S.vsa.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, A->stream));
+    if (res[1] > 0) CP_HIP(hipMemcpyAsync(vnext_out, S.vnext.p, (size_t)res[1] * sizeof(int32_t), hipMemcpyDeviceToHost, A->stream));
+    CP_HIP(hipStreamSynchronize(A->stream));
+}
+
 // ------------------------------------------------------------------ host driver for one layer
 template <typename TC>
 struct LayerWork {
@@ -2755,6 +2896,7 @@ struct LayerWork {
     DBuf<int32_t> o_spv;                                // ... and the specials between them
     // round A from cached counts
     bool ra_built = false; RATab ra_tab; int64_t ra_ntile = 0, ra_nrow = 0;
+    SplitLinks split;                                   // the link entries by plane (own_split): built by the first layer that uses them
     bool mir_built = false; RATab mir_tab; int64_t mir_ntile = 0, mir_nrow = 0, mir_w = 0;      // the mirrored heads of a window width (ra_build_mir)
     DBuf<int32_t> mir_c, mir_c2;
     DBuf<Best<TC, true>> mir_part;
@@ -2794,7 +2936,7 @@ struct LayerWork {
     // (o_rec / loc are the size witnesses of their groups: they are released first and allocated LAST, so a hipMalloc failure in
     //  the middle leaves the witness empty and the next call allocates the whole group again)
     // what the pattern's cached tables and the last layer's counts say no longer holds (another pattern, another shape)
-    void forget() { ra_built = false; pred_ok = false; win_built = false; mir_built = false; force_own.clear(); force_rows = 0; }
+    void forget() { ra_built = false; split.built = false; pred_ok = false; win_built = false; mir_built = false; force_own.clear(); force_rows = 0; }
     void ensure_own(size_t NT) {                        // per-tile arrays of the own-tiled tasks
         if (o_rec.n >= NT && o_rec.n > 0) return;
         size_t c = NT > 0 ? NT : 1;
@@ -3145,6 +3287,19 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
     // the kernels do not read -- which put the achieved rate above the box's copy rate.)
     const double step_bytes = 4.0 * (avg_deg + self_deg) + 12.0 + 32.0 / (double)LT;
     const bool own_tiles = !(g_opt_dbg & DBG_NO_OWN_TILES);      // (keep every long task in the flattened space)
+    // cp_set_option("own_split", 0 | 1): outside round A and the gap rounds the own tiles of the planes >= SPLIT_BMIN stream only their
+    // plane's variable link entries (SplitLinks).  Not for hyperedge costs (the second list is not split) nor for windowed layers
+    // (their blocks are not the Fenwick blocks).
+    const bool split_layer = !HYP && !G.win && g_opt_own_split && nbits > SPLIT_BMIN;
+    // bytes the own-tile stream moves: split tiles read two column pointers and a prefix sum per step (20 B with the cost) and the
+    // variable entries of the round's planes, at most what the columns hold.  (Tiles of planes below SPLIT_BMIN in the same launch --
+    // gap_tau < 7 only -- are priced like the others.)
+    auto own_bytes = [&](int tau, bool sp, double steps) {
+        if (!sp) return steps * step_bytes;
+        double var = 0;
+        for (int b = std::max(tau + 1, SPLIT_BMIN); b < nbits && b - SPLIT_BMIN < Wk.split.nb; b++) var += (double)Wk.split.tot[b - SPLIT_BMIN];
+        return steps * (20.0 + 32.0 / (double)LT) + 4.0 * std::min(var, avg_deg * steps);
+    };
     const int NR = nbits + 1;
     CP_HIP(hipMemsetAsync(Wk.rc.p, 0, sizeof(RoundCounts) * (size_t)NR, s));
     const bool gaps = own_tiles && g_opt_gap_tau >= 0;
@@ -3191,11 +3346,14 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
     if (++Wk.fin_stamp > 255 || Wk.fin_stamp <= 0) { CP_HIP(hipMemsetAsync(Wk.fin.p, 0, Wk.fin.bytes(), s)); Wk.fin_stamp = 1; }
     std::vector<RoundCounts> used((size_t)NR);          // what the host sized each round with
     memset(used.data(), 0, sizeof(RoundCounts) * (size_t)NR);
-    struct Patch { size_t idx; int rd; int kind; };
+    struct Patch { size_t idx; int rd; int kind; int tau; bool split; };
     std::vector<Patch> patches;                          // profile records whose algorithmic bytes depend on the true counts
-    auto note = [&](int rd, int kind, int slot) { if (prof_active(slot)) patches.push_back({g_prof_pending.size() - 1, rd, kind}); };
+    auto note = [&](int rd, int kind, int slot, int tau = 0, bool sp = false) {
+        if (prof_active(slot)) patches.push_back({g_prof_pending.size() - 1, rd, kind, tau, sp});
+    };
     auto grow = [](int64_t v) { return v + (v >> 2) + 1024; };     // head room over the prediction
     bool any_forced = false;
+    std::vector<int8_t> split_mode((size_t)NR, 0);       // own_split per round (see the launch of k_own_map)
 
     for (int rd = 0; rd <= nbits; rd++) {
         RoundDesc R;
@@ -3337,11 +3495,19 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
                             {if_hyp<HYP>(Wk.o_tileS2.p), Wk.o_tileS2.bytes()}, {Wk.o_items.p, Wk.o_items.bytes()}, {Wk.o_item_of.p, Wk.o_item_of.bytes()},
                             {Wk.o_trec.p, Wk.o_trec.bytes()}});
             const unsigned mgrid = (unsigned)std::min<int64_t>(cdiv(gNT, 256), 8192);
+            // (1: every tile of the launch is of a plane >= SPLIT_BMIN, their number is NT; 2: the launch also holds tiles of the planes
+            //  below -- gap_tau < 6 only -- and k_own_map counts: 1 600 same-address atomics per launch cost it 17 us at config 3)
+            const int split = !(split_layer && !gap && !R.isA) ? 0 : R.tau + 1 >= SPLIT_BMIN ? 1 : 2;
+            split_mode[(size_t)rd] = (int8_t)split;
+            if (split && !Wk.split.built) {             // once per pattern, by the first round that streams them
+                ProfScope ps(PROF_LINKS, s, 8.0 * (double)A->N + 16.0 * (double)(nbits - SPLIT_BMIN) * (double)(n + 1));
+                split_build(A, Wk.split, Wk.scratch);
+            }
             hipLaunchKernelGGL(k_own_map, dim3(mgrid), dim3(256), 0, s, rc, Wk.o_toffs.p, Wk.o_tdesc.p, Wk.o_rlen.p, Wk.o_rec.p, Wk.o_task.p,
                                Wk.o_tb.p, gap ? Wk.o_hi.p : (int32_t *)nullptr, R.tau, n, oblk, oblk ? Wk.b_cnt.p : (int32_t *)nullptr, Wk.o_brank.p,
-                               gap ? (int2 *)nullptr : Wk.o_items.p, Wk.o_item_of.p);
+                               gap ? (int2 *)nullptr : Wk.o_items.p, Wk.o_item_of.p, split);
             {
-                ProfScope ps(gap ? PROF_GAPSTREAM : PROF_OWN, s, (double)P.own_steps * step_bytes);      // same bytes per step as dp_lpass
+                ProfScope ps(gap ? PROF_GAPSTREAM : PROF_OWN, s, own_bytes(R.tau, split != 0, (double)P.own_steps));
                 if (oblk) {                       // the tile ids by column block (counted in k_own_map): ~10^5 tiles, a counting sort
                     exclusive_scan_i32_lb(Wk.b_cnt.p, Wk.b_start.p, Wk.b_n.p, Wk.b_nblk, nullptr, Wk.scanws, s);
                     hipLaunchKernelGGL(k_blk_order, dim3(mgrid), dim3(256), 0, s, rc, Wk.o_rec.p, Wk.o_brank.p, Wk.b_start.p, Wk.o_border.p, Wk.b_cnt.p);
@@ -3350,9 +3516,10 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
                                    R.isA, rc,
                                    oblk ? Wk.o_border.p : (const int32_t *)nullptr, A->pos32.p, A->next.p, if_hyp<HYP>(A->fpos32.p), if_hyp<HYP>(A->flast.p),
                                    Wk.o_tileS.p, Wk.o_tileS2.p, Wk.o_rec.p, W, M, alpha, recs<HYP>(Wk.o_part), R.tau, Wk.o_hi.p, Wk.o_spec.p,
-                                   (int)((g_opt_dbg & DBG_GAP_ALL_SPECIAL) != 0), recs<HYP>(Wk.o_sub), Wk.o_spv.p, A->col.p, if_hyp<HYP>(A->ffirst.p));
+                                   (int)((g_opt_dbg & DBG_GAP_ALL_SPECIAL) != 0), recs<HYP>(Wk.o_sub), Wk.o_spv.p, A->col.p, if_hyp<HYP>(A->ffirst.p),
+                                   split ? Wk.split.vnext.p : (const int32_t *)nullptr, Wk.split.vpos.p, Wk.split.vsa.p, (int64_t)(n + 1));
             }
-            note(rd, 0, gap ? PROF_GAPSTREAM : PROF_OWN);
+            note(rd, 0, gap ? PROF_GAPSTREAM : PROF_OWN, R.tau, split != 0);
             if (gap) {
                 {
                     // the gap kernels look a tile's prefix up at random: a device-wide scan of the tile counts.  (The other rounds need
@@ -3494,12 +3661,16 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
     if (ok) Wk.b_dirty = false;
     Wk.t_dirty = false;                                  // (every merge that was enqueued has run to its end, also in a layer that is redone)
     if (ok) for (int rd = 0; rd < NR; rd++) { g_fix_trips += got[(size_t)rd].n_trips; g_fix_edges |= got[(size_t)rd].n_edge; }
+    if (ok) for (int rd = 0; rd < NR; rd++) {
+        const RoundCounts &g = got[(size_t)rd];
+        if (g.nown > 0 && g.NT > 0) g_own_split_tiles += split_mode[(size_t)rd] == 1 ? g.NT : split_mode[(size_t)rd] == 2 ? g.n_split : 0;
+    }
     for (int rd = 0; rd < NR; rd++) g_fix_items += got[(size_t)rd].n_items;      // (attempts that are redone included: a dropped round lists none)
     if (ok) {
         for (auto &pt : patches) {
             const RoundCounts &g = got[(size_t)pt.rd];
             if (pt.idx < g_prof_pending.size())
-                g_prof_pending[pt.idx].bytes = (pt.kind == 0 ? (double)g.own_steps : (double)g.T) * step_bytes;
+                g_prof_pending[pt.idx].bytes = pt.kind == 0 ? own_bytes(pt.tau, pt.split, (double)g.own_steps) : (double)g.T * step_bytes;
         }
         Wk.pred = got; Wk.pred_ok = true; Wk.pred_rlo = rlo; Wk.pred_rhi = rhi; Wk.pred_win = G.win; Wk.pred_w = G.w;
         if (allow_force && 2 * (rhi - rlo + 1) >= Wk.force_rows) {

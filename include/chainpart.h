@@ -253,7 +253,8 @@ int32_t cp_reset_stream(cp_csr_t csr);
  * 0 / 1 / 2: a task of 1 / 16 / 17 tiles was merged (both sides of the lane / block split); both count the layers that stand, not
  * attempts that were redone.  "fix_items" -- the (task, trip) work items those merges were handed: one per 2 048 tiles, or part of
  * them, of every task of more than 16 tiles, in every attempt of a layer (a round dropped by its verdict lists none) and in
- * cp_test_fix_merge.  All five are reset when "poison" is switched on and by cp_set_option("stat_reset", 1); reading
+ * cp_test_fix_merge.  "own_split_tiles" -- own tiles that streamed only their plane's variable link entries ("own_split"), in
+ * the layers that stand.  All six are reset when "poison" is switched on and by cp_set_option("stat_reset", 1); reading
  * changes nothing. */
 int32_t cp_get_stat(const char *name, int64_t *out);
 /* Test entry: the launch that ends the counting phase of a DP round, on host arrays.  Exclusive scans of a[0 .. na) and (two != 0)
@@ -276,11 +277,20 @@ int32_t cp_test_fix_merge(const cp_model_t *model, int64_t ntask, const int64_t 
                           const int32_t *part_nn, const int32_t *part_nl, const int32_t *tile_s, const int32_t *tile_s2, const int32_t *anchor,
                           const int32_t *anchor2, const int32_t *row, const int32_t *plane, int64_t n, int32_t reps, int32_t *p_out,
                           int32_t *nn_out, int32_t *nl_out, int64_t *res);
+/* Test entry: the link entries of the pattern split by bit plane, as the own tiles of the total-cost DP stream them ("own_split").
+ * With nbits = the bits of n, nb = max(0, nbits - 8) planes b = 8 .. nbits - 1 (index b - 8) and, for an entry of column p (0-based)
+ * whose row next occurs in column x (n: nowhere), h = the highest bit in which p and x differ: vnext_out -- the x of the entries with
+ * h == b, plane by plane, column by column, in entry order (room for nnz values); vpos_out[(b - 8) (n + 1) + p], p = 0 .. n -- where
+ * column p's entries of plane b start in it; vsa_out[(b - 8) (n + 1) + p] -- the entries of the columns < p with h > b.
+ * res: {nb, entries in vnext_out}. */
+int32_t cp_test_own_split(cp_csr_t csr, int32_t *vpos_out, int32_t *vsa_out, int32_t *vnext_out, int64_t *res);
 /* Library-wide tunables and test switches; results never depend on them (tests/test_gpu_dynamic.py runs every one against the
  * oracle).  "force_brute" 1: the general O(K n^2) device DP even where the O(K n log^2 n) scheme applies; "brute_max_n": its size
  * limit.  Layer driver of the O(K n log^2 n) scheme: "short_t"/"short_e" (tasks finished during setup),
  * "own_min" (shortest task with tiles of its own), "own_blk" (1, default: those tiles sit at absolute 256-column blocks and are
- * streamed in block order; 0: tiles counted from each task's head, in task order), "gap_tau"/"gap_min" (gap passes: rounds and task lengths; -1: none), "gap_nr" (64-row chunks per wave of the gap finish: 1 or 2), "pool" (1, default: freed device blocks of 1 MB and more are kept for reuse by the next call; 0: returned to HIP at once, and the pool is emptied),
+ * streamed in block order; 0: tiles counted from each task's head, in task order), "own_split" (1, default: outside the first round
+ * and the gap rounds the own tiles of the planes >= 8 stream only the link entries whose count depends on the row, see
+ * cp_test_own_split; 0: whole columns), "gap_tau"/"gap_min" (gap passes: rounds and task lengths; -1: none), "gap_nr" (64-row chunks per wave of the gap finish: 1 or 2), "pool" (1, default: freed device blocks of 1 MB and more are kept for reuse by the next call; 0: returned to HIP at once, and the pool is emptied),
  * "ra_cache" (round A from counts cached per partition), "nospec" 1 (one host sync per round instead of sizing a layer from the
  * previous one), "rpass_ch"/"rpass_small_tau"/"rpass_cap" (right-part passes: columns per wave, last
  * lane-per-row round, lane-private share of a row in per cent of the mean), "setup_bs" (lanes per block of the task setup), "force_max" (a round whose flattened
