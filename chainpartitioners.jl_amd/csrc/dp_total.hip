@@ -804,8 +804,8 @@ __device__ __forceinline__ int32_t coop_count(const int32_t *__restrict__ arr, i
 // Interior tiles of a long task: the tile's steps e = 0 .. tl are adjacent descending columns p_first - e of ONE task, so
 // the step order is the (reversed) entry order of one contiguous run [Q_lo, Q_hi) and the inclusive step prefix is a
 // suffix count:  x(e) = #{q in [s(e), Q_hi) : flagged(q)},  s(e) = first entry of the step's column.  No per-column
-// counts, no wave scan, no carry.  The run is streamed once in 256-entry blocks (the next 512 entries are in flight while
-// a block is counted); per block: four ballots, a per-lane popcount prefix, and one gather per step whose column starts
+// counts, no wave scan, no carry.  The run is streamed once in 256-entry blocks (two blocks per trip; the next trip's two loads
+// are issued at the top of a trip and waited for at the top of the next one); per block: four ballots, a per-lane popcount prefix, and one gather per step whose column starts
 // inside the block.  Lane l owns the steps l, l+64, l+128, l+192.
 // DET (gap passes, see k_gap_finish): the entries of the run with a value strictly between sp_lo and sp_hi ("specials") are
 // appended to the wave's list by the lanes that hold them (LDS counter s_cnt): s_es[i] = the entry's position (the caller turns it
@@ -824,26 +824,45 @@ __device__ __forceinline__ void interior_stream(const int32_t *__restrict__ arr,
                                                 int32_t *s_es = nullptr, int32_t *s_v = nullptr, int32_t *s_cnt = nullptr, int kind = 0,
                                                 const int32_t *__restrict__ psum = nullptr)
 {
-    const int32_t FILL = GE ? INT32_MIN : INT32_MAX;      // never flagged
-    // psum (wave-uniform; own_split): a step starts from psum[end of the run's columns] - psum[its column], what the columns hold apart
-    // from the streamed entries.  (Loaded here, next to the column pointers: the counters are live through the loop anyway.)
-    const int32_t ptop = psum ? psum[p_first + 1 - head] : 0;
+    // No load of this function sits under a lane mask or a data-dependent branch: behind the join of a conditional load the
+    // compiler cannot tell how many loads are outstanding and waits for all of them, which made every guarded load a round trip
+    // of its own.  Indices are clamped into the tile instead and the guards are selects on the loaded values.
+    // The tile is the wave's: its column, its length and the run's two ends are scalars, so every address below is a scalar base
+    // plus a small unsigned lane offset (one VGPR, no 64-bit vector arithmetic; the masks tell the compiler how small).
+    p_first = __builtin_amdgcn_readfirstlane(p_first);
+    tl = __builtin_amdgcn_readfirstlane(tl) & 255;
+    // Prologue, one group of loads: the column pointers of the lane's four steps (a step beyond tl reads the tile's last column),
+    // the run's two ends, and with psum (wave-uniform; own_split) what a step starts from: psum[end of the run's columns] -
+    // psum[its column], what the columns hold apart from the streamed entries.  (The counters are live through the loop anyway.)
+    const int32_t *__restrict__ cl = cpos + (p_first - tl), *__restrict__ pl = (psum ? psum : cpos) + (p_first - tl);      // the tile's last column
+    int32_t cp[4], pv[4];
 #pragma unroll
     for (int k = 0; k < 4; k++) {
-        int32_t e = lane + 64 * k;
-        sk[k] = e <= tl ? cpos[p_first - e] : INT32_MAX;
-        acc[k] = (psum && e <= tl) ? ptop - psum[p_first - e] : 0;
+        const int32_t e = lane + 64 * k;
+        const uint32_t d = (uint32_t)(tl - (e < tl ? e : tl)) & 255u;
+        cp[k] = cl[d];
+        pv[k] = pl[d];
     }
     // head != 0: step 0 is the candidate p_first itself (no column stepped over): the run ends in front of that column
-    int32_t Q_hi = cpos[p_first + 1 - head], Q_lo = cpos[p_first - tl];       // wave-uniform
+    const int32_t ptop = pl[tl + 1 - head];
+    const int32_t Q_hi = __builtin_amdgcn_readfirstlane(cl[tl + 1 - head]), Q_lo = __builtin_amdgcn_readfirstlane(cl[0]);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const bool on = lane + 64 * k <= tl;
+        sk[k] = on ? cp[k] : INT32_MAX;
+        acc[k] = (psum && on) ? ptop - pv[k] : 0;
+    }
+    // Entries: a lane whose four positions start at or above Q_hi reads the run's last aligned quad instead -- inside the eight
+    // entries of slack behind every streamed array (next: ensure_links, flast: ensure_self, + 16; vnext: split_build, + 8) -- and
+    // what it reads is never flagged: every block that is not `inner` guards its flags by position, an inner one holds run entries only.
+    const int32_t x_end = Q_hi & ~3;
     int32_t x = Q_lo & ~3;
-    int4 c0 = make_int4(FILL, FILL, FILL, FILL), c1 = c0;
-    if (x + 4 * lane < Q_hi) c0 = *reinterpret_cast<const int4 *>(arr + x + 4 * lane);          // arrays are padded by 8 entries
-    if (x + 256 + 4 * lane < Q_hi) c1 = *reinterpret_cast<const int4 *>(arr + x + 256 + 4 * lane);
+    // (x <= x_end wherever this is called: the offset from the trip's first entry is unsigned and below 1024 or x_end - x)
+    auto quad = [&](uint32_t o) { const uint32_t r = (uint32_t)(x_end - x); return *reinterpret_cast<const int4 *>(arr + x + (o < r ? o : r)); };
+    int4 c0 = quad(4 * lane), c1 = quad(256 + 4 * lane);
     for (; x < Q_hi; x += 512) {
-        int4 n0 = make_int4(FILL, FILL, FILL, FILL), n1 = n0;
-        if (x + 512 + 4 * lane < Q_hi) n0 = *reinterpret_cast<const int4 *>(arr + x + 512 + 4 * lane);
-        if (x + 768 + 4 * lane < Q_hi) n1 = *reinterpret_cast<const int4 *>(arr + x + 768 + 4 * lane);
+        // the next 512 entries are issued before the current ones are touched: the wait below them is for c0 / c1 only
+        const int4 n0 = quad(512 + 4 * lane), n1 = quad(768 + 4 * lane);
 #pragma unroll
         for (int c = 0; c < 2; c++) {
             int32_t xc = x + c * 256;
@@ -978,26 +997,30 @@ __global__ void __launch_bounds__(256) k_own_map(RoundCounts *__restrict__ rc, c
 }
 
 // the counting sort's scatter: the tiles of column block c are border[bstart[c] .. bstart[c + 1]).  The counts have been scanned
-// by now, and the tile of rank 0 of every block that has tiles puts its block's count back to zero: bcnt is all zero between
+// by now; the tile's record goes to the same slot of srec; and the tile of rank 0 of every block that has tiles puts its block's count back to zero: bcnt is all zero between
 // rounds without a clearing pass (k_own_map and this kernel walk the same rc->NT tiles).
 __global__ void __launch_bounds__(256) k_blk_order(const RoundCounts *__restrict__ rc, const int4 *__restrict__ rec, const int32_t *__restrict__ brank,
-                                                   const int64_t *__restrict__ bstart, int32_t *__restrict__ border, int32_t *__restrict__ bcnt)
+                                                   const int64_t *__restrict__ bstart, int32_t *__restrict__ border, int4 *__restrict__ srec,
+                                                   int32_t *__restrict__ bcnt)
 {
     const int64_t ntile = rc->NT;
     for (int64_t tile = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; tile < ntile; tile += (int64_t)gridDim.x * blockDim.x) {
-        const int32_t c = rec[tile].x / LT, rk = brank[tile];
-        border[bstart[c] + rk] = (int32_t)tile;
+        const int4 r = rec[tile];
+        const int32_t c = r.x / LT, rk = brank[tile];
+        const int64_t slot = bstart[c] + rk;
+        border[slot] = (int32_t)tile;
+        srec[slot] = r;                                // (by value: the wave that runs the slot reads its record without the tile id)
         if (rk == 0) bcnt[c] = 0;
     }
 }
 
-// border (blk = 1): the tile ids in column-block order; wave k takes tile border[k]
+// border, a_srec (blk = 1): the tile ids and their records in column-block order; wave k takes tile border[k], whose record is a_srec[k]
 template <typename TC, bool HYP, bool GAP>
 __global__ void __launch_bounds__(256) k_lpass_own(int isA, const RoundCounts *__restrict__ rc, const int32_t *__restrict__ border,
                                                    const int32_t *__restrict__ a_pos, const int32_t *__restrict__ a_next,
                                                    const int32_t *__restrict__ a_fpos, const int32_t *__restrict__ a_flast,
                                                    int32_t *__restrict__ a_tileS, int32_t *__restrict__ a_tileS2, const int4 *__restrict__ a_rec,
-                                                   const TC *__restrict__ W, DevModel<TC> M, TC alpha, Best<TC, HYP> *__restrict__ part,
+                                                   const int4 *__restrict__ a_srec, const TC *__restrict__ W, DevModel<TC> M, TC alpha, Best<TC, HYP> *__restrict__ part,
                                                    int tau, const int32_t *__restrict__ gap_hi, uint8_t *__restrict__ spec, int force_spec,
                                                    Best<TC, HYP> *__restrict__ sub, int32_t *__restrict__ spv,
                                                    const int32_t *__restrict__ a_col, const int32_t *__restrict__ a_ffirst,
@@ -1015,11 +1038,14 @@ __global__ void __launch_bounds__(256) k_lpass_own(int isA, const RoundCounts *_
     // (No grid-stride loop here: it costs 14 VGPRs = two waves per SIMD.  The host launches one wave per tile of the buffer's
     //  CAPACITY, which the round's verdict (k_round_scans) has checked the true count against.)
     int lane = threadIdx.x & 63;
-    int64_t tile = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    int64_t tile = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (tile >= rc->NT) return;
+    // (own_blk: k_blk_order left the record next to the tile id, in the order the waves run: one level of loads, not two)
+    const int4 vrec = border ? a_srec[tile] : a_rec[tile];
     if (border) tile = border[tile];
-    int4 rec = a_rec[tile];
-    const int32_t rw = __builtin_amdgcn_readfirstlane(rec.w);      // (the record is the wave's: head, tile length and plane as scalars -- two VGPRs fewer)
+    // (the record is the wave's: its words as scalars -- the addresses made from them are scalar bases, and five VGPRs fewer)
+    const int32_t rw = __builtin_amdgcn_readfirstlane(vrec.w);
+    const int4 rec = make_int4(__builtin_amdgcn_readfirstlane(vrec.x), __builtin_amdgcn_readfirstlane(vrec.y), __builtin_amdgcn_readfirstlane(vrec.z), rw);
     int head = rw & 1;
     int32_t tl = (rw >> 2) & 255;
     int32_t acc[4], acc2[4] = {0, 0, 0, 0}, sk[4], sk2[4];
@@ -1053,14 +1079,18 @@ __global__ void __launch_bounds__(256) k_lpass_own(int isA, const RoundCounts *_
         const int64_t so = sb ? (int64_t)(sb - SPLIT_BMIN) * vstride : 0;
         interior_stream<true>(sb ? a_vnext : a_next, sb ? a_vpos + so : a_pos, rec.x, tl, rec.y, lane, acc, sk, head, 0, 0, nullptr, nullptr, nullptr, 0,
                               sb ? a_vsa + so : (const int32_t *)nullptr);
-        if (sb) {
+        // (a_pos is what the stream's sk holds when the tile is not split: reloaded either way, in one group with W below)
 #pragma unroll
-            for (int k = 0; k < 4; k++) if (lane + 64 * k <= tl) sk[k] = a_pos[rec.x - lane - 64 * k];
-        }
+        for (int k = 0; k < 4; k++) { const int32_t e = lane + 64 * k; sk[k] = (a_pos + (rec.x - tl))[(uint32_t)(tl - (e < tl ? e : tl)) & 255u]; }
     } else {
         interior_stream<true>(a_next, a_pos, rec.x, tl, rec.y, lane, acc, sk, head);
         if (HYP) interior_stream<false>(a_flast, a_fpos, rec.x, tl, rec.y, lane, acc2, sk2, head);
     }
+    // end of the wave, one group of loads: W of the lane's four candidates (and the pin positions above), at steps clamped into
+    // the tile; the evaluation selects afterwards
+    TC wv[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) { const int32_t e = lane + 64 * k; wv[k] = (W + (rec.x - tl))[(uint32_t)(tl - (e < tl ? e : tl)) & 255u]; }
     int sel = tl >> 6;
     if (lane == (tl & 63)) {
         a_tileS[tile] = sel == 0 ? acc[0] : sel == 1 ? acc[1] : sel == 2 ? acc[2] : acc[3];
@@ -1075,7 +1105,7 @@ __global__ void __launch_bounds__(256) k_lpass_own(int isA, const RoundCounts *_
         if (e <= tl && !(head && isA && e == 0)) {     // round A: the head element p = r is not a candidate
             int32_t p = rec.x - e;
             TC fv = dm_apply(M, alpha, (int64_t)(rec.y - p), (int64_t)(rec.z - sk[k]), (int64_t)acc[k], (int64_t)acc2[k]);
-            cand[k].v = cadd(W[p], fv); cand[k].p = p; cand[k].nn = acc[k]; best_set_nl(cand[k], acc2[k]);
+            cand[k].v = cadd(wv[k], fv); cand[k].p = p; cand[k].nn = acc[k]; best_set_nl(cand[k], acc2[k]);
         }
     }
     if (GAP && ns > SMAX) {                             // too many specials: k_gap_finish walks the tile entry by entry
@@ -2914,6 +2944,7 @@ struct LayerWork {
     DBuf<Best<TC, true>> o_part;
     // own_blk: the tiles sorted by 256-column block (k_own_map -> scan -> k_blk_order)
     DBuf<int32_t> b_cnt, b_n, o_brank, o_border;        // tiles per block, the block count (device); per tile: rank in its block, tile ids in block order
+    DBuf<int4> o_srec;                                  // ... and the tiles' records (o_rec) in block order
     DBuf<int64_t> b_start;
     int64_t b_nblk = 0;
     bool b_dirty = true;                                // b_cnt may hold counts (run_layer clears it before its first round)
@@ -2941,7 +2972,7 @@ struct LayerWork {
         if (o_rec.n >= NT && o_rec.n > 0) return;
         size_t c = NT > 0 ? NT : 1;
         o_rec.release();
-        o_task.alloc(c); o_tileS.alloc(c); o_tilePS.alloc(c + 1); o_part.alloc(c); o_hi.alloc(c); o_spec.alloc(c); o_brank.alloc(c); o_border.alloc(c);
+        o_task.alloc(c); o_tileS.alloc(c); o_tilePS.alloc(c + 1); o_part.alloc(c); o_hi.alloc(c); o_spec.alloc(c); o_brank.alloc(c); o_border.alloc(c); o_srec.alloc(c);
         o_item_of.alloc(c); o_items.alloc(fix_items_cap(c)); o_trec.alloc(fix_items_cap(c) * FIX_REC_W);
         o_sub.alloc(c * (SMAX + 1)); o_spv.alloc(c * (SMAX + 1));
         if (hyp) { o_tileS2.alloc(c); o_tilePS2.alloc(c + 1); }
@@ -3491,7 +3522,7 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
         if (P.nown > 0 && P.NT > 0) {
             // ---- long tasks with tiles of their own: map, stream + evaluate, merge
             const int64_t gNT = spec ? (int64_t)Wk.o_rec.n : P.NT, gown = spec ? grow(P.nown) : P.nown;      // (capacity >= the true NT, checked)
-            poison_fill(s, {{Wk.o_part.p, Wk.o_part.bytes()}, {Wk.o_tileS.p, Wk.o_tileS.bytes()}, {Wk.o_rec.p, Wk.o_rec.bytes()},
+            poison_fill(s, {{Wk.o_part.p, Wk.o_part.bytes()}, {Wk.o_tileS.p, Wk.o_tileS.bytes()}, {Wk.o_rec.p, Wk.o_rec.bytes()}, {Wk.o_srec.p, Wk.o_srec.bytes()},
                             {if_hyp<HYP>(Wk.o_tileS2.p), Wk.o_tileS2.bytes()}, {Wk.o_items.p, Wk.o_items.bytes()}, {Wk.o_item_of.p, Wk.o_item_of.bytes()},
                             {Wk.o_trec.p, Wk.o_trec.bytes()}});
             const unsigned mgrid = (unsigned)std::min<int64_t>(cdiv(gNT, 256), 8192);
@@ -3510,12 +3541,12 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
                 ProfScope ps(gap ? PROF_GAPSTREAM : PROF_OWN, s, own_bytes(R.tau, split != 0, (double)P.own_steps));
                 if (oblk) {                       // the tile ids by column block (counted in k_own_map): ~10^5 tiles, a counting sort
                     exclusive_scan_i32_lb(Wk.b_cnt.p, Wk.b_start.p, Wk.b_n.p, Wk.b_nblk, nullptr, Wk.scanws, s);
-                    hipLaunchKernelGGL(k_blk_order, dim3(mgrid), dim3(256), 0, s, rc, Wk.o_rec.p, Wk.o_brank.p, Wk.b_start.p, Wk.o_border.p, Wk.b_cnt.p);
+                    hipLaunchKernelGGL(k_blk_order, dim3(mgrid), dim3(256), 0, s, rc, Wk.o_rec.p, Wk.o_brank.p, Wk.b_start.p, Wk.o_border.p, Wk.o_srec.p, Wk.b_cnt.p);
                 }
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(gap ? k_lpass_own<TC, HYP, true> : k_lpass_own<TC, HYP, false>), dim3((unsigned)cdiv(gNT, 4)), dim3(256), 0, s,
                                    R.isA, rc,
                                    oblk ? Wk.o_border.p : (const int32_t *)nullptr, A->pos32.p, A->next.p, if_hyp<HYP>(A->fpos32.p), if_hyp<HYP>(A->flast.p),
-                                   Wk.o_tileS.p, Wk.o_tileS2.p, Wk.o_rec.p, W, M, alpha, recs<HYP>(Wk.o_part), R.tau, Wk.o_hi.p, Wk.o_spec.p,
+                                   Wk.o_tileS.p, Wk.o_tileS2.p, Wk.o_rec.p, Wk.o_srec.p, W, M, alpha, recs<HYP>(Wk.o_part), R.tau, Wk.o_hi.p, Wk.o_spec.p,
                                    (int)((g_opt_dbg & DBG_GAP_ALL_SPECIAL) != 0), recs<HYP>(Wk.o_sub), Wk.o_spv.p, A->col.p, if_hyp<HYP>(A->ffirst.p),
                                    split ? Wk.split.vnext.p : (const int32_t *)nullptr, Wk.split.vpos.p, Wk.split.vsa.p, (int64_t)(n + 1));
             }
