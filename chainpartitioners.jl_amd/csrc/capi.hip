@@ -140,13 +140,14 @@ static int32_t oracle_eval_into(cp_csr_t A, const cp_model_t *model, const cp_ro
 // ------------------------------------------------------------------ the counters of cp_get_stat
 // fix_trips: tasks the block merge walked in more than one trip; bits 0 / 1 / 2: a task of 1 / FIX_SERIAL / FIX_SERIAL + 1 tiles was
 // merged; fix_items: the (task, trip) items the merges were handed (every attempt of a layer: a dropped round lists none).
-// own_split_tiles: own tiles that streamed only their plane's variable link entries (layers that were not redone).
+// own_split_tiles: own tiles that streamed only their plane's variable link entries (layers that were not redone); gap_split_tiles: the
+// same for the tiles of the gap rounds, which own_split_tiles does not count.
 // bn_sym_layers: DP layers the valley search ran for the monotonized symmetric model.  kept: cp_set_option("poison", 1) starts a
 // poison pass by zeroing the other counters and leaves this one.
 static const struct { const char *name; int64_t *var; bool kept; } g_stats[] = {
     {"spec_redo", &g_spec_redo, false}, {"poison_hits", &g_poison_hits, false}, {"fix_trips", &g_fix_trips, false},
     {"fix_edges", &g_fix_edges, false}, {"fix_items", &g_fix_items, false}, {"bn_sym_layers", &g_bn_sym_layers, true},
-    {"own_split_tiles", &g_own_split_tiles, false},
+    {"own_split_tiles", &g_own_split_tiles, false}, {"gap_split_tiles", &g_gap_split_tiles, false},
 };
 static void stats_reset(bool all) { for (const auto &c : g_stats) if (all || !c.kept) *c.var = 0; }
 
@@ -163,6 +164,7 @@ static const struct Opt { const char *name; int64_t *var; OptRule rule; int64_t 
     {"pool", &g_opt_pool, OPT_BOOL, 0, 0},                      // (1: keep freed device blocks >= 1 MB for reuse; 0: return them, now and from here on)
     {"own_blk", &g_opt_own_blk, OPT_BOOL, 0, 0},                // (1, default: own tiles at 256-column blocks, run in block order; 0: tiles counted from each task head, in task order)
     {"own_split", &g_opt_own_split, OPT_BOOL, 0, 0},            // (1, default: own tiles of the planes >= 8 stream only the plane's variable link entries; 0: the whole columns)
+    {"gap_split", &g_opt_gap_split, OPT_BOOL, 0, 0},            // (1, default: so do the gap rounds' tiles of those planes -- while own_split is 1; 0: they stream the whole columns)
     {"lws", &g_opt_lws, OPT_BOOL, 0, 0},                        // (1, default: DynamicTotalChunker past the scan by chunk_lws.hip; 0: the one-wave kernel)
     {"gap_tau", &g_opt_gap_tau, OPT_CLAMP, NOLIM_LO, 20}, {"gap_min", &g_opt_gap_min, OPT_CLAMP, 8, NOLIM_HI}, {"gap_nr", &g_opt_gap_nr, OPT_CLAMP, 1, 2},
     {"force_max", &g_opt_force_max, OPT_CLAMP, 0, NOLIM_HI}, {"rpass_cap", &g_opt_rpass_cap, OPT_CLAMP, 1, NOLIM_HI},

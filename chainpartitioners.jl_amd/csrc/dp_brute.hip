@@ -22,6 +22,8 @@ int64_t g_opt_own_min = 64;
 int64_t g_opt_own_blk = 1;             // own tiles at absolute 256-column blocks, run in block order; 0: tiles from each task head (k_own_map)
 int64_t g_opt_own_split = 1;           // own tiles of the planes >= 8 stream only their plane's variable link entries (SplitLinks); 0: the whole columns
 int64_t g_own_split_tiles = 0;
+int64_t g_opt_gap_split = 1;           // ... and so do the gap rounds' tiles of those planes (effective while own_split is on)
+int64_t g_gap_split_tiles = 0;
 int64_t g_opt_rpass_ch = 256;
 int64_t g_opt_rpass_small_tau = 4;
 int64_t g_opt_force_max = 1024;           // a round's flattened stage is replaced by own tiles when it served at most this many tasks

@@ -1058,18 +1058,46 @@ __global__ void __launch_bounds__(256) k_lpass_own(int isA, const RoundCounts *_
         if (lane == 0) *s_cnt = 0;
         __threadfence_block();
         int32_t rL = rec.y - (1 << tau), hi1 = gap_hi[tile] - 1;
-        interior_stream<true, true>(a_next, a_pos, rec.x, tl, hi1, lane, acc, sk, head, rL, hi1, s_es[0], s_v[0], s_cnt, 0);
+        // gap_split (k_own_map put the plane into the record, as for the other rounds): the classification of SplitLinks holds for a
+        // gap task of plane b -- its rows (rL, hi) lie in the rectangle's rows, thr = hi - 1 and the special interval (rL, hi - 1) in
+        // the sibling block's range -- so an entry below the plane is neither counted nor special, one above it is counted by every
+        // row and never special (the prefix difference the stream starts its counters from), and only the plane's variable entries
+        // are compared and tested
+        const int sb = HYP ? 0 : rw >> 10;                               // (scalar: the arrays stay scalar operands)
+        const int64_t so = sb ? (int64_t)(sb - SPLIT_BMIN) * vstride : 0;
+        interior_stream<true, true>(sb ? a_vnext : a_next, sb ? a_vpos + so : a_pos, rec.x, tl, hi1, lane, acc, sk, head, rL, hi1, s_es[0], s_v[0], s_cnt, 0,
+                                    sb ? a_vsa + so : (const int32_t *)nullptr);
         if (HYP) interior_stream<false, true>(a_flast, a_fpos, rec.x, tl, rL + 1, lane, acc2, sk2, head, rL, hi1, s_es[0], s_v[0], s_cnt, 1);
         __threadfence_block();
         ns = *s_cnt;
         if (force_spec) ns = SMAX + 1;
         if (ns > 0 && ns <= SMAX) {                     // positions -> steps: first step whose candidate has the entry's column on its right
-            if (lane < ns) {
-                const int32_t q = s_es[0][lane];
-                const bool k1 = s_v[0][lane] < 0;       // (bit 31: an entry of the second list)
-                s_es[0][lane] = rec.x - (k1 ? a_ffirst[q] : a_col[q]);
+            if (HYP) {
+                if (lane < ns) {
+                    const int32_t q = s_es[0][lane];
+                    const bool k1 = s_v[0][lane] < 0;   // (bit 31: an entry of the second list)
+                    s_es[0][lane] = rec.x - (k1 ? a_ffirst[q] : a_col[q]);
+                }
+            } else {
+                // ... = the number of the tile's steps whose column starts above the position, from the starts the wave holds (sk: of
+                // the streamed array, whichever it is).  Empty columns have equal starts: the entry's column is the LARGEST one that
+                // starts at or below it.  (At most SMAX rounds of four ballots, in the rare tile with specials; no array, no load.)
+                int32_t es = 0;
+                for (int i = 0; i < ns; i++) {
+                    const int32_t q = s_es[0][i];       // (uniform)
+                    int32_t c = 0;
+#pragma unroll
+                    for (int k = 0; k < 4; k++) c += (int32_t)__popcll(__ballot(lane + 64 * k <= tl && sk[k] > q));
+                    if (lane == i) es = c;
+                }
+                __threadfence_block();
+                if (lane < ns) s_es[0][lane] = es;
             }
             __threadfence_block();
+        }
+        if (!HYP) {                                     // (the pin count wants the column's own position: what sk holds unless the tile is split; reloaded either way)
+#pragma unroll
+            for (int k = 0; k < 4; k++) { const int32_t e = lane + 64 * k; sk[k] = (a_pos + (rec.x - tl))[(uint32_t)(tl - (e < tl ? e : tl)) & 255u]; }
         }
     } else if (!HYP && !GAP) {
         // own_split (k_own_map put the plane into the record): only the plane's variable entries are streamed; the entries every
@@ -3318,13 +3346,13 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
     // the kernels do not read -- which put the achieved rate above the box's copy rate.)
     const double step_bytes = 4.0 * (avg_deg + self_deg) + 12.0 + 32.0 / (double)LT;
     const bool own_tiles = !(g_opt_dbg & DBG_NO_OWN_TILES);      // (keep every long task in the flattened space)
-    // cp_set_option("own_split", 0 | 1): outside round A and the gap rounds the own tiles of the planes >= SPLIT_BMIN stream only their
-    // plane's variable link entries (SplitLinks).  Not for hyperedge costs (the second list is not split) nor for windowed layers
+    // cp_set_option("own_split", 0 | 1): outside round A the own tiles of the planes >= SPLIT_BMIN stream only their plane's variable
+    // link entries (SplitLinks); the tiles of the gap rounds while "gap_split" is on too.  Not for hyperedge costs (the second list is not split) nor for windowed layers
     // (their blocks are not the Fenwick blocks).
     const bool split_layer = !HYP && !G.win && g_opt_own_split && nbits > SPLIT_BMIN;
     // bytes the own-tile stream moves: split tiles read two column pointers and a prefix sum per step (20 B with the cost) and the
     // variable entries of the round's planes, at most what the columns hold.  (Tiles of planes below SPLIT_BMIN in the same launch --
-    // gap_tau < 7 only -- are priced like the others.)
+    // the plane-7 tiles of the gap round tau = 6 -- are priced like the others.)
     auto own_bytes = [&](int tau, bool sp, double steps) {
         if (!sp) return steps * step_bytes;
         double var = 0;
@@ -3527,9 +3555,11 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
                             {Wk.o_trec.p, Wk.o_trec.bytes()}});
             const unsigned mgrid = (unsigned)std::min<int64_t>(cdiv(gNT, 256), 8192);
             // (1: every tile of the launch is of a plane >= SPLIT_BMIN, their number is NT; 2: the launch also holds tiles of the planes
-            //  below -- gap_tau < 6 only -- and k_own_map counts: 1 600 same-address atomics per launch cost it 17 us at config 3)
-            const int split = !(split_layer && !gap && !R.isA) ? 0 : R.tau + 1 >= SPLIT_BMIN ? 1 : 2;
-            split_mode[(size_t)rd] = (int8_t)split;
+            //  below -- the gap round tau = 6 with its plane-7 tiles, and every round below it with gap_tau < 6 -- and k_own_map
+            //  counts: 1 600 same-address atomics per launch cost it 17 us at config 3)
+            // (gap rounds: cp_set_option("gap_split", 0 | 1), effective while own_split is on)
+            const int split = !(split_layer && !R.isA && (!gap || g_opt_gap_split)) ? 0 : R.tau + 1 >= SPLIT_BMIN ? 1 : 2;
+            split_mode[(size_t)rd] = (int8_t)(gap ? -split : split);
             if (split && !Wk.split.built) {             // once per pattern, by the first round that streams them
                 ProfScope ps(PROF_LINKS, s, 8.0 * (double)A->N + 16.0 * (double)(nbits - SPLIT_BMIN) * (double)(n + 1));
                 split_build(A, Wk.split, Wk.scratch);
@@ -3694,7 +3724,10 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
     if (ok) for (int rd = 0; rd < NR; rd++) { g_fix_trips += got[(size_t)rd].n_trips; g_fix_edges |= got[(size_t)rd].n_edge; }
     if (ok) for (int rd = 0; rd < NR; rd++) {
         const RoundCounts &g = got[(size_t)rd];
-        if (g.nown > 0 && g.NT > 0) g_own_split_tiles += split_mode[(size_t)rd] == 1 ? g.NT : split_mode[(size_t)rd] == 2 ? g.n_split : 0;
+        if (g.nown > 0 && g.NT > 0) {                   // (negative: a gap round)
+            const int sm = split_mode[(size_t)rd];
+            (sm < 0 ? g_gap_split_tiles : g_own_split_tiles) += std::abs(sm) == 1 ? g.NT : std::abs(sm) == 2 ? g.n_split : 0;
+        }
     }
     for (int rd = 0; rd < NR; rd++) g_fix_items += got[(size_t)rd].n_items;      // (attempts that are redone included: a dropped round lists none)
     if (ok) {
