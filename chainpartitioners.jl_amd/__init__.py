@@ -10,15 +10,15 @@ from .models import (PowerWorkModel, ConvexWorkModel, ConcaveWorkModel,   # noqa
                      AffineWorkModel, AffinePrimaryConnectivityModel, AffineSecondaryConnectivityModel, AffineConnectivityModel, AffineHyperedgeCutModel,      # noqa: F401
                      AffineSymmetricConnectivityModel, AffineMonotonizedSymmetricConnectivityModel, AffineSymmetricEdgeCutModel,
                      ColumnBlockComponentCostModel, BlockComponentCostModel, VertexCount, FeasibleCost,
-                     ConstrainedCost, EquiSplitter, EquiChunker, DynamicTotalSplitter,
+                     ConstrainedCost, EquiSplitter, EquiChunker, StrictChunker, OverlapChunker, DynamicTotalSplitter,
                      DynamicBottleneckSplitter, DynamicTotalChunker, DynamicBottleneckChunker,
                      ReferenceTotalSplitter, ReferenceBottleneckSplitter, ReferenceTotalChunker,
                      BisectCostBottleneckSplitter, FlipBisectCostBottleneckSplitter,
                      BisectIndexBottleneckSplitter, FlipBisectIndexBottleneckSplitter,
                      LazyBisectCostBottleneckSplitter, DisjointPartitioner, AlternatingPartitioner,
-                     AlternatingNetPartitioner, SymmetricPartitioner,
+                     AlternatingNetPartitioner, SymmetricPartitioner, AlternatingPacker, SymmetricPacker,
                      ConvexTotalChunker, ConvexTotalSplitter, ConcaveTotalChunker, ConcaveTotalSplitter)
 from . import _lib  # noqa: F401
-from .api import (adjointpattern, partition_plaid, partition_stripe, partition_stripe_batch, pack_stripe, pack_stripe_batch, pack_stripe_tables, oracle_stripe, bound_stripe, total_value,   # noqa: F401
+from .api import (adjointpattern, partition_plaid, pack_plaid, partition_stripe, partition_stripe_batch, pack_stripe, pack_stripe_batch, pack_stripe_tables, oracle_stripe, bound_stripe, total_value,   # noqa: F401
                   bottleneck_value, netcount, selfnetcount, dominancecount, dianetcount, selfpincount, set_default_backend,
                   get_backend, CPError, Step, Same, Next, Prev, Jump)

@@ -96,6 +96,8 @@ SIGNATURES = {
     "cp_pack_convex": _PACK,
     "cp_pack_convex_batch": (_i32, [_vp, _i64, _MODEL, _I64("wmax"), _i64, _I64("spl_out"), _I64("K_out")]),
     "cp_partition_convex": _SPLIT,
+    "cp_pack_strict": (_i32, [_vp, _i64, _I64("spl_out"), _I64("K_out")]),
+    "cp_pack_overlap": (_i32, [_vp, _f64, _i64, _I64("spl_out"), _I64("K_out"), _I64("n_nets_out")]),
     "cp_partition_equi": (_i32, [_i64, _i64, _I64("spl_out")]),
     "cp_pack_equi": (_i32, [_i64, _i64, _I64("spl_out"), _I64("K_out")]),
     "cp_dynamic_tables": (_i32, [_vp, _i64, _i32, _MODEL, _ROWPART, _I64("ptr_out"), _I64("cst_i64"), _F64("cst_f64")]),
@@ -360,6 +362,13 @@ class HipBackend:
 
     def partition_concave(self, A, K, mm, rp, wm, wi, wf, spl):
         return self.lib.cp_partition_concave(self._h(A), K, mm, rp, wm, wi, wf, spl)
+
+    def pack_strict(self, A, w_max, spl, Kout):
+        return self.lib.cp_pack_strict(self._h(A), int(w_max), spl, Kout)
+
+    def pack_overlap(self, A, rho, w_max, spl, Kout, n_nets=None):
+        """n_nets: None or an int64 array of n slots; the first K receive the distinct-row count of every part"""
+        return self.lib.cp_pack_overlap(self._h(A), float(rho), int(w_max), spl, Kout, n_nets)
 
     # ---- oracles / scoring
     def oracle_eval(self, A, mm, rp, hint, j, jp, k, out):

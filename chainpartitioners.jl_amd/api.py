@@ -10,7 +10,8 @@ the same `backend=` hook to compare the two on identical marshalled inputs.
 Reference entry points mirrored (under /root/reference/src):
   partition_stripe  EquiPartitioner.jl:5, DynamicSplitter.jl:15,52,206,260,
                     BisectCostBottleneckSplitter.jl:6,70, ConvexTotalChunker.jl:26,170
-  pack_stripe       EquiPartitioner.jl:15, DynamicChunker.jl:15,20, ConvexTotalChunker.jl:9,141
+  pack_stripe       EquiPartitioner.jl:15, DynamicChunker.jl:15,20, ConvexTotalChunker.jl:9,141, StrictChunker.jl:5, OverlapChunker.jl:6
+  pack_plaid        AlternatingPacker.jl:18,40
   oracle_stripe / bound_stripe / total_value / bottleneck_value   Costs.jl:3-66
 """
 from __future__ import annotations
@@ -226,11 +227,35 @@ def pack_stripe_batch(A: SparseMatrixCSC, methods, *, backend=None):
 
 
 # ---------------------------------------------------------------- pack_stripe
-def pack_stripe(A: SparseMatrixCSC, method, Pi=None, *, backend=None) -> SplitPartition:
+def _pack_greedy(A, method, n_nets, backend):
+    """StrictChunker / OverlapChunker (StrictChunker.jl:5, OverlapChunker.jl:6): no cost model to marshal, Pi is not looked at."""
+    b = get_backend(backend)
+    call = "pack_strict" if isinstance(method, M.StrictChunker) else "pack_overlap"
+    if not hasattr(b, call):
+        raise NotImplementedError(f"{type(method).__name__} is implemented by the HIP backend only, not by backend "
+                                  f"'{getattr(b, 'name', type(b).__name__)}'")
+    spl, Kout = np.zeros(A.n + 1, dtype=np.int64), np.zeros(1, dtype=np.int64)
+    if isinstance(method, M.StrictChunker):
+        rc = b.pack_strict(A, method.w_max, spl, Kout)
+    else:
+        nn = None if n_nets is None else np.zeros(max(A.n, 1), dtype=np.int64)
+        rc = b.pack_overlap(A, method.rho, method.w_max, spl, Kout, nn)
+    _check(rc, f"pack_stripe({type(method).__name__})", b)
+    K = int(Kout[0])
+    if n_nets is not None and isinstance(method, M.OverlapChunker):
+        n_nets[0] = nn[:K].copy()
+    return SplitPartition(K, spl[:K + 1].copy())
+
+
+def pack_stripe(A: SparseMatrixCSC, method, Pi=None, *, n_nets=None, backend=None) -> SplitPartition:
+    """n_nets: a one-element list standing for the reference's Ref (OverlapChunker.jl:6, :24-29); OverlapChunker leaves the int64
+    array of the K parts' distinct-row counts in its element 0.  The other methods ignore it, as the reference's kwargs... do."""
     if isinstance(method, M.EquiChunker):
         n, w = A.n, method.w
         spl = np.concatenate([np.arange(1, n + 1, w, dtype=np.int64), [n + 1]])   # [1:w:n; n+1]
         return SplitPartition(len(spl) - 1, spl)
+    if isinstance(method, (M.StrictChunker, M.OverlapChunker)):
+        return _pack_greedy(A, method, n_nets, backend)
     spl, Kout = _dispatch("pack_stripe", _PACK, (A,), method, Pi, backend,
                           lambda: (np.zeros(A.n + 1, dtype=np.int64), np.zeros(1, dtype=np.int64)))
     return SplitPartition(int(Kout[0]), spl[:int(Kout[0]) + 1].copy())
@@ -393,6 +418,29 @@ def partition_plaid(A: SparseMatrixCSC, K, method, *, adj_A=None, backend=None):
             Pi = partition_stripe(A, K, method.mtds[0], backend=backend)
         return Pi, Pi
     raise NotImplementedError(f"partition_plaid: method {type(method).__name__} is outside the hot path")
+
+
+def pack_plaid(A: SparseMatrixCSC, method, *, adj_A=None, backend=None):
+    """pack_plaid(A, method) -> (Pi, Phi)  (AlternatingPacker.jl:18-32, :40-53): the 2-D callers of pack_stripe, host orchestration
+    over adjointpattern and pack_stripe -- any pack_stripe method, on any backend that has it.  DisjointPacker goes through a
+    PermutedDimsArray, for which the reference has no chunker method: not served."""
+    if isinstance(method, M.AlternatingPacker):
+        T = adj_A if adj_A is not None else adjointpattern(A, backend=backend)
+        Phi = pack_stripe(A, method.mtds[0], backend=backend)
+        Pi = pack_stripe(T, method.mtds[1], Phi, backend=backend)
+        for i, mtd in enumerate(method.mtds[2:], start=1):
+            if i % 2 == 1:
+                Phi = pack_stripe(A, mtd, Pi, backend=backend)
+            else:
+                Pi = pack_stripe(T, mtd, Phi, backend=backend)
+        return Pi, Phi
+    if isinstance(method, M.SymmetricPacker):
+        T = adj_A if adj_A is not None else adjointpattern(A, backend=backend)
+        Pi = pack_stripe(A, method.mtds[0], backend=backend)
+        for i, mtd in enumerate(method.mtds[1:], start=1):
+            Pi = pack_stripe(A if i % 2 == 1 else T, mtd, Pi, backend=backend)
+        return Pi, Pi
+    raise NotImplementedError(f"pack_plaid: method {type(method).__name__} is outside the hot path")
 
 
 def adjointpattern(A: SparseMatrixCSC, *, backend=None) -> SparseMatrixCSC:

@@ -141,13 +141,14 @@ static int32_t oracle_eval_into(cp_csr_t A, const cp_model_t *model, const cp_ro
 // fix_trips: tasks the block merge walked in more than one trip; bits 0 / 1 / 2: a task of 1 / FIX_SERIAL / FIX_SERIAL + 1 tiles was
 // merged; fix_items: the (task, trip) items the merges were handed (every attempt of a layer: a dropped round lists none).
 // own_split_tiles: own tiles that streamed only their plane's variable link entries (layers that were not redone); gap_split_tiles: the
-// same for the tiles of the gap rounds, which own_split_tiles does not count.
+// same for the tiles of the gap rounds, which own_split_tiles does not count.  overlap_isect: column intersections cp_pack_overlap computed.
 // bn_sym_layers: DP layers the valley search ran for the monotonized symmetric model.  kept: cp_set_option("poison", 1) starts a
 // poison pass by zeroing the other counters and leaves this one.
 static const struct { const char *name; int64_t *var; bool kept; } g_stats[] = {
     {"spec_redo", &g_spec_redo, false}, {"poison_hits", &g_poison_hits, false}, {"fix_trips", &g_fix_trips, false},
     {"fix_edges", &g_fix_edges, false}, {"fix_items", &g_fix_items, false}, {"bn_sym_layers", &g_bn_sym_layers, true},
     {"own_split_tiles", &g_own_split_tiles, false}, {"gap_split_tiles", &g_gap_split_tiles, false},
+    {"overlap_isect", &g_overlap_isect, false},
 };
 static void stats_reset(bool all) { for (const auto &c : g_stats) if (all || !c.kept) *c.var = 0; }
 

@@ -82,7 +82,8 @@ inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // ------------------------------------------------------------------ per-kernel HIP-event profiling
 struct ProfSlot { const char *name; int64_t launches; double ms; double alg_bytes; };
 enum { PROF_EXPAND = 0, PROF_EVAL, PROF_SETUP, PROF_SCAN, PROF_CARRY, PROF_FIX, PROF_COMBINE, PROF_LINKS,
-       PROF_BRUTE, PROF_WAVELET, PROF_QUERY, PROF_BISECT, PROF_CHUNK, PROF_RPASS, PROF_OWN, PROF_GAP, PROF_GAPSTREAM, PROF_RA, PROF_LEAF, PROF_LWS, PROF_NSLOTS };
+       PROF_BRUTE, PROF_WAVELET, PROF_QUERY, PROF_BISECT, PROF_CHUNK, PROF_RPASS, PROF_OWN, PROF_GAP, PROF_GAPSTREAM, PROF_RA, PROF_LEAF, PROF_LWS,
+       PROF_COLNEQ, PROF_OVNEXT, PROF_ORBIT, PROF_COMPACT, PROF_NSLOTS };
 extern ProfSlot g_prof[PROF_NSLOTS];
 extern bool g_prof_on;
 extern int g_prof_only;              // >= 0: only this slot records events (cp_set_option("prof_only")): 2 events per round instead of ~40
@@ -185,6 +186,8 @@ __device__ __forceinline__ bool scan_lb_block(const int32_t *__restrict__ in, in
     return wrote;
 }
 void exclusive_scan_i32_i32(const int32_t *in, int32_t *out, int64_t n, DBuf<int64_t> &scratch, hipStream_t s);
+// device-wide inclusive max-scan of the flagged positions: out[i] = the largest t <= i with flag[t] != 0, -1 if there is none (n < 2^31)
+void scan_last_flagged(const int32_t *flag, int32_t *out, int64_t n, DBuf<int64_t> &scratch, hipStream_t s);
 
 // wave64 helpers
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }

@@ -16,7 +16,8 @@ ProfSlot g_prof[PROF_NSLOTS] = {
     {"dp_lpass", 0, 0, 0}, {"dp_open_segments", 0, 0, 0}, {"dp_task_setup", 0, 0, 0},
     {"scan", 0, 0, 0}, {"dp_tile_carry", 0, 0, 0}, {"dp_span_fix", 0, 0, 0}, {"dp_combine", 0, 0, 0},
     {"link_build", 0, 0, 0}, {"dp_brute", 0, 0, 0}, {"wavelet_build", 0, 0, 0}, {"count_query", 0, 0, 0},
-    {"bisect_probe", 0, 0, 0}, {"chunker", 0, 0, 0}, {"dp_rpass", 0, 0, 0}, {"dp_lpass_own", 0, 0, 0}, {"dp_gap_finish", 0, 0, 0}, {"dp_lpass_gap", 0, 0, 0}, {"dp_round_a", 0, 0, 0}, {"dp_leaf", 0, 0, 0}, {"chunk_lws", 0, 0, 0}};
+    {"bisect_probe", 0, 0, 0}, {"chunker", 0, 0, 0}, {"dp_rpass", 0, 0, 0}, {"dp_lpass_own", 0, 0, 0}, {"dp_gap_finish", 0, 0, 0}, {"dp_lpass_gap", 0, 0, 0}, {"dp_round_a", 0, 0, 0}, {"dp_leaf", 0, 0, 0}, {"chunk_lws", 0, 0, 0},
+    {"chunk_col_neq", 0, 0, 0}, {"chunk_overlap_next", 0, 0, 0}, {"chunk_orbit", 0, 0, 0}, {"chunk_compact", 0, 0, 0}};
 bool g_prof_on = false;
 int g_prof_only = -1;
 std::vector<ProfPending> g_prof_pending;
@@ -243,6 +244,78 @@ void exclusive_scan_i32_i32(const int32_t *in, int32_t *out, int64_t n, DBuf<int
     hipLaunchKernelGGL(k_scan_blocksums, dim3(1), dim3(1024), 0, s, scratch.p, nb);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_scan_apply<int32_t>), dim3((unsigned)nb), dim3(SCAN_T), 0, s, in, out, scratch.p, n, nb,
                        (const int32_t *)nullptr, (int64_t *)nullptr);
+    CP_HIP(hipGetLastError());
+}
+
+// ---- max-scan of flagged positions (same three launches as the sums above; the block values are positions, -1: none)
+__global__ void __launch_bounds__(SCAN_T) k_lastflag_reduce(const int32_t *__restrict__ flag, int64_t *__restrict__ bmax, int64_t n)
+{
+    __shared__ int64_t sh[SCAN_T / 64];
+    int64_t base = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)threadIdx.x * SCAN_I;
+    int64_t v = -1;
+#pragma unroll
+    for (int k = 0; k < SCAN_I; k++) if (base + k < n && flag[base + k]) v = base + k;
+    for (int o = 32; o > 0; o >>= 1) { int64_t t = __shfl_down(v, o); v = t > v ? t : v; }
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int64_t t = -1;
+        for (int w = 0; w < SCAN_T / 64; w++) t = sh[w] > t ? sh[w] : t;
+        bmax[blockIdx.x] = t;
+    }
+}
+
+// single block: exclusive max-scan of bmax[0..nb) in place
+__global__ void __launch_bounds__(1024) k_lastflag_blocks(int64_t *__restrict__ bmax, int64_t nb)
+{
+    __shared__ int64_t sh[1024];
+    int64_t chunk = (nb + 1023) / 1024;
+    int64_t lo = (int64_t)threadIdx.x * chunk, hi = lo + chunk < nb ? lo + chunk : nb;
+    int64_t v = -1;
+    for (int64_t i = lo; i < hi; i++) v = bmax[i] > v ? bmax[i] : v;
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {
+        int64_t t = threadIdx.x >= (unsigned)o ? sh[threadIdx.x - o] : -1;
+        __syncthreads();
+        if (t > sh[threadIdx.x]) sh[threadIdx.x] = t;
+        __syncthreads();
+    }
+    int64_t run = threadIdx.x > 0 ? sh[threadIdx.x - 1] : -1;
+    for (int64_t i = lo; i < hi; i++) { int64_t t = bmax[i]; bmax[i] = run; run = t > run ? t : run; }
+}
+
+__global__ void __launch_bounds__(SCAN_T) k_lastflag_apply(const int32_t *__restrict__ flag, int32_t *__restrict__ out,
+                                                          const int64_t *__restrict__ bmax, int64_t n)
+{
+    __shared__ int64_t sh[SCAN_T];
+    int64_t base = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)threadIdx.x * SCAN_I;
+    int32_t f[SCAN_I];
+    int64_t v = -1;
+#pragma unroll
+    for (int k = 0; k < SCAN_I; k++) { f[k] = (base + k < n) ? flag[base + k] : 0; if (f[k]) v = base + k; }
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (int o = 1; o < SCAN_T; o <<= 1) {
+        int64_t t = threadIdx.x >= (unsigned)o ? sh[threadIdx.x - o] : -1;
+        __syncthreads();
+        if (t > sh[threadIdx.x]) sh[threadIdx.x] = t;
+        __syncthreads();
+    }
+    int64_t run = threadIdx.x > 0 ? sh[threadIdx.x - 1] : -1;
+    if (bmax[blockIdx.x] > run) run = bmax[blockIdx.x];
+#pragma unroll
+    for (int k = 0; k < SCAN_I; k++) if (base + k < n) { if (f[k]) run = base + k; out[base + k] = (int32_t)run; }
+}
+
+void scan_last_flagged(const int32_t *flag, int32_t *out, int64_t n, DBuf<int64_t> &scratch, hipStream_t s)
+{
+    if (n <= 0) return;
+    int64_t nb = cdiv(n, SCAN_TILE);
+    scratch.ensure((size_t)nb + 1);
+    hipLaunchKernelGGL(k_lastflag_reduce, dim3((unsigned)nb), dim3(SCAN_T), 0, s, flag, scratch.p, n);
+    hipLaunchKernelGGL(k_lastflag_blocks, dim3(1), dim3(1024), 0, s, scratch.p, nb);
+    hipLaunchKernelGGL(k_lastflag_apply, dim3((unsigned)nb), dim3(SCAN_T), 0, s, flag, out, scratch.p, n);
     CP_HIP(hipGetLastError());
 }
 

@@ -402,6 +402,20 @@ class EquiChunker:
         self.w = int(w)
 
 
+class StrictChunker:
+    """StrictChunker.jl:1-3: greedy parts of identical columns, at most w_max wide (w_max < 1: no limit)."""
+
+    def __init__(self, w_max):
+        self.w_max = int(w_max)
+
+
+class OverlapChunker:
+    """OverlapChunker.jl:1-4: greedy parts whose columns overlap the part's first column by the fraction rho, at most w_max wide."""
+
+    def __init__(self, rho, w_max):
+        self.rho, self.w_max = float(rho), int(w_max)
+
+
 class _FMethod:
     def __init__(self, f):
         self.f = f
@@ -491,6 +505,22 @@ class AlternatingNetPartitioner(AlternatingPartitioner):
 
 class SymmetricPartitioner:
     """AlternatingPartitioner.jl:60-87: one partition for rows and columns of a square matrix."""
+
+    def __init__(self, *mtds):
+        assert len(mtds) >= 1
+        self.mtds = tuple(mtds)
+
+
+class AlternatingPacker:
+    """AlternatingPacker.jl:12-32: pack_stripe for Phi on A, for Pi on the adjoint given Phi, then alternately again."""
+
+    def __init__(self, *mtds):
+        assert len(mtds) >= 2
+        self.mtds = tuple(mtds)
+
+
+class SymmetricPacker:
+    """AlternatingPacker.jl:34-53: one packing for rows and columns, refined on A and its adjoint in turn."""
 
     def __init__(self, *mtds):
         assert len(mtds) >= 1

@@ -184,6 +184,19 @@ int32_t cp_pack_convex_batch(cp_csr_t csr, int64_t B, const cp_model_t *models, 
 int32_t cp_partition_convex(cp_csr_t csr, int64_t K, const cp_model_t *model, const cp_rowpart_t *Pi,
                             const cp_model_t *weight, int64_t wmax_i64, double wmax_f64,
                             int64_t *spl_out /* K+1 */);
+/* pack_stripe(A, StrictChunker(w_max))  StrictChunker.jl:5-54: a part holds copies of its first column, at most w_max of them
+ * (w_max < 1: no width limit -- the reference's `w != w_max` never fires).  Computed as a column-against-left-neighbour comparison, a
+ * max-scan and a compaction instead of the reference's sweep; the split vector is the sweep's.  n < 1 is CP_EINVAL (the reference
+ * reads colptr[2]).  spl_out: n+1 slots, K_out[0] + 1 of them hold the split vector (the rest are unspecified); K_out: one element. */
+int32_t cp_pack_strict(cp_csr_t csr, int64_t w_max, int64_t *spl_out /* n+1 */, int64_t *K_out);
+/* pack_stripe(A, OverlapChunker(rho, w_max); n_nets)  OverlapChunker.jl:6-75: column j' joins the part that starts at column j unless
+ * j' - j == w_max or Float64(|col j' and col j|) < rho * Float64(min(c, |col j'|)), evaluated in Float64 as written (:57), where c is
+ * the length of the matrix's FIRST column throughout -- the reference never refreshes it at a split (:58-63) and its output depends on
+ * that.  Computed as next[j] for every start j at once and the orbit of column 1 by pointer doubling; the split vector is the sweep's.
+ * n_nets_out: NULL, or n slots of which the first K_out[0] receive the number of distinct rows of each part (n_nets[], :59, :67).
+ * n < 1 is CP_EINVAL.  The work is sum_j (next[j] - j) column intersections, at most n * w_max; without a width limit a run of L
+ * mutually overlapping columns costs about L^2 / 2 (cp_get_stat "overlap_isect" counts them). */
+int32_t cp_pack_overlap(cp_csr_t csr, double rho, int64_t w_max, int64_t *spl_out /* n+1 */, int64_t *K_out, int64_t *n_nets_out /* n or NULL */);
 /* EquiSplitter / EquiChunker  EquiPartitioner.jl:3-22 (closed forms, host arithmetic) */
 int32_t cp_partition_equi(int64_t n, int64_t K, int64_t *spl_out /* K+1 */);
 int32_t cp_pack_equi(int64_t n, int64_t w, int64_t *spl_out /* cld(n,w)+1 */, int64_t *K_out);
@@ -254,7 +267,7 @@ int32_t cp_reset_stream(cp_csr_t csr);
  * attempts that were redone.  "fix_items" -- the (task, trip) work items those merges were handed: one per 2 048 tiles, or part of
  * them, of every task of more than 16 tiles, in every attempt of a layer (a round dropped by its verdict lists none) and in
  * cp_test_fix_merge.  "own_split_tiles" -- own tiles that streamed only their plane's variable link entries ("own_split"), in
- * the layers that stand.  All six are reset when "poison" is switched on and by cp_set_option("stat_reset", 1); reading
+ * the layers that stand.  "overlap_isect" -- the column intersections cp_pack_overlap computed.  All of these are reset when "poison" is switched on and by cp_set_option("stat_reset", 1); reading
  * changes nothing. */
 int32_t cp_get_stat(const char *name, int64_t *out);
 /* Test entry: the launch that ends the counting phase of a DP round, on host arrays.  Exclusive scans of a[0 .. na) and (two != 0)
