@@ -9,6 +9,7 @@ from .types import to_map, to_domain   # noqa: F401
 from .models import (PowerWorkModel, ConvexWorkModel, ConcaveWorkModel,   # noqa: F401
                      AffineWorkModel, AffinePrimaryConnectivityModel, AffineSecondaryConnectivityModel, AffineConnectivityModel, AffineHyperedgeCutModel,      # noqa: F401
                      AffineSymmetricConnectivityModel, AffineMonotonizedSymmetricConnectivityModel, AffineSymmetricEdgeCutModel,
+                     AffinePrimaryEdgeCutModel, AffineSecondaryEdgeCutModel,
                      ColumnBlockComponentCostModel, BlockComponentCostModel, VertexCount, FeasibleCost,
                      ConstrainedCost, EquiSplitter, EquiChunker, StrictChunker, OverlapChunker, DynamicTotalSplitter,
                      DynamicBottleneckSplitter, DynamicTotalChunker, DynamicBottleneckChunker,

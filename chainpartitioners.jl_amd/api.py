@@ -93,8 +93,9 @@ def _w_table_for(A, f, weight, w_max, stack_method=False):
 
 
 def _need_hip(b, mdl):
-    """The symmetric cost family exists on the HIP backend only (the CPU test oracle does not know these kinds)."""
-    if getattr(mdl, "symmetric", False) and getattr(b, "name", "") != "hip":
+    """The symmetric cost family and the plaid edge-cut pair exist on the HIP backend only (the CPU test oracle does not know
+    these kinds)."""
+    if (getattr(mdl, "symmetric", False) or getattr(mdl, "hip_only", False)) and getattr(b, "name", "") != "hip":
         raise NotImplementedError(f"{type(mdl).__name__} is implemented by the HIP backend only, not by backend "
                                   f"'{getattr(b, 'name', type(b).__name__)}'")
 
@@ -355,11 +356,12 @@ def oracle_stripe(hint, mdl, A, Pi=None, *, backend=None) -> Oracle:
 
 
 def bound_stripe(A, K, mdl, Pi=None, *, backend=None):
-    """bound_stripe(A, K, [Pi], mdl): Pi only matters to the secondary connectivity model (Costs.jl:17-19)."""
+    """bound_stripe(A, K, [Pi], mdl): Pi only matters to the secondary models (Costs.jl:17-19; SecondaryConnectivityCosts.jl:21-31,
+    SecondaryEdgeCutCosts.jl:20-28)."""
     b = get_backend(backend)
     _need_hip(b, mdl)
     mm = mdl.marshal(w_table=A.n + 1)
-    if Pi is not None and isinstance(mdl, M.AffineSecondaryConnectivityModel):
+    if Pi is not None and isinstance(mdl, (M.AffineSecondaryConnectivityModel, M.AffineSecondaryEdgeCutModel)):
         rp, keep = _rowpart(Pi)
         rc, lo, hi = b.bound_stripe_pi(A, int(K), rp, mm)
     else:

@@ -14,6 +14,7 @@
 #include "model.hpp"
 #include "wavelet.hpp"
 #include "sym.hpp"
+#include "cut.hpp"
 
 namespace cpk {
 
@@ -308,10 +309,15 @@ int32_t run_bisect(cp_csr_s *A, int64_t K, const cp_model_t *mdl, const cp_rowpa
     const bool sym = model_is_sym(mdl->kind);
     if (sym) { sym_prepare(A, mdl, SH); memset(&OS, 0, sizeof(OS)); OS.M = HM.d; OS.n = A->n; OS.S = SH.d; }
     if (mdl->kind == CP_MODEL_CONNECTIVITY || mdl->kind == CP_MODEL_PRIMARY) { ensure_net_counter(A, net); O.has_net = 1; O.net = net.d; }
-    if (mdl->kind == CP_MODEL_PRIMARY || mdl->kind == CP_MODEL_SECONDARY) {
-        bool sec = mdl->kind == CP_MODEL_SECONDARY;
+    const bool cut = model_is_cut(mdl->kind);
+    CutOracleDev<TC> OC;
+    DBuf<int64_t> d_ppos;
+    if (mdl->kind == CP_MODEL_PRIMARY || mdl->kind == CP_MODEL_SECONDARY || cut) {
+        bool sec = mdl->kind == CP_MODEL_SECONDARY || mdl->kind == CP_MODEL_SECONDARY_EDGE_CUT;
         CP_REQUIRE(Pi && (Pi->asg || Pi->spl) && Pi->K >= 1, CP_EINVAL, "this cost model needs a row partition Pi");
-        CP_REQUIRE(!sec || (Pi->spl && K <= Pi->K), CP_EINVAL, "the secondary connectivity model needs a SplitPartition of the rows with >= K parts");
+        CP_REQUIRE(!sec || cut || (Pi->spl && K <= Pi->K), CP_EINVAL, "the secondary connectivity model needs a SplitPartition of the rows with >= K parts");
+        CP_REQUIRE(!sec || !cut || (Pi->spl && K <= Pi->K), CP_EINVAL, "the secondary edge-cut model needs a SplitPartition of the rows with >= K parts");
+        CP_REQUIRE(!cut || K <= Pi->K, CP_EINVAL, "the plaid edge-cut models are evaluated for parts 1..K of Pi");
         int64_t m = A->m, N = A->N, Kp = Pi->K;
         std::vector<int64_t> asg((size_t)(m > 0 ? m : 1), 1);
         if (Pi->asg) for (int64_t i = 0; i < m; i++) asg[(size_t)i] = Pi->asg[i];
@@ -324,16 +330,25 @@ int32_t run_bisect(cp_csr_s *A, int64_t K, const cp_model_t *mdl, const cp_rowpa
         CP_HIP(hipMemcpyAsync(d_pios.p, pios.data(), sizeof(int64_t) * (size_t)(Kp + 1), hipMemcpyHostToDevice, s));
         if (npr > 0) CP_HIP(hipMemcpyAsync(d_prm.p, prm.data(), sizeof(int64_t) * (size_t)npr, hipMemcpyHostToDevice, s));
         O.plaid = sec ? 2 : 1; O.pios = d_pios.p; O.prm = d_prm.p;
-        if (!sec) {
+        if (cut) {                                    // the partwise column pointer is the pin prefix: no counter
+            d_ppos.alloc((size_t)npr + 1);
+            CP_HIP(hipMemcpyAsync(d_ppos.p, ppos.data(), sizeof(int64_t) * (size_t)(npr + 1), hipMemcpyHostToDevice, s));
+        } else if (!sec) {
             rc = cp_csr_create(m, npr, N, ppos.data(), pidx.data(), A->device, &Ap.h);          // the partwise matrix and its net counter
             if (rc != CP_OK) return rc;
             ensure_net_counter(Ap.h, lcn);
             O.lcn = lcn.d; O.np = npr; O.ppos = Ap.h->pos.p;
-        } else {
+        }
+        if (sec) {
             d_spl2.alloc((size_t)Kp + 1);
             CP_HIP(hipMemcpyAsync(d_spl2.p, Pi->spl, sizeof(int64_t) * (size_t)(Kp + 1), hipMemcpyHostToDevice, s));
             ensure_links(A);
             O.spl = d_spl2.p; O.tpos = A->tpos.p;
+        }
+        if (cut) {
+            memset(&OC, 0, sizeof(OC));
+            OC.M = HM.d; OC.n = A->n; OC.secondary = sec ? 1 : 0; OC.pos = A->pos.p;
+            OC.pios = d_pios.p; OC.prm = d_prm.p; OC.ppos = d_ppos.p; OC.spl = O.spl; OC.tpos = O.tpos;
         }
         CP_HIP(hipStreamSynchronize(s));              // host staging vectors die at scope end
     }
@@ -341,7 +356,9 @@ int32_t run_bisect(cp_csr_s *A, int64_t K, const cp_model_t *mdl, const cp_rowpa
     int64_t *d_lo = buf.p, *d_hi = buf.p + (K + 1), *d_spl = buf.p + 2 * (K + 1), *d_out = buf.p + 3 * (K + 1), *d_np = buf.p + 4 * (K + 1);
     {
         ProfScope ps(PROF_BISECT, s, 0.0);
-        if (sym && by_index) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bisect_index<TC, SymOracleDev<TC>>), dim3(1), dim3(64), 0, s, OS, K, c_lo, c_hi, flip, d_lo, d_hi, d_spl, d_out, d_np);
+        if (cut && by_index) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bisect_index<TC, CutOracleDev<TC>>), dim3(1), dim3(64), 0, s, OC, K, c_lo, c_hi, flip, d_lo, d_hi, d_spl, d_out, d_np);
+        else if (cut) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bisect<CutOracleDev<TC>>), dim3(1), dim3(64), 0, s, OC, K, c_lo, c_hi, eps, flip, d_lo, d_hi, d_spl, d_out, d_np);
+        else if (sym && by_index) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bisect_index<TC, SymOracleDev<TC>>), dim3(1), dim3(64), 0, s, OS, K, c_lo, c_hi, flip, d_lo, d_hi, d_spl, d_out, d_np);
         else if (sym) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bisect<SymOracleDev<TC>>), dim3(1), dim3(64), 0, s, OS, K, c_lo, c_hi, eps, flip, d_lo, d_hi, d_spl, d_out, d_np);
         else if (by_index) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bisect_index<TC, OracleDev<TC>>), dim3(1), dim3(64), 0, s, O, K, c_lo, c_hi, flip, d_lo, d_hi, d_spl, d_out, d_np);
         else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bisect<OracleDev<TC>>), dim3(1), dim3(64), 0, s, O, K, c_lo, c_hi, eps, flip, d_lo, d_hi, d_spl, d_out, d_np);
@@ -425,7 +442,15 @@ static int32_t bisect_entry(cp_csr_t A, int64_t K, const cp_model_t *model, cons
         CP_REQUIRE(A && model && spl_out && K >= 1, CP_EINVAL, "bad argument");
         CP_HIP(hipSetDevice(A->device));
         int64_t li, hi; double lf, hf;
-        int32_t rc = cp_bound_stripe_pi(A, K, Pi, model, &li, &hi, &lf, &hf);
+        int32_t rc;
+        if (model->kind == CP_MODEL_SECONDARY_EDGE_CUT)       // the splitters pass the oracle: its own bound_stripe (SecondaryEdgeCutCosts.jl:40-57)
+            rc = with_cost_type(model->dtype, [&](auto tag) {
+                decltype(tag) lo = 0, hi2 = 0;
+                int32_t r = cut_bound_stripe<decltype(tag)>(A, K, Pi, model, true, &lo, &hi2);
+                lf = (double)lo; hf = (double)hi2;
+                return r;
+            });
+        else rc = cp_bound_stripe_pi(A, K, Pi, model, &li, &hi, &lf, &hf);
         if (rc != CP_OK) return rc;
         return with_cost_type(model->dtype, [&](auto tag) { return run_bisect<decltype(tag)>(A, K, model, Pi, lf, hf, eps, flip, spl_out, by_index); });
     });

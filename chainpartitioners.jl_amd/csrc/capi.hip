@@ -5,6 +5,7 @@
 #include "dp.hpp"
 #include "weight.hpp"
 #include "sym.hpp"
+#include "cut.hpp"
 #include <cmath>
 #include <memory>
 
@@ -65,7 +66,7 @@ __global__ void k_apply_model(int64_t nq, const int64_t *__restrict__ P, const i
 // ------------------------------------------------------------------ helpers
 static bool model_known(const cp_model_t *m)
 {
-    if (!m || m->kind < CP_MODEL_FEASIBLE || m->kind > CP_MODEL_SYM_EDGE_CUT) return false;
+    if (!m || m->kind < CP_MODEL_FEASIBLE || m->kind > CP_MODEL_SECONDARY_EDGE_CUT) return false;
     if (m->kind == CP_MODEL_POWER_WORK) return m->dtype == CP_F64;
     return m->dtype == CP_I64 || m->dtype == CP_F64;
 }
@@ -142,13 +143,14 @@ static int32_t oracle_eval_into(cp_csr_t A, const cp_model_t *model, const cp_ro
 // merged; fix_items: the (task, trip) items the merges were handed (every attempt of a layer: a dropped round lists none).
 // own_split_tiles: own tiles that streamed only their plane's variable link entries (layers that were not redone); gap_split_tiles: the
 // same for the tiles of the gap rounds, which own_split_tiles does not count.  overlap_isect: column intersections cp_pack_overlap computed.
-// bn_sym_layers: DP layers the valley search ran for the monotonized symmetric model.  kept: cp_set_option("poison", 1) starts a
+// bn_sym_layers: DP layers the valley search ran for the monotonized symmetric model.  cut_scan_layers: DP layers of the plaid edge-cut
+// models the prefix-min scan ran (plaid_cut.hip).  kept: cp_set_option("poison", 1) starts a
 // poison pass by zeroing the other counters and leaves this one.
 static const struct { const char *name; int64_t *var; bool kept; } g_stats[] = {
     {"spec_redo", &g_spec_redo, false}, {"poison_hits", &g_poison_hits, false}, {"fix_trips", &g_fix_trips, false},
     {"fix_edges", &g_fix_edges, false}, {"fix_items", &g_fix_items, false}, {"bn_sym_layers", &g_bn_sym_layers, true},
     {"own_split_tiles", &g_own_split_tiles, false}, {"gap_split_tiles", &g_gap_split_tiles, false},
-    {"overlap_isect", &g_overlap_isect, false},
+    {"overlap_isect", &g_overlap_isect, false}, {"cut_scan_layers", &g_cut_scan_layers, false},
 };
 static void stats_reset(bool all) { for (const auto &c : g_stats) if (all || !c.kept) *c.var = 0; }
 
@@ -396,6 +398,13 @@ int32_t cp_partition_dynamic(cp_csr_t A, int64_t K, int32_t combine, int32_t ord
             CP_REQUIRE(!constrained, CP_EUNSUPPORTED, "ConstrainedCost over a plaid connectivity model has no device path");
             return with_cost_type(model->dtype, [&](auto tag) { return run_plaid_dynamic<decltype(tag)>(A, K, combine, order, model, Pi, spl_out); });
         }
+        if (model_is_cut(model->kind)) {                                        // plaid_cut.hip: the prefix-min scan or the candidate sweep
+            CP_REQUIRE(!constrained, CP_EUNSUPPORTED, "ConstrainedCost over a plaid edge-cut model has no device path");
+            return with_cost_type(model->dtype, [&](auto tag) {
+                using TC = decltype(tag);
+                return run_cut_dynamic<TC>(A, K, combine, order, model, Pi, spl_out, nullptr, (TC *)nullptr);
+            });
+        }
         // the symmetric family: the O(n^2) sweep over the wavelet counters (dp_driver.hip); no constrained form
         CP_REQUIRE(!(constrained && model_is_sym(model->kind)), CP_EUNSUPPORTED, "ConstrainedCost over a symmetric cost model has no device path");
         if (constrained) {
@@ -422,10 +431,17 @@ int32_t cp_partition_dynamic(cp_csr_t A, int64_t K, int32_t combine, int32_t ord
 int32_t cp_dynamic_tables(cp_csr_t A, int64_t K, int32_t combine, const cp_model_t *model, const cp_rowpart_t *Pi,
                           int64_t *ptr_out, int64_t *cst_i64, double *cst_f64)
 {
-    (void)Pi;
     return guarded([&]() -> int32_t {
         CP_REQUIRE(A && ptr_out && model_known(model) && K >= 1, CP_EINVAL, "bad argument");
         CP_REQUIRE(combine == CP_COMBINE_SUM || combine == CP_COMBINE_MAX, CP_EINVAL, "bad combine");
+        if (model_is_cut(model->kind)) {                                        // (the only kinds here that look at Pi)
+            CP_HIP(hipSetDevice(A->device));
+            std::vector<int64_t> spl((size_t)K + 1);
+            return with_cost_type(model->dtype, [&](auto tag) {
+                using TC = decltype(tag);
+                return run_cut_dynamic<TC>(A, K, combine, CP_ORDER_SPLITTER, model, Pi, spl.data(), ptr_out, pick<TC>(cst_i64, cst_f64));
+            });
+        }
         CP_REQUIRE(model->kind == CP_MODEL_WORK || model->kind == CP_MODEL_CONNECTIVITY || model->kind == CP_MODEL_HYPEREDGE_CUT ||
                        model->kind == CP_MODEL_COLBLOCK || model->kind == CP_MODEL_POWER_WORK || model_is_sym(model->kind),
                    CP_EUNSUPPORTED, "model kind has no device DP path");
@@ -473,6 +489,7 @@ int32_t cp_oracle_eval(cp_csr_t A, const cp_model_t *model, const cp_rowpart_t *
             if (model->kind == CP_MODEL_PRIMARY || model->kind == CP_MODEL_SECONDARY) return run_plaid_eval<TC>(A, model, Pi, nq, j, jp, k, out);
             // stateful step oracle: evaluated in query order by one wave (seq.hip)
             if (model->kind == CP_MODEL_BLOCK) return run_seq_eval<TC>(A, model, Pi, nq, j, jp, k, out);
+            if (model_is_cut(model->kind)) return run_cut_eval<TC>(A, model, Pi, nq, j, jp, k, out);
             if (model_is_sym(model->kind)) return run_sym_eval<TC>(A, model, nq, j, jp, k, out);
             return run_oracle_eval<TC>(A, model, nq, j, jp, k, out);
         });
@@ -557,6 +574,11 @@ int32_t cp_bound_stripe(cp_csr_t A, int64_t K, const cp_model_t *model, int64_t 
                 cp[CP_P_NET] = std::min(P(3), P(4));
                 return cp_bound_stripe(A, K, &c, lo_i64, &dh, lo_f64, &dg);
             }
+            if (model->kind == CP_MODEL_PRIMARY_EDGE_CUT) {                            // PrimaryEdgeCutCosts.jl:28-39
+                int32_t rc = cut_bound_stripe<TC>(A, K, nullptr, model, false, lo, hi);
+                if (rc == CP_OK) also_f64(lo, hi, lo_f64, hi_f64);
+                return rc;
+            }
             const bool mono = model->kind == CP_MODEL_MONO_SYM_CONNECTIVITY;
             if (mono) {                                                                // MonotonizedSymmetricConnectivityCosts.jl:50-66
                 CP_REQUIRE(A->m == A->n, CP_EINVAL, "bound_stripe asserts m == n");
@@ -608,6 +630,17 @@ int32_t cp_bound_stripe(cp_csr_t A, int64_t K, const cp_model_t *model, int64_t 
 int32_t cp_bound_stripe_pi(cp_csr_t A, int64_t K, const cp_rowpart_t *Pi, const cp_model_t *model, int64_t *lo_i64, int64_t *hi_i64,
                            double *lo_f64, double *hi_f64)
 {
+    if (model && model->kind == CP_MODEL_SECONDARY_EDGE_CUT)                           // the model form, SecondaryEdgeCutCosts.jl:20-28
+        return guarded([&]() -> int32_t {
+            CP_REQUIRE(A && model_known(model) && K >= 1, CP_EINVAL, "bad argument");
+            return with_cost_type(model->dtype, [&](auto tag) -> int32_t {
+                using TC = decltype(tag);
+                TC *lo = pick<TC>(lo_i64, lo_f64), *hi = pick<TC>(hi_i64, hi_f64);
+                int32_t rc = cut_bound_stripe<TC>(A, K, Pi, model, false, lo, hi);
+                if (rc == CP_OK) also_f64(lo, hi, lo_f64, hi_f64);
+                return rc;
+            });
+        });
     if (!model || model->kind != CP_MODEL_SECONDARY) return cp_bound_stripe(A, K, model, lo_i64, hi_i64, lo_f64, hi_f64);
     return guarded([&]() -> int32_t {
         CP_REQUIRE(A && model_known(model) && K >= 1 && Pi && Pi->spl, CP_EINVAL, "bad argument");

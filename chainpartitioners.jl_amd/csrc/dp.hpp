@@ -88,6 +88,14 @@ int32_t run_seq_eval(cp_csr_s *A, const cp_model_t *mdl, const cp_rowpart_t *Pi,
                      const int64_t *k, TC *out);
 
 // plaid.hip: primary / secondary connectivity costs (need a row partition)
+// device copy of the row partition: owner (1-based part of every row) and the split vector (the secondary models); also plaid_cut.hip
+struct PlaidPart {
+    DBuf<int32_t> owner;
+    DBuf<int64_t> spl;
+    std::vector<int64_t> hspl;
+    int64_t K = 0;
+};
+void upload_part(cp_csr_s *A, const cp_rowpart_t *Pi, bool need_spl, PlaidPart &R);
 template <typename TC>
 int32_t run_plaid_eval(cp_csr_s *A, const cp_model_t *mdl, const cp_rowpart_t *Pi, int64_t nq, const int64_t *j, const int64_t *jp,
                        const int64_t *k, TC *out);

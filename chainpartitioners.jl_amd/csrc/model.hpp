@@ -155,6 +155,12 @@ inline bool model_exact_on(const cp_model_t *m, int64_t n, int64_t N, int64_t K)
             if (m->alpha_k) for (int64_t i = 0; i < m->n_alpha_k; i++) amax = std::max(amax, mag(((const int64_t *)m->alpha_k)[i]));
             bv = mag(m->p_i64[CP_P_VERTEX]); bp = mag(m->p_i64[CP_P_PIN]);
             bnet = std::max(mag(m->p_i64[3]), mag(m->p_i64[4]));
+        } else if (m->kind == CP_MODEL_PRIMARY_EDGE_CUT || m->kind == CP_MODEL_SECONDARY_EDGE_CUT) {
+            // every pin is a self pin or a cut pin: K*max|alpha| + n*|b_vertex| + N*max(|b_self_pin|, |b_cut_pin|)
+            amax = mag(m->p_i64[CP_P_ALPHA]);
+            if (m->alpha_k) for (int64_t i = 0; i < m->n_alpha_k; i++) amax = std::max(amax, mag(((const int64_t *)m->alpha_k)[i]));
+            bv = mag(m->p_i64[CP_P_VERTEX]);
+            bnet = std::max(mag(m->p_i64[CP_P_SELF_PIN]), mag(m->p_i64[CP_P_CUT_PIN]));
         } else {
             return false;
         }
@@ -163,6 +169,10 @@ inline bool model_exact_on(const cp_model_t *m, int64_t n, int64_t N, int64_t K)
     }
     double amax = std::fabs(m->p_f64[CP_P_ALPHA]);
     if (m->alpha_k) for (int64_t i = 0; i < m->n_alpha_k; i++) amax = std::max(amax, std::fabs(((const double *)m->alpha_k)[i]));
+    // (the edge-cut pair: this bounds the totals only; the prefix-min scan also forms W - S_k and asks for more -- cut_scan_exact, plaid_cut.hip)
+    if (m->kind == CP_MODEL_PRIMARY_EDGE_CUT || m->kind == CP_MODEL_SECONDARY_EDGE_CUT)
+        return amax * (double)(K > 0 ? K : 1) + std::fabs(m->p_f64[CP_P_VERTEX]) * (double)n +
+               std::max(std::fabs(m->p_f64[CP_P_SELF_PIN]), std::fabs(m->p_f64[CP_P_CUT_PIN])) * (double)N < 9007199254740992.0;
     const bool mono = m->kind == CP_MODEL_MONO_SYM_CONNECTIVITY;
     double bnet = mono ? std::fabs(m->p_f64[CP_P_DIA_NET]) : std::max(std::fabs(m->p_f64[3]), std::fabs(m->p_f64[4]));
     double bound = amax * (double)(K > 0 ? K : 1) + std::fabs(m->p_f64[CP_P_VERTEX]) * (double)n + std::fabs(m->p_f64[CP_P_PIN]) * (double)N + bnet * (double)(mono ? N + n : N);

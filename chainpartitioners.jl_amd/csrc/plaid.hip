@@ -66,15 +66,8 @@ __global__ void k_plaid_apply(int64_t nq, const int64_t *__restrict__ P, const i
     }
 }
 
-// device copy of the row partition: owner (1-based part of every row) and the split vector (secondary)
-struct PlaidPart {
-    DBuf<int32_t> owner;
-    DBuf<int64_t> spl;
-    std::vector<int64_t> hspl;
-    int64_t K = 0;
-};
-
-static void upload_part(cp_csr_s *A, const cp_rowpart_t *Pi, bool need_spl, PlaidPart &R)
+// device copy of the row partition (PlaidPart, dp.hpp)
+void upload_part(cp_csr_s *A, const cp_rowpart_t *Pi, bool need_spl, PlaidPart &R)
 {
     CP_REQUIRE(Pi && (Pi->asg || Pi->spl) && Pi->K >= 1, CP_EINVAL, "this cost model needs a row partition Pi");
     CP_REQUIRE(!need_spl || Pi->spl, CP_EINVAL, "the secondary connectivity model needs a SplitPartition of the rows");

@@ -17,6 +17,8 @@ Mirrors (file:line under /root/reference/src):
   AffineSymmetricConnectivityModel              SymmetricConnectivityCosts.jl:5-19
   AffineMonotonizedSymmetricConnectivityModel   MonotonizedSymmetricConnectivityCosts.jl:5-33
   AffineSymmetricEdgeCutModel                   SymmetricEdgeCutCosts.jl:5-18
+  AffinePrimaryEdgeCutModel                     PrimaryEdgeCutCosts.jl:5-18
+  AffineSecondaryEdgeCutModel                   SecondaryEdgeCutCosts.jl:5-18
 
 Julia's constructors `promote` all parameters to one element type (ConnectivityCosts.jl:14-16):
 all-int arguments give an Int64 model, any float gives Float64.  Closures (e.g.
@@ -32,6 +34,7 @@ CP_I64, CP_F64 = 0, 1
  CP_MODEL_COLBLOCK, CP_MODEL_BLOCK, CP_MODEL_VERTEX_COUNT, CP_MODEL_POWER_WORK, CP_MODEL_PRIMARY,
  CP_MODEL_SECONDARY) = range(10)
 CP_MODEL_SYM_CONNECTIVITY, CP_MODEL_MONO_SYM_CONNECTIVITY, CP_MODEL_SYM_EDGE_CUT = 10, 11, 12
+CP_MODEL_PRIMARY_EDGE_CUT, CP_MODEL_SECONDARY_EDGE_CUT = 13, 14
 CP_COMBINE_SUM, CP_COMBINE_MAX = 0, 1
 CP_ORDER_SPLITTER, CP_ORDER_CHUNKER = 0, 1
 CP_MAX_R = 4
@@ -281,6 +284,30 @@ class AffineSymmetricEdgeCutModel(_Model):
 
     def __call__(self, n_vertices, n_self_pins, n_cut_pins, k=None):
         return self.alpha + n_vertices * self.beta_vertex + n_self_pins * self.beta_self_pin + n_cut_pins * self.beta_cut_pin
+
+
+# ---------------------------------------------------------------- the plaid edge-cut pair (HIP backend only)
+class AffinePrimaryEdgeCutModel(_Model):
+    """PrimaryEdgeCutCosts.jl:5-18: alpha + nv*beta_vertex + self*beta_self_pin + cut*beta_cut_pin, the pins of a column part split
+    by the row partition Pi into self pins (row owned by the same part number) and cut pins.  Needs Pi (any partition of the
+    rows).  `alpha_k` gives a per-part alpha[k]."""
+    kind = CP_MODEL_PRIMARY_EDGE_CUT
+    needs_rowpart = True
+    hip_only = True
+    fields = ("alpha", "beta_vertex", "beta_self_pin", "beta_cut_pin")
+
+    def __init__(self, alpha=0, beta_vertex=0, beta_self_pin=0, beta_cut_pin=0, *, alpha_k=None):
+        self._set(alpha, beta_vertex, beta_self_pin, beta_cut_pin, alpha_k=alpha_k)
+
+    def __call__(self, n_vertices, n_self_pins, n_cut_pins, k=None):
+        a = self.alpha if self.alpha_k is None or k is None else self.alpha_k[k - 1]
+        return a + n_vertices * self.beta_vertex + n_self_pins * self.beta_self_pin + n_cut_pins * self.beta_cut_pin
+
+
+class AffineSecondaryEdgeCutModel(AffinePrimaryEdgeCutModel):
+    """SecondaryEdgeCutCosts.jl:5-18: the cost of giving a range of columns to part k of the SplitPartition Pi of the rows; the
+    vertices and pins are those of the part of Pi, the self pins the entries of the range in its rows."""
+    kind = CP_MODEL_SECONDARY_EDGE_CUT
 
 
 def _tabulate(f, lo, hi, npdt):

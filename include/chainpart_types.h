@@ -17,6 +17,8 @@
  *   AffineSymmetricConnectivityModel            SymmetricConnectivityCosts.jl:5-19
  *   AffineMonotonizedSymmetricConnectivityModel MonotonizedSymmetricConnectivityCosts.jl:5-33
  *   AffineSymmetricEdgeCutModel                 SymmetricEdgeCutCosts.jl:5-18
+ *   AffinePrimaryEdgeCutModel                   PrimaryEdgeCutCosts.jl:5-18
+ *   AffineSecondaryEdgeCutModel                 SecondaryEdgeCutCosts.jl:5-18
  */
 #ifndef CHAINPART_TYPES_H
 #define CHAINPART_TYPES_H
@@ -65,6 +67,13 @@ extern "C" {
                                               max(deg - Delta_pins, 0) over the columns; Delta_pins (p[4]) integer-valued */
 #define CP_MODEL_SYM_EDGE_CUT          12  /* alpha + nv*b_vertex + selfpin(j,j')*b_self_pin + (np - selfpin)*b_cut_pin */
 
+/* the plaid edge-cut pair: the pins of a part split by the row partition Pi into self pins (row owned by the same part number)
+ * and cut pins; parameters in the slots of the symmetric edge cut; HIP backend only */
+#define CP_MODEL_PRIMARY_EDGE_CUT      13  /* alpha + nv*b_vertex + self*b_self_pin + (np - self)*b_cut_pin of the column range [j, j')
+                                              as part k (PrimaryEdgeCutCosts.jl:5-18, :51-57); Pi: any partition of the rows */
+#define CP_MODEL_SECONDARY_EDGE_CUT    14  /* the same formula with nv, np the vertices / pins of part k of the SplitPartition Pi of the
+                                              ROWS and self the entries of [j, j') in those rows (SecondaryEdgeCutCosts.jl:5-18, :78-85) */
+
 /* parameter slots of p_i64 / p_f64 */
 #define CP_P_ALPHA      0
 #define CP_P_VERTEX     1
@@ -78,7 +87,7 @@ extern "C" {
 #define CP_P_OVER_PIN   2   /* monotonized symmetric connectivity */
 #define CP_P_DIA_NET    3
 #define CP_P_DELTA_PINS 4
-#define CP_P_SELF_PIN   2   /* symmetric edge cut */
+#define CP_P_SELF_PIN   2   /* symmetric / primary / secondary edge cut */
 #define CP_P_CUT_PIN    3
 
 #define CP_MAX_R 4
