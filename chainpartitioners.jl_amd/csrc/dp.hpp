@@ -125,7 +125,7 @@ void dp_fix_merge_test(const cp_model_t *model, int64_t ntask, const int64_t *to
                        const int32_t *plane, int64_t n, int reps, int32_t *p_out, int32_t *nn_out, int32_t *nl_out, int64_t *res);      // dp_total.hip: cp_test_fix_merge
 extern int64_t g_fix_trips, g_fix_edges;       // what the own-tile merges met since the last reset (tests): see RoundCounts::n_trips / n_edge
 extern int64_t g_fix_items;                    // ... and the (task, trip) items they merged, attempts that were redone included (RoundCounts::n_items)
-extern int64_t g_opt_leaf;                     // 1: the rounds tau < 6 of an unconstrained layer are one leaf pass (dp_leaf.inc)
+extern int64_t g_opt_leaf;                     // 1: the rounds tau < 6 of an unconstrained layer are one leaf pass (dp_total_leaf.hip)
 extern int64_t g_opt_block_tables;             // 1: the leaf pass also stores the per-block winners (cp_dp_block_tables)
 extern int64_t g_opt_ra_cache;                 // 1: round A from counts computed once per partition
 extern int64_t g_opt_fixed_point;              // 1: layers after a layer that reproduced its input row are copied (run_dynamic)

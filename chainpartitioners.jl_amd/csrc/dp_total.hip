@@ -30,62 +30,10 @@
 //  * width-windowed layers (candidates max(0, r - w) <= p <= r: the ConstrainedCost DP, DynamicSplitter.jl:206-258) run the same
 //    kernels on another tiling of the candidates: every row has a task in every plane b <= floor(log2 w) -- standard, common
 //    and mirrored blocks, see struct Geo below and DESIGN.md section 4b.
-#include "csr.hpp"
-#include "model.hpp"
-#include "dp.hpp"
-#include <algorithm>
+#include "dp_total.hpp"
+#include <optional>
 
 namespace cpk {
-
-// The O(n log^2 n) scheme only admits the affine Work / Connectivity / HyperedgeCut models (fast_total_ok): its kernels evaluate
-// costs through this three-way form, so the block-cost tables and pow() of the general dm_apply stay out of their registers.
-template <typename TC>
-__device__ __forceinline__ TC dm_apply_affine(const DevModel<TC> &m, TC alpha, int64_t nv, int64_t np, int64_t nn, int64_t nl)
-{
-    TC v = cadd(cadd(alpha, cmulc(nv, m.p[CP_P_VERTEX])), cmulc(np, m.p[CP_P_PIN]));       // (left to right, as the reference sums)
-    if (m.kind == CP_MODEL_CONNECTIVITY) return cadd(v, cmulc(nn, m.p[CP_P_NET]));
-    if (m.kind == CP_MODEL_HYPEREDGE_CUT) return cadd(cadd(v, cmulc(nl, m.p[CP_P_SELF_NET])), cmulc(nn - nl, m.p[CP_P_CUT_NET]));
-    return v;
-}
-#define dm_apply dm_apply_affine
-
-constexpr int LT = 256;          // steps per tile (one wave owns one tile)
-constexpr int NBMAX = 31;        // bit planes (n < 2^30)
-constexpr int SPLIT_BMIN = 8;     // own_split (SplitLinks): first plane whose own tiles stream only the plane's variable link entries (tiles are 256 columns: from here on a tile lies inside one block)
-constexpr int SPLIT_NB = NBMAX - SPLIT_BMIN;      // ... and their number at most
-
-// Plane arrays (opt / nnopt / nlopt / cr / crl) hold row r of a bit plane at slot prow(r): rows are grouped by their level
-// ctz(r) -- the rows one round reads and writes are then CONTIGUOUS in every plane (in row-major order they sit 2^(tau+1)
-// entries apart and every round drags whole planes through HBM).  #rows in [1, n] with ctz < t is n - (n >> t).
-__device__ __forceinline__ int64_t prow(int64_t r, int64_t n)
-{
-    int t = __ffsll((long long)r) - 1;
-    return (n - (n >> t)) + (r >> (t + 1));
-}
-#define PR(x) prow((x), n1 - 1)
-
-// Width-windowed layers (the ConstrainedCost DP, DynamicSplitter.jl:206-258 with a VertexCount weight; executable spec:
-// tests/dc_model.py layer_windowed): candidates of row r are max(0, r - w) <= p <= r.  With s = floor(log2 w), S = 2^s, every row
-// has a task in EVERY plane b <= s:
-//   b < s, bit b of r set   : the standard Fenwick block [r_b - 2^b, r_b)
-//   b == s                  : the common block [rho - w + S - 1, rho), rho = r with the bits below s cleared
-//   b < s, bit b of r clear : the mirrored block [rho + 2^b - 1 - w, rho + 2^(b+1) - 1 - w), rho = r with the bits <= b cleared
-// (clamped at column 0).  The rows sharing a block are always the aligned block of 2^b rows holding r -- full rectangles again.
-struct Geo { int32_t win, s; int64_t w; };
-
-// candidates [cs, ce) of row r in plane b; false: the row has no task in this plane (or the block is empty)
-__host__ __device__ __forceinline__ bool geo_block(const Geo &G, int64_t r, int b, int64_t &cs, int64_t &ce)
-{
-    const int64_t lo = (r >> b) << b;
-    if (!G.win) { cs = lo - ((int64_t)1 << b); ce = lo; return (r >> b) & 1; }
-    if (b > G.s) return false;
-    if (b == G.s) { cs = lo - G.w + ((int64_t)1 << b) - 1; ce = lo; }
-    else if ((r >> b) & 1) { cs = lo - ((int64_t)1 << b); ce = lo; }
-    else { cs = lo + ((int64_t)1 << b) - 1 - G.w; ce = cs + ((int64_t)1 << b); }
-    if (cs < 0) cs = 0;
-    if (ce < 0) ce = 0;
-    return ce > cs;
-}
 
 struct RoundDesc {
     int32_t isA, tau, nbits, nextra;
@@ -102,21 +50,6 @@ struct RoundDesc {
     int32_t nlast, last_b[31];
     int32_t skip_std, skip_mir; // windowed round A: the standard / mirrored heads (bit b of the row set / clear, b < s) come from the cached counts
     int32_t fin_stamp;          // a cell of the `fin` plane is set iff it holds this layer's stamp (1 .. 255: the plane is cleared every 255 layers, not every layer)
-};
-
-// Per-round counters, on the device (one record per round, kept for the whole layer).  Kernels read their loop bounds from
-// here, so the host can enqueue a whole layer without waiting for a count to come back (dp_total_layer).
-struct RoundCounts {
-    int32_t n_open, n_fix;            // work lists of k_span_short (tiles of long spans)
-    int32_t nlong, nown;              // flattened tasks / tasks with tiles of their own (k_setup_short)
-    unsigned long long own_steps;     // steps of the latter
-    int64_t T, NT;                    // flattened steps / own tiles (scan totals)
-    int32_t ntile, err;               // cdiv(T, LT); 1: a buffer sized from the prediction is too small (the layer is redone)
-    int32_t n_items, _pad;            // (task, trip) items of the own-tiled tasks of more than FIX_SERIAL tiles (k_own_map -> k_fix_own)
-    int32_t n_glong, n_gslots;        // gap tasks of more than GAPSEG tiles and their segment slots (k_gap_finish -> k_gap_seg)
-    int32_t n_gslow, n_sslow;         // work items of k_gap_finish / k_gap_seg that met a tile with more than SMAX specials (redone by the SLOW variants)
-    int32_t n_split, _pad2;           // own tiles that stream only their plane's variable link entries, where a launch mixes them with others (k_own_map, split == 2)
-    int32_t n_trips, n_edge;          // what the merge met (cp_get_stat, tests): tasks of more than one trip (folded by k_fix_own); bit 0 / 1 / 2: a task of 1 / FIX_SERIAL / FIX_SERIAL + 1 tiles
 };
 
 __device__ __forceinline__ void decode_task(const RoundDesc &R, int64_t t, int64_t &r, int &b)
@@ -172,7 +105,7 @@ __global__ void __launch_bounds__(256) k_rpass_small(int tau, int nbits, int64_t
     int64_t n1 = n + 1, rL = r - ((int64_t)1 << tau);
     int32_t thr[NB], cnt[NB];
     uint32_t used = 0;                                         // planes with a set bit somewhere in the wave (uniform)
-    int64_t prL = live ? PR(rL) : 0;
+    int64_t prL = live ? prow((rL), n1 - 1) : 0;
     // all threshold loads are issued back to back (a lane without bit b reads a valid dummy slot): one memory latency, not 23
 #pragma unroll
     for (int b = 0; b < NB; b++) {
@@ -247,7 +180,7 @@ __global__ void __launch_bounds__(256) k_rpass_small(int tau, int nbits, int64_t
     if (!live) return;
 #pragma unroll
     for (int b = 0; b < NB; b++)
-        if (b > tau && b < nbits && (allp || ((r >> b) & 1))) cr[(int64_t)b * n1 + PR(r)] = cnt[b];
+        if (b > tau && b < nbits && (allp || ((r >> b) & 1))) cr[(int64_t)b * n1 + prow((r), n1 - 1)] = cnt[b];
 }
 
 // Larger ranges: one wave per (row, chunk of CH columns); coalesced 64-entry loads.  The row -- hence every threshold -- is
@@ -273,7 +206,7 @@ __global__ void __launch_bounds__(64 * WPB) k_rpass_wave(int tau, int nbits, int
     int64_t n1 = n + 1, rL = r - ((int64_t)1 << tau);
     int64_t c0 = rL + (int64_t)ck * ch_cols, c1 = c0 + ch_cols;
     if (c1 > r) c1 = r;
-    int64_t prL = PR(rL);
+    int64_t prL = prow((rL), n1 - 1);
     // planes of this row (wave-uniform).  Lane b holds plane b: it fetches the plane's threshold (ONE vector memory instruction
     // for the row -- a uniform-address load per plane cost a dozen), keeps its count and stores it at the end.  The counting
     // loop walks the set bits of `act`: v_readlane hands the threshold to the scalar side, a plane's count of 64 entries is one
@@ -333,8 +266,8 @@ __global__ void __launch_bounds__(64 * WPB) k_rpass_wave(int tau, int nbits, int
         }
     }
     if (mine) {
-        if (chunks_per_row == WPB) cr[(int64_t)lane * n1 + PR(r)] = outv;
-        else atomicAdd(&cr[(int64_t)lane * n1 + PR(r)], outv);
+        if (chunks_per_row == WPB) cr[(int64_t)lane * n1 + prow((r), n1 - 1)] = outv;
+        else atomicAdd(&cr[(int64_t)lane * n1 + prow((r), n1 - 1)], outv);
     }
 }
 
@@ -385,17 +318,17 @@ __global__ void __launch_bounds__(256) k_setup(RoundDesc R, const int32_t *__res
     int64_t r; int b;
     decode_task(R, t, r, b);
     int64_t n1 = R.n + 1;
-    if (zero_cr_only) { cr[(int64_t)b * n1 + PR(r)] = 0; if (crl) crl[(int64_t)b * n1 + PR(r)] = 0; return; }
+    if (zero_cr_only) { cr[(int64_t)b * n1 + prow((r), n1 - 1)] = 0; if (crl) crl[(int64_t)b * n1 + prow((r), n1 - 1)] = 0; return; }
     int64_t B, a, S0, S0l = 0;
     if (R.isA) {
         B = r; a = r - ((int64_t)1 << b); S0 = 0;           // (zero_cr_only is the only use of this kernel in round A)
     } else {
         int64_t rb = (r >> b) << b;
         int64_t rL = r - ((int64_t)1 << R.tau), rR = r + ((int64_t)1 << R.tau);
-        B = opt[(int64_t)b * n1 + PR(rL)];
-        S0 = (int64_t)nnopt[(int64_t)b * n1 + PR(rL)] + cr[(int64_t)b * n1 + PR(r)];
-        if (tS0l) S0l = (int64_t)nlopt[(int64_t)b * n1 + PR(rL)] + crl[(int64_t)b * n1 + PR(r)];
-        a = (rR - rb) < ((int64_t)1 << b) ? (int64_t)opt[(int64_t)b * n1 + PR(rR <= R.n ? rR : R.n)] : rb - ((int64_t)1 << b);
+        B = opt[(int64_t)b * n1 + prow((rL), n1 - 1)];
+        S0 = (int64_t)nnopt[(int64_t)b * n1 + prow((rL), n1 - 1)] + cr[(int64_t)b * n1 + prow((r), n1 - 1)];
+        if (tS0l) S0l = (int64_t)nlopt[(int64_t)b * n1 + prow((rL), n1 - 1)] + crl[(int64_t)b * n1 + prow((r), n1 - 1)];
+        a = (rR - rb) < ((int64_t)1 << b) ? (int64_t)opt[(int64_t)b * n1 + prow((rR <= R.n ? rR : R.n), n1 - 1)] : rb - ((int64_t)1 << b);
         if (a > B) a = B;          // cannot happen for an inverse-Monge cost; keeps every task well-formed
     }
     tdesc[t] = make_int4((int32_t)B, (int32_t)S0, (int32_t)r, pos32[r]);      // one 16-byte record per task
@@ -405,9 +338,6 @@ __global__ void __launch_bounds__(256) k_setup(RoundDesc R, const int32_t *__res
 }
 
 // ------------------------------------------------------------------ wave-level segmented scans (64 lanes)
-template <typename TC, bool HYP> struct Best;
-template <typename TC> struct Best<TC, false> { TC v; int32_t p; int32_t nn; };                         // 16 bytes
-template <typename TC> struct Best<TC, true> { TC v; int32_t p; int32_t nn; int32_t nl; int32_t _pad; };
 template <typename TC> __device__ __forceinline__ void best_clear(Best<TC, false> &b) { b.v = (TC)0; b.p = -1; b.nn = 0; }
 template <typename TC> __device__ __forceinline__ void best_clear(Best<TC, true> &b) { b.v = (TC)0; b.p = -1; b.nn = 0; b.nl = 0; b._pad = 0; }
 template <typename TC> __device__ __forceinline__ int32_t best_nl(const Best<TC, false> &) { return 0; }
@@ -434,19 +364,6 @@ __device__ __forceinline__ Best<TC, HYP> better(const Best<TC, HYP> a, const Bes
     const bool tb = a.p < 0 || (b.p >= 0 && b.v < a.v);
     return best_sel<TC>(tb, a, b);
 }
-
-__device__ __forceinline__ int64_t shfl_up64(int64_t v, int o)
-{
-    int lo = __shfl_up((int)(v & 0xffffffffll), o), hi = __shfl_up((int)(v >> 32), o);
-    return ((int64_t)hi << 32) | (uint32_t)lo;
-}
-__device__ __forceinline__ double shfl_up64(double v, int o) { return __longlong_as_double((long long)shfl_up64((int64_t)__double_as_longlong(v), o)); }
-__device__ __forceinline__ int64_t shfl64(int64_t v, int src)
-{
-    int lo = __shfl((int)(v & 0xffffffffll), src), hi = __shfl((int)(v >> 32), src);
-    return ((int64_t)hi << 32) | (uint32_t)lo;
-}
-__device__ __forceinline__ double shfl64(double v, int src) { return __longlong_as_double((long long)shfl64((int64_t)__double_as_longlong(v), src)); }
 
 // inclusive segmented sum: v = sum from the last head at or before this lane (or lane 0), f = "a head lies in [0, lane]"
 __device__ __forceinline__ void wave_segsum(int32_t &v, int &f, int lane)
@@ -559,10 +476,10 @@ __global__ void __launch_bounds__(1024) k_setup_short(RoundDesc R, int32_t *__re
             if (ce != r) { S0 = anch[R.aoff[b] + (r >> (b + 1))]; if (HYP) S0l = anch2[R.aoff[b] + (r >> (b + 1))]; }
         } else {
             const int64_t rL = r - ((int64_t)1 << R.tau), rR = r + ((int64_t)1 << R.tau), rect_hi = ((r >> b) + 1) << b;
-            B = opt[(int64_t)b * n1 + PR(rL)];
-            S0 = (int64_t)nnopt[(int64_t)b * n1 + PR(rL)] + cr[(int64_t)b * n1 + PR(r)];
-            if (HYP) S0l = (int64_t)nlopt[(int64_t)b * n1 + PR(rL)] + crl[(int64_t)b * n1 + PR(r)];
-            a = (rR < rect_hi && rR <= R.n) ? (int64_t)opt[(int64_t)b * n1 + PR(rR)] : cs;
+            B = opt[(int64_t)b * n1 + prow((rL), n1 - 1)];
+            S0 = (int64_t)nnopt[(int64_t)b * n1 + prow((rL), n1 - 1)] + cr[(int64_t)b * n1 + prow((r), n1 - 1)];
+            if (HYP) S0l = (int64_t)nlopt[(int64_t)b * n1 + prow((rL), n1 - 1)] + crl[(int64_t)b * n1 + prow((r), n1 - 1)];
+            a = (rR < rect_hi && rR <= R.n) ? (int64_t)opt[(int64_t)b * n1 + prow((rR), n1 - 1)] : cs;
             if (a > B) a = B;
         }
     }
@@ -576,12 +493,12 @@ __global__ void __launch_bounds__(1024) k_setup_short(RoundDesc R, int32_t *__re
         } else {
             int64_t rb = (r >> b) << b;
             int64_t rL = r - ((int64_t)1 << R.tau), rR = r + ((int64_t)1 << R.tau);
-            B = opt[(int64_t)b * n1 + PR(rL)];
-            S0 = (int64_t)nnopt[(int64_t)b * n1 + PR(rL)] + cr[(int64_t)b * n1 + PR(r)];
-            if (HYP) S0l = (int64_t)nlopt[(int64_t)b * n1 + PR(rL)] + crl[(int64_t)b * n1 + PR(r)];
+            B = opt[(int64_t)b * n1 + prow((rL), n1 - 1)];
+            S0 = (int64_t)nnopt[(int64_t)b * n1 + prow((rL), n1 - 1)] + cr[(int64_t)b * n1 + prow((r), n1 - 1)];
+            if (HYP) S0l = (int64_t)nlopt[(int64_t)b * n1 + prow((rL), n1 - 1)] + crl[(int64_t)b * n1 + prow((r), n1 - 1)];
             // left end of the range: the winner of the right neighbour -- or, where that lies beyond the matrix, of the last
             // row n (same rectangle; known since round A); the block start for the last row of a rectangle
-            a = (rR - rb) < ((int64_t)1 << b) ? (int64_t)opt[(int64_t)b * n1 + PR(rR <= R.n ? rR : R.n)] : rb - ((int64_t)1 << b);
+            a = (rR - rb) < ((int64_t)1 << b) ? (int64_t)opt[(int64_t)b * n1 + prow((rR <= R.n ? rR : R.n), n1 - 1)] : rb - ((int64_t)1 << b);
             if (a > B) a = B;          // cannot happen for an inverse-Monge cost; keeps every task well-formed
         }
     }
@@ -632,7 +549,7 @@ __global__ void __launch_bounds__(1024) k_setup_short(RoundDesc R, int32_t *__re
     // the short tasks are finished by their lanes -- between the two barriers, while the list positions are on their way
     if (is_short) {
         const int64_t n1 = R.n + 1, L = 1 + (B - a);
-        int64_t rw = (int64_t)b * n1 + PR(r);
+        int64_t rw = (int64_t)b * n1 + prow((r), n1 - 1);
         if (L == 1 && !R.isA) {                  // one candidate: nothing to compare
             opt[rw] = (int32_t)B; nnopt[rw] = (int32_t)S0; if (HYP) nlopt[rw] = (int32_t)S0l;
         } else {
@@ -659,7 +576,7 @@ __global__ void __launch_bounds__(1024) k_setup_short(RoundDesc R, int32_t *__re
                     if (HYP) for (int32_t q = fp; q < fq; q++) nl += (flast[q] < rr);
                 }
                 if (!(i == 0 && R.isA)) {        // (round A: p = r is not a candidate)
-                    TC fv = dm_apply(M, alpha, r - p, (int64_t)(posr - pp), nn, nl);
+                    TC fv = dm_apply_affine(M, alpha, r - p, (int64_t)(posr - pp), nn, nl);
                     Best<TC, HYP> c; best_clear(c); c.v = cadd(wp, fv); c.p = (int32_t)p; c.nn = (int32_t)nn; best_set_nl(c, (int32_t)nl);
                     best = better(best, c);
                 }
@@ -817,7 +734,6 @@ __device__ __forceinline__ int32_t coop_count(const int32_t *__restrict__ arr, i
 // (Tried: the link values in 3 bytes (n < 2^24), a 12-byte load and six vector instructions to unpack four entries -- 19 % fewer
 //  bytes per step, and k_lpass_own 9 % SLOWER (254 vs 232 ms per partition): at 0.8 of the HBM roofline the kernel has no vector
 //  issue slots to spare.)
-constexpr int SMAX = 31;
 template <bool GE, bool DET = false>
 __device__ __forceinline__ void interior_stream(const int32_t *__restrict__ arr, const int32_t *__restrict__ cpos, int32_t p_first, int32_t tl,
                                                 int32_t thr, int lane, int32_t acc[4], int32_t sk[4], int head = 0, int32_t sp_lo = 0, int32_t sp_hi = 0,
@@ -941,9 +857,6 @@ __device__ __forceinline__ void interior_stream(const int32_t *__restrict__ arr,
 // items (outside the gap rounds): the work list of the merge, k_fix_own -- one item {task, first tile} per trip of FIX_TRIP tiles of
 // every task of more than FIX_SERIAL tiles, appended by the trip's first tile (a wave-aggregated atomic on rc->n_items; a dropped
 // round walks no tiles and lists nothing); item_of[that tile] = the item's index, by which the merge finds a task's trips in order.
-constexpr int FIX_SERIAL = 16;       // tasks of up to FIX_SERIAL tiles are merged by one lane
-constexpr int FIX_U = 8;             // consecutive tiles per lane and trip of k_fix_own
-constexpr int FIX_TRIP = 256 * FIX_U;
 __global__ void __launch_bounds__(256) k_own_map(RoundCounts *__restrict__ rc, const int64_t *__restrict__ toffs, const int4 *__restrict__ tdesc,
                                                  const int32_t *__restrict__ rlen, int4 *__restrict__ rec, int32_t *__restrict__ tile_task,
                                                  const uint8_t *__restrict__ tb, int32_t *__restrict__ gap_hi, int tau, int64_t n, int blk,
@@ -1132,7 +1045,7 @@ __global__ void __launch_bounds__(256) k_lpass_own(int isA, const RoundCounts *_
         best_clear(cand[k]);
         if (e <= tl && !(head && isA && e == 0)) {     // round A: the head element p = r is not a candidate
             int32_t p = rec.x - e;
-            TC fv = dm_apply(M, alpha, (int64_t)(rec.y - p), (int64_t)(rec.z - sk[k]), (int64_t)acc[k], (int64_t)acc2[k]);
+            TC fv = dm_apply_affine(M, alpha, (int64_t)(rec.y - p), (int64_t)(rec.z - sk[k]), (int64_t)acc[k], (int64_t)acc2[k]);
             cand[k].v = cadd(wv[k], fv); cand[k].p = p; cand[k].nn = acc[k]; best_set_nl(cand[k], acc2[k]);
         }
     }
@@ -1252,14 +1165,6 @@ struct GapCtx {
     int blk;                    // the tile geometry (own_tile_geo)
 };
 
-// wave-uniform lane index: one v_readlane instead of a ds_bpermute
-__device__ __forceinline__ int32_t rdl(int32_t v, int src) { return __builtin_amdgcn_readlane(v, src); }
-__device__ __forceinline__ int64_t rdl64(int64_t v, int src)
-{
-    return ((int64_t)__builtin_amdgcn_readlane((int)(v >> 32), src) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(v & 0xffffffffll), src);
-}
-__device__ __forceinline__ double rdl64(double v, int src) { return __longlong_as_double((long long)rdl64((int64_t)__double_as_longlong(v), src)); }
-
 // the tiles [ka, kz) of a task (first tile k0, head B, L steps, row r) walked for NR x 64 rows of the wave (lane l holds the rows
 // rr[0 .. NR-1], one per 64-row chunk: the tile records are fetched once for all of them): the winners so far (bv, bp, bl, bl2)
 // and the specials the rows count so far (cum, cum2) are carried in and out
@@ -1313,7 +1218,7 @@ __device__ __forceinline__ bool gap_walk(const GapCtx<TC, HYP> &C, const DevMode
 #pragma unroll
                     for (int u = 0; u < NR; u++) {
                         int32_t lc = d.nn + base + cum[u], lc2 = HYP ? best_nl(d) + base2 + cum2[u] : 0;
-                        TC v = cadd(d.v, dm_apply(M, (TC)0, (int64_t)0, (int64_t)0, (int64_t)(base + cum[u]), (int64_t)(base2 + cum2[u])));
+                        TC v = cadd(d.v, dm_apply_affine(M, (TC)0, (int64_t)0, (int64_t)0, (int64_t)(base + cum[u]), (int64_t)(base2 + cum2[u])));
                         if (bp[u] < 0 || v < bv[u]) { bv[u] = v; bp[u] = d.p; bl[u] = lc; bl2[u] = lc2; }
                     }
                 }
@@ -1375,7 +1280,7 @@ __device__ __forceinline__ bool gap_walk(const GapCtx<TC, HYP> &C, const DevMode
 #pragma unroll
             for (int u = 0; u < NR; u++) {
                 int32_t lc = base + cum[u] + run[u], lc2 = base2 + cum2[u] + run2[u];
-                TC v = cadd(wp, dm_apply(M, alpha, (int64_t)(r - p), (int64_t)(posr - st), (int64_t)lc, (int64_t)lc2));      // (the task's row: the rows' values differ by a row-only term)
+                TC v = cadd(wp, dm_apply_affine(M, alpha, (int64_t)(r - p), (int64_t)(posr - st), (int64_t)lc, (int64_t)lc2));      // (the task's row: the rows' values differ by a row-only term)
                 if (bp[u] < 0 || v < bv[u]) { bv[u] = v; bp[u] = p; bl[u] = lc; bl2[u] = lc2; }
             }
         }
@@ -1408,8 +1313,6 @@ __device__ __forceinline__ GapRows gap_rows(int tau, int ck, int32_t r, int b, i
     g.rcmp = g.valid ? g.rr : INT32_MAX;                    // an invalid lane counts nothing
     return g;
 }
-
-constexpr int GAPSEG = 16;      // tiles one wave walks; longer tasks are walked by several waves (k_gap_seg) and merged (k_gap_merge)
 
 template <typename TC, bool HYP>
 struct GapSegRec { TC v; int32_t p, l, l2, cum, cum2, _pad; };
@@ -1462,7 +1365,7 @@ __global__ void __launch_bounds__(256, 4) k_gap_finish(int tau, int nchunk, Roun
                 if (HYP) Rr2[u] = gap_right_counts<true>(lpos, lfirst, g[0].rL, ck0 + u, B, (int32_t)n, lane);
             }
         }
-        const int64_t rwL = (int64_t)b * n1 + PR((int64_t)g[0].rL);
+        const int64_t rwL = (int64_t)b * n1 + prow(((int64_t)g[0].rL), n1 - 1);
         const int32_t anchor = nnopt[rwL], anchor2 = HYP ? nlopt[rwL] : 0;
         TC bv[NR]; int32_t bp[NR], bl[NR], bl2[NR], cum[NR], cum2[NR];
 #pragma unroll
@@ -1474,7 +1377,7 @@ __global__ void __launch_bounds__(256, 4) k_gap_finish(int tau, int nchunk, Roun
 #pragma unroll
         for (int u = 0; u < NR; u++) {
             if (valid[u]) {
-                int64_t rw = (int64_t)b * n1 + PR((int64_t)rr[u]);
+                int64_t rw = (int64_t)b * n1 + prow(((int64_t)rr[u]), n1 - 1);
                 opt[rw] = bp[u]; nnopt[rw] = anchor + Rr[u] + bl[u];
                 if (HYP) nlopt[rw] = anchor2 + Rr2[u] + bl2[u];
                 fin[rw] = (uint8_t)fin_stamp;
@@ -1538,7 +1441,7 @@ __global__ void __launch_bounds__(256) k_gap_merge(int tau, int nchunk, const Ro
         if (g.none) continue;
         const int32_t Rr = gap_right_counts<false>(pos, prev, g.rL, ck, td.x, (int32_t)n, lane);
         const int32_t Rr2 = HYP ? gap_right_counts<true>(lpos, lfirst, g.rL, ck, td.x, (int32_t)n, lane) : 0;
-        const int64_t rwL = (int64_t)b * n1 + PR((int64_t)g.rL);
+        const int64_t rwL = (int64_t)b * n1 + prow(((int64_t)g.rL), n1 - 1);
         const int32_t anchor = nnopt[rwL], anchor2 = HYP ? nlopt[rwL] : 0;
         TC bv = (TC)0; int32_t bp = -1, bl = 0, bl2 = 0, cum = 0, cum2 = 0;
         // (the task over the top rectangle's whole block has thousands of segments: eight records per lane in flight -- the running
@@ -1553,14 +1456,14 @@ __global__ void __launch_bounds__(256) k_gap_merge(int tau, int nchunk, const Ro
                 if (s0 + u >= nseg) break;
                 const GapSegRec<TC, HYP> rec = rr[u];
                 if (rec.p >= 0) {
-                    TC v = cadd(rec.v, dm_apply(M, (TC)0, (int64_t)0, (int64_t)0, (int64_t)cum, (int64_t)cum2));
+                    TC v = cadd(rec.v, dm_apply_affine(M, (TC)0, (int64_t)0, (int64_t)0, (int64_t)cum, (int64_t)cum2));
                     if (bp < 0 || v < bv) { bv = v; bp = rec.p; bl = rec.l + cum; bl2 = rec.l2 + cum2; }
                 }
                 cum += rec.cum; cum2 += rec.cum2;
             }
         }
         if (g.valid) {
-            int64_t rw = (int64_t)b * n1 + PR((int64_t)g.rr);
+            int64_t rw = (int64_t)b * n1 + prow(((int64_t)g.rr), n1 - 1);
             opt[rw] = bp; nnopt[rw] = anchor + Rr + bl;
             if (HYP) nlopt[rw] = anchor2 + Rr2 + bl2;
             fin[rw] = (uint8_t)fin_stamp;
@@ -1590,7 +1493,7 @@ template <typename TC, bool HYP>
 __device__ __forceinline__ void fix_merge(Best<TC, HYP> &acc, Best<TC, HYP> c, int64_t base, int64_t base2, const DevModel<TC> &M)
 {
     if (c.p >= 0) {
-        c.v = cadd(c.v, dm_apply(M, (TC)0, (int64_t)0, (int64_t)0, base, base2));
+        c.v = cadd(c.v, dm_apply_affine(M, (TC)0, (int64_t)0, (int64_t)0, base, base2));
         c.nn = (int32_t)(c.nn + base);
         if (HYP) best_set_nl(c, (int32_t)(best_nl(c) + base2));
     }
@@ -1598,8 +1501,6 @@ __device__ __forceinline__ void fix_merge(Best<TC, HYP> &acc, Best<TC, HYP> c, i
     if (take) acc = c;
 }
 
-// what a trip leaves for the fold, as 8-byte words: {v, p | nn << 32, the trip's count, nl, the trip's second count}
-constexpr int FIX_REC_W = 5;
 template <typename TC> __device__ __forceinline__ unsigned long long fix_bits(TC v);
 template <> __device__ __forceinline__ unsigned long long fix_bits<int64_t>(int64_t v) { return (unsigned long long)v; }
 template <> __device__ __forceinline__ unsigned long long fix_bits<double>(double v) { return (unsigned long long)__double_as_longlong(v); }
@@ -1657,7 +1558,7 @@ __global__ void __launch_bounds__(256) k_fix_own(RoundCounts *__restrict__ rc, c
                 run += tileS[k];
                 if (HYP) run2 += tileS2[k];
             }
-            int64_t rw = (int64_t)tb[t] * n1 + PR((int64_t)td.z);
+            int64_t rw = (int64_t)tb[t] * n1 + prow(((int64_t)td.z), n1 - 1);
             opt[rw] = acc.p; nnopt[rw] = acc.nn;
             if (HYP) nlopt[rw] = best_nl(acc);
         }
@@ -1796,7 +1697,7 @@ __global__ void __launch_bounds__(256) k_fix_own(RoundCounts *__restrict__ rc, c
             }
         }
         if (write) {
-            int64_t rw = (int64_t)tb[t] * n1 + PR((int64_t)td.z);
+            int64_t rw = (int64_t)tb[t] * n1 + prow(((int64_t)td.z), n1 - 1);
             opt[rw] = out.p; nnopt[rw] = out.nn;
             if (HYP) nlopt[rw] = best_nl(out);
         }
@@ -1862,7 +1763,7 @@ __global__ void __launch_bounds__(256, 6) k_lpass(RoundDesc R, const RoundCounts
             int32_t e = lane + 64 * k;
             if (e <= tl) {
                 int32_t p = rec.x - e;
-                TC fv = dm_apply(M, alpha, (int64_t)(rec.y - p), (int64_t)(rec.z - sk[k]), (int64_t)acc[k], (int64_t)acc2[k]);
+                TC fv = dm_apply_affine(M, alpha, (int64_t)(rec.y - p), (int64_t)(rec.z - sk[k]), (int64_t)acc[k], (int64_t)acc2[k]);
                 Best<TC, HYP> c; best_clear(c); c.v = cadd(W[p], fv); c.p = p; c.nn = acc[k]; best_set_nl(c, acc2[k]);
                 best = better(best, c);
             }
@@ -1933,7 +1834,7 @@ __global__ void __launch_bounds__(256, 6) k_lpass(RoundDesc R, const RoundCounts
         Best<TC, HYP> bx; best_clear(bx);
         if (head_in_tile && p >= 0) {
             int64_t nn = (int64_t)s0 + x, nl = HYP ? (int64_t)s0l + x2 : 0;
-            TC fv = dm_apply(M, alpha, (int64_t)(r - p), (int64_t)(posr - s), nn, nl);     // s == pos[p] for every candidate
+            TC fv = dm_apply_affine(M, alpha, (int64_t)(r - p), (int64_t)(posr - s), nn, nl);     // s == pos[p] for every candidate
             bx.v = cadd(wp, fv); bx.p = p; bx.nn = (int32_t)nn; best_set_nl(bx, (int32_t)nl);
         } else if (valid && !head_in_tile) {
             a_loc[tile_start + e] = x;                  // counts since the tile start; finished by k_open
@@ -1950,9 +1851,9 @@ __global__ void __launch_bounds__(256, 6) k_lpass(RoundDesc R, const RoundCounts
         if (head_in_tile) {
             if (e == seg_last) {
                 int b = a_tb[t];
-                a_opt[(int64_t)b * n1 + PR(r)] = bx.p;
-                a_nnopt[(int64_t)b * n1 + PR(r)] = bx.nn;
-                if (HYP) a_nlopt[(int64_t)b * n1 + PR(r)] = best_nl(bx);
+                a_opt[(int64_t)b * n1 + prow((r), n1 - 1)] = bx.p;
+                a_nnopt[(int64_t)b * n1 + prow((r), n1 - 1)] = bx.nn;
+                if (HYP) a_nlopt[(int64_t)b * n1 + prow((r), n1 - 1)] = best_nl(bx);
             } else if (e == tile_last) {
                 partR[tile] = bx; a_taskR[tile] = (int64_t)t;
             }
@@ -2006,14 +1907,14 @@ __global__ void __launch_bounds__(256) k_span_short(RoundDesc R, RoundCounts *__
                 for (int64_t e = ntl; e <= end; e++) {                  // decreasing p: earlier candidates win ties
                     int64_t p = B - (e - toff);
                     int64_t nn = base + a_loc[e], nl = HYP ? base2 + a_loc2[e] : 0;
-                    TC fv = dm_apply(M, alpha, r - p, (int64_t)(td.w - a_pos[p]), nn, nl);
+                    TC fv = dm_apply_affine(M, alpha, r - p, (int64_t)(td.w - a_pos[p]), nn, nl);
                     Best<TC, HYP> c; best_clear(c); c.v = cadd(W[p], fv); c.p = (int32_t)p; c.nn = (int32_t)nn; best_set_nl(c, (int32_t)nl);
                     best = better(best, c);
                 }
                 int b = a_tb[t];
-                a_opt[(int64_t)b * n1 + PR(r)] = best.p;
-                a_nnopt[(int64_t)b * n1 + PR(r)] = best.nn;
-                if (HYP) a_nlopt[(int64_t)b * n1 + PR(r)] = best_nl(best);
+                a_opt[(int64_t)b * n1 + prow((r), n1 - 1)] = best.p;
+                a_nnopt[(int64_t)b * n1 + prow((r), n1 - 1)] = best.nn;
+                if (HYP) a_nlopt[(int64_t)b * n1 + prow((r), n1 - 1)] = best_nl(best);
             } else {
                 fix_long = true;
             }
@@ -2078,7 +1979,7 @@ __global__ void __launch_bounds__(256) k_open(RoundDesc R, const RoundCounts *__
         for (int64_t e = tile_start + lane; e <= last; e += 64) {
             int64_t p = B - (e - toff);
             int64_t nn = base + a_loc[e], nl = HYP ? base2 + a_loc2[e] : 0;
-            TC fv = dm_apply(M, alpha, r - p, (int64_t)(td.w - a_pos[p]), nn, nl);
+            TC fv = dm_apply_affine(M, alpha, r - p, (int64_t)(td.w - a_pos[p]), nn, nl);
             Best<TC, HYP> c; best_clear(c); c.v = cadd(W[p], fv); c.p = (int32_t)p; c.nn = (int32_t)nn; best_set_nl(c, (int32_t)nl);
             best = better(best, c);                         // a lane visits its steps in increasing e (decreasing p)
         }
@@ -2119,7 +2020,7 @@ __global__ void __launch_bounds__(256) k_fix(const RoundCounts *__restrict__ rc,
             if (tile_rec[k].w != 0 && c.p >= 0) {            // interior tile: counts and value are relative to the tile start
                 int64_t base = S0 + (tilePS[k] - tilePS[tile]);
                 int64_t base2 = HYP ? S0l + (tilePS2[k] - tilePS2[tile]) : 0;
-                c.v = cadd(c.v, dm_apply(M, (TC)0, (int64_t)0, (int64_t)0, base, base2));       // the costs are affine in the counts
+                c.v = cadd(c.v, dm_apply_affine(M, (TC)0, (int64_t)0, (int64_t)0, base, base2));       // the costs are affine in the counts
                 c.nn = (int32_t)(c.nn + base);
                 if (HYP) best_set_nl(c, (int32_t)(best_nl(c) + base2));
             }
@@ -2136,91 +2037,11 @@ __global__ void __launch_bounds__(256) k_fix(const RoundCounts *__restrict__ rc,
         if (lane == 0) {
             Best<TC, HYP> res = better(partR[tile], acc);   // the head tile holds the larger p: wins ties
             int64_t r = tdesc[t].z; int b = tb[t];
-            opt[(int64_t)b * n1 + PR(r)] = res.p;
-            nnopt[(int64_t)b * n1 + PR(r)] = res.nn;
-            if (HYP) nlopt[(int64_t)b * n1 + PR(r)] = best_nl(res);
+            opt[(int64_t)b * n1 + prow((r), n1 - 1)] = res.p;
+            nnopt[(int64_t)b * n1 + prow((r), n1 - 1)] = res.nn;
+            if (HYP) nlopt[(int64_t)b * n1 + prow((r), n1 - 1)] = best_nl(res);
         }
     }
-}
-
-// ------------------------------------------------------------------ combine the per-bit winners of every row
-// Which row a thread of the combine kernels takes.  lvl = 0: row rlo + i.  lvl = 1 (an experiment kept behind a debug option, see
-// run_layer): the row of plane slot i -- the order the planes are stored in (prow); row 0 is thread n.  Returns -1 for a thread
-// without a row.
-__device__ __forceinline__ int64_t combine_row(int64_t i, int64_t n, int64_t rlo, int64_t rhi, int lvl)
-{
-    int64_t r;
-    if (!lvl) r = rlo + i;
-    else if (i == n) r = 0;
-    else if (i > n) return -1;
-    else {
-        int t = 0;
-        while (t < 62 && n - (n >> (t + 1)) <= i) t++;             // level of slot i: base(t) <= i < base(t + 1), base(t) = n - (n >> t)
-        r = (((i - (n - (n >> t))) << 1) | 1) << t;
-    }
-    return (r < rlo || r > rhi) ? -1 : r;
-}
-
-template <typename TC>
-__global__ void __launch_bounds__(256) k_combine(int lvl, int64_t n, int64_t rlo, int64_t rhi, int nbits, const int32_t *__restrict__ pos,
-                                                 const int32_t *__restrict__ opt, const int32_t *__restrict__ nnopt,
-                                                 const int32_t *__restrict__ nlopt,
-                                                 const TC *__restrict__ W, DevModel<TC> M, TC alpha,
-                                                 TC *__restrict__ cst, int32_t *__restrict__ ptr, int sh, int32_t *__restrict__ pz)
-{
-    // sh > 0 (after a leaf pass): the rows (rlo + i) << sh only -- the leaf rows were combined where they were computed
-    int64_t r = combine_row((int64_t)blockIdx.x * blockDim.x + threadIdx.x, n, rlo, rhi, lvl);
-    if (r < 0) return;
-    r <<= sh;
-    int64_t n1 = n + 1;
-    TC bv = cadd(W[r], dm_apply(M, alpha, (int64_t)0, (int64_t)0, (int64_t)0, (int64_t)0));   // j = j' (empty part)
-    int64_t bp = r;
-    for (int b = 0; b < nbits; b++) {
-        if (!((r >> b) & 1)) continue;
-        int64_t p = opt[(int64_t)b * n1 + PR(r)];
-        if (pz && (uint64_t)p > (uint64_t)n) { atomicAdd(pz, 1); p = r; }      // (poison mode: a cell nobody wrote)
-        int64_t nn = nnopt[(int64_t)b * n1 + PR(r)];
-        int64_t nl = nlopt ? nlopt[(int64_t)b * n1 + PR(r)] : 0;
-        TC v = cadd(W[p], dm_apply(M, alpha, r - p, (int64_t)(pos[r] - pos[p]), nn, nl));
-        if (v < bv) { bv = v; bp = p; }            // lower bits hold larger p: strict < keeps the largest p on ties
-    }
-    cst[r] = bv;
-    ptr[r] = (int32_t)bp;
-}
-
-// windowed layers: the candidates of row r from the right: the diagonal, the standard planes by ascending bit, the common plane,
-// the mirrored planes by descending bit -- strict < while moving left keeps the largest p on ties
-template <typename TC>
-__global__ void __launch_bounds__(256) k_combine_win(int lvl, Geo G, int64_t n, int64_t rlo, int64_t rhi, const int32_t *__restrict__ pos,
-                                                     const int32_t *__restrict__ opt, const int32_t *__restrict__ nnopt,
-                                                     const int32_t *__restrict__ nlopt,
-                                                     const TC *__restrict__ W, DevModel<TC> M, TC alpha,
-                                                     TC *__restrict__ cst, int32_t *__restrict__ ptr, int sh, int32_t *__restrict__ pz)
-{
-    int64_t r = combine_row((int64_t)blockIdx.x * blockDim.x + threadIdx.x, n, rlo, rhi, lvl);
-    if (r < 0) return;
-    r <<= sh;                                                   // (after a leaf pass: the multiples of 64 only)
-    const int64_t n1 = n + 1;
-    TC bv = cadd(W[r], dm_apply(M, alpha, (int64_t)0, (int64_t)0, (int64_t)0, (int64_t)0));   // j = j' (empty part)
-    int64_t bp = r;
-    if (r >= 1) {
-        const int64_t slot = PR(r);
-        for (int i = 0; i <= 2 * G.s; i++) {
-            const int b = i <= G.s ? i : 2 * G.s - i;                       // 0 .. s, then s-1 .. 0
-            if (b < G.s && (((r >> b) & 1) != (i <= G.s))) continue;      // first pass: set bits (standard); second pass: clear bits (mirrored)
-            if (b == G.s && i != G.s) continue;
-            int64_t cs, ce;
-            if (!geo_block(G, r, b, cs, ce)) continue;
-            int64_t p = opt[(int64_t)b * n1 + slot];
-            if (pz && (uint64_t)p > (uint64_t)n) { atomicAdd(pz, 1); p = r; }
-            const int64_t nn = nnopt[(int64_t)b * n1 + slot];
-            const int64_t nl = nlopt ? nlopt[(int64_t)b * n1 + slot] : 0;
-            const TC v = cadd(W[p], dm_apply(M, alpha, r - p, (int64_t)(pos[r] - pos[p]), nn, nl));
-            if (v < bv) { bv = v; bp = p; }
-        }
-    }
-    cst[r] = bv;
-    ptr[r] = (int32_t)bp;
 }
 
 // ---- anchors of the mirrored head tasks (windowed layers), once per (pattern, w)
@@ -2328,7 +2149,6 @@ __global__ void __launch_bounds__(256) k_leaf_anchors(int64_t ng, int64_t n, con
 // mir_w = w > 0: the MIRRORED heads of the windowed geometry (geo_block) -- level b < s holds the rows r = (u+1) 2^(b+1),
 // candidates ce - 1 - i with ce = r + 2^(b+1) - 1 - w (those below column 0 do not exist); the counts carry the head's anchor
 // nets(ce, r), at aoff[b] + (r >> (b+1)) of the window anchors.  tlo / thi: the tiles of each level a windowed layer needs.
-struct RATab { int32_t nbits, _pad; int64_t n; int64_t tbase[33]; int64_t rbase[33]; int64_t mir_w; int64_t aoff[33]; int64_t tlo[33], thi[33]; };
 
 __device__ __forceinline__ int64_t ra_row(const RATab &T, int b, int64_t u)
 {
@@ -2420,7 +2240,7 @@ __global__ void __launch_bounds__(256) k_ra_layer(RATab T, int64_t ntile, const 
         best_clear(cand[k]);
         if (ok) {
             int32_t c = k == 0 ? c4.x : k == 1 ? c4.y : k == 2 ? c4.z : c4.w, c2 = k == 0 ? d4.x : k == 1 ? d4.y : k == 2 ? d4.z : d4.w;
-            cand[k].v = cadd(W[p], dm_apply(M, alpha, r - p, (int64_t)(pos[r] - pos[p]), (int64_t)c, (int64_t)c2));
+            cand[k].v = cadd(W[p], dm_apply_affine(M, alpha, r - p, (int64_t)(pos[r] - pos[p]), (int64_t)c, (int64_t)c2));
             cand[k].p = (int32_t)p; cand[k].nn = c; best_set_nl(cand[k], c2);
         }
     }
@@ -2431,7 +2251,7 @@ __global__ void __launch_bounds__(256) k_ra_layer(RATab T, int64_t ntile, const 
             if ((k & (per - 1)) != 0 || rk[k] == 0) continue;
             Best<TC, HYP> x = cand[k];
             if (per == 2 && ra_takes(x, cand[k + 1 < 4 ? k + 1 : 3])) x = cand[k + 1 < 4 ? k + 1 : 3];
-            int64_t rw = (int64_t)b * n1 + PR(rk[k]);
+            int64_t rw = (int64_t)b * n1 + prow((rk[k]), n1 - 1);
             opt[rw] = x.p; nnopt[rw] = x.nn;
             if (HYP) nlopt[rw] = best_nl(x);
         }
@@ -2450,7 +2270,7 @@ __global__ void __launch_bounds__(256) k_ra_layer(RATab T, int64_t ntile, const 
     if ((lane & (lpr - 1)) == 0) {
         if (b <= 8) {
             if (rk[0]) {
-                int64_t rw = (int64_t)b * n1 + PR(rk[0]);
+                int64_t rw = (int64_t)b * n1 + prow((rk[0]), n1 - 1);
                 opt[rw] = x.p; nnopt[rw] = x.nn;
                 if (HYP) nlopt[rw] = best_nl(x);
             }
@@ -2509,7 +2329,7 @@ __global__ void __launch_bounds__(256) k_ra_cols(RATab T, const int32_t *__restr
             for (int j = 0; j < 2; j++) {
                 const int64_t rk = r + 2 * j, pk = p0 + kk + 2 * j;
                 if (rk >= 1 && rk <= n && pk >= 0 && (!MIR || u + j >= 0)) {
-                    const int64_t rw = PR(rk);
+                    const int64_t rw = prow((rk), n1 - 1);
                     opt[rw] = (int32_t)pk; nnopt[rw] = cnt[E0 + j]; if (HYP) nlopt[rw] = cnt2[E0 + j];
                 }
             }
@@ -2534,7 +2354,7 @@ __global__ void __launch_bounds__(256) k_ra_cols(RATab T, const int32_t *__restr
             if (b == 1 && (k < k0 || k > k0 + 1)) continue;
             if (!rok || p0 + k < 0) continue;               // (mirrored heads: a block may be cut off at column 0)
             Best<TC, HYP> cc; best_clear(cc);
-            cc.v = cadd(wv[k], dm_apply(M, alpha, r - (p0 + k), (int64_t)(posr - pv[k]), (int64_t)c[k], (int64_t)d[k]));
+            cc.v = cadd(wv[k], dm_apply_affine(M, alpha, r - (p0 + k), (int64_t)(posr - pv[k]), (int64_t)c[k], (int64_t)d[k]));
             cc.p = (int32_t)(p0 + k); cc.nn = c[k]; best_set_nl(cc, d[k]);
             if (ra_takes(x, cc)) x = cc;
         }
@@ -2548,7 +2368,7 @@ __global__ void __launch_bounds__(256) k_ra_cols(RATab T, const int32_t *__restr
         if ((lane & (lpr - 1)) == 0 && rok) {
             if (b <= 8) {
                 if (x.p >= 0) {
-                    const int64_t rw = (int64_t)b * n1 + PR(r);
+                    const int64_t rw = (int64_t)b * n1 + prow((r), n1 - 1);
                     opt[rw] = x.p; nnopt[rw] = x.nn;
                     if (HYP) nlopt[rw] = best_nl(x);
                 }
@@ -2590,7 +2410,7 @@ __global__ void __launch_bounds__(256) k_ra_merge(RATab T, int64_t nrow, const B
         if (ra_takes(x, c)) x = c;
     }
     if (lane == 0 && r <= T.n) {
-        int64_t rw = (int64_t)b * n1 + PR(r);
+        int64_t rw = (int64_t)b * n1 + prow((r), n1 - 1);
         opt[rw] = x.p; nnopt[rw] = x.nn;
         if (HYP) nlopt[rw] = best_nl(x);
     }
@@ -2688,11 +2508,7 @@ void dp_round_scans_test(const int32_t *a, int64_t na, int64_t na_max, const int
     res[0] = h.T; res[1] = h.NT; res[2] = h.nlong; res[3] = h.nown; res[4] = h.ntile; res[5] = h.err;
 }
 
-#include "dp_leaf.inc"
-
 // ------------------------------------------------------------------ host side of the own-tile merge (k_fix_own)
-// items a round of `nt` own tiles can list: one per FIX_TRIP tiles and at most one partial trip per task of more than FIX_SERIAL tiles
-static size_t fix_items_cap(size_t nt) { return nt / FIX_TRIP + nt / (FIX_SERIAL + 1) + 2; }
 // the grid, from what the host knows: the round's tiles (predicted or exact) and tasks.  Both roles walk their device-side
 // counts with grid strides, so a count beyond the estimate costs time only.
 struct FixGrid { int iblocks, lblocks; };
@@ -2819,25 +2635,7 @@ void dp_fix_merge_test(const cp_model_t *model, int64_t ntask, const int64_t *to
     });
 }
 
-// ------------------------------------------------------------------ the link entries split by plane (own_split)
-// A left step of a task (row r, plane b) over column p counts the entries of p with next >= r.  The task's columns lie in the
-// Fenwick block [r_b - 2^b, r_b), r in [r_b, r_b + 2^b).  With h = the highest bit in which p and x = next[q] differ (-1: none):
-//   h < b: x lies in p's own block, below r_b: no row of the rectangle counts the entry;
-//   h > b: x >= r_b + 2^b: every row counts it -- a constant of (column, plane);
-//   h == b: x lies in the sibling block: the only entries whose contribution depends on r ("variable in plane b").
-// Every entry is variable in exactly one plane.  For the planes b = SPLIT_BMIN .. nbits - 1 (nb of them, index b - SPLIT_BMIN):
-//   vnext: the variable entries' next values, plane-major, column-major inside a plane, entry order inside a column (+ 8 of slack);
-//   vpos[b][p], p = 0 .. n: where column p's plane-b entries start in vnext (vpos[b][n] = vpos[b + 1][0]; one word more: the total);
-//   vsa[b][p]: #{entries of the columns < p with h > b}.
-// They depend on the pattern only: built once per partition, by the first layer that uses them (split_build).
-struct SplitLinks {
-    bool built = false;
-    int nb = 0;
-    int64_t stride = 0;                        // n + 1
-    int64_t tot[SPLIT_NB + 1] = {0};           // variable entries per plane; [nb]: all of them
-    DBuf<int32_t> vnext, vpos, vsa;
-};
-
+// ------------------------------------------------------------------ the link entries split by plane (own_split; SplitLinks: dp_total.hpp)
 __device__ __forceinline__ int split_plane(int32_t p, int32_t x) { return 31 - __clz((int)(p ^ x)); }       // (-1 for x == p)
 
 // one lane per column: cnt[b][p] = the column's entries with h == SPLIT_BMIN + b (column n: none)
@@ -2930,101 +2728,6 @@ void dp_own_split_test(cp_csr_s *A, int32_t *vpos_out, int32_t *vsa_out, int32_t
 }
 
 // ------------------------------------------------------------------ host driver for one layer
-template <typename TC>
-struct LayerWork {
-    int64_t n = -1; int nbits = 0; bool hyp = false;
-    DBuf<int32_t> opt, nnopt, cr, len, loc, tileS;
-    DBuf<int4> tdesc;                                    // per task {B, anchor count, row r, pos32[r]}
-    DBuf<int32_t> nlopt, crl, tS0l, loc2, tileS2;        // hyperedge-cut: second (self-net) count
-    DBuf<uint8_t> tb;
-    DBuf<int64_t> offs, scratch, taskR, tilePS, tilePS2, tile_t0;
-    ScanWS scanws;                                      // single-launch scans of the rounds
-    DBuf<Best<TC, true>> partL, partR;                  // sized for the larger record; reinterpreted per variant
-    DBuf<int32_t> open_list, fix_list;                  // tiles of long spans (k_span_short -> k_open / k_fix)
-    DBuf<int4> tile_rec;                                // {first column, row, -, interior?} per tile (k_tile_t0)
-    // tasks with tiles of their own (k_lpass_own)
-    DBuf<int4> o_tdesc, o_rec;
-    DBuf<uint8_t> o_tb;
-    DBuf<int32_t> o_rlen, o_ntl, o_tS0l, o_task, o_tileS, o_tileS2, o_hi;
-    // the merge of the own tiles (k_fix_own): its items {task, first tile} and each trip-start tile's item (k_own_map), one record per
-    // item, one ticket per task (zero between rounds: the folder of a task puts it back)
-    DBuf<int2> o_items; DBuf<int32_t> o_item_of; DBuf<unsigned long long> o_trec; DBuf<uint32_t> o_tick;
-    bool t_dirty = true;                                // o_tick may hold tickets (run_layer clears it before its first round)
-    DBuf<Best<TC, true>> o_sub;                         // gap passes: segment winners of the tiles with specials, [tile][SMAX + 1]
-    DBuf<int32_t> o_spv;                                // ... and the specials between them
-    // round A from cached counts
-    bool ra_built = false; RATab ra_tab; int64_t ra_ntile = 0, ra_nrow = 0;
-    SplitLinks split;                                   // the link entries by plane (own_split): built by the first layer that uses them
-    bool mir_built = false; RATab mir_tab; int64_t mir_ntile = 0, mir_nrow = 0, mir_w = 0;      // the mirrored heads of a window width (ra_build_mir)
-    DBuf<int32_t> mir_c, mir_c2;
-    DBuf<Best<TC, true>> mir_part;
-    DBuf<int32_t> ra_c, ra_c2;
-    DBuf<int64_t> ra_G;                                 // prefix sums while the counts are built
-    DBuf<Best<TC, true>> ra_part;
-    DBuf<int2> g_slot;                                  // segment slot -> {task, segment}
-    DBuf<int2> g_list;                                  // gap tasks of more than GAPSEG tiles: {task, first segment slot}
-    DBuf<char> g_seg;                                   // their segment records (GapSegRec)
-    DBuf<int32_t> g_slow, g_sslow;                      // work items of k_gap_finish / k_gap_seg left to the SLOW variants
-    DBuf<int32_t> last_s0;                              // anchors of the last row's round-A tasks ([b], [32 + b])
-    DBuf<uint8_t> o_spec, fin;                          // gap passes: flagged tiles; rows already final (per plane slot)
-    int fin_stamp = 255;                                // ... iff the cell holds the current layer's stamp (run_layer; 255: cleared before the next layer)
-    DBuf<int64_t> o_toffs, o_tilePS, o_tilePS2;
-    DBuf<Best<TC, true>> o_part;
-    // own_blk: the tiles sorted by 256-column block (k_own_map -> scan -> k_blk_order)
-    DBuf<int32_t> b_cnt, b_n, o_brank, o_border;        // tiles per block, the block count (device); per tile: rank in its block, tile ids in block order
-    DBuf<int4> o_srec;                                  // ... and the tiles' records (o_rec) in block order
-    DBuf<int64_t> b_start;
-    int64_t b_nblk = 0;
-    bool b_dirty = true;                                // b_cnt may hold counts (run_layer clears it before its first round)
-    int64_t max_tasks = 0;
-    bool planes_full = false;                           // the last layer stored every per-block winner (cp_dp_block_tables)
-    DBuf<int32_t> pz;                                   // poison mode: cells read that nobody wrote
-    // windowed layers: geometry of the current call; anchors of the mirrored head tasks, cached per (pattern, w)
-    Geo G{0, 0, 0};
-    bool win_built = false; int64_t win_w = -1, win_nitems = 0, win_aoff[33];
-    DBuf<int32_t> w_anch, w_anch2, w_tot, w_hist;
-    DBuf<int32_t> leaf_anch, leaf_anch2;                // leaf pass of windowed layers: nets / self nets of [64 g + 62 - w, 64 g) per group
-    DBuf<int64_t> w_E;
-    DBuf<RoundCounts> rc;                               // per-round counters of the current layer (device)
-    std::vector<RoundCounts> pred;                      // ... of the previous layer (host): sizes the next one
-    bool pred_ok = false; int64_t pred_rlo = 0, pred_rhi = 0; double pred_scale = 1.0; int pred_win = 0; int64_t pred_w = 0;
-    // rounds whose flattened stage served a handful of tasks in the last layer that ran it: their medium tasks get tiles of their
-    // own from then on and the stage (six dependent launches, ~40 us) is skipped -- see run_layer
-    std::vector<uint8_t> force_own;
-    int64_t force_rows = 0;               // rows of the layer the flags come from (a one-row last layer says nothing about a full one)
-    // (o_rec / loc are the size witnesses of their groups: they are released first and allocated LAST, so a hipMalloc failure in
-    //  the middle leaves the witness empty and the next call allocates the whole group again)
-    // what the pattern's cached tables and the last layer's counts say no longer holds (another pattern, another shape)
-    void forget() { ra_built = false; split.built = false; pred_ok = false; win_built = false; mir_built = false; force_own.clear(); force_rows = 0; }
-    void ensure_own(size_t NT) {                        // per-tile arrays of the own-tiled tasks
-        if (o_rec.n >= NT && o_rec.n > 0) return;
-        size_t c = NT > 0 ? NT : 1;
-        o_rec.release();
-        o_task.alloc(c); o_tileS.alloc(c); o_tilePS.alloc(c + 1); o_part.alloc(c); o_hi.alloc(c); o_spec.alloc(c); o_brank.alloc(c); o_border.alloc(c); o_srec.alloc(c);
-        o_item_of.alloc(c); o_items.alloc(fix_items_cap(c)); o_trec.alloc(fix_items_cap(c) * FIX_REC_W);
-        o_sub.alloc(c * (SMAX + 1)); o_spv.alloc(c * (SMAX + 1));
-        if (hyp) { o_tileS2.alloc(c); o_tilePS2.alloc(c + 1); }
-        o_rec.alloc(c);
-    }
-    void ensure_flat(size_t T) {                        // per-step and per-tile arrays of the flattened tasks
-        if (loc.n >= T && loc.n > 0) return;
-        size_t c = T > 0 ? T : 1, nt = (c + LT - 1) / LT;
-        loc.release();
-        if (hyp) loc2.alloc(c);
-        tileS.alloc(nt); tilePS.alloc(nt + 1); tile_t0.alloc(nt); partL.alloc(nt); partR.alloc(nt); taskR.alloc(nt);
-        open_list.alloc(nt); fix_list.alloc(nt); tile_rec.alloc(nt);
-        if (hyp) { tileS2.alloc(nt); tilePS2.alloc(nt + 1); }
-        loc.alloc(c);
-    }
-};
-
-// A layer's variant (HYP: hyperedge costs, with the second count) is fixed when the layer starts: run_layer<TC, HYP> and what it
-// calls see the work buffers through these two.
-// the record buffers are sized for the larger record and read as the variant's own
-template <bool HYP, typename TC> static Best<TC, HYP> *recs(const DBuf<Best<TC, true>> &b) { return reinterpret_cast<Best<TC, HYP> *>(b.p); }
-// the arrays of the second (self-net) count: the kernels of the other variant get null
-template <bool HYP, typename T> static T *if_hyp(T *p) { return HYP ? p : nullptr; }
-
 // number of rows r <= x of the form (base << (b+1)) | (1 << b) | ((2v+1) << tau): the rows with ctz == tau whose bit b is set
 static int64_t count_rows(int b, int tau, int64_t x)
 {
@@ -3154,17 +2857,17 @@ static void launch_rpass(hipStream_t s, const RoundDesc &R, int nbits, int64_t n
 
 // Builds a cached round-A table: the counts of `levels` levels of rows_of(b) rows each (they depend on the pattern only -- once per
 // partition; the table of the mirrored heads of the windowed geometry, mir_w > 0, also on the window width: once per (pattern, w),
-// after win_build, whose anchors `anch` / `anch2` its counts carry).  Fills T, the counts c (c2: second count) and the sizes;
-// `part` gets room for the partials of the rows of more than LT candidates.
+// after win_build, whose anchors `anch` / `anch2` its counts carry).  Fills the cache's table, counts (c2: second count) and
+// sizes; `part` gets room for the partials of the rows of more than LT candidates.
 template <typename TC, typename Rows>
-static void ra_build(cp_csr_s *A, LayerWork<TC> &Wk, RATab &T, int levels, Rows rows_of, int64_t mir_w, const int32_t *anch, const int32_t *anch2,
-                     DBuf<int32_t> &c, DBuf<int32_t> &c2, DBuf<Best<TC, true>> &part, int64_t &ntile, int64_t &nrow)
+static void ra_build(cp_csr_s *A, LayerWork<TC> &Wk, RaCache<TC> &Ra, int levels, Rows rows_of, int64_t mir_w, const int32_t *anch, const int32_t *anch2)
 {
     hipStream_t s = A->stream;
     const bool hyp = Wk.hyp;
+    RATab &T = Ra.tab;
     memset(&T, 0, sizeof(T));
     T.nbits = levels; T.n = A->n; T.mir_w = mir_w;
-    for (int b = 0; b < 33; b++) { T.tlo[b] = 0; T.thi[b] = INT64_MAX; T.aoff[b] = (mir_w && b < 32) ? Wk.win_aoff[b] : 0; }
+    for (int b = 0; b < 33; b++) { T.tlo[b] = 0; T.thi[b] = INT64_MAX; T.aoff[b] = (mir_w && b < 32) ? Wk.win.aoff[b] : 0; }
     int64_t tb = 0, rb = 0;
     for (int b = 0; b < 33; b++) {
         T.tbase[b] = tb; T.rbase[b] = rb;
@@ -3173,40 +2876,39 @@ static void ra_build(cp_csr_s *A, LayerWork<TC> &Wk, RATab &T, int levels, Rows 
         tb += cdiv(nrows << b, LT);
         if (b >= 9) rb += nrows;
     }
-    ntile = tb; nrow = rb;
+    Ra.ntile = tb; Ra.nrow = rb;
     const size_t total = (size_t)tb * LT;
-    c.ensure(total + 8);
-    if (hyp) c2.ensure(total + 8);
-    part.ensure((size_t)std::max<int64_t>(1, tb - T.tbase[9]));
-    if (tb <= 0) return;
-    DBuf<int64_t> &G = Wk.ra_G, &scratch = Wk.scratch;        // (kept with the layer scratch: 8 B per element)
-    G.ensure(total + 1);
-    hipLaunchKernelGGL(k_ra_colcount, dim3((unsigned)tb), dim3(LT), 0, s, T, A->pos32.p, A->next.p, hyp ? A->fpos32.p : (const int32_t *)nullptr,
-                       hyp ? A->flast.p : (const int32_t *)nullptr, c.p, hyp ? c2.p : (int32_t *)nullptr);
-    exclusive_scan_i32(c.p, G.p, (int64_t)total, scratch, s);
-    hipLaunchKernelGGL(k_ra_final, dim3((unsigned)tb), dim3(LT), 0, s, T, G.p, c.p, anch);
-    if (hyp) {
-        exclusive_scan_i32(c2.p, G.p, (int64_t)total, scratch, s);
-        hipLaunchKernelGGL(k_ra_final, dim3((unsigned)tb), dim3(LT), 0, s, T, G.p, c2.p, anch2);
+    Ra.c.ensure(total + 8);
+    if (hyp) Ra.c2.ensure(total + 8);
+    Ra.part.ensure((size_t)std::max<int64_t>(1, tb - T.tbase[9]));
+    if (tb > 0) {
+        DBuf<int64_t> &G = Wk.sc.ra_G, &scratch = Wk.sc.scratch;        // (kept with the layer scratch: 8 B per element)
+        G.ensure(total + 1);
+        hipLaunchKernelGGL(k_ra_colcount, dim3((unsigned)tb), dim3(LT), 0, s, T, A->pos32.p, A->next.p, hyp ? A->fpos32.p : (const int32_t *)nullptr,
+                           hyp ? A->flast.p : (const int32_t *)nullptr, Ra.c.p, hyp ? Ra.c2.p : (int32_t *)nullptr);
+        exclusive_scan_i32(Ra.c.p, G.p, (int64_t)total, scratch, s);
+        hipLaunchKernelGGL(k_ra_final, dim3((unsigned)tb), dim3(LT), 0, s, T, G.p, Ra.c.p, anch);
+        if (hyp) {
+            exclusive_scan_i32(Ra.c2.p, G.p, (int64_t)total, scratch, s);
+            hipLaunchKernelGGL(k_ra_final, dim3((unsigned)tb), dim3(LT), 0, s, T, G.p, Ra.c2.p, anch2);
+        }
+        CP_HIP(hipGetLastError());
     }
-    CP_HIP(hipGetLastError());
+    Ra.built = true; Ra.w = mir_w;
 }
 // the table of the unconstrained scheme's round A (the windowed layers' standard heads are its levels below s)
 template <typename TC>
 static void ra_build_std(cp_csr_s *A, LayerWork<TC> &Wk)
 {
     const int64_t n = A->n;
-    ra_build<TC>(A, Wk, Wk.ra_tab, Wk.nbits, [n](int b) { return ((n >> b) + 1) >> 1; }, 0, nullptr, nullptr, Wk.ra_c, Wk.ra_c2, Wk.ra_part, Wk.ra_ntile, Wk.ra_nrow);
-    Wk.ra_built = true;
+    ra_build<TC>(A, Wk, Wk.ra, Wk.nbits, [n](int b) { return ((n >> b) + 1) >> 1; }, 0, nullptr, nullptr);
 }
 // ... and of the mirrored heads of the current window: rows (u + 1) 2^(b+1) <= n
 template <typename TC>
 static void ra_build_mir(cp_csr_s *A, LayerWork<TC> &Wk)
 {
     const int64_t n = A->n;
-    ra_build<TC>(A, Wk, Wk.mir_tab, Wk.G.s, [n](int b) { return n >> (b + 1); }, Wk.G.w, Wk.w_anch.p, Wk.w_anch2.p, Wk.mir_c, Wk.mir_c2, Wk.mir_part,
-                 Wk.mir_ntile, Wk.mir_nrow);
-    Wk.mir_built = true; Wk.mir_w = Wk.G.w;
+    ra_build<TC>(A, Wk, Wk.mir, Wk.G.s, [n](int b) { return n >> (b + 1); }, Wk.G.w, Wk.win.w_anch.p, Wk.win.w_anch2.p);
 }
 
 // the nets (pass 0) / self nets (pass 1) a window of width x cuts, per column into w_hist and as prefix sums into w_E
@@ -3215,10 +2917,10 @@ static void win_hist_scan(cp_csr_s *A, LayerWork<TC> &Wk, int64_t x, int pass)
 {
     hipStream_t s = A->stream;
     const int64_t n = A->n;
-    if (pass == 1 || A->N == 0) CP_HIP(hipMemsetAsync(Wk.w_hist.p, 0, sizeof(int32_t) * (size_t)(n + 1), s));
-    if (pass == 0) { if (A->N > 0) hipLaunchKernelGGL(k_win_hist, dim3((unsigned)cdiv(n + 1, 256)), dim3(256), 0, s, n, x, A->pos32.p, A->prev.p, A->next.p, Wk.w_hist.p); }
-    else if (A->m > 0) hipLaunchKernelGGL(k_win_hist_rows, dim3((unsigned)cdiv(A->m, 256)), dim3(256), 0, s, A->m, n, x, A->rfirst.p, A->rlast.p, Wk.w_hist.p);
-    exclusive_scan_i32(Wk.w_hist.p, Wk.w_E.p, n + 1, Wk.scratch, s);
+    if (pass == 1 || A->N == 0) CP_HIP(hipMemsetAsync(Wk.win.w_hist.p, 0, sizeof(int32_t) * (size_t)(n + 1), s));
+    if (pass == 0) { if (A->N > 0) hipLaunchKernelGGL(k_win_hist, dim3((unsigned)cdiv(n + 1, 256)), dim3(256), 0, s, n, x, A->pos32.p, A->prev.p, A->next.p, Wk.win.w_hist.p); }
+    else if (A->m > 0) hipLaunchKernelGGL(k_win_hist_rows, dim3((unsigned)cdiv(A->m, 256)), dim3(256), 0, s, A->m, n, x, A->rfirst.p, A->rlast.p, Wk.win.w_hist.p);
+    exclusive_scan_i32(Wk.win.w_hist.p, Wk.win.w_E.p, n + 1, Wk.sc.scratch, s);
 }
 
 // anchors of the mirrored head tasks of the windowed layers (k_win_*): once per (pattern, w)
@@ -3229,40 +2931,40 @@ static void win_build(cp_csr_s *A, LayerWork<TC> &Wk)
     const int64_t n = A->n, w = Wk.G.w;
     const int sb = Wk.G.s;
     int64_t acc = 0;
-    for (int b = 0; b < 33; b++) { Wk.win_aoff[b] = acc; if (b < sb) acc += (n >> (b + 1)) + 1; }      // heads of plane b: rho = idx << (b+1), idx <= n >> (b+1)
-    Wk.win_nitems = acc;
+    for (int b = 0; b < 33; b++) { Wk.win.aoff[b] = acc; if (b < sb) acc += (n >> (b + 1)) + 1; }      // heads of plane b: rho = idx << (b+1), idx <= n >> (b+1)
+    Wk.win.nitems = acc;
     const size_t ni = (size_t)(acc > 0 ? acc : 1);
-    Wk.w_anch.ensure(ni); Wk.w_tot.ensure(ni); Wk.w_hist.ensure((size_t)n + 2); Wk.w_E.ensure((size_t)n + 2);
-    if (Wk.hyp) Wk.w_anch2.ensure(ni);
-    Wk.win_built = false;
+    Wk.win.w_anch.ensure(ni); Wk.win.w_tot.ensure(ni); Wk.win.w_hist.ensure((size_t)n + 2); Wk.win.w_E.ensure((size_t)n + 2);
+    if (Wk.hyp) Wk.win.w_anch2.ensure(ni);
+    Wk.win.built = false;
     if (acc > 0) {
         RoundDesc R;
-        make_round(R, true, 0, sb + 1, n, 0, n, Wk.G, Wk.win_aoff);
+        make_round(R, true, 0, sb + 1, n, 0, n, Wk.G, Wk.win.aoff);
         const unsigned wg = (unsigned)std::min<int64_t>(cdiv(acc, 4), 65536);
         for (int pass = 0; pass < (Wk.hyp ? 2 : 1); pass++) {
             win_hist_scan<TC>(A, Wk, w, pass);
-            if (pass == 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_win_block_totals<true>), dim3(wg), dim3(256), 0, s, R, acc, A->pos32.p, A->next.p, Wk.w_tot.p);
-            else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_win_block_totals<false>), dim3(wg), dim3(256), 0, s, R, acc, A->fpos32.p, A->flast.p, Wk.w_tot.p);
-            hipLaunchKernelGGL(k_win_anchors, dim3((unsigned)cdiv(acc, 256)), dim3(256), 0, s, R, acc, pass == 0 ? A->pos.p : A->lpos.p, Wk.w_E.p, Wk.w_tot.p,
-                               pass == 0 ? Wk.w_anch.p : Wk.w_anch2.p);
+            if (pass == 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_win_block_totals<true>), dim3(wg), dim3(256), 0, s, R, acc, A->pos32.p, A->next.p, Wk.win.w_tot.p);
+            else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_win_block_totals<false>), dim3(wg), dim3(256), 0, s, R, acc, A->fpos32.p, A->flast.p, Wk.win.w_tot.p);
+            hipLaunchKernelGGL(k_win_anchors, dim3((unsigned)cdiv(acc, 256)), dim3(256), 0, s, R, acc, pass == 0 ? A->pos.p : A->lpos.p, Wk.win.w_E.p, Wk.win.w_tot.p,
+                               pass == 0 ? Wk.win.w_anch.p : Wk.win.w_anch2.p);
         }
         CP_HIP(hipGetLastError());
     }
-    // leaf pass (dp_leaf.inc): anchors of the inner mirrored blocks, nets(64 g + 62 - w, 64 g) for every group g -- the same
+    // leaf pass (dp_total_leaf.hip): anchors of the inner mirrored blocks, nets(64 g + 62 - w, 64 g) for every group g -- the same
     // histogram with the width w - 62
-    Wk.leaf_anch.release(); Wk.leaf_anch2.release();
+    Wk.win.leaf_anch.release(); Wk.win.leaf_anch2.release();
     if (sb >= LEAF_T && w > 62) {
         const int64_t ng = (n >> LEAF_T) + 1;
-        Wk.leaf_anch.alloc((size_t)ng);
-        if (Wk.hyp) Wk.leaf_anch2.alloc((size_t)ng);
+        Wk.win.leaf_anch.alloc((size_t)ng);
+        if (Wk.hyp) Wk.win.leaf_anch2.alloc((size_t)ng);
         for (int pass = 0; pass < (Wk.hyp ? 2 : 1); pass++) {
             win_hist_scan<TC>(A, Wk, w - 62, pass);
-            hipLaunchKernelGGL(k_leaf_anchors, dim3((unsigned)cdiv(ng, 256)), dim3(256), 0, s, ng, n, pass == 0 ? A->pos.p : A->lpos.p, Wk.w_E.p,
-                               pass == 0 ? Wk.leaf_anch.p : Wk.leaf_anch2.p);
+            hipLaunchKernelGGL(k_leaf_anchors, dim3((unsigned)cdiv(ng, 256)), dim3(256), 0, s, ng, n, pass == 0 ? A->pos.p : A->lpos.p, Wk.win.w_E.p,
+                               pass == 0 ? Wk.win.leaf_anch.p : Wk.win.leaf_anch2.p);
         }
         CP_HIP(hipGetLastError());
     }
-    Wk.win_built = true; Wk.win_w = w;
+    Wk.win.built = true; Wk.win.w = w;
 }
 
 // the gap round's finishing kernels: fast variants first, then the SLOW ones over what they listed
@@ -3270,13 +2972,13 @@ template <typename TC, bool HYP>
 static void launch_gap(hipStream_t s, cp_csr_s *A, LayerWork<TC> &Wk, int tau, int nchunk, int gnr, RoundCounts *rc, int64_t n, const TC *W,
                        const DevModel<TC> &M, TC alpha, unsigned gg, unsigned gs_grid, unsigned gm, unsigned gslow_grid, int blk)
 {
-    GapCtx<TC, HYP> C{recs<HYP>(Wk.o_part), recs<HYP>(Wk.o_sub), Wk.o_spv.p, Wk.o_spec.p, Wk.o_tilePS.p, if_hyp<HYP>(Wk.o_tilePS2.p), A->pos32.p, A->next.p,
+    GapCtx<TC, HYP> C{recs<HYP>(Wk.ow.o_part), recs<HYP>(Wk.ow.o_sub), Wk.ow.o_spv.p, Wk.ow.o_spec.p, Wk.ow.o_tilePS.p, if_hyp<HYP>(Wk.ow.o_tilePS2.p), A->pos32.p, A->next.p,
                       if_hyp<HYP>(A->fpos32.p), if_hyp<HYP>(A->flast.p), W, blk};
-    auto *gs = reinterpret_cast<GapSegRec<TC, HYP> *>(Wk.g_seg.p);      // (sized for the larger record, like the Best buffers)
+    auto *gs = reinterpret_cast<GapSegRec<TC, HYP> *>(Wk.gp.g_seg.p);      // (sized for the larger record, like the Best buffers)
     const int32_t *lp = if_hyp<HYP>(A->lpos32.p), *lf = if_hyp<HYP>(A->lfirst.p);
-    int32_t *nl = if_hyp<HYP>(Wk.nlopt.p);
-#define GF_ARGS tau, nchunk, rc, n, Wk.o_toffs.p, C, Wk.o_tdesc.p, Wk.o_tb.p, Wk.o_rlen.p, A->prev.p, lp, lf, M, alpha, Wk.opt.p, Wk.nnopt.p, nl, Wk.fin.p, \
-                Wk.g_list.p, Wk.g_slot.p, Wk.fin_stamp, Wk.g_slow.p
+    int32_t *nl = if_hyp<HYP>(Wk.pl.nlopt.p);
+#define GF_ARGS tau, nchunk, rc, n, Wk.ow.o_toffs.p, C, Wk.ow.o_tdesc.p, Wk.ow.o_tb.p, Wk.ow.o_rlen.p, A->prev.p, lp, lf, M, alpha, Wk.pl.opt.p, Wk.pl.nnopt.p, nl, Wk.pl.fin.p, \
+                Wk.gp.g_list.p, Wk.gp.g_slot.p, Wk.pl.fin_stamp, Wk.gp.g_slow.p
     if (gnr == 2) {
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gap_finish<TC, HYP, 2, false>), dim3(gg), dim3(256), 0, s, GF_ARGS);
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gap_finish<TC, HYP, 2, true>), dim3(gslow_grid), dim3(256), 0, s, GF_ARGS);
@@ -3285,35 +2987,99 @@ static void launch_gap(hipStream_t s, cp_csr_s *A, LayerWork<TC> &Wk, int tau, i
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gap_finish<TC, HYP, 1, true>), dim3(gslow_grid), dim3(256), 0, s, GF_ARGS);
     }
 #undef GF_ARGS
-#define GS_ARGS tau, nchunk, rc, n, Wk.o_toffs.p, C, Wk.o_tdesc.p, Wk.o_tb.p, Wk.o_rlen.p, M, alpha, Wk.g_slot.p, gs, Wk.g_sslow.p
+#define GS_ARGS tau, nchunk, rc, n, Wk.ow.o_toffs.p, C, Wk.ow.o_tdesc.p, Wk.ow.o_tb.p, Wk.ow.o_rlen.p, M, alpha, Wk.gp.g_slot.p, gs, Wk.gp.g_sslow.p
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gap_seg<TC, HYP, false>), dim3(gs_grid), dim3(256), 0, s, GS_ARGS);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gap_seg<TC, HYP, true>), dim3(gslow_grid), dim3(256), 0, s, GS_ARGS);
 #undef GS_ARGS
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gap_merge<TC, HYP>), dim3(gm), dim3(256), 0, s, tau, nchunk, rc, n, Wk.o_toffs.p, Wk.o_tdesc.p, Wk.o_tb.p, A->pos32.p, A->prev.p,
-                       lp, lf, M, Wk.g_list.p, gs, Wk.opt.p, Wk.nnopt.p, nl, Wk.fin.p, Wk.fin_stamp);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gap_merge<TC, HYP>), dim3(gm), dim3(256), 0, s, tau, nchunk, rc, n, Wk.ow.o_toffs.p, Wk.ow.o_tdesc.p, Wk.ow.o_tb.p, A->pos32.p, A->prev.p,
+                       lp, lf, M, Wk.gp.g_list.p, gs, Wk.pl.opt.p, Wk.pl.nnopt.p, nl, Wk.pl.fin.p, Wk.pl.fin_stamp);
 }
 
 constexpr int64_t LB_MAX = 1 << 20;      // largest scan (elements) done in a single launch
 
-// Round A from a cached table T with the counts cnt / cnt2: the column-major kernel over the candidate tiles [tile0, tile1)
-// (`mirrored`: the table of the mirrored heads) or the row-major one over the table's `ntile` tiles, then the rows of more than LT
-// candidates (nrow_merge of them) merge their partials in `part`.
+// Round A from a cache with the table T (the cache's own, or a copy cut to the levels and tiles a windowed layer needs): the
+// column-major kernel over the candidate tiles [tile0, tile1) (`mirrored`: the table of the mirrored heads) or the row-major one
+// over the cache's tiles, then the rows of more than LT candidates (nrow_merge of them) merge their partials.
 template <typename TC, bool HYP>
-static void launch_round_a(hipStream_t s, cp_csr_s *A, LayerWork<TC> &Wk, const TC *W, const DevModel<TC> &M, TC alpha, const RATab &T, const DBuf<int32_t> &cnt,
-                           const DBuf<int32_t> &cnt2, const DBuf<Best<TC, true>> &part, int64_t ntile, int64_t nrow_merge, int64_t tile0, int64_t tile1,
+static void launch_round_a(const LayerCtx<TC> &C, LayerWork<TC> &Wk, const RaCache<TC> &Ra, const RATab &T, int64_t nrow_merge, int64_t tile0, int64_t tile1,
                            int bmin, bool mirrored, bool colmajor)
 {
-    int32_t *nl = if_hyp<HYP>(Wk.nlopt.p);
+    hipStream_t s = C.s;
+    cp_csr_s *A = C.A;
+    int32_t *nl = if_hyp<HYP>(Wk.pl.nlopt.p);
     if (colmajor)
         hipLaunchKernelGGL(HIP_KERNEL_NAME(mirrored ? k_ra_cols<TC, HYP, true> : k_ra_cols<TC, HYP, false>), dim3((unsigned)std::max<int64_t>(1, cdiv(tile1 - tile0, 4))), dim3(256), 0, s,
-                           T, cnt.p, if_hyp<HYP>(cnt2.p), A->pos32.p, W, M, alpha, Wk.opt.p, Wk.nnopt.p, nl, recs<HYP>(part), tile0, tile1, bmin);
+                           T, Ra.c.p, if_hyp<HYP>(Ra.c2.p), A->pos32.p, C.W, C.M, C.alpha, Wk.pl.opt.p, Wk.pl.nnopt.p, nl, recs<HYP>(Ra.part), tile0, tile1, bmin);
     else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ra_layer<TC, HYP>), dim3((unsigned)cdiv(ntile, 4)), dim3(256), 0, s, T, ntile, cnt.p, if_hyp<HYP>(cnt2.p), A->pos32.p, W, M,
-                           alpha, Wk.opt.p, Wk.nnopt.p, nl, recs<HYP>(part));
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ra_layer<TC, HYP>), dim3((unsigned)cdiv(Ra.ntile, 4)), dim3(256), 0, s, T, Ra.ntile, Ra.c.p, if_hyp<HYP>(Ra.c2.p), A->pos32.p, C.W, C.M,
+                           C.alpha, Wk.pl.opt.p, Wk.pl.nnopt.p, nl, recs<HYP>(Ra.part));
     if (nrow_merge > 0)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ra_merge<TC, HYP>), dim3((unsigned)cdiv(nrow_merge, 4)), dim3(256), 0, s, T, nrow_merge, recs<HYP>(part), Wk.opt.p,
-                           Wk.nnopt.p, nl);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ra_merge<TC, HYP>), dim3((unsigned)cdiv(nrow_merge, 4)), dim3(256), 0, s, T, nrow_merge, recs<HYP>(Ra.part), Wk.pl.opt.p,
+                           Wk.pl.nnopt.p, nl);
     CP_HIP(hipGetLastError());
+}
+
+// A full layer: round A of the rows' lowest blocks from the cached counts; what is left of round A for the generic round is the
+// last row in its upper planes
+template <typename TC, bool HYP>
+static void round_a_full(const LayerCtx<TC> &C, LayerWork<TC> &Wk)
+{
+    hipStream_t s = C.s;
+    if (!Wk.ra.built) { ProfScope ps(PROF_LINKS, s, 0.0); ra_build_std<TC>(C.A, Wk); }
+    ProfScope ps(PROF_RA, s, 16.0 * (double)Wk.ra.ntile * LT);
+    launch_round_a<TC, HYP>(C, Wk, Wk.ra, Wk.ra.tab, Wk.ra.nrow, 0, cdiv(C.n, LT), C.ra_bmin, false, !(g_opt_dbg & DBG_RA_ROWMAJOR));
+}
+
+// Windowed layer: the STANDARD heads of round A (rows with ctz == b < s, block [r - 2^b, r)) are the unconstrained scheme's
+// round-A rows of the levels below s -- same blocks, same layer-independent counts: k_ra_cols computes them for all rows
+// from the cache (60 B per candidate) and the generic round keeps the mirrored and common heads only.  The heads the layer
+// reads are those make_round lists -- within 2^(b+1) of the row tile in plane b <= s: their blocks start at rlo - 3 * 2^s or later.
+// `scope`: the stage's profile scope, opened here behind the table build and closed by the caller (the mirrored heads have always
+// been enqueued inside it).
+template <typename TC, bool HYP>
+static void round_a_win_std(const LayerCtx<TC> &C, LayerWork<TC> &Wk, std::optional<ProfScope> &scope)
+{
+    hipStream_t s = C.s;
+    const Geo &G = C.G;
+    const int64_t n = C.n, rlo = C.rlo, rhi = C.rhi;
+    if (!Wk.ra.built) { ProfScope ps(PROF_LINKS, s, 0.0); ra_build_std<TC>(C.A, Wk); }
+    RATab T2 = Wk.ra.tab;
+    T2.nbits = std::min<int32_t>(G.s, Wk.ra.tab.nbits);
+    const int64_t nrow2 = T2.nbits > 9 ? Wk.ra.tab.rbase[T2.nbits] : 0;
+    const int64_t c_lo = std::max<int64_t>(0, (rlo > 0 ? rlo : 0) - ((int64_t)4 << G.s)), c_hi = std::min<int64_t>(n, rhi);
+    const int64_t tile0 = c_lo / LT, tile1 = cdiv(c_hi, LT);
+    scope.emplace(PROF_RA, s, 60.0 * (double)(tile1 - tile0) * LT);
+    // (the standard heads below LEAF_T are rows inside a leaf group: the leaf pass computes them; the MIRRORED heads of those
+    //  levels include the multiples of 64 -- every row has a task in every plane -- and stay)
+    launch_round_a<TC, HYP>(C, Wk, Wk.ra, T2, nrow2, tile0, tile1, C.ra_bmin, false, true);
+}
+
+// Windowed layer: the MIRRORED heads of round A the same way, from their own table (per level the tiles of the rows near the
+// window); false: the table is empty, the heads stay generic tasks
+template <typename TC, bool HYP>
+static bool round_a_win_mir(const LayerCtx<TC> &C, LayerWork<TC> &Wk)
+{
+    hipStream_t s = C.s;
+    const Geo &G = C.G;
+    const int64_t n = C.n, rlo = C.rlo, rhi = C.rhi;
+    if (!Wk.mir.built || Wk.mir.w != G.w) { ProfScope ps2(PROF_LINKS, s, 0.0); ra_build_mir<TC>(C.A, Wk); }
+    if (Wk.mir.ntile <= 0) return false;
+    RATab T3 = Wk.mir.tab;
+    const int64_t r_lo = std::max<int64_t>(1, (rlo > 0 ? rlo : 0) - ((int64_t)4 << G.s)), r_hi = std::min<int64_t>(n, rhi);
+    double elems = 0;
+    for (int b = 0; b < T3.nbits; b++) {
+        const int64_t u_lo = std::max<int64_t>(0, (r_lo >> (b + 1)) - 1), u_hi = r_hi >> (b + 1);        // rows u_lo .. u_hi - 1
+        T3.tlo[b] = T3.tbase[b] + ((u_lo << b) / LT);
+        T3.thi[b] = std::min<int64_t>(T3.tbase[b + 1], T3.tbase[b] + cdiv(std::max<int64_t>(u_hi, 0) << b, LT));
+        elems += (double)std::max<int64_t>(0, T3.thi[b] - T3.tlo[b]) * LT;
+    }
+    // column-major like the standard heads (z = p + w + 1: the blocks of the rows r_lo .. r_hi lie in [r_lo, r_hi + 2^s)); the
+    // row-major kernel reads 16 B per (candidate, level) instead of 4
+    const bool mcols = !(g_opt_dbg & DBG_MIR_ROWMAJOR);
+    const int64_t zt0 = r_lo / LT, zt1 = cdiv(std::min<int64_t>(n + G.w + 1, r_hi + ((int64_t)1 << G.s) + 1), LT);
+    ProfScope ps2(PROF_RA, s, mcols ? 80.0 * (double)(zt1 - zt0) * LT : 16.0 * elems);
+    launch_round_a<TC, HYP>(C, Wk, Wk.mir, T3, Wk.mir.nrow, zt0, zt1, 0, true, mcols);
+    return true;
 }
 
 // cp_set_option("dbg", DBG_POISON [+ DBG_POISON_ZERO]): fills buffers a stage must write before it reads (null: not of this variant)
@@ -3324,22 +3090,223 @@ static void poison_fill(hipStream_t s, std::initializer_list<std::pair<void *, s
     for (const auto &b : bufs) if (b.first) CP_HIP(hipMemsetAsync(b.first, pat, b.second, s));
 }
 
-// Runs the rounds of one layer.  `spec`: the per-round counts of the PREVIOUS layer (Wk.pred) size the grids, the buffers and
-// decide which stages are launched; every kernel reads its true loop bounds from the device (RoundCounts) and walks them with
-// grid strides, so a wrong prediction costs time, never correctness -- except a stage skipped or a buffer too small, which
-// run_layer reports (false) after the layer and the caller redoes the layer with spec = false: one host sync per round brings
-// the exact counts back before the dependent launches (the only mode of the first layer).
+// ------------------------------------------------------------------ the stages of a round, each as the host function run_layer calls
+// A stage function takes the layer's context, the work object, the round and its counts.
+// The right pass of a tau round, both counters.  (Clearing the counters the chunks of a row add into is the one use the driver
+// still has for k_setup.)
 template <typename TC, bool HYP>
-static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W, TC *cst_out, int32_t *ptr_out, LayerWork<TC> &Wk,
-                      int64_t rlo, int64_t rhi, bool spec, bool allow_force)
+static void right_pass(const LayerCtx<TC> &C, LayerWork<TC> &Wk, const RoundDesc &R)
+{
+    hipStream_t s = C.s;
+    cp_csr_s *A = C.A;
+    int64_t cols = (((C.n >> R.tau) + 1) >> 1) << R.tau;
+    ProfScope ps(PROF_RPASS, s, 4.0 * (C.avg_deg + C.self_deg) * (double)cols + 8.0 * (double)R.ntask);
+    if (((int64_t)1 << R.tau) > g_opt_rpass_ch)   // several chunks per row accumulate with atomics: clear first
+        hipLaunchKernelGGL(k_setup, dim3((unsigned)cdiv(R.ntask, 256)), dim3(256), 0, s, R, Wk.pl.opt.p, Wk.pl.nnopt.p, Wk.pl.cr.p, 1,
+                           Wk.tk.tdesc.p, A->pos32.p, Wk.tk.tb.p, Wk.tk.len.p, (const int32_t *)nullptr, if_hyp<HYP>(Wk.pl.crl.p), (int32_t *)nullptr);
+    launch_rpass(s, R, C.nbits, C.n, C.rlo, C.rhi, A->pos.p, A->prev.p, 0, Wk.pl.opt.p, Wk.pl.cr.p, C.avg_deg);                   // prev[q] < B
+    if (HYP) launch_rpass(s, R, C.nbits, C.n, C.rlo, C.rhi, A->lpos.p, A->lfirst.p, 1, Wk.pl.opt.p, Wk.pl.crl.p, C.self_deg);      // rows ending in the column with first >= B
+}
+
+// round A: the anchors of the last row's tasks in the planes above its lowest bit
+template <typename TC, bool HYP>
+static void last_row_counts(const LayerCtx<TC> &C, LayerWork<TC> &Wk, const RoundDesc &R)
+{
+    cp_csr_s *A = C.A;
+    CP_HIP(hipMemsetAsync(Wk.pl.last_s0.p, 0, Wk.pl.last_s0.bytes(), C.s));
+    hipLaunchKernelGGL(k_last_row_counts, dim3(1024), dim3(256), 0, C.s, R, A->pos32.p, A->prev.p, if_hyp<HYP>(A->lpos32.p), if_hyp<HYP>(A->lfirst.p),
+                       Wk.pl.last_s0.p, Wk.pl.fin.p);
+}
+
+// Set-up of a round: one lane per task finishes the short ones and lists the others
+template <typename TC, bool HYP>
+static void setup_tasks(const LayerCtx<TC> &C, LayerWork<TC> &Wk, const RoundDesc &R, RoundCounts *rc, int32_t own_min)
+{
+    hipStream_t s = C.s;
+    cp_csr_s *A = C.A;
+    // per task: four gathers from the plane arrays + the record; short tasks also step over their columns here
+    ProfScope ps(PROF_SETUP, s, 29.0 * (double)R.ntask);
+    const int sbs = (int)g_opt_setup_bs;          // lanes per block: one list atomic per block, but the block's waves meet at two barriers
+    dim3 sgrid((unsigned)cdiv(R.ntask, sbs));
+    if (!R.isA) {                                // one grid row per bit plane above tau
+        int64_t mx = 1;
+        for (int bb = R.tau + 1; bb < C.nbits; bb++) mx = std::max<int64_t>(mx, R.tbase[bb + 1] - R.tbase[bb]);
+        sgrid = dim3((unsigned)cdiv(mx, sbs), (unsigned)std::max(1, C.nbits - R.tau - 1));
+    }
+    // (nlopt, crl, tS0l, o_tS0l and w_anch2 are read by the hyperedge variant only; null or stale for the other)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_setup_short<TC, HYP>), sgrid, dim3(sbs), 0, s, R, Wk.pl.opt.p, Wk.pl.nnopt.p, Wk.pl.nlopt.p, Wk.pl.cr.p, Wk.pl.crl.p, A->pos32.p,
+                       A->next.p, if_hyp<HYP>(A->fpos32.p), if_hyp<HYP>(A->flast.p), C.W, C.M, C.alpha, Wk.tk.tdesc.p, Wk.tk.tb.p, Wk.tk.len.p, Wk.tk.tS0l.p, &rc->nlong,
+                       (int32_t)g_opt_short_t, (int32_t)g_opt_short_e, C.own_tiles ? Wk.ow.o_tdesc.p : (int4 *)nullptr, Wk.ow.o_tb.p, Wk.ow.o_rlen.p, Wk.ow.o_ntl.p,
+                       Wk.ow.o_tS0l.p, &rc->nown, &rc->own_steps, own_min,
+                       (int32_t)std::min<size_t>(Wk.ow.o_ntl.n, (size_t)INT32_MAX), &rc->err, Wk.pl.fin.p, Wk.pl.last_s0.p,
+                       (g_opt_dbg & DBG_COUNT_NONTRIVIAL) ? &rc->_pad : (int32_t *)nullptr, Wk.win.w_anch.p, Wk.win.w_anch2.p, C.pzp, C.oblk);
+}
+
+// Both scans of a round read their element count on the device; one launch holds them and the round's verdict
+template <typename TC>
+static void round_scans(const LayerCtx<TC> &C, LayerWork<TC> &Wk, const RoundDesc &R, RoundCounts *rc)
+{
+    hipStream_t s = C.s;
+    ProfScope ps(PROF_SCAN, s, 12.0 * (double)R.ntask);
+    const bool tiny = C.spec && (g_opt_dbg & DBG_TINY_BUFFERS);       // test: pretend the buffers sized from the prediction are too small
+    const int64_t capT = C.spec ? (tiny ? (int64_t)64 : (int64_t)Wk.fl.loc.n) : INT64_MAX, capNT = C.spec ? (tiny ? (int64_t)1 : (int64_t)Wk.ow.o_rec.n) : INT64_MAX;
+    const int64_t nm = std::min<int64_t>(R.ntask, (int64_t)Wk.ow.o_ntl.n);
+    if (R.ntask <= LB_MAX) {
+        launch_round_scans(rc, Wk.tk.len.p, Wk.tk.offs.p, R.ntask, Wk.ow.o_ntl.p, Wk.ow.o_toffs.p, nm, C.own_tiles, capT, capNT, Wk.sc.scanws, s);
+    } else {
+        // (single-launch scans take their block index from one counter: fine for a few hundred blocks, not for 27 000)
+        exclusive_scan_i32_devn(Wk.tk.len.p, Wk.tk.offs.p, &rc->nlong, R.ntask, &rc->T, Wk.sc.scratch, s);
+        if (C.own_tiles) exclusive_scan_i32_devn(Wk.ow.o_ntl.p, Wk.ow.o_toffs.p, &rc->nown, nm, &rc->NT, Wk.sc.scratch, s);
+        hipLaunchKernelGGL(k_round_finish, dim3(1), dim3(1), 0, s, rc, capT, capNT);
+    }
+}
+
+// ------------------------------------------------------------------ host side: the own-tile chain of a round
+// Map and stream + evaluate.  split (run_layer): 0: whole columns; 1: every tile of the launch is of a plane >= SPLIT_BMIN, their
+// number is NT; 2: the launch also holds tiles of the planes below -- the gap round tau = 6 with its plane-7 tiles, and every
+// round below it with gap_tau < 6 -- and k_own_map counts: 1 600 same-address atomics per launch cost it 17 us at config 3.
+template <typename TC, bool HYP>
+static void own_stream(const LayerCtx<TC> &C, LayerWork<TC> &Wk, const RoundDesc &R, RoundCounts *rc, const RoundCounts &P, bool gap, int split)
+{
+    hipStream_t s = C.s;
+    cp_csr_s *A = C.A;
+    const int64_t n = C.n;
+    const int oblk = C.oblk;
+    const int64_t gNT = C.spec ? (int64_t)Wk.ow.o_rec.n : P.NT;      // (capacity >= the true NT, checked)
+    poison_fill(s, {{Wk.ow.o_part.p, Wk.ow.o_part.bytes()}, {Wk.ow.o_tileS.p, Wk.ow.o_tileS.bytes()}, {Wk.ow.o_rec.p, Wk.ow.o_rec.bytes()}, {Wk.ow.o_srec.p, Wk.ow.o_srec.bytes()},
+                    {if_hyp<HYP>(Wk.ow.o_tileS2.p), Wk.ow.o_tileS2.bytes()}, {Wk.ow.o_items.p, Wk.ow.o_items.bytes()}, {Wk.ow.o_item_of.p, Wk.ow.o_item_of.bytes()},
+                    {Wk.ow.o_trec.p, Wk.ow.o_trec.bytes()}});
+    const unsigned mgrid = (unsigned)std::min<int64_t>(cdiv(gNT, 256), 8192);
+    if (split && !Wk.ow.split.built) {             // once per pattern, by the first round that streams them
+        ProfScope ps(PROF_LINKS, s, 8.0 * (double)A->N + 16.0 * (double)(C.nbits - SPLIT_BMIN) * (double)(n + 1));
+        split_build(A, Wk.ow.split, Wk.sc.scratch);
+    }
+    hipLaunchKernelGGL(k_own_map, dim3(mgrid), dim3(256), 0, s, rc, Wk.ow.o_toffs.p, Wk.ow.o_tdesc.p, Wk.ow.o_rlen.p, Wk.ow.o_rec.p, Wk.ow.o_task.p,
+                       Wk.ow.o_tb.p, gap ? Wk.ow.o_hi.p : (int32_t *)nullptr, R.tau, n, oblk, oblk ? Wk.ow.b_cnt.p : (int32_t *)nullptr, Wk.ow.o_brank.p,
+                       gap ? (int2 *)nullptr : Wk.ow.o_items.p, Wk.ow.o_item_of.p, split);
+    ProfScope ps(gap ? PROF_GAPSTREAM : PROF_OWN, s, C.own_bytes(Wk.ow.split, R.tau, split != 0, (double)P.own_steps));
+    if (oblk) {                       // the tile ids by column block (counted in k_own_map): ~10^5 tiles, a counting sort
+        exclusive_scan_i32_lb(Wk.ow.b_cnt.p, Wk.ow.b_start.p, Wk.ow.b_n.p, Wk.ow.b_nblk, nullptr, Wk.sc.scanws, s);
+        hipLaunchKernelGGL(k_blk_order, dim3(mgrid), dim3(256), 0, s, rc, Wk.ow.o_rec.p, Wk.ow.o_brank.p, Wk.ow.b_start.p, Wk.ow.o_border.p, Wk.ow.o_srec.p, Wk.ow.b_cnt.p);
+    }
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(gap ? k_lpass_own<TC, HYP, true> : k_lpass_own<TC, HYP, false>), dim3((unsigned)cdiv(gNT, 4)), dim3(256), 0, s,
+                       R.isA, rc,
+                       oblk ? Wk.ow.o_border.p : (const int32_t *)nullptr, A->pos32.p, A->next.p, if_hyp<HYP>(A->fpos32.p), if_hyp<HYP>(A->flast.p),
+                       Wk.ow.o_tileS.p, Wk.ow.o_tileS2.p, Wk.ow.o_rec.p, Wk.ow.o_srec.p, C.W, C.M, C.alpha, recs<HYP>(Wk.ow.o_part), R.tau, Wk.ow.o_hi.p, Wk.ow.o_spec.p,
+                       (int)((g_opt_dbg & DBG_GAP_ALL_SPECIAL) != 0), recs<HYP>(Wk.ow.o_sub), Wk.ow.o_spv.p, A->col.p, if_hyp<HYP>(A->ffirst.p),
+                       split ? Wk.ow.split.vnext.p : (const int32_t *)nullptr, Wk.ow.split.vpos.p, Wk.ow.split.vsa.p, (int64_t)(n + 1));
+}
+
+// The tail of the chain outside the gap rounds: one launch, a lane per task of up to FIX_SERIAL tiles, a block per listed trip
+// of the longer ones
+template <typename TC, bool HYP>
+static void own_merge(const LayerCtx<TC> &C, LayerWork<TC> &Wk, RoundCounts *rc, const RoundCounts &P)
+{
+    ProfScope ps(PROF_FIX, C.s, 24.0 * (double)P.NT);
+    launch_fix_own<TC, HYP>(C.s, rc, Wk.ow.o_toffs.p, recs<HYP>(Wk.ow.o_part), Wk.ow.o_tdesc.p, Wk.ow.o_tb.p, if_hyp<HYP>(Wk.ow.o_tS0l.p), Wk.ow.o_tileS.p,
+                            if_hyp<HYP>(Wk.ow.o_tileS2.p), C.M, Wk.pl.opt.p, Wk.pl.nnopt.p, if_hyp<HYP>(Wk.pl.nlopt.p), C.n, Wk.ow.o_items.p, Wk.ow.o_item_of.p, Wk.ow.o_trec.p,
+                            Wk.ow.o_tick.p, C.spec ? grow_pred(P.NT) : P.NT, C.spec ? grow_pred(P.nown) : P.nown);
+}
+
+// The tail of the own-tile chain in a gap round: the tiles' prefix, then every row of the gaps gets its winner
+template <typename TC, bool HYP>
+static void gap_finish(const LayerCtx<TC> &C, LayerWork<TC> &Wk, const RoundDesc &R, RoundCounts *rc, const RoundCounts &P)
+{
+    hipStream_t s = C.s;
+    const int64_t gown = C.spec ? grow_pred(P.nown) : P.nown;
+    {
+        // the gap kernels look a tile's prefix up at random: a device-wide scan of the tile counts.  (The other rounds need
+        // sums inside one task only: k_fix_own makes them from o_tileS.)
+        ProfScope ps(PROF_CARRY, s, 12.0 * (double)P.NT);
+        const int32_t *ntp = reinterpret_cast<const int32_t *>(&rc->NT);       // (NT < 2^31: the low word)
+        exclusive_scan_i32_lb(Wk.ow.o_tileS.p, Wk.ow.o_tilePS.p, ntp, (int64_t)Wk.ow.o_tileS.n, nullptr, Wk.sc.scanws, s);
+        if (HYP) exclusive_scan_i32_lb(Wk.ow.o_tileS2.p, Wk.ow.o_tilePS2.p, ntp, (int64_t)Wk.ow.o_tileS.n, nullptr, Wk.sc.scanws, s);
+    }
+    // every row of the gaps gets its winner: one wave per (task, 64 rows); tasks of more than GAPSEG tiles in two steps
+    ProfScope ps(PROF_GAP, s, 24.0 * (double)P.NT);
+    const int nchunk = (int)std::max<int64_t>(1, ((int64_t)2 << R.tau) / 64);
+    const size_t ncap = Wk.ow.o_rec.n / GAPSEG + 2;
+    Wk.gp.g_list.ensure(ncap); Wk.gp.g_slot.ensure(2 * ncap);
+    Wk.gp.g_seg.ensure((2 * ncap) * (size_t)nchunk * 64 * sizeof(GapSegRec<TC, true>));
+    // items that meet a tile with more than SMAX specials are listed by the fast kernels and redone by the SLOW ones
+    Wk.gp.g_slow.ensure((size_t)gown * (size_t)nchunk + 64); Wk.gp.g_sslow.ensure((2 * ncap) * (size_t)nchunk + 64);
+    CP_REQUIRE((int64_t)gown * nchunk < INT32_MAX && (int64_t)(2 * ncap) * nchunk < INT32_MAX, CP_EINTERNAL, "gap work index beyond 32 bits");
+    const int gnr = (g_opt_gap_nr >= 2 && nchunk >= 2) ? 2 : 1;       // 64-row chunks per wave of k_gap_finish
+    unsigned gg = (unsigned)std::min<int64_t>(cdiv(gown * cdiv((int64_t)nchunk, gnr), 4), 16384);
+    unsigned gs_grid = (unsigned)std::min<int64_t>(cdiv((int64_t)(2 * ncap) * nchunk, 4), 8192);
+    unsigned gm = (unsigned)std::min<int64_t>(cdiv((int64_t)ncap * nchunk, 4), 4096);
+    const unsigned gslow_grid = 2048;                               // (grid-stride over the device-side counts n_gslow / n_sslow: usually none)
+    launch_gap<TC, HYP>(s, C.A, Wk, R.tau, nchunk, gnr, rc, C.n, C.W, C.M, C.alpha, gg, gs_grid, gm, gslow_grid, C.oblk);
+}
+
+// ------------------------------------------------------------------ host side: the flattened chain of a round (the tasks' number: rc->nlong)
+// the grid's tile count: the buffers' capacity in a speculative layer (>= the true tile count, checked by the round's verdict)
+template <typename TC>
+static int64_t flat_gtile(const LayerCtx<TC> &C, const LayerWork<TC> &Wk, const RoundCounts &P) { return C.spec ? (int64_t)Wk.fl.tileS.n : cdiv(P.T, LT); }
+
+// tile table and stream
+template <typename TC, bool HYP>
+static void flat_stream(const LayerCtx<TC> &C, LayerWork<TC> &Wk, const RoundDesc &R, RoundCounts *rc, const RoundCounts &P)
+{
+    hipStream_t s = C.s;
+    cp_csr_s *A = C.A;
+    const int64_t gtile = flat_gtile(C, Wk, P);
+    poison_fill(s, {{Wk.fl.loc.p, Wk.fl.loc.bytes()}, {if_hyp<HYP>(Wk.fl.loc2.p), Wk.fl.loc2.bytes()}, {Wk.fl.partL.p, Wk.fl.partL.bytes()}, {Wk.fl.partR.p, Wk.fl.partR.bytes()},
+                    {Wk.fl.tileS.p, Wk.fl.tileS.bytes()}, {if_hyp<HYP>(Wk.fl.tileS2.p), Wk.fl.tileS2.bytes()}});
+    hipLaunchKernelGGL(k_tile_t0, dim3((unsigned)cdiv(gtile, 256)), dim3(256), 0, s, rc, Wk.tk.offs.p, Wk.tk.tdesc.p, Wk.fl.tile_t0.p,
+                       Wk.fl.tile_rec.p, (int)((g_opt_dbg & DBG_NO_INTERIOR) != 0), Wk.fl.taskR.p);
+    // algorithmic bytes of one launch: per flattened step the stepped column's link
+    // entries (4 B x N/n, plus 4 B x nonempty-rows/n for hyperedge costs), its colptr entry (8 B), the
+    // candidate's previous-layer cost (8 B) and the task-descriptor share (offsets/B/anchor/row, amortised 8 B)
+    ProfScope ps(PROF_EXPAND, s, (double)P.T * C.step_bytes);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lpass<TC, HYP>), dim3((unsigned)cdiv(gtile, 4)), dim3(256), 0, s, R, rc, Wk.tk.offs.p, Wk.tk.tdesc.p, Wk.tk.tS0l.p, Wk.tk.tb.p,
+                       A->pos32.p, A->next.p, if_hyp<HYP>(A->fpos32.p), if_hyp<HYP>(A->flast.p), Wk.pl.opt.p, Wk.pl.nnopt.p, Wk.pl.nlopt.p, Wk.fl.loc.p, Wk.fl.loc2.p,
+                       Wk.fl.tileS.p, Wk.fl.tileS2.p, Wk.fl.taskR.p, Wk.fl.tile_t0.p, Wk.fl.tile_rec.p, C.W, C.M, C.alpha, recs<HYP>(Wk.fl.partR), recs<HYP>(Wk.fl.partL));
+}
+
+// the tiles' carry, the tasks that span tiles, the merge
+template <typename TC, bool HYP>
+static void flat_finish(const LayerCtx<TC> &C, LayerWork<TC> &Wk, const RoundDesc &R, RoundCounts *rc, const RoundCounts &P)
+{
+    hipStream_t s = C.s;
+    cp_csr_s *A = C.A;
+    const int64_t gtile = flat_gtile(C, Wk, P);
+    {
+        ProfScope ps(PROF_CARRY, s, 12.0 * (double)cdiv(P.T, LT));
+        exclusive_scan_i32_lb(Wk.fl.tileS.p, Wk.fl.tilePS.p, &rc->ntile, (int64_t)Wk.fl.tileS.n, nullptr, Wk.sc.scanws, s);
+        if (HYP) exclusive_scan_i32_lb(Wk.fl.tileS2.p, Wk.fl.tilePS2.p, &rc->ntile, (int64_t)Wk.fl.tileS.n, nullptr, Wk.sc.scanws, s);
+    }
+    unsigned wgrid = (unsigned)std::min<int64_t>(cdiv(gtile, 4), 8192);     // the wave kernels walk work lists
+    {
+        ProfScope ps(PROF_EVAL, s, 0.0);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_span_short<TC, HYP>), dim3((unsigned)cdiv(gtile, 256)), dim3(256), 0, s, R, rc, Wk.tk.offs.p, Wk.tk.tdesc.p, Wk.tk.tS0l.p,
+                           Wk.tk.tb.p, A->pos32.p, Wk.fl.loc.p, Wk.fl.loc2.p, Wk.fl.tile_t0.p, Wk.fl.taskR.p, Wk.fl.tileS.p, Wk.fl.tileS2.p, recs<HYP>(Wk.fl.partR), C.W, C.M, C.alpha,
+                           Wk.pl.opt.p, Wk.pl.nnopt.p, if_hyp<HYP>(Wk.pl.nlopt.p), Wk.fl.open_list.p, Wk.fl.fix_list.p, Wk.fl.tile_rec.p);
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_open<TC, HYP>), dim3(wgrid), dim3(256), 0, s, R, rc, Wk.tk.offs.p, Wk.tk.tdesc.p, Wk.tk.tS0l.p, A->pos32.p, Wk.fl.loc.p,
+                           Wk.fl.loc2.p, Wk.fl.tile_t0.p, Wk.fl.tilePS.p, if_hyp<HYP>(Wk.fl.tilePS2.p), C.W, C.M, C.alpha, recs<HYP>(Wk.fl.partL), Wk.fl.open_list.p);
+    }
+    {
+        ProfScope ps(PROF_FIX, s, 8.0 * (double)cdiv(P.T, LT));
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fix<TC, HYP>), dim3(wgrid), dim3(256), 0, s, rc, Wk.tk.offs.p, Wk.fl.taskR.p, recs<HYP>(Wk.fl.partL), recs<HYP>(Wk.fl.partR),
+                           Wk.tk.tdesc.p, Wk.tk.tb.p, Wk.pl.opt.p, Wk.pl.nnopt.p, if_hyp<HYP>(Wk.pl.nlopt.p), C.n + 1, Wk.fl.fix_list.p, Wk.fl.tile_rec.p, Wk.fl.tilePS.p,
+                           if_hyp<HYP>(Wk.fl.tilePS2.p), if_hyp<HYP>(Wk.tk.tS0l.p), C.M);
+    }
+    CP_HIP(hipGetLastError());
+}
+
+// Begins a layer ON THE STREAM and returns what it fixes once.  Enqueued here, in this order: the clear of the round counters, of
+// the block counts and the tickets where they may be dirty, the poison fills (poison mode), and the clear of the `fin` plane when
+// the layer's new stamp wraps; on the host the layer takes its `fin` stamp and `planes_full` is set.
+template <typename TC, bool HYP>
+static LayerCtx<TC> begin_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W, TC *cst_out, int32_t *ptr_out, LayerWork<TC> &Wk,
+                                int64_t rlo, int64_t rhi, bool spec)
 {
     hipStream_t s = A->stream;
     const int64_t n = A->n;
-    constexpr bool hyp = HYP;                              // (== Wk.hyp: dp_total_layer picks the instance)
     const Geo G = Wk.G;
     const int nbits = G.win ? G.s + 1 : Wk.nbits;          // windowed layers: planes 0 .. s
     const double avg_deg = n > 0 ? (double)A->N / (double)n : 0.0;
-    const double self_deg = (hyp && n > 0) ? (double)A->nrows_nonempty / (double)n : 0.0;
+    const double self_deg = (HYP && n > 0) ? (double)A->nrows_nonempty / (double)n : 0.0;
     // bytes a step of the streaming kernels moves: the stepped column's link entries (4 B each; hyperedge costs: plus the rows starting
     // in it), its 32-bit column pointer (4 B), the candidate's previous-layer cost (8 B), and the tile's record + partial
     // (16 B + 16 B per 256 steps).  (Round 1 priced a step at 4 deg + 24 B -- 8-byte column pointers and a per-step descriptor share
@@ -3350,59 +3317,71 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
     // link entries (SplitLinks); the tiles of the gap rounds while "gap_split" is on too.  Not for hyperedge costs (the second list is not split) nor for windowed layers
     // (their blocks are not the Fenwick blocks).
     const bool split_layer = !HYP && !G.win && g_opt_own_split && nbits > SPLIT_BMIN;
-    // bytes the own-tile stream moves: split tiles read two column pointers and a prefix sum per step (20 B with the cost) and the
-    // variable entries of the round's planes, at most what the columns hold.  (Tiles of planes below SPLIT_BMIN in the same launch --
-    // the plane-7 tiles of the gap round tau = 6 -- are priced like the others.)
-    auto own_bytes = [&](int tau, bool sp, double steps) {
-        if (!sp) return steps * step_bytes;
-        double var = 0;
-        for (int b = std::max(tau + 1, SPLIT_BMIN); b < nbits && b - SPLIT_BMIN < Wk.split.nb; b++) var += (double)Wk.split.tot[b - SPLIT_BMIN];
-        return steps * (20.0 + 32.0 / (double)LT) + 4.0 * std::min(var, avg_deg * steps);
-    };
-    const int NR = nbits + 1;
-    CP_HIP(hipMemsetAsync(Wk.rc.p, 0, sizeof(RoundCounts) * (size_t)NR, s));
+    CP_HIP(hipMemsetAsync(Wk.sp.rc.p, 0, sizeof(RoundCounts) * (size_t)(nbits + 1), s));
     const bool gaps = own_tiles && g_opt_gap_tau >= 0;
     // cp_set_option("own_blk", 0 | 1): the tile geometry of the own-tiled tasks (see k_own_map).  Fixed for the whole layer: the
     // tile counts of setup depend on it.
     const int oblk = g_opt_own_blk ? 1 : 0;
     if (oblk) {
         const int64_t nblk = n / LT + 1;                 // the blocks of the columns 0 .. n
-        if (Wk.b_nblk != nblk || !Wk.b_cnt.p) {
-            Wk.b_cnt.ensure((size_t)nblk); Wk.b_start.ensure((size_t)nblk + 1); Wk.b_n.ensure(1);
-            CP_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(Wk.b_n.p), (int)nblk, 1, s));
-            Wk.b_nblk = nblk;
-            Wk.b_dirty = true;
+        if (Wk.ow.b_nblk != nblk || !Wk.ow.b_cnt.p) {
+            Wk.ow.b_cnt.ensure((size_t)nblk); Wk.ow.b_start.ensure((size_t)nblk + 1); Wk.ow.b_n.ensure(1);
+            CP_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(Wk.ow.b_n.p), (int)nblk, 1, s));
+            Wk.ow.b_nblk = nblk;
+            Wk.ow.b_dirty = true;
         }
         // b_cnt is zero between rounds (k_blk_order puts back what k_own_map counted): cleared when allocated.  The clear after a
         // layer that did not come to its end in order is a safeguard only: k_own_map and k_blk_order are enqueued as a pair and
         // walk the same tiles (a dropped round: none), so only an error thrown between the two could leave counts behind.
-        if (Wk.b_dirty) CP_HIP(hipMemsetAsync(Wk.b_cnt.p, 0, Wk.b_cnt.bytes(), s));
-        Wk.b_dirty = true;
+        if (Wk.ow.b_dirty) CP_HIP(hipMemsetAsync(Wk.ow.b_cnt.p, 0, Wk.ow.b_cnt.bytes(), s));
+        Wk.ow.b_dirty = true;
     }
     // o_tick is zero between rounds the same way (the block that folds a task puts its ticket back): cleared when allocated and,
     // as a safeguard only, after a layer that did not come to its end in order
-    if (Wk.t_dirty) CP_HIP(hipMemsetAsync(Wk.o_tick.p, 0, Wk.o_tick.bytes(), s));
-    Wk.t_dirty = true;
+    if (Wk.ow.t_dirty) CP_HIP(hipMemsetAsync(Wk.ow.o_tick.p, 0, Wk.ow.o_tick.bytes(), s));
+    Wk.ow.t_dirty = true;
     // cp_set_option("poison", 1) (tests): every layer starts from planes full of an out-of-range column; the kernels that turn
     // plane cells into addresses count and clamp what they read of it.  The invariant behind the speculative layers -- "whatever a
     // layer that is NOT redone has read was written by that layer" -- then reads: hits > 0 implies the layer is flagged for a redo.
     int32_t *pzp = nullptr;
     if (g_opt_poison) {
-        Wk.pz.ensure(2);
-        pzp = Wk.pz.p;
-        CP_HIP(hipMemsetAsync(Wk.pz.p, 0, sizeof(int32_t) * 2, s));
-        CP_HIP(hipMemsetAsync(Wk.opt.p, 0x7F, Wk.opt.bytes(), s));
-        CP_HIP(hipMemsetAsync(Wk.nnopt.p, 0x7F, Wk.nnopt.bytes(), s));
-        if (hyp) CP_HIP(hipMemsetAsync(Wk.nlopt.p, 0x7F, Wk.nlopt.bytes(), s));
+        Wk.pl.pz.ensure(2);
+        pzp = Wk.pl.pz.p;
+        CP_HIP(hipMemsetAsync(Wk.pl.pz.p, 0, sizeof(int32_t) * 2, s));
+        CP_HIP(hipMemsetAsync(Wk.pl.opt.p, 0x7F, Wk.pl.opt.bytes(), s));
+        CP_HIP(hipMemsetAsync(Wk.pl.nnopt.p, 0x7F, Wk.pl.nnopt.bytes(), s));
+        if (HYP) CP_HIP(hipMemsetAsync(Wk.pl.nlopt.p, 0x7F, Wk.pl.nlopt.bytes(), s));
     }
-    // the rounds tau < LEAF_T are one pass over groups of 64 rows (dp_leaf.inc); windowed layers: when the window spans a group
+    // the rounds tau < LEAF_T are one pass over groups of 64 rows (dp_total_leaf.hip); windowed layers: when the window spans a group
     // (s >= 6) and no per-block table is asked for
-    const bool leaf = g_opt_leaf && (!G.win || (G.s >= LEAF_T && !g_opt_block_tables && Wk.leaf_anch.p));
-    Wk.planes_full = !leaf || g_opt_block_tables;
+    const bool leaf = g_opt_leaf && (!G.win || (G.s >= LEAF_T && !g_opt_block_tables && Wk.win.leaf_anch.p));
+    Wk.pl.planes_full = !leaf || g_opt_block_tables;
     // round A from the cached counts leaves the levels below LEAF_T to the leaf pass (DBG_RA_ALL_LEVELS: all levels, as without it)
-    const int ra_bmin = (leaf && !Wk.planes_full && !(g_opt_dbg & DBG_RA_ALL_LEVELS)) ? LEAF_T : 0;
+    const int ra_bmin = (leaf && !Wk.pl.planes_full && !(g_opt_dbg & DBG_RA_ALL_LEVELS)) ? LEAF_T : 0;
     // `fin` flags hold the layer's stamp: no 240 MB clear per layer (every attempt of a layer -- a redo included -- takes a new stamp)
-    if (++Wk.fin_stamp > 255 || Wk.fin_stamp <= 0) { CP_HIP(hipMemsetAsync(Wk.fin.p, 0, Wk.fin.bytes(), s)); Wk.fin_stamp = 1; }
+    if (++Wk.pl.fin_stamp > 255 || Wk.pl.fin_stamp <= 0) { CP_HIP(hipMemsetAsync(Wk.pl.fin.p, 0, Wk.pl.fin.bytes(), s)); Wk.pl.fin_stamp = 1; }
+    return LayerCtx<TC>{A, s, M, alpha, W, cst_out, ptr_out, n, rlo, rhi, G, nbits, spec, own_tiles, gaps, split_layer, leaf, oblk, ra_bmin, pzp,
+                        avg_deg, self_deg, step_bytes};
+}
+
+// Runs the rounds of one layer.  `spec`: the per-round counts of the PREVIOUS layer (Wk.sp.pred) size the grids, the buffers and
+// decide which stages are launched; every kernel reads its true loop bounds from the device (RoundCounts) and walks them with
+// grid strides, so a wrong prediction costs time, never correctness -- except a stage skipped or a buffer too small, which
+// run_layer reports (false) after the layer and the caller redoes the layer with spec = false: one host sync per round brings
+// the exact counts back before the dependent launches (the only mode of the first layer).
+// run_layer is the loop over the rounds: it decides which stage runs and with which counts; each stage is enqueued by the stage
+// function above.
+template <typename TC, bool HYP>
+static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W, TC *cst_out, int32_t *ptr_out, LayerWork<TC> &Wk,
+                      int64_t rlo, int64_t rhi, bool spec, bool allow_force)
+{
+    const LayerCtx<TC> C = begin_layer<TC, HYP>(A, M, alpha, W, cst_out, ptr_out, Wk, rlo, rhi, spec);
+    hipStream_t s = C.s;
+    const int64_t n = C.n;
+    const Geo G = C.G;
+    const int nbits = C.nbits;
+    int32_t *pzp = C.pzp;
+    const int NR = nbits + 1;
     std::vector<RoundCounts> used((size_t)NR);          // what the host sized each round with
     memset(used.data(), 0, sizeof(RoundCounts) * (size_t)NR);
     struct Patch { size_t idx; int rd; int kind; int tau; bool split; };
@@ -3410,301 +3389,89 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
     auto note = [&](int rd, int kind, int slot, int tau = 0, bool sp = false) {
         if (prof_active(slot)) patches.push_back({g_prof_pending.size() - 1, rd, kind, tau, sp});
     };
-    auto grow = [](int64_t v) { return v + (v >> 2) + 1024; };     // head room over the prediction
     bool any_forced = false;
-    std::vector<int8_t> split_mode((size_t)NR, 0);       // own_split per round (see the launch of k_own_map)
+    std::vector<int8_t> split_mode((size_t)NR, 0);       // own_split per round (see own_stream)
 
     for (int rd = 0; rd <= nbits; rd++) {
         RoundDesc R;
-        if (rd == 0) make_round(R, true, 0, nbits, n, rlo, rhi, G, Wk.win_aoff);
-        else make_round(R, false, nbits - rd, nbits, n, rlo, rhi, G, Wk.win_aoff);
-        R.fin_stamp = Wk.fin_stamp;
-        if (leaf && !R.isA && R.tau < LEAF_T) continue;
+        if (rd == 0) make_round(R, true, 0, nbits, n, rlo, rhi, G, Wk.win.aoff);
+        else make_round(R, false, nbits - rd, nbits, n, rlo, rhi, G, Wk.win.aoff);
+        R.fin_stamp = Wk.pl.fin_stamp;
+        if (C.leaf && !R.isA && R.tau < LEAF_T) continue;
         if (rd == 0 && g_opt_ra_cache && rlo <= 1 && rhi >= n && n >= 1 && !G.win) {
             // a full layer: round A of the rows' lowest blocks from the cached counts; what is left of round A below is the
             // last row in its upper planes
-            if (!Wk.ra_built) { ProfScope ps(PROF_LINKS, s, 0.0); ra_build_std<TC>(A, Wk); }
-            ProfScope ps(PROF_RA, s, 16.0 * (double)Wk.ra_ntile * LT);
-            launch_round_a<TC, HYP>(s, A, Wk, W, M, alpha, Wk.ra_tab, Wk.ra_c, Wk.ra_c2, Wk.ra_part, Wk.ra_ntile, Wk.ra_nrow, 0, cdiv(n, LT), ra_bmin, false,
-                                    !(g_opt_dbg & DBG_RA_ROWMAJOR));
+            round_a_full<TC, HYP>(C, Wk);
             R.a_nmain = 0; R.ntask = R.nextra + R.nlast;
         }
         if (rd == 0 && g_opt_ra_cache && G.win && G.s >= 1 && n >= 1 && !(g_opt_dbg & DBG_WIN_NO_RA_CACHE)) {
-            // Windowed layer: the STANDARD heads of round A (rows with ctz == b < s, block [r - 2^b, r)) are the unconstrained scheme's
-            // round-A rows of the levels below s -- same blocks, same layer-independent counts: k_ra_cols computes them for all rows
-            // from the cache (60 B per candidate) and the generic round keeps the mirrored and common heads only.  The heads the layer
-            // reads are those make_round lists -- within 2^(b+1) of the row tile in plane b <= s: their blocks start at rlo - 3 * 2^s or later.
-            if (!Wk.ra_built) { ProfScope ps(PROF_LINKS, s, 0.0); ra_build_std<TC>(A, Wk); }
-            RATab T2 = Wk.ra_tab;
-            T2.nbits = std::min<int32_t>(G.s, Wk.ra_tab.nbits);
-            const int64_t nrow2 = T2.nbits > 9 ? Wk.ra_tab.rbase[T2.nbits] : 0;
-            const int64_t c_lo = std::max<int64_t>(0, (rlo > 0 ? rlo : 0) - ((int64_t)4 << G.s)), c_hi = std::min<int64_t>(n, rhi);
-            const int64_t tile0 = c_lo / LT, tile1 = cdiv(c_hi, LT);
-            ProfScope ps(PROF_RA, s, 60.0 * (double)(tile1 - tile0) * LT);
-            // (the standard heads below LEAF_T are rows inside a leaf group: the leaf pass computes them; the MIRRORED heads of those
-            //  levels include the multiples of 64 -- every row has a task in every plane -- and stay)
-            launch_round_a<TC, HYP>(s, A, Wk, W, M, alpha, T2, Wk.ra_c, Wk.ra_c2, Wk.ra_part, Wk.ra_ntile, nrow2, tile0, tile1, ra_bmin, false, true);
+            // a windowed layer: the standard heads of round A from the cache, and the mirrored ones from theirs; the generic round
+            // keeps the common heads (and the mirrored ones where their table is empty or switched off)
+            std::optional<ProfScope> scope;       // of the standard heads: open until the mirrored ones are enqueued, as ever
+            round_a_win_std<TC, HYP>(C, Wk, scope);
             R.skip_std = 1;
-            if (!(g_opt_dbg & DBG_WIN_NO_MIR_CACHE)) {
-                // the MIRRORED heads the same way, from their own table (row-major kernel; per level the tiles of the rows near the window)
-                if (!Wk.mir_built || Wk.mir_w != G.w) { ProfScope ps2(PROF_LINKS, s, 0.0); ra_build_mir<TC>(A, Wk); }
-                if (Wk.mir_ntile > 0) {
-                    RATab T3 = Wk.mir_tab;
-                    const int64_t r_lo = std::max<int64_t>(1, (rlo > 0 ? rlo : 0) - ((int64_t)4 << G.s)), r_hi = std::min<int64_t>(n, rhi);
-                    double elems = 0;
-                    for (int b = 0; b < T3.nbits; b++) {
-                        const int64_t u_lo = std::max<int64_t>(0, (r_lo >> (b + 1)) - 1), u_hi = r_hi >> (b + 1);        // rows u_lo .. u_hi - 1
-                        T3.tlo[b] = T3.tbase[b] + ((u_lo << b) / LT);
-                        T3.thi[b] = std::min<int64_t>(T3.tbase[b + 1], T3.tbase[b] + cdiv(std::max<int64_t>(u_hi, 0) << b, LT));
-                        elems += (double)std::max<int64_t>(0, T3.thi[b] - T3.tlo[b]) * LT;
-                    }
-                    // column-major like the standard heads (z = p + w + 1: the blocks of the rows r_lo .. r_hi lie in [r_lo, r_hi + 2^s)); the
-                    // row-major kernel reads 16 B per (candidate, level) instead of 4
-                    const bool mcols = !(g_opt_dbg & DBG_MIR_ROWMAJOR);
-                    const int64_t zt0 = r_lo / LT, zt1 = cdiv(std::min<int64_t>(n + G.w + 1, r_hi + ((int64_t)1 << G.s) + 1), LT);
-                    ProfScope ps2(PROF_RA, s, mcols ? 80.0 * (double)(zt1 - zt0) * LT : 16.0 * elems);
-                    launch_round_a<TC, HYP>(s, A, Wk, W, M, alpha, T3, Wk.mir_c, Wk.mir_c2, Wk.mir_part, Wk.mir_ntile, Wk.mir_nrow, zt0, zt1, 0, true, mcols);
-                    R.skip_mir = 1;
-                }
-            }
+            if (!(g_opt_dbg & DBG_WIN_NO_MIR_CACHE) && round_a_win_mir<TC, HYP>(C, Wk)) R.skip_mir = 1;
         }
         if (R.ntask <= 0) continue;
         CP_REQUIRE(R.ntask <= Wk.max_tasks, CP_EINTERNAL, "a DP round has more tasks than the task buffers hold");
-        RoundCounts *rc = Wk.rc.p + rd;
-        const bool gap = gaps && !R.isA && R.tau <= g_opt_gap_tau;       // long tasks of this round finish all the rows of their gap
+        RoundCounts *rc = Wk.sp.rc.p + rd;
+        const bool gap = C.gaps && !R.isA && R.tau <= g_opt_gap_tau;       // long tasks of this round finish all the rows of their gap
         // In the rounds above the gap rounds the flattened stage (tile table, stream, two scans, span / open / fix: six dependent
         // launches, ~40 us) typically serves three or four medium tasks.  Where the last layer that ran it saw at most force_max (1024), every task
         // that is not finished in setup gets tiles of its own instead, and the stage disappears from the round.
-        const bool forced = allow_force && own_tiles && !gap && !R.isA && (size_t)rd < Wk.force_own.size() && Wk.force_own[(size_t)rd] &&
-                            (rhi - rlo + 1) <= 2 * Wk.force_rows && !(g_opt_dbg & DBG_NO_FORCE_OWN);
+        const bool forced = allow_force && C.own_tiles && !gap && !R.isA && (size_t)rd < Wk.sp.force_own.size() && Wk.sp.force_own[(size_t)rd] &&
+                            (rhi - rlo + 1) <= 2 * Wk.sp.force_rows && !(g_opt_dbg & DBG_NO_FORCE_OWN);
         any_forced |= forced;
-        if (!R.isA) {
-            int64_t cols = (((n >> R.tau) + 1) >> 1) << R.tau;
-            ProfScope ps(PROF_RPASS, s, 4.0 * (avg_deg + self_deg) * (double)cols + 8.0 * (double)R.ntask);
-            if (((int64_t)1 << R.tau) > g_opt_rpass_ch)   // several chunks per row accumulate with atomics: clear first
-                hipLaunchKernelGGL(k_setup, dim3((unsigned)cdiv(R.ntask, 256)), dim3(256), 0, s, R, Wk.opt.p, Wk.nnopt.p, Wk.cr.p, 1,
-                                   Wk.tdesc.p, A->pos32.p, Wk.tb.p, Wk.len.p, (const int32_t *)nullptr, if_hyp<HYP>(Wk.crl.p), (int32_t *)nullptr);
-            launch_rpass(s, R, nbits, n, rlo, rhi, A->pos.p, A->prev.p, 0, Wk.opt.p, Wk.cr.p, avg_deg);                   // prev[q] < B
-            if (hyp) launch_rpass(s, R, nbits, n, rlo, rhi, A->lpos.p, A->lfirst.p, 1, Wk.opt.p, Wk.crl.p, self_deg);      // rows ending in the column with first >= B
-        }
-        if (R.isA && R.nlast > 0) {
-            CP_HIP(hipMemsetAsync(Wk.last_s0.p, 0, Wk.last_s0.bytes(), s));
-            hipLaunchKernelGGL(k_last_row_counts, dim3(1024), dim3(256), 0, s, R, A->pos32.p, A->prev.p, if_hyp<HYP>(A->lpos32.p), if_hyp<HYP>(A->lfirst.p),
-                               Wk.last_s0.p, Wk.fin.p);
-        }
-        {
-            // per task: four gathers from the plane arrays + the record; short tasks also step over their columns here
-            ProfScope ps(PROF_SETUP, s, 29.0 * (double)R.ntask);
-            const int sbs = (int)g_opt_setup_bs;          // lanes per block: one list atomic per block, but the block's waves meet at two barriers
-            dim3 sgrid((unsigned)cdiv(R.ntask, sbs));
-            if (!R.isA) {                                // one grid row per bit plane above tau
-                int64_t mx = 1;
-                for (int bb = R.tau + 1; bb < nbits; bb++) mx = std::max<int64_t>(mx, R.tbase[bb + 1] - R.tbase[bb]);
-                sgrid = dim3((unsigned)cdiv(mx, sbs), (unsigned)std::max(1, nbits - R.tau - 1));
-            }
-            // (nlopt, crl, tS0l, o_tS0l and w_anch2 are read by the hyperedge variant only; null or stale for the other)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_setup_short<TC, HYP>), sgrid, dim3(sbs), 0, s, R, Wk.opt.p, Wk.nnopt.p, Wk.nlopt.p, Wk.cr.p, Wk.crl.p, A->pos32.p,
-                               A->next.p, if_hyp<HYP>(A->fpos32.p), if_hyp<HYP>(A->flast.p), W, M, alpha, Wk.tdesc.p, Wk.tb.p, Wk.len.p, Wk.tS0l.p, &rc->nlong,
-                               (int32_t)g_opt_short_t, (int32_t)g_opt_short_e, own_tiles ? Wk.o_tdesc.p : (int4 *)nullptr, Wk.o_tb.p, Wk.o_rlen.p, Wk.o_ntl.p,
-                               Wk.o_tS0l.p, &rc->nown, &rc->own_steps, (int32_t)(forced ? 2 : gap ? g_opt_gap_min : g_opt_own_min),
-                               (int32_t)std::min<size_t>(Wk.o_ntl.n, (size_t)INT32_MAX), &rc->err, Wk.fin.p, Wk.last_s0.p,
-                               (g_opt_dbg & DBG_COUNT_NONTRIVIAL) ? &rc->_pad : (int32_t *)nullptr, Wk.w_anch.p, Wk.w_anch2.p, pzp, oblk);
-        }
+        if (!R.isA) right_pass<TC, HYP>(C, Wk, R);
+        if (R.isA && R.nlast > 0) last_row_counts<TC, HYP>(C, Wk, R);
+        setup_tasks<TC, HYP>(C, Wk, R, rc, (int32_t)(forced ? 2 : gap ? g_opt_gap_min : g_opt_own_min));
         RoundCounts P;                                   // the counts this round is sized with
         if (spec) {
-            P = Wk.pred[(size_t)rd];
-            if (Wk.pred_scale != 1.0) {              // (windowed layers: the previous layer's tile had another number of rows)
-                auto sc = [&](int64_t v) { return (int64_t)((double)v * Wk.pred_scale) + (v > 0 ? 1 : 0); };
+            P = Wk.sp.pred[(size_t)rd];
+            if (Wk.sp.pred_scale != 1.0) {              // (windowed layers: the previous layer's tile had another number of rows)
+                auto sc = [&](int64_t v) { return (int64_t)((double)v * Wk.sp.pred_scale) + (v > 0 ? 1 : 0); };
                 P.nlong = (int32_t)sc(P.nlong); P.nown = (int32_t)sc(P.nown); P.T = sc(P.T); P.NT = sc(P.NT);
                 P.own_steps = (unsigned long long)sc((int64_t)P.own_steps);
             }
             if ((g_opt_dbg & DBG_MISPREDICT) && (rd & 1)) { P.nown = 0; P.NT = 0; P.nlong = 0; P.T = 0; }      // test: a prediction that skips stages with work
             // buffers from the prediction (grown only here; the round's verdict, k_round_scans, checks the true totals against them)
-            Wk.ensure_own((size_t)grow(P.NT));
-            Wk.ensure_flat((size_t)grow(P.T));
+            Wk.ow.ensure_own(Wk.hyp, (size_t)grow_pred(P.NT));
+            Wk.fl.ensure_flat(Wk.hyp, (size_t)grow_pred(P.T));
         }
-        {
-            // both scans read their element count on the device; one launch holds them and the round's verdict
-            ProfScope ps(PROF_SCAN, s, 12.0 * (double)R.ntask);
-            const bool tiny = spec && (g_opt_dbg & DBG_TINY_BUFFERS);       // test: pretend the buffers sized from the prediction are too small
-            const int64_t capT = spec ? (tiny ? (int64_t)64 : (int64_t)Wk.loc.n) : INT64_MAX, capNT = spec ? (tiny ? (int64_t)1 : (int64_t)Wk.o_rec.n) : INT64_MAX;
-            const int64_t nm = std::min<int64_t>(R.ntask, (int64_t)Wk.o_ntl.n);
-            if (R.ntask <= LB_MAX) {
-                launch_round_scans(rc, Wk.len.p, Wk.offs.p, R.ntask, Wk.o_ntl.p, Wk.o_toffs.p, nm, own_tiles, capT, capNT, Wk.scanws, s);
-            } else {
-                // (single-launch scans take their block index from one counter: fine for a few hundred blocks, not for 27 000)
-                exclusive_scan_i32_devn(Wk.len.p, Wk.offs.p, &rc->nlong, R.ntask, &rc->T, Wk.scratch, s);
-                if (own_tiles) exclusive_scan_i32_devn(Wk.o_ntl.p, Wk.o_toffs.p, &rc->nown, nm, &rc->NT, Wk.scratch, s);
-                hipLaunchKernelGGL(k_round_finish, dim3(1), dim3(1), 0, s, rc, capT, capNT);
-            }
-        }
+        round_scans<TC>(C, Wk, R, rc);
         if (!spec) {
             CP_HIP(hipMemcpyAsync(&P, rc, sizeof(P), hipMemcpyDeviceToHost, s));
             CP_HIP(hipStreamSynchronize(s));
-            Wk.ensure_own((size_t)P.NT);
-            Wk.ensure_flat((size_t)P.T);
+            Wk.ow.ensure_own(Wk.hyp, (size_t)P.NT);
+            Wk.fl.ensure_flat(Wk.hyp, (size_t)P.T);
         }
         used[(size_t)rd] = P;
         if (g_opt_dbg & DBG_PRINT_ROUNDS) fprintf(stderr, "round isA=%d tau=%d ntask=%lld %s long=%d own=%d T=%lld NT=%lld nontrivial=%d\n", R.isA, R.tau, (long long)R.ntask,
                                    spec ? "predicted" : "exact", P.nlong, P.nown, (long long)P.T, (long long)P.NT, P._pad);
         if (P.nown > 0 && P.NT > 0) {
-            // ---- long tasks with tiles of their own: map, stream + evaluate, merge
-            const int64_t gNT = spec ? (int64_t)Wk.o_rec.n : P.NT, gown = spec ? grow(P.nown) : P.nown;      // (capacity >= the true NT, checked)
-            poison_fill(s, {{Wk.o_part.p, Wk.o_part.bytes()}, {Wk.o_tileS.p, Wk.o_tileS.bytes()}, {Wk.o_rec.p, Wk.o_rec.bytes()}, {Wk.o_srec.p, Wk.o_srec.bytes()},
-                            {if_hyp<HYP>(Wk.o_tileS2.p), Wk.o_tileS2.bytes()}, {Wk.o_items.p, Wk.o_items.bytes()}, {Wk.o_item_of.p, Wk.o_item_of.bytes()},
-                            {Wk.o_trec.p, Wk.o_trec.bytes()}});
-            const unsigned mgrid = (unsigned)std::min<int64_t>(cdiv(gNT, 256), 8192);
-            // (1: every tile of the launch is of a plane >= SPLIT_BMIN, their number is NT; 2: the launch also holds tiles of the planes
-            //  below -- the gap round tau = 6 with its plane-7 tiles, and every round below it with gap_tau < 6 -- and k_own_map
-            //  counts: 1 600 same-address atomics per launch cost it 17 us at config 3)
+            // ---- long tasks with tiles of their own: map, stream + evaluate, then the gap passes or the merge
             // (gap rounds: cp_set_option("gap_split", 0 | 1), effective while own_split is on)
-            const int split = !(split_layer && !R.isA && (!gap || g_opt_gap_split)) ? 0 : R.tau + 1 >= SPLIT_BMIN ? 1 : 2;
+            const int split = !(C.split_layer && !R.isA && (!gap || g_opt_gap_split)) ? 0 : R.tau + 1 >= SPLIT_BMIN ? 1 : 2;
             split_mode[(size_t)rd] = (int8_t)(gap ? -split : split);
-            if (split && !Wk.split.built) {             // once per pattern, by the first round that streams them
-                ProfScope ps(PROF_LINKS, s, 8.0 * (double)A->N + 16.0 * (double)(nbits - SPLIT_BMIN) * (double)(n + 1));
-                split_build(A, Wk.split, Wk.scratch);
-            }
-            hipLaunchKernelGGL(k_own_map, dim3(mgrid), dim3(256), 0, s, rc, Wk.o_toffs.p, Wk.o_tdesc.p, Wk.o_rlen.p, Wk.o_rec.p, Wk.o_task.p,
-                               Wk.o_tb.p, gap ? Wk.o_hi.p : (int32_t *)nullptr, R.tau, n, oblk, oblk ? Wk.b_cnt.p : (int32_t *)nullptr, Wk.o_brank.p,
-                               gap ? (int2 *)nullptr : Wk.o_items.p, Wk.o_item_of.p, split);
-            {
-                ProfScope ps(gap ? PROF_GAPSTREAM : PROF_OWN, s, own_bytes(R.tau, split != 0, (double)P.own_steps));
-                if (oblk) {                       // the tile ids by column block (counted in k_own_map): ~10^5 tiles, a counting sort
-                    exclusive_scan_i32_lb(Wk.b_cnt.p, Wk.b_start.p, Wk.b_n.p, Wk.b_nblk, nullptr, Wk.scanws, s);
-                    hipLaunchKernelGGL(k_blk_order, dim3(mgrid), dim3(256), 0, s, rc, Wk.o_rec.p, Wk.o_brank.p, Wk.b_start.p, Wk.o_border.p, Wk.o_srec.p, Wk.b_cnt.p);
-                }
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(gap ? k_lpass_own<TC, HYP, true> : k_lpass_own<TC, HYP, false>), dim3((unsigned)cdiv(gNT, 4)), dim3(256), 0, s,
-                                   R.isA, rc,
-                                   oblk ? Wk.o_border.p : (const int32_t *)nullptr, A->pos32.p, A->next.p, if_hyp<HYP>(A->fpos32.p), if_hyp<HYP>(A->flast.p),
-                                   Wk.o_tileS.p, Wk.o_tileS2.p, Wk.o_rec.p, Wk.o_srec.p, W, M, alpha, recs<HYP>(Wk.o_part), R.tau, Wk.o_hi.p, Wk.o_spec.p,
-                                   (int)((g_opt_dbg & DBG_GAP_ALL_SPECIAL) != 0), recs<HYP>(Wk.o_sub), Wk.o_spv.p, A->col.p, if_hyp<HYP>(A->ffirst.p),
-                                   split ? Wk.split.vnext.p : (const int32_t *)nullptr, Wk.split.vpos.p, Wk.split.vsa.p, (int64_t)(n + 1));
-            }
+            own_stream<TC, HYP>(C, Wk, R, rc, P, gap, split);
             note(rd, 0, gap ? PROF_GAPSTREAM : PROF_OWN, R.tau, split != 0);
-            if (gap) {
-                {
-                    // the gap kernels look a tile's prefix up at random: a device-wide scan of the tile counts.  (The other rounds need
-                    // sums inside one task only: k_fix_own makes them from o_tileS.)
-                    ProfScope ps(PROF_CARRY, s, 12.0 * (double)P.NT);
-                    const int32_t *ntp = reinterpret_cast<const int32_t *>(&rc->NT);       // (NT < 2^31: the low word)
-                    exclusive_scan_i32_lb(Wk.o_tileS.p, Wk.o_tilePS.p, ntp, (int64_t)Wk.o_tileS.n, nullptr, Wk.scanws, s);
-                    if (hyp) exclusive_scan_i32_lb(Wk.o_tileS2.p, Wk.o_tilePS2.p, ntp, (int64_t)Wk.o_tileS.n, nullptr, Wk.scanws, s);
-                }
-                // every row of the gaps gets its winner: one wave per (task, 64 rows); tasks of more than GAPSEG tiles in two steps
-                ProfScope ps(PROF_GAP, s, 24.0 * (double)P.NT);
-                const int nchunk = (int)std::max<int64_t>(1, ((int64_t)2 << R.tau) / 64);
-                const size_t ncap = Wk.o_rec.n / GAPSEG + 2;
-                Wk.g_list.ensure(ncap); Wk.g_slot.ensure(2 * ncap);
-                Wk.g_seg.ensure((2 * ncap) * (size_t)nchunk * 64 * sizeof(GapSegRec<TC, true>));
-                // items that meet a tile with more than SMAX specials are listed by the fast kernels and redone by the SLOW ones
-                Wk.g_slow.ensure((size_t)gown * (size_t)nchunk + 64); Wk.g_sslow.ensure((2 * ncap) * (size_t)nchunk + 64);
-                CP_REQUIRE((int64_t)gown * nchunk < INT32_MAX && (int64_t)(2 * ncap) * nchunk < INT32_MAX, CP_EINTERNAL, "gap work index beyond 32 bits");
-                const int gnr = (g_opt_gap_nr >= 2 && nchunk >= 2) ? 2 : 1;       // 64-row chunks per wave of k_gap_finish
-                unsigned gg = (unsigned)std::min<int64_t>(cdiv(gown * cdiv((int64_t)nchunk, gnr), 4), 16384);
-                unsigned gs_grid = (unsigned)std::min<int64_t>(cdiv((int64_t)(2 * ncap) * nchunk, 4), 8192);
-                unsigned gm = (unsigned)std::min<int64_t>(cdiv((int64_t)ncap * nchunk, 4), 4096);
-                const unsigned gslow_grid = 2048;                               // (grid-stride over the device-side counts n_gslow / n_sslow: usually none)
-                launch_gap<TC, HYP>(s, A, Wk, R.tau, nchunk, gnr, rc, n, W, M, alpha, gg, gs_grid, gm, gslow_grid, oblk);
-            } else {
-                ProfScope ps(PROF_FIX, s, 24.0 * (double)P.NT);
-                // one launch: a lane per task of up to FIX_SERIAL tiles, a block per listed trip of the longer ones
-                launch_fix_own<TC, HYP>(s, rc, Wk.o_toffs.p, recs<HYP>(Wk.o_part), Wk.o_tdesc.p, Wk.o_tb.p, if_hyp<HYP>(Wk.o_tS0l.p), Wk.o_tileS.p,
-                                        if_hyp<HYP>(Wk.o_tileS2.p), M, Wk.opt.p, Wk.nnopt.p, if_hyp<HYP>(Wk.nlopt.p), n, Wk.o_items.p, Wk.o_item_of.p, Wk.o_trec.p,
-                                        Wk.o_tick.p, spec ? grow(P.NT) : P.NT, gown);
-            }
+            if (gap) gap_finish<TC, HYP>(C, Wk, R, rc, P);
+            else own_merge<TC, HYP>(C, Wk, rc, P);
             CP_HIP(hipGetLastError());
         }
         if (P.nlong <= 0 || P.T <= 0) continue;
         // ---- from here on the round consists of the flattened tasks only (their number: rc->nlong)
-        const int64_t gtile = spec ? (int64_t)Wk.tileS.n : cdiv(P.T, LT);      // (capacity >= the true tile count, checked)
-        poison_fill(s, {{Wk.loc.p, Wk.loc.bytes()}, {if_hyp<HYP>(Wk.loc2.p), Wk.loc2.bytes()}, {Wk.partL.p, Wk.partL.bytes()}, {Wk.partR.p, Wk.partR.bytes()},
-                        {Wk.tileS.p, Wk.tileS.bytes()}, {if_hyp<HYP>(Wk.tileS2.p), Wk.tileS2.bytes()}});
-        hipLaunchKernelGGL(k_tile_t0, dim3((unsigned)cdiv(gtile, 256)), dim3(256), 0, s, rc, Wk.offs.p, Wk.tdesc.p, Wk.tile_t0.p,
-                           Wk.tile_rec.p, (int)((g_opt_dbg & DBG_NO_INTERIOR) != 0), Wk.taskR.p);
-        {
-            // algorithmic bytes of one launch: per flattened step the stepped column's link
-            // entries (4 B x N/n, plus 4 B x nonempty-rows/n for hyperedge costs), its colptr entry (8 B), the
-            // candidate's previous-layer cost (8 B) and the task-descriptor share (offsets/B/anchor/row, amortised 8 B)
-            ProfScope ps(PROF_EXPAND, s, (double)P.T * step_bytes);
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lpass<TC, HYP>), dim3((unsigned)cdiv(gtile, 4)), dim3(256), 0, s, R, rc, Wk.offs.p, Wk.tdesc.p, Wk.tS0l.p, Wk.tb.p,
-                               A->pos32.p, A->next.p, if_hyp<HYP>(A->fpos32.p), if_hyp<HYP>(A->flast.p), Wk.opt.p, Wk.nnopt.p, Wk.nlopt.p, Wk.loc.p, Wk.loc2.p,
-                               Wk.tileS.p, Wk.tileS2.p, Wk.taskR.p, Wk.tile_t0.p, Wk.tile_rec.p, W, M, alpha, recs<HYP>(Wk.partR), recs<HYP>(Wk.partL));
-        }
+        flat_stream<TC, HYP>(C, Wk, R, rc, P);
         note(rd, 1, PROF_EXPAND);
-        {
-            ProfScope ps(PROF_CARRY, s, 12.0 * (double)cdiv(P.T, LT));
-            exclusive_scan_i32_lb(Wk.tileS.p, Wk.tilePS.p, &rc->ntile, (int64_t)Wk.tileS.n, nullptr, Wk.scanws, s);
-            if (hyp) exclusive_scan_i32_lb(Wk.tileS2.p, Wk.tilePS2.p, &rc->ntile, (int64_t)Wk.tileS.n, nullptr, Wk.scanws, s);
-        }
-        unsigned wgrid = (unsigned)std::min<int64_t>(cdiv(gtile, 4), 8192);     // the wave kernels walk work lists
-        {
-            ProfScope ps(PROF_EVAL, s, 0.0);
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_span_short<TC, HYP>), dim3((unsigned)cdiv(gtile, 256)), dim3(256), 0, s, R, rc, Wk.offs.p, Wk.tdesc.p, Wk.tS0l.p,
-                               Wk.tb.p, A->pos32.p, Wk.loc.p, Wk.loc2.p, Wk.tile_t0.p, Wk.taskR.p, Wk.tileS.p, Wk.tileS2.p, recs<HYP>(Wk.partR), W, M, alpha,
-                               Wk.opt.p, Wk.nnopt.p, if_hyp<HYP>(Wk.nlopt.p), Wk.open_list.p, Wk.fix_list.p, Wk.tile_rec.p);
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_open<TC, HYP>), dim3(wgrid), dim3(256), 0, s, R, rc, Wk.offs.p, Wk.tdesc.p, Wk.tS0l.p, A->pos32.p, Wk.loc.p,
-                               Wk.loc2.p, Wk.tile_t0.p, Wk.tilePS.p, if_hyp<HYP>(Wk.tilePS2.p), W, M, alpha, recs<HYP>(Wk.partL), Wk.open_list.p);
-        }
-        {
-            ProfScope ps(PROF_FIX, s, 8.0 * (double)cdiv(P.T, LT));
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fix<TC, HYP>), dim3(wgrid), dim3(256), 0, s, rc, Wk.offs.p, Wk.taskR.p, recs<HYP>(Wk.partL), recs<HYP>(Wk.partR),
-                               Wk.tdesc.p, Wk.tb.p, Wk.opt.p, Wk.nnopt.p, if_hyp<HYP>(Wk.nlopt.p), n + 1, Wk.fix_list.p, Wk.tile_rec.p, Wk.tilePS.p,
-                               if_hyp<HYP>(Wk.tilePS2.p), if_hyp<HYP>(Wk.tS0l.p), M);
-        }
-        CP_HIP(hipGetLastError());
+        flat_finish<TC, HYP>(C, Wk, R, rc, P);
     }
-    if (leaf) {
-        // every row that is not a multiple of 64: inner planes, outer planes and the combine in one pass (dp_leaf.inc)
-        const int64_t c0 = rlo > 1 ? rlo : 1, c1 = rhi < n ? rhi : n;
-        if (c1 >= c0) {
-            const int64_t g0 = c0 >> LEAF_T, g1 = c1 >> LEAF_T;
-            // bytes: the group's link entries twice (prev, next), column pointers, previous-layer costs, the two output rows
-            ProfScope ps(PROF_LEAF, s, (8.0 * (avg_deg + self_deg) + 4.0 + 8.0 + 12.0) * (double)((g1 - g0 + 1) << LEAF_T));
-            const int need = G.win ? G.s - LEAF_T + 2 : nbits - LEAF_T;           // outer planes a group can have (+ the pseudo-plane)
-            CP_REQUIRE(need <= 25, CP_EINTERNAL, "leaf pass: more outer planes than counters");
-            // With a gap pass in round 6 every task of that round with gap_min candidates or more has finished its rows (and the
-            // ranges of a leaf group in a plane b > 6 lie inside the range of the round-6 task of one of its two bounding rows): a longer
-            // range in a leaf group can only come from plane cells a mispredicted speculative layer never wrote (zeros after
-            // allocation: a range of millions of candidates per group, seconds of work for a layer that is redone anyway).  Such a
-            // group flags the layer (err) and skips the plane.
-            const int32_t lcap = (gaps && g_opt_gap_tau >= LEAF_T) ? (int32_t)std::max<int64_t>(g_opt_gap_min, 2) : INT32_MAX;
-            LeafArgs<TC, HYP> L{};
-            L.n = n; L.g0 = g0; L.ngroups = g1 - g0 + 1; L.c0 = c0; L.c1 = c1; L.nbits = nbits; L.planes = (int32_t)(g_opt_block_tables != 0);
-            L.pos = A->pos32.p; L.prev = A->prev.p; L.next = A->next.p; L.col = A->col.p;
-            L.fpos = if_hyp<HYP>(A->fpos32.p); L.flast = if_hyp<HYP>(A->flast.p); L.ffirst = if_hyp<HYP>(A->ffirst.p);
-            L.lpos = if_hyp<HYP>(A->lpos32.p); L.lfirst = if_hyp<HYP>(A->lfirst.p);
-            L.opt = Wk.opt.p; L.nnopt = Wk.nnopt.p; L.nlopt = if_hyp<HYP>(Wk.nlopt.p); L.fin = Wk.fin.p; L.fin_stamp = Wk.fin_stamp;
-            L.W = W; L.M = M; L.alpha = alpha; L.cst = cst_out; L.ptr = ptr_out; L.G = G;
-            L.anchM = Wk.leaf_anch.p; L.anchM2 = if_hyp<HYP>(Wk.leaf_anch2.p); L.lcap = lcap; L.err = &Wk.rc.p->err; L.pz = pzp;
-            constexpr int WPB = LeafWPB<HYP>::v;
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(need <= 18 ? k_leaf<TC, HYP, 18> : k_leaf<TC, HYP, 25>), dim3((unsigned)cdiv(L.ngroups, WPB)), dim3(64 * WPB), 0, s, L);
-            CP_HIP(hipGetLastError());
-        }
-    }
-    {
-        // the rows left: with the leaf pass the multiples of 64 (their planes from LEAF_T up), without it every row.  Threads in row
-        // order.  (lvl = 1, DBG_COMBINE_BY_SLOT: in plane-slot order, so that the dozen plane reads of a row are contiguous across a
-        // wave -- measured 867 us against 650 us at config 3: the 2 x 12 gathers W[p], pos[p] of a row are what counts, and they are
-        // neighbours only for neighbouring rows.)
-        ProfScope ps(PROF_COMBINE, s, 24.0 * (double)(leaf ? (n >> LEAF_T) + 1 : n + 1));
-        const int64_t c0 = rlo > 0 ? rlo : 0, c1 = rhi < n ? rhi : n;
-        const int64_t r0 = leaf ? (c0 + LEAF_G - 1) >> LEAF_T : c0, r1 = leaf ? c1 >> LEAF_T : c1;       // leaf: the multiples of 64 in [c0, c1]
-        const int lvl = (!leaf && (g_opt_dbg & DBG_COMBINE_BY_SLOT)) ? (2 * (c1 - c0 + 1) >= n + 1) : 0;
-        const int sh = leaf ? LEAF_T : 0;
-        const int32_t *nl = if_hyp<HYP>(Wk.nlopt.p);
-        if (c1 >= c0 && r1 >= r0) {
-            const unsigned cgrid = (unsigned)cdiv(lvl ? n + 1 : r1 - r0 + 1, 256);
-            if (G.win) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_combine_win<TC>), dim3(cgrid), dim3(256), 0, s, lvl, G, n, r0, r1, A->pos32.p, Wk.opt.p, Wk.nnopt.p, nl, W, M,
-                                          alpha, cst_out, ptr_out, sh, pzp);
-            else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_combine<TC>), dim3(cgrid), dim3(256), 0, s, lvl, n, r0, r1, nbits, A->pos32.p, Wk.opt.p, Wk.nnopt.p, nl, W, M, alpha,
-                                    cst_out, ptr_out, sh, pzp);
-        }
-    }
+    if (C.leaf) leaf_pass<TC, HYP>(C, Wk);
+    combine_rows<TC, HYP>(C, Wk);
     CP_HIP(hipGetLastError());
     // ---- the true counts of every round: the next layer's prediction, this layer's verdict
     std::vector<RoundCounts> got((size_t)NR);
     int32_t pz_hits[2] = {0, 0};
-    CP_HIP(hipMemcpyAsync(got.data(), Wk.rc.p, sizeof(RoundCounts) * (size_t)NR, hipMemcpyDeviceToHost, s));
+    CP_HIP(hipMemcpyAsync(got.data(), Wk.sp.rc.p, sizeof(RoundCounts) * (size_t)NR, hipMemcpyDeviceToHost, s));
     if (pzp) CP_HIP(hipMemcpyAsync(pz_hits, pzp, sizeof(pz_hits), hipMemcpyDeviceToHost, s));
     CP_HIP(hipStreamSynchronize(s));
     bool ok = true;
@@ -3719,8 +3486,8 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
         g_poison_hits += pz_hits[0];
         CP_REQUIRE(!(ok && pz_hits[0] > 0), CP_EINTERNAL, "a DP layer that is not redone read plane cells nobody wrote (poison mode)");
     }
-    if (ok) Wk.b_dirty = false;
-    Wk.t_dirty = false;                                  // (every merge that was enqueued has run to its end, also in a layer that is redone)
+    if (ok) Wk.ow.b_dirty = false;
+    Wk.ow.t_dirty = false;                                  // (every merge that was enqueued has run to its end, also in a layer that is redone)
     if (ok) for (int rd = 0; rd < NR; rd++) { g_fix_trips += got[(size_t)rd].n_trips; g_fix_edges |= got[(size_t)rd].n_edge; }
     if (ok) for (int rd = 0; rd < NR; rd++) {
         const RoundCounts &g = got[(size_t)rd];
@@ -3734,15 +3501,15 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
         for (auto &pt : patches) {
             const RoundCounts &g = got[(size_t)pt.rd];
             if (pt.idx < g_prof_pending.size())
-                g_prof_pending[pt.idx].bytes = pt.kind == 0 ? own_bytes(pt.tau, pt.split, (double)g.own_steps) : (double)g.T * step_bytes;
+                g_prof_pending[pt.idx].bytes = pt.kind == 0 ? C.own_bytes(Wk.ow.split, pt.tau, pt.split, (double)g.own_steps) : (double)g.T * C.step_bytes;
         }
-        Wk.pred = got; Wk.pred_ok = true; Wk.pred_rlo = rlo; Wk.pred_rhi = rhi; Wk.pred_win = G.win; Wk.pred_w = G.w;
-        if (allow_force && 2 * (rhi - rlo + 1) >= Wk.force_rows) {
-            Wk.force_own.resize((size_t)NR, 0);
-            Wk.force_rows = rhi - rlo + 1;
+        Wk.sp.pred = got; Wk.sp.pred_ok = true; Wk.sp.pred_rlo = rlo; Wk.sp.pred_rhi = rhi; Wk.sp.pred_win = G.win; Wk.sp.pred_w = G.w;
+        if (allow_force && 2 * (rhi - rlo + 1) >= Wk.sp.force_rows) {
+            Wk.sp.force_own.resize((size_t)NR, 0);
+            Wk.sp.force_rows = rhi - rlo + 1;
             for (int rd = 1; rd < NR; rd++) {
                 const RoundCounts &g = got[(size_t)rd];
-                if (g.nlong > 0) Wk.force_own[(size_t)rd] = g.nlong <= g_opt_force_max;         // (a forced round reports none: its flag stays)
+                if (g.nlong > 0) Wk.sp.force_own[(size_t)rd] = g.nlong <= g_opt_force_max;         // (a forced round reports none: its flag stays)
             }
         }
     }
@@ -3763,18 +3530,18 @@ void dp_total_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W, T
         // (the shape is recorded only after every allocation succeeded: a hipMalloc failure leaves n == -1 and the next call starts over)
         Wk.n = -1; Wk.nbits = nbits; Wk.hyp = hyp;
         Wk.forget();                                // (the window anchors of a hyperedge model carry a second array)
-        Wk.o_rec.release(); Wk.loc.release();       // (the per-tile arrays are re-made for the new shape on first use)
+        Wk.ow.o_rec.release(); Wk.fl.loc.release();       // (the per-tile arrays are re-made for the new shape on first use)
         size_t plane = (size_t)nbits * (size_t)(n + 1);
-        Wk.opt.alloc(plane); Wk.nnopt.alloc(plane); Wk.cr.alloc(plane);
-        if (hyp) { Wk.nlopt.alloc(plane); Wk.crl.alloc(plane); }
+        Wk.pl.opt.alloc(plane); Wk.pl.nnopt.alloc(plane); Wk.pl.cr.alloc(plane);
+        if (hyp) { Wk.pl.nlopt.alloc(plane); Wk.pl.crl.alloc(plane); }
         // The winners are zeroed once: a speculatively sized layer may skip a stage that turns out to have work (the layer is then
         // redone), and until the redo later rounds read plane cells nobody wrote.  Whatever they hold must be a valid column
         // index -- a stale winner of an earlier layer is, fresh device memory is not (a k_lpass_own wave once streamed from
         // column 13868 of a 3000-column matrix).
-        CP_HIP(hipMemsetAsync(Wk.opt.p, 0, Wk.opt.bytes(), A->stream));
-        CP_HIP(hipMemsetAsync(Wk.nnopt.p, 0, Wk.nnopt.bytes(), A->stream));
-        CP_HIP(hipMemsetAsync(Wk.cr.p, 0, Wk.cr.bytes(), A->stream));
-        if (hyp) { CP_HIP(hipMemsetAsync(Wk.nlopt.p, 0, Wk.nlopt.bytes(), A->stream)); CP_HIP(hipMemsetAsync(Wk.crl.p, 0, Wk.crl.bytes(), A->stream)); }
+        CP_HIP(hipMemsetAsync(Wk.pl.opt.p, 0, Wk.pl.opt.bytes(), A->stream));
+        CP_HIP(hipMemsetAsync(Wk.pl.nnopt.p, 0, Wk.pl.nnopt.bytes(), A->stream));
+        CP_HIP(hipMemsetAsync(Wk.pl.cr.p, 0, Wk.pl.cr.bytes(), A->stream));
+        if (hyp) { CP_HIP(hipMemsetAsync(Wk.pl.nlopt.p, 0, Wk.pl.nlopt.bytes(), A->stream)); CP_HIP(hipMemsetAsync(Wk.pl.crl.p, 0, Wk.pl.crl.bytes(), A->stream)); }
         int64_t mx = n;
         for (int tau = 0; tau < nbits; tau++) { RoundDesc R; make_round(R, false, tau, nbits, n, 0, n); if (R.ntask > mx) mx = R.ntask; }
         // windowed layers give every row of a round a task in EVERY plane above tau (up to nbits - 1 - tau of them), and round A
@@ -3783,18 +3550,18 @@ void dp_total_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W, T
         mx = std::max<int64_t>(mx, 2 * n + nbits);
         Wk.max_tasks = mx > 0 ? mx : 1;
         size_t mt = (size_t)Wk.max_tasks;
-        Wk.tdesc.alloc(mt); Wk.len.alloc(mt); Wk.tb.alloc(mt); Wk.offs.alloc(mt + 1);
-        if (hyp) Wk.tS0l.alloc(mt);
+        Wk.tk.tdesc.alloc(mt); Wk.tk.len.alloc(mt); Wk.tk.tb.alloc(mt); Wk.tk.offs.alloc(mt + 1);
+        if (hyp) Wk.tk.tS0l.alloc(mt);
         // tasks with tiles of their own have >= own_min >= 64 candidates; the ranges of one plane and round overlap in their end
         // points only: at most n / 64 + (rectangles) of them per plane -- (n / 32 + 64) per plane is a safe cap (k_setup_short guards it)
         int64_t mmin = std::max<int64_t>(2, std::min(g_opt_own_min, g_opt_gap_tau >= 0 ? g_opt_gap_min : g_opt_own_min));
         size_t mo = (size_t)(2 * n / mmin + 64) * (size_t)nbits + 1024;
         if (mo > mt) mo = mt;
-        Wk.o_tdesc.alloc(mo); Wk.o_tb.alloc(mo); Wk.o_rlen.alloc(mo); Wk.o_ntl.alloc(mo); Wk.o_toffs.alloc(mo + 1); Wk.o_tick.alloc(mo);
-        Wk.t_dirty = true;
-        if (hyp) Wk.o_tS0l.alloc(mo);
-        Wk.rc.alloc((size_t)NBMAX + 2);
-        Wk.fin.alloc(plane); Wk.last_s0.alloc(64); Wk.fin_stamp = 255;      // (fresh memory: the first layer clears it)
+        Wk.ow.o_tdesc.alloc(mo); Wk.ow.o_tb.alloc(mo); Wk.ow.o_rlen.alloc(mo); Wk.ow.o_ntl.alloc(mo); Wk.ow.o_toffs.alloc(mo + 1); Wk.ow.o_tick.alloc(mo);
+        Wk.ow.t_dirty = true;
+        if (hyp) Wk.ow.o_tS0l.alloc(mo);
+        Wk.sp.rc.alloc((size_t)NBMAX + 2);
+        Wk.pl.fin.alloc(plane); Wk.pl.last_s0.alloc(64); Wk.pl.fin_stamp = 255;      // (fresh memory: the first layer clears it)
         Wk.n = n;
     }
     // geometry of this call: wwin > 0: candidates of row r are max(0, r - wwin) <= p <= r
@@ -3803,19 +3570,19 @@ void dp_total_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W, T
     // (w >= 2^(nbits-1) > n/2: planes 0 .. nbits-1 with S = 2^(nbits-1) <= w still tile every window -- the common block just
     //  reaches further left than column 0 and is clamped)
     Wk.G = G;
-    if (G.win && (!Wk.win_built || Wk.win_w != wwin)) win_build<TC>(A, Wk);
-    bool spec = Wk.pred_ok && !g_opt_nospec && Wk.pred_win == G.win && Wk.pred_w == G.w;
-    Wk.pred_scale = 1.0;
-    if (spec && (Wk.pred_rlo != rlo || Wk.pred_rhi != rhi)) {
+    if (G.win && (!Wk.win.built || Wk.win.w != wwin)) win_build<TC>(A, Wk);
+    bool spec = Wk.sp.pred_ok && !g_opt_nospec && Wk.sp.pred_win == G.win && Wk.sp.pred_w == G.w;
+    Wk.sp.pred_scale = 1.0;
+    if (spec && (Wk.sp.pred_rlo != rlo || Wk.sp.pred_rhi != rhi)) {
         // another row tile than the layer the counts come from: the unconstrained driver keeps its tile, the constrained one moves
         // a window over the rows -- take the prediction per row of the tile
-        const double a = (double)(Wk.pred_rhi - Wk.pred_rlo + 1), b = (double)(rhi - rlo + 1);
+        const double a = (double)(Wk.sp.pred_rhi - Wk.sp.pred_rlo + 1), b = (double)(rhi - rlo + 1);
         // (a much larger tile than the counts come from -- the one-row last layer of an earlier call on this handle -- would
         //  scale a handful of tasks into buffers of any size: such a layer takes its exact counts instead)
         if (!G.win || a < 1 || b < 1 || b > 2.0 * a) spec = false;
-        else Wk.pred_scale = b / a;
+        else Wk.sp.pred_scale = b / a;
     }
-    if (Wk.pred_win != G.win || Wk.pred_w != G.w || (int)Wk.force_own.size() != (G.win ? G.s + 1 : Wk.nbits) + 1) { Wk.force_own.clear(); Wk.force_rows = 0; }      // (another geometry: other rounds)
+    if (Wk.sp.pred_win != G.win || Wk.sp.pred_w != G.w || (int)Wk.sp.force_own.size() != (G.win ? G.s + 1 : Wk.nbits) + 1) { Wk.sp.force_own.clear(); Wk.sp.force_rows = 0; }      // (another geometry: other rounds)
     // the layer's variant is chosen here, once: everything below is instantiated for it
     auto run = [&](bool sp, bool allow_force) {
         return hyp ? run_layer<TC, true>(A, M, alpha, W, cst_out, ptr_out, Wk, rlo, rhi, sp, allow_force)
@@ -3824,7 +3591,7 @@ void dp_total_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W, T
     if (run(spec, true)) return;
     // the prediction missed (a stage that had been empty, or a buffer too small): the same layer again with exact counts
     g_spec_redo++;
-    Wk.force_own.clear(); Wk.force_rows = 0;
+    Wk.sp.force_own.clear(); Wk.sp.force_rows = 0;
     bool ok = run(false, false);
     CP_REQUIRE(ok, CP_EINTERNAL, "DP layer failed with exact counts");
 }
@@ -3838,13 +3605,13 @@ int dp_total_block_tables(cp_csr_s *A, void *work_, int64_t *opt_out, int64_t *n
 {
     auto &Wk = *reinterpret_cast<LayerWork<TC> *>(work_);
     const int64_t n = A->n, n1 = n + 1;
-    CP_REQUIRE(Wk.n == n && Wk.opt.p, CP_EINVAL, "no layer has been computed by the O(n log^2 n) scheme on this handle");
-    CP_REQUIRE(Wk.planes_full, CP_EINVAL, "the last layer kept no per-block winners for its leaf rows: cp_set_option(\"block_tables\", 1) before the layer");
+    CP_REQUIRE(Wk.n == n && Wk.pl.opt.p, CP_EINVAL, "no layer has been computed by the O(n log^2 n) scheme on this handle");
+    CP_REQUIRE(Wk.pl.planes_full, CP_EINVAL, "the last layer kept no per-block winners for its leaf rows: cp_set_option(\"block_tables\", 1) before the layer");
     const size_t plane = (size_t)Wk.nbits * (size_t)n1;
     std::vector<int32_t> ho(plane), hn(plane), hl;
-    CP_HIP(hipMemcpyAsync(ho.data(), Wk.opt.p, plane * sizeof(int32_t), hipMemcpyDeviceToHost, A->stream));
-    CP_HIP(hipMemcpyAsync(hn.data(), Wk.nnopt.p, plane * sizeof(int32_t), hipMemcpyDeviceToHost, A->stream));
-    if (Wk.hyp && nl_out) { hl.resize(plane); CP_HIP(hipMemcpyAsync(hl.data(), Wk.nlopt.p, plane * sizeof(int32_t), hipMemcpyDeviceToHost, A->stream)); }
+    CP_HIP(hipMemcpyAsync(ho.data(), Wk.pl.opt.p, plane * sizeof(int32_t), hipMemcpyDeviceToHost, A->stream));
+    CP_HIP(hipMemcpyAsync(hn.data(), Wk.pl.nnopt.p, plane * sizeof(int32_t), hipMemcpyDeviceToHost, A->stream));
+    if (Wk.hyp && nl_out) { hl.resize(plane); CP_HIP(hipMemcpyAsync(hl.data(), Wk.pl.nlopt.p, plane * sizeof(int32_t), hipMemcpyDeviceToHost, A->stream)); }
     CP_HIP(hipStreamSynchronize(A->stream));
     for (int b = 0; b < Wk.nbits; b++)
         for (int64_t r = 0; r <= n; r++) {

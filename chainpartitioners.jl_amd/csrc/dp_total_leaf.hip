@@ -1,4 +1,4 @@
-// dp_leaf.inc -- the LEAF PASS of a total-cost DP layer (included by dp_total.hip inside namespace cpk).
+// dp_total_leaf.hip -- the LEAF PASS of a total-cost DP layer (dp_total.hip), and the combine of the per-plane winners.
 //
 // The divide and conquer of dp_total.hip halves the row distance per round; its last six rounds (tau = 5 .. 0) hold 63 of 64
 // rows, and almost every task there is ONE candidate (the winners of the two tree neighbours coincide): a task record, four
@@ -41,10 +41,9 @@
 //
 // cp_set_option("block_tables", 1) makes the pass also store every per-block winner and its counts (cp_dp_block_tables: tests).
 
-constexpr int LEAF_T = 6;
-constexpr int LEAF_G = 1 << LEAF_T;
-constexpr int LEAF_FEW = 12;             // local entries up to which the inner planes are one segmented scan (more: the column loop)
-constexpr int LEAF_LIST = 1024;          // local link entries of a group kept in LDS; more: the columns are re-read from HBM
+#include "dp_total.hpp"
+
+namespace cpk {
 
 template <typename TC, bool HYP>
 struct LeafArgs {
@@ -179,7 +178,7 @@ __global__ void __launch_bounds__(64 * LeafWPB<HYP>::v) k_leaf(LeafArgs<TC, HYP>
     const int32_t q0 = rdl(posr, 0), q1 = A.pos[gE];
     int32_t lposr = 0, fposr = 0, l0 = 0, l1 = 0, f0 = 0, f1 = 0;
     if (HYP) { lposr = A.lpos[rq]; fposr = A.fpos[rq]; l0 = rdl(lposr, 0); l1 = A.lpos[gE]; f0 = rdl(fposr, 0); f1 = A.fpos[gE]; }
-    const int64_t slot = r >= 1 ? PR((int64_t)rq) : 0;                   // plane slot of this lane's row
+    const int64_t slot = r >= 1 ? prow(((int64_t)rq), n1 - 1) : 0;                   // plane slot of this lane's row
 
     // ---- outer planes of the group.  Unconstrained: lane j holds the j-th set bit of g.  Windowed: lane j holds plane 6 + j for
     // every plane up to s, and lane s - 5 the pseudo-plane of the inner mirrored blocks.  pl_fin: 1 = finished by a gap pass,
@@ -205,14 +204,14 @@ __global__ void __launch_bounds__(64 * LeafWPB<HYP>::v) k_leaf(LeafArgs<TC, HYP>
         pl_b = b;
         if (!have) pl_fin = 2;
         else {
-            const int64_t sL = (int64_t)b * n1 + PR((int64_t)gG);
+            const int64_t sL = (int64_t)b * n1 + prow(((int64_t)gG), n1 - 1);
             pl_B = A.opt[sL]; pl_nn = A.nnopt[sL];
             if (HYP) pl_nl = A.nlopt[sL];
             const int64_t rb = ((int64_t)gG >> b) << b, rR = (int64_t)hiG;
-            if (win) pl_a = (rR < rb + ((int64_t)1 << b) && rR <= n) ? A.opt[(int64_t)b * n1 + PR(rR)] : (int32_t)cs;
-            else pl_a = (rR - rb) < ((int64_t)1 << b) ? A.opt[(int64_t)b * n1 + PR(rR <= n ? rR : n)] : (int32_t)(rb - ((int64_t)1 << b));
+            if (win) pl_a = (rR < rb + ((int64_t)1 << b) && rR <= n) ? A.opt[(int64_t)b * n1 + prow((rR), n1 - 1)] : (int32_t)cs;
+            else pl_a = (rR - rb) < ((int64_t)1 << b) ? A.opt[(int64_t)b * n1 + prow((rR <= n ? rR : n), n1 - 1)] : (int32_t)(rb - ((int64_t)1 << b));
             if (pl_a > pl_B) pl_a = pl_B;                                // (cannot happen for an inverse-Monge cost; keeps the ranges well-formed)
-            pl_fin = A.fin[(int64_t)b * n1 + PR((int64_t)gG + 1)] == (uint8_t)A.fin_stamp;      // (gG + 1 <= n: the group has a row)
+            pl_fin = A.fin[(int64_t)b * n1 + prow(((int64_t)gG + 1), n1 - 1)] == (uint8_t)A.fin_stamp;      // (gG + 1 <= n: the group has a row)
         }
     } else if (win && lane == 1) {
         const int64_t Bm = (int64_t)gG + 62 - A.G.w;
@@ -250,7 +249,7 @@ __global__ void __launch_bounds__(64 * LeafWPB<HYP>::v) k_leaf(LeafArgs<TC, HYP>
         for (int k = 0; k < 4; k++) { const int32_t q = q0 + 64 * k + lane; pv[k] = q < q1 ? A.prev[q] : INT32_MAX; nx[k] = q < q1 ? A.next[q] : INT32_MAX; }
         // the head candidate of every plane (lane j <-> plane j), fetched for all planes at once behind the first entries: a
         // dependent load per plane inside the plane loop would cost a memory latency each
-        if (lane < nact && pl_fin != 2) pl_U = cadd(A.W[pl_B], dm_apply(M, (TC)0, (int64_t)(-pl_B), (int64_t)(-A.pos[pl_B]), (int64_t)0, (int64_t)0));
+        if (lane < nact && pl_fin != 2) pl_U = cadd(A.W[pl_B], dm_apply_affine(M, (TC)0, (int64_t)(-pl_B), (int64_t)(-A.pos[pl_B]), (int64_t)0, (int64_t)0));
         for (int32_t base0 = q0; base0 < q1; base0 += 256) {
             int32_t cpv[4], cnx[4];
 #pragma unroll
@@ -302,13 +301,13 @@ __global__ void __launch_bounds__(64 * LeafWPB<HYP>::v) k_leaf(LeafArgs<TC, HYP>
     // ---- the diagonal and the inner planes: p = r, r - 1, .., gG
     // cost(p, r) = [W[p] - p b_v - pos[p] b_p] + [alpha + r b_v + pos[r] b_p] + the net terms: the first bracket once per column
     // (this lane's own column gG + lane), the second once per row
-    TC bv = cadd(Wr, dm_apply(M, alpha, (int64_t)0, (int64_t)0, (int64_t)0, (int64_t)0));
+    TC bv = cadd(Wr, dm_apply_affine(M, alpha, (int64_t)0, (int64_t)0, (int64_t)0, (int64_t)0));
     int32_t bp = r;
-    const TC rowbase = dm_apply(M, alpha, (int64_t)r, (int64_t)posr, (int64_t)0, (int64_t)0);
-    const TC colU = cadd(Wr, dm_apply(M, (TC)0, (int64_t)(-r), (int64_t)(-posr), (int64_t)0, (int64_t)0));
+    const TC rowbase = dm_apply_affine(M, alpha, (int64_t)r, (int64_t)posr, (int64_t)0, (int64_t)0);
+    const TC colU = cadd(Wr, dm_apply_affine(M, (TC)0, (int64_t)(-r), (int64_t)(-posr), (int64_t)0, (int64_t)0));
     // the net terms split the same way: nets(p, r) = (pos[r] - pos[p]) - (local repeats), self nets = (local)
-    const TC colN = cadd(colU, dm_apply(M, (TC)0, (int64_t)0, (int64_t)0, (int64_t)(-posr), (int64_t)0));
-    const TC rowN = cadd(rowbase, dm_apply(M, (TC)0, (int64_t)0, (int64_t)0, (int64_t)posr, (int64_t)0));
+    const TC colN = cadd(colU, dm_apply_affine(M, (TC)0, (int64_t)0, (int64_t)0, (int64_t)(-posr), (int64_t)0));
+    const TC rowN = cadd(rowbase, dm_apply_affine(M, (TC)0, (int64_t)0, (int64_t)0, (int64_t)posr, (int64_t)0));
     if (CP_LEAF_SKIP & 8) {
     } else if (nloc == 0 && nloc2 == 0 && !A.planes) {
         // no row of the group comes back inside it (the usual case away from bands): cost(p, r) = colN(p) + rowN(r), so the
@@ -361,7 +360,7 @@ __global__ void __launch_bounds__(64 * LeafWPB<HYP>::v) k_leaf(LeafArgs<TC, HYP>
             const TC sb = rdl64u(sv, b);                                 // minimum of the segment ending at column b
             const int32_t ib = rdl(si, b);
             if (b <= lane - 2) {
-                const TC v = cadd(cadd(sb, rowN), dm_apply(M, (TC)0, (int64_t)0, (int64_t)0, (int64_t)(-Dn), (int64_t)Dl));
+                const TC v = cadd(cadd(sb, rowN), dm_apply_affine(M, (TC)0, (int64_t)0, (int64_t)0, (int64_t)(-Dn), (int64_t)Dl));
                 if (v < bv) { bv = v; bp = gG + ib; }
             }
         }
@@ -398,7 +397,7 @@ __global__ void __launch_bounds__(64 * LeafWPB<HYP>::v) k_leaf(LeafArgs<TC, HYP>
             }
             const TC Up = rdl64u(colN, jc);
             if (lane > jc) {
-                const TC v = cadd(cadd(Up, rowN), dm_apply(M, (TC)0, (int64_t)0, (int64_t)0, (int64_t)(-cl), (int64_t)cl2));
+                const TC v = cadd(cadd(Up, rowN), dm_apply_affine(M, (TC)0, (int64_t)0, (int64_t)0, (int64_t)(-cl), (int64_t)cl2));
                 if (v < bv) { bv = v; bp = gG + jc; }
                 if (A.planes) {
                     const int b = 31 - __clz(lane ^ jc);                 // the block of row `lane` holding column jc
@@ -429,7 +428,7 @@ __global__ void __launch_bounds__(64 * LeafWPB<HYP>::v) k_leaf(LeafArgs<TC, HYP>
                     if (CP_LEAF_SKIP & 4) continue;
                     // one candidate (the winners of the two bounding rows coincide): nothing to stream, nothing to reduce
                     const int32_t nn = rdl(pl_nn, j) + cnt[j], nl = HYP ? rdl(pl_nl, j) + cnt2[j] : 0;
-                    const TC v = cadd(cadd(rdl64u(pl_U, j), rowbase), dm_apply(M, (TC)0, (int64_t)0, (int64_t)0, (int64_t)nn, (int64_t)nl));
+                    const TC v = cadd(cadd(rdl64u(pl_U, j), rowbase), dm_apply_affine(M, (TC)0, (int64_t)0, (int64_t)0, (int64_t)nn, (int64_t)nl));
                     if (v < bv || (v == bv && B > bp)) { bv = v; bp = B; }
                     if (A.planes && rvalid) {
                         const int64_t sw = (int64_t)rdl(pl_b, j) * n1 + slot;
@@ -453,7 +452,7 @@ __global__ void __launch_bounds__(64 * LeafWPB<HYP>::v) k_leaf(LeafArgs<TC, HYP>
                 int32_t p = A.opt[sw];
                 const int32_t nn = A.nnopt[sw], nl = HYP ? A.nlopt[sw] : 0;
                 if (A.pz && (uint32_t)p > (uint32_t)n) { atomicAdd(A.pz, 1); p = r; }
-                const TC v = cadd(A.W[p], dm_apply(M, alpha, (int64_t)(r - p), (int64_t)(posr - A.pos[p]), (int64_t)nn, (int64_t)nl));
+                const TC v = cadd(A.W[p], dm_apply_affine(M, alpha, (int64_t)(r - p), (int64_t)(posr - A.pos[p]), (int64_t)nn, (int64_t)nl));
                 if (v < bv || (v == bv && p > bp)) { bv = v; bp = p; }
             }
             continue;
@@ -500,7 +499,7 @@ __global__ void __launch_bounds__(64 * LeafWPB<HYP>::v) k_leaf(LeafArgs<TC, HYP>
             const int32_t klim = 62 - lane < Lm - 1 ? 62 - lane : Lm - 1;          // last candidate index of this lane's row
             if (!specm) {
                 // inclusive prefix-min over the candidates (ties keep the earlier = larger p), then every row reads its own prefix
-                TC U = cadd(Wp, dm_apply(M, (TC)0, (int64_t)(-p), (int64_t)(-pp), (int64_t)C, (int64_t)C2));
+                TC U = cadd(Wp, dm_apply_affine(M, (TC)0, (int64_t)(-p), (int64_t)(-pp), (int64_t)C, (int64_t)C2));
                 int32_t iu = lane;
 #pragma unroll
                 for (int o = 1; o < 64; o <<= 1) {
@@ -514,7 +513,7 @@ __global__ void __launch_bounds__(64 * LeafWPB<HYP>::v) k_leaf(LeafArgs<TC, HYP>
                 const int32_t im = __shfl(iu, src), Cm = __shfl(C, src), C2m = HYP ? __shfl(C2, src) : 0;
                 if (lane >= 1 && klim >= 0) {
                     const int32_t nn = nn0 + R + Cm, nl = nl0 + R2 + C2m;
-                    const TC v = cadd(cadd(Um, rowbase), dm_apply(M, (TC)0, (int64_t)0, (int64_t)0, (int64_t)(nn0 + R), (int64_t)(nl0 + R2)));
+                    const TC v = cadd(cadd(Um, rowbase), dm_apply_affine(M, (TC)0, (int64_t)0, (int64_t)0, (int64_t)(nn0 + R), (int64_t)(nl0 + R2)));
                     const int32_t pw = B - im;
                     (void)nn; (void)nl;
                     if (v < bv || (v == bv && pw > bp)) { bv = v; bp = pw; }
@@ -541,7 +540,7 @@ __global__ void __launch_bounds__(64 * LeafWPB<HYP>::v) k_leaf(LeafArgs<TC, HYP>
                     }
                     const TC Wc = rdl64u(Wp, t);
                     const int32_t posc = rdl(pp, t);
-                    const TC v = cadd(Wc, dm_apply(M, alpha, (int64_t)(r - pc), (int64_t)(posr - posc), (int64_t)(nn0 + R + cr), (int64_t)(nl0 + R2 + cr2)));
+                    const TC v = cadd(Wc, dm_apply_affine(M, alpha, (int64_t)(r - pc), (int64_t)(posr - posc), (int64_t)(nn0 + R + cr), (int64_t)(nl0 + R2 + cr2)));
                     if (lane >= 1 && t <= klim && (v < bv || (v == bv && pc > bp))) { bv = v; bp = pc; }
                 }
             }
@@ -592,7 +591,7 @@ __global__ void __launch_bounds__(64 * LeafWPB<HYP>::v) k_leaf(LeafArgs<TC, HYP>
                             for (int k = 0; k < ns; k++) heads |= 1ull << (__builtin_amdgcn_readfirstlane((int32_t)s_list[0][k]) >> 8);
                             if (HYP) for (int k = 0; k < ns2; k++) heads |= 1ull << (__builtin_amdgcn_readfirstlane((int32_t)s_list[HYP ? 1 : 0][k]) >> 8);
                             const int dist = lane - (63 - __clzll((unsigned long long)(heads & leaf_lowmask(lane + 1))));      // lanes since the segment start
-                            TC sv = cadd(Wp, dm_apply(M, (TC)0, (int64_t)(-p), (int64_t)(-pp), (int64_t)C, (int64_t)C2));
+                            TC sv = cadd(Wp, dm_apply_affine(M, (TC)0, (int64_t)(-p), (int64_t)(-pp), (int64_t)C, (int64_t)C2));
                             int32_t si = lane, sC = C, sC2 = C2;
 #pragma unroll
                             for (int o = 1; o < 64; o <<= 1) {
@@ -615,7 +614,7 @@ __global__ void __launch_bounds__(64 * LeafWPB<HYP>::v) k_leaf(LeafArgs<TC, HYP>
                                 if (h >= L) break;                                       // (cannot happen: a special's column is a candidate)
                                 const TC Us = rdl64u(sv, send);
                                 const int32_t is_ = rdl(si, send), Cs = rdl(sC, send), C2s = HYP ? rdl(sC2, send) : 0;
-                                const TC v = cadd(cadd(Us, rowbase), dm_apply(M, (TC)0, (int64_t)0, (int64_t)0, (int64_t)(nn0 + R + cn), (int64_t)(nl0 + R2 + cl)));
+                                const TC v = cadd(cadd(Us, rowbase), dm_apply_affine(M, (TC)0, (int64_t)0, (int64_t)0, (int64_t)(nn0 + R + cn), (int64_t)(nl0 + R2 + cl)));
                                 if (pv_p < 0 || v < pv_v) { pv_v = v; pv_p = B - is_; pv_nn = nn0 + R + Cs + cn; pv_nl = nl0 + R2 + C2s + cl; }
                             }
                             spec = false; few_done = true;
@@ -623,7 +622,7 @@ __global__ void __launch_bounds__(64 * LeafWPB<HYP>::v) k_leaf(LeafArgs<TC, HYP>
                     }
                     if (spec || few_done) break;
                 }
-                TC U = cadd(Wp, dm_apply(M, (TC)0, (int64_t)(-p), (int64_t)(-pp), (int64_t)C, (int64_t)C2));
+                TC U = cadd(Wp, dm_apply_affine(M, (TC)0, (int64_t)(-p), (int64_t)(-pp), (int64_t)C, (int64_t)C2));
                 int32_t iu = cv ? i : INT32_MAX;
                 if (L - c0 > 1) {
 #pragma unroll
@@ -640,7 +639,7 @@ __global__ void __launch_bounds__(64 * LeafWPB<HYP>::v) k_leaf(LeafArgs<TC, HYP>
             }
             if (!spec && !few_done) {
                 pv_nn = nn0 + R + Cb; pv_nl = nl0 + R2 + Cb2; pv_p = B - ib;
-                pv_v = cadd(cadd(Ub, rowbase), dm_apply(M, (TC)0, (int64_t)0, (int64_t)0, (int64_t)(nn0 + R), (int64_t)(nl0 + R2)));
+                pv_v = cadd(cadd(Ub, rowbase), dm_apply_affine(M, (TC)0, (int64_t)0, (int64_t)0, (int64_t)(nn0 + R), (int64_t)(nl0 + R2)));
             }
         }
         if (spec) {
@@ -675,7 +674,7 @@ __global__ void __launch_bounds__(64 * LeafWPB<HYP>::v) k_leaf(LeafArgs<TC, HYP>
                     const TC Wc = rdl64u(Wp, t);
                     const int32_t posc = rdl(pp, t);
                     const int32_t nn = nn0 + R + cr, nl = nl0 + R2 + cr2;
-                    const TC v = cadd(Wc, dm_apply(M, alpha, (int64_t)(r - pc), (int64_t)(posr - posc), (int64_t)nn, (int64_t)nl));
+                    const TC v = cadd(Wc, dm_apply_affine(M, alpha, (int64_t)(r - pc), (int64_t)(posr - posc), (int64_t)nn, (int64_t)nl));
                     if (pv_p < 0 || v < pv_v) { pv_v = v; pv_p = pc; pv_nn = nn; pv_nl = nl; }
                 }
             }
@@ -688,3 +687,153 @@ __global__ void __launch_bounds__(64 * LeafWPB<HYP>::v) k_leaf(LeafArgs<TC, HYP>
     }
     if (rvalid && r >= A.c0 && r <= A.c1) { A.cst[r] = bv; A.ptr[r] = bp; }
 }
+
+
+// ------------------------------------------------------------------ combine the per-bit winners of every row
+// Which row a thread of the combine kernels takes.  lvl = 0: row rlo + i.  lvl = 1 (an experiment kept behind a debug option, see
+// run_layer): the row of plane slot i -- the order the planes are stored in (prow); row 0 is thread n.  Returns -1 for a thread
+// without a row.
+__device__ __forceinline__ int64_t combine_row(int64_t i, int64_t n, int64_t rlo, int64_t rhi, int lvl)
+{
+    int64_t r;
+    if (!lvl) r = rlo + i;
+    else if (i == n) r = 0;
+    else if (i > n) return -1;
+    else {
+        int t = 0;
+        while (t < 62 && n - (n >> (t + 1)) <= i) t++;             // level of slot i: base(t) <= i < base(t + 1), base(t) = n - (n >> t)
+        r = (((i - (n - (n >> t))) << 1) | 1) << t;
+    }
+    return (r < rlo || r > rhi) ? -1 : r;
+}
+
+template <typename TC>
+__global__ void __launch_bounds__(256) k_combine(int lvl, int64_t n, int64_t rlo, int64_t rhi, int nbits, const int32_t *__restrict__ pos,
+                                                 const int32_t *__restrict__ opt, const int32_t *__restrict__ nnopt,
+                                                 const int32_t *__restrict__ nlopt,
+                                                 const TC *__restrict__ W, DevModel<TC> M, TC alpha,
+                                                 TC *__restrict__ cst, int32_t *__restrict__ ptr, int sh, int32_t *__restrict__ pz)
+{
+    // sh > 0 (after a leaf pass): the rows (rlo + i) << sh only -- the leaf rows were combined where they were computed
+    int64_t r = combine_row((int64_t)blockIdx.x * blockDim.x + threadIdx.x, n, rlo, rhi, lvl);
+    if (r < 0) return;
+    r <<= sh;
+    int64_t n1 = n + 1;
+    TC bv = cadd(W[r], dm_apply_affine(M, alpha, (int64_t)0, (int64_t)0, (int64_t)0, (int64_t)0));   // j = j' (empty part)
+    int64_t bp = r;
+    for (int b = 0; b < nbits; b++) {
+        if (!((r >> b) & 1)) continue;
+        int64_t p = opt[(int64_t)b * n1 + prow((r), n1 - 1)];
+        if (pz && (uint64_t)p > (uint64_t)n) { atomicAdd(pz, 1); p = r; }      // (poison mode: a cell nobody wrote)
+        int64_t nn = nnopt[(int64_t)b * n1 + prow((r), n1 - 1)];
+        int64_t nl = nlopt ? nlopt[(int64_t)b * n1 + prow((r), n1 - 1)] : 0;
+        TC v = cadd(W[p], dm_apply_affine(M, alpha, r - p, (int64_t)(pos[r] - pos[p]), nn, nl));
+        if (v < bv) { bv = v; bp = p; }            // lower bits hold larger p: strict < keeps the largest p on ties
+    }
+    cst[r] = bv;
+    ptr[r] = (int32_t)bp;
+}
+
+// windowed layers: the candidates of row r from the right: the diagonal, the standard planes by ascending bit, the common plane,
+// the mirrored planes by descending bit -- strict < while moving left keeps the largest p on ties
+template <typename TC>
+__global__ void __launch_bounds__(256) k_combine_win(int lvl, Geo G, int64_t n, int64_t rlo, int64_t rhi, const int32_t *__restrict__ pos,
+                                                     const int32_t *__restrict__ opt, const int32_t *__restrict__ nnopt,
+                                                     const int32_t *__restrict__ nlopt,
+                                                     const TC *__restrict__ W, DevModel<TC> M, TC alpha,
+                                                     TC *__restrict__ cst, int32_t *__restrict__ ptr, int sh, int32_t *__restrict__ pz)
+{
+    int64_t r = combine_row((int64_t)blockIdx.x * blockDim.x + threadIdx.x, n, rlo, rhi, lvl);
+    if (r < 0) return;
+    r <<= sh;                                                   // (after a leaf pass: the multiples of 64 only)
+    const int64_t n1 = n + 1;
+    TC bv = cadd(W[r], dm_apply_affine(M, alpha, (int64_t)0, (int64_t)0, (int64_t)0, (int64_t)0));   // j = j' (empty part)
+    int64_t bp = r;
+    if (r >= 1) {
+        const int64_t slot = prow((r), n1 - 1);
+        for (int i = 0; i <= 2 * G.s; i++) {
+            const int b = i <= G.s ? i : 2 * G.s - i;                       // 0 .. s, then s-1 .. 0
+            if (b < G.s && (((r >> b) & 1) != (i <= G.s))) continue;      // first pass: set bits (standard); second pass: clear bits (mirrored)
+            if (b == G.s && i != G.s) continue;
+            int64_t cs, ce;
+            if (!geo_block(G, r, b, cs, ce)) continue;
+            int64_t p = opt[(int64_t)b * n1 + slot];
+            if (pz && (uint64_t)p > (uint64_t)n) { atomicAdd(pz, 1); p = r; }
+            const int64_t nn = nnopt[(int64_t)b * n1 + slot];
+            const int64_t nl = nlopt ? nlopt[(int64_t)b * n1 + slot] : 0;
+            const TC v = cadd(W[p], dm_apply_affine(M, alpha, r - p, (int64_t)(pos[r] - pos[p]), nn, nl));
+            if (v < bv) { bv = v; bp = p; }
+        }
+    }
+    cst[r] = bv;
+    ptr[r] = (int32_t)bp;
+}
+
+// ------------------------------------------------------------------ host side
+// every row that is not a multiple of 64: inner planes, outer planes and the combine in one pass
+template <typename TC, bool HYP>
+void leaf_pass(const LayerCtx<TC> &C, LayerWork<TC> &Wk)
+{
+    hipStream_t s = C.s;
+    cp_csr_s *A = C.A;
+    const int64_t n = C.n;
+    const Geo &G = C.G;
+    const int64_t c0 = C.rlo > 1 ? C.rlo : 1, c1 = C.rhi < n ? C.rhi : n;
+    if (c1 < c0) return;
+    const int64_t g0 = c0 >> LEAF_T, g1 = c1 >> LEAF_T;
+    // bytes: the group's link entries twice (prev, next), column pointers, previous-layer costs, the two output rows
+    ProfScope ps(PROF_LEAF, s, (8.0 * (C.avg_deg + C.self_deg) + 4.0 + 8.0 + 12.0) * (double)((g1 - g0 + 1) << LEAF_T));
+    const int need = G.win ? G.s - LEAF_T + 2 : C.nbits - LEAF_T;           // outer planes a group can have (+ the pseudo-plane)
+    CP_REQUIRE(need <= 25, CP_EINTERNAL, "leaf pass: more outer planes than counters");
+    // With a gap pass in round 6 every task of that round with gap_min candidates or more has finished its rows (and the
+    // ranges of a leaf group in a plane b > 6 lie inside the range of the round-6 task of one of its two bounding rows): a longer
+    // range in a leaf group can only come from plane cells a mispredicted speculative layer never wrote (zeros after
+    // allocation: a range of millions of candidates per group, seconds of work for a layer that is redone anyway).  Such a
+    // group flags the layer (err) and skips the plane.
+    const int32_t lcap = (C.gaps && g_opt_gap_tau >= LEAF_T) ? (int32_t)std::max<int64_t>(g_opt_gap_min, 2) : INT32_MAX;
+    LeafArgs<TC, HYP> L{};
+    L.n = n; L.g0 = g0; L.ngroups = g1 - g0 + 1; L.c0 = c0; L.c1 = c1; L.nbits = C.nbits; L.planes = (int32_t)(g_opt_block_tables != 0);
+    L.pos = A->pos32.p; L.prev = A->prev.p; L.next = A->next.p; L.col = A->col.p;
+    L.fpos = if_hyp<HYP>(A->fpos32.p); L.flast = if_hyp<HYP>(A->flast.p); L.ffirst = if_hyp<HYP>(A->ffirst.p);
+    L.lpos = if_hyp<HYP>(A->lpos32.p); L.lfirst = if_hyp<HYP>(A->lfirst.p);
+    L.opt = Wk.pl.opt.p; L.nnopt = Wk.pl.nnopt.p; L.nlopt = if_hyp<HYP>(Wk.pl.nlopt.p); L.fin = Wk.pl.fin.p; L.fin_stamp = Wk.pl.fin_stamp;
+    L.W = C.W; L.M = C.M; L.alpha = C.alpha; L.cst = C.cst_out; L.ptr = C.ptr_out; L.G = G;
+    L.anchM = Wk.win.leaf_anch.p; L.anchM2 = if_hyp<HYP>(Wk.win.leaf_anch2.p); L.lcap = lcap; L.err = &Wk.sp.rc.p->err; L.pz = C.pzp;
+    constexpr int WPB = LeafWPB<HYP>::v;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(need <= 18 ? k_leaf<TC, HYP, 18> : k_leaf<TC, HYP, 25>), dim3((unsigned)cdiv(L.ngroups, WPB)), dim3(64 * WPB), 0, s, L);
+    CP_HIP(hipGetLastError());
+}
+
+// The rows left: with the leaf pass the multiples of 64 (their planes from LEAF_T up), without it every row.  Threads in row
+// order.  (lvl = 1, DBG_COMBINE_BY_SLOT: in plane-slot order, so that the dozen plane reads of a row are contiguous across a
+// wave -- measured 867 us against 650 us at config 3: the 2 x 12 gathers W[p], pos[p] of a row are what counts, and they are
+// neighbours only for neighbouring rows.)
+template <typename TC, bool HYP>
+void combine_rows(const LayerCtx<TC> &C, LayerWork<TC> &Wk)
+{
+    hipStream_t s = C.s;
+    cp_csr_s *A = C.A;
+    const int64_t n = C.n;
+    const bool leaf = C.leaf;
+    ProfScope ps(PROF_COMBINE, s, 24.0 * (double)(leaf ? (n >> LEAF_T) + 1 : n + 1));
+    const int64_t c0 = C.rlo > 0 ? C.rlo : 0, c1 = C.rhi < n ? C.rhi : n;
+    const int64_t r0 = leaf ? (c0 + LEAF_G - 1) >> LEAF_T : c0, r1 = leaf ? c1 >> LEAF_T : c1;       // leaf: the multiples of 64 in [c0, c1]
+    const int lvl = (!leaf && (g_opt_dbg & DBG_COMBINE_BY_SLOT)) ? (2 * (c1 - c0 + 1) >= n + 1) : 0;
+    const int sh = leaf ? LEAF_T : 0;
+    const int32_t *nl = if_hyp<HYP>(Wk.pl.nlopt.p);
+    if (c1 >= c0 && r1 >= r0) {
+        const unsigned cgrid = (unsigned)cdiv(lvl ? n + 1 : r1 - r0 + 1, 256);
+        if (C.G.win) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_combine_win<TC>), dim3(cgrid), dim3(256), 0, s, lvl, C.G, n, r0, r1, A->pos32.p, Wk.pl.opt.p, Wk.pl.nnopt.p, nl, C.W, C.M,
+                                        C.alpha, C.cst_out, C.ptr_out, sh, C.pzp);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_combine<TC>), dim3(cgrid), dim3(256), 0, s, lvl, n, r0, r1, C.nbits, A->pos32.p, Wk.pl.opt.p, Wk.pl.nnopt.p, nl, C.W, C.M, C.alpha,
+                                C.cst_out, C.ptr_out, sh, C.pzp);
+    }
+}
+
+#define CP_INST(TC, HYP) \
+    template void leaf_pass<TC, HYP>(const LayerCtx<TC> &, LayerWork<TC> &); \
+    template void combine_rows<TC, HYP>(const LayerCtx<TC> &, LayerWork<TC> &);
+CP_INST(int64_t, false) CP_INST(int64_t, true) CP_INST(double, false) CP_INST(double, true)
+#undef CP_INST
+
+}  // namespace cpk

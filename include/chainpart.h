@@ -308,7 +308,7 @@ int32_t cp_test_own_split(cp_csr_t csr, int32_t *vpos_out, int32_t *vsa_out, int
  * previous one), "rpass_ch"/"rpass_small_tau"/"rpass_cap" (right-part passes: columns per wave, last
  * lane-per-row round, lane-private share of a row in per cent of the mean), "setup_bs" (lanes per block of the task setup), "force_max" (a round whose flattened
  * stage served at most this many tasks gives them tiles of their own from the next layer on), "leaf" (1: the rounds tau < 6 of a
- * layer are one leaf pass, csrc/dp_leaf.inc; 0: divide-and-conquer rounds down to tau = 0), "block_tables" (1: the leaf pass also
+ * layer are one leaf pass, csrc/dp_total_leaf.hip; 0: divide-and-conquer rounds down to tau = 0), "block_tables" (1: the leaf pass also
  * stores every per-block winner, needed by cp_dp_block_tables), "poison" (1: test mode of cp_get_stat above), "fixed_point" (1: layers
  * after one that reproduced its input row are copied), "bn_wave" (bottleneck DP walk: 0 lane per chunk of "bn_chunk" rows, 1 wave
  * per run of "bn_run" rows in lockstep, 2 = default: searched crossings for Int64 costs), "bn_slack" (columns of the start bracket), "lws" (1,

@@ -1,5 +1,5 @@
-"""Per-kernel register / scratch / occupancy table of a HIP translation unit (hipcc -Rpass-analysis=kernel-resource-usage).
-usage: python tools/resource_usage.py chainpartitioners.jl_amd/csrc/dp_total.hip [--all]"""
+"""Per-kernel register / scratch / occupancy table of one or more HIP translation units (hipcc -Rpass-analysis=kernel-resource-usage).
+usage: python tools/resource_usage.py chainpartitioners.jl_amd/csrc/dp_total.hip [chainpartitioners.jl_amd/csrc/dp_total_leaf.hip ...] [--all]"""
 import re
 import subprocess
 import sys
@@ -14,11 +14,12 @@ def demangle(names):
 
 
 def main():
-    src = sys.argv[1]
     show_all = "--all" in sys.argv
-    cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off",
-           "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", "/dev/null"]
-    txt = subprocess.run(cmd, capture_output=True, text=True).stderr
+    txt = ""
+    for src in [a for a in sys.argv[1:] if not a.startswith("--")]:
+        cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off",
+               "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", "/dev/null"]
+        txt += subprocess.run(cmd, capture_output=True, text=True).stderr
     blocks = re.split(r"remark: [^\n]*Function Name: ", txt)[1:]
     rows = []
     for b in blocks:
