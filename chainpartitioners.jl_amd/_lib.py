@@ -93,6 +93,7 @@ SIGNATURES = {
     "cp_partition_bisect_index": (_i32, [_vp, _i64, _MODEL, _i32, _I64("spl_out")]),
     "cp_partition_lazy_bisect_cost": (_i32, [_vp, _i64, _MODEL, _f64, _I64("spl_out")]),
     "cp_partition_lazy_bisect_cost_probes": (_i32, [_vp, _i64, _MODEL, _f64, _I64("spl_out"), _pi64]),
+    "cp_partition_lazy_bisect_cost_pi": (_i32, [_vp, _i64, _MODEL, _ROWPART, _f64, _I64("spl_out"), _I64("nprobes_out")]),
     "cp_pack_convex": _PACK,
     "cp_pack_convex_batch": (_i32, [_vp, _i64, _MODEL, _I64("wmax"), _i64, _I64("spl_out"), _I64("K_out")]),
     "cp_partition_convex": _SPLIT,
@@ -331,11 +332,18 @@ class HipBackend:
         return self.lib.cp_partition_bisect_index_pi(self._h(A), K, mm, rp, flip, spl)
 
     def partition_lazy_bisect_cost(self, A, K, mm, eps, spl):
+        """the row partition of a primary model rides on the marshalled model (mm.rowpart, set by api._dispatch)"""
+        if getattr(mm, "rowpart", None) is not None:
+            return self.lib.cp_partition_lazy_bisect_cost_pi(self._h(A), K, mm, mm.rowpart, eps, spl, None)
         return self.lib.cp_partition_lazy_bisect_cost(self._h(A), K, mm, eps, spl)
 
-    def partition_lazy_bisect_cost_probes(self, A, K, mm, eps):
-        """(rc, spl, number of probes the bisection ran)"""
+    def partition_lazy_bisect_cost_probes(self, A, K, mm, eps, rp=None):
+        """(rc, spl, number of probes the bisection ran); rp: the row partition a primary model needs"""
         spl = np.zeros(K + 1, dtype=np.int64)
+        if rp is not None:
+            npr = np.zeros(1, dtype=np.int64)
+            rc = self.lib.cp_partition_lazy_bisect_cost_pi(self._h(A), K, mm, rp, eps, spl, npr)
+            return rc, spl, int(npr[0])
         npr = C.c_int64()
         rc = self.lib.cp_partition_lazy_bisect_cost_probes(self._h(A), K, mm, eps, spl, C.byref(npr))
         return rc, spl, npr.value

@@ -100,6 +100,14 @@ def _need_hip(b, mdl):
                                   f"'{getattr(b, 'name', type(b).__name__)}'")
 
 
+def _lazy_primary_needs_hip(b, mdl):
+    """LazyBisectCost on a primary connectivity model (LazyBisectCostBottleneckSplitter.jl:390-483) is a kernel of the HIP backend;
+    the CPU test oracle does not know the pair."""
+    if getattr(mdl, "kind", None) == M.CP_MODEL_PRIMARY and getattr(b, "name", "") != "hip":
+        raise NotImplementedError(f"LazyBisectCostBottleneckSplitter({type(mdl).__name__}) is implemented by the HIP backend only, not by "
+                                  f"backend '{getattr(b, 'name', type(b).__name__)}'")
+
+
 def _marshal(A, f, Pi, stack_method=False):
     mdl, weight, w_max = M.split_constraint(f)
     wlo, wt = _w_table_for(A, mdl, weight, w_max, stack_method)
@@ -122,6 +130,9 @@ def _marshal(A, f, Pi, stack_method=False):
 # spl[, rp]).  Rows are found along the MRO, so the Reference* and Flip* classes follow their bases.
 _Row = namedtuple("_Row", "call what stack pi refuse scalars")
 _PI_ALWAYS, _PI_IF_NEEDED, _PI_NEVER = "always", "if the model needs_rowpart", "never"
+# The backend method of LazyBisectCost has no argument for Pi (its call is pinned as (A, K, mm, eps, spl)), and only its primary
+# specialisation reads one: for a model with needs_rowpart Pi travels on the marshalled model, as mm.rowpart.
+_PI_ON_MODEL = "on the marshalled model, if the model needs_rowpart"
 _DYNAMIC = _Row("partition_dynamic", "Dynamic*", False, _PI_ALWAYS, None, lambda m: (m.combine, m.order))
 _PARTITION = {
     M.DynamicTotalSplitter: _DYNAMIC, M.DynamicBottleneckSplitter: _DYNAMIC,
@@ -130,7 +141,7 @@ _PARTITION = {
                                          "BisectCost on a ConstrainedCost errors in the reference (Costs.jl:150)", lambda m: (m.eps, m.flip)),
     M.BisectIndexBottleneckSplitter: _Row("partition_bisect_index", "BisectIndex", False, _PI_IF_NEEDED,
                                           "BisectIndex on a ConstrainedCost errors in the reference (Costs.jl:150)", lambda m: (m.flip,)),
-    M.LazyBisectCostBottleneckSplitter: _Row("partition_lazy_bisect_cost", "LazyBisectCost", False, _PI_NEVER,
+    M.LazyBisectCostBottleneckSplitter: _Row("partition_lazy_bisect_cost", "LazyBisectCost", False, _PI_ON_MODEL,
                                              "LazyBisectCost on a ConstrainedCost has no method in the reference", lambda m: (m.eps,)),
     M.ConvexTotalSplitter: _Row("partition_convex", "ConvexTotalSplitter", True, _PI_ALWAYS, None, lambda m: ()),
     M.ConcaveTotalSplitter: _Row("partition_concave", "ConcaveTotalSplitter", True, _PI_ALWAYS, None, lambda m: ()),
@@ -151,9 +162,16 @@ def _dispatch(fn, table, head, method, Pi, backend, alloc):
     row = next((table[c] for c in type(method).__mro__ if c in table), None)
     if row is None:
         raise NotImplementedError(f"{fn}: method {type(method).__name__} is outside the hot path")
-    if row.pi == _PI_NEVER or (row.pi == _PI_IF_NEEDED and not getattr(M.split_constraint(method.f)[0], "needs_rowpart", False)):
+    needs = hasattr(method, "f") and getattr(M.split_constraint(method.f)[0], "needs_rowpart", False)
+    rides = None
+    if row.pi == _PI_ON_MODEL:
+        _lazy_primary_needs_hip(b, M.split_constraint(method.f)[0])
+        rides, Pi = (Pi if needs else None), None
+    if row.pi == _PI_NEVER or (row.pi == _PI_IF_NEEDED and not needs):
         Pi = None
     mdl, mm, wm, wi, wf, rp, keep = _marshal(head[0], method.f, Pi, row.stack)
+    if rides is not None:
+        mm.rowpart, mm.rowpart_keep = _rowpart(rides)
     if row.refuse is not None and wm is not None:
         raise NotImplementedError(row.refuse)
     outs = alloc()

@@ -73,7 +73,11 @@ def _promote(*xs):
 
 
 class Marshalled:
-    """A cp_model_t plus the numpy buffers it points into (kept alive together)."""
+    """A cp_model_t plus the numpy buffers it points into (kept alive together).  `rowpart`: the row partition of a call whose
+    backend method has no argument for one (LazyBisectCost on a primary model), as (cp_rowpart_t, its buffers) in rowpart /
+    rowpart_keep; None everywhere else.  The struct bytes do not know about it."""
+    rowpart = None
+    rowpart_keep = ()
 
     def __init__(self, struct, keep):
         self.struct = struct
@@ -501,7 +505,9 @@ class FlipBisectIndexBottleneckSplitter(BisectIndexBottleneckSplitter):
 
 
 class LazyBisectCostBottleneckSplitter:
-    """LazyBisectCostBottleneckSplitter.jl:1-4, connectivity specialisation :140-258, monotonized symmetric one :260-388"""
+    """LazyBisectCostBottleneckSplitter.jl:1-4, connectivity specialisation :140-258, monotonized symmetric one :260-388, and the
+    one for an AffinePrimaryConnectivityModel under a row partition, partition_stripe(A, K, method, Pi), :390-483 (HIP backend
+    only; Pi is any partition of the rows with at most K parts)"""
 
     def __init__(self, f, eps):
         self.f, self.eps = f, float(eps)

@@ -169,6 +169,14 @@ int32_t cp_partition_lazy_bisect_cost(cp_csr_t csr, int64_t K, const cp_model_t 
  * the pattern with its diagonal added.  This form also reports the number of probes the bisection ran (nprobes_out may be NULL). */
 int32_t cp_partition_lazy_bisect_cost_probes(cp_csr_t csr, int64_t K, const cp_model_t *model, double eps,
                                              int64_t *spl_out /* K+1 */, int64_t *nprobes_out);
+/* partition_stripe(A, K, LazyBisectCostBottleneckSplitter(f::AbstractPrimaryConnectivityModel, eps), Pi)
+ * LazyBisectCostBottleneckSplitter.jl:390-483: with CP_MODEL_PRIMARY the probe counts the local and remote nets of the open part
+ * from the link array and the owner of every entry's row, and a column that closes a part is recounted for the part it opens.
+ * Pi (asg or spl; any partition of the rows) is required and Pi->K <= K; CP_EINVAL otherwise, and for a negative beta (the bound
+ * asserts).  The bounds are the model form's (Pi dropped, Costs.jl:17-19), with per-part alpha those of test_Partitioners.jl:43-48.
+ * Every other model kind: cp_partition_lazy_bisect_cost_probes, Pi is not looked at.  nprobes_out (one value) may be NULL. */
+int32_t cp_partition_lazy_bisect_cost_pi(cp_csr_t csr, int64_t K, const cp_model_t *model, const cp_rowpart_t *Pi, double eps,
+                                         int64_t *spl_out /* K+1 */, int64_t *nprobes_out);
 /* pack_stripe(A, ConvexTotalChunker(..), [Pi]) / partition_stripe(A, K, ConvexTotalSplitter(..), [Pi])
  * ConvexTotalChunker.jl:9-265 */
 int32_t cp_pack_convex(cp_csr_t csr, const cp_model_t *model, const cp_rowpart_t *Pi,
