@@ -16,7 +16,7 @@ from .models import (PowerWorkModel, ConvexWorkModel, ConcaveWorkModel,   # noqa
                      ReferenceTotalSplitter, ReferenceBottleneckSplitter, ReferenceTotalChunker,
                      BisectCostBottleneckSplitter, FlipBisectCostBottleneckSplitter,
                      BisectIndexBottleneckSplitter, FlipBisectIndexBottleneckSplitter,
-                     LazyBisectCostBottleneckSplitter, DisjointPartitioner, AlternatingPartitioner,
+                     LazyBisectCostBottleneckSplitter, LazyFlipBisectCostBottleneckSplitter, DisjointPartitioner, AlternatingPartitioner,
                      AlternatingNetPartitioner, SymmetricPartitioner, AlternatingPacker, SymmetricPacker,
                      ConvexTotalChunker, ConvexTotalSplitter, ConcaveTotalChunker, ConcaveTotalSplitter)
 from . import _lib  # noqa: F401

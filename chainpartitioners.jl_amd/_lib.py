@@ -94,6 +94,7 @@ SIGNATURES = {
     "cp_partition_lazy_bisect_cost": (_i32, [_vp, _i64, _MODEL, _f64, _I64("spl_out")]),
     "cp_partition_lazy_bisect_cost_probes": (_i32, [_vp, _i64, _MODEL, _f64, _I64("spl_out"), _pi64]),
     "cp_partition_lazy_bisect_cost_pi": (_i32, [_vp, _i64, _MODEL, _ROWPART, _f64, _I64("spl_out"), _I64("nprobes_out")]),
+    "cp_partition_lazy_flip_bisect_cost": (_i32, [_vp, _i64, _MODEL, _ROWPART, _f64, _I64("spl_out"), _I64("nprobes_out")]),
     "cp_pack_convex": _PACK,
     "cp_pack_convex_batch": (_i32, [_vp, _i64, _MODEL, _I64("wmax"), _i64, _I64("spl_out"), _I64("K_out")]),
     "cp_partition_convex": _SPLIT,
@@ -347,6 +348,15 @@ class HipBackend:
         npr = C.c_int64()
         rc = self.lib.cp_partition_lazy_bisect_cost_probes(self._h(A), K, mm, eps, spl, C.byref(npr))
         return rc, spl, npr.value
+
+    def partition_lazy_flip_bisect_cost(self, A, K, mm, eps, spl, rp=None):
+        return self.lib.cp_partition_lazy_flip_bisect_cost(self._h(A), K, mm, rp, eps, spl, None)
+
+    def partition_lazy_flip_bisect_cost_probes(self, A, K, mm, eps, rp=None):
+        """(rc, spl, number of probes the bisection ran); rp: the row partition a primary or secondary model needs"""
+        spl, npr = np.zeros(K + 1, dtype=np.int64), np.zeros(1, dtype=np.int64)
+        rc = self.lib.cp_partition_lazy_flip_bisect_cost(self._h(A), K, mm, rp, eps, spl, npr)
+        return rc, spl, int(npr[0])
 
     def pack_convex(self, A, mm, rp, wm, wi, wf, spl, Kout):
         return self.lib.cp_pack_convex(self._h(A), mm, rp, wm, wi, wf, spl, Kout)

@@ -143,6 +143,8 @@ _PARTITION = {
                                           "BisectIndex on a ConstrainedCost errors in the reference (Costs.jl:150)", lambda m: (m.flip,)),
     M.LazyBisectCostBottleneckSplitter: _Row("partition_lazy_bisect_cost", "LazyBisectCost", False, _PI_ON_MODEL,
                                              "LazyBisectCost on a ConstrainedCost has no method in the reference", lambda m: (m.eps,)),
+    M.LazyFlipBisectCostBottleneckSplitter: _Row("partition_lazy_flip_bisect_cost", "LazyFlipBisectCost", False, _PI_IF_NEEDED,
+                                                 "LazyFlipBisectCost on a ConstrainedCost has no method in the reference", lambda m: (m.eps,)),
     M.ConvexTotalSplitter: _Row("partition_convex", "ConvexTotalSplitter", True, _PI_ALWAYS, None, lambda m: ()),
     M.ConcaveTotalSplitter: _Row("partition_concave", "ConcaveTotalSplitter", True, _PI_ALWAYS, None, lambda m: ()),
 }
@@ -162,6 +164,8 @@ def _dispatch(fn, table, head, method, Pi, backend, alloc):
     row = next((table[c] for c in type(method).__mro__ if c in table), None)
     if row is None:
         raise NotImplementedError(f"{fn}: method {type(method).__name__} is outside the hot path")
+    if isinstance(method, M.LazyFlipBisectCostBottleneckSplitter) and not hasattr(b, row.call):      # a kernel of the HIP backend
+        raise NotImplementedError(f"{type(method).__name__}: backend '{getattr(b, 'name', type(b).__name__)}' has no method {row.call}")
     needs = hasattr(method, "f") and getattr(M.split_constraint(method.f)[0], "needs_rowpart", False)
     rides = None
     if row.pi == _PI_ON_MODEL:

@@ -513,6 +513,15 @@ class LazyBisectCostBottleneckSplitter:
         self.f, self.eps = f, float(eps)
 
 
+class LazyFlipBisectCostBottleneckSplitter:
+    """LazyBisectCostBottleneckSplitter.jl:72-138, for decreasing costs: partition_stripe(A, K, method, [Pi]) with a connectivity
+    model (per-part alpha included), an AffinePrimaryConnectivityModel under a row partition with at most K parts, or an
+    AffineSecondaryConnectivityModel under a SplitPartition of the rows with exactly K parts (HIP backend only)"""
+
+    def __init__(self, f, eps):
+        self.f, self.eps = f, float(eps)
+
+
 class DisjointPartitioner:
     """AlternatingPartitioner.jl:1-10: columns first, then the rows of the adjoint given the column split."""
 

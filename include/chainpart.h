@@ -177,6 +177,17 @@ int32_t cp_partition_lazy_bisect_cost_probes(cp_csr_t csr, int64_t K, const cp_m
  * Every other model kind: cp_partition_lazy_bisect_cost_probes, Pi is not looked at.  nprobes_out (one value) may be NULL. */
 int32_t cp_partition_lazy_bisect_cost_pi(cp_csr_t csr, int64_t K, const cp_model_t *model, const cp_rowpart_t *Pi, double eps,
                                          int64_t *spl_out /* K+1 */, int64_t *nprobes_out);
+/* partition_stripe(A, K, LazyFlipBisectCostBottleneckSplitter(f, eps), [Pi])  LazyBisectCostBottleneckSplitter.jl:72-138, for
+ * decreasing costs: a probe closes a part behind the first column that makes its cost small enough; the whole bisection is one
+ * launch that streams the link array (csrc/lazy_flip.hip).  Model kinds:
+ *   CP_MODEL_CONNECTIVITY, CP_MODEL_COLBLOCK (per-part alpha included)        Pi is not looked at
+ *   CP_MODEL_PRIMARY      Pi (asg or spl) required, Pi->K <= K                 CP_EINVAL otherwise
+ *   CP_MODEL_SECONDARY    Pi->spl required, Pi->K == K                         CP_EINVAL otherwise
+ * every other kind: CP_EUNSUPPORTED, naming it.  The bounds are those of cp_partition_bisect_cost_pi (a negative beta of a model
+ * without per-part alpha: CP_EINVAL, the bound asserts); a primary model with per-part alpha takes those of
+ * test_Partitioners.jl:43-48.  nnz >= 2^31 - 16384: CP_EUNSUPPORTED.  nprobes_out (one value) may be NULL. */
+int32_t cp_partition_lazy_flip_bisect_cost(cp_csr_t csr, int64_t K, const cp_model_t *model, const cp_rowpart_t *Pi, double eps,
+                                           int64_t *spl_out /* K+1 */, int64_t *nprobes_out);
 /* pack_stripe(A, ConvexTotalChunker(..), [Pi]) / partition_stripe(A, K, ConvexTotalSplitter(..), [Pi])
  * ConvexTotalChunker.jl:9-265 */
 int32_t cp_pack_convex(cp_csr_t csr, const cp_model_t *model, const cp_rowpart_t *Pi,
