@@ -8,30 +8,20 @@
 // k before another column is read (:108-120).  Reaching k == K on a cheap enough range is success; running out of columns is failure.
 // The loop tests every j' in order, so "the first column whose inclusive prefix cost is <= c" is literal for any sign pattern.
 //
-// The stream is lazy.hip's: one workgroup of 1024 lanes, 16 Ki link entries per chunk, 16 per lane, 16-bit flag masks, one block
-// scan, the first qualifying column as a block minimum, restart behind a split.  All control state is block-uniform.
+// The probe runs over the chunk stream of lazy.hpp, like lazy.hip's forward probe; it stays a kernel of its own because it closes
+// behind the first fitting column where the forward probe closes in front of the first exceeding one, and has the empty-part loops
+// where that one has probe_init.  One kernel template, three modes:
 //   connectivity  flag prev[q] < j0                                  cost f(nv, np, #flags)
-//   primary       flags (prev[q] < j0) x (eown[q] == k), two counts    cost f(nv, np, #local, #remote)        (as k_lazy_bisect_plaid)
+//   primary       flags (prev[q] < j0) x (eown[q] == k), two counts    cost f(nv, np, #local, #remote)        (as lazy.hip's LB_PRIMARY)
 //   secondary     flag e2[q] == k                                     cost f(|Pi_k|, pins(Pi_k), l, d_k - l)  (SecondaryConnectivityCosts.jl:82-89)
 // e2[q] is the owner of entry q's row if q is the first entry of its column owned by that part and 0 otherwise (rows ascend inside a
 // column and the parts of a split are contiguous: a comparison with the neighbouring entry), so l, the number of columns of [j, j')
 // holding a row of part k, is the flag count since pos[j0], and d_k is the count over all columns.
 #include "lazy.hpp"
-#include <string>
 
 namespace cpk {
 
 enum { LF_CONN = 0, LF_PRIMARY = 1, LF_SECONDARY = 2 };
-
-// kinds 2 and 4 of dm_apply, slot for slot (the whole switch sends the Float64 kernel to scratch)
-template <typename TC>
-__device__ __forceinline__ TC lf_conn(const DevModel<TC> &m, TC alpha, int64_t nv, int64_t np, int64_t nn)
-{
-    if (m.kind == CP_MODEL_COLBLOCK)
-        return cadd(dm_comp(m.ac_const, m.ac_c, m.ac_tab, m.ac_len, m.ac_lo, nv),
-                    cmulc(nn, dm_comp(m.bc_const[0], m.bc_c[0], m.bc_tab[0], m.bc_len[0], m.bc_lo[0], nv)));
-    return cadd(cadd(cadd(alpha, cmulc(nv, m.p[CP_P_VERTEX])), cmulc(np, m.p[CP_P_PIN])), cmulc(nn, m.p[CP_P_NET]));
-}
 
 // e2 of the file comment, padded like eown, and dk[k - 1] = #{q : e2[q] == k} (zeroed by the caller); one atomic per wave and owner
 __global__ void __launch_bounds__(256) k_lazy_e2(int64_t N, int64_t Npad, const int64_t *__restrict__ pos, const int32_t *__restrict__ col,
@@ -65,14 +55,10 @@ __global__ void __launch_bounds__(LZ_T) k_lazy_flip(DevModel<TC> M, int64_t n, i
                                                     int64_t *__restrict__ spl, int64_t *__restrict__ spl_hi, int64_t *__restrict__ nprobes)
 {
     // lnk: prev (connectivity, primary) or e2 (secondary); eown: primary only; pspl / tpos / dk: secondary only
-    __shared__ std::conditional_t<MODE == LF_PRIMARY, LazyPlaidShared, LazyShared> S;
-    __shared__ int32_t s_first[LZ_T / 64], s_ncmp[LZ_T / 64];
-    int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // spl / spl_hi live in global memory; every store is made by lane 0 only and read back after a barrier
-    if (tid == 0) {
-        for (int64_t k = 0; k <= K; k++) { spl[k] = 0; spl_hi[k] = n + 1; }
-        spl[0] = 1; spl_hi[0] = 1;                                     // :87-91
-    }
+    constexpr bool PRI = MODE == LF_PRIMARY;
+    constexpr int FLAGS = MODE == LF_SECONDARY ? LZ_OWNER : PRI ? LZ_NEW_OWN : LZ_NEW;
+    __shared__ LazyShared<PRI> S;
+    int tid = threadIdx.x;
     // the constants of part k (secondary: |Pi_k|, its pins, d_k; read once per k) and the cost of the empty range as part k
     int64_t nvk = 0, npk = 0, dkk = 0;
     auto empty_cost = [&](int64_t k) -> TC {
@@ -80,7 +66,7 @@ __global__ void __launch_bounds__(LZ_T) k_lazy_flip(DevModel<TC> M, int64_t n, i
             int64_t s0 = pspl[k - 1] - 1, s1 = pspl[k] - 1;
             nvk = s1 - s0; npk = tpos[s1] - tpos[s0]; dkk = (int64_t)dk[k - 1];
             return lz_primary(M, dm_alpha(M, k), nvk, npk, (int64_t)0, dkk);
-        } else if constexpr (MODE == LF_PRIMARY) {
+        } else if constexpr (PRI) {
             return lz_primary(M, dm_alpha(M, k), (int64_t)0, (int64_t)0, (int64_t)0, (int64_t)0);
         } else {
             return lf_conn(M, dm_alpha(M, k), (int64_t)0, (int64_t)0, (int64_t)0);
@@ -99,80 +85,26 @@ __global__ void __launch_bounds__(LZ_T) k_lazy_flip(DevModel<TC> M, int64_t n, i
         }
         c_lo = (double)lo; c_hi = (double)hi;
     }
-    int64_t probes = 0;
-    bool stuck = false;
-    while (c_lo * (1 + eps) < c_hi) {                                  // :127-135
-        double c = (c_lo + c_hi) / 2;
-        probes++;
+    LazyBisection B(c_lo, c_hi, eps, n, K, spl, spl_hi);               // :87-91
+    double c;
+    while (B.next(c)) {                                                // :127-135
         bool res = false;
         int64_t k = 1;
         int32_t j0 = 0;                                                // 0-based first column of the open part
         int32_t col = 0;                                               // next column to test: j' = col + 2
         int32_t qs = 0;                                                // next link entry to read
         int32_t cnt0 = 0, cr0 = 0;                                     // flagged entries in [pos[j0], qs) (primary: local, remote)
-        if (tid == 0) spl[0] = 1;
         while (lz_le(empty_cost(k), c)) {                              // :99-106  leading empty parts
             if (k == K) { res = true; break; }
             if (tid == 0) spl[k] = 1;
             k += 1;
         }
         while (!res && col < n) {                                      // :108-120
-            // ---- one chunk of link entries [qs, qe), loaded as aligned 16-byte pieces
-            int32_t qa = qs & ~3;
-            int32_t qe = (int32_t)((int64_t)qa + LZ_CH < N ? (int64_t)qa + LZ_CH : N);
-            int32_t kk = k > INT32_MAX ? -1 : (int32_t)k;              // (owners are 1 .. Pi.K <= K)
-            uint32_t ml = 0, mr = 0;
-            {
-                int32_t b = qa + tid * LZ_E;
-#pragma unroll
-                for (int v4 = 0; v4 < LZ_E / 4; v4++) {
-                    int32_t x = b + 4 * v4;
-                    if (x < qe) {                                      // the arrays are padded by 8 entries or more
-                        int4 v = *reinterpret_cast<const int4 *>(lnk + x);
-                        uint32_t in = 0, nw = 0;
-                        if (x >= qs) in |= 1u;
-                        if (x + 1 >= qs && x + 1 < qe) in |= 2u;
-                        if (x + 2 >= qs && x + 2 < qe) in |= 4u;
-                        if (x + 3 >= qs && x + 3 < qe) in |= 8u;
-                        if constexpr (MODE == LF_SECONDARY) {
-                            if (v.x == kk) nw |= 1u;
-                            if (v.y == kk) nw |= 2u;
-                            if (v.z == kk) nw |= 4u;
-                            if (v.w == kk) nw |= 8u;
-                        } else {
-                            if (v.x < j0) nw |= 1u;
-                            if (v.y < j0) nw |= 2u;
-                            if (v.z < j0) nw |= 4u;
-                            if (v.w < j0) nw |= 8u;
-                        }
-                        nw &= in;
-                        if constexpr (MODE == LF_PRIMARY) {
-                            int4 o = *reinterpret_cast<const int4 *>(eown + x);
-                            uint32_t lc = 0;
-                            if (o.x == kk) lc |= 1u;
-                            if (o.y == kk) lc |= 2u;
-                            if (o.z == kk) lc |= 4u;
-                            if (o.w == kk) lc |= 8u;
-                            ml |= (nw & lc) << (4 * v4);
-                            mr |= (nw & ~lc) << (4 * v4);
-                        } else {
-                            ml |= nw << (4 * v4);
-                        }
-                    }
-                }
-            }
-            uint32_t mine = (uint32_t)__popc(ml) | ((uint32_t)__popc(mr) << 16), incl = mine;      // (a chunk holds at most 2^14 flags of either kind)
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) { uint32_t pv = (uint32_t)__shfl_up((int)incl, o); if (lane >= o) incl += pv; }
-            if (lane == 63) S.wsum[wave] = incl;
-            __syncthreads();
-            uint32_t wbase = 0;
-            for (int w = 0; w < wave; w++) wbase += S.wsum[w];
-            S.tbase[tid] = wbase + incl - mine;
-            if constexpr (MODE == LF_PRIMARY) { S.tml[tid] = (uint16_t)ml; S.tmr[tid] = (uint16_t)mr; }
-            else S.tmask[tid] = (uint16_t)ml;
-            if (tid == LZ_T - 1) S.total = wbase + incl;
-            __syncthreads();
+            // ---- one chunk of link entries [qs, qe)
+            int32_t qa, qe;
+            uint32_t m0, m1;
+            lz_load_flags<FLAGS>(lnk, eown, qs, N, j0, k, qa, qe, m0, m1);
+            lz_publish(S, m0, m1);
             // ---- test the columns that end inside the chunk, 1024 at a time
             bool restarted = false;
             while (col < n) {
@@ -181,12 +113,12 @@ __global__ void __launch_bounds__(LZ_T) k_lazy_flip(DevModel<TC> M, int64_t n, i
                 bool complete = c_me < n && e <= qe;
                 bool fits = false;
                 if (complete) {
-                    uint32_t pr = (uint32_t)lz_prefix(S, e - qa);
+                    uint32_t pr = lz_prefix(S, e - qa);
                     TC v;
                     if constexpr (MODE == LF_SECONDARY) {
                         int64_t l = (int64_t)cnt0 + (int64_t)pr;
                         v = lz_primary(M, dm_alpha(M, k), nvk, npk, l, dkk - l);
-                    } else if constexpr (MODE == LF_PRIMARY) {
+                    } else if constexpr (PRI) {
                         v = lz_primary(M, dm_alpha(M, k), (int64_t)(c_me - j0 + 1), (int64_t)(e - pos[j0]), (int64_t)cnt0 + (int64_t)(pr & 0xffffu),
                                        (int64_t)cr0 + (int64_t)(pr >> 16));
                     } else {
@@ -194,16 +126,10 @@ __global__ void __launch_bounds__(LZ_T) k_lazy_flip(DevModel<TC> M, int64_t n, i
                     }
                     fits = lz_le(v, c);
                 }
-                // first column that is cheap enough and number of complete columns of this batch
-                unsigned long long fm = __ballot(fits), cm = __ballot(complete);
-                if (lane == 0) { s_first[wave] = fm ? (wave * 64 + __ffsll((long long)fm) - 1) : INT32_MAX; s_ncmp[wave] = __popcll(cm); }
-                __syncthreads();
-                int32_t fx = INT32_MAX, ncomp = 0;
-                for (int w = 0; w < LZ_T / 64; w++) { fx = s_first[w] < fx ? s_first[w] : fx; ncomp += s_ncmp[w]; }
-                __syncthreads();
-                if (fx != INT32_MAX) {
+                LazyBatch bt = lz_batch_reduce(S, fits, complete);     // first column of this batch that is cheap enough
+                if (bt.first != INT32_MAX) {
                     // ---- close part k behind column cx (j' = cx + 2), then empty parts while f(j', j', k) <= c  (:110-118)
-                    int32_t cx = col + fx;
+                    int32_t cx = col + bt.first;
                     while (true) {
                         if (k == K) { res = true; break; }
                         if (tid == 0) spl[k] = (int64_t)cx + 2;
@@ -217,29 +143,20 @@ __global__ void __launch_bounds__(LZ_T) k_lazy_flip(DevModel<TC> M, int64_t n, i
                     restarted = true;
                     break;
                 }
-                col += ncomp;
-                if (ncomp < LZ_T) break;                               // the next column ends beyond the chunk
+                col += bt.ncomp;
+                if (bt.ncomp < LZ_T) break;                            // the next column ends beyond the chunk
             }
             if (!restarted) {
-                cnt0 += (int32_t)(S.total & 0xffffu);                  // everything flagged in [qs, qe) belongs to [j0, col]
+                cnt0 += (int32_t)(PRI ? S.total & 0xffffu : S.total);  // everything flagged in [qs, qe) belongs to [j0, col]
                 cr0 += (int32_t)(S.total >> 16);
                 qs = qe;
             }
             __syncthreads();
         }
         if (res && tid == 0) spl[K] = n + 1;                           // :101, :112
-        __syncthreads();
-        // no bound moved: the reference would repeat this probe forever (non-positive bounds); block-uniform exit
-        if ((res ? c_hi : c_lo) == c || probes > 4096) { stuck = true; break; }
-        if (res) {
-            c_hi = c;
-            for (int64_t t = tid; t <= K; t += LZ_T) spl_hi[t] = spl[t];
-        } else {
-            c_lo = c;
-        }
-        __syncthreads();
+        if (!B.close(res, c)) break;
     }
-    if (tid == 0) *nprobes = stuck ? -1 : probes;
+    B.finish(nprobes);
 }
 
 template <typename TC>
@@ -256,7 +173,7 @@ int32_t run_lazy_flip(cp_csr_s *A, int64_t K, const cp_model_t *mdl, const cp_ro
     DBuf<unsigned long long> dk;
     if (pri || sec) {
         upload_part(A, Pi, sec, R);
-        const int64_t Npad = (A->N > 0 ? A->N : 1) + 16;
+        const int64_t Npad = lazy_padded(A->N);
         own.alloc((size_t)Npad);
         if (pri) {
             hipLaunchKernelGGL(k_lazy_eown, dim3((unsigned)cdiv(Npad, 256)), dim3(256), 0, s, A->N, Npad, A->row.p, R.owner.p, own.p);
@@ -268,10 +185,7 @@ int32_t run_lazy_flip(cp_csr_s *A, int64_t K, const cp_model_t *mdl, const cp_ro
         }
         CP_HIP(hipGetLastError());
     }
-    DBuf<int64_t> buf((size_t)(2 * (K + 1) + 1));
-    int64_t *d_spl = buf.p, *d_hi = buf.p + (K + 1), *d_np = buf.p + 2 * (K + 1);
-    {
-        ProfScope ps(PROF_BISECT, s, 0.0);
+    return lazy_run(A, K, spl_out, nprobes_out, [&](int64_t *d_spl, int64_t *d_hi, int64_t *d_np) {
         const int64_t *nil = nullptr;
         if (sec)
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lazy_flip<TC, LF_SECONDARY>), dim3(1), dim3(LZ_T), 0, s, HM.d, A->n, A->N, K, A->pos32.p, own.p,
@@ -282,16 +196,7 @@ int32_t run_lazy_flip(cp_csr_s *A, int64_t K, const cp_model_t *mdl, const cp_ro
         else
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lazy_flip<TC, LF_CONN>), dim3(1), dim3(LZ_T), 0, s, HM.d, A->n, A->N, K, A->pos32.p, A->prev.p,
                                (const int32_t *)nullptr, nil, nil, (const unsigned long long *)nullptr, c_lo, c_hi, eps, d_spl, d_hi, d_np);
-    }
-    CP_HIP(hipGetLastError());
-    int64_t np_host = 0;
-    CP_HIP(hipMemcpyAsync(spl_out, d_hi, sizeof(int64_t) * (size_t)(K + 1), hipMemcpyDeviceToHost, s));
-    CP_HIP(hipMemcpyAsync(&np_host, d_np, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    CP_HIP(hipStreamSynchronize(s));
-    prof_collect();
-    CP_REQUIRE(np_host >= 0, CP_EINVAL, "cost bisection cannot terminate on these bounds (the reference loops forever: non-positive costs)");
-    if (nprobes_out) *nprobes_out = np_host;
-    return CP_OK;
+    });
 }
 
 }  // namespace cpk
@@ -313,10 +218,9 @@ extern "C" int32_t cp_partition_lazy_flip_bisect_cost(cp_csr_t A, int64_t K, con
             set_error(std::string("LazyFlipBisectCost has no device path for the ") + name + " model (kind " + std::to_string(kind) + ")");
             return CP_EUNSUPPORTED;
         }
-        if (pri || sec) CP_REQUIRE(Pi && (Pi->asg || Pi->spl) && Pi->K >= 1, CP_EINVAL, "this cost model needs a row partition Pi");
+        if (pri || sec) lazy_require_rowpart("LazyFlipBisectCost", Pi, K, pri);
         // the reference's secondary oracle indexes Pi.spl[k + 1] for k up to K (SecondaryConnectivityCosts.jl:84-87)
         if (sec) CP_REQUIRE(Pi->spl && Pi->K == K, CP_EINVAL, "LazyFlipBisectCost: the secondary model needs a SplitPartition of the rows with exactly K parts");
-        if (pri) CP_REQUIRE(Pi->K <= K, CP_EINVAL, "LazyFlipBisectCost: the row partition has more parts than K");
         CP_HIP(hipSetDevice(A->device));
         // (c_lo, c_hi) = bound_stripe(A, K, args..., ocl) ./ 1  (:125): what the Bisect entries take for the same model
         double lf = 0, hf = 0;
@@ -335,7 +239,7 @@ extern "C" int32_t cp_partition_lazy_flip_bisect_cost(cp_csr_t A, int64_t K, con
             rc = cp_bound_stripe_pi(A, K, Pi, model, &li, &hi, &lf, &hf);
         }
         if (rc != CP_OK) return rc;
-        CP_REQUIRE(A->N < ((int64_t)1 << 31) - LZ_CH, CP_EUNSUPPORTED, "LazyFlipBisectCost needs nnz < 2^31");
+        lazy_require_int32("LazyFlipBisectCost", A->N, "nnz");
         return with_cost_type(model->dtype, [&](auto tag) { return run_lazy_flip<decltype(tag)>(A, K, model, pri || sec ? Pi : nullptr, lf, hf, eps, spl_out, nprobes_out); });
     });
 }

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 import lazy_flip_model as lfm
-from test_gpu_plaid_lazy import big, cyclic, dense_column, pattern, split
+from test_gpu_plaid_lazy import CHUNK_CASES, big, cyclic, dense_column, pattern, split
 from util import cp, golden_matrices
 
 pytestmark = pytest.mark.gpu
@@ -101,9 +101,9 @@ def test_without_a_probe(hip):
 
 
 # ---------------------------------------------------------------- chunk boundaries
-@pytest.mark.parametrize("K", [2, 32])
-def test_across_chunk_boundaries(hip, K):
-    A = big()                                                         # nnz > 2 * 16384: splits fall inside chunks
+@pytest.mark.parametrize("pat, K", CHUNK_CASES)
+def test_across_chunk_boundaries(hip, pat, K):
+    A = pat()                                                         # nnz > 2 * 16384: splits fall inside chunks
     for mdl, Pi in ((LOC, split(A.m, K)), (funky_conn(A, K), None), (funky_prim(A, K), cyclic(A.m, (K + 1) // 2))):
         spl, probes = same_as_model(hip, A, K, mdl, Pi, 0.01)
         assert probes > 0

@@ -1,5 +1,5 @@
 """partition_stripe(A, K, LazyBisectCostBottleneckSplitter(f::AffinePrimaryConnectivityModel, eps), Pi) on the device
-(csrc/lazy.hip, k_lazy_bisect_plaid; LazyBisectCostBottleneckSplitter.jl:390-483): the split vector and the number of probes are
+(csrc/lazy.hip, k_lazy_bisect in its primary mode; LazyBisectCostBottleneckSplitter.jl:390-483): the split vector and the number of probes are
 those of tests/plaid_lazy_model.py, the reference's loop in pure Python."""
 import ctypes as C
 import functools
@@ -138,9 +138,37 @@ def big():
     return A
 
 
-@pytest.mark.parametrize("K", [2, 32])
-def test_across_chunk_boundaries(hip, K):
-    A = big()
+@functools.lru_cache(maxsize=None)
+def regular(degs):
+    """2100 x 2100 with 33600 entries: the column degrees are `degs`, repeated; the rows of a column are sorted distinct draws"""
+    n = 2100
+    rng = np.random.default_rng(2100 + sum(degs))
+    deg = np.resize(np.array(degs, dtype=np.int64), n)
+    colptr = np.concatenate([[1], 1 + np.cumsum(deg)]).astype(np.int64)
+    rows = np.concatenate([np.sort(rng.choice(n, size=d, replace=False)) + 1 for d in deg]).astype(np.int64)
+    assert colptr[-1] - 1 == 33600
+    return cp.SparseMatrixCSC(n, n, colptr, rows)
+
+
+def deg16():
+    """a chunk that starts at a column start holds exactly 1024 complete columns: the column batch fills every lane (and the loop
+    goes round again with nothing left), and the last column ends at the end of the chunk"""
+    return regular((16,))
+
+
+def deg15_17():
+    """column ends are odd: the restart behind a split begins inside an aligned 16-byte piece"""
+    return regular((15, 17))
+
+
+# (pattern, K); the ids of the cases on big() are their K
+CHUNK_CASES = [pytest.param(big, 2, id="2"), pytest.param(big, 32, id="32"), pytest.param(deg16, 5, id="deg16"),
+               pytest.param(deg15_17, 5, id="deg15_17")]
+
+
+@pytest.mark.parametrize("pat, K", CHUNK_CASES)
+def test_across_chunk_boundaries(hip, pat, K):
+    A = pat()
     for Pi in (split(A.m, K), cyclic(A.m, (K + 1) // 2)):
         for mdl, eps in ((COMM, 0.01), (PRIM(0.5, 1.0, 0.25, 3.0, 7.5), 0.5)):
             spl, probes = same_as_model(hip, A, K, mdl, Pi, eps)

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import sym_model as sm
+from test_gpu_plaid_lazy import deg15_17, deg16
 from util import cp, sprand, golden_matrices, suitesparse_shaped
 
 pytestmark = pytest.mark.gpu
@@ -342,9 +343,10 @@ def test_lazy_on_reference_matrices_and_the_headline_model(hip):
                 assert np.array_equal(spl, want) and probes == wp
 
 
-@pytest.mark.parametrize("K", [1, 2, 32])
-def test_lazy_across_chunk_boundaries(hip, K):
-    A = big()
+@pytest.mark.parametrize("pat, K", [pytest.param(big, 1, id="1"), pytest.param(big, 2, id="2"), pytest.param(big, 32, id="32"),
+                                    pytest.param(deg16, 5, id="deg16"), pytest.param(deg15_17, 5, id="deg15_17")])
+def test_lazy_across_chunk_boundaries(hip, pat, K):
+    A = pat()
     for mdl, eps in ((MODELS_I[1], 0.01), (cp.AffineMonotonizedSymmetricConnectivityModel(0, 0, 1, 100, 9), 0.5)):
         want, wp = sm.lazy_bisect(A, K, mdl, eps)
         spl, probes = _lazy(hip, A, K, mdl, eps)

@@ -3,6 +3,7 @@
 import numpy as np
 import pytest
 
+from test_gpu_plaid_lazy import deg15_17, deg16
 from util import cp, sprand, golden_matrices, suitesparse_shaped, banded
 
 pytestmark = pytest.mark.gpu
@@ -64,6 +65,15 @@ def test_lazy_bisect_cost_matches_oracle(hip, orc):
                     got = cp.partition_stripe(A, K, meth, backend=hip)
                     want = cp.partition_stripe(A, K, meth, backend=orc)
                     assert got == want, (A, K, f.dtype, eps)
+    # column degrees that put column ends on the chunk's end and restarts inside a 16-byte piece
+    K, eps = 5, 0.01
+    for A in (deg16(), deg15_17()):
+        for f in (cp.AffineConnectivityModel(0, 10, 1, 100), cp.AffineConnectivityModel(0, 3, 1, 3), cp.AffineConnectivityModel(0, 0, 0, 1),
+                  cp.AffineConnectivityModel(0.5, 0.25, 1.0, 3.0), cp.AffineConnectivityModel(0, 3, 1, 3, alpha_k=rng.integers(1, 11, K).tolist())):
+            rc, spl, probes = hip.partition_lazy_bisect_cost_probes(A, K, f.marshal(), eps)
+            assert rc == 0, hip.last_error()
+            want = cp.partition_stripe(A, K, cp.LazyBisectCostBottleneckSplitter(f, eps), backend=orc)
+            assert np.array_equal(spl, want.spl) and probes > 0, (A, f.dtype, f._params())
 
 
 def test_lazy_rejects_work_models(hip):
