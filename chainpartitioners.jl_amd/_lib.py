@@ -124,6 +124,7 @@ SIGNATURES = {
                                  _I32("tile_s2"), _I32("anchor"), _I32("anchor2"), _I32("row"), _I32("plane"), _i64, _i32, _I32("p_out"),
                                  _I32("nn_out"), _I32("nl_out"), _I64("res")]),
     "cp_test_own_split": (_i32, [_vp, _I32("vpos_out"), _I32("vsa_out"), _I32("vnext_out"), _I64("res")]),
+    "cp_test_own_pair": (_i32, [_i64, _i64, _I64("res")]),
     "cp_set_option": (_i32, [_str, _i64]),
     "cp_prof_enable": (_i32, [_i32]),
     "cp_prof_reset": (_i32, []),
@@ -295,6 +296,12 @@ class HipBackend:
         self._ok(rc, "cp_test_own_split")
         assert int(res[0]) == nb
         return nb, vpos[:nb], vsa[:nb], vnext[:int(res[1])]
+
+    def test_own_pair(self, nt, wave):
+        """the two slots of the run order a wave of the paired own-tile stream takes (test entry, host only): (has work, s0, s1)"""
+        res = np.zeros(3, np.int64)
+        self._ok(self.lib.cp_test_own_pair(nt, wave, res), "cp_test_own_pair")
+        return bool(res[0]), int(res[1]), int(res[2])
 
     def set_option(self, name, value):
         return self.lib.cp_set_option(name.encode(), value)

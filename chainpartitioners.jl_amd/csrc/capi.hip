@@ -142,7 +142,8 @@ static int32_t oracle_eval_into(cp_csr_t A, const cp_model_t *model, const cp_ro
 // fix_trips: tasks the block merge walked in more than one trip; bits 0 / 1 / 2: a task of 1 / FIX_SERIAL / FIX_SERIAL + 1 tiles was
 // merged; fix_items: the (task, trip) items the merges were handed (every attempt of a layer: a dropped round lists none).
 // own_split_tiles: own tiles that streamed only their plane's variable link entries (layers that were not redone); gap_split_tiles: the
-// same for the tiles of the gap rounds, which own_split_tiles does not count.  overlap_isect: column intersections cp_pack_overlap computed.
+// same for the tiles of the gap rounds, which own_split_tiles does not count.  own_pair_waves / own_pair_lone: waves of k_lpass_own that
+// ran two tiles / one because the run order ended ("own_pair"; layers that were not redone).  overlap_isect: column intersections cp_pack_overlap computed.
 // bn_sym_layers: DP layers the valley search ran for the monotonized symmetric model.  cut_scan_layers: DP layers of the plaid edge-cut
 // models the prefix-min scan ran (plaid_cut.hip).  kept: cp_set_option("poison", 1) starts a
 // poison pass by zeroing the other counters and leaves this one.
@@ -150,6 +151,7 @@ static const struct { const char *name; int64_t *var; bool kept; } g_stats[] = {
     {"spec_redo", &g_spec_redo, false}, {"poison_hits", &g_poison_hits, false}, {"fix_trips", &g_fix_trips, false},
     {"fix_edges", &g_fix_edges, false}, {"fix_items", &g_fix_items, false}, {"bn_sym_layers", &g_bn_sym_layers, true},
     {"own_split_tiles", &g_own_split_tiles, false}, {"gap_split_tiles", &g_gap_split_tiles, false},
+    {"own_pair_waves", &g_own_pair_waves, false}, {"own_pair_lone", &g_own_pair_lone, false},
     {"overlap_isect", &g_overlap_isect, false}, {"cut_scan_layers", &g_cut_scan_layers, false},
 };
 static void stats_reset(bool all) { for (const auto &c : g_stats) if (all || !c.kept) *c.var = 0; }
@@ -167,6 +169,7 @@ static const struct Opt { const char *name; int64_t *var; OptRule rule; int64_t 
     {"pool", &g_opt_pool, OPT_BOOL, 0, 0},                      // (1: keep freed device blocks >= 1 MB for reuse; 0: return them, now and from here on)
     {"own_blk", &g_opt_own_blk, OPT_BOOL, 0, 0},                // (1, default: own tiles at 256-column blocks, run in block order; 0: tiles counted from each task head, in task order)
     {"own_split", &g_opt_own_split, OPT_BOOL, 0, 0},            // (1, default: own tiles of the planes >= 8 stream only the plane's variable link entries; 0: the whole columns)
+    {"own_pair", &g_opt_own_pair, OPT_BOOL, 0, 0},              // (1, default: outside the gap rounds and the hyperedge costs a wave streams two own tiles; 0: one)
     {"gap_split", &g_opt_gap_split, OPT_BOOL, 0, 0},            // (1, default: so do the gap rounds' tiles of those planes -- while own_split is 1; 0: they stream the whole columns)
     {"lws", &g_opt_lws, OPT_BOOL, 0, 0},                        // (1, default: DynamicTotalChunker past the scan by chunk_lws.hip; 0: the one-wave kernel)
     {"gap_tau", &g_opt_gap_tau, OPT_CLAMP, NOLIM_LO, 20}, {"gap_min", &g_opt_gap_min, OPT_CLAMP, 8, NOLIM_HI}, {"gap_nr", &g_opt_gap_nr, OPT_CLAMP, 1, 2},
@@ -308,6 +311,15 @@ int32_t cp_test_fix_merge(const cp_model_t *model, int64_t ntask, const int64_t 
     if (!model || !toffs || !part_v || !part_p || !part_nn || !tile_s || !anchor || !row || !plane || !p_out || !nn_out || !res) return CP_EINVAL;
     return guarded([&]() -> int32_t {
         dp_fix_merge_test(model, ntask, toffs, part_v, part_p, part_nn, part_nl, tile_s, tile_s2, anchor, anchor2, row, plane, n, reps, p_out, nn_out, nl_out, res);
+        return CP_OK;
+    });
+}
+
+int32_t cp_test_own_pair(int64_t nt, int64_t wave, int64_t *res)
+{
+    if (!res) return CP_EINVAL;
+    return guarded([&]() -> int32_t {
+        dp_own_pair_test(nt, wave, res);
         return CP_OK;
     });
 }

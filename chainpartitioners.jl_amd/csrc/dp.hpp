@@ -142,6 +142,9 @@ extern int64_t g_opt_own_split;                // 1: outside round A the own til
 extern int64_t g_own_split_tiles;              // own tiles that took that path since the last reset (RoundCounts::n_split)
 extern int64_t g_opt_gap_split;                // 1 (and own_split 1): the gap rounds' tiles of the planes >= 8 do the same
 extern int64_t g_gap_split_tiles;              // gap tiles that took that path since the last reset (not counted in own_split_tiles)
+extern int64_t g_opt_own_pair;                 // 1: outside the gap rounds and the hyperedge costs a wave of k_lpass_own takes two slots of the run order
+extern int64_t g_own_pair_waves, g_own_pair_lone;      // waves that ran two tiles / one because the order ended, since the last reset
+void dp_own_pair_test(int64_t nt, int64_t wave, int64_t *res);      // dp_total.hip: cp_test_own_pair
 extern int64_t g_overlap_isect;                // column intersections cp_pack_overlap computed since the last reset (chunk_greedy.hip)
 void dp_own_split_test(cp_csr_s *A, int32_t *vpos_out, int32_t *vsa_out, int32_t *vnext_out, int64_t *res);      // dp_total.hip: cp_test_own_split
 extern int64_t g_opt_short_t, g_opt_short_e;   // k_setup_short: tasks with <= short_t candidates and <= short_e link entries finish in setup

@@ -24,6 +24,8 @@ int64_t g_opt_own_split = 1;           // own tiles of the planes >= 8 stream on
 int64_t g_own_split_tiles = 0;
 int64_t g_opt_gap_split = 1;           // ... and so do the gap rounds' tiles of those planes (effective while own_split is on)
 int64_t g_gap_split_tiles = 0;
+int64_t g_opt_own_pair = 1;            // two own tiles per wave outside the gap rounds and the hyperedge costs (k_lpass_own<PAIR>); 0: one
+int64_t g_own_pair_waves = 0, g_own_pair_lone = 0;
 int64_t g_opt_rpass_ch = 256;
 int64_t g_opt_rpass_small_tau = 4;
 int64_t g_opt_force_max = 1024;           // a round's flattened stage is replaced by own tiles when it served at most this many tasks

@@ -842,6 +842,141 @@ __device__ __forceinline__ void interior_stream(const int32_t *__restrict__ arr,
     }
 }
 
+// The same stream in parts, for the second tile of a wave with two (k_lpass_own<PAIR>): its stages leave while the first tile is at
+// work -- tile_head_loads (the prologue's loads, untouched) next to the first tile's, then behind the first tile's stream
+// tile_counters (counters, the run's ends) and tile_first (the first two blocks), then tile_trips (the loop).  The first tile, like
+// every one-tile wave, goes through interior_stream itself.  (interior_stream written as these four in a row computes the same,
+// but the compiler then lets the first trip's prefetch share a register with the second block and waits for the first two blocks
+// before it sends the prefetch: one round trip more per tile of more than one trip, 1 % on the windowed layers.  So the one-tile
+// form keeps its own text, and its code is what it was.)
+struct TileHead { int32_t cp[4], pv[4], ptop, qhi, qlo; };
+struct TileRun { int32_t Q_lo, Q_hi, x, x_end; int4 c0, c1; };
+
+__device__ __forceinline__ void tile_head_loads(TileHead &h, const int32_t *__restrict__ cpos, const int32_t *__restrict__ psum, int32_t p_first, int32_t tl,
+                                                int head, int lane)
+{
+    // Prologue, one group of loads: the column pointers of the lane's four steps (a step beyond tl reads the tile's last column),
+    // the run's two ends, and with psum (wave-uniform; own_split) what a step starts from: psum[end of the run's columns] -
+    // psum[its column], what the columns hold apart from the streamed entries.  (The counters are live through the loop anyway.)
+    const int32_t *__restrict__ cl = cpos + (p_first - tl), *__restrict__ pl = (psum ? psum : cpos) + (p_first - tl);      // the tile's last column
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const int32_t e = lane + 64 * k;
+        const uint32_t d = (uint32_t)(tl - (e < tl ? e : tl)) & 255u;
+        h.cp[k] = cl[d];
+        h.pv[k] = pl[d];
+    }
+    // head != 0: step 0 is the candidate p_first itself (no column stepped over): the run ends in front of that column
+    h.ptop = pl[tl + 1 - head];
+    h.qhi = cl[tl + 1 - head];
+    h.qlo = cl[0];
+}
+
+// Entries: a lane whose four positions start at or above Q_hi reads the run's last aligned quad instead -- inside the eight
+// entries of slack behind every streamed array (next: ensure_links, flast: ensure_self, + 16; vnext: split_build, + 8) -- and
+// what it reads is never flagged: every block that is not `inner` guards its flags by position, an inner one holds run entries only.
+// (x <= x_end wherever this is called: the offset from the trip's first entry is unsigned and below 1024 or x_end - x)
+__device__ __forceinline__ int4 tile_quad(const int32_t *__restrict__ arr, int32_t x, int32_t x_end, uint32_t o)
+{
+    const uint32_t r = (uint32_t)(x_end - x);
+    return *reinterpret_cast<const int4 *>(arr + x + (o < r ? o : r));
+}
+
+__device__ __forceinline__ void tile_counters(const TileHead &h, int32_t tl, int lane, bool psum, int32_t acc[4], int32_t sk[4], TileRun &r)
+{
+    r.Q_hi = __builtin_amdgcn_readfirstlane(h.qhi);
+    r.Q_lo = __builtin_amdgcn_readfirstlane(h.qlo);
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const bool on = lane + 64 * k <= tl;
+        sk[k] = on ? h.cp[k] : INT32_MAX;
+        acc[k] = (psum && on) ? h.ptop - h.pv[k] : 0;
+    }
+    r.x_end = r.Q_hi & ~3;
+    r.x = r.Q_lo & ~3;
+}
+
+__device__ __forceinline__ void tile_first(const int32_t *__restrict__ arr, int lane, TileRun &r)
+{
+    r.c0 = tile_quad(arr, r.x, r.x_end, 4 * lane);
+    r.c1 = tile_quad(arr, r.x, r.x_end, 256 + 4 * lane);
+}
+
+template <bool GE, bool DET = false>
+__device__ __forceinline__ void tile_trips(const int32_t *__restrict__ arr, TileRun &r, int32_t thr, int lane, int32_t acc[4], const int32_t sk[4],
+                                           int32_t sp_lo = 0, int32_t sp_hi = 0, int32_t *s_es = nullptr, int32_t *s_v = nullptr, int32_t *s_cnt = nullptr,
+                                           int kind = 0)
+{
+    const int32_t Q_lo = r.Q_lo, Q_hi = r.Q_hi, x_end = r.x_end;
+    int32_t x = r.x;
+    int4 c0 = r.c0, c1 = r.c1;
+    for (; x < Q_hi; x += 512) {
+        // the next 512 entries are issued before the current ones are touched: the wait below them is for c0 / c1 only
+        const int4 n0 = tile_quad(arr, x, x_end, 512 + 4 * lane), n1 = tile_quad(arr, x, x_end, 768 + 4 * lane);
+#pragma unroll
+        for (int c = 0; c < 2; c++) {
+            int32_t xc = x + c * 256;
+            if (xc >= Q_hi) break;                        // wave-uniform
+            int4 v = c ? c1 : c0;
+            int32_t pb = xc + 4 * lane;
+            // entries at or above Q_hi belong to columns above the tile: never flagged (those below Q_lo lie below every s)
+            // the lane's four flags, and the four wave masks
+            // (a block that lies inside the run -- all but the first and the last one -- needs none of the position guards: wave-uniform)
+            const bool inner = xc >= Q_lo && xc + 256 <= Q_hi;
+            bool f0 = GE ? v.x >= thr : v.x < thr, f1 = GE ? v.y >= thr : v.y < thr, f2 = GE ? v.z >= thr : v.z < thr, f3 = GE ? v.w >= thr : v.w < thr;
+            if (!inner) { f0 = f0 && pb < Q_hi; f1 = f1 && pb + 1 < Q_hi; f2 = f2 && pb + 2 < Q_hi; f3 = f3 && pb + 3 < Q_hi; }
+            const unsigned long long m0 = __ballot(f0), m1 = __ballot(f1), m2 = __ballot(f2), m3 = __ballot(f3);
+            if (DET) {
+                const uint32_t span = (uint32_t)(sp_hi - sp_lo - 1);           // v in (sp_lo, sp_hi)  <=>  (uint)(v - sp_lo - 1) < span
+                bool s0 = (uint32_t)(v.x - sp_lo - 1) < span, s1 = (uint32_t)(v.y - sp_lo - 1) < span, s2 = (uint32_t)(v.z - sp_lo - 1) < span,
+                     s3 = (uint32_t)(v.w - sp_lo - 1) < span;
+                if (!inner) {
+                    s0 = s0 && pb >= Q_lo && pb < Q_hi; s1 = s1 && pb + 1 >= Q_lo && pb + 1 < Q_hi;
+                    s2 = s2 && pb + 2 >= Q_lo && pb + 2 < Q_hi; s3 = s3 && pb + 3 >= Q_lo && pb + 3 < Q_hi;
+                }
+                if (s0 || s1 || s2 || s3) {                           // rare; only the lanes holding a special work here
+#pragma unroll
+                    for (int j = 0; j < 4; j++) {
+                        if (j == 0 ? s0 : j == 1 ? s1 : j == 2 ? s2 : s3) {
+                            int32_t val = j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w;
+                            int slot = atomicAdd(s_cnt, 1);
+                            if (slot <= SMAX - 1) {
+                                s_es[slot] = pb + j;                  // (the position; its column is looked up after the stream: no load stalls the loop)
+                                s_v[slot] = (int32_t)(((uint32_t)val & 0x7fffffffu) | ((uint32_t)kind << 31));
+                            }
+                        }
+                    }
+                }
+            }
+            int32_t tot = __popcll(m0) + __popcll(m1) + __popcll(m2) + __popcll(m3);                       // uniform
+            // flagged entries in the lanes below this one (v_mbcnt chains), packed with the lane's own first three flags: one
+            // cross-lane read then gives a step everything it needs about the lane its column starts in
+            uint32_t P0 = 0;
+            P0 = __builtin_amdgcn_mbcnt_hi((uint32_t)(m0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m0, P0));
+            P0 = __builtin_amdgcn_mbcnt_hi((uint32_t)(m1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m1, P0));
+            P0 = __builtin_amdgcn_mbcnt_hi((uint32_t)(m2 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m2, P0));
+            P0 = __builtin_amdgcn_mbcnt_hi((uint32_t)(m3 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m3, P0));
+            const int32_t pack = (int32_t)((P0 << 3) | (uint32_t)f0 | ((uint32_t)f1 << 1) | ((uint32_t)f2 << 2));
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                int32_t idx = sk[k] - xc;                 // block position of the step's first entry (huge for invalid steps)
+                bool inside = idx > 0 && idx < 256;
+                if (__ballot(inside)) {                   // wave-uniform: some column of this group starts inside the block
+                    int32_t cidx = inside ? idx : 0;
+                    int src = cidx >> 2, comp = cidx & 3;
+                    const int32_t g = __shfl(pack, src);
+                    int32_t Fb = (g >> 3) + __popc((uint32_t)g & ((1u << comp) - 1u));        // flagged entries of the block below position idx
+                    acc[k] += idx <= 0 ? tot : (inside ? tot - Fb : 0);
+                } else {
+                    acc[k] += idx <= 0 ? tot : 0;
+                }
+            }
+        }
+        c0 = n0; c1 = n1;
+    }
+}
+
+
 // ------------------------------------------------------------------ long tasks with tiles of their own
 // A task with >= OWN_MIN steps gets tiles of its own: every tile lies in one task, so all of them -- head and tail included --
 // take the uniform path: one contiguous run of the link array, suffix counts, tile-local evaluation.  k_own_map: tile ->
@@ -927,8 +1062,52 @@ __global__ void __launch_bounds__(256) k_blk_order(const RoundCounts *__restrict
     }
 }
 
+// The tile's own winner (k_lpass_own outside the gap passes): candidates from the lane's four steps, then the wave arg-min.
+// sk: the pin positions of the steps, wv: W of the candidates, acc / acc2: the counts; lane 0 holds the result.
+template <typename TC, bool HYP>
+__device__ __forceinline__ void own_tile_cands(Best<TC, HYP> cand[4], const int4 rec, int32_t tl, int head, int isA, const DevModel<TC> &M, TC alpha, int lane,
+                                               const int32_t acc[4], const int32_t acc2[4], const int32_t sk[4], const TC wv[4])
+{
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        int32_t e = lane + 64 * k;
+        best_clear(cand[k]);
+        if (e <= tl && !(head && isA && e == 0)) {     // round A: the head element p = r is not a candidate
+            int32_t p = rec.x - e;
+            TC fv = dm_apply_affine(M, alpha, (int64_t)(rec.y - p), (int64_t)(rec.z - sk[k]), (int64_t)acc[k], (int64_t)acc2[k]);
+            cand[k].v = cadd(wv[k], fv); cand[k].p = p; cand[k].nn = acc[k]; best_set_nl(cand[k], acc2[k]);
+        }
+    }
+}
+
+template <typename TC, bool HYP>
+__device__ __forceinline__ Best<TC, HYP> own_tile_winner(const Best<TC, HYP> cand[4], int lane)
+{
+    Best<TC, HYP> best; best_clear(best);
+#pragma unroll
+    for (int k = 0; k < 4; k++) best = better(best, cand[k]);       // increasing e = decreasing p: an earlier candidate wins ties
+    for (int o = 32; o > 0; o >>= 1) {              // wave arg-min; ties -> larger p
+        int src = (lane + o) & 63;
+        Best<TC, HYP> c; best_clear(c); c.v = shfl64(best.v, src); c.p = __shfl(best.p, src); c.nn = __shfl(best.nn, src);
+        if (HYP) best_set_nl(c, __shfl(best_nl(best), src));
+        bool take = (best.p < 0) ? (c.p >= 0) : (c.p >= 0 && (c.v < best.v || (c.v == best.v && c.p > best.p)));
+        if (lane + o < 64 && take) best = c;
+    }
+    return best;
+}
+
+// cp_set_option("own_pair"): the two slots of the run order wave w takes.  false: no slot is left for the wave.  A wave whose
+// second slot lies beyond the order takes its first one again (s1 == s0: it loads what it has loaded, and stores once).
+__host__ __device__ __forceinline__ bool own_pair_slots(int64_t w, int64_t nt, int64_t &s0, int64_t &s1)
+{
+    s0 = 2 * w;
+    s1 = 2 * w + 1 < nt ? 2 * w + 1 : s0;
+    return w >= 0 && s0 < nt;
+}
+
 // border, a_srec (blk = 1): the tile ids and their records in column-block order; wave k takes tile border[k], whose record is a_srec[k]
-template <typename TC, bool HYP, bool GAP>
+// PAIR (own_pair; neither GAP nor HYP): wave k takes the slots 2k and 2k + 1 of that order.
+template <typename TC, bool HYP, bool GAP, bool PAIR = false>
 __global__ void __launch_bounds__(256) k_lpass_own(int isA, const RoundCounts *__restrict__ rc, const int32_t *__restrict__ border,
                                                    const int32_t *__restrict__ a_pos, const int32_t *__restrict__ a_next,
                                                    const int32_t *__restrict__ a_fpos, const int32_t *__restrict__ a_flast,
@@ -948,9 +1127,80 @@ __global__ void __launch_bounds__(256) k_lpass_own(int isA, const RoundCounts *_
     //  over a column meet in L2: 10 % off this kernel, less than the sort of the tile list costs.  The block order of own_blk is a
     //  counting sort by 256-column block (k_own_map, one scan, k_blk_order): 4 % off, and the sort is paid.  Staging each block's
     //  entries once per round in LDS for all its tiles (one workgroup per block) was 23 % slower: DESIGN.md section 6b.)
-    // (No grid-stride loop here: it costs 14 VGPRs = two waves per SIMD.  The host launches one wave per tile of the buffer's
-    //  CAPACITY, which the round's verdict (k_round_scans) has checked the true count against.)
+    // (No grid-stride loop here.  The host launches one wave per tile -- PAIR: per two tiles -- of the buffer's CAPACITY, which
+    //  the round's verdict (k_round_scans) has checked the true count against.  A loop over tiles cost 14 VGPRs when the body
+    //  held 58 and that meant two waves per SIMD; since the grouped loads <long,false,false> holds 42, and PAIR spends the room on
+    //  a second tile whose stages leave with the first one's: DESIGN.md section 6.)
     int lane = threadIdx.x & 63;
+    if constexpr (PAIR && !HYP && !GAP) {
+        // Two tiles, A and B, of any two tasks, planes and blocks: everything of a tile is scalar per tile.  Both records leave
+        // together, then both prologues; A streams as a one-tile wave does (interior_stream; what B's prologue brought waits in 11
+        // VGPRs); A's end group (pin positions, W) and B's first two blocks leave together and A is evaluated and stored under
+        // them; B streams, then its end group and evaluation.  Of B's four exposed round trips outside its trips three are gone.  (Tried: B's first blocks issued with A's, and A evaluated
+        // after B's stream, so that A's end group hides too: 71 VGPRs = seven waves per SIMD; held to 64 it spills.)
+        // A lone wave (the order ends at A) runs A twice and a scalar branch keeps it from storing twice.
+        int64_t s0, s1;
+        if (!own_pair_slots((int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), rc->NT, s0, s1)) return;
+        const bool lone = s1 == s0;
+        // A model whose pin coefficient is zero multiplies the pin count by it: its lanes all read the pin position of the tile's
+        // last column instead (one line, not four: 4 of a step's ~25 bytes) -- a count >= 0 like the true one, so the product is
+        // the same zero, bit for bit; the load stays where it is, unconditional.
+        const uint32_t pinm = M.p[CP_P_PIN] != (TC)0 ? 255u : 0u;
+        const int4 vA = border ? a_srec[s0] : a_rec[s0], vB = border ? a_srec[s1] : a_rec[s1];
+        int64_t tA = s0, tB = s1;
+        if (border) { tA = border[s0]; tB = border[s1]; }
+        const int4 rA = make_int4(__builtin_amdgcn_readfirstlane(vA.x), __builtin_amdgcn_readfirstlane(vA.y), __builtin_amdgcn_readfirstlane(vA.z),
+                                  __builtin_amdgcn_readfirstlane(vA.w));
+        const int4 rB = make_int4(__builtin_amdgcn_readfirstlane(vB.x), __builtin_amdgcn_readfirstlane(vB.y), __builtin_amdgcn_readfirstlane(vB.z),
+                                  __builtin_amdgcn_readfirstlane(vB.w));
+        const int hdA = rA.w & 1, hdB = rB.w & 1;
+        const int32_t tlA = (rA.w >> 2) & 255, tlB = (rB.w >> 2) & 255;
+        const int sbA = rA.w >> 10, sbB = rB.w >> 10;                    // (own_split: the plane, or 0 -- one tile of a pair may be split, the other not)
+        const int64_t soA = sbA ? (int64_t)(sbA - SPLIT_BMIN) * vstride : 0, soB = sbB ? (int64_t)(sbB - SPLIT_BMIN) * vstride : 0;
+        const int32_t *__restrict__ arrA = sbA ? a_vnext : a_next, *__restrict__ arrB = sbB ? a_vnext : a_next;
+        TileHead hB;
+        tile_head_loads(hB, sbB ? a_vpos + soB : a_pos, sbB ? a_vsa + soB : (const int32_t *)nullptr, rB.x, tlB, hdB, lane);
+        TileRun uB;
+        int32_t accA[4], accB[4], skA[4], skB[4];
+        const int32_t zero4[4] = {0, 0, 0, 0};
+        interior_stream<true>(arrA, sbA ? a_vpos + soA : a_pos, rA.x, tlA, rA.y, lane, accA, skA, hdA, 0, 0, nullptr, nullptr, nullptr, 0,
+                              sbA ? a_vsa + soA : (const int32_t *)nullptr);
+        tile_counters(hB, tlB, lane, sbB != 0, accB, skB, uB);
+        TC wv[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int32_t e = lane + 64 * k;
+            const uint32_t d = (uint32_t)(tlA - (e < tlA ? e : tlA)) & 255u;
+            skA[k] = (a_pos + (rA.x - tlA))[d & pinm];
+            wv[k] = (W + (rA.x - tlA))[d];
+        }
+        tile_first(arrB, lane, uB);
+        Best<TC, HYP> cand[4];
+        {
+            const int sel = tlA >> 6;
+            if (lane == (tlA & 63)) a_tileS[tA] = sel == 0 ? accA[0] : sel == 1 ? accA[1] : sel == 2 ? accA[2] : accA[3];
+            own_tile_cands<TC, HYP>(cand, rA, tlA, hdA, isA, M, alpha, lane, accA, zero4, skA, wv);
+            const Best<TC, HYP> best = own_tile_winner<TC, HYP>(cand, lane);
+            if (lane == 0) part[tA] = best;
+        }
+        tile_trips<true>(arrB, uB, rB.y, lane, accB, skB);
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int32_t e = lane + 64 * k;
+            const uint32_t d = (uint32_t)(tlB - (e < tlB ? e : tlB)) & 255u;
+            skB[k] = (a_pos + (rB.x - tlB))[d & pinm];
+            wv[k] = (W + (rB.x - tlB))[d];
+        }
+        if (lone) return;
+        {
+            const int sel = tlB >> 6;
+            if (lane == (tlB & 63)) a_tileS[tB] = sel == 0 ? accB[0] : sel == 1 ? accB[1] : sel == 2 ? accB[2] : accB[3];
+            own_tile_cands<TC, HYP>(cand, rB, tlB, hdB, isA, M, alpha, lane, accB, zero4, skB, wv);
+            const Best<TC, HYP> best = own_tile_winner<TC, HYP>(cand, lane);
+            if (lane == 0) part[tB] = best;
+        }
+        return;
+    }
     int64_t tile = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (tile >= rc->NT) return;
     // (own_blk: k_blk_order left the record next to the tile id, in the order the waves run: one level of loads, not two)
@@ -2710,6 +2960,15 @@ static void split_build(cp_csr_s *A, SplitLinks &S, DBuf<int64_t> &scratch)
     S.built = true;
 }
 
+// Test entry (cp_test_own_pair): what own_pair_slots gives wave `wave` among nt tiles -- the function the kernel calls
+void dp_own_pair_test(int64_t nt, int64_t wave, int64_t *res)
+{
+    int64_t s0 = 0, s1 = 0;
+    res[0] = own_pair_slots(wave, nt, s0, s1) ? 1 : 0;
+    res[1] = s0;
+    res[2] = s1;
+}
+
 // Test entry (cp_test_own_split): the three arrays of the pattern on the host.  vpos_out / vsa_out: nb (n + 1) words, vnext_out: room
 // for the N entries; res: {nb, entries in vnext}.
 void dp_own_split_test(cp_csr_s *A, int32_t *vpos_out, int32_t *vsa_out, int32_t *vnext_out, int64_t *res)
@@ -3165,6 +3424,9 @@ static void round_scans(const LayerCtx<TC> &C, LayerWork<TC> &Wk, const RoundDes
 // Map and stream + evaluate.  split (run_layer): 0: whole columns; 1: every tile of the launch is of a plane >= SPLIT_BMIN, their
 // number is NT; 2: the launch also holds tiles of the planes below -- the gap round tau = 6 with its plane-7 tiles, and every
 // round below it with gap_tau < 6 -- and k_own_map counts: 1 600 same-address atomics per launch cost it 17 us at config 3.
+// (windowed layers keep one tile per wave: their tiles stream whole columns, ten trips and more, and paired they ran 5 % slower)
+template <bool HYP> static bool own_pairs(bool gap, bool win) { return !HYP && !gap && !win && g_opt_own_pair != 0; }
+
 template <typename TC, bool HYP>
 static void own_stream(const LayerCtx<TC> &C, LayerWork<TC> &Wk, const RoundDesc &R, RoundCounts *rc, const RoundCounts &P, bool gap, int split)
 {
@@ -3189,8 +3451,10 @@ static void own_stream(const LayerCtx<TC> &C, LayerWork<TC> &Wk, const RoundDesc
         exclusive_scan_i32_lb(Wk.ow.b_cnt.p, Wk.ow.b_start.p, Wk.ow.b_n.p, Wk.ow.b_nblk, nullptr, Wk.sc.scanws, s);
         hipLaunchKernelGGL(k_blk_order, dim3(mgrid), dim3(256), 0, s, rc, Wk.ow.o_rec.p, Wk.ow.o_brank.p, Wk.ow.b_start.p, Wk.ow.o_border.p, Wk.ow.o_srec.p, Wk.ow.b_cnt.p);
     }
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(gap ? k_lpass_own<TC, HYP, true> : k_lpass_own<TC, HYP, false>), dim3((unsigned)cdiv(gNT, 4)), dim3(256), 0, s,
-                       R.isA, rc,
+    // cp_set_option("own_pair", 0 | 1): outside the gap rounds and the hyperedge costs a wave takes two slots of the run order
+    const bool pair = own_pairs<HYP>(gap, C.G.win != 0);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(gap ? k_lpass_own<TC, HYP, true> : pair ? k_lpass_own<TC, HYP, false, !HYP> : k_lpass_own<TC, HYP, false>),
+                       dim3((unsigned)cdiv(pair ? cdiv(gNT, 2) : gNT, 4)), dim3(256), 0, s, R.isA, rc,
                        oblk ? Wk.ow.o_border.p : (const int32_t *)nullptr, A->pos32.p, A->next.p, if_hyp<HYP>(A->fpos32.p), if_hyp<HYP>(A->flast.p),
                        Wk.ow.o_tileS.p, Wk.ow.o_tileS2.p, Wk.ow.o_rec.p, Wk.ow.o_srec.p, C.W, C.M, C.alpha, recs<HYP>(Wk.ow.o_part), R.tau, Wk.ow.o_hi.p, Wk.ow.o_spec.p,
                        (int)((g_opt_dbg & DBG_GAP_ALL_SPECIAL) != 0), recs<HYP>(Wk.ow.o_sub), Wk.ow.o_spv.p, A->col.p, if_hyp<HYP>(A->ffirst.p),
@@ -3391,6 +3655,7 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
     };
     bool any_forced = false;
     std::vector<int8_t> split_mode((size_t)NR, 0);       // own_split per round (see own_stream)
+    std::vector<int8_t> pair_mode((size_t)NR, 0);        // own_pair per round
 
     for (int rd = 0; rd <= nbits; rd++) {
         RoundDesc R;
@@ -3453,6 +3718,7 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
             // (gap rounds: cp_set_option("gap_split", 0 | 1), effective while own_split is on)
             const int split = !(C.split_layer && !R.isA && (!gap || g_opt_gap_split)) ? 0 : R.tau + 1 >= SPLIT_BMIN ? 1 : 2;
             split_mode[(size_t)rd] = (int8_t)(gap ? -split : split);
+            pair_mode[(size_t)rd] = own_pairs<HYP>(gap, G.win != 0);
             own_stream<TC, HYP>(C, Wk, R, rc, P, gap, split);
             note(rd, 0, gap ? PROF_GAPSTREAM : PROF_OWN, R.tau, split != 0);
             if (gap) gap_finish<TC, HYP>(C, Wk, R, rc, P);
@@ -3494,6 +3760,7 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
         if (g.nown > 0 && g.NT > 0) {                   // (negative: a gap round)
             const int sm = split_mode[(size_t)rd];
             (sm < 0 ? g_gap_split_tiles : g_own_split_tiles) += std::abs(sm) == 1 ? g.NT : std::abs(sm) == 2 ? g.n_split : 0;
+            if (pair_mode[(size_t)rd]) { g_own_pair_waves += g.NT / 2; g_own_pair_lone += g.NT & 1; }      // (own_pair_slots over the true NT)
         }
     }
     for (int rd = 0; rd < NR; rd++) g_fix_items += got[(size_t)rd].n_items;      // (attempts that are redone included: a dropped round lists none)

@@ -18,9 +18,9 @@ for name in ("fetch", "write"):
     f = glob.glob(f"{OUT}/{name}/*/*_counter_collection.csv")
     rows = list(csv.DictReader(open(f[0])))
     cname = "FETCH_SIZE" if name == "fetch" else "WRITE_SIZE"
-    # the plain streaming kernel k_lpass_own<TC, HYP, GAP = false> (the gap-pass variant is a different kernel and profile slot)
+    # the plain streaming kernel k_lpass_own<TC, HYP, GAP = false[, PAIR]> (the gap-pass variant is a different kernel and profile slot)
     def plain(nm):
-        return "k_lpass_own<" in nm and nm.split("k_lpass_own<")[1].split(">")[0].replace(" ", "").endswith("false")
+        return "k_lpass_own<" in nm and nm.split("k_lpass_own<")[1].split(">")[0].replace(" ", "").split(",")[2] == "false"
     vals = [float(r["Counter_Value"]) for r in rows if plain(r["Kernel_Name"]) and r["Counter_Name"] == cname]
     out[cname] = {"launches": len(vals), "sum": sum(vals), "mean_per_launch": sum(vals) / max(len(vals), 1)}
 # bench line of the fetch run gives the algorithmic bytes per launch at the same configuration
