@@ -17,26 +17,6 @@
 namespace cpk {
 
 int64_t g_opt_force_brute = 0;
-int64_t g_opt_short_t = 8, g_opt_short_e = 64;
-int64_t g_opt_own_min = 64;
-int64_t g_opt_own_blk = 1;             // own tiles at absolute 256-column blocks, run in block order; 0: tiles from each task head (k_own_map)
-int64_t g_opt_own_split = 1;           // own tiles of the planes >= 8 stream only their plane's variable link entries (SplitLinks); 0: the whole columns
-int64_t g_own_split_tiles = 0;
-int64_t g_opt_gap_split = 1;           // ... and so do the gap rounds' tiles of those planes (effective while own_split is on)
-int64_t g_gap_split_tiles = 0;
-int64_t g_opt_own_pair = 1;            // two own tiles per wave outside the gap rounds and the hyperedge costs (k_lpass_own<PAIR>); 0: one
-int64_t g_own_pair_waves = 0, g_own_pair_lone = 0;
-int64_t g_opt_rpass_ch = 256;
-int64_t g_opt_rpass_small_tau = 4;
-int64_t g_opt_force_max = 1024;           // a round's flattened stage is replaced by own tiles when it served at most this many tasks
-int64_t g_opt_setup_bs = 1024;          // lanes per block of k_setup_short (a multiple of 64, at most 1024)
-int64_t g_opt_rpass_cap = 200;          // lane-private entries per row in k_rpass_small, per cent of the mean
-int64_t g_opt_nospec = 0, g_spec_redo = 0;
-int64_t g_opt_gap_tau = 6, g_opt_gap_min = 64, g_opt_gap_nr = 2;
-int64_t g_opt_ra_cache = 1;
-int64_t g_opt_leaf = 1, g_opt_block_tables = 0;
-int64_t g_opt_poison = 0, g_poison_hits = 0;
-int64_t g_fix_trips = 0, g_fix_edges = 0, g_fix_items = 0;
 int64_t g_opt_fixed_point = 0;
 int64_t g_opt_brute_max_n = 200000;
 int64_t g_opt_dbg = 0;

@@ -30,341 +30,37 @@
 //  * width-windowed layers (candidates max(0, r - w) <= p <= r: the ConstrainedCost DP, DynamicSplitter.jl:206-258) run the same
 //    kernels on another tiling of the candidates: every row has a task in every plane b <= floor(log2 w) -- standard, common
 //    and mirrored blocks, see struct Geo below and DESIGN.md section 4b.
+//
+// Units: the right pass is dp_total_rpass.hip, the gap passes are dp_total_gap.hip, the leaf pass and the combine dp_total_leaf.hip;
+// the other stages and the layer driver are here.  What the units share: dp_total.hpp.
 #include "dp_total.hpp"
 #include <optional>
 
 namespace cpk {
 
-struct RoundDesc {
-    int32_t isA, tau, nbits, nextra;
-    Geo G;                      // G.win: nbits = s + 1 planes, every row takes part in each of them
-    int64_t aoff[32];           // windowed round A: anchors of the mirrored head tasks of plane b start at aoff[b] (index r >> (b+1))
-    int64_t n, ntask;
-    int64_t tbase[36];          // tau rounds: tasks of bit plane b occupy [tbase[b], tbase[b+1])
-    int64_t tskip[36];          // ... and start at linear index tskip[b] of that plane (row-tiled runs skip rows left of the tile)
-    int64_t a_r0, a_nmain;      // round A: rows a_r0 .. a_r0 + a_nmain - 1, then the `extra` rows (ancestors outside the tile)
-    int64_t extra[64];
-    // round A also takes the LAST row n in every bit plane above its lowest one (tasks after the extra rows): no row lies to
-    // its right, so nothing bounds the rows next to it from the left; with opt[b][n] known first, they start there instead of
-    // at the block start -- which every round would otherwise re-scan (n is not a power of two: ~n steps per round)
-    int32_t nlast, last_b[31];
-    int32_t skip_std, skip_mir; // windowed round A: the standard / mirrored heads (bit b of the row set / clear, b < s) come from the cached counts
-    int32_t fin_stamp;          // a cell of the `fin` plane is set iff it holds this layer's stamp (1 .. 255: the plane is cleared every 255 layers, not every layer)
-};
+// options and statistics of the scheme (cp_set_option / cp_get_stat: capi.hip; declared in dp.hpp)
+int64_t g_opt_short_t = 8, g_opt_short_e = 64;
+int64_t g_opt_own_min = 64;
+int64_t g_opt_own_blk = 1;             // own tiles at absolute 256-column blocks, run in block order; 0: tiles from each task head (k_own_map)
+int64_t g_opt_own_split = 1;           // own tiles of the planes >= 8 stream only their plane's variable link entries (SplitLinks); 0: the whole columns
+int64_t g_own_split_tiles = 0;
+int64_t g_opt_gap_split = 1;           // ... and so do the gap rounds' tiles of those planes (effective while own_split is on)
+int64_t g_gap_split_tiles = 0;
+int64_t g_opt_own_pair = 1;            // two own tiles per wave outside the gap rounds and the hyperedge costs (k_lpass_own<PAIR>); 0: one
+int64_t g_own_pair_waves = 0, g_own_pair_lone = 0;
+int64_t g_opt_rpass_ch = 256;
+int64_t g_opt_rpass_small_tau = 4;
+int64_t g_opt_force_max = 1024;           // a round's flattened stage is replaced by own tiles when it served at most this many tasks
+int64_t g_opt_setup_bs = 1024;          // lanes per block of k_setup_short (a multiple of 64, at most 1024)
+int64_t g_opt_rpass_cap = 200;          // lane-private entries per row in k_rpass_small, per cent of the mean
+int64_t g_opt_nospec = 0, g_spec_redo = 0;
+int64_t g_opt_gap_tau = 6, g_opt_gap_min = 64, g_opt_gap_nr = 2;
+int64_t g_opt_ra_cache = 1;
+int64_t g_opt_leaf = 1, g_opt_block_tables = 0;
+int64_t g_opt_poison = 0, g_poison_hits = 0;
+int64_t g_fix_trips = 0, g_fix_edges = 0, g_fix_items = 0;
 
-__device__ __forceinline__ void decode_task(const RoundDesc &R, int64_t t, int64_t &r, int &b)
-{
-    if (R.G.win) {
-        // plane-major.  Round A: plane b <= s holds the rows that are multiples of 2^b (the heads of its rectangles);
-        // round tau: every plane b in (tau, s] holds all rows with ctz == tau
-        int bb = R.isA ? 0 : R.tau + 1;
-        while (t >= R.tbase[bb + 1]) bb++;
-        const int64_t l = t - R.tbase[bb] + R.tskip[bb];
-        r = R.isA ? ((l + 1) << bb) : (((l << 1) | 1) << R.tau);
-        b = bb;
-        return;
-    }
-    if (R.isA) {
-        if (t >= R.a_nmain + R.nextra) { r = R.n; b = R.last_b[t - R.a_nmain - R.nextra]; return; }
-        r = t < R.a_nmain ? R.a_r0 + t : R.extra[t - R.a_nmain]; b = __ffsll((long long)r) - 1; return;
-    }
-    int bb = R.tau + 1;
-    while (t >= R.tbase[bb + 1]) bb++;
-    int64_t l = t - R.tbase[bb] + R.tskip[bb];
-    int sh = bb - R.tau - 1;
-    int64_t base = l >> sh, v = l & (((int64_t)1 << sh) - 1);
-    r = (base << (bb + 1)) | ((int64_t)1 << bb) | (((v << 1) | 1) << R.tau);
-    b = bb;
-}
-
-// ------------------------------------------------------------------ right part: row-major threshold counts
-// cr[b][r] = #{q in columns [r-2^tau, r) : prev[q] < opt[b][r-2^tau]} for every set bit b > tau of r.
-// Small ranges: one lane per row (tau <= 3).
-// `ge` selects the comparison: 0: link < threshold (nets: prev[q] < B); 1: link >= threshold (self nets: first >= B
-// over the rows bucketed by their LAST column).
-// The 64 rows of a wave are consecutive, so they share every bit above tau + 6: planes whose bit is clear in the whole
-// wave are skipped with a wave-uniform test (about half of them).
-// (Tried: G = 2 .. 16 lanes per row, the group reading 16 G contiguous entries per step (a load instruction within 8 cache lines
-//  instead of 64) and adding up by a butterfly: 238 / 262 / 288 / 325 us at tau = 4 .. 1 against 161 / 149 / 167 / 217 -- the
-//  per-wave prelude (thresholds of two dozen planes) is then paid per 64 / G rows.)
-// (Tried: deciding all planes but one by the position of the link value among the Fenwick blocks, with lane-private LDS
-//  histograms -- 4x fewer VALU instructions but 300 B of LDS per row leave 2 waves per SIMD: slower.)
-template <bool ge, int NB>
-__global__ void __launch_bounds__(256) k_rpass_small(int tau, int nbits, int64_t n, int64_t u0, int64_t nrows, const int64_t *__restrict__ pos,
-                                                     const int32_t *__restrict__ prev, const int32_t *__restrict__ opt,
-                                                     int32_t *__restrict__ cr, int allp, int cap)
-{
-    // allp (windowed layers): every row takes part in every plane tau < b < nbits (an empty block holds the threshold -1 or a
-    // stale value: its count is never read)
-    int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    bool live = u < nrows;
-    u += u0;
-    int64_t r = ((u << 1) | 1) << tau;
-    if (r > n) live = false;
-    if (!live) r = 0;                                          // no bits: takes part in the ballots only
-    int64_t n1 = n + 1, rL = r - ((int64_t)1 << tau);
-    int32_t thr[NB], cnt[NB];
-    uint32_t used = 0;                                         // planes with a set bit somewhere in the wave (uniform)
-    int64_t prL = live ? prow((rL), n1 - 1) : 0;
-    // all threshold loads are issued back to back (a lane without bit b reads a valid dummy slot): one memory latency, not 23
-#pragma unroll
-    for (int b = 0; b < NB; b++) {
-        cnt[b] = 0;
-        thr[b] = ge ? INT32_MAX : INT32_MIN;
-        if (b <= tau || b >= nbits) continue;                  // wave-uniform
-        bool on = live && (allp || ((r >> b) & 1));
-        if (!__ballot(on)) continue;                           // wave-uniform
-        used |= 1u << b;
-        int32_t v = opt[(int64_t)b * n1 + (on ? prL : 0)];
-        if (on) thr[b] = v;
-    }
-    // Degrees vary a lot (the bench matrix: mean 10, one column in a hundred above 60) and a wave steps as often as its longest
-    // lane: every lane takes the first `cap` entries of its row on its own, sixteen per step, and what a row has beyond them
-    // is counted by the whole wave, 64 entries per coalesced load with the row's thresholds broadcast (the k_rpass_wave scheme).
-    int64_t q0 = 0;
-    int32_t len = 0;
-    if (live) { q0 = pos[rL]; len = (int32_t)(pos[r] - q0); }
-    const int32_t NEVER = ge ? INT32_MIN : INT32_MAX;          // a link value that is never counted
-    const int32_t mlen = len < cap ? len : cap;
-    for (int32_t o = 0; o < mlen; o += 16) {                   // sixteen entries in flight per lane
-        int32_t v[16];
-        // four 16-byte loads (dword-aligned: the global path takes unaligned vectors; the link arrays carry 16 entries of
-        // slack) instead of sixteen 4-byte ones: every lane reads another cache line, and the L1 takes a line per lane and
-        // instruction whatever its width
-        struct __attribute__((packed, aligned(4))) V4 { int32_t a, b, c, d; };
-        const V4 *pv = reinterpret_cast<const V4 *>(prev + q0 + o);
-        const int32_t rem = mlen - o;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            V4 t = {NEVER, NEVER, NEVER, NEVER};
-            if (4 * j < rem) t = pv[j];
-            v[4 * j] = t.a; v[4 * j + 1] = t.b; v[4 * j + 2] = t.c; v[4 * j + 3] = t.d;
-        }
-#pragma unroll
-        for (int j = 0; j < 16; j++) v[j] = j < rem ? v[j] : NEVER;
-#pragma unroll
-        for (int b = 0; b < NB; b++) {
-            if (!((used >> b) & 1)) continue;                  // wave-uniform
-            int32_t t = thr[b];
-            int32_t c = 0;
-#pragma unroll
-            for (int j = 0; j < 16; j++) c += ge ? (v[j] >= t) : (v[j] < t);
-            cnt[b] += c;
-        }
-    }
-    {
-        const int lane = threadIdx.x & 63;
-        uint32_t mypl = 0;                                     // the planes this lane's row takes part in
-        if (live)
-            for (int b = tau + 1; b < nbits; b++) if (allp || ((r >> b) & 1)) mypl |= 1u << b;
-        uint64_t rest = __ballot(len > cap);
-        const int32_t q0lo = (int32_t)(uint32_t)q0, q0hi = (int32_t)(q0 >> 32);
-        while (rest) {                                         // wave-uniform
-            const int src = __ffsll((unsigned long long)rest) - 1;
-            rest &= rest - 1;
-            const int64_t a = (((int64_t)__builtin_amdgcn_readlane(q0hi, src) << 32) | (uint32_t)__builtin_amdgcn_readlane(q0lo, src)) + cap;
-            const int32_t ln = __builtin_amdgcn_readlane(len, src) - cap;
-            const uint32_t pl = (uint32_t)__builtin_amdgcn_readlane((int32_t)mypl, src);
-            for (int32_t o = 0; o < ln; o += 64) {
-                const int32_t v = o + lane < ln ? prev[a + o + lane] : NEVER;
-#pragma unroll
-                for (int b = 0; b < NB; b++) {
-                    if (!((pl >> b) & 1)) continue;            // scalar branch
-                    const int32_t t = __builtin_amdgcn_readlane(thr[b], src);
-                    const int32_t c = (int32_t)__popcll(__ballot(ge ? (v >= t) : (v < t)));
-                    if (lane == src) cnt[b] += c;
-                }
-            }
-        }
-    }
-    if (!live) return;
-#pragma unroll
-    for (int b = 0; b < NB; b++)
-        if (b > tau && b < nbits && (allp || ((r >> b) & 1))) cr[(int64_t)b * n1 + prow((r), n1 - 1)] = cnt[b];
-}
-
-// Larger ranges: one wave per (row, chunk of CH columns); coalesced 64-entry loads.  The row -- hence every threshold -- is
-// wave-uniform: thresholds live in SGPRs, a plane's count of 64 entries is ONE vector compare into a lane mask plus a scalar
-// popcount and add (s_bcnt1 / s_add on the scalar unit), and the wave total needs no cross-lane reduction at the end.
-// (Round 1 kept per-lane counters: a compare and an add per entry and plane on the vector unit, 6 shuffles per plane to finish.)
-template <bool ge, int WPB>
-__global__ void __launch_bounds__(64 * WPB) k_rpass_wave(int tau, int nbits, int64_t n, int64_t u0, int64_t nrows, int chunks_per_row, int ch_cols,
-                                                         const int64_t *__restrict__ pos, const int32_t *__restrict__ prev,
-                                                         const int32_t *__restrict__ opt, int32_t *__restrict__ cr, int allp)
-{
-    // WPB > 1 (the host gives such a block WPB chunks of ONE row: chunks_per_row % WPB == 0): the waves add their counts in
-    // LDS and one of them updates the row.  Thousands of chunks of a row of a high round each sending an atomic to the same
-    // dozen addresses cost 35 ns apiece, one after the other: 70 us of an 85 us pass.
-    int64_t w = (int64_t)blockIdx.x * WPB + (threadIdx.x >> 6);
-    int lane = threadIdx.x & 63;
-    int64_t u = w / chunks_per_row;
-    int ck = (int)(w - u * chunks_per_row);
-    if (u >= nrows) return;                                    // (block-uniform when WPB > 1)
-    u += u0;
-    int64_t r = ((u << 1) | 1) << tau;
-    if (r > n) return;
-    int64_t n1 = n + 1, rL = r - ((int64_t)1 << tau);
-    int64_t c0 = rL + (int64_t)ck * ch_cols, c1 = c0 + ch_cols;
-    if (c1 > r) c1 = r;
-    int64_t prL = prow((rL), n1 - 1);
-    // planes of this row (wave-uniform).  Lane b holds plane b: it fetches the plane's threshold (ONE vector memory instruction
-    // for the row -- a uniform-address load per plane cost a dozen), keeps its count and stores it at the end.  The counting
-    // loop walks the set bits of `act`: v_readlane hands the threshold to the scalar side, a plane's count of 64 entries is one
-    // vector compare into a lane mask and a scalar popcount.  (Thresholds and counts in scalar register ARRAYS, one slot per
-    // plane, spilled 40-110 SGPRs into vector lanes and paid a skipped branch for every plane the row does not have.)
-    uint32_t act = 0;
-    for (int b = tau + 1; b < nbits; b++) if (allp || ((r >> b) & 1)) act |= 1u << b;
-    act = __builtin_amdgcn_readfirstlane(act);
-    const bool mine = lane < 32 && ((act >> lane) & 1);
-    const int32_t tv = mine ? opt[(int64_t)lane * n1 + prL] : 0;
-    int32_t acc = 0;
-    const int64_t q0 = pos[c0], q1 = pos[c1];
-    const int32_t NEVER = ge ? INT32_MIN : INT32_MAX;          // a link value that is never counted
-    // 512 entries per step as two 16-byte loads per lane, the next step's issued before this one's are counted: 4 KB in flight per
-    // wave at 39 VGPRs.  (With scalar-register arrays for thresholds and counts, four 16-byte loads per lane and 1024 entries per
-    // step needed 101 VGPRs -- occupancy 4, 18 % slower.)
-    int32_t a[8], nx[8];
-    struct __attribute__((packed, aligned(4))) V4 { int32_t x, y, z, w; };      // (16-byte loads, dword-aligned: a quarter of the memory instructions)
-#pragma unroll
-    for (int k = 0; k < 2; k++) {
-        const int64_t q = q0 + 4 * lane + 256 * k;
-        V4 t = {NEVER, NEVER, NEVER, NEVER};
-        if (q < q1) t = *reinterpret_cast<const V4 *>(prev + q);
-        a[4 * k] = t.x; a[4 * k + 1] = q + 1 < q1 ? t.y : NEVER; a[4 * k + 2] = q + 2 < q1 ? t.z : NEVER; a[4 * k + 3] = q + 3 < q1 ? t.w : NEVER;
-    }
-    for (int64_t qb = q0; qb < q1; qb += 512) {                // (a wave-uniform trip count keeps the counters on the scalar unit)
-#pragma unroll
-        for (int k = 0; k < 2; k++) {
-            const int64_t q = qb + 512 + 4 * lane + 256 * k;
-            V4 t = {NEVER, NEVER, NEVER, NEVER};
-            if (q < q1) t = *reinterpret_cast<const V4 *>(prev + q);
-            nx[4 * k] = t.x; nx[4 * k + 1] = q + 1 < q1 ? t.y : NEVER; nx[4 * k + 2] = q + 2 < q1 ? t.z : NEVER; nx[4 * k + 3] = q + 3 < q1 ? t.w : NEVER;
-        }
-        for (uint32_t rem = act; rem; rem &= rem - 1) {
-            const int b = __ffs(rem) - 1;
-            const int32_t t = __builtin_amdgcn_readlane(tv, b);
-            int32_t c = 0;
-#pragma unroll
-            for (int k = 0; k < 8; k++) c += (int32_t)__popcll(__ballot(ge ? (a[k] >= t) : (a[k] < t)));
-            acc += lane == b ? c : 0;
-        }
-#pragma unroll
-        for (int k = 0; k < 8; k++) a[k] = nx[k];
-    }
-    int32_t outv = acc;
-    if (WPB > 1) {
-        __shared__ int32_t sacc[WPB > 1 ? WPB : 1][32];
-        const int wv = threadIdx.x >> 6;
-        if (lane < 32) sacc[wv][lane] = mine ? outv : 0;
-        __syncthreads();
-        if (wv != 0) return;
-        if (mine) {
-            int32_t t = 0;
-#pragma unroll
-            for (int k = 0; k < WPB; k++) t += sacc[k][lane];
-            outv = t;
-        }
-    }
-    if (mine) {
-        if (chunks_per_row == WPB) cr[(int64_t)lane * n1 + prow((r), n1 - 1)] = outv;
-        else atomicAdd(&cr[(int64_t)lane * n1 + prow((r), n1 - 1)], outv);
-    }
-}
-
-// ------------------------------------------------------------------ the last row n in the planes above its lowest bit
-// anchors of its round-A tasks: out[b] = #{q in columns [r_b, n) : prev[q] < r_b}, out[32 + b] = #{rows with last column in
-// [r_b, n) and first column >= r_b} (hyperedge costs), r_b = n with the bits below b cleared.  Entry q lies in a column >= r_b
-// iff q >= pos[r_b].  Then the rows are marked final: the round of ctz(n) skips them.
-__global__ void __launch_bounds__(256) k_last_row_counts(RoundDesc R, const int32_t *__restrict__ pos, const int32_t *__restrict__ prev,
-                                                         const int32_t *__restrict__ lpos, const int32_t *__restrict__ lfirst, int32_t *__restrict__ out,
-                                                         uint8_t *__restrict__ fin)
-{
-    __shared__ int32_t s_acc[64];
-    if (threadIdx.x < 64) s_acc[threadIdx.x] = 0;
-    __syncthreads();
-    const int64_t n = R.n, n1 = n + 1;
-    if (blockIdx.x == 0 && threadIdx.x < (unsigned)R.nlast) fin[(int64_t)R.last_b[threadIdx.x] * n1 + prow(n, n)] = (uint8_t)R.fin_stamp;
-    for (int pass = 0; pass < (lpos ? 2 : 1); pass++) {
-        const int32_t *cp = pass ? lpos : pos, *arr = pass ? lfirst : prev;
-        for (int i = 0; i < R.nlast; i++) {                 // (the ranges are nested; together at most 2 N entries)
-            const int64_t rb = (n >> R.last_b[i]) << R.last_b[i];
-            int32_t c = 0;
-            for (int64_t q = (int64_t)cp[rb] + (int64_t)blockIdx.x * blockDim.x + threadIdx.x, q1 = cp[n]; q < q1; q += (int64_t)gridDim.x * blockDim.x) {
-                int32_t v = arr[q];
-                c += pass ? (v >= rb) : (v < rb);
-            }
-            for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-            if ((threadIdx.x & 63) == 0 && c) atomicAdd(&s_acc[pass * 32 + i], c);
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < 64 && s_acc[threadIdx.x]) {
-        int pass = threadIdx.x >> 5, i = threadIdx.x & 31;
-        if (i < R.nlast) atomicAdd(&out[pass * 32 + R.last_b[i]], s_acc[threadIdx.x]);
-    }
-}
-
-// ------------------------------------------------------------------ task setup
-// element 0 of a task is the candidate p = B (its count = anchor + right part); elements i >= 1 are the
-// left steps p = B - i.  Round A: B = r is virtual (not a candidate), anchor 0.
-__global__ void __launch_bounds__(256) k_setup(RoundDesc R, const int32_t *__restrict__ opt, const int32_t *__restrict__ nnopt,
-                                               int32_t *__restrict__ cr, int zero_cr_only,
-                                               int4 *__restrict__ tdesc, const int32_t *__restrict__ pos32,
-                                               uint8_t *__restrict__ tb, int32_t *__restrict__ len,
-                                               const int32_t *__restrict__ nlopt, int32_t *__restrict__ crl, int32_t *__restrict__ tS0l)
-{
-    int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= R.ntask) return;
-    int64_t r; int b;
-    decode_task(R, t, r, b);
-    int64_t n1 = R.n + 1;
-    if (zero_cr_only) { cr[(int64_t)b * n1 + prow((r), n1 - 1)] = 0; if (crl) crl[(int64_t)b * n1 + prow((r), n1 - 1)] = 0; return; }
-    int64_t B, a, S0, S0l = 0;
-    if (R.isA) {
-        B = r; a = r - ((int64_t)1 << b); S0 = 0;           // (zero_cr_only is the only use of this kernel in round A)
-    } else {
-        int64_t rb = (r >> b) << b;
-        int64_t rL = r - ((int64_t)1 << R.tau), rR = r + ((int64_t)1 << R.tau);
-        B = opt[(int64_t)b * n1 + prow((rL), n1 - 1)];
-        S0 = (int64_t)nnopt[(int64_t)b * n1 + prow((rL), n1 - 1)] + cr[(int64_t)b * n1 + prow((r), n1 - 1)];
-        if (tS0l) S0l = (int64_t)nlopt[(int64_t)b * n1 + prow((rL), n1 - 1)] + crl[(int64_t)b * n1 + prow((r), n1 - 1)];
-        a = (rR - rb) < ((int64_t)1 << b) ? (int64_t)opt[(int64_t)b * n1 + prow((rR <= R.n ? rR : R.n), n1 - 1)] : rb - ((int64_t)1 << b);
-        if (a > B) a = B;          // cannot happen for an inverse-Monge cost; keeps every task well-formed
-    }
-    tdesc[t] = make_int4((int32_t)B, (int32_t)S0, (int32_t)r, pos32[r]);      // one 16-byte record per task
-    tb[t] = (uint8_t)b;
-    len[t] = (int32_t)(1 + (B - a));
-    if (tS0l) tS0l[t] = (int32_t)S0l;
-}
-
-// ------------------------------------------------------------------ wave-level segmented scans (64 lanes)
-template <typename TC> __device__ __forceinline__ void best_clear(Best<TC, false> &b) { b.v = (TC)0; b.p = -1; b.nn = 0; }
-template <typename TC> __device__ __forceinline__ void best_clear(Best<TC, true> &b) { b.v = (TC)0; b.p = -1; b.nn = 0; b.nl = 0; b._pad = 0; }
-template <typename TC> __device__ __forceinline__ int32_t best_nl(const Best<TC, false> &) { return 0; }
-template <typename TC> __device__ __forceinline__ int32_t best_nl(const Best<TC, true> &b) { return b.nl; }
-template <typename TC> __device__ __forceinline__ void best_set_nl(Best<TC, false> &, int32_t) {}
-template <typename TC> __device__ __forceinline__ void best_set_nl(Best<TC, true> &b, int32_t v) { b.nl = v; }
-
-// (member-wise selects on values: returning `cond ? b : a` through references makes the compiler select between the two
-//  ADDRESSES -- one of them often a global-memory record -- and keeps the local operand in private memory: 24-96 B of scratch
-//  per lane and 0.5 GB of HBM writes per launch of the streaming kernel in round 1's profile)
-template <typename TC>
-__device__ __forceinline__ Best<TC, false> best_sel(bool tb, const Best<TC, false> a, const Best<TC, false> b)
-{
-    Best<TC, false> r; r.v = tb ? b.v : a.v; r.p = tb ? b.p : a.p; r.nn = tb ? b.nn : a.nn; return r;
-}
-template <typename TC>
-__device__ __forceinline__ Best<TC, true> best_sel(bool tb, const Best<TC, true> a, const Best<TC, true> b)
-{
-    Best<TC, true> r; r.v = tb ? b.v : a.v; r.p = tb ? b.p : a.p; r.nn = tb ? b.nn : a.nn; r.nl = tb ? b.nl : a.nl; r._pad = 0; return r;
-}
-template <typename TC, bool HYP>
-__device__ __forceinline__ Best<TC, HYP> better(const Best<TC, HYP> a, const Best<TC, HYP> b)   // a is earlier (larger p): wins ties
-{
-    const bool tb = a.p < 0 || (b.p >= 0 && b.v < a.v);
-    return best_sel<TC>(tb, a, b);
-}
-
+// ------------------------------------------------------------------ wave-level segmented scans (64 lanes; the Best helpers: dp_total.hpp)
 // inclusive segmented sum: v = sum from the last head at or before this lane (or lane 0), f = "a head lies in [0, lane]"
 __device__ __forceinline__ void wave_segsum(int32_t &v, int &f, int lane)
 {
@@ -389,27 +85,6 @@ __device__ __forceinline__ void wave_segmin(Best<TC, HYP> &x, int &f, int lane)
         if (HYP) best_set_nl(p, __shfl_up(best_nl(x), o));
         int pf = __shfl_up(f, o);
         if (lane >= o) { if (!f) x = better(p, x); f |= pf; }
-    }
-}
-
-// ------------------------------------------------------------------ tile geometry of the tasks with tiles of their own (see k_own_map)
-__host__ __device__ __forceinline__ int32_t own_ntiles(int blk, int64_t B, int64_t L)
-{
-    return blk ? (int32_t)(B / LT - (B - L + 1) / LT + 1) : (int32_t)((L + LT - 1) / LT);
-}
-// tile kt of a task with head B and L steps: steps 0 .. tl of the tile are the columns pf .. pf - tl (the tile is the task's head
-// tile iff kt == 0: its step 0 is the candidate B itself, no column stepped over)
-__device__ __forceinline__ void own_tile_geo(int blk, int32_t B, int32_t L, int32_t kt, int32_t &pf, int32_t &tl)
-{
-    if (blk) {
-        const int32_t a = B - L + 1;
-        pf = kt == 0 ? B : (B / LT - kt) * LT + (LT - 1);
-        const int32_t c0 = pf - pf % LT;
-        tl = pf - (a > c0 ? a : c0);
-    } else {
-        pf = B - kt * LT;
-        const int32_t rest = L - kt * LT;                // steps of the task from this tile on
-        tl = (rest < LT ? rest : LT) - 1;
     }
 }
 
@@ -1357,368 +1032,6 @@ __global__ void __launch_bounds__(256) k_lpass_own(int isA, const RoundCounts *_
     }
     if (lane < ns) spv[sbase + lane] = s_v[1][lane];
     if (lane == 0) spec[tile] = (uint8_t)ns;
-}
-
-// ------------------------------------------------------------------ gap passes
-// The arg-min staircase of a rectangle jumps: between two neighbouring rows rL < rR of a round the winners B = opt[rL] and
-// a = opt[rR] can lie thousands of columns apart, and the divide and conquer re-scans that gap [a, B] once per level below.
-// In the rounds tau <= gap_tau a task with such a gap instead finishes EVERY row r' of (rL, hi), hi = min(rR, rectangle end,
-// n + 1), in one pass over the gap: each of them has its (rightmost) winner inside [a, B].
-//   nets(p, r') = nets(B, rL) + #{q in cols [rL, r') : prev[q] < B} + #{q in cols [p, B) : next[q] >= r'}
-// and the last term is the same for all these rows except for the entries with rL < next[q] < hi - 1 ("special": counted by
-// some rows only).  k_lpass_own<GAP> streams the gap once with the common threshold and flags the tiles holding specials; here
-// one wave per (task, 64 rows) gives every lane a row and walks the task's tiles in candidate order: a plain tile contributes
-// its winner (the same for all rows: their values differ by a row-only term plus cum(r') = the specials passed so far that
-// the row counts); a flagged tile is re-walked entry by entry with every lane counting for its own row.  Ties: strict <
-// in walking order = the larger p wins, as everywhere.  The rows are marked final (fin): later rounds skip them.
-template <bool GE>
-__device__ __forceinline__ int32_t gap_right_counts(const int32_t *__restrict__ cpos, const int32_t *__restrict__ arr, int32_t rL, int ck, int32_t thr,
-                                                    int32_t n, int lane)
-{
-    // #{entries of columns [rL, r') passing the test}, r' = rL + 1 + 64 ck + lane.  Coalesced: the columns of the earlier row
-    // chunks are summed by the whole wave; the wave's own 64 columns are one contiguous run of entries, flagged 64 at a time,
-    // and every lane counts the flags in front of the end of its column.
-    int32_t cfirst = rL + 64 * ck;
-    if (cfirst > n) cfirst = n;
-    int32_t c = 0;
-    for (int32_t q = cpos[rL] + lane, q1 = cpos[cfirst]; q < q1; q += 64) { int32_t v = arr[q]; c += GE ? (v >= thr) : (v < thr); }
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-    int32_t jn = cfirst + lane + 1, cl = cfirst + 64;
-    if (jn > n) jn = n;
-    if (cl > n) cl = n;
-    const int32_t myend = cpos[jn], e0 = cpos[cfirst], e1 = cpos[cl];
-    int32_t mine = 0;
-    for (int32_t base = e0; base < e1; base += 256) {       // four loads in flight
-        bool fl[4];
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            int32_t q = base + 64 * j + lane;
-            fl[j] = false;
-            if (q < e1) { int32_t v = arr[q]; fl[j] = GE ? (v >= thr) : (v < thr); }
-        }
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            unsigned long long m = __ballot(fl[j]);
-            int32_t w = myend - (base + 64 * j);
-            if (w > 0) mine += __popcll(w >= 64 ? m : (m & ((1ull << w) - 1ull)));
-        }
-    }
-    return c + mine;
-}
-
-template <typename TC, bool HYP>
-struct GapCtx {
-    const Best<TC, HYP> *part, *sub; const int32_t *spv; const uint8_t *spec;
-    const int64_t *tilePS, *tilePS2;
-    const int32_t *pos, *next, *fpos, *flast;
-    const TC *W;
-    int blk;                    // the tile geometry (own_tile_geo)
-};
-
-// the tiles [ka, kz) of a task (first tile k0, head B, L steps, row r) walked for NR x 64 rows of the wave (lane l holds the rows
-// rr[0 .. NR-1], one per 64-row chunk: the tile records are fetched once for all of them): the winners so far (bv, bp, bl, bl2)
-// and the specials the rows count so far (cum, cum2) are carried in and out
-// SLOW = false: the entry-by-entry walk of a tile with more than SMAX specials is compiled out (its column-pointer and cost
-// registers cost the kernels two waves per SIMD, and they wait on memory three quarters of their time): such an item returns false
-// and is redone by the SLOW variant of its kernel.
-template <typename TC, bool HYP, int NR, bool SLOW>
-__device__ __forceinline__ bool gap_walk(const GapCtx<TC, HYP> &C, const DevModel<TC> &M, TC alpha, int64_t ka, int64_t kz, int64_t k0,
-                                         int32_t B, int32_t L, int32_t r, int32_t posr, const int32_t (&rr)[NR], const int32_t (&rcmp)[NR],
-                                         const bool (&valid)[NR], int lane,
-                                         TC (&bv)[NR], int32_t (&bp)[NR], int32_t (&bl)[NR], int32_t (&bl2)[NR], int32_t (&cum)[NR], int32_t (&cum2)[NR])
-{
-    const int64_t ps0 = C.tilePS[k0], ps20 = HYP ? C.tilePS2[k0] : 0;
-    for (int64_t kb = ka; kb < kz; kb += 64) {
-    const int64_t km = kb + lane < kz ? kb + lane : kz - 1;
-    const int32_t m_base = (int32_t)(C.tilePS[km] - ps0), m_base2 = HYP ? (int32_t)(C.tilePS2[km] - ps20) : 0;
-    const int m_ns = C.spec[km];
-    Best<TC, HYP> m_part; best_clear(m_part);
-    if (m_ns == 0) m_part = C.part[km];
-    const int nb = (int)(kz - kb < 64 ? kz - kb : 64);
-    // the segment records of the NEXT tile are fetched while the current tile is walked (the walk is a chain of dependent loads)
-    Best<TC, HYP> nx_c; best_clear(nx_c);
-    int32_t nx_sv = 0;
-    {
-        const int ns0 = rdl(m_ns, 0);
-        if (ns0 > 0 && ns0 <= SMAX) { if (lane <= ns0) nx_c = C.sub[kb * (SMAX + 1) + lane]; if (lane < ns0) nx_sv = C.spv[kb * (SMAX + 1) + lane]; }
-    }
-    for (int i = 0; i < nb; i++) {
-        const int64_t k = kb + i;
-        const int32_t base = rdl(m_base, i), base2 = HYP ? rdl(m_base2, i) : 0;
-        const int ns = rdl(m_ns, i);
-        const Best<TC, HYP> cur_c = nx_c;
-        const int32_t cur_sv = nx_sv;
-        if (i + 1 < nb) {
-            const int ns1 = rdl(m_ns, i + 1);
-            if (ns1 > 0 && ns1 <= SMAX) { if (lane <= ns1) nx_c = C.sub[(k + 1) * (SMAX + 1) + lane]; if (lane < ns1) nx_sv = C.spv[(k + 1) * (SMAX + 1) + lane]; }
-        }
-        if (ns <= SMAX) {
-            // plain tile: one winner; tile with ns specials: ns + 1 segment winners, a special between two segments
-            Best<TC, HYP> c = cur_c;
-            int32_t sv = cur_sv;
-            if (ns == 0) {
-                best_clear(c);
-                c.v = rdl64(m_part.v, i); c.p = rdl(m_part.p, i); c.nn = rdl(m_part.nn, i);
-                if (HYP) best_set_nl(c, rdl(best_nl(m_part), i));
-            }
-            for (int sg = 0; sg <= ns; sg++) {
-                Best<TC, HYP> d = c;
-                if (ns) { d.v = rdl64(c.v, sg); d.p = rdl(c.p, sg); d.nn = rdl(c.nn, sg); if (HYP) best_set_nl(d, rdl(best_nl(c), sg)); }
-                if (d.p >= 0) {
-#pragma unroll
-                    for (int u = 0; u < NR; u++) {
-                        int32_t lc = d.nn + base + cum[u], lc2 = HYP ? best_nl(d) + base2 + cum2[u] : 0;
-                        TC v = cadd(d.v, dm_apply_affine(M, (TC)0, (int64_t)0, (int64_t)0, (int64_t)(base + cum[u]), (int64_t)(base2 + cum2[u])));
-                        if (bp[u] < 0 || v < bv[u]) { bv[u] = v; bp[u] = d.p; bl[u] = lc; bl2[u] = lc2; }
-                    }
-                }
-                if (sg < ns) {                          // the candidates from here on have this special on their right
-                    const int32_t s1 = rdl(sv, sg), val = s1 & 0x7fffffff;
-                    const bool first_list = s1 >= 0;        // (two unconditional adds: an if / else here becomes ONE add through a selected address, i.e. scratch)
-#pragma unroll
-                    for (int u = 0; u < NR; u++) {
-                        cum[u] += (first_list && val >= rcmp[u]);
-                        cum2[u] += (!first_list && valid[u] && val < rr[u]);
-                    }
-                }
-            }
-            continue;
-        }
-        // too many specials: every lane counts for its own rows, entry by entry
-        if (!SLOW) return false;
-        if (SLOW) {
-        const int head = k == k0 ? 1 : 0;
-        int32_t pf, tlk;
-        own_tile_geo(C.blk, B, L, (int32_t)(k - k0), pf, tlk);
-        // C.pos[pf + 1 - j] and C.W[pf - j] of the tile's columns are fetched lane-strided; the entries come through 64-entry
-        // windows (one coalesced load each) and are handed to all lanes one at a time
-#define CP_SEL5(a_, i_) ((i_) < 64 ? a_[0] : (i_) < 128 ? a_[1] : (i_) < 192 ? a_[2] : (i_) < 256 ? a_[3] : a_[4])
-        int32_t pk[5], pk2[5] = {0, 0, 0, 0, 0}; TC wk[4];
-#pragma unroll
-        for (int j = 0; j < 5; j++) {
-            int32_t e = lane + 64 * j;
-            pk[j] = e <= tlk + 1 ? C.pos[pf + 1 - e] : 0;
-            if (HYP) pk2[j] = e <= tlk + 1 ? C.fpos[pf + 1 - e] : 0;
-        }
-#pragma unroll
-        for (int j = 0; j < 4; j++) { int32_t e = lane + 64 * j; wk[j] = e <= tlk ? C.W[pf - e] : (TC)0; }
-        int32_t run[NR], run2[NR];
-#pragma unroll
-        for (int u = 0; u < NR; u++) { run[u] = 0; run2[u] = 0; }
-        int32_t wb = INT32_MAX, reg = 0, wb2 = INT32_MAX, reg2 = 0;
-        for (int32_t e = 0; e <= tlk; e++) {
-            const int32_t p = pf - e, e1 = e + 1;
-            const int32_t en = __shfl(CP_SEL5(pk, e), e & 63), st = __shfl(CP_SEL5(pk, e1), e1 & 63);      // C.pos[p + 1], C.pos[p]
-            if (!(head && e == 0)) {                    // step over column p (the head element steps over nothing)
-                for (int32_t q = en - 1; q >= st; q--) {
-                    if (q < wb || q - wb > 63) { wb = q - 63; reg = wb + lane >= 0 ? C.next[wb + lane] : 0; }
-                    const int32_t x = __shfl(reg, q - wb);           // (every lane takes part: no short-circuit around a shuffle)
-#pragma unroll
-                    for (int u = 0; u < NR; u++) run[u] += (x >= rcmp[u]);
-                }
-                if (HYP) {
-                    const int32_t en2 = __shfl(CP_SEL5(pk2, e), e & 63), st2 = __shfl(CP_SEL5(pk2, e1), e1 & 63);
-                    for (int32_t q = en2 - 1; q >= st2; q--) {
-                        if (q < wb2 || q - wb2 > 63) { wb2 = q - 63; reg2 = wb2 + lane >= 0 ? C.flast[wb2 + lane] : 0; }
-                        const int32_t x = __shfl(reg2, q - wb2);
-#pragma unroll
-                        for (int u = 0; u < NR; u++) run2[u] += (valid[u] && x < rr[u]);
-                    }
-                }
-            }
-            const TC wp = shfl64(e < 64 ? wk[0] : e < 128 ? wk[1] : e < 192 ? wk[2] : wk[3], e & 63);
-#pragma unroll
-            for (int u = 0; u < NR; u++) {
-                int32_t lc = base + cum[u] + run[u], lc2 = base2 + cum2[u] + run2[u];
-                TC v = cadd(wp, dm_apply_affine(M, alpha, (int64_t)(r - p), (int64_t)(posr - st), (int64_t)lc, (int64_t)lc2));      // (the task's row: the rows' values differ by a row-only term)
-                if (bp[u] < 0 || v < bv[u]) { bv[u] = v; bp[u] = p; bl[u] = lc; bl2[u] = lc2; }
-            }
-        }
-#undef CP_SEL5
-        // from here on the rows also count the specials of this tile they passed
-#pragma unroll
-        for (int u = 0; u < NR; u++) {
-            cum[u] += run[u] - (int32_t)(C.tilePS[k + 1] - C.tilePS[k]);
-            if (HYP) cum2[u] += run2[u] - (int32_t)(C.tilePS2[k + 1] - C.tilePS2[k]);
-        }
-        }
-    }
-    }
-    return true;
-}
-
-// rows of the wave, right parts and anchors of a gap task: shared by the kernels below
-struct GapRows { int32_t rL, hi, rr, rcmp; bool valid, none; };
-__device__ __forceinline__ GapRows gap_rows(int tau, int ck, int32_t r, int b, int64_t n, int lane)
-{
-    GapRows g;
-    g.rL = r - (1 << tau);
-    int64_t hi64 = (int64_t)r + ((int64_t)1 << tau), re = ((((int64_t)r >> b) + 1) << b);
-    if (hi64 > re) hi64 = re;
-    if (hi64 > n + 1) hi64 = n + 1;
-    g.hi = (int32_t)hi64;
-    g.rr = g.rL + 1 + 64 * ck + lane;                       // this lane's row
-    g.none = g.rL + 1 + 64 * ck >= g.hi;                    // (wave-uniform: the chunk lies beyond the gap's rows)
-    g.valid = g.rr < g.hi;
-    g.rcmp = g.valid ? g.rr : INT32_MAX;                    // an invalid lane counts nothing
-    return g;
-}
-
-template <typename TC, bool HYP>
-struct GapSegRec { TC v; int32_t p, l, l2, cum, cum2, _pad; };
-
-// NR: 64-row chunks per wave (a lane holds one row of each): the task's records -- descriptor, tile winners, segment lists -- are
-// fetched once for NR x 64 rows.  The kernel waits on memory three quarters of its time at four waves per SIMD (profiles/
-// r03_pmc_gap_finish.txt), i.e. it is bound by the number of (task, rows) items times the dependent loads of one item.
-template <typename TC, bool HYP, int NR, bool SLOW>
-__global__ void __launch_bounds__(256, 4) k_gap_finish(int tau, int nchunk, RoundCounts *__restrict__ rc, int64_t n,
-                                                    const int64_t *__restrict__ toffs, GapCtx<TC, HYP> C,
-                                                    const int4 *__restrict__ tdesc, const uint8_t *__restrict__ tb, const int32_t *__restrict__ rlen,
-                                                    const int32_t *__restrict__ prev, const int32_t *__restrict__ lpos, const int32_t *__restrict__ lfirst,
-                                                    DevModel<TC> M, TC alpha,
-                                                    int32_t *__restrict__ opt, int32_t *__restrict__ nnopt, int32_t *__restrict__ nlopt, uint8_t *__restrict__ fin,
-                                                    int2 *__restrict__ glist, int2 *__restrict__ gslot, int fin_stamp, int32_t *__restrict__ slow)
-{
-    // SLOW: the items the fast variant listed in `slow` (rc->n_gslow of them)
-    const int lane = threadIdx.x & 63;
-    const int nitem = (nchunk + NR - 1) / NR;
-    const int64_t nwork = SLOW ? (int64_t)rc->n_gslow : (int64_t)rc->nown * nitem, n1 = n + 1;
-    for (int64_t wi = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); wi < nwork; wi += (int64_t)gridDim.x * 4) {
-        const int64_t w = SLOW ? (int64_t)slow[wi] : wi;
-        const int64_t t = w / nitem;
-        const int ck0 = (int)(w - t * nitem) * NR;
-        const int64_t k0 = toffs[t], k1 = toffs[t + 1];
-        if (k1 - k0 > GAPSEG) {                             // (wave-uniform) a long task: listed for k_gap_seg / k_gap_merge
-            if (!SLOW && ck0 == 0 && lane == 0) {
-                int nseg = (int)((k1 - k0 + GAPSEG - 1) / GAPSEG);
-                int idx = atomicAdd(&rc->n_glong, 1), slot0 = atomicAdd(&rc->n_gslots, nseg);
-                glist[idx] = make_int2((int)t, slot0);
-                for (int j = 0; j < nseg; j++) gslot[slot0 + j] = make_int2((int)t, j);       // slot -> (task, segment) for k_gap_seg
-            }
-            continue;
-        }
-        const int4 td = tdesc[t];                           // {B, anchor + right part of the task's own row, row r, pos[r]}
-        const int b = tb[t];
-        const int32_t B = td.x, r = td.z, posr = td.w, L = rlen[t];
-        GapRows g[NR];
-        int32_t rr[NR], rcmp[NR]; bool valid[NR];
-#pragma unroll
-        for (int u = 0; u < NR; u++) { g[u] = gap_rows(tau, ck0 + u, r, b, n, lane); rr[u] = g[u].rr; rcmp[u] = g[u].rcmp; valid[u] = g[u].valid; }
-        if (g[0].none) continue;
-        // right parts of the rows and the anchor (counts at (B, rL))
-        int32_t Rr[NR], Rr2[NR];
-#pragma unroll
-        for (int u = 0; u < NR; u++) {
-            Rr[u] = 0; Rr2[u] = 0;
-            if (u == 0 || !g[u].none) {                     // (wave-uniform)
-                Rr[u] = gap_right_counts<false>(C.pos, prev, g[0].rL, ck0 + u, B, (int32_t)n, lane);
-                if (HYP) Rr2[u] = gap_right_counts<true>(lpos, lfirst, g[0].rL, ck0 + u, B, (int32_t)n, lane);
-            }
-        }
-        const int64_t rwL = (int64_t)b * n1 + prow(((int64_t)g[0].rL), n1 - 1);
-        const int32_t anchor = nnopt[rwL], anchor2 = HYP ? nlopt[rwL] : 0;
-        TC bv[NR]; int32_t bp[NR], bl[NR], bl2[NR], cum[NR], cum2[NR];
-#pragma unroll
-        for (int u = 0; u < NR; u++) { bv[u] = (TC)0; bp[u] = -1; bl[u] = 0; bl2[u] = 0; cum[u] = 0; cum2[u] = 0; }
-        if (!gap_walk<TC, HYP, NR, SLOW>(C, M, alpha, k0, k1, k0, B, L, r, posr, rr, rcmp, valid, lane, bv, bp, bl, bl2, cum, cum2)) {
-            if (lane == 0) slow[atomicAdd(&rc->n_gslow, 1)] = (int32_t)w;
-            continue;
-        }
-#pragma unroll
-        for (int u = 0; u < NR; u++) {
-            if (valid[u]) {
-                int64_t rw = (int64_t)b * n1 + prow(((int64_t)rr[u]), n1 - 1);
-                opt[rw] = bp[u]; nnopt[rw] = anchor + Rr[u] + bl[u];
-                if (HYP) nlopt[rw] = anchor2 + Rr2[u] + bl2[u];
-                fin[rw] = (uint8_t)fin_stamp;
-            }
-        }
-    }
-}
-
-// long gap tasks, phase 1: one wave per (segment slot = GAPSEG tiles of a listed task, 64 rows) walks its tiles as if nothing lay
-// in front of them
-template <typename TC, bool HYP, bool SLOW>
-__global__ void __launch_bounds__(256) k_gap_seg(int tau, int nchunk, RoundCounts *__restrict__ rc, int64_t n, const int64_t *__restrict__ toffs,
-                                                 GapCtx<TC, HYP> C, const int4 *__restrict__ tdesc, const uint8_t *__restrict__ tb,
-                                                 const int32_t *__restrict__ rlen, DevModel<TC> M, TC alpha, const int2 *__restrict__ gslot,
-                                                 GapSegRec<TC, HYP> *__restrict__ gseg, int32_t *__restrict__ slow)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t nwork = SLOW ? (int64_t)rc->n_sslow : (int64_t)rc->n_gslots * nchunk;
-    for (int64_t wi = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); wi < nwork; wi += (int64_t)gridDim.x * 4) {
-        const int64_t w = SLOW ? (int64_t)slow[wi] : wi;
-        const int64_t slot = w / nchunk;
-        const int ck = (int)(w - slot * nchunk);
-        const int2 se = gslot[slot];
-        const int64_t t = se.x, k0 = toffs[t], k1 = toffs[t + 1];
-        const int sg = se.y;
-        const int4 td = tdesc[t];
-        const GapRows g = gap_rows(tau, ck, td.z, tb[t], n, lane);
-        if (g.none) continue;
-        TC bv[1] = {(TC)0}; int32_t bp[1] = {-1}, bl[1] = {0}, bl2[1] = {0}, cum[1] = {0}, cum2[1] = {0};
-        const int32_t rr1[1] = {g.rr}, rcmp1[1] = {g.rcmp}; const bool valid1[1] = {g.valid};
-        const int64_t ka = k0 + (int64_t)sg * GAPSEG, kz = ka + GAPSEG < k1 ? ka + GAPSEG : k1;
-        if (!gap_walk<TC, HYP, 1, SLOW>(C, M, alpha, ka, kz, k0, td.x, rlen[t], td.z, td.w, rr1, rcmp1, valid1, lane, bv, bp, bl, bl2, cum, cum2)) {
-            if (lane == 0) slow[atomicAdd(&rc->n_sslow, 1)] = (int32_t)w;
-            continue;
-        }
-        GapSegRec<TC, HYP> rec; rec.v = bv[0]; rec.p = bp[0]; rec.l = bl[0]; rec.l2 = bl2[0]; rec.cum = cum[0]; rec.cum2 = cum2[0]; rec._pad = 0;
-        gseg[(slot * nchunk + ck) * 64 + lane] = rec;
-    }
-}
-
-// phase 2: one wave per (listed task, 64 rows) merges the segment winners in walking order, adding the specials of the
-// segments in front
-template <typename TC, bool HYP>
-__global__ void __launch_bounds__(256) k_gap_merge(int tau, int nchunk, const RoundCounts *__restrict__ rc, int64_t n, const int64_t *__restrict__ toffs,
-                                                   const int4 *__restrict__ tdesc, const uint8_t *__restrict__ tb,
-                                                   const int32_t *__restrict__ pos, const int32_t *__restrict__ prev, const int32_t *__restrict__ lpos,
-                                                   const int32_t *__restrict__ lfirst, DevModel<TC> M, const int2 *__restrict__ glist,
-                                                   const GapSegRec<TC, HYP> *__restrict__ gseg,
-                                                   int32_t *__restrict__ opt, int32_t *__restrict__ nnopt, int32_t *__restrict__ nlopt, uint8_t *__restrict__ fin, int fin_stamp)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t nwork = (int64_t)rc->n_glong * nchunk, n1 = n + 1;
-    for (int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); w < nwork; w += (int64_t)gridDim.x * 4) {
-        const int i = (int)(w / nchunk), ck = (int)(w - (int64_t)i * nchunk);
-        const int2 le = glist[i];
-        const int64_t t = le.x, k0 = toffs[t], k1 = toffs[t + 1];
-        const int nseg = (int)((k1 - k0 + GAPSEG - 1) / GAPSEG);
-        const int4 td = tdesc[t];
-        const int b = tb[t];
-        const GapRows g = gap_rows(tau, ck, td.z, b, n, lane);
-        if (g.none) continue;
-        const int32_t Rr = gap_right_counts<false>(pos, prev, g.rL, ck, td.x, (int32_t)n, lane);
-        const int32_t Rr2 = HYP ? gap_right_counts<true>(lpos, lfirst, g.rL, ck, td.x, (int32_t)n, lane) : 0;
-        const int64_t rwL = (int64_t)b * n1 + prow(((int64_t)g.rL), n1 - 1);
-        const int32_t anchor = nnopt[rwL], anchor2 = HYP ? nlopt[rwL] : 0;
-        TC bv = (TC)0; int32_t bp = -1, bl = 0, bl2 = 0, cum = 0, cum2 = 0;
-        // (the task over the top rectangle's whole block has thousands of segments: eight records per lane in flight -- the running
-        //  counts make the merge sequential, the loads need not be)
-        for (int s0 = 0; s0 < nseg; s0 += 8) {
-            GapSegRec<TC, HYP> rr[8];
-#pragma unroll
-            for (int u = 0; u < 8; u++)
-                if (s0 + u < nseg) rr[u] = gseg[((int64_t)(le.y + s0 + u) * nchunk + ck) * 64 + lane];
-#pragma unroll
-            for (int u = 0; u < 8; u++) {
-                if (s0 + u >= nseg) break;
-                const GapSegRec<TC, HYP> rec = rr[u];
-                if (rec.p >= 0) {
-                    TC v = cadd(rec.v, dm_apply_affine(M, (TC)0, (int64_t)0, (int64_t)0, (int64_t)cum, (int64_t)cum2));
-                    if (bp < 0 || v < bv) { bv = v; bp = rec.p; bl = rec.l + cum; bl2 = rec.l2 + cum2; }
-                }
-                cum += rec.cum; cum2 += rec.cum2;
-            }
-        }
-        if (g.valid) {
-            int64_t rw = (int64_t)b * n1 + prow(((int64_t)g.rr), n1 - 1);
-            opt[rw] = bp; nnopt[rw] = anchor + Rr + bl;
-            if (HYP) nlopt[rw] = anchor2 + Rr2 + bl2;
-            fin[rw] = (uint8_t)fin_stamp;
-        }
-    }
 }
 
 // Merging the tiles of a task, one launch (k_fix_own), the role of a block chosen by its index.  The counts made before a tile
@@ -3075,45 +2388,6 @@ static void make_round(RoundDesc &R, bool isA, int tau, int nbits, int64_t n, in
     R.ntask = acc;
 }
 
-// right part of one round for one counter: rows with ctz == tau stream their 2^tau columns once for all bit planes
-static void launch_rpass(hipStream_t s, const RoundDesc &R, int nbits, int64_t n, int64_t rlo, int64_t rhi, const int64_t *cpos,
-                         const int32_t *link, int ge, const int32_t *opt, int32_t *cr, double mean_deg)
-{
-    const int allp = R.G.win;
-    int tau = R.tau;
-    int64_t rmin = rlo - ((int64_t)1 << tau), rmax = rhi + ((int64_t)1 << tau);
-    if (rmax > n) rmax = n;
-    if (rmin < 0) rmin = 0;
-    // rows (2u+1)<<tau in [rmin, rmax]
-    int64_t u0 = rmin <= 0 ? 0 : (((rmin - 1) >> tau) + 1) >> 1;       // #rows < rmin
-    int64_t u1 = ((rmax >> tau) + 1) >> 1;                              // #rows <= rmax
-    int64_t nrows = u1 - u0;
-    if (nrows <= 0) return;
-    if (tau <= g_opt_rpass_small_tau) {
-        // lane-private share of a row: rpass_cap per cent of the mean number of entries of 2^tau columns, in steps of 16
-        int64_t cap = (int64_t)(0.01 * (double)g_opt_rpass_cap * mean_deg * (double)((int64_t)1 << tau));
-        cap = std::max<int64_t>(16, std::min<int64_t>((cap + 15) / 16 * 16, 1 << 20));
-#define RPS(GE, NB) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rpass_small<GE, NB>), dim3((unsigned)cdiv(nrows, 256)), dim3(256), 0, s, tau, nbits, n, u0, nrows, cpos, link, \
-                                       opt, cr, allp, (int)cap)
-        // (up to 24 bit planes -- n < 2^24 -- the per-plane registers of the kernels are a quarter fewer: one more wave per SIMD)
-        if (nbits <= 24) { if (ge) RPS(true, 24); else RPS(false, 24); }
-        else             { if (ge) RPS(true, NBMAX); else RPS(false, NBMAX); }
-#undef RPS
-    } else {
-        int ch_cols = (int)g_opt_rpass_ch;          // columns per wave (cp_set_option("rpass_ch"))
-        int64_t cpr = ((int64_t)1 << tau) > ch_cols ? (((int64_t)1 << tau) / ch_cols) : 1;
-        if (cpr == 1) ch_cols = 1 << tau;
-        int64_t waves = nrows * cpr;
-#define RPW(GE, WPB) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rpass_wave<GE, WPB>), dim3((unsigned)cdiv(waves, WPB)), dim3(64 * WPB), 0, s, tau, nbits, n, u0, \
-                                        nrows, (int)cpr, ch_cols, cpos, link, opt, cr, allp)
-        // the chunks of a row that share a workgroup add up in LDS before the row's counters see them
-        if (cpr % 16 == 0)     { if (ge) RPW(true, 16); else RPW(false, 16); }
-        else if (cpr % 4 == 0) { if (ge) RPW(true, 4);  else RPW(false, 4); }
-        else                   { if (ge) RPW(true, 1);  else RPW(false, 1); }
-#undef RPW
-    }
-}
-
 // Builds a cached round-A table: the counts of `levels` levels of rows_of(b) rows each (they depend on the pattern only -- once per
 // partition; the table of the mirrored heads of the windowed geometry, mir_w > 0, also on the window width: once per (pattern, w),
 // after win_build, whose anchors `anch` / `anch2` its counts carry).  Fills the cache's table, counts (c2: second count) and
@@ -3226,34 +2500,6 @@ static void win_build(cp_csr_s *A, LayerWork<TC> &Wk)
     Wk.win.built = true; Wk.win.w = w;
 }
 
-// the gap round's finishing kernels: fast variants first, then the SLOW ones over what they listed
-template <typename TC, bool HYP>
-static void launch_gap(hipStream_t s, cp_csr_s *A, LayerWork<TC> &Wk, int tau, int nchunk, int gnr, RoundCounts *rc, int64_t n, const TC *W,
-                       const DevModel<TC> &M, TC alpha, unsigned gg, unsigned gs_grid, unsigned gm, unsigned gslow_grid, int blk)
-{
-    GapCtx<TC, HYP> C{recs<HYP>(Wk.ow.o_part), recs<HYP>(Wk.ow.o_sub), Wk.ow.o_spv.p, Wk.ow.o_spec.p, Wk.ow.o_tilePS.p, if_hyp<HYP>(Wk.ow.o_tilePS2.p), A->pos32.p, A->next.p,
-                      if_hyp<HYP>(A->fpos32.p), if_hyp<HYP>(A->flast.p), W, blk};
-    auto *gs = reinterpret_cast<GapSegRec<TC, HYP> *>(Wk.gp.g_seg.p);      // (sized for the larger record, like the Best buffers)
-    const int32_t *lp = if_hyp<HYP>(A->lpos32.p), *lf = if_hyp<HYP>(A->lfirst.p);
-    int32_t *nl = if_hyp<HYP>(Wk.pl.nlopt.p);
-#define GF_ARGS tau, nchunk, rc, n, Wk.ow.o_toffs.p, C, Wk.ow.o_tdesc.p, Wk.ow.o_tb.p, Wk.ow.o_rlen.p, A->prev.p, lp, lf, M, alpha, Wk.pl.opt.p, Wk.pl.nnopt.p, nl, Wk.pl.fin.p, \
-                Wk.gp.g_list.p, Wk.gp.g_slot.p, Wk.pl.fin_stamp, Wk.gp.g_slow.p
-    if (gnr == 2) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gap_finish<TC, HYP, 2, false>), dim3(gg), dim3(256), 0, s, GF_ARGS);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gap_finish<TC, HYP, 2, true>), dim3(gslow_grid), dim3(256), 0, s, GF_ARGS);
-    } else {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gap_finish<TC, HYP, 1, false>), dim3(gg), dim3(256), 0, s, GF_ARGS);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gap_finish<TC, HYP, 1, true>), dim3(gslow_grid), dim3(256), 0, s, GF_ARGS);
-    }
-#undef GF_ARGS
-#define GS_ARGS tau, nchunk, rc, n, Wk.ow.o_toffs.p, C, Wk.ow.o_tdesc.p, Wk.ow.o_tb.p, Wk.ow.o_rlen.p, M, alpha, Wk.gp.g_slot.p, gs, Wk.gp.g_sslow.p
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gap_seg<TC, HYP, false>), dim3(gs_grid), dim3(256), 0, s, GS_ARGS);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gap_seg<TC, HYP, true>), dim3(gslow_grid), dim3(256), 0, s, GS_ARGS);
-#undef GS_ARGS
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_gap_merge<TC, HYP>), dim3(gm), dim3(256), 0, s, tau, nchunk, rc, n, Wk.ow.o_toffs.p, Wk.ow.o_tdesc.p, Wk.ow.o_tb.p, A->pos32.p, A->prev.p,
-                       lp, lf, M, Wk.gp.g_list.p, gs, Wk.pl.opt.p, Wk.pl.nnopt.p, nl, Wk.pl.fin.p, Wk.pl.fin_stamp);
-}
-
 constexpr int64_t LB_MAX = 1 << 20;      // largest scan (elements) done in a single launch
 
 // Round A from a cache with the table T (the cache's own, or a copy cut to the levels and tiles a windowed layer needs): the
@@ -3351,32 +2597,6 @@ static void poison_fill(hipStream_t s, std::initializer_list<std::pair<void *, s
 
 // ------------------------------------------------------------------ the stages of a round, each as the host function run_layer calls
 // A stage function takes the layer's context, the work object, the round and its counts.
-// The right pass of a tau round, both counters.  (Clearing the counters the chunks of a row add into is the one use the driver
-// still has for k_setup.)
-template <typename TC, bool HYP>
-static void right_pass(const LayerCtx<TC> &C, LayerWork<TC> &Wk, const RoundDesc &R)
-{
-    hipStream_t s = C.s;
-    cp_csr_s *A = C.A;
-    int64_t cols = (((C.n >> R.tau) + 1) >> 1) << R.tau;
-    ProfScope ps(PROF_RPASS, s, 4.0 * (C.avg_deg + C.self_deg) * (double)cols + 8.0 * (double)R.ntask);
-    if (((int64_t)1 << R.tau) > g_opt_rpass_ch)   // several chunks per row accumulate with atomics: clear first
-        hipLaunchKernelGGL(k_setup, dim3((unsigned)cdiv(R.ntask, 256)), dim3(256), 0, s, R, Wk.pl.opt.p, Wk.pl.nnopt.p, Wk.pl.cr.p, 1,
-                           Wk.tk.tdesc.p, A->pos32.p, Wk.tk.tb.p, Wk.tk.len.p, (const int32_t *)nullptr, if_hyp<HYP>(Wk.pl.crl.p), (int32_t *)nullptr);
-    launch_rpass(s, R, C.nbits, C.n, C.rlo, C.rhi, A->pos.p, A->prev.p, 0, Wk.pl.opt.p, Wk.pl.cr.p, C.avg_deg);                   // prev[q] < B
-    if (HYP) launch_rpass(s, R, C.nbits, C.n, C.rlo, C.rhi, A->lpos.p, A->lfirst.p, 1, Wk.pl.opt.p, Wk.pl.crl.p, C.self_deg);      // rows ending in the column with first >= B
-}
-
-// round A: the anchors of the last row's tasks in the planes above its lowest bit
-template <typename TC, bool HYP>
-static void last_row_counts(const LayerCtx<TC> &C, LayerWork<TC> &Wk, const RoundDesc &R)
-{
-    cp_csr_s *A = C.A;
-    CP_HIP(hipMemsetAsync(Wk.pl.last_s0.p, 0, Wk.pl.last_s0.bytes(), C.s));
-    hipLaunchKernelGGL(k_last_row_counts, dim3(1024), dim3(256), 0, C.s, R, A->pos32.p, A->prev.p, if_hyp<HYP>(A->lpos32.p), if_hyp<HYP>(A->lfirst.p),
-                       Wk.pl.last_s0.p, Wk.pl.fin.p);
-}
-
 // Set-up of a round: one lane per task finishes the short ones and lists the others
 template <typename TC, bool HYP>
 static void setup_tasks(const LayerCtx<TC> &C, LayerWork<TC> &Wk, const RoundDesc &R, RoundCounts *rc, int32_t own_min)
@@ -3470,37 +2690,6 @@ static void own_merge(const LayerCtx<TC> &C, LayerWork<TC> &Wk, RoundCounts *rc,
     launch_fix_own<TC, HYP>(C.s, rc, Wk.ow.o_toffs.p, recs<HYP>(Wk.ow.o_part), Wk.ow.o_tdesc.p, Wk.ow.o_tb.p, if_hyp<HYP>(Wk.ow.o_tS0l.p), Wk.ow.o_tileS.p,
                             if_hyp<HYP>(Wk.ow.o_tileS2.p), C.M, Wk.pl.opt.p, Wk.pl.nnopt.p, if_hyp<HYP>(Wk.pl.nlopt.p), C.n, Wk.ow.o_items.p, Wk.ow.o_item_of.p, Wk.ow.o_trec.p,
                             Wk.ow.o_tick.p, C.spec ? grow_pred(P.NT) : P.NT, C.spec ? grow_pred(P.nown) : P.nown);
-}
-
-// The tail of the own-tile chain in a gap round: the tiles' prefix, then every row of the gaps gets its winner
-template <typename TC, bool HYP>
-static void gap_finish(const LayerCtx<TC> &C, LayerWork<TC> &Wk, const RoundDesc &R, RoundCounts *rc, const RoundCounts &P)
-{
-    hipStream_t s = C.s;
-    const int64_t gown = C.spec ? grow_pred(P.nown) : P.nown;
-    {
-        // the gap kernels look a tile's prefix up at random: a device-wide scan of the tile counts.  (The other rounds need
-        // sums inside one task only: k_fix_own makes them from o_tileS.)
-        ProfScope ps(PROF_CARRY, s, 12.0 * (double)P.NT);
-        const int32_t *ntp = reinterpret_cast<const int32_t *>(&rc->NT);       // (NT < 2^31: the low word)
-        exclusive_scan_i32_lb(Wk.ow.o_tileS.p, Wk.ow.o_tilePS.p, ntp, (int64_t)Wk.ow.o_tileS.n, nullptr, Wk.sc.scanws, s);
-        if (HYP) exclusive_scan_i32_lb(Wk.ow.o_tileS2.p, Wk.ow.o_tilePS2.p, ntp, (int64_t)Wk.ow.o_tileS.n, nullptr, Wk.sc.scanws, s);
-    }
-    // every row of the gaps gets its winner: one wave per (task, 64 rows); tasks of more than GAPSEG tiles in two steps
-    ProfScope ps(PROF_GAP, s, 24.0 * (double)P.NT);
-    const int nchunk = (int)std::max<int64_t>(1, ((int64_t)2 << R.tau) / 64);
-    const size_t ncap = Wk.ow.o_rec.n / GAPSEG + 2;
-    Wk.gp.g_list.ensure(ncap); Wk.gp.g_slot.ensure(2 * ncap);
-    Wk.gp.g_seg.ensure((2 * ncap) * (size_t)nchunk * 64 * sizeof(GapSegRec<TC, true>));
-    // items that meet a tile with more than SMAX specials are listed by the fast kernels and redone by the SLOW ones
-    Wk.gp.g_slow.ensure((size_t)gown * (size_t)nchunk + 64); Wk.gp.g_sslow.ensure((2 * ncap) * (size_t)nchunk + 64);
-    CP_REQUIRE((int64_t)gown * nchunk < INT32_MAX && (int64_t)(2 * ncap) * nchunk < INT32_MAX, CP_EINTERNAL, "gap work index beyond 32 bits");
-    const int gnr = (g_opt_gap_nr >= 2 && nchunk >= 2) ? 2 : 1;       // 64-row chunks per wave of k_gap_finish
-    unsigned gg = (unsigned)std::min<int64_t>(cdiv(gown * cdiv((int64_t)nchunk, gnr), 4), 16384);
-    unsigned gs_grid = (unsigned)std::min<int64_t>(cdiv((int64_t)(2 * ncap) * nchunk, 4), 8192);
-    unsigned gm = (unsigned)std::min<int64_t>(cdiv((int64_t)ncap * nchunk, 4), 4096);
-    const unsigned gslow_grid = 2048;                               // (grid-stride over the device-side counts n_gslow / n_sslow: usually none)
-    launch_gap<TC, HYP>(s, C.A, Wk, R.tau, nchunk, gnr, rc, C.n, C.W, C.M, C.alpha, gg, gs_grid, gm, gslow_grid, C.oblk);
 }
 
 // ------------------------------------------------------------------ host side: the flattened chain of a round (the tasks' number: rc->nlong)

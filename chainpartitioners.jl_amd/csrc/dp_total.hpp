@@ -1,7 +1,7 @@
-// dp_total.hpp -- what the units of the total-cost DP layer share (dp_total.hip, dp_total_leaf.hip; nobody else includes it): the
-// constants, the device helpers and kernel-argument records used by kernels of both units, the work object of a handle
-// (LayerWork, in groups by owner), the layer context (LayerCtx) and the stage functions one unit offers the other.  A device
-// helper used by one unit stays in that unit.  No macros here.  The scheme: see dp_total.hip.
+// dp_total.hpp -- what the units of the total-cost DP layer share (dp_total.hip, dp_total_rpass.hip, dp_total_gap.hip,
+// dp_total_leaf.hip; nobody else includes it): the constants, the device helpers and kernel-argument records used by kernels of more
+// than one unit, the work object of a handle (LayerWork, in groups by owner), the layer context (LayerCtx) and the stage functions
+// the units offer the driver.  A device helper used by one unit stays in that unit.  No macros here.  The scheme: see dp_total.hip.
 #pragma once
 #include "csr.hpp"
 #include "model.hpp"
@@ -83,7 +83,50 @@ struct RoundCounts {
     int32_t n_trips, n_edge;          // what the merge met (cp_get_stat, tests): tasks of more than one trip (folded by k_fix_own); bit 0 / 1 / 2: a task of 1 / FIX_SERIAL / FIX_SERIAL + 1 tiles
 };
 
-// the record of a candidate: value, column, counts (helpers and scans: dp_total.hip)
+// The tasks of a round, by value to every kernel that decodes them (make_round: dp_total.hip)
+struct RoundDesc {
+    int32_t isA, tau, nbits, nextra;
+    Geo G;                      // G.win: nbits = s + 1 planes, every row takes part in each of them
+    int64_t aoff[32];           // windowed round A: anchors of the mirrored head tasks of plane b start at aoff[b] (index r >> (b+1))
+    int64_t n, ntask;
+    int64_t tbase[36];          // tau rounds: tasks of bit plane b occupy [tbase[b], tbase[b+1])
+    int64_t tskip[36];          // ... and start at linear index tskip[b] of that plane (row-tiled runs skip rows left of the tile)
+    int64_t a_r0, a_nmain;      // round A: rows a_r0 .. a_r0 + a_nmain - 1, then the `extra` rows (ancestors outside the tile)
+    int64_t extra[64];
+    // round A also takes the LAST row n in every bit plane above its lowest one (tasks after the extra rows): no row lies to
+    // its right, so nothing bounds the rows next to it from the left; with opt[b][n] known first, they start there instead of
+    // at the block start -- which every round would otherwise re-scan (n is not a power of two: ~n steps per round)
+    int32_t nlast, last_b[31];
+    int32_t skip_std, skip_mir; // windowed round A: the standard / mirrored heads (bit b of the row set / clear, b < s) come from the cached counts
+    int32_t fin_stamp;          // a cell of the `fin` plane is set iff it holds this layer's stamp (1 .. 255: the plane is cleared every 255 layers, not every layer)
+};
+
+__device__ __forceinline__ void decode_task(const RoundDesc &R, int64_t t, int64_t &r, int &b)
+{
+    if (R.G.win) {
+        // plane-major.  Round A: plane b <= s holds the rows that are multiples of 2^b (the heads of its rectangles);
+        // round tau: every plane b in (tau, s] holds all rows with ctz == tau
+        int bb = R.isA ? 0 : R.tau + 1;
+        while (t >= R.tbase[bb + 1]) bb++;
+        const int64_t l = t - R.tbase[bb] + R.tskip[bb];
+        r = R.isA ? ((l + 1) << bb) : (((l << 1) | 1) << R.tau);
+        b = bb;
+        return;
+    }
+    if (R.isA) {
+        if (t >= R.a_nmain + R.nextra) { r = R.n; b = R.last_b[t - R.a_nmain - R.nextra]; return; }
+        r = t < R.a_nmain ? R.a_r0 + t : R.extra[t - R.a_nmain]; b = __ffsll((long long)r) - 1; return;
+    }
+    int bb = R.tau + 1;
+    while (t >= R.tbase[bb + 1]) bb++;
+    int64_t l = t - R.tbase[bb] + R.tskip[bb];
+    int sh = bb - R.tau - 1;
+    int64_t base = l >> sh, v = l & (((int64_t)1 << sh) - 1);
+    r = (base << (bb + 1)) | ((int64_t)1 << bb) | (((v << 1) | 1) << R.tau);
+    b = bb;
+}
+
+// the record of a candidate: value, column, counts (helpers: below, behind the shuffles; scans: dp_total.hip)
 template <typename TC, bool HYP> struct Best;
 template <typename TC> struct Best<TC, false> { TC v; int32_t p; int32_t nn; };                         // 16 bytes
 template <typename TC> struct Best<TC, true> { TC v; int32_t p; int32_t nn; int32_t nl; int32_t _pad; };
@@ -109,6 +152,54 @@ __device__ __forceinline__ int64_t rdl64(int64_t v, int src)
     return ((int64_t)__builtin_amdgcn_readlane((int)(v >> 32), src) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(v & 0xffffffffll), src);
 }
 __device__ __forceinline__ double rdl64(double v, int src) { return __longlong_as_double((long long)rdl64((int64_t)__double_as_longlong(v), src)); }
+
+template <typename TC> __device__ __forceinline__ void best_clear(Best<TC, false> &b) { b.v = (TC)0; b.p = -1; b.nn = 0; }
+template <typename TC> __device__ __forceinline__ void best_clear(Best<TC, true> &b) { b.v = (TC)0; b.p = -1; b.nn = 0; b.nl = 0; b._pad = 0; }
+template <typename TC> __device__ __forceinline__ int32_t best_nl(const Best<TC, false> &) { return 0; }
+template <typename TC> __device__ __forceinline__ int32_t best_nl(const Best<TC, true> &b) { return b.nl; }
+template <typename TC> __device__ __forceinline__ void best_set_nl(Best<TC, false> &, int32_t) {}
+template <typename TC> __device__ __forceinline__ void best_set_nl(Best<TC, true> &b, int32_t v) { b.nl = v; }
+
+// (member-wise selects on values: returning `cond ? b : a` through references makes the compiler select between the two
+//  ADDRESSES -- one of them often a global-memory record -- and keeps the local operand in private memory: 24-96 B of scratch
+//  per lane and 0.5 GB of HBM writes per launch of the streaming kernel in round 1's profile)
+template <typename TC>
+__device__ __forceinline__ Best<TC, false> best_sel(bool tb, const Best<TC, false> a, const Best<TC, false> b)
+{
+    Best<TC, false> r; r.v = tb ? b.v : a.v; r.p = tb ? b.p : a.p; r.nn = tb ? b.nn : a.nn; return r;
+}
+template <typename TC>
+__device__ __forceinline__ Best<TC, true> best_sel(bool tb, const Best<TC, true> a, const Best<TC, true> b)
+{
+    Best<TC, true> r; r.v = tb ? b.v : a.v; r.p = tb ? b.p : a.p; r.nn = tb ? b.nn : a.nn; r.nl = tb ? b.nl : a.nl; r._pad = 0; return r;
+}
+template <typename TC, bool HYP>
+__device__ __forceinline__ Best<TC, HYP> better(const Best<TC, HYP> a, const Best<TC, HYP> b)   // a is earlier (larger p): wins ties
+{
+    const bool tb = a.p < 0 || (b.p >= 0 && b.v < a.v);
+    return best_sel<TC>(tb, a, b);
+}
+
+// ------------------------------------------------------------------ tile geometry of the tasks with tiles of their own (see k_own_map)
+__host__ __device__ __forceinline__ int32_t own_ntiles(int blk, int64_t B, int64_t L)
+{
+    return blk ? (int32_t)(B / LT - (B - L + 1) / LT + 1) : (int32_t)((L + LT - 1) / LT);
+}
+// tile kt of a task with head B and L steps: steps 0 .. tl of the tile are the columns pf .. pf - tl (the tile is the task's head
+// tile iff kt == 0: its step 0 is the candidate B itself, no column stepped over)
+__device__ __forceinline__ void own_tile_geo(int blk, int32_t B, int32_t L, int32_t kt, int32_t &pf, int32_t &tl)
+{
+    if (blk) {
+        const int32_t a = B - L + 1;
+        pf = kt == 0 ? B : (B / LT - kt) * LT + (LT - 1);
+        const int32_t c0 = pf - pf % LT;
+        tl = pf - (a > c0 ? a : c0);
+    } else {
+        pf = B - kt * LT;
+        const int32_t rest = L - kt * LT;                // steps of the task from this tile on
+        tl = (rest < LT ? rest : LT) - 1;
+    }
+}
 
 // ------------------------------------------------------------------ a cached round-A table (layout: dp_total.hip, round A from cached counts)
 struct RATab { int32_t nbits, _pad; int64_t n; int64_t tbase[33]; int64_t rbase[33]; int64_t mir_w; int64_t aoff[33]; int64_t tlo[33], thi[33]; };
@@ -312,8 +403,14 @@ template <bool HYP, typename TC> inline Best<TC, HYP> *recs(const DBuf<Best<TC, 
 // the arrays of the second (self-net) count: the kernels of the other variant get null
 template <bool HYP, typename T> inline T *if_hyp(T *p) { return HYP ? p : nullptr; }
 
-// ---- dp_total_leaf.hip: the leaf pass and the combine, instantiated there for TC in {int64_t, double} x HYP (its kernels are
-// named in that unit only; nothing calls across units on the device)
+// ---- the stage functions of the other units: defined there, external, instantiated for TC in {int64_t, double} x HYP (a unit's
+// kernels are named in that unit only; nothing calls across units on the device)
+// dp_total_rpass.hip: the right pass
+template <typename TC, bool HYP> void right_pass(const LayerCtx<TC> &C, LayerWork<TC> &Wk, const RoundDesc &R);
+template <typename TC, bool HYP> void last_row_counts(const LayerCtx<TC> &C, LayerWork<TC> &Wk, const RoundDesc &R);
+// dp_total_gap.hip: the gap passes
+template <typename TC, bool HYP> void gap_finish(const LayerCtx<TC> &C, LayerWork<TC> &Wk, const RoundDesc &R, RoundCounts *rc, const RoundCounts &P);
+// dp_total_leaf.hip: the leaf pass and the combine
 template <typename TC, bool HYP> void leaf_pass(const LayerCtx<TC> &C, LayerWork<TC> &Wk);
 template <typename TC, bool HYP> void combine_rows(const LayerCtx<TC> &C, LayerWork<TC> &Wk);
 

@@ -5,7 +5,8 @@ count functions and blocks in instantiation order, which host edits move), comme
 comments cut (the assembler pads them to a column that depends on the digits of the label in front: `.LBB24_9:   ; =>This Inner
 Loop Header` moves when the function's ordinal goes from one digit to two).  Text is hashed, no instruction is inspected.  Several
 units give one table; a symbol defined by two of them is an error.
-usage: python tools/kernel_text.py chainpartitioners.jl_amd/csrc/dp_total.hip [chainpartitioners.jl_amd/csrc/dp_total_leaf.hip ...]"""
+usage: python tools/kernel_text.py chainpartitioners.jl_amd/csrc/dp_total.hip [chainpartitioners.jl_amd/csrc/dp_total_gap.hip ...]
+       (the total-cost DP as one table: chainpartitioners.jl_amd/csrc/dp_total*.hip)"""
 import hashlib
 import os
 import re

@@ -1,5 +1,6 @@
 """Per-kernel register / scratch / occupancy table of one or more HIP translation units (hipcc -Rpass-analysis=kernel-resource-usage).
-usage: python tools/resource_usage.py chainpartitioners.jl_amd/csrc/dp_total.hip [chainpartitioners.jl_amd/csrc/dp_total_leaf.hip ...] [--all]"""
+usage: python tools/resource_usage.py chainpartitioners.jl_amd/csrc/dp_total.hip [chainpartitioners.jl_amd/csrc/dp_total_gap.hip ...] [--all]
+       (the total-cost DP: chainpartitioners.jl_amd/csrc/dp_total*.hip)"""
 import re
 import subprocess
 import sys
