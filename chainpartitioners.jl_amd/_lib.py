@@ -125,12 +125,16 @@ SIGNATURES = {
                                  _I32("nn_out"), _I32("nl_out"), _I64("res")]),
     "cp_test_own_split": (_i32, [_vp, _I32("vpos_out"), _I32("vsa_out"), _I32("vnext_out"), _I64("res")]),
     "cp_test_own_pair": (_i32, [_i64, _i64, _I64("res")]),
+    "cp_test_own_pack": (_i32, [_vp, _I32("vpk_out"), _I32("vbase_out"), _I64("res")]),
     "cp_set_option": (_i32, [_str, _i64]),
     "cp_prof_enable": (_i32, [_i32]),
     "cp_prof_reset": (_i32, []),
     "cp_prof_get": (_i32, [_i32, C.POINTER(C.c_char_p), _pi64, _pf64, _pf64]),
 }
 SYMBOLS = list(SIGNATURES)
+# test entries a library of an earlier build may lack when it is loaded through CP_LIB_PATH for an A/B run (tools/ab_libs.sh): the
+# call, not the load, fails there
+OPTIONAL = {"cp_test_own_pack"}
 
 _lib = None
 
@@ -148,6 +152,12 @@ def _typed(name, fn, restype, argtypes):
     return call
 
 
+def _missing(name):
+    def call(*args):
+        raise RuntimeError(f"{LIB_PATH} has no {name}: it is a library of an earlier build")
+    return call
+
+
 def load_library():
     global _lib
     if _lib is None:
@@ -156,6 +166,9 @@ def load_library():
                                "(make -C chainpartitioners.jl_amd/csrc); there is no CPU fallback")
         lib = C.CDLL(LIB_PATH)
         for name, (restype, argtypes) in SIGNATURES.items():
+            if name in OPTIONAL and not hasattr(lib, name):
+                setattr(lib, name, _missing(name))
+                continue
             setattr(lib, name, _typed(name, getattr(lib, name), restype, argtypes))
         _lib = lib
     return _lib
@@ -302,6 +315,17 @@ class HipBackend:
         res = np.zeros(3, np.int64)
         self._ok(self.lib.cp_test_own_pair(nt, wave, res), "cp_test_own_pair")
         return bool(res[0]), int(res[1]), int(res[2])
+
+    def test_own_pack(self, A):
+        """the packed words and block bases of the split link entries (test entry): (nb, vpk[nb, n + 1] uint32, vbase[nb, blocks + 1, 2],
+        {"blocks", "packed", "max_start", "max_prefix"})"""
+        nb = max(0, int(A.n).bit_length() - 8)
+        nblk = (A.n + 1 + 255) // 256
+        vpk = np.zeros((max(nb, 1), A.n + 1), np.int32); vbase = np.zeros((max(nb, 1), nblk + 1, 2), np.int32)
+        res = np.zeros(5, np.int64)
+        self._ok(self.lib.cp_test_own_pack(self._h(A), vpk.reshape(-1), vbase.reshape(-1), res), "cp_test_own_pack")
+        assert int(res[0]) == nb and int(res[1]) == nblk
+        return nb, vpk[:nb].view(np.uint32), vbase[:nb], dict(zip(("blocks", "packed", "max_start", "max_prefix"), (int(v) for v in res[1:])))
 
     def set_option(self, name, value):
         return self.lib.cp_set_option(name.encode(), value)

@@ -143,7 +143,9 @@ static int32_t oracle_eval_into(cp_csr_t A, const cp_model_t *model, const cp_ro
 // merged; fix_items: the (task, trip) items the merges were handed (every attempt of a layer: a dropped round lists none).
 // own_split_tiles: own tiles that streamed only their plane's variable link entries (layers that were not redone); gap_split_tiles: the
 // same for the tiles of the gap rounds, which own_split_tiles does not count.  own_pair_waves / own_pair_lone: waves of k_lpass_own that
-// ran two tiles / one because the run order ended ("own_pair"; layers that were not redone).  overlap_isect: column intersections cp_pack_overlap computed.
+// ran two tiles / one because the run order ended ("own_pair"; layers that were not redone).  own_pack_tiles: split tiles, gap rounds
+// included, that read the packed words ("own_pack"; layers that were not redone); own_pack_wide: 1 while the pattern of the last split
+// launch has an in-block offset beyond 16 bits and runs on the wide arrays.  overlap_isect: column intersections cp_pack_overlap computed.
 // bn_sym_layers: DP layers the valley search ran for the monotonized symmetric model.  cut_scan_layers: DP layers of the plaid edge-cut
 // models the prefix-min scan ran (plaid_cut.hip).  kept: cp_set_option("poison", 1) starts a
 // poison pass by zeroing the other counters and leaves this one.
@@ -152,6 +154,7 @@ static const struct { const char *name; int64_t *var; bool kept; } g_stats[] = {
     {"fix_edges", &g_fix_edges, false}, {"fix_items", &g_fix_items, false}, {"bn_sym_layers", &g_bn_sym_layers, true},
     {"own_split_tiles", &g_own_split_tiles, false}, {"gap_split_tiles", &g_gap_split_tiles, false},
     {"own_pair_waves", &g_own_pair_waves, false}, {"own_pair_lone", &g_own_pair_lone, false},
+    {"own_pack_tiles", &g_own_pack_tiles, false}, {"own_pack_wide", &g_own_pack_wide, false},
     {"overlap_isect", &g_overlap_isect, false}, {"cut_scan_layers", &g_cut_scan_layers, false},
 };
 static void stats_reset(bool all) { for (const auto &c : g_stats) if (all || !c.kept) *c.var = 0; }
@@ -170,6 +173,7 @@ static const struct Opt { const char *name; int64_t *var; OptRule rule; int64_t 
     {"own_blk", &g_opt_own_blk, OPT_BOOL, 0, 0},                // (1, default: own tiles at 256-column blocks, run in block order; 0: tiles counted from each task head, in task order)
     {"own_split", &g_opt_own_split, OPT_BOOL, 0, 0},            // (1, default: own tiles of the planes >= 8 stream only the plane's variable link entries; 0: the whole columns)
     {"own_pair", &g_opt_own_pair, OPT_BOOL, 0, 0},              // (1, default: outside the gap rounds and the hyperedge costs a wave streams two own tiles; 0: one)
+    {"own_pack", &g_opt_own_pack, OPT_BOOL, 0, 0},              // (1, default: split tiles read one packed word per step -- while own_split and own_blk are 1 and the pattern's offsets fit; 0: the wide arrays)
     {"gap_split", &g_opt_gap_split, OPT_BOOL, 0, 0},            // (1, default: so do the gap rounds' tiles of those planes -- while own_split is 1; 0: they stream the whole columns)
     {"lws", &g_opt_lws, OPT_BOOL, 0, 0},                        // (1, default: DynamicTotalChunker past the scan by chunk_lws.hip; 0: the one-wave kernel)
     {"gap_tau", &g_opt_gap_tau, OPT_CLAMP, NOLIM_LO, 20}, {"gap_min", &g_opt_gap_min, OPT_CLAMP, 8, NOLIM_HI}, {"gap_nr", &g_opt_gap_nr, OPT_CLAMP, 1, 2},
@@ -330,6 +334,16 @@ int32_t cp_test_own_split(cp_csr_t A, int32_t *vpos_out, int32_t *vsa_out, int32
     return guarded([&]() -> int32_t {
         CP_HIP(hipSetDevice(A->device));
         dp_own_split_test(A, vpos_out, vsa_out, vnext_out, res);
+        return CP_OK;
+    });
+}
+
+int32_t cp_test_own_pack(cp_csr_t A, int32_t *vpk_out, int32_t *vbase_out, int64_t *res)
+{
+    if (!A || !vpk_out || !vbase_out || !res) return CP_EINVAL;
+    return guarded([&]() -> int32_t {
+        CP_HIP(hipSetDevice(A->device));
+        dp_own_pack_test(A, vpk_out, vbase_out, res);
         return CP_OK;
     });
 }

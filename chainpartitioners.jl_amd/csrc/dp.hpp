@@ -145,6 +145,9 @@ extern int64_t g_gap_split_tiles;              // gap tiles that took that path 
 extern int64_t g_opt_own_pair;                 // 1: outside the gap rounds and the hyperedge costs a wave of k_lpass_own takes two slots of the run order
 extern int64_t g_own_pair_waves, g_own_pair_lone;      // waves that ran two tiles / one because the order ended, since the last reset
 void dp_own_pair_test(int64_t nt, int64_t wave, int64_t *res);      // dp_total.hip: cp_test_own_pair
+extern int64_t g_opt_own_pack;                 // 1 (and own_split 1, own_blk 1): split tiles read one packed word per step where the pattern's in-block offsets fit 16 bits
+extern int64_t g_own_pack_tiles, g_own_pack_wide;      // tiles that ran packed since the last reset; 1: the pattern of the last split launch fell back to the wide arrays
+void dp_own_pack_test(cp_csr_s *A, int32_t *vpk_out, int32_t *vbase_out, int64_t *res);      // dp_total.hip: cp_test_own_pack
 extern int64_t g_overlap_isect;                // column intersections cp_pack_overlap computed since the last reset (chunk_greedy.hip)
 void dp_own_split_test(cp_csr_s *A, int32_t *vpos_out, int32_t *vsa_out, int32_t *vnext_out, int64_t *res);      // dp_total.hip: cp_test_own_split
 extern int64_t g_opt_short_t, g_opt_short_e;   // k_setup_short: tasks with <= short_t candidates and <= short_e link entries finish in setup

@@ -48,6 +48,8 @@ int64_t g_opt_gap_split = 1;           // ... and so do the gap rounds' tiles of
 int64_t g_gap_split_tiles = 0;
 int64_t g_opt_own_pair = 1;            // two own tiles per wave outside the gap rounds and the hyperedge costs (k_lpass_own<PAIR>); 0: one
 int64_t g_own_pair_waves = 0, g_own_pair_lone = 0;
+int64_t g_opt_own_pack = 1;            // split tiles read one packed word per step and plane (SplitLinks::vpk) where the pattern's offsets fit; effective under own_split and own_blk 1
+int64_t g_own_pack_tiles = 0, g_own_pack_wide = 0;
 int64_t g_opt_rpass_ch = 256;
 int64_t g_opt_rpass_small_tau = 4;
 int64_t g_opt_force_max = 1024;           // a round's flattened stage is replaced by own tiles when it served at most this many tasks
@@ -409,11 +411,15 @@ __device__ __forceinline__ int32_t coop_count(const int32_t *__restrict__ arr, i
 // (Tried: the link values in 3 bytes (n < 2^24), a 12-byte load and six vector instructions to unpack four entries -- 19 % fewer
 //  bytes per step, and k_lpass_own 9 % SLOWER (254 vs 232 ms per partition): at 0.8 of the HBM roofline the kernel has no vector
 //  issue slots to spare.)
-template <bool GE, bool DET = false>
+// PK (own_pack; own_split tiles of the geometry own_blk 1, which lie inside one 256-column block): cpos is the plane's packed words
+// (SplitLinks::vpk), one load per step -- the column's start and its prefix sum as 16-bit offsets from the block's bases vb[0]; vb[1]
+// holds the next block's.  A tile that is not a head tile ends at the block's last column: its run ends, and its prefix sums are
+// taken from, the next block's bases; a head tile's are the offsets of its column p_first.  psum is not read.
+template <bool GE, bool DET = false, bool PK = false>
 __device__ __forceinline__ void interior_stream(const int32_t *__restrict__ arr, const int32_t *__restrict__ cpos, int32_t p_first, int32_t tl,
                                                 int32_t thr, int lane, int32_t acc[4], int32_t sk[4], int head = 0, int32_t sp_lo = 0, int32_t sp_hi = 0,
                                                 int32_t *s_es = nullptr, int32_t *s_v = nullptr, int32_t *s_cnt = nullptr, int kind = 0,
-                                                const int32_t *__restrict__ psum = nullptr)
+                                                const int32_t *__restrict__ psum = nullptr, const int2 *__restrict__ vb = nullptr)
 {
     // No load of this function sits under a lane mask or a data-dependent branch: behind the join of a conditional load the
     // compiler cannot tell how many loads are outstanding and waits for all of them, which made every guarded load a round trip
@@ -432,16 +438,32 @@ __device__ __forceinline__ void interior_stream(const int32_t *__restrict__ arr,
         const int32_t e = lane + 64 * k;
         const uint32_t d = (uint32_t)(tl - (e < tl ? e : tl)) & 255u;
         cp[k] = cl[d];
-        pv[k] = pl[d];
+        if (!PK) pv[k] = pl[d];
     }
+    int32_t Q_hi, Q_lo;
+    if constexpr (PK) {
+        // the same group: the words of column p_first and of the tile's last column, and the two base pairs (adjacent scalars)
+        const uint32_t wt = (uint32_t)__builtin_amdgcn_readfirstlane(cl[tl]), wl = (uint32_t)__builtin_amdgcn_readfirstlane(cl[0]);
+        const int2 b0 = vb[0], b1 = vb[1];
+        Q_hi = head ? b0.x + (int32_t)(wt & 0xffffu) : b1.x;
+        Q_lo = b0.x + (int32_t)(wl & 0xffffu);
+        const int32_t ptop = head ? (int32_t)(wt >> 16) : b1.y - b0.y;              // (relative to the block's base, like the steps')
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const bool on = lane + 64 * k <= tl;
+            sk[k] = on ? b0.x + (int32_t)((uint32_t)cp[k] & 0xffffu) : INT32_MAX;
+            acc[k] = on ? ptop - (int32_t)((uint32_t)cp[k] >> 16) : 0;
+        }
+    } else {
     // head != 0: step 0 is the candidate p_first itself (no column stepped over): the run ends in front of that column
     const int32_t ptop = pl[tl + 1 - head];
-    const int32_t Q_hi = __builtin_amdgcn_readfirstlane(cl[tl + 1 - head]), Q_lo = __builtin_amdgcn_readfirstlane(cl[0]);
+    Q_hi = __builtin_amdgcn_readfirstlane(cl[tl + 1 - head]); Q_lo = __builtin_amdgcn_readfirstlane(cl[0]);
 #pragma unroll
     for (int k = 0; k < 4; k++) {
         const bool on = lane + 64 * k <= tl;
         sk[k] = on ? cp[k] : INT32_MAX;
         acc[k] = (psum && on) ? ptop - pv[k] : 0;
+    }
     }
     // Entries: a lane whose four positions start at or above Q_hi reads the run's last aligned quad instead -- inside the eight
     // entries of slack behind every streamed array (next: ensure_links, flast: ensure_self, + 16; vnext: split_build, + 8) -- and
@@ -524,11 +546,12 @@ __device__ __forceinline__ void interior_stream(const int32_t *__restrict__ arr,
 // but the compiler then lets the first trip's prefetch share a register with the second block and waits for the first two blocks
 // before it sends the prefetch: one round trip more per tile of more than one trip, 1 % on the windowed layers.  So the one-tile
 // form keeps its own text, and its code is what it was.)
-struct TileHead { int32_t cp[4], pv[4], ptop, qhi, qlo; };
+struct TileHead { int32_t cp[4], pv[4], ptop, qhi, qlo; int2 b0, b1; };      // (PK: cp the packed words, ptop / qlo those of column p_first / the last column, b0 / b1 the bases)
 struct TileRun { int32_t Q_lo, Q_hi, x, x_end; int4 c0, c1; };
 
+template <bool PK = false>
 __device__ __forceinline__ void tile_head_loads(TileHead &h, const int32_t *__restrict__ cpos, const int32_t *__restrict__ psum, int32_t p_first, int32_t tl,
-                                                int head, int lane)
+                                                int head, int lane, const int2 *__restrict__ vb = nullptr)
 {
     // Prologue, one group of loads: the column pointers of the lane's four steps (a step beyond tl reads the tile's last column),
     // the run's two ends, and with psum (wave-uniform; own_split) what a step starts from: psum[end of the run's columns] -
@@ -539,7 +562,13 @@ __device__ __forceinline__ void tile_head_loads(TileHead &h, const int32_t *__re
         const int32_t e = lane + 64 * k;
         const uint32_t d = (uint32_t)(tl - (e < tl ? e : tl)) & 255u;
         h.cp[k] = cl[d];
-        h.pv[k] = pl[d];
+        if (!PK) h.pv[k] = pl[d];
+    }
+    if constexpr (PK) {                // (see interior_stream)
+        h.ptop = cl[tl];
+        h.qlo = cl[0];
+        h.b0 = vb[0]; h.b1 = vb[1];
+        return;
     }
     // head != 0: step 0 is the candidate p_first itself (no column stepped over): the run ends in front of that column
     h.ptop = pl[tl + 1 - head];
@@ -557,8 +586,21 @@ __device__ __forceinline__ int4 tile_quad(const int32_t *__restrict__ arr, int32
     return *reinterpret_cast<const int4 *>(arr + x + (o < r ? o : r));
 }
 
-__device__ __forceinline__ void tile_counters(const TileHead &h, int32_t tl, int lane, bool psum, int32_t acc[4], int32_t sk[4], TileRun &r)
+template <bool PK = false>
+__device__ __forceinline__ void tile_counters(const TileHead &h, int32_t tl, int lane, bool psum, int32_t acc[4], int32_t sk[4], TileRun &r, int head = 0)
 {
+    if constexpr (PK) {
+        const uint32_t wt = (uint32_t)__builtin_amdgcn_readfirstlane(h.ptop), wl = (uint32_t)__builtin_amdgcn_readfirstlane(h.qlo);
+        r.Q_hi = head ? h.b0.x + (int32_t)(wt & 0xffffu) : h.b1.x;
+        r.Q_lo = h.b0.x + (int32_t)(wl & 0xffffu);
+        const int32_t ptop = head ? (int32_t)(wt >> 16) : h.b1.y - h.b0.y;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const bool on = lane + 64 * k <= tl;
+            sk[k] = on ? h.b0.x + (int32_t)((uint32_t)h.cp[k] & 0xffffu) : INT32_MAX;
+            acc[k] = on ? ptop - (int32_t)((uint32_t)h.cp[k] >> 16) : 0;
+        }
+    } else {
     r.Q_hi = __builtin_amdgcn_readfirstlane(h.qhi);
     r.Q_lo = __builtin_amdgcn_readfirstlane(h.qlo);
 #pragma unroll
@@ -566,6 +608,7 @@ __device__ __forceinline__ void tile_counters(const TileHead &h, int32_t tl, int
         const bool on = lane + 64 * k <= tl;
         sk[k] = on ? h.cp[k] : INT32_MAX;
         acc[k] = (psum && on) ? h.ptop - h.pv[k] : 0;
+    }
     }
     r.x_end = r.Q_hi & ~3;
     r.x = r.Q_lo & ~3;
@@ -782,7 +825,10 @@ __host__ __device__ __forceinline__ bool own_pair_slots(int64_t w, int64_t nt, i
 
 // border, a_srec (blk = 1): the tile ids and their records in column-block order; wave k takes tile border[k], whose record is a_srec[k]
 // PAIR (own_pair; neither GAP nor HYP): wave k takes the slots 2k and 2k + 1 of that order.
-template <typename TC, bool HYP, bool GAP, bool PAIR = false>
+// PK (own_pack; not HYP): the split tiles of the launch take the packed words of their plane and the bases of their block
+// (interior_stream<PK>): a_vpos is SplitLinks::vpk then and a_vsa is SplitLinks::vbase (pairs; stride: the blocks of vstride columns
+// + 1) -- the argument list, and with it the code of the other instantiations, is what it was.  PAIR: every tile of the launch is split (own_stream).
+template <typename TC, bool HYP, bool GAP, bool PAIR = false, bool PK = false>
 __global__ void __launch_bounds__(256) k_lpass_own(int isA, const RoundCounts *__restrict__ rc, const int32_t *__restrict__ border,
                                                    const int32_t *__restrict__ a_pos, const int32_t *__restrict__ a_next,
                                                    const int32_t *__restrict__ a_fpos, const int32_t *__restrict__ a_flast,
@@ -817,6 +863,7 @@ __global__ void __launch_bounds__(256) k_lpass_own(int isA, const RoundCounts *_
         int64_t s0, s1;
         if (!own_pair_slots((int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), rc->NT, s0, s1)) return;
         const bool lone = s1 == s0;
+
         // A model whose pin coefficient is zero multiplies the pin count by it: its lanes all read the pin position of the tile's
         // last column instead (one line, not four: 4 of a step's ~25 bytes) -- a count >= 0 like the true one, so the product is
         // the same zero, bit for bit; the load stays where it is, unconditional.
@@ -832,15 +879,25 @@ __global__ void __launch_bounds__(256) k_lpass_own(int isA, const RoundCounts *_
         const int32_t tlA = (rA.w >> 2) & 255, tlB = (rB.w >> 2) & 255;
         const int sbA = rA.w >> 10, sbB = rB.w >> 10;                    // (own_split: the plane, or 0 -- one tile of a pair may be split, the other not)
         const int64_t soA = sbA ? (int64_t)(sbA - SPLIT_BMIN) * vstride : 0, soB = sbB ? (int64_t)(sbB - SPLIT_BMIN) * vstride : 0;
-        const int32_t *__restrict__ arrA = sbA ? a_vnext : a_next, *__restrict__ arrB = sbB ? a_vnext : a_next;
+        const int32_t *__restrict__ arrA = (PK || sbA) ? a_vnext : a_next, *__restrict__ arrB = (PK || sbB) ? a_vnext : a_next;
         TileHead hB;
-        tile_head_loads(hB, sbB ? a_vpos + soB : a_pos, sbB ? a_vsa + soB : (const int32_t *)nullptr, rB.x, tlB, hdB, lane);
         TileRun uB;
         int32_t accA[4], accB[4], skA[4], skB[4];
         const int32_t zero4[4] = {0, 0, 0, 0};
+        if constexpr (PK) {
+            const int64_t vbstride = ((vstride + 255) >> 8) + 1;
+            const int2 *__restrict__ a_vbase = reinterpret_cast<const int2 *>(a_vsa);
+            const int2 *__restrict__ vbA = a_vbase + (int64_t)(sbA - SPLIT_BMIN) * vbstride + (rA.x >> 8);
+            const int2 *__restrict__ vbB = a_vbase + (int64_t)(sbB - SPLIT_BMIN) * vbstride + (rB.x >> 8);
+            tile_head_loads<true>(hB, a_vpos + soB, nullptr, rB.x, tlB, hdB, lane, vbB);
+            interior_stream<true, false, true>(a_vnext, a_vpos + soA, rA.x, tlA, rA.y, lane, accA, skA, hdA, 0, 0, nullptr, nullptr, nullptr, 0, nullptr, vbA);
+            tile_counters<true>(hB, tlB, lane, true, accB, skB, uB, hdB);
+        } else {
+        tile_head_loads(hB, sbB ? a_vpos + soB : a_pos, sbB ? a_vsa + soB : (const int32_t *)nullptr, rB.x, tlB, hdB, lane);
         interior_stream<true>(arrA, sbA ? a_vpos + soA : a_pos, rA.x, tlA, rA.y, lane, accA, skA, hdA, 0, 0, nullptr, nullptr, nullptr, 0,
                               sbA ? a_vsa + soA : (const int32_t *)nullptr);
         tile_counters(hB, tlB, lane, sbB != 0, accB, skB, uB);
+        }
         TC wv[4];
 #pragma unroll
         for (int k = 0; k < 4; k++) {
@@ -903,6 +960,11 @@ __global__ void __launch_bounds__(256) k_lpass_own(int isA, const RoundCounts *_
         // are compared and tested
         const int sb = HYP ? 0 : rw >> 10;                               // (scalar: the arrays stay scalar operands)
         const int64_t so = sb ? (int64_t)(sb - SPLIT_BMIN) * vstride : 0;
+        if constexpr (PK) {            // (wave-uniform: the plane-7 tiles of the launch stream the whole columns)
+            if (sb) interior_stream<true, true, true>(a_vnext, a_vpos + so, rec.x, tl, hi1, lane, acc, sk, head, rL, hi1, s_es[0], s_v[0], s_cnt, 0, nullptr,
+                                                      reinterpret_cast<const int2 *>(a_vsa) + (int64_t)(sb - SPLIT_BMIN) * (((vstride + 255) >> 8) + 1) + (rec.x >> 8));
+            else interior_stream<true, true>(a_next, a_pos, rec.x, tl, hi1, lane, acc, sk, head, rL, hi1, s_es[0], s_v[0], s_cnt, 0);
+        } else
         interior_stream<true, true>(sb ? a_vnext : a_next, sb ? a_vpos + so : a_pos, rec.x, tl, hi1, lane, acc, sk, head, rL, hi1, s_es[0], s_v[0], s_cnt, 0,
                                     sb ? a_vsa + so : (const int32_t *)nullptr);
         if (HYP) interior_stream<false, true>(a_flast, a_fpos, rec.x, tl, rL + 1, lane, acc2, sk2, head, rL, hi1, s_es[0], s_v[0], s_cnt, 1);
@@ -943,6 +1005,11 @@ __global__ void __launch_bounds__(256) k_lpass_own(int isA, const RoundCounts *_
         // count wants the column's own position
         const int sb = rw >> 10;                                         // (scalar: the arrays stay scalar operands)
         const int64_t so = sb ? (int64_t)(sb - SPLIT_BMIN) * vstride : 0;
+        if constexpr (PK) {            // (wave-uniform: tiles of the planes below SPLIT_BMIN stream the whole columns)
+            if (sb) interior_stream<true, false, true>(a_vnext, a_vpos + so, rec.x, tl, rec.y, lane, acc, sk, head, 0, 0, nullptr, nullptr, nullptr, 0, nullptr,
+                                                       reinterpret_cast<const int2 *>(a_vsa) + (int64_t)(sb - SPLIT_BMIN) * (((vstride + 255) >> 8) + 1) + (rec.x >> 8));
+            else interior_stream<true>(a_next, a_pos, rec.x, tl, rec.y, lane, acc, sk, head);
+        } else
         interior_stream<true>(sb ? a_vnext : a_next, sb ? a_vpos + so : a_pos, rec.x, tl, rec.y, lane, acc, sk, head, 0, 0, nullptr, nullptr, nullptr, 0,
                               sb ? a_vsa + so : (const int32_t *)nullptr);
         // (a_pos is what the stream's sk holds when the tile is not split: reloaded either way, in one group with W below)
@@ -2220,20 +2287,47 @@ __global__ void __launch_bounds__(256) k_split_count(const int32_t *__restrict__
     for (int b = 0; b < SPLIT_NB; b++) if (b < nb) cnt[(int64_t)b * (n + 1) + p] = c[b];
 }
 
-// one lane per column: the column's variable entries to their planes, in entry order; vsa from the scanned offsets:
-// vsa[b][p] = sum over b' > b of (vpos[b'][p] - vpos[b'][0])
+// one lane per column, one block per 256-column block: the column's variable entries to their planes, in entry order, and the packed
+// words (SplitLinks) -- with  vsa[b][p] = sum over b' > b of (vpos[b'][p] - vpos[b'][0])  the column's two in-block offsets, from the
+// bases thread 0 (the block's first column) leaves in LDS and in vbase; they go where the counts were.  Both offsets grow with p, so a
+// block's last column holds its largest ones: it alone raises vmax (and reads it first: few blocks get as far as the atomic).
 __global__ void __launch_bounds__(256) k_split_scatter(const int32_t *__restrict__ pos, const int32_t *__restrict__ next, int64_t n, int nb,
-                                                       const int32_t *__restrict__ vpos, int32_t *__restrict__ vnext, int32_t *__restrict__ vsa)
+                                                       const int32_t *__restrict__ vpos, int32_t *__restrict__ vnext, int32_t *__restrict__ vpk,
+                                                       int2 *__restrict__ vbase, int64_t nblk, int32_t *__restrict__ vmax)
 {
+    __shared__ int32_t s_bp[SPLIT_NB], s_bs[SPLIT_NB];
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p > n) return;
+    const bool live = p <= n;
     int32_t c[SPLIT_NB];
 #pragma unroll
-    for (int b = 0; b < SPLIT_NB; b++) c[b] = b < nb ? vpos[(int64_t)b * (n + 1) + p] : 0;
-    int32_t above = 0;
+    for (int b = 0; b < SPLIT_NB; b++) c[b] = (b < nb && live) ? vpos[(int64_t)b * (n + 1) + p] : 0;
+    if (threadIdx.x == 0) {                          // (p <= n: the grid has no block without a column)
+        int32_t above = 0;
 #pragma unroll
-    for (int b = SPLIT_NB - 1; b >= 0; b--)
-        if (b < nb) { vsa[(int64_t)b * (n + 1) + p] = above; above += c[b] - vpos[(int64_t)b * (n + 1)]; }
+        for (int b = SPLIT_NB - 1; b >= 0; b--)
+            if (b < nb) {
+                s_bp[b] = c[b]; s_bs[b] = above;
+                vbase[(int64_t)b * (nblk + 1) + blockIdx.x] = make_int2(c[b], above);
+                if ((int64_t)blockIdx.x == nblk - 1) vbase[(int64_t)b * (nblk + 1) + nblk] = make_int2(vpos[(int64_t)(b + 1) * (n + 1)], 0);
+                above += c[b] - vpos[(int64_t)b * (n + 1)];
+            }
+    }
+    __syncthreads();
+    if (live) {
+        int32_t above = 0, mp = 0, ms = 0;
+#pragma unroll
+        for (int b = SPLIT_NB - 1; b >= 0; b--)
+            if (b < nb) {
+                const int32_t op = c[b] - s_bp[b], os = above - s_bs[b];
+                vpk[(int64_t)b * (n + 1) + p] = (int32_t)(((uint32_t)op & 0xffffu) | ((uint32_t)os << 16));
+                mp = op > mp ? op : mp; ms = os > ms ? os : ms;
+                above += c[b] - vpos[(int64_t)b * (n + 1)];
+            }
+        if (threadIdx.x == 255 || p == n) {
+            if (mp > vmax[0]) atomicMax(&vmax[0], mp);
+            if (ms > vmax[1]) atomicMax(&vmax[1], ms);
+        }
+    }
     if (p < n)
         for (int32_t q = pos[p], qe = pos[p + 1]; q < qe; q++) {
             const int32_t x = next[q];
@@ -2245,32 +2339,62 @@ __global__ void __launch_bounds__(256) k_split_scatter(const int32_t *__restrict
         }
 }
 
+// one lane per column: the wide vsa from vpos (split_wide)
+__global__ void __launch_bounds__(256) k_split_vsa(int64_t n, int nb, const int32_t *__restrict__ vpos, int32_t *__restrict__ vsa)
+{
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p > n) return;
+    int32_t above = 0;
+    for (int b = nb - 1; b >= 0; b--) {
+        vsa[(int64_t)b * (n + 1) + p] = above;
+        above += vpos[(int64_t)b * (n + 1) + p] - vpos[(int64_t)b * (n + 1)];
+    }
+}
+
 static void split_build(cp_csr_s *A, SplitLinks &S, DBuf<int64_t> &scratch)
 {
     hipStream_t s = A->stream;
     const int64_t n = A->n, n1 = n + 1;
     int nbits = 1;
     while (((int64_t)1 << nbits) <= n) nbits++;
-    S.nb = std::max(0, nbits - SPLIT_BMIN); S.stride = n1;
+    S.nb = std::max(0, nbits - SPLIT_BMIN); S.stride = n1; S.nblk = cdiv(n1, 256);
+    S.packed = false; S.has_wide = false; S.max_off[0] = S.max_off[1] = 0;
     for (auto &t : S.tot) t = 0;
     if (S.nb > 0) {
         CP_REQUIRE(S.nb <= SPLIT_NB, CP_EINVAL, "n exceeds the bit-plane budget");
         const size_t cells = (size_t)S.nb * (size_t)n1;
-        S.vpos.ensure(cells + 1); S.vsa.ensure(cells + 1); S.vnext.ensure((size_t)A->N + 8);
-        const unsigned grid = (unsigned)cdiv(n1, 256);
-        // (the counts live in vsa until the scatter writes it)
-        hipLaunchKernelGGL(k_split_count, dim3(grid), dim3(256), 0, s, A->pos32.p, A->next.p, n, S.nb, S.vsa.p);
-        exclusive_scan_i32_i32(S.vsa.p, S.vpos.p, (int64_t)cells, scratch, s);
-        hipLaunchKernelGGL(k_split_scatter, dim3(grid), dim3(256), 0, s, A->pos32.p, A->next.p, n, S.nb, S.vpos.p, S.vnext.p, S.vsa.p);
+        S.vpos.ensure(cells + 1); S.vpk.ensure(cells + 1); S.vnext.ensure((size_t)A->N + 8);
+        S.vbase.ensure((size_t)S.nb * (size_t)(S.nblk + 1)); S.vmax.ensure(2);
+        const unsigned grid = (unsigned)S.nblk;
+        CP_HIP(hipMemsetAsync(S.vmax.p, 0, 2 * sizeof(int32_t), s));
+        // (the counts live in vpk until the scatter writes it)
+        hipLaunchKernelGGL(k_split_count, dim3(grid), dim3(256), 0, s, A->pos32.p, A->next.p, n, S.nb, S.vpk.p);
+        exclusive_scan_i32_i32(S.vpk.p, S.vpos.p, (int64_t)cells, scratch, s);
+        hipLaunchKernelGGL(k_split_scatter, dim3(grid), dim3(256), 0, s, A->pos32.p, A->next.p, n, S.nb, S.vpos.p, S.vnext.p, S.vpk.p, S.vbase.p, S.nblk,
+                           S.vmax.p);
         CP_HIP(hipGetLastError());
         int32_t st[SPLIT_NB + 1];                       // the planes' starts and the total: the entries a round's planes stream
         for (int b = 0; b <= S.nb; b++)
             CP_HIP(hipMemcpyAsync(&st[b], S.vpos.p + (size_t)b * (size_t)n1, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        CP_HIP(hipMemcpyAsync(S.max_off, S.vmax.p, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         CP_HIP(hipStreamSynchronize(s));
         for (int b = 0; b < S.nb; b++) S.tot[b] = (int64_t)st[b + 1] - st[b];
         S.tot[S.nb] = st[S.nb];
+        S.packed = S.max_off[0] <= 0xffff && S.max_off[1] <= 0xffff;
     }
     S.built = true;
+}
+
+// the wide vsa, for whoever does not take the packed words: an offset that does not fit, own_blk 0, own_pack 0, cp_test_own_split
+static void split_wide(cp_csr_s *A, SplitLinks &S)
+{
+    if (S.has_wide) return;
+    if (S.nb > 0) {
+        S.vsa.ensure((size_t)S.nb * (size_t)S.stride + 1);
+        hipLaunchKernelGGL(k_split_vsa, dim3((unsigned)S.nblk), dim3(256), 0, A->stream, A->n, S.nb, S.vpos.p, S.vsa.p);
+        CP_HIP(hipGetLastError());
+    }
+    S.has_wide = true;
 }
 
 // Test entry (cp_test_own_pair): what own_pair_slots gives wave `wave` among nt tiles -- the function the kernel calls
@@ -2290,12 +2414,28 @@ void dp_own_split_test(cp_csr_s *A, int32_t *vpos_out, int32_t *vsa_out, int32_t
     SplitLinks S;
     DBuf<int64_t> scratch;
     split_build(A, S, scratch);
+    split_wide(A, S);
     res[0] = S.nb; res[1] = S.tot[S.nb];
     if (S.nb <= 0) return;
     const size_t cells = (size_t)S.nb * (size_t)S.stride;
     CP_HIP(hipMemcpyAsync(vpos_out, S.vpos.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, A->stream));
     CP_HIP(hipMemcpyAsync(vsa_out, S.vsa.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, A->stream));
     if (res[1] > 0) CP_HIP(hipMemcpyAsync(vnext_out, S.vnext.p, (size_t)res[1] * sizeof(int32_t), hipMemcpyDeviceToHost, A->stream));
+    CP_HIP(hipStreamSynchronize(A->stream));
+}
+
+// Test entry (cp_test_own_pack): the packed words and the block bases of the pattern on the host.  vpk_out: nb (n + 1) words;
+// vbase_out: nb (blocks + 1) pairs {start, prefix sum}; res: {nb, blocks per plane, packed, largest start offset, largest prefix offset}.
+void dp_own_pack_test(cp_csr_s *A, int32_t *vpk_out, int32_t *vbase_out, int64_t *res)
+{
+    ensure_links(A);
+    SplitLinks S;
+    DBuf<int64_t> scratch;
+    split_build(A, S, scratch);
+    res[0] = S.nb; res[1] = S.nblk; res[2] = S.packed ? 1 : 0; res[3] = S.max_off[0]; res[4] = S.max_off[1];
+    if (S.nb <= 0) return;
+    CP_HIP(hipMemcpyAsync(vpk_out, S.vpk.p, (size_t)S.nb * (size_t)S.stride * sizeof(int32_t), hipMemcpyDeviceToHost, A->stream));
+    CP_HIP(hipMemcpyAsync(vbase_out, S.vbase.p, (size_t)S.nb * (size_t)(S.nblk + 1) * sizeof(int2), hipMemcpyDeviceToHost, A->stream));
     CP_HIP(hipStreamSynchronize(A->stream));
 }
 
@@ -2647,8 +2787,11 @@ static void round_scans(const LayerCtx<TC> &C, LayerWork<TC> &Wk, const RoundDes
 // (windowed layers keep one tile per wave: their tiles stream whole columns, ten trips and more, and paired they ran 5 % slower)
 template <bool HYP> static bool own_pairs(bool gap, bool win) { return !HYP && !gap && !win && g_opt_own_pair != 0; }
 
+// cp_set_option("own_pack", 0 | 1): the split tiles of a launch take the packed words where the geometry keeps a tile inside one block
+// (own_blk 1) and the pattern's offsets fit 16 bits -- except in a paired launch that also holds tiles of the planes below (gap_tau
+// below 6): a wave's two tiles run one text.  Returns whether they did.
 template <typename TC, bool HYP>
-static void own_stream(const LayerCtx<TC> &C, LayerWork<TC> &Wk, const RoundDesc &R, RoundCounts *rc, const RoundCounts &P, bool gap, int split)
+static bool own_stream(const LayerCtx<TC> &C, LayerWork<TC> &Wk, const RoundDesc &R, RoundCounts *rc, const RoundCounts &P, bool gap, int split)
 {
     hipStream_t s = C.s;
     cp_csr_s *A = C.A;
@@ -2663,22 +2806,31 @@ static void own_stream(const LayerCtx<TC> &C, LayerWork<TC> &Wk, const RoundDesc
         ProfScope ps(PROF_LINKS, s, 8.0 * (double)A->N + 16.0 * (double)(C.nbits - SPLIT_BMIN) * (double)(n + 1));
         split_build(A, Wk.ow.split, Wk.sc.scratch);
     }
+    if (split) g_own_pack_wide = Wk.ow.split.packed ? 0 : 1;      // (of the pattern the last split launch ran on)
+    const bool pair = own_pairs<HYP>(gap, C.G.win != 0);
+    const bool pack = split && oblk && g_opt_own_pack && Wk.ow.split.packed && !(pair && split == 2);
+    if (split && !pack) split_wide(A, Wk.ow.split);
     hipLaunchKernelGGL(k_own_map, dim3(mgrid), dim3(256), 0, s, rc, Wk.ow.o_toffs.p, Wk.ow.o_tdesc.p, Wk.ow.o_rlen.p, Wk.ow.o_rec.p, Wk.ow.o_task.p,
                        Wk.ow.o_tb.p, gap ? Wk.ow.o_hi.p : (int32_t *)nullptr, R.tau, n, oblk, oblk ? Wk.ow.b_cnt.p : (int32_t *)nullptr, Wk.ow.o_brank.p,
                        gap ? (int2 *)nullptr : Wk.ow.o_items.p, Wk.ow.o_item_of.p, split);
-    ProfScope ps(gap ? PROF_GAPSTREAM : PROF_OWN, s, C.own_bytes(Wk.ow.split, R.tau, split != 0, (double)P.own_steps));
+    ProfScope ps(gap ? PROF_GAPSTREAM : PROF_OWN, s, C.own_bytes(Wk.ow.split, R.tau, pack ? 2 : split != 0, (double)P.own_steps));
     if (oblk) {                       // the tile ids by column block (counted in k_own_map): ~10^5 tiles, a counting sort
         exclusive_scan_i32_lb(Wk.ow.b_cnt.p, Wk.ow.b_start.p, Wk.ow.b_n.p, Wk.ow.b_nblk, nullptr, Wk.sc.scanws, s);
         hipLaunchKernelGGL(k_blk_order, dim3(mgrid), dim3(256), 0, s, rc, Wk.ow.o_rec.p, Wk.ow.o_brank.p, Wk.ow.b_start.p, Wk.ow.o_border.p, Wk.ow.o_srec.p, Wk.ow.b_cnt.p);
     }
     // cp_set_option("own_pair", 0 | 1): outside the gap rounds and the hyperedge costs a wave takes two slots of the run order
-    const bool pair = own_pairs<HYP>(gap, C.G.win != 0);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(gap ? k_lpass_own<TC, HYP, true> : pair ? k_lpass_own<TC, HYP, false, !HYP> : k_lpass_own<TC, HYP, false>),
+    // (the packed instantiations exist for the plain costs only: `pack` is never set for the hyperedge ones)
+    auto kern = gap ? (pack ? k_lpass_own<TC, HYP, true, false, !HYP> : k_lpass_own<TC, HYP, true>)
+              : pair ? (pack ? k_lpass_own<TC, HYP, false, !HYP, !HYP> : k_lpass_own<TC, HYP, false, !HYP>)
+              : (pack ? k_lpass_own<TC, HYP, false, false, !HYP> : k_lpass_own<TC, HYP, false>);
+    hipLaunchKernelGGL(kern,
                        dim3((unsigned)cdiv(pair ? cdiv(gNT, 2) : gNT, 4)), dim3(256), 0, s, R.isA, rc,
                        oblk ? Wk.ow.o_border.p : (const int32_t *)nullptr, A->pos32.p, A->next.p, if_hyp<HYP>(A->fpos32.p), if_hyp<HYP>(A->flast.p),
                        Wk.ow.o_tileS.p, Wk.ow.o_tileS2.p, Wk.ow.o_rec.p, Wk.ow.o_srec.p, C.W, C.M, C.alpha, recs<HYP>(Wk.ow.o_part), R.tau, Wk.ow.o_hi.p, Wk.ow.o_spec.p,
                        (int)((g_opt_dbg & DBG_GAP_ALL_SPECIAL) != 0), recs<HYP>(Wk.ow.o_sub), Wk.ow.o_spv.p, A->col.p, if_hyp<HYP>(A->ffirst.p),
-                       split ? Wk.ow.split.vnext.p : (const int32_t *)nullptr, Wk.ow.split.vpos.p, Wk.ow.split.vsa.p, (int64_t)(n + 1));
+                       split ? Wk.ow.split.vnext.p : (const int32_t *)nullptr, pack ? Wk.ow.split.vpk.p : Wk.ow.split.vpos.p,
+                       pack ? reinterpret_cast<const int32_t *>(Wk.ow.split.vbase.p) : Wk.ow.split.vsa.p, (int64_t)(n + 1));
+    return pack;
 }
 
 // The tail of the chain outside the gap rounds: one launch, a lane per task of up to FIX_SERIAL tiles, a block per listed trip
@@ -2837,14 +2989,15 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
     const int NR = nbits + 1;
     std::vector<RoundCounts> used((size_t)NR);          // what the host sized each round with
     memset(used.data(), 0, sizeof(RoundCounts) * (size_t)NR);
-    struct Patch { size_t idx; int rd; int kind; int tau; bool split; };
+    struct Patch { size_t idx; int rd; int kind; int tau; int split; };          // (split: 0 whole columns, 1 split, 2 packed -- own_bytes)
     std::vector<Patch> patches;                          // profile records whose algorithmic bytes depend on the true counts
-    auto note = [&](int rd, int kind, int slot, int tau = 0, bool sp = false) {
+    auto note = [&](int rd, int kind, int slot, int tau = 0, int sp = 0) {
         if (prof_active(slot)) patches.push_back({g_prof_pending.size() - 1, rd, kind, tau, sp});
     };
     bool any_forced = false;
     std::vector<int8_t> split_mode((size_t)NR, 0);       // own_split per round (see own_stream)
     std::vector<int8_t> pair_mode((size_t)NR, 0);        // own_pair per round
+    std::vector<int8_t> pack_mode((size_t)NR, 0);        // own_pack per round
 
     for (int rd = 0; rd <= nbits; rd++) {
         RoundDesc R;
@@ -2908,8 +3061,9 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
             const int split = !(C.split_layer && !R.isA && (!gap || g_opt_gap_split)) ? 0 : R.tau + 1 >= SPLIT_BMIN ? 1 : 2;
             split_mode[(size_t)rd] = (int8_t)(gap ? -split : split);
             pair_mode[(size_t)rd] = own_pairs<HYP>(gap, G.win != 0);
-            own_stream<TC, HYP>(C, Wk, R, rc, P, gap, split);
-            note(rd, 0, gap ? PROF_GAPSTREAM : PROF_OWN, R.tau, split != 0);
+            const bool pack = own_stream<TC, HYP>(C, Wk, R, rc, P, gap, split);
+            pack_mode[(size_t)rd] = pack;
+            note(rd, 0, gap ? PROF_GAPSTREAM : PROF_OWN, R.tau, pack ? 2 : split != 0);
             if (gap) gap_finish<TC, HYP>(C, Wk, R, rc, P);
             else own_merge<TC, HYP>(C, Wk, rc, P);
             CP_HIP(hipGetLastError());
@@ -2948,7 +3102,9 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
         const RoundCounts &g = got[(size_t)rd];
         if (g.nown > 0 && g.NT > 0) {                   // (negative: a gap round)
             const int sm = split_mode[(size_t)rd];
-            (sm < 0 ? g_gap_split_tiles : g_own_split_tiles) += std::abs(sm) == 1 ? g.NT : std::abs(sm) == 2 ? g.n_split : 0;
+            const int64_t nsp = std::abs(sm) == 1 ? g.NT : std::abs(sm) == 2 ? g.n_split : 0;
+            (sm < 0 ? g_gap_split_tiles : g_own_split_tiles) += nsp;
+            if (pack_mode[(size_t)rd]) g_own_pack_tiles += nsp;                  // (the split tiles of a packed launch, gap rounds included)
             if (pair_mode[(size_t)rd]) { g_own_pair_waves += g.NT / 2; g_own_pair_lone += g.NT & 1; }      // (own_pair_slots over the true NT)
         }
     }

@@ -216,12 +216,21 @@ struct RATab { int32_t nbits, _pad; int64_t n; int64_t tbase[33]; int64_t rbase[
 //   vpos[b][p], p = 0 .. n: where column p's plane-b entries start in vnext (vpos[b][n] = vpos[b + 1][0]; one word more: the total);
 //   vsa[b][p]: #{entries of the columns < p with h > b}.
 // They depend on the pattern only: built once per partition, by the first layer that uses them (split_build).
+// own_pack: vpos and vsa only enter a tile as differences inside its 256-column block (own_blk 1: a tile lies inside one block), so
+// with c0 = p & ~255 one word per (plane, column) and one base pair per (plane, block) carry them:
+//   vpk[b][p] = (vpos[b][p] - vpos[b][c0]) | (vsa[b][p] - vsa[b][c0]) << 16, stride n + 1;
+//   vbase[b][k] = {vpos[b][256 k], vsa[b][256 k]}, k = 0 .. nblk - 1, stride nblk + 1; vbase[b][nblk] = {the end of the plane's entries, 0}.
+// Both offsets grow with p inside a block; the build keeps the largest of each (vmax).  packed: both fit 16 bits.  Where they do not,
+// and for the tiles that straddle blocks (own_blk 0), the wide vsa is made from vpos when it is first asked for (split_wide).
 struct SplitLinks {
-    bool built = false;
+    bool built = false, packed = false, has_wide = false;
     int nb = 0;
     int64_t stride = 0;                        // n + 1
+    int64_t nblk = 0;                          // 256-column blocks of a plane: cdiv(n + 1, 256)
     int64_t tot[SPLIT_NB + 1] = {0};           // variable entries per plane; [nb]: all of them
-    DBuf<int32_t> vnext, vpos, vsa;
+    int32_t max_off[2] = {0, 0};               // the largest in-block offset of vpos / of vsa
+    DBuf<int32_t> vnext, vpos, vsa, vpk, vmax; // (vpk: the counts until the scatter writes it; vsa: empty until split_wide)
+    DBuf<int2> vbase;
 };
 
 // items a round of `nt` own tiles can list: one per FIX_TRIP tiles and at most one partial trip per task of more than FIX_SERIAL tiles
@@ -383,14 +392,15 @@ struct LayerCtx {
     int ra_bmin;                                        // round A from the cache starts at this level
     int32_t *pzp;                                       // poison mode: the hit counters (null: off)
     double avg_deg, self_deg, step_bytes;               // link entries per column; bytes a step of the streaming kernels moves
-    // bytes the own-tile stream moves: split tiles read two column pointers and a prefix sum per step (20 B with the cost) and the
-    // variable entries of the round's planes, at most what the columns hold.  (Tiles of planes below SPLIT_BMIN in the same launch --
+    // bytes the own-tile stream moves: split tiles read two column pointers and a prefix sum per step (20 B with the cost; sp == 2,
+    // own_pack: the plane's pointer and prefix sum are one word, 16 B) and the variable entries of the round's planes, at most what
+    // the columns hold.  (Tiles of planes below SPLIT_BMIN in the same launch --
     // the plane-7 tiles of the gap round tau = 6 -- are priced like the others.)
-    double own_bytes(const SplitLinks &S, int tau, bool sp, double steps) const {
+    double own_bytes(const SplitLinks &S, int tau, int sp, double steps) const {
         if (!sp) return steps * step_bytes;
         double var = 0;
         for (int b = std::max(tau + 1, SPLIT_BMIN); b < nbits && b - SPLIT_BMIN < S.nb; b++) var += (double)S.tot[b - SPLIT_BMIN];
-        return steps * (20.0 + 32.0 / (double)LT) + 4.0 * std::min(var, avg_deg * steps);
+        return steps * ((sp == 2 ? 16.0 : 20.0) + 32.0 / (double)LT) + 4.0 * std::min(var, avg_deg * steps);
     }
 };
 

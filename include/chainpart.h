@@ -287,7 +287,9 @@ int32_t cp_reset_stream(cp_csr_t csr);
  * them, of every task of more than 16 tiles, in every attempt of a layer (a round dropped by its verdict lists none) and in
  * cp_test_fix_merge.  "own_split_tiles" -- own tiles that streamed only their plane's variable link entries ("own_split"), in
  * the layers that stand.  "own_pair_waves" / "own_pair_lone" -- waves of the own-tile stream that ran two tiles / one because the run
- * order ended ("own_pair"), in the layers that stand.  "overlap_isect" -- the column intersections cp_pack_overlap computed.  All of these are reset when "poison" is switched on and by cp_set_option("stat_reset", 1); reading
+ * order ended ("own_pair"), in the layers that stand.  "own_pack_tiles" -- split tiles, those of the gap rounds included, that read the packed words
+ * ("own_pack"), in the layers that stand; "own_pack_wide" -- 1 while the pattern of the last layer with split tiles has an in-block
+ * offset beyond 16 bits and runs on the wide arrays.  "overlap_isect" -- the column intersections cp_pack_overlap computed.  All of these are reset when "poison" is switched on and by cp_set_option("stat_reset", 1); reading
  * changes nothing. */
 int32_t cp_get_stat(const char *name, int64_t *out);
 /* Test entry: the launch that ends the counting phase of a DP round, on host arrays.  Exclusive scans of a[0 .. na) and (two != 0)
@@ -321,6 +323,12 @@ int32_t cp_test_own_split(cp_csr_t csr, int32_t *vpos_out, int32_t *vsa_out, int
  * "own_pair" 1.  res: {1 if the wave has work, else 0; its first slot 2 wave; its second slot 2 wave + 1, or the first one again
  * where the order ends there (a lone wave: it stores one tile)}. */
 int32_t cp_test_own_pair(int64_t nt, int64_t wave, int64_t *res);
+/* Test entry: the arrays of cp_test_own_split as the own tiles read them with "own_pack" 1.  With c0 = p - p % 256 and k = p / 256,
+ * blocks = ceil((n + 1) / 256): vpk_out[(b - 8) (n + 1) + p] = ((vpos[b][p] - vpos[b][c0]) & 0xffff) | (vsa[b][p] - vsa[b][c0]) << 16
+ * (as the bits of an unsigned word; the low 16 bits of either offset where it is larger); vbase_out, pairs of 32-bit words: entry (b - 8) (blocks + 1) + k =
+ * {vpos[b][256 k], vsa[b][256 k]} for k < blocks, and {the end of plane b's entries in vnext, 0} for k = blocks.
+ * res: {nb, blocks, 1 if both offsets fit 16 bits everywhere (the pattern runs packed) else 0, the largest offset of vpos, of vsa}. */
+int32_t cp_test_own_pack(cp_csr_t csr, int32_t *vpk_out, int32_t *vbase_out, int64_t *res);
 /* Library-wide tunables and test switches; results never depend on them (tests/test_gpu_dynamic.py runs every one against the
  * oracle).  "force_brute" 1: the general O(K n^2) device DP even where the O(K n log^2 n) scheme applies; "brute_max_n": its size
  * limit.  Layer driver of the O(K n log^2 n) scheme: "short_t"/"short_e" (tasks finished during setup),
@@ -328,7 +336,8 @@ int32_t cp_test_own_pair(int64_t nt, int64_t wave, int64_t *res);
  * streamed in block order; 0: tiles counted from each task's head, in task order), "own_split" (1, default: outside the first round
  * and the gap rounds the own tiles of the planes >= 8 stream only the link entries whose count depends on the row, see
  * cp_test_own_split; 0: whole columns), "own_pair" (1, default: outside the gap rounds and the hyperedge costs a wave of the own-tile
- * stream takes two tiles of the run order, see cp_test_own_pair; 0: one), "gap_tau"/"gap_min" (gap passes: rounds and task lengths; -1: none), "gap_nr" (64-row chunks per wave of the gap finish: 1 or 2), "pool" (1, default: freed device blocks of 1 MB and more are kept for reuse by the next call; 0: returned to HIP at once, and the pool is emptied),
+ * stream takes two tiles of the run order, see cp_test_own_pair; 0: one), "own_pack" (1, default: while "own_split" and "own_blk" are 1
+ * and the pattern's offsets fit, those tiles read a column's start and prefix sum as one 32-bit word, see cp_test_own_pack; 0: two words), "gap_tau"/"gap_min" (gap passes: rounds and task lengths; -1: none), "gap_nr" (64-row chunks per wave of the gap finish: 1 or 2), "pool" (1, default: freed device blocks of 1 MB and more are kept for reuse by the next call; 0: returned to HIP at once, and the pool is emptied),
  * "ra_cache" (round A from counts cached per partition), "nospec" 1 (one host sync per round instead of sizing a layer from the
  * previous one), "rpass_ch"/"rpass_small_tau"/"rpass_cap" (right-part passes: columns per wave, last
  * lane-per-row round, lane-private share of a row in per cent of the mean), "setup_bs" (lanes per block of the task setup), "force_max" (a round whose flattened
