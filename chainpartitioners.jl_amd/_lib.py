@@ -66,6 +66,8 @@ SIGNATURES = {
     "cp_adjoint": (_i32, [_vp, _pvp]),
     "cp_csr_download": (_i32, [_vp, _I64("dims_out"), _I64("colptr_out"), _I64("rowval_out")]),
     "cp_csr_reset_cache": (_i32, [_vp]),
+    "cp_rcm": (_i32, [_vp, _vp, _i32, _i32, _I64("rowprm_out"), _I64("colprm_out"), _I64("stats_out")]),
+    "cp_csr_permute": (_i32, [_vp, _I64("rowprm"), _I64("colprm"), _pvp]),
     "cp_count_build": (_i32, [_vp, _i32, _i32, _pvp]),
     "cp_count_query": (_i32, [_vp, _i64, _I64("a"), _I64("b"), _I64("out")]),
     "cp_count_destroy": (_i32, [_vp]),
@@ -238,14 +240,9 @@ class HipBackend:
     def csr_destroy(self, h):
         self.lib.cp_csr_destroy(h)
 
-    def adjoint(self, A):
-        """adjointpattern(A) on the device; the result's device handle stays registered, so a following
-        partition_stripe(adj_A, ...) needs no upload."""
+    def _adopt(self, t):
+        """the host mirror of a device handle the library made; the handle stays registered with it"""
         from .types import SparseMatrixCSC
-        t = C.c_void_p()
-        rc = self.lib.cp_adjoint(self._h(A), C.byref(t))
-        if rc != 0:
-            raise RuntimeError(f"cp_adjoint failed ({rc}): {self.last_error()}")
         dims = np.zeros(3, dtype=np.int64)
         self.lib.cp_csr_download(t, dims, None, None)
         m, n, N = (int(x) for x in dims)
@@ -257,6 +254,35 @@ class HipBackend:
         T = SparseMatrixCSC(m, n, colptr, rowval[:N])
         self._register(T, t)
         return T
+
+    def adjoint(self, A):
+        """adjointpattern(A) on the device; the result's device handle stays registered, so a following
+        partition_stripe(adj_A, ...) needs no upload."""
+        t = C.c_void_p()
+        rc = self.lib.cp_adjoint(self._h(A), C.byref(t))
+        if rc != 0:
+            raise RuntimeError(f"cp_adjoint failed ({rc}): {self.last_error()}")
+        return self._adopt(t)
+
+    RCM_STATS = ("path", "trees", "levels", "wide_levels", "walker_launches", "readbacks")
+
+    def rcm(self, A, adj_A, mode, reverse):
+        """(rc, rowprm, colprm, stats) of cp_rcm: mode 0 check symmetry / 1 assume it / 2 bipartite; stats["path"]: 1 the symmetric
+        walk (both vectors are the same), 2 the bipartite one"""
+        rowprm, colprm = np.zeros(A.m, dtype=np.int64), np.zeros(A.n, dtype=np.int64)
+        stats = np.zeros(6, dtype=np.int64)
+        rc = self.lib.cp_rcm(self._h(A), None if adj_A is None else self._h(adj_A), mode, 1 if reverse else 0, rowprm, colprm, stats)
+        return rc, rowprm, colprm, dict(zip(self.RCM_STATS, (int(v) for v in stats)))
+
+    def csr_permute(self, A, rowprm, colprm):
+        """A[rowprm, colprm] on the device (None: the identity) -> (rc, matrix that keeps its device handle | None)"""
+        t = C.c_void_p()
+        as64 = lambda p: None if p is None else np.ascontiguousarray(p, dtype=np.int64)
+        rowprm, colprm = as64(rowprm), as64(colprm)
+        if (rowprm is not None and rowprm.shape != (A.m,)) or (colprm is not None and colprm.shape != (A.n,)):
+            raise ValueError("permute: a permutation must have one entry per row / column")
+        rc = self.lib.cp_csr_permute(self._h(A), rowprm, colprm, C.byref(t))
+        return rc, (self._adopt(t) if rc == 0 else None)
 
     def reset_cache(self, A_or_handle):
         return self.lib.cp_csr_reset_cache(self._h(A_or_handle))

@@ -12,6 +12,7 @@ Reference entry points mirrored (under /root/reference/src):
                     BisectCostBottleneckSplitter.jl:6,70, ConvexTotalChunker.jl:26,170
   pack_stripe       EquiPartitioner.jl:15, DynamicChunker.jl:15,20, ConvexTotalChunker.jl:9,141, StrictChunker.jl:5, OverlapChunker.jl:6
   pack_plaid        AlternatingPacker.jl:18,40
+  permute_stripe / permute_plaid   Permutations.jl:33-41, CuthillMcKeePermuter.jl:209-265; PermutingPartitioner.jl:6-64
   oracle_stripe / bound_stripe / total_value / bottleneck_value   Costs.jl:3-66
 """
 from __future__ import annotations
@@ -21,7 +22,7 @@ from collections import namedtuple
 import numpy as np
 
 from . import models as M
-from .types import (SparseMatrixCSC, SplitPartition, MapPartition, DomainPartition, StepHint, NoHint, to_map)
+from .types import (SparseMatrixCSC, SplitPartition, MapPartition, DomainPartition, StepHint, NoHint, to_map, DomainPermutation, perm)
 
 _default_backend = None
 
@@ -190,6 +191,9 @@ def _dispatch(fn, table, head, method, Pi, backend, alloc):
 
 def partition_stripe(A: SparseMatrixCSC, K, method, Pi=None, *, backend=None) -> SplitPartition:
     K = int(K)
+    if isinstance(method, M.PermutingPartitioner):              # PermutingPartitioner.jl:18-34: Pi, a row partition, passes through
+        tau, B = _permuted_stripe(A, method, backend)
+        return tau[partition_stripe(B, K, method.prt, Pi, backend=backend)]
     if isinstance(method, M.EquiSplitter):
         # closed form, O(K) host arithmetic (EquiPartitioner.jl:7)
         n = A.n
@@ -273,6 +277,9 @@ def _pack_greedy(A, method, n_nets, backend):
 def pack_stripe(A: SparseMatrixCSC, method, Pi=None, *, n_nets=None, backend=None) -> SplitPartition:
     """n_nets: a one-element list standing for the reference's Ref (OverlapChunker.jl:6, :24-29); OverlapChunker leaves the int64
     array of the K parts' distinct-row counts in its element 0.  The other methods ignore it, as the reference's kwargs... do."""
+    if isinstance(method, M.PermutingPartitioner):              # PermutingPartitioner.jl:48-64
+        tau, B = _permuted_stripe(A, method, backend)
+        return tau[pack_stripe(B, method.prt, Pi, n_nets=n_nets, backend=backend)]
     if isinstance(method, M.EquiChunker):
         n, w = A.n, method.w
         spl = np.concatenate([np.arange(1, n + 1, w, dtype=np.int64), [n + 1]])   # [1:w:n; n+1]
@@ -417,6 +424,10 @@ def partition_plaid(A: SparseMatrixCSC, K, method, *, adj_A=None, backend=None):
     """partition_plaid(A, K, method) -> (Pi, Phi)  (AlternatingPartitioner.jl:6-87): the 2-D callers of partition_stripe.
     A and its adjoint both stay resident on the device between the sweeps."""
     K = int(K)
+    if isinstance(method, M.PermutingPartitioner):              # PermutingPartitioner.jl:6-16
+        sigma, tau, B = _permuted_plaid(A, method, adj_A, backend)
+        Pi, Phi = partition_plaid(B, K, method.prt, backend=backend)
+        return sigma[Pi], tau[Phi]
     if isinstance(method, M.DisjointPartitioner):
         Phi = partition_stripe(A, K, method.mtd, backend=backend)
         T = adj_A if adj_A is not None else adjointpattern(A, backend=backend)
@@ -448,6 +459,10 @@ def pack_plaid(A: SparseMatrixCSC, method, *, adj_A=None, backend=None):
     """pack_plaid(A, method) -> (Pi, Phi)  (AlternatingPacker.jl:18-32, :40-53): the 2-D callers of pack_stripe, host orchestration
     over adjointpattern and pack_stripe -- any pack_stripe method, on any backend that has it.  DisjointPacker goes through a
     PermutedDimsArray, for which the reference has no chunker method: not served."""
+    if isinstance(method, M.PermutingPartitioner):              # PermutingPartitioner.jl:36-46
+        sigma, tau, B = _permuted_plaid(A, method, adj_A, backend)
+        Pi, Phi = pack_plaid(B, method.prt, backend=backend)
+        return sigma[Pi], tau[Phi]
     if isinstance(method, M.AlternatingPacker):
         T = adj_A if adj_A is not None else adjointpattern(A, backend=backend)
         Phi = pack_stripe(A, method.mtds[0], backend=backend)
@@ -471,6 +486,58 @@ def adjointpattern(A: SparseMatrixCSC, *, backend=None) -> SparseMatrixCSC:
     """adjointpattern(A) (util.jl:67-95): transposed pattern, computed on the device (cp_adjoint); the returned matrix
     keeps its device handle, so partitioning it needs no upload."""
     return get_backend(backend).adjoint(A)
+
+
+# ---------------------------------------------------------------- reordering
+def permute_plaid(A: SparseMatrixCSC, method, adj_A=None, *, backend=None):
+    """permute_plaid(A, method; adj_A) -> (sigma, tau), the row and the column permutation.  IdentityPermuter (Permutations.jl:38-41)
+    is host arithmetic; CuthillMcKeePermuter (CuthillMcKeePermuter.jl:221-265) is the device walk of csrc/rcm.hip.  On its symmetric
+    path sigma and tau are ONE object, as the reference returns one vector twice (test_CuthillMcKee.jl:28).  The counters of the
+    call (cp_rcm's stats_out, by name) are left in backend.last_rcm_stats."""
+    if isinstance(method, M.IdentityPermuter):
+        return (DomainPermutation(np.arange(1, A.m + 1, dtype=np.int64)), DomainPermutation(np.arange(1, A.n + 1, dtype=np.int64)))
+    if not isinstance(method, M.CuthillMcKeePermuter):
+        raise NotImplementedError(f"permute_plaid: method {type(method).__name__} is outside the hot path")
+    b = get_backend(backend)
+    if not hasattr(b, "rcm"):
+        raise NotImplementedError(f"CuthillMcKeePermuter is implemented by the HIP backend only, not by backend "
+                                  f"'{getattr(b, 'name', type(b).__name__)}'")
+    mode = 1 if method.assumesymmetry else 0 if method.checksymmetry else 2
+    rc, rowprm, colprm, stats = b.rcm(A, adj_A, mode, method.reverse)
+    _check(rc, "permute_plaid(CuthillMcKeePermuter)", b)
+    b.last_rcm_stats = stats
+    if stats["path"] == 1:
+        sigma = DomainPermutation(colprm)
+        return sigma, sigma
+    return DomainPermutation(rowprm), DomainPermutation(colprm)
+
+
+def permute_stripe(A: SparseMatrixCSC, method, *, backend=None):
+    """permute_stripe(A, method) (Permutations.jl:33-36, CuthillMcKeePermuter.jl:209-211): the column half of permute_plaid"""
+    return permute_plaid(A, method, backend=backend)[-1]
+
+
+def permute(A: SparseMatrixCSC, sigma=None, tau=None, *, backend=None) -> SparseMatrixCSC:
+    """A[perm(sigma), perm(tau)] on the device (cp_csr_permute; None: that side stays); the returned matrix keeps its device handle,
+    like adjointpattern's."""
+    b = get_backend(backend)
+    if not hasattr(b, "csr_permute"):
+        raise NotImplementedError(f"permute is implemented by the HIP backend only, not by backend '{getattr(b, 'name', type(b).__name__)}'")
+    rc, B = b.csr_permute(A, None if sigma is None else perm(sigma), None if tau is None else perm(tau))
+    _check(rc, "permute", b)
+    return B
+
+
+def _permuted_stripe(A, method, backend):
+    tau = permute_stripe(A, method.prm, backend=backend)
+    return tau, permute(A, None, tau, backend=backend)
+
+
+def _permuted_plaid(A, method, adj_A, backend):
+    """The reference hands the UNPERMUTED adj_A on to the inner call on B (PermutingPartitioner.jl:13, :43); here the inner call
+    takes the adjoint of B."""
+    sigma, tau = permute_plaid(A, method.prm, adj_A, backend=backend)
+    return sigma, tau, permute(A, sigma, tau, backend=backend)
 
 
 # ---------------------------------------------------------------- counting structures

@@ -57,5 +57,6 @@ void ensure_self(cp_csr_s *A);
 void drop_cache(cp_csr_s *A);
 void csr_adjoint(cp_csr_s *A, cp_csr_s *T);                                 // T: fresh handle (device / stream set by the caller)
 void csr_download(cp_csr_s *A, int64_t *colptr, int64_t *rowval);
+extern int64_t g_opt_rcm_narrow;                                            // rcm.hip: levels of at most this many vertices go to the walker
 __global__ void k_narrow(const int64_t *__restrict__ in, int32_t *__restrict__ out, int64_t n);      // core.hip: out[i] = (int32_t)in[i]
 }  // namespace cpk

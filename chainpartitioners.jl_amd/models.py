@@ -583,3 +583,23 @@ class ConcaveTotalChunker(_FMethod):
 
 class ConcaveTotalSplitter(_FMethod):
     """ConcaveTotalChunker.jl:5-55, :140-180"""
+
+
+# ---------------------------------------------------------------- reordering (Permutations.jl:31, CuthillMcKeePermuter.jl:1-5,199, PermutingPartitioner.jl:1-4)
+class IdentityPermuter:
+    pass
+
+
+class CuthillMcKeePermuter:
+    """reverse: the queue backwards; assumesymmetry: walk the columns of a square pattern as they are; checksymmetry: walk them if
+    the pattern equals its adjoint, else the bipartite graph of rows and columns"""
+
+    def __init__(self, reverse=False, assumesymmetry=False, checksymmetry=True):
+        self.reverse, self.assumesymmetry, self.checksymmetry = bool(reverse), bool(assumesymmetry), bool(checksymmetry)
+
+
+class PermutingPartitioner:
+    """order with prm, permute, partition with prt, map the partition back"""
+
+    def __init__(self, prm, prt):
+        self.prm, self.prt = prm, prt

@@ -6,6 +6,7 @@ as Julia stores them, so split vectors compare element-for-element):
   SparseMatrixCSC (pattern only; nzval is never read on the path)
   SplitPartition / DomainPartition / MapPartition      /root/reference/src/Partitions.jl:1-84
   NoHint / RandomHint / SparseHint / StepHint          /root/reference/src/ChainPartitioners.jl:172-176
+  DomainPermutation / MapPermutation / perm, sigma[Pi]  src/Permutations.jl:1-53
 """
 from __future__ import annotations
 
@@ -14,6 +15,7 @@ import numpy as np
 __all__ = [
     "SparseMatrixCSC", "SplitPartition", "DomainPartition", "MapPartition",
     "NoHint", "RandomHint", "SparseHint", "StepHint",
+    "DomainPermutation", "MapPermutation", "perm", "invperm",
 ]
 
 
@@ -158,3 +160,71 @@ def to_domain(P) -> DomainPartition:
         prm = np.argsort(P.asg, kind="stable").astype(np.int64) + 1
         return DomainPartition(P.K, prm, spl)
     raise TypeError(type(P))
+
+
+# ---------------------------------------------------------------- permutations (Permutations.jl:1-53)
+def invperm(p):
+    """Julia's invperm on a 1-based vector: q[p[i]] = i; ValueError unless p is a permutation of 1 .. len(p)"""
+    p = np.ascontiguousarray(p, dtype=np.int64)
+    n = p.size
+    if n and (p.min() < 1 or p.max() > n or np.bincount(p - 1, minlength=n).max() > 1):
+        raise ValueError("argument is not a permutation")
+    q = np.empty(n, dtype=np.int64)
+    q[p - 1] = np.arange(1, n + 1, dtype=np.int64)
+    return q
+
+
+class _Permutation:
+    """sigma[Pi] (Permutations.jl:43-53): the partition Pi of the permuted indices, told in the original ones."""
+
+    def __getitem__(self, P):
+        if isinstance(P, SplitPartition):
+            return DomainPartition(P.K, np.arange(1, P.spl[-1], dtype=np.int64)[perm(self) - 1], P.spl)
+        if isinstance(P, DomainPartition):
+            return DomainPartition(P.K, P.prm[perm(self) - 1], P.spl)
+        if isinstance(P, MapPartition):
+            return MapPartition(P.K, P.asg[to_map_permutation(self).asg - 1])
+        raise TypeError(type(P))
+
+
+class DomainPermutation(_Permutation):
+    """position i' of the permuted order holds the original index prm[i']"""
+    __slots__ = ("prm",)
+
+    def __init__(self, prm):
+        self.prm = np.ascontiguousarray(prm, dtype=np.int64)
+
+    def __eq__(self, other):
+        return isinstance(other, DomainPermutation) and np.array_equal(self.prm, other.prm)
+
+    def __repr__(self):
+        return f"DomainPermutation({self.prm.tolist()})"
+
+
+class MapPermutation(_Permutation):
+    """the original index i goes to position asg[i]"""
+    __slots__ = ("asg",)
+
+    def __init__(self, asg):
+        self.asg = np.ascontiguousarray(asg, dtype=np.int64)
+
+    def __eq__(self, other):
+        return isinstance(other, MapPermutation) and np.array_equal(self.asg, other.asg)
+
+    def __repr__(self):
+        return f"MapPermutation({self.asg.tolist()})"
+
+
+def to_domain_permutation(s) -> DomainPermutation:
+    """convert(DomainPermutation, s)  Permutations.jl:19-21"""
+    return s if isinstance(s, DomainPermutation) else DomainPermutation(invperm(s.asg))
+
+
+def to_map_permutation(s) -> MapPermutation:
+    """convert(MapPermutation, s)  Permutations.jl:23-25"""
+    return s if isinstance(s, MapPermutation) else MapPermutation(invperm(s.prm))
+
+
+def perm(s):
+    """perm(s) (Permutations.jl:27-29): the vector prm with permuted[i'] = original[prm[i']]"""
+    return to_domain_permutation(s).prm

@@ -49,6 +49,21 @@ int32_t cp_csr_download(cp_csr_t csr, int64_t *dims_out, int64_t *colptr_out, in
 /* drop cached derived structures (link arrays, counters) so the next call rebuilds them:
  * lets a benchmark time "one partition_stripe call including oracle construction" */
 int32_t cp_csr_reset_cache(cp_csr_t csr);
+/* permute_plaid(A, CuthillMcKeePermuter(reverse, assumesymmetry, checksymmetry); adj_A)  CuthillMcKeePermuter.jl:7-265: the exact
+ * queue of the reference's symrcm / rctrcm, built on the device level by level (csrc/rcm.hip).  mode 0: the symmetric walk if the
+ * pattern is square and equal to its adjoint, else the bipartite walk over the m + n rows and columns; 1: the symmetric walk without
+ * the test (assumesymmetry; m != n is CP_EINVAL -- the reference would read out of bounds); 2: the bipartite walk.  adj: a handle of
+ * the adjoint if the caller holds one (shape checked, CP_EINVAL), else NULL.  rowprm_out (m) / colprm_out (n): perm(sigma), perm(tau),
+ * 1-based; on the symmetric walk both receive the same vector.  reverse != 0: each reversed.  The bipartite walk keeps 32-bit ids:
+ * m + n or 2 nnz at 2^31 or beyond is CP_EUNSUPPORTED.  A pattern whose columns hold an index twice is refused with CP_EINVAL when
+ * the queue would overflow.  stats_out: NULL or 6 values {1 symmetric / 2 bipartite walk, trees, levels expanded, of them by grid
+ * kernels, launches of the one-workgroup walker, readbacks}; see the option "rcm_narrow". */
+int32_t cp_rcm(cp_csr_t csr, cp_csr_t adj_or_null, int32_t mode, int32_t reverse, int64_t *rowprm_out /* m */, int64_t *colprm_out /* n */,
+               int64_t *stats_out /* 6 or NULL */);
+/* A[rowprm, colprm] (PermutingPartitioner.jl:12, :21): out[i', j'] = A[rowprm[i'], colprm[j']] as a NEW device-resident handle, the
+ * rows of every column ascending.  rowprm (m) / colprm (n): 1-based host arrays, NULL for the identity; each is checked on the device
+ * to be a permutation (CP_EINVAL, nothing is read out of range). */
+int32_t cp_csr_permute(cp_csr_t csr, const int64_t *rowprm /* m or NULL */, const int64_t *colprm /* n or NULL */, cp_csr_t *out);
 
 /* ---- counting structures ----
  * dominancecount(hint, A)   SparsePrefixMatrices.jl:438-458   kind CP_COUNT_DOM : C[i,j]
@@ -347,7 +362,9 @@ int32_t cp_test_own_pack(cp_csr_t csr, int32_t *vpk_out, int32_t *vbase_out, int
  * after one that reproduced its input row are copied), "bn_wave" (bottleneck DP walk: 0 lane per chunk of "bn_chunk" rows, 1 wave
  * per run of "bn_run" rows in lockstep, 2 = default: searched crossings for Int64 costs), "bn_slack" (columns of the start bracket), "lws" (1,
  * default: cp_pack_dynamic past the scan -- any width, a monotone work budget, no constraint -- runs the on-line divide and conquer of
- * csrc/chunk_lws.hip; 0: the one-wave kernel), "lws_leaf" (its rows per leaf wave: 256, 512, 1024 or 2048), "prof_only" slot (events on one profile slot only), "dbg"
+ * csrc/chunk_lws.hip; 0: the one-wave kernel), "lws_leaf" (its rows per leaf wave: 256, 512, 1024 or 2048), "rcm_narrow" (cp_rcm: BFS levels of at most this many
+ * vertices are walked by one workgroup, level after level in one launch; 0: every level by grid kernels; a value beyond the walker's
+ * capacity of 1024 vertices: whenever the level fits), "prof_only" slot (events on one profile slot only), "dbg"
  * (diagnostic bit mask: the bits are named in csrc/dp.hpp, enum DbgBit, and tabulated in DESIGN.md section 4e).  Unknown names
  * return CP_EINVAL. */
 int32_t cp_set_option(const char *name, int64_t value);
