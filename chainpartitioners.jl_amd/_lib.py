@@ -102,6 +102,9 @@ SIGNATURES = {
     "cp_partition_convex": _SPLIT,
     "cp_pack_strict": (_i32, [_vp, _i64, _I64("spl_out"), _I64("K_out")]),
     "cp_pack_overlap": (_i32, [_vp, _f64, _i64, _I64("spl_out"), _I64("K_out"), _I64("n_nets_out")]),
+    "cp_partition_magnetic": (_i32, [_vp, _i64, _ROWPART, _i64, _I64("draws"), _I64("asg_out")]),
+    "cp_partition_greedy_bottleneck": (_i32, [_vp, _i64, _MODEL, _ROWPART, _i64, _I64("order"), _I64("asg_out"), _I64("order_out"),
+                                              _I64("cst_i64"), _F64("cst_f64")]),
     "cp_partition_equi": (_i32, [_i64, _i64, _I64("spl_out")]),
     "cp_pack_equi": (_i32, [_i64, _i64, _I64("spl_out"), _I64("K_out")]),
     "cp_dynamic_tables": (_i32, [_vp, _i64, _i32, _MODEL, _ROWPART, _I64("ptr_out"), _I64("cst_i64"), _F64("cst_f64")]),
@@ -444,6 +447,17 @@ class HipBackend:
     def pack_overlap(self, A, rho, w_max, spl, Kout, n_nets=None):
         """n_nets: None or an int64 array of n slots; the first K receive the distinct-row count of every part"""
         return self.lib.cp_pack_overlap(self._h(A), float(rho), int(w_max), spl, Kout, n_nets)
+
+    def partition_magnetic(self, A, K, rp, seed, draws, asg):
+        """MagneticPartitioner: draws None (the device draws draw(seed, 1, j)) or n int64 values; asg: n slots"""
+        return self.lib.cp_partition_magnetic(self._h(A), K, rp, seed, draws, asg)
+
+    def partition_greedy_bottleneck(self, A, K, mm, rp, seed, order, asg):
+        """GreedyBottleneckPartitioner: order None (the device sorts the keys draw(seed, 2, j)) or a permutation of 1 .. n;
+        -> (rc, the order that was walked, the K final part costs in the model's element type)"""
+        order_out, cst = np.zeros(A.n, dtype=np.int64), _cost_zeros(mm, K)
+        rc = self.lib.cp_partition_greedy_bottleneck(self._h(A), K, mm, rp, seed, order, asg, order_out, *_by_type(cst))
+        return rc, order_out, cst
 
     # ---- oracles / scoring
     def oracle_eval(self, A, mm, rp, hint, j, jp, k, out):

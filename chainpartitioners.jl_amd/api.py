@@ -9,7 +9,7 @@ the same `backend=` hook to compare the two on identical marshalled inputs.
 
 Reference entry points mirrored (under /root/reference/src):
   partition_stripe  EquiPartitioner.jl:5, DynamicSplitter.jl:15,52,206,260,
-                    BisectCostBottleneckSplitter.jl:6,70, ConvexTotalChunker.jl:26,170
+                    BisectCostBottleneckSplitter.jl:6,70, ConvexTotalChunker.jl:26,170, MagneticPartitioner.jl:3,26,96
   pack_stripe       EquiPartitioner.jl:15, DynamicChunker.jl:15,20, ConvexTotalChunker.jl:9,141, StrictChunker.jl:5, OverlapChunker.jl:6
   pack_plaid        AlternatingPacker.jl:18,40
   permute_stripe / permute_plaid   Permutations.jl:33-41, CuthillMcKeePermuter.jl:209-265; PermutingPartitioner.jl:6-64
@@ -22,7 +22,7 @@ from collections import namedtuple
 import numpy as np
 
 from . import models as M
-from .types import (SparseMatrixCSC, SplitPartition, MapPartition, DomainPartition, StepHint, NoHint, to_map, DomainPermutation, perm)
+from .types import (SparseMatrixCSC, SplitPartition, MapPartition, DomainPartition, StepHint, NoHint, to_map, to_domain, DomainPermutation, perm)
 
 _default_backend = None
 
@@ -72,13 +72,13 @@ def _rowpart(Pi, need_spl=False):
         keep += [spl, asg]
         rp.spl = spl.ctypes.data
         rp.asg = asg.ctypes.data
-    elif isinstance(Pi, MapPartition):
-        asg = np.ascontiguousarray(Pi.asg, dtype=np.int64)
+    elif isinstance(Pi, (MapPartition, DomainPartition)):          # a DomainPartition goes as its map (Partitions.jl:62-84)
+        asg = np.ascontiguousarray(to_map(Pi).asg, dtype=np.int64)
         keep += [asg]
         rp.asg = asg.ctypes.data
         rp.spl = None
     else:
-        raise TypeError("row partition must be a SplitPartition or MapPartition")
+        raise TypeError("row partition must be a SplitPartition, MapPartition or DomainPartition")
     return rp, keep
 
 
@@ -189,11 +189,45 @@ def _dispatch(fn, table, head, method, Pi, backend, alloc):
     return outs
 
 
-def partition_stripe(A: SparseMatrixCSC, K, method, Pi=None, *, backend=None) -> SplitPartition:
+def _partition_map(A, K, method, Pi, backend):
+    """MagneticPartitioner / GreedyBottleneckPartitioner (MagneticPartitioner.jl:3-20, :26-177): the two methods that return a
+    MapPartition.  Both need the row partition Pi (any kind, of the m rows); the draws are the method's own fields."""
+    b = get_backend(backend)
+    name = type(method).__name__
+    greedy = isinstance(method, M.GreedyBottleneckPartitioner)
+    if greedy and not isinstance(method.mdl, M.AffineSecondaryConnectivityModel):
+        raise NotImplementedError(f"{name}({type(method.mdl).__name__}): the reference has a method for an AffineSecondaryConnectivityModel only")
+    if Pi is None:
+        raise NotImplementedError(f"partition_stripe(A, K, {name}) without a row partition Pi has no method in the reference")
+    call = "partition_greedy_bottleneck" if greedy else "partition_magnetic"
+    if not hasattr(b, call):
+        raise NotImplementedError(f"{name} is implemented by the HIP backend only, not by backend '{getattr(b, 'name', type(b).__name__)}'")
+    rp, keep = _rowpart(Pi)
+    if keep[-1].shape != (A.m,):                                # (keep[-1]: the map form of Pi)
+        raise AssertionError(f"partition_stripe({name}): Pi must assign the {A.m} rows of A, it has {keep[-1].size} entries")
+    given = method.order if greedy else method.draws
+    if given is not None and given.shape != (A.n,):
+        raise AssertionError(f"partition_stripe({name}): {'order' if greedy else 'draws'} must have one entry per column")
+    asg = np.zeros(A.n, dtype=np.int64)
+    if greedy:
+        rc, order, cst = b.partition_greedy_bottleneck(A, K, method.mdl.marshal(), rp, method.seed, given, asg)
+        b.last_greedy = {"order": order, "cst": cst}             # the order that was walked and the K final part costs
+    else:
+        rc = b.partition_magnetic(A, K, rp, method.seed, given, asg)
+    _check(rc, f"partition_stripe({name})", b)
+    return MapPartition(K, asg)
+
+
+def partition_stripe(A: SparseMatrixCSC, K, method, Pi=None, *, backend=None, adj_A=None, adj_net=None):
+    """-> SplitPartition, or MapPartition from the map partitioners (DomainPartition through a PermutingPartitioner).  adj_A /
+    adj_net: the reference's keywords of GreedyBottleneckPartitioner (MagneticPartitioner.jl:26, :96), accepted and ignored -- the
+    device setup counts the parts of Pi from A's own columns and needs neither the adjoint nor its net counter."""
     K = int(K)
     if isinstance(method, M.PermutingPartitioner):              # PermutingPartitioner.jl:18-34: Pi, a row partition, passes through
         tau, B = _permuted_stripe(A, method, backend)
         return tau[partition_stripe(B, K, method.prt, Pi, backend=backend)]
+    if isinstance(method, (M.MagneticPartitioner, M.GreedyBottleneckPartitioner)):
+        return _partition_map(A, K, method, Pi, backend)
     if isinstance(method, M.EquiSplitter):
         # closed form, O(K) host arithmetic (EquiPartitioner.jl:7)
         n = A.n
@@ -401,8 +435,16 @@ def bound_stripe(A, K, mdl, Pi=None, *, backend=None):
 
 def _objective(g, A, Phi, mdl, Pi, backend):
     b = get_backend(backend)
+    if isinstance(Phi, (MapPartition, DomainPartition)):
+        # compute_objective for any Phi (Costs.jl:34-39, :52-57): gather the parts' columns together on the device and score the
+        # split of the gathered matrix; Pi, a partition of the rows, passes through.  The symmetric family has one partition for
+        # rows and columns, so both sides are permuted (the reference would permute the columns only: DESIGN.md section 5f).
+        dom = to_domain(Phi)
+        prm = DomainPermutation(dom.prm)
+        A_prm = permute(A, prm if getattr(mdl, "symmetric", False) else None, prm, backend=b)
+        return _objective(g, A_prm, SplitPartition(dom.K, dom.spl), mdl, Pi, b)
     if not isinstance(Phi, SplitPartition):
-        raise NotImplementedError("scoring of non-contiguous partitions is outside the hot path")
+        raise TypeError("Phi must be a SplitPartition, MapPartition or DomainPartition")
     _need_hip(b, mdl)
     _, mm, _, _, _, rp, keep = _marshal(A, mdl, Pi)
     rc, v = b.objective(A, Phi.K, np.ascontiguousarray(Phi.spl, dtype=np.int64), mm, rp, g)

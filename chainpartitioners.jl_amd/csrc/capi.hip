@@ -177,6 +177,7 @@ static const struct Opt { const char *name; int64_t *var; OptRule rule; int64_t 
     {"gap_split", &g_opt_gap_split, OPT_BOOL, 0, 0},            // (1, default: so do the gap rounds' tiles of those planes -- while own_split is 1; 0: they stream the whole columns)
     {"lws", &g_opt_lws, OPT_BOOL, 0, 0},                        // (1, default: DynamicTotalChunker past the scan by chunk_lws.hip; 0: the one-wave kernel)
     {"rcm_narrow", &g_opt_rcm_narrow, OPT_CLAMP, 0, NOLIM_HI},  // (cp_rcm: BFS levels of at most this many vertices go to the one-workgroup walker; 0: never; beyond its capacity: whenever the level fits)
+    {"greedy_lds_parts", &g_opt_greedy_lds_parts, OPT_CLAMP, 0, 2048},      // (cp_partition_greedy_bottleneck: the walk keeps the part costs and counts in LDS while K <= this; 0: always in global memory)
     {"gap_tau", &g_opt_gap_tau, OPT_CLAMP, NOLIM_LO, 20}, {"gap_min", &g_opt_gap_min, OPT_CLAMP, 8, NOLIM_HI}, {"gap_nr", &g_opt_gap_nr, OPT_CLAMP, 1, 2},
     {"force_max", &g_opt_force_max, OPT_CLAMP, 0, NOLIM_HI}, {"rpass_cap", &g_opt_rpass_cap, OPT_CLAMP, 1, NOLIM_HI},
     {"own_min", &g_opt_own_min, OPT_CLAMP, 64, NOLIM_HI}, {"bn_chunk", &g_opt_bn_chunk, OPT_CLAMP, 1, NOLIM_HI},

@@ -59,4 +59,7 @@ void csr_adjoint(cp_csr_s *A, cp_csr_s *T);                                 // T
 void csr_download(cp_csr_s *A, int64_t *colptr, int64_t *rowval);
 extern int64_t g_opt_rcm_narrow;                                            // rcm.hip: levels of at most this many vertices go to the walker
 __global__ void k_narrow(const int64_t *__restrict__ in, int32_t *__restrict__ out, int64_t n);      // core.hip: out[i] = (int32_t)in[i]
+// rcm.hip: prm 1-based int64 -> out 0-based int32; *bad is raised unless every value of 1 .. len occurs once (mark: len zeroed words)
+__global__ void k_perm_check(const int64_t *__restrict__ prm, int32_t *__restrict__ out, int32_t *mark, int64_t len, int32_t *__restrict__ bad);
+extern int64_t g_opt_greedy_lds_parts;                                      // map_part.hip: the greedy walk keeps its state in LDS while K <= this
 }  // namespace cpk

@@ -522,6 +522,30 @@ class LazyFlipBisectCostBottleneckSplitter:
         self.f, self.eps = f, float(eps)
 
 
+class MagneticPartitioner:
+    """MagneticPartitioner.jl:1-20: partition_stripe(A, K, method, Pi) -> MapPartition; column j with d entries takes the part of
+    the row of its entry number u_j mod d, a column without entries the part 1 + u_j mod K.  draws: the n values u_j >= 0 that
+    stand for the reference's rand calls; None: u_j = draws.draw(seed, 1, j), computed on the device."""
+
+    def __init__(self, seed=0, draws=None):
+        self.seed = int(seed)
+        self.draws = None if draws is None else np.ascontiguousarray(draws, dtype=np.int64)
+
+
+class GreedyBottleneckPartitioner:
+    """MagneticPartitioner.jl:22-177: partition_stripe(A, K, method, Pi) -> MapPartition; the columns are visited in `order` and
+    each takes the part of largest current cost among its rows' parts, whose cost then falls.  mdl: an
+    AffineSecondaryConnectivityModel (the reference has no method for another model).  order: a permutation of 1 .. n (an int64
+    array or a DomainPermutation) that stands for the reference's randperm(n); None: the columns ascending by
+    (draws.draw(seed, 2, j), j), sorted on the device."""
+
+    def __init__(self, mdl, seed=0, order=None):
+        self.mdl, self.seed = mdl, int(seed)
+        if order is not None and hasattr(order, "prm"):
+            order = order.prm
+        self.order = None if order is None else np.ascontiguousarray(order, dtype=np.int64)
+
+
 class DisjointPartitioner:
     """AlternatingPartitioner.jl:1-10: columns first, then the rows of the adjoint given the column split."""
 

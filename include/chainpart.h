@@ -231,6 +231,26 @@ int32_t cp_pack_strict(cp_csr_t csr, int64_t w_max, int64_t *spl_out /* n+1 */, 
  * n < 1 is CP_EINVAL.  The work is sum_j (next[j] - j) column intersections, at most n * w_max; without a width limit a run of L
  * mutually overlapping columns costs about L^2 / 2 (cp_get_stat "overlap_isect" counts them). */
 int32_t cp_pack_overlap(cp_csr_t csr, double rho, int64_t w_max, int64_t *spl_out /* n+1 */, int64_t *K_out, int64_t *n_nets_out /* n or NULL */);
+/* partition_stripe(A, K, MagneticPartitioner(), Pi)  MagneticPartitioner.jl:3-20: column j with d entries takes the part of the row
+ * of its entry number u_j mod d (0-based), a column without entries the part 1 + u_j mod K.  The reference draws u_j from Julia's
+ * global RNG; here draws (n values, each >= 0) are an input, or NULL: u_j = draw(seed, 1, j), the SplitMix64 counter hash of
+ * csrc/map_part.hip shifted right by one bit.  Pi (asg, m entries, or spl): any partition of the rows, required; its values are
+ * checked on the device to lie in 1 .. Pi->K and the draws to be non-negative (CP_EINVAL, nothing is read out of range).
+ * asg_out: the n entries of MapPartition(K, asg). */
+int32_t cp_partition_magnetic(cp_csr_t csr, int64_t K, const cp_rowpart_t *Pi, int64_t seed, const int64_t *draws /* n or NULL */,
+                              int64_t *asg_out /* n */);
+/* partition_stripe(A, K, GreedyBottleneckPartitioner(mdl), Pi)  MagneticPartitioner.jl:26-177 (both methods: they compute the same
+ * numbers), mdl a CP_MODEL_SECONDARY model of either element type, per-part alpha included; any other kind is CP_EUNSUPPORTED.
+ * The columns are visited in `order` (a permutation of 1 .. n standing for the reference's randperm(n)), or with NULL in ascending
+ * (draw(seed, 2, j), j).  A column takes the part of largest current cost among the parts of its rows -- the first such entry in
+ * column order -- and part 1 if it has no entries; the chosen part gains a local net, loses a remote one and its cost is recomputed
+ * from its four counts.  The counts of the parts come from A's own columns: no adjoint is needed.  Preconditions, all checked on the
+ * device before the walk (CP_EINVAL, nothing is read out of range): Pi->K == K, every Pi value in 1 .. K, order a permutation.
+ * asg_out: n entries; order_out: NULL or n entries, the order that was walked; cst_i64 / cst_f64 (K, either may be NULL): the final
+ * part costs in the one of the model's element type.  The walk is one wave; see the option "greedy_lds_parts". */
+int32_t cp_partition_greedy_bottleneck(cp_csr_t csr, int64_t K, const cp_model_t *model, const cp_rowpart_t *Pi, int64_t seed,
+                                       const int64_t *order /* n or NULL */, int64_t *asg_out /* n */, int64_t *order_out /* n or NULL */,
+                                       int64_t *cst_i64 /* K */, double *cst_f64 /* K */);
 /* EquiSplitter / EquiChunker  EquiPartitioner.jl:3-22 (closed forms, host arithmetic) */
 int32_t cp_partition_equi(int64_t n, int64_t K, int64_t *spl_out /* K+1 */);
 int32_t cp_pack_equi(int64_t n, int64_t w, int64_t *spl_out /* cld(n,w)+1 */, int64_t *K_out);
@@ -364,7 +384,8 @@ int32_t cp_test_own_pack(cp_csr_t csr, int32_t *vpk_out, int32_t *vbase_out, int
  * default: cp_pack_dynamic past the scan -- any width, a monotone work budget, no constraint -- runs the on-line divide and conquer of
  * csrc/chunk_lws.hip; 0: the one-wave kernel), "lws_leaf" (its rows per leaf wave: 256, 512, 1024 or 2048), "rcm_narrow" (cp_rcm: BFS levels of at most this many
  * vertices are walked by one workgroup, level after level in one launch; 0: every level by grid kernels; a value beyond the walker's
- * capacity of 1024 vertices: whenever the level fits), "prof_only" slot (events on one profile slot only), "dbg"
+ * capacity of 1024 vertices: whenever the level fits), "greedy_lds_parts" (cp_partition_greedy_bottleneck: the walk keeps the part costs and counts in
+ * LDS while K is at most this, default and largest value 2048; 0: always in global memory), "prof_only" slot (events on one profile slot only), "dbg"
  * (diagnostic bit mask: the bits are named in csrc/dp.hpp, enum DbgBit, and tabulated in DESIGN.md section 4e).  Unknown names
  * return CP_EINVAL. */
 int32_t cp_set_option(const char *name, int64_t value);
