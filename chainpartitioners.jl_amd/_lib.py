@@ -125,6 +125,8 @@ SIGNATURES = {
     "cp_get_stat": (_i32, [_str, _pi64]),
     "cp_test_round_scans": (_i32, [_I32("a"), _i64, _i64, _I32("b"), _i64, _i64, _i32, _i64, _i64, _i32, _i32,
                                    _I64("offs_out"), _I64("toffs_out"), _I64("res")]),
+    "cp_test_list_alloc": (_i32, [_I32("a"), _i64, _I32("b"), _i64, _i32, _i64, _i64, _i64, _i32, _i32, _i64, _i64, _i64,
+                                  _I64("offs_out"), _I32("slot_a"), _I64("toffs_out"), _I32("slot_b"), _I32("ioffs_out"), _I64("res")]),
     "cp_test_fix_merge": (_i32, [_MODEL, _i64, _I64("toffs"), _I64("part_v"), _I32("part_p"), _I32("part_nn"), _I32("part_nl"), _I32("tile_s"),
                                  _I32("tile_s2"), _I32("anchor"), _I32("anchor2"), _I32("row"), _I32("plane"), _i64, _i32, _I32("p_out"),
                                  _I32("nn_out"), _I32("nl_out"), _I64("res")]),
@@ -139,7 +141,7 @@ SIGNATURES = {
 SYMBOLS = list(SIGNATURES)
 # test entries a library of an earlier build may lack when it is loaded through CP_LIB_PATH for an A/B run (tools/ab_libs.sh): the
 # call, not the load, fails there
-OPTIONAL = {"cp_test_own_pack"}
+OPTIONAL = {"cp_test_own_pack", "cp_test_list_alloc"}
 
 _lib = None
 

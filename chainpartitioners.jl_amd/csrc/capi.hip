@@ -156,6 +156,8 @@ static const struct { const char *name; int64_t *var; bool kept; } g_stats[] = {
     {"own_pair_waves", &g_own_pair_waves, false}, {"own_pair_lone", &g_own_pair_lone, false},
     {"own_pack_tiles", &g_own_pack_tiles, false}, {"own_pack_wide", &g_own_pack_wide, false},
     {"overlap_isect", &g_overlap_isect, false}, {"cut_scan_layers", &g_cut_scan_layers, false},
+    {"cr_consume_rounds", &g_cr_consume_rounds, false}, {"cr_clear_launches", &g_cr_clear_launches, false},
+    {"round_alloc_rounds", &g_round_alloc_rounds, false},
 };
 static void stats_reset(bool all) { for (const auto &c : g_stats) if (all || !c.kept) *c.var = 0; }
 
@@ -174,6 +176,8 @@ static const struct Opt { const char *name; int64_t *var; OptRule rule; int64_t 
     {"own_split", &g_opt_own_split, OPT_BOOL, 0, 0},            // (1, default: own tiles of the planes >= 8 stream only the plane's variable link entries; 0: the whole columns)
     {"own_pair", &g_opt_own_pair, OPT_BOOL, 0, 0},              // (1, default: outside the gap rounds and the hyperedge costs a wave streams two own tiles; 0: one)
     {"own_pack", &g_opt_own_pack, OPT_BOOL, 0, 0},              // (1, default: split tiles read one packed word per step -- while own_split and own_blk are 1 and the pattern's offsets fit; 0: the wide arrays)
+    {"round_alloc", &g_opt_round_alloc, OPT_BOOL, 0, 0},        // (1, default: task set-up reserves its lists' offsets with their slots and ends with the round's verdict; 0: the scan launch k_round_scans)
+    {"cr_consume", &g_opt_cr_consume, OPT_BOOL, 0, 0},          // (1, default: full layers leave the right-pass counters zero as set-up reads them, no clearing launch per round; 0: the clear in front of every chunked right pass)
     {"gap_split", &g_opt_gap_split, OPT_BOOL, 0, 0},            // (1, default: so do the gap rounds' tiles of those planes -- while own_split is 1; 0: they stream the whole columns)
     {"lws", &g_opt_lws, OPT_BOOL, 0, 0},                        // (1, default: DynamicTotalChunker past the scan by chunk_lws.hip; 0: the one-wave kernel)
     {"rcm_narrow", &g_opt_rcm_narrow, OPT_CLAMP, 0, NOLIM_HI},  // (cp_rcm: BFS levels of at most this many vertices go to the one-workgroup walker; 0: never; beyond its capacity: whenever the level fits)
@@ -306,6 +310,17 @@ int32_t cp_test_round_scans(const int32_t *a, int64_t na, int64_t na_max, const 
     if (!offs_out || !toffs_out || !res || (na > 0 && !a) || (nb > 0 && !b)) return CP_EINVAL;
     return guarded([&]() -> int32_t {
         dp_round_scans_test(a, na, na_max, b, nb, nb_max, two, cap_t, cap_nt, err_in, reps, offs_out, toffs_out, res);
+        return CP_OK;
+    });
+}
+
+int32_t cp_test_list_alloc(const int32_t *a, int64_t na, const int32_t *b, int64_t nb, int32_t bs, int64_t cap_t, int64_t cap_nt, int64_t o_cap,
+                           int32_t err_in, int32_t reps, int64_t fit_ntask, int64_t fit_n, int64_t fit_own_min, int64_t *offs_out, int32_t *slot_a,
+                           int64_t *toffs_out, int32_t *slot_b, int32_t *ioffs_out, int64_t *res)
+{
+    if (!offs_out || !toffs_out || !slot_a || !slot_b || !ioffs_out || !res || (na > 0 && !a) || (nb > 0 && !b)) return CP_EINVAL;
+    return guarded([&]() -> int32_t {
+        dp_list_alloc_test(a, na, b, nb, bs, cap_t, cap_nt, o_cap, err_in, reps, fit_ntask, fit_n, fit_own_min, offs_out, slot_a, toffs_out, slot_b, ioffs_out, res);
         return CP_OK;
     });
 }

@@ -148,6 +148,13 @@ void dp_own_pair_test(int64_t nt, int64_t wave, int64_t *res);      // dp_total.
 extern int64_t g_opt_own_pack;                 // 1 (and own_split 1, own_blk 1): split tiles read one packed word per step where the pattern's in-block offsets fit 16 bits
 extern int64_t g_own_pack_tiles, g_own_pack_wide;      // tiles that ran packed since the last reset; 1: the pattern of the last split launch fell back to the wide arrays
 void dp_own_pack_test(cp_csr_s *A, int32_t *vpk_out, int32_t *vbase_out, int64_t *res);      // dp_total.hip: cp_test_own_pack
+extern int64_t g_opt_round_alloc;              // 1: k_setup_short reserves list slots and offsets in one atomic per list and block, its last block gives the round's verdict; 0: k_round_scans
+void dp_list_alloc_test(const int32_t *a, int64_t na, const int32_t *b, int64_t nb, int bs, int64_t capT, int64_t capNT, int64_t o_cap, int err_in, int reps,
+                        int64_t fit_ntask, int64_t fit_n, int64_t fit_own_min, int64_t *offs_out, int32_t *slot_a, int64_t *toffs_out, int32_t *slot_b,
+                        int32_t *ioffs_out, int64_t *res);      // dp_total.hip: cp_test_list_alloc
+extern int64_t g_round_alloc_rounds;          // rounds that took that path since the last reset
+extern int64_t g_opt_cr_consume;               // 1: in full layers k_setup_short zeroes the cr / crl cells it reads; the clearing launch runs only while the planes may be dirty
+extern int64_t g_cr_consume_rounds, g_cr_clear_launches;      // chunked right passes that ran without / with the clearing launch since the last reset
 extern int64_t g_overlap_isect;                // column intersections cp_pack_overlap computed since the last reset (chunk_greedy.hip)
 void dp_own_split_test(cp_csr_s *A, int32_t *vpos_out, int32_t *vsa_out, int32_t *vnext_out, int64_t *res);      // dp_total.hip: cp_test_own_split
 extern int64_t g_opt_short_t, g_opt_short_e;   // k_setup_short: tasks with <= short_t candidates and <= short_e link entries finish in setup

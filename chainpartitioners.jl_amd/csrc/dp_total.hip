@@ -61,6 +61,10 @@ int64_t g_opt_ra_cache = 1;
 int64_t g_opt_leaf = 1, g_opt_block_tables = 0;
 int64_t g_opt_poison = 0, g_poison_hits = 0;
 int64_t g_fix_trips = 0, g_fix_edges = 0, g_fix_items = 0;
+int64_t g_opt_round_alloc = 1;         // k_setup_short reserves the offsets of its lists with their slots and gives the round's verdict; 0: k_round_scans
+int64_t g_round_alloc_rounds = 0;
+int64_t g_opt_cr_consume = 1;          // full layers: set-up zeroes the cr / crl cells it reads and the clearing launch in front of the chunked right passes goes (begin_layer)
+int64_t g_cr_consume_rounds = 0, g_cr_clear_launches = 0;
 
 // ------------------------------------------------------------------ wave-level segmented scans (64 lanes; the Best helpers: dp_total.hpp)
 // inclusive segmented sum: v = sum from the last head at or before this lane (or lane 0), f = "a head lies in [0, lane]"
@@ -90,6 +94,87 @@ __device__ __forceinline__ void wave_segmin(Best<TC, HYP> &x, int &f, int lane)
     }
 }
 
+// ------------------------------------------------------------------ round_alloc: list slots and offsets reserved together
+// cp_set_option("round_alloc", 0 | 1).  A block that appends to a task list holds its tasks' lengths, so it reserves its slots AND
+// its range of the list's units (flattened steps / own tiles) with ONE 64-bit atomic, slots << ALLOC_SH | units: both bases come
+// from one draw, so a later slot always has a later offset -- the order the binary searches of k_tile_t0 and k_own_map need -- and
+// every appended lane writes its task's offset itself: no scan of the lengths afterwards.  (The order across blocks is whatever the
+// atomics decide, as it was.)  The last block to arrive (round_alloc_finish) closes the lists and gives the round's verdict.
+struct AllocSh {
+    unsigned long long wpre[2][16];      // per wave and list: the packed total, then (thread 0) the exclusive prefix inside the block
+    int32_t wit[16];                     // ... of the merge items
+    unsigned long long base[2];          // what the list's word held before this block's draw
+    int32_t ibase;
+};
+
+// one wave, one list: `on` lanes append `len` units each.  pre: the units of the wave's appending lanes below this one; returns the
+// wave's packed total (the same in every lane)
+__device__ __forceinline__ unsigned long long alloc_wave(bool on, int32_t len, int lane, unsigned long long ballot, int32_t &pre)
+{
+    const int32_t mine = on ? len : 0;
+    int32_t inc = mine;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const int32_t v = __shfl_up(inc, o); if (lane >= o) inc += v; }
+    pre = inc - mine;
+    return ((unsigned long long)__popcll(ballot) << ALLOC_SH) | (unsigned long long)(uint32_t)__shfl(inc, 63);
+}
+
+// thread 0, after the barrier behind the waves' totals: the waves' exclusive prefixes, and the block's draws.  The values come
+// back while the block does other work; alloc_publish hands them to the block in front of the next barrier.
+__device__ __forceinline__ void alloc_reserve(AllocSh &S, int nw, RoundCounts *__restrict__ rc, bool want_items, unsigned long long &b0, unsigned long long &b1,
+                                              int32_t &bi)
+{
+    unsigned long long t0 = 0, t1 = 0; int32_t ti = 0;
+    for (int w = 0; w < nw; w++) {
+        const unsigned long long c0 = S.wpre[0][w], c1 = S.wpre[1][w]; const int32_t ci = S.wit[w];
+        S.wpre[0][w] = t0; S.wpre[1][w] = t1; S.wit[w] = ti; t0 += c0; t1 += c1; ti += ci;
+    }
+    b0 = t0 ? __hip_atomic_fetch_add(&rc->alloc_l, t0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
+    b1 = t1 ? __hip_atomic_fetch_add(&rc->alloc_o, t1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
+    bi = (want_items && ti) ? atomicAdd(&rc->n_items, ti) : 0;
+}
+__device__ __forceinline__ void alloc_publish(AllocSh &S, unsigned long long b0, unsigned long long b1, int32_t bi) { S.base[0] = b0; S.base[1] = b1; S.ibase = bi; }
+
+// an appending lane's slot and offset in list `li` (after the barrier behind alloc_publish)
+__device__ __forceinline__ void alloc_place(const AllocSh &S, int li, int wv, int lane, unsigned long long ballot, int32_t pre, int32_t &idx, int64_t &off)
+{
+    const unsigned long long w = S.base[li] + S.wpre[li][wv];         // (slots and units add up side by side: neither carries into the other, round_alloc_fits)
+    idx = (int32_t)(w >> ALLOC_SH) + (int32_t)__popcll(ballot & ((1ull << lane) - 1ull));
+    off = (int64_t)(w & ALLOC_MASK) + pre;
+}
+
+// Every block, on every path, when its lanes have written their records (the whole block calls it).  The release / ticket / acquire
+// hand-off of k_fix_own: the block's stores are complete and released at agent scope before thread 0 draws the ticket; whoever
+// draws the last one acquires, reads the two words, writes the closing entries offs[nlong] = T and toffs[nown] = NT, fills the
+// counts and gives the verdict (round_verdict: a dropped round reads 0 in T, NT, nlong, nown -- and lists no merge items), then
+// puts the ticket back for the next launch.  o_cap: slots of the own list (a count beyond it has set err: nothing is written there).
+__device__ __forceinline__ void round_verdict(RoundCounts *__restrict__ rc, int64_t capT, int64_t capNT);
+__device__ __forceinline__ void round_alloc_finish(RoundCounts *__restrict__ rc, int64_t *__restrict__ offs, int64_t *__restrict__ toffs, int64_t capT, int64_t capNT,
+                                                   int64_t o_cap, uint32_t nblocks)
+{
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const uint32_t got = __hip_atomic_fetch_add(&rc->a_ticket, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    if (got != nblocks - 1u) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    const unsigned long long al = __hip_atomic_load(&rc->alloc_l, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long ao = __hip_atomic_load(&rc->alloc_o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int64_t nl = (int64_t)(al >> ALLOC_SH), no = (int64_t)(ao >> ALLOC_SH), T = (int64_t)(al & ALLOC_MASK), NT = (int64_t)(ao & ALLOC_MASK);
+    if (no > o_cap) __hip_atomic_store(&rc->err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (its lanes have said so already)
+    else { offs[nl] = T; if (toffs) toffs[no] = NT; }
+    rc->nlong = (int32_t)nl; rc->nown = (int32_t)no;
+    __hip_atomic_store(&rc->T, T, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&rc->NT, NT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    round_verdict(rc, capT, capNT);
+    if (__hip_atomic_load(&rc->err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) rc->n_items = 0;
+    __hip_atomic_store(&rc->alloc_l, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&rc->alloc_o, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&rc->a_ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // ------------------------------------------------------------------ task setup, second form: short tasks finish here
 // One lane per task.  A task with at most `short_t` candidates and at most `short_e` link entries to step over is finished
 // by its lane on the spot (at low tau more than half of all tasks have ONE candidate: B == a, nothing to compare); the
@@ -97,7 +182,7 @@ __device__ __forceinline__ void wave_segmin(Best<TC, HYP> &x, int &f, int lane)
 // (cp_set_option("short_t" / "short_e"): tunables, defaults chosen on config 3.)
 template <typename TC, bool HYP>
 __global__ void __launch_bounds__(1024) k_setup_short(RoundDesc R, int32_t *__restrict__ opt, int32_t *__restrict__ nnopt, int32_t *__restrict__ nlopt,
-                                                      const int32_t *__restrict__ cr, const int32_t *__restrict__ crl,
+                                                      int32_t *__restrict__ cr, int32_t *__restrict__ crl,
                                                       const int32_t *__restrict__ pos32, const int32_t *__restrict__ next,
                                                       const int32_t *__restrict__ fpos32, const int32_t *__restrict__ flast,
                                                       const TC *__restrict__ W, DevModel<TC> M, TC alpha,
@@ -108,8 +193,14 @@ __global__ void __launch_bounds__(1024) k_setup_short(RoundDesc R, int32_t *__re
                                                       unsigned long long *__restrict__ own_steps, int32_t OWN_MIN, int32_t o_cap,
                                                       int32_t *__restrict__ err, const uint8_t *__restrict__ fin, const int32_t *__restrict__ last_s0,
                                                       int32_t *__restrict__ dbg_ntriv, const int32_t *__restrict__ anch, const int32_t *__restrict__ anch2,
-                                                      int32_t *__restrict__ pz, int OWN_BLK)
+                                                      int32_t *__restrict__ pz, int OWN_BLK, int CR_ZERO,
+                                                      RoundCounts *arc, int64_t *__restrict__ offs, int64_t *__restrict__ o_toffs,
+                                                      int32_t *__restrict__ o_ioffs, int64_t capT, int64_t capNT, int WANT_ITEMS)
 {
+    // arc (round_alloc: the round's counters, which nlong, n_own, own_steps and err point into; null: the lists are scanned by
+    // k_round_scans): see "round_alloc" above -- offs / o_toffs / o_ioffs are written here, the verdict is given by the last block
+    // CR_ZERO (cp_set_option("cr_consume", 1), full layers, rounds whose right pass adds a row's counts chunk by chunk): the task's
+    // lane is the one reader of its cr / crl cell and leaves it zero for the same round of the next layer -- no clearing launch
     // pz (cp_set_option("poison", 1)): the planes were filled with an out-of-range column before the layer; a task whose bounds
     // come out of range has read a cell nobody wrote -- counted, and clamped so that the task stays well-formed
     int lane = threadIdx.x & 63;
@@ -173,6 +264,7 @@ __global__ void __launch_bounds__(1024) k_setup_short(RoundDesc R, int32_t *__re
             B = opt[(int64_t)b * n1 + prow((rL), n1 - 1)];
             S0 = (int64_t)nnopt[(int64_t)b * n1 + prow((rL), n1 - 1)] + cr[(int64_t)b * n1 + prow((r), n1 - 1)];
             if (HYP) S0l = (int64_t)nlopt[(int64_t)b * n1 + prow((rL), n1 - 1)] + crl[(int64_t)b * n1 + prow((r), n1 - 1)];
+            if (CR_ZERO) { cr[(int64_t)b * n1 + prow((r), n1 - 1)] = 0; if (HYP) crl[(int64_t)b * n1 + prow((r), n1 - 1)] = 0; }
             // left end of the range: the winner of the right neighbour -- or, where that lies beyond the matrix, of the last
             // row n (same rectangle; known since round A); the block start for the last row of a rectangle
             a = (rR - rb) < ((int64_t)1 << b) ? (int64_t)opt[(int64_t)b * n1 + prow((rR <= R.n ? rR : R.n), n1 - 1)] : rb - ((int64_t)1 << b);
@@ -208,9 +300,26 @@ __global__ void __launch_bounds__(1024) k_setup_short(RoundDesc R, int32_t *__re
         lsum = (unsigned long long)Lmine;
         for (int o = 32; o > 0; o >>= 1) lsum += ((unsigned long long)(uint32_t)__shfl_down((int)(lsum >> 32), o) << 32) | (uint32_t)__shfl_down((int)(lsum & 0xffffffffull), o);
     }
-    if (lane == 0) { s_wcnt[0][wv] = (int32_t)__popcll(ml); s_wcnt[1][wv] = (int32_t)__popcll(mo); s_wsteps[wv] = lsum; }
+    // round_alloc (arc non-null): the lists' offsets are reserved with the slots -- the wave-level prefixes of the appended lengths
+    __shared__ AllocSh s_al;
+    const int32_t my_ntl = is_own ? own_ntiles(OWN_BLK, B, Lmine) : 0;
+    int32_t pre_l = 0, pre_o = 0, pre_i = 0;
+    unsigned long long wt_l = 0, wt_o = 0; int32_t wt_i = 0;
+    if (arc) {
+        if (ml) wt_l = alloc_wave(is_long, (int32_t)(1 + (B - a)), lane, ml, pre_l);              // wave-uniform
+        if (mo) {
+            wt_o = alloc_wave(is_own, my_ntl, lane, mo, pre_o);
+            const int32_t it = WANT_ITEMS ? fix_items_of(my_ntl) : 0;                              // the trips k_own_map lists of the task (gap rounds: none)
+            wt_i = (int32_t)(alloc_wave(it > 0, it, lane, 0ull, pre_i) & ALLOC_MASK);
+        }
+    }
+    if (lane == 0) {
+        s_wcnt[0][wv] = (int32_t)__popcll(ml); s_wcnt[1][wv] = (int32_t)__popcll(mo); s_wsteps[wv] = lsum;
+        if (arc) { s_al.wpre[0][wv] = wt_l; s_al.wpre[1][wv] = wt_o; s_al.wit[wv] = wt_i; }
+    }
     __syncthreads();
-    int32_t base0 = 0, base1 = 0;
+    int32_t base0 = 0, base1 = 0, abi = 0;
+    unsigned long long ab0 = 0, ab1 = 0;
     if (threadIdx.x == 0) {
         int32_t t0 = 0, t1 = 0; unsigned long long st = 0;
         for (int w = 0, nw = (int)(blockDim.x >> 6); w < nw; w++) {
@@ -219,8 +328,11 @@ __global__ void __launch_bounds__(1024) k_setup_short(RoundDesc R, int32_t *__re
         }
         // (the two list positions come back from L2 while this lane, like all the others, finishes its short task below: the
         //  block used to sit at a barrier for the length of these round trips)
-        base0 = t0 ? atomicAdd(nlong, t0) : 0;
-        base1 = t1 ? atomicAdd(n_own, t1) : 0;
+        if (arc) alloc_reserve(s_al, (int)(blockDim.x >> 6), arc, WANT_ITEMS != 0, ab0, ab1, abi);
+        else {
+            base0 = t0 ? atomicAdd(nlong, t0) : 0;
+            base1 = t1 ? atomicAdd(n_own, t1) : 0;
+        }
         if (st) atomicAdd(own_steps, st);
     }
     // the short tasks are finished by their lanes -- between the two barriers, while the list positions are on their way
@@ -262,10 +374,11 @@ __global__ void __launch_bounds__(1024) k_setup_short(RoundDesc R, int32_t *__re
             opt[rw] = best.p; nnopt[rw] = best.nn; if (HYP) nlopt[rw] = best_nl(best);
         }
     }
-    if (threadIdx.x == 0) { s_base[0] = base0; s_base[1] = base1; }
+    if (threadIdx.x == 0) { s_base[0] = base0; s_base[1] = base1; if (arc) alloc_publish(s_al, ab0, ab1, abi); }
     __syncthreads();
     if (is_long) {
         int32_t idx = s_base[0] + s_wcnt[0][wv] + __popcll(ml & ((1ull << lane) - 1ull));
+        if (arc) { int64_t off; alloc_place(s_al, 0, wv, lane, ml, pre_l, idx, off); offs[idx] = off; }
         tdesc[idx] = make_int4((int32_t)B, (int32_t)S0, (int32_t)r, pos32[r]);
         tb[idx] = (uint8_t)b;
         len[idx] = (int32_t)(1 + (B - a));
@@ -273,13 +386,20 @@ __global__ void __launch_bounds__(1024) k_setup_short(RoundDesc R, int32_t *__re
     }
     if (is_own) {
         int32_t idx = s_base[1] + s_wcnt[1][wv] + __popcll(mo & ((1ull << lane) - 1ull));
-        if (idx >= o_cap) { *err = 1; return; }          // (an own task is never short) cannot happen (LayerWork sizes the list for the worst case); never write outside
-        o_tdesc[idx] = make_int4((int32_t)B, (int32_t)S0, (int32_t)r, pos32[r]);
-        o_tb[idx] = (uint8_t)b;
-        o_rlen[idx] = (int32_t)Lmine;
-        o_ntl[idx] = own_ntiles(OWN_BLK, B, Lmine);
-        if (HYP) o_tS0l[idx] = (int32_t)S0l;
+        int64_t off = 0;
+        if (arc) alloc_place(s_al, 1, wv, lane, mo, pre_o, idx, off);
+        if (idx >= o_cap) *err = 1;                      // (an own task is never short) cannot happen (LayerWork sizes the list for the worst case); never write outside
+        else {
+            o_tdesc[idx] = make_int4((int32_t)B, (int32_t)S0, (int32_t)r, pos32[r]);
+            o_tb[idx] = (uint8_t)b;
+            o_rlen[idx] = (int32_t)Lmine;
+            o_ntl[idx] = my_ntl;
+            if (HYP) o_tS0l[idx] = (int32_t)S0l;
+            if (arc) { o_toffs[idx] = off; if (WANT_ITEMS) o_ioffs[idx] = s_al.ibase + s_al.wit[wv] + pre_i; }
+        }
     }
+    // (every block draws its ticket, whatever its lanes met)
+    if (arc) round_alloc_finish(arc, offs, o_toffs, capT, capNT, (int64_t)o_cap, gridDim.x * gridDim.y);
 }
 
 // ------------------------------------------------------------------ tile task table (one wave = one tile)
@@ -714,8 +834,10 @@ __global__ void __launch_bounds__(256) k_own_map(RoundCounts *__restrict__ rc, c
                                                  const int32_t *__restrict__ rlen, int4 *__restrict__ rec, int32_t *__restrict__ tile_task,
                                                  const uint8_t *__restrict__ tb, int32_t *__restrict__ gap_hi, int tau, int64_t n, int blk,
                                                  int32_t *__restrict__ bcnt, int32_t *__restrict__ brank, int2 *__restrict__ items,
-                                                 int32_t *__restrict__ item_of, int split)
+                                                 int32_t *__restrict__ item_of, int split, const int32_t *__restrict__ ioffs)
 {
+    // ioffs (round_alloc): set-up reserved every task's items, trip j of task t is item ioffs[t] + j -- computed, not drawn: no
+    // same-address atomic per wave, no item_of; rc->n_items holds their number already
     const int64_t ntask = rc->nown, ntile = rc->NT;
     for (int64_t tile = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; tile < ntile; tile += (int64_t)gridDim.x * blockDim.x) {
     int64_t lo = 0, hi = ntask;                       // last task with toffs[task] <= tile
@@ -724,7 +846,9 @@ __global__ void __launch_bounds__(256) k_own_map(RoundCounts *__restrict__ rc, c
         if (toffs[mid] <= tile) lo = mid; else hi = mid;
     }
     int32_t kt = (int32_t)(tile - toffs[lo]);
-    if (items) {
+    if (items && ioffs) {
+        if (kt % FIX_TRIP == 0 && toffs[lo + 1] - toffs[lo] > FIX_SERIAL) items[ioffs[lo] + kt / FIX_TRIP] = make_int2((int32_t)lo, kt);
+    } else if (items) {
         const bool first = kt % FIX_TRIP == 0 && toffs[lo + 1] - toffs[lo] > FIX_SERIAL;
         const unsigned long long mf = __ballot(first);      // (the lanes still in the loop)
         if (mf) {
@@ -1157,8 +1281,10 @@ __global__ void __launch_bounds__(256) k_fix_own(RoundCounts *__restrict__ rc, c
                                                  const int32_t *__restrict__ tileS, const int32_t *__restrict__ tileS2, DevModel<TC> M,
                                                  int32_t *__restrict__ opt, int32_t *__restrict__ nnopt, int32_t *__restrict__ nlopt, int64_t n1,
                                                  const int2 *__restrict__ items, const int32_t *__restrict__ item_of,
-                                                 unsigned long long *__restrict__ trec, uint32_t *__restrict__ tick, int iblocks)
+                                                 unsigned long long *__restrict__ trec, uint32_t *__restrict__ tick, int iblocks,
+                                                 const int32_t *__restrict__ ioffs)
 {
+    // ioffs (round_alloc): trip j of task t is item ioffs[t] + j; null: item_of[the trip's first tile], as k_own_map drew it
     __shared__ Best<TC, HYP> s_part[4];
     __shared__ int64_t s_w[4], s_w2[4];
     __shared__ int64_t s_pre[FIX_TRIP], s_pre2[HYP ? FIX_TRIP : 1];      // per tile of the trip: the counts since its wave's first tile
@@ -1299,7 +1425,7 @@ __global__ void __launch_bounds__(256) k_fix_own(RoundCounts *__restrict__ rc, c
                 Best<TC, HYP> c; best_clear(c);
                 int64_t s1 = 0, s2 = 0;
                 if (j < ntrip) {
-                    const unsigned long long *r = trec + (size_t)item_of[k0 + j * FIX_TRIP] * FIX_REC_W;
+                    const unsigned long long *r = trec + (size_t)(ioffs ? ioffs[t] + (int32_t)j : item_of[k0 + j * FIX_TRIP]) * FIX_REC_W;
                     const unsigned long long w0 = __hip_atomic_load(r + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     const unsigned long long w1 = __hip_atomic_load(r + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     s1 = (int64_t)__hip_atomic_load(r + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -2138,6 +2264,90 @@ void dp_round_scans_test(const int32_t *a, int64_t na, int64_t na_max, const int
     res[0] = h.T; res[1] = h.NT; res[2] = h.nlong; res[3] = h.nown; res[4] = h.ntile; res[5] = h.err;
 }
 
+// Test entry (cp_test_list_alloc): the block-level allocation of k_setup_short (alloc_wave / alloc_reserve / alloc_place) and its
+// closing (round_alloc_finish) on host arrays of lengths.  Lane i appends a[i] units to the first list (i < na) and b[i] tiles to
+// the second (i < nb); blocks of `bs` lanes, and one block more that appends nothing.
+// The sequence wave prefix / reserve / publish / place is spelled again here (k_setup_short spreads it over its short-task walk to
+// hide the atomics' round trips): this entry proves the helpers, not their wiring in set-up -- s_wcnt against the indices of
+// alloc_place and the o_cap branch there are covered by the layer-parity tests only.
+__global__ void __launch_bounds__(1024) k_list_alloc_test(RoundCounts *rc, const int32_t *__restrict__ a, int64_t na, const int32_t *__restrict__ b, int64_t nb,
+                                                          int64_t *__restrict__ offs, int64_t *__restrict__ toffs, int32_t *__restrict__ ioffs,
+                                                          int32_t *__restrict__ slot_a, int32_t *__restrict__ slot_b, int64_t capT, int64_t capNT, int32_t o_cap)
+{
+    __shared__ AllocSh S;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const bool onA = i < na, onB = i < nb;
+    const int32_t la = onA ? a[i] : 0, lb = onB ? b[i] : 0;
+    const unsigned long long ml = __ballot(onA), mo = __ballot(onB);
+    int32_t pre_l = 0, pre_o = 0, pre_i = 0;
+    unsigned long long wt_l = 0, wt_o = 0; int32_t wt_i = 0;
+    if (ml) wt_l = alloc_wave(onA, la, lane, ml, pre_l);
+    if (mo) {
+        wt_o = alloc_wave(onB, lb, lane, mo, pre_o);
+        const int32_t it = fix_items_of(lb);
+        wt_i = (int32_t)(alloc_wave(it > 0, it, lane, 0ull, pre_i) & ALLOC_MASK);
+    }
+    if (lane == 0) { S.wpre[0][wv] = wt_l; S.wpre[1][wv] = wt_o; S.wit[wv] = wt_i; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long b0, b1; int32_t bi;
+        alloc_reserve(S, (int)(blockDim.x >> 6), rc, true, b0, b1, bi);
+        alloc_publish(S, b0, b1, bi);
+    }
+    __syncthreads();
+    if (onA) { int32_t idx; int64_t off; alloc_place(S, 0, wv, lane, ml, pre_l, idx, off); offs[idx] = off; slot_a[i] = idx; }
+    if (onB) {
+        int32_t idx; int64_t off;
+        alloc_place(S, 1, wv, lane, mo, pre_o, idx, off);
+        slot_b[i] = idx;
+        if (idx >= o_cap) rc->err = 1;
+        else { toffs[idx] = off; ioffs[idx] = S.ibase + S.wit[wv] + pre_i; }
+    }
+    round_alloc_finish(rc, offs, toffs, capT, capNT, (int64_t)o_cap, gridDim.x);
+}
+
+// res: {T, NT, nlong, nown, ntile, err, n_items, the ticket, the two packed words or-ed} after the last of `reps` launches on one record,
+// then round_alloc_fits(fit_ntask, fit_n, fit_own_min).  offs_out: na + 1 values by slot, slot_a: the slot of lane i; toffs_out,
+// slot_b, ioffs_out (by slot) likewise.  o_cap: slots of the second list.
+void dp_list_alloc_test(const int32_t *a, int64_t na, const int32_t *b, int64_t nb, int bs, int64_t capT, int64_t capNT, int64_t o_cap, int err_in, int reps,
+                        int64_t fit_ntask, int64_t fit_n, int64_t fit_own_min, int64_t *offs_out, int32_t *slot_a, int64_t *toffs_out, int32_t *slot_b,
+                        int32_t *ioffs_out, int64_t *res)
+{
+    CP_REQUIRE(na >= 0 && nb >= 0 && na < ((int64_t)1 << 24) && nb < ((int64_t)1 << 24) && reps >= 1 && bs >= 64 && bs <= 1024 && bs % 64 == 0 && o_cap >= 0 &&
+               o_cap <= nb, CP_EINVAL, "list alloc test: bad sizes");
+    hipStream_t s = nullptr;
+    DBuf<int32_t> da((size_t)na + 1), db((size_t)nb + 1), dsa((size_t)na + 1), dsb((size_t)nb + 1), dio((size_t)nb + 1);
+    DBuf<int64_t> doffs((size_t)na + 1), dtoffs((size_t)nb + 1);
+    DBuf<RoundCounts> drc(1);
+    if (na > 0) CP_HIP(hipMemcpyAsync(da.p, a, sizeof(int32_t) * (size_t)na, hipMemcpyHostToDevice, s));
+    if (nb > 0) CP_HIP(hipMemcpyAsync(db.p, b, sizeof(int32_t) * (size_t)nb, hipMemcpyHostToDevice, s));
+    RoundCounts h;
+    memset(&h, 0, sizeof(h));
+    CP_HIP(hipMemcpyAsync(drc.p, &h, sizeof(h), hipMemcpyHostToDevice, s));
+    const unsigned grid = (unsigned)(cdiv(std::max(na, nb), (int64_t)bs) + 1);
+    for (int r = 0; r < reps; r++) {
+        // (the record goes on from launch to launch: the ticket and the packed words come back as zeros; the counts are set again)
+        CP_HIP(hipMemsetAsync(&drc.p->err, 0, sizeof(int32_t), s));
+        if (err_in) CP_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(&drc.p->err), 1, 1, s));
+        CP_HIP(hipMemsetAsync(&drc.p->n_items, 0, sizeof(int32_t), s));
+        CP_HIP(hipMemsetAsync(doffs.p, 0xFF, doffs.bytes(), s)); CP_HIP(hipMemsetAsync(dtoffs.p, 0xFF, dtoffs.bytes(), s));
+        CP_HIP(hipMemsetAsync(dsa.p, 0xFF, dsa.bytes(), s)); CP_HIP(hipMemsetAsync(dsb.p, 0xFF, dsb.bytes(), s)); CP_HIP(hipMemsetAsync(dio.p, 0xFF, dio.bytes(), s));
+        hipLaunchKernelGGL(k_list_alloc_test, dim3(grid), dim3((unsigned)bs), 0, s, drc.p, da.p, na, db.p, nb, doffs.p, dtoffs.p, dio.p, dsa.p, dsb.p, capT, capNT,
+                           (int32_t)o_cap);
+        CP_HIP(hipGetLastError());
+    }
+    CP_HIP(hipMemcpyAsync(&h, drc.p, sizeof(h), hipMemcpyDeviceToHost, s));
+    CP_HIP(hipMemcpyAsync(offs_out, doffs.p, sizeof(int64_t) * (size_t)(na + 1), hipMemcpyDeviceToHost, s));
+    CP_HIP(hipMemcpyAsync(toffs_out, dtoffs.p, sizeof(int64_t) * (size_t)(nb + 1), hipMemcpyDeviceToHost, s));
+    if (na > 0) CP_HIP(hipMemcpyAsync(slot_a, dsa.p, sizeof(int32_t) * (size_t)na, hipMemcpyDeviceToHost, s));
+    if (nb > 0) CP_HIP(hipMemcpyAsync(slot_b, dsb.p, sizeof(int32_t) * (size_t)nb, hipMemcpyDeviceToHost, s));
+    if (nb > 0) CP_HIP(hipMemcpyAsync(ioffs_out, dio.p, sizeof(int32_t) * (size_t)nb, hipMemcpyDeviceToHost, s));
+    CP_HIP(hipStreamSynchronize(s));
+    res[0] = h.T; res[1] = h.NT; res[2] = h.nlong; res[3] = h.nown; res[4] = h.ntile; res[5] = h.err; res[6] = h.n_items; res[7] = h.a_ticket;
+    res[8] = (int64_t)(h.alloc_l | h.alloc_o); res[9] = round_alloc_fits(fit_ntask, fit_n, fit_own_min) ? 1 : 0;
+}
+
 // ------------------------------------------------------------------ host side of the own-tile merge (k_fix_own)
 // the grid, from what the host knows: the round's tiles (predicted or exact) and tasks.  Both roles walk their device-side
 // counts with grid strides, so a count beyond the estimate costs time only.
@@ -2155,11 +2365,11 @@ template <typename TC, bool HYP>
 static void launch_fix_own(hipStream_t s, RoundCounts *rc, const int64_t *toffs, const Best<TC, HYP> *part, const int4 *tdesc, const uint8_t *tb,
                            const int32_t *tS0l, const int32_t *tileS, const int32_t *tileS2, const DevModel<TC> &M, int32_t *opt, int32_t *nnopt,
                            int32_t *nlopt, int64_t n, const int2 *items, const int32_t *item_of, unsigned long long *trec, uint32_t *tick,
-                           int64_t nt, int64_t ntask)
+                           int64_t nt, int64_t ntask, const int32_t *ioffs)
 {
     const FixGrid g = fix_grid(nt, ntask);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fix_own<TC, HYP>), dim3((unsigned)(g.iblocks + g.lblocks)), dim3(256), 0, s, rc, toffs, part, tdesc, tb, tS0l, tileS,
-                       tileS2, M, opt, nnopt, nlopt, n + 1, items, item_of, trec, tick, g.iblocks);
+                       tileS2, M, opt, nnopt, nlopt, n + 1, items, item_of, trec, tick, g.iblocks, ioffs);
     CP_HIP(hipGetLastError());
 }
 
@@ -2209,19 +2419,29 @@ static void fix_merge_test_run(const cp_model_t *model, int64_t ntask, const int
     up(drlen.p, hrlen.data(), drlen.bytes()); up(dS.p, tile_s, dS.bytes());
     if (HYP) { up(dS0l.p, anchor2, dS0l.bytes()); up(dS2.p, tile_s2, dS2.bytes()); }
     CP_HIP(hipMemsetAsync(dtick.p, 0, dtick.bytes(), s));
+    // round_alloc: the items' bases as set-up reserves them (here: in task order) and their number; 0: k_own_map draws them
+    std::vector<int32_t> hioffs((size_t)ntask);
+    int32_t n_items0 = 0;
+    for (int64_t t = 0; t < ntask; t++) {
+        hioffs[(size_t)t] = n_items0;
+        n_items0 += fix_items_of(toffs[t + 1] - toffs[t]);
+    }
+    DBuf<int32_t> dioffs((size_t)ntask);
+    up(dioffs.p, hioffs.data(), dioffs.bytes());
+    const int32_t *ioffs = g_opt_round_alloc ? dioffs.p : nullptr;
     RoundCounts h;
     for (int r = 0; r < reps; r++) {
         memset(&h, 0, sizeof(h));
-        h.nown = (int32_t)ntask; h.NT = NT;
+        h.nown = (int32_t)ntask; h.NT = NT; h.n_items = ioffs ? n_items0 : 0;
         up(drc.p, &h, sizeof(h));
         // (whatever a launch does not write shows: no column, and records / items of the launch before are gone)
         CP_HIP(hipMemsetAsync(dopt.p, 0xFF, dopt.bytes(), s)); CP_HIP(hipMemsetAsync(dnn.p, 0xFF, dnn.bytes(), s)); CP_HIP(hipMemsetAsync(dnl.p, 0xFF, dnl.bytes(), s));
         CP_HIP(hipMemsetAsync(ditems.p, 0x7F, ditems.bytes(), s)); CP_HIP(hipMemsetAsync(ditem_of.p, 0x7F, ditem_of.bytes(), s));
         CP_HIP(hipMemsetAsync(dtrec.p, 0x7F, dtrec.bytes(), s));
         hipLaunchKernelGGL(k_own_map, dim3((unsigned)std::min<int64_t>(cdiv(NT, (int64_t)256), 8192)), dim3(256), 0, s, drc.p, dtoffs.p, dtd.p, drlen.p, drec.p,
-                           dtask.p, dtb.p, (int32_t *)nullptr, 0, n, 0, (int32_t *)nullptr, (int32_t *)nullptr, ditems.p, ditem_of.p, 0);
+                           dtask.p, dtb.p, (int32_t *)nullptr, 0, n, 0, (int32_t *)nullptr, (int32_t *)nullptr, ditems.p, ditem_of.p, 0, ioffs);
         launch_fix_own<TC, HYP>(s, drc.p, dtoffs.p, dpart.p, dtd.p, dtb.p, HYP ? dS0l.p : nullptr, dS.p, HYP ? dS2.p : nullptr, HM.d, dopt.p, dnn.p, HYP ? dnl.p : nullptr, n,
-                                ditems.p, ditem_of.p, dtrec.p, dtick.p, NT, ntask);
+                                ditems.p, ditem_of.p, dtrec.p, dtick.p, NT, ntask, ioffs);
         CP_HIP(hipMemcpyAsync(&h, drc.p, sizeof(h), hipMemcpyDeviceToHost, s));
         CP_HIP(hipStreamSynchronize(s));               // (h is reused)
         g_fix_items += h.n_items;
@@ -2737,10 +2957,23 @@ static void poison_fill(hipStream_t s, std::initializer_list<std::pair<void *, s
 
 // ------------------------------------------------------------------ the stages of a round, each as the host function run_layer calls
 // A stage function takes the layer's context, the work object, the round and its counts.
-// Set-up of a round: one lane per task finishes the short ones and lists the others
-template <typename TC, bool HYP>
-static void setup_tasks(const LayerCtx<TC> &C, LayerWork<TC> &Wk, const RoundDesc &R, RoundCounts *rc, int32_t own_min)
+// the capacities a round's verdict checks its totals against: the buffers sized from the prediction (exact counts: no limit)
+template <typename TC>
+static void round_caps(const LayerCtx<TC> &C, const LayerWork<TC> &Wk, int64_t &capT, int64_t &capNT)
 {
+    const bool tiny = C.spec && (g_opt_dbg & DBG_TINY_BUFFERS);       // test: pretend the buffers sized from the prediction are too small
+    capT = C.spec ? (tiny ? (int64_t)64 : (int64_t)Wk.fl.loc.n) : INT64_MAX;
+    capNT = C.spec ? (tiny ? (int64_t)1 : (int64_t)Wk.ow.o_rec.n) : INT64_MAX;
+}
+
+// Set-up of a round: one lane per task finishes the short ones and lists the others.  ralloc (round_alloc): the launch also writes
+// the lists' offsets and ends with the round's verdict -- the buffers the verdict checks against are sized before it
+template <typename TC, bool HYP>
+static void setup_tasks(const LayerCtx<TC> &C, LayerWork<TC> &Wk, const RoundDesc &R, RoundCounts *rc, int32_t own_min, bool cr_zero,
+                        bool ralloc, bool want_items)
+{
+    int64_t capT, capNT;
+    round_caps(C, Wk, capT, capNT);
     hipStream_t s = C.s;
     cp_csr_s *A = C.A;
     // per task: four gathers from the plane arrays + the record; short tasks also step over their columns here
@@ -2758,7 +2991,8 @@ static void setup_tasks(const LayerCtx<TC> &C, LayerWork<TC> &Wk, const RoundDes
                        (int32_t)g_opt_short_t, (int32_t)g_opt_short_e, C.own_tiles ? Wk.ow.o_tdesc.p : (int4 *)nullptr, Wk.ow.o_tb.p, Wk.ow.o_rlen.p, Wk.ow.o_ntl.p,
                        Wk.ow.o_tS0l.p, &rc->nown, &rc->own_steps, own_min,
                        (int32_t)std::min<size_t>(Wk.ow.o_ntl.n, (size_t)INT32_MAX), &rc->err, Wk.pl.fin.p, Wk.pl.last_s0.p,
-                       (g_opt_dbg & DBG_COUNT_NONTRIVIAL) ? &rc->_pad : (int32_t *)nullptr, Wk.win.w_anch.p, Wk.win.w_anch2.p, C.pzp, C.oblk);
+                       (g_opt_dbg & DBG_COUNT_NONTRIVIAL) ? &rc->_pad : (int32_t *)nullptr, Wk.win.w_anch.p, Wk.win.w_anch2.p, C.pzp, C.oblk, cr_zero ? 1 : 0,
+                       ralloc ? rc : (RoundCounts *)nullptr, Wk.tk.offs.p, Wk.ow.o_toffs.p, Wk.ow.o_ioffs.p, capT, capNT, want_items ? 1 : 0);
 }
 
 // Both scans of a round read their element count on the device; one launch holds them and the round's verdict
@@ -2767,8 +3001,8 @@ static void round_scans(const LayerCtx<TC> &C, LayerWork<TC> &Wk, const RoundDes
 {
     hipStream_t s = C.s;
     ProfScope ps(PROF_SCAN, s, 12.0 * (double)R.ntask);
-    const bool tiny = C.spec && (g_opt_dbg & DBG_TINY_BUFFERS);       // test: pretend the buffers sized from the prediction are too small
-    const int64_t capT = C.spec ? (tiny ? (int64_t)64 : (int64_t)Wk.fl.loc.n) : INT64_MAX, capNT = C.spec ? (tiny ? (int64_t)1 : (int64_t)Wk.ow.o_rec.n) : INT64_MAX;
+    int64_t capT, capNT;
+    round_caps(C, Wk, capT, capNT);
     const int64_t nm = std::min<int64_t>(R.ntask, (int64_t)Wk.ow.o_ntl.n);
     if (R.ntask <= LB_MAX) {
         launch_round_scans(rc, Wk.tk.len.p, Wk.tk.offs.p, R.ntask, Wk.ow.o_ntl.p, Wk.ow.o_toffs.p, nm, C.own_tiles, capT, capNT, Wk.sc.scanws, s);
@@ -2791,7 +3025,7 @@ template <bool HYP> static bool own_pairs(bool gap, bool win) { return !HYP && !
 // (own_blk 1) and the pattern's offsets fit 16 bits -- except in a paired launch that also holds tiles of the planes below (gap_tau
 // below 6): a wave's two tiles run one text.  Returns whether they did.
 template <typename TC, bool HYP>
-static bool own_stream(const LayerCtx<TC> &C, LayerWork<TC> &Wk, const RoundDesc &R, RoundCounts *rc, const RoundCounts &P, bool gap, int split)
+static bool own_stream(const LayerCtx<TC> &C, LayerWork<TC> &Wk, const RoundDesc &R, RoundCounts *rc, const RoundCounts &P, bool gap, int split, bool ralloc)
 {
     hipStream_t s = C.s;
     cp_csr_s *A = C.A;
@@ -2812,7 +3046,7 @@ static bool own_stream(const LayerCtx<TC> &C, LayerWork<TC> &Wk, const RoundDesc
     if (split && !pack) split_wide(A, Wk.ow.split);
     hipLaunchKernelGGL(k_own_map, dim3(mgrid), dim3(256), 0, s, rc, Wk.ow.o_toffs.p, Wk.ow.o_tdesc.p, Wk.ow.o_rlen.p, Wk.ow.o_rec.p, Wk.ow.o_task.p,
                        Wk.ow.o_tb.p, gap ? Wk.ow.o_hi.p : (int32_t *)nullptr, R.tau, n, oblk, oblk ? Wk.ow.b_cnt.p : (int32_t *)nullptr, Wk.ow.o_brank.p,
-                       gap ? (int2 *)nullptr : Wk.ow.o_items.p, Wk.ow.o_item_of.p, split);
+                       gap ? (int2 *)nullptr : Wk.ow.o_items.p, Wk.ow.o_item_of.p, split, ralloc ? Wk.ow.o_ioffs.p : (const int32_t *)nullptr);
     ProfScope ps(gap ? PROF_GAPSTREAM : PROF_OWN, s, C.own_bytes(Wk.ow.split, R.tau, pack ? 2 : split != 0, (double)P.own_steps));
     if (oblk) {                       // the tile ids by column block (counted in k_own_map): ~10^5 tiles, a counting sort
         exclusive_scan_i32_lb(Wk.ow.b_cnt.p, Wk.ow.b_start.p, Wk.ow.b_n.p, Wk.ow.b_nblk, nullptr, Wk.sc.scanws, s);
@@ -2836,12 +3070,13 @@ static bool own_stream(const LayerCtx<TC> &C, LayerWork<TC> &Wk, const RoundDesc
 // The tail of the chain outside the gap rounds: one launch, a lane per task of up to FIX_SERIAL tiles, a block per listed trip
 // of the longer ones
 template <typename TC, bool HYP>
-static void own_merge(const LayerCtx<TC> &C, LayerWork<TC> &Wk, RoundCounts *rc, const RoundCounts &P)
+static void own_merge(const LayerCtx<TC> &C, LayerWork<TC> &Wk, RoundCounts *rc, const RoundCounts &P, bool ralloc)
 {
     ProfScope ps(PROF_FIX, C.s, 24.0 * (double)P.NT);
     launch_fix_own<TC, HYP>(C.s, rc, Wk.ow.o_toffs.p, recs<HYP>(Wk.ow.o_part), Wk.ow.o_tdesc.p, Wk.ow.o_tb.p, if_hyp<HYP>(Wk.ow.o_tS0l.p), Wk.ow.o_tileS.p,
                             if_hyp<HYP>(Wk.ow.o_tileS2.p), C.M, Wk.pl.opt.p, Wk.pl.nnopt.p, if_hyp<HYP>(Wk.pl.nlopt.p), C.n, Wk.ow.o_items.p, Wk.ow.o_item_of.p, Wk.ow.o_trec.p,
-                            Wk.ow.o_tick.p, C.spec ? grow_pred(P.NT) : P.NT, C.spec ? grow_pred(P.nown) : P.nown);
+                            Wk.ow.o_tick.p, C.spec ? grow_pred(P.NT) : P.NT, C.spec ? grow_pred(P.nown) : P.nown,
+                            ralloc ? Wk.ow.o_ioffs.p : (const int32_t *)nullptr);
 }
 
 // ------------------------------------------------------------------ host side: the flattened chain of a round (the tasks' number: rc->nlong)
@@ -2965,8 +3200,19 @@ static LayerCtx<TC> begin_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, co
     const int ra_bmin = (leaf && !Wk.pl.planes_full && !(g_opt_dbg & DBG_RA_ALL_LEVELS)) ? LEAF_T : 0;
     // `fin` flags hold the layer's stamp: no 240 MB clear per layer (every attempt of a layer -- a redo included -- takes a new stamp)
     if (++Wk.pl.fin_stamp > 255 || Wk.pl.fin_stamp <= 0) { CP_HIP(hipMemsetAsync(Wk.pl.fin.p, 0, Wk.pl.fin.bytes(), s)); Wk.pl.fin_stamp = 1; }
+    // cp_set_option("cr_consume", 0 | 1): in a full layer the cells of cr / crl that a round's right pass adds into are the cells the
+    // round's tasks read, the same from layer to layer (make_round and launch_rpass with rlo <= 1, rhi >= n: the rows with ctz == tau,
+    // in the planes whose bit they have set).  Set-up zeroes what it reads (cr_zero), and while the planes are known to be clean
+    // -- since allocation, or since a full layer that cleared and zeroed under the same rpass_ch -- the clearing launch is left out
+    // (cr_consume).  Windowed and row-tiled layers add into rows next to their tile that no task of theirs reads: they keep the
+    // clear and leave the planes dirty, like a layer that threw.
+    const bool full = !G.win && rlo <= 1 && rhi >= n;
+    if (Wk.pl.cr_ch != g_opt_rpass_ch) Wk.pl.cr_dirty = true;
+    const bool cr_zero = g_opt_cr_consume && full;
+    const bool cr_consume = cr_zero && !Wk.pl.cr_dirty;
+    Wk.pl.cr_dirty = true; Wk.pl.cr_ch = g_opt_rpass_ch;
     return LayerCtx<TC>{A, s, M, alpha, W, cst_out, ptr_out, n, rlo, rhi, G, nbits, spec, own_tiles, gaps, split_layer, leaf, oblk, ra_bmin, pzp,
-                        avg_deg, self_deg, step_bytes};
+                        avg_deg, self_deg, step_bytes, cr_zero, cr_consume};
 }
 
 // Runs the rounds of one layer.  `spec`: the per-round counts of the PREVIOUS layer (Wk.sp.pred) size the grids, the buffers and
@@ -3031,8 +3277,9 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
         any_forced |= forced;
         if (!R.isA) right_pass<TC, HYP>(C, Wk, R);
         if (R.isA && R.nlast > 0) last_row_counts<TC, HYP>(C, Wk, R);
-        setup_tasks<TC, HYP>(C, Wk, R, rc, (int32_t)(forced ? 2 : gap ? g_opt_gap_min : g_opt_own_min));
-        RoundCounts P;                                   // the counts this round is sized with
+        // cp_set_option("cr_consume", 0 | 1): where the chunks of a row add into cr / crl, set-up leaves the cells it reads zero
+        const bool cr_zero = C.cr_zero && !R.isA && ((int64_t)1 << R.tau) > g_opt_rpass_ch;
+        RoundCounts P;                                   // the counts this round is sized with (before set-up: its last block gives the verdict under round_alloc)
         if (spec) {
             P = Wk.sp.pred[(size_t)rd];
             if (Wk.sp.pred_scale != 1.0) {              // (windowed layers: the previous layer's tile had another number of rows)
@@ -3045,7 +3292,14 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
             Wk.ow.ensure_own(Wk.hyp, (size_t)grow_pred(P.NT));
             Wk.fl.ensure_flat(Wk.hyp, (size_t)grow_pred(P.T));
         }
-        round_scans<TC>(C, Wk, R, rc);
+        // cp_set_option("round_alloc", 0 | 1): set-up reserves the lists' offsets with their slots and ends with the verdict, where
+        // the packed words are wide enough (round_alloc_fits) and a single launch may scan the lists at all; elsewhere k_round_scans
+        const int64_t own_min64 = forced ? 2 : gap ? g_opt_gap_min : g_opt_own_min;
+        const int32_t own_min = (int32_t)own_min64;
+        const bool ralloc = g_opt_round_alloc && C.own_tiles && R.ntask <= LB_MAX && round_alloc_fits(R.ntask, n, own_min64);
+        setup_tasks<TC, HYP>(C, Wk, R, rc, own_min, cr_zero, ralloc, !gap);
+        if (ralloc) g_round_alloc_rounds++;
+        else round_scans<TC>(C, Wk, R, rc);
         if (!spec) {
             CP_HIP(hipMemcpyAsync(&P, rc, sizeof(P), hipMemcpyDeviceToHost, s));
             CP_HIP(hipStreamSynchronize(s));
@@ -3061,11 +3315,11 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
             const int split = !(C.split_layer && !R.isA && (!gap || g_opt_gap_split)) ? 0 : R.tau + 1 >= SPLIT_BMIN ? 1 : 2;
             split_mode[(size_t)rd] = (int8_t)(gap ? -split : split);
             pair_mode[(size_t)rd] = own_pairs<HYP>(gap, G.win != 0);
-            const bool pack = own_stream<TC, HYP>(C, Wk, R, rc, P, gap, split);
+            const bool pack = own_stream<TC, HYP>(C, Wk, R, rc, P, gap, split, ralloc);
             pack_mode[(size_t)rd] = pack;
             note(rd, 0, gap ? PROF_GAPSTREAM : PROF_OWN, R.tau, pack ? 2 : split != 0);
             if (gap) gap_finish<TC, HYP>(C, Wk, R, rc, P);
-            else own_merge<TC, HYP>(C, Wk, rc, P);
+            else own_merge<TC, HYP>(C, Wk, rc, P, ralloc);
             CP_HIP(hipGetLastError());
         }
         if (P.nlong <= 0 || P.T <= 0) continue;
@@ -3096,6 +3350,7 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
         CP_REQUIRE(!(ok && pz_hits[0] > 0), CP_EINTERNAL, "a DP layer that is not redone read plane cells nobody wrote (poison mode)");
     }
     if (ok) Wk.ow.b_dirty = false;
+    Wk.pl.cr_dirty = !C.cr_zero;                            // (every right pass that was enqueued was followed by its set-up, also in a layer that is redone)
     Wk.ow.t_dirty = false;                                  // (every merge that was enqueued has run to its end, also in a layer that is redone)
     if (ok) for (int rd = 0; rd < NR; rd++) { g_fix_trips += got[(size_t)rd].n_trips; g_fix_edges |= got[(size_t)rd].n_edge; }
     if (ok) for (int rd = 0; rd < NR; rd++) {
@@ -3108,7 +3363,9 @@ static bool run_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W,
             if (pair_mode[(size_t)rd]) { g_own_pair_waves += g.NT / 2; g_own_pair_lone += g.NT & 1; }      // (own_pair_slots over the true NT)
         }
     }
-    for (int rd = 0; rd < NR; rd++) g_fix_items += got[(size_t)rd].n_items;      // (attempts that are redone included: a dropped round lists none)
+    // (attempts that are redone included: a dropped round lists none; round_alloc reserves a round's items in set-up, so a round
+    //  whose own-tile stage the host skipped on a wrong prediction holds a count nobody listed: not counted, as before)
+    for (int rd = 0; rd < NR; rd++) if (used[(size_t)rd].nown > 0 && used[(size_t)rd].NT > 0) g_fix_items += got[(size_t)rd].n_items;
     if (ok) {
         for (auto &pt : patches) {
             const RoundCounts &g = got[(size_t)pt.rd];
@@ -3169,11 +3426,12 @@ void dp_total_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W, T
         int64_t mmin = std::max<int64_t>(2, std::min(g_opt_own_min, g_opt_gap_tau >= 0 ? g_opt_gap_min : g_opt_own_min));
         size_t mo = (size_t)(2 * n / mmin + 64) * (size_t)nbits + 1024;
         if (mo > mt) mo = mt;
-        Wk.ow.o_tdesc.alloc(mo); Wk.ow.o_tb.alloc(mo); Wk.ow.o_rlen.alloc(mo); Wk.ow.o_ntl.alloc(mo); Wk.ow.o_toffs.alloc(mo + 1); Wk.ow.o_tick.alloc(mo);
+        Wk.ow.o_tdesc.alloc(mo); Wk.ow.o_tb.alloc(mo); Wk.ow.o_rlen.alloc(mo); Wk.ow.o_ntl.alloc(mo); Wk.ow.o_toffs.alloc(mo + 1); Wk.ow.o_tick.alloc(mo); Wk.ow.o_ioffs.alloc(mo);
         Wk.ow.t_dirty = true;
         if (hyp) Wk.ow.o_tS0l.alloc(mo);
         Wk.sp.rc.alloc((size_t)NBMAX + 2);
         Wk.pl.fin.alloc(plane); Wk.pl.last_s0.alloc(64); Wk.pl.fin_stamp = 255;      // (fresh memory: the first layer clears it)
+        Wk.pl.cr_dirty = false; Wk.pl.cr_ch = g_opt_rpass_ch;      // (cr / crl: cleared above)
         Wk.n = n;
     }
     // geometry of this call: wwin > 0: candidates of row r are max(0, r - wwin) <= p <= r

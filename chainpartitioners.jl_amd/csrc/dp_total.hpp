@@ -81,7 +81,22 @@ struct RoundCounts {
     int32_t n_gslow, n_sslow;         // work items of k_gap_finish / k_gap_seg that met a tile with more than SMAX specials (redone by the SLOW variants)
     int32_t n_split, _pad2;           // own tiles that stream only their plane's variable link entries, where a launch mixes them with others (k_own_map, split == 2)
     int32_t n_trips, n_edge;          // what the merge met (cp_get_stat, tests): tasks of more than one trip (folded by k_fix_own); bit 0 / 1 / 2: a task of 1 / FIX_SERIAL / FIX_SERIAL + 1 tiles
+    // round_alloc: what the blocks of k_setup_short have reserved of each list, slots << ALLOC_SH | units (steps of the flattened
+    // tasks / tiles of the own-tiled ones), and the ticket its blocks draw when their records are written (zero between launches)
+    unsigned long long alloc_l, alloc_o;
+    uint32_t a_ticket, _pad3;
 };
+constexpr int ALLOC_SH = 40;                                          // a list's units fit 40 bits, its slots 24 (round_alloc_fits)
+constexpr unsigned long long ALLOC_MASK = (1ull << ALLOC_SH) - 1ull;
+
+// round_alloc: the packed words are wide enough for a round of `ntask` tasks whose flattened tasks have fewer than `own_min` steps
+// and whose own-tiled ones at most n / 256 + 2 tiles; the wave-level prefix of the lengths is a 32-bit sum of 64 of them
+inline bool round_alloc_fits(int64_t ntask, int64_t n, int64_t own_min)
+{
+    if (ntask < 0 || ntask >= ((int64_t)1 << 24) || own_min < 1 || own_min > ((int64_t)1 << 24)) return false;
+    const int64_t lim = (int64_t)1 << ALLOC_SH;
+    return ntask * (n / 256 + 2) < lim && ntask * own_min < lim;
+}
 
 // The tasks of a round, by value to every kernel that decodes them (make_round: dp_total.hip)
 struct RoundDesc {
@@ -235,6 +250,8 @@ struct SplitLinks {
 
 // items a round of `nt` own tiles can list: one per FIX_TRIP tiles and at most one partial trip per task of more than FIX_SERIAL tiles
 inline size_t fix_items_cap(size_t nt) { return nt / FIX_TRIP + nt / (FIX_SERIAL + 1) + 2; }
+// ... and the items of one task of `ntl` tiles: one per trip where a block merges it (the rule k_own_map lists its trip starts by)
+__host__ __device__ __forceinline__ int32_t fix_items_of(int64_t ntl) { return ntl > FIX_SERIAL ? (int32_t)((ntl + FIX_TRIP - 1) / FIX_TRIP) : 0; }
 
 // ================================================================== host side
 // The work object of a handle: the shape, and one group of members per owner.
@@ -246,6 +263,8 @@ struct Planes {
     DBuf<uint8_t> fin;                                  // rows already final (per plane slot) ...
     int fin_stamp = 255;                                // ... iff the cell holds the current layer's stamp (run_layer; 255: cleared before the next layer)
     DBuf<int32_t> last_s0;                              // anchors of the last row's round-A tasks ([b], [32 + b])
+    bool cr_dirty = true;                               // cr / crl may hold counts nobody will consume (cr_consume: the next full layer clears as before)
+    int64_t cr_ch = 0;                                  // the rpass_ch the planes were left clean under (another value: other rounds add in chunks)
     DBuf<int32_t> pz;                                   // poison mode: cells read that nobody wrote
     bool planes_full = false;                           // the last layer stored every per-block winner (cp_dp_block_tables)
 };
@@ -295,6 +314,7 @@ struct OwnTiles {
     DBuf<uint8_t> o_tb;
     DBuf<int32_t> o_rlen, o_ntl, o_tS0l, o_task, o_tileS, o_tileS2, o_hi;
     DBuf<int64_t> o_toffs, o_tilePS, o_tilePS2;
+    DBuf<int32_t> o_ioffs;                              // round_alloc: per task, its first merge item (trip j: o_ioffs[t] + j)
     DBuf<Best<TC, true>> o_part;
     // the merge of the own tiles (k_fix_own): its items {task, first tile} and each trip-start tile's item (k_own_map), one record per
     // item, one ticket per task (zero between rounds: the folder of a task puts it back)
@@ -392,6 +412,7 @@ struct LayerCtx {
     int ra_bmin;                                        // round A from the cache starts at this level
     int32_t *pzp;                                       // poison mode: the hit counters (null: off)
     double avg_deg, self_deg, step_bytes;               // link entries per column; bytes a step of the streaming kernels moves
+    bool cr_zero, cr_consume;                           // set-up zeroes the cr / crl cells it reads; ... and the planes are clean: no clearing launch (begin_layer)
     // bytes the own-tile stream moves: split tiles read two column pointers and a prefix sum per step (20 B with the cost; sp == 2,
     // own_pack: the plane's pointer and prefix sum are one word, 16 B) and the variable entries of the round's planes, at most what
     // the columns hold.  (Tiles of planes below SPLIT_BMIN in the same launch --

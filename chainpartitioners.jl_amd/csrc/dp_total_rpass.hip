@@ -313,9 +313,14 @@ void right_pass(const LayerCtx<TC> &C, LayerWork<TC> &Wk, const RoundDesc &R)
     cp_csr_s *A = C.A;
     int64_t cols = (((C.n >> R.tau) + 1) >> 1) << R.tau;
     ProfScope ps(PROF_RPASS, s, 4.0 * (C.avg_deg + C.self_deg) * (double)cols + 8.0 * (double)R.ntask);
-    if (((int64_t)1 << R.tau) > g_opt_rpass_ch)   // several chunks per row accumulate with atomics: clear first
-        hipLaunchKernelGGL(k_setup, dim3((unsigned)cdiv(R.ntask, 256)), dim3(256), 0, s, R, Wk.pl.opt.p, Wk.pl.nnopt.p, Wk.pl.cr.p, 1,
-                           Wk.tk.tdesc.p, A->pos32.p, Wk.tk.tb.p, Wk.tk.len.p, (const int32_t *)nullptr, if_hyp<HYP>(Wk.pl.crl.p), (int32_t *)nullptr);
+    if (((int64_t)1 << R.tau) > g_opt_rpass_ch) { // several chunks per row accumulate with atomics: clear first ...
+        if (C.cr_consume) g_cr_consume_rounds++;  // ... unless the last layer's set-up left the cells zero (cr_consume: begin_layer)
+        else {
+            g_cr_clear_launches++;
+            hipLaunchKernelGGL(k_setup, dim3((unsigned)cdiv(R.ntask, 256)), dim3(256), 0, s, R, Wk.pl.opt.p, Wk.pl.nnopt.p, Wk.pl.cr.p, 1,
+                               Wk.tk.tdesc.p, A->pos32.p, Wk.tk.tb.p, Wk.tk.len.p, (const int32_t *)nullptr, if_hyp<HYP>(Wk.pl.crl.p), (int32_t *)nullptr);
+        }
+    }
     launch_rpass(s, R, C.nbits, C.n, C.rlo, C.rhi, A->pos.p, A->prev.p, 0, Wk.pl.opt.p, Wk.pl.cr.p, C.avg_deg);                   // prev[q] < B
     if (HYP) launch_rpass(s, R, C.nbits, C.n, C.rlo, C.rhi, A->lpos.p, A->lfirst.p, 1, Wk.pl.opt.p, Wk.pl.crl.p, C.self_deg);      // rows ending in the column with first >= B
 }

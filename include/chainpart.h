@@ -324,7 +324,10 @@ int32_t cp_reset_stream(cp_csr_t csr);
  * the layers that stand.  "own_pair_waves" / "own_pair_lone" -- waves of the own-tile stream that ran two tiles / one because the run
  * order ended ("own_pair"), in the layers that stand.  "own_pack_tiles" -- split tiles, those of the gap rounds included, that read the packed words
  * ("own_pack"), in the layers that stand; "own_pack_wide" -- 1 while the pattern of the last layer with split tiles has an in-block
- * offset beyond 16 bits and runs on the wide arrays.  "overlap_isect" -- the column intersections cp_pack_overlap computed.  All of these are reset when "poison" is switched on and by cp_set_option("stat_reset", 1); reading
+ * offset beyond 16 bits and runs on the wide arrays.  "overlap_isect" -- the column intersections cp_pack_overlap computed.
+ * "round_alloc_rounds" -- DP rounds whose task set-up reserved the lists' offsets itself ("round_alloc"), in every attempt of a layer;
+ * "cr_consume_rounds" / "cr_clear_launches" -- right passes that add a row's counts chunk by chunk and ran without / with the clearing
+ * launch in front ("cr_consume").  All of these are reset when "poison" is switched on and by cp_set_option("stat_reset", 1); reading
  * changes nothing. */
 int32_t cp_get_stat(const char *name, int64_t *out);
 /* Test entry: the launch that ends the counting phase of a DP round, on host arrays.  Exclusive scans of a[0 .. na) and (two != 0)
@@ -334,6 +337,17 @@ int32_t cp_get_stat(const char *name, int64_t *out);
  * as the round's later kernels read them -- after a dropped round {0, 0, 0, 0, 0, 1}. */
 int32_t cp_test_round_scans(const int32_t *a, int64_t na, int64_t na_max, const int32_t *b, int64_t nb, int64_t nb_max, int32_t two,
                             int64_t cap_t, int64_t cap_nt, int32_t err_in, int32_t reps, int64_t *offs_out, int64_t *toffs_out, int64_t *res);
+/* Test entry: the allocation that replaces those scans with "round_alloc" 1, on host arrays.  Lane i of blocks of bs lanes (a
+ * multiple of 64 up to 1024; one block more appends nothing) appends a[i] units to the first list (i < na) and b[i] tiles to the
+ * second (i < nb); every block reserves its slots and its range of units with one atomic per list, and the last block to finish
+ * closes the lists and gives the verdict of cp_test_round_scans (o_cap <= nb: slots of the second list; a count beyond it drops
+ * the round too).  reps launches in a row on one record.  offs_out: na + 1 offsets by slot (the last: the total), slot_a[i]: the
+ * slot of lane i; toffs_out (nb + 1), slot_b likewise; ioffs_out[slot]: the first merge item of the slot's task (ceil(tiles / 2048)
+ * items for every task of more than 16 tiles).  res: {T, NT, nlong, nown, ntile, err, items, the ticket, the two packed words
+ * or-ed (both 0 between launches), 1 if a round of fit_ntask tasks on fit_n columns with "own_min" fit_own_min may take this path}. */
+int32_t cp_test_list_alloc(const int32_t *a, int64_t na, const int32_t *b, int64_t nb, int32_t bs, int64_t cap_t, int64_t cap_nt, int64_t o_cap,
+                           int32_t err_in, int32_t reps, int64_t fit_ntask, int64_t fit_n, int64_t fit_own_min, int64_t *offs_out, int32_t *slot_a,
+                           int64_t *toffs_out, int32_t *slot_b, int32_t *ioffs_out, int64_t *res);
 /* Test entry: the launch that merges the tile partials of a DP round's own-tiled tasks, on host arrays.  Task t of ntask owns the
  * tiles toffs[t] .. toffs[t + 1) (toffs[0] == 0, at least one tile each); tile k has the partial winner {part_v[k]: the 8 bytes of
  * its cost in the model's element type, part_p[k]: its column, < 0 for a tile without a candidate, part_nn[k], part_nl[k]: its
@@ -372,7 +386,10 @@ int32_t cp_test_own_pack(cp_csr_t csr, int32_t *vpk_out, int32_t *vbase_out, int
  * and the gap rounds the own tiles of the planes >= 8 stream only the link entries whose count depends on the row, see
  * cp_test_own_split; 0: whole columns), "own_pair" (1, default: outside the gap rounds and the hyperedge costs a wave of the own-tile
  * stream takes two tiles of the run order, see cp_test_own_pair; 0: one), "own_pack" (1, default: while "own_split" and "own_blk" are 1
- * and the pattern's offsets fit, those tiles read a column's start and prefix sum as one 32-bit word, see cp_test_own_pack; 0: two words), "gap_tau"/"gap_min" (gap passes: rounds and task lengths; -1: none), "gap_nr" (64-row chunks per wave of the gap finish: 1 or 2), "pool" (1, default: freed device blocks of 1 MB and more are kept for reuse by the next call; 0: returned to HIP at once, and the pool is emptied),
+ * and the pattern's offsets fit, those tiles read a column's start and prefix sum as one 32-bit word, see cp_test_own_pack; 0: two words),
+ * "round_alloc" (1, default: the task set-up of a round reserves its lists' offsets with their slots and ends with the round's verdict, see
+ * cp_test_list_alloc; 0: the scan launch of cp_test_round_scans), "cr_consume" (1, default: in layers over all rows the set-up leaves the
+ * right-pass counters zero as it reads them and the clearing launch runs only while they may be dirty; 0: in front of every such pass), "gap_tau"/"gap_min" (gap passes: rounds and task lengths; -1: none), "gap_nr" (64-row chunks per wave of the gap finish: 1 or 2), "pool" (1, default: freed device blocks of 1 MB and more are kept for reuse by the next call; 0: returned to HIP at once, and the pool is emptied),
  * "ra_cache" (round A from counts cached per partition), "nospec" 1 (one host sync per round instead of sizing a layer from the
  * previous one), "rpass_ch"/"rpass_small_tau"/"rpass_cap" (right-part passes: columns per wave, last
  * lane-per-row round, lane-private share of a row in per cent of the mean), "setup_bs" (lanes per block of the task setup), "force_max" (a round whose flattened
