@@ -2,7 +2,9 @@
 DP entry points, BisectCost / BisectIndex / LazyBisectCost with the monotonized model, and the plaid caller -- all bit for bit
 against tests/sym_model.py (definitions and the reference's loops in pure Python).
 
-Shapes: n + 1 = 2^H changes the wavelet level count (n in 63, 64, 65, 255, 256, 257); diagonals full, empty and partial; empty
+Shapes: n in 63, 64, 65, 255, 256, 257, all just past a change of the wavelet level count (H = cllog2(n + 2) grows from n = 2^H - 2,
+where the top key n + 1 is 2^H - 1, to n = 2^H - 1: 62 -> 63, 254 -> 255; tests/test_gpu_count_edges.py has both sides of that
+edge); diagonals full, empty and partial; empty
 columns; one dense row; and one pattern with nnz + n > 2 * 16384 so the lazy stream crosses chunk boundaries and restarts inside a
 chunk after a split."""
 import functools
