@@ -9,7 +9,7 @@ from .types import to_map, to_domain, to_domain_permutation, to_map_permutation 
 from .models import (PowerWorkModel, ConvexWorkModel, ConcaveWorkModel,   # noqa: F401
                      AffineWorkModel, AffinePrimaryConnectivityModel, AffineSecondaryConnectivityModel, AffineConnectivityModel, AffineHyperedgeCutModel,      # noqa: F401
                      AffineSymmetricConnectivityModel, AffineMonotonizedSymmetricConnectivityModel, AffineSymmetricEdgeCutModel,
-                     AffinePrimaryEdgeCutModel, AffineSecondaryEdgeCutModel,
+                     AffinePrimaryEdgeCutModel, AffineSecondaryEdgeCutModel, AffineEnvelopeModel,
                      ColumnBlockComponentCostModel, BlockComponentCostModel, VertexCount, FeasibleCost,
                      ConstrainedCost, EquiSplitter, EquiChunker, StrictChunker, OverlapChunker, DynamicTotalSplitter,
                      DynamicBottleneckSplitter, DynamicTotalChunker, DynamicBottleneckChunker,
@@ -24,5 +24,5 @@ from .models import (PowerWorkModel, ConvexWorkModel, ConcaveWorkModel,   # noqa
 from . import _lib  # noqa: F401
 from . import draws  # noqa: F401
 from .api import (adjointpattern, permute_stripe, permute_plaid, permute, partition_plaid, pack_plaid, partition_stripe, partition_stripe_batch, pack_stripe, pack_stripe_batch, pack_stripe_tables, oracle_stripe, bound_stripe, total_value,   # noqa: F401
-                  bottleneck_value, netcount, selfnetcount, dominancecount, dianetcount, selfpincount, set_default_backend,
+                  bottleneck_value, netcount, selfnetcount, dominancecount, dianetcount, selfpincount, rowenvelope, EnvelopeMatrix, set_default_backend,
                   get_backend, CPError, Step, Same, Next, Prev, Jump)

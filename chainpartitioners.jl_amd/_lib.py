@@ -72,6 +72,10 @@ SIGNATURES = {
     "cp_count_query": (_i32, [_vp, _i64, _I64("a"), _I64("b"), _I64("out")]),
     "cp_count_destroy": (_i32, [_vp]),
     "cp_link_array": (_i32, [_vp, _I64("out")]),
+    "cp_envelope_build": (_i32, [_vp, _pvp]),
+    "cp_envelope_query": (_i32, [_vp, _i64, _I64("j"), _I64("jp"), _I64("lo_out"), _I64("hi_out")]),
+    "cp_envelope_tree": (_i32, [_vp, _I64("dims_out"), _I64("tree_out")]),
+    "cp_envelope_destroy": (_i32, [_vp]),
     "cp_domsum_build": (_i32, [_vp, _i32, _Words("val"), _pvp]),
     "cp_rook_build": (_i32, [_i64, _I64("idx"), _i32, _Words("val"), _i32, _pvp]),
     "cp_wsum_query": (_i32, [_vp, _i64, _I64("i"), _I64("j"), _I64("count_out"), _I64("sum_i64"), _F64("sum_f64")]),
@@ -516,6 +520,32 @@ class HipBackend:
 
     def count_free(self, kind, h):
         self.lib.cp_count_destroy(h)
+
+    # ---- rowenvelope (EnvelopeMatrices.jl)
+    def envelope_build(self, A):
+        h = C.c_void_p()
+        rc = self.lib.cp_envelope_build(self._h(A), C.byref(h))
+        if rc == M.CP_EINVAL:
+            raise AssertionError(f"cp_envelope_build: violated precondition ({self.last_error()})")
+        self._ok(rc, "cp_envelope_build")
+        return h
+
+    def envelope_dims(self, h):
+        dims = np.zeros(3, dtype=np.int64)
+        self._ok(self.lib.cp_envelope_tree(h, dims, None), "cp_envelope_tree")
+        return tuple(int(v) for v in dims)
+
+    def envelope_tree(self, h):
+        H = self.envelope_dims(h)[0]
+        dims, tree = np.zeros(3, dtype=np.int64), np.zeros(((2 << H) - 1, 2), dtype=np.int64)
+        self._ok(self.lib.cp_envelope_tree(h, dims, tree.reshape(-1)), "cp_envelope_tree")
+        return tree
+
+    def envelope_query(self, h, j, jp, lo, hi):
+        return self.lib.cp_envelope_query(h, j.size, j, jp, lo, hi)
+
+    def envelope_free(self, h):
+        self.lib.cp_envelope_destroy(h)
 
     # ---- weighted dominance (a13)
     def domsum_build(self, A, val):

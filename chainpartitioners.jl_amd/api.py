@@ -101,6 +101,27 @@ def _need_hip(b, mdl):
                                   f"'{getattr(b, 'name', type(b).__name__)}'")
 
 
+def _refuse_envelope(fn, method):
+    """The envelope oracle has a 3-argument method only (EnvelopeCosts.jl:66-73): the splitter-order DP and the (non-flip) Bisect
+    splitters can call it, the chunker loops and stack methods (ocl(j, j')) cannot, and the library has no constrained, lazy or
+    flip form for it.  Raised before anything is marshalled, in the words the library's own refusals use (each entry of
+    the library refuses the kind as well: tests/test_gpu_envelope.py calls them directly)."""
+    if not hasattr(method, "f"):
+        return
+    mdl, weight, _ = M.split_constraint(method.f)
+    if not isinstance(mdl, M.AffineEnvelopeModel) and not isinstance(weight, M.AffineEnvelopeModel):
+        return
+    name = type(method).__name__
+    if weight is not None:
+        raise NotImplementedError(f"{fn}({name}): ConstrainedCost with an AffineEnvelopeModel as cost or weight has no device path")
+    served = (isinstance(method, (M.DynamicTotalSplitter, M.DynamicBottleneckSplitter, M.BisectCostBottleneckSplitter, M.BisectIndexBottleneckSplitter))
+              and not getattr(method, "flip", 0) and fn == "partition_stripe")
+    if not served:
+        raise NotImplementedError(f"{fn}({name}): AffineEnvelopeModel has no device path in this method (served: Dynamic{{Total,Bottleneck}}Splitter, "
+                                  f"BisectCostBottleneckSplitter and BisectIndexBottleneckSplitter; the chunker loops call ocl(j, j'), for which "
+                                  f"the envelope oracle has no method)")
+
+
 def _lazy_primary_needs_hip(b, mdl):
     """LazyBisectCost on a primary connectivity model (LazyBisectCostBottleneckSplitter.jl:390-483) is a kernel of the HIP backend;
     the CPU test oracle does not know the pair."""
@@ -162,6 +183,7 @@ def _dispatch(fn, table, head, method, Pi, backend, alloc):
     b = get_backend(backend)
     if hasattr(method, "f"):
         _need_hip(b, M.split_constraint(method.f)[0])
+    _refuse_envelope(fn, method)
     row = next((table[c] for c in type(method).__mro__ if c in table), None)
     if row is None:
         raise NotImplementedError(f"{fn}: method {type(method).__name__} is outside the hot path")
@@ -248,6 +270,7 @@ def partition_stripe_batch(A: SparseMatrixCSC, requests, *, backend=None):
     for _, m in requests:
         if hasattr(m, "f"):
             _need_hip(b, M.split_constraint(m.f)[0])
+        _refuse_envelope("partition_stripe_batch", m)
     if not all(isinstance(m, M.BisectCostBottleneckSplitter) for _, m in requests):
         raise NotImplementedError("partition_stripe_batch takes BisectCostBottleneckSplitter requests")
     if not hasattr(b, "partition_bisect_cost_batch"):
@@ -273,6 +296,7 @@ def pack_stripe_batch(A: SparseMatrixCSC, methods, *, backend=None):
     for m in methods:
         if hasattr(m, "f"):
             _need_hip(b, M.split_constraint(m.f)[0])
+        _refuse_envelope("pack_stripe_batch", m)
     ok = all(isinstance(m, M.ConvexTotalChunker) and isinstance(M.split_constraint(m.f)[1], M.VertexCount) for m in methods)
     if not ok:
         raise NotImplementedError("pack_stripe_batch takes ConvexTotalChunker(ConstrainedCost(f, VertexCount(), w)) requests")
@@ -333,6 +357,7 @@ def pack_stripe_tables(A: SparseMatrixCSC, method, Pi=None, *, backend=None):
         raise NotImplementedError(f"pack_stripe_tables: method {type(method).__name__} is not a DynamicTotalChunker")
     b = get_backend(backend)
     _need_hip(b, M.split_constraint(method.f)[0])
+    _refuse_envelope("pack_stripe_tables", method)
     if not hasattr(b, "pack_dynamic_tables"):
         raise NotImplementedError(f"pack_stripe_tables: backend {b.name} has no tables")
     mdl, mm, wm, wi, wf, rp, keep = _marshal(A, method.f, Pi)
@@ -622,6 +647,54 @@ def selfnetcount(A, hint=None, *, backend=None):
 def dominancecount(A, hint=None, *, backend=None):
     """dominancecount(hint, A)  SparsePrefixMatrices.jl:438-446 : C[i, j] = #{nonzeros row < i, col < j}"""
     return CountMatrix("dom", A, hint or NoHint(), get_backend(backend))
+
+
+class EnvelopeMatrix:
+    """rowenvelope(A) (EnvelopeMatrices.jl:1-57): env[j, j'] -> (lo, hi), the least first row and the greatest last row of the
+    columns j : j'-1, (m + 1, 0) for a range without entries.  The reference's implicit tree, built and walked on the device;
+    .query(j, jp) is the batched getindex, .tree the (2^(H+1) - 1, 2) int64 nodes in the reference's order."""
+
+    def __init__(self, A, backend):
+        self.A, self.backend = A, backend                       # (the matrix keeps the device handle the tree is cached on alive)
+        self.handle = backend.envelope_build(A)
+        self.H, self.m, self.n = backend.envelope_dims(self.handle)
+
+    @property
+    def shape(self):
+        return (self.n + 1, self.n + 1)
+
+    @property
+    def tree(self):
+        return self.backend.envelope_tree(self.handle)
+
+    def query(self, j, jp):
+        """(lo, hi) arrays of env[j[i], jp[i]]"""
+        jj = np.ascontiguousarray(np.atleast_1d(j), dtype=np.int64)
+        jjp = np.ascontiguousarray(np.atleast_1d(jp), dtype=np.int64)
+        if jj.shape != jjp.shape:
+            raise ValueError("query: j and jp must have one shape")
+        lo, hi = np.zeros(jj.shape, dtype=np.int64), np.zeros(jj.shape, dtype=np.int64)
+        rc = self.backend.envelope_query(self.handle, jj, jjp, lo, hi)
+        _check(rc, "envelope query", self.backend)
+        return lo, hi
+
+    def __getitem__(self, jjp):
+        lo, hi = self.query(*jjp)
+        return (int(lo[0]), int(hi[0])) if np.isscalar(jjp[0]) else (lo, hi)
+
+    def __del__(self):
+        try:
+            self.backend.envelope_free(self.handle)
+        except Exception:
+            pass
+
+
+def rowenvelope(A, backend=None):
+    """rowenvelope(A)  EnvelopeMatrices.jl:10-33 (HIP backend only)"""
+    b = get_backend(backend)
+    if not hasattr(b, "envelope_build") or getattr(b, "name", "") != "hip":
+        raise NotImplementedError(f"rowenvelope is implemented by the HIP backend only, not by backend '{getattr(b, 'name', type(b).__name__)}'")
+    return EnvelopeMatrix(A, b)
 
 
 def _sym_count(kind, A, hint, backend):

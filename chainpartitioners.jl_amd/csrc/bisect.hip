@@ -15,6 +15,7 @@
 #include "wavelet.hpp"
 #include "sym.hpp"
 #include "cut.hpp"
+#include "envelope.hpp"
 
 namespace cpk {
 
@@ -308,6 +309,9 @@ int32_t run_bisect(cp_csr_s *A, int64_t K, const cp_model_t *mdl, const cp_rowpa
     SymOracleDev<TC> OS;
     const bool sym = model_is_sym(mdl->kind);
     if (sym) { sym_prepare(A, mdl, SH); memset(&OS, 0, sizeof(OS)); OS.M = HM.d; OS.n = A->n; OS.S = SH.d; }
+    const bool env = model_is_env(mdl->kind);              // (Pi accepted and ignored: Costs.jl:5-7)
+    EnvOracleDev<TC> OE;
+    if (env) { memset(&OE, 0, sizeof(OE)); OE.M = HM.d; OE.n = A->n; OE.E = env_prepare(A); }
     if (mdl->kind == CP_MODEL_CONNECTIVITY || mdl->kind == CP_MODEL_PRIMARY) { ensure_net_counter(A, net); O.has_net = 1; O.net = net.d; }
     const bool cut = model_is_cut(mdl->kind);
     CutOracleDev<TC> OC;
@@ -356,7 +360,9 @@ int32_t run_bisect(cp_csr_s *A, int64_t K, const cp_model_t *mdl, const cp_rowpa
     int64_t *d_lo = buf.p, *d_hi = buf.p + (K + 1), *d_spl = buf.p + 2 * (K + 1), *d_out = buf.p + 3 * (K + 1), *d_np = buf.p + 4 * (K + 1);
     {
         ProfScope ps(PROF_BISECT, s, 0.0);
-        if (cut && by_index) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bisect_index<TC, CutOracleDev<TC>>), dim3(1), dim3(64), 0, s, OC, K, c_lo, c_hi, flip, d_lo, d_hi, d_spl, d_out, d_np);
+        if (env && by_index) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bisect_index<TC, EnvOracleDev<TC>>), dim3(1), dim3(64), 0, s, OE, K, c_lo, c_hi, flip, d_lo, d_hi, d_spl, d_out, d_np);
+        else if (env) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bisect<EnvOracleDev<TC>>), dim3(1), dim3(64), 0, s, OE, K, c_lo, c_hi, eps, flip, d_lo, d_hi, d_spl, d_out, d_np);
+        else if (cut && by_index) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bisect_index<TC, CutOracleDev<TC>>), dim3(1), dim3(64), 0, s, OC, K, c_lo, c_hi, flip, d_lo, d_hi, d_spl, d_out, d_np);
         else if (cut) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bisect<CutOracleDev<TC>>), dim3(1), dim3(64), 0, s, OC, K, c_lo, c_hi, eps, flip, d_lo, d_hi, d_spl, d_out, d_np);
         else if (sym && by_index) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bisect_index<TC, SymOracleDev<TC>>), dim3(1), dim3(64), 0, s, OS, K, c_lo, c_hi, flip, d_lo, d_hi, d_spl, d_out, d_np);
         else if (sym) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_bisect<SymOracleDev<TC>>), dim3(1), dim3(64), 0, s, OS, K, c_lo, c_hi, eps, flip, d_lo, d_hi, d_spl, d_out, d_np);
@@ -426,6 +432,7 @@ extern "C" int32_t cp_partition_bisect_cost_batch(cp_csr_t A, int64_t B, const i
         CP_REQUIRE(A && K && models && eps && spl_out && B >= 1 && B <= 65535, CP_EINVAL, "bad argument");
         for (int64_t b = 0; b < B; b++) {
             CP_REQUIRE(K[b] >= 1 && K[b] + 1 <= ld, CP_EINVAL, "every request needs 1 <= K and K + 1 <= ld");
+            CP_REFUSE_ENV(models + b, "the BisectCost batch");
             CP_REQUIRE((models[b].kind == CP_MODEL_WORK || models[b].kind == CP_MODEL_CONNECTIVITY) && models[b].dtype == models[0].dtype, CP_EUNSUPPORTED,
                        "a batch takes Work / Connectivity models of one element type");
         }
@@ -440,6 +447,8 @@ static int32_t bisect_entry(cp_csr_t A, int64_t K, const cp_model_t *model, cons
 {
     return guarded([&]() -> int32_t {
         CP_REQUIRE(A && model && spl_out && K >= 1, CP_EINVAL, "bad argument");
+        CP_REQUIRE(!(flip && model_is_env(model->kind)), CP_EUNSUPPORTED,
+                   "AffineEnvelopeModel has no device path in the Flip bisections (they search a cost that falls with the part)");
         CP_HIP(hipSetDevice(A->device));
         int64_t li, hi; double lf, hf;
         int32_t rc;

@@ -6,6 +6,7 @@
 #include "weight.hpp"
 #include "sym.hpp"
 #include "cut.hpp"
+#include "envelope.hpp"
 #include <cmath>
 #include <memory>
 
@@ -66,7 +67,7 @@ __global__ void k_apply_model(int64_t nq, const int64_t *__restrict__ P, const i
 // ------------------------------------------------------------------ helpers
 static bool model_known(const cp_model_t *m)
 {
-    if (!m || m->kind < CP_MODEL_FEASIBLE || m->kind > CP_MODEL_SECONDARY_EDGE_CUT) return false;
+    if (!m || m->kind < CP_MODEL_FEASIBLE || m->kind > CP_MODEL_ENVELOPE) return false;
     if (m->kind == CP_MODEL_POWER_WORK) return m->dtype == CP_F64;
     return m->dtype == CP_I64 || m->dtype == CP_F64;
 }
@@ -147,7 +148,8 @@ static int32_t oracle_eval_into(cp_csr_t A, const cp_model_t *model, const cp_ro
 // included, that read the packed words ("own_pack"; layers that were not redone); own_pack_wide: 1 while the pattern of the last split
 // launch has an in-block offset beyond 16 bits and runs on the wide arrays.  overlap_isect: column intersections cp_pack_overlap computed.
 // bn_sym_layers: DP layers the valley search ran for the monotonized symmetric model.  cut_scan_layers: DP layers of the plaid edge-cut
-// models the prefix-min scan ran (plaid_cut.hip).  kept: cp_set_option("poison", 1) starts a
+// models the prefix-min scan ran (plaid_cut.hip).  env_valley_layers: DP layers the valley search ran for the envelope model
+// (envelope.hip).  kept: cp_set_option("poison", 1) starts a
 // poison pass by zeroing the other counters and leaves this one.
 static const struct { const char *name; int64_t *var; bool kept; } g_stats[] = {
     {"spec_redo", &g_spec_redo, false}, {"poison_hits", &g_poison_hits, false}, {"fix_trips", &g_fix_trips, false},
@@ -157,7 +159,7 @@ static const struct { const char *name; int64_t *var; bool kept; } g_stats[] = {
     {"own_pack_tiles", &g_own_pack_tiles, false}, {"own_pack_wide", &g_own_pack_wide, false},
     {"overlap_isect", &g_overlap_isect, false}, {"cut_scan_layers", &g_cut_scan_layers, false},
     {"cr_consume_rounds", &g_cr_consume_rounds, false}, {"cr_clear_launches", &g_cr_clear_launches, false},
-    {"round_alloc_rounds", &g_round_alloc_rounds, false},
+    {"round_alloc_rounds", &g_round_alloc_rounds, false}, {"env_valley_layers", &g_env_valley_layers, false},
 };
 static void stats_reset(bool all) { for (const auto &c : g_stats) if (all || !c.kept) *c.var = 0; }
 
@@ -448,6 +450,15 @@ int32_t cp_partition_dynamic(cp_csr_t A, int64_t K, int32_t combine, int32_t ord
                 return run_cut_dynamic<TC>(A, K, combine, order, model, Pi, spl_out, nullptr, (TC *)nullptr);
             });
         }
+        // the envelope cost: the valley search or the candidate sweep of envelope.hip through the K-layer driver; splitter order only
+        // (the chunker loop calls the oracle with two arguments, for which the reference has no method), no constrained form
+        CP_REQUIRE(!(constrained && model_is_env(weight->kind)), CP_EUNSUPPORTED, "AffineEnvelopeModel has no device path as the weight of a ConstrainedCost");
+        if (model_is_env(model->kind)) {
+            CP_REQUIRE(!constrained, CP_EUNSUPPORTED, "ConstrainedCost over an AffineEnvelopeModel has no device path");
+            CP_REQUIRE(order == CP_ORDER_SPLITTER, CP_EUNSUPPORTED,
+                       "AffineEnvelopeModel: the chunker loop order calls ocl(j, j'), for which the envelope oracle has no method; splitter order only");
+            return run_dynamic(A, K, combine, order, model, spl_out, nullptr, nullptr, nullptr);
+        }
         // the symmetric family: the O(n^2) sweep over the wavelet counters (dp_driver.hip); no constrained form
         CP_REQUIRE(!(constrained && model_is_sym(model->kind)), CP_EUNSUPPORTED, "ConstrainedCost over a symmetric cost model has no device path");
         if (constrained) {
@@ -486,7 +497,7 @@ int32_t cp_dynamic_tables(cp_csr_t A, int64_t K, int32_t combine, const cp_model
             });
         }
         CP_REQUIRE(model->kind == CP_MODEL_WORK || model->kind == CP_MODEL_CONNECTIVITY || model->kind == CP_MODEL_HYPEREDGE_CUT ||
-                       model->kind == CP_MODEL_COLBLOCK || model->kind == CP_MODEL_POWER_WORK || model_is_sym(model->kind),
+                       model->kind == CP_MODEL_COLBLOCK || model->kind == CP_MODEL_POWER_WORK || model_is_sym(model->kind) || model_is_env(model->kind),
                    CP_EUNSUPPORTED, "model kind has no device DP path");
         CP_HIP(hipSetDevice(A->device));
         std::vector<int64_t> spl((size_t)K + 1);
@@ -501,6 +512,8 @@ int32_t cp_dynamic_tables_constrained_combine(cp_csr_t A, int64_t K, int32_t com
     return guarded([&]() -> int32_t {
         CP_REQUIRE(A && ptr_out && win_lo && win_hi && model_known(model) && K >= 1, CP_EINVAL, "bad argument");
         CP_REQUIRE(combine == CP_COMBINE_SUM || combine == CP_COMBINE_MAX, CP_EINVAL, "bad combine");
+        CP_REFUSE_ENV(model, "the constrained DP");
+        CP_REFUSE_ENV(weight, "the constrained DP (as the weight)");
         CP_REQUIRE(!weight || weight->kind == CP_MODEL_VERTEX_COUNT || (weight->kind == CP_MODEL_WORK && !weight->alpha_k), CP_EINVAL,
                    "weight must be VertexCount or an AffineWorkModel");
         const int64_t wv = weight ? width_of_weight(weight, A->n, wmax_i64, wmax_f64) : wmax_i64;      // (null: the width weight)
@@ -534,6 +547,7 @@ int32_t cp_oracle_eval(cp_csr_t A, const cp_model_t *model, const cp_rowpart_t *
             if (model->kind == CP_MODEL_BLOCK) return run_seq_eval<TC>(A, model, Pi, nq, j, jp, k, out);
             if (model_is_cut(model->kind)) return run_cut_eval<TC>(A, model, Pi, nq, j, jp, k, out);
             if (model_is_sym(model->kind)) return run_sym_eval<TC>(A, model, nq, j, jp, k, out);
+            if (model_is_env(model->kind)) return run_env_eval<TC>(A, model, nq, j, jp, k, out);      // (Pi accepted and ignored: Costs.jl:5-7)
             return run_oracle_eval<TC>(A, model, nq, j, jp, k, out);
         });
     });
@@ -619,6 +633,11 @@ int32_t cp_bound_stripe(cp_csr_t A, int64_t K, const cp_model_t *model, int64_t 
             }
             if (model->kind == CP_MODEL_PRIMARY_EDGE_CUT) {                            // PrimaryEdgeCutCosts.jl:28-39
                 int32_t rc = cut_bound_stripe<TC>(A, K, nullptr, model, false, lo, hi);
+                if (rc == CP_OK) also_f64(lo, hi, lo_f64, hi_f64);
+                return rc;
+            }
+            if (model_is_env(model->kind)) {                                           // EnvelopeCosts.jl:43-53
+                int32_t rc = env_bound_stripe<TC>(A, K, model, lo, hi);
                 if (rc == CP_OK) also_f64(lo, hi, lo_f64, hi_f64);
                 return rc;
             }
@@ -738,6 +757,7 @@ int32_t cp_dp_begin(cp_csr_t A, int64_t K, int32_t combine, int32_t order, const
     return guarded([&]() -> int32_t {
         CP_REQUIRE(A && out && model_known(model) && K >= 1, CP_EINVAL, "bad argument");
         CP_REQUIRE(row_lo >= 1 && row_hi >= row_lo && row_hi <= A->n + 2, CP_EINVAL, "row tile must satisfy 1 <= row_lo <= row_hi <= n+2");
+        CP_REFUSE_ENV(model, "the row-tiled DP");
         CP_REQUIRE(model->kind == CP_MODEL_WORK || model->kind == CP_MODEL_CONNECTIVITY || model->kind == CP_MODEL_HYPEREDGE_CUT ||
                        model->kind == CP_MODEL_COLBLOCK, CP_EUNSUPPORTED, "model kind has no device DP path");
         CP_HIP(hipSetDevice(A->device));

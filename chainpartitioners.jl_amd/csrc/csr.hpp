@@ -41,8 +41,13 @@ struct cp_csr_s {
     void *sym_work = nullptr;
     void (*sym_work_free_fn)(void *) = nullptr;
     void (*sym_work_reset_fn)(void *) = nullptr;
+    // the row-envelope tree and sparse table of the envelope cost family: envelope.hpp
+    void *env_work = nullptr;
+    void (*env_work_free_fn)(void *) = nullptr;
+    void (*env_work_reset_fn)(void *) = nullptr;
     ~cp_csr_s()
     {
+        if (env_work && env_work_free_fn) env_work_free_fn(env_work);
         for (int i = 0; i < 2; i++) if (dp_work[i] && dp_work_free_fn[i]) dp_work_free_fn[i](dp_work[i]);
         if (bn_work && bn_work_free_fn) bn_work_free_fn(bn_work);
         if (sym_work && sym_work_free_fn) sym_work_free_fn(sym_work);

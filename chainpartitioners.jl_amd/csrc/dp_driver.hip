@@ -5,6 +5,7 @@
 #include "dp.hpp"
 #include "weight.hpp"
 #include "sym.hpp"
+#include "envelope.hpp"
 #include <memory>
 
 namespace cpk {
@@ -94,6 +95,8 @@ struct DpRun : cp_dp_s {
     DBuf<int64_t> firsts, scan_tmp;
     bool sym = false;                          // a symmetric cost model: every layer is the candidate sweep over the counters (sym.hip)
     SymHost SH;
+    bool env = false;                          // the envelope cost: the valley search (fast_bn) or the candidate sweep of envelope.hip
+    EnvDev ED{};
     int64_t *ptr_tab = nullptr;                // host tables (n+1) x K filled by dump_layer, or null: none asked for
     TC *cst_tab = nullptr;
 
@@ -111,6 +114,19 @@ struct DpRun : cp_dp_s {
         sym = model_is_sym(mdl.kind);
         fast = combine == CP_COMBINE_SUM && fast_total_ok(&mdl, A->n, A->N, K) && !g_opt_force_brute;
         fast_bn = combine == CP_COMBINE_MAX && fast_bottleneck_ok(&mdl, A->n, A->N, K) && !g_opt_force_brute;
+        env = model_is_env(mdl.kind);
+        if (env) {
+            // never the O(n log^2 n) total scheme: the span satisfies the quadrangle inequality in neither direction
+            fast = false;
+            fast_bn = combine == CP_COMBINE_MAX && env_valley_ok(&mdl, A->m, A->n, A->N, K) && !g_opt_force_brute;
+            CP_REQUIRE(fast_bn || A->n <= g_opt_brute_max_n, CP_EUNSUPPORTED,
+                       "AffineEnvelopeModel: the total objective (not Monge) and the bottleneck objective outside the valley gate (a negative beta, "
+                       "wrapping Int64 costs, force_brute) run the O(n^2) device sweep: n too large");
+            ED = env_prepare(A);
+            build_dev_model<TC>(&mdl, HM, A->stream);
+            ptr.alloc((size_t)K * n1());
+            return;
+        }
         if (!fast && !fast_bn)
             CP_REQUIRE(A->n <= g_opt_brute_max_n, CP_EUNSUPPORTED,
                        "model/objective outside the O(n log^2 n) class and n too large for the O(n^2) device sweep");
@@ -135,6 +151,7 @@ struct DpRun : cp_dp_s {
         hipStream_t s = A->stream;
         const int64_t n = A->n;
         if (sym) { sym_layer1<TC>(A, SH.d, HM.d, alpha_of(1), cur, ptr_row(1)); return; }
+        if (env) { env_layer1<TC>(A, ED, HM.d, alpha_of(1), cur, ptr_row(1)); return; }
         const bool has_nets = mdl.kind == CP_MODEL_CONNECTIVITY || mdl.kind == CP_MODEL_HYPEREDGE_CUT || mdl.kind == CP_MODEL_COLBLOCK;
         if (has_nets) {
             cnt0.alloc((size_t)(n > 0 ? n : 1)); firsts.alloc(n1());
@@ -149,7 +166,11 @@ struct DpRun : cp_dp_s {
     // layer k >= 2, rows [rlo, rhi] (0-based), from the previous layer's cost row
     void layer(int64_t k, const TC *prev, TC *cur, int64_t rlo, int64_t rhi, const DpWindow &win = DpWindow())
     {
-        if (sym && fast_bn) {
+        if (env) {
+            if (fast_bn) env_valley_layer<TC>(A, ED, HM.d, alpha_of(k), prev, cur, ptr_row(k), rlo, rhi);
+            else env_sweep_layer<TC>(A, ED, HM.d, alpha_of(k), combine, prev, cur, ptr_row(k), rlo, rhi);
+        }
+        else if (sym && fast_bn) {
             // kind 11 under max: the valley search over D's links and counter, pins from overpos; the formula is Connectivity's slot for slot
             DevModel<TC> Mc = HM.d;
             Mc.kind = CP_MODEL_CONNECTIVITY;

@@ -22,6 +22,7 @@
 //               has no probe_init.
 #include "lazy.hpp"
 #include "sym.hpp"
+#include "envelope.hpp"
 
 namespace cpk {
 
@@ -217,6 +218,7 @@ extern "C" int32_t cp_partition_lazy_bisect_cost_probes(cp_csr_t A, int64_t K, c
 {
     return guarded([&]() -> int32_t {
         CP_REQUIRE(A && model && spl_out && K >= 1, CP_EINVAL, "bad argument");
+        CP_REFUSE_ENV(model, "LazyBisectCost");
         // only AbstractConnectivityModel reaches the specialised method; other models hit the generic one whose g() asserts
         // false for them (LazyBisectCostBottleneckSplitter.jl:486-501)
         CP_REQUIRE(model->kind == CP_MODEL_CONNECTIVITY || model->kind == CP_MODEL_COLBLOCK || model->kind == CP_MODEL_MONO_SYM_CONNECTIVITY, CP_EINVAL,

@@ -18,6 +18,7 @@
 // column and the parts of a split are contiguous: a comparison with the neighbouring entry), so l, the number of columns of [j, j')
 // holding a row of part k, is the flag count since pos[j0], and d_k is the count over all columns.
 #include "lazy.hpp"
+#include "envelope.hpp"
 
 namespace cpk {
 
@@ -208,6 +209,7 @@ extern "C" int32_t cp_partition_lazy_flip_bisect_cost(cp_csr_t A, int64_t K, con
 {
     return guarded([&]() -> int32_t {
         CP_REQUIRE(A && model && spl_out && K >= 1, CP_EINVAL, "bad argument");
+        CP_REFUSE_ENV(model, "LazyFlipBisectCost");
         const int32_t kind = model->kind;
         const bool pri = kind == CP_MODEL_PRIMARY, sec = kind == CP_MODEL_SECONDARY;
         if (!(kind == CP_MODEL_CONNECTIVITY || kind == CP_MODEL_COLBLOCK || pri || sec)) {

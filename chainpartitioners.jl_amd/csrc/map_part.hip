@@ -18,6 +18,7 @@
 //           state lives in LDS up to "greedy_lds_parts" parts and in global memory above.
 #include "csr.hpp"
 #include "model.hpp"
+#include "envelope.hpp"
 #include <rocprim/rocprim.hpp>
 
 namespace cpk {
@@ -406,6 +407,7 @@ extern "C" int32_t cp_partition_greedy_bottleneck(cp_csr_t A, int64_t K, const c
 {
     return guarded([&]() -> int32_t {
         CP_REQUIRE(A && model && (asg_out || A->n == 0), CP_EINVAL, "null argument");
+        CP_REFUSE_ENV(model, "GreedyBottleneckPartitioner");
         CP_REQUIRE(model->kind == CP_MODEL_SECONDARY && (model->dtype == CP_I64 || model->dtype == CP_F64), CP_EUNSUPPORTED,
                    "cp_partition_greedy_bottleneck: the reference has a method for the secondary connectivity model only");
         CP_REQUIRE(K >= 1 && K < ((int64_t)1 << 31), CP_EINVAL, "cp_partition_greedy_bottleneck: K must be at least 1");

@@ -15,6 +15,7 @@
 #include "model.hpp"
 #include "wavelet.hpp"
 #include "dp.hpp"
+#include "envelope.hpp"
 #include <type_traits>
 #include <memory>
 
@@ -1257,6 +1258,8 @@ static bool seq_model_sym(const cp_model_t *m) { return m && m->kind >= CP_MODEL
 static void seq_check(bool args_ok, const cp_model_t *model, const cp_model_t *weight)
 {
     CP_REQUIRE(!seq_model_sym(model), CP_EUNSUPPORTED, "the symmetric cost models have no device path in this method");
+    CP_REFUSE_ENV(model, "this method (the chunkers and the convex / concave splitters call ocl(j, j'), for which the envelope oracle has no method)");
+    CP_REFUSE_ENV(weight, "this method (as the weight of a ConstrainedCost)");
     CP_REQUIRE(args_ok && seq_model_ok(model) && weight_ok(weight), CP_EINVAL, "bad argument");
 }
 // ... and how it leaves for its runner: f(tag) with the model's cost type, on the handle's device
@@ -1307,6 +1310,7 @@ int32_t cp_pack_convex_batch(cp_csr_t A, int64_t B, const cp_model_t *models, co
         CP_REQUIRE(A->n >= 1 && (double)(A->n + 2) * (double)(2 * CW_MAXW + 3) < 2e9, CP_EUNSUPPORTED, "pattern too small / too large for the window table");
         for (int64_t b = 0; b < B; b++) {
             CP_REQUIRE(!seq_model_sym(models + b), CP_EUNSUPPORTED, "the symmetric cost models have no device path in this method");
+            CP_REFUSE_ENV(models + b, "the ConvexTotalChunker batch");
             CP_REQUIRE(seq_model_ok(models + b) && models[b].dtype == models[0].dtype, CP_EINVAL, "bad model in the batch (one element type per batch)");
             CP_REQUIRE((models[b].kind == CP_MODEL_COLBLOCK || models[b].kind == CP_MODEL_CONNECTIVITY || models[b].kind == CP_MODEL_WORK) && !models[b].alpha_k,
                        CP_EUNSUPPORTED, "a batch takes ColumnBlock / Connectivity / Work models without per-part alpha");

@@ -425,6 +425,7 @@ int32_t cp_count_query(cp_count_t h, int64_t nq, const int64_t *a, const int64_t
 {
     try {
         CP_REQUIRE(h && (nq == 0 || (a && b && out)), CP_EINVAL, "bad argument");
+        CP_REQUIRE(h->kind != CP_COUNT_ENVELOPE, CP_EINVAL, "an envelope handle answers cp_envelope_query");
         if (nq == 0) return CP_OK;
         cp_csr_s *A = h->A;
         CP_HIP(hipSetDevice(A->device));

@@ -19,6 +19,7 @@ Mirrors (file:line under /root/reference/src):
   AffineSymmetricEdgeCutModel                   SymmetricEdgeCutCosts.jl:5-18
   AffinePrimaryEdgeCutModel                     PrimaryEdgeCutCosts.jl:5-18
   AffineSecondaryEdgeCutModel                   SecondaryEdgeCutCosts.jl:5-18
+  AffineEnvelopeModel                           EnvelopeCosts.jl:5-20
 
 Julia's constructors `promote` all parameters to one element type (ConnectivityCosts.jl:14-16):
 all-int arguments give an Int64 model, any float gives Float64.  Closures (e.g.
@@ -35,6 +36,7 @@ CP_I64, CP_F64 = 0, 1
  CP_MODEL_SECONDARY) = range(10)
 CP_MODEL_SYM_CONNECTIVITY, CP_MODEL_MONO_SYM_CONNECTIVITY, CP_MODEL_SYM_EDGE_CUT = 10, 11, 12
 CP_MODEL_PRIMARY_EDGE_CUT, CP_MODEL_SECONDARY_EDGE_CUT = 13, 14
+CP_MODEL_ENVELOPE = 15
 CP_COMBINE_SUM, CP_COMBINE_MAX = 0, 1
 CP_ORDER_SPLITTER, CP_ORDER_CHUNKER = 0, 1
 CP_MAX_R = 4
@@ -312,6 +314,24 @@ class AffineSecondaryEdgeCutModel(AffinePrimaryEdgeCutModel):
     """SecondaryEdgeCutCosts.jl:5-18: the cost of giving a range of columns to part k of the SplitPartition Pi of the rows; the
     vertices and pins are those of the part of Pi, the self pins the entries of the range in its rows."""
     kind = CP_MODEL_SECONDARY_EDGE_CUT
+
+
+# ---------------------------------------------------------------- the envelope cost (HIP backend only)
+class AffineEnvelopeModel(_Model):
+    """EnvelopeCosts.jl:5-20: alpha + nv*beta_vertex + np*beta_pin + d*beta_net, d = max(hi - lo, 0) the span between the least
+    first row and the greatest last row of the part's columns (rowenvelope, EnvelopeMatrices.jl:10-57).  Positional or keyword
+    form with zero defaults (:12-14).  `alpha_k` gives a per-part alpha[k]: the reference's 4-argument fallback (:3) makes the
+    part number meaningful.  A row partition passed along is accepted and ignored (Costs.jl:5-7, :17-19)."""
+    kind = CP_MODEL_ENVELOPE
+    hip_only = True
+    fields = ("alpha", "beta_vertex", "beta_pin", "beta_net")
+
+    def __init__(self, alpha=0, beta_vertex=0, beta_pin=0, beta_net=0, alpha_k=None):
+        self._set(alpha, beta_vertex, beta_pin, beta_net, alpha_k=alpha_k)
+
+    def __call__(self, n_vertices, n_pins, n_nets, k=None):
+        a = self.alpha if self.alpha_k is None or k is None else self.alpha_k[k - 1]
+        return a + n_vertices * self.beta_vertex + n_pins * self.beta_pin + n_nets * self.beta_net
 
 
 def _tabulate(f, lo, hi, npdt):

@@ -85,6 +85,19 @@ int32_t cp_count_destroy(cp_count_t h);
 /* the NetCount link array idx'[q] = (n+1) - hst[i] (SparseColorArrays.jl:106-113), for tests */
 int32_t cp_link_array(cp_csr_t csr, int64_t *out /* N */);
 
+/* ---- rowenvelope(A)  EnvelopeMatrices.jl:10-57 ----
+ * env[j, j'] = (least first row, greatest last row) of the columns j : j'-1, (m + 1, 0) for a range without entries.  The handle is
+ * a cp_count_t of kind CP_COUNT_ENVELOPE over the reference's implicit tree, H = cllog2(n), built on the device level by level and kept
+ * in the matrix handle's cache (cp_csr_reset_cache drops it; the next call rebuilds it).  n == 0 is CP_EINVAL (cllog2(0)).  The matrix
+ * handle must outlive it.  cp_envelope_query walks the tree bottom-up as getindex does, 1 <= j <= j' <= n + 1.  cp_envelope_tree copies the
+ * nodes out in the reference's order.  cp_count_query refuses the kind; cp_count_destroy frees it as cp_envelope_destroy does. */
+#define CP_COUNT_ENVELOPE 5
+int32_t cp_envelope_build(cp_csr_t csr, cp_count_t *out);
+int32_t cp_envelope_query(cp_count_t h, int64_t nq, const int64_t *j, const int64_t *jp, int64_t *lo_out, int64_t *hi_out);
+int32_t cp_envelope_tree(cp_count_t h, int64_t *dims_out /* 3: H, m, n */,
+                         int64_t *tree_out /* 2*(2^(H+1)-1): (lo, hi) pairs in the reference's node order; NULL: dims only */);
+int32_t cp_envelope_destroy(cp_count_t h);
+
 /* ---- weighted dominance (used by no cost oracle of the path, kept for the reference's AbstractMatrix API) ----
  * dominancesum(hint, A)                 SparsePrefixMatrices.jl:1-250   S[i, j] = sum(A[1:i-1, 1:j-1])  (test_SparsePrefixMatrices.jl:15)
  * rookcount!(hint, N, idx) / rooksum!(hint, N, idx, val)  :825-1273   the same over ONE point (idx[j], j) per column
@@ -327,7 +340,8 @@ int32_t cp_reset_stream(cp_csr_t csr);
  * offset beyond 16 bits and runs on the wide arrays.  "overlap_isect" -- the column intersections cp_pack_overlap computed.
  * "round_alloc_rounds" -- DP rounds whose task set-up reserved the lists' offsets itself ("round_alloc"), in every attempt of a layer;
  * "cr_consume_rounds" / "cr_clear_launches" -- right passes that add a row's counts chunk by chunk and ran without / with the clearing
- * launch in front ("cr_consume").  All of these are reset when "poison" is switched on and by cp_set_option("stat_reset", 1); reading
+ * launch in front ("cr_consume").  "env_valley_layers" -- DP layers of the envelope model (kind 15) the valley search ran; the
+ * candidate sweep counts none.  All of these are reset when "poison" is switched on and by cp_set_option("stat_reset", 1); reading
  * changes nothing. */
 int32_t cp_get_stat(const char *name, int64_t *out);
 /* Test entry: the launch that ends the counting phase of a DP round, on host arrays.  Exclusive scans of a[0 .. na) and (two != 0)

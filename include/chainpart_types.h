@@ -19,6 +19,7 @@
  *   AffineSymmetricEdgeCutModel                 SymmetricEdgeCutCosts.jl:5-18
  *   AffinePrimaryEdgeCutModel                   PrimaryEdgeCutCosts.jl:5-18
  *   AffineSecondaryEdgeCutModel                 SecondaryEdgeCutCosts.jl:5-18
+ *   AffineEnvelopeModel                         EnvelopeCosts.jl:5-20
  */
 #ifndef CHAINPART_TYPES_H
 #define CHAINPART_TYPES_H
@@ -73,6 +74,13 @@ extern "C" {
                                               as part k (PrimaryEdgeCutCosts.jl:5-18, :51-57); Pi: any partition of the rows */
 #define CP_MODEL_SECONDARY_EDGE_CUT    14  /* the same formula with nv, np the vertices / pins of part k of the SplitPartition Pi of the
                                               ROWS and self the entries of [j, j') in those rows (SecondaryEdgeCutCosts.jl:5-18, :78-85) */
+
+/* the envelope cost: alpha + nv*b_vertex + np*b_pin + d*b_net (b_net in p[CP_P_NET]), d = max(hi - lo, 0) the span between the least
+ * first row and the greatest last row of the columns [j, j') (EnvelopeCosts.jl:5-20, :66-73; rowenvelope: EnvelopeMatrices.jl:10-57);
+ * per-part alpha[k] allowed (the reference's 4-argument fallback, EnvelopeCosts.jl:3); a row partition Pi is accepted and ignored;
+ * HIP backend only.  Served: oracle, bound_stripe (the model form, :43-53), objective, the splitter-order DP, BisectCost and
+ * BisectIndex (non-flip); every other entry returns CP_EUNSUPPORTED */
+#define CP_MODEL_ENVELOPE              15
 
 /* parameter slots of p_i64 / p_f64 */
 #define CP_P_ALPHA      0
