@@ -149,7 +149,7 @@ static int32_t oracle_eval_into(cp_csr_t A, const cp_model_t *model, const cp_ro
 // launch has an in-block offset beyond 16 bits and runs on the wide arrays.  overlap_isect: column intersections cp_pack_overlap computed.
 // bn_sym_layers: DP layers the valley search ran for the monotonized symmetric model.  cut_scan_layers: DP layers of the plaid edge-cut
 // models the prefix-min scan ran (plaid_cut.hip).  env_valley_layers: DP layers the valley search ran for the envelope model
-// (envelope.hip).  kept: cp_set_option("poison", 1) starts a
+// (envelope.hip).  env_dc_layers: layers >= 2 of its total objective the divide and conquer ran (envelope_total.hip).  kept:cp_set_option("poison", 1) starts a
 // poison pass by zeroing the other counters and leaves this one.
 static const struct { const char *name; int64_t *var; bool kept; } g_stats[] = {
     {"spec_redo", &g_spec_redo, false}, {"poison_hits", &g_poison_hits, false}, {"fix_trips", &g_fix_trips, false},
@@ -160,6 +160,7 @@ static const struct { const char *name; int64_t *var; bool kept; } g_stats[] = {
     {"overlap_isect", &g_overlap_isect, false}, {"cut_scan_layers", &g_cut_scan_layers, false},
     {"cr_consume_rounds", &g_cr_consume_rounds, false}, {"cr_clear_launches", &g_cr_clear_launches, false},
     {"round_alloc_rounds", &g_round_alloc_rounds, false}, {"env_valley_layers", &g_env_valley_layers, false},
+    {"env_dc_layers", &g_env_dc_layers, false},
 };
 static void stats_reset(bool all) { for (const auto &c : g_stats) if (all || !c.kept) *c.var = 0; }
 
@@ -183,7 +184,8 @@ static const struct Opt { const char *name; int64_t *var; OptRule rule; int64_t 
     {"gap_split", &g_opt_gap_split, OPT_BOOL, 0, 0},            // (1, default: so do the gap rounds' tiles of those planes -- while own_split is 1; 0: they stream the whole columns)
     {"lws", &g_opt_lws, OPT_BOOL, 0, 0},                        // (1, default: DynamicTotalChunker past the scan by chunk_lws.hip; 0: the one-wave kernel)
     {"rcm_narrow", &g_opt_rcm_narrow, OPT_CLAMP, 0, NOLIM_HI},  // (cp_rcm: BFS levels of at most this many vertices go to the one-workgroup walker; 0: never; beyond its capacity: whenever the level fits)
-    {"greedy_lds_parts", &g_opt_greedy_lds_parts, OPT_CLAMP, 0, 2048},      // (cp_partition_greedy_bottleneck: the walk keeps the part costs and counts in LDS while K <= this; 0: always in global memory)
+    {"env_dc_min_n", &g_opt_env_dc_min_n, OPT_CLAMP, 0, NOLIM_HI},          // (AffineEnvelopeModel, total objective: the smallest n the divide and conquer of envelope_total.hip takes; below, the candidate sweep)
+    {"greedy_lds_parts", &g_opt_greedy_lds_parts, OPT_CLAMP, 0, 2048},     // (cp_partition_greedy_bottleneck: the walk keeps the part costs and counts in LDS while K <= this; 0: always in global memory)
     {"gap_tau", &g_opt_gap_tau, OPT_CLAMP, NOLIM_LO, 20}, {"gap_min", &g_opt_gap_min, OPT_CLAMP, 8, NOLIM_HI}, {"gap_nr", &g_opt_gap_nr, OPT_CLAMP, 1, 2},
     {"force_max", &g_opt_force_max, OPT_CLAMP, 0, NOLIM_HI}, {"rpass_cap", &g_opt_rpass_cap, OPT_CLAMP, 1, NOLIM_HI},
     {"own_min", &g_opt_own_min, OPT_CLAMP, 64, NOLIM_HI}, {"bn_chunk", &g_opt_bn_chunk, OPT_CLAMP, 1, NOLIM_HI},

@@ -96,6 +96,7 @@ struct DpRun : cp_dp_s {
     bool sym = false;                          // a symmetric cost model: every layer is the candidate sweep over the counters (sym.hip)
     SymHost SH;
     bool env = false;                          // the envelope cost: the valley search (fast_bn) or the candidate sweep of envelope.hip
+    bool env_dc = false;                       // ... its total objective by divide and conquer (envelope_total.hip)
     EnvDev ED{};
     int64_t *ptr_tab = nullptr;                // host tables (n+1) x K filled by dump_layer, or null: none asked for
     TC *cst_tab = nullptr;
@@ -116,11 +117,15 @@ struct DpRun : cp_dp_s {
         fast_bn = combine == CP_COMBINE_MAX && fast_bottleneck_ok(&mdl, A->n, A->N, K) && !g_opt_force_brute;
         env = model_is_env(mdl.kind);
         if (env) {
-            // never the O(n log^2 n) total scheme: the span satisfies the quadrangle inequality in neither direction
+            // never the O(n log^2 n) total scheme of dp_total.hip: the span satisfies the quadrangle inequality in neither direction.
+            // The total objective in splitter order splits at the cut column instead (envelope_total.hip)
             fast = false;
             fast_bn = combine == CP_COMBINE_MAX && env_valley_ok(&mdl, A->m, A->n, A->N, K) && !g_opt_force_brute;
-            CP_REQUIRE(fast_bn || A->n <= g_opt_brute_max_n, CP_EUNSUPPORTED,
-                       "AffineEnvelopeModel: the total objective (not Monge) and the bottleneck objective outside the valley gate (a negative beta, "
+            env_dc = combine == CP_COMBINE_SUM && order == CP_ORDER_SPLITTER && !g_opt_force_brute && A->n >= g_opt_env_dc_min_n &&
+                     env_dc_ok(&mdl, A->m, A->n, A->N, K);
+            CP_REQUIRE(fast_bn || env_dc || A->n <= g_opt_brute_max_n, CP_EUNSUPPORTED,
+                       "AffineEnvelopeModel: the total objective outside the divide-and-conquer gate (a non-integral Float64 model, costs past "
+                       "2^60 / 2^51, n < env_dc_min_n, force_brute) and the bottleneck objective outside the valley gate (a negative beta, "
                        "wrapping Int64 costs, force_brute) run the O(n^2) device sweep: n too large");
             ED = env_prepare(A);
             build_dev_model<TC>(&mdl, HM, A->stream);
@@ -168,6 +173,7 @@ struct DpRun : cp_dp_s {
     {
         if (env) {
             if (fast_bn) env_valley_layer<TC>(A, ED, HM.d, alpha_of(k), prev, cur, ptr_row(k), rlo, rhi);
+            else if (env_dc) env_dc_layer<TC>(A, ED, HM.d, alpha_of(k), prev, cur, ptr_row(k), rlo, rhi);
             else env_sweep_layer<TC>(A, ED, HM.d, alpha_of(k), combine, prev, cur, ptr_row(k), rlo, rhi);
         }
         else if (sym && fast_bn) {

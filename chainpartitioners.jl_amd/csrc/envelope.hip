@@ -7,7 +7,8 @@
 // with j' and does not rise with j, the previous layer's costs do not fall, so j -> max(cst[j, k-1], f(j, j', k)) is a valley; its
 // floor is at the first j with cst[j, k-1] >= f(j, j', k) or at the one before, and the reference's winner -- the largest j whose
 // value is the minimum (`<=` at DynamicSplitter.jl:40) -- is found by a second binary search over the previous layer.  The total
-// objective has no such path: the span satisfies the quadrangle inequality in neither direction.
+// objective has no such path: the span satisfies the quadrangle inequality in neither direction; its scalable path
+// splits the span at a cut column instead (envelope_total.hip).
 #include "envelope.hpp"
 #include "dp.hpp"
 #include "wavelet.hpp"
@@ -29,6 +30,7 @@ static void env_work_reset(void *w)
 {
     EnvWork *E = reinterpret_cast<EnvWork *>(w);
     E->have_tree = E->have_table = false;      // (the arrays stay allocated, as the link arrays do)
+    E->dc_kv.release(); E->dc_pv.release(); E->dc_ib.release(); E->dc_bt.release(); E->dc_pa.release();      // (workspace, not a cache: dropped)
 }
 
 EnvWork *env_work_get(cp_csr_s *A)

@@ -28,6 +28,11 @@ struct EnvWork {
     int32_t L = 0;                 // table levels: floor(log2 n) + 1 (0 for n == 0)
     DBuf<int2> tree;               // node t (1-based, the reference's order) at tree[t - 1]; values are the reference's 1-based rows
     DBuf<int2> table;              // level t, start c (0-based) at table[t * n + c]: columns [c, min(c + 2^t, n))
+    // workspace of the divide-and-conquer total layer (envelope_total.hip), dropped with the cache: four keys of 8 B per row, their
+    // in-block tables (6 B per key and row), the tables over block minima (4 B per key, level and block of 64), one-row partials
+    DBuf<int64_t> dc_kv, dc_pv;
+    DBuf<uint8_t> dc_ib;
+    DBuf<int32_t> dc_bt, dc_pa;
 };
 EnvWork *env_work_get(cp_csr_s *A);
 void ensure_env_tree(cp_csr_s *A);         // needs n >= 1 (cllog2(0) has no meaning)
@@ -100,5 +105,14 @@ void env_sweep_layer(cp_csr_s *A, const EnvDev &E, const DevModel<TC> &M, TC alp
 template <typename TC>
 void env_valley_layer(cp_csr_s *A, const EnvDev &E, const DevModel<TC> &M, TC alpha, const TC *W, TC *cst, int32_t *ptr,
                       int64_t r_lo, int64_t r_hi);
+
+// envelope_total.hip: the total objective by divide and conquer over the cut column
+extern int64_t g_env_dc_layers;            // DP layers >= 2 it ran (cp_get_stat("env_dc_layers"))
+extern int64_t g_opt_env_dc_min_n;         // smallest n it takes; below, the candidate sweep (cp_set_option("env_dc_min_n"))
+// are the regrouped sums the literal total DP for this model?  Any sign of the betas; exact integers only
+bool env_dc_ok(const cp_model_t *m, int64_t m_rows, int64_t n, int64_t N, int64_t K);
+// one row (r_lo == r_hi: a single reduction over the candidates) or all rows 0 .. n
+template <typename TC>
+void env_dc_layer(cp_csr_s *A, const EnvDev &E, const DevModel<TC> &M, TC alpha, const TC *W, TC *cst, int32_t *ptr, int64_t r_lo, int64_t r_hi);
 
 }  // namespace cpk

@@ -341,7 +341,8 @@ int32_t cp_reset_stream(cp_csr_t csr);
  * "round_alloc_rounds" -- DP rounds whose task set-up reserved the lists' offsets itself ("round_alloc"), in every attempt of a layer;
  * "cr_consume_rounds" / "cr_clear_launches" -- right passes that add a row's counts chunk by chunk and ran without / with the clearing
  * launch in front ("cr_consume").  "env_valley_layers" -- DP layers of the envelope model (kind 15) the valley search ran; the
- * candidate sweep counts none.  All of these are reset when "poison" is switched on and by cp_set_option("stat_reset", 1); reading
+ * candidate sweep counts none.  "env_dc_layers" -- its DP layers >= 2 under the total objective that the divide and conquer over the
+ * cut column ran (a layer of one row counts).  All of these are reset when "poison" is switched on and by cp_set_option("stat_reset", 1); reading
  * changes nothing. */
 int32_t cp_get_stat(const char *name, int64_t *out);
 /* Test entry: the launch that ends the counting phase of a DP round, on host arrays.  Exclusive scans of a[0 .. na) and (two != 0)
@@ -394,7 +395,10 @@ int32_t cp_test_own_pair(int64_t nt, int64_t wave, int64_t *res);
 int32_t cp_test_own_pack(cp_csr_t csr, int32_t *vpk_out, int32_t *vbase_out, int64_t *res);
 /* Library-wide tunables and test switches; results never depend on them (tests/test_gpu_dynamic.py runs every one against the
  * oracle).  "force_brute" 1: the general O(K n^2) device DP even where the O(K n log^2 n) scheme applies; "brute_max_n": its size
- * limit.  Layer driver of the O(K n log^2 n) scheme: "short_t"/"short_e" (tasks finished during setup),
+ * limit.  "env_dc_min_n" (default 256, the measured crossover with the candidate sweep): the smallest n at which the total objective of
+ * the envelope model (kind 15) in splitter order takes the divide and conquer over the cut column -- exact for Int64 models while
+ * K max|alpha| + n |b_vertex| + N |b_pin| + K m |b_net| < 2^60 and for Float64 models with integral parameters while it is < 2^51, any
+ * sign of the betas; below it, and for every other model of the kind, the candidate sweep up to "brute_max_n".  Layer driver of the O(K n log^2 n) scheme: "short_t"/"short_e" (tasks finished during setup),
  * "own_min" (shortest task with tiles of its own), "own_blk" (1, default: those tiles sit at absolute 256-column blocks and are
  * streamed in block order; 0: tiles counted from each task's head, in task order), "own_split" (1, default: outside the first round
  * and the gap rounds the own tiles of the planes >= 8 stream only the link entries whose count depends on the row, see

@@ -6,6 +6,9 @@
     table (cp_oracle_eval) -- the comparison that says whether the table pays for its 8 B n (floor(log2 n) + 1);
   * partition_stripe(A, 32, DynamicBottleneckSplitter(AffineEnvelopeModel(0, 10, 1, 100))) by the valley search, per call and per layer;
   * the same at n = 2 10^5 by the valley search and by the candidate sweep (force_brute), the split vectors asserted equal;
+  * partition_stripe(A, 32, DynamicTotalSplitter(model)) by the divide and conquer of csrc/envelope_total.hip at both sizes, and at
+    n = 2 10^5 by it and by the candidate sweep, the split vectors asserted equal; the same pair at K = 8 for n = 2^7 .. 2^17 (the
+    table the default of env_dc_min_n rests on);
   * BisectCostBottleneckSplitter(model, 0.01), K = 32;
   * the script pipeline PermutingPartitioner(CuthillMcKeePermuter(), DynamicBottleneckSplitter(model)), K = 32, with the bottleneck
     values with and without the reordering beside it.
@@ -23,6 +26,7 @@ from bench_configs import banded_dev
 
 MDL = cp.AffineEnvelopeModel(0, 10, 1, 100)
 K = 32
+ENV_DC_MIN_N = 256                                             # the library's default of env_dc_min_n (csrc/envelope_total.hip)
 
 
 def clock(f):
@@ -105,6 +109,34 @@ def valley_against_sweep(hip, A, reps):
     return out
 
 
+def total_dp(hip, A, reps):
+    """partition_stripe(A, 32, DynamicTotalSplitter(model)) by the divide and conquer of envelope_total.hip (default options)"""
+    tot = cp.DynamicTotalSplitter(MDL)
+    hip.set_option("stat_reset", 0)
+    r, Phi = timed(hip, lambda: cp.partition_stripe(A, K, tot, backend=hip), reps, "env_dc")
+    r["kernel_ms_per_layer"] = round(r["kernel_ms"] / max(r["launches"], 1), 4)
+    r["env_dc_layers_per_call"] = hip.get_stat("env_dc_layers") // (reps + 1)
+    r["total_value"] = int(cp.total_value(A, Phi, MDL, backend=hip))
+    return {"dynamic_total_K32": r}
+
+
+def total_both_paths(hip, A, k, reps):
+    """the total DP at K = k by the divide and conquer (env_dc_min_n = 0) and by the candidate sweep (force_brute), one after the other"""
+    tot = cp.DynamicTotalSplitter(MDL)
+    out = {"n": A.n, "nnz": A.nnz, "K": k}
+    hip.set_option("env_dc_min_n", 0)
+    try:
+        out["divide_and_conquer"], a = timed(hip, lambda: cp.partition_stripe(A, k, tot, backend=hip), reps, "env_dc")
+        hip.set_option("force_brute", 1)
+        out["sweep"], b = timed(hip, lambda: cp.partition_stripe(A, k, tot, backend=hip), 1 if A.n > 100_000 else reps, "env_sweep")
+    finally:
+        hip.set_option("force_brute", 0)
+        hip.set_option("env_dc_min_n", ENV_DC_MIN_N)
+    assert np.array_equal(a.spl, b.spl), "the divide and conquer and the candidate sweep disagree"
+    out["same_split_vector"] = True
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n-shaped", type=int, default=1_000_000)
@@ -113,24 +145,27 @@ def main():
     ap.add_argument("--n-sweep", type=int, default=200_000)
     ap.add_argument("--queries", type=int, default=1_000_000)
     ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--skip", default="", help="comma list of shaped, banded, sweep")
+    ap.add_argument("--skip", default="", help="comma list of shaped, banded, sweep (families and the n-sweep comparisons); structure, bottleneck, total, "
+                                               "crossover (sections)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r20_envelope.json"))
     args = ap.parse_args()
     skip = set(args.skip.split(","))
     dev = torch.device("cuda", 0)
     hip = cp.get_backend()
     out = {"device": torch.cuda.get_device_name(0), "model": "AffineEnvelopeModel(0, 10, 1, 100)", "K": K, "reps": args.reps,
-           "method": "host clock around synchronising calls, best of reps after a warm call; kernel_ms: HIP events of the profile slot per call"}
+           "method": "host clock around synchronising calls, best of reps after a warm call; kernel_ms: HIP events of the profile slot per call",
+           "note": "one run of this script: single measurements, the spread between runs was not measured"}
     warm = host_matrix(3000, *banded_dev(3000, 4, 0.5, 7, dev))    # code objects
     partitioners(hip, warm, 1); structure(hip, warm, 1, 1000)
 
     def family(tag, A):
         res = {"n": A.n, "nnz": A.nnz}
         hip.csr(A)
-        res.update(structure(hip, A, args.reps, args.queries))
-        print(json.dumps({tag: res}), file=sys.stderr, flush=True)
-        res.update(partitioners(hip, A, args.reps))
-        print(json.dumps({tag: res}), file=sys.stderr, flush=True)
+        for name, section in (("structure", lambda: structure(hip, A, args.reps, args.queries)), ("bottleneck", lambda: partitioners(hip, A, args.reps)),
+                              ("total", lambda: total_dp(hip, A, args.reps))):
+            if name not in skip:
+                res.update(section())
+                print(json.dumps({tag: res}), file=sys.stderr, flush=True)
         return res
     if "shaped" not in skip:
         n = args.n_shaped
@@ -140,7 +175,14 @@ def main():
         out["banded"] = family("banded", host_matrix(n, *banded_dev(n, 16, 0.5, 0xDEADBEEF + 4, dev)))
     if "sweep" not in skip:
         n = args.n_sweep
-        out["valley_against_sweep"] = valley_against_sweep(hip, host_matrix(n, *gen_suitesparse_shaped(n, args.deg * n, 0xDEADBEEF + 2, dev)), args.reps)
+        A = host_matrix(n, *gen_suitesparse_shaped(n, args.deg * n, 0xDEADBEEF + 2, dev))
+        if "bottleneck" not in skip:
+            out["valley_against_sweep"] = valley_against_sweep(hip, A, args.reps)
+        if "total" not in skip:
+            out["total_against_sweep"] = total_both_paths(hip, A, K, args.reps)
+    if "crossover" not in skip:                                # what the default of env_dc_min_n rests on
+        out["total_crossover_K8"] = [total_both_paths(hip, host_matrix(1 << lg, *gen_suitesparse_shaped(1 << lg, args.deg << lg, 0xDEADBEEF + 2, dev)), 8, args.reps)
+                                     for lg in range(7, 18)]
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(out, f, indent=1)
