@@ -149,7 +149,8 @@ static int32_t oracle_eval_into(cp_csr_t A, const cp_model_t *model, const cp_ro
 // launch has an in-block offset beyond 16 bits and runs on the wide arrays.  overlap_isect: column intersections cp_pack_overlap computed.
 // bn_sym_layers: DP layers the valley search ran for the monotonized symmetric model.  cut_scan_layers: DP layers of the plaid edge-cut
 // models the prefix-min scan ran (plaid_cut.hip).  env_valley_layers: DP layers the valley search ran for the envelope model
-// (envelope.hip).  env_dc_layers: layers >= 2 of its total objective the divide and conquer ran (envelope_total.hip).  kept:cp_set_option("poison", 1) starts a
+// (envelope.hip).  env_dc_layers: layers >= 2 of its total objective the divide and conquer ran (envelope_total.hip).  budget_layers:
+// layers >= 2 of the total-cost DP under a work budget that dp_total_budget.hip ran.  kept:cp_set_option("poison", 1) starts a
 // poison pass by zeroing the other counters and leaves this one.
 static const struct { const char *name; int64_t *var; bool kept; } g_stats[] = {
     {"spec_redo", &g_spec_redo, false}, {"poison_hits", &g_poison_hits, false}, {"fix_trips", &g_fix_trips, false},
@@ -160,7 +161,7 @@ static const struct { const char *name; int64_t *var; bool kept; } g_stats[] = {
     {"overlap_isect", &g_overlap_isect, false}, {"cut_scan_layers", &g_cut_scan_layers, false},
     {"cr_consume_rounds", &g_cr_consume_rounds, false}, {"cr_clear_launches", &g_cr_clear_launches, false},
     {"round_alloc_rounds", &g_round_alloc_rounds, false}, {"env_valley_layers", &g_env_valley_layers, false},
-    {"env_dc_layers", &g_env_dc_layers, false},
+    {"env_dc_layers", &g_env_dc_layers, false}, {"budget_layers", &g_budget_layers, false},
 };
 static void stats_reset(bool all) { for (const auto &c : g_stats) if (all || !c.kept) *c.var = 0; }
 
@@ -183,6 +184,10 @@ static const struct Opt { const char *name; int64_t *var; OptRule rule; int64_t 
     {"cr_consume", &g_opt_cr_consume, OPT_BOOL, 0, 0},          // (1, default: full layers leave the right-pass counters zero as set-up reads them, no clearing launch per round; 0: the clear in front of every chunked right pass)
     {"gap_split", &g_opt_gap_split, OPT_BOOL, 0, 0},            // (1, default: so do the gap rounds' tiles of those planes -- while own_split is 1; 0: they stream the whole columns)
     {"lws", &g_opt_lws, OPT_BOOL, 0, 0},                        // (1, default: DynamicTotalChunker past the scan by chunk_lws.hip; 0: the one-wave kernel)
+    {"budget_total", &g_opt_budget_total, OPT_BOOL, 0, 0},      // (1, default: total-cost DP under a pin / work budget by dp_total_budget.hip; 0: the one-wave kernel)
+    {"budget_scan_cells", &g_opt_budget_scan_cells, OPT_CLAMP, 1, NOLIM_HI},      // (that path: a full rectangle of at most this many cells ...
+    {"budget_scan_cols", &g_opt_budget_scan_cols, OPT_CLAMP, 1, NOLIM_HI},        //  ... and columns is scanned whole; default 2^20 / 1024)
+    {"budget_stair_cols", &g_opt_budget_stair_cols, OPT_CLAMP, 1, NOLIM_HI},      // (the partial rows of a block below this many columns are scanned whole; default 1024)
     {"rcm_narrow", &g_opt_rcm_narrow, OPT_CLAMP, 0, NOLIM_HI},  // (cp_rcm: BFS levels of at most this many vertices go to the one-workgroup walker; 0: never; beyond its capacity: whenever the level fits)
     {"env_dc_min_n", &g_opt_env_dc_min_n, OPT_CLAMP, 0, NOLIM_HI},          // (AffineEnvelopeModel, total objective: the smallest n the divide and conquer of envelope_total.hip takes; below, the candidate sweep)
     {"greedy_lds_parts", &g_opt_greedy_lds_parts, OPT_CLAMP, 0, 2048},     // (cp_partition_greedy_bottleneck: the walk keeps the part costs and counts in LDS while K <= this; 0: always in global memory)
@@ -473,6 +478,9 @@ int32_t cp_partition_dynamic(cp_csr_t A, int64_t K, int32_t combine, int32_t ord
             // bottleneck under any monotone work weight (pins, vertices + pins): the valley search with the weight's j0 array (Int64 costs only)
             if (combine == CP_COMBINE_MAX && wv == -2 && monotone_work_weight(weight) && model->dtype == CP_I64 && windowed_ok(A, K, combine, model, 1))
                 return run_dynamic_windowed(A, K, combine, order, model, 0, weight, wmax_i64, wmax_f64, spl_out, nullptr, nullptr, nullptr, nullptr, nullptr);
+            // total cost under such a weight: the two-staircase divide and conquer of dp_total_budget.hip (either cost type, both loop orders)
+            if (combine == CP_COMBINE_SUM && budget_total_ok(A, K, model, weight, wmax_i64, wmax_f64))
+                return run_dynamic_windowed(A, K, combine, order, model, 0, weight, wmax_i64, wmax_f64, spl_out, nullptr, nullptr, nullptr, nullptr, nullptr);
             return with_cost_type(model->dtype, [&](auto tag) {
                 return run_dyn_constrained<decltype(tag)>(A, K, combine, order, model, Pi, weight, wmax_i64, wmax_f64, spl_out);
             });
@@ -519,8 +527,9 @@ int32_t cp_dynamic_tables_constrained_combine(cp_csr_t A, int64_t K, int32_t com
         CP_REQUIRE(!weight || weight->kind == CP_MODEL_VERTEX_COUNT || (weight->kind == CP_MODEL_WORK && !weight->alpha_k), CP_EINVAL,
                    "weight must be VertexCount or an AffineWorkModel");
         const int64_t wv = weight ? width_of_weight(weight, A->n, wmax_i64, wmax_f64) : wmax_i64;      // (null: the width weight)
-        const bool general = wv == -2 && combine == CP_COMBINE_MAX && monotone_work_weight(weight) && model->dtype == CP_I64;
-        CP_REQUIRE(windowed_ok(A, K, combine, model, general ? 1 : wv), CP_EUNSUPPORTED, "outside the windowed scalable path");
+        const bool budget = wv == -2 && combine == CP_COMBINE_SUM && budget_total_ok(A, K, model, weight, wmax_i64, wmax_f64);      // dp_total_budget.hip
+        const bool general = budget || (wv == -2 && combine == CP_COMBINE_MAX && monotone_work_weight(weight) && model->dtype == CP_I64);
+        CP_REQUIRE(budget || windowed_ok(A, K, combine, model, general ? 1 : wv), CP_EUNSUPPORTED, "outside the windowed scalable path");
         CP_HIP(hipSetDevice(A->device));
         std::vector<int64_t> spl((size_t)K + 1);
         return run_dynamic_windowed(A, K, combine, CP_ORDER_SPLITTER, model, general ? 0 : wv, general ? weight : nullptr, wmax_i64, wmax_f64,

@@ -8,13 +8,10 @@
 //
 // A push covers the staircase {(r, p) : p >= lo(r)}, which does NOT keep the monotone argmin, so it is split into full rectangles
 // (push): the rows with lo(r) <= ja see all of [ja, jb] -- a prefix of the rows, lo being non-decreasing -- and the rest recurse
-// into the two halves of the columns.  Every feasible cell lies in exactly one rectangle.  Inside a full rectangle the cost is
-// inverse-Monge for the fast_total_ok models (for p1 < p2 <= jb < r1 < r2, submodularity of the net count gives
-// f(p1, r2) + f(p2, r1) <= f(p1, r1) + f(p2, r2)), so a column that wins or ties at r1 keeps doing so at r2: the leftmost argmin
-// is non-INCREASING in r and the row minima come from the monotone divide and conquer, run level by level (k_lws_level: row i of
-// the level searches [opt(i + h), opt(i - h)], cut into chunks of LWS_CH columns, one wave each; k_lws_fin reduces the chunks).
-// Small rectangles are scanned whole (k_lws_brute), and so is the staircase left of a push below LWS_STAIR_COLS columns
-// (k_lws_stair).  Rectangle cells come from the device counters (wavelet rank queries).
+// into the two halves of the columns.  Every feasible cell lies in exactly one rectangle.  Inside a full rectangle the leftmost
+// argmin is non-INCREASING in r and the row minima come from the monotone divide and conquer of lws_rect.hpp, which this unit
+// shares with dp_total_budget.hip: the rectangle, level and staircase kernels live there, this unit's policy is LwsFirst.  Small
+// rectangles are scanned whole, and so is the staircase left of a push below LWS_STAIR_COLS columns.
 //
 // A leaf of at most 64 * CPT rows runs on one wave, row after row (k_lws_leaf): lane l owns the candidates x + l + 64 k and keeps
 // their counts in registers, updated per new column from the link arrays -- nets grow by #{q in column : prev[q] < p}, self nets by
@@ -24,30 +21,17 @@
 #include "wavelet.hpp"
 #include "weight.hpp"
 #include "dp.hpp"
-#include <algorithm>
+#include "lws_rect.hpp"
 
 namespace cpk {
 
 int64_t g_opt_lws = 1, g_opt_lws_leaf = 512;
 
-static constexpr int LWS_CH = 256;              // columns per wave in a rectangle level
-static constexpr int LWS_LDS_ROWS = 4096;       // levels with at most this many rows find their chunks in LDS
-static constexpr int64_t LWS_BRUTE_CELLS = (int64_t)1 << 20, LWS_BRUTE_COLS = 1024, LWS_STAIR_COLS = 1024;
-
 template <typename TC>
-struct LwsArgs {
-    DevModel<TC> M;
-    TC alpha;
-    int64_t n;
-    int32_t nets, self;
-    const int64_t *pos;
+struct LwsArgs : LwsCounts<TC> {
     const int32_t *prev;                         // link arrays (leaf rows)
-    const int64_t *lpos;
     const int32_t *lfirst;
-    WaveletDev wnet, wself;                      // rank queries (rectangles)
     const int32_t *lo;                           // n + 1 : first candidate of each row
-    TC *bc; int32_t *bp;                         // n + 1 : best pair pushed into each row so far (bp < 0: none)
-    int32_t *opt;                                // n + 1 : leftmost argmin of a row inside the current rectangle
     TC *cst1; int64_t *spl1;                     // the 1-based tables of k_pack_dynamic: cst1[r] = C[r], spl1[r] = p + 1
 };
 
@@ -57,27 +41,19 @@ __device__ __forceinline__ bool lex_less(TC c, int32_t p, TC bc, int32_t bp)
     return p >= 0 && (bp < 0 || c < bc || (c == bc && p < bp));
 }
 
-template <typename TC>
-__device__ __forceinline__ void wave_lexmin(TC &c, int32_t &p)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const TC oc = __shfl_xor(c, o);
-        const int32_t op = __shfl_xor(p, o);
-        if (lex_less(oc, op, c, p)) { c = oc; p = op; }
-    }
-}
+// the policy of lws_rect.hpp: candidates start from the finished C[p], ties go to the smallest p, a block is bounded by lo(r) on the left only
+template <typename TC_>
+struct LwsFirst {
+    using TC = TC_;
+    using Args = LwsArgs<TC>;
+    static __device__ __forceinline__ TC base(const Args &G, int64_t p) { return G.cst1[p]; }
+    static __device__ __forceinline__ bool better(TC c, int32_t p, TC bc, int32_t bp) { return lex_less(c, p, bc, bp); }
+    static __device__ __forceinline__ int64_t stair_lo(const Args &G, int64_t r, int64_t ja) { return G.lo[r] > ja ? (int64_t)G.lo[r] : ja; }
+    static __device__ __forceinline__ int64_t stair_hi(const Args &, int64_t, int64_t jb) { return jb; }
+};
 
-// f(p, r), columns [p, r): the counts of ocl (seq.hip) for a stateless model without per-part alpha
 template <typename TC>
-__device__ __forceinline__ TC lws_f(const LwsArgs<TC> &G, int64_t p, int64_t r)
-{
-    const int64_t np = G.pos[r] - G.pos[p];
-    int64_t nn = 0, nl = 0;
-    if (G.nets) nn = np - wt_count_le(G.wnet, G.n - p, G.pos[r]);
-    if (G.self) nl = wt_count_le(G.wself, G.n - p, G.lpos[r]);
-    return dm_apply(G.M, G.alpha, r - p, np, nn, nl);
-}
+__device__ __forceinline__ void wave_lexmin(TC &c, int32_t &p) { wave_best<LwsFirst<TC>>(c, p); }
 
 // ------------------------------------------------------------------ leaf: rows [x, y], candidates inside the leaf, one wave
 // Nothing a leaf row reads but the costs of its own candidates depends on the rows before it, so the leaf's column pointers, lower
@@ -148,174 +124,17 @@ __global__ void __launch_bounds__(64) k_lws_leaf(LwsArgs<TC> G, int64_t x, int64
     }
 }
 
-// ------------------------------------------------------------------ small full rectangle: rows ra + blockIdx.x, columns [ja, jb]
-template <typename TC>
-__global__ void __launch_bounds__(64) k_lws_brute(LwsArgs<TC> G, int64_t ja, int64_t jb, int64_t ra)
-{
-    const int64_t r = ra + blockIdx.x;
-    TC bc = (TC)0;
-    int32_t bp = -1;
-    for (int64_t p = ja + threadIdx.x; p <= jb; p += 64) {
-        const TC v = cadd(G.cst1[p], lws_f(G, p, r));
-        if (lex_less(v, (int32_t)p, bc, bp)) { bc = v; bp = (int32_t)p; }
-    }
-    wave_lexmin(bc, bp);
-    if (threadIdx.x == 0 && lex_less(bc, bp, G.bc[r], G.bp[r])) { G.bc[r] = bc; G.bp[r] = bp; }
-}
-
-// ------------------------------------------------------------------ small staircase: rows ra + blockIdx.x, columns [max(lo(r), ja), jb]
-// (along a moving lower bound the full rectangles of the decomposition shrink to single cells: below LWS_STAIR_COLS columns the
-// staircase is scanned whole in one launch instead)
-template <typename TC>
-__global__ void __launch_bounds__(64) k_lws_stair(LwsArgs<TC> G, int64_t ja, int64_t jb, int64_t ra)
-{
-    const int64_t r = ra + blockIdx.x;
-    const int64_t a = G.lo[r] > ja ? (int64_t)G.lo[r] : ja;
-    TC bc = (TC)0;
-    int32_t bp = -1;
-    for (int64_t p = a + threadIdx.x; p <= jb; p += 64) {
-        const TC v = cadd(G.cst1[p], lws_f(G, p, r));
-        if (lex_less(v, (int32_t)p, bc, bp)) { bc = v; bp = (int32_t)p; }
-    }
-    wave_lexmin(bc, bp);
-    if (threadIdx.x == 0 && lex_less(bc, bp, G.bc[r], G.bp[r])) { G.bc[r] = bc; G.bp[r] = bp; }
-}
-
-// ------------------------------------------------------------------ large full rectangle: one level of the monotone D&C
-// level h (a power of two): rows i = h - 1 + 2 h u < m of the rectangle (row ra + i); rows i - h and i + h were done on coarser levels
-struct LwsLevel { int64_t ra, m, ja, jb, h, cnt, cap; };
-
-template <typename TC>
-__device__ __forceinline__ void lws_range(const LwsArgs<TC> &G, const LwsLevel &L, int64_t u, int64_t &r, int64_t &lo, int64_t &hi)
-{
-    const int64_t i = L.h - 1 + 2 * L.h * u;
-    r = L.ra + i;
-    lo = i + L.h < L.m ? (int64_t)G.opt[r + L.h] : L.ja;
-    hi = i >= L.h ? (int64_t)G.opt[r - L.h] : L.jb;
-    if (hi < lo) hi = lo;                        // (cannot happen for an inverse-Monge cost)
-}
-
-template <typename TC>
-__global__ void __launch_bounds__(256) k_lws_count(LwsArgs<TC> G, LwsLevel L, int32_t *__restrict__ cnt)
-{
-    const int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (u >= L.cnt) return;
-    int64_t r, lo, hi;
-    lws_range(G, L, u, r, lo, hi);
-    cnt[u] = (int32_t)((hi - lo + LWS_CH) / LWS_CH);
-}
-
-// chunk g of the level: binary search of the row in the chunk offsets off[0..cnt] (in LDS for small levels, else from the scan)
-template <typename TC>
-__global__ void __launch_bounds__(256) k_lws_level(LwsArgs<TC> G, LwsLevel L, int64_t *__restrict__ goff, int32_t lds,
-                                                   TC *__restrict__ pc, int32_t *__restrict__ pq)
-{
-    __shared__ int64_t off[LWS_LDS_ROWS + 1];
-    __shared__ int64_t wsum[256];
-    const int t = threadIdx.x;
-    if (lds) {
-        const int64_t per = (L.cnt + 255) / 256, u0 = t * per;
-        int64_t sum = 0;
-        for (int64_t u = u0; u < u0 + per && u < L.cnt; u++) {
-            int64_t r, lo, hi;
-            lws_range(G, L, u, r, lo, hi);
-            off[u] = sum;
-            sum += (hi - lo + LWS_CH) / LWS_CH;
-        }
-        wsum[t] = sum;
-        __syncthreads();
-        for (int o = 1; o < 256; o <<= 1) {      // inclusive scan of the thread sums
-            const int64_t v = t >= o ? wsum[t - o] : 0;
-            __syncthreads();
-            wsum[t] += v;
-            __syncthreads();
-        }
-        const int64_t base = t > 0 ? wsum[t - 1] : 0;
-        for (int64_t u = u0; u < u0 + per && u < L.cnt; u++) off[u] += base;
-        if (t == 255) off[L.cnt] = wsum[255];
-        __syncthreads();
-        if (blockIdx.x == 0) for (int64_t u = t; u <= L.cnt; u += 256) goff[u] = off[u];
-    }
-    const int64_t *O = lds ? off : goff;
-    const int64_t g = (int64_t)blockIdx.x * 4 + (t >> 6);
-    const int64_t total = O[L.cnt];
-    if (g >= total || g >= L.cap) return;
-    int64_t a = 0, b = L.cnt - 1;                // the last u with off[u] <= g
-    while (a < b) { const int64_t mid = (a + b + 1) >> 1; if (O[mid] <= g) a = mid; else b = mid - 1; }
-    int64_t r, lo, hi;
-    lws_range(G, L, a, r, lo, hi);
-    const int64_t c0 = lo + (g - O[a]) * LWS_CH, c1 = std::min<int64_t>(hi, c0 + LWS_CH - 1);
-    TC bc = (TC)0;
-    int32_t bp = -1;
-    for (int64_t p = c0 + (t & 63); p <= c1; p += 64) {
-        const TC v = cadd(G.cst1[p], lws_f(G, p, r));
-        if (lex_less(v, (int32_t)p, bc, bp)) { bc = v; bp = (int32_t)p; }
-    }
-    wave_lexmin(bc, bp);
-    if ((t & 63) == 0) { pc[g] = bc; pq[g] = bp; }
-}
-
-// one thread per level row: the chunks in order -> opt of the row, merged into its best pair
-template <typename TC>
-__global__ void __launch_bounds__(256) k_lws_fin(LwsArgs<TC> G, LwsLevel L, const int64_t *__restrict__ off, const TC *__restrict__ pc,
-                                                 const int32_t *__restrict__ pq)
-{
-    const int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (u >= L.cnt) return;
-    const int64_t r = L.ra + L.h - 1 + 2 * L.h * u;
-    TC bc = (TC)0;
-    int32_t bp = -1;
-    const int64_t e = std::min<int64_t>(off[u + 1], L.cap);
-    for (int64_t g = off[u]; g < e; g++) if (lex_less(pc[g], pq[g], bc, bp)) { bc = pc[g]; bp = pq[g]; }
-    if (bp < 0) return;
-    G.opt[r] = bp;
-    if (lex_less(bc, bp, G.bc[r], G.bp[r])) { G.bc[r] = bc; G.bp[r] = bp; }
-}
-
 // ------------------------------------------------------------------ host
 template <typename TC>
-struct LwsRun {
+struct LwsRun : LwsRect<LwsFirst<TC>> {
+    using LwsRect<LwsFirst<TC>>::s;
+    using LwsRect<LwsFirst<TC>>::G;
+    using LwsRect<LwsFirst<TC>>::rect;
+    using LwsRect<LwsFirst<TC>>::stair;
+    using LwsRect<LwsFirst<TC>>::launch;
     cp_csr_s *A;
-    hipStream_t s;
-    LwsArgs<TC> G;
     const std::vector<int32_t> *lo;
     int64_t L;
-    DBuf<int64_t> off, scratch;
-    DBuf<int32_t> cnt32, pq;
-    DBuf<TC> pc;
-    int64_t cap;
-
-    template <typename F> void launch(F &&f) { ProfScope ps(PROF_LWS, s, 0.0); f(); }
-
-    void rect(int64_t ja, int64_t jb, int64_t ra, int64_t rb)
-    {
-        const int64_t m = rb - ra + 1, cols = jb - ja + 1;
-        if (cols <= LWS_BRUTE_COLS && m * cols <= LWS_BRUTE_CELLS) {
-            launch([&] { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lws_brute<TC>), dim3((unsigned)m), dim3(64), 0, s, G, ja, jb, ra); });
-            return;
-        }
-        int64_t h = 1;
-        while (2 * h <= m) h *= 2;               // rows h - 1 (+ 2h u) first
-        for (; h >= 1; h /= 2) {
-            LwsLevel Lv;
-            Lv.ra = ra; Lv.m = m; Lv.ja = ja; Lv.jb = jb; Lv.h = h;
-            Lv.cnt = (m - h + 1 + 2 * h - 1) / (2 * h);
-            Lv.cap = std::min<int64_t>(cap, (cols + Lv.cnt + LWS_CH - 1) / LWS_CH + Lv.cnt);
-            const bool lds = Lv.cnt <= LWS_LDS_ROWS;
-            if (!lds) {
-                launch([&] { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lws_count<TC>), dim3((unsigned)cdiv(Lv.cnt, 256)), dim3(256), 0, s, G, Lv, cnt32.p); });
-                launch([&] { exclusive_scan_i32(cnt32.p, off.p, Lv.cnt, scratch, s); });          // (three kernels, one timed step)
-            }
-            launch([&] {
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lws_level<TC>), dim3((unsigned)cdiv(Lv.cap, 4)), dim3(256), 0, s, G, Lv, off.p, (int32_t)lds,
-                                   pc.p, pq.p);
-            });
-            launch([&] {
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lws_fin<TC>), dim3((unsigned)cdiv(Lv.cnt, 256)), dim3(256), 0, s, G, Lv, (const int64_t *)off.p,
-                                   (const TC *)pc.p, (const int32_t *)pq.p);
-            });
-        }
-    }
 
     // the feasible cells of columns [ja, jb] x rows [ra, rb] as full rectangles (rows with lo(r) <= ja see every column)
     void push(int64_t ja, int64_t jb, int64_t ra, int64_t rb)
@@ -326,7 +145,7 @@ struct LwsRun {
         const int64_t r2 = (int64_t)(std::upper_bound(l + ra, l + rb + 1, (int32_t)jb) - l) - 1;     // last row with lo <= jb
         if (r1 >= ra) rect(ja, jb, ra, r1);
         if (r2 > r1 && jb - ja < LWS_STAIR_COLS) {
-            launch([&] { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lws_stair<TC>), dim3((unsigned)(r2 - r1)), dim3(64), 0, s, G, ja, jb, r1 + 1); });
+            stair(ja, jb, r1 + 1, r2 - r1);
         } else if (r2 > r1) {
             const int64_t jm = (ja + jb) / 2;
             push(jm + 1, jb, r1 + 1, r2);
@@ -363,12 +182,7 @@ static int lws_weight_kind(const cp_csr_s *A, const cp_model_t *w, int64_t wi, d
     if (!w || w->kind == CP_MODEL_FEASIBLE) return 0;
     if (w->kind == CP_MODEL_VERTEX_COUNT) { *wv = wi; return wi <= 16 ? -1 : 1; }      // (w <= 16: the (min,+) scan / one-wave kernel)
     if (w->kind != CP_MODEL_WORK || w->alpha_k) return -1;
-    if (w->dtype == CP_I64) {
-        typedef unsigned __int128 u128;
-        auto mag = [](int64_t v) { return v < 0 ? (u128)0 - (u128)(__int128)v : (u128)v; };
-        const u128 b = mag(w->p_i64[CP_P_ALPHA]) + mag(w->p_i64[CP_P_VERTEX]) * (u128)(A->n + 1) + mag(w->p_i64[CP_P_PIN]) * (u128)(A->N + 1) + mag(wi);
-        if (b >= ((u128)1 << 62)) return -1;
-    }
+    if (!work_weight_no_wrap(w, A->n, A->N, wi)) return -1;
     const int64_t v = width_of_weight(w, A->n, wi, wf);
     if (v >= -1) { *wv = v; return 1; }
     return monotone_work_weight(w) ? 2 : -1;
@@ -420,9 +234,7 @@ int32_t run_pack_lws(cp_csr_s *A, const DevModel<TC> &M, const WaveletDev &wnet,
     DBuf<TC> bc((size_t)n1);
     DBuf<int32_t> bp((size_t)n1), opt((size_t)n1);
     CP_HIP(hipMemsetAsync(bp.p, 0xff, bp.bytes(), s));
-    R.cap = (2 * n1 + LWS_CH - 1) / LWS_CH + n1 + 1;
-    R.pc.alloc((size_t)R.cap); R.pq.alloc((size_t)R.cap);
-    R.off.alloc((size_t)n1 + 1); R.cnt32.alloc((size_t)n1);
+    R.reserve(n1);
     LwsArgs<TC> &G = R.G;
     memset(&G, 0, sizeof(G));
     G.M = M; G.alpha = M.p[CP_P_ALPHA]; G.n = n; G.nets = nets; G.self = self;

@@ -19,7 +19,7 @@ ProfSlot g_prof[PROF_NSLOTS] = {
     {"bisect_probe", 0, 0, 0}, {"chunker", 0, 0, 0}, {"dp_rpass", 0, 0, 0}, {"dp_lpass_own", 0, 0, 0}, {"dp_gap_finish", 0, 0, 0}, {"dp_lpass_gap", 0, 0, 0}, {"dp_round_a", 0, 0, 0}, {"dp_leaf", 0, 0, 0}, {"chunk_lws", 0, 0, 0},
     {"chunk_col_neq", 0, 0, 0}, {"chunk_overlap_next", 0, 0, 0}, {"chunk_orbit", 0, 0, 0}, {"chunk_compact", 0, 0, 0},
     {"map_magnetic", 0, 0, 0}, {"map_greedy_setup", 0, 0, 0}, {"map_greedy_gather", 0, 0, 0}, {"map_greedy_walk", 0, 0, 0},
-    {"env_build", 0, 0, 0}, {"env_valley", 0, 0, 0}, {"env_sweep", 0, 0, 0}, {"env_dc", 0, 0, 0}};
+    {"env_build", 0, 0, 0}, {"env_valley", 0, 0, 0}, {"env_sweep", 0, 0, 0}, {"env_dc", 0, 0, 0}, {"dp_budget", 0, 0, 0}};
 bool g_prof_on = false;
 int g_prof_only = -1;
 std::vector<ProfPending> g_prof_pending;
@@ -566,6 +566,7 @@ void drop_cache(cp_csr_s *A)
     if (A->bn_work && A->bn_work_reset_fn) A->bn_work_reset_fn(A->bn_work);
     if (A->sym_work && A->sym_work_reset_fn) A->sym_work_reset_fn(A->sym_work);
     if (A->env_work && A->env_work_reset_fn) A->env_work_reset_fn(A->env_work);
+    if (A->budget_work && A->budget_work_reset_fn) A->budget_work_reset_fn(A->budget_work);
     // (the arrays themselves stay allocated: the next build refills them -- a multi-GB hipFree + hipMalloc pair per call buys nothing)
 }
 

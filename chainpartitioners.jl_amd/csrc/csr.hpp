@@ -45,8 +45,13 @@ struct cp_csr_s {
     void *env_work = nullptr;
     void (*env_work_free_fn)(void *) = nullptr;
     void (*env_work_reset_fn)(void *) = nullptr;
+    // the counters and rectangle scratch of the budget-constrained total-cost layers: dp_total_budget.hip
+    void *budget_work = nullptr;
+    void (*budget_work_free_fn)(void *) = nullptr;
+    void (*budget_work_reset_fn)(void *) = nullptr;
     ~cp_csr_s()
     {
+        if (budget_work && budget_work_free_fn) budget_work_free_fn(budget_work);
         if (env_work && env_work_free_fn) env_work_free_fn(env_work);
         for (int i = 0; i < 2; i++) if (dp_work[i] && dp_work_free_fn[i]) dp_work_free_fn[i](dp_work[i]);
         if (bn_work && bn_work_free_fn) bn_work_free_fn(bn_work);

@@ -29,7 +29,8 @@ using DpBase = ::cp_dp_s;
 struct DpWindow {
     int64_t w = 0;                             // row r takes its candidates from p >= r - w (0: no width)
     int64_t lo = 0, hi = -1;                   // and from the previous layer's row window [lo, hi] (bottleneck; hi < 0: none)
-    const int32_t *j0 = nullptr;               // device array (n + 1): p >= j0[r] instead of the width (bottleneck)
+    const int32_t *j0 = nullptr;               // device array (n + 1): p >= j0[r] instead of the width (a general weight)
+    const int32_t *j0_host = nullptr;          // ... and its host copy (the total-cost layers of dp_total_budget.hip decompose on the host)
 };
 
 // dp_driver.hip: the K-layer drivers.  cst_i64 / cst_f64: the one matching model->dtype is used.
@@ -78,6 +79,20 @@ void dp_bottleneck_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC 
                          const BnPattern *pat = nullptr);      // null: A's own links, counter and pins
 extern int64_t g_opt_bn_wave, g_opt_bn_run, g_opt_bn_slack;    // wave-per-run walk (default) and its rows per wave
 extern int64_t g_opt_bn_chunk;                 // rows per two-pointer walk (one lane each)
+
+// dp_total_budget.hip: one layer of the total-cost DP under a monotone work budget, for the inverse-Monge models at any n.
+// Rows [rlo, rhi] (0-based); row r takes its candidates from max(j0[r], p_lo0) <= p <= min(r, p_hi0), ties -> the largest p; W is
+// read inside [p_lo0, p_hi0] only.  j0_dev / j0_host: the weight's j0 array (k_weight_j0) on both sides.  Only enqueues.
+template <typename TC>
+void dp_total_budget_layer(cp_csr_s *A, const DevModel<TC> &M, TC alpha, const TC *W, TC *cst_out, int32_t *ptr_out, int64_t rlo, int64_t rhi,
+                           int64_t p_lo0, int64_t p_hi0, const int32_t *j0_dev, const int32_t *j0_host);
+// the gate of that path: an inverse-Monge model with exact totals (fast_total_ok) of kind Work / Connectivity / HyperedgeCut, a monotone
+// AffineWorkModel weight without per-part alpha that is not a width and cannot wrap, n < 2^30, N < 2^31 - 1, no force_brute, and
+// cp_set_option("budget_total", 1) (the default)
+bool budget_total_ok(const cp_csr_s *A, int64_t K, const cp_model_t *model, const cp_model_t *weight, int64_t wmax_i64, double wmax_f64);
+extern int64_t g_opt_budget_total;             // 1: on
+extern int64_t g_opt_budget_scan_cells, g_opt_budget_scan_cols, g_opt_budget_stair_cols;      // rectangles within both limits / partial rows of blocks below stair_cols columns are scanned whole
+extern int64_t g_budget_layers;                // layers that path ran since the last reset (cp_get_stat("budget_layers"))
 
 // seq.hip
 template <typename TC>

@@ -185,6 +185,8 @@ struct DpRun : cp_dp_s {
             dp_bottleneck_layer<TC>(A, Mc, alpha_of(k), prev, cur, ptr_row(k), rlo, rhi, win.w, win.lo, win.hi, win.j0, &pat);
         }
         else if (sym) sym_brute_layer<TC>(A, SH.d, HM.d, alpha_of(k), combine, prev, cur, ptr_row(k), rlo, rhi);
+        else if (fast && win.j0)      // a work budget: the limits [win.lo, win.hi] themselves, not the masked row (nothing outside them is read)
+            dp_total_budget_layer<TC>(A, HM.d, alpha_of(k), prev, cur, ptr_row(k), rlo, rhi, win.lo, win.hi, win.j0, win.j0_host);
         else if (fast) dp_total_layer<TC>(A, HM.d, alpha_of(k), prev, cur, ptr_row(k), work, rlo, rhi, win.w);
         else if (fast_bn) dp_bottleneck_layer<TC>(A, HM.d, alpha_of(k), prev, cur, ptr_row(k), rlo, rhi, win.w, win.lo, win.hi, win.j0);
         else dp_brute_layer<TC>(A, HM.d, alpha_of(k), combine, prev, cur, ptr_row(k), rlo, rhi);
@@ -329,7 +331,8 @@ static void weight_windows(int64_t n, int64_t K, const std::vector<int32_t> &j0,
     }
 }
 
-// weight == null: parts of at most `width` columns; else (bottleneck only) the monotone work weight's budget wmax_i64 / wmax_f64
+// weight == null: parts of at most `width` columns; else the monotone work weight's budget wmax_i64 / wmax_f64 (bottleneck: the valley
+// search; total: dp_total_budget.hip -- the caller's gate, budget_total_ok, admitted the pair)
 template <typename TC>
 static int32_t run_dynamic_windowed_t(cp_csr_s *A, int64_t K, int32_t combine, int32_t order, const cp_model_t *mdl, int64_t width,
                                       const cp_model_t *weight, int64_t wmax_i64, double wmax_f64,
@@ -340,8 +343,9 @@ static int32_t run_dynamic_windowed_t(cp_csr_s *A, int64_t K, int32_t combine, i
     const size_t n1 = (size_t)n + 1;
     std::vector<int64_t> lo, hi;
     DBuf<int32_t> j0;
-    if (weight) {                                                        // a general monotone weight (bottleneck only): its j0 array
-        CP_REQUIRE(combine == CP_COMBINE_MAX && weight->kind == CP_MODEL_WORK && !weight->alpha_k, CP_EINTERNAL, "general weights: bottleneck DP only");
+    std::vector<int32_t> hj;
+    if (weight) {                                                        // a general monotone weight: its j0 array
+        CP_REQUIRE(weight->kind == CP_MODEL_WORK && !weight->alpha_k, CP_EINTERNAL, "general weights: an AffineWorkModel without per-part alpha");
         j0.alloc(n1);
         const unsigned gw = (unsigned)cdiv((int64_t)n1, 256);
         if (weight->dtype == CP_I64)
@@ -351,7 +355,7 @@ static int32_t run_dynamic_windowed_t(cp_csr_s *A, int64_t K, int32_t combine, i
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_weight_j0<double>), dim3(gw), dim3(256), 0, s, n, A->pos.p, weight->p_f64[CP_P_ALPHA],
                                weight->p_f64[CP_P_VERTEX], weight->p_f64[CP_P_PIN], wmax_f64, j0.p);
         CP_HIP(hipGetLastError());
-        std::vector<int32_t> hj(n1);
+        hj.resize(n1);
         CP_HIP(hipMemcpyAsync(hj.data(), j0.p, sizeof(int32_t) * n1, hipMemcpyDeviceToHost, s));
         CP_HIP(hipStreamSynchronize(s));
         weight_windows(n, K, hj, lo, hi);
@@ -368,9 +372,10 @@ static int32_t run_dynamic_windowed_t(cp_csr_s *A, int64_t K, int32_t combine, i
     DpRun<TC> D;
     D.begin(A, K, combine, order, mdl);                                  // (windowed_ok admitted the model: never the O(n^2) sweep)
     D.ptr_tab = ptr_tab; D.cst_tab = cst_tab;
+    CP_REQUIRE(!weight || combine == CP_COMBINE_MAX || D.fast, CP_EINTERNAL, "general weights: the total objective needs an inverse-Monge model");
     DpWindow win;
     win.w = weight ? 0 : std::min<int64_t>(width, std::max<int64_t>(n, 1));     // (wider than the matrix: every window is [0, r])
-    win.j0 = j0.p;
+    win.j0 = j0.p; win.j0_host = weight ? hj.data() : nullptr;
     DBuf<TC> cst(n1), Wm(n1);
     D.layer1(cst.p);
     D.dump_layer(1, cst.p, lo[1] - 1, hi[1] - 1, false);

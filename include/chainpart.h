@@ -145,7 +145,11 @@ int32_t cp_objective(cp_csr_t csr, int64_t K, const int64_t *spl, const cp_model
 /* partition_stripe(A, K, Dynamic{Total,Bottleneck}{Splitter,Chunker}(f | ConstrainedCost(f,w,w_max)), [Pi])
  * DynamicSplitter.jl:15-50 (order SPLITTER), :52-87 (order CHUNKER), :206-314 (constrained);
  * Reference{Total,Bottleneck}Splitter (ReferenceSplitter.jl:1-13) are the same entry.  A model whose totals can round (Float64
- * above 2^53) or wrap (Int64 at 2^60 and beyond) has no fast path: above the brute_max_n option it is CP_EUNSUPPORTED, never a guess. */
+ * above 2^53) or wrap (Int64 at 2^60 and beyond) has no fast path: above the brute_max_n option it is CP_EUNSUPPORTED, never a guess.
+ * Constrained, total cost: width weights (VertexCount, AffineWorkModel(alpha, c, 0)) take the windowed O(K n log^2 n) path; any other
+ * AffineWorkModel weight with b_v, b_p >= 0 and no per-part alpha (pins per part, work per part) the two-staircase divide and conquer
+ * of csrc/dp_total_budget.hip -- Work / Connectivity / HyperedgeCut models of the inverse-Monge class with exact totals, either
+ * element type, both loop orders, any n (option "budget_total"); everything else the one-wave literal kernel. */
 int32_t cp_partition_dynamic(cp_csr_t csr, int64_t K, int32_t combine, int32_t order,
                              const cp_model_t *model, const cp_rowpart_t *Pi,
                              const cp_model_t *weight, int64_t wmax_i64, double wmax_f64,
@@ -284,7 +288,9 @@ int32_t cp_dynamic_tables_constrained(cp_csr_t csr, int64_t K, const cp_model_t 
 /* ... with the combine op and the weight given (NULL: VertexCount).  CP_COMBINE_MAX is DynamicBottleneckSplitter(ConstrainedCost(f,
  * w, w_max)) (DynamicSplitter.jl:206-258 with g = max) on the valley search with candidate limits: Int64 cost models; width
  * weights (VertexCount, AffineWorkModel(alpha, c, 0)) or any AffineWorkModel weight with b_v, b_p >= 0 (pins per part).
- * CP_COMBINE_SUM takes width weights only.  w_max in the weight's element type, as in cp_partition_dynamic. */
+ * CP_COMBINE_SUM takes width weights (the windowed path) and, through csrc/dp_total_budget.hip, any AffineWorkModel weight with
+ * b_v, b_p >= 0 and no per-part alpha under the gate named at cp_partition_dynamic, cost models of either element type.  w_max in
+ * the weight's element type, as in cp_partition_dynamic. */
 int32_t cp_dynamic_tables_constrained_combine(cp_csr_t csr, int64_t K, int32_t combine, const cp_model_t *model, const cp_model_t *weight,
                                               int64_t wmax_i64, double wmax_f64, int64_t *win_lo /* K */, int64_t *win_hi /* K */,
                                               int64_t *ptr_out, int64_t *cst_i64, double *cst_f64);
@@ -342,7 +348,8 @@ int32_t cp_reset_stream(cp_csr_t csr);
  * "cr_consume_rounds" / "cr_clear_launches" -- right passes that add a row's counts chunk by chunk and ran without / with the clearing
  * launch in front ("cr_consume").  "env_valley_layers" -- DP layers of the envelope model (kind 15) the valley search ran; the
  * candidate sweep counts none.  "env_dc_layers" -- its DP layers >= 2 under the total objective that the divide and conquer over the
- * cut column ran (a layer of one row counts).  All of these are reset when "poison" is switched on and by cp_set_option("stat_reset", 1); reading
+ * cut column ran (a layer of one row counts).  "budget_layers" -- DP layers >= 2 of the total objective under a pin or work budget that
+ * csrc/dp_total_budget.hip ran (its profile slot is "dp_budget").  All of these are reset when "poison" is switched on and by cp_set_option("stat_reset", 1); reading
  * changes nothing. */
 int32_t cp_get_stat(const char *name, int64_t *out);
 /* Test entry: the launch that ends the counting phase of a DP round, on host arrays.  Exclusive scans of a[0 .. na) and (two != 0)
@@ -417,7 +424,10 @@ int32_t cp_test_own_pack(cp_csr_t csr, int32_t *vpk_out, int32_t *vbase_out, int
  * after one that reproduced its input row are copied), "bn_wave" (bottleneck DP walk: 0 lane per chunk of "bn_chunk" rows, 1 wave
  * per run of "bn_run" rows in lockstep, 2 = default: searched crossings for Int64 costs), "bn_slack" (columns of the start bracket), "lws" (1,
  * default: cp_pack_dynamic past the scan -- any width, a monotone work budget, no constraint -- runs the on-line divide and conquer of
- * csrc/chunk_lws.hip; 0: the one-wave kernel), "lws_leaf" (its rows per leaf wave: 256, 512, 1024 or 2048), "rcm_narrow" (cp_rcm: BFS levels of at most this many
+ * csrc/chunk_lws.hip; 0: the one-wave kernel), "lws_leaf" (its rows per leaf wave: 256, 512, 1024 or 2048), "budget_total" (1, default:
+ * the total-cost DP under a pin or work budget runs the two-staircase divide and conquer of csrc/dp_total_budget.hip; 0: the one-wave
+ * kernel), "budget_scan_cells" / "budget_scan_cols" (that path scans a full rectangle whole while it has at most this many cells and
+ * columns: 2^20 / 1024; at least 1), "budget_stair_cols" (... and the partial rows of a block of fewer columns than this: 1024), "rcm_narrow" (cp_rcm: BFS levels of at most this many
  * vertices are walked by one workgroup, level after level in one launch; 0: every level by grid kernels; a value beyond the walker's
  * capacity of 1024 vertices: whenever the level fits), "greedy_lds_parts" (cp_partition_greedy_bottleneck: the walk keeps the part costs and counts in
  * LDS while K is at most this, default and largest value 2048; 0: always in global memory), "prof_only" slot (events on one profile slot only), "dbg"

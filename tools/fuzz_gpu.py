@@ -71,14 +71,12 @@ while time.time() - t0 < budget:
             # the width weight under its own name, or as a work model alpha + c * width (windowed path too: csrc/weight.hpp width_of_weight)
             wk = int(rng.integers(0, 4))
             c = int(rng.integers(1, 4)); a0 = int(rng.integers(0, 3))
-            # wk 3: a pin-weighted budget (the bottleneck DP takes it on the valley search through the weight's j0 array)
+            # wk 3: a pin-weighted budget (the weight's j0 array: valley search for the bottleneck DP, two-staircase divide and conquer for the total one)
             fc = (cp.ConstrainedCost(f, cp.VertexCount(), w) if wk == 0 else
                   cp.ConstrainedCost(f, cp.AffineWorkModel(a0, c, 0), a0 + c * w + int(rng.integers(0, c))) if wk == 1 else
                   cp.ConstrainedCost(f, cp.AffineWorkModel(0.25 * a0, 0.5 * c, 0.0), 0.25 * a0 + 0.5 * c * w + 0.1) if wk == 2 else
                   cp.ConstrainedCost(f, cp.AffineWorkModel(a0, c - 1, 1), a0 + (c - 1) * w + int(w * max(A.nnz, 1) / max(A.n, 1)) + int(rng.integers(0, 5))))
             for meth in (cp.DynamicTotalSplitter(fc), cp.DynamicTotalChunker(fc), cp.DynamicBottleneckSplitter(fc), cp.DynamicBottleneckChunker(fc)):
-                if wk == 3 and A.n > 600 and meth.combine == 0:
-                    continue                       # (total cost under a pin weight: the one-wave literal kernel, 40 s at n = 6000)
                 if meth.order == 1 and getattr(f, "alpha_k", None) is not None:
                     continue
                 got = cp.partition_stripe(A, K, meth, backend=hip)
