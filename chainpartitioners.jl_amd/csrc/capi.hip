@@ -3,7 +3,6 @@
 #include "csr.hpp"
 #include "model.hpp"
 #include "dp.hpp"
-#include "weight.hpp"
 #include "sym.hpp"
 #include "cut.hpp"
 #include "envelope.hpp"
@@ -464,31 +463,22 @@ int32_t cp_partition_dynamic(cp_csr_t A, int64_t K, int32_t combine, int32_t ord
             CP_REQUIRE(!constrained, CP_EUNSUPPORTED, "ConstrainedCost over an AffineEnvelopeModel has no device path");
             CP_REQUIRE(order == CP_ORDER_SPLITTER, CP_EUNSUPPORTED,
                        "AffineEnvelopeModel: the chunker loop order calls ocl(j, j'), for which the envelope oracle has no method; splitter order only");
-            return run_dynamic(A, K, combine, order, model, spl_out, nullptr, nullptr, nullptr);
+            return run_dynamic(A, K, combine, order, model, spl_out);
         }
         // the symmetric family: the O(n^2) sweep over the wavelet counters (dp_driver.hip); no constrained form
         CP_REQUIRE(!(constrained && model_is_sym(model->kind)), CP_EUNSUPPORTED, "ConstrainedCost over a symmetric cost model has no device path");
         if (constrained) {
             CP_REQUIRE(weight->kind == CP_MODEL_VERTEX_COUNT || (weight->kind == CP_MODEL_WORK && !weight->alpha_k), CP_EINVAL,
                        "weight must be VertexCount or an AffineWorkModel");
-            // width weights (VertexCount, AffineWorkModel(alpha, c, 0)): the equivalent number of columns
-            const int64_t wv = width_of_weight(weight, A->n, wmax_i64, wmax_f64);
-            if (windowed_ok(A, K, combine, model, wv))                          // O(K n log^2 n): the windowed geometry of dp_total.hip
-                return run_dynamic_windowed(A, K, combine, order, model, wv, nullptr, 0, 0, spl_out, nullptr, nullptr, nullptr, nullptr, nullptr);
-            // bottleneck under any monotone work weight (pins, vertices + pins): the valley search with the weight's j0 array (Int64 costs only)
-            if (combine == CP_COMBINE_MAX && wv == -2 && monotone_work_weight(weight) && model->dtype == CP_I64 && windowed_ok(A, K, combine, model, 1))
-                return run_dynamic_windowed(A, K, combine, order, model, 0, weight, wmax_i64, wmax_f64, spl_out, nullptr, nullptr, nullptr, nullptr, nullptr);
-            // total cost under such a weight: the two-staircase divide and conquer of dp_total_budget.hip (either cost type, both loop orders)
-            if (combine == CP_COMBINE_SUM && budget_total_ok(A, K, model, weight, wmax_i64, wmax_f64))
-                return run_dynamic_windowed(A, K, combine, order, model, 0, weight, wmax_i64, wmax_f64, spl_out, nullptr, nullptr, nullptr, nullptr, nullptr);
+            const ConstrainedRoute route = constrained_route(A, K, combine, model, weight, wmax_i64, wmax_f64);
+            if (route.kind != ConstrainedRoute::OneWave)                        // the scalable paths of dp_driver.hip
+                return run_dynamic_windowed(A, K, combine, order, model, route, weight, wmax_i64, wmax_f64, spl_out);
             return with_cost_type(model->dtype, [&](auto tag) {
                 return run_dyn_constrained<decltype(tag)>(A, K, combine, order, model, Pi, weight, wmax_i64, wmax_f64, spl_out);
             });
         }
-        CP_REQUIRE(model->kind == CP_MODEL_WORK || model->kind == CP_MODEL_CONNECTIVITY || model->kind == CP_MODEL_HYPEREDGE_CUT ||
-                       model->kind == CP_MODEL_COLBLOCK || model->kind == CP_MODEL_POWER_WORK || model_is_sym(model->kind),
-                   CP_EUNSUPPORTED, "model kind has no device DP path yet");
-        return run_dynamic(A, K, combine, order, model, spl_out, nullptr, nullptr, nullptr);
+        CP_REQUIRE(dp_takes_kind(model->kind, DP_KINDS_STRIPE), CP_EUNSUPPORTED, "model kind has no device DP path yet");
+        return run_dynamic(A, K, combine, order, model, spl_out);
     });
 }
 
@@ -506,12 +496,12 @@ int32_t cp_dynamic_tables(cp_csr_t A, int64_t K, int32_t combine, const cp_model
                 return run_cut_dynamic<TC>(A, K, combine, CP_ORDER_SPLITTER, model, Pi, spl.data(), ptr_out, pick<TC>(cst_i64, cst_f64));
             });
         }
-        CP_REQUIRE(model->kind == CP_MODEL_WORK || model->kind == CP_MODEL_CONNECTIVITY || model->kind == CP_MODEL_HYPEREDGE_CUT ||
-                       model->kind == CP_MODEL_COLBLOCK || model->kind == CP_MODEL_POWER_WORK || model_is_sym(model->kind) || model_is_env(model->kind),
-                   CP_EUNSUPPORTED, "model kind has no device DP path");
+        CP_REQUIRE(dp_takes_kind(model->kind, DP_KINDS_TABLES), CP_EUNSUPPORTED, "model kind has no device DP path");
         CP_HIP(hipSetDevice(A->device));
         std::vector<int64_t> spl((size_t)K + 1);
-        return run_dynamic(A, K, combine, CP_ORDER_SPLITTER, model, spl.data(), ptr_out, cst_i64, cst_f64);
+        DpTables tabs;
+        tabs.ptr_tab = ptr_out; tabs.cst_i64 = cst_i64; tabs.cst_f64 = cst_f64;
+        return run_dynamic(A, K, combine, CP_ORDER_SPLITTER, model, spl.data(), tabs);
     });
 }
 
@@ -526,14 +516,13 @@ int32_t cp_dynamic_tables_constrained_combine(cp_csr_t A, int64_t K, int32_t com
         CP_REFUSE_ENV(weight, "the constrained DP (as the weight)");
         CP_REQUIRE(!weight || weight->kind == CP_MODEL_VERTEX_COUNT || (weight->kind == CP_MODEL_WORK && !weight->alpha_k), CP_EINVAL,
                    "weight must be VertexCount or an AffineWorkModel");
-        const int64_t wv = weight ? width_of_weight(weight, A->n, wmax_i64, wmax_f64) : wmax_i64;      // (null: the width weight)
-        const bool budget = wv == -2 && combine == CP_COMBINE_SUM && budget_total_ok(A, K, model, weight, wmax_i64, wmax_f64);      // dp_total_budget.hip
-        const bool general = budget || (wv == -2 && combine == CP_COMBINE_MAX && monotone_work_weight(weight) && model->dtype == CP_I64);
-        CP_REQUIRE(budget || windowed_ok(A, K, combine, model, general ? 1 : wv), CP_EUNSUPPORTED, "outside the windowed scalable path");
+        const ConstrainedRoute route = constrained_route(A, K, combine, model, weight, wmax_i64, wmax_f64);      // (null weight: the width wmax_i64)
+        CP_REQUIRE(route.kind != ConstrainedRoute::OneWave, CP_EUNSUPPORTED, "outside the windowed scalable path");
         CP_HIP(hipSetDevice(A->device));
         std::vector<int64_t> spl((size_t)K + 1);
-        return run_dynamic_windowed(A, K, combine, CP_ORDER_SPLITTER, model, general ? 0 : wv, general ? weight : nullptr, wmax_i64, wmax_f64,
-                                    spl.data(), ptr_out, cst_i64, cst_f64, win_lo, win_hi);
+        DpTables tabs;
+        tabs.ptr_tab = ptr_out; tabs.cst_i64 = cst_i64; tabs.cst_f64 = cst_f64; tabs.win_lo = win_lo; tabs.win_hi = win_hi;
+        return run_dynamic_windowed(A, K, combine, CP_ORDER_SPLITTER, model, route, weight, wmax_i64, wmax_f64, spl.data(), tabs);
     });
 }
 
@@ -744,9 +733,6 @@ int32_t cp_bound_stripe_pi(cp_csr_t A, int64_t K, const cp_rowpart_t *Pi, const 
     });
 }
 
-// ---- entry points whose device kernels land in later files; until then they refuse loudly ----
-#define CP_TODO(msg) do { set_error(msg); return CP_EUNSUPPORTED; } while (0)
-
 int32_t cp_link_array(cp_csr_t A, int64_t *out)
 {
     return guarded([&]() -> int32_t {
@@ -769,8 +755,7 @@ int32_t cp_dp_begin(cp_csr_t A, int64_t K, int32_t combine, int32_t order, const
         CP_REQUIRE(A && out && model_known(model) && K >= 1, CP_EINVAL, "bad argument");
         CP_REQUIRE(row_lo >= 1 && row_hi >= row_lo && row_hi <= A->n + 2, CP_EINVAL, "row tile must satisfy 1 <= row_lo <= row_hi <= n+2");
         CP_REFUSE_ENV(model, "the row-tiled DP");
-        CP_REQUIRE(model->kind == CP_MODEL_WORK || model->kind == CP_MODEL_CONNECTIVITY || model->kind == CP_MODEL_HYPEREDGE_CUT ||
-                       model->kind == CP_MODEL_COLBLOCK, CP_EUNSUPPORTED, "model kind has no device DP path");
+        CP_REQUIRE(dp_takes_kind(model->kind, DP_KINDS_TILED), CP_EUNSUPPORTED, "model kind has no device DP path");
         CP_HIP(hipSetDevice(A->device));
         return dp_begin(A, K, combine, order, model, row_lo, row_hi, out);
     });

@@ -1,7 +1,28 @@
-// dp.hpp -- internal interfaces between the DP translation units.
+// dp.hpp -- internal interfaces between the DP translation units: the engine a K-layer run takes (DpPath), the route of a
+// ConstrainedCost (ConstrainedRoute), the drivers' entries and the per-layer functions of every engine.
 #pragma once
 #include "csr.hpp"
 #include "model.hpp"
+
+namespace cpk {
+
+// The engine that runs the layers k >= 2 of a K-layer DP.  dp_path (dp_driver.hip) is the one place that decides it; the gates it
+// combines stay with their arguments: fast_total_ok (model.hpp), fast_bottleneck_ok (dp_driver.hip), env_valley_ok (envelope.hip),
+// env_dc_ok (envelope_total.hip).
+enum class DpPath {
+    Total,         // dp_total.hip: the O(n log^2 n) scheme for inverse-Monge totals; under a weight's j0 array dp_total_budget.hip
+    Valley,        // dp_bottleneck.hip: the valley search for bottleneck costs that grow with their part
+    SymValley,     // ... over the derived pattern of the monotonized symmetric model (sym.hpp)
+    SymSweep,      // sym.hip: the O(n^2) candidate sweep over the symmetric counters
+    EnvValley,     // envelope.hip: the valley search of the envelope cost
+    EnvDc,         // envelope_total.hip: its total objective by divide and conquer
+    EnvSweep,      // envelope.hip: its O(n^2) candidate sweep
+    Sweep,         // dp_brute.hip: the general O(n^2) sweep
+};
+// Pure: no allocation, no launch.  Raises CP_EUNSUPPORTED where only a sweep is left and n > brute_max_n.
+DpPath dp_path(const cp_csr_s *A, int64_t K, int32_t combine, int32_t order, const cp_model_t *model);
+
+}  // namespace cpk
 
 // The handle of the row-tiled step protocol (cp_dp_t) and the base of the K-layer driver DpRun<TC> (dp_driver.hip): what does not
 // depend on the cost type.
@@ -9,7 +30,7 @@ struct cp_dp_s {
     cp_csr_s *A = nullptr;
     int64_t K = 0;
     int32_t combine = 0, order = 0;
-    bool fast = false, fast_bn = false, need_self = false;      // O(n log^2 n) total / valley-search bottleneck / neither: the O(n^2) sweep
+    cpk::DpPath path = cpk::DpPath::Sweep;     // the engine of the layers k >= 2 (dp_path)
     void *work = nullptr;                      // scratch of the total-cost layers (dp_total_work_get)
     cpk::DBuf<int32_t> ptr;                    // K x (n+1) argmins; a step handle fills only its tile rows of layers >= 2
     // step protocol only
@@ -33,13 +54,31 @@ struct DpWindow {
     const int32_t *j0_host = nullptr;          // ... and its host copy (the total-cost layers of dp_total_budget.hip decompose on the host)
 };
 
-// dp_driver.hip: the K-layer drivers.  cst_i64 / cst_f64: the one matching model->dtype is used.
-int32_t run_dynamic(cp_csr_s *A, int64_t K, int32_t combine, int32_t order, const cp_model_t *mdl, int64_t *spl_out,
-                    int64_t *ptr_tab, int64_t *cst_i64, double *cst_f64);
-bool windowed_ok(cp_csr_s *A, int64_t K, int32_t combine, const cp_model_t *model, int64_t wmax);      // the gate of:
-int32_t run_dynamic_windowed(cp_csr_s *A, int64_t K, int32_t combine, int32_t order, const cp_model_t *mdl, int64_t width,
-                             const cp_model_t *weight, int64_t wmax_i64, double wmax_f64, int64_t *spl_out, int64_t *ptr_tab,
-                             int64_t *cst_i64, double *cst_f64, int64_t *win_lo, int64_t *win_hi);
+// How the DP under ConstrainedCost(f, weight, w_max) runs (constrained_route, dp_driver.hip: the one place that decides it).
+struct ConstrainedRoute {
+    enum Kind {
+        OneWave,   // outside the scalable paths: the one-wave literal kernel (run_dyn_constrained, seq.hip)
+        Width,     // parts of at most `width` columns: the windowed geometry of dp_total.hip (sum), the valley search with r - width (max)
+        Weight,    // the weight's j0 array: the budget divide and conquer of dp_total_budget.hip (sum), the valley search (max)
+    } kind;
+    int64_t width;
+};
+// weight == null: the width w_max = wmax_i64 itself
+ConstrainedRoute constrained_route(cp_csr_s *A, int64_t K, int32_t combine, const cp_model_t *model, const cp_model_t *weight,
+                                   int64_t wmax_i64, double wmax_f64);
+
+// optional host tables of the drivers below, (n + 1) x K and K entries; cst_i64 / cst_f64: the one matching model->dtype is used
+struct DpTables {
+    int64_t *ptr_tab = nullptr, *cst_i64 = nullptr;
+    double *cst_f64 = nullptr;
+    int64_t *win_lo = nullptr, *win_hi = nullptr;          // the layers' row windows (run_dynamic_windowed)
+};
+
+// dp_driver.hip: the K-layer drivers.
+int32_t run_dynamic(cp_csr_s *A, int64_t K, int32_t combine, int32_t order, const cp_model_t *mdl, int64_t *spl_out, const DpTables &tabs = DpTables());
+// route: Width or Weight (constrained_route admitted the pair: never an O(n^2) sweep)
+int32_t run_dynamic_windowed(cp_csr_s *A, int64_t K, int32_t combine, int32_t order, const cp_model_t *mdl, ConstrainedRoute route,
+                             const cp_model_t *weight, int64_t wmax_i64, double wmax_f64, int64_t *spl_out, const DpTables &tabs = DpTables());
 int32_t dp_begin(cp_csr_s *A, int64_t K, int32_t combine, int32_t order, const cp_model_t *model, int64_t row_lo, int64_t row_hi,
                  cp_dp_s **out);
 

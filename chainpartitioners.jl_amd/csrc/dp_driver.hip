@@ -1,5 +1,7 @@
-// dp_driver.hip -- the K-layer dynamic programme of DynamicSplitter.jl:15-50.  One driver object, DpRun<TC>, knows how a layer is run;
-// the one-shot (run_dynamic), windowed (run_dynamic_windowed) and row-tiled step (dp_begin / cp_dp_s::step_layer) entries loop over it.
+// dp_driver.hip -- the K-layer dynamic programme of DynamicSplitter.jl:15-50.  dp_path decides the engine of a run and
+// constrained_route how a ConstrainedCost runs: the only two places that combine the models' gates with the objective, the loop order
+// and the options.  One driver object, DpRun<TC>, prepares what its path needs and switches on it per layer; the one-shot
+// (run_dynamic), windowed (run_dynamic_windowed) and row-tiled step (dp_begin / cp_dp_s::step_layer) entries loop over it.
 #include "csr.hpp"
 #include "model.hpp"
 #include "dp.hpp"
@@ -83,9 +85,34 @@ static bool fast_bottleneck_ok(const cp_model_t *m, int64_t n, int64_t N, int64_
     return false;
 }
 
+// ------------------------------------------------------------------ the path decision
+DpPath dp_path(const cp_csr_s *A, int64_t K, int32_t combine, int32_t order, const cp_model_t *m)
+{
+    // (force_brute: every scalable engine off)
+    const bool total = combine == CP_COMBINE_SUM && !g_opt_force_brute, bottleneck = combine == CP_COMBINE_MAX && !g_opt_force_brute;
+    if (model_is_env(m->kind)) {
+        // never the O(n log^2 n) total scheme of dp_total.hip: the span satisfies the quadrangle inequality in neither direction.
+        // The total objective in splitter order splits at the cut column instead (envelope_total.hip)
+        if (bottleneck && env_valley_ok(m, A->m, A->n, A->N, K)) return DpPath::EnvValley;
+        if (total && order == CP_ORDER_SPLITTER && A->n >= g_opt_env_dc_min_n && env_dc_ok(m, A->m, A->n, A->N, K)) return DpPath::EnvDc;
+        CP_REQUIRE(A->n <= g_opt_brute_max_n, CP_EUNSUPPORTED,
+                   "AffineEnvelopeModel: the total objective outside the divide-and-conquer gate (a non-integral Float64 model, costs past "
+                   "2^60 / 2^51, n < env_dc_min_n, force_brute) and the bottleneck objective outside the valley gate (a negative beta, "
+                   "wrapping Int64 costs, force_brute) run the O(n^2) device sweep: n too large");
+        return DpPath::EnvSweep;
+    }
+    const bool sym = model_is_sym(m->kind);        // (of that family only the monotonized model passes a gate: fast_bottleneck_ok)
+    if (total && fast_total_ok(m, A->n, A->N, K)) return DpPath::Total;
+    if (bottleneck && fast_bottleneck_ok(m, A->n, A->N, K)) return sym ? DpPath::SymValley : DpPath::Valley;
+    CP_REQUIRE(A->n <= g_opt_brute_max_n, CP_EUNSUPPORTED,
+               "model/objective outside the O(n log^2 n) class and n too large for the O(n^2) device sweep");
+    return sym ? DpPath::SymSweep : DpPath::Sweep;
+}
+
 // ------------------------------------------------------------------ the driver object
-// One K-layer run for cost type TC: the path choice, the device model, the argmin table and how a layer is launched.  layer1() and
-// layer() only enqueue; who waits for the stream, and when, is the entry's business (the one-shot entries never wait per layer).
+// One K-layer run for cost type TC: the path, what it needs prepared, the device model, the argmin table and how a layer is launched.
+// layer1() and layer() only enqueue; who waits for the stream, and when, is the entry's business (the one-shot entries never wait per
+// layer).
 template <typename TC>
 struct DpRun : cp_dp_s {
     cp_model_t mdl{};                          // own copy (with its alphas): a step handle outlives the caller's struct
@@ -93,11 +120,8 @@ struct DpRun : cp_dp_s {
     HostModel<TC> HM;
     DBuf<int32_t> cnt0;                        // layer-1 scratch: stays until the stream has run layer 1
     DBuf<int64_t> firsts, scan_tmp;
-    bool sym = false;                          // a symmetric cost model: every layer is the candidate sweep over the counters (sym.hip)
-    SymHost SH;
-    bool env = false;                          // the envelope cost: the valley search (fast_bn) or the candidate sweep of envelope.hip
-    bool env_dc = false;                       // ... its total objective by divide and conquer (envelope_total.hip)
-    EnvDev ED{};
+    SymHost SH;                                // the symmetric paths' counters (sym_prepare)
+    EnvDev ED{};                               // the envelope paths' tree (env_prepare)
     int64_t *ptr_tab = nullptr;                // host tables (n+1) x K filled by dump_layer, or null: none asked for
     TC *cst_tab = nullptr;
 
@@ -111,37 +135,21 @@ struct DpRun : cp_dp_s {
             alpha_k_host.assign((const TC *)model->alpha_k, (const TC *)model->alpha_k + model->n_alpha_k);
             mdl.alpha_k = alpha_k_host.data();
         }
-        need_self = mdl.kind == CP_MODEL_HYPEREDGE_CUT;
-        sym = model_is_sym(mdl.kind);
-        fast = combine == CP_COMBINE_SUM && fast_total_ok(&mdl, A->n, A->N, K) && !g_opt_force_brute;
-        fast_bn = combine == CP_COMBINE_MAX && fast_bottleneck_ok(&mdl, A->n, A->N, K) && !g_opt_force_brute;
-        env = model_is_env(mdl.kind);
-        if (env) {
-            // never the O(n log^2 n) total scheme of dp_total.hip: the span satisfies the quadrangle inequality in neither direction.
-            // The total objective in splitter order splits at the cut column instead (envelope_total.hip)
-            fast = false;
-            fast_bn = combine == CP_COMBINE_MAX && env_valley_ok(&mdl, A->m, A->n, A->N, K) && !g_opt_force_brute;
-            env_dc = combine == CP_COMBINE_SUM && order == CP_ORDER_SPLITTER && !g_opt_force_brute && A->n >= g_opt_env_dc_min_n &&
-                     env_dc_ok(&mdl, A->m, A->n, A->N, K);
-            CP_REQUIRE(fast_bn || env_dc || A->n <= g_opt_brute_max_n, CP_EUNSUPPORTED,
-                       "AffineEnvelopeModel: the total objective outside the divide-and-conquer gate (a non-integral Float64 model, costs past "
-                       "2^60 / 2^51, n < env_dc_min_n, force_brute) and the bottleneck objective outside the valley gate (a negative beta, "
-                       "wrapping Int64 costs, force_brute) run the O(n^2) device sweep: n too large");
+        path = dp_path(A, K, combine, order, &mdl);
+        switch (path) {
+        case DpPath::EnvValley: case DpPath::EnvDc: case DpPath::EnvSweep:
             ED = env_prepare(A);
-            build_dev_model<TC>(&mdl, HM, A->stream);
-            ptr.alloc((size_t)K * n1());
-            return;
+            break;
+        default:
+            ensure_links(A);
+            if (hyperedge()) ensure_self(A);
+            if (model_is_sym(mdl.kind)) sym_prepare(A, &mdl, SH);
+            if (path == DpPath::Total) work = dp_total_work_get<TC>(A);       // (kept in the matrix handle between calls)
         }
-        if (!fast && !fast_bn)
-            CP_REQUIRE(A->n <= g_opt_brute_max_n, CP_EUNSUPPORTED,
-                       "model/objective outside the O(n log^2 n) class and n too large for the O(n^2) device sweep");
-        ensure_links(A);
-        if (need_self) ensure_self(A);
-        if (sym) sym_prepare(A, &mdl, SH);
         build_dev_model<TC>(&mdl, HM, A->stream);
         ptr.alloc((size_t)K * n1());
-        if (fast) work = dp_total_work_get<TC>(A);       // (kept in the matrix handle between calls)
     }
+    bool hyperedge() const { return mdl.kind == CP_MODEL_HYPEREDGE_CUT; }      // the kind that reads the self-net arrays (ensure_self)
 
     // splitter order passes the part index (per-part alpha[k]); the chunker loop order calls f(j,j') (DynamicSplitter.jl:64)
     TC alpha_of(int64_t k) const
@@ -155,8 +163,11 @@ struct DpRun : cp_dp_s {
     {
         hipStream_t s = A->stream;
         const int64_t n = A->n;
-        if (sym) { sym_layer1<TC>(A, SH.d, HM.d, alpha_of(1), cur, ptr_row(1)); return; }
-        if (env) { env_layer1<TC>(A, ED, HM.d, alpha_of(1), cur, ptr_row(1)); return; }
+        switch (path) {
+        case DpPath::SymValley: case DpPath::SymSweep: sym_layer1<TC>(A, SH.d, HM.d, alpha_of(1), cur, ptr_row(1)); return;
+        case DpPath::EnvValley: case DpPath::EnvDc: case DpPath::EnvSweep: env_layer1<TC>(A, ED, HM.d, alpha_of(1), cur, ptr_row(1)); return;
+        default: break;                        // Total, Valley, Sweep: the column scan below
+        }
         const bool has_nets = mdl.kind == CP_MODEL_CONNECTIVITY || mdl.kind == CP_MODEL_HYPEREDGE_CUT || mdl.kind == CP_MODEL_COLBLOCK;
         if (has_nets) {
             cnt0.alloc((size_t)(n > 0 ? n : 1)); firsts.alloc(n1());
@@ -164,32 +175,37 @@ struct DpRun : cp_dp_s {
             exclusive_scan_i32(cnt0.p, firsts.p, n, scan_tmp, s);
         }
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_layer1<TC>), dim3((unsigned)cdiv(n + 1, 256)), dim3(256), 0, s, n, A->pos.p,
-                           has_nets ? firsts.p : nullptr, need_self ? A->lpos.p : nullptr, HM.d, alpha_of(1), cur, ptr_row(1));
+                           has_nets ? firsts.p : nullptr, hyperedge() ? A->lpos.p : nullptr, HM.d, alpha_of(1), cur, ptr_row(1));
         CP_HIP(hipGetLastError());
     }
 
     // layer k >= 2, rows [rlo, rhi] (0-based), from the previous layer's cost row
     void layer(int64_t k, const TC *prev, TC *cur, int64_t rlo, int64_t rhi, const DpWindow &win = DpWindow())
     {
-        if (env) {
-            if (fast_bn) env_valley_layer<TC>(A, ED, HM.d, alpha_of(k), prev, cur, ptr_row(k), rlo, rhi);
-            else if (env_dc) env_dc_layer<TC>(A, ED, HM.d, alpha_of(k), prev, cur, ptr_row(k), rlo, rhi);
-            else env_sweep_layer<TC>(A, ED, HM.d, alpha_of(k), combine, prev, cur, ptr_row(k), rlo, rhi);
-        }
-        else if (sym && fast_bn) {
+        switch (path) {
+        case DpPath::Total:
+            if (win.j0)       // a work budget: the limits [win.lo, win.hi] themselves, not the masked row (nothing outside them is read)
+                dp_total_budget_layer<TC>(A, HM.d, alpha_of(k), prev, cur, ptr_row(k), rlo, rhi, win.lo, win.hi, win.j0, win.j0_host);
+            else dp_total_layer<TC>(A, HM.d, alpha_of(k), prev, cur, ptr_row(k), work, rlo, rhi, win.w);
+            break;
+        case DpPath::Valley:
+            dp_bottleneck_layer<TC>(A, HM.d, alpha_of(k), prev, cur, ptr_row(k), rlo, rhi, win.w, win.lo, win.hi, win.j0);
+            break;
+        case DpPath::SymValley: {
             // kind 11 under max: the valley search over D's links and counter, pins from overpos; the formula is Connectivity's slot for slot
             DevModel<TC> Mc = HM.d;
             Mc.kind = CP_MODEL_CONNECTIVITY;
             const SymWork *SW = sym_work_get(A);
             const BnPattern pat{SW->dpos.p, SW->dpos32.p, SW->pin32.p, SW->dprev.p, SW->dnext.p, SW->Nd, &SW->dia.d};
             dp_bottleneck_layer<TC>(A, Mc, alpha_of(k), prev, cur, ptr_row(k), rlo, rhi, win.w, win.lo, win.hi, win.j0, &pat);
+            break;
         }
-        else if (sym) sym_brute_layer<TC>(A, SH.d, HM.d, alpha_of(k), combine, prev, cur, ptr_row(k), rlo, rhi);
-        else if (fast && win.j0)      // a work budget: the limits [win.lo, win.hi] themselves, not the masked row (nothing outside them is read)
-            dp_total_budget_layer<TC>(A, HM.d, alpha_of(k), prev, cur, ptr_row(k), rlo, rhi, win.lo, win.hi, win.j0, win.j0_host);
-        else if (fast) dp_total_layer<TC>(A, HM.d, alpha_of(k), prev, cur, ptr_row(k), work, rlo, rhi, win.w);
-        else if (fast_bn) dp_bottleneck_layer<TC>(A, HM.d, alpha_of(k), prev, cur, ptr_row(k), rlo, rhi, win.w, win.lo, win.hi, win.j0);
-        else dp_brute_layer<TC>(A, HM.d, alpha_of(k), combine, prev, cur, ptr_row(k), rlo, rhi);
+        case DpPath::SymSweep: sym_brute_layer<TC>(A, SH.d, HM.d, alpha_of(k), combine, prev, cur, ptr_row(k), rlo, rhi); break;
+        case DpPath::EnvValley: env_valley_layer<TC>(A, ED, HM.d, alpha_of(k), prev, cur, ptr_row(k), rlo, rhi); break;
+        case DpPath::EnvDc: env_dc_layer<TC>(A, ED, HM.d, alpha_of(k), prev, cur, ptr_row(k), rlo, rhi); break;
+        case DpPath::EnvSweep: env_sweep_layer<TC>(A, ED, HM.d, alpha_of(k), combine, prev, cur, ptr_row(k), rlo, rhi); break;
+        case DpPath::Sweep: dp_brute_layer<TC>(A, HM.d, alpha_of(k), combine, prev, cur, ptr_row(k), rlo, rhi); break;
+        }
     }
 
     // rows [rlo, rhi] of layer k into the host tables (waits for the stream); fill: the other rows become zeros(Ti) / fill(typemax)
@@ -229,7 +245,7 @@ struct DpRun : cp_dp_s {
     int32_t step_layer(int64_t k, const void *prev, void *cur) override;
     int32_t block_tables(int32_t *nplanes_out, int64_t *opt_out, int64_t *nets_out, int64_t *selfnets_out) override
     {
-        CP_REQUIRE(fast && work, CP_EUNSUPPORTED, "block tables exist on the O(n log^2 n) path only");
+        CP_REQUIRE(path == DpPath::Total && work, CP_EUNSUPPORTED, "block tables exist on the O(n log^2 n) path only");
         const int nb = dp_total_block_tables<TC>(A, work, opt_out, nets_out, selfnets_out);
         if (nplanes_out) *nplanes_out = nb;
         return CP_OK;
@@ -238,15 +254,14 @@ struct DpRun : cp_dp_s {
 
 // ------------------------------------------------------------------ the K-part DP driver (unconstrained)
 template <typename TC>
-static int32_t run_dynamic_t(cp_csr_s *A, int64_t K, int32_t combine, int32_t order, const cp_model_t *mdl,
-                             int64_t *spl_out, int64_t *ptr_tab, TC *cst_tab)
+static int32_t run_dynamic_t(cp_csr_s *A, int64_t K, int32_t combine, int32_t order, const cp_model_t *mdl, int64_t *spl_out, const DpTables &tabs)
 {
     hipStream_t s = A->stream;
     const int64_t n = A->n;
     const size_t n1 = (size_t)n + 1;
     DpRun<TC> D;
     D.begin(A, K, combine, order, mdl);
-    D.ptr_tab = ptr_tab; D.cst_tab = cst_tab;
+    D.ptr_tab = tabs.ptr_tab; D.cst_tab = pick<TC>(tabs.cst_i64, tabs.cst_f64);
     DBuf<TC> cstA(n1), cstB(n1);
     D.layer1(cstA.p);
     D.dump_layer(1, cstA.p, 0, n, true);
@@ -284,13 +299,9 @@ static int32_t run_dynamic_t(cp_csr_s *A, int64_t K, int32_t combine, int32_t or
     return CP_OK;
 }
 
-int32_t run_dynamic(cp_csr_s *A, int64_t K, int32_t combine, int32_t order, const cp_model_t *mdl, int64_t *spl_out,
-                    int64_t *ptr_tab, int64_t *cst_i64, double *cst_f64)
+int32_t run_dynamic(cp_csr_s *A, int64_t K, int32_t combine, int32_t order, const cp_model_t *mdl, int64_t *spl_out, const DpTables &tabs)
 {
-    return with_cost_type(mdl->dtype, [&](auto tag) {
-        using TC = decltype(tag);
-        return run_dynamic_t<TC>(A, K, combine, order, mdl, spl_out, ptr_tab, pick<TC>(cst_i64, cst_f64));
-    });
+    return with_cost_type(mdl->dtype, [&](auto tag) { return run_dynamic_t<decltype(tag)>(A, K, combine, order, mdl, spl_out, tabs); });
 }
 
 // ------------------------------------------------------------------ the K-part DP under a width constraint
@@ -331,21 +342,23 @@ static void weight_windows(int64_t n, int64_t K, const std::vector<int32_t> &j0,
     }
 }
 
-// weight == null: parts of at most `width` columns; else the monotone work weight's budget wmax_i64 / wmax_f64 (bottleneck: the valley
-// search; total: dp_total_budget.hip -- the caller's gate, budget_total_ok, admitted the pair)
+// route Width: parts of at most route.width columns; Weight: the monotone work weight's budget wmax_i64 / wmax_f64 through its j0 array
 template <typename TC>
-static int32_t run_dynamic_windowed_t(cp_csr_s *A, int64_t K, int32_t combine, int32_t order, const cp_model_t *mdl, int64_t width,
-                                      const cp_model_t *weight, int64_t wmax_i64, double wmax_f64,
-                                      int64_t *spl_out, int64_t *ptr_tab, TC *cst_tab, int64_t *win_lo, int64_t *win_hi)
+static int32_t run_dynamic_windowed_t(cp_csr_s *A, int64_t K, int32_t combine, int32_t order, const cp_model_t *mdl, ConstrainedRoute route,
+                                      const cp_model_t *weight, int64_t wmax_i64, double wmax_f64, int64_t *spl_out, const DpTables &tabs)
 {
+    CP_REQUIRE(route.kind != ConstrainedRoute::OneWave, CP_EINTERNAL, "the one-wave route has no windowed form");
+    const bool by_weight = route.kind == ConstrainedRoute::Weight;
+    int64_t *const ptr_tab = tabs.ptr_tab;
+    TC *const cst_tab = pick<TC>(tabs.cst_i64, tabs.cst_f64);
     hipStream_t s = A->stream;
     const int64_t n = A->n;
     const size_t n1 = (size_t)n + 1;
     std::vector<int64_t> lo, hi;
     DBuf<int32_t> j0;
     std::vector<int32_t> hj;
-    if (weight) {                                                        // a general monotone weight: its j0 array
-        CP_REQUIRE(weight->kind == CP_MODEL_WORK && !weight->alpha_k, CP_EINTERNAL, "general weights: an AffineWorkModel without per-part alpha");
+    if (by_weight) {                                                     // a general monotone weight: its j0 array
+        CP_REQUIRE(weight && weight->kind == CP_MODEL_WORK && !weight->alpha_k, CP_EINTERNAL, "general weights: an AffineWorkModel without per-part alpha");
         j0.alloc(n1);
         const unsigned gw = (unsigned)cdiv((int64_t)n1, 256);
         if (weight->dtype == CP_I64)
@@ -360,9 +373,9 @@ static int32_t run_dynamic_windowed_t(cp_csr_s *A, int64_t K, int32_t combine, i
         CP_HIP(hipStreamSynchronize(s));
         weight_windows(n, K, hj, lo, hi);
     } else {
-        width_windows(n, K, width, lo, hi);
+        width_windows(n, K, route.width, lo, hi);
     }
-    if (win_lo) for (int64_t k = 1; k <= K; k++) { win_lo[k - 1] = lo[(size_t)k]; win_hi[k - 1] = hi[(size_t)k]; }
+    if (tabs.win_lo) for (int64_t k = 1; k <= K; k++) { tabs.win_lo[k - 1] = lo[(size_t)k]; tabs.win_hi[k - 1] = hi[(size_t)k]; }
     if (ptr_tab) for (size_t i = 0; i < (size_t)K * n1; i++) { ptr_tab[i] = 0; cst_tab[i] = CostTraits<TC>::typemax(); }
     if (hi[(size_t)K] < n + 1) {                                         // infeasible (:217-222): a degenerate partition, no exception
         for (int64_t k = 0; k < K; k++) spl_out[k] = 1;
@@ -370,12 +383,12 @@ static int32_t run_dynamic_windowed_t(cp_csr_s *A, int64_t K, int32_t combine, i
         return CP_INFEASIBLE;
     }
     DpRun<TC> D;
-    D.begin(A, K, combine, order, mdl);                                  // (windowed_ok admitted the model: never the O(n^2) sweep)
+    D.begin(A, K, combine, order, mdl);                                  // (constrained_route admitted the model: never the O(n^2) sweep)
     D.ptr_tab = ptr_tab; D.cst_tab = cst_tab;
-    CP_REQUIRE(!weight || combine == CP_COMBINE_MAX || D.fast, CP_EINTERNAL, "general weights: the total objective needs an inverse-Monge model");
+    CP_REQUIRE(!by_weight || combine == CP_COMBINE_MAX || D.path == DpPath::Total, CP_EINTERNAL, "general weights: the total objective needs an inverse-Monge model");
     DpWindow win;
-    win.w = weight ? 0 : std::min<int64_t>(width, std::max<int64_t>(n, 1));     // (wider than the matrix: every window is [0, r])
-    win.j0 = j0.p; win.j0_host = weight ? hj.data() : nullptr;
+    win.w = by_weight ? 0 : std::min<int64_t>(route.width, std::max<int64_t>(n, 1));     // (wider than the matrix: every window is [0, r])
+    win.j0 = j0.p; win.j0_host = by_weight ? hj.data() : nullptr;
     DBuf<TC> cst(n1), Wm(n1);
     D.layer1(cst.p);
     D.dump_layer(1, cst.p, lo[1] - 1, hi[1] - 1, false);
@@ -391,26 +404,38 @@ static int32_t run_dynamic_windowed_t(cp_csr_s *A, int64_t K, int32_t combine, i
     return CP_OK;
 }
 
-int32_t run_dynamic_windowed(cp_csr_s *A, int64_t K, int32_t combine, int32_t order, const cp_model_t *mdl, int64_t width,
-                             const cp_model_t *weight, int64_t wmax_i64, double wmax_f64, int64_t *spl_out, int64_t *ptr_tab,
-                             int64_t *cst_i64, double *cst_f64, int64_t *win_lo, int64_t *win_hi)
+int32_t run_dynamic_windowed(cp_csr_s *A, int64_t K, int32_t combine, int32_t order, const cp_model_t *mdl, ConstrainedRoute route,
+                             const cp_model_t *weight, int64_t wmax_i64, double wmax_f64, int64_t *spl_out, const DpTables &tabs)
 {
     return with_cost_type(mdl->dtype, [&](auto tag) {
-        using TC = decltype(tag);
-        return run_dynamic_windowed_t<TC>(A, K, combine, order, mdl, width, weight, wmax_i64, wmax_f64, spl_out, ptr_tab,
-                                          pick<TC>(cst_i64, cst_f64), win_lo, win_hi);
+        return run_dynamic_windowed_t<decltype(tag)>(A, K, combine, order, mdl, route, weight, wmax_i64, wmax_f64, spl_out, tabs);
     });
 }
 
-// the scalable path takes: a model of the inverse-Monge class (total cost) or one the valley search is exact for (bottleneck),
+// ------------------------------------------------------------------ the route of a ConstrainedCost
+// the scalable paths take: a model of the inverse-Monge class (total cost) or one the valley search is exact for (bottleneck),
 // under a width w_max >= 1
-bool windowed_ok(cp_csr_s *A, int64_t K, int32_t combine, const cp_model_t *model, int64_t wmax)
+static bool windowed_ok(cp_csr_s *A, int64_t K, int32_t combine, const cp_model_t *model, int64_t wmax)
 {
     if (wmax < 1 || g_opt_force_brute) return false;
-    if (model->kind != CP_MODEL_WORK && model->kind != CP_MODEL_CONNECTIVITY && model->kind != CP_MODEL_HYPEREDGE_CUT) return false;
+    if (!dp_takes_kind(model->kind, DP_KINDS_AFFINE)) return false;
     // bottleneck: the searched-crossings walk carries the candidate limits (Int64 costs; dp_bottleneck.hip)
     if (combine == CP_COMBINE_MAX) return model->dtype == CP_I64 && g_opt_bn_wave >= 2 && fast_bottleneck_ok(model, A->n, A->N, K);
     return combine == CP_COMBINE_SUM && fast_total_ok(model, A->n, A->N, K);
+}
+
+ConstrainedRoute constrained_route(cp_csr_s *A, int64_t K, int32_t combine, const cp_model_t *model, const cp_model_t *weight,
+                                   int64_t wmax_i64, double wmax_f64)
+{
+    // width weights (VertexCount, AffineWorkModel(alpha, c, 0)): the equivalent number of columns; -2: not a width
+    const int64_t wv = weight ? width_of_weight(weight, A->n, wmax_i64, wmax_f64) : wmax_i64;
+    if (windowed_ok(A, K, combine, model, wv)) return {ConstrainedRoute::Width, wv};
+    // bottleneck under any monotone work weight (pins, vertices + pins): the valley search with the weight's j0 array (Int64 costs only)
+    if (combine == CP_COMBINE_MAX && wv == -2 && monotone_work_weight(weight) && model->dtype == CP_I64 && windowed_ok(A, K, combine, model, 1))
+        return {ConstrainedRoute::Weight, 0};
+    // total cost under such a weight: the two-staircase divide and conquer of dp_total_budget.hip (either cost type, both loop orders)
+    if (combine == CP_COMBINE_SUM && budget_total_ok(A, K, model, weight, wmax_i64, wmax_f64)) return {ConstrainedRoute::Weight, 0};
+    return {ConstrainedRoute::OneWave, 0};
 }
 
 // ------------------------------------------------------------------ row-tiled DP (one rank = one tile of rows per layer)
@@ -447,7 +472,7 @@ int32_t DpRun<TC>::step_layer(int64_t k, const void *prev, void *cur)
     const int64_t lo = rlo < 0 ? 0 : rlo, hi = rhi > A->n ? A->n : rhi;
     lay_lo[(size_t)k] = lo; lay_hi[(size_t)k] = hi;
     if (hi >= lo) {
-        CP_REQUIRE(wwin == 0 || fast, CP_EUNSUPPORTED, "the width window needs the O(n log^2 n) path");
+        CP_REQUIRE(wwin == 0 || path == DpPath::Total, CP_EUNSUPPORTED, "the width window needs the O(n log^2 n) path");
         DpWindow win;
         win.w = wwin;
         layer(k, (const TC *)prev, (TC *)cur, lo, hi, win);

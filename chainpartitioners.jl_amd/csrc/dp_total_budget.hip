@@ -180,7 +180,7 @@ template void dp_total_budget_layer<double>(cp_csr_s *, const DevModel<double> &
 bool budget_total_ok(const cp_csr_s *A, int64_t K, const cp_model_t *model, const cp_model_t *weight, int64_t wi, double wf)
 {
     if (!g_opt_budget_total || g_opt_force_brute || !weight) return false;
-    if (model->kind != CP_MODEL_WORK && model->kind != CP_MODEL_CONNECTIVITY && model->kind != CP_MODEL_HYPEREDGE_CUT) return false;
+    if (!dp_takes_kind(model->kind, DP_KINDS_AFFINE)) return false;
     if (A->n >= ((int64_t)1 << 30) || A->N >= ((int64_t)1 << 31) - 1) return false;
     if (!fast_total_ok(model, A->n, A->N, K)) return false;
     // a monotone AffineWorkModel without per-part alpha that is no width (those take the windowed geometry of dp_total.hip)

@@ -227,11 +227,9 @@ int32_t env_bound_stripe(cp_csr_s *A, int64_t K, const cp_model_t *mdl, TC *lo, 
 bool env_valley_ok(const cp_model_t *m, int64_t m_rows, int64_t n, int64_t N, int64_t K)
 {
     if (m->dtype == CP_I64) {
-        typedef unsigned __int128 u128;
-        auto mag = [](int64_t v) { return v < 0 ? (u128)0 - (u128)(__int128)v : (u128)v; };
         if (m->p_i64[CP_P_VERTEX] < 0 || m->p_i64[CP_P_PIN] < 0 || m->p_i64[CP_P_NET] < 0) return false;
-        u128 amax = mag(m->p_i64[CP_P_ALPHA]);
-        if (m->alpha_k) for (int64_t i = 0; i < m->n_alpha_k; i++) amax = std::max(amax, mag(((const int64_t *)m->alpha_k)[i]));
+        u128 amax = mag128(m->p_i64[CP_P_ALPHA]);
+        if (m->alpha_k) for (int64_t i = 0; i < m->n_alpha_k; i++) amax = std::max(amax, mag128(((const int64_t *)m->alpha_k)[i]));
         const u128 bound = amax * (u128)(K > 0 ? K : 1) + (u128)m->p_i64[CP_P_VERTEX] * (u128)(n > 0 ? n : 0) +
                            (u128)m->p_i64[CP_P_PIN] * (u128)(N > 0 ? N : 0) + (u128)m->p_i64[CP_P_NET] * (u128)(m_rows > 0 ? m_rows : 0);
         return bound < ((u128)1 << 60);

@@ -16,7 +16,6 @@
 
 namespace cpk {
 
-inline bool model_is_env(int32_t kind) { return kind == CP_MODEL_ENVELOPE; }
 // how the entries without an envelope path refuse the kind
 #define CP_REFUSE_ENV(m, what) \
     CP_REQUIRE(!((m) && cpk::model_is_env((m)->kind)), CP_EUNSUPPORTED, "AffineEnvelopeModel has no device path in " what)

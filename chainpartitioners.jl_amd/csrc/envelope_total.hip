@@ -49,13 +49,11 @@ struct DcDev {
 // left-to-right rounding is not what the regrouped sums give.
 bool env_dc_ok(const cp_model_t *m, int64_t m_rows, int64_t n, int64_t N, int64_t K)
 {
-    typedef unsigned __int128 u128;
     const u128 k = (u128)(K > 0 ? K : 1), un = (u128)(n > 0 ? n : 0), uN = (u128)(N > 0 ? N : 0), um = (u128)(m_rows > 0 ? m_rows : 0);
     if (m->dtype == CP_I64) {
-        auto mag = [](int64_t v) { return v < 0 ? (u128)0 - (u128)(__int128)v : (u128)v; };
-        u128 amax = mag(m->p_i64[CP_P_ALPHA]);
-        if (m->alpha_k) for (int64_t i = 0; i < m->n_alpha_k; i++) amax = std::max(amax, mag(((const int64_t *)m->alpha_k)[i]));
-        const u128 bound = amax * k + mag(m->p_i64[CP_P_VERTEX]) * un + mag(m->p_i64[CP_P_PIN]) * uN + mag(m->p_i64[CP_P_NET]) * um * k;
+        u128 amax = mag128(m->p_i64[CP_P_ALPHA]);
+        if (m->alpha_k) for (int64_t i = 0; i < m->n_alpha_k; i++) amax = std::max(amax, mag128(((const int64_t *)m->alpha_k)[i]));
+        const u128 bound = amax * k + mag128(m->p_i64[CP_P_VERTEX]) * un + mag128(m->p_i64[CP_P_PIN]) * uN + mag128(m->p_i64[CP_P_NET]) * um * k;
         return bound < ((u128)1 << 60);
     }
     const double lim = 2251799813685248.0;                     // 2^51

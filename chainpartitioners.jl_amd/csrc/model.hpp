@@ -109,6 +109,29 @@ __device__ __forceinline__ TC comb(int32_t g, TC a, TC b)
     return a > b ? a : b;
 }
 
+// The model families with counters of their own (sym.hpp, envelope.hpp)
+inline bool model_is_sym(int32_t kind) { return kind >= CP_MODEL_SYM_CONNECTIVITY && kind <= CP_MODEL_SYM_EDGE_CUT; }
+inline bool model_is_env(int32_t kind) { return kind == CP_MODEL_ENVELOPE; }
+
+// The kinds the K-layer stripe DP driver (dp_driver.hip) takes, as nested sets: each caller names the largest it serves.
+enum DpKinds {
+    DP_KINDS_AFFINE,       // Work / Connectivity / HyperedgeCut: the only kinds of the scalable constrained paths
+    DP_KINDS_TILED,        // + ColumnBlockComponent: the row-tiled entry
+    DP_KINDS_STRIPE,       // + PowerWork and the symmetric family: the one-shot partition entry
+    DP_KINDS_TABLES,       // + the envelope model: the tables entry
+};
+inline bool dp_takes_kind(int32_t kind, DpKinds set)
+{
+    if (kind == CP_MODEL_WORK || kind == CP_MODEL_CONNECTIVITY || kind == CP_MODEL_HYPEREDGE_CUT) return true;
+    if (kind == CP_MODEL_COLBLOCK) return set >= DP_KINDS_TILED;
+    if (kind == CP_MODEL_POWER_WORK || model_is_sym(kind)) return set >= DP_KINDS_STRIPE;
+    return model_is_env(kind) && set >= DP_KINDS_TABLES;
+}
+
+// |v| in 128 bits (|INT64_MIN| included): the Int64 exactness gates sum parameter magnitudes times counts without wrapping
+typedef unsigned __int128 u128;
+inline u128 mag128(int64_t v) { return v < 0 ? (u128)0 - (u128)(__int128)v : (u128)v; }
+
 // Int64 model, or a Float64 model whose scalar parameters are all integer-valued (then every cost is an exactly
 // represented integer).  Neither makes sums exact by itself: Float64 rounds above 2^53 and Int64 wraps (cadd / cmulc, as
 // Julia does) -- model_exact_on adds the bound.
@@ -132,35 +155,33 @@ inline bool model_exact_on(const cp_model_t *m, int64_t n, int64_t N, int64_t K)
 {
     if (!model_all_integral(m)) return false;
     if (m->dtype == CP_I64) {
-        typedef unsigned __int128 u128;
-        auto mag = [](int64_t v) { return v < 0 ? (u128)0 - (u128)(__int128)v : (u128)v; };
         auto comp_max = [&](const cp_component_t &c) {
-            u128 r = mag(c.c_i64);
-            if (!c.is_const) { r = 0; if (c.table) for (int64_t i = 0; i < c.len; i++) r = std::max(r, mag(((const int64_t *)c.table)[i])); }
+            u128 r = mag128(c.c_i64);
+            if (!c.is_const) { r = 0; if (c.table) for (int64_t i = 0; i < c.len; i++) r = std::max(r, mag128(((const int64_t *)c.table)[i])); }
             return r;
         };
         u128 amax, bv = 0, bp = 0, bnet;
         int64_t Nnet = N;                      // how many entries the net-like count can reach
         if (m->kind == CP_MODEL_MONO_SYM_CONNECTIVITY) {
             // the Connectivity bound on the pattern with its diagonal added: the dianet count reaches N + n; p[4] is Delta_pins, no cost
-            amax = mag(m->p_i64[CP_P_ALPHA]);
-            if (m->alpha_k) for (int64_t i = 0; i < m->n_alpha_k; i++) amax = std::max(amax, mag(((const int64_t *)m->alpha_k)[i]));
-            bv = mag(m->p_i64[CP_P_VERTEX]); bp = mag(m->p_i64[CP_P_OVER_PIN]); bnet = mag(m->p_i64[CP_P_DIA_NET]);
+            amax = mag128(m->p_i64[CP_P_ALPHA]);
+            if (m->alpha_k) for (int64_t i = 0; i < m->n_alpha_k; i++) amax = std::max(amax, mag128(((const int64_t *)m->alpha_k)[i]));
+            bv = mag128(m->p_i64[CP_P_VERTEX]); bp = mag128(m->p_i64[CP_P_OVER_PIN]); bnet = mag128(m->p_i64[CP_P_DIA_NET]);
             Nnet = N + n;
         } else if (m->kind == CP_MODEL_COLBLOCK) {
             amax = comp_max(m->alpha_col);
             bnet = comp_max(m->beta_col[0]);
-        } else if (m->kind == CP_MODEL_WORK || m->kind == CP_MODEL_CONNECTIVITY || m->kind == CP_MODEL_HYPEREDGE_CUT) {
-            amax = mag(m->p_i64[CP_P_ALPHA]);
-            if (m->alpha_k) for (int64_t i = 0; i < m->n_alpha_k; i++) amax = std::max(amax, mag(((const int64_t *)m->alpha_k)[i]));
-            bv = mag(m->p_i64[CP_P_VERTEX]); bp = mag(m->p_i64[CP_P_PIN]);
-            bnet = std::max(mag(m->p_i64[3]), mag(m->p_i64[4]));
+        } else if (dp_takes_kind(m->kind, DP_KINDS_AFFINE)) {
+            amax = mag128(m->p_i64[CP_P_ALPHA]);
+            if (m->alpha_k) for (int64_t i = 0; i < m->n_alpha_k; i++) amax = std::max(amax, mag128(((const int64_t *)m->alpha_k)[i]));
+            bv = mag128(m->p_i64[CP_P_VERTEX]); bp = mag128(m->p_i64[CP_P_PIN]);
+            bnet = std::max(mag128(m->p_i64[3]), mag128(m->p_i64[4]));
         } else if (m->kind == CP_MODEL_PRIMARY_EDGE_CUT || m->kind == CP_MODEL_SECONDARY_EDGE_CUT) {
             // every pin is a self pin or a cut pin: K*max|alpha| + n*|b_vertex| + N*max(|b_self_pin|, |b_cut_pin|)
-            amax = mag(m->p_i64[CP_P_ALPHA]);
-            if (m->alpha_k) for (int64_t i = 0; i < m->n_alpha_k; i++) amax = std::max(amax, mag(((const int64_t *)m->alpha_k)[i]));
-            bv = mag(m->p_i64[CP_P_VERTEX]);
-            bnet = std::max(mag(m->p_i64[CP_P_SELF_PIN]), mag(m->p_i64[CP_P_CUT_PIN]));
+            amax = mag128(m->p_i64[CP_P_ALPHA]);
+            if (m->alpha_k) for (int64_t i = 0; i < m->n_alpha_k; i++) amax = std::max(amax, mag128(((const int64_t *)m->alpha_k)[i]));
+            bv = mag128(m->p_i64[CP_P_VERTEX]);
+            bnet = std::max(mag128(m->p_i64[CP_P_SELF_PIN]), mag128(m->p_i64[CP_P_CUT_PIN]));
         } else {
             return false;
         }

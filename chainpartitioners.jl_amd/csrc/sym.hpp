@@ -13,8 +13,6 @@
 
 namespace cpk {
 
-inline bool model_is_sym(int32_t kind) { return kind >= CP_MODEL_SYM_CONNECTIVITY && kind <= CP_MODEL_SYM_EDGE_CUT; }
-
 // what the device needs to evaluate a symmetric cost on [p, r) (0-based columns)
 struct SymDev {
     int32_t kind;

@@ -55,9 +55,7 @@ inline bool monotone_work_weight(const cp_model_t *w)
 inline bool work_weight_no_wrap(const cp_model_t *w, int64_t n, int64_t N, int64_t wmax_i64)
 {
     if (w->dtype != CP_I64) return true;
-    typedef unsigned __int128 u128;
-    auto mag = [](int64_t v) { return v < 0 ? (u128)0 - (u128)(__int128)v : (u128)v; };
-    const u128 b = mag(w->p_i64[CP_P_ALPHA]) + mag(w->p_i64[CP_P_VERTEX]) * (u128)(n + 1) + mag(w->p_i64[CP_P_PIN]) * (u128)(N + 1) + mag(wmax_i64);
+    const u128 b = mag128(w->p_i64[CP_P_ALPHA]) + mag128(w->p_i64[CP_P_VERTEX]) * (u128)(n + 1) + mag128(w->p_i64[CP_P_PIN]) * (u128)(N + 1) + mag128(wmax_i64);
     return b < ((u128)1 << 62);
 }
 
