@@ -686,6 +686,11 @@ __global__ void __launch_bounds__(256) k_bn_walk_vec(BnCtx<int64_t> C, int64_t r
                     else { fm = fprev; have_fm = have_prev && xw - 1 >= plo_r; }
                     // column and counts the next sub-run starts from: the crossing, or -- none -- the row's last candidate phi
                     if (found) { c_carry = c; nn = nn - (Pns - Pnb) - (sns - snb); nl = nl - (Pls - Plb) - (sls - slb); }
+                    // (phi was the previous window's last lane: jmax < 0, no lane of this window is a candidate, and the counts already
+                    //  refer to this window's first column xw = phi + 1 -- that column is carried, not phi, which they do not describe.
+                    //  Never a sub-run's first window, where the counts refer to lane jb = 1: there xw = cs - jb <= phi of the anchor
+                    //  <= phi_r, so jmax >= 0; here jb = 0 and nn / nl are as the previous window left them.)
+                    else if (jmax < 0) c_carry = xw;
                     else { c_carry = phi_r; nn = nn - (Pnm - Pnb) - (snm - snb); nl = nl - (Plm - Plb) - (slm - slb); }
                     open = false;
                 } else {

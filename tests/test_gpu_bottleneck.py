@@ -222,3 +222,31 @@ def test_pin_weighted_bottleneck_larger(hip, orc):
         got = cp.partition_stripe(A, K, cp.DynamicBottleneckSplitter(f), backend=hip)
         assert got == cp.partition_stripe(A, K, cp.DynamicBottleneckSplitter(f), backend=orc) and len(set(got.spl.tolist())) == K + 1
         assert (got == free) == (budget == int(1.3 * A.nnz / K))        # the tight budgets decide the answer
+
+
+def test_last_candidate_on_a_windows_last_lane(hip, orc):
+    """k_bn_walk_vec searches a row's crossing through windows of 64 columns.  A row whose last candidate (the previous layer's last
+    feasible column) is a window's last lane and that finds no crossing there closes in the next window, where no lane is a candidate:
+    the counts it hands to the next 64 rows then describe that window's first column, and it is that column that must be carried.
+    Where the windows fall depends on the rows per wave and on the slack of the hinted starts, so both are swept: with a row in every
+    column and one column of n / 4 entries (tests/test_gpu_metamorphic.edge_shape; found at n = 70 001, where the default settings hit
+    it on the second call), a pin budget of 1.3 x the mean and Connectivity costs, rows per wave 67 .. 71 and a few slacks left 3 to
+    1114 cells of the tables wrong at n = 1001 and 2001."""
+    from test_gpu_metamorphic import edge_shape
+    mdl, wgt = cp.AffineConnectivityModel(0, 10, 1, 100), cp.AffineWorkModel(0, 0, 1)
+    try:
+        for n, K, settings in ((1001, 16, ((67, 21), (69, 0), (69, 6))), (2001, 16, ((69, 9), (71, 24))), (1001, 7, ((70, 63), (93, 63)))):
+            A = edge_shape(n)
+            budget = -(-13 * A.nnz // (10 * K))
+            rc2, lo2, hi2, p2, c2 = orc.dynamic_tables_constrained(A, K, 1, mdl.marshal(), None, wgt.marshal(), budget, float(budget))
+            assert rc2 == 0
+            for run, slack in settings:
+                hip.set_option("bn_run", run); hip.set_option("bn_slack", slack)
+                for call in (1, 2):                                     # (the second starts from the first one's hints)
+                    rc1, lo1, hi1, p1, c1 = hip.dynamic_tables_constrained(A, K, mdl.marshal(), budget, combine=1, wm=wgt.marshal())
+                    assert rc1 == 0 and np.array_equal(lo1, lo2) and np.array_equal(hi1, hi2)
+                    for k in range(1, K + 1):
+                        a, b = lo2[k - 1] - 1, hi2[k - 1]
+                        assert np.array_equal(p1[a:b, k - 1], p2[a:b, k - 1]) and np.array_equal(c1[a:b, k - 1], c2[a:b, k - 1]), (n, K, run, slack, call, k)
+    finally:
+        hip.set_option("bn_run", 253); hip.set_option("bn_slack", 64)
