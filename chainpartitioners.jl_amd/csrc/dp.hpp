@@ -176,7 +176,7 @@ void dp_round_scans_test(const int32_t *a, int64_t na, int64_t na_max, const int
                          int err_in, int reps, int64_t *offs_out, int64_t *toffs_out, int64_t *res);      // dp_total.hip: cp_test_round_scans
 void dp_fix_merge_test(const cp_model_t *model, int64_t ntask, const int64_t *toffs, const int64_t *part_v, const int32_t *part_p, const int32_t *part_nn,
                        const int32_t *part_nl, const int32_t *tile_s, const int32_t *tile_s2, const int32_t *anchor, const int32_t *anchor2, const int32_t *row,
-                       const int32_t *plane, int64_t n, int reps, int32_t *p_out, int32_t *nn_out, int32_t *nl_out, int64_t *res);      // dp_total.hip: cp_test_fix_merge
+                       const int32_t *plane, int64_t n, int reps, int32_t *p_out, int32_t *nn_out, int32_t *nl_out, int64_t *res);      // dp_total_own.hip: cp_test_fix_merge
 extern int64_t g_fix_trips, g_fix_edges;       // what the own-tile merges met since the last reset (tests): see RoundCounts::n_trips / n_edge
 extern int64_t g_fix_items;                    // ... and the (task, trip) items they merged, attempts that were redone included (RoundCounts::n_items)
 extern int64_t g_opt_leaf;                     // 1: the rounds tau < 6 of an unconstrained layer are one leaf pass (dp_total_leaf.hip)
@@ -198,10 +198,10 @@ extern int64_t g_opt_gap_split;                // 1 (and own_split 1): the gap r
 extern int64_t g_gap_split_tiles;              // gap tiles that took that path since the last reset (not counted in own_split_tiles)
 extern int64_t g_opt_own_pair;                 // 1: outside the gap rounds and the hyperedge costs a wave of k_lpass_own takes two slots of the run order
 extern int64_t g_own_pair_waves, g_own_pair_lone;      // waves that ran two tiles / one because the order ended, since the last reset
-void dp_own_pair_test(int64_t nt, int64_t wave, int64_t *res);      // dp_total.hip: cp_test_own_pair
+void dp_own_pair_test(int64_t nt, int64_t wave, int64_t *res);      // dp_total_own.hip: cp_test_own_pair
 extern int64_t g_opt_own_pack;                 // 1 (and own_split 1, own_blk 1): split tiles read one packed word per step where the pattern's in-block offsets fit 16 bits
 extern int64_t g_own_pack_tiles, g_own_pack_wide;      // tiles that ran packed since the last reset; 1: the pattern of the last split launch fell back to the wide arrays
-void dp_own_pack_test(cp_csr_s *A, int32_t *vpk_out, int32_t *vbase_out, int64_t *res);      // dp_total.hip: cp_test_own_pack
+void dp_own_pack_test(cp_csr_s *A, int32_t *vpk_out, int32_t *vbase_out, int64_t *res);      // dp_total_own.hip: cp_test_own_pack
 extern int64_t g_opt_round_alloc;              // 1: k_setup_short reserves list slots and offsets in one atomic per list and block, its last block gives the round's verdict; 0: k_round_scans
 void dp_list_alloc_test(const int32_t *a, int64_t na, const int32_t *b, int64_t nb, int bs, int64_t capT, int64_t capNT, int64_t o_cap, int err_in, int reps,
                         int64_t fit_ntask, int64_t fit_n, int64_t fit_own_min, int64_t *offs_out, int32_t *slot_a, int64_t *toffs_out, int32_t *slot_b,
@@ -210,7 +210,7 @@ extern int64_t g_round_alloc_rounds;          // rounds that took that path sinc
 extern int64_t g_opt_cr_consume;               // 1: in full layers k_setup_short zeroes the cr / crl cells it reads; the clearing launch runs only while the planes may be dirty
 extern int64_t g_cr_consume_rounds, g_cr_clear_launches;      // chunked right passes that ran without / with the clearing launch since the last reset
 extern int64_t g_overlap_isect;                // column intersections cp_pack_overlap computed since the last reset (chunk_greedy.hip)
-void dp_own_split_test(cp_csr_s *A, int32_t *vpos_out, int32_t *vsa_out, int32_t *vnext_out, int64_t *res);      // dp_total.hip: cp_test_own_split
+void dp_own_split_test(cp_csr_s *A, int32_t *vpos_out, int32_t *vsa_out, int32_t *vnext_out, int64_t *res);      // dp_total_own.hip: cp_test_own_split
 extern int64_t g_opt_short_t, g_opt_short_e;   // k_setup_short: tasks with <= short_t candidates and <= short_e link entries finish in setup
 extern int64_t g_opt_force_brute;      // cp_set_option("force_brute", 1)
 extern int64_t g_opt_brute_max_n;      // largest n the O(n^2) path accepts

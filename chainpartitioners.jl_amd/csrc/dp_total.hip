@@ -31,10 +31,12 @@
 //    kernels on another tiling of the candidates: every row has a task in every plane b <= floor(log2 w) -- standard, common
 //    and mirrored blocks, see struct Geo below and DESIGN.md section 4b.
 //
-// Units: the right pass is dp_total_rpass.hip, the gap passes are dp_total_gap.hip, the leaf pass and the combine dp_total_leaf.hip;
-// the other stages and the layer driver are here.  What the units share: dp_total.hpp.
-#include "dp_total.hpp"
-#include <optional>
+// Units: the right pass is dp_total_rpass.hip, the gap passes are dp_total_gap.hip, the leaf pass and the combine dp_total_leaf.hip,
+// the own-tile chain of a round dp_total_own.hip, round A from the cached counts and the windowed anchors dp_total_rounda.hip;
+// task set-up with the round allocator and the scans, the flattened stage and the layer driver are here.  What the units share:
+// dp_total.hpp; with the own-tile unit also dp_total_own.hpp and the tile stream, dp_total_stream.hpp.
+#include "dp_total_own.hpp"
+#include "dp_total_stream.hpp"
 
 namespace cpk {
 
@@ -65,34 +67,6 @@ int64_t g_opt_round_alloc = 1;         // k_setup_short reserves the offsets of 
 int64_t g_round_alloc_rounds = 0;
 int64_t g_opt_cr_consume = 1;          // full layers: set-up zeroes the cr / crl cells it reads and the clearing launch in front of the chunked right passes goes (begin_layer)
 int64_t g_cr_consume_rounds = 0, g_cr_clear_launches = 0;
-
-// ------------------------------------------------------------------ wave-level segmented scans (64 lanes; the Best helpers: dp_total.hpp)
-// inclusive segmented sum: v = sum from the last head at or before this lane (or lane 0), f = "a head lies in [0, lane]"
-__device__ __forceinline__ void wave_segsum(int32_t &v, int &f, int lane)
-{
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        int32_t pv = __shfl_up(v, o);
-        int pf = __shfl_up(f, o);
-        if (lane >= o) { if (!f) v += pv; f |= pf; }
-    }
-}
-
-template <typename TC, bool HYP>
-__device__ __forceinline__ void wave_segmin(Best<TC, HYP> &x, int &f, int lane)
-{
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        Best<TC, HYP> p;
-        best_clear(p);
-        p.v = shfl_up64(x.v, o);
-        p.p = __shfl_up(x.p, o);
-        p.nn = __shfl_up(x.nn, o);
-        if (HYP) best_set_nl(p, __shfl_up(best_nl(x), o));
-        int pf = __shfl_up(f, o);
-        if (lane >= o) { if (!f) x = better(p, x); f |= pf; }
-    }
-}
 
 // ------------------------------------------------------------------ round_alloc: list slots and offsets reserved together
 // cp_set_option("round_alloc", 0 | 1).  A block that appends to a task list holds its tasks' lengths, so it reserves its slots AND
@@ -446,1020 +420,6 @@ __device__ __forceinline__ void load_tile_tasks(const int64_t *__restrict__ offs
     }
 }
 
-// ------------------------------------------------------------------ cooperative column counts
-// Every lane owns one column-like range [s, en) of `arr` and a threshold; lanes whose ranges are adjacent and
-// descending form a run whose entries [q_lo, q_hi) are read as aligned 16-byte-per-lane loads (1 KiB per wave
-// instruction, two in flight); position x + 4*lane' + j sits in component j of lane'.  Returns, per lane,
-// #{entries of its range with  v >= thr (GE)  or  v < thr (!GE)}.  One ballot pass per distinct threshold
-// (= task) touching a 256-entry block.
-template <bool GE>
-__device__ __forceinline__ int32_t coop_count(const int32_t *__restrict__ arr, int32_t s, int32_t en, int32_t thr, bool valid, int lane)
-{
-    int32_t prev_s = __shfl_up(s, 1);
-    int prev_valid = __shfl_up((int)valid, 1);
-    bool cont = valid && lane > 0 && prev_valid && (en == prev_s);
-    unsigned long long heads = __ballot(valid && !cont);
-    unsigned long long vm = __ballot(valid);
-    int32_t d = 0;
-    const int32_t FILL = GE ? INT32_MIN : INT32_MAX;          // never counted
-    while (heads) {
-        int h0 = __ffsll((long long)heads) - 1;
-        heads &= heads - 1;
-        int h1 = heads ? (__ffsll((long long)heads) - 1) : 64;
-        unsigned long long inrun = vm & (h1 == 64 ? ~0ull : ((1ull << h1) - 1)) & ~((1ull << h0) - 1);
-        int hl = 63 - __clzll((long long)inrun);          // last valid lane of the run
-        int32_t q_hi = __shfl(en, h0), q_lo = __shfl(s, hl);
-        bool mine = lane >= h0 && lane <= hl && en > s;
-        for (int32_t x = q_lo & ~3; x < q_hi; x += 512) {
-            int4 v0 = make_int4(FILL, FILL, FILL, FILL), v1 = v0;
-            int32_t b0 = x + 4 * lane, b1 = b0 + 256;
-            if (b0 < q_hi) v0 = *reinterpret_cast<const int4 *>(arr + b0);        // arrays are padded by 8 entries
-            if (b1 < q_hi) v1 = *reinterpret_cast<const int4 *>(arr + b1);
-#pragma unroll
-            for (int c = 0; c < 2; c++) {
-                int32_t xc = x + c * 256;
-                if (xc >= q_hi) break;                    // wave-uniform
-                int4 v = c ? v1 : v0;
-                // (entries outside the run need no masking: a lane only counts inside its own range, which lies in the run)
-                bool ov = mine && s < xc + 256 && en > xc;
-                // this lane's range covers positions [a0, a1) of the block: lanes [lo_j, hi_j) of component j
-                int a0 = ov ? ((s > xc ? s : xc) - xc) : 0, a1 = ov ? ((en < xc + 256 ? en : xc + 256) - xc) : 0;
-                unsigned long long rem = __ballot(ov);
-                while (rem) {                             // one pass per distinct threshold touching the block
-                    int l = __ffsll((long long)rem) - 1;
-                    int32_t tu = __shfl(thr, l);
-                    const bool f0 = GE ? v.x >= tu : v.x < tu, f1 = GE ? v.y >= tu : v.y < tu, f2 = GE ? v.z >= tu : v.z < tu, f3 = GE ? v.w >= tu : v.w < tu;
-                    const unsigned long long m0 = __ballot(f0), m1 = __ballot(f1), m2 = __ballot(f2), m3 = __ballot(f3);
-                    // F(x) = flagged entries at block positions < x = (flags in the lanes below lane x/4) + (flags of that lane below
-                    // component x%4): the lane-below counts come from v_mbcnt chains, packed with the lane's own flags, and a lane
-                    // takes  F(a1) - F(a0)  for its range [a0, a1) with two cross-lane reads
-                    uint32_t P0 = 0;
-                    P0 = __builtin_amdgcn_mbcnt_hi((uint32_t)(m0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m0, P0));
-                    P0 = __builtin_amdgcn_mbcnt_hi((uint32_t)(m1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m1, P0));
-                    P0 = __builtin_amdgcn_mbcnt_hi((uint32_t)(m2 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m2, P0));
-                    P0 = __builtin_amdgcn_mbcnt_hi((uint32_t)(m3 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m3, P0));
-                    const int32_t pack = (int32_t)((P0 << 3) | (uint32_t)f0 | ((uint32_t)f1 << 1) | ((uint32_t)f2 << 2));
-                    const int32_t tot = __popcll(m0) + __popcll(m1) + __popcll(m2) + __popcll(m3);         // (uniform)
-                    const int32_t g0 = __shfl(pack, (a0 >> 2) & 63), g1 = __shfl(pack, (a1 >> 2) & 63);      // (every lane takes part)
-                    bool same = ov && thr == tu;
-                    if (same) {
-                        int32_t F0 = (g0 >> 3) + __popc((uint32_t)g0 & ((1u << (a0 & 3)) - 1u));
-                        int32_t F1 = a1 >= 256 ? tot : (g1 >> 3) + __popc((uint32_t)g1 & ((1u << (a1 & 3)) - 1u));
-                        d += F1 - F0;
-                    }
-                    rem &= ~__ballot(same);
-                }
-            }
-        }
-    }
-    return d;
-}
-
-// Interior tiles of a long task: the tile's steps e = 0 .. tl are adjacent descending columns p_first - e of ONE task, so
-// the step order is the (reversed) entry order of one contiguous run [Q_lo, Q_hi) and the inclusive step prefix is a
-// suffix count:  x(e) = #{q in [s(e), Q_hi) : flagged(q)},  s(e) = first entry of the step's column.  No per-column
-// counts, no wave scan, no carry.  The run is streamed once in 256-entry blocks (two blocks per trip; the next trip's two loads
-// are issued at the top of a trip and waited for at the top of the next one); per block: four ballots, a per-lane popcount prefix, and one gather per step whose column starts
-// inside the block.  Lane l owns the steps l, l+64, l+128, l+192.
-// DET (gap passes, see k_gap_finish): the entries of the run with a value strictly between sp_lo and sp_hi ("specials") are
-// appended to the wave's list by the lanes that hold them (LDS counter s_cnt): s_es[i] = the entry's position (the caller turns it
-// into the first step whose candidate has the entry's column on its right), s_v[i] = the value, tagged with `kind` in bit 31.
-// Only the first SMAX specials are stored; s_cnt keeps counting.
-// (Tried: a step's count taken once, in the block its column starts in, as TOTAL - (flagged entries below the start), the groups
-//  that can start in a block picked on the scalar side -- 30 instead of 70 vector instructions per block, but 65 VGPRs: 254 ms
-//  against 232; forced back to 64 VGPRs: 241 ms.)
-// (Tried: the link values in 3 bytes (n < 2^24), a 12-byte load and six vector instructions to unpack four entries -- 19 % fewer
-//  bytes per step, and k_lpass_own 9 % SLOWER (254 vs 232 ms per partition): at 0.8 of the HBM roofline the kernel has no vector
-//  issue slots to spare.)
-// PK (own_pack; own_split tiles of the geometry own_blk 1, which lie inside one 256-column block): cpos is the plane's packed words
-// (SplitLinks::vpk), one load per step -- the column's start and its prefix sum as 16-bit offsets from the block's bases vb[0]; vb[1]
-// holds the next block's.  A tile that is not a head tile ends at the block's last column: its run ends, and its prefix sums are
-// taken from, the next block's bases; a head tile's are the offsets of its column p_first.  psum is not read.
-template <bool GE, bool DET = false, bool PK = false>
-__device__ __forceinline__ void interior_stream(const int32_t *__restrict__ arr, const int32_t *__restrict__ cpos, int32_t p_first, int32_t tl,
-                                                int32_t thr, int lane, int32_t acc[4], int32_t sk[4], int head = 0, int32_t sp_lo = 0, int32_t sp_hi = 0,
-                                                int32_t *s_es = nullptr, int32_t *s_v = nullptr, int32_t *s_cnt = nullptr, int kind = 0,
-                                                const int32_t *__restrict__ psum = nullptr, const int2 *__restrict__ vb = nullptr)
-{
-    // No load of this function sits under a lane mask or a data-dependent branch: behind the join of a conditional load the
-    // compiler cannot tell how many loads are outstanding and waits for all of them, which made every guarded load a round trip
-    // of its own.  Indices are clamped into the tile instead and the guards are selects on the loaded values.
-    // The tile is the wave's: its column, its length and the run's two ends are scalars, so every address below is a scalar base
-    // plus a small unsigned lane offset (one VGPR, no 64-bit vector arithmetic; the masks tell the compiler how small).
-    p_first = __builtin_amdgcn_readfirstlane(p_first);
-    tl = __builtin_amdgcn_readfirstlane(tl) & 255;
-    // Prologue, one group of loads: the column pointers of the lane's four steps (a step beyond tl reads the tile's last column),
-    // the run's two ends, and with psum (wave-uniform; own_split) what a step starts from: psum[end of the run's columns] -
-    // psum[its column], what the columns hold apart from the streamed entries.  (The counters are live through the loop anyway.)
-    const int32_t *__restrict__ cl = cpos + (p_first - tl), *__restrict__ pl = (psum ? psum : cpos) + (p_first - tl);      // the tile's last column
-    int32_t cp[4], pv[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int32_t e = lane + 64 * k;
-        const uint32_t d = (uint32_t)(tl - (e < tl ? e : tl)) & 255u;
-        cp[k] = cl[d];
-        if (!PK) pv[k] = pl[d];
-    }
-    int32_t Q_hi, Q_lo;
-    if constexpr (PK) {
-        // the same group: the words of column p_first and of the tile's last column, and the two base pairs (adjacent scalars)
-        const uint32_t wt = (uint32_t)__builtin_amdgcn_readfirstlane(cl[tl]), wl = (uint32_t)__builtin_amdgcn_readfirstlane(cl[0]);
-        const int2 b0 = vb[0], b1 = vb[1];
-        Q_hi = head ? b0.x + (int32_t)(wt & 0xffffu) : b1.x;
-        Q_lo = b0.x + (int32_t)(wl & 0xffffu);
-        const int32_t ptop = head ? (int32_t)(wt >> 16) : b1.y - b0.y;              // (relative to the block's base, like the steps')
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const bool on = lane + 64 * k <= tl;
-            sk[k] = on ? b0.x + (int32_t)((uint32_t)cp[k] & 0xffffu) : INT32_MAX;
-            acc[k] = on ? ptop - (int32_t)((uint32_t)cp[k] >> 16) : 0;
-        }
-    } else {
-    // head != 0: step 0 is the candidate p_first itself (no column stepped over): the run ends in front of that column
-    const int32_t ptop = pl[tl + 1 - head];
-    Q_hi = __builtin_amdgcn_readfirstlane(cl[tl + 1 - head]); Q_lo = __builtin_amdgcn_readfirstlane(cl[0]);
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const bool on = lane + 64 * k <= tl;
-        sk[k] = on ? cp[k] : INT32_MAX;
-        acc[k] = (psum && on) ? ptop - pv[k] : 0;
-    }
-    }
-    // Entries: a lane whose four positions start at or above Q_hi reads the run's last aligned quad instead -- inside the eight
-    // entries of slack behind every streamed array (next: ensure_links, flast: ensure_self, + 16; vnext: split_build, + 8) -- and
-    // what it reads is never flagged: every block that is not `inner` guards its flags by position, an inner one holds run entries only.
-    const int32_t x_end = Q_hi & ~3;
-    int32_t x = Q_lo & ~3;
-    // (x <= x_end wherever this is called: the offset from the trip's first entry is unsigned and below 1024 or x_end - x)
-    auto quad = [&](uint32_t o) { const uint32_t r = (uint32_t)(x_end - x); return *reinterpret_cast<const int4 *>(arr + x + (o < r ? o : r)); };
-    int4 c0 = quad(4 * lane), c1 = quad(256 + 4 * lane);
-    for (; x < Q_hi; x += 512) {
-        // the next 512 entries are issued before the current ones are touched: the wait below them is for c0 / c1 only
-        const int4 n0 = quad(512 + 4 * lane), n1 = quad(768 + 4 * lane);
-#pragma unroll
-        for (int c = 0; c < 2; c++) {
-            int32_t xc = x + c * 256;
-            if (xc >= Q_hi) break;                        // wave-uniform
-            int4 v = c ? c1 : c0;
-            int32_t pb = xc + 4 * lane;
-            // entries at or above Q_hi belong to columns above the tile: never flagged (those below Q_lo lie below every s)
-            // the lane's four flags, and the four wave masks
-            // (a block that lies inside the run -- all but the first and the last one -- needs none of the position guards: wave-uniform)
-            const bool inner = xc >= Q_lo && xc + 256 <= Q_hi;
-            bool f0 = GE ? v.x >= thr : v.x < thr, f1 = GE ? v.y >= thr : v.y < thr, f2 = GE ? v.z >= thr : v.z < thr, f3 = GE ? v.w >= thr : v.w < thr;
-            if (!inner) { f0 = f0 && pb < Q_hi; f1 = f1 && pb + 1 < Q_hi; f2 = f2 && pb + 2 < Q_hi; f3 = f3 && pb + 3 < Q_hi; }
-            const unsigned long long m0 = __ballot(f0), m1 = __ballot(f1), m2 = __ballot(f2), m3 = __ballot(f3);
-            if (DET) {
-                const uint32_t span = (uint32_t)(sp_hi - sp_lo - 1);           // v in (sp_lo, sp_hi)  <=>  (uint)(v - sp_lo - 1) < span
-                bool s0 = (uint32_t)(v.x - sp_lo - 1) < span, s1 = (uint32_t)(v.y - sp_lo - 1) < span, s2 = (uint32_t)(v.z - sp_lo - 1) < span,
-                     s3 = (uint32_t)(v.w - sp_lo - 1) < span;
-                if (!inner) {
-                    s0 = s0 && pb >= Q_lo && pb < Q_hi; s1 = s1 && pb + 1 >= Q_lo && pb + 1 < Q_hi;
-                    s2 = s2 && pb + 2 >= Q_lo && pb + 2 < Q_hi; s3 = s3 && pb + 3 >= Q_lo && pb + 3 < Q_hi;
-                }
-                if (s0 || s1 || s2 || s3) {                           // rare; only the lanes holding a special work here
-#pragma unroll
-                    for (int j = 0; j < 4; j++) {
-                        if (j == 0 ? s0 : j == 1 ? s1 : j == 2 ? s2 : s3) {
-                            int32_t val = j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w;
-                            int slot = atomicAdd(s_cnt, 1);
-                            if (slot <= SMAX - 1) {
-                                s_es[slot] = pb + j;                  // (the position; its column is looked up after the stream: no load stalls the loop)
-                                s_v[slot] = (int32_t)(((uint32_t)val & 0x7fffffffu) | ((uint32_t)kind << 31));
-                            }
-                        }
-                    }
-                }
-            }
-            int32_t tot = __popcll(m0) + __popcll(m1) + __popcll(m2) + __popcll(m3);                       // uniform
-            // flagged entries in the lanes below this one (v_mbcnt chains), packed with the lane's own first three flags: one
-            // cross-lane read then gives a step everything it needs about the lane its column starts in
-            uint32_t P0 = 0;
-            P0 = __builtin_amdgcn_mbcnt_hi((uint32_t)(m0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m0, P0));
-            P0 = __builtin_amdgcn_mbcnt_hi((uint32_t)(m1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m1, P0));
-            P0 = __builtin_amdgcn_mbcnt_hi((uint32_t)(m2 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m2, P0));
-            P0 = __builtin_amdgcn_mbcnt_hi((uint32_t)(m3 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m3, P0));
-            const int32_t pack = (int32_t)((P0 << 3) | (uint32_t)f0 | ((uint32_t)f1 << 1) | ((uint32_t)f2 << 2));
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                int32_t idx = sk[k] - xc;                 // block position of the step's first entry (huge for invalid steps)
-                bool inside = idx > 0 && idx < 256;
-                if (__ballot(inside)) {                   // wave-uniform: some column of this group starts inside the block
-                    int32_t cidx = inside ? idx : 0;
-                    int src = cidx >> 2, comp = cidx & 3;
-                    const int32_t g = __shfl(pack, src);
-                    int32_t Fb = (g >> 3) + __popc((uint32_t)g & ((1u << comp) - 1u));        // flagged entries of the block below position idx
-                    acc[k] += idx <= 0 ? tot : (inside ? tot - Fb : 0);
-                } else {
-                    acc[k] += idx <= 0 ? tot : 0;
-                }
-            }
-        }
-        c0 = n0; c1 = n1;
-    }
-}
-
-// The same stream in parts, for the second tile of a wave with two (k_lpass_own<PAIR>): its stages leave while the first tile is at
-// work -- tile_head_loads (the prologue's loads, untouched) next to the first tile's, then behind the first tile's stream
-// tile_counters (counters, the run's ends) and tile_first (the first two blocks), then tile_trips (the loop).  The first tile, like
-// every one-tile wave, goes through interior_stream itself.  (interior_stream written as these four in a row computes the same,
-// but the compiler then lets the first trip's prefetch share a register with the second block and waits for the first two blocks
-// before it sends the prefetch: one round trip more per tile of more than one trip, 1 % on the windowed layers.  So the one-tile
-// form keeps its own text, and its code is what it was.)
-struct TileHead { int32_t cp[4], pv[4], ptop, qhi, qlo; int2 b0, b1; };      // (PK: cp the packed words, ptop / qlo those of column p_first / the last column, b0 / b1 the bases)
-struct TileRun { int32_t Q_lo, Q_hi, x, x_end; int4 c0, c1; };
-
-template <bool PK = false>
-__device__ __forceinline__ void tile_head_loads(TileHead &h, const int32_t *__restrict__ cpos, const int32_t *__restrict__ psum, int32_t p_first, int32_t tl,
-                                                int head, int lane, const int2 *__restrict__ vb = nullptr)
-{
-    // Prologue, one group of loads: the column pointers of the lane's four steps (a step beyond tl reads the tile's last column),
-    // the run's two ends, and with psum (wave-uniform; own_split) what a step starts from: psum[end of the run's columns] -
-    // psum[its column], what the columns hold apart from the streamed entries.  (The counters are live through the loop anyway.)
-    const int32_t *__restrict__ cl = cpos + (p_first - tl), *__restrict__ pl = (psum ? psum : cpos) + (p_first - tl);      // the tile's last column
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int32_t e = lane + 64 * k;
-        const uint32_t d = (uint32_t)(tl - (e < tl ? e : tl)) & 255u;
-        h.cp[k] = cl[d];
-        if (!PK) h.pv[k] = pl[d];
-    }
-    if constexpr (PK) {                // (see interior_stream)
-        h.ptop = cl[tl];
-        h.qlo = cl[0];
-        h.b0 = vb[0]; h.b1 = vb[1];
-        return;
-    }
-    // head != 0: step 0 is the candidate p_first itself (no column stepped over): the run ends in front of that column
-    h.ptop = pl[tl + 1 - head];
-    h.qhi = cl[tl + 1 - head];
-    h.qlo = cl[0];
-}
-
-// Entries: a lane whose four positions start at or above Q_hi reads the run's last aligned quad instead -- inside the eight
-// entries of slack behind every streamed array (next: ensure_links, flast: ensure_self, + 16; vnext: split_build, + 8) -- and
-// what it reads is never flagged: every block that is not `inner` guards its flags by position, an inner one holds run entries only.
-// (x <= x_end wherever this is called: the offset from the trip's first entry is unsigned and below 1024 or x_end - x)
-__device__ __forceinline__ int4 tile_quad(const int32_t *__restrict__ arr, int32_t x, int32_t x_end, uint32_t o)
-{
-    const uint32_t r = (uint32_t)(x_end - x);
-    return *reinterpret_cast<const int4 *>(arr + x + (o < r ? o : r));
-}
-
-template <bool PK = false>
-__device__ __forceinline__ void tile_counters(const TileHead &h, int32_t tl, int lane, bool psum, int32_t acc[4], int32_t sk[4], TileRun &r, int head = 0)
-{
-    if constexpr (PK) {
-        const uint32_t wt = (uint32_t)__builtin_amdgcn_readfirstlane(h.ptop), wl = (uint32_t)__builtin_amdgcn_readfirstlane(h.qlo);
-        r.Q_hi = head ? h.b0.x + (int32_t)(wt & 0xffffu) : h.b1.x;
-        r.Q_lo = h.b0.x + (int32_t)(wl & 0xffffu);
-        const int32_t ptop = head ? (int32_t)(wt >> 16) : h.b1.y - h.b0.y;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const bool on = lane + 64 * k <= tl;
-            sk[k] = on ? h.b0.x + (int32_t)((uint32_t)h.cp[k] & 0xffffu) : INT32_MAX;
-            acc[k] = on ? ptop - (int32_t)((uint32_t)h.cp[k] >> 16) : 0;
-        }
-    } else {
-    r.Q_hi = __builtin_amdgcn_readfirstlane(h.qhi);
-    r.Q_lo = __builtin_amdgcn_readfirstlane(h.qlo);
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const bool on = lane + 64 * k <= tl;
-        sk[k] = on ? h.cp[k] : INT32_MAX;
-        acc[k] = (psum && on) ? h.ptop - h.pv[k] : 0;
-    }
-    }
-    r.x_end = r.Q_hi & ~3;
-    r.x = r.Q_lo & ~3;
-}
-
-__device__ __forceinline__ void tile_first(const int32_t *__restrict__ arr, int lane, TileRun &r)
-{
-    r.c0 = tile_quad(arr, r.x, r.x_end, 4 * lane);
-    r.c1 = tile_quad(arr, r.x, r.x_end, 256 + 4 * lane);
-}
-
-template <bool GE, bool DET = false>
-__device__ __forceinline__ void tile_trips(const int32_t *__restrict__ arr, TileRun &r, int32_t thr, int lane, int32_t acc[4], const int32_t sk[4],
-                                           int32_t sp_lo = 0, int32_t sp_hi = 0, int32_t *s_es = nullptr, int32_t *s_v = nullptr, int32_t *s_cnt = nullptr,
-                                           int kind = 0)
-{
-    const int32_t Q_lo = r.Q_lo, Q_hi = r.Q_hi, x_end = r.x_end;
-    int32_t x = r.x;
-    int4 c0 = r.c0, c1 = r.c1;
-    for (; x < Q_hi; x += 512) {
-        // the next 512 entries are issued before the current ones are touched: the wait below them is for c0 / c1 only
-        const int4 n0 = tile_quad(arr, x, x_end, 512 + 4 * lane), n1 = tile_quad(arr, x, x_end, 768 + 4 * lane);
-#pragma unroll
-        for (int c = 0; c < 2; c++) {
-            int32_t xc = x + c * 256;
-            if (xc >= Q_hi) break;                        // wave-uniform
-            int4 v = c ? c1 : c0;
-            int32_t pb = xc + 4 * lane;
-            // entries at or above Q_hi belong to columns above the tile: never flagged (those below Q_lo lie below every s)
-            // the lane's four flags, and the four wave masks
-            // (a block that lies inside the run -- all but the first and the last one -- needs none of the position guards: wave-uniform)
-            const bool inner = xc >= Q_lo && xc + 256 <= Q_hi;
-            bool f0 = GE ? v.x >= thr : v.x < thr, f1 = GE ? v.y >= thr : v.y < thr, f2 = GE ? v.z >= thr : v.z < thr, f3 = GE ? v.w >= thr : v.w < thr;
-            if (!inner) { f0 = f0 && pb < Q_hi; f1 = f1 && pb + 1 < Q_hi; f2 = f2 && pb + 2 < Q_hi; f3 = f3 && pb + 3 < Q_hi; }
-            const unsigned long long m0 = __ballot(f0), m1 = __ballot(f1), m2 = __ballot(f2), m3 = __ballot(f3);
-            if (DET) {
-                const uint32_t span = (uint32_t)(sp_hi - sp_lo - 1);           // v in (sp_lo, sp_hi)  <=>  (uint)(v - sp_lo - 1) < span
-                bool s0 = (uint32_t)(v.x - sp_lo - 1) < span, s1 = (uint32_t)(v.y - sp_lo - 1) < span, s2 = (uint32_t)(v.z - sp_lo - 1) < span,
-                     s3 = (uint32_t)(v.w - sp_lo - 1) < span;
-                if (!inner) {
-                    s0 = s0 && pb >= Q_lo && pb < Q_hi; s1 = s1 && pb + 1 >= Q_lo && pb + 1 < Q_hi;
-                    s2 = s2 && pb + 2 >= Q_lo && pb + 2 < Q_hi; s3 = s3 && pb + 3 >= Q_lo && pb + 3 < Q_hi;
-                }
-                if (s0 || s1 || s2 || s3) {                           // rare; only the lanes holding a special work here
-#pragma unroll
-                    for (int j = 0; j < 4; j++) {
-                        if (j == 0 ? s0 : j == 1 ? s1 : j == 2 ? s2 : s3) {
-                            int32_t val = j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w;
-                            int slot = atomicAdd(s_cnt, 1);
-                            if (slot <= SMAX - 1) {
-                                s_es[slot] = pb + j;                  // (the position; its column is looked up after the stream: no load stalls the loop)
-                                s_v[slot] = (int32_t)(((uint32_t)val & 0x7fffffffu) | ((uint32_t)kind << 31));
-                            }
-                        }
-                    }
-                }
-            }
-            int32_t tot = __popcll(m0) + __popcll(m1) + __popcll(m2) + __popcll(m3);                       // uniform
-            // flagged entries in the lanes below this one (v_mbcnt chains), packed with the lane's own first three flags: one
-            // cross-lane read then gives a step everything it needs about the lane its column starts in
-            uint32_t P0 = 0;
-            P0 = __builtin_amdgcn_mbcnt_hi((uint32_t)(m0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m0, P0));
-            P0 = __builtin_amdgcn_mbcnt_hi((uint32_t)(m1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m1, P0));
-            P0 = __builtin_amdgcn_mbcnt_hi((uint32_t)(m2 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m2, P0));
-            P0 = __builtin_amdgcn_mbcnt_hi((uint32_t)(m3 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m3, P0));
-            const int32_t pack = (int32_t)((P0 << 3) | (uint32_t)f0 | ((uint32_t)f1 << 1) | ((uint32_t)f2 << 2));
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                int32_t idx = sk[k] - xc;                 // block position of the step's first entry (huge for invalid steps)
-                bool inside = idx > 0 && idx < 256;
-                if (__ballot(inside)) {                   // wave-uniform: some column of this group starts inside the block
-                    int32_t cidx = inside ? idx : 0;
-                    int src = cidx >> 2, comp = cidx & 3;
-                    const int32_t g = __shfl(pack, src);
-                    int32_t Fb = (g >> 3) + __popc((uint32_t)g & ((1u << comp) - 1u));        // flagged entries of the block below position idx
-                    acc[k] += idx <= 0 ? tot : (inside ? tot - Fb : 0);
-                } else {
-                    acc[k] += idx <= 0 ? tot : 0;
-                }
-            }
-        }
-        c0 = n0; c1 = n1;
-    }
-}
-
-
-// ------------------------------------------------------------------ long tasks with tiles of their own
-// A task with >= OWN_MIN steps gets tiles of its own: every tile lies in one task, so all of them -- head and tail included --
-// take the uniform path: one contiguous run of the link array, suffix counts, tile-local evaluation.  k_own_map: tile ->
-// (task, tile index inside the task); k_lpass_own: one wave per tile; k_fix_own: one lane per short task, one block per trip of a longer one merges the tiles
-// (adding the counts made before each tile).  Tile ids are task-major, the head tile first.  Two geometries (own_ntiles / own_tile_geo):
-//   blk = 1 (default, cp_set_option("own_blk")): one tile per 256-column block floor(p / LT) the task's candidates [a, B] touch
-//           (the head and the tail tile partial: at most one tile more than cdiv(L, LT)).  k_own_map counts the tiles of every
-//           block, a scan and k_blk_order sort the tile ids by block, and k_lpass_own runs them in that order: the four waves
-//           of a workgroup mostly stream the same block's entries for different tasks (the bit planes of the round) at the
-//           same time, and all but the first find them in the caches.
-//   blk = 0: tiles counted from the task's own head, LT steps each (the last one partial), in task order.
-// bcnt (blk = 1): tiles per column block, and each tile's rank inside its block (brank)
-// items (outside the gap rounds): the work list of the merge, k_fix_own -- one item {task, first tile} per trip of FIX_TRIP tiles of
-// every task of more than FIX_SERIAL tiles, appended by the trip's first tile (a wave-aggregated atomic on rc->n_items; a dropped
-// round walks no tiles and lists nothing); item_of[that tile] = the item's index, by which the merge finds a task's trips in order.
-__global__ void __launch_bounds__(256) k_own_map(RoundCounts *__restrict__ rc, const int64_t *__restrict__ toffs, const int4 *__restrict__ tdesc,
-                                                 const int32_t *__restrict__ rlen, int4 *__restrict__ rec, int32_t *__restrict__ tile_task,
-                                                 const uint8_t *__restrict__ tb, int32_t *__restrict__ gap_hi, int tau, int64_t n, int blk,
-                                                 int32_t *__restrict__ bcnt, int32_t *__restrict__ brank, int2 *__restrict__ items,
-                                                 int32_t *__restrict__ item_of, int split, const int32_t *__restrict__ ioffs)
-{
-    // ioffs (round_alloc): set-up reserved every task's items, trip j of task t is item ioffs[t] + j -- computed, not drawn: no
-    // same-address atomic per wave, no item_of; rc->n_items holds their number already
-    const int64_t ntask = rc->nown, ntile = rc->NT;
-    for (int64_t tile = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; tile < ntile; tile += (int64_t)gridDim.x * blockDim.x) {
-    int64_t lo = 0, hi = ntask;                       // last task with toffs[task] <= tile
-    while (hi - lo > 1) {
-        int64_t mid = (lo + hi) >> 1;
-        if (toffs[mid] <= tile) lo = mid; else hi = mid;
-    }
-    int32_t kt = (int32_t)(tile - toffs[lo]);
-    if (items && ioffs) {
-        if (kt % FIX_TRIP == 0 && toffs[lo + 1] - toffs[lo] > FIX_SERIAL) items[ioffs[lo] + kt / FIX_TRIP] = make_int2((int32_t)lo, kt);
-    } else if (items) {
-        const bool first = kt % FIX_TRIP == 0 && toffs[lo + 1] - toffs[lo] > FIX_SERIAL;
-        const unsigned long long mf = __ballot(first);      // (the lanes still in the loop)
-        if (mf) {
-            const int lane = threadIdx.x & 63, lead = __ffsll((long long)mf) - 1;
-            int32_t base = 0;
-            if (lane == lead) base = atomicAdd(&rc->n_items, (int32_t)__popcll(mf));
-            base = __shfl(base, lead);
-            if (first) {
-                const int32_t it = base + __popcll(mf & ((1ull << lane) - 1ull));
-                items[it] = make_int2((int32_t)lo, kt);
-                item_of[tile] = it;
-            }
-        }
-    }
-    int4 td = tdesc[lo];
-    int32_t pf, tl;
-    own_tile_geo(blk, td.x, rlen[lo], kt, pf, tl);
-    // {column of step 0, row, pos[row], split plane (bits 10 ..; 0: the tile streams the whole columns) | tl (8 bits) | tile of a gap task | head}
-    const bool isgap = gap_hi != nullptr;
-    const int sb = (split && tb[lo] >= SPLIT_BMIN) ? tb[lo] : 0;
-    rec[tile] = make_int4(pf, td.z, td.w, (sb << 10) | (tl << 2) | (isgap ? 2 : 0) | (kt == 0 ? 1 : 0));
-    if (split == 2) {                                  // (a launch that also holds tiles of the planes below: counted here, one atomic per wave)
-        const unsigned long long ms = __ballot(sb != 0);
-        if (ms && (int)(threadIdx.x & 63) == __ffsll((long long)ms) - 1) atomicAdd(&rc->n_split, (int32_t)__popcll(ms));
-    }
-    tile_task[tile] = (int32_t)lo;
-    if (bcnt) brank[tile] = atomicAdd(&bcnt[pf / LT], 1);
-    if (isgap) {                                       // gap pass: rows (r - 2^tau, hi) of the rectangle are finished together
-        int64_t r = td.z, b = tb[lo];
-        int64_t hi = r + ((int64_t)1 << tau), re = (((r >> b) + 1) << b);
-        if (hi > re) hi = re;
-        if (hi > n + 1) hi = n + 1;
-        gap_hi[tile] = (int32_t)hi;
-    }
-    }
-}
-
-// the counting sort's scatter: the tiles of column block c are border[bstart[c] .. bstart[c + 1]).  The counts have been scanned
-// by now; the tile's record goes to the same slot of srec; and the tile of rank 0 of every block that has tiles puts its block's count back to zero: bcnt is all zero between
-// rounds without a clearing pass (k_own_map and this kernel walk the same rc->NT tiles).
-__global__ void __launch_bounds__(256) k_blk_order(const RoundCounts *__restrict__ rc, const int4 *__restrict__ rec, const int32_t *__restrict__ brank,
-                                                   const int64_t *__restrict__ bstart, int32_t *__restrict__ border, int4 *__restrict__ srec,
-                                                   int32_t *__restrict__ bcnt)
-{
-    const int64_t ntile = rc->NT;
-    for (int64_t tile = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; tile < ntile; tile += (int64_t)gridDim.x * blockDim.x) {
-        const int4 r = rec[tile];
-        const int32_t c = r.x / LT, rk = brank[tile];
-        const int64_t slot = bstart[c] + rk;
-        border[slot] = (int32_t)tile;
-        srec[slot] = r;                                // (by value: the wave that runs the slot reads its record without the tile id)
-        if (rk == 0) bcnt[c] = 0;
-    }
-}
-
-// The tile's own winner (k_lpass_own outside the gap passes): candidates from the lane's four steps, then the wave arg-min.
-// sk: the pin positions of the steps, wv: W of the candidates, acc / acc2: the counts; lane 0 holds the result.
-template <typename TC, bool HYP>
-__device__ __forceinline__ void own_tile_cands(Best<TC, HYP> cand[4], const int4 rec, int32_t tl, int head, int isA, const DevModel<TC> &M, TC alpha, int lane,
-                                               const int32_t acc[4], const int32_t acc2[4], const int32_t sk[4], const TC wv[4])
-{
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        int32_t e = lane + 64 * k;
-        best_clear(cand[k]);
-        if (e <= tl && !(head && isA && e == 0)) {     // round A: the head element p = r is not a candidate
-            int32_t p = rec.x - e;
-            TC fv = dm_apply_affine(M, alpha, (int64_t)(rec.y - p), (int64_t)(rec.z - sk[k]), (int64_t)acc[k], (int64_t)acc2[k]);
-            cand[k].v = cadd(wv[k], fv); cand[k].p = p; cand[k].nn = acc[k]; best_set_nl(cand[k], acc2[k]);
-        }
-    }
-}
-
-template <typename TC, bool HYP>
-__device__ __forceinline__ Best<TC, HYP> own_tile_winner(const Best<TC, HYP> cand[4], int lane)
-{
-    Best<TC, HYP> best; best_clear(best);
-#pragma unroll
-    for (int k = 0; k < 4; k++) best = better(best, cand[k]);       // increasing e = decreasing p: an earlier candidate wins ties
-    for (int o = 32; o > 0; o >>= 1) {              // wave arg-min; ties -> larger p
-        int src = (lane + o) & 63;
-        Best<TC, HYP> c; best_clear(c); c.v = shfl64(best.v, src); c.p = __shfl(best.p, src); c.nn = __shfl(best.nn, src);
-        if (HYP) best_set_nl(c, __shfl(best_nl(best), src));
-        bool take = (best.p < 0) ? (c.p >= 0) : (c.p >= 0 && (c.v < best.v || (c.v == best.v && c.p > best.p)));
-        if (lane + o < 64 && take) best = c;
-    }
-    return best;
-}
-
-// cp_set_option("own_pair"): the two slots of the run order wave w takes.  false: no slot is left for the wave.  A wave whose
-// second slot lies beyond the order takes its first one again (s1 == s0: it loads what it has loaded, and stores once).
-__host__ __device__ __forceinline__ bool own_pair_slots(int64_t w, int64_t nt, int64_t &s0, int64_t &s1)
-{
-    s0 = 2 * w;
-    s1 = 2 * w + 1 < nt ? 2 * w + 1 : s0;
-    return w >= 0 && s0 < nt;
-}
-
-// border, a_srec (blk = 1): the tile ids and their records in column-block order; wave k takes tile border[k], whose record is a_srec[k]
-// PAIR (own_pair; neither GAP nor HYP): wave k takes the slots 2k and 2k + 1 of that order.
-// PK (own_pack; not HYP): the split tiles of the launch take the packed words of their plane and the bases of their block
-// (interior_stream<PK>): a_vpos is SplitLinks::vpk then and a_vsa is SplitLinks::vbase (pairs; stride: the blocks of vstride columns
-// + 1) -- the argument list, and with it the code of the other instantiations, is what it was.  PAIR: every tile of the launch is split (own_stream).
-template <typename TC, bool HYP, bool GAP, bool PAIR = false, bool PK = false>
-__global__ void __launch_bounds__(256) k_lpass_own(int isA, const RoundCounts *__restrict__ rc, const int32_t *__restrict__ border,
-                                                   const int32_t *__restrict__ a_pos, const int32_t *__restrict__ a_next,
-                                                   const int32_t *__restrict__ a_fpos, const int32_t *__restrict__ a_flast,
-                                                   int32_t *__restrict__ a_tileS, int32_t *__restrict__ a_tileS2, const int4 *__restrict__ a_rec,
-                                                   const int4 *__restrict__ a_srec, const TC *__restrict__ W, DevModel<TC> M, TC alpha, Best<TC, HYP> *__restrict__ part,
-                                                   int tau, const int32_t *__restrict__ gap_hi, uint8_t *__restrict__ spec, int force_spec,
-                                                   Best<TC, HYP> *__restrict__ sub, int32_t *__restrict__ spv,
-                                                   const int32_t *__restrict__ a_col, const int32_t *__restrict__ a_ffirst,
-                                                   const int32_t *__restrict__ a_vnext, const int32_t *__restrict__ a_vpos,
-                                                   const int32_t *__restrict__ a_vsa, int64_t vstride)
-{
-    // GAP (rounds tau <= gap_tau, see k_gap_finish): the tile is evaluated for ALL rows r' of (r - 2^tau, hi) at once: the counts
-    // taken here are those of the entries every such row counts (next >= hi - 1; last <= r - 2^tau), the candidates are valued
-    // with the task's own row (the rows differ by terms that do not depend on the candidate), and `spec` says whether the tile
-    // holds an entry that only some of the rows count.
-    // (Tried: tiles visited in column order, one contiguous share of the order per XCD, so that the ~10 passes of the bit planes
-    //  over a column meet in L2: 10 % off this kernel, less than the sort of the tile list costs.  The block order of own_blk is a
-    //  counting sort by 256-column block (k_own_map, one scan, k_blk_order): 4 % off, and the sort is paid.  Staging each block's
-    //  entries once per round in LDS for all its tiles (one workgroup per block) was 23 % slower: DESIGN.md section 6b.)
-    // (No grid-stride loop here.  The host launches one wave per tile -- PAIR: per two tiles -- of the buffer's CAPACITY, which
-    //  the round's verdict (k_round_scans) has checked the true count against.  A loop over tiles cost 14 VGPRs when the body
-    //  held 58 and that meant two waves per SIMD; since the grouped loads <long,false,false> holds 42, and PAIR spends the room on
-    //  a second tile whose stages leave with the first one's: DESIGN.md section 6.)
-    int lane = threadIdx.x & 63;
-    if constexpr (PAIR && !HYP && !GAP) {
-        // Two tiles, A and B, of any two tasks, planes and blocks: everything of a tile is scalar per tile.  Both records leave
-        // together, then both prologues; A streams as a one-tile wave does (interior_stream; what B's prologue brought waits in 11
-        // VGPRs); A's end group (pin positions, W) and B's first two blocks leave together and A is evaluated and stored under
-        // them; B streams, then its end group and evaluation.  Of B's four exposed round trips outside its trips three are gone.  (Tried: B's first blocks issued with A's, and A evaluated
-        // after B's stream, so that A's end group hides too: 71 VGPRs = seven waves per SIMD; held to 64 it spills.)
-        // A lone wave (the order ends at A) runs A twice and a scalar branch keeps it from storing twice.
-        int64_t s0, s1;
-        if (!own_pair_slots((int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), rc->NT, s0, s1)) return;
-        const bool lone = s1 == s0;
-
-        // A model whose pin coefficient is zero multiplies the pin count by it: its lanes all read the pin position of the tile's
-        // last column instead (one line, not four: 4 of a step's ~25 bytes) -- a count >= 0 like the true one, so the product is
-        // the same zero, bit for bit; the load stays where it is, unconditional.
-        const uint32_t pinm = M.p[CP_P_PIN] != (TC)0 ? 255u : 0u;
-        const int4 vA = border ? a_srec[s0] : a_rec[s0], vB = border ? a_srec[s1] : a_rec[s1];
-        int64_t tA = s0, tB = s1;
-        if (border) { tA = border[s0]; tB = border[s1]; }
-        const int4 rA = make_int4(__builtin_amdgcn_readfirstlane(vA.x), __builtin_amdgcn_readfirstlane(vA.y), __builtin_amdgcn_readfirstlane(vA.z),
-                                  __builtin_amdgcn_readfirstlane(vA.w));
-        const int4 rB = make_int4(__builtin_amdgcn_readfirstlane(vB.x), __builtin_amdgcn_readfirstlane(vB.y), __builtin_amdgcn_readfirstlane(vB.z),
-                                  __builtin_amdgcn_readfirstlane(vB.w));
-        const int hdA = rA.w & 1, hdB = rB.w & 1;
-        const int32_t tlA = (rA.w >> 2) & 255, tlB = (rB.w >> 2) & 255;
-        const int sbA = rA.w >> 10, sbB = rB.w >> 10;                    // (own_split: the plane, or 0 -- one tile of a pair may be split, the other not)
-        const int64_t soA = sbA ? (int64_t)(sbA - SPLIT_BMIN) * vstride : 0, soB = sbB ? (int64_t)(sbB - SPLIT_BMIN) * vstride : 0;
-        const int32_t *__restrict__ arrA = (PK || sbA) ? a_vnext : a_next, *__restrict__ arrB = (PK || sbB) ? a_vnext : a_next;
-        TileHead hB;
-        TileRun uB;
-        int32_t accA[4], accB[4], skA[4], skB[4];
-        const int32_t zero4[4] = {0, 0, 0, 0};
-        if constexpr (PK) {
-            const int64_t vbstride = ((vstride + 255) >> 8) + 1;
-            const int2 *__restrict__ a_vbase = reinterpret_cast<const int2 *>(a_vsa);
-            const int2 *__restrict__ vbA = a_vbase + (int64_t)(sbA - SPLIT_BMIN) * vbstride + (rA.x >> 8);
-            const int2 *__restrict__ vbB = a_vbase + (int64_t)(sbB - SPLIT_BMIN) * vbstride + (rB.x >> 8);
-            tile_head_loads<true>(hB, a_vpos + soB, nullptr, rB.x, tlB, hdB, lane, vbB);
-            interior_stream<true, false, true>(a_vnext, a_vpos + soA, rA.x, tlA, rA.y, lane, accA, skA, hdA, 0, 0, nullptr, nullptr, nullptr, 0, nullptr, vbA);
-            tile_counters<true>(hB, tlB, lane, true, accB, skB, uB, hdB);
-        } else {
-        tile_head_loads(hB, sbB ? a_vpos + soB : a_pos, sbB ? a_vsa + soB : (const int32_t *)nullptr, rB.x, tlB, hdB, lane);
-        interior_stream<true>(arrA, sbA ? a_vpos + soA : a_pos, rA.x, tlA, rA.y, lane, accA, skA, hdA, 0, 0, nullptr, nullptr, nullptr, 0,
-                              sbA ? a_vsa + soA : (const int32_t *)nullptr);
-        tile_counters(hB, tlB, lane, sbB != 0, accB, skB, uB);
-        }
-        TC wv[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int32_t e = lane + 64 * k;
-            const uint32_t d = (uint32_t)(tlA - (e < tlA ? e : tlA)) & 255u;
-            skA[k] = (a_pos + (rA.x - tlA))[d & pinm];
-            wv[k] = (W + (rA.x - tlA))[d];
-        }
-        tile_first(arrB, lane, uB);
-        Best<TC, HYP> cand[4];
-        {
-            const int sel = tlA >> 6;
-            if (lane == (tlA & 63)) a_tileS[tA] = sel == 0 ? accA[0] : sel == 1 ? accA[1] : sel == 2 ? accA[2] : accA[3];
-            own_tile_cands<TC, HYP>(cand, rA, tlA, hdA, isA, M, alpha, lane, accA, zero4, skA, wv);
-            const Best<TC, HYP> best = own_tile_winner<TC, HYP>(cand, lane);
-            if (lane == 0) part[tA] = best;
-        }
-        tile_trips<true>(arrB, uB, rB.y, lane, accB, skB);
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int32_t e = lane + 64 * k;
-            const uint32_t d = (uint32_t)(tlB - (e < tlB ? e : tlB)) & 255u;
-            skB[k] = (a_pos + (rB.x - tlB))[d & pinm];
-            wv[k] = (W + (rB.x - tlB))[d];
-        }
-        if (lone) return;
-        {
-            const int sel = tlB >> 6;
-            if (lane == (tlB & 63)) a_tileS[tB] = sel == 0 ? accB[0] : sel == 1 ? accB[1] : sel == 2 ? accB[2] : accB[3];
-            own_tile_cands<TC, HYP>(cand, rB, tlB, hdB, isA, M, alpha, lane, accB, zero4, skB, wv);
-            const Best<TC, HYP> best = own_tile_winner<TC, HYP>(cand, lane);
-            if (lane == 0) part[tB] = best;
-        }
-        return;
-    }
-    int64_t tile = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if (tile >= rc->NT) return;
-    // (own_blk: k_blk_order left the record next to the tile id, in the order the waves run: one level of loads, not two)
-    const int4 vrec = border ? a_srec[tile] : a_rec[tile];
-    if (border) tile = border[tile];
-    // (the record is the wave's: its words as scalars -- the addresses made from them are scalar bases, and five VGPRs fewer)
-    const int32_t rw = __builtin_amdgcn_readfirstlane(vrec.w);
-    const int4 rec = make_int4(__builtin_amdgcn_readfirstlane(vrec.x), __builtin_amdgcn_readfirstlane(vrec.y), __builtin_amdgcn_readfirstlane(vrec.z), rw);
-    int head = rw & 1;
-    int32_t tl = (rw >> 2) & 255;
-    int32_t acc[4], acc2[4] = {0, 0, 0, 0}, sk[4], sk2[4];
-    __shared__ int32_t s_es_all[4][2][SMAX + 1], s_v_all[4][2][SMAX + 1];      // the wave's specials: as found / sorted by step
-    __shared__ int32_t s_cnt_all[4];
-    int32_t(*s_es)[SMAX + 1] = s_es_all[threadIdx.x >> 6], (*s_v)[SMAX + 1] = s_v_all[threadIdx.x >> 6];
-    int ns = 0;
-    if (GAP && (rw & 2)) {
-        int32_t *s_cnt = &s_cnt_all[threadIdx.x >> 6];
-        if (lane == 0) *s_cnt = 0;
-        __threadfence_block();
-        int32_t rL = rec.y - (1 << tau), hi1 = gap_hi[tile] - 1;
-        // gap_split (k_own_map put the plane into the record, as for the other rounds): the classification of SplitLinks holds for a
-        // gap task of plane b -- its rows (rL, hi) lie in the rectangle's rows, thr = hi - 1 and the special interval (rL, hi - 1) in
-        // the sibling block's range -- so an entry below the plane is neither counted nor special, one above it is counted by every
-        // row and never special (the prefix difference the stream starts its counters from), and only the plane's variable entries
-        // are compared and tested
-        const int sb = HYP ? 0 : rw >> 10;                               // (scalar: the arrays stay scalar operands)
-        const int64_t so = sb ? (int64_t)(sb - SPLIT_BMIN) * vstride : 0;
-        if constexpr (PK) {            // (wave-uniform: the plane-7 tiles of the launch stream the whole columns)
-            if (sb) interior_stream<true, true, true>(a_vnext, a_vpos + so, rec.x, tl, hi1, lane, acc, sk, head, rL, hi1, s_es[0], s_v[0], s_cnt, 0, nullptr,
-                                                      reinterpret_cast<const int2 *>(a_vsa) + (int64_t)(sb - SPLIT_BMIN) * (((vstride + 255) >> 8) + 1) + (rec.x >> 8));
-            else interior_stream<true, true>(a_next, a_pos, rec.x, tl, hi1, lane, acc, sk, head, rL, hi1, s_es[0], s_v[0], s_cnt, 0);
-        } else
-        interior_stream<true, true>(sb ? a_vnext : a_next, sb ? a_vpos + so : a_pos, rec.x, tl, hi1, lane, acc, sk, head, rL, hi1, s_es[0], s_v[0], s_cnt, 0,
-                                    sb ? a_vsa + so : (const int32_t *)nullptr);
-        if (HYP) interior_stream<false, true>(a_flast, a_fpos, rec.x, tl, rL + 1, lane, acc2, sk2, head, rL, hi1, s_es[0], s_v[0], s_cnt, 1);
-        __threadfence_block();
-        ns = *s_cnt;
-        if (force_spec) ns = SMAX + 1;
-        if (ns > 0 && ns <= SMAX) {                     // positions -> steps: first step whose candidate has the entry's column on its right
-            if (HYP) {
-                if (lane < ns) {
-                    const int32_t q = s_es[0][lane];
-                    const bool k1 = s_v[0][lane] < 0;   // (bit 31: an entry of the second list)
-                    s_es[0][lane] = rec.x - (k1 ? a_ffirst[q] : a_col[q]);
-                }
-            } else {
-                // ... = the number of the tile's steps whose column starts above the position, from the starts the wave holds (sk: of
-                // the streamed array, whichever it is).  Empty columns have equal starts: the entry's column is the LARGEST one that
-                // starts at or below it.  (At most SMAX rounds of four ballots, in the rare tile with specials; no array, no load.)
-                int32_t es = 0;
-                for (int i = 0; i < ns; i++) {
-                    const int32_t q = s_es[0][i];       // (uniform)
-                    int32_t c = 0;
-#pragma unroll
-                    for (int k = 0; k < 4; k++) c += (int32_t)__popcll(__ballot(lane + 64 * k <= tl && sk[k] > q));
-                    if (lane == i) es = c;
-                }
-                __threadfence_block();
-                if (lane < ns) s_es[0][lane] = es;
-            }
-            __threadfence_block();
-        }
-        if (!HYP) {                                     // (the pin count wants the column's own position: what sk holds unless the tile is split; reloaded either way)
-#pragma unroll
-            for (int k = 0; k < 4; k++) { const int32_t e = lane + 64 * k; sk[k] = (a_pos + (rec.x - tl))[(uint32_t)(tl - (e < tl ? e : tl)) & 255u]; }
-        }
-    } else if (!HYP && !GAP) {
-        // own_split (k_own_map put the plane into the record): only the plane's variable entries are streamed; the entries every
-        // row of the rectangle counts are a difference of prefix sums per step (the stream starts its counters from it), and the pin
-        // count wants the column's own position
-        const int sb = rw >> 10;                                         // (scalar: the arrays stay scalar operands)
-        const int64_t so = sb ? (int64_t)(sb - SPLIT_BMIN) * vstride : 0;
-        if constexpr (PK) {            // (wave-uniform: tiles of the planes below SPLIT_BMIN stream the whole columns)
-            if (sb) interior_stream<true, false, true>(a_vnext, a_vpos + so, rec.x, tl, rec.y, lane, acc, sk, head, 0, 0, nullptr, nullptr, nullptr, 0, nullptr,
-                                                       reinterpret_cast<const int2 *>(a_vsa) + (int64_t)(sb - SPLIT_BMIN) * (((vstride + 255) >> 8) + 1) + (rec.x >> 8));
-            else interior_stream<true>(a_next, a_pos, rec.x, tl, rec.y, lane, acc, sk, head);
-        } else
-        interior_stream<true>(sb ? a_vnext : a_next, sb ? a_vpos + so : a_pos, rec.x, tl, rec.y, lane, acc, sk, head, 0, 0, nullptr, nullptr, nullptr, 0,
-                              sb ? a_vsa + so : (const int32_t *)nullptr);
-        // (a_pos is what the stream's sk holds when the tile is not split: reloaded either way, in one group with W below)
-#pragma unroll
-        for (int k = 0; k < 4; k++) { const int32_t e = lane + 64 * k; sk[k] = (a_pos + (rec.x - tl))[(uint32_t)(tl - (e < tl ? e : tl)) & 255u]; }
-    } else {
-        interior_stream<true>(a_next, a_pos, rec.x, tl, rec.y, lane, acc, sk, head);
-        if (HYP) interior_stream<false>(a_flast, a_fpos, rec.x, tl, rec.y, lane, acc2, sk2, head);
-    }
-    // end of the wave, one group of loads: W of the lane's four candidates (and the pin positions above), at steps clamped into
-    // the tile; the evaluation selects afterwards
-    TC wv[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) { const int32_t e = lane + 64 * k; wv[k] = (W + (rec.x - tl))[(uint32_t)(tl - (e < tl ? e : tl)) & 255u]; }
-    int sel = tl >> 6;
-    if (lane == (tl & 63)) {
-        a_tileS[tile] = sel == 0 ? acc[0] : sel == 1 ? acc[1] : sel == 2 ? acc[2] : acc[3];
-        if (HYP) a_tileS2[tile] = sel == 0 ? acc2[0] : sel == 1 ? acc2[1] : sel == 2 ? acc2[2] : acc2[3];
-    }
-    // tile-local evaluation (the costs are affine in the counts; k_fix_own adds the counts made before the tile)
-    Best<TC, HYP> cand[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        int32_t e = lane + 64 * k;
-        best_clear(cand[k]);
-        if (e <= tl && !(head && isA && e == 0)) {     // round A: the head element p = r is not a candidate
-            int32_t p = rec.x - e;
-            TC fv = dm_apply_affine(M, alpha, (int64_t)(rec.y - p), (int64_t)(rec.z - sk[k]), (int64_t)acc[k], (int64_t)acc2[k]);
-            cand[k].v = cadd(wv[k], fv); cand[k].p = p; cand[k].nn = acc[k]; best_set_nl(cand[k], acc2[k]);
-        }
-    }
-    if (GAP && ns > SMAX) {                             // too many specials: k_gap_finish walks the tile entry by entry
-        if (lane == 0) spec[tile] = 255;
-        return;
-    }
-    if (!GAP || ns == 0) {                              // one winner
-        Best<TC, HYP> best; best_clear(best);
-#pragma unroll
-        for (int k = 0; k < 4; k++) best = better(best, cand[k]);       // increasing e = decreasing p: an earlier candidate wins ties
-        for (int o = 32; o > 0; o >>= 1) {              // wave arg-min; ties -> larger p
-            int src = (lane + o) & 63;
-            Best<TC, HYP> c; best_clear(c); c.v = shfl64(best.v, src); c.p = __shfl(best.p, src); c.nn = __shfl(best.nn, src);
-            if (HYP) best_set_nl(c, __shfl(best_nl(best), src));
-            bool take = (best.p < 0) ? (c.p >= 0) : (c.p >= 0 && (c.v < best.v || (c.v == best.v && c.p > best.p)));
-            if (lane + o < 64 && take) best = c;
-        }
-        if (lane == 0) { part[tile] = best; if (GAP) spec[tile] = 0; }
-        return;
-    }
-    // GAP with specials: they cut the tile into segments of candidates that see the same specials on their right; every
-    // segment keeps a winner of its own (the rows weigh the segments differently): one segmented arg-min scan.
-    __threadfence_block();                              // (lane 0 wrote the list)
-    if (lane < ns) {                                    // sort by step: rank = number of specials in front
-        int32_t es_i = s_es[0][lane]; int rank = 0;
-        for (int j = 0; j < ns; j++) { int32_t es_j = s_es[0][j]; rank += (es_j < es_i) || (es_j == es_i && j < lane); }
-        s_es[1][rank] = es_i; s_v[1][rank] = s_v[0][lane];
-    }
-    __threadfence_block();
-    int seg[4] = {0, 0, 0, 0}, hd[5] = {0, 0, 0, 0, 0};
-    for (int i = 0; i < ns; i++) {
-        int32_t es_i = s_es[1][i];                      // (uniform)
-#pragma unroll
-        for (int k = 0; k < 4; k++) { seg[k] += (es_i <= lane + 64 * k); hd[k] |= (es_i == lane + 64 * k); }
-    }
-    if (lane == 0) hd[0] = 1;
-    const int64_t sbase = tile * (SMAX + 1);
-    if (lane <= ns) {                                   // segments without a candidate (two specials at one step, a special at step 0)
-        int32_t lo = lane == 0 ? 0 : s_es[1][lane - 1], hi = lane == ns ? tl + 1 : s_es[1][lane];
-        if (hi <= lo) { Best<TC, HYP> z; best_clear(z); sub[sbase + lane] = z; }
-    }
-    Best<TC, HYP> bcarry; best_clear(bcarry);
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        int32_t e = lane + 64 * k;
-        Best<TC, HYP> x = cand[k];
-        int f = hd[k];
-        wave_segmin<TC, HYP>(x, f, lane);
-        if (!f) x = better(bcarry, x);
-        {
-            Best<TC, HYP> nb; best_clear(nb); nb.v = shfl64(x.v, 63); nb.p = __shfl(x.p, 63); nb.nn = __shfl(x.nn, 63);
-            if (HYP) best_set_nl(nb, __shfl(best_nl(x), 63));
-            bcarry = nb;
-        }
-        int nh = __shfl_down(hd[k], 1), nh0 = __shfl(hd[k + 1], 0);
-        if (lane == 63) nh = nh0;
-        if (e <= tl && (e == tl || nh)) sub[sbase + seg[k]] = x;       // the last candidate of a segment holds its winner
-    }
-    if (lane < ns) spv[sbase + lane] = s_v[1][lane];
-    if (lane == 0) spec[tile] = (uint8_t)ns;
-}
-
-// Merging the tiles of a task, one launch (k_fix_own), the role of a block chosen by its index.  The counts made before a tile
-// are the task's anchor plus the counts of the task's earlier tiles (tileS, written by k_lpass_own) -- sums inside ONE task, so no
-// device-wide prefix over the round's tiles is made for them.  (The gap rounds do make one: k_gap_finish and its helpers look
-// tiles up at random.)
-//   lane blocks: one LANE per task; up to FIX_SERIAL tiles are merged by the lane with a running sum, longer tasks are left to
-//   item blocks: one BLOCK per item {task, first tile} of the list k_own_map made: a trip of FIX_TRIP tiles, merged with the
-//     trip-LOCAL exclusive prefix as base (the trip's first tile: 0).  The costs are affine in the counts, so what the task's
-//     earlier trips counted adds the same amount to every candidate of the trip: neither the order nor the ties inside the trip
-//     depend on it.  A task of one trip is finished by its block (anchor added to the winner).  Otherwise the block leaves a
-//     record {winner, the trip's counts} and draws a ticket of its task; whoever draws the last one folds the task: the records in
-//     trip order, a running base from the anchor on, each trip winner raised by its base through the same fix_merge arithmetic
-//     (sums of integers below 2^53 / wrapping Int64: adding the base in two steps is exact) and compared by the same rule --
-//     smaller value, then larger p, a total order: the winner does not depend on who finishes when.  The folder puts the ticket
-//     back to zero (no clearing pass between rounds: the b_cnt pattern of k_blk_order).  No block waits for another one.
-//     Records cross XCDs: written with agent-scope stores, released at agent scope before the ticket is drawn, read by the
-//     folder behind an agent-scope acquire with agent-scope loads (never from a stale L1 / L2 line).
-// (Tried: k_lpass_own writing the winner of a single-tile task itself -- the dependent loads at the end of every wave cost it
-//  more than the merge saves.)
-template <typename TC, bool HYP>
-__device__ __forceinline__ void fix_merge(Best<TC, HYP> &acc, Best<TC, HYP> c, int64_t base, int64_t base2, const DevModel<TC> &M)
-{
-    if (c.p >= 0) {
-        c.v = cadd(c.v, dm_apply_affine(M, (TC)0, (int64_t)0, (int64_t)0, base, base2));
-        c.nn = (int32_t)(c.nn + base);
-        if (HYP) best_set_nl(c, (int32_t)(best_nl(c) + base2));
-    }
-    bool take = (acc.p < 0) ? (c.p >= 0) : (c.p >= 0 && (c.v < acc.v || (c.v == acc.v && c.p > acc.p)));
-    if (take) acc = c;
-}
-
-template <typename TC> __device__ __forceinline__ unsigned long long fix_bits(TC v);
-template <> __device__ __forceinline__ unsigned long long fix_bits<int64_t>(int64_t v) { return (unsigned long long)v; }
-template <> __device__ __forceinline__ unsigned long long fix_bits<double>(double v) { return (unsigned long long)__double_as_longlong(v); }
-template <typename TC> __device__ __forceinline__ TC fix_val(unsigned long long w);
-template <> __device__ __forceinline__ int64_t fix_val<int64_t>(unsigned long long w) { return (int64_t)w; }
-template <> __device__ __forceinline__ double fix_val<double>(unsigned long long w) { return __longlong_as_double((long long)w); }
-
-template <typename TC, bool HYP>
-__device__ __forceinline__ void best_wave_min(Best<TC, HYP> &acc, int lane)      // lane 0 ends with the wave's winner
-{
-    for (int o = 32; o > 0; o >>= 1) {
-        int src = (lane + o) & 63;
-        Best<TC, HYP> c; best_clear(c); c.v = shfl64(acc.v, src); c.p = __shfl(acc.p, src); c.nn = __shfl(acc.nn, src);
-        if (HYP) best_set_nl(c, __shfl(best_nl(acc), src));
-        bool take = (acc.p < 0) ? (c.p >= 0) : (c.p >= 0 && (c.v < acc.v || (c.v == acc.v && c.p > acc.p)));
-        if (lane + o < 64 && take) acc = c;
-    }
-}
-
-// grid: `iblocks` item blocks (grid stride over rc->n_items), then the lane blocks (grid stride over rc->nown)
-template <typename TC, bool HYP>
-__global__ void __launch_bounds__(256) k_fix_own(RoundCounts *__restrict__ rc, const int64_t *__restrict__ toffs, const Best<TC, HYP> *__restrict__ part,
-                                                 const int4 *__restrict__ tdesc, const uint8_t *__restrict__ tb, const int32_t *__restrict__ tS0l,
-                                                 const int32_t *__restrict__ tileS, const int32_t *__restrict__ tileS2, DevModel<TC> M,
-                                                 int32_t *__restrict__ opt, int32_t *__restrict__ nnopt, int32_t *__restrict__ nlopt, int64_t n1,
-                                                 const int2 *__restrict__ items, const int32_t *__restrict__ item_of,
-                                                 unsigned long long *__restrict__ trec, uint32_t *__restrict__ tick, int iblocks,
-                                                 const int32_t *__restrict__ ioffs)
-{
-    // ioffs (round_alloc): trip j of task t is item ioffs[t] + j; null: item_of[the trip's first tile], as k_own_map drew it
-    __shared__ Best<TC, HYP> s_part[4];
-    __shared__ int64_t s_w[4], s_w2[4];
-    __shared__ int64_t s_pre[FIX_TRIP], s_pre2[HYP ? FIX_TRIP : 1];      // per tile of the trip: the counts since its wave's first tile
-    // (The lane blocks carry these 16 / 32 KB without using them: static LDS is per kernel.  A dozen lane blocks per round -- the
-    //  allocation limits nothing there.)
-    int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if ((int)blockIdx.x >= iblocks) {
-        // ---- lane blocks
-        const int64_t ntask = rc->nown;
-        const int64_t nlb = (int64_t)gridDim.x - iblocks;
-        for (int64_t t0 = ((int64_t)blockIdx.x - iblocks) * blockDim.x; t0 < ntask; t0 += nlb * blockDim.x) {      // wave-uniform
-            int64_t t = t0 + threadIdx.x;
-            int64_t k0 = 0, k1 = 0;
-            if (t < ntask) { k0 = toffs[t]; k1 = toffs[t + 1]; }
-            int64_t nt = k1 - k0;
-            const unsigned long long e1 = __ballot(nt == 1), e2 = __ballot(nt == FIX_SERIAL), e3 = __ballot(nt == FIX_SERIAL + 1);
-            if (lane == 0) {
-                const int32_t em = (e1 ? 1 : 0) | (e2 ? 2 : 0) | (e3 ? 4 : 0);
-                if (em & ~rc->n_edge) atomicOr(&rc->n_edge, em);
-            }
-            if (nt < 1 || nt > FIX_SERIAL) continue;
-            int4 td = tdesc[t];
-            int64_t run = td.y, run2 = HYP ? (int64_t)tS0l[t] : 0;     // the counts made before tile k
-            Best<TC, HYP> acc; best_clear(acc);
-            for (int64_t k = k0; k < k1; k++) {                        // (the winner does not depend on the order: larger p wins ties)
-                fix_merge<TC, HYP>(acc, part[k], run, run2, M);
-                run += tileS[k];
-                if (HYP) run2 += tileS2[k];
-            }
-            int64_t rw = (int64_t)tb[t] * n1 + prow(((int64_t)td.z), n1 - 1);
-            opt[rw] = acc.p; nnopt[rw] = acc.nn;
-            if (HYP) nlopt[rw] = best_nl(acc);
-        }
-        return;
-    }
-    // ---- item blocks
-    // (In every round the last row of the top rectangle owns a task over its whole block -- tens of thousands of tiles, a dozen
-    //  trips and more: as one block's serial walk that task alone set the length of the launch.)
-    const int64_t nlist = rc->n_items;
-    for (int64_t i = blockIdx.x; i < nlist; i += iblocks) {          // block-uniform: the barriers below are reached by the whole block
-        const int2 it = items[i];
-        const int64_t t = it.x;
-        const int64_t k0 = toffs[t], k1 = toffs[t + 1], kt = k0 + it.y;
-        Best<TC, HYP> acc; best_clear(acc);
-        // the 16-byte partials: lane x takes the tiles x, x + 256, ... of the trip (neighbouring lanes, neighbouring records)
-        Best<TC, HYP> cc[FIX_U];
-#pragma unroll
-        for (int u = 0; u < FIX_U; u++) {
-            const int64_t k = kt + u * 256 + (int64_t)threadIdx.x;
-            best_clear(cc[u]);
-            if (k < k1) cc[u] = part[k];
-        }
-        // the 4-byte counts: lane x takes FIX_U consecutive tiles, scans them with its wave and leaves every tile's exclusive
-        // prefix inside the wave's 64 * FIX_U tiles in LDS
-        int32_t ts[FIX_U], ts2[FIX_U];
-        int64_t sum = 0, sum2 = 0;
-#pragma unroll
-        for (int u = 0; u < FIX_U; u++) {
-            const int64_t k = kt + (int64_t)threadIdx.x * FIX_U + u;
-            ts[u] = 0; ts2[u] = 0;
-            if (k < k1) { ts[u] = tileS[k]; if (HYP) ts2[u] = tileS2[k]; }
-            sum += ts[u]; sum2 += ts2[u];
-        }
-        int64_t inc = sum, inc2 = sum2;
-        for (int o = 1; o < 64; o <<= 1) {
-            int64_t v = shfl_up64(inc, o);
-            if (lane >= o) inc += v;
-            if (HYP) { int64_t v2 = shfl_up64(inc2, o); if (lane >= o) inc2 += v2; }
-        }
-        __syncthreads();                                     // (the previous item's prefixes and partials have been read)
-        {
-            int64_t run = inc - sum, run2 = inc2 - sum2;
-#pragma unroll
-            for (int u = 0; u < FIX_U; u++) {
-                s_pre[threadIdx.x * FIX_U + u] = run; run += ts[u];
-                if (HYP) { s_pre2[threadIdx.x * FIX_U + u] = run2; run2 += ts2[u]; }
-            }
-        }
-        if (lane == 63) { s_w[wv] = inc; if (HYP) s_w2[wv] = inc2; }
-        __syncthreads();
-        int64_t wb[5], wb2[5];                               // counts of the trip before wave w's tiles; [4]: the trip's total
-        wb[0] = 0; wb2[0] = 0;
-#pragma unroll
-        for (int w = 0; w < 4; w++) { wb[w + 1] = wb[w] + s_w[w]; wb2[w + 1] = HYP ? wb2[w] + s_w2[w] : 0; }
-#pragma unroll
-        for (int u = 0; u < FIX_U; u++) {                    // tile u * 256 + x of the trip was scanned by wave (u * 256 + x) / (64 * FIX_U)
-            static_assert((64 * FIX_U) % 256 == 0, "a wave's tiles are whole rows of 256");
-            const int e = u * 256 + (int)threadIdx.x, w = (u * 256) / (64 * FIX_U);
-            fix_merge<TC, HYP>(acc, cc[u], wb[w] + s_pre[e], HYP ? wb2[w] + s_pre2[e] : 0, M);
-        }
-        best_wave_min<TC, HYP>(acc, lane);
-        if (lane == 0) s_part[wv] = acc;
-        __syncthreads();
-        if (wv != 0) continue;                               // (wave-uniform; the other waves go on to the next item's loads)
-        const int64_t ntrip = (k1 - k0 + FIX_TRIP - 1) / FIX_TRIP;
-        const int4 td = tdesc[t];
-        const int64_t anchor = td.y, anchor2 = HYP ? (int64_t)tS0l[t] : 0;
-        Best<TC, HYP> out; best_clear(out);
-        bool write = false;
-        if (lane == 0) {
-            for (int w = 1; w < 4; w++) {
-                Best<TC, HYP> c = s_part[w];
-                bool take = (acc.p < 0) ? (c.p >= 0) : (c.p >= 0 && (c.v < acc.v || (c.v == acc.v && c.p > acc.p)));
-                if (take) acc = c;
-            }
-        }
-        if (ntrip == 1) {                                    // the whole task: the anchor on top, done
-            if (lane == 0) { fix_merge<TC, HYP>(out, acc, anchor, anchor2, M); write = true; }
-        } else {
-            uint32_t got = 0;
-            if (lane == 0) {
-                unsigned long long *r = trec + (size_t)i * FIX_REC_W;
-                __hip_atomic_store(r + 0, fix_bits<TC>(acc.v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(r + 1, (unsigned long long)(uint32_t)acc.p | ((unsigned long long)(uint32_t)acc.nn << 32), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(r + 2, (unsigned long long)wb[4], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (HYP) {
-                    __hip_atomic_store(r + 3, (unsigned long long)(uint32_t)best_nl(acc), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(r + 4, (unsigned long long)wb2[4], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                // The record is released at agent scope BEFORE the ticket is drawn.  The fence alone is the release the memory model asks
-                // for; the explicit wait behind it is there because a release fence's own wait for the stores has been seen to be
-                // dropped by the compiler when a waited load or a used atomic precedes it, and ACQ_REL on the ticket costs nothing more
-                // (one more write-back of an L2 that is clean by then) and makes the last arriver's acquire part of the atomic itself.
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                got = __hip_atomic_fetch_add(&tick[t], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            got = (uint32_t)__shfl((int)got, 0);
-            if ((int64_t)got != ntrip - 1) continue;         // (wave-uniform) somebody else draws the last ticket
-            // ---- the fold, by this wave: lane j takes the trips j, j + 64, ... in order
-            // Only lane 0 drew the ticket, all 64 lanes read records.  What that relies on: the acquire fence is one instruction of the
-            // WAVE (it drops the stale lines of this CU's L1 and of this XCD's L2 for every lane), it is executed after the ticket's
-            // value has come back, and every record word is read by an agent-scope load, which is served from neither of those caches.
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            int64_t base = anchor, base2 = anchor2;
-            for (int64_t j0 = 0; j0 < ntrip; j0 += 64) {
-                const int64_t j = j0 + lane;
-                Best<TC, HYP> c; best_clear(c);
-                int64_t s1 = 0, s2 = 0;
-                if (j < ntrip) {
-                    const unsigned long long *r = trec + (size_t)(ioffs ? ioffs[t] + (int32_t)j : item_of[k0 + j * FIX_TRIP]) * FIX_REC_W;
-                    const unsigned long long w0 = __hip_atomic_load(r + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    const unsigned long long w1 = __hip_atomic_load(r + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    s1 = (int64_t)__hip_atomic_load(r + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    c.v = fix_val<TC>(w0); c.p = (int32_t)(uint32_t)w1; c.nn = (int32_t)(uint32_t)(w1 >> 32);
-                    if (HYP) {
-                        best_set_nl(c, (int32_t)(uint32_t)__hip_atomic_load(r + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-                        s2 = (int64_t)__hip_atomic_load(r + 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                }
-                int64_t inc1 = s1, incb = s2;
-                for (int o = 1; o < 64; o <<= 1) {
-                    int64_t v = shfl_up64(inc1, o);
-                    if (lane >= o) inc1 += v;
-                    if (HYP) { int64_t v2 = shfl_up64(incb, o); if (lane >= o) incb += v2; }
-                }
-                fix_merge<TC, HYP>(out, c, base + inc1 - s1, base2 + incb - s2, M);
-                base += shfl64(inc1, 63);
-                if (HYP) base2 += shfl64(incb, 63);
-            }
-            best_wave_min<TC, HYP>(out, lane);
-            if (lane == 0) {
-                __hip_atomic_store(&tick[t], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (every ticket of the task is drawn: zero again for the next round)
-                atomicAdd(&rc->n_trips, 1);
-                write = true;
-            }
-        }
-        if (write) {
-            int64_t rw = (int64_t)tb[t] * n1 + prow(((int64_t)td.z), n1 - 1);
-            opt[rw] = out.p; nnopt[rw] = out.nn;
-            if (HYP) nlopt[rw] = best_nl(out);
-        }
-    }
-}
-
 // ------------------------------------------------------------------ left part: stream, scan, evaluate, arg-min
 // HYP: hyperedge-cut costs carry a second count (self nets): rows bucketed by their FIRST column (fpos / flast),
 // a column p joining on the left adds the rows with first == p and last < r.
@@ -1800,378 +760,6 @@ __global__ void __launch_bounds__(256) k_fix(const RoundCounts *__restrict__ rc,
     }
 }
 
-// ---- anchors of the mirrored head tasks (windowed layers), once per (pattern, w)
-// hist[e] = #{q : e(q) = e}, e(q) = min(next[q], col[q] + w, n): then  nets(max(0, r - w), r) = pos[r] - #{q : e(q) < r}   (an entry is counted by
-// the window ending before r iff it lies in a column < r, is the LAST occurrence of its row before r, and its column is >= r - w)
-// Without atomics (10^8 scattered atomic adds took 12.5 ms; this takes the time of two column passes): the entries with e = x are
-//   * next[q] = x <= col[q] + w : one per entry q' of COLUMN x whose previous occurrence is within the window, prev[q'] >= max(0, x - w);
-//   * col[q] + w = x < next[q]  : the entries of column x - w that do not come back by column x;
-// one lane per column x < n (hist[n] is never read: E[r] sums the values below r <= n), eight loads in flight.
-__global__ void __launch_bounds__(256) k_win_hist(int64_t n, int64_t w, const int32_t *__restrict__ pos, const int32_t *__restrict__ prev,
-                                                  const int32_t *__restrict__ next, int32_t *__restrict__ hist)
-{
-    const int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (x > n) return;
-    int32_t c = 0;
-    if (x < n) {
-        const int32_t lo = (int32_t)(x > w ? x - w : 0);
-        for (int32_t q = pos[x], q1 = pos[x + 1]; q < q1; q += 8) {
-            int32_t v[8];
-#pragma unroll
-            for (int k = 0; k < 8; k++) v[k] = q + k < q1 ? prev[q + k] : -1;
-#pragma unroll
-            for (int k = 0; k < 8; k++) c += (v[k] >= lo);
-        }
-        if (x >= w) {
-            const int32_t xx = (int32_t)x;
-            for (int32_t q = pos[x - w], q1 = pos[x - w + 1]; q < q1; q += 8) {
-                int32_t v[8];
-#pragma unroll
-                for (int k = 0; k < 8; k++) v[k] = q + k < q1 ? next[q + k] : INT32_MIN;
-#pragma unroll
-                for (int k = 0; k < 8; k++) c += (v[k] > xx);
-            }
-        }
-    }
-    hist[x] = c;
-}
-// the same for whole rows (self nets): rows with first >= r - w and last < r  =  #{last < r} - #{max(last, first + w) < r}
-__global__ void __launch_bounds__(256) k_win_hist_rows(int64_t m, int64_t n, int64_t w, const int32_t *__restrict__ rfirst, const int32_t *__restrict__ rlast,
-                                                       int32_t *__restrict__ hist)
-{
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= m) return;
-    int64_t f = rfirst[i];
-    if (f < 0) return;                                      // empty row
-    int64_t e = f + w, l = rlast[i];
-    if (l > e) e = l;
-    if (e > n) e = n;
-    atomicAdd(&hist[e], 1);
-}
-// one wave per mirrored head (plane b < s, rho = idx << (b+1)): entries of the block's columns passing the test
-//   tot[aoff[b] + idx] = #{q in the columns of the block : next[q] >= rho}   (GE)   /   #{rows starting in the block with last < rho}
-template <bool GE>
-__global__ void __launch_bounds__(256) k_win_block_totals(RoundDesc R, int64_t nitems, const int32_t *__restrict__ cpos, const int32_t *__restrict__ arr,
-                                                          int32_t *__restrict__ tot)
-{
-    const int lane = threadIdx.x & 63;
-    for (int64_t it = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6); it < nitems; it += (int64_t)gridDim.x * 4) {
-        int b = 0;
-        while (it >= R.aoff[b + 1]) b++;
-        const int64_t idx = it - R.aoff[b], rho = idx << (b + 1);
-        int32_t c = 0;
-        int64_t cs, ce;
-        if (idx >= 1 && rho <= R.n && geo_block(R.G, rho, b, cs, ce)) {
-            const int32_t thr = (int32_t)rho;
-            for (int32_t q = cpos[cs] + lane, q1 = cpos[ce]; q < q1; q += 64) { const int32_t v = arr[q]; c += GE ? (v >= thr) : (v < thr); }
-        }
-        for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
-        if (lane == 0) tot[it] = c;
-    }
-}
-// anchor of (b, rho) = count of the whole window [max(0, rho - w), rho) minus the totals of the blocks b' <= b left of the block's end
-__global__ void __launch_bounds__(256) k_win_anchors(RoundDesc R, int64_t nitems, const int64_t *__restrict__ base, const int64_t *__restrict__ E,
-                                                     const int32_t *__restrict__ tot, int32_t *__restrict__ anch)
-{
-    int64_t it = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (it >= nitems) return;
-    int b = 0;
-    while (it >= R.aoff[b + 1]) b++;
-    const int64_t idx = it - R.aoff[b], rho = idx << (b + 1);
-    if (idx < 1 || rho > R.n) { anch[it] = 0; return; }
-    int64_t v = base[rho] - E[rho];
-    for (int bb = 0; bb <= b; bb++) v -= tot[R.aoff[bb] + (rho >> (bb + 1))];
-    anch[it] = (int32_t)v;
-}
-
-// leaf pass: the part [64 g + 62 - w, 64 g) of every group (E from the histogram of width w - 62)
-__global__ void __launch_bounds__(256) k_leaf_anchors(int64_t ng, int64_t n, const int64_t *__restrict__ base, const int64_t *__restrict__ E,
-                                                      int32_t *__restrict__ anch)
-{
-    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= ng) return;
-    const int64_t r = g << 6;
-    anch[g] = r <= n ? (int32_t)(base[r] - E[r]) : 0;
-}
-
-// ------------------------------------------------------------------ round A from cached counts
-// Round A (row r against its lowest block [r - 2^b, r), b = ctz(r)) is the one round whose candidate ranges do not depend on
-// the layer: nets(p, r) for all its (row, candidate) pairs -- sum_r 2^ctz(r) = n log2(n) / 2 values -- is computed ONCE per
-// partition and kept (4 B each); a layer then evaluates round A by streaming counts, W and pos (16 B per candidate instead
-// of the candidate's whole column).  Elements are stored level by level (b), row by row, candidate p = r - 1 - i at index i;
-// every level is padded to whole tiles of LT elements.
-// tiles of level b: [tbase[b], tbase[b+1]); rows of the levels >= 9: [rbase[b], rbase[b+1]).
-// mir_w = 0: the unconstrained scheme's round-A rows -- level b holds the rows r = (2u+1) 2^b, candidates r - 1 - i, i < 2^b.
-// mir_w = w > 0: the MIRRORED heads of the windowed geometry (geo_block) -- level b < s holds the rows r = (u+1) 2^(b+1),
-// candidates ce - 1 - i with ce = r + 2^(b+1) - 1 - w (those below column 0 do not exist); the counts carry the head's anchor
-// nets(ce, r), at aoff[b] + (r >> (b+1)) of the window anchors.  tlo / thi: the tiles of each level a windowed layer needs.
-
-__device__ __forceinline__ int64_t ra_row(const RATab &T, int b, int64_t u)
-{
-    return T.mir_w ? (u + 1) << (b + 1) : ((u << 1) | 1) << b;
-}
-
-__device__ __forceinline__ bool ra_decode(const RATab &T, int64_t tile, int j, int &b, int64_t &r, int64_t &p, int64_t &i)
-{
-    b = 0;
-    while (tile >= T.tbase[b + 1]) b++;                     // (uniform per tile)
-    int64_t e = (tile - T.tbase[b]) * LT + j;               // element inside the level
-    int64_t u = e >> b;
-    i = e & (((int64_t)1 << b) - 1);
-    r = ra_row(T, b, u);
-    p = (T.mir_w ? r + ((int64_t)2 << b) - 1 - T.mir_w : r) - 1 - i;
-    return r <= T.n && p >= 0;
-}
-
-// d[E] = #{q in column p : next[q] >= r} (d2: rows whose first column is p and whose last column is < r)
-__global__ void __launch_bounds__(256) k_ra_colcount(RATab T, const int32_t *__restrict__ pos, const int32_t *__restrict__ next,
-                                                     const int32_t *__restrict__ fpos, const int32_t *__restrict__ flast,
-                                                     int32_t *__restrict__ d, int32_t *__restrict__ d2)
-{
-    int b; int64_t r, p, i;
-    bool ok = ra_decode(T, blockIdx.x, threadIdx.x, b, r, p, i);
-    int64_t E = (int64_t)blockIdx.x * LT + threadIdx.x;
-    int32_t c = 0, c2 = 0;
-    if (ok) {
-        int32_t rr = (int32_t)r;
-        for (int32_t q = pos[p], q1 = pos[p + 1]; q < q1; q += 8) {        // eight loads in flight (one at a time: a memory latency per entry)
-            int32_t v[8];
-#pragma unroll
-            for (int k = 0; k < 8; k++) v[k] = q + k < q1 ? next[q + k] : INT32_MIN;
-#pragma unroll
-            for (int k = 0; k < 8; k++) c += (v[k] >= rr);
-        }
-        if (d2) for (int32_t q = fpos[p], q1 = fpos[p + 1]; q < q1; q++) c2 += (flast[q] < rr);
-    }
-    d[E] = c;
-    if (d2) d2[E] = c2;
-}
-
-// c[E] = sum of d over the row's elements 0 .. i  (G = exclusive prefix sums of d over all elements)
-__global__ void __launch_bounds__(256) k_ra_final(RATab T, const int64_t *__restrict__ G, int32_t *__restrict__ c, const int32_t *__restrict__ anch)
-{
-    int b; int64_t r, p, i;
-    ra_decode(T, blockIdx.x, threadIdx.x, b, r, p, i);
-    int64_t E = (int64_t)blockIdx.x * LT + threadIdx.x;
-    int32_t v = (int32_t)(G[E + 1] - G[E - i]);
-    if (anch && r <= T.n) v += anch[T.aoff[b] + (r >> (b + 1))];            // (mirrored heads: the part [ce, r) the block's columns stand on)
-    c[E] = v;
-}
-
-template <typename TC, bool HYP>
-__device__ __forceinline__ bool ra_takes(const Best<TC, HYP> &x, const Best<TC, HYP> &c)      // c replaces x: smaller value, or equal value and larger p
-{
-    return (x.p < 0) ? (c.p >= 0) : (c.p >= 0 && (c.v < x.v || (c.v == x.v && c.p > x.p)));
-}
-
-// one wave per tile of LT elements; a lane holds four consecutive elements.  Rows of up to LT candidates (b <= 8) lie inside
-// one tile and are finished here; longer rows leave one partial per tile for k_ra_merge.
-template <typename TC, bool HYP>
-__global__ void __launch_bounds__(256) k_ra_layer(RATab T, int64_t ntile, const int32_t *__restrict__ cnt, const int32_t *__restrict__ cnt2,
-                                                  const int32_t *__restrict__ pos, const TC *__restrict__ W, DevModel<TC> M, TC alpha,
-                                                  int32_t *__restrict__ opt, int32_t *__restrict__ nnopt, int32_t *__restrict__ nlopt,
-                                                  Best<TC, HYP> *__restrict__ part)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t tile = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (tile >= ntile) return;
-    const int64_t n1 = T.n + 1;
-    const int64_t E0 = tile * LT + 4 * lane;
-    const int4 c4 = *reinterpret_cast<const int4 *>(cnt + E0);
-    int4 d4 = make_int4(0, 0, 0, 0);
-    if (HYP) d4 = *reinterpret_cast<const int4 *>(cnt2 + E0);
-    // the lane's first element is decoded; from level 2 on the other three are the next candidates of the same row
-    int b = 0;
-    int64_t r0, p0, i0;
-    const bool ok0 = ra_decode(T, tile, 4 * lane, b, r0, p0, i0);
-    if (tile < T.tlo[b] || tile >= T.thi[b]) return;        // (uniform) a windowed layer: rows far from its window
-    Best<TC, HYP> cand[4];
-    int64_t rk[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        int64_t r = r0, p = p0 - k;
-        bool ok = ok0 && p >= 0;                            // (mirrored heads: a block may be cut off at column 0)
-        if (b < 2) { int bb; int64_t ii; ok = ra_decode(T, tile, 4 * lane + k, bb, r, p, ii); }      // (uniform branch)
-        rk[k] = ok ? r : 0;
-        best_clear(cand[k]);
-        if (ok) {
-            int32_t c = k == 0 ? c4.x : k == 1 ? c4.y : k == 2 ? c4.z : c4.w, c2 = k == 0 ? d4.x : k == 1 ? d4.y : k == 2 ? d4.z : d4.w;
-            cand[k].v = cadd(W[p], dm_apply_affine(M, alpha, r - p, (int64_t)(pos[r] - pos[p]), (int64_t)c, (int64_t)c2));
-            cand[k].p = (int32_t)p; cand[k].nn = c; best_set_nl(cand[k], c2);
-        }
-    }
-    if (b < 2) {                                            // rows of one or two candidates: finished inside the lane
-        const int per = 1 << b;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            if ((k & (per - 1)) != 0 || rk[k] == 0) continue;
-            Best<TC, HYP> x = cand[k];
-            if (per == 2 && ra_takes(x, cand[k + 1 < 4 ? k + 1 : 3])) x = cand[k + 1 < 4 ? k + 1 : 3];
-            int64_t rw = (int64_t)b * n1 + prow((rk[k]), n1 - 1);
-            opt[rw] = x.p; nnopt[rw] = x.nn;
-            if (HYP) nlopt[rw] = best_nl(x);
-        }
-        return;
-    }
-    Best<TC, HYP> x = cand[0];
-#pragma unroll
-    for (int k = 1; k < 4; k++) if (ra_takes(x, cand[k])) x = cand[k];
-    const int lpr = b >= 8 ? 64 : (1 << (b - 2));          // lanes per row
-    for (int o = 1; o < lpr; o <<= 1) {                     // butterfly inside the row's lanes: every lane ends with the winner
-        Best<TC, HYP> c; best_clear(c);
-        c.v = shfl64(x.v, lane ^ o); c.p = __shfl(x.p, lane ^ o); c.nn = __shfl(x.nn, lane ^ o);
-        if (HYP) best_set_nl(c, __shfl(best_nl(x), lane ^ o));
-        if (ra_takes(x, c)) x = c;
-    }
-    if ((lane & (lpr - 1)) == 0) {
-        if (b <= 8) {
-            if (rk[0]) {
-                int64_t rw = (int64_t)b * n1 + prow((rk[0]), n1 - 1);
-                opt[rw] = x.p; nnopt[rw] = x.nn;
-                if (HYP) nlopt[rw] = best_nl(x);
-            }
-        } else {
-            part[tile - T.tbase[9]] = x;
-        }
-    }
-}
-
-// The same round, COLUMN-major: one wave per 256 consecutive candidates p, all levels.  A candidate p belongs to the round-A row
-// of every level b whose bit is clear in p (r = p with the bits below b cleared, plus 2^b), a dozen rows on average: k_ra_layer reads
-// its cost W[p] and its column pointer once per row (16 B per (candidate, row)); here they are read once per candidate and
-// only the 4-byte cached count is read per row -- 60 B instead of 190 B per candidate and layer.  Lane l holds the candidates
-// P0 + 4 l .. + 3; the count elements of a row are stored by descending p (ra_decode), so a lane's four are one aligned vector.
-// Rows of up to 256 candidates (b <= 8) lie inside the wave's columns and are finished here (butterfly over the row's lanes);
-// longer rows leave one partial per 256 candidates for k_ra_merge, in the slot k_ra_layer would use.
-template <typename TC, bool HYP, bool MIR>
-__global__ void __launch_bounds__(256) k_ra_cols(RATab T, const int32_t *__restrict__ cnt, const int32_t *__restrict__ cnt2,
-                                                 const int32_t *__restrict__ pos, const TC *__restrict__ W, DevModel<TC> M, TC alpha,
-                                                 int32_t *__restrict__ opt, int32_t *__restrict__ nnopt, int32_t *__restrict__ nlopt,
-                                                 Best<TC, HYP> *__restrict__ part, int64_t tile0, int64_t tile1, int bmin)
-{
-    // levels bmin .. nbits - 1 (the leaf pass computes the levels below LEAF_T itself: their rows are never multiples of 64).
-    // tiles [tile0, tile1) of 256 consecutive values of the coordinate z (a windowed layer needs the rows near its window only).
-    // MIR = false: z = p, the candidate p belongs to the level-b row of the block [r - 2^b, r) iff bit b of z is CLEAR.
-    // MIR = true (table with mir_w = w): z = p + w + 1, p belongs to the mirrored head rho = z with the bits <= b cleared
-    // (block [rho + 2^b - 1 - w, rho + 2^(b+1) - 1 - w)) iff bit b of z is SET.  In both maps a row's 2^b candidates are an aligned
-    // block of z and its elements run by descending z: element i = (2^b - 1) - (z mod 2^b).
-    const int lane = threadIdx.x & 63;
-    const int64_t n = T.n, n1 = n + 1, off = MIR ? T.mir_w + 1 : 0;
-    const int64_t Z0 = (tile0 + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * LT;
-    if (Z0 - off >= n || Z0 >= tile1 * LT) return;          // (wave-uniform) candidates are the columns 0 .. n - 1
-    const int64_t z0 = Z0 + 4 * lane, p0 = z0 - off;
-    TC wv[4]; int32_t pv[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) { int64_t p = p0 + k; p = p < 0 ? 0 : p < n ? p : n; wv[k] = W[p]; pv[k] = pos[p]; }
-    for (int b = bmin; b < T.nbits; b++) {
-        if (b >= 8 && (bool)((Z0 >> b) & 1) != MIR) continue;       // (wave-uniform) no row of this level over the wave's columns
-        // the lane's row of this level and its candidates among z0 .. z0 + 3:
-        //   b = 0: two rows of one candidate each; b = 1: one row of two; b >= 2: all four
-        const int64_t mask = ((int64_t)1 << b) - 1;
-        const bool cov = b < 2 || (bool)((z0 >> b) & 1) == MIR;
-        const int64_t zr = (z0 >> (b + 1)) << (b + 1);              // z0 with the bits <= b cleared
-        const int64_t r = MIR ? zr : zr + ((int64_t)1 << b);        // (b = 0: the first of the lane's two rows)
-        const int64_t u = MIR ? (z0 >> (b + 1)) - 1 : z0 >> (b + 1);
-        // the lane's candidates k0, k0 + 1 (b = 1) or 0 .. 3 (b >= 2); element of the LAST one (the smallest index)
-        const int k0 = (b == 1 && MIR) ? 2 : 0;
-        const int64_t zlast = b == 1 ? z0 + k0 + 1 : z0 + 3;
-        const int64_t E = (T.tbase[b] << 8) + ((u << b) | (mask - (zlast & mask)));
-        int32_t c[4] = {0, 0, 0, 0}, d[4] = {0, 0, 0, 0};
-        if (b == 0) {
-            // single candidates: z0 + k (k = 0, 2; mirrored: 1, 3) -> rows r, r + 2; their elements are neighbours
-            const int kk = MIR ? 1 : 0;
-            const int64_t E0 = (T.tbase[0] << 8) + u;
-#pragma unroll
-            for (int j = 0; j < 2; j++) {
-                const int64_t rk = r + 2 * j, pk = p0 + kk + 2 * j;
-                if (rk >= 1 && rk <= n && pk >= 0 && (!MIR || u + j >= 0)) {
-                    const int64_t rw = prow((rk), n1 - 1);
-                    opt[rw] = (int32_t)pk; nnopt[rw] = cnt[E0 + j]; if (HYP) nlopt[rw] = cnt2[E0 + j];
-                }
-            }
-            continue;
-        }
-        const bool rok = cov && r >= 1 && r <= n && u >= 0;
-        if (rok) {
-            if (b >= 2) {
-                const int4 t = *reinterpret_cast<const int4 *>(cnt + E);
-                c[3] = t.x; c[2] = t.y; c[1] = t.z; c[0] = t.w;
-                if (HYP) { const int4 t2 = *reinterpret_cast<const int4 *>(cnt2 + E); d[3] = t2.x; d[2] = t2.y; d[1] = t2.z; d[0] = t2.w; }
-            } else {
-                const int2 t = *reinterpret_cast<const int2 *>(cnt + E);
-                c[k0 + 1] = t.x; c[k0] = t.y;
-                if (HYP) { const int2 t2 = *reinterpret_cast<const int2 *>(cnt2 + E); d[k0 + 1] = t2.x; d[k0] = t2.y; }
-            }
-        }
-        const int32_t posr = pos[rok ? r : 0];
-        Best<TC, HYP> x; best_clear(x);
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            if (b == 1 && (k < k0 || k > k0 + 1)) continue;
-            if (!rok || p0 + k < 0) continue;               // (mirrored heads: a block may be cut off at column 0)
-            Best<TC, HYP> cc; best_clear(cc);
-            cc.v = cadd(wv[k], dm_apply_affine(M, alpha, r - (p0 + k), (int64_t)(posr - pv[k]), (int64_t)c[k], (int64_t)d[k]));
-            cc.p = (int32_t)(p0 + k); cc.nn = c[k]; best_set_nl(cc, d[k]);
-            if (ra_takes(x, cc)) x = cc;
-        }
-        const int lpr = b <= 2 ? 1 : b >= 8 ? 64 : (1 << (b - 2));          // lanes per row
-        for (int o = 1; o < lpr; o <<= 1) {                 // butterfly inside the row's lanes: every lane ends with the winner
-            Best<TC, HYP> cc; best_clear(cc);
-            cc.v = shfl64(x.v, lane ^ o); cc.p = __shfl(x.p, lane ^ o); cc.nn = __shfl(x.nn, lane ^ o);
-            if (HYP) best_set_nl(cc, __shfl(best_nl(x), lane ^ o));
-            if (ra_takes(x, cc)) x = cc;
-        }
-        if ((lane & (lpr - 1)) == 0 && rok) {
-            if (b <= 8) {
-                if (x.p >= 0) {
-                    const int64_t rw = (int64_t)b * n1 + prow((r), n1 - 1);
-                    opt[rw] = x.p; nnopt[rw] = x.nn;
-                    if (HYP) nlopt[rw] = best_nl(x);
-                }
-            } else {
-                // lane 0: the wave's smallest element of the row is that of its last column
-                const int64_t el = (u << b) | (mask - ((Z0 + LT - 1) & mask));
-                part[T.tbase[b] + (el >> 8) - T.tbase[9]] = x;
-            }
-        }
-    }
-}
-
-// rows of more than LT candidates (b >= 9): one wave per row merges the row's tile partials
-template <typename TC, bool HYP>
-__global__ void __launch_bounds__(256) k_ra_merge(RATab T, int64_t nrow, const Best<TC, HYP> *__restrict__ part,
-                                                  int32_t *__restrict__ opt, int32_t *__restrict__ nnopt, int32_t *__restrict__ nlopt)
-{
-    const int lane = threadIdx.x & 63;
-    const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (w >= nrow) return;
-    int b = 9;
-    while (w >= T.rbase[b + 1]) b++;
-    const int64_t u = w - T.rbase[b], r = ra_row(T, b, u), n1 = T.n + 1;
-    const int64_t t0 = T.tbase[b] + (u << (b - 8)) - T.tbase[9], cntt = (int64_t)1 << (b - 8);
-    Best<TC, HYP> x; best_clear(x);
-    // (the top row's block is half the matrix -- 2^15 partials at n = 10^7: eight loads per lane in flight; one at a time, that row
-    //  alone made the kernel 160 us long)
-    for (int64_t kb = lane; kb < cntt; kb += 512) {
-        Best<TC, HYP> cc[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) { best_clear(cc[u]); if (kb + 64 * u < cntt) cc[u] = part[t0 + kb + 64 * u]; }
-#pragma unroll
-        for (int u = 0; u < 8; u++) if (kb + 64 * u < cntt && ra_takes(x, cc[u])) x = cc[u];
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        Best<TC, HYP> c; best_clear(c);
-        c.v = shfl64(x.v, lane ^ o); c.p = __shfl(x.p, lane ^ o); c.nn = __shfl(x.nn, lane ^ o);
-        if (HYP) best_set_nl(c, __shfl(best_nl(x), lane ^ o));
-        if (ra_takes(x, c)) x = c;
-    }
-    if (lane == 0 && r <= T.n) {
-        int64_t rw = (int64_t)b * n1 + prow((r), n1 - 1);
-        opt[rw] = x.p; nnopt[rw] = x.nn;
-        if (HYP) nlopt[rw] = best_nl(x);
-    }
-}
-
 // ------------------------------------------------------------------ end of a round's counting phase
 // The verdict on a round's scan totals, by one thread: derives the tile count and checks the totals against the capacities of
 // the buffers the host sized from its prediction (the previous layer); on overflow -- or a flag set earlier in the round -- the
@@ -2348,317 +936,6 @@ void dp_list_alloc_test(const int32_t *a, int64_t na, const int32_t *b, int64_t 
     res[8] = (int64_t)(h.alloc_l | h.alloc_o); res[9] = round_alloc_fits(fit_ntask, fit_n, fit_own_min) ? 1 : 0;
 }
 
-// ------------------------------------------------------------------ host side of the own-tile merge (k_fix_own)
-// the grid, from what the host knows: the round's tiles (predicted or exact) and tasks.  Both roles walk their device-side
-// counts with grid strides, so a count beyond the estimate costs time only.
-struct FixGrid { int iblocks, lblocks; };
-static FixGrid fix_grid(int64_t nt, int64_t ntask)
-{
-    nt = std::max<int64_t>(nt, 0); ntask = std::max<int64_t>(ntask, 0);
-    const int64_t items = nt / FIX_TRIP + std::min<int64_t>(ntask, nt / (FIX_SERIAL + 1)) + 1;
-    FixGrid g;
-    g.iblocks = (int)std::min<int64_t>(items, 2048);
-    g.lblocks = (int)std::min<int64_t>(std::max<int64_t>(cdiv(ntask, (int64_t)256), 1), 4096);
-    return g;
-}
-template <typename TC, bool HYP>
-static void launch_fix_own(hipStream_t s, RoundCounts *rc, const int64_t *toffs, const Best<TC, HYP> *part, const int4 *tdesc, const uint8_t *tb,
-                           const int32_t *tS0l, const int32_t *tileS, const int32_t *tileS2, const DevModel<TC> &M, int32_t *opt, int32_t *nnopt,
-                           int32_t *nlopt, int64_t n, const int2 *items, const int32_t *item_of, unsigned long long *trec, uint32_t *tick,
-                           int64_t nt, int64_t ntask, const int32_t *ioffs)
-{
-    const FixGrid g = fix_grid(nt, ntask);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fix_own<TC, HYP>), dim3((unsigned)(g.iblocks + g.lblocks)), dim3(256), 0, s, rc, toffs, part, tdesc, tb, tS0l, tileS,
-                       tileS2, M, opt, nnopt, nlopt, n + 1, items, item_of, trec, tick, g.iblocks, ioffs);
-    CP_HIP(hipGetLastError());
-}
-
-// Test entry (cp_test_fix_merge): k_own_map (tiles counted from the task heads: it lists the items) and the merge launch on host
-// arrays, `reps` times on one workspace (the tickets must come back to zero).  Task t has the tiles toffs[t] .. toffs[t + 1),
-// partial records {part_v (the value's 8 bytes), part_p (< 0: an empty tile), part_nn, part_nl}, tile counts tile_s / tile_s2,
-// anchors anchor / anchor2 and writes its winner to the cell of (plane[t], row[t]) of planes over the rows 0 .. n.
-// res: {items listed, tasks folded from more than one trip, the edge bits, tickets left nonzero} of the last launch.
-template <typename TC, bool HYP>
-static void fix_merge_test_run(const cp_model_t *model, int64_t ntask, const int64_t *toffs, const int64_t *part_v, const int32_t *part_p, const int32_t *part_nn,
-                               const int32_t *part_nl, const int32_t *tile_s, const int32_t *tile_s2, const int32_t *anchor, const int32_t *anchor2,
-                               const int32_t *row, const int32_t *plane, int64_t n, int reps, int32_t *p_out, int32_t *nn_out, int32_t *nl_out, int64_t *res)
-{
-    hipStream_t s = nullptr;
-    const int64_t NT = toffs[ntask], n1 = n + 1;
-    int np = 1;
-    for (int64_t t = 0; t < ntask; t++) np = std::max(np, plane[t] + 1);
-    std::vector<Best<TC, HYP>> hpart((size_t)NT);
-    for (int64_t k = 0; k < NT; k++) {
-        Best<TC, HYP> b;
-        memset(&b, 0, sizeof(b));
-        memcpy(&b.v, part_v + k, sizeof(TC)); b.p = part_p[k]; b.nn = part_nn[k];
-        if constexpr (HYP) b.nl = part_nl[k];
-        hpart[(size_t)k] = b;
-    }
-    std::vector<int4> htd((size_t)ntask);
-    std::vector<uint8_t> htb((size_t)ntask);
-    std::vector<int32_t> hrlen((size_t)ntask);
-    for (int64_t t = 0; t < ntask; t++) {
-        htd[(size_t)t] = make_int4(0, anchor[t], row[t], 0); htb[(size_t)t] = (uint8_t)plane[t];
-        hrlen[(size_t)t] = (int32_t)std::min<int64_t>((toffs[t + 1] - toffs[t]) * LT, INT32_MAX);
-    }
-    HostModel<TC> HM;
-    build_dev_model<TC>(model, HM, s);
-    const size_t c = (size_t)NT, icap = fix_items_cap(c), pl = (size_t)np * (size_t)n1;
-    DBuf<int64_t> dtoffs((size_t)ntask + 1);
-    DBuf<Best<TC, HYP>> dpart(c);
-    DBuf<int4> dtd((size_t)ntask), drec(c);
-    DBuf<uint8_t> dtb((size_t)ntask);
-    DBuf<int32_t> drlen((size_t)ntask), dS0l((size_t)ntask), dS(c), dS2(c), dtask(c), ditem_of(c), dopt(pl), dnn(pl), dnl(pl);
-    DBuf<int2> ditems(icap);
-    DBuf<unsigned long long> dtrec(icap * FIX_REC_W);
-    DBuf<uint32_t> dtick((size_t)ntask);
-    DBuf<RoundCounts> drc(1);
-    auto up = [&](void *d, const void *h, size_t bytes) { CP_HIP(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s)); };
-    up(dtoffs.p, toffs, dtoffs.bytes()); up(dpart.p, hpart.data(), dpart.bytes()); up(dtd.p, htd.data(), dtd.bytes()); up(dtb.p, htb.data(), dtb.bytes());
-    up(drlen.p, hrlen.data(), drlen.bytes()); up(dS.p, tile_s, dS.bytes());
-    if (HYP) { up(dS0l.p, anchor2, dS0l.bytes()); up(dS2.p, tile_s2, dS2.bytes()); }
-    CP_HIP(hipMemsetAsync(dtick.p, 0, dtick.bytes(), s));
-    // round_alloc: the items' bases as set-up reserves them (here: in task order) and their number; 0: k_own_map draws them
-    std::vector<int32_t> hioffs((size_t)ntask);
-    int32_t n_items0 = 0;
-    for (int64_t t = 0; t < ntask; t++) {
-        hioffs[(size_t)t] = n_items0;
-        n_items0 += fix_items_of(toffs[t + 1] - toffs[t]);
-    }
-    DBuf<int32_t> dioffs((size_t)ntask);
-    up(dioffs.p, hioffs.data(), dioffs.bytes());
-    const int32_t *ioffs = g_opt_round_alloc ? dioffs.p : nullptr;
-    RoundCounts h;
-    for (int r = 0; r < reps; r++) {
-        memset(&h, 0, sizeof(h));
-        h.nown = (int32_t)ntask; h.NT = NT; h.n_items = ioffs ? n_items0 : 0;
-        up(drc.p, &h, sizeof(h));
-        // (whatever a launch does not write shows: no column, and records / items of the launch before are gone)
-        CP_HIP(hipMemsetAsync(dopt.p, 0xFF, dopt.bytes(), s)); CP_HIP(hipMemsetAsync(dnn.p, 0xFF, dnn.bytes(), s)); CP_HIP(hipMemsetAsync(dnl.p, 0xFF, dnl.bytes(), s));
-        CP_HIP(hipMemsetAsync(ditems.p, 0x7F, ditems.bytes(), s)); CP_HIP(hipMemsetAsync(ditem_of.p, 0x7F, ditem_of.bytes(), s));
-        CP_HIP(hipMemsetAsync(dtrec.p, 0x7F, dtrec.bytes(), s));
-        hipLaunchKernelGGL(k_own_map, dim3((unsigned)std::min<int64_t>(cdiv(NT, (int64_t)256), 8192)), dim3(256), 0, s, drc.p, dtoffs.p, dtd.p, drlen.p, drec.p,
-                           dtask.p, dtb.p, (int32_t *)nullptr, 0, n, 0, (int32_t *)nullptr, (int32_t *)nullptr, ditems.p, ditem_of.p, 0, ioffs);
-        launch_fix_own<TC, HYP>(s, drc.p, dtoffs.p, dpart.p, dtd.p, dtb.p, HYP ? dS0l.p : nullptr, dS.p, HYP ? dS2.p : nullptr, HM.d, dopt.p, dnn.p, HYP ? dnl.p : nullptr, n,
-                                ditems.p, ditem_of.p, dtrec.p, dtick.p, NT, ntask, ioffs);
-        CP_HIP(hipMemcpyAsync(&h, drc.p, sizeof(h), hipMemcpyDeviceToHost, s));
-        CP_HIP(hipStreamSynchronize(s));               // (h is reused)
-        g_fix_items += h.n_items;
-    }
-    std::vector<int32_t> hopt(pl), hnn(pl), hnl(HYP ? pl : 0);
-    std::vector<uint32_t> htick((size_t)ntask);
-    CP_HIP(hipMemcpyAsync(hopt.data(), dopt.p, dopt.bytes(), hipMemcpyDeviceToHost, s));
-    CP_HIP(hipMemcpyAsync(hnn.data(), dnn.p, dnn.bytes(), hipMemcpyDeviceToHost, s));
-    if (HYP) CP_HIP(hipMemcpyAsync(hnl.data(), dnl.p, dnl.bytes(), hipMemcpyDeviceToHost, s));
-    CP_HIP(hipMemcpyAsync(htick.data(), dtick.p, dtick.bytes(), hipMemcpyDeviceToHost, s));
-    CP_HIP(hipStreamSynchronize(s));
-    int64_t left = 0;
-    for (int64_t t = 0; t < ntask; t++) {
-        const int64_t r = row[t];
-        const int lv = __builtin_ctzll((unsigned long long)r);                  // prow on the host
-        const size_t cell = (size_t)plane[t] * (size_t)n1 + (size_t)((n - (n >> lv)) + (r >> (lv + 1)));
-        p_out[t] = hopt[cell]; nn_out[t] = hnn[cell];
-        if (HYP) nl_out[t] = hnl[cell];
-        left += htick[(size_t)t] != 0;
-    }
-    res[0] = h.n_items; res[1] = h.n_trips; res[2] = h.n_edge; res[3] = left;
-}
-
-void dp_fix_merge_test(const cp_model_t *model, int64_t ntask, const int64_t *toffs, const int64_t *part_v, const int32_t *part_p, const int32_t *part_nn,
-                       const int32_t *part_nl, const int32_t *tile_s, const int32_t *tile_s2, const int32_t *anchor, const int32_t *anchor2, const int32_t *row,
-                       const int32_t *plane, int64_t n, int reps, int32_t *p_out, int32_t *nn_out, int32_t *nl_out, int64_t *res)
-{
-    const bool hyp = model->kind == CP_MODEL_HYPEREDGE_CUT;
-    CP_REQUIRE(model->kind == CP_MODEL_WORK || model->kind == CP_MODEL_CONNECTIVITY || hyp, CP_EINVAL, "fix merge test: not a model of the O(n log^2 n) scheme");
-    CP_REQUIRE(!hyp || (part_nl && tile_s2 && anchor2 && nl_out), CP_EINVAL, "fix merge test: a hyperedge model needs the second counts");
-    CP_REQUIRE(ntask >= 1 && ntask < ((int64_t)1 << 24) && n >= 1 && n < ((int64_t)1 << 26) && reps >= 1 && reps <= 16, CP_EINVAL, "fix merge test: bad sizes");
-    CP_REQUIRE(toffs[0] == 0, CP_EINVAL, "fix merge test: toffs must start at 0");
-    for (int64_t t = 0; t < ntask; t++) {
-        CP_REQUIRE(toffs[t + 1] > toffs[t] && toffs[t + 1] < ((int64_t)1 << 26), CP_EINVAL, "fix merge test: every task needs a tile, 2^26 tiles at most");
-        CP_REQUIRE(row[t] >= 1 && row[t] <= n && plane[t] >= 0 && plane[t] < 4, CP_EINVAL, "fix merge test: rows are 1 .. n, planes 0 .. 3");
-    }
-    with_cost_type(model->dtype, [&](auto tag) {
-        using TC = decltype(tag);
-        if (hyp) fix_merge_test_run<TC, true>(model, ntask, toffs, part_v, part_p, part_nn, part_nl, tile_s, tile_s2, anchor, anchor2, row, plane, n, reps, p_out, nn_out, nl_out, res);
-        else fix_merge_test_run<TC, false>(model, ntask, toffs, part_v, part_p, part_nn, part_nl, tile_s, tile_s2, anchor, anchor2, row, plane, n, reps, p_out, nn_out, nl_out, res);
-    });
-}
-
-// ------------------------------------------------------------------ the link entries split by plane (own_split; SplitLinks: dp_total.hpp)
-__device__ __forceinline__ int split_plane(int32_t p, int32_t x) { return 31 - __clz((int)(p ^ x)); }       // (-1 for x == p)
-
-// one lane per column: cnt[b][p] = the column's entries with h == SPLIT_BMIN + b (column n: none)
-__global__ void __launch_bounds__(256) k_split_count(const int32_t *__restrict__ pos, const int32_t *__restrict__ next, int64_t n, int nb,
-                                                     int32_t *__restrict__ cnt)
-{
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p > n) return;
-    int32_t c[SPLIT_NB];
-#pragma unroll
-    for (int b = 0; b < SPLIT_NB; b++) c[b] = 0;
-    if (p < n)
-        for (int32_t q = pos[p], qe = pos[p + 1]; q < qe; q++) {
-            const int h = split_plane((int32_t)p, next[q]) - SPLIT_BMIN;
-#pragma unroll
-            for (int b = 0; b < SPLIT_NB; b++) c[b] += (h == b);
-        }
-#pragma unroll
-    for (int b = 0; b < SPLIT_NB; b++) if (b < nb) cnt[(int64_t)b * (n + 1) + p] = c[b];
-}
-
-// one lane per column, one block per 256-column block: the column's variable entries to their planes, in entry order, and the packed
-// words (SplitLinks) -- with  vsa[b][p] = sum over b' > b of (vpos[b'][p] - vpos[b'][0])  the column's two in-block offsets, from the
-// bases thread 0 (the block's first column) leaves in LDS and in vbase; they go where the counts were.  Both offsets grow with p, so a
-// block's last column holds its largest ones: it alone raises vmax (and reads it first: few blocks get as far as the atomic).
-__global__ void __launch_bounds__(256) k_split_scatter(const int32_t *__restrict__ pos, const int32_t *__restrict__ next, int64_t n, int nb,
-                                                       const int32_t *__restrict__ vpos, int32_t *__restrict__ vnext, int32_t *__restrict__ vpk,
-                                                       int2 *__restrict__ vbase, int64_t nblk, int32_t *__restrict__ vmax)
-{
-    __shared__ int32_t s_bp[SPLIT_NB], s_bs[SPLIT_NB];
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const bool live = p <= n;
-    int32_t c[SPLIT_NB];
-#pragma unroll
-    for (int b = 0; b < SPLIT_NB; b++) c[b] = (b < nb && live) ? vpos[(int64_t)b * (n + 1) + p] : 0;
-    if (threadIdx.x == 0) {                          // (p <= n: the grid has no block without a column)
-        int32_t above = 0;
-#pragma unroll
-        for (int b = SPLIT_NB - 1; b >= 0; b--)
-            if (b < nb) {
-                s_bp[b] = c[b]; s_bs[b] = above;
-                vbase[(int64_t)b * (nblk + 1) + blockIdx.x] = make_int2(c[b], above);
-                if ((int64_t)blockIdx.x == nblk - 1) vbase[(int64_t)b * (nblk + 1) + nblk] = make_int2(vpos[(int64_t)(b + 1) * (n + 1)], 0);
-                above += c[b] - vpos[(int64_t)b * (n + 1)];
-            }
-    }
-    __syncthreads();
-    if (live) {
-        int32_t above = 0, mp = 0, ms = 0;
-#pragma unroll
-        for (int b = SPLIT_NB - 1; b >= 0; b--)
-            if (b < nb) {
-                const int32_t op = c[b] - s_bp[b], os = above - s_bs[b];
-                vpk[(int64_t)b * (n + 1) + p] = (int32_t)(((uint32_t)op & 0xffffu) | ((uint32_t)os << 16));
-                mp = op > mp ? op : mp; ms = os > ms ? os : ms;
-                above += c[b] - vpos[(int64_t)b * (n + 1)];
-            }
-        if (threadIdx.x == 255 || p == n) {
-            if (mp > vmax[0]) atomicMax(&vmax[0], mp);
-            if (ms > vmax[1]) atomicMax(&vmax[1], ms);
-        }
-    }
-    if (p < n)
-        for (int32_t q = pos[p], qe = pos[p + 1]; q < qe; q++) {
-            const int32_t x = next[q];
-            const int h = split_plane((int32_t)p, x) - SPLIT_BMIN;
-            int32_t dst = -1;
-#pragma unroll
-            for (int b = 0; b < SPLIT_NB; b++) if (h == b) { dst = c[b]; c[b]++; }
-            if (dst >= 0) vnext[dst] = x;
-        }
-}
-
-// one lane per column: the wide vsa from vpos (split_wide)
-__global__ void __launch_bounds__(256) k_split_vsa(int64_t n, int nb, const int32_t *__restrict__ vpos, int32_t *__restrict__ vsa)
-{
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p > n) return;
-    int32_t above = 0;
-    for (int b = nb - 1; b >= 0; b--) {
-        vsa[(int64_t)b * (n + 1) + p] = above;
-        above += vpos[(int64_t)b * (n + 1) + p] - vpos[(int64_t)b * (n + 1)];
-    }
-}
-
-static void split_build(cp_csr_s *A, SplitLinks &S, DBuf<int64_t> &scratch)
-{
-    hipStream_t s = A->stream;
-    const int64_t n = A->n, n1 = n + 1;
-    int nbits = 1;
-    while (((int64_t)1 << nbits) <= n) nbits++;
-    S.nb = std::max(0, nbits - SPLIT_BMIN); S.stride = n1; S.nblk = cdiv(n1, 256);
-    S.packed = false; S.has_wide = false; S.max_off[0] = S.max_off[1] = 0;
-    for (auto &t : S.tot) t = 0;
-    if (S.nb > 0) {
-        CP_REQUIRE(S.nb <= SPLIT_NB, CP_EINVAL, "n exceeds the bit-plane budget");
-        const size_t cells = (size_t)S.nb * (size_t)n1;
-        S.vpos.ensure(cells + 1); S.vpk.ensure(cells + 1); S.vnext.ensure((size_t)A->N + 8);
-        S.vbase.ensure((size_t)S.nb * (size_t)(S.nblk + 1)); S.vmax.ensure(2);
-        const unsigned grid = (unsigned)S.nblk;
-        CP_HIP(hipMemsetAsync(S.vmax.p, 0, 2 * sizeof(int32_t), s));
-        // (the counts live in vpk until the scatter writes it)
-        hipLaunchKernelGGL(k_split_count, dim3(grid), dim3(256), 0, s, A->pos32.p, A->next.p, n, S.nb, S.vpk.p);
-        exclusive_scan_i32_i32(S.vpk.p, S.vpos.p, (int64_t)cells, scratch, s);
-        hipLaunchKernelGGL(k_split_scatter, dim3(grid), dim3(256), 0, s, A->pos32.p, A->next.p, n, S.nb, S.vpos.p, S.vnext.p, S.vpk.p, S.vbase.p, S.nblk,
-                           S.vmax.p);
-        CP_HIP(hipGetLastError());
-        int32_t st[SPLIT_NB + 1];                       // the planes' starts and the total: the entries a round's planes stream
-        for (int b = 0; b <= S.nb; b++)
-            CP_HIP(hipMemcpyAsync(&st[b], S.vpos.p + (size_t)b * (size_t)n1, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        CP_HIP(hipMemcpyAsync(S.max_off, S.vmax.p, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        CP_HIP(hipStreamSynchronize(s));
-        for (int b = 0; b < S.nb; b++) S.tot[b] = (int64_t)st[b + 1] - st[b];
-        S.tot[S.nb] = st[S.nb];
-        S.packed = S.max_off[0] <= 0xffff && S.max_off[1] <= 0xffff;
-    }
-    S.built = true;
-}
-
-// the wide vsa, for whoever does not take the packed words: an offset that does not fit, own_blk 0, own_pack 0, cp_test_own_split
-static void split_wide(cp_csr_s *A, SplitLinks &S)
-{
-    if (S.has_wide) return;
-    if (S.nb > 0) {
-        S.vsa.ensure((size_t)S.nb * (size_t)S.stride + 1);
-        hipLaunchKernelGGL(k_split_vsa, dim3((unsigned)S.nblk), dim3(256), 0, A->stream, A->n, S.nb, S.vpos.p, S.vsa.p);
-        CP_HIP(hipGetLastError());
-    }
-    S.has_wide = true;
-}
-
-// Test entry (cp_test_own_pair): what own_pair_slots gives wave `wave` among nt tiles -- the function the kernel calls
-void dp_own_pair_test(int64_t nt, int64_t wave, int64_t *res)
-{
-    int64_t s0 = 0, s1 = 0;
-    res[0] = own_pair_slots(wave, nt, s0, s1) ? 1 : 0;
-    res[1] = s0;
-    res[2] = s1;
-}
-
-// Test entry (cp_test_own_split): the three arrays of the pattern on the host.  vpos_out / vsa_out: nb (n + 1) words, vnext_out: room
-// for the N entries; res: {nb, entries in vnext}.
-void dp_own_split_test(cp_csr_s *A, int32_t *vpos_out, int32_t *vsa_out, int32_t *vnext_out, int64_t *res)
-{
-    ensure_links(A);
-    SplitLinks S;
-    DBuf<int64_t> scratch;
-    split_build(A, S, scratch);
-    split_wide(A, S);
-    res[0] = S.nb; res[1] = S.tot[S.nb];
-    if (S.nb <= 0) return;
-    const size_t cells = (size_t)S.nb * (size_t)S.stride;
-    CP_HIP(hipMemcpyAsync(vpos_out, S.vpos.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, A->stream));
-    CP_HIP(hipMemcpyAsync(vsa_out, S.vsa.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, A->stream));
-    if (res[1] > 0) CP_HIP(hipMemcpyAsync(vnext_out, S.vnext.p, (size_t)res[1] * sizeof(int32_t), hipMemcpyDeviceToHost, A->stream));
-    CP_HIP(hipStreamSynchronize(A->stream));
-}
-
-// Test entry (cp_test_own_pack): the packed words and the block bases of the pattern on the host.  vpk_out: nb (n + 1) words;
-// vbase_out: nb (blocks + 1) pairs {start, prefix sum}; res: {nb, blocks per plane, packed, largest start offset, largest prefix offset}.
-void dp_own_pack_test(cp_csr_s *A, int32_t *vpk_out, int32_t *vbase_out, int64_t *res)
-{
-    ensure_links(A);
-    SplitLinks S;
-    DBuf<int64_t> scratch;
-    split_build(A, S, scratch);
-    res[0] = S.nb; res[1] = S.nblk; res[2] = S.packed ? 1 : 0; res[3] = S.max_off[0]; res[4] = S.max_off[1];
-    if (S.nb <= 0) return;
-    CP_HIP(hipMemcpyAsync(vpk_out, S.vpk.p, (size_t)S.nb * (size_t)S.stride * sizeof(int32_t), hipMemcpyDeviceToHost, A->stream));
-    CP_HIP(hipMemcpyAsync(vbase_out, S.vbase.p, (size_t)S.nb * (size_t)(S.nblk + 1) * sizeof(int2), hipMemcpyDeviceToHost, A->stream));
-    CP_HIP(hipStreamSynchronize(A->stream));
-}
-
 // ------------------------------------------------------------------ host driver for one layer
 // number of rows r <= x of the form (base << (b+1)) | (1 << b) | ((2v+1) << tau): the rows with ctz == tau whose bit b is set
 static int64_t count_rows(int b, int tau, int64_t x)
@@ -2676,8 +953,7 @@ static int64_t count_rows(int b, int tau, int64_t x)
 // Rows computed by a run restricted to the row tile [rlo, rhi]: every row r with
 //     r - 2^ctz(r) <= rhi  and  r + 2^ctz(r) >= rlo
 // -- the tile plus the O(log n) tree ancestors its rows take their candidate bounds from (closed under ancestors).
-static void make_round(RoundDesc &R, bool isA, int tau, int nbits, int64_t n, int64_t rlo, int64_t rhi, const Geo &G = Geo{0, 0, 0},
-                       const int64_t *aoff = nullptr)
+void make_round(RoundDesc &R, bool isA, int tau, int nbits, int64_t n, int64_t rlo, int64_t rhi, const Geo &G, const int64_t *aoff)      // (defaults: dp_total.hpp)
 {
     memset(&R, 0, sizeof(R));
     R.isA = isA; R.tau = tau; R.nbits = nbits; R.n = n; R.G = G;
@@ -2748,212 +1024,7 @@ static void make_round(RoundDesc &R, bool isA, int tau, int nbits, int64_t n, in
     R.ntask = acc;
 }
 
-// Builds a cached round-A table: the counts of `levels` levels of rows_of(b) rows each (they depend on the pattern only -- once per
-// partition; the table of the mirrored heads of the windowed geometry, mir_w > 0, also on the window width: once per (pattern, w),
-// after win_build, whose anchors `anch` / `anch2` its counts carry).  Fills the cache's table, counts (c2: second count) and
-// sizes; `part` gets room for the partials of the rows of more than LT candidates.
-template <typename TC, typename Rows>
-static void ra_build(cp_csr_s *A, LayerWork<TC> &Wk, RaCache<TC> &Ra, int levels, Rows rows_of, int64_t mir_w, const int32_t *anch, const int32_t *anch2)
-{
-    hipStream_t s = A->stream;
-    const bool hyp = Wk.hyp;
-    RATab &T = Ra.tab;
-    memset(&T, 0, sizeof(T));
-    T.nbits = levels; T.n = A->n; T.mir_w = mir_w;
-    for (int b = 0; b < 33; b++) { T.tlo[b] = 0; T.thi[b] = INT64_MAX; T.aoff[b] = (mir_w && b < 32) ? Wk.win.aoff[b] : 0; }
-    int64_t tb = 0, rb = 0;
-    for (int b = 0; b < 33; b++) {
-        T.tbase[b] = tb; T.rbase[b] = rb;
-        if (b >= levels) continue;
-        const int64_t nrows = rows_of(b);
-        tb += cdiv(nrows << b, LT);
-        if (b >= 9) rb += nrows;
-    }
-    Ra.ntile = tb; Ra.nrow = rb;
-    const size_t total = (size_t)tb * LT;
-    Ra.c.ensure(total + 8);
-    if (hyp) Ra.c2.ensure(total + 8);
-    Ra.part.ensure((size_t)std::max<int64_t>(1, tb - T.tbase[9]));
-    if (tb > 0) {
-        DBuf<int64_t> &G = Wk.sc.ra_G, &scratch = Wk.sc.scratch;        // (kept with the layer scratch: 8 B per element)
-        G.ensure(total + 1);
-        hipLaunchKernelGGL(k_ra_colcount, dim3((unsigned)tb), dim3(LT), 0, s, T, A->pos32.p, A->next.p, hyp ? A->fpos32.p : (const int32_t *)nullptr,
-                           hyp ? A->flast.p : (const int32_t *)nullptr, Ra.c.p, hyp ? Ra.c2.p : (int32_t *)nullptr);
-        exclusive_scan_i32(Ra.c.p, G.p, (int64_t)total, scratch, s);
-        hipLaunchKernelGGL(k_ra_final, dim3((unsigned)tb), dim3(LT), 0, s, T, G.p, Ra.c.p, anch);
-        if (hyp) {
-            exclusive_scan_i32(Ra.c2.p, G.p, (int64_t)total, scratch, s);
-            hipLaunchKernelGGL(k_ra_final, dim3((unsigned)tb), dim3(LT), 0, s, T, G.p, Ra.c2.p, anch2);
-        }
-        CP_HIP(hipGetLastError());
-    }
-    Ra.built = true; Ra.w = mir_w;
-}
-// the table of the unconstrained scheme's round A (the windowed layers' standard heads are its levels below s)
-template <typename TC>
-static void ra_build_std(cp_csr_s *A, LayerWork<TC> &Wk)
-{
-    const int64_t n = A->n;
-    ra_build<TC>(A, Wk, Wk.ra, Wk.nbits, [n](int b) { return ((n >> b) + 1) >> 1; }, 0, nullptr, nullptr);
-}
-// ... and of the mirrored heads of the current window: rows (u + 1) 2^(b+1) <= n
-template <typename TC>
-static void ra_build_mir(cp_csr_s *A, LayerWork<TC> &Wk)
-{
-    const int64_t n = A->n;
-    ra_build<TC>(A, Wk, Wk.mir, Wk.G.s, [n](int b) { return n >> (b + 1); }, Wk.G.w, Wk.win.w_anch.p, Wk.win.w_anch2.p);
-}
-
-// the nets (pass 0) / self nets (pass 1) a window of width x cuts, per column into w_hist and as prefix sums into w_E
-template <typename TC>
-static void win_hist_scan(cp_csr_s *A, LayerWork<TC> &Wk, int64_t x, int pass)
-{
-    hipStream_t s = A->stream;
-    const int64_t n = A->n;
-    if (pass == 1 || A->N == 0) CP_HIP(hipMemsetAsync(Wk.win.w_hist.p, 0, sizeof(int32_t) * (size_t)(n + 1), s));
-    if (pass == 0) { if (A->N > 0) hipLaunchKernelGGL(k_win_hist, dim3((unsigned)cdiv(n + 1, 256)), dim3(256), 0, s, n, x, A->pos32.p, A->prev.p, A->next.p, Wk.win.w_hist.p); }
-    else if (A->m > 0) hipLaunchKernelGGL(k_win_hist_rows, dim3((unsigned)cdiv(A->m, 256)), dim3(256), 0, s, A->m, n, x, A->rfirst.p, A->rlast.p, Wk.win.w_hist.p);
-    exclusive_scan_i32(Wk.win.w_hist.p, Wk.win.w_E.p, n + 1, Wk.sc.scratch, s);
-}
-
-// anchors of the mirrored head tasks of the windowed layers (k_win_*): once per (pattern, w)
-template <typename TC>
-static void win_build(cp_csr_s *A, LayerWork<TC> &Wk)
-{
-    hipStream_t s = A->stream;
-    const int64_t n = A->n, w = Wk.G.w;
-    const int sb = Wk.G.s;
-    int64_t acc = 0;
-    for (int b = 0; b < 33; b++) { Wk.win.aoff[b] = acc; if (b < sb) acc += (n >> (b + 1)) + 1; }      // heads of plane b: rho = idx << (b+1), idx <= n >> (b+1)
-    Wk.win.nitems = acc;
-    const size_t ni = (size_t)(acc > 0 ? acc : 1);
-    Wk.win.w_anch.ensure(ni); Wk.win.w_tot.ensure(ni); Wk.win.w_hist.ensure((size_t)n + 2); Wk.win.w_E.ensure((size_t)n + 2);
-    if (Wk.hyp) Wk.win.w_anch2.ensure(ni);
-    Wk.win.built = false;
-    if (acc > 0) {
-        RoundDesc R;
-        make_round(R, true, 0, sb + 1, n, 0, n, Wk.G, Wk.win.aoff);
-        const unsigned wg = (unsigned)std::min<int64_t>(cdiv(acc, 4), 65536);
-        for (int pass = 0; pass < (Wk.hyp ? 2 : 1); pass++) {
-            win_hist_scan<TC>(A, Wk, w, pass);
-            if (pass == 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_win_block_totals<true>), dim3(wg), dim3(256), 0, s, R, acc, A->pos32.p, A->next.p, Wk.win.w_tot.p);
-            else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_win_block_totals<false>), dim3(wg), dim3(256), 0, s, R, acc, A->fpos32.p, A->flast.p, Wk.win.w_tot.p);
-            hipLaunchKernelGGL(k_win_anchors, dim3((unsigned)cdiv(acc, 256)), dim3(256), 0, s, R, acc, pass == 0 ? A->pos.p : A->lpos.p, Wk.win.w_E.p, Wk.win.w_tot.p,
-                               pass == 0 ? Wk.win.w_anch.p : Wk.win.w_anch2.p);
-        }
-        CP_HIP(hipGetLastError());
-    }
-    // leaf pass (dp_total_leaf.hip): anchors of the inner mirrored blocks, nets(64 g + 62 - w, 64 g) for every group g -- the same
-    // histogram with the width w - 62
-    Wk.win.leaf_anch.release(); Wk.win.leaf_anch2.release();
-    if (sb >= LEAF_T && w > 62) {
-        const int64_t ng = (n >> LEAF_T) + 1;
-        Wk.win.leaf_anch.alloc((size_t)ng);
-        if (Wk.hyp) Wk.win.leaf_anch2.alloc((size_t)ng);
-        for (int pass = 0; pass < (Wk.hyp ? 2 : 1); pass++) {
-            win_hist_scan<TC>(A, Wk, w - 62, pass);
-            hipLaunchKernelGGL(k_leaf_anchors, dim3((unsigned)cdiv(ng, 256)), dim3(256), 0, s, ng, n, pass == 0 ? A->pos.p : A->lpos.p, Wk.win.w_E.p,
-                               pass == 0 ? Wk.win.leaf_anch.p : Wk.win.leaf_anch2.p);
-        }
-        CP_HIP(hipGetLastError());
-    }
-    Wk.win.built = true; Wk.win.w = w;
-}
-
 constexpr int64_t LB_MAX = 1 << 20;      // largest scan (elements) done in a single launch
-
-// Round A from a cache with the table T (the cache's own, or a copy cut to the levels and tiles a windowed layer needs): the
-// column-major kernel over the candidate tiles [tile0, tile1) (`mirrored`: the table of the mirrored heads) or the row-major one
-// over the cache's tiles, then the rows of more than LT candidates (nrow_merge of them) merge their partials.
-template <typename TC, bool HYP>
-static void launch_round_a(const LayerCtx<TC> &C, LayerWork<TC> &Wk, const RaCache<TC> &Ra, const RATab &T, int64_t nrow_merge, int64_t tile0, int64_t tile1,
-                           int bmin, bool mirrored, bool colmajor)
-{
-    hipStream_t s = C.s;
-    cp_csr_s *A = C.A;
-    int32_t *nl = if_hyp<HYP>(Wk.pl.nlopt.p);
-    if (colmajor)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(mirrored ? k_ra_cols<TC, HYP, true> : k_ra_cols<TC, HYP, false>), dim3((unsigned)std::max<int64_t>(1, cdiv(tile1 - tile0, 4))), dim3(256), 0, s,
-                           T, Ra.c.p, if_hyp<HYP>(Ra.c2.p), A->pos32.p, C.W, C.M, C.alpha, Wk.pl.opt.p, Wk.pl.nnopt.p, nl, recs<HYP>(Ra.part), tile0, tile1, bmin);
-    else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ra_layer<TC, HYP>), dim3((unsigned)cdiv(Ra.ntile, 4)), dim3(256), 0, s, T, Ra.ntile, Ra.c.p, if_hyp<HYP>(Ra.c2.p), A->pos32.p, C.W, C.M,
-                           C.alpha, Wk.pl.opt.p, Wk.pl.nnopt.p, nl, recs<HYP>(Ra.part));
-    if (nrow_merge > 0)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ra_merge<TC, HYP>), dim3((unsigned)cdiv(nrow_merge, 4)), dim3(256), 0, s, T, nrow_merge, recs<HYP>(Ra.part), Wk.pl.opt.p,
-                           Wk.pl.nnopt.p, nl);
-    CP_HIP(hipGetLastError());
-}
-
-// A full layer: round A of the rows' lowest blocks from the cached counts; what is left of round A for the generic round is the
-// last row in its upper planes
-template <typename TC, bool HYP>
-static void round_a_full(const LayerCtx<TC> &C, LayerWork<TC> &Wk)
-{
-    hipStream_t s = C.s;
-    if (!Wk.ra.built) { ProfScope ps(PROF_LINKS, s, 0.0); ra_build_std<TC>(C.A, Wk); }
-    ProfScope ps(PROF_RA, s, 16.0 * (double)Wk.ra.ntile * LT);
-    launch_round_a<TC, HYP>(C, Wk, Wk.ra, Wk.ra.tab, Wk.ra.nrow, 0, cdiv(C.n, LT), C.ra_bmin, false, !(g_opt_dbg & DBG_RA_ROWMAJOR));
-}
-
-// Windowed layer: the STANDARD heads of round A (rows with ctz == b < s, block [r - 2^b, r)) are the unconstrained scheme's
-// round-A rows of the levels below s -- same blocks, same layer-independent counts: k_ra_cols computes them for all rows
-// from the cache (60 B per candidate) and the generic round keeps the mirrored and common heads only.  The heads the layer
-// reads are those make_round lists -- within 2^(b+1) of the row tile in plane b <= s: their blocks start at rlo - 3 * 2^s or later.
-// `scope`: the stage's profile scope, opened here behind the table build and closed by the caller (the mirrored heads have always
-// been enqueued inside it).
-template <typename TC, bool HYP>
-static void round_a_win_std(const LayerCtx<TC> &C, LayerWork<TC> &Wk, std::optional<ProfScope> &scope)
-{
-    hipStream_t s = C.s;
-    const Geo &G = C.G;
-    const int64_t n = C.n, rlo = C.rlo, rhi = C.rhi;
-    if (!Wk.ra.built) { ProfScope ps(PROF_LINKS, s, 0.0); ra_build_std<TC>(C.A, Wk); }
-    RATab T2 = Wk.ra.tab;
-    T2.nbits = std::min<int32_t>(G.s, Wk.ra.tab.nbits);
-    const int64_t nrow2 = T2.nbits > 9 ? Wk.ra.tab.rbase[T2.nbits] : 0;
-    const int64_t c_lo = std::max<int64_t>(0, (rlo > 0 ? rlo : 0) - ((int64_t)4 << G.s)), c_hi = std::min<int64_t>(n, rhi);
-    const int64_t tile0 = c_lo / LT, tile1 = cdiv(c_hi, LT);
-    scope.emplace(PROF_RA, s, 60.0 * (double)(tile1 - tile0) * LT);
-    // (the standard heads below LEAF_T are rows inside a leaf group: the leaf pass computes them; the MIRRORED heads of those
-    //  levels include the multiples of 64 -- every row has a task in every plane -- and stay)
-    launch_round_a<TC, HYP>(C, Wk, Wk.ra, T2, nrow2, tile0, tile1, C.ra_bmin, false, true);
-}
-
-// Windowed layer: the MIRRORED heads of round A the same way, from their own table (per level the tiles of the rows near the
-// window); false: the table is empty, the heads stay generic tasks
-template <typename TC, bool HYP>
-static bool round_a_win_mir(const LayerCtx<TC> &C, LayerWork<TC> &Wk)
-{
-    hipStream_t s = C.s;
-    const Geo &G = C.G;
-    const int64_t n = C.n, rlo = C.rlo, rhi = C.rhi;
-    if (!Wk.mir.built || Wk.mir.w != G.w) { ProfScope ps2(PROF_LINKS, s, 0.0); ra_build_mir<TC>(C.A, Wk); }
-    if (Wk.mir.ntile <= 0) return false;
-    RATab T3 = Wk.mir.tab;
-    const int64_t r_lo = std::max<int64_t>(1, (rlo > 0 ? rlo : 0) - ((int64_t)4 << G.s)), r_hi = std::min<int64_t>(n, rhi);
-    double elems = 0;
-    for (int b = 0; b < T3.nbits; b++) {
-        const int64_t u_lo = std::max<int64_t>(0, (r_lo >> (b + 1)) - 1), u_hi = r_hi >> (b + 1);        // rows u_lo .. u_hi - 1
-        T3.tlo[b] = T3.tbase[b] + ((u_lo << b) / LT);
-        T3.thi[b] = std::min<int64_t>(T3.tbase[b + 1], T3.tbase[b] + cdiv(std::max<int64_t>(u_hi, 0) << b, LT));
-        elems += (double)std::max<int64_t>(0, T3.thi[b] - T3.tlo[b]) * LT;
-    }
-    // column-major like the standard heads (z = p + w + 1: the blocks of the rows r_lo .. r_hi lie in [r_lo, r_hi + 2^s)); the
-    // row-major kernel reads 16 B per (candidate, level) instead of 4
-    const bool mcols = !(g_opt_dbg & DBG_MIR_ROWMAJOR);
-    const int64_t zt0 = r_lo / LT, zt1 = cdiv(std::min<int64_t>(n + G.w + 1, r_hi + ((int64_t)1 << G.s) + 1), LT);
-    ProfScope ps2(PROF_RA, s, mcols ? 80.0 * (double)(zt1 - zt0) * LT : 16.0 * elems);
-    launch_round_a<TC, HYP>(C, Wk, Wk.mir, T3, Wk.mir.nrow, zt0, zt1, 0, true, mcols);
-    return true;
-}
-
-// cp_set_option("dbg", DBG_POISON [+ DBG_POISON_ZERO]): fills buffers a stage must write before it reads (null: not of this variant)
-static void poison_fill(hipStream_t s, std::initializer_list<std::pair<void *, size_t>> bufs)
-{
-    if (!(g_opt_dbg & DBG_POISON)) return;
-    const int pat = (g_opt_dbg & DBG_POISON_ZERO) ? 0x00 : 0x7F;
-    for (const auto &b : bufs) if (b.first) CP_HIP(hipMemsetAsync(b.first, pat, b.second, s));
-}
 
 // ------------------------------------------------------------------ the stages of a round, each as the host function run_layer calls
 // A stage function takes the layer's context, the work object, the round and its counts.
@@ -3012,71 +1083,6 @@ static void round_scans(const LayerCtx<TC> &C, LayerWork<TC> &Wk, const RoundDes
         if (C.own_tiles) exclusive_scan_i32_devn(Wk.ow.o_ntl.p, Wk.ow.o_toffs.p, &rc->nown, nm, &rc->NT, Wk.sc.scratch, s);
         hipLaunchKernelGGL(k_round_finish, dim3(1), dim3(1), 0, s, rc, capT, capNT);
     }
-}
-
-// ------------------------------------------------------------------ host side: the own-tile chain of a round
-// Map and stream + evaluate.  split (run_layer): 0: whole columns; 1: every tile of the launch is of a plane >= SPLIT_BMIN, their
-// number is NT; 2: the launch also holds tiles of the planes below -- the gap round tau = 6 with its plane-7 tiles, and every
-// round below it with gap_tau < 6 -- and k_own_map counts: 1 600 same-address atomics per launch cost it 17 us at config 3.
-// (windowed layers keep one tile per wave: their tiles stream whole columns, ten trips and more, and paired they ran 5 % slower)
-template <bool HYP> static bool own_pairs(bool gap, bool win) { return !HYP && !gap && !win && g_opt_own_pair != 0; }
-
-// cp_set_option("own_pack", 0 | 1): the split tiles of a launch take the packed words where the geometry keeps a tile inside one block
-// (own_blk 1) and the pattern's offsets fit 16 bits -- except in a paired launch that also holds tiles of the planes below (gap_tau
-// below 6): a wave's two tiles run one text.  Returns whether they did.
-template <typename TC, bool HYP>
-static bool own_stream(const LayerCtx<TC> &C, LayerWork<TC> &Wk, const RoundDesc &R, RoundCounts *rc, const RoundCounts &P, bool gap, int split, bool ralloc)
-{
-    hipStream_t s = C.s;
-    cp_csr_s *A = C.A;
-    const int64_t n = C.n;
-    const int oblk = C.oblk;
-    const int64_t gNT = C.spec ? (int64_t)Wk.ow.o_rec.n : P.NT;      // (capacity >= the true NT, checked)
-    poison_fill(s, {{Wk.ow.o_part.p, Wk.ow.o_part.bytes()}, {Wk.ow.o_tileS.p, Wk.ow.o_tileS.bytes()}, {Wk.ow.o_rec.p, Wk.ow.o_rec.bytes()}, {Wk.ow.o_srec.p, Wk.ow.o_srec.bytes()},
-                    {if_hyp<HYP>(Wk.ow.o_tileS2.p), Wk.ow.o_tileS2.bytes()}, {Wk.ow.o_items.p, Wk.ow.o_items.bytes()}, {Wk.ow.o_item_of.p, Wk.ow.o_item_of.bytes()},
-                    {Wk.ow.o_trec.p, Wk.ow.o_trec.bytes()}});
-    const unsigned mgrid = (unsigned)std::min<int64_t>(cdiv(gNT, 256), 8192);
-    if (split && !Wk.ow.split.built) {             // once per pattern, by the first round that streams them
-        ProfScope ps(PROF_LINKS, s, 8.0 * (double)A->N + 16.0 * (double)(C.nbits - SPLIT_BMIN) * (double)(n + 1));
-        split_build(A, Wk.ow.split, Wk.sc.scratch);
-    }
-    if (split) g_own_pack_wide = Wk.ow.split.packed ? 0 : 1;      // (of the pattern the last split launch ran on)
-    const bool pair = own_pairs<HYP>(gap, C.G.win != 0);
-    const bool pack = split && oblk && g_opt_own_pack && Wk.ow.split.packed && !(pair && split == 2);
-    if (split && !pack) split_wide(A, Wk.ow.split);
-    hipLaunchKernelGGL(k_own_map, dim3(mgrid), dim3(256), 0, s, rc, Wk.ow.o_toffs.p, Wk.ow.o_tdesc.p, Wk.ow.o_rlen.p, Wk.ow.o_rec.p, Wk.ow.o_task.p,
-                       Wk.ow.o_tb.p, gap ? Wk.ow.o_hi.p : (int32_t *)nullptr, R.tau, n, oblk, oblk ? Wk.ow.b_cnt.p : (int32_t *)nullptr, Wk.ow.o_brank.p,
-                       gap ? (int2 *)nullptr : Wk.ow.o_items.p, Wk.ow.o_item_of.p, split, ralloc ? Wk.ow.o_ioffs.p : (const int32_t *)nullptr);
-    ProfScope ps(gap ? PROF_GAPSTREAM : PROF_OWN, s, C.own_bytes(Wk.ow.split, R.tau, pack ? 2 : split != 0, (double)P.own_steps));
-    if (oblk) {                       // the tile ids by column block (counted in k_own_map): ~10^5 tiles, a counting sort
-        exclusive_scan_i32_lb(Wk.ow.b_cnt.p, Wk.ow.b_start.p, Wk.ow.b_n.p, Wk.ow.b_nblk, nullptr, Wk.sc.scanws, s);
-        hipLaunchKernelGGL(k_blk_order, dim3(mgrid), dim3(256), 0, s, rc, Wk.ow.o_rec.p, Wk.ow.o_brank.p, Wk.ow.b_start.p, Wk.ow.o_border.p, Wk.ow.o_srec.p, Wk.ow.b_cnt.p);
-    }
-    // cp_set_option("own_pair", 0 | 1): outside the gap rounds and the hyperedge costs a wave takes two slots of the run order
-    // (the packed instantiations exist for the plain costs only: `pack` is never set for the hyperedge ones)
-    auto kern = gap ? (pack ? k_lpass_own<TC, HYP, true, false, !HYP> : k_lpass_own<TC, HYP, true>)
-              : pair ? (pack ? k_lpass_own<TC, HYP, false, !HYP, !HYP> : k_lpass_own<TC, HYP, false, !HYP>)
-              : (pack ? k_lpass_own<TC, HYP, false, false, !HYP> : k_lpass_own<TC, HYP, false>);
-    hipLaunchKernelGGL(kern,
-                       dim3((unsigned)cdiv(pair ? cdiv(gNT, 2) : gNT, 4)), dim3(256), 0, s, R.isA, rc,
-                       oblk ? Wk.ow.o_border.p : (const int32_t *)nullptr, A->pos32.p, A->next.p, if_hyp<HYP>(A->fpos32.p), if_hyp<HYP>(A->flast.p),
-                       Wk.ow.o_tileS.p, Wk.ow.o_tileS2.p, Wk.ow.o_rec.p, Wk.ow.o_srec.p, C.W, C.M, C.alpha, recs<HYP>(Wk.ow.o_part), R.tau, Wk.ow.o_hi.p, Wk.ow.o_spec.p,
-                       (int)((g_opt_dbg & DBG_GAP_ALL_SPECIAL) != 0), recs<HYP>(Wk.ow.o_sub), Wk.ow.o_spv.p, A->col.p, if_hyp<HYP>(A->ffirst.p),
-                       split ? Wk.ow.split.vnext.p : (const int32_t *)nullptr, pack ? Wk.ow.split.vpk.p : Wk.ow.split.vpos.p,
-                       pack ? reinterpret_cast<const int32_t *>(Wk.ow.split.vbase.p) : Wk.ow.split.vsa.p, (int64_t)(n + 1));
-    return pack;
-}
-
-// The tail of the chain outside the gap rounds: one launch, a lane per task of up to FIX_SERIAL tiles, a block per listed trip
-// of the longer ones
-template <typename TC, bool HYP>
-static void own_merge(const LayerCtx<TC> &C, LayerWork<TC> &Wk, RoundCounts *rc, const RoundCounts &P, bool ralloc)
-{
-    ProfScope ps(PROF_FIX, C.s, 24.0 * (double)P.NT);
-    launch_fix_own<TC, HYP>(C.s, rc, Wk.ow.o_toffs.p, recs<HYP>(Wk.ow.o_part), Wk.ow.o_tdesc.p, Wk.ow.o_tb.p, if_hyp<HYP>(Wk.ow.o_tS0l.p), Wk.ow.o_tileS.p,
-                            if_hyp<HYP>(Wk.ow.o_tileS2.p), C.M, Wk.pl.opt.p, Wk.pl.nnopt.p, if_hyp<HYP>(Wk.pl.nlopt.p), C.n, Wk.ow.o_items.p, Wk.ow.o_item_of.p, Wk.ow.o_trec.p,
-                            Wk.ow.o_tick.p, C.spec ? grow_pred(P.NT) : P.NT, C.spec ? grow_pred(P.nown) : P.nown,
-                            ralloc ? Wk.ow.o_ioffs.p : (const int32_t *)nullptr);
 }
 
 // ------------------------------------------------------------------ host side: the flattened chain of a round (the tasks' number: rc->nlong)

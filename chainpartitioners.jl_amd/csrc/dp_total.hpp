@@ -1,12 +1,13 @@
-// dp_total.hpp -- what the units of the total-cost DP layer share (dp_total.hip, dp_total_rpass.hip, dp_total_gap.hip,
-// dp_total_leaf.hip; nobody else includes it): the constants, the device helpers and kernel-argument records used by kernels of more
-// than one unit, the work object of a handle (LayerWork, in groups by owner), the layer context (LayerCtx) and the stage functions
+// dp_total.hpp -- what the units of the total-cost DP layer share (dp_total.hip, dp_total_own.hip, dp_total_rounda.hip,
+// dp_total_rpass.hip, dp_total_gap.hip, dp_total_leaf.hip; nobody else includes it): the constants, the device helpers and
+// kernel-argument records used by kernels of more than one unit, the work object of a handle (LayerWork, in groups by owner), the layer context (LayerCtx) and the stage functions
 // the units offer the driver.  A device helper used by one unit stays in that unit.  No macros here.  The scheme: see dp_total.hip.
 #pragma once
 #include "csr.hpp"
 #include "model.hpp"
 #include "dp.hpp"
 #include <algorithm>
+#include <optional>
 
 namespace cpk {
 
@@ -141,7 +142,7 @@ __device__ __forceinline__ void decode_task(const RoundDesc &R, int64_t t, int64
     b = bb;
 }
 
-// the record of a candidate: value, column, counts (helpers: below, behind the shuffles; scans: dp_total.hip)
+// the record of a candidate: value, column, counts (helpers: below, behind the shuffles; scans: dp_total_stream.hpp)
 template <typename TC, bool HYP> struct Best;
 template <typename TC> struct Best<TC, false> { TC v; int32_t p; int32_t nn; };                         // 16 bytes
 template <typename TC> struct Best<TC, true> { TC v; int32_t p; int32_t nn; int32_t nl; int32_t _pad; };
@@ -216,7 +217,7 @@ __device__ __forceinline__ void own_tile_geo(int blk, int32_t B, int32_t L, int3
     }
 }
 
-// ------------------------------------------------------------------ a cached round-A table (layout: dp_total.hip, round A from cached counts)
+// ------------------------------------------------------------------ a cached round-A table (layout: dp_total_rounda.hip, round A from cached counts)
 struct RATab { int32_t nbits, _pad; int64_t n; int64_t tbase[33]; int64_t rbase[33]; int64_t mir_w; int64_t aoff[33]; int64_t tlo[33], thi[33]; };
 
 
@@ -444,5 +445,13 @@ template <typename TC, bool HYP> void gap_finish(const LayerCtx<TC> &C, LayerWor
 // dp_total_leaf.hip: the leaf pass and the combine
 template <typename TC, bool HYP> void leaf_pass(const LayerCtx<TC> &C, LayerWork<TC> &Wk);
 template <typename TC, bool HYP> void combine_rows(const LayerCtx<TC> &C, LayerWork<TC> &Wk);
+// dp_total_rounda.hip: the window anchors (instantiated for TC; dp_total_layer builds them) and round A from the cached tables
+// (`scope`: opened by round_a_win_std, closed by run_layer behind round_a_win_mir)
+template <typename TC> void win_build(cp_csr_s *A, LayerWork<TC> &Wk);
+template <typename TC, bool HYP> void round_a_full(const LayerCtx<TC> &C, LayerWork<TC> &Wk);
+template <typename TC, bool HYP> void round_a_win_std(const LayerCtx<TC> &C, LayerWork<TC> &Wk, std::optional<ProfScope> &scope);
+template <typename TC, bool HYP> bool round_a_win_mir(const LayerCtx<TC> &C, LayerWork<TC> &Wk);
+// dp_total.hip: the tasks of a round (win_build lists the mirrored heads with it)
+void make_round(RoundDesc &R, bool isA, int tau, int nbits, int64_t n, int64_t rlo, int64_t rhi, const Geo &G = Geo{0, 0, 0}, const int64_t *aoff = nullptr);
 
 }  // namespace cpk

@@ -1,5 +1,5 @@
 // dp_total_gap.hip -- the GAP PASSES of a round of the total-cost DP layer (scheme: dp_total.hip): behind k_lpass_own<GAP>
-// (dp_total.hip) every row of a task's gap gets its winner in one pass over the gap's tiles (k_gap_finish; tasks of more than
+// (dp_total_own.hip) every row of a task's gap gets its winner in one pass over the gap's tiles (k_gap_finish; tasks of more than
 // GAPSEG tiles: k_gap_seg, k_gap_merge).
 #include "dp_total.hpp"
 

@@ -1,4 +1,4 @@
-"""Executable specification of the paired own-tile stream of csrc/dp_total.hip (cp_set_option("own_pair"), cp_test_own_pair): with
+"""Executable specification of the paired own-tile stream of csrc/dp_total_own.hip (cp_set_option("own_pair"), cp_test_own_pair): with
 the option on, wave w of k_lpass_own takes the slots 2 w and 2 w + 1 of the run order of a round's nt own tiles (own_blk 1: the
 order of k_blk_order; own_blk 0: the tile ids).  A wave whose second slot lies beyond the order takes its first slot again and
 stores one tile: a lone wave.  The gap rounds and the hyperedge costs keep one tile per wave.

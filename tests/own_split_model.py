@@ -1,4 +1,4 @@
-"""Executable specification (numpy) of the link entries split by bit plane, as the own tiles of csrc/dp_total.hip stream them
+"""Executable specification (numpy) of the link entries split by bit plane, as the own tiles of csrc/dp_total_own.hip stream them
 (cp_set_option("own_split"), cp_test_own_split).  0-based columns p = 0 .. n - 1; entry q of column p has next[q] = the next column
 that holds q's row, n when there is none.
 

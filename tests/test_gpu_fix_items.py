@@ -1,4 +1,4 @@
-"""The merge of the own-tile partials of a DP round (csrc/dp_total.hip, k_fix_own): one launch, a lane per task of up to
+"""The merge of the own-tile partials of a DP round (csrc/dp_total_own.hip, k_fix_own): one launch, a lane per task of up to
 FIX_SERIAL tiles, a block per (task, trip of 2 048 tiles) item of the longer ones, the trips of a task folded by whichever block
 finishes last.
 
@@ -17,7 +17,7 @@ from util import cp, suitesparse_shaped
 
 pytestmark = pytest.mark.gpu
 
-FIX_SERIAL = 16          # csrc/dp_total.hip: tasks of up to FIX_SERIAL tiles are merged by one lane
+FIX_SERIAL = 16          # csrc/dp_total.hpp: tasks of up to FIX_SERIAL tiles are merged by one lane
 TRIP = 2048              # ... longer ones in trips of 256 * FIX_U tiles, one block each
 MODELS = [cp.AffineConnectivityModel(1, 10, 1, 100), cp.AffineHyperedgeCutModel(0, 2, 1, 1, 3),
           cp.AffineConnectivityModel(0.0, 0.0, 0.0, 1.0), cp.AffineHyperedgeCutModel(0.0, 1.0, 0.0, -1.0, 2.0)]

@@ -1,5 +1,5 @@
 """Gap tiles of the planes >= 8 that stream only their plane's variable link entries (cp_set_option("gap_split", 1), the default;
-k_lpass_own<GAP> of csrc/dp_total.hip) against the gap tiles that stream whole columns (gap_split 0) and against brute force
+k_lpass_own<GAP> of csrc/dp_total_own.hip) against the gap tiles that stream whole columns (gap_split 0) and against brute force
 (check_layer of tests/test_gpu_blocks.py: the combined row, every per-block winner and the counts stored with it).
 
 Which gap tasks a layer has is modelled here in numpy from brute force's per-block winners (gap_tasks: the rule of k_setup_short),

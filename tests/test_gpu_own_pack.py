@@ -1,6 +1,6 @@
 """Split own tiles that read a column's start and prefix sum as one packed word (cp_set_option("own_pack", 1), the default;
-csrc/dp_total.hip, SplitLinks::vpk / vbase, interior_stream<PK>) against the tiles that read the two wide arrays (own_pack 0) and
-against brute force.
+csrc/dp_total_own.hip, SplitLinks::vpk / vbase, interior_stream<PK> of csrc/dp_total_stream.hpp) against the tiles that read the
+two wide arrays (own_pack 0) and against brute force.
 
   * cp_test_own_pack: the device arrays equal the numpy specification (tests/own_pack_model.py) exactly -- sizes around a block edge,
     around n + 1 = 0 (mod 256) and around the first stored plane, empty columns, a column of several 256-entry blocks, one row;

@@ -1,4 +1,4 @@
-"""Two own tiles per wave (cp_set_option("own_pair", 1), the default; k_lpass_own<PAIR> of csrc/dp_total.hip) against one tile per
+"""Two own tiles per wave (cp_set_option("own_pair", 1), the default; k_lpass_own<PAIR> of csrc/dp_total_own.hip) against one tile per
 wave (own_pair 0) and against brute force.  Wave w takes the slots 2 w and 2 w + 1 of a round's run order (tests/own_pair_model.py;
 the pairing itself is checked without a device in tests/test_own_pair_model.py); the two tiles may belong to different tasks, planes
 and blocks, one may be split (own_split) and the other not, and the wave that ends an odd order runs one tile and stores once.

@@ -1,4 +1,4 @@
-"""Own tiles that stream only their plane's variable link entries (cp_set_option("own_split", 1), the default; csrc/dp_total.hip,
+"""Own tiles that stream only their plane's variable link entries (cp_set_option("own_split", 1), the default; csrc/dp_total_own.hip,
 SplitLinks) against the tiles that stream whole columns (own_split 0) and against brute force.
 
   * cp_test_own_split: the three device arrays equal the numpy specification (tests/own_split_model.py) exactly -- sizes around the

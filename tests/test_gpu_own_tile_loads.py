@@ -1,4 +1,5 @@
-"""The loads of an own tile (k_lpass_own / interior_stream, csrc/dp_total.hip) are unconditional, at indices clamped into the tile:
+"""The loads of an own tile (k_lpass_own, csrc/dp_total_own.hip / interior_stream, csrc/dp_total_stream.hpp) are unconditional,
+at indices clamped into the tile:
 the column pointers of steps beyond the tile's length, the entry quads at and above the end of the run, the end-of-wave reloads of
 the pin positions and of W, and the tile's record read from its sorted slot.  The shapes here are the smallest at which such a load
 can go wrong; every case is compared with brute force (check_layer of tests/test_gpu_blocks.py: the combined row, every per-block

@@ -1,4 +1,4 @@
-"""The per-round kernel chain of the total-cost DP layer (csrc/dp_total.hip) against the path that never uses it.
+"""The per-round kernel chain of the total-cost DP layer (csrc/dp_total.hip, csrc/dp_total_own.hip) against the path that never uses it.
 
 The own-tile path of a round -- one launch for the two task scans and the round's verdict, tile map, block order that hands
 its counters back as zeros, stream, and the two merges that sum a task's tile counts themselves -- is compared with the
@@ -15,9 +15,9 @@ from util import cp, suitesparse_shaped
 pytestmark = pytest.mark.gpu
 
 SCAN_TILE = 2048         # csrc/common.hpp: elements per block of the chained scans
-LT = 256                 # csrc/dp_total.hip: steps per tile
+LT = 256                 # csrc/dp_total.hpp: steps per tile
 
-FIX_SERIAL = 16          # csrc/dp_total.hip: tasks of up to FIX_SERIAL tiles are merged by one lane, longer ones by one block
+FIX_SERIAL = 16          # csrc/dp_total.hpp: tasks of up to FIX_SERIAL tiles are merged by one lane, longer ones by one block
 MODELS = [cp.AffineConnectivityModel(1, 10, 1, 100), cp.AffineHyperedgeCutModel(0, 2, 1, 1, 3),
           cp.AffineConnectivityModel(0.0, 0.0, 0.0, 1.0), cp.AffineHyperedgeCutModel(0.0, 1.0, 0.0, -1.0, 2.0)]
 IDS = ["conn-i64", "hyper-i64", "conn-f64", "hyper-f64"]

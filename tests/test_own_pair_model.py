@@ -1,5 +1,5 @@
 """The slots a wave of the paired own-tile stream takes (tests/own_pair_model.py) against the function the kernel calls
-(own_pair_slots of csrc/dp_total.hip, through the host-only test entry cp_test_own_pair).  No device is needed."""
+(own_pair_slots of csrc/dp_total_own.hip, through the host-only test entry cp_test_own_pair).  No device is needed."""
 import ctypes as C
 
 import numpy as np

@@ -6,8 +6,10 @@ with the Makefile's flags; a `.s` file is read as it is).  Four numbers per kern
   inloop  full waits between a label and a backward branch to it: paid once per trip
 A full wait after a GROUP of loads is one round trip for the group; `tight` counts the loads that are their own group.  The tool
 counts loads and waits, nothing else.
-usage: python tools/load_waits.py chainpartitioners.jl_amd/csrc/dp_total.hip [name-substring ...]   (one unit per call, the one that
-       names the kernel: dp_total_rpass.hip for k_rpass_*, dp_total_gap.hip for k_gap_*, dp_total_leaf.hip for k_leaf)"""
+usage: python tools/load_waits.py chainpartitioners.jl_amd/csrc/dp_total_own.hip [name-substring ...]   (one unit per call, the one that
+       names the kernel: dp_total_own.hip for k_lpass_own / k_fix_own / k_own_map, dp_total.hip for k_setup_short and the flattened
+       stage's k_lpass, dp_total_rounda.hip for k_ra_* / k_win_*, dp_total_rpass.hip for k_rpass_*, dp_total_gap.hip for k_gap_*,
+       dp_total_leaf.hip for k_leaf)"""
 import re
 import subprocess
 import sys
