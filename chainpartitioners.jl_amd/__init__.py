@@ -23,6 +23,6 @@ from .models import (PowerWorkModel, ConvexWorkModel, ConcaveWorkModel,   # noqa
                      MagneticPartitioner, GreedyBottleneckPartitioner)
 from . import _lib  # noqa: F401
 from . import draws  # noqa: F401
-from .api import (adjointpattern, permute_stripe, permute_plaid, permute, partition_plaid, pack_plaid, partition_stripe, partition_stripe_batch, pack_stripe, pack_stripe_batch, pack_stripe_tables, oracle_stripe, bound_stripe, total_value,   # noqa: F401
+from .api import (adjointpattern, permute_stripe, permute_plaid, permute, quotientpattern, partition_plaid, pack_plaid, partition_stripe, partition_stripe_batch, pack_stripe, pack_stripe_batch, pack_stripe_tables, oracle_stripe, bound_stripe, total_value,   # noqa: F401
                   bottleneck_value, netcount, selfnetcount, dominancecount, dianetcount, selfpincount, rowenvelope, EnvelopeMatrix, set_default_backend,
                   get_backend, CPError, Step, Same, Next, Prev, Jump)

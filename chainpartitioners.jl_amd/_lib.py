@@ -68,6 +68,7 @@ SIGNATURES = {
     "cp_csr_reset_cache": (_i32, [_vp]),
     "cp_rcm": (_i32, [_vp, _vp, _i32, _i32, _I64("rowprm_out"), _I64("colprm_out"), _I64("stats_out")]),
     "cp_csr_permute": (_i32, [_vp, _I64("rowprm"), _I64("colprm"), _pvp]),
+    "cp_csr_quotient": (_i32, [_vp, _ROWPART, _pvp]),
     "cp_count_build": (_i32, [_vp, _i32, _i32, _pvp]),
     "cp_count_query": (_i32, [_vp, _i64, _I64("a"), _I64("b"), _I64("out")]),
     "cp_count_destroy": (_i32, [_vp]),
@@ -291,6 +292,12 @@ class HipBackend:
         if (rowprm is not None and rowprm.shape != (A.m,)) or (colprm is not None and colprm.shape != (A.n,)):
             raise ValueError("permute: a permutation must have one entry per row / column")
         rc = self.lib.cp_csr_permute(self._h(A), rowprm, colprm, C.byref(t))
+        return rc, (self._adopt(t) if rc == 0 else None)
+
+    def csr_quotient(self, A, rp):
+        """the quotient pattern of A under the marshalled row split rp, on the device -> (rc, matrix that keeps its device handle | None)"""
+        t = C.c_void_p()
+        rc = self.lib.cp_csr_quotient(self._h(A), rp, C.byref(t))
         return rc, (self._adopt(t) if rc == 0 else None)
 
     def reset_cache(self, A_or_handle):

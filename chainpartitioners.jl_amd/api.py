@@ -595,6 +595,19 @@ def permute(A: SparseMatrixCSC, sigma=None, tau=None, *, backend=None) -> Sparse
     return B
 
 
+def quotientpattern(A: SparseMatrixCSC, Pi, *, backend=None) -> SparseMatrixCSC:
+    """A with the rows of every part of the SplitPartition Pi merged (cp_csr_quotient): Pi.K x n, entry (k, c) where part k has a nonzero
+    in column c -- the pattern BlockComponentCostModel is a weighted net count on.  Empty parts give empty rows.  The returned matrix
+    keeps its device handle, like adjointpattern's."""
+    b = get_backend(backend)
+    if not hasattr(b, "csr_quotient"):
+        raise NotImplementedError(f"quotientpattern is implemented by the HIP backend only, not by backend '{getattr(b, 'name', type(b).__name__)}'")
+    rp, keep = _rowpart(Pi)
+    rc, Q = b.csr_quotient(A, rp)
+    _check(rc, "quotientpattern", b)
+    return Q
+
+
 def _permuted_stripe(A, method, backend):
     tau = permute_stripe(A, method.prm, backend=backend)
     return tau, permute(A, None, tau, backend=backend)

@@ -6,6 +6,7 @@
 #include "sym.hpp"
 #include "cut.hpp"
 #include "envelope.hpp"
+#include "blockcost.hpp"
 #include <cmath>
 #include <memory>
 
@@ -149,7 +150,9 @@ static int32_t oracle_eval_into(cp_csr_t A, const cp_model_t *model, const cp_ro
 // bn_sym_layers: DP layers the valley search ran for the monotonized symmetric model.  cut_scan_layers: DP layers of the plaid edge-cut
 // models the prefix-min scan ran (plaid_cut.hip).  env_valley_layers: DP layers the valley search ran for the envelope model
 // (envelope.hip).  env_dc_layers: layers >= 2 of its total objective the divide and conquer ran (envelope_total.hip).  budget_layers:
-// layers >= 2 of the total-cost DP under a work budget that dp_total_budget.hip ran.  kept:cp_set_option("poison", 1) starts a
+// layers >= 2 of the total-cost DP under a work budget that dp_total_budget.hip ran.  blockcost_scan_packs: chunker calls that ran the
+// window table over the quotient pattern and the (min,+) scan for a block model; blockcost_wave_evals: oracle queries of a block model
+// that k_block_eval answered (blockcost.hip).  kept:cp_set_option("poison", 1) starts a
 // poison pass by zeroing the other counters and leaves this one.
 static const struct { const char *name; int64_t *var; bool kept; } g_stats[] = {
     {"spec_redo", &g_spec_redo, false}, {"poison_hits", &g_poison_hits, false}, {"fix_trips", &g_fix_trips, false},
@@ -161,6 +164,7 @@ static const struct { const char *name; int64_t *var; bool kept; } g_stats[] = {
     {"cr_consume_rounds", &g_cr_consume_rounds, false}, {"cr_clear_launches", &g_cr_clear_launches, false},
     {"round_alloc_rounds", &g_round_alloc_rounds, false}, {"env_valley_layers", &g_env_valley_layers, false},
     {"env_dc_layers", &g_env_dc_layers, false}, {"budget_layers", &g_budget_layers, false},
+    {"blockcost_scan_packs", &g_blockcost_scan_packs, false}, {"blockcost_wave_evals", &g_blockcost_wave_evals, false},
 };
 static void stats_reset(bool all) { for (const auto &c : g_stats) if (all || !c.kept) *c.var = 0; }
 
@@ -184,6 +188,7 @@ static const struct Opt { const char *name; int64_t *var; OptRule rule; int64_t 
     {"gap_split", &g_opt_gap_split, OPT_BOOL, 0, 0},            // (1, default: so do the gap rounds' tiles of those planes -- while own_split is 1; 0: they stream the whole columns)
     {"lws", &g_opt_lws, OPT_BOOL, 0, 0},                        // (1, default: DynamicTotalChunker past the scan by chunk_lws.hip; 0: the one-wave kernel)
     {"budget_total", &g_opt_budget_total, OPT_BOOL, 0, 0},      // (1, default: total-cost DP under a pin / work budget by dp_total_budget.hip; 0: the one-wave kernel)
+    {"blockcost_par", &g_opt_blockcost_par, OPT_BOOL, 0, 0},    // (1, default: BlockComponentCostModel by the quotient-pattern table + scan and the wave-per-query evaluation of blockcost.hip, inside blockcost_exact; 0: the one-wave step oracle)
     {"budget_scan_cells", &g_opt_budget_scan_cells, OPT_CLAMP, 1, NOLIM_HI},      // (that path: a full rectangle of at most this many cells ...
     {"budget_scan_cols", &g_opt_budget_scan_cols, OPT_CLAMP, 1, NOLIM_HI},        //  ... and columns is scanned whole; default 2^20 / 1024)
     {"budget_stair_cols", &g_opt_budget_stair_cols, OPT_CLAMP, 1, NOLIM_HI},      // (the partial rows of a block below this many columns are scanned whole; default 1024)
@@ -543,8 +548,10 @@ int32_t cp_oracle_eval(cp_csr_t A, const cp_model_t *model, const cp_rowpart_t *
             using TC = decltype(tag);
             TC *out = pick<TC>(out_i64, out_f64);
             if (model->kind == CP_MODEL_PRIMARY || model->kind == CP_MODEL_SECONDARY) return run_plaid_eval<TC>(A, model, Pi, nq, j, jp, k, out);
-            // stateful step oracle: evaluated in query order by one wave (seq.hip)
-            if (model->kind == CP_MODEL_BLOCK) return run_seq_eval<TC>(A, model, Pi, nq, j, jp, k, out);
+            // the block model: one wave per query over the quotient pattern (blockcost.hip) where that route applies, else the
+            // stateful step oracle, evaluated in query order by one wave (seq.hip)
+            if (model->kind == CP_MODEL_BLOCK)
+                return run_block_eval<TC>(A, model, Pi, nq, j, jp, out) ? CP_OK : run_seq_eval<TC>(A, model, Pi, nq, j, jp, k, out);
             if (model_is_cut(model->kind)) return run_cut_eval<TC>(A, model, Pi, nq, j, jp, k, out);
             if (model_is_sym(model->kind)) return run_sym_eval<TC>(A, model, nq, j, jp, k, out);
             if (model_is_env(model->kind)) return run_env_eval<TC>(A, model, nq, j, jp, k, out);      // (Pi accepted and ignored: Costs.jl:5-7)

@@ -16,6 +16,7 @@
 #include "wavelet.hpp"
 #include "dp.hpp"
 #include "envelope.hpp"
+#include "blockcost.hpp"
 #include <type_traits>
 #include <memory>
 
@@ -853,8 +854,9 @@ struct SeqCtx {
     DBuf<TC> Delta, dvec, brtab[CP_MAX_R], ftab;
 };
 
+// block_state false: a block model's caller reads its costs from the table of blockcost.hip, the step oracle's state stays unbuilt
 template <typename TC>
-static void seq_oracle(cp_csr_s *A, const cp_model_t *mdl, const cp_rowpart_t *Pi, SeqCtx<TC> &C)
+static void seq_oracle(cp_csr_s *A, const cp_model_t *mdl, const cp_rowpart_t *Pi, SeqCtx<TC> &C, bool block_state = true)
 {
     hipStream_t s = A->stream;
     build_dev_model<TC>(mdl, C.HM, s);
@@ -866,7 +868,7 @@ static void seq_oracle(cp_csr_s *A, const cp_model_t *mdl, const cp_rowpart_t *P
     if (mdl->kind == CP_MODEL_HYPEREDGE_CUT) {
         ensure_selfnet_counter(A, C.self); C.O.has_self = 1; C.O.self = C.self.d; C.O.lpos = A->lpos.p;
     }
-    if (mdl->kind == CP_MODEL_BLOCK) {
+    if (mdl->kind == CP_MODEL_BLOCK && block_state) {
         CP_REQUIRE(Pi && Pi->spl && Pi->K >= 1, CP_EINVAL, "BlockComponentCostModel needs a SplitPartition of the rows");
         CP_REQUIRE(Pi->spl[0] == 1 && Pi->spl[Pi->K] == A->m + 1, CP_EINVAL, "row partition does not cover 1:m");
         int64_t K = Pi->K, m = A->m;
@@ -962,7 +964,10 @@ struct SeqRun {
     DBuf<int32_t> st;             // the kernel's status word ...
     int32_t rc = 0;               // ... and its host copy, valid after finish()
 
-    SeqRun(cp_csr_s *A, const cp_model_t *mdl, const cp_rowpart_t *Pi) : s(A->stream), n(A->n), C(new SeqCtx<TC>()) { seq_oracle<TC>(A, mdl, Pi, *C); }
+    SeqRun(cp_csr_s *A, const cp_model_t *mdl, const cp_rowpart_t *Pi, bool block_state = true) : s(A->stream), n(A->n), C(new SeqCtx<TC>())
+    {
+        seq_oracle<TC>(A, mdl, Pi, *C, block_state);
+    }
     void begin() { st.alloc(1); CP_HIP(hipMemsetAsync(st.p, 0, sizeof(int32_t), s)); }
     void launched() { CP_HIP(hipGetLastError()); CP_HIP(hipMemcpyAsync(&rc, st.p, sizeof(int32_t), hipMemcpyDeviceToHost, s)); }
     template <typename... P, typename... Q>
@@ -999,10 +1004,17 @@ template <typename TC>
 int32_t run_pack_dynamic(cp_csr_s *A, const cp_model_t *mdl, const cp_rowpart_t *Pi, const cp_model_t *w, int64_t wi, double wf,
                          int64_t *spl_out, int64_t *K_out, int64_t *spl_tab = nullptr, TC *cst_tab = nullptr)
 {
-    SeqRun<TC> R(A, mdl, Pi);
+    // a block model under a width of at most 16 columns, inside its gate: the window table over the quotient pattern (blockcost.hip),
+    // then the scan below; bq stays null for everything else
+    std::unique_ptr<BlockQ> bq;
+    if (mdl->kind == CP_MODEL_BLOCK && w && w->kind == CP_MODEL_VERTEX_COUNT && wi >= 1 && wi <= 16 && A->n >= 1 && block_table_fits(A->n, wi) &&
+        !g_opt_force_brute && g_opt_blockcost_par)
+        bq = block_quotient_exact(A, mdl, Pi);
+    SeqRun<TC> R(A, mdl, Pi, !bq);
     hipStream_t s = R.s;
     int64_t n = R.n;
     SeqCtx<TC> &C = *R.C;
+    if (bq) { block_window_table<TC>(A, *bq, mdl, C.HM.d, wi, C.ftab); C.O.Ftab = C.ftab.p; C.O.Wc = wi; }
     // any width past the scan's 16 columns, a monotone work budget or no constraint: the on-line divide and conquer (chunk_lws.hip)
     const bool lws = lws_ok(A, mdl, w, wi, wf);
     if (!lws) seq_window_table<TC>(A, mdl, w, wi, C);
@@ -1019,9 +1031,12 @@ int32_t run_pack_dynamic(cp_csr_s *A, const cp_model_t *mdl, const cp_rowpart_t 
         // width-windowed costs whose sums are exact: parallel (min,+) scan (chunk_scan.hip).  Int64 sums wrap, so Int64 models
         // are bounded as Float64 ones are (model_exact_on; column-block models by their tabulated components)
         bool scanned = false;
-        bool exact = model_exact_on(mdl, n, A->N, n + 1) && (std::is_same<TC, int64_t>::value || mdl->kind != CP_MODEL_COLBLOCK);
+        bool exact = bq ? true      // (blockcost_exact held)
+                        : model_exact_on(mdl, n, A->N, n + 1) && (std::is_same<TC, int64_t>::value || mdl->kind != CP_MODEL_COLBLOCK);
         if (W.kind == CP_MODEL_VERTEX_COUNT && C.O.Ftab && C.O.Wc == wi && exact && !g_opt_force_brute)
             scanned = pack_dynamic_scan<TC>(s, n, wi, C.O.Ftab, cst.p, spl.p);
+        CP_REQUIRE(scanned || !bq, CP_EHIP, "internal: the block window table was built and the scan refused it");      // (no step-oracle state to fall back on)
+        if (bq) g_blockcost_scan_packs++;
         if (!scanned)
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pack_dynamic<TC>), dim3(1), dim3(64), 0, s, C.O, W, cst.p, spl.p, R.st.p);
     }

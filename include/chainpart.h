@@ -64,6 +64,11 @@ int32_t cp_rcm(cp_csr_t csr, cp_csr_t adj_or_null, int32_t mode, int32_t reverse
  * rows of every column ascending.  rowprm (m) / colprm (n): 1-based host arrays, NULL for the identity; each is checked on the device
  * to be a permutation (CP_EINVAL, nothing is read out of range). */
 int32_t cp_csr_permute(cp_csr_t csr, const int64_t *rowprm /* m or NULL */, const int64_t *colprm /* n or NULL */, cp_csr_t *out);
+/* The quotient pattern of A under a SplitPartition Pi of its rows: the rows of every part merged, Pi->K x n, one entry (k, c) per part k
+ * with a nonzero in column c, as a NEW device-resident handle (the parts of every column ascending).  The 2-D block cost is a weighted
+ * net count on it (BlockCosts.jl:19-152; csrc/blockcost.hip).  Pi->spl must run from 1 to m + 1 (CP_EINVAL; a Map- or DomainPartition,
+ * spl == NULL, too); a repeated boundary is an empty part, an empty row of the result. */
+int32_t cp_csr_quotient(cp_csr_t csr, const cp_rowpart_t *Pi, cp_csr_t *out);
 
 /* ---- counting structures ----
  * dominancecount(hint, A)   SparsePrefixMatrices.jl:438-458   kind CP_COUNT_DOM : C[i,j]
