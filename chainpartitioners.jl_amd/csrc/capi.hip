@@ -152,7 +152,8 @@ static int32_t oracle_eval_into(cp_csr_t A, const cp_model_t *model, const cp_ro
 // (envelope.hip).  env_dc_layers: layers >= 2 of its total objective the divide and conquer ran (envelope_total.hip).  budget_layers:
 // layers >= 2 of the total-cost DP under a work budget that dp_total_budget.hip ran.  blockcost_scan_packs: chunker calls that ran the
 // window table over the quotient pattern and the (min,+) scan for a block model; blockcost_wave_evals: oracle queries of a block model
-// that k_block_eval answered (blockcost.hip).  kept:cp_set_option("poison", 1) starts a
+// that k_block_eval answered (blockcost.hip).  sym_total_layers: layers >= 2 of the total objective of a symmetric model that the divide
+// and conquer of sym_total.hip ran.  kept:cp_set_option("poison", 1) starts a
 // poison pass by zeroing the other counters and leaves this one.
 static const struct { const char *name; int64_t *var; bool kept; } g_stats[] = {
     {"spec_redo", &g_spec_redo, false}, {"poison_hits", &g_poison_hits, false}, {"fix_trips", &g_fix_trips, false},
@@ -165,6 +166,7 @@ static const struct { const char *name; int64_t *var; bool kept; } g_stats[] = {
     {"round_alloc_rounds", &g_round_alloc_rounds, false}, {"env_valley_layers", &g_env_valley_layers, false},
     {"env_dc_layers", &g_env_dc_layers, false}, {"budget_layers", &g_budget_layers, false},
     {"blockcost_scan_packs", &g_blockcost_scan_packs, false}, {"blockcost_wave_evals", &g_blockcost_wave_evals, false},
+    {"sym_total_layers", &g_sym_total_layers, false},
 };
 static void stats_reset(bool all) { for (const auto &c : g_stats) if (all || !c.kept) *c.var = 0; }
 
@@ -189,6 +191,12 @@ static const struct Opt { const char *name; int64_t *var; OptRule rule; int64_t 
     {"lws", &g_opt_lws, OPT_BOOL, 0, 0},                        // (1, default: DynamicTotalChunker past the scan by chunk_lws.hip; 0: the one-wave kernel)
     {"budget_total", &g_opt_budget_total, OPT_BOOL, 0, 0},      // (1, default: total-cost DP under a pin / work budget by dp_total_budget.hip; 0: the one-wave kernel)
     {"blockcost_par", &g_opt_blockcost_par, OPT_BOOL, 0, 0},    // (1, default: BlockComponentCostModel by the quotient-pattern table + scan and the wave-per-query evaluation of blockcost.hip, inside blockcost_exact; 0: the one-wave step oracle)
+    {"sym_total", &g_opt_sym_total, OPT_BOOL, 0, 0},            // (1, default: the total objective of a symmetric model inside sym_total_ok by sym_total.hip; 0: the candidate sweep)
+    {"sym_total_batch", &g_opt_sym_total_batch, OPT_BOOL, 0, 0},      // (1, default: that path runs the rectangles of one depth of the column tree in one launch sequence; 0: one per rectangle)
+    {"sym_total_min_n", &g_opt_sym_total_min_n, OPT_CLAMP, 0, NOLIM_HI},      // (the smallest n that path takes where the sweep is allowed; default 10240, the measured crossover.  Past brute_max_n: from 1024 on)
+    {"sym_total_scan_cells", &g_opt_sym_total_scan_cells, OPT_CLAMP, 1, NOLIM_HI},      // (that path's limits, as budget_scan_cells / budget_scan_cols / budget_stair_cols;
+    {"sym_total_scan_cols", &g_opt_sym_total_scan_cols, OPT_CLAMP, 1, NOLIM_HI},        //  defaults 2^20 / 1024 / 1024)
+    {"sym_total_stair_cols", &g_opt_sym_total_stair_cols, OPT_CLAMP, 1, NOLIM_HI},
     {"budget_scan_cells", &g_opt_budget_scan_cells, OPT_CLAMP, 1, NOLIM_HI},      // (that path: a full rectangle of at most this many cells ...
     {"budget_scan_cols", &g_opt_budget_scan_cols, OPT_CLAMP, 1, NOLIM_HI},        //  ... and columns is scanned whole; default 2^20 / 1024)
     {"budget_stair_cols", &g_opt_budget_stair_cols, OPT_CLAMP, 1, NOLIM_HI},      // (the partial rows of a block below this many columns are scanned whole; default 1024)

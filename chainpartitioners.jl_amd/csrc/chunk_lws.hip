@@ -47,6 +47,7 @@ struct LwsFirst {
     using TC = TC_;
     using Args = LwsArgs<TC>;
     static __device__ __forceinline__ TC base(const Args &G, int64_t p) { return G.cst1[p]; }
+    static __device__ __forceinline__ TC cell(const Args &G, int64_t p, int64_t r) { return lws_f<TC>(G, p, r); }
     static __device__ __forceinline__ bool better(TC c, int32_t p, TC bc, int32_t bp) { return lex_less(c, p, bc, bp); }
     static __device__ __forceinline__ int64_t stair_lo(const Args &G, int64_t r, int64_t ja) { return G.lo[r] > ja ? (int64_t)G.lo[r] : ja; }
     static __device__ __forceinline__ int64_t stair_hi(const Args &, int64_t, int64_t jb) { return jb; }

@@ -13,6 +13,7 @@ enum class DpPath {
     Total,         // dp_total.hip: the O(n log^2 n) scheme for inverse-Monge totals; under a weight's j0 array dp_total_budget.hip
     Valley,        // dp_bottleneck.hip: the valley search for bottleneck costs that grow with their part
     SymValley,     // ... over the derived pattern of the monotonized symmetric model (sym.hpp)
+    SymTotal,      // sym_total.hip: the total objective of the symmetric family by divide and conquer (sym_total_ok, model.hpp)
     SymSweep,      // sym.hip: the O(n^2) candidate sweep over the symmetric counters
     EnvValley,     // envelope.hip: the valley search of the envelope cost
     EnvDc,         // envelope_total.hip: its total objective by divide and conquer
@@ -132,6 +133,18 @@ bool budget_total_ok(const cp_csr_s *A, int64_t K, const cp_model_t *model, cons
 extern int64_t g_opt_budget_total;             // 1: on
 extern int64_t g_opt_budget_scan_cells, g_opt_budget_scan_cols, g_opt_budget_stair_cols;      // rectangles within both limits / partial rows of blocks below stair_cols columns are scanned whole
 extern int64_t g_budget_layers;                // layers that path ran since the last reset (cp_get_stat("budget_layers"))
+
+// sym_total.hip: one layer of the unconstrained total-cost DP of a symmetric model inside sym_total_ok, at any n.  Rows [rlo, rhi]
+// (0-based); row r takes its candidates from 0 <= p <= r, ties -> the largest p.  Only enqueues.
+struct SymDev;
+template <typename TC>
+void sym_total_layer(cp_csr_s *A, const SymDev &S, const DevModel<TC> &M, TC alpha, const TC *W, TC *cst_out, int32_t *ptr_out, int64_t rlo, int64_t rhi);
+extern int64_t g_opt_sym_total;                // 1: on
+extern int64_t g_opt_sym_total_min_n;          // the smallest n that path takes where the sweep is allowed too (the measured crossover)
+constexpr int64_t SYM_TOTAL_FLOOR = 1024;      // ... and where the sweep would be refused (n > brute_max_n): LWS_STAIR_COLS
+extern int64_t g_opt_sym_total_batch;          // 1: the rectangles of one depth of the column tree share one launch sequence; 0: one per rectangle
+extern int64_t g_opt_sym_total_scan_cells, g_opt_sym_total_scan_cols, g_opt_sym_total_stair_cols;      // as the budget path's limits
+extern int64_t g_sym_total_layers;             // layers that path ran since the last reset (cp_get_stat("sym_total_layers"))
 
 // seq.hip
 template <typename TC>

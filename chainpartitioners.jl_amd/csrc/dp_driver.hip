@@ -101,8 +101,14 @@ DpPath dp_path(const cp_csr_s *A, int64_t K, int32_t combine, int32_t order, con
                    "wrapping Int64 costs, force_brute) run the O(n^2) device sweep: n too large");
         return DpPath::EnvSweep;
     }
-    const bool sym = model_is_sym(m->kind);        // (of that family only the monotonized model passes a gate: fast_bottleneck_ok)
+    const bool sym = model_is_sym(m->kind);        // (of that family only the monotonized model passes fast_bottleneck_ok)
     if (total && fast_total_ok(m, A->n, A->N, K)) return DpPath::Total;
+    // the family's total objective: both loop orders (the chunker order passes no part index: alpha_of).  sym_total_min_n is where the
+    // divide and conquer overtakes the sweep; a sweep that would be refused is no competitor, so there it runs from the first n at
+    // which it is a decomposition at all (below SYM_TOTAL_FLOOR columns it is one whole-row scan, which is the sweep)
+    if (total && sym && g_opt_sym_total && sym_total_ok(m, A->n, A->N, K) &&
+        (A->n >= g_opt_sym_total_min_n || (A->n > g_opt_brute_max_n && A->n >= SYM_TOTAL_FLOOR)))
+        return DpPath::SymTotal;
     if (bottleneck && fast_bottleneck_ok(m, A->n, A->N, K)) return sym ? DpPath::SymValley : DpPath::Valley;
     CP_REQUIRE(A->n <= g_opt_brute_max_n, CP_EUNSUPPORTED,
                "model/objective outside the O(n log^2 n) class and n too large for the O(n^2) device sweep");
@@ -164,7 +170,7 @@ struct DpRun : cp_dp_s {
         hipStream_t s = A->stream;
         const int64_t n = A->n;
         switch (path) {
-        case DpPath::SymValley: case DpPath::SymSweep: sym_layer1<TC>(A, SH.d, HM.d, alpha_of(1), cur, ptr_row(1)); return;
+        case DpPath::SymValley: case DpPath::SymTotal: case DpPath::SymSweep: sym_layer1<TC>(A, SH.d, HM.d, alpha_of(1), cur, ptr_row(1)); return;
         case DpPath::EnvValley: case DpPath::EnvDc: case DpPath::EnvSweep: env_layer1<TC>(A, ED, HM.d, alpha_of(1), cur, ptr_row(1)); return;
         default: break;                        // Total, Valley, Sweep: the column scan below
         }
@@ -200,6 +206,7 @@ struct DpRun : cp_dp_s {
             dp_bottleneck_layer<TC>(A, Mc, alpha_of(k), prev, cur, ptr_row(k), rlo, rhi, win.w, win.lo, win.hi, win.j0, &pat);
             break;
         }
+        case DpPath::SymTotal: sym_total_layer<TC>(A, SH.d, HM.d, alpha_of(k), prev, cur, ptr_row(k), rlo, rhi); break;
         case DpPath::SymSweep: sym_brute_layer<TC>(A, SH.d, HM.d, alpha_of(k), combine, prev, cur, ptr_row(k), rlo, rhi); break;
         case DpPath::EnvValley: env_valley_layer<TC>(A, ED, HM.d, alpha_of(k), prev, cur, ptr_row(k), rlo, rhi); break;
         case DpPath::EnvDc: env_dc_layer<TC>(A, ED, HM.d, alpha_of(k), prev, cur, ptr_row(k), rlo, rhi); break;

@@ -21,6 +21,7 @@
 #include "dp.hpp"
 #include "weight.hpp"
 #include "lws_rect.hpp"
+#include "lws_decomp.hpp"
 
 namespace cpk {
 
@@ -41,6 +42,7 @@ struct BudgetLast {
     using TC = TC_;
     using Args = BudgetArgs<TC>;
     static __device__ __forceinline__ TC base(const Args &G, int64_t p) { return G.W[p]; }
+    static __device__ __forceinline__ TC cell(const Args &G, int64_t p, int64_t r) { return lws_f<TC>(G, p, r); }
     static __device__ __forceinline__ bool better(TC c, int32_t p, TC bc, int32_t bp) { return p >= 0 && (bp < 0 || c < bc || (c == bc && p > bp)); }
     static __device__ __forceinline__ int64_t stair_lo(const Args &G, int64_t r, int64_t ja)
     {
@@ -100,32 +102,21 @@ struct BudgetRun {
 
     explicit BudgetRun(LwsRect<BudgetLast<TC>> &E_) : E(E_) {}
 
-    // the feasible cells of the candidates [ja, jb] in the rows [ra, rb]
-    void push(int64_t ja, int64_t jb, int64_t ra, int64_t rb)
+    // the two staircases, read from the arrays
+    int64_t first_b_ge(int64_t x, int64_t y, int64_t v) const
     {
-        if (ja > jb || ra > rb) return;
-        auto first_b_ge = [&](int64_t x, int64_t y, int64_t v) {      // the first row of [x, y] with b(r) >= v; y + 1: none
-            return rlo + (int64_t)(std::lower_bound(b.begin() + (x - rlo), b.begin() + (y - rlo) + 1, (int32_t)v) - b.begin());
-        };
-        auto last_a_le = [&](int64_t x, int64_t y, int64_t v) {       // the last row of [x, y] with a(r) <= v; x - 1: none
-            return rlo + (int64_t)(std::upper_bound(a.begin() + (x - rlo), a.begin() + (y - rlo) + 1, (int32_t)v) - a.begin()) - 1;
-        };
-        // the rows that meet the block: b(r) >= ja (a suffix of the rows) and a(r) <= jb (a prefix)
-        const int64_t s = first_b_ge(ra, rb, ja), e = last_a_le(ra, rb, jb);
-        if (s > e) return;
-        // ... and among them those that see all of it: b(r) >= jb (a suffix) and a(r) <= ja (a prefix)
-        const int64_t f1 = first_b_ge(s, e, jb), f2 = last_a_le(s, e, ja);
-        int64_t t0 = s, t1 = e, u0 = e + 1, u1 = e;      // partial rows above [t0, t1] and below [u0, u1] the rectangle; none full: all in the first
-        if (f1 <= f2) {
-            E.rect(ja, jb, f1, f2);
-            t1 = f1 - 1; u0 = f2 + 1;
-        }
-        if (t1 < t0 && u1 < u0) return;
-        if (jb - ja < stair_cols) { E.stair(ja, jb, t0, t1 - t0 + 1, u0, u1 - u0 + 1); return; }
-        const int64_t jm = (ja + jb) / 2;
-        push(ja, jm, t0, t1); push(jm + 1, jb, t0, t1);
-        push(ja, jm, u0, u1); push(jm + 1, jb, u0, u1);
+        return rlo + (int64_t)(std::lower_bound(b.begin() + (x - rlo), b.begin() + (y - rlo) + 1, (int32_t)v) - b.begin());
     }
+    int64_t last_a_le(int64_t x, int64_t y, int64_t v) const
+    {
+        return rlo + (int64_t)(std::upper_bound(a.begin() + (x - rlo), a.begin() + (y - rlo) + 1, (int32_t)v) - a.begin()) - 1;
+    }
+    // every rectangle and every set of partial rows is launched as it is found
+    void rect(int, int64_t ja, int64_t jb, int64_t ra, int64_t rb) { E.rect(ja, jb, ra, rb); }
+    void stair(int, int64_t ja, int64_t jb, int64_t ra, int64_t m, int64_t ra2, int64_t m2) { E.stair(ja, jb, ra, m, ra2, m2); }
+
+    // the feasible cells of the candidates [ja, jb] in the rows [ra, rb]
+    void push(int64_t ja, int64_t jb, int64_t ra, int64_t rb) { stair_decompose(*this, *this, stair_cols, ja, jb, ra, rb); }
 };
 
 template <typename TC>

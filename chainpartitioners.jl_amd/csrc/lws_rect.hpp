@@ -4,6 +4,7 @@
 //
 //     P::TC, P::Args                    cost type; the kernel argument block, derived from LwsCounts<TC>
 //     P::base(G, p)                     the cost the candidate p starts from (the finished C[p] / the previous layer's W[p])
+//     P::cell(G, p, r)                  f(p, r): lws_f over the counters of LwsCounts, or a family's own evaluation (sym_total.hip)
 //     P::better(c, p, bc, bp)           does the pair (c, p) replace (bc, bp)?  p < 0: no pair.  Fixes the tie direction
 //     P::stair_lo / stair_hi(G, r, j)   the first / last feasible candidate of row r inside a block that starts / ends at column j
 //
@@ -13,6 +14,9 @@
 // rightmost argmin are both non-INCREASING in r.  So under either tie direction row i of a level searches [opt(i + h), opt(i - h)]
 // (k_lws_level, cut into chunks of LWS_CH columns, one wave each; k_lws_fin reduces the chunks).  Small rectangles are scanned
 // whole (k_lws_brute), and so are the partial rows of a narrow block (k_lws_stair).
+//
+// The level kernels take their rows from a level description LV: LwsLevel, one rectangle, or LwsBatch, the rectangles of one depth
+// of a column tree together -- pairwise disjoint in rows and in columns, so one launch sequence serves them all (sym_total.hip).
 #pragma once
 #include "csr.hpp"
 #include "model.hpp"
@@ -69,7 +73,7 @@ __device__ __forceinline__ void lws_scan_row(const typename P::Args &G, int64_t 
     bc = (TC)0;
     bp = -1;
     for (int64_t p = c0 + lane; p <= c1; p += 64) {
-        const TC v = cadd(P::base(G, p), lws_f<TC>(G, p, r));
+        const TC v = cadd(P::base(G, p), P::cell(G, p, r));
         if (P::better(v, (int32_t)p, bc, bp)) { bc = v; bp = (int32_t)p; }
     }
     wave_best<P>(bc, bp);
@@ -112,9 +116,52 @@ __device__ __forceinline__ void lws_range(const int32_t *__restrict__ opt, const
     hi = i >= L.h ? (int64_t)opt[r - L.h] : L.jb;
     if (hi < lo) hi = lo;                        // (cannot happen for an inverse-Monge cost)
 }
+__device__ __forceinline__ int64_t lws_row(const LwsLevel &L, int64_t u) { return L.ra + L.h - 1 + 2 * L.h * u; }
 
+// the same level of several rectangles: rd[0 .. nr), pre[0 .. nr] the prefix of their row counts on this level (a rectangle with
+// m < h has none); level row u belongs to the last rectangle with pre <= u and its opt neighbours stay inside that rectangle
+struct LwsRectD { int32_t ra, m, ja, jb; };      // rows ra .. ra + m - 1, candidates [ja, jb]
+struct LwsBatch { const LwsRectD *rd; const int32_t *pre; int64_t nr, h, cnt, cap; };
+
+__device__ __forceinline__ int64_t lws_batch_find(const int32_t *__restrict__ pre, int64_t nr, int64_t u)
+{
+    int64_t a = 0, b = nr - 1;
+    while (a < b) { const int64_t mid = (a + b + 1) >> 1; if ((int64_t)pre[mid] <= u) a = mid; else b = mid - 1; }
+    return a;
+}
+
+__device__ __forceinline__ void lws_range(const int32_t *opt, const LwsBatch &L, int64_t u, int64_t &r, int64_t &lo, int64_t &hi)
+{
+    const int64_t a = lws_batch_find(L.pre, L.nr, u);
+    const LwsRectD R = L.rd[a];
+    const int64_t i = L.h - 1 + 2 * L.h * (u - L.pre[a]);
+    r = R.ra + i;
+    lo = i + L.h < R.m ? (int64_t)opt[r + L.h] : (int64_t)R.ja;
+    hi = i >= L.h ? (int64_t)opt[r - L.h] : (int64_t)R.jb;
+    if (hi < lo) hi = lo;
+}
+__device__ __forceinline__ int64_t lws_row(const LwsBatch &L, int64_t u)
+{
+    const int64_t a = lws_batch_find(L.pre, L.nr, u);
+    return L.rd[a].ra + L.h - 1 + 2 * L.h * (u - L.pre[a]);
+}
+
+// ... and the small rectangles, or the partial rows, of one depth in one launch: block x is row x of the concatenated descriptors
+// (pre[0 .. nr]: the prefix of their m).  A row of a full rectangle sees all of [ja, jb], so stair_lo / stair_hi return ja / jb there
 template <typename P>
-__global__ void __launch_bounds__(256) k_lws_count(typename P::Args G, LwsLevel L, int32_t *__restrict__ cnt)
+__global__ void __launch_bounds__(64) k_lws_rows(typename P::Args G, const LwsRectD *__restrict__ rd, const int32_t *__restrict__ pre, int64_t nr)
+{
+    const int64_t a = lws_batch_find(pre, nr, (int64_t)blockIdx.x);
+    const LwsRectD R = rd[a];
+    const int64_t r = R.ra + ((int64_t)blockIdx.x - pre[a]);
+    typename P::TC bc;
+    int32_t bp;
+    lws_scan_row<P>(G, r, P::stair_lo(G, r, R.ja), P::stair_hi(G, r, R.jb), threadIdx.x, bc, bp);
+    if (threadIdx.x == 0 && P::better(bc, bp, G.bc[r], G.bp[r])) { G.bc[r] = bc; G.bp[r] = bp; }
+}
+
+template <typename P, typename LV>
+__global__ void __launch_bounds__(256) k_lws_count(typename P::Args G, LV L, int32_t *__restrict__ cnt)
 {
     const int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (u >= L.cnt) return;
@@ -124,8 +171,8 @@ __global__ void __launch_bounds__(256) k_lws_count(typename P::Args G, LwsLevel 
 }
 
 // chunk g of the level: binary search of the row in the chunk offsets off[0..cnt] (in LDS for small levels, else from the scan)
-template <typename P>
-__global__ void __launch_bounds__(256) k_lws_level(typename P::Args G, LwsLevel L, int64_t *__restrict__ goff, int32_t lds,
+template <typename P, typename LV>
+__global__ void __launch_bounds__(256) k_lws_level(typename P::Args G, LV L, int64_t *__restrict__ goff, int32_t lds,
                                                    typename P::TC *__restrict__ pc, int32_t *__restrict__ pq)
 {
     __shared__ int64_t off[LWS_LDS_ROWS + 1];
@@ -170,13 +217,13 @@ __global__ void __launch_bounds__(256) k_lws_level(typename P::Args G, LwsLevel 
 }
 
 // one thread per level row: its chunks -> opt of the row, merged into its best pair
-template <typename P>
-__global__ void __launch_bounds__(256) k_lws_fin(typename P::Args G, LwsLevel L, const int64_t *__restrict__ off, const typename P::TC *__restrict__ pc,
+template <typename P, typename LV>
+__global__ void __launch_bounds__(256) k_lws_fin(typename P::Args G, LV L, const int64_t *__restrict__ off, const typename P::TC *__restrict__ pc,
                                                  const int32_t *__restrict__ pq)
 {
     const int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (u >= L.cnt) return;
-    const int64_t r = L.ra + L.h - 1 + 2 * L.h * u;
+    const int64_t r = lws_row(L, u);
     typename P::TC bc = (typename P::TC)0;
     int32_t bp = -1;
     const int64_t e = std::min<int64_t>(off[u + 1], L.cap);
@@ -187,6 +234,11 @@ __global__ void __launch_bounds__(256) k_lws_fin(typename P::Args G, LwsLevel L,
 }
 
 // ------------------------------------------------------------------ host: the launches of one rectangle / one set of partial rows
+// rows of an m-row rectangle on level h, and a bound on the chunks of cnt level rows over cols columns: the search ranges of
+// neighbouring rows share at most their end points
+inline int64_t lws_level_rows(int64_t m, int64_t h) { return m < h ? 0 : (m - h + 1 + 2 * h - 1) / (2 * h); }
+inline int64_t lws_level_chunks(int64_t cols, int64_t cnt) { return (cols + cnt + LWS_CH - 1) / LWS_CH + cnt; }
+
 template <typename P>
 struct LwsRect {
     using TC = typename P::TC;
@@ -221,22 +273,35 @@ struct LwsRect {
         for (; h >= 1; h /= 2) {
             LwsLevel Lv;
             Lv.ra = ra; Lv.m = m; Lv.ja = ja; Lv.jb = jb; Lv.h = h;
-            Lv.cnt = (m - h + 1 + 2 * h - 1) / (2 * h);
-            Lv.cap = std::min<int64_t>(cap, (cols + Lv.cnt + LWS_CH - 1) / LWS_CH + Lv.cnt);
-            const bool lds = Lv.cnt <= LWS_LDS_ROWS;
-            if (!lds) {
-                launch([&] { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lws_count<P>), dim3((unsigned)cdiv(Lv.cnt, 256)), dim3(256), 0, s, G, Lv, cnt32.p); });
-                launch([&] { exclusive_scan_i32(cnt32.p, off.p, Lv.cnt, scratch, s); });          // (three kernels, one timed step)
-            }
-            launch([&] {
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lws_level<P>), dim3((unsigned)cdiv(Lv.cap, 4)), dim3(256), 0, s, G, Lv, off.p, (int32_t)lds,
-                                   pc.p, pq.p);
-            });
-            launch([&] {
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lws_fin<P>), dim3((unsigned)cdiv(Lv.cnt, 256)), dim3(256), 0, s, G, Lv, (const int64_t *)off.p,
-                                   (const TC *)pc.p, (const int32_t *)pq.p);
-            });
+            Lv.cnt = lws_level_rows(m, h);
+            Lv.cap = std::min<int64_t>(cap, lws_level_chunks(cols, Lv.cnt));
+            level(Lv);
         }
+    }
+
+    // one level, of one rectangle or of a depth's rectangles: Lv.cnt rows in at most Lv.cap <= cap chunks
+    template <typename LV> void level(const LV &Lv)
+    {
+        const bool lds = Lv.cnt <= LWS_LDS_ROWS;
+        if (!lds) {
+            launch([&] { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lws_count<P, LV>), dim3((unsigned)cdiv(Lv.cnt, 256)), dim3(256), 0, s, G, Lv, cnt32.p); });
+            launch([&] { exclusive_scan_i32(cnt32.p, off.p, Lv.cnt, scratch, s); });          // (three kernels, one timed step)
+        }
+        launch([&] {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lws_level<P, LV>), dim3((unsigned)cdiv(Lv.cap, 4)), dim3(256), 0, s, G, Lv, off.p, (int32_t)lds,
+                               pc.p, pq.p);
+        });
+        launch([&] {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lws_fin<P, LV>), dim3((unsigned)cdiv(Lv.cnt, 256)), dim3(256), 0, s, G, Lv, (const int64_t *)off.p,
+                               (const TC *)pc.p, (const int32_t *)pq.p);
+        });
+    }
+
+    // the rows of the descriptors rd[0 .. nr) scanned whole, one launch (pre: the prefix of their row counts, `rows` in all)
+    void rows(const LwsRectD *rd, const int32_t *pre, int64_t nr, int64_t rows)
+    {
+        if (nr <= 0 || rows <= 0) return;
+        launch([&] { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_lws_rows<P>), dim3((unsigned)rows), dim3(64), 0, s, G, rd, pre, nr); });
     }
 
     // the partial rows [ra, ra + m) and [ra2, ra2 + m2) of the block [ja, jb], one launch

@@ -215,6 +215,43 @@ inline bool fast_total_ok(const cp_model_t *m, int64_t n, int64_t N, int64_t K)
     return false;
 }
 
+// The same question for the symmetric family (sym.hpp), a predicate of its own: is the divide and conquer of sym_total.hip exact?
+// All three costs are modular terms plus multiples of counts that are submodular in the column range -- the net count of A, the net
+// count dianet of the derived pattern D -- or supermodular -- selfpin, the entries with both ends inside the range:
+//   kind 11   modular + dianet*b_dia_net                                          b_dia_net >= 0
+//   kind 10   modular + net*b_local_net + (dianet - nv)*(b_remote_net - b_local_net)      b_local_net >= 0, b_remote_net >= b_local_net
+//   kind 12   modular + selfpin*(b_self_pin - b_cut_pin)                           b_self_pin <= b_cut_pin
+// alpha, alpha[k], b_vertex and b_pin / b_over_pin are free.  Every reachable total must be exact, as for fast_total_ok: integer-valued
+// parameters, and K*max|alpha| + n*|b_vertex| + ... below 2^60 (Int64, in 128 bits) or 2^53 (Float64), where the counts reach
+//   kind 11   what model_exact_on bounds
+//   kind 10   N pins, and N + n for each of the two net terms (local + remote = net <= N, remote <= dianet <= N + n)
+//   kind 12   N pins in all, each a self pin or a cut pin
+// n < 2^30 and the 32-bit layout of D's keys (ensure_sym_links) hold besides.
+inline bool sym_total_ok(const cp_model_t *m, int64_t n, int64_t N, int64_t K)
+{
+    if (!model_is_sym(m->kind) || !model_all_integral(m)) return false;
+    if (n < 0 || N < 0 || n >= ((int64_t)1 << 30) || N + n >= ((int64_t)1 << 31) - 1) return false;
+    auto P = [&](int i) { return m->dtype == CP_I64 ? (double)m->p_i64[i] : m->p_f64[i]; };
+    if (m->kind == CP_MODEL_MONO_SYM_CONNECTIVITY) return P(CP_P_DIA_NET) >= 0 && model_exact_on(m, n, N, K);
+    const bool conn = m->kind == CP_MODEL_SYM_CONNECTIVITY;
+    if (conn ? !(P(CP_P_LOCAL_NET) >= 0 && P(CP_P_REMOTE_NET) >= P(CP_P_LOCAL_NET)) : !(P(CP_P_SELF_PIN) <= P(CP_P_CUT_PIN))) return false;
+    const int64_t Kk = K > 0 ? K : 1;
+    if (m->dtype == CP_I64) {
+        u128 amax = mag128(m->p_i64[CP_P_ALPHA]);
+        if (m->alpha_k) for (int64_t i = 0; i < m->n_alpha_k; i++) amax = std::max(amax, mag128(((const int64_t *)m->alpha_k)[i]));
+        u128 bound = amax * (u128)Kk + mag128(m->p_i64[CP_P_VERTEX]) * (u128)n;
+        if (conn) bound += mag128(m->p_i64[CP_P_PIN]) * (u128)N + (mag128(m->p_i64[CP_P_LOCAL_NET]) + mag128(m->p_i64[CP_P_REMOTE_NET])) * (u128)(N + n);
+        else bound += std::max(mag128(m->p_i64[CP_P_SELF_PIN]), mag128(m->p_i64[CP_P_CUT_PIN])) * (u128)N;
+        return bound < ((u128)1 << 60);
+    }
+    double amax = std::fabs(m->p_f64[CP_P_ALPHA]);
+    if (m->alpha_k) for (int64_t i = 0; i < m->n_alpha_k; i++) amax = std::max(amax, std::fabs(((const double *)m->alpha_k)[i]));
+    double bound = amax * (double)Kk + std::fabs(m->p_f64[CP_P_VERTEX]) * (double)n;
+    if (conn) bound += std::fabs(m->p_f64[CP_P_PIN]) * (double)N + (std::fabs(m->p_f64[CP_P_LOCAL_NET]) + std::fabs(m->p_f64[CP_P_REMOTE_NET])) * (double)(N + n);
+    else bound += std::max(std::fabs(m->p_f64[CP_P_SELF_PIN]), std::fabs(m->p_f64[CP_P_CUT_PIN])) * (double)N;
+    return bound < 9007199254740992.0;       // 2^53
+}
+
 // host: build a DevModel from the C-ABI struct, uploading alpha_k / tables
 template <typename TC>
 struct HostModel {

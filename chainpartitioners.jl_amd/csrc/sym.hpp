@@ -59,6 +59,10 @@ struct SymWork {
     DBuf<int32_t> pin32;
     DBuf<int64_t> spos;                   // n+1
     WaveletHost dia, selfpin, net;
+    // the scratch and launch plans of the total-cost layers (sym_total.hip owns the type)
+    void *total = nullptr;
+    void (*total_free_fn)(void *) = nullptr;
+    ~SymWork() { if (total && total_free_fn) total_free_fn(total); }
 };
 SymWork *sym_work_get(cp_csr_s *A);
 void ensure_sym_links(cp_csr_s *A);                                                  // dpos, dpos32, dprev, dnext

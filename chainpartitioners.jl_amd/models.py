@@ -228,16 +228,18 @@ class AffineSecondaryConnectivityModel(AffinePrimaryConnectivityModel):
 # rows and columns; HIP backend only)
 class AffineSymmetricConnectivityModel(_Model):
     """SymmetricConnectivityCosts.jl:5-19: alpha + nv*beta_vertex + np*beta_pin + local*beta_local_net + remote*beta_remote_net with
-    remote = dianet(j, j') - nv (the nets of the part that reach outside its own rows) and local = net(j, j') - remote."""
+    remote = dianet(j, j') - nv (the nets of the part that reach outside its own rows) and local = net(j, j') - remote.
+    `alpha_k` gives a per-part alpha[k], as for the monotonized model."""
     kind = CP_MODEL_SYM_CONNECTIVITY
     symmetric = True
     fields = ("alpha", "beta_vertex", "beta_pin", "beta_local_net", "beta_remote_net")
 
-    def __init__(self, alpha=0, beta_vertex=0, beta_pin=0, beta_local_net=0, beta_remote_net=0):
-        self._set(alpha, beta_vertex, beta_pin, beta_local_net, beta_remote_net)
+    def __init__(self, alpha=0, beta_vertex=0, beta_pin=0, beta_local_net=0, beta_remote_net=0, *, alpha_k=None):
+        self._set(alpha, beta_vertex, beta_pin, beta_local_net, beta_remote_net, alpha_k=alpha_k)
 
     def __call__(self, n_vertices, n_pins, n_local, n_remote, k=None):
-        return (self.alpha + n_vertices * self.beta_vertex + n_pins * self.beta_pin + n_local * self.beta_local_net
+        a = self.alpha if self.alpha_k is None or k is None else self.alpha_k[k - 1]
+        return (a + n_vertices * self.beta_vertex + n_pins * self.beta_pin + n_local * self.beta_local_net
                 + n_remote * self.beta_remote_net)
 
 
@@ -280,16 +282,17 @@ class AffineMonotonizedSymmetricConnectivityModel(_Model):
 
 class AffineSymmetricEdgeCutModel(_Model):
     """SymmetricEdgeCutCosts.jl:5-18: alpha + nv*beta_vertex + selfpin(j, j')*beta_self_pin + (np - selfpin)*beta_cut_pin,
-    selfpin = nonzeros of the part's diagonal block."""
+    selfpin = nonzeros of the part's diagonal block.  `alpha_k` gives a per-part alpha[k]."""
     kind = CP_MODEL_SYM_EDGE_CUT
     symmetric = True
     fields = ("alpha", "beta_vertex", "beta_self_pin", "beta_cut_pin")
 
-    def __init__(self, alpha=0, beta_vertex=0, beta_self_pin=0, beta_cut_pin=0):
-        self._set(alpha, beta_vertex, beta_self_pin, beta_cut_pin)
+    def __init__(self, alpha=0, beta_vertex=0, beta_self_pin=0, beta_cut_pin=0, *, alpha_k=None):
+        self._set(alpha, beta_vertex, beta_self_pin, beta_cut_pin, alpha_k=alpha_k)
 
     def __call__(self, n_vertices, n_self_pins, n_cut_pins, k=None):
-        return self.alpha + n_vertices * self.beta_vertex + n_self_pins * self.beta_self_pin + n_cut_pins * self.beta_cut_pin
+        a = self.alpha if self.alpha_k is None or k is None else self.alpha_k[k - 1]
+        return a + n_vertices * self.beta_vertex + n_self_pins * self.beta_self_pin + n_cut_pins * self.beta_cut_pin
 
 
 # ---------------------------------------------------------------- the plaid edge-cut pair (HIP backend only)

@@ -354,7 +354,9 @@ int32_t cp_reset_stream(cp_csr_t csr);
  * launch in front ("cr_consume").  "env_valley_layers" -- DP layers of the envelope model (kind 15) the valley search ran; the
  * candidate sweep counts none.  "env_dc_layers" -- its DP layers >= 2 under the total objective that the divide and conquer over the
  * cut column ran (a layer of one row counts).  "budget_layers" -- DP layers >= 2 of the total objective under a pin or work budget that
- * csrc/dp_total_budget.hip ran (its profile slot is "dp_budget").  All of these are reset when "poison" is switched on and by cp_set_option("stat_reset", 1); reading
+ * csrc/dp_total_budget.hip ran (its profile slot is "dp_budget").  "sym_total_layers" -- DP layers >= 2 of the total objective of a
+ * symmetric model (kinds 10 - 12) that the divide and conquer of csrc/sym_total.hip ran (its profile slot is "dp_sym_total"; a layer of
+ * one row counts).  All of these are reset when "poison" is switched on and by cp_set_option("stat_reset", 1); reading
  * changes nothing. */
 int32_t cp_get_stat(const char *name, int64_t *out);
 /* Test entry: the launch that ends the counting phase of a DP round, on host arrays.  Exclusive scans of a[0 .. na) and (two != 0)
@@ -432,7 +434,14 @@ int32_t cp_test_own_pack(cp_csr_t csr, int32_t *vpk_out, int32_t *vbase_out, int
  * csrc/chunk_lws.hip; 0: the one-wave kernel), "lws_leaf" (its rows per leaf wave: 256, 512, 1024 or 2048), "budget_total" (1, default:
  * the total-cost DP under a pin or work budget runs the two-staircase divide and conquer of csrc/dp_total_budget.hip; 0: the one-wave
  * kernel), "budget_scan_cells" / "budget_scan_cols" (that path scans a full rectangle whole while it has at most this many cells and
- * columns: 2^20 / 1024; at least 1), "budget_stair_cols" (... and the partial rows of a block of fewer columns than this: 1024), "rcm_narrow" (cp_rcm: BFS levels of at most this many
+ * columns: 2^20 / 1024; at least 1), "budget_stair_cols" (... and the partial rows of a block of fewer columns than this: 1024),
+ * "sym_total" (1, default: the total objective of a symmetric model inside its gate -- b_dia_net >= 0; b_local_net >= 0 and b_remote_net >=
+ * b_local_net; b_self_pin <= b_cut_pin; integer-valued parameters and exact totals -- runs the divide and conquer of csrc/sym_total.hip at
+ * any n; 0: the candidate sweep, n <= "brute_max_n"), "sym_total_min_n" (the smallest n that path takes while the
+ * sweep is allowed, the measured crossover: 10240; where n > "brute_max_n" it runs from n = 1024 on instead of refusing), "sym_total_batch" (1,
+ * default: the rectangles of one depth of its column tree share one launch sequence; 0: one sequence per rectangle), "sym_total_scan_cells" /
+ * "sym_total_scan_cols" / "sym_total_stair_cols" (that path's limits, as the three budget options: 2^20 / 1024 / 1024; at least 1),
+ * "rcm_narrow" (cp_rcm: BFS levels of at most this many
  * vertices are walked by one workgroup, level after level in one launch; 0: every level by grid kernels; a value beyond the walker's
  * capacity of 1024 vertices: whenever the level fits), "greedy_lds_parts" (cp_partition_greedy_bottleneck: the walk keeps the part costs and counts in
  * LDS while K is at most this, default and largest value 2048; 0: always in global memory), "prof_only" slot (events on one profile slot only), "dbg"
