@@ -13,6 +13,7 @@
 #include "csr.hpp"
 #include "model.hpp"
 #include "wavelet.hpp"
+#include "partwise.hpp"
 #include "sym.hpp"
 #include "cut.hpp"
 #include "envelope.hpp"
@@ -290,8 +291,6 @@ __global__ void __launch_bounds__(64) k_bisect_index(OD O, int64_t K, double c_l
     if (lane == 0) *nprobes = probes;
 }
 
-struct CsrGuard { cp_csr_t h = nullptr; ~CsrGuard() { if (h) cp_csr_destroy(h); } };
-
 template <typename TC>
 int32_t run_bisect(cp_csr_s *A, int64_t K, const cp_model_t *mdl, const cp_rowpart_t *Pi, double c_lo, double c_hi, double eps, int flip,
                    int64_t *spl_out, bool by_index = false)
@@ -302,9 +301,9 @@ int32_t run_bisect(cp_csr_s *A, int64_t K, const cp_model_t *mdl, const cp_rowpa
     OracleDev<TC> O;
     memset(&O, 0, sizeof(O));
     O.M = HM.d; O.pos = A->pos.p; O.n = A->n; O.has_net = 0;
-    WaveletHost net, lcn;
-    CsrGuard Ap;
-    DBuf<int64_t> d_pios, d_prm, d_spl2;
+    WaveletHost net;
+    PartwiseStage PW;
+    DBuf<int64_t> d_spl2;
     SymHost SH;
     SymOracleDev<TC> OS;
     const bool sym = model_is_sym(mdl->kind);
@@ -315,34 +314,17 @@ int32_t run_bisect(cp_csr_s *A, int64_t K, const cp_model_t *mdl, const cp_rowpa
     if (mdl->kind == CP_MODEL_CONNECTIVITY || mdl->kind == CP_MODEL_PRIMARY) { ensure_net_counter(A, net); O.has_net = 1; O.net = net.d; }
     const bool cut = model_is_cut(mdl->kind);
     CutOracleDev<TC> OC;
-    DBuf<int64_t> d_ppos;
     if (mdl->kind == CP_MODEL_PRIMARY || mdl->kind == CP_MODEL_SECONDARY || cut) {
         bool sec = mdl->kind == CP_MODEL_SECONDARY || mdl->kind == CP_MODEL_SECONDARY_EDGE_CUT;
         CP_REQUIRE(Pi && (Pi->asg || Pi->spl) && Pi->K >= 1, CP_EINVAL, "this cost model needs a row partition Pi");
         CP_REQUIRE(!sec || cut || (Pi->spl && K <= Pi->K), CP_EINVAL, "the secondary connectivity model needs a SplitPartition of the rows with >= K parts");
         CP_REQUIRE(!sec || !cut || (Pi->spl && K <= Pi->K), CP_EINVAL, "the secondary edge-cut model needs a SplitPartition of the rows with >= K parts");
         CP_REQUIRE(!cut || K <= Pi->K, CP_EINVAL, "the plaid edge-cut models are evaluated for parts 1..K of Pi");
-        int64_t m = A->m, N = A->N, Kp = Pi->K;
-        std::vector<int64_t> asg((size_t)(m > 0 ? m : 1), 1);
-        if (Pi->asg) for (int64_t i = 0; i < m; i++) asg[(size_t)i] = Pi->asg[i];
-        else for (int64_t k = 1; k <= Kp; k++) for (int64_t i = Pi->spl[k - 1]; i <= Pi->spl[k] - 1; i++) { CP_REQUIRE(i >= 1 && i <= m, CP_EINVAL, "split vector out of range"); asg[(size_t)i - 1] = k; }
-        std::vector<int64_t> pios((size_t)Kp + 1), prm((size_t)(N > 0 ? N : 1)), ppos((size_t)N + 2), pidx((size_t)(N > 0 ? N : 1));
-        int64_t npr = 0;
-        int32_t rc = cp_partwise(A, Kp, asg.data(), &npr, pios.data(), prm.data(), ppos.data(), pidx.data());
+        const int64_t Kp = Pi->K;
+        int32_t rc = partwise_stage(A, Pi, cut ? PW_PINS : sec ? PW_RANK : PW_NETS, PW);      // partwise(A, Pi); primary: the partwise matrix and its net counter
         if (rc != CP_OK) return rc;
-        d_pios.alloc((size_t)Kp + 1); d_prm.alloc((size_t)(npr > 0 ? npr : 1));
-        CP_HIP(hipMemcpyAsync(d_pios.p, pios.data(), sizeof(int64_t) * (size_t)(Kp + 1), hipMemcpyHostToDevice, s));
-        if (npr > 0) CP_HIP(hipMemcpyAsync(d_prm.p, prm.data(), sizeof(int64_t) * (size_t)npr, hipMemcpyHostToDevice, s));
-        O.plaid = sec ? 2 : 1; O.pios = d_pios.p; O.prm = d_prm.p;
-        if (cut) {                                    // the partwise column pointer is the pin prefix: no counter
-            d_ppos.alloc((size_t)npr + 1);
-            CP_HIP(hipMemcpyAsync(d_ppos.p, ppos.data(), sizeof(int64_t) * (size_t)(npr + 1), hipMemcpyHostToDevice, s));
-        } else if (!sec) {
-            rc = cp_csr_create(m, npr, N, ppos.data(), pidx.data(), A->device, &Ap.h);          // the partwise matrix and its net counter
-            if (rc != CP_OK) return rc;
-            ensure_net_counter(Ap.h, lcn);
-            O.lcn = lcn.d; O.np = npr; O.ppos = Ap.h->pos.p;
-        }
+        O.plaid = sec ? 2 : 1; O.pios = PW.pios.p; O.prm = PW.prm.p;
+        if (!cut && !sec) { O.lcn = PW.lcn.d; O.np = PW.npr; O.ppos = PW.Ap->pos.p; }
         if (sec) {
             d_spl2.alloc((size_t)Kp + 1);
             CP_HIP(hipMemcpyAsync(d_spl2.p, Pi->spl, sizeof(int64_t) * (size_t)(Kp + 1), hipMemcpyHostToDevice, s));
@@ -352,9 +334,9 @@ int32_t run_bisect(cp_csr_s *A, int64_t K, const cp_model_t *mdl, const cp_rowpa
         if (cut) {
             memset(&OC, 0, sizeof(OC));
             OC.M = HM.d; OC.n = A->n; OC.secondary = sec ? 1 : 0; OC.pos = A->pos.p;
-            OC.pios = d_pios.p; OC.prm = d_prm.p; OC.ppos = d_ppos.p; OC.spl = O.spl; OC.tpos = O.tpos;
+            OC.pios = PW.pios.p; OC.prm = PW.prm.p; OC.ppos = PW.ppos.p; OC.spl = O.spl; OC.tpos = O.tpos;
         }
-        CP_HIP(hipStreamSynchronize(s));              // host staging vectors die at scope end
+        CP_HIP(hipStreamSynchronize(s));              // (the copy of the caller's split vector)
     }
     DBuf<int64_t> buf((size_t)(4 * (K + 1) + 1));
     int64_t *d_lo = buf.p, *d_hi = buf.p + (K + 1), *d_spl = buf.p + 2 * (K + 1), *d_out = buf.p + 3 * (K + 1), *d_np = buf.p + 4 * (K + 1);

@@ -5,6 +5,7 @@
 #include "dp.hpp"
 #include "sym.hpp"
 #include "cut.hpp"
+#include "plaid_total.hpp"
 #include "envelope.hpp"
 #include "blockcost.hpp"
 #include <cmath>
@@ -153,7 +154,8 @@ static int32_t oracle_eval_into(cp_csr_t A, const cp_model_t *model, const cp_ro
 // layers >= 2 of the total-cost DP under a work budget that dp_total_budget.hip ran.  blockcost_scan_packs: chunker calls that ran the
 // window table over the quotient pattern and the (min,+) scan for a block model; blockcost_wave_evals: oracle queries of a block model
 // that k_block_eval answered (blockcost.hip).  sym_total_layers: layers >= 2 of the total objective of a symmetric model that the divide
-// and conquer of sym_total.hip ran.  kept:cp_set_option("poison", 1) starts a
+// and conquer of sym_total.hip ran.  plaid_total_layers / plaid_scan_layers: layers >= 2 of the total objective of the primary / secondary
+// plaid connectivity model that the rectangle engine / the prefix-min scan of plaid_total.hip ran.  kept:cp_set_option("poison", 1) starts a
 // poison pass by zeroing the other counters and leaves this one.
 static const struct { const char *name; int64_t *var; bool kept; } g_stats[] = {
     {"spec_redo", &g_spec_redo, false}, {"poison_hits", &g_poison_hits, false}, {"fix_trips", &g_fix_trips, false},
@@ -167,6 +169,7 @@ static const struct { const char *name; int64_t *var; bool kept; } g_stats[] = {
     {"env_dc_layers", &g_env_dc_layers, false}, {"budget_layers", &g_budget_layers, false},
     {"blockcost_scan_packs", &g_blockcost_scan_packs, false}, {"blockcost_wave_evals", &g_blockcost_wave_evals, false},
     {"sym_total_layers", &g_sym_total_layers, false},
+    {"plaid_total_layers", &g_plaid_total_layers, false}, {"plaid_scan_layers", &g_plaid_scan_layers, false},
 };
 static void stats_reset(bool all) { for (const auto &c : g_stats) if (all || !c.kept) *c.var = 0; }
 
@@ -197,6 +200,12 @@ static const struct Opt { const char *name; int64_t *var; OptRule rule; int64_t 
     {"sym_total_scan_cells", &g_opt_sym_total_scan_cells, OPT_CLAMP, 1, NOLIM_HI},      // (that path's limits, as budget_scan_cells / budget_scan_cols / budget_stair_cols;
     {"sym_total_scan_cols", &g_opt_sym_total_scan_cols, OPT_CLAMP, 1, NOLIM_HI},        //  defaults 2^20 / 1024 / 1024)
     {"sym_total_stair_cols", &g_opt_sym_total_stair_cols, OPT_CLAMP, 1, NOLIM_HI},
+    {"plaid_total", &g_opt_plaid_total, OPT_BOOL, 0, 0},        // (1, default: the total objective of the plaid connectivity pair inside plaid_total_ok / plaid_scan_exact by plaid_total.hip; 0: the candidate sweep)
+    {"plaid_total_min_n", &g_opt_plaid_total_min_n, OPT_CLAMP, 0, NOLIM_HI},      // (the smallest n the primary path takes where the sweep is allowed; default 1024, the first measured size, at which it already wins.  Past brute_max_n: from 1024 on)
+    {"plaid_scan_min_n", &g_opt_plaid_scan_min_n, OPT_CLAMP, 0, NOLIM_HI},        // (the same for the secondary scan; default 1024.  Past brute_max_n: any n)
+    {"plaid_total_scan_cells", &g_opt_plaid_total_scan_cells, OPT_CLAMP, 1, NOLIM_HI},      // (the primary path's limits, as sym_total_scan_cells / _scan_cols / _stair_cols;
+    {"plaid_total_scan_cols", &g_opt_plaid_total_scan_cols, OPT_CLAMP, 1, NOLIM_HI},        //  defaults 2^20 / 1024 / 1024)
+    {"plaid_total_stair_cols", &g_opt_plaid_total_stair_cols, OPT_CLAMP, 1, NOLIM_HI},
     {"budget_scan_cells", &g_opt_budget_scan_cells, OPT_CLAMP, 1, NOLIM_HI},      // (that path: a full rectangle of at most this many cells ...
     {"budget_scan_cols", &g_opt_budget_scan_cols, OPT_CLAMP, 1, NOLIM_HI},        //  ... and columns is scanned whole; default 2^20 / 1024)
     {"budget_stair_cols", &g_opt_budget_stair_cols, OPT_CLAMP, 1, NOLIM_HI},      // (the partial rows of a block below this many columns are scanned whole; default 1024)
@@ -501,12 +510,14 @@ int32_t cp_dynamic_tables(cp_csr_t A, int64_t K, int32_t combine, const cp_model
     return guarded([&]() -> int32_t {
         CP_REQUIRE(A && ptr_out && model_known(model) && K >= 1, CP_EINVAL, "bad argument");
         CP_REQUIRE(combine == CP_COMBINE_SUM || combine == CP_COMBINE_MAX, CP_EINVAL, "bad combine");
-        if (model_is_cut(model->kind)) {                                        // (the only kinds here that look at Pi)
+        if (model_is_cut(model->kind) || model->kind == CP_MODEL_PRIMARY || model->kind == CP_MODEL_SECONDARY) {      // (the only kinds here that look at Pi)
             CP_HIP(hipSetDevice(A->device));
             std::vector<int64_t> spl((size_t)K + 1);
+            const bool cut = model_is_cut(model->kind);
             return with_cost_type(model->dtype, [&](auto tag) {
                 using TC = decltype(tag);
-                return run_cut_dynamic<TC>(A, K, combine, CP_ORDER_SPLITTER, model, Pi, spl.data(), ptr_out, pick<TC>(cst_i64, cst_f64));
+                if (cut) return run_cut_dynamic<TC>(A, K, combine, CP_ORDER_SPLITTER, model, Pi, spl.data(), ptr_out, pick<TC>(cst_i64, cst_f64));
+                return run_plaid_dynamic<TC>(A, K, combine, CP_ORDER_SPLITTER, model, Pi, spl.data(), ptr_out, pick<TC>(cst_i64, cst_f64));
             });
         }
         CP_REQUIRE(dp_takes_kind(model->kind, DP_KINDS_TABLES), CP_EUNSUPPORTED, "model kind has no device DP path");

@@ -20,7 +20,7 @@ ProfSlot g_prof[PROF_NSLOTS] = {
     {"chunk_col_neq", 0, 0, 0}, {"chunk_overlap_next", 0, 0, 0}, {"chunk_orbit", 0, 0, 0}, {"chunk_compact", 0, 0, 0},
     {"map_magnetic", 0, 0, 0}, {"map_greedy_setup", 0, 0, 0}, {"map_greedy_gather", 0, 0, 0}, {"map_greedy_walk", 0, 0, 0},
     {"env_build", 0, 0, 0}, {"env_valley", 0, 0, 0}, {"env_sweep", 0, 0, 0}, {"env_dc", 0, 0, 0}, {"dp_budget", 0, 0, 0},
-    {"block_quotient", 0, 0, 0}, {"block_table", 0, 0, 0}, {"block_eval", 0, 0, 0}, {"dp_sym_total", 0, 0, 0}};
+    {"block_quotient", 0, 0, 0}, {"block_table", 0, 0, 0}, {"block_eval", 0, 0, 0}, {"dp_sym_total", 0, 0, 0}, {"dp_plaid_total", 0, 0, 0}};
 bool g_prof_on = false;
 int g_prof_only = -1;
 std::vector<ProfPending> g_prof_pending;

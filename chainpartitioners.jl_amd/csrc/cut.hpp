@@ -59,7 +59,24 @@ __device__ __forceinline__ TC oracle_eval_dev(const CutOracleDev<TC> &O, int64_t
     return cut_apply(O.M.p, alpha, jp - j, l, (O.pos[jp - 1] - O.pos[j - 1]) - l);      // PrimaryEdgeCutCosts.jl:51-57
 }
 
+// what a kernel of plaid_cut.hip needs to evaluate the cost of part k
+template <typename TC>
+struct CutLayer {
+    int32_t secondary;
+    TC alpha;                  // alpha_k
+    int64_t nvk, wk;           // secondary: vertices / pins of part k of Pi
+    TC p[5];
+};
+
 // plaid_cut.hip
+// One total-cost layer as a prefix-min scan with the reference's tie rule (the largest minimiser), for a cost of the form
+// f(p, r, k) = constk + S_k[r] - S_k[p]:  cst[r] = constk + S_k[r] + min over p <= r of W[p] - S_k[p].  S_k comes from Y and the prefix
+// counts Lc[0 .. n1): secondary form S_k[c] = Lc[c]*p[CP_P_SELF_PIN] - Lc[c]*p[CP_P_CUT_PIN] (pos unused), primary form as plaid_cut.hip
+// states it.  Exact only while no intermediate rounds or wraps: the caller's gate.  Only enqueues.
+template <typename TC> struct CutScanWork { DBuf<TC> tv, av; DBuf<int32_t> ti, ai; };
+template <typename TC>
+void cut_scan_layer(hipStream_t s, int64_t n1, const CutLayer<TC> &Y, TC constk, const int64_t *pos, const int32_t *Lc, const TC *W,
+                    CutScanWork<TC> &ws, TC *cst, int32_t *ptr);
 extern int64_t g_cut_scan_layers;          // DP layers the prefix-min scan ran (cp_get_stat("cut_scan_layers"))
 template <typename TC>
 int32_t run_cut_eval(cp_csr_s *A, const cp_model_t *mdl, const cp_rowpart_t *Pi, int64_t nq, const int64_t *j, const int64_t *jp,

@@ -166,9 +166,10 @@ void upload_part(cp_csr_s *A, const cp_rowpart_t *Pi, bool need_spl, PlaidPart &
 template <typename TC>
 int32_t run_plaid_eval(cp_csr_s *A, const cp_model_t *mdl, const cp_rowpart_t *Pi, int64_t nq, const int64_t *j, const int64_t *jp,
                        const int64_t *k, TC *out);
+// the K-part DP; ptr_tab / cst_tab: the host tables of cp_dynamic_tables, or null
 template <typename TC>
 int32_t run_plaid_dynamic(cp_csr_s *A, int64_t K, int32_t combine, int32_t order, const cp_model_t *mdl, const cp_rowpart_t *Pi,
-                          int64_t *spl_out);
+                          int64_t *spl_out, int64_t *ptr_tab = nullptr, TC *cst_tab = nullptr);
 
 // chunk_scan.hip: DynamicTotalChunker under a VertexCount window as a (min,+) scan; false = not applicable
 template <typename TC>

@@ -252,6 +252,65 @@ inline bool sym_total_ok(const cp_model_t *m, int64_t n, int64_t N, int64_t K)
     return bound < 9007199254740992.0;       // 2^53
 }
 
+// ... and for the plaid connectivity pair (plaid.hip), kinds 8 / 9 under a row partition Pi: the exact total-cost paths of
+// plaid_total.hip.  max|alpha| over the scalar and the per-part values, in 128 bits / as a double:
+inline u128 model_amax128(const cp_model_t *m)
+{
+    u128 amax = mag128(m->p_i64[CP_P_ALPHA]);
+    if (m->alpha_k) for (int64_t i = 0; i < m->n_alpha_k; i++) amax = std::max(amax, mag128(((const int64_t *)m->alpha_k)[i]));
+    return amax;
+}
+inline double model_amax_f64(const cp_model_t *m)
+{
+    double amax = std::fabs(m->p_f64[CP_P_ALPHA]);
+    if (m->alpha_k) for (int64_t i = 0; i < m->n_alpha_k; i++) amax = std::max(amax, std::fabs(((const double *)m->alpha_k)[i]));
+    return amax;
+}
+// Primary, layer k: f(p, r, k) = alpha_k + (r - p)*b_vertex + pins*b_pin + b_local_net*nets_k(p, r) + b_remote_net*nets_notk(p, r), nets_k
+// the net count of the rows Pi gives to part k and nets_notk = nets - nets_k that of all other rows.  Both are net counts of row
+// sub-matrices, hence submodular in the column range: with b_local_net >= 0 and b_remote_net >= 0 the cost is modular plus
+// non-negative multiples of submodular counts, which is the inverse-Monge property lws_rect.hpp asks for (bound_stripe asserts the
+// same two signs).  alpha, alpha[k], b_vertex and b_pin are free.  The objective is a sum and the loop order is the splitter's (the
+// cost needs k).  Every reachable total is exact: integer-valued parameters and K*max|alpha| + n*|b_vertex| + N*|b_pin| +
+// N*max(b_local_net, b_remote_net) -- the nets of disjoint column ranges sum to at most N -- below 2^60 (Int64, in 128 bits) or 2^53
+// (Float64).  n < 2^30.
+inline bool plaid_total_ok(const cp_model_t *m, int64_t n, int64_t N, int64_t K, int32_t combine, int32_t order)
+{
+    if (m->kind != CP_MODEL_PRIMARY || combine != CP_COMBINE_SUM || order != CP_ORDER_SPLITTER || !model_all_integral(m)) return false;
+    if (n < 0 || N < 0 || n >= ((int64_t)1 << 30)) return false;
+    const int64_t Kk = K > 0 ? K : 1;
+    if (m->dtype == CP_I64) {
+        if (m->p_i64[CP_P_LOCAL_NET] < 0 || m->p_i64[CP_P_REMOTE_NET] < 0) return false;
+        const u128 bound = model_amax128(m) * (u128)Kk + mag128(m->p_i64[CP_P_VERTEX]) * (u128)n + mag128(m->p_i64[CP_P_PIN]) * (u128)N +
+                           std::max(mag128(m->p_i64[CP_P_LOCAL_NET]), mag128(m->p_i64[CP_P_REMOTE_NET])) * (u128)N;
+        return bound < ((u128)1 << 60);
+    }
+    if (!(m->p_f64[CP_P_LOCAL_NET] >= 0) || !(m->p_f64[CP_P_REMOTE_NET] >= 0)) return false;
+    const double bound = model_amax_f64(m) * (double)Kk + std::fabs(m->p_f64[CP_P_VERTEX]) * (double)n + std::fabs(m->p_f64[CP_P_PIN]) * (double)N +
+                         std::max(m->p_f64[CP_P_LOCAL_NET], m->p_f64[CP_P_REMOTE_NET]) * (double)N;
+    return bound < 9007199254740992.0;       // 2^53
+}
+// Secondary, layer k: f(i, i', k) = const_k + (P_k[i'] - P_k[i])*(b_local_net - b_remote_net), P_k[c] the columns < c that hold a row of
+// part k, const_k = alpha_k + nv_k*b_vertex + w_k*b_pin + d_k*b_remote_net: the prefix-difference form of the edge-cut pair, so a layer
+// is one prefix-min scan for any sign of the two betas.  The scan reassociates the sums and is the sweep only while every value is the
+// true integer: B = K*max|alpha| + m*|b_vertex| + N*|b_pin| + N*max(|b_local_net|, |b_remote_net|) bounds the totals (m: the rows Pi
+// splits); the scan also forms S_k (at most 2B) and W - S_k (at most 3B), so an integral Float64 model needs 4B < 2^53 and Int64 B < 2^60,
+// as cut_scan_exact (plaid_cut.hip).
+inline bool plaid_scan_exact(const cp_model_t *m, int64_t mrows, int64_t N, int64_t K, int32_t combine, int32_t order)
+{
+    if (m->kind != CP_MODEL_SECONDARY || combine != CP_COMBINE_SUM || order != CP_ORDER_SPLITTER || !model_all_integral(m)) return false;
+    if (mrows < 0 || N < 0) return false;
+    const int64_t Kk = K > 0 ? K : 1;
+    if (m->dtype == CP_I64) {
+        const u128 bound = model_amax128(m) * (u128)Kk + mag128(m->p_i64[CP_P_VERTEX]) * (u128)mrows + mag128(m->p_i64[CP_P_PIN]) * (u128)N +
+                           std::max(mag128(m->p_i64[CP_P_LOCAL_NET]), mag128(m->p_i64[CP_P_REMOTE_NET])) * (u128)N;
+        return bound < ((u128)1 << 60);
+    }
+    const double B = model_amax_f64(m) * (double)Kk + std::fabs(m->p_f64[CP_P_VERTEX]) * (double)mrows + std::fabs(m->p_f64[CP_P_PIN]) * (double)N +
+                     std::max(std::fabs(m->p_f64[CP_P_LOCAL_NET]), std::fabs(m->p_f64[CP_P_REMOTE_NET])) * (double)N;
+    return 4.0 * B < 9007199254740992.0;
+}
+
 // host: build a DevModel from the C-ABI struct, uploading alpha_k / tables
 template <typename TC>
 struct HostModel {

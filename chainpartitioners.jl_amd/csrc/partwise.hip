@@ -4,6 +4,7 @@
 // pass finds the boundaries of the non-empty (k, j) pairs (= columns of A'), and a scatter writes pos', prm and
 // the part offsets pios.
 #include "csr.hpp"
+#include "partwise.hpp"
 #include <rocprim/rocprim.hpp>
 
 namespace cpk {
@@ -97,4 +98,34 @@ extern "C" int32_t cp_partwise(cp_csr_t A, int64_t K, const int64_t *asg, int64_
         *nprime_out = nprime;
         return CP_OK;
     } CP_CATCH_ALL
+}
+
+// the staging that bisect.hip and plaid_total.hip share: once per call
+int32_t cpk::partwise_stage(cp_csr_s *A, const cp_rowpart_t *Pi, PartwiseNeed need, PartwiseStage &S)
+{
+    hipStream_t s = A->stream;
+    const int64_t m = A->m, N = A->N, Kp = Pi->K;
+    std::vector<int64_t> asg((size_t)(m > 0 ? m : 1), 1);
+    if (Pi->asg) for (int64_t i = 0; i < m; i++) asg[(size_t)i] = Pi->asg[i];
+    else for (int64_t k = 1; k <= Kp; k++) for (int64_t i = Pi->spl[k - 1]; i <= Pi->spl[k] - 1; i++) { CP_REQUIRE(i >= 1 && i <= m, CP_EINVAL, "split vector out of range"); asg[(size_t)i - 1] = k; }
+    std::vector<int64_t> prm((size_t)(N > 0 ? N : 1)), ppos((size_t)N + 2), pidx((size_t)(N > 0 ? N : 1));
+    S.Kp = Kp; S.hpios.assign((size_t)Kp + 1, 0);
+    int64_t npr = 0;
+    int32_t rc = cp_partwise(A, Kp, asg.data(), &npr, S.hpios.data(), prm.data(), ppos.data(), pidx.data());
+    if (rc != CP_OK) return rc;
+    S.npr = npr;
+    S.pios.alloc((size_t)Kp + 1); S.prm.alloc((size_t)(npr > 0 ? npr : 1));
+    CP_HIP(hipMemcpyAsync(S.pios.p, S.hpios.data(), sizeof(int64_t) * (size_t)(Kp + 1), hipMemcpyHostToDevice, s));
+    if (npr > 0) CP_HIP(hipMemcpyAsync(S.prm.p, prm.data(), sizeof(int64_t) * (size_t)npr, hipMemcpyHostToDevice, s));
+    if (need == PW_PINS) {
+        S.ppos.alloc((size_t)npr + 1);
+        CP_HIP(hipMemcpyAsync(S.ppos.p, ppos.data(), sizeof(int64_t) * (size_t)(npr + 1), hipMemcpyHostToDevice, s));
+    } else if (need == PW_NETS) {
+        rc = cp_csr_create(m, npr, N, ppos.data(), pidx.data(), A->device, &S.Ap);
+        if (rc != CP_OK) { (void)hipStreamSynchronize(s); return rc; }
+        ensure_net_counter(S.Ap, S.lcn);
+        CP_HIP(hipStreamSynchronize(S.Ap->stream));      // (the partwise matrix has a stream of its own; its counter is read from A's)
+    }
+    CP_HIP(hipStreamSynchronize(s));
+    return CP_OK;
 }

@@ -9,11 +9,13 @@
 // array and the owner of each row:
 //   local nets of [p, r) for part k  = #{q in columns [p, r) : prev[q] < p  and  owner[row[q]] == k}
 //   secondary local count            = #{columns c in [p, r) that hold a row owned by k}  (prefix sums per part)
-// Entry points: oracle values for batches (objective / bounds / oracle_stripe) and the K-part DP by the general
-// O(n^2) candidate sweep (the costs depend on k through the ownership, so the O(n log^2 n) scheme does not apply).
+// Entry points: oracle values for batches (objective / bounds / oracle_stripe) and the K-part DP: the general O(n^2) candidate sweep
+// here (the costs depend on k through the ownership, so the link-streaming O(n log^2 n) scheme does not apply), or, for the total
+// objective inside the gates of model.hpp, the exact paths of plaid_total.hip (plaid_path decides).
 #include "csr.hpp"
 #include "model.hpp"
 #include "dp.hpp"
+#include "plaid_total.hpp"
 #include <vector>
 
 namespace cpk {
@@ -184,13 +186,14 @@ template <typename TC> static TC plaid_alpha(const cp_model_t *m, int64_t k)
 
 template <typename TC>
 int32_t run_plaid_dynamic(cp_csr_s *A, int64_t K, int32_t combine, int32_t order, const cp_model_t *mdl, const cp_rowpart_t *Pi,
-                          int64_t *spl_out)
+                          int64_t *spl_out, int64_t *ptr_tab, TC *cst_tab)
 {
     hipStream_t s = A->stream;
     int64_t n = A->n;
     bool sec = mdl->kind == CP_MODEL_SECONDARY;
     CP_REQUIRE(order == CP_ORDER_SPLITTER, CP_EUNSUPPORTED, "the plaid cost models need the part number: splitter loop order only");
-    CP_REQUIRE(n <= g_opt_brute_max_n, CP_EUNSUPPORTED, "plaid cost models run the O(n^2) device sweep: n too large");
+    const PlaidPath path = plaid_path(A, K, combine, order, mdl);     // (refuses n > brute_max_n where only the sweep is left)
+    const bool sweep = path == PlaidPath::Sweep;
     ensure_links(A);
     PlaidPart R;
     upload_part(A, Pi, sec, R);
@@ -199,36 +202,55 @@ int32_t run_plaid_dynamic(cp_csr_s *A, int64_t K, int32_t combine, int32_t order
     build_dev_model<TC>(mdl, HM, s);
     size_t n1 = (size_t)n + 1;
     DBuf<TC> cstA(n1), cstB(n1);
-    DBuf<int32_t> ptr((size_t)K * n1), flag((size_t)(n > 0 ? n : 1)), Lk(n1 + 1);
+    DBuf<int32_t> ptr((size_t)K * n1), flag, Lk;
     DBuf<int64_t> scratch;
     std::vector<int64_t> htpos;
-    if (sec) {                                                       // pins of every part of Pi: tpos = row pointer of A
+    std::unique_ptr<PlaidTotalRun> run;
+    if (!sweep) run = plaid_total_begin<TC>(A, path, mdl, HM.d, Pi, R);      // plaid_total.hip: partwise(A, Pi) staged once
+    else { flag.alloc((size_t)(n > 0 ? n : 1)); Lk.alloc(n1 + 1); }
+    if (sec && sweep) {                                              // pins of every part of Pi: tpos = row pointer of A
         htpos.resize((size_t)A->m + 1);
         CP_HIP(hipMemcpyAsync(htpos.data(), A->tpos.p, sizeof(int64_t) * (size_t)(A->m + 1), hipMemcpyDeviceToHost, s));
         CP_HIP(hipStreamSynchronize(s));
     }
+    std::vector<TC> hc;
+    std::vector<int32_t> hp;
     TC *prevc = cstA.p, *curc = cstB.p;
     for (int64_t k = 1; k <= K; k++) {
-        int64_t nvk = 0, wk = 0, dk = 0;
-        if (sec) {
-            if (n > 0) hipLaunchKernelGGL(k_sec_flags, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, n, (int32_t)k, A->pos.p, A->row.p, R.owner.p, flag.p);
-            exclusive_scan_i32_i32(flag.p, Lk.p, n, scratch, s);
-            int32_t tot = 0;
-            CP_HIP(hipMemcpyAsync(&tot, Lk.p + n, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-            CP_HIP(hipStreamSynchronize(s));
-            dk = tot;
-            int64_t s0 = R.hspl[(size_t)k - 1] - 1, s1 = R.hspl[(size_t)k] - 1;
-            nvk = s1 - s0; wk = htpos[(size_t)s1] - htpos[(size_t)s0];
-        }
         int32_t *pk = ptr.p + (size_t)(k - 1) * n1;
         bool last = (k == K) && K > 1;
         int64_t rlo = last ? n : 0;                                   // layer K: row n+1 only (DynamicSplitter.jl:34)
-        int64_t waves = cdiv(n - rlo + 1, (int64_t)64);
-        ProfScope ps(PROF_BRUTE, s, 0.0);
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_plaid_layer<TC>), dim3((unsigned)cdiv(waves, 4)), dim3(256), 0, s, n, rlo, n, sec ? 1 : 0, k == 1 ? 1 : 0,
-                           (int32_t)k, A->pos.p, A->row.p, A->next.p, R.owner.p, Lk.p, nvk, wk, dk, HM.d, plaid_alpha<TC>(mdl, k), combine,
-                           prevc, curc, pk);
-        CP_HIP(hipGetLastError());
+        if (!sweep) {
+            plaid_total_layer<TC>(run.get(), k, plaid_alpha<TC>(mdl, k), prevc, curc, pk, rlo, n);
+        } else {
+            int64_t nvk = 0, wk = 0, dk = 0;
+            if (sec) {
+                if (n > 0) hipLaunchKernelGGL(k_sec_flags, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, n, (int32_t)k, A->pos.p, A->row.p, R.owner.p, flag.p);
+                exclusive_scan_i32_i32(flag.p, Lk.p, n, scratch, s);
+                int32_t tot = 0;
+                CP_HIP(hipMemcpyAsync(&tot, Lk.p + n, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+                CP_HIP(hipStreamSynchronize(s));
+                dk = tot;
+                int64_t s0 = R.hspl[(size_t)k - 1] - 1, s1 = R.hspl[(size_t)k] - 1;
+                nvk = s1 - s0; wk = htpos[(size_t)s1] - htpos[(size_t)s0];
+            }
+            int64_t waves = cdiv(n - rlo + 1, (int64_t)64);
+            ProfScope ps(PROF_BRUTE, s, 0.0);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_plaid_layer<TC>), dim3((unsigned)cdiv(waves, 4)), dim3(256), 0, s, n, rlo, n, sec ? 1 : 0, k == 1 ? 1 : 0,
+                               (int32_t)k, A->pos.p, A->row.p, A->next.p, R.owner.p, Lk.p, nvk, wk, dk, HM.d, plaid_alpha<TC>(mdl, k), combine,
+                               prevc, curc, pk);
+            CP_HIP(hipGetLastError());
+        }
+        if (ptr_tab) {                                               // rows outside [rlo, n]: zeros(Ti) / fill(typemax), as run_cut_dynamic's tables
+            hc.resize(n1); hp.resize(n1);
+            CP_HIP(hipMemcpyAsync(hc.data(), curc, sizeof(TC) * n1, hipMemcpyDeviceToHost, s));
+            CP_HIP(hipMemcpyAsync(hp.data(), pk, sizeof(int32_t) * n1, hipMemcpyDeviceToHost, s));
+            CP_HIP(hipStreamSynchronize(s));
+            for (int64_t r = 0; r <= n; r++) {
+                ptr_tab[(size_t)(k - 1) * n1 + (size_t)r] = r >= rlo ? (int64_t)hp[(size_t)r] + 1 : 0;
+                cst_tab[(size_t)(k - 1) * n1 + (size_t)r] = r >= rlo ? hc[(size_t)r] : CostTraits<TC>::typemax();
+            }
+        }
         std::swap(prevc, curc);
     }
     std::vector<int64_t> spl((size_t)K + 1);
@@ -246,7 +268,7 @@ int32_t run_plaid_dynamic(cp_csr_s *A, int64_t K, int32_t combine, int32_t order
 
 template int32_t run_plaid_eval<int64_t>(cp_csr_s *, const cp_model_t *, const cp_rowpart_t *, int64_t, const int64_t *, const int64_t *, const int64_t *, int64_t *);
 template int32_t run_plaid_eval<double>(cp_csr_s *, const cp_model_t *, const cp_rowpart_t *, int64_t, const int64_t *, const int64_t *, const int64_t *, double *);
-template int32_t run_plaid_dynamic<int64_t>(cp_csr_s *, int64_t, int32_t, int32_t, const cp_model_t *, const cp_rowpart_t *, int64_t *);
-template int32_t run_plaid_dynamic<double>(cp_csr_s *, int64_t, int32_t, int32_t, const cp_model_t *, const cp_rowpart_t *, int64_t *);
+template int32_t run_plaid_dynamic<int64_t>(cp_csr_s *, int64_t, int32_t, int32_t, const cp_model_t *, const cp_rowpart_t *, int64_t *, int64_t *, int64_t *);
+template int32_t run_plaid_dynamic<double>(cp_csr_s *, int64_t, int32_t, int32_t, const cp_model_t *, const cp_rowpart_t *, int64_t *, int64_t *, double *);
 
 }  // namespace cpk

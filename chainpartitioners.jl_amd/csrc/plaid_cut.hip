@@ -19,15 +19,6 @@ namespace cpk {
 
 int64_t g_cut_scan_layers = 0;
 
-// what a kernel needs to evaluate the cost of part k
-template <typename TC>
-struct CutLayer {
-    int32_t secondary;
-    TC alpha;                  // alpha_k
-    int64_t nvk, wk;           // secondary: vertices / pins of part k of Pi
-    TC p[5];
-};
-
 template <typename TC>
 __device__ __forceinline__ TC cut_f(const CutLayer<TC> &Y, const int64_t *__restrict__ pos, const int32_t *__restrict__ Lc, int64_t p, int64_t r)
 {
@@ -319,6 +310,22 @@ __global__ void __launch_bounds__(256) k_cut_scan_finish(int64_t n1, CutLayer<TC
     ptr[r] = i;
 }
 
+// one layer by the scan, three launches: cst[r] = constk + S_k[r] + min over p <= r of W[p] - S_k[p], ptr[r] the largest minimiser.
+// Also the secondary connectivity cost's layer (plaid_total.hip), whose S_k has the secondary edge-cut form over another prefix count.
+template <typename TC>
+void cut_scan_layer(hipStream_t s, int64_t n1, const CutLayer<TC> &Y, TC constk, const int64_t *pos, const int32_t *Lc, const TC *W,
+                    CutScanWork<TC> &ws, TC *cst, int32_t *ptr)
+{
+    const int64_t nb = cdiv(n1, (int64_t)CUT_TILE);
+    ws.tv.ensure((size_t)n1); ws.ti.ensure((size_t)n1); ws.av.ensure((size_t)nb); ws.ai.ensure((size_t)nb);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cut_scan_tiles<TC>), dim3((unsigned)nb), dim3(CUT_T), 0, s, n1, Y, pos, Lc, W, ws.tv.p, ws.ti.p, ws.av.p, ws.ai.p);
+    if (nb > 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cut_scan_aggs<TC>), dim3(1), dim3(1024), 0, s, nb, ws.av.p, ws.ai.p);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cut_scan_finish<TC>), dim3((unsigned)cdiv(n1, 256)), dim3(256), 0, s, n1, Y, constk, pos, Lc, ws.tv.p, ws.ti.p,
+                       ws.av.p, ws.ai.p, cst, ptr);
+}
+template void cut_scan_layer<int64_t>(hipStream_t, int64_t, const CutLayer<int64_t> &, int64_t, const int64_t *, const int32_t *, const int64_t *, CutScanWork<int64_t> &, int64_t *, int32_t *);
+template void cut_scan_layer<double>(hipStream_t, int64_t, const CutLayer<double> &, double, const int64_t *, const int32_t *, const double *, CutScanWork<double> &, double *, int32_t *);
+
 // The scan is the sweep only while no sum rounds or wraps.  model_exact_on bounds every total by B = K*max|alpha| + n*|b_vertex| +
 // N*max(|b_self_pin|, |b_cut_pin|); the scan also forms S_k (at most 2B: the secondary one is a difference of two products) and
 // W - S_k (at most 3B), so Float64 needs 4B < 2^53.  Int64: B < 2^60 keeps 3B below 2^63.
@@ -355,10 +362,9 @@ int32_t run_cut_dynamic(cp_csr_s *A, int64_t K, int32_t combine, int32_t order, 
     upload_part(A, Pi, sec, R);
     CP_REQUIRE(K <= R.K, CP_EINVAL, "the plaid edge-cut models are evaluated for parts 1..K of Pi");
     const size_t n1 = (size_t)n + 1;
-    const int64_t nb = cdiv((int64_t)n1, (int64_t)CUT_TILE);
-    DBuf<TC> cstA(n1), cstB(n1), tv, av;
-    DBuf<int32_t> ptr((size_t)K * n1), flag((size_t)(N > 0 ? N : 1)), Lq((size_t)N + 1), Lc(n1), ti, ai;
-    if (scan) { tv.alloc(n1); ti.alloc(n1); av.alloc((size_t)nb); ai.alloc((size_t)nb); }
+    DBuf<TC> cstA(n1), cstB(n1);
+    DBuf<int32_t> ptr((size_t)K * n1), flag((size_t)(N > 0 ? N : 1)), Lq((size_t)N + 1), Lc(n1);
+    CutScanWork<TC> ws;
     DBuf<int64_t> scratch;
     std::vector<int64_t> htpos;
     if (sec) {                                                       // pins of every part of Pi: tpos = row pointer of A
@@ -391,11 +397,7 @@ int32_t run_cut_dynamic(cp_csr_s *A, int64_t K, int32_t combine, int32_t order, 
         } else if (scan) {
             const TC constk = sec ? cadd(cadd(Y.alpha, cmulc(Y.nvk, Y.p[CP_P_VERTEX])), cmulc(Y.wk, Y.p[CP_P_CUT_PIN])) : Y.alpha;
             ProfScope ps(PROF_SCAN, s, 0.0);
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cut_scan_tiles<TC>), dim3((unsigned)nb), dim3(CUT_T), 0, s, (int64_t)n1, Y, A->pos.p, Lc.p, prevc,
-                               tv.p, ti.p, av.p, ai.p);
-            if (nb > 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cut_scan_aggs<TC>), dim3(1), dim3(1024), 0, s, nb, av.p, ai.p);
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cut_scan_finish<TC>), dim3((unsigned)cdiv((int64_t)n1, 256)), dim3(256), 0, s, (int64_t)n1, Y, constk,
-                               A->pos.p, Lc.p, tv.p, ti.p, av.p, ai.p, curc, pk);
+            cut_scan_layer<TC>(s, (int64_t)n1, Y, constk, A->pos.p, Lc.p, prevc, ws, curc, pk);
             g_cut_scan_layers++;
         } else {
             const int64_t waves = cdiv(n - rlo + 1, (int64_t)64);

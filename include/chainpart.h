@@ -278,7 +278,8 @@ int32_t cp_partition_equi(int64_t n, int64_t K, int64_t *spl_out /* K+1 */);
 int32_t cp_pack_equi(int64_t n, int64_t w, int64_t *spl_out /* cld(n,w)+1 */, int64_t *K_out);
 
 /* full (n+1) x K tables of the splitter-order DP, column-major like the reference's cst/ptr
- * (DynamicSplitter.jl:23-24), for table-level parity tests.  Layer K holds row n+1 only. */
+ * (DynamicSplitter.jl:23-24), for table-level parity tests.  Layer K holds row n+1 only.  Pi is read by the four plaid kinds (8 / 9 and
+ * 13 / 14), on whichever of their paths runs. */
 int32_t cp_dynamic_tables(cp_csr_t csr, int64_t K, int32_t combine, const cp_model_t *model,
                           const cp_rowpart_t *Pi, int64_t *ptr_out, int64_t *cst_i64, double *cst_f64);
 
@@ -356,7 +357,9 @@ int32_t cp_reset_stream(cp_csr_t csr);
  * cut column ran (a layer of one row counts).  "budget_layers" -- DP layers >= 2 of the total objective under a pin or work budget that
  * csrc/dp_total_budget.hip ran (its profile slot is "dp_budget").  "sym_total_layers" -- DP layers >= 2 of the total objective of a
  * symmetric model (kinds 10 - 12) that the divide and conquer of csrc/sym_total.hip ran (its profile slot is "dp_sym_total"; a layer of
- * one row counts).  All of these are reset when "poison" is switched on and by cp_set_option("stat_reset", 1); reading
+ * one row counts).  "plaid_total_layers" / "plaid_scan_layers" -- DP layers >= 2 of the total objective of the primary / secondary plaid
+ * connectivity model (kinds 8 / 9) that the rectangle engine / the prefix-min scan of csrc/plaid_total.hip ran (profile slot
+ * "dp_plaid_total" for both; the candidate sweep keeps "dp_brute" and counts none).  All of these are reset when "poison" is switched on and by cp_set_option("stat_reset", 1); reading
  * changes nothing. */
 int32_t cp_get_stat(const char *name, int64_t *out);
 /* Test entry: the launch that ends the counting phase of a DP round, on host arrays.  Exclusive scans of a[0 .. na) and (two != 0)
@@ -441,6 +444,12 @@ int32_t cp_test_own_pack(cp_csr_t csr, int32_t *vpk_out, int32_t *vbase_out, int
  * sweep is allowed, the measured crossover: 10240; where n > "brute_max_n" it runs from n = 1024 on instead of refusing), "sym_total_batch" (1,
  * default: the rectangles of one depth of its column tree share one launch sequence; 0: one sequence per rectangle), "sym_total_scan_cells" /
  * "sym_total_scan_cols" / "sym_total_stair_cols" (that path's limits, as the three budget options: 2^20 / 1024 / 1024; at least 1),
+ * "plaid_total" (1, default: the total objective of the plaid connectivity pair in splitter order runs csrc/plaid_total.hip at any n --
+ * the primary model with b_local_net >= 0 and b_remote_net >= 0 on the rectangle engine, the secondary model on the prefix-min scan, both
+ * with integer-valued parameters and exact totals; 0: the candidate sweep, n <= "brute_max_n"), "plaid_total_min_n" / "plaid_scan_min_n"
+ * (the smallest n the primary / the secondary path takes while the sweep is allowed: 1024 both, the first measured size; where n >
+ * "brute_max_n" the primary runs from n = 1024 on and the secondary at any n instead of refusing), "plaid_total_scan_cells" /
+ * "plaid_total_scan_cols" / "plaid_total_stair_cols" (the primary path's limits, as the three budget options: 2^20 / 1024 / 1024; at least 1),
  * "rcm_narrow" (cp_rcm: BFS levels of at most this many
  * vertices are walked by one workgroup, level after level in one launch; 0: every level by grid kernels; a value beyond the walker's
  * capacity of 1024 vertices: whenever the level fits), "greedy_lds_parts" (cp_partition_greedy_bottleneck: the walk keeps the part costs and counts in
