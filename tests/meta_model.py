@@ -2,7 +2,7 @@
 straight from their definitions, and optimality certificates computed on the host in O(nnz).  Pure numpy; shares no code with
 oracle/, with the layer functions of tests/brute.py or with the kernels.
 
-  transforms of a pattern   relabel_rows, mirror_columns, reverse_rows, shift_rows
+  transforms of a pattern   relabel_rows, mirror_columns, reverse_rows, shift_rows, mirror_both
   transforms of a model     scaled, shifted
   definition-level values   pins / nets / selfnets / span of a column range by np.unique, part_cost, total, bottleneck
   pair_optimal              every interior boundary is the best place between its two neighbours (necessary for a total-cost optimum)
@@ -12,8 +12,15 @@ oracle/, with the layer functions of tests/brute.py or with the kernels.
 
 Split vectors are 1-based as the library returns them (part k = columns spl[k] : spl[k + 1] - 1); everything inside works on 0-based
 boundary positions.  The models are told apart by their class names and read through their attributes: AffineWorkModel,
-AffineConnectivityModel, AffineHyperedgeCutModel, AffineEnvelopeModel, and -- with a MapPartition Pi of the rows -- the primary
-connectivity and primary edge-cut models, whose part number k (1-based) enters the counts.  No per-part alpha."""
+AffineConnectivityModel, AffineHyperedgeCutModel, AffineEnvelopeModel; the three symmetric models on a square pattern (dianet: the rows
+of a column range united with its own indices, selfpin: the entries of its diagonal block); and -- with a partition Pi of the rows, a
+MapPartition or a SplitPartition -- the primary connectivity and primary edge-cut models and the secondary connectivity model, whose
+part number k (1-based) enters the counts.  No per-part alpha.
+
+What referees what: part_cost is the definition by np.unique / set operations; left_costs / right_costs are its window forms, checked
+against part_cost and against the dense tables of brute.py, sym_model.py and plaid_total_model.py at small n by
+tests/test_meta_model.py; at n = 4 099 and 70 001 tests/test_gpu_metamorphic.py holds the library's split vectors to the invariances
+and to pair_slack == 0 computed here alone."""
 import numpy as np
 
 INFEASIBLE = 1 << 62
@@ -61,6 +68,12 @@ def shift_rows(A, d):
     return _pattern(A, A.m + d, A.n, cols, rows + d)
 
 
+def mirror_both(A):
+    """row i -> n + 1 - i and column j -> n + 1 - j of a square pattern: dianet, selfpin and net of a range become those of its mirror"""
+    cols, rows = _entries(A)
+    return _pattern(A, A.m, A.n, A.n - 1 - cols, A.m - 1 - rows)
+
+
 def mirror_split(spl, n):
     """the split vector of the mirrored parts on mirror_columns(A)"""
     return (n + 2 - np.asarray(spl, dtype=np.int64))[::-1].copy()
@@ -81,7 +94,16 @@ def shifted(mdl, a):
 # ---------------------------------------------------------------- values from the definition
 def _kind(mdl):
     return {"AffineWorkModel": "work", "AffineConnectivityModel": "conn", "AffineHyperedgeCutModel": "hcut", "AffineEnvelopeModel": "env",
-            "AffinePrimaryConnectivityModel": "prim", "AffinePrimaryEdgeCutModel": "pcut"}[type(mdl).__name__]
+            "AffinePrimaryConnectivityModel": "prim", "AffinePrimaryEdgeCutModel": "pcut", "AffineSecondaryConnectivityModel": "sec",
+            "AffineSymmetricConnectivityModel": "symc", "AffineMonotonizedSymmetricConnectivityModel": "msym",
+            "AffineSymmetricEdgeCutModel": "scut"}[type(mdl).__name__]
+
+
+def row_owner(Pi, m):
+    """the 1-based part of every row under a MapPartition or a SplitPartition"""
+    if hasattr(Pi, "asg"):
+        return np.asarray(Pi.asg, dtype=np.int64)
+    return np.searchsorted(np.asarray(Pi.spl, dtype=np.int64), np.arange(1, m + 1), side="right").astype(np.int64)
 
 
 def _range_rows(A, j, jp):
@@ -110,6 +132,22 @@ def span(A, j, jp):
     return int(r.max() - r.min()) if r.size else 0
 
 
+def dianets(A, j, jp):
+    """the rows of the columns j : j' - 1 united with j : j' - 1 themselves"""
+    return int(np.union1d(_range_rows(A, j, jp), np.arange(j, jp)).size)
+
+
+def selfpins(A, j, jp):
+    """the entries of the block A[j : j' - 1, j : j' - 1]"""
+    r = _range_rows(A, j, jp)
+    return int(((r >= j) & (r < jp)).sum())
+
+
+def overpins(A, j, jp, delta):
+    deg = np.diff(np.asarray(A.colptr, dtype=np.int64))[j - 1:jp - 1]
+    return int(np.maximum(deg - int(delta), 0).sum())
+
+
 def split_selfnets(A, spl):
     """selfnets of every part of a split at once: the rows whose first and last column lie in one part, counted per part (the
     definition of selfnets(), one O(nnz) pass per part, is too slow for the thousands of parts a narrow chunker makes)"""
@@ -124,9 +162,23 @@ def split_selfnets(A, spl):
 def part_cost(A, mdl, j, jp, k=None, Pi=None, n_self=None):
     """f(j, j', k) from the definition, in Python numbers (n_self: the part's self nets where split_selfnets has counted them)"""
     kind = _kind(mdl)
+    if kind == "sec":                                              # the rows, pins and columns of part k; local: its columns inside j : j' - 1
+        own = row_owner(Pi, A.m)
+        cols, rows = _entries(A)
+        mine = np.unique(cols[own[rows] == k]) + 1
+        inside = int(((mine >= j) & (mine < jp)).sum())
+        return (mdl.alpha + int((own == k).sum()) * mdl.beta_vertex + int((own[rows] == k).sum()) * mdl.beta_pin
+                + inside * mdl.beta_local_net + (int(mine.size) - inside) * mdl.beta_remote_net)
     v = mdl.alpha + (jp - j) * mdl.beta_vertex
+    if kind == "msym":
+        return v + overpins(A, j, jp, mdl.delta_pins) * mdl.beta_over_pin + dianets(A, j, jp) * mdl.beta_dia_net
+    if kind == "scut":
+        return v + selfpins(A, j, jp) * mdl.beta_self_pin + (pins(A, j, jp) - selfpins(A, j, jp)) * mdl.beta_cut_pin
     if kind != "pcut":
         v = v + pins(A, j, jp) * mdl.beta_pin
+    if kind == "symc":
+        rem = dianets(A, j, jp) - (jp - j)
+        return v + (nets(A, j, jp) - rem) * mdl.beta_local_net + rem * mdl.beta_remote_net
     if kind == "conn":
         v = v + nets(A, j, jp) * mdl.beta_net
     elif kind == "hcut":
@@ -135,10 +187,10 @@ def part_cost(A, mdl, j, jp, k=None, Pi=None, n_self=None):
     elif kind == "env":
         v = v + span(A, j, jp) * mdl.beta_net
     elif kind == "prim":
-        own = np.asarray(Pi.asg)[np.unique(_range_rows(A, j, jp)) - 1] == k
+        own = row_owner(Pi, A.m)[np.unique(_range_rows(A, j, jp)) - 1] == k
         v = v + int(own.sum()) * mdl.beta_local_net + int((~own).sum()) * mdl.beta_remote_net
     elif kind == "pcut":
-        own = np.asarray(Pi.asg)[_range_rows(A, j, jp) - 1] == k
+        own = row_owner(Pi, A.m)[_range_rows(A, j, jp) - 1] == k
         v = v + int(own.sum()) * mdl.beta_self_pin + int((~own).sum()) * mdl.beta_cut_pin
     return v
 
@@ -212,16 +264,57 @@ def _below(x, lo, hi):
 def _affine(ix, mdl, nv, npins, terms):
     dt = np.int64 if mdl.dtype == 0 else np.float64
     v = dt(mdl.alpha) + nv.astype(dt) * dt(mdl.beta_vertex)
-    if _kind(mdl) != "pcut":
+    if _kind(mdl) not in ("pcut", "msym", "scut", "sec"):
         v = v + npins.astype(dt) * dt(mdl.beta_pin)
     for count, beta in terms:
         v = v + count.astype(dt) * dt(beta)
     return v
 
 
+def _sym_terms(ix, mdl, a, b, t, lo, hi, entered, diag_key, count):
+    """the terms of a symmetric model over the windows [lo, hi) inside [a, b).  entered: the one entry per row that brings the row in
+    (its first at or after a / its last before b), diag_key: min or max, the rule that joins a row's own diagonal position to that entry,
+    count: keys -> how many count at every t"""
+    pos, kind = ix.pos, _kind(mdl)
+    sl = slice(pos[a], pos[b])
+    i, c = ix.rows[sl], ix.cols[sl]
+    if kind == "scut":
+        ok = (i >= a) & (i < b)                                    # an entry lies in the block once both its indices do
+        own = count(diag_key(i[ok], c[ok]))
+        return [(own, mdl.beta_self_pin), (pos[hi] - pos[lo] - own, mdl.beta_cut_pin)]
+    key = np.arange(a, b, dtype=np.int64)                          # the rows a .. b - 1 count from their own position on ...
+    ie, ce = i[entered], c[entered]
+    inside = (ie >= a) & (ie < b)
+    key[ie[inside] - a] = diag_key(ie[inside], ce[inside])         # ... or from the entry that brings them in, whichever comes first
+    dia = count(np.concatenate([key, ce[~inside]]))
+    if kind == "msym":
+        over = np.concatenate([[0], np.cumsum(np.maximum(np.diff(pos) - int(mdl.delta_pins), 0))])
+        return [(over[hi] - over[lo], mdl.beta_over_pin), (dia, mdl.beta_dia_net)]
+    rem = dia - (hi - lo)
+    return [(count(ce) - rem, mdl.beta_local_net), (rem, mdl.beta_remote_net)]
+
+
+def _sec_parts(ix, mdl, k, Pi):
+    """the secondary model's part k: the flag of every column that holds one of its rows, and its constant terms"""
+    own = row_owner(Pi, ix.m)
+    mine = own[ix.rows] == k
+    has = np.bincount(ix.cols[mine], minlength=ix.n) > 0
+    dt = np.int64 if mdl.dtype == 0 else np.float64
+    const = dt(mdl.alpha) + dt(int((own == k).sum())) * dt(mdl.beta_vertex) + dt(int(mine.sum())) * dt(mdl.beta_pin)
+    return has, int(has.sum()), const, dt
+
+
 def left_costs(ix, mdl, a, b, k=None, Pi=None):
     """f of the columns [a, t) for t = a .. b (0-based positions)"""
     pos, kind = ix.pos, _kind(mdl)
+    if kind in ("symc", "msym", "scut"):
+        t = np.arange(a, b + 1, dtype=np.int64)
+        terms = _sym_terms(ix, mdl, a, b, t, a, t, ix.prev[pos[a]:pos[b]] < a, np.maximum if kind == "scut" else np.minimum, lambda x: _below(x, a, b))
+        return _affine(ix, mdl, t - a, pos[t] - pos[a], terms)
+    if kind == "sec":
+        has, d, const, dt = _sec_parts(ix, mdl, k, Pi)
+        loc = np.concatenate([[0], np.cumsum(has[a:b])]).astype(np.int64)
+        return const + loc.astype(dt) * dt(mdl.beta_local_net) + (d - loc).astype(dt) * dt(mdl.beta_remote_net)
     sl = slice(pos[a], pos[b])
     t = np.arange(a, b + 1, dtype=np.int64)
     c = ix.cols[sl]
@@ -240,10 +333,10 @@ def left_costs(ix, mdl, a, b, k=None, Pi=None):
         hi = np.concatenate([[-1], np.maximum.accumulate(ix.colhi[a:b])])
         terms = [(np.maximum(hi - lo, 0), mdl.beta_net)]
     elif kind == "prim":
-        loc = _below(c[new & (np.asarray(Pi.asg)[ix.rows[sl]] == k)], a, b)
+        loc = _below(c[new & (row_owner(Pi, ix.m)[ix.rows[sl]] == k)], a, b)
         terms = [(loc, mdl.beta_local_net), (net - loc, mdl.beta_remote_net)]
     elif kind == "pcut":
-        own = _below(c[np.asarray(Pi.asg)[ix.rows[sl]] == k], a, b)
+        own = _below(c[row_owner(Pi, ix.m)[ix.rows[sl]] == k], a, b)
         terms = [(own, mdl.beta_self_pin), (pos[t] - pos[a] - own, mdl.beta_cut_pin)]
     return _affine(ix, mdl, t - a, pos[t] - pos[a], terms)
 
@@ -251,6 +344,15 @@ def left_costs(ix, mdl, a, b, k=None, Pi=None):
 def right_costs(ix, mdl, a, b, k=None, Pi=None):
     """f of the columns [t, b) for t = a .. b"""
     pos, kind = ix.pos, _kind(mdl)
+    if kind in ("symc", "msym", "scut"):
+        t = np.arange(a, b + 1, dtype=np.int64)
+        at_least = lambda x: x.size - _below(x, a, b)
+        terms = _sym_terms(ix, mdl, a, b, t, t, b, ix.next[pos[a]:pos[b]] >= b, np.minimum if kind == "scut" else np.maximum, at_least)
+        return _affine(ix, mdl, b - t, pos[b] - pos[t], terms)
+    if kind == "sec":
+        has, d, const, dt = _sec_parts(ix, mdl, k, Pi)
+        loc = np.concatenate([np.cumsum(has[a:b][::-1])[::-1], [0]]).astype(np.int64)
+        return const + loc.astype(dt) * dt(mdl.beta_local_net) + (d - loc).astype(dt) * dt(mdl.beta_remote_net)
     sl = slice(pos[a], pos[b])
     t = np.arange(a, b + 1, dtype=np.int64)
     c = ix.cols[sl]
@@ -271,10 +373,10 @@ def right_costs(ix, mdl, a, b, k=None, Pi=None):
         hi = np.concatenate([np.maximum.accumulate(ix.colhi[a:b][::-1])[::-1], [-1]])
         terms = [(np.maximum(hi - lo, 0), mdl.beta_net)]
     elif kind == "prim":
-        loc = at_least(c[end & (np.asarray(Pi.asg)[ix.rows[sl]] == k)])
+        loc = at_least(c[end & (row_owner(Pi, ix.m)[ix.rows[sl]] == k)])
         terms = [(loc, mdl.beta_local_net), (net - loc, mdl.beta_remote_net)]
     elif kind == "pcut":
-        own = at_least(c[np.asarray(Pi.asg)[ix.rows[sl]] == k])
+        own = at_least(c[row_owner(Pi, ix.m)[ix.rows[sl]] == k])
         terms = [(own, mdl.beta_self_pin), (pos[b] - pos[t] - own, mdl.beta_cut_pin)]
     return _affine(ix, mdl, b - t, pos[b] - pos[t], terms)
 

@@ -1,6 +1,7 @@
-"""Executable statement (numpy / plain Python, small n) of csrc/plaid_total.hip: the cost tables of the plaid connectivity pair from
+"""Executable statement (numpy / plain Python) of csrc/plaid_total.hip: the cost tables of the plaid connectivity pair from
 their DEFINITION (the rows of a column range, owners from Pi), the primary layer as the unconstrained two-staircase layer of
-tests/budget_model.py, the secondary layer as a prefix-min scan, and the literal K-layer DP both are compared with.
+tests/budget_model.py, the secondary layer as a prefix-min scan, and the literal K-layer DP both are compared with (small n); PrimaryCols and Secondary.column give rows and columns of the same cost
+tables from the entry list alone, at any n, for the audits of tests/bellman_audit.py.
 
 0-based indices as in budget_model: row r = j' - 1, candidate p = j - 1, F[p, r] = cost of the columns [p, r) as part k."""
 import numpy as np
@@ -96,6 +97,13 @@ class Secondary:
         Pk = self.prefix(1)
         return _apply(mdl, 1, np.full_like(Pk, self.nv[1]), np.full_like(Pk, self.w[1]), Pk, self.d[1] - Pk)
 
+    def column(self, mdl, jp, k):
+        """f(j, j', k) for j = 1 .. j' without the table: the columns [j - 1, j' - 1) that hold a row of part k are local, the part's
+        other columns remote"""
+        Pk = self.prefix(k)
+        L = Pk[jp - 1] - Pk[:jp]
+        return _apply(mdl, k, np.full_like(L, self.nv[k]), np.full_like(L, self.w[k]), L, self.d[k] - L)
+
     def table(self, mdl, k):
         Pk = self.prefix(k)
         L = Pk[None, :] - Pk[:, None]
@@ -147,3 +155,55 @@ def unravel(ptrs, n):
 def launch_cap(n, stair):
     """launches of the profile slot for one layer >= 2 of the primary path: the plan's D (4 L + 2) + 1 and the preparation steps"""
     return stm.launch_cap(n, stair) + PREP_LAUNCHES
+
+
+class PrimaryCols:
+    """f(j, j', k) of the primary model along a row (j fixed) or a column (j' fixed) of its cost table from the entry list alone, so at
+    any n: one stable sort of the entries by row gives every entry the previous and the next column that holds its row, and a call
+    reads the entries of its window's columns once.  nets(p, r) counts the rows whose last column below r is >= p (for a fixed p: whose
+    first column >= p is below r); local(p, r, k) those of them that Pi gives to part k.  Pi: a MapPartition or a SplitPartition
+    (through owners); a part number past Pi.K owns no row.  The element type and the operand order are _apply's."""
+
+    def __init__(self, A, Pi, mdl=None):
+        self.A, self.Pi, self.mdl, self.n = A, Pi, mdl, A.n
+        self.own = owners(Pi, A.m)
+        self.pos = np.asarray(A.colptr, dtype=np.int64) - 1
+        self.rows = np.asarray(A.rowval, dtype=np.int64) - 1
+        self.cols = np.repeat(np.arange(A.n, dtype=np.int64), np.diff(self.pos))
+        nnz = self.rows.size
+        order = np.argsort(self.rows, kind="stable")
+        rs, cs = self.rows[order], self.cols[order]
+        same = rs[1:] == rs[:-1]
+        self.prev = np.full(nnz, -1, dtype=np.int64); self.prev[order[1:][same]] = cs[:-1][same]
+        self.next = np.full(nnz, A.n, dtype=np.int64); self.next[order[:-1][same]] = cs[1:][same]
+
+    def counts_col(self, r, k, p0=0):
+        """(nets, local of part k) of the columns [p, r) for p = p0 .. r"""
+        sl = slice(self.pos[p0], self.pos[r])
+        last = self.next[sl] >= r
+        c, mine = self.cols[sl][last], self.own[self.rows[sl][last]] == k
+        at_least = lambda x: np.cumsum(np.bincount(x - p0, minlength=r - p0 + 1)[::-1])[::-1].astype(np.int64)
+        return at_least(c), at_least(c[mine])
+
+    def counts_row(self, p, k, r1=None):
+        """the same for the columns [p, r), r = p .. r1"""
+        r1 = self.n if r1 is None else r1
+        sl = slice(self.pos[p], self.pos[r1])
+        first = self.prev[sl] < p
+        c, mine = self.cols[sl][first], self.own[self.rows[sl][first]] == k
+        below = lambda x: np.concatenate([[0], np.cumsum(np.bincount(x - p, minlength=r1 - p))]).astype(np.int64)
+        return below(c), below(c[mine])
+
+    def row(self, j, k, upto=None):
+        """f(j, j', k) for j' = j .. upto (n + 1 by default)"""
+        p, r1 = j - 1, (self.n if upto is None else upto - 1)
+        t = np.arange(p, r1 + 1, dtype=np.int64)
+        nets, loc = self.counts_row(p, k, r1)
+        return _apply(self.mdl, k, t - p, self.pos[t] - self.pos[p], loc, nets - loc)
+
+    def column(self, jp, k, frm=1):
+        """f(j, j', k) for j = frm .. j'"""
+        r, p0 = jp - 1, frm - 1
+        t = np.arange(p0, r + 1, dtype=np.int64)
+        nets, loc = self.counts_col(r, k, p0)
+        return _apply(self.mdl, k, r - t, self.pos[r] - self.pos[t], loc, nets - loc)

@@ -388,3 +388,128 @@ def lazy_bisect(A, K, mdl, eps):
         else:
             c_lo = c
     return np.array(spl_hi, dtype=np.int64), probes
+
+
+# ---------------------------------------------------------------- rows and columns of the tables without a dense table
+class Sym:
+    """f(j, j', k) of one symmetric model along a row (j fixed) or a column (j' fixed) of its cost table, and the three counts in
+    the same two forms, from the entry list alone: any n.  One stable sort of the entries by row gives every entry the previous
+    and the next column that holds its row; a call then reads the entries of its window's columns once, O(nnz of the window +
+    its width).  0-based boundaries inside: p = j - 1, r = j' - 1, the part is the columns [p, r).
+
+      net(p, r)      row i counts iff its last column below r is >= p (fixed r), iff its first column >= p is < r (fixed p)
+      dianet(p, r)   row i counts iff max(last column < r that holds i, i if i < r) >= p: the diagonal joins the last column.
+                     For a fixed p: iff min(first column >= p that holds i, i if i >= p) < r
+      selfpin(p, r)  the entries (i, c) with min(i, c) >= p and max(i, c) < r
+
+    so for a fixed end every count is one bincount of a key per row (or entry) and one cumulative sum, reversed where the fixed
+    end is r.  The element type, the operand order and the alpha_k rule are cost_table's."""
+
+    def __init__(self, A, mdl=None):
+        assert A.m == A.n
+        self.A, self.mdl, self.n = A, mdl, A.n
+        self.pos = (np.asarray(A.colptr, dtype=np.int64) - 1)
+        self.rows = np.asarray(A.rowval, dtype=np.int64) - 1
+        self.cols = np.repeat(np.arange(A.n, dtype=np.int64), np.diff(self.pos))
+        nnz, n = self.rows.size, A.n
+        order = np.argsort(self.rows, kind="stable")               # by (row, column): columns ascend in storage order
+        rs, cs = self.rows[order], self.cols[order]
+        same = rs[1:] == rs[:-1]
+        self.prev = np.full(nnz, -1, dtype=np.int64); self.prev[order[1:][same]] = cs[:-1][same]
+        self.next = np.full(nnz, n, dtype=np.int64); self.next[order[:-1][same]] = cs[1:][same]
+        self.op = None if mdl is None or not hasattr(mdl, "delta_pins") else overpos(A, mdl.delta_pins)
+
+    # ---- counts, one fixed end.  *_col(r, p0): p = p0 .. r;  *_row(p, r1): r = p .. r1
+    def _window(self, a, b):
+        sl = slice(self.pos[a], self.pos[b])
+        return self.rows[sl], self.cols[sl], self.prev[sl], self.next[sl]
+
+    @staticmethod
+    def _at_least(keys, lo, hi):
+        """out[t - lo] = #{keys >= t} for t = lo .. hi, keys in [lo, hi)"""
+        h = np.bincount(keys - lo, minlength=hi - lo + 1)
+        return np.cumsum(h[::-1])[::-1].astype(np.int64)
+
+    @staticmethod
+    def _below(keys, lo, hi):
+        """out[t - lo] = #{keys < t} for t = lo .. hi, keys in [lo, hi)"""
+        return np.concatenate([[0], np.cumsum(np.bincount(keys - lo, minlength=hi - lo))]).astype(np.int64)
+
+    def net_col(self, r, p0=0):
+        i, c, _, nx = self._window(p0, r)
+        return self._at_least(c[nx >= r], p0, r)
+
+    def net_row(self, p, r1=None):
+        r1 = self.n if r1 is None else r1
+        i, c, pv, _ = self._window(p, r1)
+        return self._below(c[pv < p], p, r1)
+
+    def dianet_col(self, r, p0=0):
+        i, c, _, nx = self._window(p0, r)
+        last = nx >= r                                             # the last entry of its row below column r: one per row
+        i, c = i[last], c[last]
+        key = np.arange(p0, r, dtype=np.int64)                     # rows p0 .. r - 1: at least their own diagonal position
+        inside = (i >= p0) & (i < r)
+        key[i[inside] - p0] = np.maximum(i[inside], c[inside])
+        return self._at_least(np.concatenate([key, c[~inside]]), p0, r)
+
+    def dianet_row(self, p, r1=None):
+        r1 = self.n if r1 is None else r1
+        i, c, pv, _ = self._window(p, r1)
+        first = pv < p
+        i, c = i[first], c[first]
+        key = np.arange(p, r1, dtype=np.int64)
+        inside = (i >= p) & (i < r1)
+        key[i[inside] - p] = np.minimum(i[inside], c[inside])
+        return self._below(np.concatenate([key, c[~inside]]), p, r1)
+
+    def selfpin_col(self, r, p0=0):
+        i, c, _, _ = self._window(p0, r)
+        ok = (i >= p0) & (i < r)
+        return self._at_least(np.minimum(i[ok], c[ok]), p0, r)
+
+    def selfpin_row(self, p, r1=None):
+        r1 = self.n if r1 is None else r1
+        i, c, _, _ = self._window(p, r1)
+        ok = (i >= p) & (i < r1)
+        return self._below(np.maximum(i[ok], c[ok]), p, r1)
+
+    # ---- 1-based forms of the library's counters: one fixed end, all other ends
+    def count_column(self, name, jp, frm=1):
+        """count(j, jp) for j = frm .. jp"""
+        return getattr(self, name + "_col")(jp - 1, frm - 1)
+
+    def count_row(self, name, j, upto=None):
+        """count(j, j') for j' = j .. upto"""
+        return getattr(self, name + "_row")(j - 1, None if upto is None else upto - 1)
+
+    # ---- costs
+    def _cost(self, k, nv, lo, hi, count):
+        mdl = self.mdl
+        dt = np.int64 if _is_int_model(mdl) else np.float64
+        name = type(mdl).__name__
+        ak = getattr(mdl, "alpha_k", None)
+        alpha = mdl.alpha if ak is None or k is None else ak[k - 1]
+        w = self.pos[hi] - self.pos[lo]
+        if name == "AffineSymmetricConnectivityModel":
+            rem = count("dianet") - nv
+            loc = count("net") - rem
+            return _acc(dt, alpha, [(nv, mdl.beta_vertex), (w, mdl.beta_pin), (loc, mdl.beta_local_net), (rem, mdl.beta_remote_net)])
+        if name == "AffineMonotonizedSymmetricConnectivityModel":
+            return _acc(dt, alpha, [(nv, mdl.beta_vertex), (self.op[hi] - self.op[lo], mdl.beta_over_pin), (count("dianet"), mdl.beta_dia_net)])
+        if name == "AffineSymmetricEdgeCutModel":
+            l = count("selfpin")
+            return _acc(dt, alpha, [(nv, mdl.beta_vertex), (l, mdl.beta_self_pin), (w - l, mdl.beta_cut_pin)])
+        raise TypeError(name)
+
+    def row(self, j, k=None, upto=None):
+        """f(j, j', k) for j' = j .. upto (n + 1 by default)"""
+        p, r1 = j - 1, (self.n if upto is None else upto - 1)
+        t = np.arange(p, r1 + 1, dtype=np.int64)
+        return self._cost(k, t - p, p, t, lambda name: getattr(self, name + "_row")(p, r1))
+
+    def column(self, jp, k=None, frm=1):
+        """f(j, j', k) for j = frm .. j'"""
+        r, p0 = jp - 1, frm - 1
+        t = np.arange(p0, r + 1, dtype=np.int64)
+        return self._cost(k, r - t, t, r, lambda name: getattr(self, name + "_col")(r, p0))

@@ -8,6 +8,12 @@ serves by a sweep runs at n = 4 099 only; a pair it serves by the one-wave liter
 gate, or a Float64 bottleneck, under a ConstrainedCost or in pack_stripe) runs every relation at n = 1 031 on one pattern and K: that
 kernel is Theta(n w) steps of one wave.
 
+The symmetric cost family (SymTotal) and the plaid connectivity pair (PlaidTotal for the primary model, PlaidScan for the secondary)
+run the relations of the total objective at both sizes; at n = 70 001 their engines are asserted like the others.  Inside SymTotal's
+gate a symmetric cost is alpha plus a subadditive function of the range, so its total optimum is the closed form [1, n + 1, ...] like
+the unconstrained connectivity total: those cases take part in the identities and in pair_slack == 0, and it is the plaid pair that
+brings optima with many parts in use (asserted).
+
 All model parameters are integers or dyadic rationals and all sums stay far below 2^53: every comparison is `==`.
 
 The relations are written over a solver `lib(A, K, method, mdl, con, Pi)`, so tests/test_meta_model.py runs the same code on the
@@ -38,6 +44,10 @@ ENV_SPREAD = cp.AffineEnvelopeModel(0, 10, 1, -3)
 PCUT = cp.AffinePrimaryEdgeCutModel(0, 2, 1, 7)
 PRIM = cp.AffinePrimaryConnectivityModel(0, 2, 1, 1, 7)
 PINS = cp.AffineWorkModel(0, 0, 1)
+SYM = (cp.AffineSymmetricConnectivityModel(0, 2, 1, 1, 7), cp.AffineMonotonizedSymmetricConnectivityModel(0, 0, 1, 100, 2),
+       cp.AffineSymmetricEdgeCutModel(0, 2, 1, 7))
+PRIM_BAND = cp.AffinePrimaryConnectivityModel(0, 2, 1, 0, 100)      # remote far above local: under banded owners every part follows its rows
+SECOND = cp.AffineSecondaryConnectivityModel(0, 2, 1, 1, 7)
 MONGE = (CONN_I, WORK, CONN_F, HCUT_M)                               # the scalable total-cost engines (and the LWS chunker) take these
 INT = (CONN_I, WORK, HCUT)                                           # the constrained valley search takes Int64 costs only
 ALL = (CONN_I, WORK, HCUT, CONN_F, CONN_D)
@@ -162,7 +172,10 @@ class Lib:
                     "EnvDc": ran("env_dc") and b.get_stat("env_dc_layers") > 0 and not ran("env_sweep"),
                     "EnvValley": ran("env_valley") and b.get_stat("env_valley_layers") > 0 and not ran("env_sweep"),
                     "Lws": ran("chunk_lws"),
-                    "CutScan": b.get_stat("cut_scan_layers") > 0}[engine]
+                    "CutScan": b.get_stat("cut_scan_layers") > 0,
+                    "SymTotal": ran("dp_sym_total") and b.get_stat("sym_total_layers") > 0 and not ran("dp_brute"),
+                    "PlaidTotal": ran("dp_plaid_total") and b.get_stat("plaid_total_layers") > 0 and not ran("dp_brute"),
+                    "PlaidScan": ran("dp_plaid_total") and b.get_stat("plaid_scan_layers") > 0 and not ran("dp_brute")}[engine]
             assert seen, (engine, {s: v["launches"] for s, v in p.items() if v["launches"]})
 
     def __call__(self, A, K, method, mdl, con=None, Pi=None, engine=None):
@@ -525,7 +538,77 @@ def check_plaid(lib, case, P, K, mdl):
 @pytest.mark.parametrize("case,n", [(PLAID_CASES[0], SMALL), (PLAID_CASES[0], SCALE), (PLAID_CASES[1], SMALL)],
                          ids=["plaid_cut-4099", "plaid_cut-70001", "plaid_connectivity-4099"])
 def test_plaid(lib, case, n):
-    """primary connectivity at n = 4 099 only: its DP is the O(n^2) sweep"""
     for name, K in grid(n):
         for mdl in case.models(n):
             check_plaid(lib, case, pat(name, n), K, mdl)
+
+
+# ---------------------------------------------------------------- the symmetric family and the plaid connectivity pair, total objective
+SYM_CASE = Case("sym_total", "total", None, "sum", "SymTotal", SYM, SYM, True)
+PRIMARY_CASE = Case("plaid_connectivity", "total", None, "sum", "PlaidTotal", (PRIM, PRIM_BAND), (PRIM, PRIM_BAND), True)
+SECONDARY_CASE = Case("plaid_secondary", "total", None, "sum", "PlaidScan", (SECOND,), (SECOND,), True)
+
+
+def check_total_relations(lib, case, A, K, mdl, Pi, mirrored, many_parts):
+    """structure; the value on the mirrored problem; the split vector under a factor of 3 and 2^20 and under a shift; pair_slack == 0;
+    alpha = 0: K + 1 parts cost no more (where part K + 1 may stay empty at no cost).  mirrored: (pattern, partition) of the mirror"""
+    spl = lib.base(A, K, case, mdl, None, Pi)
+    assert mm.structure_ok(A, spl) and len(spl) == K + 1, (case.id, K, spl)
+    if many_parts:
+        assert len(set(spl.tolist())) > 3, (case.id, key_of(mdl), K, spl)
+    B, Pj = mirrored
+    got = lib.base(B, K, case, mdl, None, Pj)
+    assert mm.total(B, mdl, got, Pj) == mm.total(A, mdl, spl, Pi), (case.id, key_of(mdl), K, got, spl)
+    for other in (mm.scaled(mdl, 3), mm.scaled(mdl, 1 << 20), mm.shifted(mdl, 12345)):
+        got = lib(A, K, case.method, other, None, Pi)
+        assert np.array_equal(got, spl), (case.id, key_of(other), K, got, spl)
+    slack = mm.pair_slack(A, mdl, spl, Pi=Pi)
+    assert all(x == 0 for x in slack), (case.id, key_of(mdl), K, spl, slack)
+    if mdl.alpha == 0 and case is not SECONDARY_CASE:               # (a secondary part costs its rows and pins even without a column)
+        more = lib(A, K + 1, case.method, mdl, None, Pi)
+        assert mm.structure_ok(A, more) and mm.total(A, mdl, more, Pi) <= mm.total(A, mdl, spl, Pi), (case.id, key_of(mdl), K, more, spl)
+
+
+def check_sym(lib, case, P, K, mdl):
+    mirrored = P._made.setdefault("mirror_both", mm.mirror_both(P.A))
+    check_total_relations(lib, case, P.A, K, mdl, None, (mirrored, None), False)
+
+
+def check_primary(lib, case, P, K, mdl, name):
+    """banded owners; on the mirrored columns the parts run the other way, so part k's rows become part K + 1 - k's"""
+    A = P.A
+    Pi = P._made.setdefault(("rows", K), row_map(A, K, 5 + K))
+    Pj = P._made.setdefault(("rows mirrored", K), cp.MapPartition(K, K + 1 - np.asarray(Pi.asg, dtype=np.int64)))
+    # where every row lies within a few columns of the diagonal a part that follows its rows pays for the strayed rows only
+    check_total_relations(lib, case, A, K, mdl, Pi, (P.get("mirror"), Pj), mdl is PRIM_BAND and name == "band")
+
+
+def check_secondary(lib, case, P, K, mdl, name):
+    """an even SplitPartition of the rows; the mirror turns rows and columns round, and with them the order of the parts"""
+    A = P.A
+    cuts = np.linspace(1, A.m + 1, K + 1).astype(np.int64)
+    Phi = P._made.setdefault(("split", K), cp.SplitPartition(K, cuts))
+    B = P._made.setdefault("mirror reversed", mm.mirror_columns(mm.reverse_rows(A)))
+    Phj = P._made.setdefault(("split mirrored", K), cp.SplitPartition(K, (A.m + 2 - cuts)[::-1].copy()))
+    check_total_relations(lib, case, A, K, mdl, Phi, (B, Phj), name in ("ss", "band"))
+
+
+@pytest.mark.parametrize("n", [SMALL, SCALE])
+@pytest.mark.parametrize("mdl", SYM, ids=["sym_conn", "mono_sym", "edge_cut"])
+def test_symmetric_total(lib, mdl, n):
+    for name, K in grid(n):
+        if name != "edge":                                         # (the edge shape is not square)
+            check_sym(lib, SYM_CASE, pat(name, n), K, mdl)
+
+
+@pytest.mark.parametrize("n", [SMALL, SCALE])
+def test_plaid_connectivity_total(lib, n):
+    for name, K in grid(n):
+        for mdl in PRIMARY_CASE.models(n):
+            check_primary(lib, PRIMARY_CASE, pat(name, n), K, mdl, name)
+
+
+@pytest.mark.parametrize("n", [SMALL, SCALE])
+def test_plaid_secondary_total(lib, n):
+    for name, K in grid(n):
+        check_secondary(lib, SECONDARY_CASE, pat(name, n), K, SECOND, name)

@@ -1,8 +1,21 @@
 """GPU tests of the total objective of the plaid connectivity pair (kinds 8 / 9) on the exact paths of csrc/plaid_total.hip: the
-primary model on the rectangle engine, the secondary model on the prefix-min scan.  Tables bit for bit against the literal DP over
-cost tables built from the definition (tests/plaid_total_model.py) with the engine's limits shrunk; more than one 256-column chunk
-per level row; the defaults as shipped against the device sweep with the launch cap; the scan at the tile edges and past one strip
-of its second level; the routing of everything outside the gates; n = 250 000, which the sweep refuses; and the plaid callers.
+primary model on the rectangle engine, the secondary model on the prefix-min scan.
+
+What referees what, by size:
+
+  n <= 1000              tables bit for bit against the literal DP over cost tables built from the definition
+                         (tests/plaid_total_model.py) with the engine's limits shrunk; more than one 256-column chunk per level row;
+  n = 10 500 / 17 000    the defaults as shipped against the device sweep with the launch cap (the sweep counts by link scans of its
+                         own, so it would notice a miscount of the engine's wavelet counters, not an error both share); the scan at
+                         the tile edges and past one strip of its second level against its numpy restatement;
+  n = 20 011             the public oracle entry (a link scan again; 15 wavelet levels and more than ten 2048-key blocks on the
+                         pattern) against ptm.PrimaryCols on whole rows and columns of the cost table;
+  n = 17 001             the defaults against the DEFINITION: tests/bellman_audit.py audits sampled Bellman cells of the device table
+                         with the columns of ptm.PrimaryCols (entry list only, no dense table, no library code), then the split vector
+                         and its definition-level total; the secondary scan's first layer and last row against Secondary.column;
+  n = 250 000            past the sweep's default reach: the same audit on top of the forced sweep.
+
+Also the routing of everything outside the gates, and the plaid callers.
 
 Every case asserts its route: the stat of the path that ran equals K - 1, its profile slot ticks and the sweep's does not -- or the
 reverse.  The reference tables of a (pattern, partition) are computed once and shared by the cases that need them."""
@@ -12,6 +25,7 @@ import functools
 import numpy as np
 import pytest
 
+import bellman_audit as ba
 import plaid_total_model as ptm
 from util import cp, banded, golden_matrices, suitesparse_shaped
 
@@ -372,7 +386,139 @@ def test_brute_max_n_100_answers_inside_the_gate_and_refuses_outside(hip):
         assert got2 == cp.partition_stripe(T, K, SP(SEC_MODELS[0]), Phi, backend=hip)
 
 
-# ---------------------------------------------------------------- 5. at size
+
+# ---------------------------------------------------------------- 5. the defaults against the definition (tests/bellman_audit.py)
+def holed(n, seed):
+    """suitesparse_shaped(n, 6, seed, m = n + 11) with a run of n // 40 consecutive columns emptied (a model without a vertex and a pin
+    term ties there) and one column of n // 4 further entries"""
+    B = suitesparse_shaped(n, 6, seed, m=n + 11)
+    m = B.m
+    cols = np.repeat(np.arange(n, dtype=np.int64), np.diff(B.colptr))
+    rows = np.asarray(B.rowval, dtype=np.int64) - 1
+    lo, run, hub = n // 3, n // 40, (2 * n) // 3
+    keep = ~((cols >= lo) & (cols < lo + run))
+    pick = np.random.default_rng(seed).choice(m, n // 4, replace=False)
+    key = np.unique(np.concatenate([cols[keep], np.full(pick.size, hub)]) * m + np.concatenate([rows[keep], pick]))
+    c, r = key // m, key % m
+    colptr = np.concatenate([[1], 1 + np.cumsum(np.bincount(c, minlength=n))]).astype(np.int64)
+    return cp.SparseMatrixCSC(m, n, colptr, r + 1)
+
+
+def check_holed(A):
+    n, deg = A.n, np.diff(A.colptr)
+    lo, run = n // 3, n // 40
+    assert A.m == n + 11 and run > 0 and not deg[lo:lo + run].any() and deg[lo - 1] > 0 and deg[lo + run] > 0
+    assert int(deg.max()) >= n // 4 and int(deg.argmax()) == (2 * n) // 3
+
+
+@functools.lru_cache(maxsize=None)
+def sized(n):
+    A = holed(n, 3)
+    check_holed(A)
+    return A
+
+
+def lead_split(m):
+    """a SplitPartition of 7 parts whose first ones are 600 rows each (a few widths of the pattern's band), part 4 empty: the parts of a
+    K = 5 run then have their rows in front of nearly every audited row, and a part that follows its rows beats one part for all"""
+    return cp.SplitPartition(7, np.array([1, 601, 1201, 1801, 1801, 2401, 3001, m + 1], dtype=np.int64))
+
+
+AUDIT_PARTS = {"band": lambda m: band_owner(m, 5, 4), "lead_split": lead_split}
+AUDIT_MODELS = {"i0": MODELS["i"][0], "i1": MODELS["i"][1], "no_vertex": MODELS["i"][5], "alpha_k": MODELS["ak"][0], "float64": MODELS["f"][1]}
+
+
+def audit_primary(hip, A, Pi, mdl, K, seed, nrand):
+    """one run at the options as they stand: route, sampled Bellman cells, split vector, definition-level total -> the audit's counts"""
+    n = A.n
+    with watched(hip) as seen:
+        ptr, cst = tables(hip, A, K, mdl, Pi)
+    assert on_total(seen, K), seen
+    C = ptm.PrimaryCols(A, Pi, mdl)
+    rows = ba.audit_rows(n, DEFAULTS["plaid_total_stair_cols"], seed, nrand)
+    counts = ba.audit(ptr, cst, K, C.row, C.column, rows)
+    assert len(rows) >= 24 and counts["cells"] == len(rows) * (K - 2) + 1, (len(rows), counts)
+    with watched(hip) as seen:
+        got = cp.partition_stripe(A, K, SP(mdl), Pi, backend=hip)
+    assert on_total(seen, K), seen
+    spl = got.spl.tolist()
+    assert spl == unravel(ptr, K)
+    with np.errstate(over="ignore"):
+        total = sum(C.row(spl[k], k + 1, upto=spl[k + 1])[-1] for k in range(K))
+    assert total == cst[n, K - 1], (total, cst[n, K - 1])
+    return counts
+
+
+@pytest.mark.parametrize("part", list(AUDIT_PARTS))
+def test_audit_at_the_default_limits(hip, part):
+    """n = 17 001 (the depth-1 rectangle takes the count-and-scan branch past LWS_LDS_ROWS), K = 5, no option set: sampled Bellman cells
+    against the definition at the rows where the engine changes its path and at 32 random rows.  (The chunker order of this kind is
+    refused, test_routing, so there is no third closing check.)  Under lead_split the model i0 has an interior argmin in more than
+    half of its audited cells (164 of 283; a DP in numpy over PrimaryCols columns alone gives the same share); under the five even
+    bands no model does, because a fifth of the pattern's entries are spread over all rows and one part for everything wins.  The
+    model without vertex and pin terms ties."""
+    A, K = sized(17_001), 5
+    assert A.n > DEFAULTS["plaid_total_min_n"]
+    Pi = AUDIT_PARTS[part](A.m)
+    for name, mdl in AUDIT_MODELS.items():
+        counts = audit_primary(hip, A, Pi, mdl, K, 17, 32)
+        print(part, name, "audited", counts)
+        if name == "no_vertex":
+            assert counts["tied"] >= 1, counts
+        if name == "i0" and part == "lead_split":
+            assert 2 * counts["interior"] >= counts["cells"], counts
+
+
+def test_audit_with_layers_whose_part_owns_no_row(hip):
+    """K = Pi.K + 2 = 7: the layers 6 and 7 belong to parts that own no row (every net remote)"""
+    A = sized(17_001)
+    Pi = band_owner(A.m, 5, 4)
+    for name in ("i1", "alpha_k"):
+        counts = audit_primary(hip, A, Pi, AUDIT_MODELS[name], Pi.K + 2, 18, 32)
+        print(name, "audited", counts)
+        assert counts["interior"] >= 1, counts
+
+
+def test_secondary_first_layer_and_last_row_against_the_definition(hip):
+    """the scan's first layer (every cell) and its last row, with f(j, j', k) straight from the definition (Secondary.column)"""
+    T = cp.adjointpattern(sized(17_001), backend=hip)
+    K = 5
+    Phi = sec_split(T.m, K, 23)
+    S = ptm.Secondary(T, Phi)
+    for mdl in SEC_MODELS:
+        with watched(hip) as seen:
+            ptr, cst = tables(hip, T, K, mdl, Phi)
+        assert on_scan(seen, K), seen
+        counts = ba.audit(ptr, cst, K, lambda j, k: S.first(mdl), lambda jp, k: S.column(mdl, jp, k), [])
+        assert counts["cells"] == 1
+
+
+@pytest.mark.parametrize("part", ["band7", "split"])
+def test_primary_oracle_against_the_definition_at_20011(hip, part):
+    """the cells the sweep and the rectangle engine both evaluate: cp.oracle_stripe on 64 whole columns and 16 whole rows of the cost
+    table (the fixed ends: 1, 2, n, n + 1, columns where colptr crosses a multiple of 2048, random) against ptm.PrimaryCols"""
+    A = sized(20_011)
+    n = A.n
+    assert (n + 2).bit_length() == 15 and A.nnz + n > 10 * 2048               # H = cllog2(n + 2) = 15 wavelet levels
+    Pi = {"band7": band_owner(A.m, 7, 5), "split": split_part(A.m)}[part]
+    rng = np.random.default_rng(2011)
+    ends, starts = ba.fixed_ends(A, rng, 64), ba.fixed_ends(A, rng, 16)
+    j, jp = ba.line_pairs(n, ends, starts)
+    assert j.size >= 700_000
+    cases = [(MODELS["i"][1], 2), (MODELS["ak"][0], 3), (MODELS["f"][1], Pi.K), (MODELS["i"][0], 4)]
+    for mdl, k in cases:
+        C = ptm.PrimaryCols(A, Pi, mdl)
+        want = np.concatenate([C.column(int(e), k) for e in ends] + [C.row(int(s), k) for s in starts])
+        got = cp.oracle_stripe(cp.NoHint(), mdl, A, Pi, backend=hip)(j, jp, k)
+        bad = np.nonzero(got != want)[0]
+        assert got.dtype == want.dtype and bad.size == 0, (part, mdl._params(), k, j[bad[:5]], jp[bad[:5]], got[bad[:5]], want[bad[:5]])
+    # a part number past Pi.K is a violated precondition of the oracle entry; the DP evaluates such layers itself
+    # (test_audit_with_layers_whose_part_owns_no_row)
+    with pytest.raises(AssertionError, match="out of range"):
+        cp.oracle_stripe(cp.NoHint(), MODELS["i"][1], A, Pi, backend=hip)(j[:4], jp[:4], Pi.K + 1)
+
+
+# ---------------------------------------------------------------- 6. at size
 @pytest.fixture(scope="module")
 def large():
     A = banded(250_000, 5, 0.9, 1)
@@ -396,6 +542,12 @@ def test_primary_past_brute_max_n(hip, large):
             old = tables(hip, A, K, mdl, Pi)
         assert on_sweep(swept), swept
     assert same_tables(K, (ptr, cst), old) and spl == unravel(old[0], K)
+    # optimality, from the definition: sampled Bellman cells of the full layer and the last row
+    C = ptm.PrimaryCols(A, Pi, mdl)
+    rows = ba.audit_rows(n, DEFAULTS["plaid_total_stair_cols"], 250, 8)
+    counts = ba.audit(ptr, cst, K, C.row, C.column, rows)
+    print("audited", counts)
+    assert len(rows) >= 24 and counts["cells"] == len(rows) * (K - 2) + 1 and counts["interior"] >= 1, (len(rows), counts)
 
 
 def test_secondary_past_brute_max_n(hip, large):
@@ -417,7 +569,7 @@ def test_secondary_past_brute_max_n(hip, large):
     assert same_tables(K, (ptr, cst), old) and spl == unravel(old[0], K)
 
 
-# ---------------------------------------------------------------- 6. callers
+# ---------------------------------------------------------------- 7. callers
 def test_alternating_partitioner_on_the_new_routes(hip):
     n, K = 12000, 4
     A = suitesparse_shaped(n, 6, 11)

@@ -1,16 +1,32 @@
-"""GPU tests of the total objective of the symmetric cost family on the divide and conquer of csrc/sym_total.hip (path SymTotal):
-tables bit for bit against the literal DP of tests/sym_model.py with the limits shrunk so that small patterns run levels, stair scans
-and whole-scanned rectangles, in both launch forms ("sym_total_batch" 1 and 0); more than one 256-column chunk per level row; the
-defaults as shipped past the LDS level limit, against the device sweep, with the launch cap of the batched form; the routing of
-everything outside the gate; n = 250 000, which the sweep refuses; and the plaid callers.
+"""GPU tests of the total objective of the symmetric cost family on the divide and conquer of csrc/sym_total.hip (path SymTotal).
 
-The reference tables of a (pattern, model) are computed once and shared by every case that needs them."""
+What referees what, by size:
+
+  n <= 1000     tables bit for bit against the literal DP over the dense count tables of tests/sym_model.py, with the limits shrunk so
+                that small patterns run levels, stair scans and whole-scanned rectangles, in both launch forms ("sym_total_batch" 1
+                and 0); more than one 256-column chunk per level row;
+  n = 17 000    the defaults as shipped past the LDS level limit against the device sweep (which counts with the same device
+                structures), with the launch cap of the batched form;
+  n = 17 001    the defaults again, now against the DEFINITION: tests/bellman_audit.py audits sampled Bellman cells of the device table
+                with the columns of sm.Sym (entry list only, no dense table, no library code), then the split vector, its
+                definition-level total and the chunker order;
+  n = 250 000   past the sweep's reach: the same audit on top of the older inequalities.
+
+Inside the gate of SymTotal every cost is alpha_k plus a subadditive function g of the column range (net and dianet are subadditive,
+selfpin is superadditive with a non-positive weight, everything else is additive), so appending an empty part never costs more than
+any other last part: cst[r, k] = alpha_1 + .. + alpha_k + g(0, r), the candidates p = 0 and p = r both attain it and the largest
+minimiser is p = r.  No in-gate model of this family has an interior argmin; the audits therefore assert the whole closed form (every
+cell of every layer, from Sym.row) next to the sampled cells, and that every audited cell with r >= 1 is tied.
+
+Also: the routing of everything outside the gate, and the plaid callers.  The reference tables of a (pattern, model) are computed once
+and shared by every case that needs them."""
 import contextlib
 import functools
 
 import numpy as np
 import pytest
 
+import bellman_audit as ba
 import sym_model as sm
 import sym_total_model as stm
 from test_gpu_symmetric import pattern, tables, MODELS_I, VARIANTS
@@ -186,6 +202,99 @@ def test_full_layer_launch_cap(hip):
     assert each["sym"] >= three["sym"], (each, three)                       # the per-rectangle form never launches less
 
 
+
+# ---------------------------------------------------------------- the defaults against the definition (tests/bellman_audit.py)
+def holed(n, seed):
+    """symmetrised(n, 6, seed) with the columns and rows of n // 40 consecutive indices emptied (a model without a vertex term ties
+    there) and one column and row of n // 4 further entries"""
+    B = symmetrised(n, 6, seed)
+    cols = np.repeat(np.arange(n, dtype=np.int64), np.diff(B.colptr))
+    rows = np.asarray(B.rowval, dtype=np.int64) - 1
+    lo, run, hub = n // 3, n // 40, (2 * n) // 3
+    keep = ~(((cols >= lo) & (cols < lo + run)) | ((rows >= lo) & (rows < lo + run)))
+    pick = np.random.default_rng(seed).choice(np.setdiff1d(np.arange(n), np.arange(lo, lo + run)), n // 4, replace=False)
+    c = np.concatenate([cols[keep], np.full(pick.size, hub), pick])
+    r = np.concatenate([rows[keep], pick, np.full(pick.size, hub)])
+    key = np.unique(c * n + r)
+    c, r = key // n, key % n
+    colptr = np.concatenate([[1], 1 + np.cumsum(np.bincount(c, minlength=n))]).astype(np.int64)
+    return cp.SparseMatrixCSC(n, n, colptr, r + 1)
+
+
+def check_holed(A):
+    """the properties the audits rely on: symmetric, an empty run of n // 40 columns and rows, one column of at least n // 4 entries"""
+    n = A.n
+    deg = np.diff(A.colptr)
+    cols = np.repeat(np.arange(n, dtype=np.int64), deg)
+    rows = np.asarray(A.rowval, dtype=np.int64) - 1
+    lo, run = n // 3, n // 40
+    assert np.array_equal(np.sort(cols * n + rows), np.sort(rows * n + cols))
+    assert run > 0 and not deg[lo:lo + run].any() and not ((rows >= lo) & (rows < lo + run)).any()
+    assert deg[lo - 1] > 0 and deg[lo + run] > 0 and int(deg.max()) >= n // 4 and int(deg.argmax()) == (2 * n) // 3
+
+
+@functools.lru_cache(maxsize=None)
+def audit_pattern():
+    A = holed(17_001, 3)
+    check_holed(A)
+    return A
+
+
+def alpha_sums(mdl, K, dt):
+    ak = mdl.alpha_k
+    return np.cumsum(np.array([mdl.alpha if ak is None else ak[k] for k in range(K)], dtype=dt))
+
+
+def audit_tables(A, mdl, K, ptr, cst, seed, nrand):
+    """the sampled Bellman cells, and the closed form of the whole table (module docstring) -> the audit's counts"""
+    n = A.n
+    S = sm.Sym(A, mdl)
+    rows = ba.audit_rows(n, DEFAULTS["sym_total_stair_cols"], seed, nrand)
+    counts = ba.audit(ptr, cst, K, S.row, S.column if mdl.alpha_k is not None else ba.same_for_all_k(S.column), rows)
+    assert len(rows) >= 24 and counts["cells"] == len(rows) * (K - 2) + 1, (len(rows), counts)
+    # every audited cell with r >= 1 has the two minimisers p = 0 and p = r, and none is interior
+    assert counts["tied"] == counts["cells"] - (K - 2) * int(rows[0] == 0) and counts["interior"] == 0, counts
+    sums = alpha_sums(mdl, K, cst.dtype)
+    for k in range(2, K):
+        assert np.array_equal(cst[:, k - 1], S.row(1, k) + sums[k - 2]), k
+        assert np.array_equal(ptr[:, k - 1], np.arange(1, n + 2)), k
+    assert cst[n, K - 1] == S.row(1, K)[n] + sums[K - 2] and ptr[n, K - 1] == n + 1
+    return counts, S
+
+
+AUDITED = {"sym_conn": (ONE_PER_KIND[0], 1), "mono_sym": (ONE_PER_KIND[1], 1), "edge_cut": (ONE_PER_KIND[2], 1), "alpha_k": (MODELS_AK[1], 1),
+           "float64": (MODELS_IN_F[0], 1), "ties": (SEC(0, 0, 0, 1), 1), "per_rectangle": (ONE_PER_KIND[0], 0)}
+
+
+@pytest.mark.parametrize("case", list(AUDITED))
+def test_audit_at_the_default_limits(hip, case):
+    """n = 17 001 (the depth-1 rectangle takes the count-and-scan branch past LWS_LDS_ROWS), K = 5, no option set but the launch form:
+    sampled Bellman cells against the definition at the rows where the engine changes its path and at 32 random rows; the split
+    vector is the table's, its total summed from definition-level part costs is cst[n, K - 1]; the chunker order, which fills the same
+    tables for a model without alpha_k, returns the same split."""
+    (mdl, batch), K = AUDITED[case], 5
+    A = audit_pattern()
+    n = A.n
+    assert n > DEFAULTS["sym_total_min_n"]
+    with options(hip, sym_total_batch=batch):
+        with watched(hip) as seen:
+            rc, ptr, cst = hip.dynamic_tables(A, K, SUM, mdl.marshal(), None)
+        assert rc == 0, hip.last_error()
+        assert seen["layers"] == K - 1 and seen["sym"] > 0 and seen["brute"] == 0, seen
+        counts, S = audit_tables(A, mdl, K, ptr, cst, 17, 32)
+        print(case, "audited", counts)
+        orders = (cp.DynamicTotalSplitter,) if mdl.alpha_k is not None else (cp.DynamicTotalSplitter, cp.DynamicTotalChunker)
+        for meth in orders:
+            with watched(hip) as seen:
+                got = cp.partition_stripe(A, K, meth(mdl), backend=hip)
+            assert seen["layers"] == K - 1 and seen["sym"] > 0 and seen["brute"] == 0, (seen, meth.__name__)
+            spl = got.spl.tolist()
+            assert spl == unravel(ptr, K), meth.__name__
+    with np.errstate(over="ignore"):
+        total = sum(S.row(spl[k], k + 1, upto=spl[k + 1])[-1] for k in range(K))
+    assert total == cst[n, K - 1], (total, cst[n, K - 1])
+
+
 def test_routing(hip):
     n, K = 2000, 4
     A = symmetrised(n, 6, 5)
@@ -265,6 +374,10 @@ def test_past_brute_max_n(hip, large, mdl):
         assert value <= cp.total_value(A, cp.partition_stripe(A, K, cp.DynamicBottleneckSplitter(mdl), backend=hip), mdl, backend=hip)
     rc4, _, cst4 = hip.dynamic_tables(A, 4, SUM, mdl.marshal(), None)       # alpha = 0: more parts never cost more
     assert rc4 == 0 and value <= cst4[n, 3]
+    # optimality, from the definition: sampled Bellman cells of the six full layers and the last row, and the closed form of every cell
+    counts, _ = audit_tables(A, mdl, K, ptr, cst, 250, 8)
+    print("audited", counts)
+    assert spl == unravel(ptr, K)
 
 
 def test_through_the_public_callers(hip):

@@ -6,12 +6,18 @@ Shapes: n in 63, 64, 65, 255, 256, 257, all just past a change of the wavelet le
 where the top key n + 1 is 2^H - 1, to n = 2^H - 1: 62 -> 63, 254 -> 255; tests/test_gpu_count_edges.py has both sides of that
 edge); diagonals full, empty and partial; empty
 columns; one dense row; and one pattern with nnz + n > 2 * 16384 so the lazy stream crosses chunk boundaries and restarts inside a
-chunk after a split."""
+chunk after a split.
+
+Those sizes keep the dense tables of sym_model.py in reach.  At n = 20 011 (15 wavelet levels, more than ten 2048-key blocks of the
+counter builds) the two counters and the oracle of every kind are compared with sm.Sym instead: whole rows and columns of the count
+and cost tables from the entry list, about 7.5 * 10^5 pairs per counter.  The DP engines count with these structures on both sides
+of their own comparisons at size, so this is where a miscount that appears only at size would show."""
 import functools
 
 import numpy as np
 import pytest
 
+import bellman_audit as ba
 import sym_model as sm
 from test_gpu_plaid_lazy import deg15_17, deg16
 from util import cp, sprand, golden_matrices, suitesparse_shaped
@@ -101,6 +107,53 @@ def test_counters_on_reference_matrices_and_reproducible(hip):
         assert np.array_equal(d1, T.get("dianet")[j - 1, jp - 1]) and np.array_equal(s1, T.get("selfpin")[j - 1, jp - 1])
         hip.reset_cache(A)
         assert np.array_equal(cp.dianetcount(A, backend=hip)(j, jp), d1) and np.array_equal(cp.selfpincount(A, backend=hip)(j, jp), s1)
+
+
+@functools.lru_cache(maxsize=None)
+def at_size():
+    """the pattern of the audits of test_gpu_sym_total.py at n = 20 011, 64 fixed ends j' and 16 fixed starts j (1, 2, n, n + 1, columns
+    where colptr crosses a multiple of 2048, random) and the (j, j') pairs of their whole columns and rows"""
+    from test_gpu_sym_total import holed, check_holed
+    A = holed(20_011, 3)
+    check_holed(A)
+    n = A.n
+    assert (n + 2).bit_length() == 15 and A.nnz + n > 10 * 2048               # H = cllog2(n + 2) = 15 wavelet levels
+    rng = np.random.default_rng(2011)
+    ends, starts = ba.fixed_ends(A, rng, 64), ba.fixed_ends(A, rng, 16)
+    j, jp = ba.line_pairs(n, ends, starts)
+    assert j.size >= 700_000 and {1, 2, n, n + 1} <= set(ends.tolist())
+    return A, ends, starts, j, jp
+
+
+def lines(ends, starts, column, row):
+    return np.concatenate([column(int(e)) for e in ends] + [row(int(s)) for s in starts])
+
+
+def test_counters_match_definitions_at_20011(hip):
+    A, ends, starts, j, jp = at_size()
+    S = sm.Sym(A)
+    for name, count in (("dianet", cp.dianetcount), ("selfpin", cp.selfpincount)):
+        want = lines(ends, starts, lambda e: S.count_column(name, e), lambda b: S.count_row(name, b))
+        got = count(A, backend=hip)(j, jp)
+        bad = np.nonzero(got != want)[0]
+        assert bad.size == 0, (name, j[bad[:5]], jp[bad[:5]], got[bad[:5]], want[bad[:5]])
+
+
+AT_SIZE_MODELS = [(MODELS_I[0], None), (MODELS_I[1], None), (MODELS_I[2], None), (cp.AffineSymmetricConnectivityModel(3.0, 2.0, 1.0, 5.0, 40.0), None),
+                  (cp.AffineMonotonizedSymmetricConnectivityModel(0, 1, 2, 3, 1, alpha_k=[5, 7, 11]), 1),
+                  (cp.AffineMonotonizedSymmetricConnectivityModel(0, 1, 2, 3, 1, alpha_k=[5, 7, 11]), 3)]
+
+
+@pytest.mark.parametrize("which", range(len(AT_SIZE_MODELS)), ids=["sym_conn", "mono_sym", "edge_cut", "float64", "alpha_k_1", "alpha_k_3"])
+def test_oracle_eval_matches_formulas_at_20011(hip, which):
+    A, ends, starts, j, jp = at_size()
+    mdl, k = AT_SIZE_MODELS[which]
+    S = sm.Sym(A, mdl)
+    want = lines(ends, starts, lambda e: S.column(e, k), lambda b: S.row(b, k))
+    ocl = cp.oracle_stripe(cp.NoHint(), mdl, A, backend=hip)
+    got = ocl(j, jp) if k is None else ocl(j, jp, k)
+    bad = np.nonzero(got != want)[0]
+    assert got.dtype == want.dtype and bad.size == 0, (mdl._params(), k, j[bad[:5]], jp[bad[:5]], got[bad[:5]], want[bad[:5]])
 
 
 def test_non_square_is_a_violated_precondition(hip):

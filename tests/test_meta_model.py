@@ -8,6 +8,8 @@ import pytest
 import brute
 import envelope_model as em
 import meta_model as mm
+import plaid_total_model as ptm
+import sym_model as sm
 import test_gpu_metamorphic as gm
 from util import cp, sprand, suitesparse_shaped, banded
 
@@ -58,6 +60,61 @@ def test_envelope_and_plaid_sweeps_equal_the_definitions():
         E = em.Env(A, gm.ENV)
         assert np.array_equal(np.triu(E.table(1)), np.triu(np.array([[mm.part_cost(A, gm.ENV, p + 1, r + 1) if p <= r else 0 for r in range(n + 1)]
                                                                      for p in range(n + 1)])))
+
+
+def test_symmetric_kinds_equal_the_dense_tables():
+    """part_cost (set operations) and both sweeps against sym_model's dense tables; mirror_both keeps every count"""
+    rng = np.random.default_rng(11)
+    models = gm.SYM + (cp.AffineSymmetricConnectivityModel(1.0, 0.5, 2.0, 3.0, 7.0), cp.AffineMonotonizedSymmetricConnectivityModel(3, 1, 2, 5, 0))
+    for n, p in ((1, 0.5), (7, 0.4), (16, 0.0), (23, 0.2), (33, 0.1)):
+        A = sprand(n, n, p, rng)
+        T, ix = sm.Tables(A), mm.index(A)
+        for p0 in range(n + 1):
+            for r in range(p0, n + 1):
+                assert mm.dianets(A, p0 + 1, r + 1) == T.get("dianet")[p0, r] and mm.selfpins(A, p0 + 1, r + 1) == T.get("selfpin")[p0, r]
+        B = mm.mirror_both(A)
+        for name in ("dianet", "selfpin", "net"):
+            assert np.array_equal(sm.Tables(B).get(name), sm.Tables(A).get(name)[::-1, ::-1].T), name
+        for mdl in models:
+            F = sm.cost_table(T, mdl)
+            for p0 in range(n + 1):
+                for r in range(p0, n + 1):
+                    assert np.array_equal(mm.left_costs(ix, mdl, p0, r), F[p0, p0:r + 1]), (A, p0, r, mdl._params())
+                    assert np.array_equal(mm.right_costs(ix, mdl, p0, r), F[p0:r + 1, r]), (A, p0, r, mdl._params())
+                    if (p0 + r) % 3 == 0:
+                        assert mm.part_cost(A, mdl, p0 + 1, r + 1) == F[p0, r], (A, p0, r, mdl._params())
+
+
+def test_plaid_pair_equals_the_dense_tables():
+    """the secondary model and the primary model under a SplitPartition (with an empty part) and a MapPartition"""
+    rng = np.random.default_rng(12)
+    for m, n, p in ((5, 7, 0.4), (12, 23, 0.2), (30, 19, 0.1), (6, 16, 0.0)):
+        A = sprand(m, n, p, rng)
+        ix = mm.index(A)
+        cut = np.sort(rng.integers(1, m + 2, 2))
+        Phi = cp.SplitPartition(4, np.array([1, cut[0], cut[0], cut[1], m + 1], dtype=np.int64))
+        Pi = cp.MapPartition(4, rng.integers(1, 5, m))
+        S = ptm.Secondary(A, Phi)
+        for P in (Phi, Pi):
+            T = ptm.Primary(A, P)
+            for mdl in (gm.PRIM, gm.PRIM_BAND):
+                for k in (1, 2, 4):
+                    F = T.table(mdl, k)
+                    for p0 in range(n + 1):
+                        for r in range(p0, n + 1):
+                            assert np.array_equal(mm.left_costs(ix, mdl, p0, r, k, P), F[p0, p0:r + 1]), (A, p0, r, k)
+                            assert np.array_equal(mm.right_costs(ix, mdl, p0, r, k, P), F[p0:r + 1, r]), (A, p0, r, k)
+                            if (p0 + r) % 3 == 0:
+                                assert mm.part_cost(A, mdl, p0 + 1, r + 1, k, P) == F[p0, r]
+        for mdl in (gm.SECOND, cp.AffineSecondaryConnectivityModel(1.0, 2.0, 0.5, 3.0, 1.0)):
+            for k in (1, 2, 3, 4):
+                F = S.table(mdl, k)
+                for p0 in range(n + 1):
+                    for r in range(p0, n + 1):
+                        assert np.array_equal(mm.left_costs(ix, mdl, p0, r, k, Phi), F[p0, p0:r + 1]), (A, p0, r, k)
+                        assert np.array_equal(mm.right_costs(ix, mdl, p0, r, k, Phi), F[p0:r + 1, r]), (A, p0, r, k)
+                        if (p0 + r) % 3 == 0:
+                            assert mm.part_cost(A, mdl, p0 + 1, r + 1, k, Phi) == F[p0, r]
 
 
 def test_transforms():
@@ -183,6 +240,14 @@ def test_reference_optimality(ref, pats):
 def test_reference_plaid_connectivity(ref, pats):
     for P, K in pats:
         gm.check_plaid(ref, gm.PLAID_CASES[1], P, K, gm.PRIM)
+
+
+def test_reference_plaid_pair_total(ref):
+    """the relations of the primary and the secondary total on the reference, with their optima of many parts"""
+    for name, P, K in (("ss", gm.Pat(suitesparse_shaped(1500, 8, 4), 1), 7), ("band", gm.Pat(banded(1200, 6, 0.5, 5), 2), 16)):
+        for mdl in (gm.PRIM, gm.PRIM_BAND):
+            gm.check_primary(ref, gm.PRIMARY_CASE, P, K, mdl, name)
+        gm.check_secondary(ref, gm.SECONDARY_CASE, P, K, gm.SECOND, name)
 
 
 class EnvLiteral:

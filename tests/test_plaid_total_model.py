@@ -111,3 +111,46 @@ def test_secondary_tables_come_from_the_definition():
     # part 2 and the first two columns: neither holds row 3 -> 0 local, 1 remote; the last two: column 3 does -> 1 local, 0 remote
     assert S.table(SEC(1, 10, 100, 1000, 10000), 2)[0, 2] == 1 + 10 + 100 + 0 + 10000
     assert S.table(SEC(1, 10, 100, 1000, 10000), 2)[1, 3] == 1 + 10 + 100 + 1000 + 0
+
+
+# ---------------------------------------------------------------- PrimaryCols: rows and columns against the dense tables
+@pytest.mark.parametrize("part", ["split", "map"])
+@pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 257])
+def test_primary_rows_and_columns_equal_the_dense_tables(n, part):
+    """every row, every column and windows with frm > 1 / upto < n + 1, for all in-gate models of the GPU file, the alpha_k model, a
+    Float64 twin and a part number past Pi.K"""
+    import test_gpu_plaid_total as g
+    T = g.counts(n, part)
+    A, Pi = T.A, T.Pi
+    rng = np.random.default_rng(n)
+    windows = [(int(a), int(b)) for a, b in np.sort(rng.integers(1, n + 2, (6, 2)), axis=1)] + [(1, 1), (n + 1, n + 1), (2, n + 1), (1, n)]
+    cases = [(m, k) for m in g.MODELS["i"] for k in (1, 5)] + [(g.MODELS["i"][1], Pi.K + 1), (g.MODELS["f"][1], 2)]
+    cases += [(g.MODELS["ak"][0], k) for k in (1, 3, 7)]
+    C = ptm.PrimaryCols(A, Pi)
+    for k in (1, 4, 5, Pi.K + 1):                                               # the counts themselves (5 / 4: the empty part of split / none)
+        loc = T.local[k] if k in T.local else np.zeros_like(T.nets)
+        for j in range(1, n + 2):
+            nets, l = C.counts_row(j - 1, k)
+            assert np.array_equal(nets, T.nets[j - 1, j - 1:]) and np.array_equal(l, loc[j - 1, j - 1:]), (k, j)
+            nets, l = C.counts_col(j - 1, k)
+            assert np.array_equal(nets, T.nets[:j, j - 1]) and np.array_equal(l, loc[:j, j - 1]), (k, j)
+    for mdl, k in cases:
+        F, C = T.table(mdl, k), ptm.PrimaryCols(A, Pi, mdl)
+        for j in range(1, n + 2):
+            row, col = C.row(j, k), C.column(j, k)
+            assert row.dtype == F.dtype and np.array_equal(row, F[j - 1, j - 1:]), (mdl._params(), k, j)
+            assert col.dtype == F.dtype and np.array_equal(col, F[:j, j - 1]), (mdl._params(), k, j)
+        for a, b in windows:
+            assert np.array_equal(C.row(a, k, upto=b), F[a - 1, a - 1:b]) and np.array_equal(C.column(b, k, frm=a), F[a - 1:b, b - 1]), (a, b)
+
+
+def test_secondary_columns_equal_the_table():
+    rng = np.random.default_rng(910)
+    A = _pattern(45, 37, 0.15, rng)
+    S = ptm.Secondary(A, cp.SplitPartition(4, np.array([1, 9, 9, 30, 46], dtype=np.int64)))
+    for mdl in (SEC(3, 2, 1, 1, 7), SEC(0.0, 1.0, 1.0, 5.0, 2.0, alpha_k=[5.0, 1.0, 9.0, 2.0])):
+        for k in (1, 2, 4):
+            F = S.table(mdl, k)
+            for jp in range(1, A.n + 2):
+                col = S.column(mdl, jp, k)
+                assert col.dtype == F.dtype and np.array_equal(col, F[:jp, jp - 1]), (k, jp)

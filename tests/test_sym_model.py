@@ -1,5 +1,6 @@
 """Self-checks of tests/sym_model.py (the pure-Python statement of the symmetric cost family) and of the host mirror's three
-model classes.  No GPU."""
+model classes, and of Sym, its rows and columns of the count and cost tables that need no dense table (the referee of the GPU
+tests past the literal tables' reach): every row, every column and windows of both against the dense tables.  No GPU."""
 import numpy as np
 import pytest
 
@@ -111,3 +112,42 @@ def test_lazy_and_bisect_within_eps_of_the_dp_optimum(eps):
                     _check_spl(spl, A.n, K)
                     got = sm.objective(T, mdl, spl, "max")
                     assert opt <= got <= (1 + eps) * opt, (K, got, opt)
+
+
+# ---------------------------------------------------------------- Sym: rows and columns against the dense tables
+def _sym_models():
+    import test_gpu_sym_total as g
+    return [(m, None) for m in g.MODELS_IN] + [(g.MODELS_IN_F[0], None)] + [(m, k) for m in g.MODELS_AK for k in (1, 3)]
+
+
+@pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 257])
+def test_sym_rows_and_columns_equal_the_dense_tables(n):
+    from test_gpu_symmetric import pattern, tables, VARIANTS
+    rng = np.random.default_rng(n)
+    for v in VARIANTS:
+        A, T = pattern(n, v), tables(n, v)
+        S = sm.Sym(A)
+        windows = [(int(a), int(b)) for a, b in np.sort(rng.integers(1, n + 2, (6, 2)), axis=1)] + [(1, 1), (n + 1, n + 1), (2, n + 1), (1, n)]
+        for name in ("dianet", "selfpin", "net"):
+            D = T.get(name)
+            for j in range(1, n + 2):
+                assert np.array_equal(S.count_row(name, j), D[j - 1, j - 1:]), (v, name, j)
+                assert np.array_equal(S.count_column(name, j), D[:j, j - 1]), (v, name, j)
+            for a, b in windows:                                                # frm > 1 / upto < n + 1
+                assert np.array_equal(S.count_row(name, a, upto=b), D[a - 1, a - 1:b]), (v, name, a, b)
+                assert np.array_equal(S.count_column(name, b, frm=a), D[a - 1:b, b - 1]), (v, name, a, b)
+        for mdl, k in _sym_models():
+            F, S = sm.cost_table(T, mdl, k), sm.Sym(A, mdl)
+            for j in range(1, n + 2):
+                row, col = S.row(j, k), S.column(j, k)
+                assert row.dtype == F.dtype and np.array_equal(row, F[j - 1, j - 1:]), (v, mdl._params(), k, j)
+                assert col.dtype == F.dtype and np.array_equal(col, F[:j, j - 1]), (v, mdl._params(), k, j)
+            for a, b in windows:
+                assert np.array_equal(S.row(a, k, upto=b), F[a - 1, a - 1:b]) and np.array_equal(S.column(b, k, frm=a), F[a - 1:b, b - 1]), (v, a, b)
+
+
+def test_sym_wraps_like_the_dense_table():
+    from test_gpu_symmetric import pattern, tables
+    A, T = pattern(65, "partial"), tables(65, "partial")
+    mdl = cp.AffineSymmetricConnectivityModel(2**62, 2**61, 3, -2**60, 2**59)
+    assert np.array_equal(sm.Sym(A, mdl).column(66), sm.cost_table(T, mdl)[:66, 65])
